@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — spectral points / s of the STARDIS hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S-c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S-c2] [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts the N ranks itself (fresh child processes
 through torch.distributed.run, before anything in this process touches the GPU) and relays rank 0's JSON line; under
@@ -12,11 +12,20 @@ One "step" = one full pass of the hot path over inputs already resident in HBM: 
 over N_theta angles -> F_nu (N_d, N_nu).  Metric: spectral points per second = N_nu * N_depth * steps / time
 (BASELINE.json).  At N = 1 `value` is measured on BASELINE configs[1] (S-c2, the 1-GPU config).  At N > 1 it is BASELINE
 configs[2] — S-c3, the fixed 3000-10000 A grid (120 398 frequencies, 1.5e5 lines) split N ways in shards of equal estimated
-work, `scaling: "strong"`; every step ends with ONE all-gather of the emergent flux (RCCL); `n1_same_workload` carries the
-one-GPU step of the same workload measured in the same run, `collective` what torch.distributed actually ran, `per_rank` every
-rank's shard and kernel times.  (--workload / --scaling override both, e.g. --workload S-c2 --scaling weak.)
+work, `scaling: "strong"`; every step ends with ONE all-gather of the emergent flux (RCCL); `collective` says what
+torch.distributed actually ran.  (--workload / --scaling override both, e.g. --workload S-c2 --scaling weak.)
 
-Besides `value` the JSON line carries
+A plain run sets up, warms up, times the K steps and prints `value` and `ms_per_step` (milliseconds per timed step) with the
+workload's description.  --dump-outputs DIR then also writes what the last timed step handed its caller as DIR/<name>.npy
+(float64; the inputs are seeded, so two builds can be compared array for array): F_nu.npy and total_alphas.npy (N_d, N_nu) on
+one GPU, the gathered emergent flux spectrum.npy (N_nu,) on several.
+
+With --full the JSON line also carries what takes runs of its own:
+  ms_per_step_cold      the K steps timed right after the W warm-up steps (runs of fewer than 200 steps)
+  throughput_two_syntheses_in_flight   one GPU: two syntheses on two streams, stepped alternately
+  per_rank              several GPUs: every rank's shard and kernel times
+  n1_same_workload      several GPUs: the one-GPU step of the same workload measured in the same run (speedup_vs_n1,
+                        gathered_spectrum_equals_n1_bit_for_bit)
   roofline              HBM roofline of the dominant kernel (live HIP-event durations), traffic from profiles/
   roofline_fp64_valu    the bound that really limits the path: wave-level fp64 instructions per second against the spec issue rate
   cpu_baseline          the oracle (reference algorithm restated in C) on this box's host cores: one_core / best / all_cores
@@ -692,6 +701,18 @@ class Runner:
         torch.cuda.synchronize()
         return self.last._assemble().cpu().numpy() if self.world > 1 else None
 
+    def last_outputs(self):
+        """what the last step handed its caller, as host arrays: one GPU F_nu and total_alphas (N_d, N_nu) of the lane that ran it,
+        several GPUs the gathered emergent flux (N_nu,)"""
+        if self.world > 1:
+            return {"spectrum": self.last_spectrum()}
+        import torch
+
+        self.drain()
+        torch.cuda.synchronize()
+        syn, flux, _ = self.lanes[(self.counter - 1) % len(self.lanes)]  # (batched replays run lane 0 only and leave counter at 0)
+        return {"F_nu": flux.cpu().numpy(), "total_alphas": np.array(syn.total_alphas(), dtype=np.float64)}
+
     def close(self):
         for syn, _, _ in self.lanes:
             syn.close()
@@ -786,6 +807,23 @@ def timed(runner, steps, warmup, world, local, settle_s=0.5, cold=True):
         fence()
     elapsed, t_local = run(steps)
     return dict(elapsed=elapsed, local=t_local, cold=t_cold, settle=extra + 1, launch=launch)
+
+
+DUMP_BYTES = 64 * 10**6  # --dump-outputs writes at most this much
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as <directory>/<name>.npy in float64.  Above DUMP_BYTES in all, a fixed, seeded sample of the
+    frequency columns (the last axis, the same columns in every array) is written instead of the whole arrays."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    cols = None
+    if total > DUMP_BYTES:
+        n_nu = next(iter(arrays.values())).shape[-1]
+        cols = np.sort(np.random.default_rng(0).choice(n_nu, size=n_nu * DUMP_BYTES // total, replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a if cols is None else np.ascontiguousarray(a[..., cols]))
 
 
 def n1_same_workload(w, local, steps, use_graph, in_flight=1):
@@ -970,9 +1008,17 @@ def main():
                     help="one GPU: replay the step as a hipGraph (the default on several GPUs).  Round 6 measured successive graph launches "
                          "8.5-9 us apart on this runtime while plain launches of the same three kernels follow each other closely and cost the "
                          "host 10 us per step: S-c2 86-88 us per step with plain launches, 91-93 as graph replays")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip every leg that runs the CPU oracle (baseline and parity checks)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the S-c3 / S-c4m / S-c5 / drop-in blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure also measure and check everything else: cold timing, per-kernel times and rooflines, "
+                         "the CPU baseline and parity against the oracle, two syntheses in flight, the secondary and drop-in blocks (one GPU), "
+                         "per-rank times and the one-GPU run of the same workload (several GPUs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip every leg that runs the CPU oracle (baseline and parity checks)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the S-c3 / S-c4m / S-c5 / drop-in blocks")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.workload is None:
         args.workload = "S-c2" if args.gpus == 1 else "S-c3"
     if args.scaling is None:
@@ -1024,17 +1070,22 @@ def main():
         runner.auto_mode = args.steps < 200
     # a run of >= 200 timed steps is long enough for the clocks to have settled within its first few percent: the W warm-up steps
     # the driver asked for are then ALL that precedes the timed region; shorter runs get ~0.5 s of untimed settling (disclosed)
-    tm = timed(runner, args.steps, args.warmup, world, local, settle_s=0.0 if args.steps >= 200 else 0.5, cold=args.steps < 200)
+    tm = timed(runner, args.steps, args.warmup, world, local, settle_s=0.0 if args.steps >= 200 else 0.5, cold=args.full and args.steps < 200)
     elapsed, settle = tm["elapsed"], tm["settle"]
     syn, flux, count, evals = runner.syn, runner.flux, runner.count, runner.evals
-    spectrum = runner.last_spectrum()
-    kern = kernel_times(ctx, syn, 20)
-    rt_variant = PROFILED_PASS[id(ctx)]["k_raytrace_is"]
+    outputs = runner.last_outputs()
+    spectrum = outputs.get("spectrum")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+    # everything below that is not the headline figure runs under --full only
+    if args.full:
+        kern = kernel_times(ctx, syn, 20)
+        rt_variant = PROFILED_PASS[id(ctx)]["k_raytrace_is"]
 
     # N > 1: what every rank did (shard, its own time for the timed steps, per-kernel times), gathered on rank 0, and the
     # one-GPU step of the same workload on rank 0's GPU
     per_rank, n1 = None, None
-    if world > 1:
+    if world > 1 and args.full:
         mine = {"rank": rank, "device": local, "shard": [int(runner.begin), int(runner.count)], "ms_per_step_own": tm["local"] / args.steps * 1e3,
                 "avg_kernel_ms": kern}
         per_rank = [None] * world
@@ -1047,7 +1098,7 @@ def main():
     # secondary figure (not `value`): two independent syntheses in flight on two streams — what a parameter grid
     # of stars would use; each is still a full pass, they only overlap on the device
     pipelined = None
-    if world == 1 and not args.no_secondary:
+    if world == 1 and args.full and not args.no_secondary:
         from stardis_amd.engine import SpectralSynthesizer
 
         ctx_b = _lib.Context(local)
@@ -1072,17 +1123,6 @@ def main():
         ms_per_step = elapsed / args.steps * 1e3
         value = pts_total * args.steps / elapsed
         n_l, g_cols = syn.n_lines, syn.gamma_cols
-        dom = max(kern, key=kern.get)
-        alg_bytes = {
-            # SURVEY §8d per-stage figures, for the columns this rank produced
-            "k_line_all": 8 * (n_l * (1 + 2 * nd + g_cols) + nus.size + nd * count),
-            "k_raytrace": 16 * nd * count,
-        }.get(dom, syn.algorithmic_bytes())
-        achieved = alg_bytes / (kern[dom] * 1e-3) / 1e9
-        copy_gbps = measured_copy_bandwidth(local) if world == 1 else None
-        dom_traffic = profiled_traffic(args.workload, dom) if world == 1 else None
-        line_ms = kern.get("k_line_all", 0.0) + kern.get("k_line_wide", 0.0) + kern.get("k_line_narrow", 0.0)
-        far_on = "far" in (PROFILED_PASS.get(id(ctx)) or {}).get("k_line_all_is", "") or bool(kern.get("k_line_far"))
         scaling_text = {"weak": "weak (fixed points per GPU: N x the resolving power on the same window)",
                         "strong": "strong (BASELINE's fixed grid split N ways in shards of equal estimated work)"}[args.scaling]
         out = {
@@ -1098,10 +1138,8 @@ def main():
             "untimed_settle_steps_after_warmup": settle,
             "timed_region": ("the K steps follow the W warm-up steps directly" if settle == 0 else
                              f"K steps after W warm-up steps + {settle} untimed settling steps (~0.5 s: clocks; runs of >= 200 steps skip it); "
-                             "ms_per_step_cold = the same K steps timed right after the W warm-up steps"),
-            "counters_from": "instruction counts (roofline_fp64_valu) and HBM traffic (roofline.traffic, hbm_traffic) are read from the committed "
-                             "rocprofv3 PMC passes under profiles/ (newest round), not counted in this run; every time in this line is "
-                             "measured in this run; a figure is refused when the committed pass does not hold exactly the kernels that ran",
+                             + ("ms_per_step_cold = the same K steps timed right after the W warm-up steps" if tm["cold"] is not None else
+                                "ms_per_step_cold is measured with --full")),
             "higher_is_better": True,
             "scaling": args.scaling,
             "vs_baseline": None,
@@ -1131,7 +1169,23 @@ def main():
                 "line_inputs": args.inputs,
                 "outputs": "F_nu and total_alphas (N_d, N_nu); the optional alpha_line plane is not written",
             },
-            "roofline": {
+        }
+        if args.full:
+            dom = max(kern, key=kern.get)
+            alg_bytes = {
+                # SURVEY §8d per-stage figures, for the columns this rank produced
+                "k_line_all": 8 * (n_l * (1 + 2 * nd + g_cols) + nus.size + nd * count),
+                "k_raytrace": 16 * nd * count,
+            }.get(dom, syn.algorithmic_bytes())
+            achieved = alg_bytes / (kern[dom] * 1e-3) / 1e9
+            copy_gbps = measured_copy_bandwidth(local) if world == 1 else None
+            dom_traffic = profiled_traffic(args.workload, dom) if world == 1 else None
+            line_ms = kern.get("k_line_all", 0.0) + kern.get("k_line_wide", 0.0) + kern.get("k_line_narrow", 0.0)
+            far_on = "far" in (PROFILED_PASS.get(id(ctx)) or {}).get("k_line_all_is", "") or bool(kern.get("k_line_far"))
+            out["counters_from"] = ("instruction counts (roofline_fp64_valu) and HBM traffic (roofline.traffic, hbm_traffic) are read from the "
+                                    "committed rocprofv3 PMC passes under profiles/ (newest round), not counted in this run; every time in this "
+                                    "line is measured in this run; a figure is refused when the committed pass does not hold exactly the kernels that ran")
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": rt_variant if dom == "k_raytrace" else dom,
                 "stage": dom,
@@ -1156,8 +1210,7 @@ def main():
                 "voigt_evaluations_per_s_is": "the reference's window points (sum of hi - lo) per second of the line kernel: nominal where the far "
                                               "field is on (see voigt_evaluations_performed)",
                 "voigt_evaluations_performed": performed_evaluations(w, far_on) if world == 1 else None,
-            },
-        }
+            }
         if world > 1:
             out["collective"] = collective_info(world, runner)
             if spectrum is not None:
@@ -1169,7 +1222,8 @@ def main():
                         out["max_rel_dev_vs_n1"] = float(np.max(np.abs(np.asarray(spectrum, dtype=np.float64) - ref) / np.maximum(np.abs(ref), 1e-300)))
             if n1 is not None:
                 n1.pop("_spectrum", None)
-            out["per_rank"] = per_rank
+            if per_rank is not None:
+                out["per_rank"] = per_rank
             out["config"]["shards"] = [[int(b), int(c)] for b, c in (runner.shards or [])] or "equal blocks of ceil(N_nu / N)"
             if n1 is not None:
                 out["n1_same_workload"] = n1
@@ -1177,10 +1231,10 @@ def main():
                 # the denominator a driver needs for scaling efficiency: `value` at N = 1 is a DIFFERENT workload (S-c2, the 1-GPU
                 # config); this is the N = 1 value of THIS line's workload, measured in this run
                 out["value_n1_same_workload"] = n1["value"]
-        valu = profiled_valu(args.workload, kern) if world == 1 else None
+        valu = profiled_valu(args.workload, kern) if world == 1 and args.full else None
         if valu is not None:
             out["roofline_fp64_valu"] = valu
-        if world == 1 and check:
+        if world == 1 and args.full and check:
             base, F_cpu = cpu_baseline(w)
             out["cpu_baseline"] = base
             F_gpu = flux.cpu().numpy()
@@ -1191,7 +1245,7 @@ def main():
             out["speedup_vs_cpu_baseline"] = value / base["value"]
         if pipelined is not None:
             out["throughput_two_syntheses_in_flight"] = pipelined
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             runner.close()
             out["secondary"] = {tag: secondary_block(tag, local, 10, check) for tag in ("S-c3", "S-c4m")}
             out["secondary"]["S-c5"] = s_c5_block(local, 10, check)

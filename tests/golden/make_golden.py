@@ -5,8 +5,8 @@
                                                                                 every array with the committed file
 
 Every fixture draws from ITS OWN generator, np.random.default_rng([20250926, k]) for fixture Gk: what a fixture contains does
-not depend on which other fixtures were requested in the same run (tests/test_golden_recipe.py runs --verify where the reference
-is available).
+not depend on which other fixtures were requested in the same run (--verify checks every committed fixture against a fresh
+regeneration wherever the reference is available).
 
 Runs only in the authoring container (needs /root/reference and astropy).  The
 outputs are data: seeded inputs and what the reference's own functions return

@@ -56,7 +56,7 @@ def test_bench_self_launches_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     if torch.cuda.device_count() < 2:
         env.update(SDX_BENCH_BACKEND="gloo", SDX_BENCH_SINGLE_DEVICE="1")
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"],
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline"],
                           env=env, capture_output=True, text=True, timeout=1200)
     assert proc.returncode == 0, proc.stdout[-3000:] + proc.stderr[-3000:]
     line = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1]
@@ -86,7 +86,7 @@ def test_bench_eight_ranks_on_one_device_rehearse_the_scale_run(mode):
     two_collectives = "two collectives" in mode
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(SDX_BENCH_BACKEND="gloo", SDX_BENCH_SINGLE_DEVICE="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     # (the defaults of a strong-scaling run on several GPUs are "two collectives, two in flight": that mode passes no flag at all)
     default = mode == "two collectives, two in flight"
     extra = [] if default else ((["--two-collectives"] if two_collectives else ["--one-collective"]) + ["--in-flight", "2" if "two in flight" in mode else "1"])
