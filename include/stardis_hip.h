@@ -376,6 +376,8 @@ int sdx_convolve1d_reflect_dev(sdx_ctx* ctx, int64_t n, const double* in, int m,
 /* spectrum_lambda = F_nu * nu / lambda, element-wise (stardis/base.py:137-141) — keeps the emergent spectrum on the
  * device between the formal solution and the instrumental / rotational convolutions */
 int sdx_flux_nu_to_lambda_dev(sdx_ctx* ctx, int64_t n, const double* f_nu, const double* nus, const double* lambdas, double* out);
+/* out[i] = a[i] / b[i] (the continuum-normalised spectrum: flux over continuum). */
+int sdx_divide_dev(sdx_ctx* ctx, int64_t n, const double* a, const double* b, double* out);
 
 /* Everything in one call for resident data: pre-pass + line opacity + total (above) + raytrace (F_nu
  * overwritten).  F_nu is [n_depth][ld].  alpha_line_out and total_alphas ([n_depth][ld]) are OPTIONAL outputs (NULL: the
@@ -527,7 +529,17 @@ int sdx_alpha_line_levels_dev(sdx_ctx* ctx, int64_t n_lines, int n_depth, int n_
  *                        total = ((continuum + line) + plane 0) + plane 1, what Opacities.calc_total_alphas does with the
  *                        dictionary entries (opacities/base.py:24-28);
  *   linelist             when set, the step's own lines come as per-line scalars (f1, below) and the dense arrays
- *                        (line_nus ... alphas, n_lines) are ignored.
+ *                        (line_nus ... alphas, n_lines) are ignored;
+ *   F_nu_continuum       when set, the continuum flux [n_depth][continuum_ld] (column 0 = column nu_begin) is traced with F_nu
+ *                        (beside it in k_raytrace_cont; on the small grids of the segmented kernel by a second launch of it on the
+ *                        continuum plane): the formal solution of the continuum plane alone, with the same angles, source function
+ *                        and geometry (inward_rays, photospheric_correction).  The step's lines, linelist and line_plane[] are
+ *                        excluded; it is F_nu of the same step with no lines and no line planes, bit for bit, on every kernel the
+ *                        option "segmented_raytrace" selects, and on frequency shards.  F_nu, total_alphas, alpha_line_out and I_nus
+ *                        (still the total intensity) are unchanged by it.  Works with source, I_nus, inward_rays, line_plane[],
+ *                        linelist and line_m_max (the synthesis after the classification in the two-collective mode, step 3 below).  SDX_ERR_ARG (-1) with "mixed_precision" = 1,
+ *                        or where the step cannot fuse the total into the formal solution (n_theta > 64, models whose columns do
+ *                        not fit LDS).
  * A zero-initialised description is sdx_synthesize_dev, bit for bit; `options` itself must not be NULL (-1). */
 typedef struct sdx_synthesis_options {
     const double* source;
@@ -540,6 +552,8 @@ typedef struct sdx_synthesis_options {
     int64_t line_plane_ld;
     const sdx_linelist* linelist;
     const double* line_m_max; /* two-collective mode (below): the gathered per-line maxima [n_lines], or NULL */
+    double* F_nu_continuum;   /* [n_depth][continuum_ld] continuum flux, or NULL (no continuum chain) */
+    int64_t continuum_ld;
 } sdx_synthesis_options;
 int sdx_synthesize_opt_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
                            int64_t n_lines, const double* line_nus, const double* doppler_widths, const double* gammas,

@@ -95,6 +95,8 @@ class SynthesisOptions(C.Structure):
         ("line_plane_ld", _i64),
         ("linelist", C.POINTER(LineListStruct)),
         ("line_m_max", _vp),
+        ("F_nu_continuum", _vp),
+        ("continuum_ld", _i64),
     ]
 
 
@@ -172,6 +174,7 @@ PROTOTYPES = {
     "sdx_total_alphas_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, C.POINTER(Continuum), _vp, _i64, _vp, _i64]),
     "sdx_convolve1d_reflect_dev": (_int, [_vp, _i64, _vp, _int, _vp, _int, _vp]),
     "sdx_flux_nu_to_lambda_dev": (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "sdx_divide_dev": (_int, [_vp, _i64, _vp, _vp, _vp]),
     "sdx_synthesize_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, C.POINTER(Continuum), _int,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sdx_synthesize_ex_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, C.POINTER(Continuum), _int,

@@ -2595,6 +2595,11 @@ __global__ __launch_bounds__(kBlock) void k_flux_nu_to_lambda(int64_t n, const d
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i < n) out[i] = mul_rn(f_nu[i], nus[i]) / lambdas[i];
 }
+__global__ __launch_bounds__(kBlock) void k_divide(int64_t n, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) out[i] = a[i] / b[i];
+}
 
 __global__ __launch_bounds__(kBlock) void k_blackbody(int n_depth, int64_t n_nu, const double* __restrict__ nus,
                                                       const double* __restrict__ temps, double* __restrict__ out, int64_t ld)
@@ -3828,6 +3833,198 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
             const int64_t iq = i0 + gq;
             if (h == 0 && iq < n_nu) F[(size_t)(g_lo + b + 1) * fld + iq] = add_rn(sum, other);
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The formal solution with the CONTINUUM FLUX beside the total one (sdx_synthesis_options.F_nu_continuum): F_nu of the continuum
+// plane alone — what radiation_field_solvers/base.py:271-346 gives for the total_alphas of a run with the lines disabled (the
+// reference's `alpha_line_at_nu = 0` entry adds nothing, opacities/base.py:24-28) — from the same staging.  Requires a fused total
+// (ft.cont): the continuum column is read there anyway.
+//
+// k_raytrace_cont<P>: the layout of k_raytrace<P> with sqrt(alpha_cont) staged per depth point beside the (S, sqrt(alpha)) pair, and
+// per lane TWO independent recurrences — total and continuum — on the same ray lengths, the same source values and the same rt_coef
+// arithmetic (the same operations as k_raytrace on a zero-line total, so the continuum flux is that run's F_nu bit for bit).  The
+// k_raytrace chain is latency-bound (one wave walks all N_d - 1 dependent gaps); the second chain gives the scheduler independent work
+// to interleave.  Both flux sums use k_raytrace's order (two ascending halves over theta); the spherical inward sweep runs for both.
+template <int P>
+__global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
+                                                          const double* __restrict__ nus, const double* __restrict__ temps,
+                                                          const double* __restrict__ ray_dist, const double* __restrict__ wts,
+                                                          double* __restrict__ F, int64_t fld, double* __restrict__ Fc, int64_t fcld,
+                                                          double* __restrict__ I_nus, int inward, int gpw, FusedTotal ft)
+{
+    constexpr int kBatch = P == 1 ? 4 : 2;
+    extern __shared__ double smem[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int grp = lane / G, g = lane - grp * G;
+    const int TH = P * G;
+    const int64_t i0 = ((int64_t)blockIdx.x * (kRtBlock / 64) + wave) * gpw;
+    const int64_t i = i0 + grp;
+    const bool active = grp < gpw;
+    const bool valid = active && i < n_nu;
+    const int64_t ic = i < n_nu ? i : n_nu - 1;
+    const int n_gap = n_depth - 1;
+    const int col = n_depth;
+    double* wbase = smem + (size_t)wave * ((3 * gpw * col + 2 * kBatch * gpw * TH + 1) & ~1);  // (even: 16-byte aligned pairs)
+    double2* sP = (double2*)wbase;            // (source function, sqrt(alpha total)) [gpw][col]
+    double* sC = wbase + 2 * gpw * col;       // sqrt(alpha continuum)             [gpw][col]
+    double* sX = sC + gpw * col;              // flux terms, total                 [kBatch][gpw][TH]
+    double* sXc = sX + kBatch * gpw * TH;     // flux terms, continuum             [kBatch][gpw][TH]
+    const double nu = nus[ic];
+
+    if (active) {
+        for (int d = g; d < n_depth; d += G) {
+            const double ac = ft.cont[(size_t)d * ft.cld + ic];
+            double a = ac;
+            if (ft.planes) {
+                double line = ft.planes[(size_t)d * ft.pld + ic];
+                for (int sp = 1; sp < ft.n_planes; ++sp) line = add_rn(line, ft.planes[((size_t)sp * n_depth + d) * ft.pld + ic]);
+                a = add_rn(a, line);
+                if (valid && ft.line_out) ft.line_out[(size_t)d * ft.out_ld + i] = line;
+            }
+            for (int x = 0; x < ft.n_extra; ++x) a = add_rn(a, ft.extra[x][(size_t)d * ft.eld + ic]);
+            if (valid && ft.total_out) ft.total_out[(size_t)d * ft.out_ld + i] = a;
+            sP[grp * col + d] = double2{ft.source ? ft.source[(size_t)d * ft.sld + ic] : planck_staged(nu, temps[d]), sqrt(a)};
+            sC[grp * col + d] = sqrt(ac);
+        }
+    }
+    wave_sync();
+
+    const int gi = (active ? grp : 0) * col;
+    double inten[P], intc[P], wt[P];
+    int th[P];
+    bool on[P];
+#pragma unroll
+    for (int k = 0; k < P; ++k) {
+        th[k] = min(g + k * G, n_theta - 1);
+        on[k] = g + k * G < n_theta;
+        inten[k] = 0.0, intc[k] = 0.0;
+        wt[k] = on[k] ? wts[th[k]] : 0.0;
+    }
+    if (inward) {  // the surface-to-centre sweep of k_raytrace, for both chains
+        for (int gap = n_gap - 1; gap >= 0; --gap) {
+            const int gm = gap > 0 ? gap - 1 : n_gap - 1;
+            const int dm = gap > 0 ? gap - 1 : n_depth - 1;
+            const double2 q0 = sP[gi + gap + 1], q1 = sP[gi + gap], q2 = sP[gi + dm];
+            const double s0 = q0.x, s1 = q1.x, s2 = q2.x;
+            const double mg = q1.y * q0.y, mm = sP[gi + gm].y * sP[gi + gm + 1].y;
+            const double mgc = sC[gi + gap] * sC[gi + gap + 1], mmc = sC[gi + gm] * sC[gi + gm + 1];
+#pragma unroll
+            for (int k = 0; k < P; ++k) {
+                const double rg = ray_dist[(size_t)gap * theta_stride + th[k]], rm = ray_dist[(size_t)gm * theta_stride + th[k]];
+                const double tg = mul_rn(mg, rg), tm = mul_rn(mm, rm);
+                const double tgc = mul_rn(mgc, rg), tmc = mul_rn(mmc, rm);
+                double c, e, cc, ec;
+                rt_coef<false>(tg, tm, s0 - s1, s2 - s1, s1, c, e);
+                rt_coef<false>(tgc, tmc, s0 - s1, s2 - s1, s1, cc, ec);
+                inten[k] = tm == 0.0 ? inten[k] : fma(c, inten[k], e);
+                intc[k] = tmc == 0.0 ? intc[k] : fma(cc, intc[k], ec);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            if (valid && I_nus && on[k]) I_nus[(size_t)i * theta_stride + th[k]] = inten[k];
+            if (active) sX[grp * TH + k * G + g] = inten[k] * wt[k], sXc[grp * TH + k * G + g] = intc[k] * wt[k];
+        }
+        wave_sync();
+        if (lane < gpw && i0 + lane < n_nu) {
+            double sum = 0.0, sumc = 0.0;
+            for (int t = 0; t < n_theta; ++t) sum = add_rn(sum, sX[lane * TH + t]), sumc = add_rn(sumc, sXc[lane * TH + t]);
+            F[i0 + lane] = sum;
+            Fc[i0 + lane] = sumc;
+        }
+        wave_sync();
+    } else {
+#pragma unroll
+        for (int k = 0; k < P; ++k)
+            if (valid && I_nus && on[k]) I_nus[(size_t)i * theta_stride + th[k]] = 0.0;
+        if (valid && g == 0) F[i] = 0.0, Fc[i] = 0.0;
+    }
+    double tau0[P], tauc0[P], rd_next[P];
+    const double* rdp[P];
+    const double2 p0 = sP[gi], p1 = sP[gi + 1];
+    double a1 = p1.y, ac1 = sC[gi + 1];
+    {
+        const double mean0 = p0.y * a1, meanc0 = sC[gi] * ac1;
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            rdp[k] = ray_dist + th[k];
+            const double r0 = *rdp[k];
+            tau0[k] = mul_rn(mean0, r0);
+            tauc0[k] = mul_rn(meanc0, r0);
+            rdp[k] += n_gap > 1 ? theta_stride : 0;
+            rd_next[k] = *rdp[k];
+        }
+    }
+    double s1 = p1.x, d10 = p0.x - s1;
+    const float inv_gpw = 1.0f / (float)gpw;
+
+    for (int gap0 = 0; gap0 < n_gap; gap0 += kBatch) {
+        const int nb = min(kBatch, n_gap - gap0);
+        for (int b = 0; b < nb; ++b) {
+            const int gap = gap0 + b;
+            if (gap < n_gap - 1) {
+                const double2 p2 = sP[gi + gap + 2];
+                const double s2 = p2.x, a2 = p2.y, ac2 = sC[gi + gap + 2];
+                const double mean1 = a1 * a2, meanc1 = ac1 * ac2, d21 = s2 - s1;
+#pragma unroll
+                for (int k = 0; k < P; ++k) {
+                    const double rd = rd_next[k];
+                    const double t1 = mul_rn(mean1, rd), tc1 = mul_rn(meanc1, rd);
+                    rdp[k] += gap + 2 < n_gap ? theta_stride : 0;
+                    rd_next[k] = *rdp[k];
+                    double c, e, cc, ec;
+                    rt_coef<false>(tau0[k], t1, d10, d21, s1, c, e);
+                    rt_coef<false>(tauc0[k], tc1, d10, d21, s1, cc, ec);
+                    const double inew = fma(c, inten[k], e), icnew = fma(cc, intc[k], ec);
+                    inten[k] = inew, intc[k] = icnew;
+                    tau0[k] = t1, tauc0[k] = tc1;
+                    if (valid && I_nus && on[k]) I_nus[((size_t)(gap + 1) * n_nu + i) * theta_stride + th[k]] = inew;
+                    if (active) sX[(b * gpw + grp) * TH + k * G + g] = inew * wt[k], sXc[(b * gpw + grp) * TH + k * G + g] = icnew * wt[k];
+                }
+                d10 = -d21, s1 = s2, a1 = a2, ac1 = ac2;
+            } else {
+#pragma unroll
+                for (int k = 0; k < P; ++k) {
+                    double c, e, cc, ec;
+                    rt_coef<true>(tau0[k], 0.0, d10, 0.0, s1, c, e);
+                    rt_coef<true>(tauc0[k], 0.0, d10, 0.0, s1, cc, ec);
+                    const double inew = fma(c, inten[k], e), icnew = fma(cc, intc[k], ec);
+                    inten[k] = inew, intc[k] = icnew;
+                    if (valid && I_nus && on[k]) I_nus[((size_t)(gap + 1) * n_nu + i) * theta_stride + th[k]] = inew;
+                    if (active) sX[(b * gpw + grp) * TH + k * G + g] = inew * wt[k], sXc[(b * gpw + grp) * TH + k * G + g] = icnew * wt[k];
+                }
+            }
+        }
+        wave_sync();
+        {
+            const int half = (n_theta + 1) >> 1;
+            for (int p = lane; p < 2 * nb * gpw; p += 64) {
+                const int h = p & 1, q = p >> 1;
+                const int b = (int)(((float)q + 0.5f) * inv_gpw), gq = q - b * gpw;
+                const int off = (b * gpw + gq) * TH + (h ? half : 0);
+                const double* c = sX + off;
+                const double* cc = sXc + off;
+                const int cnt = h ? n_theta - half : half;
+                double sum = 0.0, sumc = 0.0;
+                int t = 0;
+                for (; t + 5 <= cnt; t += 5) {
+                    const double c0 = c[t], c1 = c[t + 1], c2 = c[t + 2], c3 = c[t + 3], c4 = c[t + 4];
+                    const double e0 = cc[t], e1 = cc[t + 1], e2 = cc[t + 2], e3 = cc[t + 3], e4 = cc[t + 4];
+                    sum = add_rn(add_rn(add_rn(add_rn(add_rn(sum, c0), c1), c2), c3), c4);
+                    sumc = add_rn(add_rn(add_rn(add_rn(add_rn(sumc, e0), e1), e2), e3), e4);
+                }
+                for (; t < cnt; ++t) sum = add_rn(sum, c[t]), sumc = add_rn(sumc, cc[t]);
+                const double other = __shfl_xor(sum, 1), otherc = __shfl_xor(sumc, 1);
+                const int64_t iq = i0 + gq;
+                if (h == 0 && iq < n_nu) {
+                    F[(size_t)(gap0 + b + 1) * fld + iq] = add_rn(sum, other);
+                    Fc[(size_t)(gap0 + b + 1) * fcld + iq] = add_rn(sumc, otherc);
+                }
+            }
+        }
+        wave_sync();
     }
 }
 

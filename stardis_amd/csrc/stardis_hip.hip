@@ -1913,7 +1913,8 @@ int sdx_calc_weights_dev(sdx_ctx* ctx, int64_t n, const double* tau, double* w0,
 
 static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
                          const double* ray_dist, const double* wts, const double* alphas, int64_t ald, double* F, int64_t fld,
-                         double* I_nus, int accumulate, int inward, const FusedTotal* fused = nullptr, int64_t nu_global = -1);
+                         double* I_nus, int accumulate, int inward, const FusedTotal* fused = nullptr, int64_t nu_global = -1,
+                         double* Fc = nullptr, int64_t fcld = 0);
 
 int sdx_raytrace_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
                      const double* ray_dist, const double* wts, const double* alphas, int64_t ald, double* F, int64_t fld,
@@ -1956,7 +1957,7 @@ int sdx_raytrace_spherical_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_th
 
 static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
                          const double* ray_dist, const double* wts, const double* alphas, int64_t ald, double* F, int64_t fld,
-                         double* I_nus, int accumulate, int inward, const FusedTotal* fused, int64_t nu_global)
+                         double* I_nus, int accumulate, int inward, const FusedTotal* fused, int64_t nu_global, double* Fc, int64_t fcld)
 {
     if (nu_global < n_nu) nu_global = n_nu;  // stand-alone calls: the grid handed over is the whole grid
     FusedTotal ft{};
@@ -1967,6 +1968,10 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
     REQUIRE(!ft.cont || n_theta <= 64, "raytrace: the fused total needs all angles in one launch");
     REQUIRE(!ft.source || n_theta <= 64, "raytrace: a caller-provided source plane needs all angles in one launch");
     REQUIRE((F && fld >= n_nu) || I_nus, "raytrace: no output requested");
+    // the continuum flux (k_raytrace_cont, or a second k_raytrace_seg) is traced beside a fused total, whose continuum column it reads
+    REQUIRE(!Fc || ft.cont, "raytrace: the continuum flux needs a fused total");
+    REQUIRE(!Fc || (F && fcld >= n_nu && !accumulate), "raytrace: the continuum flux needs F_nu and continuum_ld >= the columns");
+    REQUIRE(!Fc || !ctx->mixed_precision, "raytrace: no continuum flux with mixed_precision = 1 (the fp32 formal solution has no continuum chain)");
     constexpr int kMaxChunk = 64;
     for (int th0 = 0; th0 < n_theta; th0 += kMaxChunk) {
         const int nth = std::min(kMaxChunk, n_theta - th0);
@@ -2006,6 +2011,23 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
             }
             int rc = check_launch("k_raytrace_seg");
             if (rc) return rc;
+            if (Fc) {
+                // the continuum on the small grids: k_raytrace_seg once more, on the continuum plane alone (the zero-line run's own
+                // launch, so its bits).  A fused k_raytrace_seg_cont (both chains over one staging, four waves per SIMD) was built and
+                // measured at S-c2: 81 us against 36 for this kernel, 45 us extra per step against 44 for a whole zero-line synthesis
+                // (DESIGN.md).  Removed.
+                FusedTotal fc{};
+                fc.cont = ft.cont, fc.cld = ft.cld, fc.source = ft.source, fc.sld = ft.sld;
+                {
+                    LaunchScope ls(ctx, "k_raytrace", kSegWaves == 4 ? "k_raytrace_seg<4,14> (continuum)" : "k_raytrace_seg<8,7> (continuum)");
+                    const unsigned seg_blocks = (unsigned)(((n_nu + seg_gpw - 1) / seg_gpw + 7) / 8 * 8);
+#define SDX_SEG_ARGS n_depth, n_nu, nth, n_theta, nus, temps, rd, w, nullptr, 0, Fc, fcld, nullptr, seg_gpw, fc
+                    if (kSegWaves == 4) hipLaunchKernelGGL((k_raytrace_seg<4, 14>), dim3(seg_blocks), dim3(256), seg_doubles * sizeof(double), ctx->stream, SDX_SEG_ARGS);
+                    else hipLaunchKernelGGL((k_raytrace_seg<8, 7>), dim3(seg_blocks), dim3(512), seg_doubles * sizeof(double), ctx->stream, SDX_SEG_ARGS);
+#undef SDX_SEG_ARGS
+                }
+                if ((rc = check_launch("k_raytrace_seg"))) return rc;
+            }
             continue;
         }
         // the tolerance path (mixed_precision = 1): plane-parallel, all angles in one launch, flux only -> the fp32 recurrence
@@ -2024,6 +2046,29 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
                 if (rc) return rc;
                 continue;
             }
+        }
+        if (Fc) {
+            REQUIRE(shmem <= 64 * 1024, "raytrace: no continuum flux for models this deep (the columns do not fit LDS)");
+            auto lds_cont = [&](int groups) {  // per wave: (S, sqrt(alpha)) pairs, sqrt(alpha continuum), flux terms of both chains;
+                // an even number of doubles, so that every wave's pairs stay 16-byte aligned (k_raytrace_cont)
+                return ((size_t)(kRtBlock / 64) * ((3 * (size_t)groups * n_depth + 2 * (size_t)kbatch * groups * P * G + 1) & ~(size_t)1)) * sizeof(double);
+            };
+            int gpwc = 64 / G;
+            while (gpwc > 1 && lds_cont(gpwc) > 64 * 1024) --gpwc;
+            const size_t shmemc = lds_cont(gpwc);
+            REQUIRE(shmemc <= 64 * 1024, "raytrace: no continuum flux for models this deep (the columns do not fit LDS)");
+            const unsigned blocksc = (unsigned)((n_nu + (int64_t)gpwc * (kRtBlock / 64) - 1) / ((int64_t)gpwc * (kRtBlock / 64)));
+            {
+                LaunchScope ls(ctx, "k_raytrace", P == 1 ? "k_raytrace_cont<1>" : (P == 2 ? "k_raytrace_cont<2>" : "k_raytrace_cont<4>"));
+#define SDX_RTC_ARGS n_depth, n_nu, nth, n_theta, G, nus, temps, rd, w, F, fld, Fc, fcld, inus, inward, gpwc, ft
+                if (P == 1) hipLaunchKernelGGL(k_raytrace_cont<1>, dim3(blocksc), dim3(kRtBlock), shmemc, ctx->stream, SDX_RTC_ARGS);
+                else if (P == 2) hipLaunchKernelGGL(k_raytrace_cont<2>, dim3(blocksc), dim3(kRtBlock), shmemc, ctx->stream, SDX_RTC_ARGS);
+                else hipLaunchKernelGGL(k_raytrace_cont<4>, dim3(blocksc), dim3(kRtBlock), shmemc, ctx->stream, SDX_RTC_ARGS);
+#undef SDX_RTC_ARGS
+            }
+            int rc = check_launch("k_raytrace_cont");
+            if (rc) return rc;
+            continue;
         }
         {
             LaunchScope ls(ctx, "k_raytrace", shmem <= 64 * 1024 ? (P == 1 ? "k_raytrace<1>" : (P == 2 ? "k_raytrace<2>" : "k_raytrace<4>")) : "k_raytrace_basic");
@@ -2099,6 +2144,17 @@ int sdx_flux_nu_to_lambda_dev(sdx_ctx* ctx, int64_t n, const double* f_nu, const
     return check_launch("k_flux_nu_to_lambda");
 }
 
+int sdx_divide_dev(sdx_ctx* ctx, int64_t n, const double* a, const double* b, double* out)
+{
+    REQUIRE(ctx && n >= 0 && (n == 0 || (a && b && out)), "divide: bad arguments");
+    if (n == 0) return SDX_OK;
+    {
+        LaunchScope ls(ctx, "k_divide");
+        hipLaunchKernelGGL(k_divide, dim3(blocks1(n)), dim3(kBlock), 0, ctx->stream, n, a, b, out);
+    }
+    return check_launch("k_divide");
+}
+
 // ================================================================================================ fused synthesis
 static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
                            int64_t n_lines, const double* line_nus, const double* doppler, const double* gammas, int gamma_cols,
@@ -2115,7 +2171,18 @@ static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
     const int inward = opt && opt->inward_rays ? 1 : 0;
     const int n_extra = opt ? opt->n_line_planes : 0;
     REQUIRE(n_extra >= 0 && n_extra <= 2, "synthesize: n_line_planes must be 0..2");
+    double* const Fc = opt ? opt->F_nu_continuum : nullptr;
+    REQUIRE(!Fc || opt->continuum_ld >= nu_count, "synthesize: continuum_ld must cover the columns");
     for (int k = 0; k < n_extra; ++k) REQUIRE(opt->line_plane[k] && opt->line_plane_ld >= nu_count, "synthesize: bad line plane");
+    // the formal solution forms total = continuum + line planes while staging its columns when those fit LDS
+    const size_t lds_columns = ((size_t)(kRtBlock / 64) * (2 * (size_t)n_depth + 4 * 64)) * sizeof(double);  // k_raytrace with one frequency per wave
+    const bool fuse = n_theta <= 64 && lds_columns <= 64 * 1024;
+    // a continuum request that cannot be served is refused here, before anything is enqueued (k_raytrace_cont: one frequency per
+    // wave, one more column and a second batch of flux terms)
+    REQUIRE(!Fc || !ctx->mixed_precision, "synthesize: no continuum flux with mixed_precision = 1 (the fp32 formal solution has no continuum chain)");
+    REQUIRE(!Fc || fuse, "synthesize: the continuum flux needs the fused total (n_theta <= 64 and the model's columns in LDS)");
+    REQUIRE(!Fc || (size_t)(kRtBlock / 64) * ((3 * (size_t)n_depth + 2 * 4 * 64 + 1) & ~(size_t)1) * sizeof(double) <= 64 * 1024,
+            "synthesize: no continuum flux for models this deep (the columns do not fit LDS)");
     if (nu_count == 0) return SDX_OK;
     // Three launches on one stream: [pre-pass + continuum plane] -> [wide + narrow line kernels] -> [raytrace, which
     // forms total = continuum + line while staging its columns].  Independent work shares a launch instead of a
@@ -2123,9 +2190,6 @@ static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
     int rc2 = ensure(ctx, &ctx->cont_ws, &ctx->cont_ws_bytes, (size_t)n_depth * nu_count * sizeof(double));
     if (rc2) return rc2;
     double* cont_plane = (double*)ctx->cont_ws;
-    // the formal solution forms total = continuum + line planes while staging its columns when those fit LDS
-    const size_t lds_columns = ((size_t)(kRtBlock / 64) * (2 * (size_t)n_depth + 4 * 64)) * sizeof(double);  // k_raytrace with one frequency per wave
-    const bool fuse = n_theta <= 64 && lds_columns <= 64 * 1024;
     // spherical geometry (opt->inward_rays): the inward sweep before the outward one, then F_nu *= (r[-1] / reference_r)^2
     // (radiation_field_solvers/base.py:141-198, :340-344)
     auto finish = [&](int rc_trace) -> int {
@@ -2133,6 +2197,9 @@ static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
         {
             LaunchScope ls(ctx, "k_scale");
             hipLaunchKernelGGL(k_scale, grid2(nu_count, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, nu_count, F_nu, ld, opt->photospheric_correction);
+            if (Fc)
+                hipLaunchKernelGGL(k_scale, grid2(nu_count, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, nu_count, Fc, opt->continuum_ld,
+                                   opt->photospheric_correction);
         }
         return check_launch("k_scale");
     };
@@ -2199,7 +2266,8 @@ static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
     ft.n_extra = n_extra;
     for (int k = 0; k < n_extra; ++k) ft.extra[k] = opt->line_plane[k];
     ft.eld = n_extra ? opt->line_plane_ld : 0;
-    return finish(raytrace_impl(ctx, n_depth, nu_count, n_theta, nus + nu_begin, temps, ray_dist, wts, nullptr, 0, F_nu, ld, I_nus, 0, inward, &ft, n_nu));
+    return finish(raytrace_impl(ctx, n_depth, nu_count, n_theta, nus + nu_begin, temps, ray_dist, wts, nullptr, 0, F_nu, ld, I_nus, 0, inward, &ft, n_nu,
+                                Fc, Fc ? opt->continuum_ld : 0));
 }
 
 int sdx_synthesize_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,

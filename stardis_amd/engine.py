@@ -38,7 +38,8 @@ def _require_f64_buffer(name, buf, n_min):
 
 class SpectralSynthesizer:
     def __init__(self, nus, temperatures, dist, thetas, theta_weights, lines, continuum=None, ctx=None, shard=None,
-                 flux_out=None, track_evaluations=True, keep_line=True, keep_total=True, classify_share=None, m_max=None, m_share_out=None):
+                 flux_out=None, track_evaluations=True, keep_line=True, keep_total=True, classify_share=None, m_max=None, m_share_out=None,
+                 keep_continuum_flux=False):
         """nus: global grid (descending).  lines: dict(line_nus, doppler_widths, gammas, alphas) in the
         reference layout (N_l, N_d), or a stardis_amd.linelist.LineList (per-line scalars; the pre-pass generates the
         three values per (line, depth) itself).  continuum: dict as produced by synth.synth_continuum_state or None.
@@ -49,7 +50,9 @@ class SpectralSynthesizer:
         buffer of n_lines doubles (DeviceArray or CUDA tensor) that holds every rank's share once the caller has gathered it.
         m_share_out: optional device buffer that receives the share's values from its index 0 (the send buffer of the all-gather;
         default: they are written in place, m_max[first line ...]).
-        A step is then enqueue_classify() [-> the caller's all-gather of m_max] -> enqueue()."""
+        A step is then enqueue_classify() [-> the caller's all-gather of m_max] -> enqueue().
+        keep_continuum_flux: also trace the continuum flux (N_d, count) in the same formal solution (sdx_synthesis_options.
+        F_nu_continuum): F_nu of the same step without lines, bit for bit (F_nu_continuum(), emergent_continuum())."""
         self.ctx = ctx or default_context()
         c = self.ctx
         nus = np.ascontiguousarray(nus, dtype=np.float64)
@@ -105,6 +108,8 @@ class SpectralSynthesizer:
         self._flux_tensor = flux_out
         self.d_F = None if flux_out is not None else c.empty((self.n_depth, self.count))
         self.d_evals = c.zeros((1,), np.int64) if track_evaluations else None
+        self.keep_continuum_flux = bool(keep_continuum_flux)
+        self.d_Fc = c.empty((self.n_depth, self.count)) if self.keep_continuum_flux else None
         self._keep_line = keep_line  # also write the summed line opacity plane (alpha_line())
         self._keep_total = keep_total  # also write total_alphas (the reference keeps it on Opacities; the flux does not need it in HBM)
         self.count_evaluations = track_evaluations  # sum(hi - lo) per step costs a memset + copy: switch off when timing
@@ -197,6 +202,9 @@ class SpectralSynthesizer:
     def enqueue(self):
         """One fused step on the context's stream: sdx_synthesize_dev (pre-pass, line gather, total, raytrace)."""
         c = self.ctx
+        if self.keep_continuum_flux:
+            self._enqueue_opt()
+            return
         if self.m_max is not None:  # phase 2 of the two-collective mode: everything behind the classification launch
             opt = _lib.SynthesisOptions()
             opt.line_m_max = ptr_of(self.m_max)
@@ -215,6 +223,27 @@ class SpectralSynthesizer:
                self.d_ln.ptr, self.d_dw.ptr, self.d_g.ptr, self.gamma_cols, self.d_a.ptr, C.byref(self.cont), self.n_theta,
                self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, self.d_line.ptr if self.keep_line else None,
                self.d_total.ptr if self.keep_total else None, self.flux_ptr, self.count, ptr_of(self.d_evals) if self.count_evaluations else None)
+
+    def _enqueue_opt(self):
+        """The step through sdx_synthesize_opt_dev with the continuum flux (dense list, line list or phase 2 of the two-collective
+        mode)."""
+        c = self.ctx
+        opt = _lib.SynthesisOptions()
+        opt.F_nu_continuum = self.d_Fc.ptr
+        opt.continuum_ld = self.count
+        if self.m_max is not None:
+            opt.line_m_max = ptr_of(self.m_max)
+        evals = ptr_of(self.d_evals) if self.count_evaluations and self.m_max is None else None
+        line, total = self.d_line.ptr if self.keep_line else None, self.d_total.ptr if self.keep_total else None
+        if self.linelist is not None:
+            opt.linelist = C.cast(self.linelist.byref(), C.POINTER(_lib.LineListStruct))
+            c.call("sdx_synthesize_opt_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, self.n_lines, None, None,
+                   None, self.gamma_cols, None, C.byref(self.cont), self.n_theta, self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, line, total,
+                   self.flux_ptr, self.count, C.byref(opt), evals)
+            return
+        c.call("sdx_synthesize_opt_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, self.n_lines, self.d_ln.ptr,
+               self.d_dw.ptr, self.d_g.ptr, self.gamma_cols, self.d_a.ptr, C.byref(self.cont), self.n_theta, self.d_t.ptr, self.d_ray.ptr,
+               self.d_w.ptr, line, total, self.flux_ptr, self.count, C.byref(opt), evals)
 
     def enqueue_unfused(self):
         """The same step through the individual entry points (what calc_alphas + raytrace issue)."""
@@ -318,6 +347,21 @@ class SpectralSynthesizer:
             self.ctx.synchronize()
             return self._flux_tensor.cpu().numpy()
         return self.d_F.numpy()
+
+    def _require_continuum(self):
+        if not self.keep_continuum_flux:
+            raise RuntimeError("the continuum flux was not kept: construct the synthesizer with keep_continuum_flux=True")
+
+    @property
+    def F_nu_continuum(self):
+        """-> (N_d, count) numpy array: the continuum flux of the last step."""
+        self._require_continuum()
+        return self.d_Fc.numpy()
+
+    @property
+    def emergent_continuum(self):
+        """-> (count,) numpy array: the continuum flux of the outermost depth point, F_nu_continuum[-1]."""
+        return self.F_nu_continuum[-1]
 
     def total_alphas(self):
         if not self.keep_total:

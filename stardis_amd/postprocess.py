@@ -117,3 +117,21 @@ class DeviceSpectrum:
         if velocity_per_pix is not None and abs(_kms(v_rot)) >= 1e-5:
             d = convolve1d_reflect_device(d, self.n, rotation_profile(_kms(velocity_per_pix), _kms(v_rot), limb_darkening), self.ctx)
         return d
+
+    def normalized(self, sigma_pix=None, velocity_per_pix=None, v_rot=0.0, limb_darkening=0.6):
+        """The continuum-normalised spectrum: broadened() of the flux over the same convolutions of the continuum flux (the
+        synthesizer needs keep_continuum_flux=True), divided on the device.  Returns the DeviceArray (N_nu,)."""
+        syn = self.syn
+        syn._require_continuum()
+        flux = self.broadened(sigma_pix, velocity_per_pix, v_rot, limb_darkening)
+        cont = self.ctx.empty((self.n,))
+        row = syn.d_Fc.ptr + 8 * (syn.n_depth - 1) * syn.count  # F_nu_continuum[-1]
+        self.ctx.call("sdx_flux_nu_to_lambda_dev", self.n, row, syn.d_nus.ptr, self.d_lambdas.ptr, cont.ptr)
+        if sigma_pix:
+            cont = convolve1d_reflect_device(cont, self.n, gaussian_kernel(float(sigma_pix)), self.ctx)
+        if velocity_per_pix is not None and abs(_kms(v_rot)) >= 1e-5:
+            cont = convolve1d_reflect_device(cont, self.n, rotation_profile(_kms(velocity_per_pix), _kms(v_rot), limb_darkening), self.ctx)
+        out = self.ctx.empty((self.n,))
+        self.ctx.call("sdx_divide_dev", self.n, flux.ptr, cont.ptr, out.ptr)
+        return out
+

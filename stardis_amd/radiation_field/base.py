@@ -6,7 +6,7 @@ import numpy as np
 
 from stardis_amd.radiation_field.opacities import Opacities
 from stardis_amd.radiation_field.opacities.opacities_solvers import calc_alphas
-from stardis_amd.radiation_field.radiation_field_solvers import raytrace
+from stardis_amd.radiation_field.radiation_field_solvers import continuum_flux, raytrace
 from stardis_amd.radiation_field.source_functions.blackbody import blackbody_flux_at_nu
 
 logger = logging.getLogger(__name__)
@@ -41,14 +41,16 @@ class RadiationField(_Base):
 FUSED = os.environ.get("STARDIS_AMD_FUSED", "1") != "0"  # one fused device pass when the configuration allows it
 
 
-def create_stellar_radiation_field(tracing_nus, stellar_model, stellar_plasma, config):
+def create_stellar_radiation_field(tracing_nus, stellar_model, stellar_plasma, config, *, continuum=False):
     """Opacities then formal solution, as the reference's driver (:71-117).  Configurations the fused synthesis covers run
     as ONE device pass with lazily materialised dictionary entries (stardis_amd/radiation_field/fused.py); everything else —
-    and STARDIS_AMD_FUSED=0 — takes the source-by-source path below.  Both produce the same numbers."""
+    and STARDIS_AMD_FUSED=0 — takes the source-by-source path below.  Both produce the same numbers.
+    continuum=True: the field also gets F_nu_continuum (N_d, N_nu), the formal solution of the continuum alone — F_nu of the same
+    configuration with opacity.line.disable = True and include_molecules = False, bit for bit."""
     if FUSED:
         from stardis_amd.radiation_field.fused import try_fused
 
-        field = try_fused(RadiationField, tracing_nus, stellar_model, stellar_plasma, config, blackbody_flux_at_nu)
+        field = try_fused(RadiationField, tracing_nus, stellar_model, stellar_plasma, config, blackbody_flux_at_nu, continuum=continuum)
         if field is not None:
             logger.info("Radiation field computed by the fused synthesis")
             return field
@@ -64,4 +66,8 @@ def create_stellar_radiation_field(tracing_nus, stellar_model, stellar_plasma, c
                 opacity_config=config.opacity)
     logger.info("Raytracing")
     raytrace(stellar_model, field)
+    if continuum:
+        from stardis_amd._lib import default_context
+
+        field.F_nu_continuum = continuum_flux(stellar_model, field, field.opacities.continuum_alphas_device(default_context()))
     return field

@@ -53,13 +53,14 @@ MEMO_MAX_BYTES = 2 << 30  # ... and at most this much derived data (numpy arrays
 DEVICE_BUDGET_BYTES = 8 << 30  # device memory the lazy entries of live fused fields may hold per process (fused_lazy)
 
 
-def try_fused(field_cls, tracing_nus, stellar_model, stellar_plasma, config, source_function):
-    """-> RadiationField computed by one fused device pass, or None when the configuration needs the general path."""
+def try_fused(field_cls, tracing_nus, stellar_model, stellar_plasma, config, source_function, continuum=False):
+    """-> RadiationField computed by one fused device pass, or None when the configuration needs the general path.
+    continuum: also trace the continuum flux in the same step (field.F_nu_continuum, sdx_synthesis_options.F_nu_continuum)."""
     with one_call():  # (witnesses are per call and per thread: the tables may be edited before the next one)
-        return _try_fused(field_cls, tracing_nus, stellar_model, stellar_plasma, config, source_function)
+        return _try_fused(field_cls, tracing_nus, stellar_model, stellar_plasma, config, source_function, continuum)
 
 
-def _try_fused(field_cls, tracing_nus, stellar_model, stellar_plasma, config, source_function):
+def _try_fused(field_cls, tracing_nus, stellar_model, stellar_plasma, config, source_function, continuum=False):
     opacity = config.opacity
     spherical = bool(getattr(stellar_model, "spherical", False))
     tracked = bool(config.result_options.return_radiation_field)
@@ -229,6 +230,7 @@ def _run_step(v):
                        "n_e", "line", "line_spec", "mol", "mol_spec", "n_lines", "n_mol", "opacity", "config", "stellar_plasma", "stellar_model",
                        "tracked", "spherical", "correction", "source", "rayleigh_species", "ff_ions"))
     P = lambda name: ptrs[slot[name]] if name in slot else None  # noqa: E731
+    continuum = bool(v["continuum"])
 
     file_planes = []
     for source, fpath, tab in plane_sources:
@@ -290,8 +292,11 @@ def _run_step(v):
     if tracked:  # every ray's intensity at every depth point stays on the device until somebody reads field.I_nus
         field._I_dev = ctx.empty((nd, nus.size, int(config.no_of_thetas)))
     line_struct = None
-    if spherical or n_mol or (line_spec is not None and n_lines):
+    d_Fc = ctx.empty((nd, nus.size)) if continuum else None
+    if spherical or n_mol or (line_spec is not None and n_lines) or continuum:
         opt = SynthesisOptions()
+        if continuum:
+            opt.F_nu_continuum, opt.continuum_ld = d_Fc.ptr, nus.size
         opt.source, opt.source_ld = P("source"), nus.size
         opt.I_nus = field._I_dev.ptr if tracked else None
         opt.inward_rays, opt.photospheric_correction = (1 if spherical else 0), float(correction)
@@ -313,6 +318,8 @@ def _run_step(v):
     else:
         field.F_nu = np.empty((nd, nus.size))
         ctx.call("sdx_memcpy_d2h", field.F_nu.ctypes.data, d_F.ptr, field.F_nu.nbytes)
+    if continuum:
+        field.F_nu_continuum = d_Fc.numpy()
     blob._staging = None  # (the download above synchronised: the staging block may go back to the pool)
     opac._total_twin = d_total
     field._device_blob = (blob, file_planes)  # keeps the staged inputs alive as long as the lazy entries may need them

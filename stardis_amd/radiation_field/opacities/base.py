@@ -40,6 +40,18 @@ class Opacities:
         self._total_dev = (self.total_alphas.copy(), total)
         return self.total_alphas
 
+    def continuum_alphas_device(self, ctx):
+        """The total of a run with the lines disabled, on the device: the dictionary's continuum entries summed in its order from
+        zero, as calc_total_alphas sums them (the line entries — atomic and molecular — left out)."""
+        total = ctx.zeros(self.total_alphas.shape)
+        for key, value in self.opacities_dict.items():
+            if key.startswith(("alpha_line_at_nu", "molecule_alpha_line_at_nu")):
+                continue
+            if np.ndim(value) == 0 and value == 0:
+                continue
+            ops.accumulate(total, self._device_entry(ctx, key, value), ctx)
+        return total
+
     def total_alphas_device(self, ctx):
         """Device copy of total_alphas, reused if the host array is unchanged since calc_total_alphas."""
         if self._total_dev is not None and np.array_equal(self._total_dev[0], self.total_alphas):

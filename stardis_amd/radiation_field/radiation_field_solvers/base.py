@@ -83,3 +83,25 @@ def raytrace(stellar_model, stellar_radiation_field):
     if track:
         field.I_nus[...] = I
     return field.F_nu
+
+
+def continuum_flux(stellar_model, stellar_radiation_field, continuum_alphas):
+    """The raytrace above applied to a continuum plane (N_d, N_nu; host or device array) into a fresh zero flux: the same angles,
+    source function and geometry as the field's own F_nu, no intensities.  -> F_nu_continuum (N_d, N_nu)."""
+    field = stellar_radiation_field
+    thetas = np.asarray(field.thetas, dtype=np.float64)
+    correction = 1.0
+    if stellar_model.spherical:
+        radii = np.asarray(plain(stellar_model.geometry.r), dtype=np.float64)
+        ray_distances = calculate_spherical_ray(thetas, radii)
+        correction = (radii[-1] / float(plain(stellar_model.geometry.reference_r))) ** 2
+    else:
+        dist = np.asarray(plain(stellar_model.geometry.dist_to_next_depth_point), dtype=np.float64)
+        ray_distances = dist.reshape(-1, 1) / np.cos(thetas)
+    F, _ = ops.raytrace_arrays(
+        field.frequencies, plain(stellar_model.temperatures), ray_distances, field.I_nus_weights, continuum_alphas,
+        ctx=default_context(), inward_rays=bool(stellar_model.spherical), photospheric_correction=correction,
+        source=_source_plane(getattr(field, "source_function", None), field.frequencies, stellar_model.temperatures),
+    )
+    return F
+
