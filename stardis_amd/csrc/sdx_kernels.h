@@ -3337,6 +3337,13 @@ struct FusedTotal {
 //            two ascending halves and writes F_nu.
 // Only the ray table is shared by the block: after the staging barrier the waves never meet again (wave-level hand-overs).
 constexpr int kRtBlock = 256;
+// lane / G for lane < 64 and 1 <= G <= 64 without an integer division (~25 instructions where G is a kernel argument): one multiply
+// by g_recip = 65536 / G + 1, formed once on the host (lane_recip, stardis_hip.hip), and a shift.  Exact over that whole range.
+// (k_raytrace_seg, whose prologue is a visible share of a wave's life; k_raytrace<P> and k_raytrace_cont<P> keep the division)
+__device__ __forceinline__ int lane_div(int lane, int g_recip)
+{
+    return (lane * g_recip) >> 16;
+}
 template <int P>
 __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
                                                      const double* __restrict__ nus, const double* __restrict__ temps,
@@ -3387,6 +3394,9 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
         }
     }
     wave_sync();  // (nothing is shared between the waves of a block any more: the ray table is read from L1)
+    // (the step's constants stay literals here: the gap loop is rolled and the compiler already holds them in scalar registers across it
+    // — no literal move in the loop body; pinned with rt_const_resident they cost k_raytrace<1> five more SGPR spills and put two moves back)
+    const RtConst kc = rt_const_literals();
 
     const int gi = (active ? grp : 0) * col;  // idle lanes shadow group 0 and never store
     double inten[P], wt[P];
@@ -3413,7 +3423,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
             for (int k = 0; k < P; ++k) {
                 const double tg = mul_rn(mg, ray_dist[(size_t)gap * theta_stride + th[k]]), tm = mul_rn(mm, ray_dist[(size_t)gm * theta_stride + th[k]]);
                 double c, e;
-                rt_coef<false>(tg, tm, s0 - s1, s2 - s1, s1, c, e);
+                rt_coef<false>(tg, tm, s0 - s1, s2 - s1, s1, c, e, kc);
                 inten[k] = tm == 0.0 ? inten[k] : fma(c, inten[k], e);
             }
         }
@@ -3470,7 +3480,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
                     rdp[k] += gap + 2 < n_gap ? theta_stride : 0;
                     rd_next[k] = *rdp[k];  // gap + 2, for the next trip
                     double c, e;
-                    rt_coef<false>(tau0[k], t1, d10, d21, s1, c, e);
+                    rt_coef<false>(tau0[k], t1, d10, d21, s1, c, e, kc);
                     const double inew = fma(c, inten[k], e);
                     inten[k] = inew;
                     tau0[k] = t1;
@@ -3482,7 +3492,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
 #pragma unroll
                 for (int k = 0; k < P; ++k) {
                     double c, e;
-                    rt_coef<true>(tau0[k], 0.0, d10, 0.0, s1, c, e);
+                    rt_coef<true>(tau0[k], 0.0, d10, 0.0, s1, c, e, kc);
                     const double inew = fma(c, inten[k], e);
                     inten[k] = inew;
                     if (valid && I_nus && on[k]) I_nus[((size_t)(gap + 1) * n_nu + i) * theta_stride + th[k]] = inew;
@@ -3666,21 +3676,23 @@ template <int NS, int LMAX>
 __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8 ? 6 : 4, 8))) void k_raytrace_seg(
     int n_depth, int64_t n_nu, int n_theta, int theta_stride, const double* __restrict__ nus, const double* __restrict__ temps,
     const double* __restrict__ ray_dist, const double* __restrict__ wts, const double* __restrict__ alphas,
-    int64_t ald, double* __restrict__ F, int64_t fld, double* __restrict__ I_nus, int gpw, FusedTotal ft)
+    int64_t ald, double* __restrict__ F, int64_t fld, double* __restrict__ I_nus, int gpw, int g_recip, unsigned n_wg, unsigned per_xcd,
+    FusedTotal ft)
 {
     extern __shared__ double smem[];
     const int lane = threadIdx.x & 63;
     const int seg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: gap indices and their branches stay scalar
     const int G = n_theta;
-    const int grp = lane / G, g = lane - grp * G;
+    const int grp = lane_div(lane, g_recip), g = lane - grp * G;
     // XCD-aware order: a workgroup reads and writes only gpw (= 3) adjacent columns of every plane row, less than half a 64-byte
     // sector — the workgroups that share a sector must share an L2, or every XCD fetches and writes back its own copy of it
     // (measured: 30 MB fetched, 13 MB written for 10 + 7 MB).  Workgroups b, b + 8, ... run on one XCD: they take one
-    // contiguous eighth of the frequencies (the work per frequency is uniform here).
-    const int64_t n_wg = (n_nu + gpw - 1) / gpw, per_xcd = (n_wg + 7) / 8;
-    const int64_t wg = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if ((int64_t)(blockIdx.x >> 3) >= per_xcd || wg >= n_wg) return;  // (the whole workgroup: no barrier is left waiting)
-    const int64_t i0 = wg * gpw;
+    // contiguous eighth of the frequencies (the work per frequency is uniform here).  n_wg = ceil(n_nu / gpw) and per_xcd =
+    // ceil(n_wg / 8) are launch constants and come from the host: formed here, two 64-bit divisions ran in every wave.  The grid is
+    // 8 per_xcd workgroups, so the index fits 32 bits.
+    const unsigned wg = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    if ((blockIdx.x >> 3) >= per_xcd || wg >= n_wg) return;  // (the whole workgroup: no barrier is left waiting)
+    const int64_t i0 = (int64_t)wg * gpw;
     const int64_t i = i0 + grp;
     const bool active = grp < gpw;
     const bool valid = active && i < n_nu;
@@ -3748,6 +3760,10 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
     // outside the normal range) only raises the wave's flag, and the wave then redoes its segment in the reference's own form
     unsigned long long redo = 0;
     const int gc = count > 0 ? g_lo : 0;
+    const RtConst kc = rt_const_resident();  // the step's literals, in scalar registers from here on (sdx_math.h)
+    // (A straight-line copy of this pass and of the replay for the waves whose segment fills all LMAX slots — no `j >= j0` test per
+    // slot — was built and measured: 34.7 us against 35.0 at S-c2, inside the spread of either, for a third more code; the compiler
+    // also sank every slot's tail behind the last one, 48 spilled VGPRs, until each slot's (c, e) was pinned.  Removed.)
     {
         const double2* pP = sP + gi + gc - j0;
         const double* pR = sRT + th * rstride + gc - j0;
@@ -3764,10 +3780,10 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
                     const double s2 = q2.x, a2 = q2.y;
                     const double t1 = mul_rn(a1 * a2, pR[j + 1]);
                     const double d21 = s2 - s1;
-                    redo |= rt_coef_fast<false>(t0, t1, d10, d21, s1, c[j], e[j]);
+                    redo |= rt_coef_fast<false>(t0, t1, d10, d21, s1, c[j], e[j], kc);
                     t0 = t1, d10 = -d21, s1 = s2, a1 = a2;
                 } else {  // the final gap (:253-266)
-                    redo |= rt_coef_fast<true>(t0, 0.0, d10, 0.0, s1, c[j], e[j]);
+                    redo |= rt_coef_fast<true>(t0, 0.0, d10, 0.0, s1, c[j], e[j], kc);
                 }
                 A *= c[j];
                 B = fma(c[j], B, e[j]);
@@ -3890,6 +3906,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
         }
     }
     wave_sync();
+    const RtConst kc = rt_const_literals();  // (literals, as in k_raytrace)
 
     const int gi = (active ? grp : 0) * col;
     double inten[P], intc[P], wt[P];
@@ -3916,8 +3933,8 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
                 const double tg = mul_rn(mg, rg), tm = mul_rn(mm, rm);
                 const double tgc = mul_rn(mgc, rg), tmc = mul_rn(mmc, rm);
                 double c, e, cc, ec;
-                rt_coef<false>(tg, tm, s0 - s1, s2 - s1, s1, c, e);
-                rt_coef<false>(tgc, tmc, s0 - s1, s2 - s1, s1, cc, ec);
+                rt_coef<false>(tg, tm, s0 - s1, s2 - s1, s1, c, e, kc);
+                rt_coef<false>(tgc, tmc, s0 - s1, s2 - s1, s1, cc, ec, kc);
                 inten[k] = tm == 0.0 ? inten[k] : fma(c, inten[k], e);
                 intc[k] = tmc == 0.0 ? intc[k] : fma(cc, intc[k], ec);
             }
@@ -3975,8 +3992,8 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
                     rdp[k] += gap + 2 < n_gap ? theta_stride : 0;
                     rd_next[k] = *rdp[k];
                     double c, e, cc, ec;
-                    rt_coef<false>(tau0[k], t1, d10, d21, s1, c, e);
-                    rt_coef<false>(tauc0[k], tc1, d10, d21, s1, cc, ec);
+                    rt_coef<false>(tau0[k], t1, d10, d21, s1, c, e, kc);
+                    rt_coef<false>(tauc0[k], tc1, d10, d21, s1, cc, ec, kc);
                     const double inew = fma(c, inten[k], e), icnew = fma(cc, intc[k], ec);
                     inten[k] = inew, intc[k] = icnew;
                     tau0[k] = t1, tauc0[k] = tc1;
@@ -3988,8 +4005,8 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
 #pragma unroll
                 for (int k = 0; k < P; ++k) {
                     double c, e, cc, ec;
-                    rt_coef<true>(tau0[k], 0.0, d10, 0.0, s1, c, e);
-                    rt_coef<true>(tauc0[k], 0.0, d10, 0.0, s1, cc, ec);
+                    rt_coef<true>(tau0[k], 0.0, d10, 0.0, s1, c, e, kc);
+                    rt_coef<true>(tauc0[k], 0.0, d10, 0.0, s1, cc, ec, kc);
                     const double inew = fma(c, inten[k], e), icnew = fma(cc, intc[k], ec);
                     inten[k] = inew, intc[k] = icnew;
                     if (valid && I_nus && on[k]) I_nus[((size_t)(gap + 1) * n_nu + i) * theta_stride + th[k]] = inew;

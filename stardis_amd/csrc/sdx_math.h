@@ -244,11 +244,25 @@ __device__ __forceinline__ double fma3(double a, double b, double c)
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
     return d;
 }
-__device__ __forceinline__ double exp_neg(double tau)
+// The constants of exp_neg as data.  The default argument of exp_neg hands them over as literals (every caller outside the formal
+// solution); the formal-solution kernels pass a copy they have pinned in scalar registers (RtConst below).
+struct ExpConst {
+    double nlog2e;           // -log2(e)
+    double nln2_hi, nln2_lo; // -ln2, high and low part
+    double p0;               // leading Horner coefficient (a VGPR operand: the second constant of the first step)
+    double p[9];             // the other nine, in the order of use
+};
+__host__ __device__ constexpr ExpConst exp_literals()
 {
-    const double n = rint(mul_rn(tau, -0x1.71547652b82fep+0));       // -log2(e)
-    double r = fma(n, -0x1.62e42fefa39efp-1, -tau);                    // -ln2 (high part)
-    r = fma(-0x1.abc9e3b39803fp-56, n, r);                             // -ln2 (low part)
+    return {-0x1.71547652b82fep+0, -0x1.62e42fefa39efp-1, -0x1.abc9e3b39803fp-56, 0x1.ade156a5dcb37p-26,
+            {0x1.28af3fca7ab0cp-22, 0x1.71dee623fde64p-19, 0x1.a01997c89e6b0p-16, 0x1.a01a014761f6ep-13, 0x1.6c16c1852b7b0p-10,
+             0x1.1111111122322p-7, 0x1.55555555502a1p-5, 0x1.5555555555511p-3, 0x1.000000000000bp-1}};
+}
+__device__ __forceinline__ double exp_neg(double tau, const ExpConst& k = exp_literals())
+{
+    const double n = rint(mul_rn(tau, k.nlog2e));
+    double r = fma(n, k.nln2_hi, -tau);
+    r = fma(k.nln2_lo, n, r);
     // the nine three-address Horner steps as ONE asm block: after every separate asm statement the compiler inserts a
     // defensive s_nop, which would hand back the issue slots the three-address form saves.  The coefficients sit in SGPR
     // pairs (one scalar operand per VALU instruction is allowed): as VGPR operands they would pin 20 vector registers
@@ -264,9 +278,7 @@ __device__ __forceinline__ double exp_neg(double tau)
         "v_fma_f64 %0, %1, %0, %10\n\t"
         "v_fma_f64 %0, %1, %0, %11"
         : "=&v"(p)
-        : "v"(r), "v"(0x1.ade156a5dcb37p-26), "s"(0x1.28af3fca7ab0cp-22), "s"(0x1.71dee623fde64p-19), "s"(0x1.a01997c89e6b0p-16),
-          "s"(0x1.a01a014761f6ep-13), "s"(0x1.6c16c1852b7b0p-10), "s"(0x1.1111111122322p-7), "s"(0x1.55555555502a1p-5),
-          "s"(0x1.5555555555511p-3), "s"(0x1.000000000000bp-1));
+        : "v"(r), "v"(k.p0), "s"(k.p[0]), "s"(k.p[1]), "s"(k.p[2]), "s"(k.p[3]), "s"(k.p[4]), "s"(k.p[5]), "s"(k.p[6]), "s"(k.p[7]), "s"(k.p[8]));
     p = fma(r, p, 1.0);
     p = fma(r, p, 1.0);
     return ldexp(p, (int)n);
@@ -537,9 +549,43 @@ __device__ __forceinline__ double planck_staged(double nu, double temp)
 // Anything unusual — t0 = 0 (no change, :203-206), t1 = 0, a denominator that is zero, subnormal, infinite or NaN — is caught
 // by ONE class test of D and redone per lane in the reference's own form, IEEE divisions and all: the same inf / NaN pattern.
 // LAST: the final gap (:253-266), e = w0 S1 + w2 (S0 - S1) / t0^2.
-__device__ __forceinline__ void rt_weights_wave(double tau, double& w0, double& w1, double& w2)
+//
+// The literals of the step live in an RtConst.  A kernel fills one before its gap loop with rt_const_resident(): each member passes
+// through an empty asm statement, after which the compiler sees a value it cannot form again from a literal and keeps the
+// SGPR pair for the life of the wave.  Left as literals, every use is preceded by its own s_mov_b32 pair (the compiler takes a
+// scalar move of a literal for free to repeat): 24 - 30 scalar moves per gap next to ~58 vector instructions, all of them issued
+// from the wave's one instruction stream and retired by the CU's one scalar unit.  Same operands, same vector instructions.
+struct RtConst {
+    ExpConst x;
+    double tau_small;  // below: the series forms of the weights
+    double tau_max;    // the clamp that makes the exponential form exact for tau >= 50
+    double third;
+};
+__device__ __forceinline__ double sgpr_resident(double v)
 {
-    const bool small = tau < 5e-4;
+    asm volatile("" : "+s"(v));
+    return v;
+}
+__host__ __device__ constexpr RtConst rt_const_literals()
+{
+    return {exp_literals(), 5e-4, 64.0, 1.0 / 3};
+}
+__device__ __forceinline__ RtConst rt_const_resident()
+{
+    RtConst k = rt_const_literals();
+    k.x.nlog2e = sgpr_resident(k.x.nlog2e);
+    k.x.nln2_hi = sgpr_resident(k.x.nln2_hi);
+    k.x.nln2_lo = sgpr_resident(k.x.nln2_lo);
+#pragma unroll
+    for (int j = 0; j < 9; ++j) k.x.p[j] = sgpr_resident(k.x.p[j]);
+    k.tau_small = sgpr_resident(k.tau_small);
+    k.tau_max = sgpr_resident(k.tau_max);
+    k.third = sgpr_resident(k.third);
+    return k;
+}
+__device__ __forceinline__ void rt_weights_wave(double tau, double& w0, double& w1, double& w2, const RtConst& k)
+{
+    const bool small = tau < k.tau_small;
     const unsigned long long m_small = __builtin_amdgcn_ballot_w64(small), m_all = __builtin_amdgcn_ballot_w64(true);
     // (no initial values: every lane that is read below has been written — the exponential form unless ALL lanes take the
     // series, the series in the lanes that select it; the empty statements only tell the compiler so.  Initial values, or an
@@ -551,8 +597,8 @@ __device__ __forceinline__ void rt_weights_wave(double tau, double& w0, double& 
         // min(tau, 64) as the bare instruction (NaN -> 64: the reference's else-branch, (1, 1, 2), too); fmin() would first
         // canonicalise its argument with a v_max_f64
         double tc;
-        asm("v_min_f64 %0, %1, %2" : "=v"(tc) : "v"(tau), "s"(64.0));
-        const double e = exp_neg(tc);
+        asm("v_min_f64 %0, %1, %2" : "=v"(tc) : "v"(tau), "s"(k.tau_max));
+        const double e = exp_neg(tc, k.x);
         w0 = sub_rn(1.0, e);
         w1 = sub_rn(w0, mul_rn(tc, e));
         w2 = sub_rn(mul_rn(2.0, w1), mul_rn(mul_rn(tc, tc), e));
@@ -560,8 +606,8 @@ __device__ __forceinline__ void rt_weights_wave(double tau, double& w0, double& 
     if (m_small) {
         const double a0 = mul_rn(tau, sub_rn(1.0, mul_rn(tau, 0.5)));
         const double t2 = mul_rn(tau, tau);
-        const double a1 = mul_rn(t2, sub_rn(0.5, mul_rn(tau, 1.0 / 3)));
-        const double a2 = mul_rn(mul_rn(t2, tau), sub_rn(1.0 / 3, mul_rn(tau, 0.25)));
+        const double a1 = mul_rn(t2, sub_rn(0.5, mul_rn(tau, k.third)));
+        const double a2 = mul_rn(mul_rn(t2, tau), sub_rn(k.third, mul_rn(tau, 0.25)));
         w0 = small ? a0 : w0;
         w1 = small ? a1 : w1;
         w2 = small ? a2 : w2;
@@ -590,10 +636,10 @@ __device__ __forceinline__ void rt_coef_reference(double t0, double t1, double d
 }
 // -> wave mask of the lanes whose (c, e) must be redone by rt_coef_reference
 template <bool LAST>
-__device__ __forceinline__ unsigned long long rt_coef_fast(double t0, double t1, double d10, double d21, double s1, double& c, double& e)
+__device__ __forceinline__ unsigned long long rt_coef_fast(double t0, double t1, double d10, double d21, double s1, double& c, double& e, const RtConst& k)
 {
     double w0, w1, w2;
-    rt_weights_wave(t0, w0, w1, w2);
+    rt_weights_wave(t0, w0, w1, w2, k);
     double den;
     if constexpr (LAST) {
         den = t0 * t0;
@@ -611,9 +657,9 @@ __device__ __forceinline__ unsigned long long rt_coef_fast(double t0, double t1,
     return unusual;
 }
 template <bool LAST>
-__device__ __forceinline__ void rt_coef(double t0, double t1, double d10, double d21, double s1, double& c, double& e)
+__device__ __forceinline__ void rt_coef(double t0, double t1, double d10, double d21, double s1, double& c, double& e, const RtConst& k)
 {
-    const unsigned long long unusual = rt_coef_fast<LAST>(t0, t1, d10, d21, s1, c, e);
+    const unsigned long long unusual = rt_coef_fast<LAST>(t0, t1, d10, d21, s1, c, e, k);
     if (unusual) {
         if ((unusual >> (threadIdx.x & 63)) & 1) rt_coef_reference<LAST>(t0, t1, d10, d21, s1, c, e);
     }

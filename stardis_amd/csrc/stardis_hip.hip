@@ -792,6 +792,11 @@ struct ClassifyPhase {
 // instructions for eight times the waves: it wins where k_raytrace would leave the chip under three waves per SIMD.
 static const int kSegWaves = knob("SDX_RT_NS") && std::atoi(knob("SDX_RT_NS")) == 4 ? 4 : 8;  // experiment knob: 4 waves x 14 gaps
 static const int kSegMax = kSegWaves == 4 ? 14 : 7;
+// lane / G as a multiply and a shift in k_raytrace_seg (lane_div, sdx_kernels.h): exact for lane < 64, 1 <= G <= 64
+static int lane_recip(int G)
+{
+    return 65536 / G + 1;
+}
 static size_t seg_lds_doubles(int n_depth, int nth)
 {
     const int gpw = 64 / nth;
@@ -2000,11 +2005,12 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
         // workgroup (k_raytrace_seg)
         const int seg_gpw = 64 / nth;
         const size_t seg_doubles = seg_lds_doubles(n_depth, nth);
+        // the launch geometry of the XCD-aware order, handed to the kernel: workgroups, workgroups per XCD, whole rounds of eight
+        const unsigned seg_wg = (unsigned)((n_nu + seg_gpw - 1) / seg_gpw), seg_per_xcd = (seg_wg + 7) / 8, seg_blocks = seg_per_xcd * 8;
         if (use_segmented_raytrace(ctx, n_depth, nu_global, n_theta, P == 1 && !inward && !acc)) {
             {
                 LaunchScope ls(ctx, "k_raytrace", kSegWaves == 4 ? "k_raytrace_seg<4,14>" : "k_raytrace_seg<8,7>");
-                const unsigned seg_blocks = (unsigned)(((n_nu + seg_gpw - 1) / seg_gpw + 7) / 8 * 8);  // whole rounds of the XCD-aware order
-#define SDX_SEG_ARGS n_depth, n_nu, nth, n_theta, nus, temps, rd, w, alphas, ald, F, fld, inus, seg_gpw, ft
+#define SDX_SEG_ARGS n_depth, n_nu, nth, n_theta, nus, temps, rd, w, alphas, ald, F, fld, inus, seg_gpw, lane_recip(nth), seg_wg, seg_per_xcd, ft
                 if (kSegWaves == 4) hipLaunchKernelGGL((k_raytrace_seg<4, 14>), dim3(seg_blocks), dim3(256), seg_doubles * sizeof(double), ctx->stream, SDX_SEG_ARGS);
                 else hipLaunchKernelGGL((k_raytrace_seg<8, 7>), dim3(seg_blocks), dim3(512), seg_doubles * sizeof(double), ctx->stream, SDX_SEG_ARGS);
 #undef SDX_SEG_ARGS
@@ -2020,8 +2026,7 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
                 fc.cont = ft.cont, fc.cld = ft.cld, fc.source = ft.source, fc.sld = ft.sld;
                 {
                     LaunchScope ls(ctx, "k_raytrace", kSegWaves == 4 ? "k_raytrace_seg<4,14> (continuum)" : "k_raytrace_seg<8,7> (continuum)");
-                    const unsigned seg_blocks = (unsigned)(((n_nu + seg_gpw - 1) / seg_gpw + 7) / 8 * 8);
-#define SDX_SEG_ARGS n_depth, n_nu, nth, n_theta, nus, temps, rd, w, nullptr, 0, Fc, fcld, nullptr, seg_gpw, fc
+#define SDX_SEG_ARGS n_depth, n_nu, nth, n_theta, nus, temps, rd, w, nullptr, 0, Fc, fcld, nullptr, seg_gpw, lane_recip(nth), seg_wg, seg_per_xcd, fc
                     if (kSegWaves == 4) hipLaunchKernelGGL((k_raytrace_seg<4, 14>), dim3(seg_blocks), dim3(256), seg_doubles * sizeof(double), ctx->stream, SDX_SEG_ARGS);
                     else hipLaunchKernelGGL((k_raytrace_seg<8, 7>), dim3(seg_blocks), dim3(512), seg_doubles * sizeof(double), ctx->stream, SDX_SEG_ARGS);
 #undef SDX_SEG_ARGS
