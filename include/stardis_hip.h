@@ -312,6 +312,37 @@ int sdx_raytrace_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const
                      const double* temperature, const double* ray_dist, const double* theta_weights,
                      const double* total_alphas, double* F_nu, double* I_nus);
 
+/* ---- flux contribution function and formation depth ------------------------------------------
+ * WHERE the emergent flux is formed.  The reference has no such output; it follows from its formal solution without a new
+ * model: per ray and gap the step of single_theta_trace_parallel (radiation_field_solvers/base.py:200-266) is the affine map
+ * I[g+1] = c[g] I[g] + e[g], every ray starts at I[0] = 0 (:134), so the emergent intensity is exactly sum_g T[g+1] e[g] with
+ * T[N_d-1] = 1, T[k] = T[k+1] c[k] the transmission from row k to the surface.  With tau[g] = mean_alpha[g] ray_dist[g] (:121-129),
+ * (c, e) the step of the formal-solution kernels themselves (the tau == 0 -> (1, 0) rule of :203-206 and :253-254 included; the
+ * last gap by :253-266) and the flux weights of :324-338:
+ *     C[0][nu] = 0,   C[k][nu] = sum_theta w_theta (T[k] e[k-1])       what the layer below row k adds to F_nu[N_d-1][nu]
+ * (theta in two ascending halves, the lower added to the upper, as F_nu is summed), hence sum_k C[k] = F_nu[N_d-1] up to rounding.
+ * C may be negative in a layer where the second-order scheme overshoots; it is reported as it is.
+ * nus / total_alphas / C hold the n_nu columns being traced (a shard passes its own slice), as for sdx_raytrace_dev; ray_dist
+ * [n_depth-1][n_theta]; source = NULL: Planck, else a plane [n_depth][source_ld] as for sdx_raytrace_source_dev; C [n_depth][C_ld].
+ * Refused with SDX_ERR_ARG before anything is enqueued (also for n_nu = 0, so a caller can ask at set-up time): a context with
+ * mixed_precision = 1, n_theta > 64, a model whose columns do not fit 64 KB of LDS at one frequency per wave.  Plane-parallel
+ * geometry only: the inward sweep of the spherical branch (:141-198) makes I[0] != 0, and there is no argument to ask for it. */
+int sdx_contribution_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                         const double* temperature, const double* ray_dist, const double* theta_weights,
+                         const double* total_alphas, int64_t alpha_ld, const double* source, int64_t source_ld,
+                         double* C, int64_t C_ld);
+/* Formation mean of a per-depth quantity x[n_depth] the caller chooses (geometric depth, temperature, a reference log tau), weighted
+ * by the contribution function above (a decomposition of the flux sum of :324-338):
+ *     out[nu] = (sum_{k>=1} C[k][nu] m_k) / (sum_{k>=1} C[k][nu]),   m_k = (x[k-1] + x[k]) 0.5
+ * both sums over ascending k, every operation one correctly rounded fp64 operation; a zero denominator gives what IEEE gives (NaN). */
+int sdx_formation_mean_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* C, int64_t C_ld, const double* x,
+                           double* out);
+/* host-buffer twin of sdx_contribution_dev (decomposes raytrace :271-346 as above): contiguous arrays, total_alphas / source / C
+ * [n_depth][n_nu]; source = NULL: Planck. */
+int sdx_contribution_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                         const double* temperature, const double* ray_dist, const double* theta_weights,
+                         const double* total_alphas, const double* source, double* C);
+
 /* ---- fused synthesis for resident data (the benchmark path) ---------------------------------
  * total_alphas[d,i] = ((((file + bf) + ff) + rayleigh) + electron) + line   in calc_alphas order
  * (:655-738), then raytrace.  Any source pointer group may be NULL (skipped, contributes nothing).

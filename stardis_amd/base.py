@@ -11,11 +11,14 @@ from stardis_amd.radiation_field.base import create_stellar_radiation_field
 logger = logging.getLogger(__name__)
 
 
-def run_stardis(config_fname, tracing_lambdas_or_nus, add_config_dict=None, *, continuum=False):
+def run_stardis(config_fname, tracing_lambdas_or_nus, add_config_dict=None, *, continuum=False, contribution=False):
     """Same signature and return type as stardis.base.run_stardis.  continuum=True: the same single synthesis also traces the
     continuum, and the output gains spectrum_nu_continuum and spectrum_lambda_continuum (built as STARDISOutput builds
     spectrum_nu / spectrum_lambda, stardis/base.py:133-141) and spectrum_normalized = spectrum_nu / spectrum_nu_continuum —
-    what a second run with opacity.line.disable (and no molecules) would give."""
+    what a second run with opacity.line.disable (and no molecules) would give.
+    contribution=True (plane-parallel models; combines with continuum): the output gains contribution_function (N_d, N_nu), what the
+    layer below each depth point adds to the emergent flux — its sum over depth is spectrum_nu up to rounding
+    (radiation_field_solvers.contribution_function, formation_mean).  A spherical model raises NotImplementedError."""
     try:
         from astropy import units as u
         from stardis.base import STARDISOutput, set_num_threads
@@ -30,13 +33,21 @@ def run_stardis(config_fname, tracing_lambdas_or_nus, add_config_dict=None, *, c
     tracing_nus = tracing_lambdas_or_nus.to(u.Hz, u.spectral())  # wavelengths ascending -> frequencies descending
     config, adata, stellar_model = parse_config_to_model(config_fname, add_config_dict)
     set_num_threads(config.n_threads)  # still governs the plasma stage
+    if contribution and bool(getattr(stellar_model, "spherical", False)):  # (before the plasma and any device work)
+        from stardis_amd.radiation_field.radiation_field_solvers.base import SPHERICAL_CONTRIBUTION
+
+        raise NotImplementedError(SPHERICAL_CONTRIBUTION)
     stellar_plasma = create_stellar_plasma(stellar_model, adata, config)
-    if not continuum:
+    if not continuum and not contribution:
         stellar_radiation_field = create_stellar_radiation_field(tracing_nus, stellar_model, stellar_plasma, config)
         return STARDISOutput(config.result_options, stellar_model, stellar_plasma, stellar_radiation_field)
-    stellar_radiation_field = create_stellar_radiation_field(tracing_nus, stellar_model, stellar_plasma, config, continuum=True)
+    stellar_radiation_field = create_stellar_radiation_field(tracing_nus, stellar_model, stellar_plasma, config, continuum=continuum,
+                                                             contribution=contribution)
     sim = STARDISOutput(config.result_options, stellar_model, stellar_plasma, stellar_radiation_field)
-    _add_continuum_spectra(sim, stellar_radiation_field.F_nu_continuum)
+    if continuum:
+        _add_continuum_spectra(sim, stellar_radiation_field.F_nu_continuum)
+    if contribution:
+        sim.contribution_function = stellar_radiation_field.contribution_function
     return sim
 
 

@@ -4046,6 +4046,139 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
 }
 
 // ------------------------------------------------------------------------------------------------
+// Flux contribution function: WHERE the emergent flux is formed.  The formal solution is, per ray and gap, the affine map
+// I[g+1] = c[g] I[g] + e[g] (rt_coef; radiation_field_solvers/base.py:200-266) and every ray starts at I[0] = 0 (:134), so the emergent
+// intensity is exactly sum_g T[g+1] e[g], T[k] = prod_{j >= k} c[j] the transmission from row k to the surface (T[N_d - 1] = 1).  Summed
+// over the angles with the flux weights (:324-338), the terms are what the layer below row k adds to F_nu[N_d - 1]:
+//     C[0] = 0,   C[k] = sum_theta w_theta (T[k] e[k-1]),   sum_k C[k] = F_nu[N_d - 1] up to rounding.
+// Nothing is modelled anew: (c, e) come from the device functions k_raytrace calls — rt_coef<false> for the inner gaps, rt_coef<true> for the
+// last one, the tau == 0 -> (1, 0) rule and the rare-lane fallback included — on the same tau = (sqrt(alpha[g]) sqrt(alpha[g+1])) ray_dist.
+//
+// The layout of k_raytrace<P>: lane <-> (frequency, angle), a group of G lanes per frequency, (S, sqrt(alpha)) staged per wave in LDS as one
+// 16-byte pair per point, from a FINISHED total_alphas plane.  Each lane walks its ray from the surface INWARDS — the rolling state of
+// k_raytrace mirrored: the optical depth of the gap and of the one above it, the source at the gap's upper end and the two differences, one
+// 16-byte LDS read per step for the point below — carrying only the running product T: the (c, e) of different gaps do not depend on each
+// other, so this is not the 55-step dependent chain of the forward recurrence.  T e w_theta goes to the wave's LDS; every kBatch gaps
+// the wave sums each (gap, frequency) over theta in k_raytrace's order (two ascending halves, the lower added to the upper) and writes row
+// gap + 1 of C.  T underflows to 0 in deep layers: C is 0 there, no special case.  Plane-parallel only (the inward sweep of spherical
+// geometry makes I[0] != 0), all angles in one launch.
+template <int P>
+__global__ __launch_bounds__(kRtBlock) void k_contribution(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
+                                                         const double* __restrict__ nus, const double* __restrict__ temps,
+                                                         const double* __restrict__ ray_dist, const double* __restrict__ wts,
+                                                         const double* __restrict__ alphas, int64_t ald, const double* __restrict__ source,
+                                                         int64_t sld, double* __restrict__ C, int64_t cld, int gpw)
+{
+    constexpr int kBatch = P == 1 ? 4 : 2;
+    extern __shared__ double smem[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int grp = lane / G, g = lane - grp * G;
+    const int TH = P * G;  // theta slots per group, ascending theta = k*G + g
+    const int64_t i0 = ((int64_t)blockIdx.x * (kRtBlock / 64) + wave) * gpw;  // first frequency of this wave
+    const int64_t i = i0 + grp;
+    const bool active = grp < gpw;
+    const bool valid = active && i < n_nu;
+    const int64_t ic = i < n_nu ? i : n_nu - 1;
+    const int n_gap = n_depth - 1;
+    const int col = n_depth;  // LDS row stride per group
+    double* wbase = smem + (size_t)wave * (2 * gpw * col + kBatch * gpw * TH);
+    double2* sP = (double2*)wbase;       // (source function, sqrt(alpha)) [gpw][col]
+    double* sX = wbase + 2 * gpw * col;  // flux terms T e w_theta [kBatch][gpw][TH]
+    const double nu = nus[ic];
+
+    if (active) {
+        for (int d = g; d < n_depth; d += G)
+            sP[grp * col + d] = double2{source ? source[(size_t)d * sld + ic] : planck_staged(nu, temps[d]), sqrt(alphas[(size_t)d * ald + ic])};
+    }
+    if (valid && g == 0) C[i] = 0.0;  // nothing lies below row 0
+    wave_sync();
+    const RtConst kc = rt_const_literals();  // (literals, as in k_raytrace: the gap loop is rolled)
+
+    const int gi = (active ? grp : 0) * col;  // idle lanes shadow group 0 and never store
+    double wt[P], trans[P], tau0[P], tau1[P], rd_next[P];
+    const double* rdp[P];
+    int th[P];
+    // rolling state, for the gap being visited: its optical depth tau0 and that of the gap above tau1 per angle; the source at its upper
+    // end s1, at its lower end s0, the differences d10 = S[gap] - S[gap+1] and d21 = S[gap+2] - S[gap+1]; sqrt(alpha) at its lower end
+    const double2 pt = sP[gi + n_gap], pb = sP[gi + n_gap - 1];
+    double s1 = pt.x, s0 = pb.x, a0 = pb.y;
+    double d10 = s0 - s1, d21 = 0.0;
+    {
+        const double mean = a0 * pt.y;
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            th[k] = min(g + k * G, n_theta - 1);
+            wt[k] = g + k * G < n_theta ? wts[th[k]] : 0.0;
+            trans[k] = 1.0;  // T[N_d - 1]
+            rdp[k] = ray_dist + (size_t)(n_gap - 1) * theta_stride + th[k];
+            tau0[k] = mul_rn(mean, *rdp[k]);
+            tau1[k] = 0.0;
+            rdp[k] -= n_gap > 1 ? theta_stride : 0;
+            rd_next[k] = *rdp[k];  // gap n_gap - 2
+        }
+    }
+    const float inv_gpw = 1.0f / (float)gpw;
+
+    for (int gtop = n_gap - 1; gtop >= 0; gtop -= kBatch) {
+        const int nb = min(kBatch, gtop + 1);
+        for (int b = 0; b < nb; ++b) {
+            const int gap = gtop - b;
+            const double2 pm = sP[gi + max(gap - 1, 0)];  // the point below this gap: what the NEXT step needs, one 16-byte read
+            const double mean_next = pm.y * a0;
+#pragma unroll
+            for (int k = 0; k < P; ++k) {
+                double c, e;
+                if (gap == n_gap - 1) rt_coef<true>(tau0[k], 0.0, d10, 0.0, s1, c, e, kc);  // the final gap (:253-266), visited first
+                else rt_coef<false>(tau0[k], tau1[k], d10, d21, s1, c, e, kc);               // :208-249
+                if (active) sX[(b * gpw + grp) * TH + k * G + g] = (trans[k] * e) * wt[k];
+                trans[k] *= c;  // T[gap]
+                tau1[k] = tau0[k];
+                tau0[k] = mul_rn(mean_next, rd_next[k]);
+                rdp[k] -= gap >= 2 ? theta_stride : 0;
+                rd_next[k] = *rdp[k];  // gap - 2, for the next trip
+            }
+            d21 = -d10, s1 = s0, s0 = pm.x, a0 = pm.y;
+            d10 = s0 - s1;
+        }
+        wave_sync();
+        {
+            // the nb rows of this batch: lanes <-> (gap, frequency, half of the angles), each half summed in ascending theta and the lower
+            // half added to the upper one (k_raytrace's flux sum)
+            const int half = (n_theta + 1) >> 1;
+            for (int p = lane; p < 2 * nb * gpw; p += 64) {
+                const int h = p & 1, q = p >> 1;
+                const int b = (int)(((float)q + 0.5f) * inv_gpw), gq = q - b * gpw;  // q / gpw without an integer division (q < 2^20: exact)
+                const double* t = sX + (b * gpw + gq) * TH + (h ? half : 0);
+                const int cnt = h ? n_theta - half : half;
+                double sum = 0.0;
+                for (int j = 0; j < cnt; ++j) sum = add_rn(sum, t[j]);
+                const double other = __shfl_xor(sum, 1);  // 2 nb gpw is even: the partner lane is in the loop too
+                const int64_t iq = i0 + gq;
+                if (h == 0 && iq < n_nu) C[(size_t)(gtop - b + 1) * cld + iq] = add_rn(sum, other);
+            }
+        }
+        wave_sync();
+    }
+}
+
+// Formation mean of a per-depth quantity x (geometric depth, temperature, a reference log tau): the contribution-weighted mean of its
+// layer values m_k = (x[k-1] + x[k]) 0.5,  <x> = (sum_{k>=1} C[k] m_k) / (sum_{k>=1} C[k]).  One lane per frequency, both sums over ascending
+// k, every operation one correctly rounded fp64 operation; a zero denominator gives what IEEE gives.
+__global__ __launch_bounds__(kBlock) void k_formation_mean(int n_depth, int64_t n_nu, const double* __restrict__ C, int64_t cld,
+                                                           const double* __restrict__ x, double* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_nu) return;
+    double num = 0.0, den = 0.0;
+    for (int k = 1; k < n_depth; ++k) {
+        const double c = C[(size_t)k * cld + i];
+        num = add_rn(num, mul_rn(c, mul_rn(add_rn(x[k - 1], x[k]), 0.5)));
+        den = add_rn(den, c);
+    }
+    out[i] = num / den;
+}
+
+// ------------------------------------------------------------------------------------------------
 // scipy.ndimage.convolve1d(in, w) with the default mode='reflect' (d c b a | a b c d | d c b a), odd kernel, origin 0:
 // what rotation_broadening applies to the spectrum (broadening.py:869-871).  scipy's summation order is kept:
 // for a symmetric kernel  out = in[0] w[c], then pairs (in[-j] + in[+j]) w[c-j] from the OUTERMOST inwards;

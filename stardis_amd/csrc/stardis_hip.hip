@@ -2125,6 +2125,76 @@ int sdx_raytrace_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const
     return io.finish();
 }
 
+// ---- flux contribution function and formation depth (k_contribution, k_formation_mean) ------------------------------------
+// Everything is checked before anything is enqueued — also for an empty grid, so that a caller can ask at set-up time whether this
+// context and shape are served (the engine does).
+int sdx_contribution_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
+                         const double* ray_dist, const double* wts, const double* alphas, int64_t ald, const double* source,
+                         int64_t source_ld, double* C, int64_t cld)
+{
+    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "contribution: need n_depth >= 2, n_theta > 0");
+    REQUIRE(!ctx->mixed_precision, "contribution: no contribution function with mixed_precision = 1 (it decomposes the fp64 formal solution)");
+    REQUIRE(n_theta <= 64, "contribution: more than 64 angles are not supported (all angles are traced in one launch)");
+    constexpr int P = 1, kbatch = 4;
+    const int G = n_theta;
+    auto lds_bytes = [&](int groups) {  // per wave: (S, sqrt(alpha)) pairs, flux terms of a batch of gaps (k_raytrace<1>'s budget)
+        return ((size_t)(kRtBlock / 64) * (2 * (size_t)groups * n_depth + (size_t)kbatch * groups * P * G)) * sizeof(double);
+    };
+    int gpw = 64 / G;  // frequencies per wave; lowered (idle lanes) until the staged columns fit 64 KB of LDS
+    while (gpw > 1 && lds_bytes(gpw) > 64 * 1024) --gpw;
+    const size_t shmem = lds_bytes(gpw);
+    REQUIRE(shmem <= 64 * 1024, "contribution: no contribution function for models this deep (the columns do not fit LDS)");
+    if (n_nu == 0) return SDX_OK;
+    REQUIRE(nus && ray_dist && wts && alphas && ald >= n_nu && C && cld >= n_nu, "contribution: null pointer or leading dimension below n_nu");
+    REQUIRE(source ? source_ld >= n_nu : temps != nullptr, "contribution: bad source plane (source_ld < n_nu), or neither a source plane nor temperatures");
+    const unsigned blocks = (unsigned)((n_nu + (int64_t)gpw * (kRtBlock / 64) - 1) / ((int64_t)gpw * (kRtBlock / 64)));
+    {
+        LaunchScope ls(ctx, "k_contribution", "k_contribution<1>");
+        hipLaunchKernelGGL(k_contribution<1>, dim3(blocks), dim3(kRtBlock), shmem, ctx->stream, n_depth, n_nu, n_theta, n_theta, G, nus, temps, ray_dist,
+                           wts, alphas, ald, source, source_ld, C, cld, gpw);
+    }
+    return check_launch("k_contribution");
+}
+
+int sdx_formation_mean_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* C, int64_t cld, const double* x, double* out)
+{
+    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0, "formation_mean: need n_depth >= 2");
+    if (n_nu == 0) return SDX_OK;
+    REQUIRE(C && cld >= n_nu && x && out, "formation_mean: null pointer or C_ld below n_nu");
+    {
+        LaunchScope ls(ctx, "k_formation_mean");
+        hipLaunchKernelGGL(k_formation_mean, dim3(blocks1(n_nu)), dim3(kBlock), 0, ctx->stream, n_depth, n_nu, C, cld, x, out);
+    }
+    return check_launch("k_formation_mean");
+}
+
+int sdx_contribution_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
+                         const double* ray_dist, const double* wts, const double* alphas, const double* source, double* C)
+{
+    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "contribution: need n_depth >= 2, n_theta > 0");
+    REQUIRE(n_nu == 0 || (nus && temps && ray_dist && wts && alphas && C), "contribution: null pointer");
+    int rc;
+    if (n_nu == 0) return sdx_contribution_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0);
+    if ((rc = sdx_contribution_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0))) return rc;  // refusals before any copy
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
+    const size_t in_bytes[] = {(size_t)n_nu * f8, (size_t)n_depth * f8, (size_t)(n_depth - 1) * n_theta * f8, (size_t)n_theta * f8, plane, source ? plane : 0};
+    size_t dev_need = 256 + HostIo::pad(plane), pin_need = HostIo::pad(plane) + 256;
+    for (size_t b : in_bytes) dev_need += HostIo::pad(b), pin_need += HostIo::pad(b);
+    HostIo io{ctx};
+    if ((rc = io.begin(dev_need, pin_need))) return rc;
+    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_s = nullptr;
+    if ((rc = io.upload(nus, in_bytes[0], (const void**)&d_nus)) || (rc = io.upload(temps, in_bytes[1], (const void**)&d_t)) ||
+        (rc = io.upload(ray_dist, in_bytes[2], (const void**)&d_rd)) || (rc = io.upload(wts, in_bytes[3], (const void**)&d_w)) ||
+        (rc = io.upload(alphas, in_bytes[4], (const void**)&d_a)) || (source && (rc = io.upload(source, in_bytes[5], (const void**)&d_s))))
+        return rc;
+    double* d_c = (double*)io.alloc(plane);
+    rc = sdx_contribution_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_s, n_nu, d_c, n_nu);
+    if (rc) return rc;
+    if ((rc = io.download(C, d_c, plane))) return rc;
+    return io.finish();
+}
+
 // ================================================================================================ post-processing
 int sdx_convolve1d_reflect_dev(sdx_ctx* ctx, int64_t n, const double* in, int m, const double* weights, int symmetric, double* out)
 {

@@ -39,7 +39,7 @@ def _require_f64_buffer(name, buf, n_min):
 class SpectralSynthesizer:
     def __init__(self, nus, temperatures, dist, thetas, theta_weights, lines, continuum=None, ctx=None, shard=None,
                  flux_out=None, track_evaluations=True, keep_line=True, keep_total=True, classify_share=None, m_max=None, m_share_out=None,
-                 keep_continuum_flux=False):
+                 keep_continuum_flux=False, keep_contribution=False):
         """nus: global grid (descending).  lines: dict(line_nus, doppler_widths, gammas, alphas) in the
         reference layout (N_l, N_d), or a stardis_amd.linelist.LineList (per-line scalars; the pre-pass generates the
         three values per (line, depth) itself).  continuum: dict as produced by synth.synth_continuum_state or None.
@@ -52,7 +52,11 @@ class SpectralSynthesizer:
         default: they are written in place, m_max[first line ...]).
         A step is then enqueue_classify() [-> the caller's all-gather of m_max] -> enqueue().
         keep_continuum_flux: also trace the continuum flux (N_d, count) in the same formal solution (sdx_synthesis_options.
-        F_nu_continuum): F_nu of the same step without lines, bit for bit (F_nu_continuum(), emergent_continuum())."""
+        F_nu_continuum): F_nu of the same step without lines, bit for bit (F_nu_continuum(), emergent_continuum()).
+        keep_contribution: after the synthesis, every step also forms the flux contribution function C (N_d, count) of its own columns
+        from the step's total_alphas (sdx_contribution_dev; implies keep_total): what the layer below row k adds to the emergent flux,
+        sum_k C[k] = F_nu[-1] up to rounding (`contribution`, `formation_mean(x)`).  Plane-parallel, fp64, at most 64 angles: a context
+        with mixed_precision = 1 or more angles are refused here.  Off, the step is unchanged."""
         self.ctx = ctx or default_context()
         c = self.ctx
         nus = np.ascontiguousarray(nus, dtype=np.float64)
@@ -103,6 +107,11 @@ class SpectralSynthesizer:
         self.cont = self._build_continuum(continuum, nus, t)
 
         # optional output planes: allocated only when asked for (0.5 GB each at 1.2e6 frequencies)
+        self.keep_contribution = bool(keep_contribution)
+        if self.keep_contribution:
+            # the library's own refusals (mixed precision, angles, depth), asked with an empty grid: nothing is enqueued
+            c.call("sdx_contribution_dev", self.n_depth, 0, self.n_theta, None, None, None, None, None, 0, None, 0, None, 0)
+            keep_total = True
         self.d_line = c.empty((self.n_depth, self.count)) if keep_line else None
         self.d_total = c.empty((self.n_depth, self.count)) if keep_total else None
         self._flux_tensor = flux_out
@@ -110,6 +119,7 @@ class SpectralSynthesizer:
         self.d_evals = c.zeros((1,), np.int64) if track_evaluations else None
         self.keep_continuum_flux = bool(keep_continuum_flux)
         self.d_Fc = c.empty((self.n_depth, self.count)) if self.keep_continuum_flux else None
+        self.d_C = c.empty((self.n_depth, self.count)) if self.keep_contribution else None
         self._keep_line = keep_line  # also write the summed line opacity plane (alpha_line())
         self._keep_total = keep_total  # also write total_alphas (the reference keeps it on Opacities; the flux does not need it in HBM)
         self.count_evaluations = track_evaluations  # sum(hi - lo) per step costs a memset + copy: switch off when timing
@@ -176,6 +186,8 @@ class SpectralSynthesizer:
 
     @keep_total.setter
     def keep_total(self, on):
+        if not on and self.keep_contribution:
+            raise ValueError("keep_contribution reads the step's total_alphas: keep_total stays on")
         if on and self.d_total is None:
             self.d_total = self.ctx.empty((self.n_depth, self.count))
         self._keep_total = bool(on)
@@ -200,7 +212,18 @@ class SpectralSynthesizer:
                self.d_dw.ptr, self.d_g.ptr, self.gamma_cols, self.d_a.ptr, C.byref(self.cont), int(b), int(n), base)
 
     def enqueue(self):
-        """One fused step on the context's stream: sdx_synthesize_dev (pre-pass, line gather, total, raytrace)."""
+        """One fused step on the context's stream: sdx_synthesize_dev (pre-pass, line gather, total, raytrace); with
+        keep_contribution, sdx_contribution_dev on the step's total_alphas behind it."""
+        self._enqueue_synthesis()
+        if self.keep_contribution:
+            self._enqueue_contribution()
+
+    def _enqueue_contribution(self):
+        cnt = self.count
+        self.ctx.call("sdx_contribution_dev", self.n_depth, cnt, self.n_theta, self.d_nus.ptr + 8 * self.begin, self.d_t.ptr, self.d_ray.ptr,
+                      self.d_w.ptr, self.d_total.ptr, cnt, None, 0, self.d_C.ptr, cnt)
+
+    def _enqueue_synthesis(self):
         c = self.ctx
         if self.keep_continuum_flux:
             self._enqueue_opt()
@@ -261,6 +284,8 @@ class SpectralSynthesizer:
         nus_shard = self.d_nus.ptr + 8 * self.begin
         c.call("sdx_raytrace_dev", nd, cnt, self.n_theta, nus_shard, self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr,
                self.d_total.ptr, cnt, self.flux_ptr, cnt, None, 0)
+        if self.keep_contribution:
+            self._enqueue_contribution()
 
     def capture(self, eager_phase2=True, batch=1):
         """Record one step into a hipGraph (after one eager step has sized the scratch).  batch > 1: ALSO a graph of `batch` consecutive
@@ -362,6 +387,30 @@ class SpectralSynthesizer:
     def emergent_continuum(self):
         """-> (count,) numpy array: the continuum flux of the outermost depth point, F_nu_continuum[-1]."""
         return self.F_nu_continuum[-1]
+
+    @property
+    def contribution(self):
+        """-> DeviceArray (N_d, count): the flux contribution function of the last step (`.numpy()` for a host array)."""
+        if not self.keep_contribution:
+            raise RuntimeError("the contribution function was not kept: construct the synthesizer with keep_contribution=True")
+        return self.d_C
+
+    def formation_mean(self, x):
+        """-> DeviceArray (count,): the formation mean of a per-depth quantity x (N_d values; host array, DeviceArray or CUDA tensor)
+        under the last step's contribution function (sdx_formation_mean_dev)."""
+        c = self.ctx
+        d_C = self.contribution
+        if isinstance(x, _lib.DeviceArray) or hasattr(x, "data_ptr"):
+            _require_f64_buffer("x", x, self.n_depth)
+            d_x = x
+        else:
+            host = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+            if host.size != self.n_depth:
+                raise ValueError(f"x must hold one value per depth point ({self.n_depth}), got {host.size}")
+            d_x = c.upload(host)
+        out = c.empty((self.count,))
+        c.call("sdx_formation_mean_dev", self.n_depth, self.count, d_C.ptr, self.count, ptr_of(d_x), out.ptr)
+        return out
 
     def total_alphas(self):
         if not self.keep_total:

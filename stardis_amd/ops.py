@@ -356,3 +356,41 @@ def raytrace_arrays(tracing_nus, temperatures, ray_distances, theta_weights, tot
     else:
         ctx.call("sdx_raytrace_dev", *args)
     return (d_F.numpy() if want_flux else None), (d_I.numpy() if track else None)
+
+
+def contribution_arrays(tracing_nus, temperatures, ray_distances, theta_weights, total_alphas, ctx=None, source=None, device=False):
+    """Flux contribution function C (N_d, N_nu) of the plane-parallel formal solution (sdx_contribution_dev): what the layer below
+    row k adds to the emergent flux, sum_k C[k] = F_nu[-1] up to rounding.  Arguments as raytrace_arrays (ray_distances is the
+    (N_d-1, N_theta) table of radiation_field_solvers/base.py:302-305; total_alphas a host or device array; source an optional
+    (N_d, N_nu) source-function plane).  device=True: the DeviceArray instead of a host array."""
+    ctx = ctx or default_context()
+    nus = _host(tracing_nus).reshape(-1)
+    t = _host(temperatures).reshape(-1)
+    rd = _host(ray_distances).reshape(t.size - 1, -1)
+    w = _host(theta_weights).reshape(-1)
+    d_alpha = _dev(ctx, total_alphas)
+    d_S = None
+    if source is not None:
+        src = _host(source)
+        if src.shape != (t.size, nus.size):
+            raise ValueError(f"source function must return shape {(t.size, nus.size)}, got {src.shape}")
+        d_S = ctx.upload(src)
+    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd), ctx.upload(w)]
+    d_C = ctx.empty((t.size, nus.size))
+    ctx.call("sdx_contribution_dev", t.size, nus.size, w.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, ptr_of(d_alpha), nus.size,
+             ptr_of(d_S), nus.size, d_C.ptr, nus.size)
+    return d_C if device else d_C.numpy()
+
+
+def formation_mean(contribution, x, ctx=None, device=False):
+    """Formation mean of a per-depth quantity x (N_d) under a contribution function (N_d, N_nu; host or device array):
+    (sum_{k>=1} C[k] m_k) / (sum_{k>=1} C[k]), m_k = (x[k-1] + x[k]) / 2 (sdx_formation_mean_dev) -> (N_nu,)."""
+    ctx = ctx or default_context()
+    d_C = _dev(ctx, contribution)
+    n_depth, n_nu = (int(s) for s in d_C.shape)
+    d_x = _dev(ctx, x)
+    if int(np.prod(d_x.shape)) != n_depth:
+        raise ValueError(f"x must hold one value per depth point ({n_depth}), got shape {tuple(d_x.shape)}")
+    d_out = ctx.empty((n_nu,))
+    ctx.call("sdx_formation_mean_dev", n_depth, n_nu, ptr_of(d_C), n_nu, ptr_of(d_x), d_out.ptr)
+    return d_out if device else d_out.numpy()

@@ -6,7 +6,8 @@ import numpy as np
 
 from stardis_amd.radiation_field.opacities import Opacities
 from stardis_amd.radiation_field.opacities.opacities_solvers import calc_alphas
-from stardis_amd.radiation_field.radiation_field_solvers import continuum_flux, raytrace
+from stardis_amd.radiation_field.radiation_field_solvers import continuum_flux, contribution_function, raytrace
+from stardis_amd.radiation_field.radiation_field_solvers.base import SPHERICAL_CONTRIBUTION
 from stardis_amd.radiation_field.source_functions.blackbody import blackbody_flux_at_nu
 
 logger = logging.getLogger(__name__)
@@ -41,16 +42,21 @@ class RadiationField(_Base):
 FUSED = os.environ.get("STARDIS_AMD_FUSED", "1") != "0"  # one fused device pass when the configuration allows it
 
 
-def create_stellar_radiation_field(tracing_nus, stellar_model, stellar_plasma, config, *, continuum=False):
+def create_stellar_radiation_field(tracing_nus, stellar_model, stellar_plasma, config, *, continuum=False, contribution=False):
     """Opacities then formal solution, as the reference's driver (:71-117).  Configurations the fused synthesis covers run
     as ONE device pass with lazily materialised dictionary entries (stardis_amd/radiation_field/fused.py); everything else —
     and STARDIS_AMD_FUSED=0 — takes the source-by-source path below.  Both produce the same numbers.
     continuum=True: the field also gets F_nu_continuum (N_d, N_nu), the formal solution of the continuum alone — F_nu of the same
-    configuration with opacity.line.disable = True and include_molecules = False, bit for bit."""
+    configuration with opacity.line.disable = True and include_molecules = False, bit for bit.
+    contribution=True: the field also gets contribution_function (N_d, N_nu), what the layer below each depth point adds to the emergent
+    flux (sum over depth = F_nu[-1] up to rounding; radiation_field_solvers.contribution_function).  Plane-parallel models only."""
+    if contribution and bool(getattr(stellar_model, "spherical", False)):
+        raise NotImplementedError(SPHERICAL_CONTRIBUTION)
     if FUSED:
         from stardis_amd.radiation_field.fused import try_fused
 
-        field = try_fused(RadiationField, tracing_nus, stellar_model, stellar_plasma, config, blackbody_flux_at_nu, continuum=continuum)
+        field = try_fused(RadiationField, tracing_nus, stellar_model, stellar_plasma, config, blackbody_flux_at_nu, continuum=continuum,
+                          contribution=contribution)
         if field is not None:
             logger.info("Radiation field computed by the fused synthesis")
             return field
@@ -70,4 +76,6 @@ def create_stellar_radiation_field(tracing_nus, stellar_model, stellar_plasma, c
         from stardis_amd._lib import default_context
 
         field.F_nu_continuum = continuum_flux(stellar_model, field, field.opacities.continuum_alphas_device(default_context()))
+    if contribution:
+        field.contribution_function = contribution_function(stellar_model, field)
     return field

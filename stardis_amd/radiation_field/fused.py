@@ -53,14 +53,16 @@ MEMO_MAX_BYTES = 2 << 30  # ... and at most this much derived data (numpy arrays
 DEVICE_BUDGET_BYTES = 8 << 30  # device memory the lazy entries of live fused fields may hold per process (fused_lazy)
 
 
-def try_fused(field_cls, tracing_nus, stellar_model, stellar_plasma, config, source_function, continuum=False):
+def try_fused(field_cls, tracing_nus, stellar_model, stellar_plasma, config, source_function, continuum=False, contribution=False):
     """-> RadiationField computed by one fused device pass, or None when the configuration needs the general path.
-    continuum: also trace the continuum flux in the same step (field.F_nu_continuum, sdx_synthesis_options.F_nu_continuum)."""
+    continuum: also trace the continuum flux in the same step (field.F_nu_continuum, sdx_synthesis_options.F_nu_continuum).
+    contribution: also form the flux contribution function from the step's total_alphas (field.contribution_function,
+    sdx_contribution_dev; plane-parallel models)."""
     with one_call():  # (witnesses are per call and per thread: the tables may be edited before the next one)
-        return _try_fused(field_cls, tracing_nus, stellar_model, stellar_plasma, config, source_function, continuum)
+        return _try_fused(field_cls, tracing_nus, stellar_model, stellar_plasma, config, source_function, continuum, contribution)
 
 
-def _try_fused(field_cls, tracing_nus, stellar_model, stellar_plasma, config, source_function, continuum=False):
+def _try_fused(field_cls, tracing_nus, stellar_model, stellar_plasma, config, source_function, continuum=False, contribution=False):
     opacity = config.opacity
     spherical = bool(getattr(stellar_model, "spherical", False))
     tracked = bool(config.result_options.return_radiation_field)
@@ -230,7 +232,7 @@ def _run_step(v):
                        "n_e", "line", "line_spec", "mol", "mol_spec", "n_lines", "n_mol", "opacity", "config", "stellar_plasma", "stellar_model",
                        "tracked", "spherical", "correction", "source", "rayleigh_species", "ff_ions"))
     P = lambda name: ptrs[slot[name]] if name in slot else None  # noqa: E731
-    continuum = bool(v["continuum"])
+    continuum, contribution = bool(v["continuum"]), bool(v["contribution"])
 
     file_planes = []
     for source, fpath, tab in plane_sources:
@@ -310,6 +312,11 @@ def _run_step(v):
         ctx.call("sdx_synthesize_ex_dev", *step, P("source"), nus.size, field._I_dev.ptr if tracked else None, None)
     else:
         ctx.call("sdx_synthesize_dev", *step, None)
+    d_C = None
+    if contribution:  # the decomposition of the emergent flux by layer, from the total opacity and source function the step traced
+        d_C = ctx.empty((nd, nus.size))
+        ctx.call("sdx_contribution_dev", nd, nus.size, int(config.no_of_thetas), P("nus"), P("temps"), P("ray"), P("wts"), d_total.ptr, nus.size,
+                 P("source"), nus.size, d_C.ptr, nus.size)
     # F_nu lands in page-locked memory by DMA (no bounce buffer, no second copy); the block returns to the context's pool when
     # the last reference to the array is gone
     field.F_nu = ctx.pinned.empty((nd, nus.size))
@@ -320,6 +327,8 @@ def _run_step(v):
         ctx.call("sdx_memcpy_d2h", field.F_nu.ctypes.data, d_F.ptr, field.F_nu.nbytes)
     if continuum:
         field.F_nu_continuum = d_Fc.numpy()
+    if contribution:
+        field.contribution_function = d_C.numpy()
     blob._staging = None  # (the download above synchronised: the staging block may go back to the pool)
     opac._total_twin = d_total
     field._device_blob = (blob, file_planes)  # keeps the staged inputs alive as long as the lazy entries may need them

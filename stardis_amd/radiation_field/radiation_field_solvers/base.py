@@ -105,3 +105,36 @@ def continuum_flux(stellar_model, stellar_radiation_field, continuum_alphas):
     )
     return F
 
+
+
+SPHERICAL_CONTRIBUTION = ("the flux contribution function is defined for plane-parallel models: the inward sweep of the spherical formal "
+                          "solution makes the intensity at the innermost point non-zero, and the emergent flux is then not a sum over layers alone")
+
+
+def contribution_function(stellar_model, stellar_radiation_field):
+    """Flux contribution function (N_d, N_nu) of the field's formal solution: row k is what the layer below depth point k adds to the
+    emergent flux, sum over k = F_nu[-1] up to rounding (row 0 is 0; sdx_contribution_dev).  The same angles, weights, source function,
+    geometry and total opacity as raytrace() above; the reference has no counterpart.  A spherical model raises NotImplementedError."""
+    field = stellar_radiation_field
+    if bool(getattr(stellar_model, "spherical", False)):
+        raise NotImplementedError(SPHERICAL_CONTRIBUTION)
+    thetas = np.asarray(field.thetas, dtype=np.float64)
+    dist = np.asarray(plain(stellar_model.geometry.dist_to_next_depth_point), dtype=np.float64)
+    ray_distances = dist.reshape(-1, 1) / np.cos(thetas)  # :302-305
+    ctx = default_context()
+    opac = field.opacities
+    alphas = opac.total_alphas_device(ctx) if hasattr(opac, "total_alphas_device") else opac.total_alphas
+    return ops.contribution_arrays(
+        field.frequencies, plain(stellar_model.temperatures), ray_distances, field.I_nus_weights, alphas, ctx=ctx,
+        source=_source_plane(getattr(field, "source_function", None), field.frequencies, stellar_model.temperatures),
+    )
+
+
+def formation_mean(stellar_radiation_field, x):
+    """Formation mean (N_nu,) of a per-depth quantity x (N_d: geometric depth, temperature, a reference log tau) under the field's
+    contribution function: (sum_{k>=1} C[k] m_k) / (sum_{k>=1} C[k]), m_k = (x[k-1] + x[k]) / 2 (sdx_formation_mean_dev).  The field must
+    carry contribution_function (create_stellar_radiation_field(..., contribution=True), or assign contribution_function()'s result)."""
+    C = getattr(stellar_radiation_field, "contribution_function", None)
+    if C is None:
+        raise ValueError("the field carries no contribution_function: create it with contribution=True")
+    return ops.formation_mean(C, np.asarray(plain(x), dtype=np.float64).reshape(-1))
