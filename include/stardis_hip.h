@@ -124,7 +124,17 @@ int sdx_synchronize(sdx_ctx* ctx);
  *       the caller's doppler widths, gammas and alphas — the same three operations, so the results are bit-identical — and the pre-pass
  *       writes one byte per item (long dense fp64 lists only: lists of at least "indexed_min_lines" lines, no line-list scalars, no
  *       "mixed_precision"); -1: 0 for lists of at least four lines per grid point (1e6 lines: 1.35 GB less traffic and scratch per
- *       synthesis, the step 0.5 % faster), 1 otherwise (1.5e5 lines: the step is 0.4 % slower without the records). */
+ *       synthesis, the step 0.5 % faster), 1 otherwise (1.5e5 lines: the step is 0.4 % slower without the records).
+ *   "wide_list" (default -1): how the wide role of the line kernel finds its candidates in a SHORT list (fewer than "indexed_min_lines"
+ *       lines; long lists have the list launches).  0: every tile tests every line of its line subset, 64 per round trip.  1: the last
+ *       line block of the pre-pass launch to finish lists the lines that have a wide window (half-width > 64 grid points) at any depth,
+ *       one ascending list per line subset, and a tile tests those alone — the lines it would have met as possible hits, in the same
+ *       order: the same hits, the same sums, bit-identical results (tests/test_gpu_wide_list.py).  No further launch; the list is built
+ *       for dense tables and line-list inputs, whole grids and frequency shards.  The fp32-mixed mode keeps the full scan whatever the
+ *       option says (its fp32 partial sums are flushed at chunk boundaries, which a compacted list would move).  -1: 1 for lists of at
+ *       least 16 chunks of 64 lines per line subset (2000 lines on 7634 points, two subsets: the line kernel 1.2 us faster, the list
+ *       built in the shadow of the launch's continuum tiles), 0 below (2000 lines on 1000 points, eight subsets: nothing gained and 3 us
+ *       more at the end of the pre-pass launch). */
 int sdx_set_int_option(sdx_ctx* ctx, const char* name, int64_t value);
 /* The far-field rule as the library applies it — for planners that weigh shards (stardis_amd.parallel.column_cost) and must not
  * carry constants of their own.  sdx_far_field_active: 1 when a synthesis of a GLOBAL grid of n_nu_global points on this context runs

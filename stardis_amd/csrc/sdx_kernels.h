@@ -308,7 +308,7 @@ struct LineWork {
     int* nhw_max;    // [N_l] largest NARROW half-width of the line over all depths (0: no narrow item)
     int* whw_max;    // [N_l] largest WIDE half-width of the line over all depths (0: no wide item)
     // long line lists: ascending indices of the lines whose widest window exceeds kMediumHalfWidth (they may reach any tile and
-    // are scanned completely; all other lines are found by centre range).  nullptr for short lists (every line is scanned).
+    // are scanned completely; all other lines are found by centre range).  nullptr for short lists (every line is scanned, or — n_csplit, below — every line with a wide window somewhere).
     int* hlist;
     int* hcount;     // [0] entries of hlist, [1] entries of wlist, [2] entries of xlist
     // frequency shards of long lists: the lines with a wide window whose centre lies within kMediumHalfWidth of the shard's
@@ -337,6 +337,14 @@ struct LineWork {
     unsigned long long* evals;
     int* ticket;  // culled runs: the pre-pass launch's work counter, one per depth block (zeroed by k_hlist_count), or nullptr
     int front;    // culled runs: the blocks with work are the FIRST blocks of the pre-pass grid (k_line_prepass maps its block index)
+    // SHORT lists (no hlist), full pre-pass, n_csplit > 0: the lines with a wide window at any depth (whw_max > 0), ascending, one
+    // list per line subset s < n_csplit of the wide role (chunk q of 64 consecutive line indices belongs to subset q % n_csplit) — the
+    // set and the order in which subset s meets its possible hits when it scans every line.  The lists lie one behind the other where
+    // long lists keep hlist (wide_list_of), their entries and offsets where the list launches keep their block counts
+    // (wide_list_counts: [s] entries, [8 + s] offset).  Written by the LAST line block of the pre-pass launch to finish
+    // (compact_wide_lines); `ticket` then counts the finished line blocks and is left at zero.  0: the wide role scans the whole list.
+    // (no pointers of their own: a larger LineWork made every launch that takes one slower, list or no list)
+    int n_csplit;
     // far field (k_line_far): the (line, depth, tile) triples that far_eligible() accepts are left to k_line_far — the wide role
     // skips them — and their sum reaches the grid through the tile's 16 Chebyshev nodes (a third plane).
     // far_range[2 T], [2 T + 1] (k_far_ranges): a line is far from global tile T when its centre index is < the first or > the second
@@ -344,12 +352,62 @@ struct LineWork {
     const int* far_range;
 };
 
+__device__ __forceinline__ int* wide_list_of(const LineWork& w, int64_t n_lines) { return w.whw_max + n_lines; }
+__device__ __forceinline__ int* wide_list_counts(const LineWork& w) { return w.hcount + 16; }
+
 // k / d for 0 <= k < 65536 and 1 <= d < 65536 with the divisor's reciprocal m = small_div_magic(d) = ceil(2^32 / d): one multiply-high
 // instead of the ~30 instructions of a 32-bit division by a run-time value (the pre-pass indexes its (line, depth) items six times)
 __device__ __forceinline__ unsigned small_div_magic(int d) { return d > 1 ? 0xFFFFFFFFu / (unsigned)d + 1u : 0u; }
 __device__ __forceinline__ int small_div(int k, unsigned magic) { return magic ? (int)__umulhi((unsigned)k, magic) : k; }
 
-template <bool GEN, int kPreLines>
+// Short lists: the wide role's candidates, compacted per line subset (LineWork::n_csplit).  Run by ONE block, the last line block of
+// the pre-pass launch to finish, behind the agent-scope acquire of its ticket: whw_max is complete.  Chunk q (the 64 lines a wave
+// reads with one load) belongs to subset q % n_split; its wide lines go, in ascending order, behind those of the subset's earlier
+// chunks.  The masks of all chunks meet in LDS (the grid sample's 16 KB, free by now): one load per line, two barriers.
+constexpr int kListMaxChunks = kGridSample - 8;  // 64-bit masks in the sample's array, the subset totals behind them
+__device__ __forceinline__ void compact_wide_lines(const LineWork& w, const int64_t n_lines, unsigned long long* __restrict__ s_mask, const int tid)
+{
+    const int n_split = w.n_csplit;
+    const int n_chunks = (int)((n_lines + 63) >> 6);
+    const int wave = tid >> 6, lane = tid & 63;
+    int* const s_tot = reinterpret_cast<int*>(s_mask + kListMaxChunks);
+    int* const clist = wide_list_of(w, n_lines);
+    int* const ccount = wide_list_counts(w);
+    for (int q = wave; q < n_chunks; q += kPreBlock / 64) {
+        const int64_t l = (int64_t)q * 64 + lane;
+        const unsigned long long m = __ballot(l < n_lines && w.whw_max[l] > 0);
+        if (lane == 0) s_mask[q] = m;
+    }
+    __syncthreads();
+    // wide lines of subset s in the chunks below q (lanes share the subset's earlier chunks)
+    auto below = [&](int s, int q) {
+        int c = 0;
+        for (int j = lane; s + j * n_split < q; j += 64) c += __popcll(s_mask[s + j * n_split]);
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+        return c;
+    };
+    if (wave < n_split) {
+        const int t = below(wave, n_chunks);
+        if (lane == 0) s_tot[wave] = t;
+    }
+    __syncthreads();
+    for (int q = wave; q < n_chunks; q += kPreBlock / 64) {
+        const int s = q % n_split;
+        int base = below(s, q);
+        for (int k = 0; k < s; ++k) base += s_tot[k];
+        const unsigned long long m = s_mask[q];
+        if ((m >> lane) & 1)
+            clist[base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = q * 64 + lane;
+    }
+    if (tid < n_split) {
+        int off = 0;
+        for (int k = 0; k < tid; ++k) off += s_tot[k];
+        ccount[tid] = s_tot[tid];
+        ccount[8 + tid] = off;
+    }
+}
+
+template <bool GEN, int kPreLines, bool LIST = true>
 __device__ __forceinline__ void prepass_block(const int bx, const int by, const int gy, int n_depth, int64_t n_nu, const double* __restrict__ nus,
                                                          const double* __restrict__ dnu_partial, int n_partial,
                                                          int64_t n_lines, const double* __restrict__ line_nus,
@@ -661,8 +719,12 @@ __device__ __forceinline__ void prepass_block(const int bx, const int by, const 
     }
     // per-line summary for the narrow kernel's candidate test: centre index and the largest narrow half-width
     if (w.nhw_max && tid < nl) {
-        if (gy == 1) w.nhw_max[SDX_LINE_OF(tid)] = s_hwmax[tid], w.whw_max[SDX_LINE_OF(tid)] = s_whwmax[tid];
-        else {  // deep models: several depth blocks per line, both arrays zeroed by the host first
+        if (gy == 1) {
+            w.nhw_max[SDX_LINE_OF(tid)] = s_hwmax[tid];
+            // (write-through where the block that lists the wide lines reads it in this launch)
+            if (LIST && kPreLines <= 32 && w.n_csplit) __hip_atomic_store(&w.whw_max[SDX_LINE_OF(tid)], s_whwmax[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else w.whw_max[SDX_LINE_OF(tid)] = s_whwmax[tid];
+        } else {  // deep models: several depth blocks per line, both arrays zeroed by the host first
             atomicMax(&w.nhw_max[SDX_LINE_OF(tid)], s_hwmax[tid]);
             atomicMax(&w.whw_max[SDX_LINE_OF(tid)], s_whwmax[tid]);
         }
@@ -682,6 +744,28 @@ __device__ __forceinline__ void prepass_block(const int bx, const int by, const 
                 if (ev) atomicAdd(w.evals, ev);
             }
         }
+    }
+    // Short lists: the LAST line block to finish lists the lines with a wide window for the wide role (LineWork::n_csplit) — in this
+    // launch, and no block waits for another.  whw_max went out write-through (an atomic store / atomicMax at the L2); every storing
+    // wave drains its stores, ONE lane draws the block's ticket, and in the block that drew the last one that lane's agent-scope
+    // acquire precedes the block's (vector) loads of whw_max.  The launch boundary publishes the list to the line kernel.
+    // (short lists run 16 or 32 lines per block, never the counter-driven launch)
+    if constexpr (LIST && kPreLines <= 32) if (w.n_csplit) {  // (block-uniform)
+        __shared__ int s_last;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0) {
+            const int t = __hip_atomic_fetch_add(w.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int last = t == n_line_blocks * gy - 1 ? 1 : 0;
+            if (last) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __hip_atomic_store(w.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the next step counts from zero
+            }
+            s_last = last;
+        }
+        __syncthreads();
+        if (s_last) compact_wide_lines(w, n_lines, reinterpret_cast<unsigned long long*>(s_coarse), tid);
     }
 #ifdef SDX_PRE_STATS
     if (tid == 0) {
@@ -753,7 +837,7 @@ __global__ __launch_bounds__(kPreBlock) __attribute__((amdgpu_num_sgpr(80), amdg
         // (the long items first, the pixel blocks — a binary search per thread — last: they fill the launch's tail)
         const int n_long = total - w.n_pix;
         const int bx = item < n_range ? first + item : (item < n_long ? n_line_blocks + w.n_pix + (item - n_range) : n_line_blocks + (item - n_long));
-        prepass_block<false, LINES>(bx, blockIdx.y, gridDim.y, n_depth, n_nu, nus, dnu_partial, n_partial, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, w,
+        prepass_block<false, LINES, false>(bx, blockIdx.y, gridDim.y, n_depth, n_nu, nus, dnu_partial, n_partial, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, w,
                                     nullptr, nullptr, n_line_blocks, lp, tid);
     }
 }
@@ -885,7 +969,9 @@ __device__ __forceinline__ float2v region1_f32x2(float2v acc, float2v dq, float 
 // DEFER: the partial sums of this wave are handed back (acc_out) instead of being reduced and stored here — the kernel of dense
 // long lists has ONE reduction for both roles (line_all_body)
 // STAGED (fp32-mixed mode, the kernel of very dense lists): the records of a chunk's hits reach the lanes through LDS (below)
-template <int R, bool MIXED, bool DEFER = false, bool STAGED = false, bool FAR = false>
+// LISTED (fp64, short lists): the candidates are this subset's list of wide lines (LineWork::n_csplit) — a kernel of its own
+// (k_line_listed), so that the kernels that scan compile to what they were
+template <int R, bool MIXED, bool DEFER = false, bool STAGED = false, bool FAR = false, bool LISTED = false>
 __device__ __forceinline__ void line_wide_walk(const int tile_idx, const int split, const int n_split, const int d, int64_t n_nu,
                                                const double* __restrict__ nus, int64_t nu_begin, int64_t nu_count, int64_t n_lines,
                                                LineWork w, double* __restrict__ plane, int64_t pld, double* __restrict__ lds_all,
@@ -1026,8 +1112,18 @@ __device__ __forceinline__ void line_wide_walk(const int tile_idx, const int spl
     for (int pass = w.hlist ? 0 : 1; pass < 2; ++pass) {
         // candidate positions [ka, kb) of this pass: hlist positions (pass 0); wlist positions or — short lists — line indices (pass 1)
         int ka = 0, kb = n_h;
+        // short lists with a compacted candidate list: this subset's own list, chunk after chunk — the lines it would meet as
+        // possible hits scanning every chunk q = split (mod n_split) of the whole list, in the same order
+        const int* clist_s = nullptr;
+        int q_step = n_split;
         if (pass == 1) {
             kb = (int)n_lines;
+            if constexpr (LISTED && !MIXED) if (!w.hlist && w.n_csplit) {
+                const int* const ccount = wide_list_counts(w);
+                kb = __builtin_amdgcn_readfirstlane(ccount[split]);
+                clist_s = wide_list_of(w, n_lines) + __builtin_amdgcn_readfirstlane(ccount[8 + split]);
+                q_step = 1;
+            }
             if (w.hlist) {  // lines whose centre c satisfies t0 - H < c < t1 + H: line indices [la, lb), wlist positions [wrank[la], wrank[lb])
                 const int64_t pa = max(t0 - kMediumHalfWidth + 1, (int64_t)0), pb = min(t1 + kMediumHalfWidth - 1, n_nu);
                 ka = __builtin_amdgcn_readfirstlane(w.wrank[w.cnt_ge[pb + 1]]);
@@ -1044,7 +1140,7 @@ __device__ __forceinline__ void line_wide_walk(const int tile_idx, const int spl
         }
         if (kb <= ka) continue;
         const int q_first = ka >> 6, q_last = (kb - 1) >> 6;
-        int q = q_first + ((split - q_first % n_split) + n_split) % n_split;  // first chunk >= q_first of this subset
+        int q = clist_s ? 0 : q_first + ((split - q_first % n_split) + n_split) % n_split;  // first chunk >= q_first of this subset
         // the scan word of the NEXT chunk is requested behind the current chunk's arithmetic
         auto fetch = [&](int qq, int& line, WideScan& sc) {
             const int k = qq * 64 + lane;
@@ -1055,7 +1151,7 @@ __device__ __forceinline__ void line_wide_walk(const int tile_idx, const int spl
                     line = w.hlist[k];
                     sc = w.hscan ? hscan_row[k] : scan_row[line];
                 } else {
-                    line = w.hlist ? w.wlist[k] : k;
+                    line = w.hlist ? w.wlist[k] : (clist_s ? clist_s[k] : k);
                     sc = scan_row[line];
                 }
             }
@@ -1064,11 +1160,11 @@ __device__ __forceinline__ void line_wide_walk(const int tile_idx, const int spl
             // the scan of a queued walk has nothing to wait for but its own loads: kScanBatch chunks are requested together (a chunk is
             // two dependent loads in the wlist pass), tested, and their hits appended in list order
             constexpr int kScanBatch = SDX_SCAN_BATCH;
-            for (; q <= q_last; q += kScanBatch * n_split) {
+            for (; q <= q_last; q += kScanBatch * q_step) {
                 int bl[kScanBatch];
                 WideScan bs[kScanBatch];
 #pragma unroll
-                for (int u = 0; u < kScanBatch; ++u) fetch(q + u * n_split, bl[u], bs[u]);
+                for (int u = 0; u < kScanBatch; ++u) fetch(q + u * q_step, bl[u], bs[u]);
 #pragma unroll
                 for (int u = 0; u < kScanBatch; ++u) {
                     const int line = bl[u];
@@ -1079,7 +1175,7 @@ __device__ __forceinline__ void line_wide_walk(const int tile_idx, const int spl
                     const bool fast = hit & (sc.lo <= it0) & (sc.hi >= it1) & ((it1 <= clo) | (it0 >= sc.chi));
                     const unsigned long long m = __ballot(hit);
 #ifdef SDX_WALK_STATS
-                    if (q + u * n_split <= q_last) ++st_chunks;
+                    if (q + u * q_step <= q_last) ++st_chunks;
 #endif
                     if (m == 0) continue;
                     const int n = __popcll(m);
@@ -1102,10 +1198,10 @@ __device__ __forceinline__ void line_wide_walk(const int tile_idx, const int spl
         int line_next;
         WideScan sc_next;
         fetch(q, line_next, sc_next);
-        for (; q <= q_last; q += n_split) {
+        for (; q <= q_last; q += q_step) {
             const int line = line_next;
             const WideScan sc = sc_next;
-            fetch(q + n_split, line_next, sc_next);
+            fetch(q + q_step, line_next, sc_next);
             const bool far = FAR && far_eligible(sc, it0, it1, far_ihi, far_ilo);  // k_line_far's
             const bool hit = (line >= 0) & (sc.lo < it1) & (sc.hi > it0) & !far;  // narrow / empty items have lo = hi = 0
             const int clo = sc.clo < 0 ? -sc.clo - 1 : sc.clo;                // sign: core delegated to the narrow role
@@ -2371,7 +2467,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 // roles: bit 0 wide, bit 1 narrow (both by default; one at a time for split-launch profiling, SDX_SPLIT_LAUNCHES=1); bits 16-17: the
 // far field's workgroups (line_far_body) come FIRST in the grid, n_depth x far_units of them (fp64 kernels with a far field).
 // Output planes: [0] the wide windows (all subsets summed), [1] the narrow windows.
-template <int R, bool MIXED, bool SUBSETS, bool FAR = false>
+template <int R, bool MIXED, bool SUBSETS, bool FAR = false, bool LISTED = false>
 __device__ __forceinline__ void line_all_body(int n_wide, int tiles, int n_split, int n_depth, int64_t n_nu,
                                                    const double* __restrict__ nus, int64_t nu_begin, int64_t nu_count,
                                                    int64_t n_lines, const double* __restrict__ line_nus, LineWork w,
@@ -2427,11 +2523,11 @@ __device__ __forceinline__ void line_all_body(int n_wide, int tiles, int n_split
             if (tile >= tiles) return;
         }
         if constexpr (SUBSETS) {
-            line_wide_walk<R, WM, true, WM, FAR>(tile, wave, n_split, d, n_nu, nus, nu_begin, nu_count, n_lines, w, planes, pld, s_wide, part);
+            line_wide_walk<R, WM, true, WM, FAR, LISTED>(tile, wave, n_split, d, n_nu, nus, nu_begin, nu_count, n_lines, w, planes, pld, s_wide, part);
             out_row = d;
             out_col = (int)((nu_begin / (64 * R) + (int64_t)tile) * (64 * R)) + (int)(threadIdx.x & 63);
         } else {
-            line_wide_walk<R, WM, false, false, FAR>(tile, wave, n_split, d, n_nu, nus, nu_begin, nu_count, n_lines, w, planes, pld, s_wide);
+            line_wide_walk<R, WM, false, false, FAR, LISTED>(tile, wave, n_split, d, n_nu, nus, nu_begin, nu_count, n_lines, w, planes, pld, s_wide);
         }
     } else {
         if (!(roles & 2)) return;
@@ -2518,6 +2614,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FAR ? SDX_F
                                                    double* __restrict__ planes, int64_t pld, int roles, int far_units)
 {
     line_all_body<R, false, SUBSETS, FAR>(n_wide, tiles, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, planes, pld, roles, far_units);
+}
+// short lists whose pre-pass has listed their wide lines (LineWork::n_csplit, context option "wide_list"): the wide role walks its
+// subset's list instead of scanning every line; everything else is k_line_all
+template <int R, bool SUBSETS = false, bool FAR = false>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FAR ? SDX_FAR_WAVES : 7, 8))) void k_line_listed(int n_wide, int tiles, int n_split, int n_depth, int64_t n_nu,
+                                                   const double* __restrict__ nus, int64_t nu_begin, int64_t nu_count,
+                                                   int64_t n_lines, const double* __restrict__ line_nus, LineWork w,
+                                                   double* __restrict__ planes, int64_t pld, int roles, int far_units)
+{
+    line_all_body<R, false, SUBSETS, FAR, true>(n_wide, tiles, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, planes, pld, roles, far_units);
 }
 // the mixed-precision variant: 512-point tiles; the register budget is capped at 128 (4 waves per SIMD) — what exceeds it
 // sits in the rarely taken fp64 general path

@@ -98,6 +98,7 @@ struct sdx_ctx {
     int64_t mixed_precision = 0;       // 1: fp32 rational for far-wing (region I) evaluations of whole-tile windows
     int64_t segmented_raytrace = -1;   // -1: by the size of the GLOBAL grid; 0 never; 1 whenever the kernel supports the shape
     int64_t far_field = -1;            // -1: by the size of the GLOBAL grid; 0 never; 1 whenever the line kernel runs 256-point tiles
+    int64_t wide_list = -1;            // -1 / 1: short lists walk a compacted list of their wide lines wherever the pre-pass can build it; 0: they scan every line
     int64_t narrow_records = -1;       // -1: by the density of the list; 1: the pre-pass writes narrow records; 0: the narrow role reads the caller's tables (long dense fp64 lists)
     // timing
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -168,6 +169,20 @@ int ensure(sdx_ctx* ctx, void** buf, size_t* have, size_t need)
     }
     *have = need;
     ++ctx->ws_generation;
+    return SDX_OK;
+}
+
+// the small scratch: its counters ([2048, 4096): evaluation counter, the ticket counters of the pre-pass launches) start at zero — the
+// launch that counts the finished line blocks of a short list's pre-pass (LineWork::ticket with n_csplit) leaves its counter at zero and relies
+// on finding it so
+constexpr size_t kListTicketOffset = 2128;
+constexpr int64_t kListAutoChunks = 16;  // "wide_list" = -1: short lists of at least this many chunks of 64 lines per line subset
+int ensure_small(sdx_ctx* ctx, size_t need)
+{
+    const size_t before = ctx->small_ws_bytes;
+    int rc = ensure(ctx, &ctx->small_ws, &ctx->small_ws_bytes, need);
+    if (rc) return rc;
+    if (ctx->small_ws_bytes != before) HIP_TRY(hipMemsetAsync((char*)ctx->small_ws + 2048, 0, 2048, ctx->stream));
     return SDX_OK;
 }
 
@@ -259,7 +274,7 @@ inline unsigned blocks1(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock
 // d_nu partial maxima into small_ws
 int launch_dnu(sdx_ctx* ctx, int64_t n_nu, const double* nus, int* n_partial, int* zero = nullptr, int64_t n_zero = 0)
 {
-    int rc = ensure(ctx, &ctx->small_ws, &ctx->small_ws_bytes, kSmallHeader);
+    int rc = ensure_small(ctx, kSmallHeader);
     if (rc) return rc;
     ctx->classified.valid = false;  // (the grid-spacing partials of a two-collective phase 1 are overwritten)
     const int nb = (int)std::min<int64_t>(kDnuPartials, std::max<int64_t>(1, (n_nu + kBlock * 8 - 1) / (kBlock * 8)));
@@ -314,7 +329,7 @@ int launch_bf_coef(sdx_ctx* ctx, int n_depth, int n_species, int n_levels, const
                    const double* cutoff, const double* level_density, double** coef_out)
 {
     const size_t need = kSmallHeader + (size_t)n_levels * n_depth * sizeof(double);
-    int rc = ensure(ctx, &ctx->small_ws, &ctx->small_ws_bytes, need);
+    int rc = ensure_small(ctx, need);
     if (rc) return rc;
     double* coef = (double*)((char*)ctx->small_ws + kSmallHeader);
     {
@@ -442,6 +457,10 @@ int sdx_set_int_option(sdx_ctx* ctx, const char* name, int64_t value)
     }
     if (std::strcmp(name, "far_field") == 0) {
         ctx->far_field = value < 0 ? -1 : (value ? 1 : 0);
+        return SDX_OK;
+    }
+    if (std::strcmp(name, "wide_list") == 0) {
+        ctx->wide_list = value < 0 ? -1 : (value ? 1 : 0);
         return SDX_OK;
     }
     if (std::strcmp(name, "narrow_records") == 0) {
@@ -653,7 +672,7 @@ int sdx_memset(sdx_ctx* ctx, void* dst, int value, size_t bytes)
 int sdx_reserve_line_workspace(sdx_ctx* ctx, int n_depth, int64_t n_lines)
 {
     REQUIRE(ctx && n_depth > 0 && n_lines >= 0, "sdx_reserve_line_workspace: bad sizes");
-    int rc = ensure(ctx, &ctx->small_ws, &ctx->small_ws_bytes, kSmallHeader);
+    int rc = ensure_small(ctx, kSmallHeader);
     if (rc) return rc;
     return ensure(ctx, &ctx->line_ws, &ctx->line_ws_bytes, line_ws_need(n_depth, n_lines));
 }
@@ -841,7 +860,7 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
                         const double* doppler, const double* gammas, int gamma_cols, const double* alphas, bool fill_work,
                         int32_t* lo_ref, int32_t* hi_ref, LineWork* w_out, bool count_evals = true,
                         const ContinuumJob* job = nullptr, const LineParams* gen = nullptr, int64_t nu_begin = 0, int64_t nu_count = -1,
-                        const ClassifyPhase* ph = nullptr)
+                        const ClassifyPhase* ph = nullptr, int wide_splits = 0)
 {
     if (nu_count < 0) nu_count = n_nu;
     const LineParams lp = gen ? *gen : LineParams{};
@@ -850,7 +869,7 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
     // phase 2 that consumes it may find it valid (phase 1 sets the flag again when its launch is enqueued)
     const bool consumes_classified = ph && ph->phase == 2;
     if (!consumes_classified) ctx->classified.valid = false;
-    int rc = ensure(ctx, &ctx->small_ws, &ctx->small_ws_bytes, kSmallHeader);
+    int rc = ensure_small(ctx, kSmallHeader);
     if (rc) return rc;
     const bool scan_in_block = n_nu <= 16384;  // every pre-pass block re-scans a small grid instead of a separate launch
     LineWork w{};
@@ -887,6 +906,20 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
     w.gather = 0;
     w.ticket = nullptr;
     w.front = 0;
+    // SHORT lists (never culled, no list launches): the last line block of the pre-pass launch to finish lists the lines with a wide
+    // window per line subset of the wide role (LineWork::n_csplit; in the space long lists keep hlist in, the counts and offsets where
+    // the list launches keep their per-block counts) and the wide role walks that list instead of every line.  Same hits in the
+    // same order: scheduling only (context option "wide_list").  Not in the mixed-precision mode, whose fp32 sums are flushed into
+    // the fp64 sums at chunk boundaries: other chunks would move those roundings.
+    // Automatic rule: from kListAutoChunks chunks of 64 lines per subset on.  Measured (profiles/EXPERIMENTS.md, "Short lists walk a
+    // list of their wide lines"): at S-c2 (16 chunks per subset, 2 listed) the line kernel runs 1.2 us faster and the list is built in
+    // the shadow of the launch's continuum tiles; at S-c1 (4 per subset, 1 listed) the line kernel gains nothing and the last block's
+    // 3 us show at the end of a pre-pass launch whose continuum tiles are done before its line blocks.
+    const int64_t chunks_per_subset = wide_splits > 0 ? ((n_lines + 63) / 64 + wide_splits - 1) / wide_splits : 0;
+    if (fill_work && wide_splits > 0 && (ctx->wide_list == 1 || (ctx->wide_list < 0 && chunks_per_subset >= kListAutoChunks)) &&
+        !ctx->mixed_precision && n_lines > 0 && n_lines < ctx->indexed_min_lines && (n_lines + 63) / 64 <= kListMaxChunks) {
+        w.n_csplit = wide_splits;  // (its counter of finished line blocks: `ticket`, set where the launch is enqueued)
+    }
     // VERY dense long fp64 lists (>= 4 lines per grid point: the rule of the narrow role's subsets): no narrow records — the narrow role
     // reads the caller's three tables itself (LineWork::narrow_raw).  Pure scheduling (the same three operations form 1 / dw, y and the
     // amplitude either way).  Measured in round 6 (profiles/r06_raw.txt): 1e6 lines on 120 398 points — pre-pass 904 -> 721 us (a stream:
@@ -1049,6 +1082,8 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
         w.front = no_front ? 0 : 1;
     }
     const dim3 grid((unsigned)(n_line_blocks + n_pixel_blocks + w.gather), (unsigned)((n_depth + kPreDepths - 1) / kPreDepths));
+    const bool ticket_launch = w.ticket != nullptr;  // (the counter-driven launch of a culled shard)
+    if (w.n_csplit) w.ticket = (int*)((char*)ctx->small_ws + kListTicketOffset);
     if (job && !continuum_done) {
         ContPlan cp;
         if ((rc = plan_continuum(kPreBlock, &cp))) return rc;
@@ -1057,7 +1092,7 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
         const size_t shmem = cp.shmem;
         const unsigned total_blocks = grid.x * grid.y + (unsigned)cont_tiles * cp.cont_rows;
         {
-        LaunchScope ls(ctx, "k_prepass_continuum");
+        LaunchScope ls(ctx, "k_prepass_continuum", w.n_csplit ? "+ wide-line list" : nullptr);
 #define SDX_PRE_ARGS (int)grid.x, (int)grid.y, cont_tiles, n_depth, n_nu, nus, scan_in_block ? (const double*)nullptr : (const double*)ctx->small_ws, \
                      n_partial, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, w, n_line_blocks, job->nu_begin, job->nu_count, ca,          \
                      job->plane, job->nu_count, lp, stage_table
@@ -1070,10 +1105,10 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
 #undef SDX_PRE_ARGS
         }
     } else {
-        LaunchScope ls(ctx, job ? "k_prepass_continuum" : "k_line_prepass");
+        LaunchScope ls(ctx, job ? "k_prepass_continuum" : "k_line_prepass", w.n_csplit ? "+ wide-line list" : nullptr);
 #define SDX_PRE_ARGS n_depth, n_nu, nus, scan_in_block ? (const double*)nullptr : (const double*)ctx->small_ws, n_partial, n_lines, line_nus, doppler, \
                      gammas, gamma_cols, alphas, w, (int*)lo_ref, (int*)hi_ref, n_line_blocks, lp
-        if (w.ticket) {
+        if (ticket_launch) {
             const dim3 pgrid(std::min<unsigned>(grid.x, 2u * (unsigned)ctx->n_cu), grid.y);
             const double* dnu_arg = scan_in_block ? (const double*)nullptr : (const double*)ctx->small_ws;
 #define SDX_TICKET_ARGS n_depth, n_nu, nus, dnu_arg, n_partial, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, w, n_line_blocks, lp
@@ -1167,15 +1202,17 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     const bool classified_far = ph && ph->phase == 2 && ctx->classified.valid && ctx->classified.far && ctx->classified.far_ranges;
     if (far && !classified_far && (rc = request_far_ranges(ctx, n_nu, nu_begin, nu_count))) return rc;
     LineWork w;
+    // (the number of line subsets depends on the global grid and the list alone; the pre-pass of a short list sorts its wide lines by it)
+    const int n_split = choose_splits(n_depth, n_nu, n_lines, Rm, n_lines >= ctx->indexed_min_lines ? 4 : 2);
     rc = line_prepass(ctx, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, true, nullptr, nullptr, &w,
-                      count_evals, job, gen, nu_begin, nu_count, ph);
+                      count_evals, job, gen, nu_begin, nu_count, ph, n_split);
     const FarReq far_req = ctx->far_req;
     const bool far_req_done = ctx->far_req_done || classified_far;
     ctx->far_req = FarReq{nullptr, 0, 0};
     if (rc) return rc;
-    const int n_split = choose_splits(n_depth, n_nu, n_lines, Rm, n_lines >= ctx->indexed_min_lines ? 4 : 2);
     // long line lists: the lines with a window wider than kMediumHalfWidth are listed once (they are scanned by every tile);
-    // all others are found by centre range.  Short lists are scanned completely.
+    // all others are found by centre range.  Short lists are scanned completely, or — where the pre-pass has listed their wide lines
+    // (LineWork::n_csplit, option "wide_list") — through that list: no further launch either way.
     const int indexed = n_lines >= ctx->indexed_min_lines ? 1 : 0;
     if (indexed && !w.hlist) {  // (a culled pre-pass has built the lists already)
         LaunchScope ls(ctx, "k_hlist");
@@ -1293,6 +1330,10 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
         else if (ctx->mixed_precision && narrow_sub) hipLaunchKernelGGL((k_line_all_mixed<R_MIXED, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
         else if (ctx->mixed_precision && far) hipLaunchKernelGGL((k_line_all_mixed<R_MIXED, false, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
         else if (ctx->mixed_precision) hipLaunchKernelGGL((k_line_all_mixed<R_MIXED>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
+        else if (w.n_csplit && narrow_sub && far) hipLaunchKernelGGL((k_line_listed<R, true, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
+        else if (w.n_csplit && narrow_sub) hipLaunchKernelGGL((k_line_listed<R, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
+        else if (w.n_csplit && far) hipLaunchKernelGGL((k_line_listed<R, false, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
+        else if (w.n_csplit) hipLaunchKernelGGL((k_line_listed<R>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
         else if (narrow_sub && far) hipLaunchKernelGGL((k_line_all<R, true, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
         else if (narrow_sub) hipLaunchKernelGGL((k_line_all<R, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
         else if (far) hipLaunchKernelGGL((k_line_all<R, false, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
