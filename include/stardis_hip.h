@@ -24,7 +24,8 @@
  *   runs a synthesis under a hostile environment without the switch and compares bits):
  *     changes kernel choice or summation order (last bits of a result; shards of one spectrum must agree on them):
  *       SDX_WIDE_BLOCKS   target number of wide-role workgroups -> line subsets per (depth, tile)
- *       SDX_RT_SEG        0 / 1: never / always the segmented formal-solution kernel (the option "segmented_raytrace" wins)
+ *       SDX_RT_SEG        0 / 1 / 2: never / always the segmented formal-solution kernel, 2 preferring its step-shaped form (the option
+ *                         "segmented_raytrace" wins; same values)
  *       SDX_FAR           0 / 1: never / always the far field of the line kernels (the option "far_field" wins); SDX_FAR_RF 1 / 2 / 4
  *                         (tiles per unit of the far role / 4: scheduling only); SDX_FAR_LAUNCH: the far field as a launch of its own
  *                         (k_line_far, 8 line subsets — SDX_FAR_SPLIT 1 .. 8 — instead of the line kernel's: the order of a sum)
@@ -104,7 +105,12 @@ int sdx_synchronize(sdx_ctx* ctx);
  *   "segmented_raytrace" (default -1): which formal-solution kernel runs.  -1: decided from the size of the GLOBAL grid against
  *       a fixed constant (grids under 3 x 4 x 256 k_raytrace waves take the segmented kernel) — never from the shard's own
  *       width or the device's CU count, so that a frequency shard and the unsharded grid run the same arithmetic and stay
- *       bit-identical; 0: never the segmented kernel; 1: whenever it supports the shape.  The fp32-mixed twins (*_f32mix) that
+ *       bit-identical; 0: never the segmented kernel; 1: whenever it supports the shape, always the general kernel
+ *       k_raytrace_seg<8,7>; 2: whenever it supports the shape, and k_raytrace_seg_step<8,7> for the launches that have the shape
+ *       of the fused synthesis step (a fused total of 0, 2 or 3 line planes, the Planck source, no extra line plane, no
+ *       alpha_line_out, no I_nus, F_nu requested; the continuum launch of F_nu_continuum too) — the same arithmetic in the same
+ *       order as the general kernel, so the same bits, with less fixed cost per wave.  -1 takes the step kernel under the same
+ *       rule wherever it chooses the segmented one.  The fp32-mixed twins (*_f32mix) that
  *       SURVEY §8b proposed exist for the host-buffer entry points (below) and are this library's "mixed_precision" option for the rest.
  *   "far_field" (default -1): the far field of the line opacity.  A (line, depth) item whose window (base.py:561-575) contains a whole
  *       256-point tile of the GLOBAL grid, clear of the line's core range (every point of the tile in Faddeeva region I) and with the
@@ -179,7 +185,7 @@ int sdx_timer_stop(sdx_ctx* ctx, double* elapsed_ms);
 int sdx_profile_enable(sdx_ctx* ctx, int on); /* bracket every kernel launch with events */
 int sdx_profile_reset(sdx_ctx* ctx);
 int sdx_profile_get(sdx_ctx* ctx, const char* kernel, int64_t* launches, double* total_ms);
-/* which device kernel last ran under the stage name `kernel` while profiling was on ("k_raytrace" -> "k_raytrace_seg<8,7>",
+/* which device kernel last ran under the stage name `kernel` while profiling was on ("k_raytrace" -> "k_raytrace_seg<8,7>", "k_raytrace_seg_step<8,7>",
  * "k_raytrace<1>", "k_raytrace_f32", ...); "" when the stage has one kernel only or did not run */
 int sdx_profile_variant(sdx_ctx* ctx, const char* kernel, char* out, int out_len);
 

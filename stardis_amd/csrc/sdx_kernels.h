@@ -357,7 +357,7 @@ __device__ __forceinline__ int* wide_list_counts(const LineWork& w) { return w.h
 
 // k / d for 0 <= k < 65536 and 1 <= d < 65536 with the divisor's reciprocal m = small_div_magic(d) = ceil(2^32 / d): one multiply-high
 // instead of the ~30 instructions of a 32-bit division by a run-time value (the pre-pass indexes its (line, depth) items six times)
-__device__ __forceinline__ unsigned small_div_magic(int d) { return d > 1 ? 0xFFFFFFFFu / (unsigned)d + 1u : 0u; }
+__host__ __device__ __forceinline__ unsigned small_div_magic(int d) { return d > 1 ? 0xFFFFFFFFu / (unsigned)d + 1u : 0u; }
 __device__ __forceinline__ int small_div(int k, unsigned magic) { return magic ? (int)__umulhi((unsigned)k, magic) : k; }
 
 // Short lists: the wide role's candidates, compacted per line subset (LineWork::n_csplit).  Run by ONE block, the last line block of
@@ -3955,6 +3955,171 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
             const int64_t iq = i0 + gq;
             if (h == 0 && iq < n_nu) F[(size_t)(g_lo + b + 1) * fld + iq] = add_rn(sum, other);
         }
+    }
+}
+
+// k_raytrace_seg in the ONE SHAPE the fused synthesis step launches it in: a fused total (continuum + N_PLANES partial line planes,
+// N_PLANES = 0 for a zero-line run and for the continuum-only second launch), the Planck source, flux only.  The same algorithm and
+// the same floating-point operations in the same order — segment alignment, rt_coef_fast / rt_coef_reference on resident constants,
+// the composition, the fold, the two ascending halves of the flux, total = cont + (p0 + p1 (+ p2)) — so the same bits; what differs
+// is the fixed cost a wave pays around its LMAX gaps:
+//   prologue  every launch constant the general kernel forms per wave comes from the host (SegStepGeom); no address of an output the
+//             shape lacks; the Planck literals live only in the waves that stage;
+//   staging   items are (depth, column) with the column fastest, dense over the lanes: a wave's loads and its total_out stores cover
+//             whole runs of a row (the general kernel gives a column to a wave: three waves touch the same sectors of every row), all
+//             plane loads of a point are in flight before the first add, the Planck value — no load of a plane behind it — is formed
+//             under their latency, and a point's (source, sqrt(alpha)) pair is ONE 16-byte LDS write.  The ray table goes to the waves
+//             in descending order, so that the waves without columns take its extra trip;
+//   replay    no test for the optional intensity output;
+//   flux      (gap, frequency) of a lane from the host's reciprocal of gpw.
+struct SegStepGeom {
+    int gpw, g_recip;         // frequencies per workgroup 64 / n_theta; lane_recip(n_theta)
+    int per;                  // 64 / n_theta: gaps of the ray table per wave and trip
+    int L;                    // segment length ceil(n_gap / NS)
+    int rstride;              // n_gap | 1
+    int sp_off;               // doubles from the ray table to the (source, sqrt(alpha)) pairs: (n_theta rstride + 1) & ~1
+    unsigned gpw_magic;       // small_div_magic(gpw)
+    unsigned n_wg, per_xcd;   // as k_raytrace_seg
+};
+template <int NS, int LMAX, int N_PLANES, bool KEEP_TOTAL>
+__global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8 ? 6 : 4, 8))) void k_raytrace_seg_step(
+    int n_depth, int64_t n_nu, int n_theta, int theta_stride, const double* __restrict__ nus, const double* __restrict__ temps,
+    const double* __restrict__ ray_dist, const double* __restrict__ wts, const double* __restrict__ cont, int64_t cld,
+    const double* __restrict__ planes, int64_t pld, double* __restrict__ total_out, int64_t out_ld, double* __restrict__ F, int64_t fld,
+    SegStepGeom geo)
+{
+    extern __shared__ double smem[];
+    const int lane = threadIdx.x & 63;
+    const int seg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int G = n_theta, gpw = geo.gpw;
+    const int grp = lane_div(lane, geo.g_recip), g = lane - grp * G;
+    const unsigned wg = (blockIdx.x & 7) * geo.per_xcd + (blockIdx.x >> 3);  // XCD-aware order, as k_raytrace_seg
+    if ((blockIdx.x >> 3) >= geo.per_xcd || wg >= geo.n_wg) return;
+    const int64_t i0 = (int64_t)wg * gpw;
+    const bool active = grp < gpw;
+    const int n_gap = n_depth - 1, col = n_depth;
+    const int rstride = geo.rstride;
+    double* sAB = smem;                        // [NS][64][2] segment maps
+    double* sRT = sAB + NS * 128;              // ray_dist transposed [n_theta][rstride]
+    double2* sP = (double2*)(sRT + geo.sp_off);  // (source function, sqrt(alpha)) [gpw][col]
+    double* sFx = sRT;                         // after the barrier of step 2: flux terms [NS][LMAX][gpw][G]
+
+    if (grp < geo.per)
+        for (int gp = (NS - 1 - seg) * geo.per + grp; gp < n_gap; gp += NS * geo.per) sRT[g * rstride + gp] = ray_dist[gp * theta_stride + g];
+    const int n_items = n_depth * gpw;
+    if (seg * 64 < n_items) {  // (wave-uniform: a wave without items forms no Planck constant)
+        for (int k = threadIdx.x; k < n_items; k += 64 * NS) {
+            const int d = small_div(k, geo.gpw_magic), gq = k - d * gpw;
+            const int64_t iq = i0 + gq;
+            const bool vq = iq < n_nu;
+            const int64_t ic = vq ? iq : n_nu - 1;
+            const double c0 = cont[(size_t)d * cld + ic];
+            double pl[N_PLANES > 0 ? N_PLANES : 1];
+#pragma unroll
+            for (int sp = 0; sp < N_PLANES; ++sp) pl[sp] = planes[((size_t)sp * n_depth + d) * pld + ic];
+            const double src = planck_staged(nus[ic], temps[d]);
+            double a = c0;
+            if (N_PLANES > 0) {
+                double line = pl[0];
+#pragma unroll
+                for (int sp = 1; sp < N_PLANES; ++sp) line = add_rn(line, pl[sp]);
+                a = add_rn(a, line);
+            }
+            if (KEEP_TOTAL && vq) total_out[(size_t)d * out_ld + iq] = a;
+            sP[gq * col + d] = double2{src, sqrt(a)};
+        }
+    }
+    __syncthreads();
+
+    // step 1, as k_raytrace_seg: segments aligned to the end of the ray, a wave's gaps to the end of its LMAX register slots
+    const int L = geo.L;
+    const int g_end = n_gap - (NS - 1 - seg) * L;
+    const int g_lo = max(0, g_end - L);
+    const int count = max(0, g_end - g_lo);
+    const int j0 = LMAX - count;
+    const int gi = (active ? grp : 0) * col;  // idle lanes shadow group 0 and never store
+    const int th = min(g, n_theta - 1);
+    const double wt = wts[th];
+    double c[LMAX], e[LMAX];
+    double A = 1.0, B = 0.0;
+    unsigned long long redo = 0;
+    const int gc = count > 0 ? g_lo : 0;
+    const RtConst kc = rt_const_resident();
+    {
+        const double2* pP = sP + gi + gc - j0;
+        const double* pR = sRT + th * rstride + gc - j0;
+        const double2 q0 = pP[j0], q1 = pP[j0 + 1];
+        double a1 = q1.y, s1 = q1.x;
+        double d10 = q0.x - s1;
+        double t0 = mul_rn(q0.y * a1, pR[j0]);
+#pragma unroll
+        for (int j = 0; j < LMAX; ++j) {
+            c[j] = 1.0, e[j] = 0.0;
+            if (j >= j0) {
+                if (j < LMAX - 1 || seg < NS - 1) {  // :208-249
+                    const double2 q2 = pP[j + 2];
+                    const double s2 = q2.x, a2 = q2.y;
+                    const double t1 = mul_rn(a1 * a2, pR[j + 1]);
+                    const double d21 = s2 - s1;
+                    redo |= rt_coef_fast<false>(t0, t1, d10, d21, s1, c[j], e[j], kc);
+                    t0 = t1, d10 = -d21, s1 = s2, a1 = a2;
+                } else {  // the final gap (:253-266)
+                    redo |= rt_coef_fast<true>(t0, 0.0, d10, 0.0, s1, c[j], e[j], kc);
+                }
+                A *= c[j];
+                B = fma(c[j], B, e[j]);
+            }
+        }
+    }
+    if (redo) {  // rare: the segment once more in the reference's own form
+        A = 1.0, B = 0.0;
+        for (int j = j0; j < LMAX; ++j) {
+            const int gap = gc + j - j0;
+            const double s0 = sP[gi + gap].x, s1 = sP[gi + gap + 1].x;
+            const double t0 = mul_rn(sP[gi + gap].y * sP[gi + gap + 1].y, sRT[th * rstride + gap]);
+            double cj, ej;
+            if (gap < n_gap - 1) {
+                const double t1 = mul_rn(sP[gi + gap + 1].y * sP[gi + gap + 2].y, sRT[th * rstride + gap + 1]);
+                rt_coef_reference<false>(t0, t1, s0 - s1, sP[gi + gap + 2].x - s1, s1, cj, ej);
+            } else {
+                rt_coef_reference<true>(t0, 0.0, s0 - s1, 0.0, s1, cj, ej);
+            }
+            A *= cj;
+            B = fma(cj, B, ej);
+#pragma unroll
+            for (int k = 0; k < LMAX; ++k)
+                if (k == j) c[k] = cj, e[k] = ej;
+        }
+    }
+    sAB[(seg * 64 + lane) * 2] = A;
+    sAB[(seg * 64 + lane) * 2 + 1] = B;
+    __syncthreads();
+    // step 2: the intensity entering this segment
+    double inten = 0.0;
+    for (int k = 0; k < seg; ++k) inten = fma(sAB[(k * 64 + lane) * 2], inten, sAB[(k * 64 + lane) * 2 + 1]);
+    if (seg == 0 && active && g == 0 && i0 + grp < n_nu) F[i0 + grp] = 0.0;
+    // step 3: replay, flux terms to LDS
+    double* fx = sFx + seg * LMAX * gpw * G + (active ? grp * G + g : 0);
+#pragma unroll
+    for (int j = 0; j < LMAX; ++j) {
+        if (j >= j0) {
+            inten = fma(c[j], inten, e[j]);
+            if (active) fx[(j - j0) * gpw * G] = inten * wt;
+        }
+    }
+    fx = sFx + seg * LMAX * gpw * G;
+    wave_sync();
+    const int half = (n_theta + 1) >> 1;
+    for (int p = lane; p < 2 * count * gpw; p += 64) {
+        const int h = p & 1, q = p >> 1;  // q = b * gpw + gq
+        const int b = small_div(q, geo.gpw_magic), gq = q - b * gpw;
+        const double* cc = fx + q * G + (h ? half : 0);
+        const int cnt = h ? n_theta - half : half;
+        double sum = 0.0;
+        for (int t = 0; t < cnt; ++t) sum = add_rn(sum, cc[t]);
+        const double other = __shfl_xor(sum, 1);
+        const int64_t iq = i0 + gq;
+        if (h == 0 && iq < n_nu) F[(size_t)(g_lo + b + 1) * fld + iq] = add_rn(sum, other);
     }
 }
 

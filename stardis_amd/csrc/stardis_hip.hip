@@ -96,7 +96,8 @@ struct sdx_ctx {
     int64_t indexed_min_lines = 8192;  // line lists at least this long: wide lines found by centre range / the huge-line list instead of a full scan
     int64_t prepass_ticket_min_blocks = 16384;  // culled shards: from this many line blocks on the pre-pass draws its work from a counter
     int64_t mixed_precision = 0;       // 1: fp32 rational for far-wing (region I) evaluations of whole-tile windows
-    int64_t segmented_raytrace = -1;   // -1: by the size of the GLOBAL grid; 0 never; 1 whenever the kernel supports the shape
+    int64_t segmented_raytrace = -1;   // -1: by the size of the GLOBAL grid; 0 never; 1 whenever the kernel supports the shape (the general
+                                       // kernel); 2 the same, preferring k_raytrace_seg_step where the launch has its shape (as -1 does)
     int64_t far_field = -1;            // -1: by the size of the GLOBAL grid; 0 never; 1 whenever the line kernel runs 256-point tiles
     int64_t wide_list = -1;            // -1 / 1: short lists walk a compacted list of their wide lines wherever the pre-pass can build it; 0: they scan every line
     int64_t narrow_records = -1;       // -1: by the density of the list; 1: the pre-pass writes narrow records; 0: the narrow role reads the caller's tables (long dense fp64 lists)
@@ -452,7 +453,7 @@ int sdx_set_int_option(sdx_ctx* ctx, const char* name, int64_t value)
         return SDX_OK;
     }
     if (std::strcmp(name, "segmented_raytrace") == 0) {
-        ctx->segmented_raytrace = value < 0 ? -1 : (value ? 1 : 0);
+        ctx->segmented_raytrace = value < 0 ? -1 : (value >= 2 ? 2 : (value ? 1 : 0));
         return SDX_OK;
     }
     if (std::strcmp(name, "far_field") == 0) {
@@ -828,13 +829,19 @@ static size_t seg_lds_doubles(int n_depth, int nth)
 // sharded and unsharded spectra): the choice is made from the GLOBAL grid size against a fixed constant — three k_raytrace
 // waves per SIMD of a 256-CU part — or set explicitly (context option "segmented_raytrace").
 constexpr int64_t kSegLegacyWaves = (int64_t)3 * 4 * 256;
+static int segmented_mode(const sdx_ctx* ctx)
+{
+    // A/B knob: 0 never, 1 whenever possible (the general kernel), 2 whenever possible and the step kernel where the shape allows
+    static const int env_mode = knob("SDX_RT_SEG") ? std::atoi(knob("SDX_RT_SEG")) : -1;
+    const int mode = ctx->segmented_raytrace >= 0 ? (int)ctx->segmented_raytrace : env_mode;
+    return mode < 0 ? -1 : std::min(mode, 2);
+}
 static bool use_segmented_raytrace(const sdx_ctx* ctx, int n_depth, int64_t n_nu_global, int n_theta, bool plain)
 {
-    static const int env_mode = knob("SDX_RT_SEG") ? std::atoi(knob("SDX_RT_SEG")) : -1;  // A/B knob: 0 never, 1 whenever possible
-    const int mode = ctx->segmented_raytrace >= 0 ? (int)ctx->segmented_raytrace : env_mode;
+    const int mode = segmented_mode(ctx);
     if (mode == 0 || !plain || n_theta > 64) return false;
     if ((n_depth - 1 + kSegWaves - 1) / kSegWaves > kSegMax || seg_lds_doubles(n_depth, n_theta) * sizeof(double) > 64 * 1024) return false;
-    if (mode == 1) return true;
+    if (mode >= 1) return true;
     const int64_t legacy_waves = (n_nu_global + 64 / n_theta - 1) / (64 / n_theta);
     return legacy_waves < kSegLegacyWaves;
 }
@@ -2049,7 +2056,35 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
         // the launch geometry of the XCD-aware order, handed to the kernel: workgroups, workgroups per XCD, whole rounds of eight
         const unsigned seg_wg = (unsigned)((n_nu + seg_gpw - 1) / seg_gpw), seg_per_xcd = (seg_wg + 7) / 8, seg_blocks = seg_per_xcd * 8;
         if (use_segmented_raytrace(ctx, n_depth, nu_global, n_theta, P == 1 && !inward && !acc)) {
-            {
+            // the shape of the fused synthesis step — a fused total of 0, 2 or 3 line planes, the Planck source, flux only — has a kernel
+            // of its own (k_raytrace_seg_step: the same bits); "segmented_raytrace" = 1 keeps the general kernel
+            const int step_planes = ft.planes ? ft.n_planes : 0;
+            const bool step_shape = segmented_mode(ctx) != 1 && kSegWaves == 8 && ft.cont && !ft.source && ft.n_extra == 0 && !ft.line_out && !inus && F &&
+                                    (step_planes == 0 || step_planes == 2 || step_planes == 3);
+            SegStepGeom geo{};
+            geo.gpw = seg_gpw, geo.g_recip = lane_recip(nth), geo.per = 64 / nth, geo.L = (n_depth - 1 + kSegWaves - 1) / kSegWaves;
+            geo.rstride = (n_depth - 1) | 1, geo.sp_off = (nth * geo.rstride + 1) & ~1, geo.gpw_magic = small_div_magic(seg_gpw);
+            geo.n_wg = seg_wg, geo.per_xcd = seg_per_xcd;
+            auto launch_step = [&](int planes_n, const double* planes, double* total_out, double* flux, int64_t flux_ld) {
+#define SDX_STEP_LAUNCH(NP, KEEP)                                                                                                              \
+    hipLaunchKernelGGL((k_raytrace_seg_step<8, 7, NP, KEEP>), dim3(seg_blocks), dim3(512), seg_doubles * sizeof(double), ctx->stream, n_depth, n_nu, nth, \
+                       n_theta, nus, temps, rd, w, ft.cont, ft.cld, planes, ft.pld, total_out, ft.out_ld, flux, flux_ld, geo)
+                if (planes_n == 0) {
+                    if (total_out) SDX_STEP_LAUNCH(0, true);
+                    else SDX_STEP_LAUNCH(0, false);
+                } else if (planes_n == 2) {
+                    if (total_out) SDX_STEP_LAUNCH(2, true);
+                    else SDX_STEP_LAUNCH(2, false);
+                } else {
+                    if (total_out) SDX_STEP_LAUNCH(3, true);
+                    else SDX_STEP_LAUNCH(3, false);
+                }
+#undef SDX_STEP_LAUNCH
+            };
+            if (step_shape) {
+                LaunchScope ls(ctx, "k_raytrace", "k_raytrace_seg_step<8,7>");
+                launch_step(step_planes, ft.planes, ft.total_out, F, fld);
+            } else {
                 LaunchScope ls(ctx, "k_raytrace", kSegWaves == 4 ? "k_raytrace_seg<4,14>" : "k_raytrace_seg<8,7>");
 #define SDX_SEG_ARGS n_depth, n_nu, nth, n_theta, nus, temps, rd, w, alphas, ald, F, fld, inus, seg_gpw, lane_recip(nth), seg_wg, seg_per_xcd, ft
                 if (kSegWaves == 4) hipLaunchKernelGGL((k_raytrace_seg<4, 14>), dim3(seg_blocks), dim3(256), seg_doubles * sizeof(double), ctx->stream, SDX_SEG_ARGS);
@@ -2065,7 +2100,10 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
                 // (DESIGN.md).  Removed.
                 FusedTotal fc{};
                 fc.cont = ft.cont, fc.cld = ft.cld, fc.source = ft.source, fc.sld = ft.sld;
-                {
+                if (segmented_mode(ctx) != 1 && kSegWaves == 8 && !ft.source) {  // (this launch has the step kernel's shape whatever the first one had)
+                    LaunchScope ls(ctx, "k_raytrace", "k_raytrace_seg_step<8,7> (continuum)");
+                    launch_step(0, nullptr, nullptr, Fc, fcld);
+                } else {
                     LaunchScope ls(ctx, "k_raytrace", kSegWaves == 4 ? "k_raytrace_seg<4,14> (continuum)" : "k_raytrace_seg<8,7> (continuum)");
 #define SDX_SEG_ARGS n_depth, n_nu, nth, n_theta, nus, temps, rd, w, nullptr, 0, Fc, fcld, nullptr, seg_gpw, lane_recip(nth), seg_wg, seg_per_xcd, fc
                     if (kSegWaves == 4) hipLaunchKernelGGL((k_raytrace_seg<4, 14>), dim3(seg_blocks), dim3(256), seg_doubles * sizeof(double), ctx->stream, SDX_SEG_ARGS);
