@@ -12,6 +12,7 @@
 #include "sdx_math.h"
 #include "sdx_broadening.h"
 #include "sdx_cheb.h"
+#include "sdx_rt_layout.h"
 
 namespace sdx {
 
@@ -3442,7 +3443,7 @@ struct FusedTotal {
 //   flux     I_theta * w_theta goes to the wave's LDS; every kBatch gaps the wave sums each (gap, frequency) over theta in
 //            two ascending halves and writes F_nu.
 // Only the ray table is shared by the block: after the staging barrier the waves never meet again (wave-level hand-overs).
-constexpr int kRtBlock = 256;
+// kRtBlock and the LDS layout of every kernel of the family: sdx_rt_layout.h.
 // lane / G for lane < 64 and 1 <= G <= 64 without an integer division (~25 instructions where G is a kernel argument): one multiply
 // by g_recip = 65536 / G + 1, formed once on the host (lane_recip, stardis_hip.hip), and a shift.  Exact over that whole range.
 // (k_raytrace_seg, whose prologue is a visible share of a wave's life; k_raytrace<P> and k_raytrace_cont<P> keep the division)
@@ -3457,7 +3458,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
                                                      const double* __restrict__ alphas, int64_t ald, double* __restrict__ F,
                                                      int64_t fld, double* __restrict__ I_nus, int accumulate, int inward, int gpw, FusedTotal ft)
 {
-    constexpr int kBatch = P == 1 ? 4 : 2;
+    constexpr int kBatch = RtColumns::gaps_per_batch(P);
     extern __shared__ double smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // gpw = groups (frequencies) per wave, <= 64 / G; the host lowers it when the LDS columns would not fit
@@ -3470,9 +3471,10 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
     const int64_t ic = i < n_nu ? i : n_nu - 1;
     const int n_gap = n_depth - 1;
     const int col = n_depth;  // LDS row stride per group
-    double* wbase = smem + (size_t)wave * (2 * gpw * col + kBatch * gpw * TH);
-    double2* sP = (double2*)wbase;            // (source function, sqrt(alpha)) [gpw][col]: a point's pair is ONE 16-byte LDS read
-    double* sX = wbase + 2 * gpw * col;       // flux terms       [kBatch][gpw][TH]
+    const RtColumns lay(P, G, n_depth, gpw);
+    double* wbase = smem + (size_t)wave * lay.wave_doubles();
+    double2* sP = (double2*)(wbase + lay.pairs());  // (source function, sqrt(alpha)) [gpw][col]: a point's pair is ONE 16-byte LDS read
+    double* sX = wbase + lay.flux();                // flux terms       [kBatch][gpw][TH]
     const double nu = nus[ic];
 
     // (Staging the columns a batch of G depth points AHEAD of the recurrence — the loads of batch b + 1 requested when batch b is
@@ -3642,7 +3644,6 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
 // differences between adjacent points (formed as differences: planck32_pair) and the ray lengths are staged as floats (the totals
 // are formed in fp64 and rounded once); F_nu is written as doubles.
 // Against the fp64 kernels: < 1e-5 of the flux on the full-size workloads (tests/test_gpu_configs.py, stated tolerance 1e-4).
-constexpr int kRt32Batch = 8;  // gaps per flux reduction of k_raytrace_f32 (6 measured: no gain from the eighth block a CU's LDS then holds)
 __global__ __launch_bounds__(kRtBlock) void k_raytrace_f32(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
                                                            const double* __restrict__ nus, const double* __restrict__ temps,
                                                            const double* __restrict__ ray_dist, const double* __restrict__ wts,
@@ -3660,16 +3661,16 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_f32(int n_depth, int64_t 
     const bool valid = active && i < n_nu;
     const int64_t ic = i < n_nu ? i : n_nu - 1;
     const int n_gap = n_depth - 1, col = n_depth;
-    float* sRD = fmem;                                   // ray_dist [n_gap][n_theta], shared by the block
-    float* sK = sRD + n_gap * n_theta;                   // 1 / (k T_d) [col], shared by the block
-    float* sR = sK + col;                                // (T_d - T_{d+1}) / T_{d+1} [col]: the difference formed in fp64
+    const RtF32Columns lay(n_theta, G, n_depth, gpw);
+    float* sRD = fmem + lay.ray_table();                 // ray_dist [n_gap][n_theta], shared by the block
+    float* sK = fmem + lay.inv_kt();                     // 1 / (k T_d) [col], shared by the block
+    float* sR = fmem + lay.dtemp();                      // (T_d - T_{d+1}) / T_{d+1} [col]: the difference formed in fp64
     // per wave: what a step of the recurrence needs of its NEXT point as ONE 16-byte LDS read — sP[k] = (sqrt(alpha_{k+1}), S_{k+1},
     // S_k - S_{k+1}, -) for k < n_gap, the difference formed as a difference (planck32_pair), not from the two rounded values; the
     // first point's (sqrt(alpha_0), S_0) in the spare slot k = n_gap
-    const int shared_floats = (n_gap * n_theta + 2 * col + 3) & ~3;
-    float* wbase = fmem + shared_floats + (size_t)wave * (4 * gpw * col + kBatch * gpw * G);
-    float4* sP = (float4*)wbase;                         // [gpw][col]
-    float* sX = wbase + 4 * gpw * col;                   // flux terms [kBatch][gpw][G]
+    float* wbase = fmem + lay.shared_floats() + (size_t)wave * lay.wave_floats();
+    float4* sP = (float4*)(wbase + lay.points());        // [gpw][col]
+    float* sX = wbase + lay.flux();                      // flux terms [kBatch][gpw][G]
     const double nu = nus[ic];
     for (int k = threadIdx.x; k < n_gap * n_theta; k += kRtBlock) {
         const int gp = k / n_theta, t = k - gp * n_theta;
@@ -3803,13 +3804,14 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
     const bool active = grp < gpw;
     const bool valid = active && i < n_nu;
     const int n_gap = n_depth - 1, col = n_depth;
-    const int rstride = n_gap | 1;             // odd row stride: the angles of a wave read distinct banks
-    double* sAB = smem;                        // [NS][64][2] segment maps
-    double* sRT = sAB + NS * 128;              // ray_dist TRANSPOSED [n_theta][rstride]: a lane's gaps are consecutive (immediate offsets)
+    const RtSegments lay(NS, LMAX, n_theta, n_depth);
+    const int rstride = lay.rstride();         // odd row stride: the angles of a wave read distinct banks
+    double* sAB = smem + lay.maps();           // [NS][64][2] segment maps
+    double* sRT = smem + lay.ray_table();      // ray_dist TRANSPOSED [n_theta][rstride]: a lane's gaps are consecutive (immediate offsets)
     // (source function, sqrt(alpha)) [gpw][col], a point's pair ONE 16-byte LDS read; the geometric-mean opacity of a gap (:121) is
     // the product of its two ends' square roots
-    double2* sP = (double2*)(sRT + ((n_theta * rstride + 1) & ~1));
-    double* sFx = sRT;                         // after the barrier of step 2: flux terms [NS][LMAX][gpw][G]
+    double2* sP = (double2*)(smem + lay.pairs());
+    double* sFx = smem + lay.flux();           // after the barrier of step 2: flux terms [NS][LMAX][gpw][G]
 
     // staging without a division per item: lane <-> (one of 64 / n_theta gaps, angle) once; then a wave takes one frequency's
     // column (lane <-> depth) — waves 0 .. gpw-1 sqrt(alpha), the next gpw the source function
@@ -3852,7 +3854,7 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
     // step 1: the coefficients of this wave's gaps [g_lo, g_lo + count).  The segments are aligned to the END of the ray — the first
     // wave takes the short one — and a wave's gaps to the end of its LMAX register slots (slot j <-> gap g_lo + j - j0): the final
     // gap, the one step with a formula of its own (:253-266), is then always slot LMAX - 1 of the last wave, a static place
-    const int L = (n_gap + NS - 1) / NS;
+    const int L = lay.segment();
     const int g_end = n_gap - (NS - 1 - seg) * L;
     const int g_lo = max(0, g_end - L);
     const int count = max(0, g_end - g_lo);
@@ -3975,9 +3977,9 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
 struct SegStepGeom {
     int gpw, g_recip;         // frequencies per workgroup 64 / n_theta; lane_recip(n_theta)
     int per;                  // 64 / n_theta: gaps of the ray table per wave and trip
-    int L;                    // segment length ceil(n_gap / NS)
-    int rstride;              // n_gap | 1
-    int sp_off;               // doubles from the ray table to the (source, sqrt(alpha)) pairs: (n_theta rstride + 1) & ~1
+    int L;                    // RtSegments::segment()
+    int rstride;              // RtSegments::rstride()
+    int sp_off;               // doubles from the ray table to the (source, sqrt(alpha)) pairs: RtSegments::pairs_from_table()
     unsigned gpw_magic;       // small_div_magic(gpw)
     unsigned n_wg, per_xcd;   // as k_raytrace_seg
 };
@@ -3999,8 +4001,8 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
     const bool active = grp < gpw;
     const int n_gap = n_depth - 1, col = n_depth;
     const int rstride = geo.rstride;
-    double* sAB = smem;                        // [NS][64][2] segment maps
-    double* sRT = sAB + NS * 128;              // ray_dist transposed [n_theta][rstride]
+    double* sAB = smem;                        // [NS][64][2] segment maps (the layout is RtSegments, its run-time values in geo)
+    double* sRT = smem + RtSegments(NS, LMAX, n_theta, n_depth).ray_table();  // ray_dist transposed [n_theta][rstride]
     double2* sP = (double2*)(sRT + geo.sp_off);  // (source function, sqrt(alpha)) [gpw][col]
     double* sFx = sRT;                         // after the barrier of step 2: flux terms [NS][LMAX][gpw][G]
 
@@ -4141,7 +4143,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
                                                           double* __restrict__ F, int64_t fld, double* __restrict__ Fc, int64_t fcld,
                                                           double* __restrict__ I_nus, int inward, int gpw, FusedTotal ft)
 {
-    constexpr int kBatch = P == 1 ? 4 : 2;
+    constexpr int kBatch = RtColumns::gaps_per_batch(P);
     extern __shared__ double smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = lane / G, g = lane - grp * G;
@@ -4153,6 +4155,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
     const int64_t ic = i < n_nu ? i : n_nu - 1;
     const int n_gap = n_depth - 1;
     const int col = n_depth;
+    // must match RtContColumns (sdx_rt_layout.h), which the host sizes the launch by: taken from the struct, <2> and <4> spill two more SGPRs
     double* wbase = smem + (size_t)wave * ((3 * gpw * col + 2 * kBatch * gpw * TH + 1) & ~1);  // (even: 16-byte aligned pairs)
     double2* sP = (double2*)wbase;            // (source function, sqrt(alpha total)) [gpw][col]
     double* sC = wbase + 2 * gpw * col;       // sqrt(alpha continuum)             [gpw][col]
@@ -4340,7 +4343,7 @@ __global__ __launch_bounds__(kRtBlock) void k_contribution(int n_depth, int64_t 
                                                          const double* __restrict__ alphas, int64_t ald, const double* __restrict__ source,
                                                          int64_t sld, double* __restrict__ C, int64_t cld, int gpw)
 {
-    constexpr int kBatch = P == 1 ? 4 : 2;
+    constexpr int kBatch = RtColumns::gaps_per_batch(P);
     extern __shared__ double smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = lane / G, g = lane - grp * G;
@@ -4352,9 +4355,10 @@ __global__ __launch_bounds__(kRtBlock) void k_contribution(int n_depth, int64_t 
     const int64_t ic = i < n_nu ? i : n_nu - 1;
     const int n_gap = n_depth - 1;
     const int col = n_depth;  // LDS row stride per group
-    double* wbase = smem + (size_t)wave * (2 * gpw * col + kBatch * gpw * TH);
-    double2* sP = (double2*)wbase;       // (source function, sqrt(alpha)) [gpw][col]
-    double* sX = wbase + 2 * gpw * col;  // flux terms T e w_theta [kBatch][gpw][TH]
+    const RtColumns lay(P, G, n_depth, gpw);
+    double* wbase = smem + (size_t)wave * lay.wave_doubles();
+    double2* sP = (double2*)(wbase + lay.pairs());  // (source function, sqrt(alpha)) [gpw][col]
+    double* sX = wbase + lay.flux();                // flux terms T e w_theta [kBatch][gpw][TH]
     const double nu = nus[ic];
 
     if (active) {

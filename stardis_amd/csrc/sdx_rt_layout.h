@@ -1,0 +1,133 @@
+// sdx_rt_layout.h — the dynamic-LDS layouts of the formal-solution kernels (sdx_kernels.h), each stated ONCE: the kernel takes its
+// region offsets from the struct, the host (stardis_hip.hip) takes the launch's byte count and chooses the launch shape from it.
+// Offsets and sizes are ints, as the kernels index; the host's helpers below keep them exact by refusing, before any arithmetic, a
+// model whose single column is larger than LDS.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+
+constexpr int kRtBlock = 256;             // k_raytrace<P>, k_raytrace_cont<P>, k_raytrace_f32, k_contribution<P>: four waves
+constexpr int kRtWaves = kRtBlock / 64;
+constexpr size_t kLdsBytes = 64 * 1024;   // what a workgroup may ask for
+
+// k_raytrace<P>, k_contribution<P>.  Per wave: the (source function, sqrt(alpha)) pairs [gpw][col] as double2, then the flux terms
+// [batch][gpw][TH] of a batch of gaps.  G lanes per frequency, P angles per lane, gpw frequencies per wave.
+struct RtColumns {
+    int gpw, col, TH, batch;
+    static __host__ __device__ constexpr int gaps_per_batch(int P) { return P == 1 ? 4 : 2; }
+    __host__ __device__ constexpr RtColumns(int P, int G, int n_depth, int gpw_) : gpw(gpw_), col(n_depth), TH(P * G), batch(gaps_per_batch(P)) {}
+    __host__ __device__ constexpr int pairs() const { return 0; }
+    __host__ __device__ constexpr int flux() const { return 2 * gpw * col; }
+    __host__ __device__ constexpr int wave_doubles() const { return flux() + batch * gpw * TH; }
+    __host__ __device__ constexpr size_t bytes() const { return (size_t)kRtWaves * wave_doubles() * sizeof(double); }
+};
+
+// k_raytrace_cont<P>: RtColumns with sqrt(alpha continuum) [gpw][col] behind the pairs and a second batch of flux terms for the
+// continuum chain; a wave's share is rounded up to an even number of doubles, so that every wave's pairs stay 16-byte aligned.
+struct RtContColumns {
+    int gpw, col, TH, batch;
+    __host__ __device__ constexpr RtContColumns(int P, int G, int n_depth, int gpw_)
+        : gpw(gpw_), col(n_depth), TH(P * G), batch(RtColumns::gaps_per_batch(P)) {}
+    __host__ __device__ constexpr int pairs() const { return 0; }
+    __host__ __device__ constexpr int cont() const { return 2 * gpw * col; }
+    __host__ __device__ constexpr int flux() const { return cont() + gpw * col; }
+    __host__ __device__ constexpr int flux_cont() const { return flux() + batch * gpw * TH; }
+    __host__ __device__ constexpr int wave_doubles() const { return (flux_cont() + batch * gpw * TH + 1) & ~1; }
+    __host__ __device__ constexpr size_t bytes() const { return (size_t)kRtWaves * wave_doubles() * sizeof(double); }
+};
+
+// k_raytrace_f32 (floats).  Shared by the block: the ray table [n_gap][n_theta], 1 / (k T) [col] and the relative temperature
+// differences [col], rounded up to whole float4s; then per wave the float4 of every point [gpw][col] and the flux terms [batch][gpw][G].
+constexpr int kRt32Batch = 8;  // gaps per flux reduction of k_raytrace_f32 (6 measured: no gain from the eighth block a CU's LDS then holds)
+struct RtF32Columns {
+    int n_gap, col, n_theta, G, gpw;
+    __host__ __device__ constexpr RtF32Columns(int n_theta_, int G_, int n_depth, int gpw_)
+        : n_gap(n_depth - 1), col(n_depth), n_theta(n_theta_), G(G_), gpw(gpw_) {}
+    __host__ __device__ constexpr int ray_table() const { return 0; }
+    __host__ __device__ constexpr int inv_kt() const { return n_gap * n_theta; }
+    __host__ __device__ constexpr int dtemp() const { return inv_kt() + col; }
+    __host__ __device__ constexpr int shared_floats() const { return (dtemp() + col + 3) & ~3; }
+    __host__ __device__ constexpr int points() const { return 0; }  // (this and flux(): from the wave's base)
+    __host__ __device__ constexpr int flux() const { return 4 * gpw * col; }
+    __host__ __device__ constexpr int wave_floats() const { return flux() + kRt32Batch * gpw * G; }
+    __host__ __device__ constexpr size_t bytes() const { return ((size_t)shared_floats() + (size_t)kRtWaves * wave_floats()) * sizeof(float); }
+};
+
+// k_raytrace_seg<NS, LMAX>, k_raytrace_seg_step<NS, LMAX, ..>, per workgroup of NS waves and gpw = 64 / n_theta frequencies: the
+// segment maps [NS][64][2]; the ray table TRANSPOSED [n_theta][rstride] with an odd row stride (the angles of a wave read distinct
+// banks); the (source, sqrt(alpha)) pairs [gpw][col], 16-byte aligned.  After the barrier of step 2 the flux terms [NS][LMAX][gpw][G]
+// reuse the space from the ray table on, so the launch asks for the larger of the two.
+struct RtSegments {
+    int NS, LMAX, n_theta, n_gap, col;
+    __host__ __device__ constexpr RtSegments(int NS_, int LMAX_, int n_theta_, int n_depth)
+        : NS(NS_), LMAX(LMAX_), n_theta(n_theta_), n_gap(n_depth - 1), col(n_depth) {}
+    __host__ __device__ constexpr int gpw() const { return 64 / n_theta; }
+    __host__ __device__ constexpr int segment() const { return (n_gap + NS - 1) / NS; }  // gaps per wave
+    __host__ __device__ constexpr int rstride() const { return n_gap | 1; }
+    __host__ __device__ constexpr int maps() const { return 0; }
+    __host__ __device__ constexpr int ray_table() const { return NS * 128; }
+    __host__ __device__ constexpr int pairs_from_table() const { return (n_theta * rstride() + 1) & ~1; }
+    __host__ __device__ constexpr int pairs() const { return ray_table() + pairs_from_table(); }
+    __host__ __device__ constexpr int flux() const { return ray_table(); }
+    __host__ __device__ constexpr int staging_end() const { return pairs() + 2 * gpw() * col; }
+    __host__ __device__ constexpr int flux_end() const { return flux() + NS * LMAX * gpw() * n_theta; }
+    __host__ __device__ constexpr int doubles() const { return staging_end() > flux_end() ? staging_end() : flux_end(); }
+    __host__ __device__ constexpr size_t bytes() const { return (size_t)doubles() * sizeof(double); }
+    // (what keeps a wave's gaps inside its LMAX register slots; the host checks it beside bytes())
+    __host__ __device__ constexpr bool segment_fits() const { return segment() <= LMAX; }
+};
+
+// ---- the host's choice of a launch shape ----------------------------------------------------------------------------------------
+// A model whose column alone is larger than LDS fits no layout; asked first, it also keeps every int above far from overflow.
+constexpr int kRtMaxDepth = (int)(kLdsBytes / sizeof(double));
+// Frequencies per wave of a per-wave layout (RtColumns, RtContColumns): 64 / G, lowered (idle lanes) until the staged columns fit LDS;
+// 0 when not even one frequency per wave does.
+template <class Layout>
+inline int rt_fit_gpw(int P, int G, int n_depth)
+{
+    if (n_depth > kRtMaxDepth) return 0;
+    int gpw = 64 / G;
+    while (gpw > 1 && Layout(P, G, n_depth, gpw).bytes() > kLdsBytes) --gpw;
+    return Layout(P, G, n_depth, gpw).bytes() <= kLdsBytes ? gpw : 0;
+}
+// Workgroups of kRtBlock threads that cover n_nu frequencies at gpw frequencies per wave.
+inline unsigned rt_blocks(long long n_nu, int gpw)
+{
+    return (unsigned)((n_nu + (long long)gpw * kRtWaves - 1) / ((long long)gpw * kRtWaves));
+}
+
+// ---- what the kernels rely on, at a few representative shapes --------------------------------------------------------------------
+namespace rt_layout_checks {
+constexpr bool even(int doubles) { return doubles % 2 == 0; }      // a double2 region: 16-byte aligned
+constexpr bool quad(int floats) { return floats % 4 == 0; }        // a float4 region
+constexpr bool columns_ok(int P, int G, int n_depth, int gpw)
+{
+    const RtColumns a(P, G, n_depth, gpw);
+    const RtContColumns c(P, G, n_depth, gpw);
+    return a.pairs() + 2 * gpw * n_depth <= a.flux() && a.flux() + a.batch * gpw * a.TH <= a.wave_doubles() && even(a.pairs()) && even(a.wave_doubles()) &&
+           c.pairs() + 2 * gpw * n_depth <= c.cont() && c.cont() + gpw * n_depth <= c.flux() && c.flux() + c.batch * gpw * c.TH <= c.flux_cont() &&
+           c.flux_cont() + c.batch * gpw * c.TH <= c.wave_doubles() && even(c.pairs()) && even(c.wave_doubles());
+}
+constexpr bool f32_ok(int n_theta, int n_depth)
+{
+    const RtF32Columns f(n_theta, n_theta, n_depth, 64 / n_theta);
+    return f.ray_table() + f.n_gap * n_theta <= f.inv_kt() && f.inv_kt() + n_depth <= f.dtemp() && f.dtemp() + n_depth <= f.shared_floats() &&
+           f.points() + 4 * f.gpw * n_depth <= f.flux() && f.flux() + kRt32Batch * f.gpw * f.G <= f.wave_floats() && quad(f.shared_floats()) && quad(f.points()) && quad(f.wave_floats());
+}
+constexpr bool segments_ok(int NS, int LMAX, int n_theta, int n_depth)
+{
+    const RtSegments s(NS, LMAX, n_theta, n_depth);
+    return s.maps() + NS * 128 <= s.ray_table() && s.ray_table() + n_theta * s.rstride() <= s.pairs() && even(s.pairs()) && s.rstride() % 2 == 1 &&
+           s.rstride() >= s.n_gap && s.flux() >= s.ray_table() && s.flux_end() <= s.doubles() && s.staging_end() <= s.doubles();
+}
+// one angle per lane at 3, 7 and 20 angles (odd row counts), two and four angles per lane, a deep model with gpw lowered
+static_assert(columns_ok(1, 3, 56, 21) && columns_ok(1, 7, 301, 3) && columns_ok(1, 20, 302, 2) && columns_ok(1, 5, 984, 1), "RtColumns / RtContColumns");
+static_assert(columns_ok(2, 4, 56, 16) && columns_ok(4, 5, 57, 12) && columns_ok(1, 20, 175, 2) && columns_ok(1, 64, 2, 1), "RtColumns / RtContColumns");
+static_assert(f32_ok(20, 56) && f32_ok(7, 57) && f32_ok(64, 2) && f32_ok(1, 3), "RtF32Columns");
+// even and odd gap counts, both segmentations, the shallowest models; the flux terms fit the launch whichever of the two is larger
+static_assert(segments_ok(8, 7, 20, 56) && segments_ok(8, 7, 7, 57) && segments_ok(4, 14, 20, 56) && segments_ok(8, 7, 64, 2) && segments_ok(8, 7, 1, 3),
+              "RtSegments");
+static_assert(RtSegments(8, 7, 20, 56).doubles() == RtSegments(8, 7, 20, 56).flux_end(), "20 angles: the flux terms are the larger");
+static_assert(RtSegments(8, 7, 1, 57).doubles() == RtSegments(8, 7, 1, 57).staging_end(), "one angle, 64 columns: the staging is the larger");
+}  // namespace rt_layout_checks

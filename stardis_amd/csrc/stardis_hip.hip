@@ -342,6 +342,14 @@ int launch_bf_coef(sdx_ctx* ctx, int n_depth, int n_species, int n_levels, const
     return check_launch("k_bf_coef");
 }
 
+// the formal solution's angles per lane P in {1, 2, 4} as a compile-time constant: f(std::integral_constant<int, P>)
+template <class F>
+void with_angles_per_lane(int P, F&& f)
+{
+    if (P == 1) f(std::integral_constant<int, 1>{});
+    else if (P == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 4>{});
+}
 }  // namespace
 
 // ================================================================================================ runtime
@@ -817,12 +825,9 @@ static int lane_recip(int G)
 {
     return 65536 / G + 1;
 }
-static size_t seg_lds_doubles(int n_depth, int nth)
+static RtSegments seg_layout(int n_depth, int nth)
 {
-    const int gpw = 64 / nth;
-    // segment maps, then the larger of the staging arrays (transposed ray table with an odd row stride, then — 16-byte aligned — the
-    // (source, sqrt(alpha)) pairs) and the flux terms that reuse their space
-    return (size_t)kSegWaves * 128 + std::max((((size_t)nth * ((n_depth - 1) | 1) + 1) & ~(size_t)1) + (size_t)2 * gpw * n_depth, (size_t)kSegWaves * kSegMax * gpw * nth);
+    return RtSegments(kSegWaves, kSegMax, nth, n_depth);
 }
 // Which kernel runs must not depend on how the grid is sharded or on the device (the two differ by the rounding of the affine
 // composition, a few ulp: a shard below the threshold next to an unsharded run above it would break the bit-identity of
@@ -840,7 +845,7 @@ static bool use_segmented_raytrace(const sdx_ctx* ctx, int n_depth, int64_t n_nu
 {
     const int mode = segmented_mode(ctx);
     if (mode == 0 || !plain || n_theta > 64) return false;
-    if ((n_depth - 1 + kSegWaves - 1) / kSegWaves > kSegMax || seg_lds_doubles(n_depth, n_theta) * sizeof(double) > 64 * 1024) return false;
+    if (!seg_layout(n_depth, n_theta).segment_fits() || seg_layout(n_depth, n_theta).bytes() > kLdsBytes) return false;
     if (mode >= 1) return true;
     const int64_t legacy_waves = (n_nu_global + 64 / n_theta - 1) / (64 / n_theta);
     return legacy_waves < kSegLegacyWaves;
@@ -1969,6 +1974,21 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
                          double* I_nus, int accumulate, int inward, const FusedTotal* fused = nullptr, int64_t nu_global = -1,
                          double* Fc = nullptr, int64_t fcld = 0);
 
+static const char* const kRtVariant[] = {"k_raytrace<1>", "k_raytrace<2>", "k_raytrace<4>"};  // [P / 2]
+static const char* const kRtContVariant[] = {"k_raytrace_cont<1>", "k_raytrace_cont<2>", "k_raytrace_cont<4>"};
+
+// the tail of spherical geometry: F_nu *= (r[-1] / reference_r)^2 (radiation_field_solvers/base.py:340-344); the continuum flux,
+// where there is one, in the same profiled launch scope
+static int scale_flux(sdx_ctx* ctx, int n_depth, int64_t n_nu, double* F, int64_t ld, double factor, double* Fc = nullptr, int64_t fcld = 0)
+{
+    {
+        LaunchScope ls(ctx, "k_scale");
+        hipLaunchKernelGGL(k_scale, grid2(n_nu, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, n_nu, F, ld, factor);
+        if (Fc) hipLaunchKernelGGL(k_scale, grid2(n_nu, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, n_nu, Fc, fcld, factor);
+    }
+    return check_launch("k_scale");
+}
+
 int sdx_raytrace_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
                      const double* ray_dist, const double* wts, const double* alphas, int64_t ald, double* F, int64_t fld,
                      double* I_nus, int accumulate)
@@ -1988,11 +2008,7 @@ int sdx_raytrace_source_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta
     int rc = raytrace_impl(ctx, n_depth, n_nu, n_theta, nus, temps, ray_dist, wts, alphas, ald, F, fld, I_nus, accumulate, inward ? 1 : 0,
                            source ? &ft : nullptr);
     if (rc || !inward || !F || n_nu == 0) return rc;
-    {
-        LaunchScope ls(ctx, "k_scale");
-        hipLaunchKernelGGL(k_scale, grid2(n_nu, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, n_nu, F, fld, photospheric_correction);
-    }
-    return check_launch("k_scale");
+    return scale_flux(ctx, n_depth, n_nu, F, fld, photospheric_correction);
 }
 
 int sdx_raytrace_spherical_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
@@ -2001,11 +2017,7 @@ int sdx_raytrace_spherical_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_th
 {
     int rc = raytrace_impl(ctx, n_depth, n_nu, n_theta, nus, temps, ray_dist, wts, alphas, ald, F, fld, I_nus, accumulate, 1);
     if (rc || !F || n_nu == 0) return rc;
-    {
-        LaunchScope ls(ctx, "k_scale");
-        hipLaunchKernelGGL(k_scale, grid2(n_nu, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, n_nu, F, fld, photospheric_correction);
-    }
-    return check_launch("k_scale");
+    return scale_flux(ctx, n_depth, n_nu, F, fld, photospheric_correction);
 }
 
 static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
@@ -2040,19 +2052,12 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
             if (v == 1 || v == 2 || v == 4) P = v;
         }
         const int G = (nth + P - 1) / P;
-        const int kbatch = P == 1 ? 4 : 2;
-        auto lds_bytes = [&](int groups) {  // per wave: source and sqrt(alpha) columns, flux terms of a batch of gaps
-            return ((size_t)(kRtBlock / 64) * (2 * (size_t)groups * n_depth + (size_t)kbatch * groups * P * G)) * sizeof(double);
-        };
-        int gpw = 64 / G;  // frequencies per wave; lowered (idle lanes) until the staged columns fit 64 KB of LDS
-        while (gpw > 1 && lds_bytes(gpw) > 64 * 1024) --gpw;
-        const size_t shmem = lds_bytes(gpw);
-        const unsigned blocks = (unsigned)((n_nu + (int64_t)gpw * (kRtBlock / 64) - 1) / ((int64_t)gpw * (kRtBlock / 64)));
+        const int gpw = rt_fit_gpw<RtColumns>(P, G, n_depth);  // 0: the columns do not fit LDS
         const unsigned blocks_basic = (unsigned)((n_nu + (int64_t)(64 / G) * (kBlock / 64) - 1) / ((int64_t)(64 / G) * (kBlock / 64)));
         // plane-parallel, one angle per lane, nothing to add to, a small grid: the gaps of a ray split over the 8 waves of a
         // workgroup (k_raytrace_seg)
-        const int seg_gpw = 64 / nth;
-        const size_t seg_doubles = seg_lds_doubles(n_depth, nth);
+        const RtSegments seg = seg_layout(n_depth, nth);
+        const int seg_gpw = seg.gpw();
         // the launch geometry of the XCD-aware order, handed to the kernel: workgroups, workgroups per XCD, whole rounds of eight
         const unsigned seg_wg = (unsigned)((n_nu + seg_gpw - 1) / seg_gpw), seg_per_xcd = (seg_wg + 7) / 8, seg_blocks = seg_per_xcd * 8;
         if (use_segmented_raytrace(ctx, n_depth, nu_global, n_theta, P == 1 && !inward && !acc)) {
@@ -2062,12 +2067,12 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
             const bool step_shape = segmented_mode(ctx) != 1 && kSegWaves == 8 && ft.cont && !ft.source && ft.n_extra == 0 && !ft.line_out && !inus && F &&
                                     (step_planes == 0 || step_planes == 2 || step_planes == 3);
             SegStepGeom geo{};
-            geo.gpw = seg_gpw, geo.g_recip = lane_recip(nth), geo.per = 64 / nth, geo.L = (n_depth - 1 + kSegWaves - 1) / kSegWaves;
-            geo.rstride = (n_depth - 1) | 1, geo.sp_off = (nth * geo.rstride + 1) & ~1, geo.gpw_magic = small_div_magic(seg_gpw);
+            geo.gpw = seg_gpw, geo.g_recip = lane_recip(nth), geo.per = 64 / nth, geo.L = seg.segment();
+            geo.rstride = seg.rstride(), geo.sp_off = seg.pairs_from_table(), geo.gpw_magic = small_div_magic(seg_gpw);
             geo.n_wg = seg_wg, geo.per_xcd = seg_per_xcd;
             auto launch_step = [&](int planes_n, const double* planes, double* total_out, double* flux, int64_t flux_ld) {
 #define SDX_STEP_LAUNCH(NP, KEEP)                                                                                                              \
-    hipLaunchKernelGGL((k_raytrace_seg_step<8, 7, NP, KEEP>), dim3(seg_blocks), dim3(512), seg_doubles * sizeof(double), ctx->stream, n_depth, n_nu, nth, \
+    hipLaunchKernelGGL((k_raytrace_seg_step<8, 7, NP, KEEP>), dim3(seg_blocks), dim3(512), seg.bytes(), ctx->stream, n_depth, n_nu, nth, \
                        n_theta, nus, temps, rd, w, ft.cont, ft.cld, planes, ft.pld, total_out, ft.out_ld, flux, flux_ld, geo)
                 if (planes_n == 0) {
                     if (total_out) SDX_STEP_LAUNCH(0, true);
@@ -2081,15 +2086,21 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
                 }
 #undef SDX_STEP_LAUNCH
             };
+            // the general kernel: the total as the caller asked for it, or the continuum plane alone
+            auto launch_seg = [&](const double* a, int64_t a_ld, double* flux, int64_t flux_ld, double* intensity, const FusedTotal& fused_total) {
+                auto launch = [&](auto kernel) {
+                    hipLaunchKernelGGL(kernel, dim3(seg_blocks), dim3(64 * kSegWaves), seg.bytes(), ctx->stream, n_depth, n_nu, nth, n_theta, nus, temps, rd, w,
+                                       a, a_ld, flux, flux_ld, intensity, seg_gpw, lane_recip(nth), seg_wg, seg_per_xcd, fused_total);
+                };
+                if (kSegWaves == 4) launch(k_raytrace_seg<4, 14>);
+                else launch(k_raytrace_seg<8, 7>);
+            };
             if (step_shape) {
                 LaunchScope ls(ctx, "k_raytrace", "k_raytrace_seg_step<8,7>");
                 launch_step(step_planes, ft.planes, ft.total_out, F, fld);
             } else {
                 LaunchScope ls(ctx, "k_raytrace", kSegWaves == 4 ? "k_raytrace_seg<4,14>" : "k_raytrace_seg<8,7>");
-#define SDX_SEG_ARGS n_depth, n_nu, nth, n_theta, nus, temps, rd, w, alphas, ald, F, fld, inus, seg_gpw, lane_recip(nth), seg_wg, seg_per_xcd, ft
-                if (kSegWaves == 4) hipLaunchKernelGGL((k_raytrace_seg<4, 14>), dim3(seg_blocks), dim3(256), seg_doubles * sizeof(double), ctx->stream, SDX_SEG_ARGS);
-                else hipLaunchKernelGGL((k_raytrace_seg<8, 7>), dim3(seg_blocks), dim3(512), seg_doubles * sizeof(double), ctx->stream, SDX_SEG_ARGS);
-#undef SDX_SEG_ARGS
+                launch_seg(alphas, ald, F, fld, inus, ft);
             }
             int rc = check_launch("k_raytrace_seg");
             if (rc) return rc;
@@ -2105,10 +2116,7 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
                     launch_step(0, nullptr, nullptr, Fc, fcld);
                 } else {
                     LaunchScope ls(ctx, "k_raytrace", kSegWaves == 4 ? "k_raytrace_seg<4,14> (continuum)" : "k_raytrace_seg<8,7> (continuum)");
-#define SDX_SEG_ARGS n_depth, n_nu, nth, n_theta, nus, temps, rd, w, nullptr, 0, Fc, fcld, nullptr, seg_gpw, lane_recip(nth), seg_wg, seg_per_xcd, fc
-                    if (kSegWaves == 4) hipLaunchKernelGGL((k_raytrace_seg<4, 14>), dim3(seg_blocks), dim3(256), seg_doubles * sizeof(double), ctx->stream, SDX_SEG_ARGS);
-                    else hipLaunchKernelGGL((k_raytrace_seg<8, 7>), dim3(seg_blocks), dim3(512), seg_doubles * sizeof(double), ctx->stream, SDX_SEG_ARGS);
-#undef SDX_SEG_ARGS
+                    launch_seg(nullptr, 0, Fc, fcld, nullptr, fc);
                 }
                 if ((rc = check_launch("k_raytrace_seg"))) return rc;
             }
@@ -2117,14 +2125,12 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
         // the tolerance path (mixed_precision = 1): plane-parallel, all angles in one launch, flux only -> the fp32 recurrence
         if (ctx->mixed_precision && P == 1 && !inward && !acc && !inus && F && n_theta <= 64) {
             const int g32 = 64 / G;
-            const size_t shmem32 = ((((size_t)(n_depth - 1) * nth + 2 * (size_t)n_depth + 3) & ~(size_t)3) +
-                                    (size_t)(kRtBlock / 64) * (4 * (size_t)g32 * n_depth + kRt32Batch * (size_t)g32 * G)) * sizeof(float);
-            if (shmem32 <= 64 * 1024) {
+            const RtF32Columns lay32(nth, G, n_depth, g32);
+            if (n_depth <= kRtMaxDepth && lay32.bytes() <= kLdsBytes) {
                 {
                     LaunchScope ls(ctx, "k_raytrace", "k_raytrace_f32");
-                    const unsigned blocks32 = (unsigned)((n_nu + (int64_t)g32 * (kRtBlock / 64) - 1) / ((int64_t)g32 * (kRtBlock / 64)));
-                    hipLaunchKernelGGL(k_raytrace_f32, dim3(blocks32), dim3(kRtBlock), shmem32, ctx->stream, n_depth, n_nu, nth, n_theta, G, nus, temps, rd, w, alphas,
-                                       ald, F, fld, g32, ft);
+                    hipLaunchKernelGGL(k_raytrace_f32, dim3(rt_blocks(n_nu, g32)), dim3(kRtBlock), lay32.bytes(), ctx->stream, n_depth, n_nu, nth, n_theta, G, nus, temps, rd,
+                                       w, alphas, ald, F, fld, g32, ft);
                 }
                 int rc = check_launch("k_raytrace_f32");
                 if (rc) return rc;
@@ -2132,43 +2138,35 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
             }
         }
         if (Fc) {
-            REQUIRE(shmem <= 64 * 1024, "raytrace: no continuum flux for models this deep (the columns do not fit LDS)");
-            auto lds_cont = [&](int groups) {  // per wave: (S, sqrt(alpha)) pairs, sqrt(alpha continuum), flux terms of both chains;
-                // an even number of doubles, so that every wave's pairs stay 16-byte aligned (k_raytrace_cont)
-                return ((size_t)(kRtBlock / 64) * ((3 * (size_t)groups * n_depth + 2 * (size_t)kbatch * groups * P * G + 1) & ~(size_t)1)) * sizeof(double);
-            };
-            int gpwc = 64 / G;
-            while (gpwc > 1 && lds_cont(gpwc) > 64 * 1024) --gpwc;
-            const size_t shmemc = lds_cont(gpwc);
-            REQUIRE(shmemc <= 64 * 1024, "raytrace: no continuum flux for models this deep (the columns do not fit LDS)");
-            const unsigned blocksc = (unsigned)((n_nu + (int64_t)gpwc * (kRtBlock / 64) - 1) / ((int64_t)gpwc * (kRtBlock / 64)));
+            REQUIRE(gpw > 0, "raytrace: no continuum flux for models this deep (the columns do not fit LDS)");
+            const int gpwc = rt_fit_gpw<RtContColumns>(P, G, n_depth);
+            REQUIRE(gpwc > 0, "raytrace: no continuum flux for models this deep (the columns do not fit LDS)");
             {
-                LaunchScope ls(ctx, "k_raytrace", P == 1 ? "k_raytrace_cont<1>" : (P == 2 ? "k_raytrace_cont<2>" : "k_raytrace_cont<4>"));
-#define SDX_RTC_ARGS n_depth, n_nu, nth, n_theta, G, nus, temps, rd, w, F, fld, Fc, fcld, inus, inward, gpwc, ft
-                if (P == 1) hipLaunchKernelGGL(k_raytrace_cont<1>, dim3(blocksc), dim3(kRtBlock), shmemc, ctx->stream, SDX_RTC_ARGS);
-                else if (P == 2) hipLaunchKernelGGL(k_raytrace_cont<2>, dim3(blocksc), dim3(kRtBlock), shmemc, ctx->stream, SDX_RTC_ARGS);
-                else hipLaunchKernelGGL(k_raytrace_cont<4>, dim3(blocksc), dim3(kRtBlock), shmemc, ctx->stream, SDX_RTC_ARGS);
-#undef SDX_RTC_ARGS
+                LaunchScope ls(ctx, "k_raytrace", kRtContVariant[P / 2]);
+                with_angles_per_lane(P, [&](auto p) {
+                    hipLaunchKernelGGL(k_raytrace_cont<decltype(p)::value>, dim3(rt_blocks(n_nu, gpwc)), dim3(kRtBlock), RtContColumns(P, G, n_depth, gpwc).bytes(),
+                                       ctx->stream, n_depth, n_nu, nth, n_theta, G, nus, temps, rd, w, F, fld, Fc, fcld, inus, inward, gpwc, ft);
+                });
             }
             int rc = check_launch("k_raytrace_cont");
             if (rc) return rc;
             continue;
         }
         {
-            LaunchScope ls(ctx, "k_raytrace", shmem <= 64 * 1024 ? (P == 1 ? "k_raytrace<1>" : (P == 2 ? "k_raytrace<2>" : "k_raytrace<4>")) : "k_raytrace_basic");
-#define SDX_RT_ARGS n_depth, n_nu, nth, n_theta, G, nus, temps, rd, w, alphas, ald, F, fld, inus, acc
-            if (shmem <= 64 * 1024) {
-                if (P == 1) hipLaunchKernelGGL(k_raytrace<1>, dim3(blocks), dim3(kRtBlock), shmem, ctx->stream, SDX_RT_ARGS, inward, gpw, ft);
-                else if (P == 2) hipLaunchKernelGGL(k_raytrace<2>, dim3(blocks), dim3(kRtBlock), shmem, ctx->stream, SDX_RT_ARGS, inward, gpw, ft);
-                else hipLaunchKernelGGL(k_raytrace<4>, dim3(blocks), dim3(kRtBlock), shmem, ctx->stream, SDX_RT_ARGS, inward, gpw, ft);
-            } else {  // very deep models: the column does not fit LDS, recompute per lane instead
+            LaunchScope ls(ctx, "k_raytrace", gpw > 0 ? kRtVariant[P / 2] : "k_raytrace_basic");
+            if (gpw == 0) {  // very deep models: the column does not fit LDS, recompute per lane instead
                 REQUIRE(!ft.cont && !ft.source, "raytrace: fused total / caller's source plane not available for models this deep");
                 REQUIRE(!inward, "raytrace: spherical geometry needs (3*n_depth*64/n_theta + 2*n_depth*n_theta) doubles of LDS per wave; model too deep");
-                if (P == 1) hipLaunchKernelGGL(k_raytrace_basic<1>, dim3(blocks_basic), dim3(kBlock), 0, ctx->stream, SDX_RT_ARGS);
-                else if (P == 2) hipLaunchKernelGGL(k_raytrace_basic<2>, dim3(blocks_basic), dim3(kBlock), 0, ctx->stream, SDX_RT_ARGS);
-                else hipLaunchKernelGGL(k_raytrace_basic<4>, dim3(blocks_basic), dim3(kBlock), 0, ctx->stream, SDX_RT_ARGS);
             }
-#undef SDX_RT_ARGS
+            with_angles_per_lane(P, [&](auto p) {
+                constexpr int kP = decltype(p)::value;
+                if (gpw > 0)
+                    hipLaunchKernelGGL(k_raytrace<kP>, dim3(rt_blocks(n_nu, gpw)), dim3(kRtBlock), RtColumns(P, G, n_depth, gpw).bytes(), ctx->stream, n_depth, n_nu, nth,
+                                       n_theta, G, nus, temps, rd, w, alphas, ald, F, fld, inus, acc, inward, gpw, ft);
+                else
+                    hipLaunchKernelGGL(k_raytrace_basic<kP>, dim3(blocks_basic), dim3(kBlock), 0, ctx->stream, n_depth, n_nu, nth, n_theta, G, nus, temps, rd, w,
+                                       alphas, ald, F, fld, inus, acc);
+            });
         }
         int rc = check_launch("k_raytrace");
         if (rc) return rc;
@@ -2214,23 +2212,17 @@ int sdx_contribution_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
     REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "contribution: need n_depth >= 2, n_theta > 0");
     REQUIRE(!ctx->mixed_precision, "contribution: no contribution function with mixed_precision = 1 (it decomposes the fp64 formal solution)");
     REQUIRE(n_theta <= 64, "contribution: more than 64 angles are not supported (all angles are traced in one launch)");
-    constexpr int P = 1, kbatch = 4;
+    constexpr int P = 1;
     const int G = n_theta;
-    auto lds_bytes = [&](int groups) {  // per wave: (S, sqrt(alpha)) pairs, flux terms of a batch of gaps (k_raytrace<1>'s budget)
-        return ((size_t)(kRtBlock / 64) * (2 * (size_t)groups * n_depth + (size_t)kbatch * groups * P * G)) * sizeof(double);
-    };
-    int gpw = 64 / G;  // frequencies per wave; lowered (idle lanes) until the staged columns fit 64 KB of LDS
-    while (gpw > 1 && lds_bytes(gpw) > 64 * 1024) --gpw;
-    const size_t shmem = lds_bytes(gpw);
-    REQUIRE(shmem <= 64 * 1024, "contribution: no contribution function for models this deep (the columns do not fit LDS)");
+    const int gpw = rt_fit_gpw<RtColumns>(P, G, n_depth);  // (k_raytrace<1>'s budget)
+    REQUIRE(gpw > 0, "contribution: no contribution function for models this deep (the columns do not fit LDS)");
     if (n_nu == 0) return SDX_OK;
     REQUIRE(nus && ray_dist && wts && alphas && ald >= n_nu && C && cld >= n_nu, "contribution: null pointer or leading dimension below n_nu");
     REQUIRE(source ? source_ld >= n_nu : temps != nullptr, "contribution: bad source plane (source_ld < n_nu), or neither a source plane nor temperatures");
-    const unsigned blocks = (unsigned)((n_nu + (int64_t)gpw * (kRtBlock / 64) - 1) / ((int64_t)gpw * (kRtBlock / 64)));
     {
         LaunchScope ls(ctx, "k_contribution", "k_contribution<1>");
-        hipLaunchKernelGGL(k_contribution<1>, dim3(blocks), dim3(kRtBlock), shmem, ctx->stream, n_depth, n_nu, n_theta, n_theta, G, nus, temps, ray_dist,
-                           wts, alphas, ald, source, source_ld, C, cld, gpw);
+        hipLaunchKernelGGL(k_contribution<P>, dim3(rt_blocks(n_nu, gpw)), dim3(kRtBlock), RtColumns(P, G, n_depth, gpw).bytes(), ctx->stream, n_depth, n_nu, n_theta, n_theta, G,
+                           nus, temps, ray_dist, wts, alphas, ald, source, source_ld, C, cld, gpw);
     }
     return check_launch("k_contribution");
 }
@@ -2329,14 +2321,13 @@ static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
     REQUIRE(!Fc || opt->continuum_ld >= nu_count, "synthesize: continuum_ld must cover the columns");
     for (int k = 0; k < n_extra; ++k) REQUIRE(opt->line_plane[k] && opt->line_plane_ld >= nu_count, "synthesize: bad line plane");
     // the formal solution forms total = continuum + line planes while staging its columns when those fit LDS
-    const size_t lds_columns = ((size_t)(kRtBlock / 64) * (2 * (size_t)n_depth + 4 * 64)) * sizeof(double);  // k_raytrace with one frequency per wave
-    const bool fuse = n_theta <= 64 && lds_columns <= 64 * 1024;
-    // a continuum request that cannot be served is refused here, before anything is enqueued (k_raytrace_cont: one frequency per
-    // wave, one more column and a second batch of flux terms)
+    // (k_raytrace<1> at G = 64: one frequency per wave and the flux terms of 64 lanes, the worst case whatever n_theta is)
+    const bool fuse = n_theta <= 64 && rt_fit_gpw<RtColumns>(1, 64, n_depth) > 0;
+    // a continuum request that cannot be served is refused here, before anything is enqueued (k_raytrace_cont<1>, also at G = 64:
+    // deliberately the conservative limit, not the layout at this n_theta)
     REQUIRE(!Fc || !ctx->mixed_precision, "synthesize: no continuum flux with mixed_precision = 1 (the fp32 formal solution has no continuum chain)");
     REQUIRE(!Fc || fuse, "synthesize: the continuum flux needs the fused total (n_theta <= 64 and the model's columns in LDS)");
-    REQUIRE(!Fc || (size_t)(kRtBlock / 64) * ((3 * (size_t)n_depth + 2 * 4 * 64 + 1) & ~(size_t)1) * sizeof(double) <= 64 * 1024,
-            "synthesize: no continuum flux for models this deep (the columns do not fit LDS)");
+    REQUIRE(!Fc || rt_fit_gpw<RtContColumns>(1, 64, n_depth) > 0, "synthesize: no continuum flux for models this deep (the columns do not fit LDS)");
     if (nu_count == 0) return SDX_OK;
     // Three launches on one stream: [pre-pass + continuum plane] -> [wide + narrow line kernels] -> [raytrace, which
     // forms total = continuum + line while staging its columns].  Independent work shares a launch instead of a
@@ -2348,14 +2339,7 @@ static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
     // (radiation_field_solvers/base.py:141-198, :340-344)
     auto finish = [&](int rc_trace) -> int {
         if (rc_trace || !inward) return rc_trace;
-        {
-            LaunchScope ls(ctx, "k_scale");
-            hipLaunchKernelGGL(k_scale, grid2(nu_count, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, nu_count, F_nu, ld, opt->photospheric_correction);
-            if (Fc)
-                hipLaunchKernelGGL(k_scale, grid2(nu_count, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, nu_count, Fc, opt->continuum_ld,
-                                   opt->photospheric_correction);
-        }
-        return check_launch("k_scale");
+        return scale_flux(ctx, n_depth, nu_count, F_nu, ld, opt->photospheric_correction, Fc, Fc ? opt->continuum_ld : 0);
     };
     const ContinuumJob job{cont, nu_begin, nu_count, cont_plane};
     const double* part = nullptr;

@@ -10,6 +10,7 @@ from stardis_amd import constants as K
 from stardis_amd import synth
 from stardis_amd.engine import SpectralSynthesizer, shard_bounds
 from stardis_amd.postprocess import DeviceSpectrum
+from test_gpu_engine import deep_atmosphere
 
 pytestmark = pytest.mark.gpu
 
@@ -54,14 +55,28 @@ def test_continuum_flux_is_the_zero_line_flux(ctx, seg_mode, tag, n_lines):
     zero.close()
 
 
-@pytest.mark.parametrize("n_theta", [1, 4, 20])
-def test_continuum_flux_against_oracle_raytrace(ctx, n_theta):
+@pytest.mark.parametrize("n_theta,n_depth", [(1, 56), (4, 56), (20, 56), (20, 174), (20, 175)], ids=["1", "4", "20", "20-174deep", "20-175deep"])
+def test_continuum_flux_against_oracle_raytrace(ctx, n_theta, n_depth):
+    """The solar structure as it is (56 depths), and resampled to 174 and 175: at 20 angles k_raytrace_cont<1> stages 3 frequencies
+    per wave up to 174 depths and 2 from 175 on (its third column and second batch of flux terms), where k_raytrace<1> still stages 3."""
     w = synth.make_workload("S-c1", n_lines=300)
+    if n_depth != 56:
+        w["atm"] = deep_atmosphere(n_depth)
+        w["lines"] = synth.synth_lines(w["nus"], w["atm"], 300)
+        w["cont"] = synth.synth_continuum_state(w["atm"])
     th, wt = synth.thetas_and_weights(n_theta)
     zero = run(ctx, w, no_lines(w["atm"]["temperatures"].size), thetas=th, weights=wt)
     cont_total = zero.total_alphas()
     zero.close()
-    syn = run(ctx, w, w["lines"], thetas=th, weights=wt, keep_continuum_flux=True)
+    ctx.call("sdx_profile_enable", 1)
+    ctx.call("sdx_profile_reset")
+    try:
+        syn = run(ctx, w, w["lines"], thetas=th, weights=wt, keep_continuum_flux=True)
+        variant = ctx.profile_variant("k_raytrace")
+    finally:
+        ctx.call("sdx_profile_enable", 0)
+    if n_depth != 56:
+        assert variant == "k_raytrace_cont<1>"
     atm = w["atm"]
     ref, _ = oracle.raytrace(w["nus"], atm["temperatures"], atm["dist"], th, wt, cont_total)
     assert rel_err(syn.F_nu_continuum, ref) <= 1e-10

@@ -318,11 +318,9 @@ def test_refusals_before_any_launch(ctx, sc2):
     assert np.array_equal(d_C.numpy(), before, equal_nan=True)
 
 
-def test_deep_model_with_lowered_groups_per_wave(ctx):
-    """300 depths x 5 angles: the staged columns of 12 frequencies per wave would not fit 64 KB of LDS, so the launch lowers the
-    frequencies per wave to 3 (idle lanes), as k_raytrace<1> does: same sum identity, same agreement with the restatement."""
+def deep_model(ctx, n_depth, n_theta):
+    """the g7 columns resampled to n_depth points: the sum identity against k_raytrace<1>'s flux, and the numpy restatement"""
     g7 = load_golden("g7_raytrace")
-    n_depth, n_theta = 300, 5
     pos = np.linspace(0.0, g7["temperatures"].size - 1.0, n_depth)
     rows = np.arange(g7["temperatures"].size, dtype=np.float64)
     cols = np.ones(g7["nus"].size, bool)
@@ -339,9 +337,22 @@ def test_deep_model_with_lowered_groups_per_wave(ctx):
         F, _ = ops.raytrace_arrays(nus, temps, ray, w, total, ctx=ctx)
     finally:
         ctx.set_option("segmented_raytrace", -1)
-    sum_identity(Cg, F[-1], "300 depths x 5 angles")
+    sum_identity(Cg, F[-1], f"{n_depth} depths x {n_theta} angles")
     C_ref = cref.contribution_function(nus, temps, ray, w, total)
     F_ref = C_ref.sum(axis=0)
     err = np.abs(Cg - C_ref) / F_ref
-    print(f"300 depths x 5 angles against the numpy restatement: max |C_gpu - C_ref| / F_ref[-1] = {err.max():.3e}")
+    print(f"{n_depth} depths x {n_theta} angles against the numpy restatement: max |C_gpu - C_ref| / F_ref[-1] = {err.max():.3e}")
     assert np.all(np.abs(Cg - C_ref) <= FLUX_TOL * F_ref)
+
+
+def test_deep_model_with_lowered_groups_per_wave(ctx):
+    """300 depths x 5 angles: the staged columns of 12 frequencies per wave would not fit 64 KB of LDS, so the launch lowers the
+    frequencies per wave to 3 (idle lanes), as k_raytrace<1> does: same sum identity, same agreement with the restatement."""
+    deep_model(ctx, 300, 5)
+
+
+@pytest.mark.parametrize("n_depth", [301, 302])
+def test_deep_model_either_side_of_a_lowered_group(ctx, n_depth):
+    """20 angles: the last depth at which 3 frequencies per wave fit LDS and the first at which the launch lowers them to 2 — where a
+    launch sized by another layout than the kernel's first shows."""
+    deep_model(ctx, n_depth, 20)

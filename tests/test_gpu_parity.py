@@ -256,13 +256,20 @@ def test_raytrace_many_angles_chunks(ctx):
     assert rel_err(F, ref) < FLUX_RTOL
 
 
+# where the LDS layout of k_raytrace<1> changes the launch at 20 angles: 3 frequencies per wave up to 301 depths, 2 from 302 on; the
+# columns of one frequency per wave fit up to 984 depths, from 985 on k_raytrace_basic recomputes them per lane
+LAYOUT_EDGES = {301: "k_raytrace<1>", 302: "k_raytrace<1>", 984: "k_raytrace<1>", 985: "k_raytrace_basic"}
+
+
 @pytest.mark.parametrize("n_depth,n_theta,n_nu", [(2, 3, 5), (3, 1, 70), (9, 7, 33), (30, 20, 200), (57, 20, 100), (57, 64, 9),
-                                                  (58, 20, 50), (12, 33, 17), (56, 20, 3000)])
+                                                  (58, 20, 50), (12, 33, 17), (56, 20, 3000), (301, 20, 7), (302, 20, 7), (984, 20, 5),
+                                                  (985, 20, 5)])
 def test_raytrace_fresh_flux_shapes(ctx, n_depth, n_theta, n_nu):
     """A flux that is written, not added to, on grids of every shape: small plane-parallel grids take the segmented formal
     solution (the gaps of a ray over the 8 waves of a workgroup: segments of 1..7 gaps, idle trailing waves, angle counts
     that do not divide 64, one frequency in the last workgroup), the rest the one-wave-per-ray kernel — both against the oracle,
-    intensities included (radiation_field_solvers/base.py:85-268)."""
+    intensities included (radiation_field_solvers/base.py:85-268).  The deep shapes (LAYOUT_EDGES) sit on either side of the depths
+    at which the staged columns stop fitting LDS, where a launch sized by another layout than the kernel's first goes wrong."""
     rng = np.random.default_rng(100 * n_depth + n_theta)
     temps = np.linspace(3900.0, 9500.0, n_depth)
     dist = rng.uniform(2e5, 4e6, n_depth - 1)
@@ -272,7 +279,15 @@ def test_raytrace_fresh_flux_shapes(ctx, n_depth, n_theta, n_nu):
         alphas[:, 3] = 0.0  # a transparent column (:203-206)
     th, w = synth.thetas_and_weights(n_theta)
     rd = dist.reshape(-1, 1) / np.cos(th)
-    F, I = ops.raytrace_arrays(nus, temps, rd, w, alphas, track=True)
+    ctx.call("sdx_profile_enable", 1)
+    ctx.call("sdx_profile_reset")
+    try:
+        F, I = ops.raytrace_arrays(nus, temps, rd, w, alphas, track=True)
+        variant = ctx.profile_variant("k_raytrace")
+    finally:
+        ctx.call("sdx_profile_enable", 0)
+    if n_depth in LAYOUT_EDGES:
+        assert variant == LAYOUT_EDGES[n_depth]
     ref, Iref = oracle.raytrace(nus, temps, dist, th, w, alphas, track=True)
     # random columns are far rougher than an atmosphere: where the intensity passes through ~1e-6 of its scale the
     # reference's own formulas lose six digits (both kernels and the oracle differ there by the same 1e-9), so the error is
