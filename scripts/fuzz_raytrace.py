@@ -6,7 +6,7 @@ mixed within one ray, plane-parallel and spherical (inward sweep + photospheric 
 to, with and without tracked intensities, and the fp32 formal solution of the mixed mode against the fp64 one.
 Criterion: on random rough columns the reference's formulas are ill-conditioned (w1 = w0 - tau e^-tau, w2 = 2 w1 - tau^2 e^-tau for
 tau >= 5e-4: one ulp of exp times 1 / tau^3), so the double-precision oracle itself is 1e-9 .. 4e-7 from an exact evaluation of the
-same formulas; the GPU is therefore measured against an 80-bit evaluation (scripts/r4/rt_truth.py) and must be no further from it
+same formulas; the GPU is therefore measured against an 80-bit evaluation (tests/formal_solution_truth.py) and must be no further from it
 than four times the oracle's own distance (+ 1e-10; over 200 seeds the ratio was below 1.2 in all but two cases: 2.4 and 3.2).
 python scripts/fuzz_raytrace.py FIRST LAST"""
 import os, sys, traceback
@@ -14,8 +14,8 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root)
 import numpy as np
 import oracle
-sys.path.insert(0, os.path.join(root, "scripts", "r4"))
-from rt_truth import truth
+sys.path.insert(0, os.path.join(root, "tests"))
+from formal_solution_truth import truth
 from stardis_amd import ops, synth
 from stardis_amd._lib import default_context
 

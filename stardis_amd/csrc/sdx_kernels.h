@@ -3865,7 +3865,8 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
     double c[LMAX], e[LMAX];
     double A = 1.0, B = 0.0;
     // the unrolled pass carries no per-lane exception handling: a lane with anything unusual (a transparent gap, a denominator
-    // outside the normal range) only raises the wave's flag, and the wave then redoes its segment in the reference's own form
+    // outside the normal range) only raises the wave's flag, and the wave then walks its segment once more, the flagged lanes'
+    // steps in the reference's own form
     unsigned long long redo = 0;
     const int gc = count > 0 ? g_lo : 0;
     const RtConst kc = rt_const_resident();  // the step's literals, in scalar registers from here on (sdx_math.h)
@@ -3904,12 +3905,15 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
             const int gap = gc + j - j0;
             const double s0 = sP[gi + gap].x, s1 = sP[gi + gap + 1].x;
             const double t0 = mul_rn(sP[gi + gap].y * sP[gi + gap + 1].y, sRT[th * rstride + gap]);
-            double cj, ej;
+            double cj = 1.0, ej = 0.0;  // (the lanes that did not raise the flag keep the fast pass's pair)
+#pragma unroll
+            for (int k = 0; k < LMAX; ++k)
+                if (k == j) cj = c[k], ej = e[k];
             if (gap < n_gap - 1) {
                 const double t1 = mul_rn(sP[gi + gap + 1].y * sP[gi + gap + 2].y, sRT[th * rstride + gap + 1]);
-                rt_coef_reference<false>(t0, t1, s0 - s1, sP[gi + gap + 2].x - s1, s1, cj, ej);
+                if (rt_coef_is_unusual<false>(t0, t1)) rt_coef_reference<false>(t0, t1, s0 - s1, sP[gi + gap + 2].x - s1, s1, cj, ej);
             } else {
-                rt_coef_reference<true>(t0, 0.0, s0 - s1, 0.0, s1, cj, ej);
+                if (rt_coef_is_unusual<true>(t0, 0.0)) rt_coef_reference<true>(t0, 0.0, s0 - s1, 0.0, s1, cj, ej);
             }
             A *= cj;
             B = fma(cj, B, ej);
@@ -4073,18 +4077,21 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
             }
         }
     }
-    if (redo) {  // rare: the segment once more in the reference's own form
+    if (redo) {  // rare: the segment once more, the flagged lanes' steps in the reference's own form
         A = 1.0, B = 0.0;
         for (int j = j0; j < LMAX; ++j) {
             const int gap = gc + j - j0;
             const double s0 = sP[gi + gap].x, s1 = sP[gi + gap + 1].x;
             const double t0 = mul_rn(sP[gi + gap].y * sP[gi + gap + 1].y, sRT[th * rstride + gap]);
-            double cj, ej;
+            double cj = 1.0, ej = 0.0;  // (the lanes that did not raise the flag keep the fast pass's pair)
+#pragma unroll
+            for (int k = 0; k < LMAX; ++k)
+                if (k == j) cj = c[k], ej = e[k];
             if (gap < n_gap - 1) {
                 const double t1 = mul_rn(sP[gi + gap + 1].y * sP[gi + gap + 2].y, sRT[th * rstride + gap + 1]);
-                rt_coef_reference<false>(t0, t1, s0 - s1, sP[gi + gap + 2].x - s1, s1, cj, ej);
+                if (rt_coef_is_unusual<false>(t0, t1)) rt_coef_reference<false>(t0, t1, s0 - s1, sP[gi + gap + 2].x - s1, s1, cj, ej);
             } else {
-                rt_coef_reference<true>(t0, 0.0, s0 - s1, 0.0, s1, cj, ej);
+                if (rt_coef_is_unusual<true>(t0, 0.0)) rt_coef_reference<true>(t0, 0.0, s0 - s1, 0.0, s1, cj, ej);
             }
             A *= cj;
             B = fma(cj, B, ej);

@@ -548,6 +548,10 @@ __device__ __forceinline__ double planck_staged(double nu, double temp)
 // of 2).  Which lanes take the series (tau < 5e-4) is decided per lane, whether the block runs at all per wave.
 // Anything unusual — t0 = 0 (no change, :203-206), t1 = 0, a denominator that is zero, subnormal, infinite or NaN — is caught
 // by ONE class test of D and redone per lane in the reference's own form, IEEE divisions and all: the same inf / NaN pattern.
+// So is a product t0 t1 (the final gap: t0^2) below 2^-384: the numerator above is of the order (S0-S1) (t0 t1)^2 and underflows long
+// before D does — at tau ~ 1e-100 D ~ 1e-300 is still a normal number while every product of the numerator is zero, and the step
+// lost its second-order terms altogether, an error of the order of the step itself (tests/test_gpu_formal_solution_truth.py, class
+// `tiny`).  Above the bound the numerator keeps 2^-768 (S0-S1), a normal number for any source difference above 1e-77.
 // LAST: the final gap (:253-266), e = w0 S1 + w2 (S0 - S1) / t0^2.
 //
 // The literals of the step live in an RtConst.  A kernel fills one before its gap loop with rt_const_resident(): each member passes
@@ -560,15 +564,18 @@ struct RtConst {
     double tau_small;  // below: the series forms of the weights
     double tau_max;    // the clamp that makes the exponential form exact for tau >= 50
     double third;
+    int p_min_hi;      // t0 t1 below kRtProductMin is too small for the common-denominator form: the bound's upper word
 };
 __device__ __forceinline__ double sgpr_resident(double v)
 {
     asm volatile("" : "+s"(v));
     return v;
 }
+constexpr double kRtProductMin = 0x1p-384;
+constexpr int kRtProductMinHi = (1023 - 384) << 20;  // (a power of two: its lower word is zero)
 __host__ __device__ constexpr RtConst rt_const_literals()
 {
-    return {exp_literals(), 5e-4, 64.0, 1.0 / 3};
+    return {exp_literals(), 5e-4, 64.0, 1.0 / 3, kRtProductMinHi};
 }
 __device__ __forceinline__ RtConst rt_const_resident()
 {
@@ -581,6 +588,7 @@ __device__ __forceinline__ RtConst rt_const_resident()
     k.tau_small = sgpr_resident(k.tau_small);
     k.tau_max = sgpr_resident(k.tau_max);
     k.third = sgpr_resident(k.third);
+    asm volatile("" : "+s"(k.p_min_hi));
     return k;
 }
 __device__ __forceinline__ void rt_weights_wave(double tau, double& w0, double& w1, double& w2, const RtConst& k)
@@ -640,21 +648,35 @@ __device__ __forceinline__ unsigned long long rt_coef_fast(double t0, double t1,
 {
     double w0, w1, w2;
     rt_weights_wave(t0, w0, w1, w2, k);
-    double den;
+    double prod, den;
     if constexpr (LAST) {
-        den = t0 * t0;
+        prod = den = t0 * t0;
         e = fma(w0, s1, (w2 * d10) * recip(den));
     } else {
-        den = (t0 * t1) * (t0 + t1);
+        prod = t0 * t1;
+        den = prod * (t0 + t1);
         const double u = fma(w1, t1, w2), v = fma(-w1, t0, w2);
         const double num = fma(d10 * t1, u, (d21 * t0) * v);
         e = fma(w0, s1, num * recip(den));
     }
     c = 1.0 - w0;
     // (the wave mask straight from the compare: through a bool the compiler materialises 0 / 1 per lane and compares again)
-    unsigned long long unusual;
+    unsigned long long unusual, tiny;
     asm("v_cmp_class_f64 %0, %1, %2" : "=s"(unusual) : "v"(den), "s"(kClassUnusual));
-    return unusual;
+    // (a product of optical depths is no negative number, and of two non-negative doubles the smaller has the smaller upper word: a
+    // 32-bit compare against one resident SGPR serves; v_cmp_lt_f64 measured the same)
+    asm("v_cmp_lt_u32 %0, %1, %2" : "=s"(tiny) : "v"(__double2hiint(prod)), "s"(k.p_min_hi));
+    return unusual | tiny;
+}
+// the same question per lane in plain C++ (the same operations on the same operands: the same answer), for the segmented kernels'
+// replay of a flagged wave — only the lanes that raised the flag take the reference's form there, so that a column's value does not
+// depend on what else its wave holds
+template <bool LAST>
+__device__ __forceinline__ bool rt_coef_is_unusual(double t0, double t1)
+{
+    const double prod = LAST ? t0 * t0 : t0 * t1;
+    const double den = LAST ? prod : prod * (t0 + t1);
+    return !(den >= 0x1p-1022 && den <= 0x1.fffffffffffffp+1023) || (unsigned)__double2hiint(prod) < (unsigned)kRtProductMinHi;
 }
 template <bool LAST>
 __device__ __forceinline__ void rt_coef(double t0, double t1, double d10, double d21, double s1, double& c, double& e, const RtConst& k)

@@ -44,7 +44,8 @@ def test_contribution_kernel_resources(resources):  # noqa: F811
 
 def test_formal_solution_kernels_keep_their_figures(resources):  # noqa: F811
     assert {k: resources["k_raytrace<1>"][k] for k in ("vgpr", "spill", "occ")} == {"vgpr": 71, "spill": 0, "occ": 7}
-    assert {k: resources["k_raytrace_seg<8, 7>"][k] for k in ("vgpr", "spill", "occ")} == {"vgpr": 79, "spill": 0, "occ": 6}
+    # (77 since the flagged wave's replay keeps the fast pass's coefficients in the lanes that did not raise the flag; 79 before)
+    assert {k: resources["k_raytrace_seg<8, 7>"][k] for k in ("vgpr", "spill", "occ")} == {"vgpr": 77, "spill": 0, "occ": 6}
     assert resources["k_raytrace_cont<1>"]["spill"] == 0 and resources["k_raytrace_cont<1>"]["occ"] == 5
 
 

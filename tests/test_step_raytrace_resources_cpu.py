@@ -1,7 +1,7 @@
 """k_raytrace_seg_step at build time, read off the gfx950 assembly and the compiler's resource remarks (hipcc cross-compiles without a
 GPU): every instantiation free of spilled vector registers and of scratch at six waves per SIMD or more, no more spilled scalar
 registers than k_raytrace_seg<8, 7> in the same build, and — the point of the kernel — fewer instructions than it.  The general
-kernel is not touched: it keeps 79 VGPRs, no spill, six waves.
+kernel keeps its figures: 77 VGPRs (79 until the replay of a flagged wave became per lane), no spill, six waves.
 
 This tree: k_raytrace_seg<8, 7> 2204 instructions (1319 vector, 814 scalar), 19 spilled SGPRs behind 49 v_writelane / v_readlane;
 k_raytrace_seg_step<8, 7, 2, true> 1830 (1175 / 596), none spilled, 76 VGPRs (profiles/EXPERIMENTS.md)."""
@@ -64,4 +64,4 @@ def test_step_kernel_is_shorter_than_the_general_one(build):
 
 def test_general_kernel_keeps_its_figures(build):
     _, meta, occupancy = build
-    assert (meta[GENERAL]["vgpr_count"], meta[GENERAL]["vgpr_spill_count"], occupancy[GENERAL]) == (79, 0, 6), (meta[GENERAL], occupancy[GENERAL])
+    assert (meta[GENERAL]["vgpr_count"], meta[GENERAL]["vgpr_spill_count"], occupancy[GENERAL]) == (77, 0, 6), (meta[GENERAL], occupancy[GENERAL])
