@@ -426,6 +426,41 @@ int sdx_flux_nu_to_lambda_dev(sdx_ctx* ctx, int64_t n, const double* f_nu, const
 /* out[i] = a[i] / b[i] (the continuum-normalised spectrum: flux over continuum). */
 int sdx_divide_dev(sdx_ctx* ctx, int64_t n, const double* a, const double* b, double* out);
 
+/* ---- instrument model: Doppler shift, line-spread function, pixel integration ---------------------
+ * From a spectrum on the model's own grid to what a spectrograph records, in one launch (k_observe).  The reference has no
+ * counterpart: its rotation-broadening walk-through smooths the spectrum with scipy.ndimage.gaussian_filter1d at ONE sigma in grid
+ * points (mirrored by stardis_amd.postprocess.gaussian_filter1d), which is a line-spread function of constant resolving power only
+ * on a log-uniform grid, shifts nothing and rebins nothing.  This generalises it: the width is given per pixel in Angstrom, on any
+ * ascending grid.  fp64 whatever "mixed_precision" says; every operation below is one correctly rounded fp64 operation.
+ *   lambdas[n]     strictly ascending wavelengths (Angstrom), flux[n] the spectrum on them, reference[n] optional (NULL: none);
+ *   edges[n_pix+1] strictly ascending pixel edges (Angstrom), sigma[n_pix] > 0 the Gaussian width of the line-spread function at
+ *                  each pixel (Angstrom; constant resolving power R: sigma = centre / (R 2 sqrt(2 ln 2)));
+ *   D              the Doppler factor sqrt((1 + beta) / (1 - beta)), beta = v_rad / c: x_i = lambdas[i] D.  Only the wavelengths
+ *                  move; the flux is not rescaled.
+ * Trapezoid weights h_i = (x[i+1] - x[i-1]) / 2, at the ends h_0 = (x[1] - x[0]) / 2 and h_{n-1} = (x[n-1] - x[n-2]) / 2.  The Gaussian
+ * around x_i integrated over pixel j, with a = (edges[j] - x_i) / (sigma[j] sqrt 2), b = (edges[j+1] - x_i) / (sigma[j] sqrt 2):
+ *     r = 0.5 (erfc(a) - erfc(b))  where a > 0,   r = 0.5 (erfc(-b) - erfc(-a))  where b < 0,   r = 0.5 (erf(b) - erf(a))  otherwise
+ * (the tails keep their relative accuracy).  The window of pixel j is the points with lo_j <= x_i <= hi_j, lo_j = edges[j] - 8 sigma[j],
+ * hi_j = edges[j+1] + 8 sigma[j] (what lies outside is below 1e-15 of the sum), and over it
+ *     out[j] = (sum_i r h_i flux[i]) / (sum_i r h_i g_i),   g_i = 1, or reference[i]:
+ * with a reference the continuum-normalised observed spectrum, observe(flux) / observe(reference), from the same launch.  A pixel
+ * whose window the grid does not cover, !(lo_j >= x_0 && hi_j <= x_{n-1}), is NaN.
+ * out depends on the arrays alone: no floating-point atomics, and the order of the sums does not follow from the device or the
+ * launch — two calls, and the replay of a captured graph, give the same bits.
+ * sdx_observe_dev: device pointers, asynchronous on the context's stream, no allocation, no synchronisation (capturable).  The Doppler
+ * factor is read from device memory when the kernel runs (doppler_dev; NULL: 1), so a captured graph follows a new velocity without
+ * being recorded again.  n_pix = 0 returns at once; n < 2 or a null required pointer is SDX_ERR_ARG before anything is enqueued.  The
+ * arrays' contents cannot be checked here: whatever they hold (NaN, unordered values, sigma <= 0), every access stays inside the
+ * arrays and a pixel's loop runs at most n trips — the result is then meaningless, never an out-of-range access.
+ * Stage name for sdx_profile_get: "k_observe". */
+int sdx_observe_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
+                    const double* edges, const double* sigma, const double* doppler_dev, double* out);
+/* host-buffer twin: host pointers, the Doppler factor by value.  The arrays ARE checked here, before any upload: lambdas and edges
+ * finite and strictly ascending, sigma finite and > 0, doppler finite and > 0; anything else is SDX_ERR_ARG with a message that names
+ * the argument. */
+int sdx_observe_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
+                    const double* edges, const double* sigma, double doppler, double* out);
+
 /* Everything in one call for resident data: pre-pass + line opacity + total (above) + raytrace (F_nu
  * overwritten).  F_nu is [n_depth][ld].  alpha_line_out and total_alphas ([n_depth][ld]) are OPTIONAL outputs (NULL: the
  * plane is never written to HBM — the reference only reads them back through opacities_dict / Opacities.total_alphas;

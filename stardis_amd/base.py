@@ -11,14 +11,17 @@ from stardis_amd.radiation_field.base import create_stellar_radiation_field
 logger = logging.getLogger(__name__)
 
 
-def run_stardis(config_fname, tracing_lambdas_or_nus, add_config_dict=None, *, continuum=False, contribution=False):
+def run_stardis(config_fname, tracing_lambdas_or_nus, add_config_dict=None, *, continuum=False, contribution=False, instrument=None):
     """Same signature and return type as stardis.base.run_stardis.  continuum=True: the same single synthesis also traces the
     continuum, and the output gains spectrum_nu_continuum and spectrum_lambda_continuum (built as STARDISOutput builds
     spectrum_nu / spectrum_lambda, stardis/base.py:133-141) and spectrum_normalized = spectrum_nu / spectrum_nu_continuum —
     what a second run with opacity.line.disable (and no molecules) would give.
     contribution=True (plane-parallel models; combines with continuum): the output gains contribution_function (N_d, N_nu), what the
     layer below each depth point adds to the emergent flux — its sum over depth is spectrum_nu up to rounding
-    (radiation_field_solvers.contribution_function, formation_mean).  A spherical model raises NotImplementedError."""
+    (radiation_field_solvers.contribution_function, formation_mean).  A spherical model raises NotImplementedError.
+    instrument (a stardis_amd.instrument.Instrument): the output gains spectrum_observed (n_pix,), spectrum_lambda through the instrument
+    (radial velocity, line-spread function, pixels; Instrument.observe_host); with continuum=True also spectrum_observed_normalized, the
+    same with spectrum_lambda_continuum as reference."""
     try:
         from astropy import units as u
         from stardis.base import STARDISOutput, set_num_threads
@@ -40,7 +43,10 @@ def run_stardis(config_fname, tracing_lambdas_or_nus, add_config_dict=None, *, c
     stellar_plasma = create_stellar_plasma(stellar_model, adata, config)
     if not continuum and not contribution:
         stellar_radiation_field = create_stellar_radiation_field(tracing_nus, stellar_model, stellar_plasma, config)
-        return STARDISOutput(config.result_options, stellar_model, stellar_plasma, stellar_radiation_field)
+        sim = STARDISOutput(config.result_options, stellar_model, stellar_plasma, stellar_radiation_field)
+        if instrument is not None:
+            _add_observed_spectra(sim, instrument, False)
+        return sim
     stellar_radiation_field = create_stellar_radiation_field(tracing_nus, stellar_model, stellar_plasma, config, continuum=continuum,
                                                              contribution=contribution)
     sim = STARDISOutput(config.result_options, stellar_model, stellar_plasma, stellar_radiation_field)
@@ -48,7 +54,16 @@ def run_stardis(config_fname, tracing_lambdas_or_nus, add_config_dict=None, *, c
         _add_continuum_spectra(sim, stellar_radiation_field.F_nu_continuum)
     if contribution:
         sim.contribution_function = stellar_radiation_field.contribution_function
+    if instrument is not None:
+        _add_observed_spectra(sim, instrument, continuum)
     return sim
+
+
+def _add_observed_spectra(sim, instrument, continuum):
+    """(plain arrays, the values in the unit of spectrum_lambda: the instrument's pixels are not the model's grid)"""
+    sim.spectrum_observed = instrument.observe_host(sim.lambdas, sim.spectrum_lambda)
+    if continuum:
+        sim.spectrum_observed_normalized = instrument.observe_host(sim.lambdas, sim.spectrum_lambda, reference=sim.spectrum_lambda_continuum)
 
 
 def _add_continuum_spectra(sim, F_nu_continuum):

@@ -4490,4 +4490,123 @@ __global__ __launch_bounds__(kBlock) void k_convolve1d_reflect(int64_t n, const 
     out[i] = acc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The instrument model (include/stardis_hip.h, sdx_observe_dev): Doppler shift, a Gaussian line-spread function whose width is
+// given per pixel, and integration over the detector's pixels, in one launch:
+//     x_i = lambdas[i] D,   h_i = the trapezoid weight of x_i,   r_ij = the Gaussian of width sigma[j] around x_i integrated over pixel j,
+//     out[j] = (sum_i r_ij h_i flux[i]) / (sum_i r_ij h_i g_i)  over the points with edges[j] - 8 sigma[j] <= x_i <= edges[j+1] + 8 sigma[j]
+// (g = 1, or the reference spectrum); NaN where the grid does not cover that window.  fp64, every operation one rounded operation.
+//
+// One wave per pixel; the pixels go in groups of kObsGroup.  A group whose windows are short — none is expected to hold more than
+// kObsShort points at the grid's MEAN spacing, (x_{n-1} - x_0) / (n - 1): an estimate, taken before anything is searched — is done by its
+// FIRST wave, eight lanes per pixel, and the other waves leave at once: an undersampled line-spread function has one to five points per
+// window, and a wave per pixel would keep five lanes of 64 busy.  Otherwise every wave does its own pixel with 64 lanes.  The estimate
+// only chooses the mapping; either mapping serves any window.  A pixel's W lanes find its window [i0, i1) together (obs_windows), its
+// points are dealt to them round-robin from i0, each lane adds its own in ascending order, and a butterfly over the W lanes (offsets
+// W/2 ... 1) adds the partials: the order of the sums follows from the arrays alone, not from the launch or the device.
+//
+// Whatever the arrays hold (NaN, unordered values, sigma <= 0): a search reads only indices inside its bracket [lo, hi) within [0, n)
+// and shrinks the bracket at least W + 1 times per round, a window is [i0, i1) with 0 <= i0 <= i1 <= n, and a lane makes at most
+// (i1 - i0) / W + 1 trips.
+constexpr int kObsGroup = 8;
+constexpr int kObsShort = 32;
+
+// One round of a (W + 1)-ary search for the first index in [lo, hi) at which a predicate that holds on a prefix fails: lane t of the
+// pixel's W probes p = lo + (t + 1) chunk - 1, chunk = ceil((hi - lo) / (W + 1)).
+struct ObsBracket {
+    int64_t lo, hi;
+};
+__device__ __forceinline__ int64_t obs_probe(const ObsBracket& b, int W, int t, int64_t& chunk)
+{
+    const int64_t len = b.hi - b.lo;
+    chunk = W == 64 ? (len + 64) / 65 : (len + 8) / 9;
+    const int64_t p = b.lo + (t + 1) * chunk - 1;
+    return len > 0 && p < b.hi ? p : -1;  // (-1: nothing to read)
+}
+// ... c of the W probes held: the index lies behind probe c - 1 and not behind probe c.  The probes that exist are a prefix of the lanes
+// and only they can hold, so lo + c chunk <= hi whatever the data; the bracket shrinks to at most chunk - 1 or len / (W + 1) indices.
+__device__ __forceinline__ void obs_narrow(ObsBracket& b, int W, int c, int64_t chunk)
+{
+    if (b.hi <= b.lo) return;
+    b.lo += c * chunk;
+    const int64_t pc = b.lo + chunk - 1;  // probe c
+    if (c < W && pc < b.hi) b.hi = pc;
+}
+// The window of a pixel, by its W lanes (W = 64: the wave; W = 8: each of the wave's eight segments its own pixel): i0 = the first index
+// with x >= lo, i1 = the first with x > hi, searched side by side (one round = one load per lane and bound).  Every lane of the wave
+// calls this; a pixel that is not searched (`on` false) reads nothing.
+__device__ __forceinline__ void obs_windows(const double* __restrict__ lam, int64_t n, double D, double lo, double hi, bool on, int W, int lane,
+                                            int64_t& i0, int64_t& i1)
+{
+    const int t = W == 64 ? lane : lane & 7, shift = W == 64 ? 0 : lane & ~7;
+    const unsigned long long seg = W == 64 ? ~0ull : 0xffull;
+    ObsBracket a{0, on ? n : 0}, b{0, on ? n : 0};
+    while (__any(a.hi > a.lo || b.hi > b.lo)) {
+        int64_t ca, cb;
+        const int64_t pa = obs_probe(a, W, t, ca), pb = obs_probe(b, W, t, cb);
+        const double xa = pa >= 0 ? mul_rn(lam[pa], D) : 0.0, xb = pb >= 0 ? mul_rn(lam[pb], D) : 0.0;
+        const unsigned long long ma = __ballot(pa >= 0 && xa < lo), mb = __ballot(pb >= 0 && xb <= hi);
+        obs_narrow(a, W, __popcll((ma >> shift) & seg), ca);
+        obs_narrow(b, W, __popcll((mb >> shift) & seg), cb);
+    }
+    i0 = a.lo;
+    i1 = max(a.lo, b.lo);
+}
+
+// the Gaussian around x integrated from e0 to e1; s2 = sigma sqrt(2).  Both tails through erfc, which keeps their relative accuracy.
+__device__ __forceinline__ double obs_response(double e0, double e1, double x, double s2)
+{
+    const double a = sub_rn(e0, x) / s2, b = sub_rn(e1, x) / s2;
+    const bool above = a > 0.0;
+    if (above || b < 0.0) {
+        const double p = above ? a : -b, q = above ? b : -a;
+        return mul_rn(0.5, sub_rn(erfc(p), erfc(q)));
+    }
+    return mul_rn(0.5, sub_rn(erf(b), erf(a)));
+}
+
+__global__ __launch_bounds__(kBlock) void k_observe(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                                    const double* __restrict__ ref, int64_t n_pix, const double* __restrict__ edges,
+                                                    const double* __restrict__ sigma, const double* __restrict__ doppler,
+                                                    double* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    const int64_t first = wave - wave % kObsGroup;  // the group's first pixel
+    if (first >= n_pix) return;
+    const double D = doppler ? *doppler : 1.0;
+    const double x_first = mul_rn(lam[0], D), x_last = mul_rn(lam[n - 1], D);
+
+    // the group's mapping, from pixel first + lane / 8 in every lane
+    int64_t pj = first + (lane >> 3);
+    double e0 = 0.0, e1 = 0.0, s = 0.0;
+    if (pj < n_pix) e0 = edges[pj], e1 = edges[pj + 1], s = sigma[pj];
+    const double expected = (e1 - e0 + 16.0 * s) * (double)(n - 1) / (x_last - x_first);  // points in the window at the mean spacing
+    int W = 8;
+    if (__all(!(expected > (double)kObsShort))) {
+        if (wave != first) return;
+    } else {
+        if (wave >= n_pix) return;
+        pj = wave, W = 64;
+        e0 = edges[pj], e1 = edges[pj + 1], s = sigma[pj];
+    }
+    const int t = W == 64 ? lane : lane & 7;
+
+    const double reach = mul_rn(8.0, s), lo = sub_rn(e0, reach), hi = add_rn(e1, reach), s2 = mul_rn(s, 1.4142135623730951);
+    const bool covered = pj < n_pix && lo >= x_first && hi <= x_last;
+    int64_t i0, i1;
+    obs_windows(lam, n, D, lo, hi, covered, W, lane, i0, i1);
+
+    double num = 0.0, den = 0.0;
+    for (int64_t i = i0 + t; i < i1; i += W) {
+        const double x = mul_rn(lam[i], D);
+        const double below = mul_rn(lam[i > 0 ? i - 1 : 0], D), above = mul_rn(lam[i < n - 1 ? i + 1 : n - 1], D);
+        const double w = mul_rn(obs_response(e0, e1, x, s2), mul_rn(sub_rn(above, below), 0.5));
+        num = add_rn(num, mul_rn(w, flux[i]));
+        den = add_rn(den, ref ? mul_rn(w, ref[i]) : w);
+    }
+    for (int off = W >> 1; off > 0; off >>= 1) num = add_rn(num, __shfl_xor(num, off)), den = add_rn(den, __shfl_xor(den, off));
+    if (t == 0 && pj < n_pix) out[pj] = covered ? num / den : __longlong_as_double(0x7ff8000000000000LL);
+}
+
 }  // namespace sdx

@@ -2301,6 +2301,64 @@ int sdx_divide_dev(sdx_ctx* ctx, int64_t n, const double* a, const double* b, do
     return check_launch("k_divide");
 }
 
+// ---- the instrument model (k_observe): Doppler shift, line-spread function and pixel integration in one launch ------------------
+int sdx_observe_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
+                    const double* edges, const double* sigma, const double* doppler_dev, double* out)
+{
+    REQUIRE(ctx && n_pix >= 0, "observe: null context or n_pix < 0");
+    if (n_pix == 0) return SDX_OK;
+    REQUIRE(n >= 2, "observe: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && flux && edges && sigma && out, "observe: null pointer (lambdas, flux, edges, sigma and out are required)");
+    REQUIRE((n_pix + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "observe: too many pixels for one launch");
+    {
+        // one wave per pixel (the last group's waves included: a short group is done by its first wave alone)
+        const int64_t waves = (n_pix + kObsGroup - 1) / kObsGroup * kObsGroup;
+        LaunchScope ls(ctx, "k_observe");
+        hipLaunchKernelGGL(k_observe, dim3((unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, ctx->stream, n, lambdas, flux,
+                           reference, n_pix, edges, sigma, doppler_dev, out);
+    }
+    return check_launch("k_observe");
+}
+
+// what the kernel cannot check: the host-buffer twin does, before any upload
+static int observe_host_check(int64_t n, const double* lambdas, int64_t n_pix, const double* edges, const double* sigma, double doppler)
+{
+    REQUIRE(std::isfinite(doppler) && doppler > 0.0, "observe: doppler must be finite and > 0");
+    for (int64_t i = 0; i < n; ++i)
+        REQUIRE(std::isfinite(lambdas[i]) && (i == 0 || lambdas[i - 1] < lambdas[i]), "observe: lambdas must be finite and strictly ascending");
+    for (int64_t j = 0; j <= n_pix; ++j)
+        REQUIRE(std::isfinite(edges[j]) && (j == 0 || edges[j - 1] < edges[j]), "observe: edges must be finite and strictly ascending");
+    for (int64_t j = 0; j < n_pix; ++j) REQUIRE(std::isfinite(sigma[j]) && sigma[j] > 0.0, "observe: sigma must be finite and > 0");
+    return SDX_OK;
+}
+
+int sdx_observe_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
+                    const double* edges, const double* sigma, double doppler, double* out)
+{
+    REQUIRE(ctx && n_pix >= 0, "observe: null context or n_pix < 0");
+    if (n_pix == 0) return SDX_OK;
+    REQUIRE(n >= 2, "observe: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && flux && edges && sigma && out, "observe: null pointer (lambdas, flux, edges, sigma and out are required)");
+    int rc;
+    if ((rc = observe_host_check(n, lambdas, n_pix, edges, sigma, doppler))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double);
+    const size_t in_bytes[] = {(size_t)n * f8, (size_t)n * f8, reference ? (size_t)n * f8 : 0, (size_t)(n_pix + 1) * f8, (size_t)n_pix * f8, f8};
+    size_t dev_need = 256 + HostIo::pad((size_t)n_pix * f8), pin_need = HostIo::pad((size_t)n_pix * f8) + 256;
+    for (size_t b : in_bytes) dev_need += HostIo::pad(b ? b : 8), pin_need += HostIo::pad(b);
+    HostIo io{ctx};
+    if ((rc = io.begin(dev_need, pin_need))) return rc;
+    const double *d_l, *d_f, *d_r = nullptr, *d_e, *d_s, *d_D;
+    if ((rc = io.upload(lambdas, in_bytes[0], (const void**)&d_l)) || (rc = io.upload(flux, in_bytes[1], (const void**)&d_f)) ||
+        (reference && (rc = io.upload(reference, in_bytes[2], (const void**)&d_r))) || (rc = io.upload(edges, in_bytes[3], (const void**)&d_e)) ||
+        (rc = io.upload(sigma, in_bytes[4], (const void**)&d_s)) || (rc = io.upload(&doppler, in_bytes[5], (const void**)&d_D)))
+        return rc;
+    double* d_o = (double*)io.alloc((size_t)n_pix * f8);
+    if ((rc = sdx_observe_dev(ctx, n, d_l, d_f, d_r, n_pix, d_e, d_s, d_D, d_o))) return rc;
+    if ((rc = io.download(out, d_o, (size_t)n_pix * f8))) return rc;
+    return io.finish();
+}
+
 // ================================================================================================ fused synthesis
 static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
                            int64_t n_lines, const double* line_nus, const double* doppler, const double* gammas, int gamma_cols,

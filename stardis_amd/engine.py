@@ -39,7 +39,7 @@ def _require_f64_buffer(name, buf, n_min):
 class SpectralSynthesizer:
     def __init__(self, nus, temperatures, dist, thetas, theta_weights, lines, continuum=None, ctx=None, shard=None,
                  flux_out=None, track_evaluations=True, keep_line=True, keep_total=True, classify_share=None, m_max=None, m_share_out=None,
-                 keep_continuum_flux=False, keep_contribution=False):
+                 keep_continuum_flux=False, keep_contribution=False, instrument=None):
         """nus: global grid (descending).  lines: dict(line_nus, doppler_widths, gammas, alphas) in the
         reference layout (N_l, N_d), or a stardis_amd.linelist.LineList (per-line scalars; the pre-pass generates the
         three values per (line, depth) itself).  continuum: dict as produced by synth.synth_continuum_state or None.
@@ -56,7 +56,12 @@ class SpectralSynthesizer:
         keep_contribution: after the synthesis, every step also forms the flux contribution function C (N_d, count) of its own columns
         from the step's total_alphas (sdx_contribution_dev; implies keep_total): what the layer below row k adds to the emergent flux,
         sum_k C[k] = F_nu[-1] up to rounding (`contribution`, `formation_mean(x)`).  Plane-parallel, fp64, at most 64 angles: a context
-        with mixed_precision = 1 or more angles are refused here.  Off, the step is unchanged."""
+        with mixed_precision = 1 or more angles are refused here.  Off, the step is unchanged.
+        instrument: a stardis_amd.instrument.Instrument on this context.  Every step then also forms F_lambda of F_nu[-1]
+        (sdx_flux_nu_to_lambda_dev) and passes it through the instrument (sdx_observe_dev: radial velocity, line-spread function,
+        pixels) -> `observed` (n_pix,); with keep_continuum_flux also `observed_normalized`, the same with the continuum's F_lambda as
+        reference.  Both launches are part of whatever capture() records, and a recorded step follows instrument.set_radial_velocity().
+        Needs the whole grid (a shard raises ValueError: gather first).  Off, the step is unchanged."""
         self.ctx = ctx or default_context()
         c = self.ctx
         nus = np.ascontiguousarray(nus, dtype=np.float64)
@@ -70,6 +75,11 @@ class SpectralSynthesizer:
             raise ZeroDivisionError("float division by zero")  # voigt.py:148
         self.n_nu = nus.size
         self.begin, self.count = shard if shard is not None else (0, self.n_nu)
+        if instrument is not None:  # (before anything is uploaded)
+            if self.begin != 0 or self.count != self.n_nu:
+                raise ValueError("the instrument needs the whole spectrum: gather the shards first")
+            if instrument.ctx is not c:
+                raise ValueError("the instrument and the synthesizer must share a context (one stream orders the launches)")
         t = np.ascontiguousarray(temperatures, dtype=np.float64).reshape(-1)
         self.n_depth = t.size
         thetas = np.asarray(thetas, dtype=np.float64)
@@ -120,6 +130,14 @@ class SpectralSynthesizer:
         self.keep_continuum_flux = bool(keep_continuum_flux)
         self.d_Fc = c.empty((self.n_depth, self.count)) if self.keep_continuum_flux else None
         self.d_C = c.empty((self.n_depth, self.count)) if self.keep_contribution else None
+        self.instrument = instrument
+        if instrument is not None:
+            self.d_lambdas = c.upload(K.nu_to_angstrom(nus))
+            self.d_Flam = c.empty((self.n_nu,))
+            self.d_observed = c.empty((instrument.n_pix,))
+            if self.keep_continuum_flux:
+                self.d_Fclam = c.empty((self.n_nu,))
+                self.d_observed_normalized = c.empty((instrument.n_pix,))
         self._keep_line = keep_line  # also write the summed line opacity plane (alpha_line())
         self._keep_total = keep_total  # also write total_alphas (the reference keeps it on Opacities; the flux does not need it in HBM)
         self.count_evaluations = track_evaluations  # sum(hi - lo) per step costs a memset + copy: switch off when timing
@@ -213,10 +231,22 @@ class SpectralSynthesizer:
 
     def enqueue(self):
         """One fused step on the context's stream: sdx_synthesize_dev (pre-pass, line gather, total, raytrace); with
-        keep_contribution, sdx_contribution_dev on the step's total_alphas behind it."""
+        keep_contribution, sdx_contribution_dev on the step's total_alphas behind it; with an instrument, F_lambda and sdx_observe_dev
+        behind that."""
         self._enqueue_synthesis()
         if self.keep_contribution:
             self._enqueue_contribution()
+        if self.instrument is not None:
+            self._enqueue_observe()
+
+    def _enqueue_observe(self):
+        c, n, inst = self.ctx, self.n_nu, self.instrument
+        last = 8 * (self.n_depth - 1) * self.count  # row N_d - 1
+        c.call("sdx_flux_nu_to_lambda_dev", n, self.flux_ptr + last, self.d_nus.ptr, self.d_lambdas.ptr, self.d_Flam.ptr)
+        inst.observe(self.d_lambdas, self.d_Flam, n, out=self.d_observed)
+        if self.keep_continuum_flux:
+            c.call("sdx_flux_nu_to_lambda_dev", n, self.d_Fc.ptr + last, self.d_nus.ptr, self.d_lambdas.ptr, self.d_Fclam.ptr)
+            inst.observe(self.d_lambdas, self.d_Flam, n, reference=self.d_Fclam, out=self.d_observed_normalized)
 
     def _enqueue_contribution(self):
         cnt = self.count
@@ -286,6 +316,8 @@ class SpectralSynthesizer:
                self.d_total.ptr, cnt, self.flux_ptr, cnt, None, 0)
         if self.keep_contribution:
             self._enqueue_contribution()
+        if self.instrument is not None:
+            self._enqueue_observe()
 
     def capture(self, eager_phase2=True, batch=1):
         """Record one step into a hipGraph (after one eager step has sized the scratch).  batch > 1: ALSO a graph of `batch` consecutive
@@ -394,6 +426,21 @@ class SpectralSynthesizer:
         if not self.keep_contribution:
             raise RuntimeError("the contribution function was not kept: construct the synthesizer with keep_contribution=True")
         return self.d_C
+
+    @property
+    def observed(self):
+        """-> DeviceArray (n_pix,): the last step's spectrum as the instrument records it (`.numpy()` for a host array)."""
+        if self.instrument is None:
+            raise RuntimeError("no instrument: construct the synthesizer with instrument=Instrument(...)")
+        return self.d_observed
+
+    @property
+    def observed_normalized(self):
+        """-> DeviceArray (n_pix,): the continuum-normalised observed spectrum of the last step."""
+        if self.instrument is None:
+            raise RuntimeError("no instrument: construct the synthesizer with instrument=Instrument(...)")
+        self._require_continuum()
+        return self.d_observed_normalized
 
     def formation_mean(self, x):
         """-> DeviceArray (count,): the formation mean of a per-depth quantity x (N_d values; host array, DeviceArray or CUDA tensor)

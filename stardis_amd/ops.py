@@ -394,3 +394,18 @@ def formation_mean(contribution, x, ctx=None, device=False):
     d_out = ctx.empty((n_nu,))
     ctx.call("sdx_formation_mean_dev", n_depth, n_nu, ptr_of(d_C), n_nu, ptr_of(d_x), d_out.ptr)
     return d_out if device else d_out.numpy()
+
+
+# ------------------------------------------------------------------------------------------------ instrument model
+def observe(lambdas, flux, pixel_edges, sigma, v_rad=0.0, reference=None, ctx=None):
+    """What a spectrograph records of a spectrum (sdx_observe_dev): the wavelengths shifted by the radial velocity v_rad (km/s), a
+    Gaussian line-spread function of width sigma (Angstrom; a scalar or one value per pixel) and integration over the pixels between
+    pixel_edges -> (n_pix,).  With a reference the continuum-normalised observed spectrum, observe(flux) / observe(reference).  A
+    pixel whose window (its edges -+ 8 sigma) the shifted grid does not cover is NaN.  stardis_amd.instrument.Instrument keeps the
+    pixels on the device for repeated calls."""
+    from .instrument import Instrument
+
+    inst = Instrument(pixel_edges, sigma=sigma, ctx=ctx)
+    if v_rad:
+        inst.set_radial_velocity(v_rad)
+    return inst.observe_host(lambdas, flux, reference)

@@ -135,3 +135,19 @@ class DeviceSpectrum:
         self.ctx.call("sdx_divide_dev", self.n, flux.ptr, cont.ptr, out.ptr)
         return out
 
+    def observed(self, instrument, normalized=False):
+        """spectrum_lambda through a stardis_amd.instrument.Instrument (radial velocity, line-spread function, pixels) without leaving
+        the device -> DeviceArray (n_pix,).  normalized=True: the continuum's F_lambda goes along as the reference (the synthesizer needs
+        keep_continuum_flux=True) and the result is the continuum-normalised observed spectrum, from the same launch."""
+        if instrument.ctx is not self.ctx:
+            raise ValueError("the instrument and the synthesizer must share a context (one stream orders the launches)")
+        syn, reference = self.syn, None
+        if normalized:
+            syn._require_continuum()
+            if getattr(self, "d_continuum", None) is None:
+                self.d_continuum = self.ctx.empty((self.n,))
+            row = syn.d_Fc.ptr + 8 * (syn.n_depth - 1) * syn.count  # F_nu_continuum[-1]
+            self.ctx.call("sdx_flux_nu_to_lambda_dev", self.n, row, syn.d_nus.ptr, self.d_lambdas.ptr, self.d_continuum.ptr)
+            reference = self.d_continuum
+        return instrument.observe(self.d_lambdas, self.spectrum_lambda(), self.n, reference)
+
