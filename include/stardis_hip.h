@@ -29,8 +29,6 @@
  *       SDX_FAR           0 / 1: never / always the far field of the line kernels (the option "far_field" wins); SDX_FAR_RF 1 / 2 / 4
  *                         (tiles per unit of the far role / 4: scheduling only); SDX_FAR_LAUNCH: the far field as a launch of its own
  *                         (k_line_far, 8 line subsets — SDX_FAR_SPLIT 1 .. 8 — instead of the line kernel's: the order of a sum)
- *       SDX_RT_NS         4: segmented kernel with 4 waves x 14 gaps instead of 8 x 7
- *       SDX_RT_P          1, 2, 4: angles per lane of k_raytrace
  *       SDX_R_MIXED       4 / 8: grid points per lane of a mixed-precision tile
  *       SDX_NO_NARROW_SUBSETS, SDX_NARROW_SUBSETS_DENSITY (halves of a line per grid point from which the narrow role of a long
  *                         list splits its candidate lines over the four waves of a workgroup; default 8 = four lines per point)

@@ -3293,19 +3293,23 @@ __global__ __launch_bounds__(kBlock) void k_classify_continuum(int n_dnu, int n_
 
 // ------------------------------------------------------------------------------------------------
 // Formal solution (radiation_field_solvers/base.py:85-346).  A group of G adjacent lanes of one wave
-// owns one frequency (64/G groups per wave); lane g of the group traces angles g, g+G, ... (at most P of
-// them) through all depth gaps, keeping the rolling state — two mean opacities, three source values, one
-// intensity per angle — in registers.  After every gap the group sums I_theta * w_theta in ascending-theta
-// order with wave shuffles and lane 0 adds it to F_nu[gap+1] (:336-338).  Geometric-mean opacity (:121),
-// tau (:123-129), Planck source (:133) and the weights (:138) are formed with the reference's operations;
-// the mean opacity and source are shared by the angles a lane owns instead of being recomputed per angle.
-template <int P>
+// owns one frequency (64/G groups per wave); lane g of the group traces angle g through all depth gaps,
+// keeping the rolling state — two mean opacities, three source values, one intensity — in registers.
+// After every gap the group sums I_theta * w_theta in ascending-theta order with wave shuffles and lane 0
+// adds it to F_nu[gap+1] (:336-338).  Geometric-mean opacity (:121), tau (:123-129), Planck source (:133)
+// and the weights (:138) are formed with the reference's operations.
+//
+// One angle per lane, here and in k_raytrace, k_raytrace_cont and k_contribution (two and four: measured slower, removed).
+// The lane's state stays one-element arrays walked by one-trip loops over k ON PURPOSE: with them the compiler emits, instruction for
+// instruction, the code every recorded time was measured on; as scalars, or as the same arrays indexed by 0, all four kernels come out
+// in another order and three of them longer (k_raytrace by 18 instructions; profiles/EXPERIMENTS.md): a change that has to be measured.
 __global__ __launch_bounds__(kBlock) void k_raytrace_basic(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
                                                      const double* __restrict__ nus, const double* __restrict__ temps,
                                                      const double* __restrict__ ray_dist, const double* __restrict__ wts,
                                                      const double* __restrict__ alphas, int64_t ald, double* __restrict__ F,
                                                      int64_t fld, double* __restrict__ I_nus, int accumulate)
 {
+    constexpr int P = 1;  // angles per lane: the note above
     // n_theta angles are traced here; ray_dist / I_nus rows have theta_stride entries (a chunk of a longer list)
     const int lane = threadIdx.x & 63;
     const int gpw = 64 / G;  // groups per wave
@@ -3326,7 +3330,7 @@ __global__ __launch_bounds__(kBlock) void k_raytrace_basic(int n_depth, int64_t 
 #pragma unroll
     for (int k = 0; k < P; ++k) {
         inten[k] = 0.0;  // I[0] = 0 (:134-136)
-        th[k] = g + k * G;
+        th[k] = g;
         wt[k] = th[k] < n_theta ? wts[th[k]] : 0.0;
         if (valid && I_nus && th[k] < n_theta) I_nus[(size_t)i * theta_stride + th[k]] = 0.0;
     }
@@ -3372,13 +3376,13 @@ __global__ __launch_bounds__(kBlock) void k_raytrace_basic(int n_depth, int64_t 
                 for (int k = 0; k < P; ++k)
                     if (th[k] < n_theta) fsum = add_rn(fsum, mul_rn(inten[k], wt[k]));
             } else {
-                // ascending theta = gg + k*G: k outer, group lanes inner
+                // ascending theta: the group's lanes in order
 #pragma unroll
                 for (int k = 0; k < P; ++k) {
                     const double mine = mul_rn(inten[k], wt[k]);
                     for (int gg = 0; gg < G; ++gg) {
                         const double v = __shfl(mine, lane0 + gg);
-                        if (gg + k * G < n_theta) fsum = add_rn(fsum, v);
+                        if (gg < n_theta) fsum = add_rn(fsum, v);
                     }
                 }
             }
@@ -3394,12 +3398,12 @@ __global__ __launch_bounds__(kBlock) void k_raytrace_basic(int n_depth, int64_t 
 
 // ------------------------------------------------------------------------------------------------
 // Formal solution, LDS-staged (the default).  Same lane <-> (frequency, angle) mapping as k_raytrace_basic:
-// a group of G adjacent lanes owns one frequency, lane g traces angle(s) g, g+G, ...  What is shared is
+// a group of G adjacent lanes owns one frequency, lane g traces angle g.  What is shared is
 // prepared once and kept in LDS:
 //   block    the ray-length table ray_dist[gap][theta] (:302-305) and its reciprocals;
 //   group    phase 1: the G lanes split the N_d depth points: log(alpha) and the Planck source S (:133) -> LDS,
 //            then per gap the geometric-mean opacity exp((log a[g+1] + log a[g]) * 0.5) (:121) and its reciprocal;
-//   lane     phase 2: walks the gaps for its own angle(s): tau = mean * ray_dist (:123-129, the reference's
+//   lane     phase 2: walks the gaps for its own angle: tau = mean * ray_dist (:123-129, the reference's
 //            product), weights (:22-45), second-order recurrence (:200-266).  The divisions of :208-242 are
 //            re-expressed with the slopes a = (S[g+2]-S[g+1])/tau[g+1], b = (S[g]-S[g+1])/tau[g]:
 //                second = w1 (b tau[g+1] - a tau[g]) / (tau[g] + tau[g+1]),   third = w2 (a + b) / (tau[g] + tau[g+1])
@@ -3431,14 +3435,14 @@ struct FusedTotal {
 };
 
 // Formal solution, LDS-staged (grids that fill the chip; every geometry).  Lane <-> (frequency, angle): a group of G adjacent
-// lanes owns one frequency, lane g traces angle(s) g, g + G, ...  Staged once and kept in LDS:
+// lanes owns one frequency, lane g traces angle g.  Staged once and kept in LDS:
 //   block    the ray-length table ray_dist[gap][theta] (:302-305);
 //   wave     per frequency of the wave, the G lanes of its group split the N_d depth points: the source function S (:133;
 //            planck_staged, or the caller's plane) and sqrt(alpha).  The geometric-mean opacity of a gap (:121,
 //            exp((log a[g+1] + log a[g]) / 2)) is the product of the two square roots at its ends — one correctly rounded
 //            square root per point instead of a logarithm per point and an exponential per gap, and within 1e-15 of the
 //            reference's value (whose own error is ~|log alpha| ulp);
-//   lane     walks the gaps for its own angle(s): tau = mean * ray_dist (:123-129), then one rt_coef (sdx_math.h: the
+//   lane     walks the gaps for its own angle: tau = mean * ray_dist (:123-129), then one rt_coef (sdx_math.h: the
 //            step as an affine map of the incoming intensity, one reciprocal, the reference's weights) and one FMA;
 //   flux     I_theta * w_theta goes to the wave's LDS; every kBatch gaps the wave sums each (gap, frequency) over theta in
 //            two ascending halves and writes F_nu.
@@ -3446,24 +3450,22 @@ struct FusedTotal {
 // kRtBlock and the LDS layout of every kernel of the family: sdx_rt_layout.h.
 // lane / G for lane < 64 and 1 <= G <= 64 without an integer division (~25 instructions where G is a kernel argument): one multiply
 // by g_recip = 65536 / G + 1, formed once on the host (lane_recip, stardis_hip.hip), and a shift.  Exact over that whole range.
-// (k_raytrace_seg, whose prologue is a visible share of a wave's life; k_raytrace<P> and k_raytrace_cont<P> keep the division)
+// (k_raytrace_seg, whose prologue is a visible share of a wave's life; k_raytrace and k_raytrace_cont keep the division)
 __device__ __forceinline__ int lane_div(int lane, int g_recip)
 {
     return (lane * g_recip) >> 16;
 }
-template <int P>
 __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
                                                      const double* __restrict__ nus, const double* __restrict__ temps,
                                                      const double* __restrict__ ray_dist, const double* __restrict__ wts,
                                                      const double* __restrict__ alphas, int64_t ald, double* __restrict__ F,
                                                      int64_t fld, double* __restrict__ I_nus, int accumulate, int inward, int gpw, FusedTotal ft)
 {
-    constexpr int kBatch = RtColumns::gaps_per_batch(P);
+    constexpr int P = 1, kBatch = kRtBatch;  // P: angles per lane (why the one-trip loops over k stay: the note above k_raytrace_basic)
     extern __shared__ double smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // gpw = groups (frequencies) per wave, <= 64 / G; the host lowers it when the LDS columns would not fit
     const int grp = lane / G, g = lane - grp * G;
-    const int TH = P * G;  // theta slots per group, ascending theta = k*G + g
     const int64_t i0 = ((int64_t)blockIdx.x * (kRtBlock / 64) + wave) * gpw;  // first frequency of this wave
     const int64_t i = i0 + grp;
     const bool active = grp < gpw;
@@ -3471,10 +3473,10 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
     const int64_t ic = i < n_nu ? i : n_nu - 1;
     const int n_gap = n_depth - 1;
     const int col = n_depth;  // LDS row stride per group
-    const RtColumns lay(P, G, n_depth, gpw);
+    const RtColumns lay(G, n_depth, gpw);
     double* wbase = smem + (size_t)wave * lay.wave_doubles();
     double2* sP = (double2*)(wbase + lay.pairs());  // (source function, sqrt(alpha)) [gpw][col]: a point's pair is ONE 16-byte LDS read
-    double* sX = wbase + lay.flux();                // flux terms       [kBatch][gpw][TH]
+    double* sX = wbase + lay.flux();                // flux terms       [kBatch][gpw][G]
     const double nu = nus[ic];
 
     // (Staging the columns a batch of G depth points AHEAD of the recurrence — the loads of batch b + 1 requested when batch b is
@@ -3503,7 +3505,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
     }
     wave_sync();  // (nothing is shared between the waves of a block any more: the ray table is read from L1)
     // (the step's constants stay literals here: the gap loop is rolled and the compiler already holds them in scalar registers across it
-    // — no literal move in the loop body; pinned with rt_const_resident they cost k_raytrace<1> five more SGPR spills and put two moves back)
+    // — no literal move in the loop body; pinned with rt_const_resident they cost k_raytrace five more SGPR spills and put two moves back)
     const RtConst kc = rt_const_literals();
 
     const int gi = (active ? grp : 0) * col;  // idle lanes shadow group 0 and never store
@@ -3512,8 +3514,8 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
     bool on[P];
 #pragma unroll
     for (int k = 0; k < P; ++k) {
-        th[k] = min(g + k * G, n_theta - 1);
-        on[k] = g + k * G < n_theta;
+        th[k] = min(g, n_theta - 1);
+        on[k] = g < n_theta;
         inten[k] = 0.0;  // np.zeros (:134)
         wt[k] = on[k] ? wts[th[k]] : 0.0;
     }
@@ -3538,12 +3540,12 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
 #pragma unroll
         for (int k = 0; k < P; ++k) {
             if (valid && I_nus && on[k]) I_nus[(size_t)i * theta_stride + th[k]] = inten[k];
-            if (active) sX[grp * TH + k * G + g] = inten[k] * wt[k];
+            if (active) sX[grp * G + g] = inten[k] * wt[k];
         }
         wave_sync();
         if (F && lane < gpw && i0 + lane < n_nu) {
             double sum = 0.0;
-            for (int t = 0; t < n_theta; ++t) sum = add_rn(sum, sX[lane * TH + t]);
+            for (int t = 0; t < n_theta; ++t) sum = add_rn(sum, sX[lane * G + t]);
             double* dst = F + i0 + lane;
             *dst = accumulate ? add_rn(*dst, sum) : sum;
         }
@@ -3593,7 +3595,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
                     inten[k] = inew;
                     tau0[k] = t1;
                     if (valid && I_nus && on[k]) I_nus[((size_t)(gap + 1) * n_nu + i) * theta_stride + th[k]] = inew;
-                    if (active) sX[(b * gpw + grp) * TH + k * G + g] = inew * wt[k];
+                    if (active) sX[(b * gpw + grp) * G + g] = inew * wt[k];
                 }
                 d10 = -d21, s1 = s2, a1 = a2;
             } else {  // the final gap (:253-266)
@@ -3604,7 +3606,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
                     const double inew = fma(c, inten[k], e);
                     inten[k] = inew;
                     if (valid && I_nus && on[k]) I_nus[((size_t)(gap + 1) * n_nu + i) * theta_stride + th[k]] = inew;
-                    if (active) sX[(b * gpw + grp) * TH + k * G + g] = inew * wt[k];
+                    if (active) sX[(b * gpw + grp) * G + g] = inew * wt[k];
                 }
             }
         }
@@ -3616,7 +3618,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
             for (int p = lane; p < 2 * nb * gpw; p += 64) {
                 const int h = p & 1, q = p >> 1;
                 const int b = (int)(((float)q + 0.5f) * inv_gpw), gq = q - b * gpw;  // q / gpw without an integer division (q < 2^20: exact)
-                const double* c = sX + (b * gpw + gq) * TH + (h ? half : 0);
+                const double* c = sX + (b * gpw + gq) * G + (h ? half : 0);
                 const int cnt = h ? n_theta - half : half;
                 double sum = 0.0;
                 int t = 0;
@@ -3639,7 +3641,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
 }
 
 // The formal solution of the fp32-mixed TOLERANCE path (mixed_precision = 1; plane-parallel, one angle per lane, flux only): the
-// layout of k_raytrace<1> — lane <-> (frequency, angle), columns staged per wave — with the recurrence in fp32 (rt_coef32:
+// layout of k_raytrace — lane <-> (frequency, angle), columns staged per wave — with the recurrence in fp32 (rt_coef32:
 // hardware exp2 / rcp, ~27 instructions per step at twice the fp64 issue rate against ~54).  sqrt(alpha), the source function, its
 // differences between adjacent points (formed as differences: planck32_pair) and the ray lengths are staged as floats (the totals
 // are formed in fp64 and rounded once); F_nu is written as doubles.
@@ -4138,23 +4140,21 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
 // reference's `alpha_line_at_nu = 0` entry adds nothing, opacities/base.py:24-28) — from the same staging.  Requires a fused total
 // (ft.cont): the continuum column is read there anyway.
 //
-// k_raytrace_cont<P>: the layout of k_raytrace<P> with sqrt(alpha_cont) staged per depth point beside the (S, sqrt(alpha)) pair, and
+// k_raytrace_cont: the layout of k_raytrace with sqrt(alpha_cont) staged per depth point beside the (S, sqrt(alpha)) pair, and
 // per lane TWO independent recurrences — total and continuum — on the same ray lengths, the same source values and the same rt_coef
 // arithmetic (the same operations as k_raytrace on a zero-line total, so the continuum flux is that run's F_nu bit for bit).  The
 // k_raytrace chain is latency-bound (one wave walks all N_d - 1 dependent gaps); the second chain gives the scheduler independent work
 // to interleave.  Both flux sums use k_raytrace's order (two ascending halves over theta); the spherical inward sweep runs for both.
-template <int P>
 __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
                                                           const double* __restrict__ nus, const double* __restrict__ temps,
                                                           const double* __restrict__ ray_dist, const double* __restrict__ wts,
                                                           double* __restrict__ F, int64_t fld, double* __restrict__ Fc, int64_t fcld,
                                                           double* __restrict__ I_nus, int inward, int gpw, FusedTotal ft)
 {
-    constexpr int kBatch = RtColumns::gaps_per_batch(P);
+    constexpr int P = 1, kBatch = kRtBatch;  // P: angles per lane (why the one-trip loops over k stay: the note above k_raytrace_basic)
     extern __shared__ double smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = lane / G, g = lane - grp * G;
-    const int TH = P * G;
     const int64_t i0 = ((int64_t)blockIdx.x * (kRtBlock / 64) + wave) * gpw;
     const int64_t i = i0 + grp;
     const bool active = grp < gpw;
@@ -4162,12 +4162,12 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
     const int64_t ic = i < n_nu ? i : n_nu - 1;
     const int n_gap = n_depth - 1;
     const int col = n_depth;
-    // must match RtContColumns (sdx_rt_layout.h), which the host sizes the launch by: taken from the struct, <2> and <4> spill two more SGPRs
-    double* wbase = smem + (size_t)wave * ((3 * gpw * col + 2 * kBatch * gpw * TH + 1) & ~1);  // (even: 16-byte aligned pairs)
+    // must match RtContColumns (sdx_rt_layout.h), which the host sizes the launch by (taken from the struct the instructions change)
+    double* wbase = smem + (size_t)wave * ((3 * gpw * col + 2 * kBatch * gpw * G + 1) & ~1);  // (even: 16-byte aligned pairs)
     double2* sP = (double2*)wbase;            // (source function, sqrt(alpha total)) [gpw][col]
     double* sC = wbase + 2 * gpw * col;       // sqrt(alpha continuum)             [gpw][col]
-    double* sX = sC + gpw * col;              // flux terms, total                 [kBatch][gpw][TH]
-    double* sXc = sX + kBatch * gpw * TH;     // flux terms, continuum             [kBatch][gpw][TH]
+    double* sX = sC + gpw * col;              // flux terms, total                 [kBatch][gpw][G]
+    double* sXc = sX + kBatch * gpw * G;      // flux terms, continuum             [kBatch][gpw][G]
     const double nu = nus[ic];
 
     if (active) {
@@ -4195,8 +4195,8 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
     bool on[P];
 #pragma unroll
     for (int k = 0; k < P; ++k) {
-        th[k] = min(g + k * G, n_theta - 1);
-        on[k] = g + k * G < n_theta;
+        th[k] = min(g, n_theta - 1);
+        on[k] = g < n_theta;
         inten[k] = 0.0, intc[k] = 0.0;
         wt[k] = on[k] ? wts[th[k]] : 0.0;
     }
@@ -4223,12 +4223,12 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
 #pragma unroll
         for (int k = 0; k < P; ++k) {
             if (valid && I_nus && on[k]) I_nus[(size_t)i * theta_stride + th[k]] = inten[k];
-            if (active) sX[grp * TH + k * G + g] = inten[k] * wt[k], sXc[grp * TH + k * G + g] = intc[k] * wt[k];
+            if (active) sX[grp * G + g] = inten[k] * wt[k], sXc[grp * G + g] = intc[k] * wt[k];
         }
         wave_sync();
         if (lane < gpw && i0 + lane < n_nu) {
             double sum = 0.0, sumc = 0.0;
-            for (int t = 0; t < n_theta; ++t) sum = add_rn(sum, sX[lane * TH + t]), sumc = add_rn(sumc, sXc[lane * TH + t]);
+            for (int t = 0; t < n_theta; ++t) sum = add_rn(sum, sX[lane * G + t]), sumc = add_rn(sumc, sXc[lane * G + t]);
             F[i0 + lane] = sum;
             Fc[i0 + lane] = sumc;
         }
@@ -4279,7 +4279,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
                     inten[k] = inew, intc[k] = icnew;
                     tau0[k] = t1, tauc0[k] = tc1;
                     if (valid && I_nus && on[k]) I_nus[((size_t)(gap + 1) * n_nu + i) * theta_stride + th[k]] = inew;
-                    if (active) sX[(b * gpw + grp) * TH + k * G + g] = inew * wt[k], sXc[(b * gpw + grp) * TH + k * G + g] = icnew * wt[k];
+                    if (active) sX[(b * gpw + grp) * G + g] = inew * wt[k], sXc[(b * gpw + grp) * G + g] = icnew * wt[k];
                 }
                 d10 = -d21, s1 = s2, a1 = a2, ac1 = ac2;
             } else {
@@ -4291,7 +4291,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
                     const double inew = fma(c, inten[k], e), icnew = fma(cc, intc[k], ec);
                     inten[k] = inew, intc[k] = icnew;
                     if (valid && I_nus && on[k]) I_nus[((size_t)(gap + 1) * n_nu + i) * theta_stride + th[k]] = inew;
-                    if (active) sX[(b * gpw + grp) * TH + k * G + g] = inew * wt[k], sXc[(b * gpw + grp) * TH + k * G + g] = icnew * wt[k];
+                    if (active) sX[(b * gpw + grp) * G + g] = inew * wt[k], sXc[(b * gpw + grp) * G + g] = icnew * wt[k];
                 }
             }
         }
@@ -4301,7 +4301,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
             for (int p = lane; p < 2 * nb * gpw; p += 64) {
                 const int h = p & 1, q = p >> 1;
                 const int b = (int)(((float)q + 0.5f) * inv_gpw), gq = q - b * gpw;
-                const int off = (b * gpw + gq) * TH + (h ? half : 0);
+                const int off = (b * gpw + gq) * G + (h ? half : 0);
                 const double* c = sX + off;
                 const double* cc = sXc + off;
                 const int cnt = h ? n_theta - half : half;
@@ -4335,7 +4335,7 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
 // Nothing is modelled anew: (c, e) come from the device functions k_raytrace calls — rt_coef<false> for the inner gaps, rt_coef<true> for the
 // last one, the tau == 0 -> (1, 0) rule and the rare-lane fallback included — on the same tau = (sqrt(alpha[g]) sqrt(alpha[g+1])) ray_dist.
 //
-// The layout of k_raytrace<P>: lane <-> (frequency, angle), a group of G lanes per frequency, (S, sqrt(alpha)) staged per wave in LDS as one
+// The layout of k_raytrace: lane <-> (frequency, angle), a group of G lanes per frequency, (S, sqrt(alpha)) staged per wave in LDS as one
 // 16-byte pair per point, from a FINISHED total_alphas plane.  Each lane walks its ray from the surface INWARDS — the rolling state of
 // k_raytrace mirrored: the optical depth of the gap and of the one above it, the source at the gap's upper end and the two differences, one
 // 16-byte LDS read per step for the point below — carrying only the running product T: the (c, e) of different gaps do not depend on each
@@ -4343,18 +4343,16 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace_cont(int n_depth, int64_t
 // the wave sums each (gap, frequency) over theta in k_raytrace's order (two ascending halves, the lower added to the upper) and writes row
 // gap + 1 of C.  T underflows to 0 in deep layers: C is 0 there, no special case.  Plane-parallel only (the inward sweep of spherical
 // geometry makes I[0] != 0), all angles in one launch.
-template <int P>
 __global__ __launch_bounds__(kRtBlock) void k_contribution(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
                                                          const double* __restrict__ nus, const double* __restrict__ temps,
                                                          const double* __restrict__ ray_dist, const double* __restrict__ wts,
                                                          const double* __restrict__ alphas, int64_t ald, const double* __restrict__ source,
                                                          int64_t sld, double* __restrict__ C, int64_t cld, int gpw)
 {
-    constexpr int kBatch = RtColumns::gaps_per_batch(P);
+    constexpr int P = 1, kBatch = kRtBatch;  // P: angles per lane (why the one-trip loops over k stay: the note above k_raytrace_basic)
     extern __shared__ double smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int grp = lane / G, g = lane - grp * G;
-    const int TH = P * G;  // theta slots per group, ascending theta = k*G + g
     const int64_t i0 = ((int64_t)blockIdx.x * (kRtBlock / 64) + wave) * gpw;  // first frequency of this wave
     const int64_t i = i0 + grp;
     const bool active = grp < gpw;
@@ -4362,10 +4360,10 @@ __global__ __launch_bounds__(kRtBlock) void k_contribution(int n_depth, int64_t 
     const int64_t ic = i < n_nu ? i : n_nu - 1;
     const int n_gap = n_depth - 1;
     const int col = n_depth;  // LDS row stride per group
-    const RtColumns lay(P, G, n_depth, gpw);
+    const RtColumns lay(G, n_depth, gpw);
     double* wbase = smem + (size_t)wave * lay.wave_doubles();
     double2* sP = (double2*)(wbase + lay.pairs());  // (source function, sqrt(alpha)) [gpw][col]
-    double* sX = wbase + lay.flux();                // flux terms T e w_theta [kBatch][gpw][TH]
+    double* sX = wbase + lay.flux();                // flux terms T e w_theta [kBatch][gpw][G]
     const double nu = nus[ic];
 
     if (active) {
@@ -4389,8 +4387,8 @@ __global__ __launch_bounds__(kRtBlock) void k_contribution(int n_depth, int64_t 
         const double mean = a0 * pt.y;
 #pragma unroll
         for (int k = 0; k < P; ++k) {
-            th[k] = min(g + k * G, n_theta - 1);
-            wt[k] = g + k * G < n_theta ? wts[th[k]] : 0.0;
+            th[k] = min(g, n_theta - 1);
+            wt[k] = g < n_theta ? wts[th[k]] : 0.0;
             trans[k] = 1.0;  // T[N_d - 1]
             rdp[k] = ray_dist + (size_t)(n_gap - 1) * theta_stride + th[k];
             tau0[k] = mul_rn(mean, *rdp[k]);
@@ -4412,7 +4410,7 @@ __global__ __launch_bounds__(kRtBlock) void k_contribution(int n_depth, int64_t 
                 double c, e;
                 if (gap == n_gap - 1) rt_coef<true>(tau0[k], 0.0, d10, 0.0, s1, c, e, kc);  // the final gap (:253-266), visited first
                 else rt_coef<false>(tau0[k], tau1[k], d10, d21, s1, c, e, kc);               // :208-249
-                if (active) sX[(b * gpw + grp) * TH + k * G + g] = (trans[k] * e) * wt[k];
+                if (active) sX[(b * gpw + grp) * G + g] = (trans[k] * e) * wt[k];
                 trans[k] *= c;  // T[gap]
                 tau1[k] = tau0[k];
                 tau0[k] = mul_rn(mean_next, rd_next[k]);
@@ -4430,7 +4428,7 @@ __global__ __launch_bounds__(kRtBlock) void k_contribution(int n_depth, int64_t 
             for (int p = lane; p < 2 * nb * gpw; p += 64) {
                 const int h = p & 1, q = p >> 1;
                 const int b = (int)(((float)q + 0.5f) * inv_gpw), gq = q - b * gpw;  // q / gpw without an integer division (q < 2^20: exact)
-                const double* t = sX + (b * gpw + gq) * TH + (h ? half : 0);
+                const double* t = sX + (b * gpw + gq) * G + (h ? half : 0);
                 const int cnt = h ? n_theta - half : half;
                 double sum = 0.0;
                 for (int j = 0; j < cnt; ++j) sum = add_rn(sum, t[j]);

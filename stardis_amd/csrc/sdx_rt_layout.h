@@ -7,33 +7,32 @@
 
 #include <cstddef>
 
-constexpr int kRtBlock = 256;             // k_raytrace<P>, k_raytrace_cont<P>, k_raytrace_f32, k_contribution<P>: four waves
+constexpr int kRtBlock = 256;             // k_raytrace, k_raytrace_cont, k_raytrace_f32, k_contribution: four waves
 constexpr int kRtWaves = kRtBlock / 64;
 constexpr size_t kLdsBytes = 64 * 1024;   // what a workgroup may ask for
 
-// k_raytrace<P>, k_contribution<P>.  Per wave: the (source function, sqrt(alpha)) pairs [gpw][col] as double2, then the flux terms
-// [batch][gpw][TH] of a batch of gaps.  G lanes per frequency, P angles per lane, gpw frequencies per wave.
+constexpr int kRtBatch = 4;  // gaps per flux reduction of k_raytrace, k_raytrace_cont and k_contribution
+// k_raytrace, k_contribution.  Per wave: the (source function, sqrt(alpha)) pairs [gpw][col] as double2, then the flux terms
+// [kRtBatch][gpw][G] of a batch of gaps.  G lanes per frequency, one angle per lane, gpw frequencies per wave.
 struct RtColumns {
-    int gpw, col, TH, batch;
-    static __host__ __device__ constexpr int gaps_per_batch(int P) { return P == 1 ? 4 : 2; }
-    __host__ __device__ constexpr RtColumns(int P, int G, int n_depth, int gpw_) : gpw(gpw_), col(n_depth), TH(P * G), batch(gaps_per_batch(P)) {}
+    int gpw, col, G;
+    __host__ __device__ constexpr RtColumns(int G_, int n_depth, int gpw_) : gpw(gpw_), col(n_depth), G(G_) {}
     __host__ __device__ constexpr int pairs() const { return 0; }
     __host__ __device__ constexpr int flux() const { return 2 * gpw * col; }
-    __host__ __device__ constexpr int wave_doubles() const { return flux() + batch * gpw * TH; }
+    __host__ __device__ constexpr int wave_doubles() const { return flux() + kRtBatch * gpw * G; }
     __host__ __device__ constexpr size_t bytes() const { return (size_t)kRtWaves * wave_doubles() * sizeof(double); }
 };
 
-// k_raytrace_cont<P>: RtColumns with sqrt(alpha continuum) [gpw][col] behind the pairs and a second batch of flux terms for the
+// k_raytrace_cont: RtColumns with sqrt(alpha continuum) [gpw][col] behind the pairs and a second batch of flux terms for the
 // continuum chain; a wave's share is rounded up to an even number of doubles, so that every wave's pairs stay 16-byte aligned.
 struct RtContColumns {
-    int gpw, col, TH, batch;
-    __host__ __device__ constexpr RtContColumns(int P, int G, int n_depth, int gpw_)
-        : gpw(gpw_), col(n_depth), TH(P * G), batch(RtColumns::gaps_per_batch(P)) {}
+    int gpw, col, G;
+    __host__ __device__ constexpr RtContColumns(int G_, int n_depth, int gpw_) : gpw(gpw_), col(n_depth), G(G_) {}
     __host__ __device__ constexpr int pairs() const { return 0; }
     __host__ __device__ constexpr int cont() const { return 2 * gpw * col; }
     __host__ __device__ constexpr int flux() const { return cont() + gpw * col; }
-    __host__ __device__ constexpr int flux_cont() const { return flux() + batch * gpw * TH; }
-    __host__ __device__ constexpr int wave_doubles() const { return (flux_cont() + batch * gpw * TH + 1) & ~1; }
+    __host__ __device__ constexpr int flux_cont() const { return flux() + kRtBatch * gpw * G; }
+    __host__ __device__ constexpr int wave_doubles() const { return (flux_cont() + kRtBatch * gpw * G + 1) & ~1; }
     __host__ __device__ constexpr size_t bytes() const { return (size_t)kRtWaves * wave_doubles() * sizeof(double); }
 };
 
@@ -84,12 +83,12 @@ constexpr int kRtMaxDepth = (int)(kLdsBytes / sizeof(double));
 // Frequencies per wave of a per-wave layout (RtColumns, RtContColumns): 64 / G, lowered (idle lanes) until the staged columns fit LDS;
 // 0 when not even one frequency per wave does.
 template <class Layout>
-inline int rt_fit_gpw(int P, int G, int n_depth)
+inline int rt_fit_gpw(int G, int n_depth)
 {
     if (n_depth > kRtMaxDepth) return 0;
     int gpw = 64 / G;
-    while (gpw > 1 && Layout(P, G, n_depth, gpw).bytes() > kLdsBytes) --gpw;
-    return Layout(P, G, n_depth, gpw).bytes() <= kLdsBytes ? gpw : 0;
+    while (gpw > 1 && Layout(G, n_depth, gpw).bytes() > kLdsBytes) --gpw;
+    return Layout(G, n_depth, gpw).bytes() <= kLdsBytes ? gpw : 0;
 }
 // Workgroups of kRtBlock threads that cover n_nu frequencies at gpw frequencies per wave.
 inline unsigned rt_blocks(long long n_nu, int gpw)
@@ -101,13 +100,13 @@ inline unsigned rt_blocks(long long n_nu, int gpw)
 namespace rt_layout_checks {
 constexpr bool even(int doubles) { return doubles % 2 == 0; }      // a double2 region: 16-byte aligned
 constexpr bool quad(int floats) { return floats % 4 == 0; }        // a float4 region
-constexpr bool columns_ok(int P, int G, int n_depth, int gpw)
+constexpr bool columns_ok(int G, int n_depth, int gpw)
 {
-    const RtColumns a(P, G, n_depth, gpw);
-    const RtContColumns c(P, G, n_depth, gpw);
-    return a.pairs() + 2 * gpw * n_depth <= a.flux() && a.flux() + a.batch * gpw * a.TH <= a.wave_doubles() && even(a.pairs()) && even(a.wave_doubles()) &&
-           c.pairs() + 2 * gpw * n_depth <= c.cont() && c.cont() + gpw * n_depth <= c.flux() && c.flux() + c.batch * gpw * c.TH <= c.flux_cont() &&
-           c.flux_cont() + c.batch * gpw * c.TH <= c.wave_doubles() && even(c.pairs()) && even(c.wave_doubles());
+    const RtColumns a(G, n_depth, gpw);
+    const RtContColumns c(G, n_depth, gpw);
+    return a.pairs() + 2 * gpw * n_depth <= a.flux() && a.flux() + kRtBatch * gpw * G <= a.wave_doubles() && even(a.pairs()) && even(a.wave_doubles()) &&
+           c.pairs() + 2 * gpw * n_depth <= c.cont() && c.cont() + gpw * n_depth <= c.flux() && c.flux() + kRtBatch * gpw * G <= c.flux_cont() &&
+           c.flux_cont() + kRtBatch * gpw * G <= c.wave_doubles() && even(c.pairs()) && even(c.wave_doubles());
 }
 constexpr bool f32_ok(int n_theta, int n_depth)
 {
@@ -121,13 +120,12 @@ constexpr bool segments_ok(int NS, int LMAX, int n_theta, int n_depth)
     return s.maps() + NS * 128 <= s.ray_table() && s.ray_table() + n_theta * s.rstride() <= s.pairs() && even(s.pairs()) && s.rstride() % 2 == 1 &&
            s.rstride() >= s.n_gap && s.flux() >= s.ray_table() && s.flux_end() <= s.doubles() && s.staging_end() <= s.doubles();
 }
-// one angle per lane at 3, 7 and 20 angles (odd row counts), two and four angles per lane, a deep model with gpw lowered
-static_assert(columns_ok(1, 3, 56, 21) && columns_ok(1, 7, 301, 3) && columns_ok(1, 20, 302, 2) && columns_ok(1, 5, 984, 1), "RtColumns / RtContColumns");
-static_assert(columns_ok(2, 4, 56, 16) && columns_ok(4, 5, 57, 12) && columns_ok(1, 20, 175, 2) && columns_ok(1, 64, 2, 1), "RtColumns / RtContColumns");
+// 3, 7 and 20 angles (odd row counts), deep models with gpw lowered, 64 angles at the shallowest model
+static_assert(columns_ok(3, 56, 21) && columns_ok(7, 301, 3) && columns_ok(20, 302, 2) && columns_ok(5, 984, 1), "RtColumns / RtContColumns");
+static_assert(columns_ok(20, 175, 2) && columns_ok(64, 2, 1), "RtColumns / RtContColumns");
 static_assert(f32_ok(20, 56) && f32_ok(7, 57) && f32_ok(64, 2) && f32_ok(1, 3), "RtF32Columns");
-// even and odd gap counts, both segmentations, the shallowest models; the flux terms fit the launch whichever of the two is larger
-static_assert(segments_ok(8, 7, 20, 56) && segments_ok(8, 7, 7, 57) && segments_ok(4, 14, 20, 56) && segments_ok(8, 7, 64, 2) && segments_ok(8, 7, 1, 3),
-              "RtSegments");
+// even and odd gap counts, the shallowest models; the flux terms fit the launch whichever of the two is larger
+static_assert(segments_ok(8, 7, 20, 56) && segments_ok(8, 7, 7, 57) && segments_ok(8, 7, 64, 2) && segments_ok(8, 7, 1, 3), "RtSegments");
 static_assert(RtSegments(8, 7, 20, 56).doubles() == RtSegments(8, 7, 20, 56).flux_end(), "20 angles: the flux terms are the larger");
 static_assert(RtSegments(8, 7, 1, 57).doubles() == RtSegments(8, 7, 1, 57).staging_end(), "one angle, 64 columns: the staging is the larger");
 }  // namespace rt_layout_checks

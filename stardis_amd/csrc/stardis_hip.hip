@@ -342,14 +342,6 @@ int launch_bf_coef(sdx_ctx* ctx, int n_depth, int n_species, int n_levels, const
     return check_launch("k_bf_coef");
 }
 
-// the formal solution's angles per lane P in {1, 2, 4} as a compile-time constant: f(std::integral_constant<int, P>)
-template <class F>
-void with_angles_per_lane(int P, F&& f)
-{
-    if (P == 1) f(std::integral_constant<int, 1>{});
-    else if (P == 2) f(std::integral_constant<int, 2>{});
-    else f(std::integral_constant<int, 4>{});
-}
 }  // namespace
 
 // ================================================================================================ runtime
@@ -818,8 +810,6 @@ struct ClassifyPhase {
 
 // The segmented formal solution (k_raytrace_seg: the gaps of a ray over the 8 waves of a workgroup) pays ~40 % more
 // instructions for eight times the waves: it wins where k_raytrace would leave the chip under three waves per SIMD.
-static const int kSegWaves = knob("SDX_RT_NS") && std::atoi(knob("SDX_RT_NS")) == 4 ? 4 : 8;  // experiment knob: 4 waves x 14 gaps
-static const int kSegMax = kSegWaves == 4 ? 14 : 7;
 // lane / G as a multiply and a shift in k_raytrace_seg (lane_div, sdx_kernels.h): exact for lane < 64, 1 <= G <= 64
 static int lane_recip(int G)
 {
@@ -827,7 +817,7 @@ static int lane_recip(int G)
 }
 static RtSegments seg_layout(int n_depth, int nth)
 {
-    return RtSegments(kSegWaves, kSegMax, nth, n_depth);
+    return RtSegments(8, 7, nth, n_depth);  // eight waves, at most seven gaps each
 }
 // Which kernel runs must not depend on how the grid is sharded or on the device (the two differ by the rounding of the affine
 // composition, a few ulp: a shard below the threshold next to an unsharded run above it would break the bit-identity of
@@ -1974,9 +1964,6 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
                          double* I_nus, int accumulate, int inward, const FusedTotal* fused = nullptr, int64_t nu_global = -1,
                          double* Fc = nullptr, int64_t fcld = 0);
 
-static const char* const kRtVariant[] = {"k_raytrace<1>", "k_raytrace<2>", "k_raytrace<4>"};  // [P / 2]
-static const char* const kRtContVariant[] = {"k_raytrace_cont<1>", "k_raytrace_cont<2>", "k_raytrace_cont<4>"};
-
 // the tail of spherical geometry: F_nu *= (r[-1] / reference_r)^2 (radiation_field_solvers/base.py:340-344); the continuum flux,
 // where there is one, in the same profiled launch scope
 static int scale_flux(sdx_ctx* ctx, int n_depth, int64_t n_nu, double* F, int64_t ld, double factor, double* Fc = nullptr, int64_t fcld = 0)
@@ -2044,15 +2031,13 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
         const double* w = wts + th0;
         double* inus = I_nus ? I_nus + th0 : nullptr;
         const int acc = (accumulate || th0 > 0) ? 1 : 0;
-        // Angles per lane P and lanes per frequency G = ceil(n_theta / P).  P = 1 (one lane per (frequency, angle)) is the
-        // default at every size measured; SDX_RT_P overrides it for experiments.
-        int P = 1;  // measured on MI355X at 7.6e3 and 1.2e5 frequencies: one angle per lane wins (more waves in flight)
-        if (const char* e = knob("SDX_RT_P")) {  // tuning knob: angles per lane (1, 2 or 4)
-            const int v = std::atoi(e);
-            if (v == 1 || v == 2 || v == 4) P = v;
-        }
-        const int G = (nth + P - 1) / P;
-        const int gpw = rt_fit_gpw<RtColumns>(P, G, n_depth);  // 0: the columns do not fit LDS
+        // One lane per (frequency, angle): G = nth lanes per frequency.  (Two and four angles per lane were measured on MI355X at 7.6e3
+        // and 1.2e5 frequencies and lost — fewer waves in flight; profiles/EXPERIMENTS.md.)
+        // The second argument of a LaunchScope (what sdx_profile_variant returns) is a profile LABEL, not a symbol: the name under which
+        // the kernel stands in every recorded benchmark and profile and in the GPU tests.  "k_raytrace<1>", "k_raytrace_cont<1>" and
+        // "k_contribution<1>" are the plain kernels k_raytrace, k_raytrace_cont and k_contribution; the labels stay byte for byte.
+        const int G = nth;
+        const int gpw = rt_fit_gpw<RtColumns>(G, n_depth);  // 0: the columns do not fit LDS
         const unsigned blocks_basic = (unsigned)((n_nu + (int64_t)(64 / G) * (kBlock / 64) - 1) / ((int64_t)(64 / G) * (kBlock / 64)));
         // plane-parallel, one angle per lane, nothing to add to, a small grid: the gaps of a ray split over the 8 waves of a
         // workgroup (k_raytrace_seg)
@@ -2060,11 +2045,11 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
         const int seg_gpw = seg.gpw();
         // the launch geometry of the XCD-aware order, handed to the kernel: workgroups, workgroups per XCD, whole rounds of eight
         const unsigned seg_wg = (unsigned)((n_nu + seg_gpw - 1) / seg_gpw), seg_per_xcd = (seg_wg + 7) / 8, seg_blocks = seg_per_xcd * 8;
-        if (use_segmented_raytrace(ctx, n_depth, nu_global, n_theta, P == 1 && !inward && !acc)) {
+        if (use_segmented_raytrace(ctx, n_depth, nu_global, n_theta, !inward && !acc)) {
             // the shape of the fused synthesis step — a fused total of 0, 2 or 3 line planes, the Planck source, flux only — has a kernel
             // of its own (k_raytrace_seg_step: the same bits); "segmented_raytrace" = 1 keeps the general kernel
             const int step_planes = ft.planes ? ft.n_planes : 0;
-            const bool step_shape = segmented_mode(ctx) != 1 && kSegWaves == 8 && ft.cont && !ft.source && ft.n_extra == 0 && !ft.line_out && !inus && F &&
+            const bool step_shape = segmented_mode(ctx) != 1 && ft.cont && !ft.source && ft.n_extra == 0 && !ft.line_out && !inus && F &&
                                     (step_planes == 0 || step_planes == 2 || step_planes == 3);
             SegStepGeom geo{};
             geo.gpw = seg_gpw, geo.g_recip = lane_recip(nth), geo.per = 64 / nth, geo.L = seg.segment();
@@ -2088,18 +2073,14 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
             };
             // the general kernel: the total as the caller asked for it, or the continuum plane alone
             auto launch_seg = [&](const double* a, int64_t a_ld, double* flux, int64_t flux_ld, double* intensity, const FusedTotal& fused_total) {
-                auto launch = [&](auto kernel) {
-                    hipLaunchKernelGGL(kernel, dim3(seg_blocks), dim3(64 * kSegWaves), seg.bytes(), ctx->stream, n_depth, n_nu, nth, n_theta, nus, temps, rd, w,
-                                       a, a_ld, flux, flux_ld, intensity, seg_gpw, lane_recip(nth), seg_wg, seg_per_xcd, fused_total);
-                };
-                if (kSegWaves == 4) launch(k_raytrace_seg<4, 14>);
-                else launch(k_raytrace_seg<8, 7>);
+                hipLaunchKernelGGL((k_raytrace_seg<8, 7>), dim3(seg_blocks), dim3(512), seg.bytes(), ctx->stream, n_depth, n_nu, nth, n_theta, nus, temps, rd, w,
+                                   a, a_ld, flux, flux_ld, intensity, seg_gpw, lane_recip(nth), seg_wg, seg_per_xcd, fused_total);
             };
             if (step_shape) {
                 LaunchScope ls(ctx, "k_raytrace", "k_raytrace_seg_step<8,7>");
                 launch_step(step_planes, ft.planes, ft.total_out, F, fld);
             } else {
-                LaunchScope ls(ctx, "k_raytrace", kSegWaves == 4 ? "k_raytrace_seg<4,14>" : "k_raytrace_seg<8,7>");
+                LaunchScope ls(ctx, "k_raytrace", "k_raytrace_seg<8,7>");
                 launch_seg(alphas, ald, F, fld, inus, ft);
             }
             int rc = check_launch("k_raytrace_seg");
@@ -2111,11 +2092,11 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
                 // (DESIGN.md).  Removed.
                 FusedTotal fc{};
                 fc.cont = ft.cont, fc.cld = ft.cld, fc.source = ft.source, fc.sld = ft.sld;
-                if (segmented_mode(ctx) != 1 && kSegWaves == 8 && !ft.source) {  // (this launch has the step kernel's shape whatever the first one had)
+                if (segmented_mode(ctx) != 1 && !ft.source) {  // (this launch has the step kernel's shape whatever the first one had)
                     LaunchScope ls(ctx, "k_raytrace", "k_raytrace_seg_step<8,7> (continuum)");
                     launch_step(0, nullptr, nullptr, Fc, fcld);
                 } else {
-                    LaunchScope ls(ctx, "k_raytrace", kSegWaves == 4 ? "k_raytrace_seg<4,14> (continuum)" : "k_raytrace_seg<8,7> (continuum)");
+                    LaunchScope ls(ctx, "k_raytrace", "k_raytrace_seg<8,7> (continuum)");
                     launch_seg(nullptr, 0, Fc, fcld, nullptr, fc);
                 }
                 if ((rc = check_launch("k_raytrace_seg"))) return rc;
@@ -2123,7 +2104,7 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
             continue;
         }
         // the tolerance path (mixed_precision = 1): plane-parallel, all angles in one launch, flux only -> the fp32 recurrence
-        if (ctx->mixed_precision && P == 1 && !inward && !acc && !inus && F && n_theta <= 64) {
+        if (ctx->mixed_precision && !inward && !acc && !inus && F && n_theta <= 64) {
             const int g32 = 64 / G;
             const RtF32Columns lay32(nth, G, n_depth, g32);
             if (n_depth <= kRtMaxDepth && lay32.bytes() <= kLdsBytes) {
@@ -2139,34 +2120,28 @@ static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
         }
         if (Fc) {
             REQUIRE(gpw > 0, "raytrace: no continuum flux for models this deep (the columns do not fit LDS)");
-            const int gpwc = rt_fit_gpw<RtContColumns>(P, G, n_depth);
+            const int gpwc = rt_fit_gpw<RtContColumns>(G, n_depth);
             REQUIRE(gpwc > 0, "raytrace: no continuum flux for models this deep (the columns do not fit LDS)");
             {
-                LaunchScope ls(ctx, "k_raytrace", kRtContVariant[P / 2]);
-                with_angles_per_lane(P, [&](auto p) {
-                    hipLaunchKernelGGL(k_raytrace_cont<decltype(p)::value>, dim3(rt_blocks(n_nu, gpwc)), dim3(kRtBlock), RtContColumns(P, G, n_depth, gpwc).bytes(),
-                                       ctx->stream, n_depth, n_nu, nth, n_theta, G, nus, temps, rd, w, F, fld, Fc, fcld, inus, inward, gpwc, ft);
-                });
+                LaunchScope ls(ctx, "k_raytrace", "k_raytrace_cont<1>");
+                hipLaunchKernelGGL(k_raytrace_cont, dim3(rt_blocks(n_nu, gpwc)), dim3(kRtBlock), RtContColumns(G, n_depth, gpwc).bytes(), ctx->stream, n_depth, n_nu,
+                                   nth, n_theta, G, nus, temps, rd, w, F, fld, Fc, fcld, inus, inward, gpwc, ft);
             }
             int rc = check_launch("k_raytrace_cont");
             if (rc) return rc;
             continue;
         }
         {
-            LaunchScope ls(ctx, "k_raytrace", gpw > 0 ? kRtVariant[P / 2] : "k_raytrace_basic");
-            if (gpw == 0) {  // very deep models: the column does not fit LDS, recompute per lane instead
+            LaunchScope ls(ctx, "k_raytrace", gpw > 0 ? "k_raytrace<1>" : "k_raytrace_basic");
+            if (gpw > 0) {
+                hipLaunchKernelGGL(k_raytrace, dim3(rt_blocks(n_nu, gpw)), dim3(kRtBlock), RtColumns(G, n_depth, gpw).bytes(), ctx->stream, n_depth, n_nu, nth, n_theta,
+                                   G, nus, temps, rd, w, alphas, ald, F, fld, inus, acc, inward, gpw, ft);
+            } else {  // very deep models: the column does not fit LDS, recompute per lane instead
                 REQUIRE(!ft.cont && !ft.source, "raytrace: fused total / caller's source plane not available for models this deep");
                 REQUIRE(!inward, "raytrace: spherical geometry needs (3*n_depth*64/n_theta + 2*n_depth*n_theta) doubles of LDS per wave; model too deep");
+                hipLaunchKernelGGL(k_raytrace_basic, dim3(blocks_basic), dim3(kBlock), 0, ctx->stream, n_depth, n_nu, nth, n_theta, G, nus, temps, rd, w, alphas, ald, F,
+                                   fld, inus, acc);
             }
-            with_angles_per_lane(P, [&](auto p) {
-                constexpr int kP = decltype(p)::value;
-                if (gpw > 0)
-                    hipLaunchKernelGGL(k_raytrace<kP>, dim3(rt_blocks(n_nu, gpw)), dim3(kRtBlock), RtColumns(P, G, n_depth, gpw).bytes(), ctx->stream, n_depth, n_nu, nth,
-                                       n_theta, G, nus, temps, rd, w, alphas, ald, F, fld, inus, acc, inward, gpw, ft);
-                else
-                    hipLaunchKernelGGL(k_raytrace_basic<kP>, dim3(blocks_basic), dim3(kBlock), 0, ctx->stream, n_depth, n_nu, nth, n_theta, G, nus, temps, rd, w,
-                                       alphas, ald, F, fld, inus, acc);
-            });
         }
         int rc = check_launch("k_raytrace");
         if (rc) return rc;
@@ -2212,16 +2187,15 @@ int sdx_contribution_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
     REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "contribution: need n_depth >= 2, n_theta > 0");
     REQUIRE(!ctx->mixed_precision, "contribution: no contribution function with mixed_precision = 1 (it decomposes the fp64 formal solution)");
     REQUIRE(n_theta <= 64, "contribution: more than 64 angles are not supported (all angles are traced in one launch)");
-    constexpr int P = 1;
     const int G = n_theta;
-    const int gpw = rt_fit_gpw<RtColumns>(P, G, n_depth);  // (k_raytrace<1>'s budget)
+    const int gpw = rt_fit_gpw<RtColumns>(G, n_depth);  // (k_raytrace's budget)
     REQUIRE(gpw > 0, "contribution: no contribution function for models this deep (the columns do not fit LDS)");
     if (n_nu == 0) return SDX_OK;
     REQUIRE(nus && ray_dist && wts && alphas && ald >= n_nu && C && cld >= n_nu, "contribution: null pointer or leading dimension below n_nu");
     REQUIRE(source ? source_ld >= n_nu : temps != nullptr, "contribution: bad source plane (source_ld < n_nu), or neither a source plane nor temperatures");
     {
         LaunchScope ls(ctx, "k_contribution", "k_contribution<1>");
-        hipLaunchKernelGGL(k_contribution<P>, dim3(rt_blocks(n_nu, gpw)), dim3(kRtBlock), RtColumns(P, G, n_depth, gpw).bytes(), ctx->stream, n_depth, n_nu, n_theta, n_theta, G,
+        hipLaunchKernelGGL(k_contribution, dim3(rt_blocks(n_nu, gpw)), dim3(kRtBlock), RtColumns(G, n_depth, gpw).bytes(), ctx->stream, n_depth, n_nu, n_theta, n_theta, G,
                            nus, temps, ray_dist, wts, alphas, ald, source, source_ld, C, cld, gpw);
     }
     return check_launch("k_contribution");
@@ -2379,13 +2353,13 @@ static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
     REQUIRE(!Fc || opt->continuum_ld >= nu_count, "synthesize: continuum_ld must cover the columns");
     for (int k = 0; k < n_extra; ++k) REQUIRE(opt->line_plane[k] && opt->line_plane_ld >= nu_count, "synthesize: bad line plane");
     // the formal solution forms total = continuum + line planes while staging its columns when those fit LDS
-    // (k_raytrace<1> at G = 64: one frequency per wave and the flux terms of 64 lanes, the worst case whatever n_theta is)
-    const bool fuse = n_theta <= 64 && rt_fit_gpw<RtColumns>(1, 64, n_depth) > 0;
-    // a continuum request that cannot be served is refused here, before anything is enqueued (k_raytrace_cont<1>, also at G = 64:
+    // (k_raytrace at G = 64: one frequency per wave and the flux terms of 64 lanes, the worst case whatever n_theta is)
+    const bool fuse = n_theta <= 64 && rt_fit_gpw<RtColumns>(64, n_depth) > 0;
+    // a continuum request that cannot be served is refused here, before anything is enqueued (k_raytrace_cont, also at G = 64:
     // deliberately the conservative limit, not the layout at this n_theta)
     REQUIRE(!Fc || !ctx->mixed_precision, "synthesize: no continuum flux with mixed_precision = 1 (the fp32 formal solution has no continuum chain)");
     REQUIRE(!Fc || fuse, "synthesize: the continuum flux needs the fused total (n_theta <= 64 and the model's columns in LDS)");
-    REQUIRE(!Fc || rt_fit_gpw<RtContColumns>(1, 64, n_depth) > 0, "synthesize: no continuum flux for models this deep (the columns do not fit LDS)");
+    REQUIRE(!Fc || rt_fit_gpw<RtContColumns>(64, n_depth) > 0, "synthesize: no continuum flux for models this deep (the columns do not fit LDS)");
     if (nu_count == 0) return SDX_OK;
     // Three launches on one stream: [pre-pass + continuum plane] -> [wide + narrow line kernels] -> [raytrace, which
     // forms total = continuum + line while staging its columns].  Independent work shares a launch instead of a

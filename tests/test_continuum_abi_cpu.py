@@ -1,6 +1,6 @@
 """The continuum-flux option at build time: the C struct and its ctypes mirror end with the two new fields, and the continuum
-formal-solution kernel k_raytrace_cont<1> compiles without spilled vector registers at the occupancy DESIGN.md gives for them, while the resource
-figures of k_raytrace<1> and k_raytrace_seg<8, 7> stay where they were."""
+formal-solution kernel k_raytrace_cont compiles without spilled vector registers at the occupancy DESIGN.md gives for them, while the resource
+figures of k_raytrace and k_raytrace_seg<8, 7> stay where they were."""
 import os
 import re
 
@@ -22,7 +22,7 @@ def test_options_struct_ends_with_the_continuum_fields():
 
 
 def test_continuum_kernel_does_not_spill(resources):  # noqa: F811
-    cont = resources["k_raytrace_cont<1>"]
+    cont = resources["k_raytrace_cont"]
     assert cont["spill"] == 0, cont
     # five waves per SIMD: what its 31.5 KB of LDS per block at S-c3 allows too
     assert cont["occ"] == 5, cont
@@ -31,6 +31,6 @@ def test_continuum_kernel_does_not_spill(resources):  # noqa: F811
 
 
 def test_existing_raytrace_kernels_keep_their_figures(resources):  # noqa: F811
-    assert {k: resources["k_raytrace<1>"][k] for k in ("vgpr", "spill", "occ")} == {"vgpr": 71, "spill": 0, "occ": 7}
+    assert {k: resources["k_raytrace"][k] for k in ("vgpr", "spill", "occ")} == {"vgpr": 71, "spill": 0, "occ": 7}
     # (77 since the flagged wave's replay keeps the fast pass's coefficients in the lanes that did not raise the flag; 79 before)
     assert {k: resources["k_raytrace_seg<8, 7>"][k] for k in ("vgpr", "spill", "occ")} == {"vgpr": 77, "spill": 0, "occ": 6}

@@ -1,5 +1,5 @@
 """The contribution-function entry points at build time: declared in the header, exported by the built library, mirrored in
-_lib.PROTOTYPES with matching argument counts; k_contribution<1> compiles for gfx950 without spilled vector registers at the figures
+_lib.PROTOTYPES with matching argument counts; k_contribution compiles for gfx950 without spilled vector registers at the figures
 DESIGN.md section 4 records; the formal-solution kernels beside it keep theirs; without a device the Python entry points raise."""
 import ctypes
 import os
@@ -32,21 +32,21 @@ def test_entry_points_declared_exported_and_mirrored():
 
 
 def test_contribution_kernel_resources(resources):  # noqa: F811
-    k = resources["k_contribution<1>"]
+    k = resources["k_contribution"]
     assert k["spill"] == 0, k
     # what the compiler gives: 60 VGPRs, eight waves per SIMD; the LDS is dynamic (the launch sizes it:
-    # k_raytrace<1>'s budget, 21 KB per block at 56 depths x 20 angles)
+    # k_raytrace's budget, 21 KB per block at 56 depths x 20 angles)
     assert (k["vgpr"], k["occ"], k["lds"]) == (60, 8, 0), k
     assert any(n.endswith("k_formation_mean") for n in resources)
-    # only P = 1 is built: more than 64 angles are refused
-    assert not any(n.startswith("k_contribution<") and n != "k_contribution<1>" for n in resources)
+    # one angle per lane and no other variant: more than 64 angles are refused
+    assert not any(n.startswith("k_contribution") and n != "k_contribution" for n in resources)
 
 
 def test_formal_solution_kernels_keep_their_figures(resources):  # noqa: F811
-    assert {k: resources["k_raytrace<1>"][k] for k in ("vgpr", "spill", "occ")} == {"vgpr": 71, "spill": 0, "occ": 7}
+    assert {k: resources["k_raytrace"][k] for k in ("vgpr", "spill", "occ")} == {"vgpr": 71, "spill": 0, "occ": 7}
     # (77 since the flagged wave's replay keeps the fast pass's coefficients in the lanes that did not raise the flag; 79 before)
     assert {k: resources["k_raytrace_seg<8, 7>"][k] for k in ("vgpr", "spill", "occ")} == {"vgpr": 77, "spill": 0, "occ": 6}
-    assert resources["k_raytrace_cont<1>"]["spill"] == 0 and resources["k_raytrace_cont<1>"]["occ"] == 5
+    assert resources["k_raytrace_cont"]["spill"] == 0 and resources["k_raytrace_cont"]["occ"] == 5
 
 
 def test_entry_points_fail_loudly():

@@ -35,12 +35,13 @@ def resources():
     names = {}
     for mangled in table:
         out = subprocess.run([filt, mangled], capture_output=True, text=True).stdout if filt else mangled
-        names[out.split("(")[0].replace("void sdx::", "").strip()] = table[mangled]
+        # (c++filt gives a template kernel its return type and a plain one none: both lose the namespace here)
+        names[out.split("(")[0].replace("void ", "").replace("sdx::", "").strip()] = table[mangled]
     return names
 
 
 def test_hot_kernels_do_not_spill_vector_registers(resources):
-    hot = [k for k in resources if k.startswith(("k_line_all<", "k_line_far<", "k_raytrace<1>", "k_raytrace_seg<8", "k_line_prepass<", "k_prepass_continuum<"))]
+    hot = [k for k in resources if k == "k_raytrace" or k.startswith(("k_line_all<", "k_line_far<", "k_raytrace_seg<8", "k_line_prepass<", "k_prepass_continuum<"))]
     assert len(hot) >= 10, sorted(resources)
     for k in hot:
         # the GENERATING pre-pass variants (<true, ...>: line parameters from per-line scalars, f1) evaluate every pow, log and tgamma of the
@@ -64,8 +65,15 @@ def test_line_kernels_keep_their_occupancy(resources):
     # (the kernels of the far field queue their hits: twelve more registers, six waves — measured against five and seven)
     assert resources["k_line_all<4, false, true>"]["occ"] >= 6 and resources["k_line_all<4, true, true>"]["occ"] >= 6
     assert resources["k_line_far<4, 2>"]["occ"] >= 6 and resources["k_line_far<4, 1>"]["occ"] >= 7
-    assert resources["k_raytrace<1>"]["occ"] >= 7 and resources["k_raytrace_seg<8, 7>"]["occ"] >= 6
+    assert resources["k_raytrace"]["occ"] >= 7 and resources["k_raytrace_seg<8, 7>"]["occ"] >= 6
     assert resources["k_line_all_mixed<4, false, false>"]["occ"] >= 6
+
+
+def test_formal_solution_family_is_the_set_the_truth_tests_run(resources):
+    """every formal-solution kernel the library ships is one a caller can reach, and tests/test_gpu_formal_solution_truth.py runs it"""
+    family = sorted(k for k in resources if k.startswith(("k_raytrace", "k_contribution")))
+    step = [f"k_raytrace_seg_step<8, 7, {p}, {k}>" for p in (0, 2, 3) for k in ("false", "true")]
+    assert family == sorted(["k_raytrace", "k_raytrace_basic", "k_raytrace_cont", "k_raytrace_f32", "k_raytrace_seg<8, 7>", "k_contribution"] + step), family
 
 
 def test_analysis_builds_compile():

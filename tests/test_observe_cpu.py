@@ -33,7 +33,7 @@ def test_entry_points_declared_exported_and_mirrored():
 
 
 def test_observe_kernel_does_not_spill(resources):  # noqa: F811
-    found = [v for name, v in resources.items() if name.endswith("k_observe")]  # (a plain kernel keeps its namespace in the table)
+    found = [v for name, v in resources.items() if name.endswith("k_observe")]
     assert len(found) == 1, sorted(resources)
     print(found[0])
     assert found[0]["spill"] == 0, found[0]
