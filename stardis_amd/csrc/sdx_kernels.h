@@ -13,6 +13,7 @@
 #include "sdx_broadening.h"
 #include "sdx_cheb.h"
 #include "sdx_rt_layout.h"
+#include "sdx_line_geom.h"
 
 namespace sdx {
 
@@ -2461,6 +2462,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     line_far_body<R, RF>(blockIdx.x, units, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, w, plane, pld, s_far);
 }
 
+// The kernels with a far field (FAR) take the launch as LineWords instead: the four words of the host's choices, which every wave
+// decodes itself with the divisions that LineGeom (sdx_line_geom.h) spares the others.  Every FAR instantiation fills its 80 registers
+// (six waves per SIMD) without a spill only as long as its entry code is what it was: with LineGeom's decode in the place of the one below
+// each of them spilled a vector register, and a kernel that spills is not run.  Their grids are large
+// and their waves long: ~600 scalar instructions at the head of a narrow wave are below one per cent of such a launch.
+// roles: bit 0 wide, bit 1 narrow; bits 2-3 narrow order; bits 4-7 wide group; bits 8-11 F; bits 16-17 RF of the merged far role (0: the
+// far field has a launch of its own).  Same grid, same units in the same order as line_launch_make's.
+struct LineWords {
+    int n_wide, tiles, roles, far_units;
+};
+template <bool FAR>
+using LineLaunchArg = std::conditional_t<FAR, LineWords, LineGeom>;
+
 // Both line kernels in ONE launch of workgroups of S waves (S = number of line subsets): workgroups [0, n_wide) take the
 // wide role — one (depth, tile) each, wave s walks subset s — depth slowest, hottest layers first; the rest take the narrow
 // role, one frequency per wave.  The two roles only share the pre-pass, and each leaves issue slots idle on its own; a
@@ -2469,12 +2483,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 // far field's workgroups (line_far_body) come FIRST in the grid, n_depth x far_units of them (fp64 kernels with a far field).
 // Output planes: [0] the wide windows (all subsets summed), [1] the narrow windows.
 template <int R, bool MIXED, bool SUBSETS, bool FAR = false, bool LISTED = false>
-__device__ __forceinline__ void line_all_body(int n_wide, int tiles, int n_split, int n_depth, int64_t n_nu,
+__device__ __forceinline__ void line_all_body(LineLaunchArg<FAR> g, int n_split, int n_depth, int64_t n_nu,
                                                    const double* __restrict__ nus, int64_t nu_begin, int64_t nu_count,
                                                    int64_t n_lines, const double* __restrict__ line_nus, LineWork w,
-                                                   double* __restrict__ planes, int64_t pld, int roles, int far_units)
+                                                   double* __restrict__ planes, int64_t pld)
 {
     extern __shared__ double s_wide[];  // n_split x kWideLdsDoubles
+    // block -> unit of work.  Without a far field: sdx_line_geom.h — the launch's constants come formed from the host, no wave divides by
+    // one; g is read where a role begins and nowhere else (n_split, which lives as long as the walks, is an argument of its own: a word of
+    // g that stays live keeps the words it was loaded with in registers, or in spill lanes).  FAR: LineWords, decoded here.
     int b = blockIdx.x;
     // (fp32-mixed kernels with a far field: what is left to the wide role — a line's near zone, window edges, kept cores — is walked in
     // fp64 by the queued walk like the fp64 kernels'; the narrow role and the formal solution stay the mode's fp32)
@@ -2482,14 +2499,14 @@ __device__ __forceinline__ void line_all_body(int n_wide, int tiles, int n_split
     if constexpr (FAR) {
         // far role (roles bits 16-17: RF, 0 = the far field has a launch of its own): the FIRST workgroups of the grid — their waves are
         // the longest chains of the launch (a unit walks every huge line of the list) — n_depth x far_units of them
-        const int rf = (roles >> 16) & 3;
+        const int rf = (g.roles >> 16) & 3;
         if (rf) {
-            const int n_far = n_depth * far_units;
+            const int n_far = n_depth * g.far_units;
             if (b < n_far) {
                 double* const far_plane = planes + (size_t)2 * n_depth * pld;
                 // (fp32-mixed mode: the node sums in packed fp32 — units of 8 tiles, the default; the experiment knob's units of 4 stay fp64)
-                if (rf == 2) line_far_body<R, 2, MIXED>(b, far_units, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, w, far_plane, pld, s_wide);
-                else line_far_body<R, 1>(b, far_units, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, w, far_plane, pld, s_wide);
+                if (rf == 2) line_far_body<R, 2, MIXED>(b, g.far_units, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, w, far_plane, pld, s_wide);
+                else line_far_body<R, 1>(b, g.far_units, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, w, far_plane, pld, s_wide);
                 return;
             }
             b -= n_far;
@@ -2503,25 +2520,35 @@ __device__ __forceinline__ void line_all_body(int n_wide, int tiles, int n_split
     [[maybe_unused]] double part[R];
     [[maybe_unused]] int out_row = 0, out_col = 0;      // where lane's sums go: row (depth), first column; columns step 64 (wide) or 1 (narrow)
     [[maybe_unused]] bool out_wide = true, out_valid = true;
-    if (b < n_wide) {
-        if (!(roles & 1)) return;
+    bool wide_role;
+    if constexpr (FAR) wide_role = b < g.n_wide;
+    else wide_role = b < g.narrow_first;
+    if (wide_role) {
         // XCD-aware tile order: workgroup i runs on XCD i % 8, each with its own L2.  Within a depth the workgroups of one XCD
         // take CONTIGUOUS tiles (position p -> tile prefix(p % 8) + p / 8), so neighbouring tiles, whose line ranges
         // overlap, hit the same L2 instead of pulling the same records into all eight.
-        const int wg = (roles >> 4) & 15;  // 0: one contiguous eighth of the tiles per XCD; g > 0: groups of g tiles going round the XCDs
         int tile, d;
-        if (wg == 0) {
-            const int p = b % tiles;
-            d = b / tiles;
-            tile = p >> 3;
-            for (int f = 0; f < (p & 7); ++f) tile += (tiles - f + 7) >> 3;
+        if constexpr (FAR) {
+            if (!(g.roles & 1)) return;
+            const int tiles = g.tiles;
+            const int wg = (g.roles >> 4) & 15;  // 0: one contiguous eighth of the tiles per XCD; g > 0: groups of g tiles going round the XCDs
+            if (wg == 0) {
+                const int p = b % tiles;
+                d = b / tiles;
+                tile = p >> 3;
+                for (int f = 0; f < (p & 7); ++f) tile += (tiles - f + 7) >> 3;
+            } else {
+                // (the host pads the tiles of a depth to whole rounds of 8 g workgroups: b % 8 is then the XCD within every depth)
+                const int tiles_pad = (tiles + 8 * wg - 1) / (8 * wg) * (8 * wg);
+                const int p = b % tiles_pad, j = p >> 3;
+                d = b / tiles_pad;
+                tile = ((j / wg) * 8 + (p & 7)) * wg + j % wg;
+                if (tile >= tiles) return;
+            }
         } else {
-            // (the host pads the tiles of a depth to whole rounds of 8 g workgroups: b % 8 is then the XCD within every depth)
-            const int tiles_pad = (tiles + 8 * wg - 1) / (8 * wg) * (8 * wg);
-            const int p = b % tiles_pad, j = p >> 3;
-            d = b / tiles_pad;
-            tile = ((j / wg) * 8 + (p & 7)) * wg + j % wg;
-            if (tile >= tiles) return;
+            const WideUnit wu = wide_unit(g, b);
+            if (!wu.live) return;
+            tile = wu.tile, d = wu.depth;
         }
         if constexpr (SUBSETS) {
             line_wide_walk<R, WM, true, WM, FAR, LISTED>(tile, wave, n_split, d, n_nu, nus, nu_begin, nu_count, n_lines, w, planes, pld, s_wide, part);
@@ -2531,7 +2558,6 @@ __device__ __forceinline__ void line_all_body(int n_wide, int tiles, int n_split
             line_wide_walk<R, WM, false, false, FAR, LISTED>(tile, wave, n_split, d, n_nu, nus, nu_begin, nu_count, n_lines, w, planes, pld, s_wide);
         }
     } else {
-        if (!(roles & 2)) return;
         // A wave writes one value into each of the N_d rows of the narrow plane: the waves that fill a 64-byte sector of a
         // row (8 consecutive frequencies) should share an L2, or every XCD writes its own fragment of every sector back on
         // its own.  Workgroups p, p + 8, ... (one XCD) therefore take GROUPS of kNarrowGroup consecutive workgroups' worth
@@ -2539,28 +2565,36 @@ __device__ __forceinline__ void line_all_body(int n_wide, int tiles, int n_split
         // 45 % slower: the lines per grid point follow the frequency, so one XCD gets several times the work of another.)
         // (SUBSETS: a workgroup is ONE group of frequencies, not four — sixteen workgroups keep the 64 consecutive frequencies per XCD
         // whose lines' records then meet in one L2)
-        constexpr int kNarrowGroup = SUBSETS ? 16 : 4;
-        // F consecutive frequencies per wave (roles bits 8-11: 1, 2 or 4 — 8 was measured slower), groups aligned
-        // to the global grid
-        const int F = max(1, (roles >> 8) & 15);
+        // F consecutive frequencies per wave (1, 2 or 4 — 8 was measured slower), groups aligned to the global grid.
         // dense long lists (a kernel of their own — SUBSETS — so that neither walk pays for the other's registers: with both narrow
         // walks in one kernel the WIDE role spilled, and a kernel that touches scratch memory ran a third slower): the workgroup's
         // four waves share one group of F = 4 frequencies
-        constexpr bool subsets = SUBSETS;
-        const int64_t g0 = nu_begin / F;
-        const int64_t n_grp = (nu_begin + nu_count + F - 1) / F - g0;
-        const int64_t n_narrow = n_grp * ((n_depth + 63) / 64);
-        const int64_t n_nb = subsets ? n_narrow : (n_narrow + n_split - 1) / n_split;
-        const int64_t p = b - n_wide, j = p >> 3;
-        const int order = (roles >> 2) & 3;  // analysis knob (SDX_NARROW_ORDER): 0 grouped (default), 1 plain, 2 one block per XCD
-        int64_t wg = ((j / kNarrowGroup) * 8 + (p & 7)) * kNarrowGroup + j % kNarrowGroup;
-        if (order == 1) wg = p;
-        if (order == 2) wg = (p & 7) * ((n_nb + 7) / 8) + j;
-        if ((order == 2 && j >= (n_nb + 7) / 8) || wg >= n_nb) return;
-        const int64_t c = subsets ? wg : wg * n_split + wave;
-        if (c >= n_narrow) return;  // (subsets: the whole workgroup)
-        const int64_t i0 = (g0 + c % n_grp) * F;
-        const int chunk = (int)(c / n_grp);
+        int64_t i0;
+        int chunk;
+        [[maybe_unused]] int F;
+        if constexpr (FAR) {
+            if (!(g.roles & 2)) return;
+            constexpr int kNarrowGroup = SUBSETS ? kNarrowGroupSubsets : kNarrowGroupPlain;
+            F = max(1, (g.roles >> 8) & 15);
+            const int64_t g0 = nu_begin / F;
+            const int64_t n_grp = (nu_begin + nu_count + F - 1) / F - g0;
+            const int64_t n_narrow = n_grp * ((n_depth + 63) / 64);
+            const int64_t n_nb = SUBSETS ? n_narrow : (n_narrow + n_split - 1) / n_split;
+            const int64_t p = b - g.n_wide, j = p >> 3;
+            const int order = (g.roles >> 2) & 3;  // analysis knob (SDX_NARROW_ORDER): 0 grouped (default), 1 plain, 2 one block per XCD
+            int64_t wg = ((j / kNarrowGroup) * 8 + (p & 7)) * kNarrowGroup + j % kNarrowGroup;
+            if (order == 1) wg = p;
+            if (order == 2) wg = (p & 7) * ((n_nb + 7) / 8) + j;
+            if ((order == 2 && j >= (n_nb + 7) / 8) || wg >= n_nb) return;
+            const int64_t c = SUBSETS ? wg : wg * n_split + wave;
+            if (c >= n_narrow) return;  // (subsets: the whole workgroup)
+            i0 = (g0 + c % n_grp) * F;
+            chunk = (int)(c / n_grp);
+        } else {
+            const NarrowUnit unit = narrow_unit<SUBSETS>(g, b, wave);
+            if (!unit.live) return;  // (subsets: the whole workgroup)
+            i0 = unit.i0, chunk = unit.chunk, F = 1 << g.f_shift;
+        }
         double* __restrict__ nplane = planes + (size_t)n_depth * pld;
         if constexpr (SUBSETS) {
             static_assert(!SUBSETS || R == 4, "the common reduction: R points per wide lane = F frequencies per narrow group");
@@ -2609,31 +2643,31 @@ __device__ __forceinline__ void line_all_body(int n_wide, int tiles, int n_split
 }
 
 template <int R, bool SUBSETS = false, bool FAR = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FAR ? SDX_FAR_WAVES : 7, 8))) void k_line_all(int n_wide, int tiles, int n_split, int n_depth, int64_t n_nu,
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FAR ? SDX_FAR_WAVES : 7, 8))) void k_line_all(LineLaunchArg<FAR> g, int n_split, int n_depth, int64_t n_nu,
                                                    const double* __restrict__ nus, int64_t nu_begin, int64_t nu_count,
                                                    int64_t n_lines, const double* __restrict__ line_nus, LineWork w,
-                                                   double* __restrict__ planes, int64_t pld, int roles, int far_units)
+                                                   double* __restrict__ planes, int64_t pld)
 {
-    line_all_body<R, false, SUBSETS, FAR>(n_wide, tiles, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, planes, pld, roles, far_units);
+    line_all_body<R, false, SUBSETS, FAR>(g, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, planes, pld);
 }
 // short lists whose pre-pass has listed their wide lines (LineWork::n_csplit, context option "wide_list"): the wide role walks its
 // subset's list instead of scanning every line; everything else is k_line_all
 template <int R, bool SUBSETS = false, bool FAR = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FAR ? SDX_FAR_WAVES : 7, 8))) void k_line_listed(int n_wide, int tiles, int n_split, int n_depth, int64_t n_nu,
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FAR ? SDX_FAR_WAVES : 7, 8))) void k_line_listed(LineLaunchArg<FAR> g, int n_split, int n_depth, int64_t n_nu,
                                                    const double* __restrict__ nus, int64_t nu_begin, int64_t nu_count,
                                                    int64_t n_lines, const double* __restrict__ line_nus, LineWork w,
-                                                   double* __restrict__ planes, int64_t pld, int roles, int far_units)
+                                                   double* __restrict__ planes, int64_t pld)
 {
-    line_all_body<R, false, SUBSETS, FAR, true>(n_wide, tiles, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, planes, pld, roles, far_units);
+    line_all_body<R, false, SUBSETS, FAR, true>(g, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, planes, pld);
 }
 // the mixed-precision variant: 512-point tiles; the register budget is capped at 128 (4 waves per SIMD) — what exceeds it
 // sits in the rarely taken fp64 general path
 template <int R, bool SUBSETS = false, bool FAR = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(R == 4 ? 6 : 4, 8))) void k_line_all_mixed(
-    int n_wide, int tiles, int n_split, int n_depth, int64_t n_nu, const double* __restrict__ nus, int64_t nu_begin, int64_t nu_count,
-    int64_t n_lines, const double* __restrict__ line_nus, LineWork w, double* __restrict__ planes, int64_t pld, int roles, int far_units)
+    LineLaunchArg<FAR> g, int n_split, int n_depth, int64_t n_nu, const double* __restrict__ nus, int64_t nu_begin, int64_t nu_count,
+    int64_t n_lines, const double* __restrict__ line_nus, LineWork w, double* __restrict__ planes, int64_t pld)
 {
-    line_all_body<R, true, SUBSETS, FAR>(n_wide, tiles, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, planes, pld, roles, far_units);
+    line_all_body<R, true, SUBSETS, FAR>(g, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, planes, pld);
 }
 
 // out (+)= sum over the S line subsets, in subset order

@@ -1246,13 +1246,10 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     const int64_t pld = nu_count;
     // tiles are aligned to the GLOBAL grid (multiples of 64 Rm points from index 0), whatever the shard: which points share a
     // tile — and with it how a (line, depth, tile) is classified and which points share a reciprocal — is a property of the grid
-    const int tiles = (int)((nu_begin + nu_count + 64 * Rm - 1) / (64 * Rm) - nu_begin / (64 * Rm));
     // order of the wide role's tiles over the XCDs: one contiguous eighth each (0), or groups of g tiles going round them —
     // better balance where an eighth is only a few tiles (a shard's), at the price of fewer neighbouring tiles per L2
     static const int wide_group_env = knob("SDX_WIDE_GROUP") ? std::atoi(knob("SDX_WIDE_GROUP")) & 15 : -1;
     const int wide_group = wide_group_env >= 0 ? wide_group_env : 0;
-    const int64_t tiles_pad = wide_group ? ((int64_t)tiles + 8 * wide_group - 1) / (8 * wide_group) * (8 * wide_group) : tiles;
-    const int64_t n_wide = tiles_pad * n_depth;
     // workgroups of n_split waves, rounded up to whole rounds of the XCD-aware order (surplus workgroups return at once)
     // narrow role: F consecutive frequencies per wave (a line's records, loaded once, serve F evaluations) for DENSE lists —
     // at least one line per two grid points, where a frequency visits many lines and the walk is bound by its loads and
@@ -1275,13 +1272,8 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     const int64_t sub_density = sub_density_env >= 0 ? sub_density_env : 8;
     const int narrow_sub = (!no_narrow_subsets && 2 * n_lines >= sub_density * n_nu && n_split == 4 && Rm != 8) ? 4 : 0;
     if (narrow_sub) narrow_f = 4;
-    const int64_t n_grp = (nu_begin + nu_count + narrow_f - 1) / narrow_f - nu_begin / narrow_f;
-    const int64_t n_narrow_units = n_grp * ((n_depth + 63) / 64);
-    // (whole rounds of the XCD-aware order: 8 XCDs x groups of 4 workgroups, 16 in the subsets kernel)
-    const int64_t narrow_round = narrow_sub ? 128 : 32;
-    const int64_t n_narrow = (((narrow_sub ? n_narrow_units : (n_narrow_units + n_split - 1) / n_split) + narrow_round - 1) / narrow_round) * narrow_round;
+    // (the narrow workgroups come in whole rounds of the XCD-aware order: line_launch_make, sdx_line_geom.h)
     static const int narrow_order = knob("SDX_NARROW_ORDER") ? atoi(knob("SDX_NARROW_ORDER")) & 3 : 0;
-    REQUIRE(n_wide + n_narrow < ((int64_t)1 << 31), "line opacity: grid too large for one launch");
     static const bool split_launches = knob("SDX_SPLIT_LAUNCHES") != nullptr;  // analysis knob: time the two roles apart
     const bool split_launches_early = split_launches;
     size_t shmem = (size_t)n_split * (far && SDX_WIDE_QUEUED ? kWideFarLdsDoubles : kWideLdsDoubles) * sizeof(double);
@@ -1299,10 +1291,14 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     if (far_rf_env == 1 || far_rf_env == 2) far_rf = far_rf_env;
     const int64_t far_units = far ? far_units_of(far_rf) : 0;
     const bool far_merged = far && !far_own_launch && !split_launches_early;
-    const int64_t n_far = far_merged ? far_units * n_depth : 0;
     if (far_merged) shmem = std::max(shmem, (((size_t)n_split + 2) * far_rf * 64 + (size_t)n_split * kFarWaveLdsDoubles) * sizeof(double));
-    REQUIRE(n_far + n_wide + n_narrow < ((int64_t)1 << 31), "line opacity: grid too large for one launch");
-    const dim3 g((unsigned)(n_far + n_wide + n_narrow)), blk((unsigned)(64 * n_split));
+    // The launch's geometry, formed ONCE here (sdx_line_geom.h): which block is which role's which unit — tiles aligned to the global
+    // grid, the XCD-aware orders of both roles, the narrow role's groups of F frequencies, every knob above resolved — so that no wave
+    // divides by a launch constant.  It also states the range: grid, units and frequency indices stay 32-bit.
+    const LineLaunch launch = line_launch_make(nu_begin, nu_count, n_depth, n_split, 64 * Rm, narrow_f, narrow_sub != 0, wide_group, narrow_order,
+                                               kLineRoleWide | kLineRoleNarrow, far_merged ? far_units * n_depth : 0);
+    REQUIRE(launch.ok, "line opacity: grid too large for one launch");
+    const dim3 g((unsigned)launch.blocks), blk((unsigned)(64 * n_split));
     // (k_line_far on a second stream beside k_line_all — a fork and a join per step — was measured in round 5: S-c3 1.857 -> 1.840 ms, its
     // eighth 0.419 -> 0.420, S-c4m 7.49 -> 7.48: both kernels are bound by their instructions, neither leaves the other idle slots)
     auto launch_far = [&]() -> int {
@@ -1324,23 +1320,32 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     for (int pass = 0; pass < (split_launches ? 2 : 1); ++pass) {
         // (raising the priority of the hot layers' waves with s_setprio was measured in round 4: the instruction has side effects as
         // far as the compiler is concerned, the record fetches of the walk stopped being scalar loads and the kernel ran 37 % slower)
-        const int roles = (split_launches ? (1 << pass) : 3) | (narrow_order << 2) | (wide_group << 4) | (narrow_f << 8) | (narrow_sub << 12) | ((far_merged ? far_rf : 0) << 16);
+        // (split launches: the same grid twice, one role live in each)
+        const LineGeom geom = split_launches ? line_launch_make(nu_begin, nu_count, n_depth, n_split, 64 * Rm, narrow_f, narrow_sub != 0, wide_group, narrow_order,
+                                                                pass ? kLineRoleNarrow : kLineRoleWide, 0).g : launch.g;
         LaunchScope ls(ctx, split_launches ? (pass ? "k_line_narrow" : "k_line_wide") : "k_line_all", far_merged ? "k_line_all + far role" : (far ? "k_line_all (far field in k_line_far)" : nullptr));
-#define SDX_LINE_ARGS (int)n_wide, tiles, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, part, pld, roles, (int)far_units
+        // (the kernels with a far field decode the launch themselves: LineWords, sdx_kernels.h — the same grid and the same units)
+        const LineWords words{geom.narrow_first - geom.wide_first, (int)(((nu_begin + nu_count + 64 * Rm - 1) / (64 * Rm)) - nu_begin / (64 * Rm)),
+                              (split_launches ? (1 << pass) : 3) | (narrow_order << 2) | (wide_group << 4) | (narrow_f << 8) | ((far_merged ? far_rf : 0) << 16), (int)far_units};
+#define SDX_LINE_TAIL n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, part, pld
+#define SDX_LINE_ARGS geom, SDX_LINE_TAIL
+#define SDX_LINE_FAR_ARGS words, SDX_LINE_TAIL
         if (ctx->mixed_precision && Rm == 8) hipLaunchKernelGGL((k_line_all_mixed<8>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
-        else if (ctx->mixed_precision && narrow_sub && far) hipLaunchKernelGGL((k_line_all_mixed<R_MIXED, true, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
+        else if (ctx->mixed_precision && narrow_sub && far) hipLaunchKernelGGL((k_line_all_mixed<R_MIXED, true, true>), g, blk, shmem, ctx->stream, SDX_LINE_FAR_ARGS);
         else if (ctx->mixed_precision && narrow_sub) hipLaunchKernelGGL((k_line_all_mixed<R_MIXED, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
-        else if (ctx->mixed_precision && far) hipLaunchKernelGGL((k_line_all_mixed<R_MIXED, false, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
+        else if (ctx->mixed_precision && far) hipLaunchKernelGGL((k_line_all_mixed<R_MIXED, false, true>), g, blk, shmem, ctx->stream, SDX_LINE_FAR_ARGS);
         else if (ctx->mixed_precision) hipLaunchKernelGGL((k_line_all_mixed<R_MIXED>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
-        else if (w.n_csplit && narrow_sub && far) hipLaunchKernelGGL((k_line_listed<R, true, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
+        else if (w.n_csplit && narrow_sub && far) hipLaunchKernelGGL((k_line_listed<R, true, true>), g, blk, shmem, ctx->stream, SDX_LINE_FAR_ARGS);
         else if (w.n_csplit && narrow_sub) hipLaunchKernelGGL((k_line_listed<R, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
-        else if (w.n_csplit && far) hipLaunchKernelGGL((k_line_listed<R, false, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
+        else if (w.n_csplit && far) hipLaunchKernelGGL((k_line_listed<R, false, true>), g, blk, shmem, ctx->stream, SDX_LINE_FAR_ARGS);
         else if (w.n_csplit) hipLaunchKernelGGL((k_line_listed<R>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
-        else if (narrow_sub && far) hipLaunchKernelGGL((k_line_all<R, true, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
+        else if (narrow_sub && far) hipLaunchKernelGGL((k_line_all<R, true, true>), g, blk, shmem, ctx->stream, SDX_LINE_FAR_ARGS);
         else if (narrow_sub) hipLaunchKernelGGL((k_line_all<R, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
-        else if (far) hipLaunchKernelGGL((k_line_all<R, false, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
+        else if (far) hipLaunchKernelGGL((k_line_all<R, false, true>), g, blk, shmem, ctx->stream, SDX_LINE_FAR_ARGS);
         else hipLaunchKernelGGL((k_line_all<R>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
 #undef SDX_LINE_ARGS
+#undef SDX_LINE_FAR_ARGS
+#undef SDX_LINE_TAIL
     }
     if (far && !far_merged && (rc = launch_far())) return rc;
     *partial_out = part;
