@@ -138,7 +138,10 @@ int sdx_synchronize(sdx_ctx* ctx);
  *       option says (its fp32 partial sums are flushed at chunk boundaries, which a compacted list would move).  -1: 1 for lists of at
  *       least 16 chunks of 64 lines per line subset (2000 lines on 7634 points, two subsets: the line kernel 1.2 us faster, the list
  *       built in the shadow of the launch's continuum tiles), 0 below (2000 lines on 1000 points, eight subsets: nothing gained and 3 us
- *       more at the end of the pre-pass launch). */
+ *       more at the end of the pre-pass launch).
+ *   "grid_plan" (default -1): -1: a step that is given an sdx_grid_plan (sdx_synthesis_options.grid_plan) uses it; 0: the plan is
+ *       checked and then ignored — the step runs the kernels it runs without one (A/B runs inside one library).  The same bits
+ *       either way. */
 int sdx_set_int_option(sdx_ctx* ctx, const char* name, int64_t value);
 /* The far-field rule as the library applies it — for planners that weigh shards (stardis_amd.parallel.column_cost) and must not
  * carry constants of their own.  sdx_far_field_active: 1 when a synthesis of a GLOBAL grid of n_nu_global points on this context runs
@@ -620,7 +623,12 @@ int sdx_alpha_line_levels_dev(sdx_ctx* ctx, int64_t n_lines, int n_depth, int n_
  *                        linelist and line_m_max (the synthesis after the classification in the two-collective mode, step 3 below).  SDX_ERR_ARG (-1) with "mixed_precision" = 1,
  *                        or where the step cannot fuse the total into the formal solution (n_theta > 64, models whose columns do
  *                        not fit LDS).
+ *   grid_plan            when set, a plan built for this grid, line list and cross-section table (sdx_grid_plan_create, below): the
+ *                        pre-pass launch reads what depends on them alone from the plan instead of forming it again.  Bit-identical
+ *                        results.  A plan whose recorded pointers or sizes differ from this call's is SDX_ERR_ARG before anything is
+ *                        enqueued.
  * A zero-initialised description is sdx_synthesize_dev, bit for bit; `options` itself must not be NULL (-1). */
+typedef struct sdx_grid_plan sdx_grid_plan;
 typedef struct sdx_synthesis_options {
     const double* source;
     int64_t source_ld;
@@ -632,9 +640,38 @@ typedef struct sdx_synthesis_options {
     int64_t line_plane_ld;
     const sdx_linelist* linelist;
     const double* line_m_max; /* two-collective mode (below): the gathered per-line maxima [n_lines], or NULL */
+    const sdx_grid_plan* grid_plan; /* or NULL */
     double* F_nu_continuum;   /* [n_depth][continuum_ld] continuum flux, or NULL (no continuum chain) */
     int64_t continuum_ld;
 } sdx_synthesis_options;
+
+/* ---- grid plan: the grid-only work of the fused step, once per grid instead of once per step -----------------------------------
+ * The pre-pass launch of a step begins with work that reads nothing but the frequency grid, the line frequencies and the tabulated
+ * cross-section: the grid spacing d_nu (opacities_solvers/base.py:524-526) and 1 / d_nu, every line's centre index (:556-558),
+ * the number of lines centred at or beyond each grid index, and per frequency the interpolated cross-section (util.py:94-103),
+ * nu^-3 and the Rayleigh powers (nu / (2 c R))^4,6,8.  A synthesis that is stepped many times on one grid and one list — a fit,
+ * a model grid: line STRENGTHS, widths, dampings, temperatures and densities change from step to step, the grid and the list do
+ * not — forms them once:
+ *   sdx_grid_plan_create   allocates the plan's device arrays from the context's block pool and enqueues ONE launch
+ *                          (k_grid_plan_build) on the context's stream that fills them with the step's own device functions and
+ *                          operations: the values are the step's, bit for bit.  cont may be NULL (no table).  No host round trip;
+ *                          the allocation makes it unfit for stream capture, the other two calls are capturable.
+ *   sdx_grid_plan_refresh  the same launch again — after the caller has changed the VALUES of the arrays in place.
+ *   sdx_grid_plan_destroy  returns the arrays to the pool (uses are ordered on the context's stream).
+ * Contract: the plan records the pointers and sizes it was built from (nus, n_nu, line_nus, n_lines, cont->lambdas,
+ * cont->table_wavelength, cont->table_sigma, cont->n_table).  While a plan is in use the VALUES of nus, line_nus, lambdas, the
+ * table's axis and the table must not change, short of a refresh.  Everything per depth (temperatures, every density, ray
+ * distances), the bound-free edges and the lines' doppler_widths, gammas and alphas may change freely: none of it is in the plan.
+ * Honoured by sdx_synthesize_opt_dev on the un-culled pre-pass of a dense line list next to the tiled continuum (at most 4096
+ * bound-free levels): whole grids and frequency shards of lists below "indexed_min_lines", whole grids of longer ones.  IGNORED
+ * (after the check of its pointers and sizes) by culled shards and the two-collective mode (line_m_max) and where the context
+ * option "grid_plan" is 0; ignored unchecked with a line list given as scalars (options->linelist: the generating pre-pass has no
+ * planned form).  On grids of more than 16384 points the planned step also drops the grid-spacing launch unless the far field
+ * needs its tile ranges.  A recorded hipGraph holds the plan's device pointers: destroy the graph before the plan. */
+int sdx_grid_plan_create(sdx_ctx* ctx, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus,
+                         const sdx_continuum* cont_or_null, sdx_grid_plan** out);
+int sdx_grid_plan_refresh(sdx_grid_plan* plan);
+void sdx_grid_plan_destroy(sdx_grid_plan* plan);
 int sdx_synthesize_opt_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
                            int64_t n_lines, const double* line_nus, const double* doppler_widths, const double* gammas,
                            int gamma_cols, const double* alphas, const sdx_continuum* cont, int n_theta,

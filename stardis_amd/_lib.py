@@ -95,6 +95,7 @@ class SynthesisOptions(C.Structure):
         ("line_plane_ld", _i64),
         ("linelist", C.POINTER(LineListStruct)),
         ("line_m_max", _vp),
+        ("grid_plan", _vp),
         ("F_nu_continuum", _vp),
         ("continuum_ld", _i64),
     ]
@@ -186,6 +187,9 @@ PROTOTYPES = {
                                      _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "sdx_synthesize_opt_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, C.POINTER(Continuum), _int,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(SynthesisOptions), _vp]),
+    "sdx_grid_plan_create": (_int, [_vp, _i64, _vp, _i64, _vp, C.POINTER(Continuum), C.POINTER(_vp)]),
+    "sdx_grid_plan_refresh": (_int, [_vp]),
+    "sdx_grid_plan_destroy": (None, [_vp]),
     "sdx_synthesize_classify_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, C.POINTER(Continuum), _i64, _i64, _vp]),
     "sdx_synthesize_f64": (_int, [_vp, _int, _i64, _vp, _i64, _vp, _vp, _vp, _int, _vp, C.POINTER(Continuum), _int, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _vp]),

@@ -409,7 +409,12 @@ __device__ __forceinline__ void compact_wide_lines(const LineWork& w, const int6
     }
 }
 
-template <bool GEN, int kPreLines, bool LIST = true>
+// PLANNED (sdx_grid_plan, include/stardis_hip.h): what depends on the grid and the line frequencies alone was formed once, by
+// k_grid_plan_build — a planned line block stages no grid sample, searches no centre and scans no spacing: `dnu_partial` is then the
+// plan's array of doubles ([0] = d_nu, [1] = 1 / d_nu), w.centre and w.cnt_ge point into the plan, the launch has no pixel blocks, and
+// the block's chain is ONE round trip (centres, the two scalars, the dense inputs) and one barrier in front of the arithmetic.
+constexpr int kPlanFreqOffset = 8;  // doubles: the per-frequency planes of a plan lie behind its scalars
+template <bool GEN, int kPreLines, bool LIST = true, bool PLANNED = false>
 __device__ __forceinline__ void prepass_block(const int bx, const int by, const int gy, int n_depth, int64_t n_nu, const double* __restrict__ nus,
                                                          const double* __restrict__ dnu_partial, int n_partial,
                                                          int64_t n_lines, const double* __restrict__ line_nus,
@@ -462,6 +467,7 @@ __device__ __forceinline__ void prepass_block(const int bx, const int by, const 
     constexpr int kItemDepths = kPreLines == 54 ? 56 : kPreDepths;
     constexpr int kPreItems = (kPreLines * kItemDepths + kPreBlock - 1) / kPreBlock;  // items per thread
     static_assert(kPreLines <= 64, "lines per pre-pass block");
+    static_assert(!(PLANNED && GEN), "the generating pre-pass takes no grid plan");
 #ifdef SDX_PRE_STATS
     unsigned long long pst[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -507,8 +513,11 @@ __device__ __forceinline__ void prepass_block(const int bx, const int by, const 
     // steps in global memory — device time stamps, scripts/r5/pre_stats.sh)
     __shared__ double s_coarse[kGridSample];
     const int n_samp = dnu_partial ? kGridSample : 128;  // (the launch that left the partial maxima also left the sample)
-    const int64_t cstride = (n_nu + n_samp - 1) / n_samp;
-    if (dnu_partial) {
+    [[maybe_unused]] const int64_t cstride = (n_nu + n_samp - 1) / n_samp;
+    if constexpr (PLANNED) {
+        // (s_coarse stays: the block that lists the wide lines keeps its masks there)
+        if (tid < kPreLines) s_c[tid] = tid < nl ? (int64_t)w.centre[SDX_LINE_OF(tid)] : 0;
+    } else if (dnu_partial) {
         for (int q = tid; q < kGridSample; q += kPreBlock) s_coarse[q] = dnu_partial[kGridSampleOffset + q];
     } else if (tid < 128) {
         const int64_t j = (int64_t)tid * cstride;
@@ -521,8 +530,13 @@ __device__ __forceinline__ void prepass_block(const int bx, const int by, const 
 
     // this thread's share of max(diff(nus)), requested now — its loads travel while the centres are searched: one of the partial
     // maxima a launch before this one left (long grids: n_partial <= kDnuPartials < the block's threads), or its part of the scan
-    const double dnu_local = dnu_partial ? (tid < n_partial ? dnu_partial[tid] : -INFINITY) : dnu_scan_local(nus, n_nu);
-    __syncthreads();
+    [[maybe_unused]] double dnu_local = 0.0, plan_dnu = 0.0, plan_rdnu = 0.0;
+    if constexpr (PLANNED) {
+        plan_dnu = dnu_partial[0], plan_rdnu = dnu_partial[1];  // (requested with the centres above and the dense inputs below)
+    } else {
+        dnu_local = dnu_partial ? (tid < n_partial ? dnu_partial[tid] : -INFINITY) : dnu_scan_local(nus, n_nu);
+        __syncthreads();
+    }
     SDX_PRE_STAMP(1);  // the grid sample and the line frequencies are in LDS
     // The block's dense inputs are requested now (kPreItems per thread): their latency hides behind the centre search below —
     // whose one global load they precede in the queue — instead of following it; requested before the barrier above they only
@@ -545,6 +559,7 @@ __device__ __forceinline__ void prepass_block(const int bx, const int by, const 
     }
     // wave ll narrows the bracket of line ll to 64 points by bisection (none needed when the grid has <= 8192 points) and resolves
     // it with ONE coalesced load and a ballot — a chain of one or two dependent global loads instead of log2(N_nu / 128)
+    if constexpr (!PLANNED)
     for (int ll = tid >> 6; ll < nl; ll += kPreBlock / 64) {
         const int lane = tid & 63;
         {
@@ -572,9 +587,15 @@ __device__ __forceinline__ void prepass_block(const int bx, const int by, const 
     // d_nu (:524-526): from the partial maxima of k_dnu_partial, or — small grids — scanned here directly
     // (its barriers also publish the centres and the cleared maxima)
     // (block-uniform: both live in scalar registers — three items per thread leave the 64-VGPR budget no room for them)
-    const double d_nu_v = block_max_to_dnu(dnu_local, s_red);
+    double d_nu_v, r_dnu_v;
+    if constexpr (PLANNED) {
+        d_nu_v = plan_dnu, r_dnu_v = plan_rdnu;
+        __syncthreads();  // the line frequencies, the centres and the cleared maxima are in LDS
+    } else {
+        d_nu_v = block_max_to_dnu(dnu_local, s_red);
+        r_dnu_v = 1.0 / d_nu_v;
+    }
     const double d_nu = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(d_nu_v)), __builtin_amdgcn_readfirstlane(__double2loint(d_nu_v)));
-    const double r_dnu_v = 1.0 / d_nu_v;
     const double r_dnu = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(r_dnu_v)), __builtin_amdgcn_readfirstlane(__double2loint(r_dnu_v)));
     SDX_PRE_STAMP(3);  // grid spacing known
 
@@ -730,7 +751,7 @@ __device__ __forceinline__ void prepass_block(const int bx, const int by, const 
             atomicMax(&w.nhw_max[SDX_LINE_OF(tid)], s_hwmax[tid]);
             atomicMax(&w.whw_max[SDX_LINE_OF(tid)], s_whwmax[tid]);
         }
-        if (by == 0) w.centre[SDX_LINE_OF(tid)] = (int)s_c[tid];
+        if constexpr (!PLANNED) if (by == 0) w.centre[SDX_LINE_OF(tid)] = (int)s_c[tid];
         if (by == 0 && w.lnu32) {
             const double lnu = s_lnu[tid];
             w.lnu32[SDX_LINE_OF(tid)] = float2v{(float)lnu, (float)(lnu - (double)(float)lnu)};
@@ -3169,18 +3190,36 @@ __global__ __launch_bounds__(kBlock) void k_total_alphas(int n_depth, int64_t nu
 // multiplications, in calc_alphas' order and rounding (:655-700), where evaluating every point from scratch
 // (total_alphas_block) costs ~400 instructions.
 constexpr int kContDepths = 8;  // at most; the host picks 1..8 depths per block so that small grids still fill the chip
+// PLANNED (sdx_grid_plan): the per-frequency part — the interpolated cross-section, nu^-3, the Rayleigh powers — was formed once by
+// k_grid_plan_build with the operations below and lies in `pf` ([5][pld], indexed by the GLOBAL frequency): the tile stages no table,
+// requests its frequency's values BEFORE the per-depth staging and its barrier instead of behind them, and keeps the bound-free edges
+// in LDS beside the coefficients.  The point loop is the same.
+template <bool PLANNED = false>
 __device__ __forceinline__ void continuum_tile_block(const int tile, const int dg, const int dgs, int n_depth, int64_t nu_begin, int64_t nu_count,
                                                      const double* __restrict__ nus, ContinuumArgs a, double* __restrict__ cont,
-                                                     int64_t cont_ld, const bool stage_table)
+                                                     int64_t cont_ld, const bool stage_table, const double* __restrict__ pf = nullptr,
+                                                     int64_t pld = 0)
 {
     extern __shared__ double s_mem[];
     const int n_levels = a.bf_n_species > 0 ? a.bf_n_levels : 0;
     double* s_coef = s_mem;                              // [kContDepths][n_levels]
     double* s_dep = s_coef + kContDepths * n_levels;     // [kContDepths][6]: file density, ff sum, Rayleigh c4 c6 c8, Thomson
-    double* s_xp = s_dep + kContDepths * 6;
+    double* s_xp = s_dep + kContDepths * 6;              // (PLANNED: the bound-free edges [n_levels] instead of the table)
     double* s_fp = s_xp + a.n_table;
     const int d0 = dg * dgs;
     const int nd = min(dgs, n_depth - d0);
+    [[maybe_unused]] double p_nu = 0.0, p_sig = 0.0, p_inv3 = 0.0, p_r4 = 0.0, p_r6 = 0.0, p_r8 = 0.0;
+    if constexpr (PLANNED) {
+        const int64_t pj = (int64_t)tile * blockDim.x + threadIdx.x;
+        if (pj < nu_count) {
+            const int64_t pi = nu_begin + pj;
+            p_nu = nus[pi];
+            if (a.table_sigma) p_sig = pf[pi];
+            if (a.bf_n_species > 0 || a.ff_n_species > 0) p_inv3 = pf[pld + pi];
+            if (a.rayleigh_enabled) p_r4 = pf[2 * pld + pi], p_r6 = pf[3 * pld + pi], p_r8 = pf[4 * pld + pi];
+        }
+    }
+    if constexpr (!PLANNED)
     if (stage_table && a.table_sigma)
         for (int k = threadIdx.x; k < a.n_table; k += blockDim.x) {
             s_xp[k] = a.table_wavelength[k];
@@ -3191,6 +3230,7 @@ __device__ __forceinline__ void continuum_tile_block(const int tile, const int d
         int sp = 0;
         while (sp + 1 < a.bf_n_species && L >= a.bf_species_offsets[sp + 1]) ++sp;
         const int zi = a.bf_species_ion_number[sp] + 1;
+        if constexpr (PLANNED) if (dd == 0) s_xp[L] = a.bf_cutoff[L];
         const double r = mul_rn((double)zi, sqrt(kRydFreq / a.bf_cutoff[L]));
         const double r2 = mul_rn(r, r);
         const double n5 = mul_rn(mul_rn(r2, r2), r);
@@ -3220,16 +3260,22 @@ __device__ __forceinline__ void continuum_tile_block(const int tile, const int d
     const int64_t j = (int64_t)tile * blockDim.x + threadIdx.x;
     if (j >= nu_count) return;
     const int64_t i = nu_begin + j;
-    const double nu = nus[i];
-    const double sig = a.table_sigma ? (stage_table ? interp1(a.lambdas[i], a.n_table, s_xp, s_fp) : interp1(a.lambdas[i], a.n_table, a.table_wavelength, a.table_sigma)) : 0.0;
-    const double inv3 = (a.bf_n_species > 0 || a.ff_n_species > 0) ? inv_nu3(nu) : 0.0;
+    double nu, sig, inv3;
     double r4 = 0, r6 = 0, r8 = 0;
+    if constexpr (PLANNED) {
+        nu = p_nu, sig = p_sig, inv3 = p_inv3, r4 = p_r4, r6 = p_r6, r8 = p_r8;
+    } else {
+    nu = nus[i];
+    sig = a.table_sigma ? (stage_table ? interp1(a.lambdas[i], a.n_table, s_xp, s_fp) : interp1(a.lambdas[i], a.n_table, a.table_wavelength, a.table_sigma)) : 0.0;
+    inv3 = (a.bf_n_species > 0 || a.ff_n_species > 0) ? inv_nu3(nu) : 0.0;
     if (a.rayleigh_enabled) {
         const double nuc = nu > 2.3e15 ? 0.0 : nu;
         const double r = nuc / mul_rn(2.0, mul_rn(kC, kRydCm));
         const double r2 = mul_rn(r, r);
         r4 = mul_rn(r2, r2), r6 = mul_rn(r4, r2), r8 = mul_rn(r4, r4);
     }
+    }
+    const double* const cut = PLANNED ? s_xp : a.bf_cutoff;  // the bound-free edges: from LDS in a planned tile
     for (int dd = 0; dd < nd; ++dd) {
         const double* dep = s_dep + dd * 6;
         const double* coef = s_coef + dd * n_levels;
@@ -3239,7 +3285,7 @@ __device__ __forceinline__ void continuum_tile_block(const int tile, const int d
         double bf = 0.0;
         for (int sp = 0; sp < a.bf_n_species; ++sp) {
             double spec = 0.0;  // alpha_spec (:214), levels in plasma order (:221-233)
-            for (int L = a.bf_species_offsets[sp]; L < a.bf_species_offsets[sp + 1]; ++L) spec = add_rn(spec, nu >= a.bf_cutoff[L] ? coef[L] : 0.0);
+            for (int L = a.bf_species_offsets[sp]; L < a.bf_species_offsets[sp + 1]; ++L) spec = add_rn(spec, nu >= cut[L] ? coef[L] : 0.0);
             bf = add_rn(bf, spec);
         }
         t = add_rn(t, a.bf_n_species > 0 ? mul_rn(bf, inv3) : 0.0);
@@ -3257,7 +3303,7 @@ __device__ __forceinline__ void continuum_tile_block(const int tile, const int d
 constexpr int kContPoints = 1;
 // Pre-pass and continuum in ONE launch: the pre-pass is a few latency-bound blocks (binary searches, a grid scan);
 // the continuum plane depends on nothing and fills the rest of the chip meanwhile.
-template <bool GEN, int LINES>
+template <bool GEN, int LINES, bool PLANNED = false>
 __global__ __launch_bounds__(kPreBlock) __attribute__((amdgpu_num_sgpr(80), amdgpu_waves_per_eu(8, 8))) void k_prepass_continuum(int n_pre_x, int n_pre_y, int cont_tiles, int n_depth, int64_t n_nu,
                                                               const double* __restrict__ nus,
                                                               const double* __restrict__ dnu_partial, int n_partial,
@@ -3271,14 +3317,17 @@ __global__ __launch_bounds__(kPreBlock) __attribute__((amdgpu_num_sgpr(80), amdg
     const int b = blockIdx.x;
     const int n_pre = n_pre_x * n_pre_y;
     if (b < n_pre) {
-        prepass_block<GEN, LINES>(b % n_pre_x, b / n_pre_x, n_pre_y, n_depth, n_nu, nus, dnu_partial, n_partial, n_lines, line_nus, doppler,
+        prepass_block<GEN, LINES, true, PLANNED>(b % n_pre_x, b / n_pre_x, n_pre_y, n_depth, n_nu, nus, dnu_partial, n_partial, n_lines, line_nus, doppler,
                            gammas, gamma_cols, alphas, w, nullptr, nullptr, n_line_blocks, lp);
     } else {
         const int c = b - n_pre;
 #ifdef SDX_PRE_STATS
         const unsigned long long st0 = wall_clock64();
 #endif
-        if (stage_table & 2)  // bit 1: depth-group blocks (the per-depth factors of a group fit LDS); bits 4..7: depths per block
+        if constexpr (PLANNED)  // (a planned launch always runs the tiled continuum)
+            continuum_tile_block<true>(c % cont_tiles, c / cont_tiles, (stage_table >> 4) & 15, n_depth, nu_begin, nu_count, nus, ca, cont_plane, cont_ld,
+                                       false, dnu_partial + kPlanFreqOffset, n_nu);
+        else if (stage_table & 2)  // bit 1: depth-group blocks (the per-depth factors of a group fit LDS); bits 4..7: depths per block
             continuum_tile_block(c % cont_tiles, c / cont_tiles, (stage_table >> 4) & 15, n_depth, nu_begin, nu_count, nus, ca, cont_plane, cont_ld,
                                  (stage_table & 1) != 0);
         else
@@ -3293,6 +3342,66 @@ __global__ __launch_bounds__(kPreBlock) __attribute__((amdgpu_num_sgpr(80), amdg
         }
 #endif
     }
+}
+
+// The grid plan (sdx_grid_plan_create / _refresh): everything the un-culled pre-pass launch forms from the grid, the line frequencies
+// and the tabulated cross-section alone, once instead of in every step — by the step's own device functions, so the values are the
+// step's.  Block 0: the grid spacing and its reciprocal (block_dnu_scan; a maximum is exact, so the partial maxima of k_dnu_partial on
+// long grids give the same number); then one thread per line: its centre index #{i : nus[i] >= line_nu} (what the sampled search of
+// prepass_block resolves to on a descending grid); one thread per entry of cnt_ge (the pixel blocks' bisection); one thread per
+// frequency: interp1, inv_nu3 and the Rayleigh powers as continuum_tile_block forms them.
+__global__ __launch_bounds__(kPreBlock) void k_grid_plan_build(int64_t n_nu, const double* __restrict__ nus, int64_t n_lines,
+                                                               const double* __restrict__ line_nus, const double* __restrict__ lambdas, int n_table,
+                                                               const double* __restrict__ table_wavelength, const double* __restrict__ table_sigma,
+                                                               double* __restrict__ pd, int* __restrict__ cnt_ge, int* __restrict__ centre,
+                                                               int n_line_blocks, int n_pix_blocks)
+{
+    const int tid = threadIdx.x;
+    int b = blockIdx.x;
+    if (b == 0) {
+        __shared__ double s_red[kPreBlock / 64];
+        const double d_nu = block_dnu_scan(nus, n_nu, s_red);
+        if (tid == 0) pd[0] = d_nu, pd[1] = 1.0 / d_nu;
+        return;
+    }
+    b -= 1;
+    if (b < n_line_blocks) {
+        const int64_t l = (int64_t)b * kPreBlock + tid;
+        if (l < n_lines) centre[l] = (int)closest_index(nus, n_nu, line_nus[l]);
+        return;
+    }
+    b -= n_line_blocks;
+    if (b < n_pix_blocks) {
+        const int64_t pidx = (int64_t)b * kPreBlock + tid;
+        if (pidx <= n_nu + 1) {
+            int64_t cnt;
+            if (pidx == 0) cnt = n_lines;
+            else if (pidx == n_nu + 1) cnt = 0;
+            else {
+                const double v = nus[pidx - 1];
+                int64_t lo = 0, hi = n_lines;  // first l with line_nus[l] > v
+                while (lo < hi) {
+                    const int64_t mid = lo + ((hi - lo) >> 1);
+                    if (line_nus[mid] <= v) lo = mid + 1; else hi = mid;
+                }
+                cnt = lo;
+            }
+            cnt_ge[pidx] = (int)cnt;
+        }
+        return;
+    }
+    b -= n_pix_blocks;
+    const int64_t i = (int64_t)b * kPreBlock + tid;
+    if (i >= n_nu) return;
+    double* const pf = pd + kPlanFreqOffset;
+    const double nu = nus[i];
+    pf[i] = table_sigma ? interp1(lambdas[i], n_table, table_wavelength, table_sigma) : 0.0;
+    pf[n_nu + i] = inv_nu3(nu);
+    const double nuc = nu > 2.3e15 ? 0.0 : nu;
+    const double r = nuc / mul_rn(2.0, mul_rn(kC, kRydCm));
+    const double r2 = mul_rn(r, r);
+    const double r4 = mul_rn(r2, r2);
+    pf[2 * n_nu + i] = r4, pf[3 * n_nu + i] = mul_rn(r4, r2), pf[4 * n_nu + i] = mul_rn(r4, r4);
 }
 
 // Culled shards of the fused step: the classification stream (HBM-bound, vector units idle) and the continuum plane (arithmetic,

@@ -100,6 +100,7 @@ struct sdx_ctx {
                                        // kernel); 2 the same, preferring k_raytrace_seg_step where the launch has its shape (as -1 does)
     int64_t far_field = -1;            // -1: by the size of the GLOBAL grid; 0 never; 1 whenever the line kernel runs 256-point tiles
     int64_t wide_list = -1;            // -1 / 1: short lists walk a compacted list of their wide lines wherever the pre-pass can build it; 0: they scan every line
+    int64_t grid_plan = -1;            // -1: a step that is given an sdx_grid_plan uses it; 0: it is ignored (A/B runs inside one library)
     int64_t narrow_records = -1;       // -1: by the density of the list; 1: the pre-pass writes narrow records; 0: the narrow role reads the caller's tables (long dense fp64 lists)
     // timing
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -133,6 +134,19 @@ struct sdx_ctx {
     bool profile = false;
     std::vector<ProfileRecord> records;
     std::vector<hipEvent_t> event_pool;
+};
+
+// What the un-culled pre-pass launch forms from the grid, the line frequencies and the tabulated cross-section alone (include/stardis_hip.h)
+struct sdx_grid_plan {
+    sdx_ctx* ctx;
+    // built from (checked against the step's arguments)
+    int64_t n_nu, n_lines;
+    const double *nus, *line_nus, *lambdas, *table_wavelength, *table_sigma;
+    int n_table;
+    // owned: doubles [0] = d_nu, [1] = 1 / d_nu, [kPlanFreqOffset + k n_nu + i] = plane k of frequency i (cross-section, nu^-3, r4, r6, r8);
+    // ints cnt_ge [n_nu + 2], then centre [n_lines]
+    double* d;
+    int* i;
 };
 
 namespace {
@@ -464,6 +478,10 @@ int sdx_set_int_option(sdx_ctx* ctx, const char* name, int64_t value)
         ctx->wide_list = value < 0 ? -1 : (value ? 1 : 0);
         return SDX_OK;
     }
+    if (std::strcmp(name, "grid_plan") == 0) {
+        ctx->grid_plan = value < 0 ? -1 : (value ? 1 : 0);
+        return SDX_OK;
+    }
     if (std::strcmp(name, "narrow_records") == 0) {
         ctx->narrow_records = value < 0 ? -1 : (value ? 1 : 0);
         return SDX_OK;
@@ -557,6 +575,77 @@ int sdx_free(sdx_ctx* ctx, void* ptr)
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipFree(ptr));
+    return SDX_OK;
+}
+
+// ---- grid plan -------------------------------------------------------------------------------------------------------------
+static int enqueue_grid_plan(sdx_grid_plan* p)
+{
+    sdx_ctx* ctx = p->ctx;
+    const int n_line_blocks = (int)((p->n_lines + kPreBlock - 1) / kPreBlock);
+    const int n_pix_blocks = (int)((p->n_nu + 2 + kPreBlock - 1) / kPreBlock);
+    const int n_freq_blocks = (int)((p->n_nu + kPreBlock - 1) / kPreBlock);
+    {
+        LaunchScope ls(ctx, "k_grid_plan_build");
+        hipLaunchKernelGGL(k_grid_plan_build, dim3((unsigned)(1 + n_line_blocks + n_pix_blocks + n_freq_blocks)), dim3(kPreBlock), 0, ctx->stream, p->n_nu,
+                           p->nus, p->n_lines, p->line_nus, p->lambdas, p->n_table, p->table_wavelength, p->table_sigma, p->d, p->i,
+                           p->i + (p->n_nu + 2), n_line_blocks, n_pix_blocks);
+    }
+    return check_launch("k_grid_plan_build");
+}
+
+int sdx_grid_plan_create(sdx_ctx* ctx, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus, const sdx_continuum* cont,
+                         sdx_grid_plan** out)
+{
+    REQUIRE(ctx && out, "grid plan: null context or result pointer");
+    *out = nullptr;
+    REQUIRE(n_nu > 0 && n_nu < (int64_t)2147483647 && nus, "grid plan: the grid must have 1 .. 2^31 - 2 points");
+    REQUIRE(n_lines >= 0 && n_lines < (int64_t)2147483647 && (n_lines == 0 || line_nus), "grid plan: bad line list");
+    const bool table = cont && cont->table_sigma;
+    REQUIRE(!table || (cont->lambdas && cont->table_wavelength && cont->n_table > 0), "grid plan: a cross-section table needs lambdas and its wavelength axis");
+    hipSetDevice(ctx->device);
+    sdx_grid_plan* p = new sdx_grid_plan{};
+    p->ctx = ctx, p->n_nu = n_nu, p->n_lines = n_lines, p->nus = nus, p->line_nus = line_nus;
+    p->lambdas = cont ? cont->lambdas : nullptr;
+    p->table_wavelength = cont ? cont->table_wavelength : nullptr;
+    p->table_sigma = cont ? cont->table_sigma : nullptr;
+    p->n_table = cont ? cont->n_table : 0;
+    p->d = (double*)sdx_malloc(ctx, ((size_t)kPlanFreqOffset + 5 * (size_t)n_nu) * sizeof(double));
+    p->i = p->d ? (int*)sdx_malloc(ctx, ((size_t)n_nu + 2 + (size_t)n_lines) * sizeof(int)) : nullptr;
+    int rc = p->i ? enqueue_grid_plan(p) : sdx_last_error_code();
+    if (rc) {
+        sdx_grid_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return SDX_OK;
+}
+
+int sdx_grid_plan_refresh(sdx_grid_plan* plan)
+{
+    REQUIRE(plan, "grid plan: null plan");
+    return enqueue_grid_plan(plan);
+}
+
+void sdx_grid_plan_destroy(sdx_grid_plan* plan)
+{
+    if (!plan) return;
+    // (blocks go back to the context's pool: every use is ordered on its stream)
+    if (plan->i) sdx_free(plan->ctx, plan->i);
+    if (plan->d) sdx_free(plan->ctx, plan->d);
+    delete plan;
+}
+
+// the step's arguments against what a plan was built from: refused before anything is enqueued
+static int check_grid_plan(const sdx_ctx* ctx, const sdx_grid_plan* p, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus,
+                           const sdx_continuum* cont)
+{
+    REQUIRE(p->ctx == ctx, "synthesize: the grid plan belongs to another context");
+    REQUIRE(p->n_nu == n_nu && p->nus == nus, "synthesize: the grid plan was built for another frequency grid (pointer or size)");
+    REQUIRE(p->n_lines == n_lines && (n_lines == 0 || p->line_nus == line_nus), "synthesize: the grid plan was built for another line list (pointer or size)");
+    REQUIRE(p->table_sigma == cont->table_sigma && (!cont->table_sigma || (p->lambdas == cont->lambdas && p->table_wavelength == cont->table_wavelength &&
+                                                                           p->n_table == cont->n_table)),
+            "synthesize: the grid plan was built for another cross-section table (pointers or size)");
     return SDX_OK;
 }
 
@@ -862,7 +951,7 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
                         const double* doppler, const double* gammas, int gamma_cols, const double* alphas, bool fill_work,
                         int32_t* lo_ref, int32_t* hi_ref, LineWork* w_out, bool count_evals = true,
                         const ContinuumJob* job = nullptr, const LineParams* gen = nullptr, int64_t nu_begin = 0, int64_t nu_count = -1,
-                        const ClassifyPhase* ph = nullptr, int wide_splits = 0)
+                        const ClassifyPhase* ph = nullptr, int wide_splits = 0, const sdx_grid_plan* plan = nullptr)
 {
     if (nu_count < 0) nu_count = n_nu;
     const LineParams lp = gen ? *gen : LineParams{};
@@ -955,7 +1044,6 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
     int* const sel = cull ? w.hcount + 4 : nullptr;
     // (grid-spacing blocks of a classification launch: four pairs of loads per thread — one trip of their loop — up to 256 blocks)
     if (cull) n_partial = (int)std::min<int64_t>(kDnuPartials, std::max<int64_t>(1, (n_nu + kBlock * 4 - 1) / (kBlock * 4)));
-    else if (!scan_in_block && (rc = launch_dnu(ctx, n_nu, nus, &n_partial))) return rc;
     // continuum blocks of the fused step: one per (frequency tile of `threads` points, group of dgs depths) when the per-depth
     // factors of a group fit LDS (always, for a handful of bound-free levels), else one per (tile, depth) evaluating every point
     // from scratch
@@ -1005,6 +1093,27 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
         }
         return SDX_OK;
     };
+    // The grid plan (sdx_grid_plan): honoured on the un-culled pre-pass of a dense list next to the tiled continuum — the launch then has
+    // no pixel blocks, its line blocks read centres and spacing from the plan and its tiles the per-frequency values
+    // (k_prepass_continuum<false, LINES, true>).  Long grids: the grid-spacing launch stays only where it computes the far ranges.
+    ContPlan planned_cp;
+    bool planned = plan && ctx->grid_plan != 0 && fill_work && !cull && !gen && job && !lo_ref && (pre_lines == 16 || pre_lines == 32);
+    if (planned) {
+        const int pix = n_pixel_blocks;
+        n_pixel_blocks = 0;  // (the tiles are sized for the launch without them)
+        if ((rc = plan_continuum(kPreBlock, &planned_cp))) return rc;
+        planned = planned_cp.tiled;
+        if (!planned) n_pixel_blocks = pix;
+        w.n_pix = n_pixel_blocks;
+    }
+    if (planned) {
+        w.cnt_ge = plan->i;
+        w.centre = plan->i + (n_nu + 2);
+        // no table in LDS: the bound-free edges instead
+        const size_t n_lev = planned_cp.ca.bf_n_species > 0 ? (size_t)job->cont->bf_n_levels : 0;
+        planned_cp.shmem = ((size_t)kContDepths * (n_lev + 6) + n_lev) * sizeof(double);
+    }
+    if (!cull && !scan_in_block && !(planned && !ctx->far_req.count) && (rc = launch_dnu(ctx, n_nu, nus, &n_partial))) return rc;
     // culled runs: classification stream, the line lists, then ONE pre-pass launch with range + gather blocks.  In the fused
     // step the continuum plane rides with the classification launch — an HBM stream that leaves the vector units idle —
     // instead of the pre-pass launch, which a shard's line blocks already fill (S-c3 / 8: 540 line + gather blocks and 590
@@ -1088,17 +1197,21 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
     if (w.n_csplit) w.ticket = (int*)((char*)ctx->small_ws + kListTicketOffset);
     if (job && !continuum_done) {
         ContPlan cp;
-        if ((rc = plan_continuum(kPreBlock, &cp))) return rc;
+        if (planned) cp = planned_cp;
+        else if ((rc = plan_continuum(kPreBlock, &cp))) return rc;
         const ContinuumArgs& ca = cp.ca;
         const int cont_tiles = cp.cont_tiles, stage_table = cp.stage_table;
         const size_t shmem = cp.shmem;
         const unsigned total_blocks = grid.x * grid.y + (unsigned)cont_tiles * cp.cont_rows;
         {
-        LaunchScope ls(ctx, "k_prepass_continuum", w.n_csplit ? "+ wide-line list" : nullptr);
-#define SDX_PRE_ARGS (int)grid.x, (int)grid.y, cont_tiles, n_depth, n_nu, nus, scan_in_block ? (const double*)nullptr : (const double*)ctx->small_ws, \
+        LaunchScope ls(ctx, "k_prepass_continuum", planned ? (w.n_csplit ? "planned + wide-line list" : "planned") : (w.n_csplit ? "+ wide-line list" : nullptr));
+#define SDX_PRE_ARGS (int)grid.x, (int)grid.y, cont_tiles, n_depth, n_nu, nus,                                                                     \
+                     planned ? (const double*)plan->d : (scan_in_block ? (const double*)nullptr : (const double*)ctx->small_ws),                \
                      n_partial, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, w, n_line_blocks, job->nu_begin, job->nu_count, ca,          \
                      job->plane, job->nu_count, lp, stage_table
-        if (gen && pre_lines == 16) hipLaunchKernelGGL((k_prepass_continuum<true, 16>), dim3(total_blocks), dim3(kPreBlock), shmem, ctx->stream, SDX_PRE_ARGS);
+        if (planned && pre_lines == 16) hipLaunchKernelGGL((k_prepass_continuum<false, 16, true>), dim3(total_blocks), dim3(kPreBlock), shmem, ctx->stream, SDX_PRE_ARGS);
+        else if (planned) hipLaunchKernelGGL((k_prepass_continuum<false, 32, true>), dim3(total_blocks), dim3(kPreBlock), shmem, ctx->stream, SDX_PRE_ARGS);
+        else if (gen && pre_lines == 16) hipLaunchKernelGGL((k_prepass_continuum<true, 16>), dim3(total_blocks), dim3(kPreBlock), shmem, ctx->stream, SDX_PRE_ARGS);
         else if (gen) hipLaunchKernelGGL((k_prepass_continuum<true, 32>), dim3(total_blocks), dim3(kPreBlock), shmem, ctx->stream, SDX_PRE_ARGS);
         else if (pre_lines == 16) hipLaunchKernelGGL((k_prepass_continuum<false, 16>), dim3(total_blocks), dim3(kPreBlock), shmem, ctx->stream, SDX_PRE_ARGS);
         else if (pre_lines == 48) hipLaunchKernelGGL((k_prepass_continuum<false, 48>), dim3(total_blocks), dim3(kPreBlock), shmem, ctx->stream, SDX_PRE_ARGS);
@@ -1192,7 +1305,8 @@ static int request_far_ranges(sdx_ctx* ctx, int64_t n_nu, int64_t nu_begin, int6
 static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
                          int64_t n_lines, const double* line_nus, const double* doppler, const double* gammas, int gamma_cols,
                          const double* alphas, const double** partial_out, int64_t* pld_out, int* n_planes_out, LineWork* w_out,
-                         bool count_evals, const ContinuumJob* job = nullptr, const LineParams* gen = nullptr, const ClassifyPhase* ph = nullptr)
+                         bool count_evals, const ContinuumJob* job = nullptr, const LineParams* gen = nullptr, const ClassifyPhase* ph = nullptr,
+                         const sdx_grid_plan* plan = nullptr)
 {
     constexpr int R = 4;       // grid points per lane of a wide-role tile (tile = 64 R points)
     constexpr int R_MIXED = 4;  // fp32 far wings (8 — twice the points per fetched record — measured slower: fewer tiles qualify as far wing)
@@ -1207,7 +1321,7 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     // (the number of line subsets depends on the global grid and the list alone; the pre-pass of a short list sorts its wide lines by it)
     const int n_split = choose_splits(n_depth, n_nu, n_lines, Rm, n_lines >= ctx->indexed_min_lines ? 4 : 2);
     rc = line_prepass(ctx, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, true, nullptr, nullptr, &w,
-                      count_evals, job, gen, nu_begin, nu_count, ph, n_split);
+                      count_evals, job, gen, nu_begin, nu_count, ph, n_split, plan);
     const FarReq far_req = ctx->far_req;
     const bool far_req_done = ctx->far_req_done || classified_far;
     ctx->far_req = FarReq{nullptr, 0, 0};
@@ -2354,6 +2468,9 @@ static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
     const int inward = opt && opt->inward_rays ? 1 : 0;
     const int n_extra = opt ? opt->n_line_planes : 0;
     REQUIRE(n_extra >= 0 && n_extra <= 2, "synthesize: n_line_planes must be 0..2");
+    // (a plan is for dense lists: the generating pre-pass ignores it, and so do culled shards and the two-collective mode)
+    const sdx_grid_plan* const plan = opt && !gen ? opt->grid_plan : nullptr;
+    if (plan && (rc = check_grid_plan(ctx, plan, n_nu, nus, n_lines, line_nus, cont))) return rc;
     double* const Fc = opt ? opt->F_nu_continuum : nullptr;
     REQUIRE(!Fc || opt->continuum_ld >= nu_count, "synthesize: continuum_ld must cover the columns");
     for (int k = 0; k < n_extra; ++k) REQUIRE(opt->line_plane[k] && opt->line_plane_ld >= nu_count, "synthesize: bad line plane");
@@ -2389,7 +2506,7 @@ static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
     if (n_lines > 0) {
         LineWork w;
         rc = line_partials(ctx, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, &part, &pld,
-                           &n_planes, &w, n_evaluations_dev != nullptr, &job, gen, second.m_max ? &second : nullptr);
+                           &n_planes, &w, n_evaluations_dev != nullptr, &job, gen, second.m_max ? &second : nullptr, plan);
         if (rc) return rc;
         if (n_evaluations_dev)
             HIP_TRY(hipMemcpyAsync(n_evaluations_dev, w.evals, sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream));

@@ -39,7 +39,7 @@ def _require_f64_buffer(name, buf, n_min):
 class SpectralSynthesizer:
     def __init__(self, nus, temperatures, dist, thetas, theta_weights, lines, continuum=None, ctx=None, shard=None,
                  flux_out=None, track_evaluations=True, keep_line=True, keep_total=True, classify_share=None, m_max=None, m_share_out=None,
-                 keep_continuum_flux=False, keep_contribution=False, instrument=None):
+                 keep_continuum_flux=False, keep_contribution=False, instrument=None, grid_plan=True):
         """nus: global grid (descending).  lines: dict(line_nus, doppler_widths, gammas, alphas) in the
         reference layout (N_l, N_d), or a stardis_amd.linelist.LineList (per-line scalars; the pre-pass generates the
         three values per (line, depth) itself).  continuum: dict as produced by synth.synth_continuum_state or None.
@@ -61,7 +61,11 @@ class SpectralSynthesizer:
         (sdx_flux_nu_to_lambda_dev) and passes it through the instrument (sdx_observe_dev: radial velocity, line-spread function,
         pixels) -> `observed` (n_pix,); with keep_continuum_flux also `observed_normalized`, the same with the continuum's F_lambda as
         reference.  Both launches are part of whatever capture() records, and a recorded step follows instrument.set_radial_velocity().
-        Needs the whole grid (a shard raises ValueError: gather first).  Off, the step is unchanged."""
+        Needs the whole grid (a shard raises ValueError: gather first).  Off, the step is unchanged.
+        grid_plan: build an sdx_grid_plan (include/stardis_hip.h) from the uploaded grid, line frequencies and cross-section table
+        and pass it with every step: what the pre-pass launch forms from them alone is then formed once, here.  The same bits; dense
+        line lists only (a line list of scalars and the two-collective mode step without one).  refresh_grid_plan() after changing the
+        uploaded values in place; False: no plan."""
         self.ctx = ctx or default_context()
         c = self.ctx
         nus = np.ascontiguousarray(nus, dtype=np.float64)
@@ -159,6 +163,17 @@ class SpectralSynthesizer:
             if m_share_out is not None:
                 _require_f64_buffer("m_share_out", m_share_out, n)
         c.call("sdx_reserve_line_workspace", self.n_depth, self.n_lines)
+        self.plan = None
+        if grid_plan and self.linelist is None and self.m_max is None and self.n_lines > 0:
+            plan = C.c_void_p()
+            c.call("sdx_grid_plan_create", self.n_nu, self.d_nus.ptr, self.n_lines, self.d_ln.ptr, C.byref(self.cont), C.byref(plan))
+            self.plan = plan
+
+    def refresh_grid_plan(self):
+        """Rebuild the plan's arrays (one launch on the context's stream) after the uploaded frequency grid, line frequencies or
+        cross-section table were overwritten in place."""
+        if self.plan is not None:
+            _lib.check(self.ctx.lib.sdx_grid_plan_refresh(self.plan))
 
     # -- set-up ---------------------------------------------------------------------------------
     def _build_continuum(self, cont, nus, t):
@@ -272,6 +287,15 @@ class SpectralSynthesizer:
                    self.d_line.ptr if self.keep_line else None, self.d_total.ptr if self.keep_total else None, self.flux_ptr, self.count,
                    ptr_of(self.d_evals) if self.count_evaluations else None)
             return
+        if self.plan is not None:  # (a description that is zero but for the plan: sdx_synthesize_dev, bit for bit)
+            opt = _lib.SynthesisOptions()
+            opt.grid_plan = self.plan
+            c.call("sdx_synthesize_opt_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, self.n_lines,
+                   self.d_ln.ptr, self.d_dw.ptr, self.d_g.ptr, self.gamma_cols, self.d_a.ptr, C.byref(self.cont), self.n_theta,
+                   self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, self.d_line.ptr if self.keep_line else None,
+                   self.d_total.ptr if self.keep_total else None, self.flux_ptr, self.count, C.byref(opt),
+                   ptr_of(self.d_evals) if self.count_evaluations else None)
+            return
         c.call("sdx_synthesize_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, self.n_lines,
                self.d_ln.ptr, self.d_dw.ptr, self.d_g.ptr, self.gamma_cols, self.d_a.ptr, C.byref(self.cont), self.n_theta,
                self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, self.d_line.ptr if self.keep_line else None,
@@ -294,6 +318,8 @@ class SpectralSynthesizer:
                    None, self.gamma_cols, None, C.byref(self.cont), self.n_theta, self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, line, total,
                    self.flux_ptr, self.count, C.byref(opt), evals)
             return
+        if self.plan is not None and self.m_max is None:
+            opt.grid_plan = self.plan
         c.call("sdx_synthesize_opt_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, self.n_lines, self.d_ln.ptr,
                self.d_dw.ptr, self.d_g.ptr, self.gamma_cols, self.d_a.ptr, C.byref(self.cont), self.n_theta, self.d_t.ptr, self.d_ray.ptr,
                self.d_w.ptr, line, total, self.flux_ptr, self.count, C.byref(opt), evals)
@@ -362,7 +388,7 @@ class SpectralSynthesizer:
                 return
             except _lib.StaleGraphError:
                 # (m_max holds the previous step's values or nothing yet: no eager phase 2 on it)
-                self.close()
+                self._destroy_graphs()
                 self.capture(eager_phase2=False)
                 self.ctx.call("sdx_graph_launch", self.graph_classify)
                 return
@@ -375,7 +401,7 @@ class SpectralSynthesizer:
             except _lib.StaleGraphError:
                 # another, larger synthesis on this context made the library reallocate its scratch: the captured pointers
                 # are dead.  Capture again (the scratch is large enough for both now) and replay.
-                self.close()
+                self._destroy_graphs()
                 self.capture()
                 self.ctx.call("sdx_graph_launch", self.graph)
         else:
@@ -390,7 +416,7 @@ class SpectralSynthesizer:
             self.ctx.call("sdx_graph_launch", self.graph_batch)
         except _lib.StaleGraphError:
             n = self.batch
-            self.close()
+            self._destroy_graphs()
             self.capture(batch=n)
             self.ctx.call("sdx_graph_launch", self.graph_batch)
         return self.batch
@@ -481,6 +507,19 @@ class SpectralSynthesizer:
         return lines + 8 * self.n_nu + 16 * self.n_depth * self.count
 
     def close(self):
+        """Destroy the recorded graphs and the grid plan (a step after close() runs without one)."""
+        self._destroy_graphs()
+        plan, self.plan = getattr(self, "plan", None), None
+        if plan is not None and self.ctx.handle:
+            self.ctx.lib.sdx_grid_plan_destroy(plan)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _destroy_graphs(self):
         if self.graph is not None:
             self.ctx.call("sdx_graph_destroy", self.graph)
             self.graph = None
