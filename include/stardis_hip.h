@@ -360,6 +360,50 @@ int sdx_contribution_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
                          const double* temperature, const double* ray_dist, const double* theta_weights,
                          const double* total_alphas, const double* source, double* C);
 
+/* ---- response functions: flux derivatives to opacity and source per depth ------------------------
+ * HOW the emergent flux changes: the exact derivative of the formal solution above, the companion of the contribution function.
+ * It is the derivative of the reference's formulas as written, branch by branch (radiation_field_solvers/base.py:22-45, :200-266).
+ * Per ray t[g] = sqrt(alpha[g]) sqrt(alpha[g+1]) ray_dist[g], I[g+1] = c[g] I[g] + e[g], I[0] = 0, T[N_d-1] = 1, T[k] = T[k+1] c[k].
+ * Derivatives of the weights, (p0, p1, p2) = d(w0, w1, w2)/dt:  t < 5e-4: (1 - t, t - t^2, t^2 - t^3);  t < 50: (E, t E, t^2 E),
+ * E = exp(-t);  otherwise 0.
+ * Inner gap g < N_d-2, t0 = t[g], t1 = t[g+1], s = t0 + t1, d10 = S[g] - S[g+1], d21 = S[g+2] - S[g+1],
+ * A = d10 t1/t0 - d21 t0/t1, B = d10/t0 + d21/t1:
+ *     e      = w0 S[g+1] + (w1 A + w2 B)/s
+ *     de/dt0 = p0 S[g+1] + (p1 A + p2 B)/s + w1 [(-d21/t1 - d10 t1/t0^2)/s - A/s^2] + w2 [(-d10/t0^2)/s - B/s^2]
+ *     de/dt1 = w1 [(d10/t0 + d21 t0/t1^2)/s - A/s^2] + w2 [(-d21/t1^2)/s - B/s^2]
+ *     e = a S[g] + q S[g+1] + r S[g+2]:   a = (w1 t1/t0 + w2/t0)/s,   r = (-w1 t0/t1 + w2/t1)/s,   q = w0 - a - r
+ * Last gap:  e = w0 S1 + w2 d10/t0^2,   de/dt0 = p0 S1 + p2 d10/t0^2 - 2 w2 d10/t0^3,   a = w2/t0^2,  q = w0 - a,  r = 0.
+ * A gap with t0 == 0 is the (1, 0) step (:203-206, :253-254): its derivatives and its three coefficients are 0 — so a row with
+ * alpha = 0 contributes 0 through t = 0.
+ * With G[j] = dI_emergent/dt[j] = T[j+1] (-p0[j] I[j] + de[j]/dt0) + T[j] de[j-1]/dt1 (the last term absent for j = 0):
+ *     R_alpha[k][nu]  = sum_theta w_theta (t[k-1] G[k-1] + t[k] G[k]) / 2                    = dF_nu[N_d-1] / d ln alpha[k]
+ *     R_source[k][nu] = sum_theta w_theta (T[k+1] a[k] + T[k] q[k-1] + T[k-1] r[k-2])        = dF_nu[N_d-1] / dS[k]
+ * (terms that do not exist are dropped; theta in two ascending halves, the lower added to the upper, as F_nu is summed).
+ * sum_k R_source[k] S[k] = F_nu[N_d-1] up to rounding, since I is linear in S.  T[j+1] I[j] is formed from a forward and a backward
+ * walk, not from differences of the emergent intensity: deep layers keep their (tiny) response instead of a cancelled one.
+ * Range: the derivative divides by t0^3 and s^2 and so leaves the normal numbers earlier than the flux does — optical depths at the
+ * ends of the double range (about 1e-100 and 1e100) are outside the contract; where the reference's own formulas divide by zero
+ * (a transparent row above an opaque one) the rows concerned are inf / NaN as the formulas give them.
+ * Arguments as for sdx_contribution_dev; R_alpha [n_depth][R_alpha_ld], R_source [n_depth][R_source_ld]; either may be NULL (not
+ * formed), not both.  Refused with SDX_ERR_ARG before anything is enqueued (also for n_nu = 0, so a caller can ask at set-up time):
+ * mixed_precision = 1, n_theta > 64, a model whose columns and stashed intensities — ((n_theta + 2) n_depth + 7 n_theta) doubles at
+ * one frequency per wave — do not fit 64 KB of LDS (117 depth points at 64 angles, 366 at 20).  Plane-parallel geometry only. */
+int sdx_response_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                     const double* temperature, const double* ray_dist, const double* theta_weights,
+                     const double* total_alphas, int64_t alpha_ld, const double* source, int64_t source_ld,
+                     double* R_alpha, int64_t R_alpha_ld, double* R_source, int64_t R_source_ld);
+/* host-buffer twin of sdx_response_dev: contiguous arrays, total_alphas / source / R_alpha / R_source [n_depth][n_nu]; source = NULL:
+ * Planck; R_alpha or R_source may be NULL. */
+int sdx_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                     const double* temperature, const double* ray_dist, const double* theta_weights,
+                     const double* total_alphas, const double* source, double* R_alpha, double* R_source);
+/* The response to a scale factor on one part of the opacity (the line opacity of one species, say: dF/d ln epsilon at fixed
+ * ionisation and continuum):
+ *     out[nu] = sum_k R_alpha[k][nu] (part[k][nu] / total[k][nu])
+ * over ascending k, every operation one correctly rounded fp64 operation; a zero in total gives what IEEE gives. */
+int sdx_response_project_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* R_alpha, int64_t R_ld, const double* part,
+                             int64_t part_ld, const double* total, int64_t total_ld, double* out);
+
 /* ---- fused synthesis for resident data (the benchmark path) ---------------------------------
  * total_alphas[d,i] = ((((file + bf) + ff) + rayleigh) + electron) + line   in calc_alphas order
  * (:655-738), then raytrace.  Any source pointer group may be NULL (skipped, contributes nothing).

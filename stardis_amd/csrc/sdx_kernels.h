@@ -4602,6 +4602,167 @@ __global__ __launch_bounds__(kBlock) void k_formation_mean(int n_depth, int64_t 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Response functions: HOW the emergent flux changes — its exact derivative with respect to the opacity and to the source function at
+// every depth point (include/stardis_hip.h, sdx_response_dev, states the formulas).  The chain of affine steps I[g+1] = c[g] I[g] + e[g]
+// differentiates into
+//     G[j] = dI_emergent / dt[j] = T[j+1] (-p0[j] I[j] + de[j]/dt0) + T[j] de[j-1]/dt1
+// which needs the intensity ENTERING gap j from below and the transmission from its upper end to the surface: two walks.  The first
+// is k_raytrace's forward recurrence (rt_coef, the kernels' own (c, e)) and stashes I[j] per (ray, gap) in the wave's LDS; the second is
+// k_contribution's walk from the surface inwards with the running product T and rt_coef_derivative per gap.  T[j+1] I[j] is formed
+// from its two factors, never as the emergent intensity minus a suffix sum (that cancels completely in deep layers).
+// Row k of either output collects from the gaps k, k-1 and k-2:
+//     R_alpha[k]  = sum_theta w_theta (t[k-1] G[k-1] + t[k] G[k]) / 2      (G[k-1] needs gap k-2)
+//     R_source[k] = sum_theta w_theta (T[k+1] a[k] + T[k] q[k-1] + T[k-1] r[k-2])
+// so the walk visits gap k-2 and then emits row k, two rows behind the gap; what does not exist (a gap below 0 or above N_d-2) is 0.
+// The layout is k_contribution's — lane <-> (frequency, angle), (S, sqrt(alpha)) pairs staged per wave from a FINISHED total_alphas
+// plane, the terms of kRtBatch rows summed over theta through LDS in the flux's order — in a workgroup of one wave (RtResponse).
+// Either output may be NULL: its terms are neither formed nor stored.
+__global__ __launch_bounds__(kRespBlock) void k_response(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
+                                                       const double* __restrict__ nus, const double* __restrict__ temps,
+                                                       const double* __restrict__ ray_dist, const double* __restrict__ wts,
+                                                       const double* __restrict__ alphas, int64_t ald, const double* __restrict__ source,
+                                                       int64_t sld, double* __restrict__ Ra, int64_t rald, double* __restrict__ Rs,
+                                                       int64_t rsld, int gpw)
+{
+    constexpr int kBatch = kRtBatch;
+    extern __shared__ double smem[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int grp = lane / G, g = lane - grp * G;
+    const int64_t i0 = ((int64_t)blockIdx.x * kRespWaves + wave) * gpw;  // first frequency of this wave
+    const int64_t i = i0 + grp;
+    const bool active = grp < gpw;
+    const int64_t ic = i < n_nu ? i : n_nu - 1;
+    const int n_gap = n_depth - 1;
+    const int col = n_depth;
+    const RtResponse lay(G, n_depth, gpw);
+    const int n_slot = lay.slots();
+    double* wbase = smem + (size_t)wave * lay.wave_doubles();
+    double2* sP = (double2*)(wbase + lay.pairs());  // (source function, sqrt(alpha)) [gpw][col]
+    double* sI = wbase + lay.stash();               // the intensity entering gap j, [n_gap][n_slot]
+    double* sA = wbase + lay.terms_alpha();         // terms of R_alpha  [kBatch][gpw][G]
+    double* sS = wbase + lay.terms_source();        // terms of R_source [kBatch][gpw][G]
+    const double nu = nus[ic];
+
+    if (active) {
+        for (int d = g; d < n_depth; d += G)
+            sP[grp * col + d] = double2{source ? source[(size_t)d * sld + ic] : planck_staged(nu, temps[d]), sqrt(alphas[(size_t)d * ald + ic])};
+    }
+    wave_sync();
+    const RtConst kc = rt_const_literals();
+
+    const int gi = (active ? grp : 0) * col;            // idle lanes shadow group 0 and never store
+    const int slot = (active ? grp : 0) * G + g;        // (their slot is group 0's: a valid read)
+    const int th = min(g, n_theta - 1);
+    const double wt = g < n_theta ? wts[th] : 0.0;
+    const double* rd = ray_dist + th;                   // rd[gap * theta_stride]
+
+    // ---- walk 1, from the bottom up: I[j], the intensity entering gap j (I[0] = 0, :134) ----
+    {
+        double2 pa = sP[gi], pb = sP[gi + 1];
+        double t0 = mul_rn(pa.y * pb.y, rd[0]);
+        double inten = 0.0;
+        for (int j = 0; j < n_gap; ++j) {
+            const bool last = j == n_gap - 1;
+            const double2 pc = sP[gi + min(j + 2, n_gap)];
+            const double t1 = last ? 0.0 : mul_rn(pb.y * pc.y, rd[(size_t)(j + 1) * theta_stride]);
+            if (active) sI[j * n_slot + slot] = inten;
+            double c, e;
+            if (last) rt_coef<true>(t0, 0.0, pa.x - pb.x, 0.0, pb.x, c, e, kc);
+            else rt_coef<false>(t0, t1, pa.x - pb.x, pc.x - pb.x, pb.x, c, e, kc);
+            inten = fma(c, inten, e);
+            pa = pb, pb = pc, t0 = t1;
+        }
+    }
+    wave_sync();
+
+    // ---- walk 2, from the surface inwards ----
+    // of the gap last visited (m + 1) and the one before (m + 2), for the row being emitted (m + 2):
+    double trans = 1.0;                  // T[m+1] for the gap m about to be visited
+    double t_up = 0.0;                   // t[m+1]
+    double x0_up = 0.0;                  // T[m+2] (-p0 I + de/dt0) of gap m+1
+    double tg_up = 0.0;                  // t[m+2] G[m+2]
+    double ta_up = 0.0, ta_up2 = 0.0;    // T[m+2] a[m+1], T[m+3] a[m+2]
+    double tq_up = 0.0;                  // T[m+2] q[m+1]
+    double2 pB = sP[gi + n_gap], pC = pB;  // the points m+1 and m+2
+    double x0 = 0.0, x1 = 0.0, ta = 0.0, tq = 0.0, tr = 0.0, tm = 0.0;
+    // one visit: gap m from the points (m, m+1, m+2) -> x0, x1, ta, tq, tr, tm; zeros below the first gap
+    auto visit = [&](int m) {
+        if (m < 0) {
+            x0 = x1 = ta = tq = tr = tm = 0.0;
+            return;
+        }
+        const double2 pA = sP[gi + m];
+        tm = mul_rn(pA.y * pB.y, rd[(size_t)m * theta_stride]);
+        const double inten = sI[m * n_slot + slot];
+        const RtStepDerivative d = m == n_gap - 1 ? rt_coef_derivative<true>(tm, 0.0, pA.x - pB.x, 0.0, pB.x)
+                                                  : rt_coef_derivative<false>(tm, t_up, pA.x - pB.x, pC.x - pB.x, pB.x);
+        x0 = trans * (d.de_dt0 - d.p0 * inten);
+        x1 = trans * d.de_dt1;
+        ta = trans * d.a, tq = trans * d.q, tr = trans * d.r;
+        trans *= d.c;  // T[m]
+        pC = pB, pB = pA;
+    };
+    visit(n_gap - 1);  // the final gap: no row is complete yet
+    t_up = tm, x0_up = x0, ta_up = ta, tq_up = tq;
+    const float inv_gpw = 1.0f / (float)gpw;
+
+    for (int ktop = n_depth - 1; ktop >= 0; ktop -= kBatch) {
+        const int nb = min(kBatch, ktop + 1);
+        for (int b = 0; b < nb; ++b) {
+            const int k = ktop - b;
+            visit(k - 2);
+            const double g_up = x0_up + x1;       // G[k-1]
+            const double tg = t_up * g_up;        // t[k-1] G[k-1]
+            if (active) {
+                if (Ra) sA[(b * gpw + grp) * G + g] = (0.5 * (tg + tg_up)) * wt;
+                if (Rs) sS[(b * gpw + grp) * G + g] = ((ta_up2 + tq_up) + tr) * wt;
+            }
+            tg_up = tg, x0_up = x0, t_up = tm;
+            ta_up2 = ta_up, ta_up = ta, tq_up = tq;
+        }
+        wave_sync();
+        {
+            // the nb rows of this batch, each output in turn: lanes <-> (row, frequency, half of the angles), each half summed in
+            // ascending theta and the lower half added to the upper one (k_raytrace's flux sum)
+            const int half = (n_theta + 1) >> 1;
+            for (int o = 0; o < 2; ++o) {
+                double* out = o ? Rs : Ra;
+                if (!out) continue;
+                const double* terms = o ? sS : sA;
+                const int64_t ld = o ? rsld : rald;
+                for (int p = lane; p < 2 * nb * gpw; p += 64) {
+                    const int h = p & 1, q = p >> 1;
+                    const int b = (int)(((float)q + 0.5f) * inv_gpw), gq = q - b * gpw;  // q / gpw without an integer division (q < 2^20: exact)
+                    const double* t = terms + (b * gpw + gq) * G + (h ? half : 0);
+                    const int cnt = h ? n_theta - half : half;
+                    double sum = 0.0;
+                    for (int j = 0; j < cnt; ++j) sum = add_rn(sum, t[j]);
+                    const double other = __shfl_xor(sum, 1);  // 2 nb gpw is even: the partner lane is in the loop too
+                    const int64_t iq = i0 + gq;
+                    if (h == 0 && iq < n_nu) out[(size_t)(ktop - b) * ld + iq] = add_rn(sum, other);
+                }
+            }
+        }
+        wave_sync();
+    }
+}
+
+// The response to a scale factor on ONE part of the opacity: out[nu] = sum_k R_alpha[k][nu] (part[k][nu] / total[k][nu]), the
+// derivative of the emergent flux with respect to the logarithm of that factor (d ln alpha[k] = part[k] / total[k] d ln factor).  One lane per
+// frequency, ascending k, every operation one correctly rounded fp64 operation; a zero in total gives what IEEE gives.
+__global__ __launch_bounds__(kBlock) void k_response_project(int n_depth, int64_t n_nu, const double* __restrict__ R, int64_t rld,
+                                                             const double* __restrict__ part, int64_t pld, const double* __restrict__ total,
+                                                             int64_t tld, double* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_nu) return;
+    double acc = 0.0;
+    for (int k = 0; k < n_depth; ++k)
+        acc = add_rn(acc, mul_rn(R[(size_t)k * rld + i], part[(size_t)k * pld + i] / total[(size_t)k * tld + i]));
+    out[i] = acc;
+}
+
+// ------------------------------------------------------------------------------------------------
 // scipy.ndimage.convolve1d(in, w) with the default mode='reflect' (d c b a | a b c d | d c b a), odd kernel, origin 0:
 // what rotation_broadening applies to the spectrum (broadening.py:869-871).  scipy's summation order is kept:
 // for a symmetric kernel  out = in[0] w[c], then pairs (in[-j] + in[+j]) w[c-j] from the OUTERMOST inwards;

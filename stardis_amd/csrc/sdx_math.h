@@ -687,6 +687,64 @@ __device__ __forceinline__ void rt_coef(double t0, double t1, double d10, double
     }
 }
 
+// The derivative twin of rt_coef: the step's c and, of e as the reference writes it (:208-249, the final gap :253-266), the partial
+// derivatives with respect to the optical depth of this gap (de_dt0) and of the next (de_dt1), p0 = dw0/dt0 (c = 1 - w0, so dc/dt0
+// = -p0), and the coefficients of e on the three source values, e = a S[g] + q S[g+1] + r S[g+2] (include/stardis_hip.h,
+// sdx_response_dev, has the formulas).  Branch by branch the reference's forms: the weights' three regimes (their derivatives
+// (1 - t, t - t^2, t^2 - t^3), (E, t E, t^2 E) and 0), t0 == 0 -> the (1, 0) step, whose derivatives and coefficients are all 0.
+// (w1 and w2 of the exponential regime are evaluated by series at small t: the same functions, without the cancellation.)
+// Every lane takes the reference's own form with IEEE divisions — what rt_coef keeps for its rare lanes is the only path here: the
+// derivative divides by t0^3 and (t0 + t1)^2, a common denominator would leave the normal numbers long before the flux's does,
+// and a zero optical depth of the NEXT gap gives the reference's inf / NaN pattern without a class test.
+constexpr double kRtSeriesBelow = 0.05;  // the exponential regime's w1 and w2 from their series below this optical depth
+struct RtStepDerivative {
+    double c, p0, de_dt0, de_dt1, a, q, r;
+};
+template <bool LAST>
+__device__ __forceinline__ RtStepDerivative rt_coef_derivative(double t0, double t1, double d10, double d21, double s1)
+{
+    if (t0 == 0.0) return {1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double w0, w1, w2, p0, p1, p2;
+    rt_weights(t0, w0, w1, w2);
+    const double tt = t0 * t0;
+    if (t0 < 5e-4) {
+        p0 = 1.0 - t0, p1 = t0 - tt, p2 = tt - tt * t0;
+    } else if (t0 < 50) {
+        p0 = exp_neg(t0), p1 = t0 * p0, p2 = tt * p0;
+        if (t0 < kRtSeriesBelow) {
+            // the SAME functions w1 = 1 - E (1 + t), w2 = 2 - E (2 + 2 t + t^2) by their power series (t^n (n-1)/n! and
+            // t^n (n-1)(n-2)/n!, alternating, through t^12: truncation below 1e-17 relative): the reference's differences lose
+            // 1e-16 / t^2 and 1e-16 / t^3 of their value, which the flux tolerates (the terms they weigh are small there) and the
+            // derivative, which divides them by t0^2 and t0^3 again, does not
+            w1 = tt * fma(t0, fma(t0, fma(t0, fma(t0, fma(t0, fma(t0, fma(t0, fma(t0, fma(t0, fma(t0, 11.0 / 479001600, -10.0 / 39916800),
+                 9.0 / 3628800), -8.0 / 362880), 7.0 / 40320), -6.0 / 5040), 5.0 / 720), -4.0 / 120), 3.0 / 24), -2.0 / 6), 0.5);
+            w2 = (tt * t0) * fma(t0, fma(t0, fma(t0, fma(t0, fma(t0, fma(t0, fma(t0, fma(t0, fma(t0, -110.0 / 479001600, 90.0 / 39916800),
+                 -72.0 / 3628800), 56.0 / 362880), -42.0 / 40320), 30.0 / 5040), -20.0 / 720), 12.0 / 120), -6.0 / 24), 2.0 / 6);
+        }
+    } else {
+        p0 = p1 = p2 = 0.0;
+    }
+    RtStepDerivative o;
+    o.c = 1.0 - w0, o.p0 = p0;
+    if constexpr (LAST) {
+        const double x = d10 / tt;  // (S[g] - S[g+1]) / t0^2
+        o.de_dt0 = (p0 * s1 + p2 * x) - 2.0 * w2 * (x / t0);
+        o.de_dt1 = 0.0;
+        o.a = w2 / tt, o.q = w0 - o.a, o.r = 0.0;
+    } else {
+        const double i0 = 1.0 / t0, i1 = 1.0 / t1, is = 1.0 / (t0 + t1);
+        const double r10 = t1 * i0, r01 = t0 * i1, x10 = d10 * i0, x21 = d21 * i1;
+        const double A = d10 * r10 - d21 * r01, B = x10 + x21;
+        const double Ais = (A * is) * is, Bis = (B * is) * is;  // A / s^2, B / s^2
+        o.de_dt0 = ((p0 * s1 + (p1 * A + p2 * B) * is) + w1 * ((-x21 - (d10 * r10) * i0) * is - Ais)) + w2 * ((-x10 * i0) * is - Bis);
+        o.de_dt1 = w1 * ((x10 + (d21 * r01) * i1) * is - Ais) + w2 * ((-x21 * i1) * is - Bis);
+        o.a = (w1 * r10 + w2 * i0) * is;
+        o.r = (w2 * i1 - w1 * r01) * is;
+        o.q = (w0 - o.a) - o.r;
+    }
+    return o;
+}
+
 // ---- the formal solution's step in fp32: the tolerance path (mixed_precision = 1), stated tolerance 1e-4 on the flux -------------
 // The same affine map I' = c I + e as rt_coef, from the EXACT weight functions (van Noort 2002 eq. 14)
 //     w0 = 1 - e^-t,   w1 = 1 - e^-t (1 + t),   w2 = 2 - e^-t (2 + 2 t + t^2)

@@ -77,6 +77,24 @@ struct RtSegments {
     __host__ __device__ constexpr bool segment_fits() const { return segment() <= LMAX; }
 };
 
+// k_response: a workgroup of ONE wave (kRespBlock lanes).  RtColumns' pairs [gpw][col] as double2; then the stash of the forward walk,
+// the intensity entering every gap per ray [col - 1][gpw * G] (a ray's slot is group * G + angle: consecutive lanes, consecutive
+// doubles); then the terms of a batch of rows for each of the two outputs, [2][kRtBatch][gpw][G].  At 56 depth points and 20 angles
+// that is 32.2 KB per wave — four waves of it do not fit the 64 KB a workgroup may ask for, hence the block size of its own.
+constexpr int kRespBlock = 64;
+constexpr int kRespWaves = kRespBlock / 64;
+struct RtResponse {
+    int gpw, col, G;
+    __host__ __device__ constexpr RtResponse(int G_, int n_depth, int gpw_) : gpw(gpw_), col(n_depth), G(G_) {}
+    __host__ __device__ constexpr int pairs() const { return 0; }
+    __host__ __device__ constexpr int slots() const { return gpw * G; }  // rays of a wave
+    __host__ __device__ constexpr int stash() const { return 2 * gpw * col; }
+    __host__ __device__ constexpr int terms_alpha() const { return stash() + (col - 1) * slots(); }
+    __host__ __device__ constexpr int terms_source() const { return terms_alpha() + kRtBatch * slots(); }
+    __host__ __device__ constexpr int wave_doubles() const { return (terms_source() + kRtBatch * slots() + 1) & ~1; }
+    __host__ __device__ constexpr size_t bytes() const { return (size_t)kRespWaves * wave_doubles() * sizeof(double); }
+};
+
 // ---- the host's choice of a launch shape ----------------------------------------------------------------------------------------
 // A model whose column alone is larger than LDS fits no layout; asked first, it also keeps every int above far from overflow.
 constexpr int kRtMaxDepth = (int)(kLdsBytes / sizeof(double));
@@ -94,6 +112,12 @@ inline int rt_fit_gpw(int G, int n_depth)
 inline unsigned rt_blocks(long long n_nu, int gpw)
 {
     return (unsigned)((n_nu + (long long)gpw * kRtWaves - 1) / ((long long)gpw * kRtWaves));
+}
+
+// Workgroups of kRespBlock threads (k_response) that cover n_nu frequencies at gpw frequencies per wave.
+inline unsigned response_blocks(long long n_nu, int gpw)
+{
+    return (unsigned)((n_nu + (long long)gpw * kRespWaves - 1) / ((long long)gpw * kRespWaves));
 }
 
 // ---- what the kernels rely on, at a few representative shapes --------------------------------------------------------------------
@@ -120,6 +144,13 @@ constexpr bool segments_ok(int NS, int LMAX, int n_theta, int n_depth)
     return s.maps() + NS * 128 <= s.ray_table() && s.ray_table() + n_theta * s.rstride() <= s.pairs() && even(s.pairs()) && s.rstride() % 2 == 1 &&
            s.rstride() >= s.n_gap && s.flux() >= s.ray_table() && s.flux_end() <= s.doubles() && s.staging_end() <= s.doubles();
 }
+constexpr bool response_ok(int G, int n_depth, int gpw)
+{
+    const RtResponse r(G, n_depth, gpw);
+    return gpw * G <= 64 && r.pairs() + 2 * gpw * n_depth <= r.stash() && r.stash() + (n_depth - 1) * r.slots() <= r.terms_alpha() &&
+           r.terms_alpha() + kRtBatch * r.slots() <= r.terms_source() && r.terms_source() + kRtBatch * r.slots() <= r.wave_doubles() &&
+           even(r.pairs()) && even(r.wave_doubles());
+}
 // 3, 7 and 20 angles (odd row counts), deep models with gpw lowered, 64 angles at the shallowest model
 static_assert(columns_ok(3, 56, 21) && columns_ok(7, 301, 3) && columns_ok(20, 302, 2) && columns_ok(5, 984, 1), "RtColumns / RtContColumns");
 static_assert(columns_ok(20, 175, 2) && columns_ok(64, 2, 1), "RtColumns / RtContColumns");
@@ -128,4 +159,7 @@ static_assert(f32_ok(20, 56) && f32_ok(7, 57) && f32_ok(64, 2) && f32_ok(1, 3), 
 static_assert(segments_ok(8, 7, 20, 56) && segments_ok(8, 7, 7, 57) && segments_ok(8, 7, 64, 2) && segments_ok(8, 7, 1, 3), "RtSegments");
 static_assert(RtSegments(8, 7, 20, 56).doubles() == RtSegments(8, 7, 20, 56).flux_end(), "20 angles: the flux terms are the larger");
 static_assert(RtSegments(8, 7, 1, 57).doubles() == RtSegments(8, 7, 1, 57).staging_end(), "one angle, 64 columns: the staging is the larger");
+// the benchmark's shape (56 depth points, 20 angles: three frequencies per wave) fits; odd ray counts, both ends of the angle range
+static_assert(response_ok(20, 56, 3) && RtResponse(20, 56, 3).bytes() <= kLdsBytes, "RtResponse: 56 depth points at 20 angles must fit");
+static_assert(response_ok(1, 2, 64) && response_ok(5, 3, 12) && response_ok(7, 9, 9) && response_ok(64, 40, 1) && response_ok(3, 117, 21), "RtResponse");
 }  // namespace rt_layout_checks

@@ -2359,6 +2359,74 @@ int sdx_contribution_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
     return io.finish();
 }
 
+// ---- response functions (k_response, k_response_project) -------------------------------------------------------------------
+// As for the contribution function, everything is checked before anything is enqueued, also for an empty grid.
+int sdx_response_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                     const double* wts, const double* alphas, int64_t ald, const double* source, int64_t source_ld, double* R_alpha,
+                     int64_t R_alpha_ld, double* R_source, int64_t R_source_ld)
+{
+    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "response: need n_depth >= 2, n_theta > 0");
+    REQUIRE(!ctx->mixed_precision, "response: no response functions with mixed_precision = 1 (they differentiate the fp64 formal solution)");
+    REQUIRE(n_theta <= 64, "response: more than 64 angles are not supported (all angles are traced in one launch)");
+    const int G = n_theta;
+    const int gpw = rt_fit_gpw<RtResponse>(G, n_depth);
+    REQUIRE(gpw > 0, "response: no response functions for models this deep (the columns and the stashed intensities do not fit LDS)");
+    if (n_nu == 0) return SDX_OK;
+    REQUIRE(R_alpha || R_source, "response: no output requested");
+    REQUIRE(nus && ray_dist && wts && alphas && ald >= n_nu, "response: null pointer or alpha_ld below n_nu");
+    REQUIRE((!R_alpha || R_alpha_ld >= n_nu) && (!R_source || R_source_ld >= n_nu), "response: leading dimension of an output below n_nu");
+    REQUIRE(source ? source_ld >= n_nu : temps != nullptr, "response: bad source plane (source_ld < n_nu), or neither a source plane nor temperatures");
+    {
+        LaunchScope ls(ctx, "k_response");
+        hipLaunchKernelGGL(k_response, dim3(response_blocks(n_nu, gpw)), dim3(kRespBlock), RtResponse(G, n_depth, gpw).bytes(), ctx->stream, n_depth, n_nu, n_theta,
+                           n_theta, G, nus, temps, ray_dist, wts, alphas, ald, source, source_ld, R_alpha, R_alpha_ld, R_source, R_source_ld, gpw);
+    }
+    return check_launch("k_response");
+}
+
+int sdx_response_project_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* R_alpha, int64_t R_ld, const double* part, int64_t part_ld,
+                             const double* total, int64_t total_ld, double* out)
+{
+    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0, "response_project: need n_depth >= 2");
+    if (n_nu == 0) return SDX_OK;
+    REQUIRE(R_alpha && part && total && out && R_ld >= n_nu && part_ld >= n_nu && total_ld >= n_nu, "response_project: null pointer or leading dimension below n_nu");
+    {
+        LaunchScope ls(ctx, "k_response_project");
+        hipLaunchKernelGGL(k_response_project, dim3(blocks1(n_nu)), dim3(kBlock), 0, ctx->stream, n_depth, n_nu, R_alpha, R_ld, part, part_ld, total, total_ld, out);
+    }
+    return check_launch("k_response_project");
+}
+
+int sdx_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                     const double* wts, const double* alphas, const double* source, double* R_alpha, double* R_source)
+{
+    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "response: need n_depth >= 2, n_theta > 0");
+    REQUIRE(n_nu == 0 || (nus && temps && ray_dist && wts && alphas), "response: null pointer");
+    REQUIRE(n_nu == 0 || R_alpha || R_source, "response: no output requested");
+    int rc;
+    if ((rc = sdx_response_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0)) || n_nu == 0)
+        return rc;  // refusals before any copy
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
+    const size_t in_bytes[] = {(size_t)n_nu * f8, (size_t)n_depth * f8, (size_t)(n_depth - 1) * n_theta * f8, (size_t)n_theta * f8, plane, source ? plane : 0};
+    size_t dev_need = 256 + 2 * HostIo::pad(plane), pin_need = 2 * HostIo::pad(plane) + 256;
+    for (size_t b : in_bytes) dev_need += HostIo::pad(b), pin_need += HostIo::pad(b);
+    HostIo io{ctx};
+    if ((rc = io.begin(dev_need, pin_need))) return rc;
+    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_s = nullptr;
+    if ((rc = io.upload(nus, in_bytes[0], (const void**)&d_nus)) || (rc = io.upload(temps, in_bytes[1], (const void**)&d_t)) ||
+        (rc = io.upload(ray_dist, in_bytes[2], (const void**)&d_rd)) || (rc = io.upload(wts, in_bytes[3], (const void**)&d_w)) ||
+        (rc = io.upload(alphas, in_bytes[4], (const void**)&d_a)) || (source && (rc = io.upload(source, in_bytes[5], (const void**)&d_s))))
+        return rc;
+    double* d_ra = R_alpha ? (double*)io.alloc(plane) : nullptr;
+    double* d_rs = R_source ? (double*)io.alloc(plane) : nullptr;
+    rc = sdx_response_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_s, n_nu, d_ra, n_nu, d_rs, n_nu);
+    if (rc) return rc;
+    if (R_alpha && (rc = io.download(R_alpha, d_ra, plane))) return rc;
+    if (R_source && (rc = io.download(R_source, d_rs, plane))) return rc;
+    return io.finish();
+}
+
 // ================================================================================================ post-processing
 int sdx_convolve1d_reflect_dev(sdx_ctx* ctx, int64_t n, const double* in, int m, const double* weights, int symmetric, double* out)
 {

@@ -39,7 +39,7 @@ def _require_f64_buffer(name, buf, n_min):
 class SpectralSynthesizer:
     def __init__(self, nus, temperatures, dist, thetas, theta_weights, lines, continuum=None, ctx=None, shard=None,
                  flux_out=None, track_evaluations=True, keep_line=True, keep_total=True, classify_share=None, m_max=None, m_share_out=None,
-                 keep_continuum_flux=False, keep_contribution=False, instrument=None, grid_plan=True):
+                 keep_continuum_flux=False, keep_contribution=False, instrument=None, grid_plan=True, keep_response=False):
         """nus: global grid (descending).  lines: dict(line_nus, doppler_widths, gammas, alphas) in the
         reference layout (N_l, N_d), or a stardis_amd.linelist.LineList (per-line scalars; the pre-pass generates the
         three values per (line, depth) itself).  continuum: dict as produced by synth.synth_continuum_state or None.
@@ -57,6 +57,11 @@ class SpectralSynthesizer:
         from the step's total_alphas (sdx_contribution_dev; implies keep_total): what the layer below row k adds to the emergent flux,
         sum_k C[k] = F_nu[-1] up to rounding (`contribution`, `formation_mean(x)`).  Plane-parallel, fp64, at most 64 angles: a context
         with mixed_precision = 1 or more angles are refused here.  Off, the step is unchanged.
+        keep_response: after the synthesis (and the contribution function), every step also forms the response functions of its own
+        columns from the step's total_alphas (sdx_response_dev; implies keep_total): `response_opacity` (N_d, count), the derivative of
+        F_nu[-1] with respect to ln alpha at every depth point, and `response_source`, its derivative with respect to the source
+        function there; `flux_derivative(alpha_part)` projects the first on one part of the opacity.  The limits of keep_contribution,
+        and a depth whose stashed intensities fit LDS (include/stardis_hip.h).  Off, the step is unchanged.
         instrument: a stardis_amd.instrument.Instrument on this context.  Every step then also forms F_lambda of F_nu[-1]
         (sdx_flux_nu_to_lambda_dev) and passes it through the instrument (sdx_observe_dev: radial velocity, line-spread function,
         pixels) -> `observed` (n_pix,); with keep_continuum_flux also `observed_normalized`, the same with the continuum's F_lambda as
@@ -126,6 +131,10 @@ class SpectralSynthesizer:
             # the library's own refusals (mixed precision, angles, depth), asked with an empty grid: nothing is enqueued
             c.call("sdx_contribution_dev", self.n_depth, 0, self.n_theta, None, None, None, None, None, 0, None, 0, None, 0)
             keep_total = True
+        self.keep_response = bool(keep_response)
+        if self.keep_response:
+            c.call("sdx_response_dev", self.n_depth, 0, self.n_theta, None, None, None, None, None, 0, None, 0, None, 0, None, 0)
+            keep_total = True
         self.d_line = c.empty((self.n_depth, self.count)) if keep_line else None
         self.d_total = c.empty((self.n_depth, self.count)) if keep_total else None
         self._flux_tensor = flux_out
@@ -134,6 +143,8 @@ class SpectralSynthesizer:
         self.keep_continuum_flux = bool(keep_continuum_flux)
         self.d_Fc = c.empty((self.n_depth, self.count)) if self.keep_continuum_flux else None
         self.d_C = c.empty((self.n_depth, self.count)) if self.keep_contribution else None
+        self.d_Ra = c.empty((self.n_depth, self.count)) if self.keep_response else None
+        self.d_Rs = c.empty((self.n_depth, self.count)) if self.keep_response else None
         self.instrument = instrument
         if instrument is not None:
             self.d_lambdas = c.upload(K.nu_to_angstrom(nus))
@@ -221,6 +232,8 @@ class SpectralSynthesizer:
     def keep_total(self, on):
         if not on and self.keep_contribution:
             raise ValueError("keep_contribution reads the step's total_alphas: keep_total stays on")
+        if not on and self.keep_response:
+            raise ValueError("keep_response reads the step's total_alphas: keep_total stays on")
         if on and self.d_total is None:
             self.d_total = self.ctx.empty((self.n_depth, self.count))
         self._keep_total = bool(on)
@@ -246,11 +259,13 @@ class SpectralSynthesizer:
 
     def enqueue(self):
         """One fused step on the context's stream: sdx_synthesize_dev (pre-pass, line gather, total, raytrace); with
-        keep_contribution, sdx_contribution_dev on the step's total_alphas behind it; with an instrument, F_lambda and sdx_observe_dev
-        behind that."""
+        keep_contribution, sdx_contribution_dev on the step's total_alphas behind it; with keep_response, sdx_response_dev behind that;
+        with an instrument, F_lambda and sdx_observe_dev last."""
         self._enqueue_synthesis()
         if self.keep_contribution:
             self._enqueue_contribution()
+        if self.keep_response:
+            self._enqueue_response()
         if self.instrument is not None:
             self._enqueue_observe()
 
@@ -267,6 +282,11 @@ class SpectralSynthesizer:
         cnt = self.count
         self.ctx.call("sdx_contribution_dev", self.n_depth, cnt, self.n_theta, self.d_nus.ptr + 8 * self.begin, self.d_t.ptr, self.d_ray.ptr,
                       self.d_w.ptr, self.d_total.ptr, cnt, None, 0, self.d_C.ptr, cnt)
+
+    def _enqueue_response(self):
+        cnt = self.count
+        self.ctx.call("sdx_response_dev", self.n_depth, cnt, self.n_theta, self.d_nus.ptr + 8 * self.begin, self.d_t.ptr, self.d_ray.ptr,
+                      self.d_w.ptr, self.d_total.ptr, cnt, None, 0, self.d_Ra.ptr, cnt, self.d_Rs.ptr, cnt)
 
     def _enqueue_synthesis(self):
         c = self.ctx
@@ -342,6 +362,8 @@ class SpectralSynthesizer:
                self.d_total.ptr, cnt, self.flux_ptr, cnt, None, 0)
         if self.keep_contribution:
             self._enqueue_contribution()
+        if self.keep_response:
+            self._enqueue_response()
         if self.instrument is not None:
             self._enqueue_observe()
 
@@ -452,6 +474,45 @@ class SpectralSynthesizer:
         if not self.keep_contribution:
             raise RuntimeError("the contribution function was not kept: construct the synthesizer with keep_contribution=True")
         return self.d_C
+
+    def _require_response(self):
+        if not self.keep_response:
+            raise RuntimeError("the response functions were not kept: construct the synthesizer with keep_response=True")
+
+    @property
+    def response_opacity(self):
+        """-> DeviceArray (N_d, count): dF_nu[-1] / d ln alpha[k] of the last step (`.numpy()` for a host array)."""
+        self._require_response()
+        return self.d_Ra
+
+    @property
+    def response_source(self):
+        """-> DeviceArray (N_d, count): dF_nu[-1] / dS[k] of the last step."""
+        self._require_response()
+        return self.d_Rs
+
+    def flux_derivative(self, alpha_part):
+        """-> DeviceArray (count,): sum_k response_opacity[k] alpha_part[k] / total_alphas[k] (sdx_response_project_dev), the derivative
+        of the emergent flux with respect to the logarithm of a scale factor on the part alpha_part (N_d, count; host array,
+        DeviceArray or CUDA tensor) of the last step's opacity — the line opacity of one species: dF/d ln(abundance) at fixed ionisation
+        and continuum."""
+        c = self.ctx
+        d_R = self.response_opacity
+        n = self.n_depth * self.count
+        if isinstance(alpha_part, _lib.DeviceArray) or hasattr(alpha_part, "data_ptr"):
+            _require_f64_buffer("alpha_part", alpha_part, n)
+            if tuple(int(v) for v in alpha_part.shape) != (self.n_depth, self.count):
+                raise ValueError(f"alpha_part must have shape {(self.n_depth, self.count)}, got {tuple(alpha_part.shape)}")
+            d_part = alpha_part
+        else:
+            host = np.ascontiguousarray(alpha_part, dtype=np.float64)
+            if host.shape != (self.n_depth, self.count):
+                raise ValueError(f"alpha_part must have shape {(self.n_depth, self.count)}, got {host.shape}")
+            d_part = c.upload(host)
+        out = c.empty((self.count,))
+        c.call("sdx_response_project_dev", self.n_depth, self.count, d_R.ptr, self.count, ptr_of(d_part), self.count, self.d_total.ptr,
+               self.count, out.ptr)
+        return out
 
     @property
     def observed(self):

@@ -382,6 +382,42 @@ def contribution_arrays(tracing_nus, temperatures, ray_distances, theta_weights,
     return d_C if device else d_C.numpy()
 
 
+def response(tracing_nus, temperatures, ray_distances, theta_weights, total_alphas, ctx=None, source=None, device=False,
+             want_opacity=True, want_source=True):
+    """Response functions of the plane-parallel formal solution (sdx_response_dev) -> (R_alpha, R_source), each (N_d, N_nu): the
+    derivative of the emergent flux F_nu[-1] with respect to ln alpha[k] and to the source function S[k] at every depth point
+    (sum_k R_source[k] S[k] = F_nu[-1] up to rounding).  Arguments as contribution_arrays; want_opacity / want_source = False: that
+    output is not formed (None in its place).  device=True: DeviceArrays instead of host arrays."""
+    nus = _host(tracing_nus).reshape(-1)
+    t = _host(temperatures).reshape(-1)
+    w = _host(theta_weights).reshape(-1)
+    rd = _host(ray_distances)
+    if t.size < 2 or rd.size != (t.size - 1) * w.size:
+        raise ValueError(f"ray_distances must have shape {(t.size - 1, w.size)}, got {rd.shape}")
+    rd = rd.reshape(t.size - 1, w.size)
+    shape = tuple(int(v) for v in (total_alphas.shape if hasattr(total_alphas, "shape") else np.shape(total_alphas)))
+    if shape != (t.size, nus.size):
+        raise ValueError(f"total_alphas must have shape {(t.size, nus.size)}, got {shape}")
+    src = None
+    if source is not None:
+        src = _host(source)
+        if src.shape != (t.size, nus.size):
+            raise ValueError(f"source function must return shape {(t.size, nus.size)}, got {src.shape}")
+    if not (want_opacity or want_source):
+        raise ValueError("response: no output requested")
+    ctx = ctx or default_context()
+    d_alpha = _dev(ctx, total_alphas)
+    d_S = ctx.upload(src) if src is not None else None
+    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd), ctx.upload(w)]
+    d_Ra = ctx.empty((t.size, nus.size)) if want_opacity else None
+    d_Rs = ctx.empty((t.size, nus.size)) if want_source else None
+    ctx.call("sdx_response_dev", t.size, nus.size, w.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, ptr_of(d_alpha), nus.size,
+             ptr_of(d_S), nus.size, ptr_of(d_Ra), nus.size, ptr_of(d_Rs), nus.size)
+    if device:
+        return d_Ra, d_Rs
+    return (d_Ra.numpy() if want_opacity else None), (d_Rs.numpy() if want_source else None)
+
+
 def formation_mean(contribution, x, ctx=None, device=False):
     """Formation mean of a per-depth quantity x (N_d) under a contribution function (N_d, N_nu; host or device array):
     (sum_{k>=1} C[k] m_k) / (sum_{k>=1} C[k]), m_k = (x[k-1] + x[k]) / 2 (sdx_formation_mean_dev) -> (N_nu,)."""

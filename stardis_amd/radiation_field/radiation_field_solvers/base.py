@@ -130,6 +130,30 @@ def contribution_function(stellar_model, stellar_radiation_field):
     )
 
 
+SPHERICAL_RESPONSE = ("the response functions are defined for plane-parallel models: the inward sweep of the spherical formal solution makes "
+                      "the intensity at the innermost point depend on every layer, and the derivative is then not that of the outward chain alone")
+
+
+def response_functions(stellar_model, stellar_radiation_field):
+    """Response functions (R_alpha, R_source), each (N_d, N_nu), of the field's formal solution: the derivative of the emergent flux
+    F_nu[-1] with respect to ln(total opacity) and to the source function at every depth point (sdx_response_dev); the sensitivity to
+    any parameter is a weighted sum of them over depth.  The same angles, weights, source function, geometry and total opacity as
+    raytrace() above; the reference has no counterpart.  A spherical model raises NotImplementedError."""
+    field = stellar_radiation_field
+    if bool(getattr(stellar_model, "spherical", False)):
+        raise NotImplementedError(SPHERICAL_RESPONSE)
+    thetas = np.asarray(field.thetas, dtype=np.float64)
+    dist = np.asarray(plain(stellar_model.geometry.dist_to_next_depth_point), dtype=np.float64)
+    ray_distances = dist.reshape(-1, 1) / np.cos(thetas)  # :302-305
+    ctx = default_context()
+    opac = field.opacities
+    alphas = opac.total_alphas_device(ctx) if hasattr(opac, "total_alphas_device") else opac.total_alphas
+    return ops.response(
+        field.frequencies, plain(stellar_model.temperatures), ray_distances, field.I_nus_weights, alphas, ctx=ctx,
+        source=_source_plane(getattr(field, "source_function", None), field.frequencies, stellar_model.temperatures),
+    )
+
+
 def formation_mean(stellar_radiation_field, x):
     """Formation mean (N_nu,) of a per-depth quantity x (N_d: geometric depth, temperature, a reference log tau) under the field's
     contribution function: (sum_{k>=1} C[k] m_k) / (sum_{k>=1} C[k]), m_k = (x[k-1] + x[k]) / 2 (sdx_formation_mean_dev).  The field must
