@@ -129,6 +129,11 @@ int sdx_synchronize(sdx_ctx* ctx);
  *       writes one byte per item (long dense fp64 lists only: lists of at least "indexed_min_lines" lines, no line-list scalars, no
  *       "mixed_precision"); -1: 0 for lists of at least four lines per grid point (1e6 lines: 1.35 GB less traffic and scratch per
  *       synthesis, the step 0.5 % faster), 1 otherwise (1.5e5 lines: the step is 0.4 % slower without the records).
+ *   "adjoint_partials" (default 2^22, at least 1): how many doubles sdx_line_adjoint_dev may spend on the partial sums of its tiled role
+ *       (windows of more than 4096 points; at least one per (line, depth) item is always there).  It bounds the number of supertiles — runs
+ *       of consecutive 1024-column tiles whose sums one wave adds — per item: min(tiles of the shard, partials / tiled items).  Scheduling
+ *       and scratch only, but not bit-neutral: another number of supertiles adds an item's tiles in another grouping (the results stay
+ *       deterministic and within the rounding of the sum).  32 MB at the default; tests lower it to run several tiles per supertile.
  *   "wide_list" (default -1): how the wide role of the line kernel finds its candidates in a SHORT list (fewer than "indexed_min_lines"
  *       lines; long lists have the list launches).  0: every tile tests every line of its line subset, 64 per round trip.  1: the last
  *       line block of the pre-pass launch to finish lists the lines that have a wide window (half-width > 64 grid points) at any depth,
@@ -403,6 +408,44 @@ int sdx_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const
  * over ascending k, every operation one correctly rounded fp64 operation; a zero in total gives what IEEE gives. */
 int sdx_response_project_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* R_alpha, int64_t R_ld, const double* part,
                              int64_t part_ld, const double* total, int64_t total_ld, double* out);
+
+/* ---- per-line flux sensitivities: the adjoint of the line-opacity sum -----------------------------
+ * WHICH lines matter: the line opacity scatters, for every line l and depth point d,
+ *     alpha_line[d][i] += alpha_ld voigt(nu_i - nu_l; doppler_ld, gamma_ld)     for i in the reference's window [lo_ld, hi_ld)
+ * (window opacities_solvers/base.py:556-575, profile voigt.py:17-86,153-155, amplitude base.py:627), and this gathers the same terms per
+ * line against a weight plane W:
+ *     out_line_depth[l][d] = sum over i in [lo_ld, hi_ld) within the shard of  W[d][i] alpha_ld voigt(nu_i - nu_l; doppler_ld, gamma_ld)
+ *     out_line[l]          = sum_d out_line_depth[l][d]
+ * the vector-Jacobian product of the line opacity with respect to the logarithm of a per-line (per-line, per-depth) strength.  With
+ * W[d][i] = w_i R_alpha[d][i] / total_alphas[d][i] (sdx_response_weight_dev) out_line[l] is d(sum_i w_i F_nu_i[N_d-1]) / d ln(strength of
+ * line l) AT FIXED WINDOWS: the derivative of a band flux, an equivalent width or any linear functional of the spectrum with respect to
+ * ln gf of every line, in one pass with the Voigt evaluations of one direct-sum line opacity.  The reference has no counterpart.
+ * Fixed windows: the reference's window has the half-width int(max(10, (gamma + doppler) alpha / d_nu * 20)), so the flux is a step
+ * function of a line's strength wherever that integer moves; this is the derivative between the steps.
+ * The windows are formed on the GLOBAL grid and are bit for bit those of sdx_line_windows_dev, clipped to the columns [nu_begin,
+ * nu_begin + nu_count); each term is what the fp64 line kernels evaluate, always by the direct sum (no far field, no fp32 path).  The list
+ * may be in any order; row k of an output belongs to line k.  Deterministic: no floating-point atomics, every sum in an order that follows
+ * from the shapes, the windows and the shard.  Shards add: the sum of the shards' outputs is the whole grid's up to rounding, and an item
+ * whose window misses the shard is exactly 0.
+ * line arrays as for sdx_line_windows_dev; weight [n_depth][weight_ld], column 0 at global index nu_begin; out_line [n_lines],
+ * out_line_depth [n_lines][n_depth]; either may be NULL, not both.  Refused with SDX_ERR_ARG before anything is enqueued (also for
+ * n_nu = 0, so a caller can ask at set-up time): a null context, mixed_precision = 1, both outputs NULL, gamma_cols neither 1 nor n_depth,
+ * a shard outside the grid.  n_lines = 0 or nu_count = 0: nothing is launched.  Only enqueues on the context's stream; its scratch is the
+ * context's and grows outside a capture only (one eager call of the same size first). */
+int sdx_line_adjoint_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
+                         int64_t n_lines, const double* line_nus, const double* doppler_widths, const double* gammas,
+                         int gamma_cols, const double* alphas, const double* weight, int64_t weight_ld,
+                         double* out_line, double* out_line_depth);
+/* host-buffer twin of sdx_line_adjoint_dev: the whole grid, contiguous arrays, weight [n_depth][n_nu]; out_line or out_line_depth may
+ * be NULL. */
+int sdx_line_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus,
+                         const double* doppler_widths, const double* gammas, int gamma_cols, const double* alphas,
+                         const double* weight, double* out_line, double* out_line_depth);
+/* The weight plane of the flux sensitivities from the response functions (sdx_response_dev):
+ *     weight[k][j] = nu_weight[j] (R_alpha[k][j] / total[k][j])          (nu_weight = NULL: 1)
+ * every operation one correctly rounded fp64 operation; a zero in total gives what IEEE gives (as sdx_response_project_dev). */
+int sdx_response_weight_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* R_alpha, int64_t R_ld,
+                            const double* total, int64_t total_ld, const double* nu_weight, double* weight, int64_t weight_ld);
 
 /* ---- fused synthesis for resident data (the benchmark path) ---------------------------------
  * total_alphas[d,i] = ((((file + bf) + ff) + rayleigh) + electron) + line   in calc_alphas order

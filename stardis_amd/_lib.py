@@ -178,6 +178,9 @@ PROTOTYPES = {
     "sdx_response_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
     "sdx_response_f64": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sdx_response_project_dev": (_int, [_vp, _int, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "sdx_line_adjoint_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp]),
+    "sdx_line_adjoint_f64": (_int, [_vp, _int, _i64, _vp, _i64, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
+    "sdx_response_weight_dev": (_int, [_vp, _int, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64]),
     "sdx_total_alphas_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, C.POINTER(Continuum), _vp, _i64, _vp, _i64]),
     "sdx_convolve1d_reflect_dev": (_int, [_vp, _i64, _vp, _int, _vp, _int, _vp]),
     "sdx_flux_nu_to_lambda_dev": (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),

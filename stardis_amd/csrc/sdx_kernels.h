@@ -4911,4 +4911,270 @@ __global__ __launch_bounds__(kBlock) void k_observe(int64_t n, const double* __r
     if (t == 0 && pj < n_pix) out[pj] = covered ? num / den : __longlong_as_double(0x7ff8000000000000LL);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The weight plane of the per-line sensitivities from the response functions: W[k][j] = w[j] R_alpha[k][j] / total[k][j] (w = nullptr: 1),
+// every operation one correctly rounded fp64 operation; a zero in total gives what IEEE gives.
+__global__ __launch_bounds__(kBlock) void k_response_weight(int n_depth, int64_t n_nu, const double* __restrict__ R, int64_t rld,
+                                                            const double* __restrict__ total, int64_t tld, const double* __restrict__ w,
+                                                            double* __restrict__ out, int64_t old)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int k = blockIdx.y;
+    if (i >= n_nu) return;
+    const double q = R[(size_t)k * rld + i] / total[(size_t)k * tld + i];
+    out[(size_t)k * old + i] = w ? mul_rn(w[i], q) : q;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The adjoint of the line-opacity sum (include/stardis_hip.h, sdx_line_adjoint_dev): per (line, depth) item
+//     s[l][d] = sum over i in [lo_ld, hi_ld) within the shard of  W[d][i] * voigt_term(nu_i - nu_l; 1 / dw_ld, y_ld, amp_ld),
+// the window from window_rule on the GLOBAL grid (d_nu by block_dnu_scan, the centre by closest_index: what sdx_line_windows_dev
+// reports), the term with narrow_params + region1_setup as the fp64 line kernels form it.  Always the direct sum, always fp64.
+//
+// Windows run from 20 points to the whole grid, so k_line_adjoint_plan (one thread per item) sorts the items by the length of the
+// clipped window first.  It appends with integer atomics, so the position of an item in a list depends on the run — which wave sums
+// an item does, the order of its sum does not:
+//   short  half-width <= kNarrowHalfWidth: k_line_adjoint<4>, sixteen items per wave, four lanes per item — the 20 points of a floor
+//          window keep all four lanes busy for five trips, where sixteen lanes per item idle 12 of 32 lane-trips and a wave per item
+//          44 of 64 lanes; the floor windows are line cores, every point the long Faddeeva regions;
+//   long   up to kAdjTiledMin points: k_line_adjoint<64>, one wave per item, lanes striding the window (coalesced loads of W and nus);
+//   tiled  longer: k_line_adjoint_tiled, the transpose of the line kernels' wide role.  A wave per item reads 16 bytes per term and is
+//          bound by the L2 (the first measurement in profiles/EXPERIMENTS.md: 5 x the direct sum at S-c3); here a wave holds a TILE of kAdjTile columns of one depth
+//          in registers (nus, W: sixteen of each per lane), walks the depth's list of tiled lines and closes every (line, tile) with a
+//          butterfly — the loads are shared by all the lines of the depth.  A wave owns a run of consecutive tiles (a supertile) and
+//          every J-th line of the list; lane 0 adds the tiles of a supertile in ascending order into the item's slot of `partial`.
+//          The number of supertiles M follows from the number of tiled items (adj_tiling: `cap` partial sums in all), i.e. from the
+//          shapes, the windows and the shard.
+// A lane adds its points in ascending order with one FMA each, a butterfly over the lanes (offsets G/2 ... 1) closes the item or the
+// tile; k_line_adjoint_gather (one wave per line, lane <-> depth) adds an item's supertiles in ascending order and the line's depths
+// by the same butterfly.  No floating-point atomics.  An item whose window misses the shard is exactly 0.
+constexpr int kAdjTileP = 16;
+constexpr int kAdjTile = 64 * kAdjTileP;
+constexpr int kAdjTiledMin = 4 * kAdjTile;
+struct AdjWork {
+    double* pd;        // [0] = d_nu, [1] = 1 / d_nu
+    int* counters;     // [0] short items, [1] long items, [2] tiled items, [4 + d] tiled items of depth d
+    int* centre;       // [N_l]
+    int* list_short;   // [items]
+    int* list_long;    // [items]
+    int* list_tiled;   // [N_d][N_l] the lines of the tiled items of each depth
+    int* tslot;        // [items] a tiled item's row of `partial` (not written for the others)
+    double* sld;       // [items] s[l][d]: the caller's out_line_depth, or scratch
+    double* partial;   // [tiled items][M]
+    int64_t cap;       // doubles in `partial`, at least the number of items
+    int n_tiles;       // tiles of the shard
+};
+struct AdjLines {
+    int n_depth, gamma_cols;
+    int64_t n_nu, nu_begin, nu_count, n_lines;
+    const double *nus, *line_nus, *doppler, *gammas, *alphas;
+};
+
+__global__ __launch_bounds__(kPreBlock) void k_line_adjoint_setup(AdjLines a, AdjWork w)
+{
+    const int tid = threadIdx.x;
+    if (blockIdx.x == 0) {
+        __shared__ double s_red[kPreBlock / 64];
+        for (int k = tid; k < 4 + a.n_depth; k += kPreBlock) w.counters[k] = 0;
+        const double d_nu = block_dnu_scan(a.nus, a.n_nu, s_red);
+        if (tid == 0) w.pd[0] = d_nu, w.pd[1] = 1.0 / d_nu;
+        return;
+    }
+    const int64_t l = (int64_t)(blockIdx.x - 1) * kPreBlock + tid;
+    if (l < a.n_lines) w.centre[l] = (int)closest_index(a.nus, a.n_nu, a.line_nus[l]);
+}
+
+// the item's window clipped to the shard -> [b, e) (e <= b: empty); returns the half-width of the rule
+__device__ __forceinline__ int64_t adjoint_window(const AdjLines& a, const AdjWork& w, double d_nu, double r_dnu, int64_t l, double dw, double g,
+                                                  double al, int64_t& b, int64_t& e)
+{
+    int lo, hi;
+    const int64_t hw = window_rule(w.centre[l], a.n_nu, d_nu, r_dnu, g, dw, al, lo, hi);
+    b = max((int64_t)lo, a.nu_begin);
+    e = min((int64_t)hi, a.nu_begin + a.nu_count);
+    return hw;
+}
+// supertiles per item and tiles per supertile, from the number of tiled items
+__device__ __forceinline__ void adj_tiling(const AdjWork& w, int& M, int& tps)
+{
+    const int64_t n_tiled = max(w.counters[2], 1);
+    const int64_t m = max((int64_t)1, min((int64_t)w.n_tiles, w.cap / n_tiled));
+    tps = (int)((w.n_tiles + m - 1) / m);
+    M = (w.n_tiles + tps - 1) / tps;  // (<= m: the rows of `partial` fit)
+}
+
+// 0: nothing to add, 1: short, 2: long, 3: tiled
+__device__ __forceinline__ int adjoint_class(int64_t hw, int64_t b, int64_t e)
+{
+    return e <= b ? 0 : (hw <= kNarrowHalfWidth ? 1 : (e - b > kAdjTiledMin ? 3 : 2));
+}
+
+// One thread per item in memory order, so that neighbours in a list are neighbours in the tables.  A tiled item takes a row of `partial`
+// (one atomic per wave) and a place in its depth's list of tiled lines (one atomic per item).  Two other plans were measured and left
+// (profiles/EXPERIMENTS.md, "Per-line flux sensitivities"): a wave per 64 lines of one depth appends with one atomic, but its lists then
+// jump through the tables and the list walks pay for it; one list of the lines tiled at ANY depth, walked at every depth, costs the
+// tiled role more than the atomics cost here.
+__global__ __launch_bounds__(kBlock) void k_line_adjoint_plan(AdjLines a, AdjWork w)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t n_items = a.n_lines * a.n_depth;
+    const int64_t item = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    int cls = 0;
+    int64_t l = 0;
+    int d = 0;
+    if (item < n_items) {
+        l = item / a.n_depth;
+        d = (int)(item - l * a.n_depth);
+        int64_t b, e;
+        const int64_t hw = adjoint_window(a, w, w.pd[0], w.pd[1], l, a.doppler[item], a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)],
+                                          a.alphas[item], b, e);
+        cls = adjoint_class(hw, b, e);
+        if (cls == 0) w.sld[item] = 0.0;
+    }
+    const unsigned long long below = (1ull << lane) - 1;
+    const unsigned long long ms = __ballot(cls == 1), ml = __ballot(cls == 2), mt = __ballot(cls == 3);
+    int bs = 0, bl = 0, bt = 0;
+    if (lane == 0) {
+        if (ms) bs = atomicAdd(&w.counters[0], __popcll(ms));
+        if (ml) bl = atomicAdd(&w.counters[1], __popcll(ml));
+        if (mt) bt = atomicAdd(&w.counters[2], __popcll(mt));
+    }
+    bs = __shfl(bs, 0), bl = __shfl(bl, 0), bt = __shfl(bt, 0);
+    if (cls == 1) w.list_short[bs + __popcll(ms & below)] = (int)item;
+    if (cls == 2) w.list_long[bl + __popcll(ml & below)] = (int)item;
+    if (cls == 3) {
+        w.tslot[item] = bt + __popcll(mt & below);
+        w.list_tiled[(size_t)d * a.n_lines + atomicAdd(&w.counters[4 + d], 1)] = (int)l;
+    }
+}
+
+template <int G>
+__global__ __launch_bounds__(kBlock) void k_line_adjoint(AdjLines a, AdjWork w, const double* __restrict__ weight, int64_t wld)
+{
+    constexpr int kPerWave = 64 / G;
+    const int lane = threadIdx.x & 63, sub = lane & (G - 1);
+    const int64_t n_waves = (int64_t)gridDim.x * (kBlock / 64);
+    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    const double d_nu = w.pd[0], r_dnu = w.pd[1];
+    const int64_t n_units = w.counters[G == 64 ? 1 : 0];
+    const int* __restrict__ list = G == 64 ? w.list_long : w.list_short;
+    for (int64_t u0 = wave * kPerWave; u0 < n_units; u0 += n_waves * kPerWave) {  // (wave-uniform: every lane reaches the butterfly)
+        const int64_t u = u0 + lane / G;
+        const bool on = u < n_units;
+        const int64_t item = on ? list[u] : 0;
+        const int64_t l = item / a.n_depth;
+        const int d = (int)(item - l * a.n_depth);
+        const double lnu = a.line_nus[l], dw = a.doppler[item], g = a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)], al = a.alphas[item];
+        int64_t b, e;
+        adjoint_window(a, w, d_nu, r_dnu, l, dw, g, al, b, e);
+        if (!on) e = b;
+        double inv, y, amp;
+        narrow_params(dw, g, al, inv, y, amp);
+        const RegionI k1 = region1_setup(y, amp);
+        const double* __restrict__ wrow = weight + (size_t)d * wld;
+        double acc = 0.0;
+        for (int64_t i = b + sub; i < e; i += G) acc = fma(wrow[i - a.nu_begin], voigt_term(a.nus[i] - lnu, inv, y, amp, k1), acc);
+#pragma unroll
+        for (int off = G >> 1; off > 0; off >>= 1) acc = add_rn(acc, __shfl_xor(acc, off));
+        if (sub == 0 && on) w.sld[item] = acc;
+    }
+}
+
+// wave = (depth d, supertile s, line subset j of J): the tiles of s in ascending order, in each the lines j, j + J, ... of depth d's list
+__global__ __launch_bounds__(kBlock) void k_line_adjoint_tiled(AdjLines a, AdjWork w, const double* __restrict__ weight, int64_t wld, int J)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wid = (int64_t)blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int per_depth = w.n_tiles * J;
+    const int d = (int)(wid / per_depth);
+    if (d >= a.n_depth || w.counters[2] == 0) return;
+    const int r = (int)(wid - (int64_t)d * per_depth), s = r / J, j = r - s * J;
+    int M, tps;
+    adj_tiling(w, M, tps);
+    const int n_d = w.counters[4 + d];
+    if (s >= M || j >= n_d) return;
+    const double d_nu = w.pd[0], r_dnu = w.pd[1];
+    const int64_t shard_end = a.nu_begin + a.nu_count;
+    const double* __restrict__ wrow = weight + (size_t)d * wld;
+    const int* __restrict__ list = w.list_tiled + (size_t)d * a.n_lines;
+    const int t_end = min((s + 1) * tps, w.n_tiles);
+    for (int t = s * tps; t < t_end; ++t) {
+        const int64_t base = a.nu_begin + (int64_t)t * kAdjTile;
+        const int64_t tile_end = min(base + kAdjTile, shard_end);
+        const double nu_first = a.nus[base], nu_last = a.nus[tile_end - 1];  // (the grid descends)
+        double nu[kAdjTileP], wt[kAdjTileP];
+#pragma unroll
+        for (int p = 0; p < kAdjTileP; ++p) {
+            const int64_t i = base + p * 64 + lane;
+            const bool ok = i < shard_end;
+            nu[p] = ok ? a.nus[i] : 0.0;
+            wt[p] = ok ? wrow[i - a.nu_begin] : 0.0;
+        }
+        for (int e = j; e < n_d; e += J) {
+            const int64_t l = list[e];
+            const size_t item = (size_t)l * a.n_depth + d;
+            const double lnu = a.line_nus[l], dw = a.doppler[item], g = a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)], al = a.alphas[item];
+            int64_t b, we;
+            adjoint_window(a, w, d_nu, r_dnu, l, dw, g, al, b, we);
+            if (we <= base || b >= tile_end) continue;  // (uniform)
+            double inv, y, amp;
+            narrow_params(dw, g, al, inv, y, amp);
+            const RegionI k1 = region1_setup(y, amp);
+            double acc = 0.0;
+            // A whole tile inside the window and in the line's far wing — the line's frequency outside the tile's, both end points
+            // with |x| + y > 15 — needs no test per point: the rounded difference and product are monotone in the frequency, so every
+            // point of the tile then passes voigt_term's own test, and region1_add is what it evaluates.
+            const bool wings = (lnu > nu_first || lnu < nu_last) && add_rn(fabs((nu_first - lnu) * inv), y) > 15.0 && add_rn(fabs((nu_last - lnu) * inv), y) > 15.0;
+            if (wings && b <= base && we >= base + kAdjTile) {
+#pragma unroll
+                for (int p = 0; p < kAdjTileP; ++p) acc = fma(wt[p], region1_add(0.0, (nu[p] - lnu) * inv, k1), acc);
+            } else {
+                const unsigned len = (unsigned)(we - b);
+                const int rel0 = (int)(base + lane - b);  // (negative: in front of the window, far above len as an unsigned number)
+#pragma unroll
+                for (int p = 0; p < kAdjTileP; ++p)
+                    if ((unsigned)(rel0 + p * 64) < len) acc = fma(wt[p], voigt_term(nu[p] - lnu, inv, y, amp, k1), acc);
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) acc = add_rn(acc, __shfl_xor(acc, off));
+            if (lane == 0) {
+                double* const slot = w.partial + (size_t)w.tslot[item] * M + s;
+                const bool first = t == max(s * tps, (int)((b - a.nu_begin) / kAdjTile));  // the supertile's first tile inside the window
+                *slot = first ? acc : add_rn(*slot, acc);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_line_adjoint_gather(AdjLines a, AdjWork w, double* __restrict__ out_line)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t l = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (l >= a.n_lines) return;
+    int M, tps;
+    adj_tiling(w, M, tps);
+    double line = 0.0;
+    for (int d0 = 0; d0 < a.n_depth; d0 += 64) {
+        const int d = d0 + lane;
+        double v = 0.0;
+        if (d < a.n_depth) {
+            const size_t item = (size_t)l * a.n_depth + d;
+            int64_t b, e;
+            const int64_t hw = adjoint_window(a, w, w.pd[0], w.pd[1], l, a.doppler[item], a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)],
+                                              a.alphas[item], b, e);
+            if (adjoint_class(hw, b, e) == 3) {
+                const int slot = w.tslot[item];
+                const int sa = (int)((b - a.nu_begin) / kAdjTile) / tps, sb = (int)((e - 1 - a.nu_begin) / kAdjTile) / tps;
+                for (int s = sa; s <= sb; ++s) v = add_rn(v, w.partial[(size_t)slot * M + s]);
+                w.sld[item] = v;
+            } else {
+                v = w.sld[item];
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) v = add_rn(v, __shfl_xor(v, off));
+        line = add_rn(line, v);
+    }
+    if (lane == 0 && out_line) out_line[l] = line;
+}
+
 }  // namespace sdx

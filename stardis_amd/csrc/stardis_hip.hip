@@ -84,6 +84,8 @@ struct sdx_ctx {
     // partial line-opacity planes [n_split + 1][n_depth][nu_count] (last plane: narrow windows)
     void* part_ws = nullptr;
     size_t part_ws_bytes = 0;
+    void* adj_ws = nullptr;  // the per-line sensitivities' centres, lists and partial sums (sdx_line_adjoint_dev)
+    size_t adj_ws_bytes = 0;
     void* far_ws = nullptr;  // far_range of the line kernels' far field: two ints per global tile
     size_t far_ws_bytes = 0;
     FarReq far_req{nullptr, 0, 0};  // the tiles whose ranges the step's next grid-spacing launch computes on the side (count = 0: none)
@@ -101,6 +103,7 @@ struct sdx_ctx {
     int64_t far_field = -1;            // -1: by the size of the GLOBAL grid; 0 never; 1 whenever the line kernel runs 256-point tiles
     int64_t wide_list = -1;            // -1 / 1: short lists walk a compacted list of their wide lines wherever the pre-pass can build it; 0: they scan every line
     int64_t grid_plan = -1;            // -1: a step that is given an sdx_grid_plan uses it; 0: it is ignored (A/B runs inside one library)
+    int64_t adjoint_partials = (int64_t)1 << 22;  // doubles of sdx_line_adjoint_dev's partial sums (at least one per item is always there): bounds the supertiles per item
     int64_t narrow_records = -1;       // -1: by the density of the list; 1: the pre-pass writes narrow records; 0: the narrow role reads the caller's tables (long dense fp64 lists)
     // timing
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -423,6 +426,7 @@ void sdx_destroy(sdx_ctx* ctx)
     if (ctx->small_ws) hipFree(ctx->small_ws);
     if (ctx->part_ws) hipFree(ctx->part_ws);
     if (ctx->far_ws) hipFree(ctx->far_ws);
+    if (ctx->adj_ws) hipFree(ctx->adj_ws);
     if (ctx->cnt_ws) hipFree(ctx->cnt_ws);
     if (ctx->io_dev) hipFree(ctx->io_dev);
     if (ctx->io_pin) hipHostFree(ctx->io_pin);
@@ -484,6 +488,10 @@ int sdx_set_int_option(sdx_ctx* ctx, const char* name, int64_t value)
     }
     if (std::strcmp(name, "narrow_records") == 0) {
         ctx->narrow_records = value < 0 ? -1 : (value ? 1 : 0);
+        return SDX_OK;
+    }
+    if (std::strcmp(name, "adjoint_partials") == 0) {
+        ctx->adjoint_partials = value < 1 ? 1 : value;
         return SDX_OK;
     }
     return fail(SDX_ERR_ARG, std::string("unknown option ") + name);
@@ -2424,6 +2432,109 @@ int sdx_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const
     if (rc) return rc;
     if (R_alpha && (rc = io.download(R_alpha, d_ra, plane))) return rc;
     if (R_source && (rc = io.download(R_source, d_rs, plane))) return rc;
+    return io.finish();
+}
+
+// ---- per-line flux sensitivities (k_response_weight, k_line_adjoint) --------------------------------------------------------
+int sdx_response_weight_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* R_alpha, int64_t R_ld, const double* total, int64_t total_ld,
+                            const double* nu_weight, double* weight, int64_t weight_ld)
+{
+    REQUIRE(ctx && n_depth >= 1 && n_depth <= 65535 && n_nu >= 0, "response_weight: need 1 <= n_depth <= 65535, n_nu >= 0");
+    if (n_nu == 0) return SDX_OK;
+    REQUIRE(R_alpha && total && weight && R_ld >= n_nu && total_ld >= n_nu && weight_ld >= n_nu, "response_weight: null pointer or leading dimension below n_nu");
+    {
+        LaunchScope ls(ctx, "k_response_weight");
+        hipLaunchKernelGGL(k_response_weight, grid2(n_nu, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, n_nu, R_alpha, R_ld, total, total_ld, nu_weight, weight,
+                           weight_ld);
+    }
+    return check_launch("k_response_weight");
+}
+
+// Everything is checked before anything is enqueued, also for an empty grid.  Six launches under the stage name k_line_adjoint: the grid
+// spacing and the centres, the item lists, the short (k_line_adjoint<4>), the long (<64>) and the tiled items, the sums per line.
+int sdx_line_adjoint_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count, int64_t n_lines,
+                         const double* line_nus, const double* doppler, const double* gammas, int gamma_cols, const double* alphas,
+                         const double* weight, int64_t weight_ld, double* out_line, double* out_line_depth)
+{
+    REQUIRE(ctx, "line_adjoint: null context");
+    REQUIRE(!ctx->mixed_precision, "line_adjoint: no per-line sensitivities with mixed_precision = 1 (the adjoint is that of the fp64 direct sum)");
+    REQUIRE(n_depth > 0 && n_depth <= 65535 && n_nu >= 0 && n_lines >= 0 && n_nu < (int64_t)2147483647, "line_adjoint: need 1 <= n_depth <= 65535, sizes >= 0 and n_nu within int32");
+    REQUIRE(n_lines * (int64_t)n_depth < (int64_t)2147483647 - 64, "line_adjoint: n_lines * n_depth must fit int32");
+    REQUIRE(out_line || out_line_depth, "line_adjoint: no output requested");
+    REQUIRE(gamma_cols == n_depth || gamma_cols == 1, "line_adjoint: gammas must have n_depth or 1 columns");
+    REQUIRE(nu_begin >= 0 && nu_count >= 0 && nu_begin + nu_count <= n_nu, "line_adjoint: frequency shard outside the grid");
+    if (n_nu == 0 || n_lines == 0 || nu_count == 0) return SDX_OK;
+    REQUIRE(nus && line_nus && doppler && gammas && alphas && weight && weight_ld >= nu_count, "line_adjoint: null pointer or weight_ld below nu_count");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int64_t n_items = n_lines * n_depth;
+    AdjWork w{};
+    w.n_tiles = (int)((nu_count + kAdjTile - 1) / kAdjTile);
+    REQUIRE((int64_t)n_depth * w.n_tiles < ((int64_t)1 << 26), "line_adjoint: n_depth * nu_count too large for one launch");
+    w.cap = std::min<int64_t>(std::max<int64_t>(ctx->adjoint_partials, n_items), n_items * w.n_tiles);
+    const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_int = pad(4 * (size_t)n_items), b_dbl = pad(8 * (size_t)n_items), b_lines = pad(4 * (size_t)n_lines), b_cnt = pad(4 * (size_t)(4 + n_depth));
+    const size_t need = 256 + b_cnt + b_lines + 4 * b_int + (out_line_depth ? 0 : b_dbl) + pad(8 * (size_t)w.cap);
+    int rc = ensure(ctx, &ctx->adj_ws, &ctx->adj_ws_bytes, need);
+    if (rc) return rc;
+    char* p = (char*)ctx->adj_ws;
+    w.pd = (double*)p, p += 256;
+    w.counters = (int*)p, p += b_cnt;
+    w.centre = (int*)p, p += b_lines;
+    w.list_short = (int*)p, p += b_int;
+    w.list_long = (int*)p, p += b_int;
+    w.list_tiled = (int*)p, p += b_int;
+    w.tslot = (int*)p, p += b_int;
+    if (out_line_depth) w.sld = out_line_depth;
+    else w.sld = (double*)p, p += b_dbl;
+    w.partial = (double*)p;
+    const AdjLines a{n_depth, gamma_cols, n_nu, nu_begin, nu_count, n_lines, nus, line_nus, doppler, gammas, alphas};
+    const int64_t cap = (int64_t)ctx->n_cu * 32;  // blocks of a list walk: the lists' lengths are known on the device only
+    const unsigned nb_short = (unsigned)std::min<int64_t>(cap, (n_items + 63) / 64);
+    const unsigned nb_long = (unsigned)std::min<int64_t>(cap, (n_items + 3) / 4);
+    // the tiled role: a wave per (depth, supertile, line subset); the line subsets fill the chip where depths x tiles alone do not
+    const int64_t dt = (int64_t)n_depth * w.n_tiles;
+    const int J = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)32, n_lines, ((int64_t)ctx->n_cu * 32 + dt - 1) / dt}));
+    {
+        LaunchScope ls(ctx, "k_line_adjoint");
+        hipLaunchKernelGGL(k_line_adjoint_setup, dim3(1 + (unsigned)((n_lines + kPreBlock - 1) / kPreBlock)), dim3(kPreBlock), 0, ctx->stream, a, w);
+        hipLaunchKernelGGL(k_line_adjoint_plan, dim3(blocks1(n_items)), dim3(kBlock), 0, ctx->stream, a, w);
+        hipLaunchKernelGGL(k_line_adjoint<4>, dim3(nb_short), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld);
+        hipLaunchKernelGGL(k_line_adjoint<64>, dim3(nb_long), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld);
+        hipLaunchKernelGGL(k_line_adjoint_tiled, dim3((unsigned)((dt * J + 3) / 4)), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld, J);
+        hipLaunchKernelGGL(k_line_adjoint_gather, dim3((unsigned)((n_lines + 3) / 4)), dim3(kBlock), 0, ctx->stream, a, w, out_line);
+    }
+    return check_launch("k_line_adjoint");
+}
+
+int sdx_line_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus, const double* doppler,
+                         const double* gammas, int gamma_cols, const double* alphas, const double* weight, double* out_line, double* out_line_depth)
+{
+    int rc;
+    if ((rc = sdx_line_adjoint_dev(ctx, n_depth, 0, nullptr, 0, 0, n_lines, nullptr, nullptr, nullptr, gamma_cols, nullptr, nullptr, 0, out_line, out_line_depth)))
+        return rc;  // refusals before any copy
+    REQUIRE(n_nu >= 0, "line_adjoint: negative n_nu");
+    if (n_nu == 0 || n_lines == 0) return SDX_OK;
+    REQUIRE(nus && line_nus && doppler && gammas && alphas && weight, "line_adjoint: null pointer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), items = (size_t)n_lines * n_depth * f8;
+    const size_t in_bytes[] = {(size_t)n_nu * f8, (size_t)n_lines * f8, items, (size_t)n_lines * gamma_cols * f8, items, (size_t)n_depth * n_nu * f8};
+    const size_t out_bytes[] = {out_line ? (size_t)n_lines * f8 : 0, out_line_depth ? items : 0};
+    size_t dev_need = 256, pin_need = 256;
+    for (size_t b : in_bytes) dev_need += HostIo::pad(b), pin_need += HostIo::pad(b);
+    for (size_t b : out_bytes) dev_need += HostIo::pad(b ? b : 8), pin_need += HostIo::pad(b);
+    HostIo io{ctx};
+    if ((rc = io.begin(dev_need, pin_need))) return rc;
+    const void* d_in[6];
+    const void* src[] = {nus, line_nus, doppler, gammas, alphas, weight};
+    for (int k = 0; k < 6; ++k)
+        if ((rc = io.upload(src[k], in_bytes[k], &d_in[k]))) return rc;
+    double* d_line = out_line ? (double*)io.alloc(out_bytes[0]) : nullptr;
+    double* d_ld = out_line_depth ? (double*)io.alloc(out_bytes[1]) : nullptr;
+    rc = sdx_line_adjoint_dev(ctx, n_depth, n_nu, (const double*)d_in[0], 0, n_nu, n_lines, (const double*)d_in[1], (const double*)d_in[2], (const double*)d_in[3],
+                              gamma_cols, (const double*)d_in[4], (const double*)d_in[5], n_nu, d_line, d_ld);
+    if (rc) return rc;
+    if (out_line && (rc = io.download(out_line, d_line, out_bytes[0]))) return rc;
+    if (out_line_depth && (rc = io.download(out_line_depth, d_ld, out_bytes[1]))) return rc;
     return io.finish();
 }
 

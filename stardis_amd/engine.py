@@ -77,6 +77,8 @@ class SpectralSynthesizer:
         if np.any(np.diff(nus) >= 0):
             raise ValueError("tracing frequencies must be strictly descending (stardis/base.py:34)")
         self.linelist = None
+        self._line_order = None  # the stable sort applied to an unsorted dense list (line_sensitivities answers in the caller's order)
+        self._line_tables = None  # (line_nus, doppler_widths, gammas, alphas) in the caller's order, on first use by line_sensitivities
         if isinstance(lines, (LL.LineList, LL.DeviceLineList)):
             (lines.host if isinstance(lines, LL.DeviceLineList) else lines).check_sorted()
             self.linelist = lines if isinstance(lines, LL.DeviceLineList) else lines.upload(c)
@@ -116,6 +118,7 @@ class SpectralSynthesizer:
                 # reference's calc_alan_entries accepts any order, so an unsorted list is sorted (stably) here, not refused
                 order = np.argsort(ln, kind="stable")
                 ln, g, dw, al = (np.ascontiguousarray(a[order]) for a in (ln, g, dw, al))
+                self._line_order = order
             self.gamma_cols = g.shape[1]
             self.d_ln = c.upload(ln)
             self.d_dw = c.upload(dw)
@@ -512,6 +515,72 @@ class SpectralSynthesizer:
         out = c.empty((self.count,))
         c.call("sdx_response_project_dev", self.n_depth, self.count, d_R.ptr, self.count, ptr_of(d_part), self.count, self.d_total.ptr,
                self.count, out.ptr)
+        return out
+
+    def _tables_in_caller_order(self):
+        """The four line tables as sdx_line_adjoint_dev reads them, row k = line k of the caller's list: the uploaded dense tables
+        themselves (a sorted list: nothing is copied, values overwritten in place are seen), or — built on first use and kept, a
+        SNAPSHOT of the values at that moment, as large as the tables — those of a line list of scalars, materialised by
+        sdx_line_params_dev (the values its pre-pass generates), or the rows of an unsorted dense list, which the constructor sorted,
+        put back in the caller's order.  `forget_line_tables()` drops the snapshot; the next call builds it again."""
+        if self.linelist is None and self._line_order is None:
+            return self.d_ln.ptr, self.d_dw, self.d_g, self.d_a
+        if self._line_tables is None:
+            c = self.ctx
+            if self.linelist is not None:
+                ll = self.linelist
+                d_a, d_g, d_dw = c.empty((self.n_lines, self.n_depth)), c.empty((self.n_lines, self.gamma_cols)), c.empty((self.n_lines, self.n_depth))
+                c.call("sdx_line_params_dev", self.n_depth, ll.byref(), d_a.ptr, d_g.ptr, d_dw.ptr)
+                self._line_tables = (ll.nu_ptr, d_dw, d_g, d_a)
+            else:
+                back = np.argsort(self._line_order, kind="stable")
+                d_ln, d_dw, d_g, d_a = (c.upload(a.numpy()[back]) for a in (self.d_ln, self.d_dw, self.d_g, self.d_a))
+                self._line_tables = (d_ln.ptr, d_dw, d_g, d_a, d_ln)  # (the last entry keeps the frequencies alive)
+        return self._line_tables[:4]
+
+    def forget_line_tables(self):
+        """Drop the snapshot of the line tables that line_sensitivities keeps for a line list of scalars or an unsorted dense list
+        (after the uploaded tables or the list's device arrays were overwritten in place)."""
+        self._line_tables = None
+
+    def line_sensitivities(self, weights=None, per_depth=False):
+        """-> DeviceArray (n_lines,), or (n_lines, N_d) with per_depth=True: for every line l of the list, in the order the caller passed
+        the lines, the derivative of  sum_i weights[i] F_nu_i[-1]  over this synthesizer's columns with respect to ln(strength of line
+        l) — ln gf, or the abundance of a species that has this line alone — at FIXED WINDOWS, from the last step: the weight plane
+        weights[i] response_opacity[k, i] / total_alphas[k, i] (sdx_response_weight_dev) gathered against every line's own terms
+        (sdx_line_adjoint_dev: one pass with the Voigt evaluations of one direct-sum line opacity, whatever the number of lines).
+        per_depth=True keeps the depth points apart: the response to the line's strength at depth point d alone.
+        weights: None (1 for every column) or one value per column of this synthesizer (host array, DeviceArray or CUDA tensor).  The
+        equivalent width W = sum_i (1 - F_i / F_c) dlambda_i of a feature on a flat continuum F_c has weights[i] = -dlambda_i / F_c on
+        its columns and 0 elsewhere:  dW / d ln gf_l = line_sensitivities(weights)[l].
+        Fixed windows: the reference's window half-width is int(max(10, (gamma + doppler) alpha / d_nu * 20)), the flux is a step
+        function of a line's strength wherever that integer moves, and this is the derivative between the steps.
+        The line tables: a sorted dense list is read where the step reads it; a line list of scalars and an unsorted dense list are
+        read from a snapshot taken at the first call (forget_line_tables() after changing the uploaded values in place).
+        A frequency shard returns the partial sum over its own columns: shards add.  Needs keep_response=True; on demand, like
+        flux_derivative — a synthesizer that never asks runs the launches it always ran."""
+        self._require_response()
+        c = self.ctx
+        d_w = None
+        if weights is not None:
+            if isinstance(weights, _lib.DeviceArray) or hasattr(weights, "data_ptr"):
+                _require_f64_buffer("weights", weights, 0)
+                size = int(np.prod(tuple(weights.shape), dtype=np.int64))
+                d_w = weights
+            else:
+                host = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+                size = host.size
+            if size != self.count:
+                raise ValueError(f"weights must hold one value per column of the synthesizer ({self.count}), got {size}")
+            if d_w is None:
+                d_w = c.upload(host)
+        cnt = self.count
+        d_W = c.empty((self.n_depth, cnt))
+        c.call("sdx_response_weight_dev", self.n_depth, cnt, self.d_Ra.ptr, cnt, self.d_total.ptr, cnt, ptr_of(d_w), d_W.ptr, cnt)
+        ln_ptr, d_dw, d_g, d_a = self._tables_in_caller_order()
+        out = c.empty((self.n_lines, self.n_depth) if per_depth else (self.n_lines,))
+        c.call("sdx_line_adjoint_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, cnt, self.n_lines, ln_ptr, d_dw.ptr, d_g.ptr,
+               self.gamma_cols, d_a.ptr, d_W.ptr, cnt, None if per_depth else out.ptr, out.ptr if per_depth else None)
         return out
 
     @property

@@ -127,6 +127,31 @@ def line_windows(no_of_depth_points, tracing_nus_values, line_nus, doppler_width
     return lo.numpy(), hi.numpy()
 
 
+def line_adjoint(no_of_depth_points, tracing_nus_values, line_nus, doppler_widths, gammas, alphas_array, weight, per_depth=False,
+                 ctx=None, device=False, shard=None):
+    """The adjoint of calc_alan_entries (sdx_line_adjoint_dev): per line l, sum_d sum_i weight[d, i] * (the term line l adds to
+    alpha_line_at_nu[d, i]) over the reference's window of (l, d) -> (n_lines,), or with per_depth=True the sums per depth point
+    (n_lines, N_d).  Row k belongs to line k of the caller's list whatever its order.  weight: (N_d, N_nu) host array, DeviceArray or
+    CUDA tensor; shard = (begin, count): only these columns of the global grid are summed and weight is (N_d, count) — shards add.
+    device=True: a DeviceArray instead of a host array."""
+    nus = _host(tracing_nus_values).reshape(-1)
+    ln, dw, g, al = _line_inputs(no_of_depth_points, line_nus, doppler_widths, gammas, alphas_array, sort=False)
+    nd = int(no_of_depth_points)
+    begin, count = (0, nus.size) if shard is None else (int(v) for v in shard)
+    if begin < 0 or count < 0 or begin + count > nus.size:
+        raise ValueError(f"shard {(begin, count)} lies outside the grid of {nus.size} frequencies")
+    shape = tuple(int(v) for v in (weight.shape if hasattr(weight, "shape") else np.shape(weight)))
+    if shape != (nd, count):
+        raise ValueError(f"weight must have shape {(nd, count)}, got {shape}")
+    ctx = ctx or default_context()
+    d_w = _dev(ctx, weight)
+    d = [ctx.upload(x) for x in (nus, ln, dw, g, al)]
+    out = ctx.empty((ln.size, nd) if per_depth else (ln.size,))
+    ctx.call("sdx_line_adjoint_dev", nd, nus.size, d[0].ptr, begin, count, ln.size, d[1].ptr, d[2].ptr, d[3].ptr, g.shape[1], d[4].ptr,
+             ptr_of(d_w), count, None if per_depth else out.ptr, out.ptr if per_depth else None)
+    return out if device else out.numpy()
+
+
 # ------------------------------------------------------------------------------------------------ broadening
 def _flags(linear_stark, quadratic_stark, van_der_waals, radiation):
     return (1 if linear_stark else 0) | (2 if quadratic_stark else 0) | (4 if van_der_waals else 0) | (8 if radiation else 0)
