@@ -26,17 +26,8 @@
  *       SDX_WIDE_BLOCKS   target number of wide-role workgroups -> line subsets per (depth, tile)
  *       SDX_RT_SEG        0 / 1 / 2: never / always the segmented formal-solution kernel, 2 preferring its step-shaped form (the option
  *                         "segmented_raytrace" wins; same values)
- *       SDX_FAR           0 / 1: never / always the far field of the line kernels (the option "far_field" wins); SDX_FAR_RF 1 / 2 / 4
- *                         (tiles per unit of the far role / 4: scheduling only); SDX_FAR_LAUNCH: the far field as a launch of its own
- *                         (k_line_far, 8 line subsets — SDX_FAR_SPLIT 1 .. 8 — instead of the line kernel's: the order of a sum)
- *       SDX_R_MIXED       4 / 8: grid points per lane of a mixed-precision tile
- *       SDX_NO_NARROW_SUBSETS, SDX_NARROW_SUBSETS_DENSITY (halves of a line per grid point from which the narrow role of a long
- *                         list splits its candidate lines over the four waves of a workgroup; default 8 = four lines per point)
- *     scheduling and layout only (same bits): SDX_NARROW_F (1, 2, 4 frequencies per narrow wave), SDX_NARROW_ORDER,
- *       SDX_WIDE_GROUP, SDX_CONT_DGS, SDX_CLS_BLOCKS (workgroups of a shard's classification stream), SDX_NO_CULL,
- *       SDX_NO_CONT_RIDE, SDX_NO_PREPASS_TICKET, SDX_NO_PREPASS_FRONT, SDX_PRE_LINES (32 / 48 lines per pre-pass block of a
- *       culled shard), SDX_NO_HSCAN, SDX_NO_PINNED_STAGING,
- *       SDX_SPLIT_LAUNCHES (the two roles of the line kernel as two launches, for profiling)
+ *     scheduling only (same bits): SDX_NO_PINNED_STAGING,
+ *       SDX_SPLIT_LAUNCHES (the line kernel as two launches, for profiling: the far and the wide role, then the narrow role)
  *     test hook: SDX_GROUP_LOOPBACK (see sdx_group_create).
  */
 #ifndef STARDIS_HIP_H

@@ -347,7 +347,7 @@ struct LineWork {
     // (compact_wide_lines); `ticket` then counts the finished line blocks and is left at zero.  0: the wide role scans the whole list.
     // (no pointers of their own: a larger LineWork made every launch that takes one slower, list or no list)
     int n_csplit;
-    // far field (k_line_far): the (line, depth, tile) triples that far_eligible() accepts are left to k_line_far — the wide role
+    // far field (line_far_body): the (line, depth, tile) triples that far_eligible() accepts are left to the far role — the wide role
     // skips them — and their sum reaches the grid through the tile's 16 Chebyshev nodes (a third plane).
     // far_range[2 T], [2 T + 1] (k_far_ranges): a line is far from global tile T when its centre index is < the first or > the second
     // (0 and INT_MAX: tile T has no far field); nullptr = no far field in this launch
@@ -898,14 +898,13 @@ __global__ __launch_bounds__(kPreBlock) __attribute__((amdgpu_num_sgpr(80), amdg
 // half-width h = (nu_a - nu_b) / 2, a (line, depth) item is FAR when the tile lies wholly inside its window, clear of its core
 // range (every point in region I) and |c - nu_l| >= 6 h (decided in index space, k_far_ranges).  The sum of the far items of a tile is then evaluated at the tile's
 // kFarNodes = 16 Chebyshev nodes c + h cos(pi (j + 1/2) / 16) — the same rational, the same records, fp64 — and carried to
-// the tile's grid points by the degree-15 interpolant (k_line_far): 16 evaluations per (item, tile) instead of 64 R.  The
+// the tile's grid points by the degree-15 interpolant (line_far_body): 16 evaluations per (item, tile) instead of 64 R.  The
 // interpolation error of a function analytic inside the ellipse through a pole at distance D from the centre is
 // ~ (D/h + sqrt((D/h)^2 - 1))^-16 <= 11.9^-16 = 6e-18 of the item's value; measured against 80-bit sums of the far items of
 // S-c3's tiles: 2.5e-14 relative, rounding included (the direct fp64 sum: 4e-15).  The opacity tolerance is 1e-12, the flux's 1e-10.
 // Which triples are far is a property of the grid and the list (global tiles), not of the shard or the launch geometry; both
 // kernels decide it with THIS function on the same operands, so every triple is evaluated exactly once.
-constexpr int kFarSplit = 8;  // line subsets (waves per workgroup) of k_line_far — the far field as a launch of its own (experiment knob SDX_FAR_LAUNCH, split-launch profiling): a shard's launch is a few hundred workgroups, its waves' chains are its duration
-constexpr int kFarWaveLdsDoubles = 64 * 6 + 64;  // per wave of k_line_far: 64 staged records, the queue's line indices and tile masks
+constexpr int kFarWaveLdsDoubles = 64 * 6 + 64;  // per wave of the far role: 64 staged records, the queue's line indices and tile masks
 // The distance test in INDEX space, once per tile (one thread each): a line's centre index is cidx = #{i : nus[i] >= nu_l}
 // (closest_index, the reference's own quantity), so with ihi = #{i : nus[i] >= c + 6 h} and ilo = #{i : nus[i] >= c - 6 h}
 //   cidx < ihi  =>  nu_l > nus[ihi - 1] >= c + 6 h        cidx > ilo  =>  nu_l <= nus[ilo] < c - 6 h
@@ -1043,7 +1042,7 @@ __device__ __forceinline__ void line_wide_walk(const int tile_idx, const int spl
             dnu[r] = nu - nu_base;
         }
     }
-    // far field: the triples k_line_far evaluates at the tile's Chebyshev nodes are no hits here (full tiles only)
+    // far field: the triples the far role evaluates at the tile's Chebyshev nodes are no hits here (full tiles only)
     // (FAR is a kernel of its own: the candidate's centre index is one more register carried through the walk, and the walk's
     // budget has none to spare — with the test in the one kernel its sums spilled to scratch)
     static_assert(!FAR || kTile == kFarTile, "the far field lives on 256-point tiles");
@@ -1192,7 +1191,7 @@ __device__ __forceinline__ void line_wide_walk(const int tile_idx, const int spl
                 for (int u = 0; u < kScanBatch; ++u) {
                     const int line = bl[u];
                     const WideScan sc = bs[u];
-                    const bool far = far_eligible(sc, it0, it1, far_ihi, far_ilo);  // k_line_far's
+                    const bool far = far_eligible(sc, it0, it1, far_ihi, far_ilo);  // the far role's
                     const bool hit = (line >= 0) & (sc.lo < it1) & (sc.hi > it0) & !far;
                     const int clo = sc.clo < 0 ? -sc.clo - 1 : sc.clo;
                     const bool fast = hit & (sc.lo <= it0) & (sc.hi >= it1) & ((it1 <= clo) | (it0 >= sc.chi));
@@ -1225,7 +1224,7 @@ __device__ __forceinline__ void line_wide_walk(const int tile_idx, const int spl
             const int line = line_next;
             const WideScan sc = sc_next;
             fetch(q + q_step, line_next, sc_next);
-            const bool far = FAR && far_eligible(sc, it0, it1, far_ihi, far_ilo);  // k_line_far's
+            const bool far = FAR && far_eligible(sc, it0, it1, far_ihi, far_ilo);  // the far role's
             const bool hit = (line >= 0) & (sc.lo < it1) & (sc.hi > it0) & !far;  // narrow / empty items have lo = hi = 0
             const int clo = sc.clo < 0 ? -sc.clo - 1 : sc.clo;                // sign: core delegated to the narrow role
             const bool fast = hit & (sc.lo <= it0) & (sc.hi >= it1) & ((it1 <= clo) | (it0 >= sc.chi));
@@ -2166,7 +2165,7 @@ __device__ __forceinline__ void line_narrow_subsets32(const int64_t i0, const in
 
 // FAR FIELD of the line opacity (far_eligible above): the third plane of the line kernels.  One workgroup owns (depth d, a unit of
 // 4 RF consecutive global tiles, RF = 1 or 2); lane <-> (tile 4 r + lane / 16 of the unit, Chebyshev node lane % 16), r < RF.  Its
-// n_split waves (the line kernel's, whose far role this is; kFarSplit in a launch of its own) go through the candidate lists exactly
+// n_split waves (the line kernel's, whose far role this is) go through the candidate lists exactly
 // as the wide role does (hlist, then the wlist range around the unit; chunk q of 64 candidates belongs to wave q mod n_split): each
 // lane tests ONE candidate against the unit (its whole span first, the single tiles where that does not settle it) and keeps the
 // mask of the tiles it is far from; the hits are queued in LDS in list order and evaluated 64 at a time — records fetched by the
@@ -2473,23 +2472,13 @@ __device__ __forceinline__ void line_far_body(const int block, const int units, 
     }
 }
 
-// (the far field as a launch of its own: experiment knob SDX_FAR_LAUNCH; by default its workgroups are the FIRST of the line kernel's grid)
-template <int R, int RF>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_line_far(int units, int n_split, int n_depth, int64_t n_nu,
-                                                                                           const double* __restrict__ nus, int64_t nu_begin, int64_t nu_count,
-                                                                                           int64_t n_lines, LineWork w, double* __restrict__ plane, int64_t pld)
-{
-    extern __shared__ double s_far[];
-    line_far_body<R, RF>(blockIdx.x, units, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, w, plane, pld, s_far);
-}
-
 // The kernels with a far field (FAR) take the launch as LineWords instead: the four words of the host's choices, which every wave
 // decodes itself with the divisions that LineGeom (sdx_line_geom.h) spares the others.  Every FAR instantiation fills its 80 registers
 // (six waves per SIMD) without a spill only as long as its entry code is what it was: with LineGeom's decode in the place of the one below
 // each of them spilled a vector register, and a kernel that spills is not run.  Their grids are large
 // and their waves long: ~600 scalar instructions at the head of a narrow wave are below one per cent of such a launch.
-// roles: bit 0 wide, bit 1 narrow; bits 2-3 narrow order; bits 4-7 wide group; bits 8-11 F; bits 16-17 RF of the merged far role (0: the
-// far field has a launch of its own).  Same grid, same units in the same order as line_launch_make's.
+// roles: bit 0 wide, bit 1 narrow; bits 2-3 narrow order; bits 4-7 wide group; bits 8-11 F; bits 16-17 RF of the far role in front of the grid (0: none —
+// the second of two split launches).  Same grid, same units in the same order as line_launch_make's.
 struct LineWords {
     int n_wide, tiles, roles, far_units;
 };
@@ -2518,14 +2507,17 @@ __device__ __forceinline__ void line_all_body(LineLaunchArg<FAR> g, int n_split,
     // fp64 by the queued walk like the fp64 kernels'; the narrow role and the formal solution stay the mode's fp32)
     constexpr bool WM = MIXED && !FAR;  // the wide role's arithmetic
     if constexpr (FAR) {
-        // far role (roles bits 16-17: RF, 0 = the far field has a launch of its own): the FIRST workgroups of the grid — their waves are
+        // far role (roles bits 16-17: RF, 0 = no far workgroups in this launch): the FIRST workgroups of the grid — their waves are
         // the longest chains of the launch (a unit walks every huge line of the list) — n_depth x far_units of them
         const int rf = (g.roles >> 16) & 3;
         if (rf) {
             const int n_far = n_depth * g.far_units;
             if (b < n_far) {
                 double* const far_plane = planes + (size_t)2 * n_depth * pld;
-                // (fp32-mixed mode: the node sums in packed fp32 — units of 8 tiles, the default; the experiment knob's units of 4 stay fp64)
+                // (fp32-mixed mode: the node sums in packed fp32 — units of 8 tiles)
+                // (the host sets rf to 0 or 2.  Deleting the <R, 1> branch was tried: 1460 - 1660 fewer instructions in each of the six
+                // kernels, but more spilled SGPRs in three to five of them however the test is written — k_line_all<4, true, true>
+                // 58 -> 63 or 67, k_line_listed<4, false, true> 76 -> 80 or 94: it stays, profiles/EXPERIMENTS.md)
                 if (rf == 2) line_far_body<R, 2, MIXED>(b, g.far_units, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, w, far_plane, pld, s_wide);
                 else line_far_body<R, 1>(b, g.far_units, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, w, far_plane, pld, s_wide);
                 return;
@@ -2552,6 +2544,8 @@ __device__ __forceinline__ void line_all_body(LineLaunchArg<FAR> g, int n_split,
         if constexpr (FAR) {
             if (!(g.roles & 1)) return;
             const int tiles = g.tiles;
+            // (the host sets the wide group to 0.  Deleting the other decode here and in wide_unit was tried: spilled SGPRs 46 -> 49 in
+            // k_line_all<4, true, false>, 76 -> 81 in k_line_listed<4, false, true>, 76 -> 86 in k_line_all_mixed<4, true, true>: it stays)
             const int wg = (g.roles >> 4) & 15;  // 0: one contiguous eighth of the tiles per XCD; g > 0: groups of g tiles going round the XCDs
             if (wg == 0) {
                 const int p = b % tiles;
@@ -2602,7 +2596,9 @@ __device__ __forceinline__ void line_all_body(LineLaunchArg<FAR> g, int n_split,
             const int64_t n_narrow = n_grp * ((n_depth + 63) / 64);
             const int64_t n_nb = SUBSETS ? n_narrow : (n_narrow + n_split - 1) / n_split;
             const int64_t p = b - g.n_wide, j = p >> 3;
-            const int order = (g.roles >> 2) & 3;  // analysis knob (SDX_NARROW_ORDER): 0 grouped (default), 1 plain, 2 one block per XCD
+            // (the host sets the order to 0.  Deleting orders 1 and 2 here and in narrow_unit was tried: spilled SGPRs 51 -> 60 in
+            // k_line_all<4, false, false>, 46 -> 56 in k_line_all<4, true, false>, 80 -> 90 in k_line_listed<4, false, false>: they stay)
+            const int order = (g.roles >> 2) & 3;  // 0 grouped (what the host sets), 1 plain, 2 one block per XCD
             int64_t wg = ((j / kNarrowGroup) * 8 + (p & 7)) * kNarrowGroup + j % kNarrowGroup;
             if (order == 1) wg = p;
             if (order == 2) wg = (p & 7) * ((n_nb + 7) / 8) + j;
@@ -2681,8 +2677,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FAR ? SDX_F
 {
     line_all_body<R, false, SUBSETS, FAR, true>(g, n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, planes, pld);
 }
-// the mixed-precision variant: 512-point tiles; the register budget is capped at 128 (4 waves per SIMD) — what exceeds it
-// sits in the rarely taken fp64 general path
+// the mixed-precision variant (R = 4: 256-point tiles, six waves per SIMD; with 512-point tiles, measured slower and no longer
+// instantiated, the budget was capped at 128 registers — what exceeds it sits in the rarely taken fp64 general path)
 template <int R, bool SUBSETS = false, bool FAR = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(R == 4 ? 6 : 4, 8))) void k_line_all_mixed(
     LineLaunchArg<FAR> g, int n_split, int n_depth, int64_t n_nu, const double* __restrict__ nus, int64_t nu_begin, int64_t nu_count,

@@ -1,5 +1,5 @@
 // sdx_line_geom.h — how a block index of the line launch (k_line_all, k_line_listed, k_line_all_mixed; sdx_kernels.h) becomes a unit
-// of work, stated ONCE: the host (stardis_hip.hip) forms a LineGeom per launch from the shard, the grid and its knobs, the kernels
+// of work, stated ONCE: the host (stardis_hip.hip) forms a LineGeom per launch from the shard and the grid, the kernels
 // decode their block index with the two functions below, and the host-side test runs the same functions over every block index.
 // (The kernels with a far field keep decoding the host's four words themselves — LineWords, sdx_kernels.h, which says why — on the same
 // grid: line_launch_make counts their far workgroups, which come first.)
@@ -71,7 +71,9 @@ struct LineLaunch {
 };
 
 // nu_begin, nu_count: the shard's columns; tile_points: 64 R; narrow_f in {1, 2, 4}; subsets: the narrow role of the SUBSETS kernels;
-// wide_group 0 .. 15; order 0 grouped, 1 plain, 2 one block per XCD; far_blocks: the workgroups of a merged far role, first in the grid.
+// wide_group 0 .. 15; order 0 grouped, 1 plain, 2 one block per XCD (the host passes 0 for both: the other orders were measured and lost,
+// and stay only because the kernels spill more scalar registers without them — LineWords, sdx_kernels.h); far_blocks: the workgroups of
+// the far role, first in the grid.
 SDX_GEOM_FN LineLaunch line_launch_make(int64_t nu_begin, int64_t nu_count, int n_depth, int n_split, int tile_points, int narrow_f, bool subsets,
                                         int wide_group, int order, int mask, int64_t far_blocks)
 {

@@ -978,13 +978,11 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
     // lines ~22 000 lines, 690 blocks of 32 on the chip's 512 slots of 1024 threads — a whole second round of the block's chain of
     // round trips for a third of a round's work.  48 lines per block (three items per thread, registers only) are 470 blocks:
     // ONE round, a chain one item longer.
-    static const bool no_cull_early = knob("SDX_NO_CULL") != nullptr;
-    static const int pre_lines_env = knob("SDX_PRE_LINES") ? std::atoi(knob("SDX_PRE_LINES")) : 0;  // experiment knob: 32, 48 or 64 on culled shards
-    const bool will_cull = fill_work && !no_cull_early && n_lines >= ctx->indexed_min_lines && !count_evals && !gen && n_nu > 16384 && nu_count < n_nu;
+    const bool will_cull = fill_work && n_lines >= ctx->indexed_min_lines && !count_evals && !gen && n_nu > 16384 && nu_count < n_nu;
     // (lists long enough for the counter-driven launch keep 32: its looping kernel has no registers to spare for a third item)
     // (54 when the model has at most 56 depth points — every MARCS model — and three items per thread still cover the block)
     if (will_cull && !lo_ref && (n_lines + 31) / 32 < ctx->prepass_ticket_min_blocks)
-        pre_lines = (pre_lines_env == 32 || pre_lines_env == 48) ? pre_lines_env : (n_depth <= 56 ? 54 : 48);
+        pre_lines = n_depth <= 56 ? 54 : 48;
     const int n_line_blocks = (int)((n_lines + pre_lines - 1) / pre_lines);
     int n_pixel_blocks = 0;
     if (fill_work) {
@@ -1025,8 +1023,7 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
     // 2.13 GB of traffic counted, 1.31 GB of it these records), line kernel 5.93 -> 6.07 ms (ten more instructions per evaluated line), step
     // 7.27 -> 7.24 ms and 1.35 GB less scratch; 1.5e5 lines: pre-pass 165 -> 149 us, line kernel 1.218 -> 1.241 ms, the step 7 us SLOWER —
     // hence the density in the rule.
-    static const int narrow_records_env = knob("SDX_NARROW_RECORDS") ? std::atoi(knob("SDX_NARROW_RECORDS")) : -1;  // A/B knob; the option "narrow_records" wins
-    const int narrow_records = ctx->narrow_records >= 0 ? (int)ctx->narrow_records : narrow_records_env;
+    const int narrow_records = (int)ctx->narrow_records;  // (context option: -1 by this rule, 0 never, 1 always)
     const bool very_dense = 2 * n_lines >= 8 * n_nu;
     if (fill_work && !gen && !ctx->mixed_precision && n_lines >= ctx->indexed_min_lines && (narrow_records == 0 || (very_dense && narrow_records != 1))) {
         w.narrow_raw = gamma_cols > 1 ? n_depth : 1;
@@ -1044,8 +1041,7 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
     // that can reach any column (-> hlist), the full pre-pass then runs on the lines centred near the shard plus those.
     // Everything is decided on the device (no host round trip, graph-capturable); which lines a shard prepares does not
     // change what it computes for them.
-    static const bool no_cull = knob("SDX_NO_CULL") != nullptr;
-    const bool cull = fill_work && !no_cull && n_lines >= ctx->indexed_min_lines && !count_evals && !gen && !scan_in_block && nu_count < n_nu;
+    const bool cull = fill_work && n_lines >= ctx->indexed_min_lines && !count_evals && !gen && !scan_in_block && nu_count < n_nu;
     REQUIRE(!ph || cull, "two-collective mode is for frequency shards of long dense line lists (>= indexed_min_lines lines, a grid of more than "
                          "16384 points, nu_count < n_nu, no evaluation count)");
     // the grid-spacing reduction: a launch of its own, or — culled runs — the first blocks of the classification launch
@@ -1078,8 +1074,7 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
         const size_t tile_shmem = ((size_t)kContDepths * (n_lev + 6) + (p->stage_table ? 2 * (size_t)ca.n_table : 0)) * sizeof(double);
         p->cont_rows = (unsigned)n_depth;
         p->tiled = false;
-        static const int cont_dgs_env = knob("SDX_CONT_DGS") ? std::atoi(knob("SDX_CONT_DGS")) : -1;  // experiment knob: 0 = per-point blocks
-        if (tile_shmem <= 48 * 1024 && cont_dgs_env != 0) {
+        if (tile_shmem <= 48 * 1024) {
             // depths per block: as many as leave ~2 x 1024 threads of such blocks per CU (one depth per block on small grids)
             int dgs = (int)std::max<int64_t>(1, std::min<int64_t>(kContDepths, ((int64_t)p->cont_tiles * threads / kPreBlock * n_depth) / (2 * (int64_t)ctx->n_cu)));
             if (threads == kPreBlock) {
@@ -1093,7 +1088,6 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
             // riding with the classification stream (256-thread blocks) the chip is full anyway: as many depths per block as
             // there are — the per-frequency work (table search, nu^-3, Rayleigh powers) is then shared by eight points
             if (threads == kBlock) dgs = kContDepths;
-            if (cont_dgs_env > 0) dgs = std::min(cont_dgs_env, kContDepths);
             p->stage_table |= 2 | (dgs << 4);
             p->shmem = tile_shmem;
             p->cont_rows = (unsigned)((n_depth + dgs - 1) / dgs);
@@ -1130,21 +1124,18 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
     if (cull) {
         w.sel = sel;
         // classification blocks: contiguous runs of lines, a few blocks per CU (256 threads: 4 waves x 4 lines x 3 arrays in flight)
-        static const int cls_blocks_env = knob("SDX_CLS_BLOCKS") ? std::atoi(knob("SDX_CLS_BLOCKS")) : 0;  // experiment knob
         const int64_t cls_begin = ph && ph->phase == 1 ? ph->begin : 0, cls_end = ph && ph->phase == 1 ? ph->begin + ph->count : n_lines;
         // (a SHARE of the list — two-collective mode — is a few microseconds of streaming: sixteen lines per block, one trip of each
         // wave's loop, so that the launch is as long as one round trip and not as a chain of nine; the whole list is a stream that
         // wants its bytes in flight, not short chains)
         const bool share = ph && ph->phase == 1;
         const int64_t cls_per_block = share ? 16 : 64;
-        const unsigned n_cls = cls_blocks_env > 0 ? (unsigned)cls_blocks_env
-                                                  : (unsigned)std::max<int64_t>(1, std::min<int64_t>((cls_end - cls_begin + cls_per_block - 1) / cls_per_block, (int64_t)8 * ctx->n_cu));
+        const unsigned n_cls = (unsigned)std::max<int64_t>(1, std::min<int64_t>((cls_end - cls_begin + cls_per_block - 1) / cls_per_block, (int64_t)8 * ctx->n_cu));
         // the per-line maxima: doubles behind the integer lists of cnt_ws (8-byte aligned), or the caller's array (two-collective mode)
         double* const m_max = ph ? ph->m_max : (double*)(((uintptr_t)(w.hcount + 16 + 3 * ((size_t)n_lines / 1024 + 8)) + 7) & ~(uintptr_t)7);
         double* const dnu_ws = (double*)ctx->small_ws;
         ContPlan cp;
-        static const bool no_ride = knob("SDX_NO_CONT_RIDE") != nullptr;  // A/B knob
-        if (job && !no_ride) {
+        if (job) {
             if ((rc = plan_continuum(kBlock, &cp))) return rc;
             continuum_done = cp.tiled;
         }
@@ -1184,11 +1175,10 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
             c.generation = ctx->ws_generation;
             return check_launch("k_classify");
         }
-        static const bool no_ticket = knob("SDX_NO_PREPASS_TICKET") != nullptr;  // A/B knob: one block per candidate instead
         // the pre-pass launch that follows draws its items from a counter (k_line_prepass_ticket); the list launch zeroes it
         // (worth it where the candidates are many: at 1e6 lines 57 000 of 62 000 candidate blocks are empty and the launch takes 245
         // instead of 292 us on an eighth of the grid; at 1.5e5 lines 9 500 candidates cost less than the counter's round trips)
-        const bool ticket = !no_ticket && !(job && !continuum_done) && !gen && !lo_ref && n_line_blocks >= ctx->prepass_ticket_min_blocks;
+        const bool ticket = !(job && !continuum_done) && !gen && !lo_ref && n_line_blocks >= ctx->prepass_ticket_min_blocks;
         if (ticket) w.ticket = (int*)((char*)ctx->small_ws + 2064);
         {
             LaunchScope ls(ctx, "k_hlist");
@@ -1197,8 +1187,7 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
             launch_line_lists(ctx, n_lines, w, pre_lines, &cs);
         }
         w.gather = n_line_blocks;  // worst case: every line listed; blocks beyond the lists' end return at once
-        static const bool no_front = knob("SDX_NO_PREPASS_FRONT") != nullptr;  // A/B knob
-        w.front = no_front ? 0 : 1;
+        w.front = 1;
     }
     const dim3 grid((unsigned)(n_line_blocks + n_pixel_blocks + w.gather), (unsigned)((n_depth + kPreDepths - 1) / kPreDepths));
     const bool ticket_launch = w.ticket != nullptr;  // (the counter-driven launch of a culled shard)
@@ -1282,17 +1271,14 @@ static int choose_splits(int n_depth, int64_t n_nu_global, int64_t n_lines, int 
     return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, chunks), 8));  // the subsets are the waves of one workgroup
 }
 
-// FAR FIELD (k_line_far): a third plane.  Like every choice that moves a rounding it is made from the GLOBAL grid — grids of at
+// FAR FIELD (line_far_body, the far role of the line kernels): a third plane.  Like every choice that moves a rounding it is made from the GLOBAL grid — grids of at
 // least kFarMinPoints frequencies (below that a launch of the line kernel is bound by latency, not by its evaluations) — or set
 // explicitly (context option "far_field").
 constexpr int64_t kFarMinPoints = 32768;
 static_assert(kFarMinPoints == 32768, "sdx_far_field_rule reports this constant");
 static bool far_field_on(const sdx_ctx* ctx, int64_t n_nu_global)
 {
-    static const int far_env = knob("SDX_FAR") ? std::atoi(knob("SDX_FAR")) : -1;  // A/B knob: 0 never, 1 whenever possible
-    static const int r_mixed_env = knob("SDX_R_MIXED") ? std::atoi(knob("SDX_R_MIXED")) : 4;
-    const int far_mode = ctx->far_field >= 0 ? (int)ctx->far_field : far_env;
-    if (ctx->mixed_precision && r_mixed_env == 8) return false;  // (experiment knob: 512-point tiles)
+    const int far_mode = (int)ctx->far_field;  // (context option: -1 by the rule, 0 never, 1 whenever possible)
     return far_mode != 0 && (far_mode == 1 || n_nu_global >= kFarMinPoints);
 }
 // The (ihi, ilo) pair of every GLOBAL tile that holds columns of the launch: asked of the step's grid-spacing launch (launch_dnu, the
@@ -1316,10 +1302,9 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
                          bool count_evals, const ContinuumJob* job = nullptr, const LineParams* gen = nullptr, const ClassifyPhase* ph = nullptr,
                          const sdx_grid_plan* plan = nullptr)
 {
-    constexpr int R = 4;       // grid points per lane of a wide-role tile (tile = 64 R points)
-    constexpr int R_MIXED = 4;  // fp32 far wings (8 — twice the points per fetched record — measured slower: fewer tiles qualify as far wing)
-    static const int r_mixed_env = knob("SDX_R_MIXED") ? std::atoi(knob("SDX_R_MIXED")) : R_MIXED;  // experiment knob: 4 or 8
-    const int Rm = ctx->mixed_precision ? (r_mixed_env == 8 ? 8 : R_MIXED) : R;
+    // grid points per lane of a wide-role tile (tile = 64 R points), in every mode (fp32 far wings with 8 — twice the points per fetched
+    // record — were measured slower: fewer tiles qualify as far wing)
+    constexpr int R = 4;
     const bool far = far_field_on(ctx, n_nu) && nu_count > 0;
     int rc;
     // (phase 1 computed the ranges — with the far field on then; if the option was switched on in between, k_far_ranges below does it)
@@ -1327,7 +1312,7 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     if (far && !classified_far && (rc = request_far_ranges(ctx, n_nu, nu_begin, nu_count))) return rc;
     LineWork w;
     // (the number of line subsets depends on the global grid and the list alone; the pre-pass of a short list sorts its wide lines by it)
-    const int n_split = choose_splits(n_depth, n_nu, n_lines, Rm, n_lines >= ctx->indexed_min_lines ? 4 : 2);
+    const int n_split = choose_splits(n_depth, n_nu, n_lines, R, n_lines >= ctx->indexed_min_lines ? 4 : 2);
     rc = line_prepass(ctx, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, true, nullptr, nullptr, &w,
                       count_evals, job, gen, nu_begin, nu_count, ph, n_split, plan);
     const FarReq far_req = ctx->far_req;
@@ -1342,9 +1327,7 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
         LaunchScope ls(ctx, "k_hlist");
         launch_line_lists(ctx, n_lines, w, 32);
     }
-    static const bool no_hscan = knob("SDX_NO_HSCAN") != nullptr;  // A/B knob
-    if (no_hscan) w.hscan = nullptr;
-    if (indexed && !no_hscan && !w.sel) {  // the huge lines' scan words in list order (a culled pre-pass has written them itself)
+    if (indexed && !w.sel) {  // the huge lines' scan words in list order (a culled pre-pass has written them itself)
         LaunchScope ls(ctx, "k_hlist");
         hipLaunchKernelGGL(k_hscan, dim3(64, (unsigned)n_depth), dim3(kBlock), 0, ctx->stream, n_depth, n_lines, (const int*)w.hlist, (const int*)w.hcount,
                            (const WideScan*)w.wscan, w.hscan);
@@ -1366,97 +1349,68 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     if (rc) return rc;
     double* part = (double*)ctx->part_ws;
     const int64_t pld = nu_count;
-    // tiles are aligned to the GLOBAL grid (multiples of 64 Rm points from index 0), whatever the shard: which points share a
-    // tile — and with it how a (line, depth, tile) is classified and which points share a reciprocal — is a property of the grid
-    // order of the wide role's tiles over the XCDs: one contiguous eighth each (0), or groups of g tiles going round them —
-    // better balance where an eighth is only a few tiles (a shard's), at the price of fewer neighbouring tiles per L2
-    static const int wide_group_env = knob("SDX_WIDE_GROUP") ? std::atoi(knob("SDX_WIDE_GROUP")) & 15 : -1;
-    const int wide_group = wide_group_env >= 0 ? wide_group_env : 0;
-    // workgroups of n_split waves, rounded up to whole rounds of the XCD-aware order (surplus workgroups return at once)
-    // narrow role: F consecutive frequencies per wave (a line's records, loaded once, serve F evaluations) for DENSE lists —
+    // tiles are aligned to the GLOBAL grid (multiples of 64 R points from index 0), whatever the shard: which points share a
+    // tile — and with it how a (line, depth, tile) is classified and which points share a reciprocal — is a property of the grid.
+    // Order of the wide role's tiles over the XCDs: one contiguous eighth each (groups of g tiles going round them — better balance
+    // where an eighth is only a few tiles, a shard's, at the price of fewer neighbouring tiles per L2 — ran the line
+    // launch of two such shards 2 - 24 % slower: profiles/r06_roles2.txt).
+    // Workgroups of n_split waves, rounded up to whole rounds of the XCD-aware order (surplus workgroups return at once).
+    // Narrow role: F consecutive frequencies per wave (a line's records, loaded once, serve F evaluations) for DENSE lists —
     // at least one line per two grid points, where a frequency visits many lines and the walk is bound by its loads and
     // instructions — as long as >= 8192 such waves remain: an eighth of S-c3 (11 000 - 21 000 columns) with F = 4 ran its
     // line kernel 20 % SLOWER (414 against 345 us: a few thousand four-times-longer waves are the launch's tail); sparse lists
     // on small grids (S-c2: 2000 lines on 7634 points, a latency-bound launch) keep one frequency per wave.  Pure scheduling:
     // every frequency adds its lines in the same order whatever F.  (F = 8 was measured slower than 4 at every size.)
-    static const int narrow_f_env = knob("SDX_NARROW_F") ? std::atoi(knob("SDX_NARROW_F")) : 0;  // A/B knob: 1, 2, 4
     int narrow_f = 1;
     if (2 * n_lines >= n_nu) narrow_f = nu_count >= 32768 ? 4 : (nu_count >= 16384 ? 2 : 1);
-    if (narrow_f_env == 1 || narrow_f_env == 2 || narrow_f_env == 4) narrow_f = narrow_f_env;
     // VERY dense long lists (>= 4 lines per grid point, four line subsets): the four waves of a narrow-role workgroup share one group
     // of four frequencies and split its candidate lines (line_narrow_subsets) — the record sharing of F = 4 with the wave count of
     // F = 1, whatever the width of the launch.  Decided from the global list and grid: it changes the order of a sum.  Measured in
     // round 5: 1e6 lines on 120 398 points (8.3 per point) 10.2 -> 9.9 ms for the whole grid and 1.52 -> 1.36 ms on an eighth; 1.5e5
     // lines (1.25 per point: ~17 lines per wave, less than the wave's start-up and the workgroup's reduction) 2.03 -> 2.20 ms and
     // 311 -> 320 us — hence the density in the rule.
-    static const bool no_narrow_subsets = knob("SDX_NO_NARROW_SUBSETS") != nullptr;  // A/B knob
-    static const int sub_density_env = knob("SDX_NARROW_SUBSETS_DENSITY") ? std::atoi(knob("SDX_NARROW_SUBSETS_DENSITY")) : -1;  // experiment knob: halves of a line per grid point
-    const int64_t sub_density = sub_density_env >= 0 ? sub_density_env : 8;
-    const int narrow_sub = (!no_narrow_subsets && 2 * n_lines >= sub_density * n_nu && n_split == 4 && Rm != 8) ? 4 : 0;
+    const int narrow_sub = (2 * n_lines >= 8 * n_nu && n_split == 4) ? 4 : 0;
     if (narrow_sub) narrow_f = 4;
     // (the narrow workgroups come in whole rounds of the XCD-aware order: line_launch_make, sdx_line_geom.h)
-    static const int narrow_order = knob("SDX_NARROW_ORDER") ? atoi(knob("SDX_NARROW_ORDER")) & 3 : 0;
     static const bool split_launches = knob("SDX_SPLIT_LAUNCHES") != nullptr;  // analysis knob: time the two roles apart
-    const bool split_launches_early = split_launches;
     size_t shmem = (size_t)n_split * (far && SDX_WIDE_QUEUED ? kWideFarLdsDoubles : kWideLdsDoubles) * sizeof(double);
-    // FAR FIELD: units of 4 RF global tiles; RF (1 or 2 node groups per lane) is scheduling only (4 was measured slower than 2 at every size).  Its workgroups are the FIRST of the line kernel's grid (one launch, and a
-    // shard's far waves — the launch's longest chains — run beside the other roles instead of alone on the chip); experiment knob
-    // SDX_FAR_LAUNCH gives them a launch of their own, with kFarSplit waves per workgroup.  Either way the number of line subsets is
-    // a constant of the mode (it fixes the order of a node's sum): n_split merged, kFarSplit alone.
-    static const bool far_own_launch = knob("SDX_FAR_LAUNCH") != nullptr;
-    static const int far_rf_env = knob("SDX_FAR_RF") ? std::atoi(knob("SDX_FAR_RF")) : 0;  // experiment knob: 1, 2
-    const int64_t far_t_first = nu_begin / (64 * R), far_t_last = (nu_begin + nu_count - 1) / (64 * R);
-    auto far_units_of = [&](int f) { return far_t_last / (4 * f) - far_t_first / (4 * f) + 1; };
-    // (round 6: units of 8 tiles at every size — on the eighths of S-c3 / S-c4m, where the rule above chose 4, the line launch ran 2 - 5 %
-    // faster with 8: half as many waves walk the huge lines' scan words)
-    int far_rf = 2;
-    if (far_rf_env == 1 || far_rf_env == 2) far_rf = far_rf_env;
-    const int64_t far_units = far ? far_units_of(far_rf) : 0;
-    const bool far_merged = far && !far_own_launch && !split_launches_early;
-    if (far_merged) shmem = std::max(shmem, (((size_t)n_split + 2) * far_rf * 64 + (size_t)n_split * kFarWaveLdsDoubles) * sizeof(double));
-    // The launch's geometry, formed ONCE here (sdx_line_geom.h): which block is which role's which unit — tiles aligned to the global
-    // grid, the XCD-aware orders of both roles, the narrow role's groups of F frequencies, every knob above resolved — so that no wave
-    // divides by a launch constant.  It also states the range: grid, units and frequency indices stay 32-bit.
-    const LineLaunch launch = line_launch_make(nu_begin, nu_count, n_depth, n_split, 64 * Rm, narrow_f, narrow_sub != 0, wide_group, narrow_order,
-                                               kLineRoleWide | kLineRoleNarrow, far_merged ? far_units * n_depth : 0);
-    REQUIRE(launch.ok, "line opacity: grid too large for one launch");
-    const dim3 g((unsigned)launch.blocks), blk((unsigned)(64 * n_split));
-    // (k_line_far on a second stream beside k_line_all — a fork and a join per step — was measured in round 5: S-c3 1.857 -> 1.840 ms, its
-    // eighth 0.419 -> 0.420, S-c4m 7.49 -> 7.48: both kernels are bound by their instructions, neither leaves the other idle slots)
-    auto launch_far = [&]() -> int {
-        const int rf = far_rf;
-        const int64_t units = far_units;
-        REQUIRE(units * n_depth < ((int64_t)1 << 31), "line opacity: grid too large for one launch");
-        static const int far_split_env = knob("SDX_FAR_SPLIT") ? std::atoi(knob("SDX_FAR_SPLIT")) : 0;  // experiment knob: 1 .. 8
-        const int far_split = far_split_env >= 1 && far_split_env <= 8 ? far_split_env : kFarSplit;
-        const size_t far_shmem = (((size_t)far_split + 2) * rf * 64 + (size_t)far_split * kFarWaveLdsDoubles) * sizeof(double);
-        const dim3 fg((unsigned)(units * n_depth)), fblk((unsigned)(64 * far_split));
-        double* far_plane = part + (size_t)2 * n_depth * pld;
-        LaunchScope ls(ctx, "k_line_far");
-#define SDX_FAR_ARGS (int)units, far_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, w, far_plane, pld
-        if (rf == 2) hipLaunchKernelGGL((k_line_far<R, 2>), fg, fblk, far_shmem, ctx->stream, SDX_FAR_ARGS);
-        else hipLaunchKernelGGL((k_line_far<R, 1>), fg, fblk, far_shmem, ctx->stream, SDX_FAR_ARGS);
-#undef SDX_FAR_ARGS
-        return SDX_OK;
-    };
+    // FAR FIELD: units of 4 RF global tiles; RF (1 or 2 node groups per lane) is scheduling only (4 was measured slower than 2 at every
+    // size).  Its workgroups are the FIRST of the line kernel's grid (one launch, and a shard's far waves — the launch's longest chains —
+    // run beside the other roles instead of alone on the chip: as a launch of their own they lost, profiles/r06_roles.txt).  The number of
+    // line subsets fixes the order of a node's sum: n_split, the line kernel's.
+    // (round 6: units of 8 tiles at every size — on the eighths of S-c3 / S-c4m, where an earlier rule chose 4, the line launch ran 2 - 5 %
+    // faster with 8: half as many waves walk the huge lines' scan words; profiles/r06_far_rf.txt)
+    constexpr int far_rf = 2;
+    const int64_t far_units = far ? (nu_begin + nu_count - 1) / (64 * R) / (4 * far_rf) - nu_begin / (64 * R) / (4 * far_rf) + 1 : 0;
+    if (far) shmem = std::max(shmem, (((size_t)n_split + 2) * far_rf * 64 + (size_t)n_split * kFarWaveLdsDoubles) * sizeof(double));
+    // (the far role on a second stream beside the other two — a fork and a join per step — was measured in round 5: S-c3 1.857 -> 1.840 ms,
+    // its eighth 0.419 -> 0.420, S-c4m 7.49 -> 7.48: both are bound by their instructions, neither leaves the other idle slots)
     for (int pass = 0; pass < (split_launches ? 2 : 1); ++pass) {
         // (raising the priority of the hot layers' waves with s_setprio was measured in round 4: the instruction has side effects as
         // far as the compiler is concerned, the record fetches of the walk stopped being scalar loads and the kernel ran 37 % slower)
-        // (split launches: the same grid twice, one role live in each)
-        const LineGeom geom = split_launches ? line_launch_make(nu_begin, nu_count, n_depth, n_split, 64 * Rm, narrow_f, narrow_sub != 0, wide_group, narrow_order,
-                                                                pass ? kLineRoleNarrow : kLineRoleWide, 0).g : launch.g;
-        LaunchScope ls(ctx, split_launches ? (pass ? "k_line_narrow" : "k_line_wide") : "k_line_all", far_merged ? "k_line_all + far role" : (far ? "k_line_all (far field in k_line_far)" : nullptr));
+        // The launch's geometry, formed here on the host (sdx_line_geom.h): which block is which role's which unit — tiles aligned to the global
+        // grid, the XCD-aware orders of both roles, the narrow role's groups of F frequencies — so that no wave divides by a launch
+        // constant.  It also states the range: grid, units and frequency indices stay 32-bit.
+        // (split launches: one role live in each; the far role's workgroups are in front of the first, the wide role's, and nowhere in the
+        // second: the same units with the same subsets as in the one launch, so the same three planes)
+        const bool far_front = far && pass == 0;
+        const LineLaunch launch = line_launch_make(nu_begin, nu_count, n_depth, n_split, 64 * R, narrow_f, narrow_sub != 0, 0, 0,
+                                                   split_launches ? (pass ? kLineRoleNarrow : kLineRoleWide) : kLineRoleWide | kLineRoleNarrow,
+                                                   far_front ? far_units * n_depth : 0);
+        REQUIRE(launch.ok, "line opacity: grid too large for one launch");
+        const LineGeom& geom = launch.g;
+        const dim3 g((unsigned)launch.blocks), blk((unsigned)(64 * n_split));
+        LaunchScope ls(ctx, split_launches ? (pass ? "k_line_narrow" : "k_line_wide") : "k_line_all", far_front ? "k_line_all + far role" : nullptr);
         // (the kernels with a far field decode the launch themselves: LineWords, sdx_kernels.h — the same grid and the same units)
-        const LineWords words{geom.narrow_first - geom.wide_first, (int)(((nu_begin + nu_count + 64 * Rm - 1) / (64 * Rm)) - nu_begin / (64 * Rm)),
-                              (split_launches ? (1 << pass) : 3) | (narrow_order << 2) | (wide_group << 4) | (narrow_f << 8) | ((far_merged ? far_rf : 0) << 16), (int)far_units};
+        const LineWords words{geom.narrow_first - geom.wide_first, (int)(((nu_begin + nu_count + 64 * R - 1) / (64 * R)) - nu_begin / (64 * R)),
+                              (split_launches ? (1 << pass) : 3) | (narrow_f << 8) | ((far_front ? far_rf : 0) << 16), (int)far_units};
 #define SDX_LINE_TAIL n_split, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, part, pld
 #define SDX_LINE_ARGS geom, SDX_LINE_TAIL
 #define SDX_LINE_FAR_ARGS words, SDX_LINE_TAIL
-        if (ctx->mixed_precision && Rm == 8) hipLaunchKernelGGL((k_line_all_mixed<8>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
-        else if (ctx->mixed_precision && narrow_sub && far) hipLaunchKernelGGL((k_line_all_mixed<R_MIXED, true, true>), g, blk, shmem, ctx->stream, SDX_LINE_FAR_ARGS);
-        else if (ctx->mixed_precision && narrow_sub) hipLaunchKernelGGL((k_line_all_mixed<R_MIXED, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
-        else if (ctx->mixed_precision && far) hipLaunchKernelGGL((k_line_all_mixed<R_MIXED, false, true>), g, blk, shmem, ctx->stream, SDX_LINE_FAR_ARGS);
-        else if (ctx->mixed_precision) hipLaunchKernelGGL((k_line_all_mixed<R_MIXED>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
+        if (ctx->mixed_precision && narrow_sub && far) hipLaunchKernelGGL((k_line_all_mixed<R, true, true>), g, blk, shmem, ctx->stream, SDX_LINE_FAR_ARGS);
+        else if (ctx->mixed_precision && narrow_sub) hipLaunchKernelGGL((k_line_all_mixed<R, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
+        else if (ctx->mixed_precision && far) hipLaunchKernelGGL((k_line_all_mixed<R, false, true>), g, blk, shmem, ctx->stream, SDX_LINE_FAR_ARGS);
+        else if (ctx->mixed_precision) hipLaunchKernelGGL((k_line_all_mixed<R>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
         else if (w.n_csplit && narrow_sub && far) hipLaunchKernelGGL((k_line_listed<R, true, true>), g, blk, shmem, ctx->stream, SDX_LINE_FAR_ARGS);
         else if (w.n_csplit && narrow_sub) hipLaunchKernelGGL((k_line_listed<R, true>), g, blk, shmem, ctx->stream, SDX_LINE_ARGS);
         else if (w.n_csplit && far) hipLaunchKernelGGL((k_line_listed<R, false, true>), g, blk, shmem, ctx->stream, SDX_LINE_FAR_ARGS);
@@ -1469,7 +1423,6 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
 #undef SDX_LINE_FAR_ARGS
 #undef SDX_LINE_TAIL
     }
-    if (far && !far_merged && (rc = launch_far())) return rc;
     *partial_out = part;
     *pld_out = pld;
     *n_planes_out = far ? 3 : 2;

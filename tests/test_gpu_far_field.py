@@ -1,4 +1,4 @@
-"""The far field of the line kernels (k_line_far, context option "far_field"): (line, depth, tile) triples whose 256-point tile lies
+"""The far field of the line kernels (line_far_body, context option "far_field"): (line, depth, tile) triples whose 256-point tile lies
 wholly inside the line's window, clear of its core and at least three tile widths from its centre are summed at the tile's 16
 Chebyshev nodes and carried to the grid points by the degree-15 interpolant.  It must agree with the direct sum far inside the
 opacity tolerance (1e-12), keep the zeros of the reference, stay bit-identical under frequency sharding and work on grids whose
@@ -30,8 +30,8 @@ def run(ctx, far, nus, atm, lines, cont, th, w, **kw):
     syn = SpectralSynthesizer(nus, atm["temperatures"], atm["dist"], th, w, lines, cont, ctx=ctx, track_evaluations=False, **kw)
     syn.step()
     out = syn.alpha_line().copy(), syn.total_alphas().copy(), syn.F_nu().copy()
-    # (the far field is a role of the line kernel's launch — or, under an experiment knob, a launch of its own)
-    launched = ctx.profile("k_line_far")[0] > 0 or "far" in ctx.profile_variant("k_line_all")
+    # (the far field is a role of the line kernel's launch)
+    launched = "far" in ctx.profile_variant("k_line_all")
     ctx.call("sdx_profile_enable", 0)
     syn.close()
     return out, launched
@@ -43,6 +43,72 @@ def workload(lam0, lam1, R, n_lines, seed, mix=(0.5, 0.3, 0.2), n_theta=4):
     lines = synth.synth_lines(nus, atm, n_lines, seed=seed, mix=mix)
     th, w = synth.thetas_and_weights(n_theta)
     return atm, nus, lines, synth.synth_continuum_state(atm), th, w
+
+
+_SPLIT_CHILD = r"""
+import hashlib, sys
+import numpy as np
+sys.path.insert(0, %r)
+from stardis_amd import _lib, synth
+from stardis_amd.engine import SpectralSynthesizer
+atm = synth.solar_atmosphere()
+nus = synth.tracing_grid(4000.0, 4170.0, R=1.0e5)
+lines = synth.synth_lines(nus, atm, 400, seed=5, mix=(0.5, 0.3, 0.2))  # (workload() below, seed 5)
+th, w = synth.thetas_and_weights(4)
+cont = synth.synth_continuum_state(atm)
+assert 2 * 2048 < nus.size < 2 * 2048 + 256 and atm["temperatures"].size == 56  # just over two far units of 2048 points
+shard = (700, nus.size - 730)  # begins inside the first unit, ends inside the third
+ctx = _lib.Context(0)
+for min_lines in (8192, 100):  # a short list (every line scanned) and the same list as a long one (hlist / wlist)
+    ctx.set_option("indexed_min_lines", min_lines)
+    out = []
+    for far in (0, 1):
+        ctx.set_option("far_field", far)
+        ctx.call("sdx_profile_enable", 1)
+        ctx.call("sdx_profile_reset")
+        syn = SpectralSynthesizer(nus, atm["temperatures"], atm["dist"], th, w, lines, cont, ctx=ctx, track_evaluations=False, shard=shard)
+        syn.step()
+        out.append((syn.alpha_line().copy(), syn.F_nu().copy()))
+        launches = [ctx.profile(k)[0] for k in ("k_line_all", "k_line_wide", "k_line_narrow", "k_line_far")]
+        far_role = "far" in ctx.profile_variant("k_line_wide" if launches[1] else "k_line_all")
+        ctx.call("sdx_profile_enable", 0)
+        syn.close()
+    assert not np.array_equal(out[0][0], out[1][0])  # lines wide enough for the far role
+    print("LAUNCHES", min_lines, *launches, int(far_role))
+    print("RESULT", min_lines, *(hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest() for a in out[1]))
+ctx.close()
+"""
+
+
+def test_split_launches_write_the_planes_of_the_single_launch():
+    """SDX_SPLIT_LAUNCHES (profiling: the line kernel as two launches) keeps the far role in front of the first launch, with the line
+    kernel's own subsets: a profiled run sums in the order of the run it profiles.  alpha_line and F_nu of a shard that begins and ends
+    inside a far unit, short list and long, byte for byte; each run in a process of its own (the knob is read once)."""
+    import os
+    import subprocess
+    import sys
+
+    from conftest import ROOT
+
+    def child(extra):
+        env = {k: v for k, v in os.environ.items() if not k.startswith("SDX_")}
+        env.update(extra)
+        r = subprocess.run([sys.executable, "-c", _SPLIT_CHILD % ROOT], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        return [[ln.split()[1:] for ln in r.stdout.splitlines() if ln.startswith(tag)] for tag in ("RESULT", "LAUNCHES")]
+
+    plain, plain_launches = child({})
+    split, split_launches = child(dict(SDX_EXPERIMENT="1", SDX_SPLIT_LAUNCHES="1"))
+    # (k_line_all, k_line_wide, k_line_narrow, k_line_far launches of the step, and whether the first carried the far role)
+    for row in plain_launches:
+        n_all, n_wide, n_narrow, n_far, far_role = (int(v) for v in row[1:])
+        assert n_all >= 1 and n_wide == n_narrow == n_far == 0 and far_role, row
+    for row in split_launches:
+        n_all, n_wide, n_narrow, n_far, far_role = (int(v) for v in row[1:])
+        assert n_all == 0 and n_wide == n_narrow >= 1 and n_far == 0 and far_role, row
+    assert len(plain_launches) == len(split_launches) == 2
+    assert len(plain) == 2 and [p[0] for p in plain] == ["8192", "100"]
+    assert split == plain
 
 
 @pytest.mark.parametrize("n_lines", [700, 9000])  # short lists are scanned completely; long ones go through hlist / wlist

@@ -169,7 +169,7 @@ def test_wide_units_of_every_block(probe):
                     seen.add(check_wide(probe, nu_begin, nu_count, n_depth, wide_group, far_blocks=5 * n_depth))
                 check_wide(probe, nu_begin, nu_count, n_depth, 0, mask=2)
     assert seen >= {1, 7, 8, 9, 471, 4703}, seen
-    # the listed shards too, 512-point tiles (the mixed mode's experiment knob) and a wide group that is no power of two
+    # the listed shards too, 512-point tiles (which no kernel runs any more: the header takes any tile) and a wide group that is no power of two
     for nu_begin in NU_BEGIN:
         for nu_count in NU_COUNT:
             check_wide(probe, nu_begin, nu_count, 56, 0)

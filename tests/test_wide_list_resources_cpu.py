@@ -22,7 +22,7 @@ def test_every_line_kernel_keeps_its_occupancy_without_spills(resources):  # noq
     for name, waves in LINE_KERNELS.items():
         assert name in resources, sorted(resources)
         assert resources[name]["occ"] >= waves and resources[name]["spill"] == 0, (name, resources[name])
-    # (the 512-point tiles of the mixed mode are an experiment knob: no occupancy bound, but no spills either)
+    # (and whatever other instantiation of these families the library ships: no spills either)
     for name in resources:
         if name.startswith(("k_line_all<", "k_line_all_mixed<", "k_line_listed<")):
             assert resources[name]["spill"] == 0, (name, resources[name])
