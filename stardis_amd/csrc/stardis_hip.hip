@@ -88,12 +88,9 @@ struct sdx_ctx {
     size_t adj_ws_bytes = 0;
     void* far_ws = nullptr;  // far_range of the line kernels' far field: two ints per global tile
     size_t far_ws_bytes = 0;
-    FarReq far_req{nullptr, 0, 0};  // the tiles whose ranges the step's next grid-spacing launch computes on the side (count = 0: none)
-    bool far_req_done = false;       // ... and whether a launch has taken them along
-    // cnt_ge[N_nu + 2] (lines per centre index, for the narrow-window kernel)
+    // cnt_ge[N_nu + 2] (lines per centre index, for the narrow-window kernel) and the per-line integer lists: CntLayout
     void* cnt_ws = nullptr;
     size_t cnt_ws_bytes = 0;
-    size_t cnt_ge_len = 0;
     // tuning options (sdx_set_int_option)
     int64_t indexed_min_lines = 8192;  // line lists at least this long: wide lines found by centre range / the huge-line list instead of a full scan
     int64_t prepass_ticket_min_blocks = 16384;  // culled shards: from this many line blocks on the pre-pass draws its work from a counter
@@ -154,7 +151,50 @@ struct sdx_grid_plan {
 
 namespace {
 
-constexpr size_t kSmallHeader = 4096 + 8 * (size_t)sdx::kGridSample;  // [0,2048): d_nu partials; [2048,2056): evaluation counter; [2064, ..): ticket counters; [4096, ..): grid sample
+// The problem as values: built once by the extern "C" entry points, right after their argument checks, and handed down as they are.
+struct Grid {  // the model's depths, the frequency grid and the columns [nu_begin, nu_begin + nu_count) of this call
+    int n_depth;
+    int64_t n_nu;
+    const double* nus;
+    int64_t nu_begin, nu_count;
+};
+struct Lines {  // dense tables, or — `gen` — the description the pre-pass generates them from (doppler, gammas and alphas are then null)
+    int64_t n_lines;
+    const double *line_nus, *doppler, *gammas;
+    int gamma_cols;
+    const double* alphas;
+    const LineParams* gen;
+};
+struct Rays {
+    int n_theta;
+    const double *temps, *ray_dist, *wts;
+};
+
+// small_ws, in bytes: the grid-spacing partial maxima, the counters (zeroed when the buffer is allocated: ensure_small), the grid sample
+constexpr size_t kEvalsOffset = 2048;       // evaluation counter (one unsigned long long)
+constexpr size_t kTicketOffset = 2064;      // work counters of a culled shard's counter-driven pre-pass launch (k_hlist_count zeroes eight)
+constexpr size_t kListTicketOffset = 2128;  // finished line blocks of a short list's pre-pass (LineWork::ticket with n_csplit)
+constexpr size_t kSampleOffset = 4096;      // the grid sample
+constexpr size_t kSmallHeader = kSampleOffset + 8 * (size_t)sdx::kGridSample;
+static_assert(sizeof(double) * sdx::kDnuPartials <= kEvalsOffset, "the partial maxima end before the evaluation counter");
+static_assert(kEvalsOffset + sizeof(unsigned long long) <= kTicketOffset, "the evaluation counter ends before the ticket counters");
+static_assert(kTicketOffset + 8 * sizeof(int) <= kListTicketOffset, "the ticket counters end before the list ticket");
+static_assert(kListTicketOffset + sizeof(int) <= kSampleOffset, "the list ticket ends before the grid sample");
+static_assert(kSampleOffset == sizeof(double) * sdx::kGridSampleOffset, "the kernels find the grid sample kGridSampleOffset doubles behind the partial maxima");
+
+// cnt_ws, in ints: cnt_ge, then per line centre, nhw_max, whw_max and the lists hlist, wlist, wrank [n + 1], xlist; then hcount (its
+// counters, `sel` 4 behind them), the list launches' per-block counts and — 8-byte aligned, doubles — the classification pass's per-line maxima
+struct CntLayout {
+    size_t n, centre, nhw_max, whw_max, hlist, wlist, wrank, xlist, hcount, sel, block_cnt, m_max, bytes;
+    CntLayout(int64_t n_nu, int64_t n_lines) : n((size_t)n_lines)
+    {
+        centre = (size_t)(n_nu + 2 + 63) / 64 * 64;  // the length of cnt_ge
+        nhw_max = centre + n, whw_max = nhw_max + n, hlist = whw_max + n, wlist = hlist + n, wrank = wlist + n, xlist = wrank + n + 1;
+        hcount = whw_max + 5 * n + 8, sel = hcount + 4, block_cnt = hcount + 16;  // 3 ints per block of the list launches behind block_cnt
+        m_max = (block_cnt + 3 * (n / 1024 + 8) + 1) & ~(size_t)1;  // (the buffer itself is aligned far beyond 8 bytes)
+        bytes = (centre + 10 * n + 128 + 3 * (n / 1024 + 8) + 8) * sizeof(int);
+    }
+};
 
 int ensure(sdx_ctx* ctx, void** buf, size_t* have, size_t need)
 {
@@ -190,24 +230,22 @@ int ensure(sdx_ctx* ctx, void** buf, size_t* have, size_t need)
     return SDX_OK;
 }
 
-// the small scratch: its counters ([2048, 4096): evaluation counter, the ticket counters of the pre-pass launches) start at zero — the
-// launch that counts the finished line blocks of a short list's pre-pass (LineWork::ticket with n_csplit) leaves its counter at zero and relies
-// on finding it so
-constexpr size_t kListTicketOffset = 2128;
+// the small scratch: its counters [kEvalsOffset, kSampleOffset) start at zero — the launch that counts the finished line blocks of a short
+// list's pre-pass (LineWork::ticket with n_csplit) leaves its counter at zero and relies on finding it so
 constexpr int64_t kListAutoChunks = 16;  // "wide_list" = -1: short lists of at least this many chunks of 64 lines per line subset
 int ensure_small(sdx_ctx* ctx, size_t need)
 {
     const size_t before = ctx->small_ws_bytes;
     int rc = ensure(ctx, &ctx->small_ws, &ctx->small_ws_bytes, need);
     if (rc) return rc;
-    if (ctx->small_ws_bytes != before) HIP_TRY(hipMemsetAsync((char*)ctx->small_ws + 2048, 0, 2048, ctx->stream));
+    if (ctx->small_ws_bytes != before) HIP_TRY(hipMemsetAsync((char*)ctx->small_ws + kEvalsOffset, 0, kSampleOffset - kEvalsOffset, ctx->stream));
     return SDX_OK;
 }
 
 // per (line, depth) item: wide scan 16 + record 48 + slow 16 + fp32 record 32, narrow record 32, huge-line scan copy 16
 size_t line_ws_need(int n_depth, int64_t n_lines) { return (size_t)n_depth * (size_t)n_lines * 160 + 256; }
 
-LineWork carve(sdx_ctx* ctx, int n_depth, int64_t n_lines)
+LineWork carve(sdx_ctx* ctx, int n_depth, int64_t n_lines, const CntLayout& cnt)
 {
     const size_t n = (size_t)n_depth * (size_t)n_lines;
     char* p = (char*)ctx->line_ws;
@@ -221,9 +259,6 @@ LineWork carve(sdx_ctx* ctx, int n_depth, int64_t n_lines)
     w.n_y = w.n_inv + n;
     w.n_amp = w.n_y + n;
     w.nhw = (unsigned char*)(w.n_amp + n);  // 1 n (the 8 n bytes of the former window bounds stay reserved)
-    w.skip_unlisted_scan = 0;
-    w.n_inv32 = w.n_y32 = w.n_amp32 = nullptr;
-    w.lnu32 = nullptr;
     if (ctx->mixed_precision) {  // the narrow role's records as floats in the same 24 n bytes, + the line frequencies as float pairs
         w.n_inv32 = (float*)w.n_inv;
         w.n_y32 = w.n_inv32 + n;
@@ -232,15 +267,11 @@ LineWork carve(sdx_ctx* ctx, int n_depth, int64_t n_lines)
     }
     w.hscan = (WideScan*)((int*)(w.n_amp + n) + 2 * n);  // 16 n (only the first hcount[0] entries of a row are used)
     w.cnt_ge = (int*)ctx->cnt_ws;
-    w.centre = w.cnt_ge + ctx->cnt_ge_len;
-    w.nhw_max = w.centre + n_lines;
-    w.whw_max = w.nhw_max + n_lines;
-    w.hlist = nullptr;  // set for long lists (set_line_lists)
-    w.wlist = nullptr;
-    w.wrank = nullptr;
-    w.xlist = nullptr;
-    w.hcount = w.whw_max + 5 * n_lines + 8;  // behind hlist [n], wlist [n], wrank [n + 1], xlist [n]
-    w.evals = (unsigned long long*)((char*)ctx->small_ws + 2048);
+    w.centre = w.cnt_ge + cnt.centre;
+    w.nhw_max = w.cnt_ge + cnt.nhw_max;
+    w.whw_max = w.cnt_ge + cnt.whw_max;
+    w.hcount = w.cnt_ge + cnt.hcount;  // (hlist, wlist, wrank, xlist: set for long lists, launch_line_lists)
+    w.evals = (unsigned long long*)((char*)ctx->small_ws + kEvalsOffset);
     return w;
 }
 
@@ -289,17 +320,13 @@ int check_launch(const char* what)
 inline dim3 grid2(int64_t n, int rows) { return dim3((unsigned)((n + kBlock - 1) / kBlock), (unsigned)rows); }
 inline unsigned blocks1(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
-// d_nu partial maxima into small_ws
-int launch_dnu(sdx_ctx* ctx, int64_t n_nu, const double* nus, int* n_partial, int* zero = nullptr, int64_t n_zero = 0)
+// d_nu partial maxima into small_ws (reserved by line_prepass), and on the side the far ranges the step asks for (FarReq, count = 0: none)
+int launch_dnu(sdx_ctx* ctx, int64_t n_nu, const double* nus, int* n_partial, const FarReq& far)
 {
-    int rc = ensure_small(ctx, kSmallHeader);
-    if (rc) return rc;
-    ctx->classified.valid = false;  // (the grid-spacing partials of a two-collective phase 1 are overwritten)
     const int nb = (int)std::min<int64_t>(kDnuPartials, std::max<int64_t>(1, (n_nu + kBlock * 8 - 1) / (kBlock * 8)));
     {
         LaunchScope ls(ctx, "k_dnu_partial");
-        hipLaunchKernelGGL(k_dnu_partial, dim3(nb), dim3(kBlock), 0, ctx->stream, n_nu, nus, (double*)ctx->small_ws, zero, n_zero, ctx->far_req);
-        if (ctx->far_req.count) ctx->far_req_done = true;
+        hipLaunchKernelGGL(k_dnu_partial, dim3(nb), dim3(kBlock), 0, ctx->stream, n_nu, nus, (double*)ctx->small_ws, (int*)nullptr, (int64_t)0, far);
     }
     *n_partial = nb;
     return check_launch("k_dnu_partial");
@@ -497,7 +524,16 @@ int sdx_set_int_option(sdx_ctx* ctx, const char* name, int64_t value)
     return fail(SDX_ERR_ARG, std::string("unknown option ") + name);
 }
 
-static bool far_field_on(const sdx_ctx* ctx, int64_t n_nu_global);
+// FAR FIELD (line_far_body, the far role of the line kernels): a third plane.  Like every choice that moves a rounding it is made from the GLOBAL grid — grids of at
+// least kFarMinPoints frequencies (below that a launch of the line kernel is bound by latency, not by its evaluations) — or set
+// explicitly (context option "far_field").
+constexpr int64_t kFarMinPoints = 32768;
+static_assert(kFarMinPoints == 32768, "sdx_far_field_rule reports this constant");
+static bool far_field_on(const sdx_ctx* ctx, int64_t n_nu_global)
+{
+    const int far_mode = (int)ctx->far_field;  // (context option: -1 by the rule, 0 never, 1 whenever possible)
+    return far_mode != 0 && (far_mode == 1 || n_nu_global >= kFarMinPoints);
+}
 int sdx_far_field_active(const sdx_ctx* ctx, int64_t n_nu_global)
 {
     REQUIRE(ctx, "null context");
@@ -645,12 +681,11 @@ void sdx_grid_plan_destroy(sdx_grid_plan* plan)
 }
 
 // the step's arguments against what a plan was built from: refused before anything is enqueued
-static int check_grid_plan(const sdx_ctx* ctx, const sdx_grid_plan* p, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus,
-                           const sdx_continuum* cont)
+static int check_grid_plan(const sdx_ctx* ctx, const sdx_grid_plan* p, const Grid& g, const Lines& l, const sdx_continuum* cont)
 {
     REQUIRE(p->ctx == ctx, "synthesize: the grid plan belongs to another context");
-    REQUIRE(p->n_nu == n_nu && p->nus == nus, "synthesize: the grid plan was built for another frequency grid (pointer or size)");
-    REQUIRE(p->n_lines == n_lines && (n_lines == 0 || p->line_nus == line_nus), "synthesize: the grid plan was built for another line list (pointer or size)");
+    REQUIRE(p->n_nu == g.n_nu && p->nus == g.nus, "synthesize: the grid plan was built for another frequency grid (pointer or size)");
+    REQUIRE(p->n_lines == l.n_lines && (l.n_lines == 0 || p->line_nus == l.line_nus), "synthesize: the grid plan was built for another line list (pointer or size)");
     REQUIRE(p->table_sigma == cont->table_sigma && (!cont->table_sigma || (p->lambdas == cont->lambdas && p->table_wavelength == cont->table_wavelength &&
                                                                            p->n_table == cont->n_table)),
             "synthesize: the grid plan was built for another cross-section table (pointers or size)");
@@ -890,11 +925,6 @@ int sdx_profile_variant(sdx_ctx* ctx, const char* kernel, char* out, int out_len
 }
 
 // ================================================================================================ line opacity
-struct ContinuumJob {  // continuum plane computed by the trailing blocks of the pre-pass launch
-    const sdx_continuum* cont;
-    int64_t nu_begin, nu_count;
-    double* plane;
-};
 // Frequency shards of long lists, two-collective mode: the classification stream of a culled pre-pass (the largest (gamma + dw) alpha
 // of every line, 8 N_l (2 N_d + G) bytes read by EVERY rank) split over the ranks — phase 1 classifies a share of the lines into the
 // caller's m_max array (and does everything else of that launch: grid spacing, the shard's line ranges, the continuum plane), the
@@ -938,274 +968,207 @@ static bool use_segmented_raytrace(const sdx_ctx* ctx, int n_depth, int64_t n_nu
     return legacy_waves < kSegLegacyWaves;
 }
 
-// long lists: hlist / wlist / wrank from whw_max (two small launches)
-static void launch_line_lists(sdx_ctx* ctx, int64_t n_lines, LineWork& w, int pre_lines, const ClassSource* from_classification = nullptr)
+// long lists: hlist / wlist / wrank from whw_max, or from a classification pass (two small launches)
+static void launch_line_lists(sdx_ctx* ctx, const CntLayout& cnt, LineWork& w, int pre_lines, const ClassSource* from_classification)
 {
     ClassSource cs{};
     if (from_classification) cs = *from_classification;
     else cs.whw_max = w.whw_max;
-    w.hlist = w.whw_max + n_lines;
-    w.wlist = w.hlist + n_lines;
-    w.wrank = w.wlist + n_lines;
-    w.xlist = w.sel ? w.wrank + n_lines + 1 : nullptr;  // culled runs only
+    int* const base = (int*)ctx->cnt_ws;
+    const int64_t n_lines = (int64_t)cnt.n;
+    w.hlist = base + cnt.hlist;
+    w.wlist = base + cnt.wlist;
+    w.wrank = base + cnt.wrank;
+    w.xlist = w.sel ? base + cnt.xlist : nullptr;  // culled runs only
     const unsigned hb = (unsigned)((n_lines + kHlistBlock - 1) / kHlistBlock);
-    int* block_cnt = w.hcount + 16;  // 3 hb ints behind the counters and sel (reserved in cnt_ws)
+    int* block_cnt = base + cnt.block_cnt;  // 3 hb ints behind the counters and sel
     hipLaunchKernelGGL(k_hlist_count, dim3(hb), dim3(kHlistBlock), 0, ctx->stream, n_lines, cs, block_cnt, w.sel, pre_lines, w.ticket);
     hipLaunchKernelGGL(k_hlist_scatter, dim3(hb), dim3(kHlistBlock), 0, ctx->stream, n_lines, cs, (const int*)block_cnt, w.hlist,
                        w.wlist, w.wrank, w.hcount, w.xlist, w.sel, pre_lines);
 }
 
-static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus,
-                        const double* doppler, const double* gammas, int gamma_cols, const double* alphas, bool fill_work,
-                        int32_t* lo_ref, int32_t* hi_ref, LineWork* w_out, bool count_evals = true,
-                        const ContinuumJob* job = nullptr, const LineParams* gen = nullptr, int64_t nu_begin = 0, int64_t nu_count = -1,
-                        const ClassifyPhase* ph = nullptr, int wide_splits = 0, const sdx_grid_plan* plan = nullptr)
+// What a caller asks of the pre-pass beyond the problem itself ...
+struct PrepassRequest {
+    int32_t *lo_ref, *hi_ref;   // the windows alone (sdx_line_windows_dev); null: the line kernels' records
+    bool count_evals;
+    const sdx_continuum* cont;  // the fused step: its continuum plane [n_depth][nu_count] is computed ...
+    double* cont_plane;         // ... into this by the trailing blocks of the pre-pass (or the classification) launch
+    const ClassifyPhase* ph;    // two-collective mode
+    int wide_splits;            // the wide role's line subsets (a short list's wide lines are listed per subset); 0: no such list
+    const sdx_grid_plan* plan;
+    FarReq far;                 // the tiles whose far ranges the step's grid-spacing launch computes on the side (count = 0: none)
+};
+
+// continuum blocks of the fused step: one per (frequency tile of `threads` points, group of dgs depths) when the per-depth
+// factors of a group fit LDS (always, for a handful of bound-free levels), else one per (tile, depth) evaluating every point
+// from scratch
+struct ContPlan {
+    ContinuumArgs ca;
+    size_t shmem;
+    int cont_tiles, stage_table;
+    unsigned cont_rows;
+    bool tiled;
+};
+// (other_blocks: the line and pixel blocks of a pre-pass launch the tiles ride with)
+static int plan_continuum(const sdx_ctx* ctx, const sdx_continuum* cont, const Grid& g, int threads, int64_t other_blocks, ContPlan* p)
 {
-    if (nu_count < 0) nu_count = n_nu;
-    const LineParams lp = gen ? *gen : LineParams{};
-    int n_partial = 0;
-    // every pre-pass rewrites the scratch a two-collective phase 1 leaves for its phase 2 (grid spacing, line ranges, lists): only the
-    // phase 2 that consumes it may find it valid (phase 1 sets the flag again when its launch is enqueued)
-    const bool consumes_classified = ph && ph->phase == 2;
-    if (!consumes_classified) ctx->classified.valid = false;
-    int rc = ensure_small(ctx, kSmallHeader);
-    if (rc) return rc;
-    const bool scan_in_block = n_nu <= 16384;  // every pre-pass block re-scans a small grid instead of a separate launch
-    LineWork w{};
-    // 16 lines per block while all such blocks are resident at once (two 1024-thread blocks per CU), else 32
-    int pre_lines = ((n_lines + 15) / 16) * ((n_depth + kPreDepths - 1) / kPreDepths) <= 2 * (int64_t)ctx->n_cu ? 16 : 32;
-    // A culled shard (decided below from the same quantities) prepares its own line range + the listed lines: at an eighth of 1.5e5
-    // lines ~22 000 lines, 690 blocks of 32 on the chip's 512 slots of 1024 threads — a whole second round of the block's chain of
-    // round trips for a third of a round's work.  48 lines per block (three items per thread, registers only) are 470 blocks:
-    // ONE round, a chain one item longer.
-    const bool will_cull = fill_work && n_lines >= ctx->indexed_min_lines && !count_evals && !gen && n_nu > 16384 && nu_count < n_nu;
-    // (lists long enough for the counter-driven launch keep 32: its looping kernel has no registers to spare for a third item)
-    // (54 when the model has at most 56 depth points — every MARCS model — and three items per thread still cover the block)
-    if (will_cull && !lo_ref && (n_lines + 31) / 32 < ctx->prepass_ticket_min_blocks)
-        pre_lines = n_depth <= 56 ? 54 : 48;
-    const int n_line_blocks = (int)((n_lines + pre_lines - 1) / pre_lines);
-    int n_pixel_blocks = 0;
-    if (fill_work) {
-        rc = ensure(ctx, &ctx->line_ws, &ctx->line_ws_bytes, line_ws_need(n_depth, n_lines));
-        if (rc) return rc;
-        ctx->cnt_ge_len = (size_t)(n_nu + 2 + 63) / 64 * 64;
-        // cnt_ge, then per line: centre, nhw_max, whw_max, hlist, wlist, wrank, xlist; then hcount, sel and the per-block counts
-        // ... and, behind those, the classification pass's per-line maxima (doubles)
-        rc = ensure(ctx, &ctx->cnt_ws, &ctx->cnt_ws_bytes, (ctx->cnt_ge_len + 10 * (size_t)n_lines + 128 + 3 * ((size_t)n_lines / 1024 + 8) + 8) * sizeof(int));
-        if (rc) return rc;
-        w = carve(ctx, n_depth, n_lines);
-        if (n_depth > kPreDepths) HIP_TRY(hipMemsetAsync(w.nhw_max, 0, (size_t)2 * n_lines * sizeof(int), ctx->stream));  // nhw_max and whw_max
-        if (count_evals) HIP_TRY(hipMemsetAsync(w.evals, 0, sizeof(unsigned long long), ctx->stream));
-        else w.evals = nullptr;
-        n_pixel_blocks = (int)((n_nu + 2 + kPreBlock - 1) / kPreBlock);
-    }
-    w.sel = nullptr;
-    w.gather = 0;
-    w.ticket = nullptr;
-    w.front = 0;
-    // SHORT lists (never culled, no list launches): the last line block of the pre-pass launch to finish lists the lines with a wide
-    // window per line subset of the wide role (LineWork::n_csplit; in the space long lists keep hlist in, the counts and offsets where
-    // the list launches keep their per-block counts) and the wide role walks that list instead of every line.  Same hits in the
-    // same order: scheduling only (context option "wide_list").  Not in the mixed-precision mode, whose fp32 sums are flushed into
-    // the fp64 sums at chunk boundaries: other chunks would move those roundings.
-    // Automatic rule: from kListAutoChunks chunks of 64 lines per subset on.  Measured (profiles/EXPERIMENTS.md, "Short lists walk a
-    // list of their wide lines"): at S-c2 (16 chunks per subset, 2 listed) the line kernel runs 1.2 us faster and the list is built in
-    // the shadow of the launch's continuum tiles; at S-c1 (4 per subset, 1 listed) the line kernel gains nothing and the last block's
-    // 3 us show at the end of a pre-pass launch whose continuum tiles are done before its line blocks.
-    const int64_t chunks_per_subset = wide_splits > 0 ? ((n_lines + 63) / 64 + wide_splits - 1) / wide_splits : 0;
-    if (fill_work && wide_splits > 0 && (ctx->wide_list == 1 || (ctx->wide_list < 0 && chunks_per_subset >= kListAutoChunks)) &&
-        !ctx->mixed_precision && n_lines > 0 && n_lines < ctx->indexed_min_lines && (n_lines + 63) / 64 <= kListMaxChunks) {
-        w.n_csplit = wide_splits;  // (its counter of finished line blocks: `ticket`, set where the launch is enqueued)
-    }
-    // VERY dense long fp64 lists (>= 4 lines per grid point: the rule of the narrow role's subsets): no narrow records — the narrow role
-    // reads the caller's three tables itself (LineWork::narrow_raw).  Pure scheduling (the same three operations form 1 / dw, y and the
-    // amplitude either way).  Measured in round 6 (profiles/r06_raw.txt): 1e6 lines on 120 398 points — pre-pass 904 -> 721 us (a stream:
-    // 2.13 GB of traffic counted, 1.31 GB of it these records), line kernel 5.93 -> 6.07 ms (ten more instructions per evaluated line), step
-    // 7.27 -> 7.24 ms and 1.35 GB less scratch; 1.5e5 lines: pre-pass 165 -> 149 us, line kernel 1.218 -> 1.241 ms, the step 7 us SLOWER —
-    // hence the density in the rule.
-    const int narrow_records = (int)ctx->narrow_records;  // (context option: -1 by this rule, 0 never, 1 always)
-    const bool very_dense = 2 * n_lines >= 8 * n_nu;
-    if (fill_work && !gen && !ctx->mixed_precision && n_lines >= ctx->indexed_min_lines && (narrow_records == 0 || (very_dense && narrow_records != 1))) {
-        w.narrow_raw = gamma_cols > 1 ? n_depth : 1;
-        w.n_inv = const_cast<double*>(doppler);
-        w.n_y = const_cast<double*>(gammas);
-        w.n_amp = const_cast<double*>(alphas);
-    }
-    // long lists find their wide lines through hlist / wlist: the scan words of a line without a wide window anywhere are never
-    // read (needs the line's widest window inside one block: one depth block per line)
-    w.skip_unlisted_scan = (fill_work && n_lines >= ctx->indexed_min_lines && n_depth <= kPreDepths) ? 1 : 0;
-    w.n_pix = n_pixel_blocks;
-    w.shard_begin = nu_begin;
-    w.shard_end = nu_begin + nu_count;
-    // A frequency shard of a long list does not need every line prepared: a streaming classification pass finds the lines
-    // that can reach any column (-> hlist), the full pre-pass then runs on the lines centred near the shard plus those.
-    // Everything is decided on the device (no host round trip, graph-capturable); which lines a shard prepares does not
-    // change what it computes for them.
-    const bool cull = fill_work && n_lines >= ctx->indexed_min_lines && !count_evals && !gen && !scan_in_block && nu_count < n_nu;
-    REQUIRE(!ph || cull, "two-collective mode is for frequency shards of long dense line lists (>= indexed_min_lines lines, a grid of more than "
-                         "16384 points, nu_count < n_nu, no evaluation count)");
-    // the grid-spacing reduction: a launch of its own, or — culled runs — the first blocks of the classification launch
-    int* const sel = cull ? w.hcount + 4 : nullptr;
-    // (grid-spacing blocks of a classification launch: four pairs of loads per thread — one trip of their loop — up to 256 blocks)
-    if (cull) n_partial = (int)std::min<int64_t>(kDnuPartials, std::max<int64_t>(1, (n_nu + kBlock * 4 - 1) / (kBlock * 4)));
-    // continuum blocks of the fused step: one per (frequency tile of `threads` points, group of dgs depths) when the per-depth
-    // factors of a group fit LDS (always, for a handful of bound-free levels), else one per (tile, depth) evaluating every point
-    // from scratch
-    struct ContPlan {
-        ContinuumArgs ca;
-        size_t shmem;
-        int cont_tiles, stage_table;
-        unsigned cont_rows;
-        bool tiled;
-    };
-    auto plan_continuum = [&](int threads, ContPlan* p) -> int {
-        p->ca = to_args(job->cont, nullptr);
-        ContinuumArgs& ca = p->ca;
-        ca.bf_level_density = job->cont->bf_level_density;
-        p->shmem = 8;
-        if (ca.bf_n_species > 0) {
-            REQUIRE(job->cont->bf_n_levels > 0 && job->cont->bf_n_levels <= 4096, "synthesize: bf_n_levels must be set (1..4096)");
-            p->shmem = (size_t)job->cont->bf_n_levels * sizeof(double);
+    const int n_depth = g.n_depth;
+    p->ca = to_args(cont, nullptr);
+    ContinuumArgs& ca = p->ca;
+    ca.bf_level_density = cont->bf_level_density;
+    REQUIRE(ca.bf_n_species <= 0 || (cont->bf_n_levels > 0 && cont->bf_n_levels <= 4096), "synthesize: bf_n_levels must be set (1..4096)");
+    const size_t n_lev = ca.bf_n_species > 0 ? (size_t)cont->bf_n_levels : 0;
+    p->stage_table = ca.table_sigma && ca.n_table > 0 && ca.n_table <= 1024;  // 1-D cross-section table searched from LDS
+    p->shmem = std::max<size_t>(8, (n_lev + (p->stage_table ? 2 * (size_t)ca.n_table : 0)) * sizeof(double));  // (untiled: the bound-free edges, the table)
+    p->cont_tiles = (int)((g.nu_count + (int64_t)threads * kContPoints - 1) / ((int64_t)threads * kContPoints));
+    const size_t tile_shmem = ((size_t)kContDepths * (n_lev + 6) + (p->stage_table ? 2 * (size_t)ca.n_table : 0)) * sizeof(double);
+    p->cont_rows = (unsigned)n_depth;
+    p->tiled = false;
+    if (tile_shmem <= 48 * 1024) {
+        // depths per block: as many as leave ~2 x 1024 threads of such blocks per CU (one depth per block on small grids)
+        int dgs = (int)std::max<int64_t>(1, std::min<int64_t>(kContDepths, ((int64_t)p->cont_tiles * threads / kPreBlock * n_depth) / (2 * (int64_t)ctx->n_cu)));
+        if (threads == kPreBlock) {
+            // ... next to the launch's pre-pass blocks: ALL blocks of the launch in one round of the chip's 2 x n_cu slots of 1024
+            // threads (S-c2: 133 pre-pass blocks + 448 one-depth tiles were 581 on 512 slots — the 69 of the second round ended
+            // the launch at 15.6 us where two depths per tile end it at 12.0; device time stamps, scripts/r5/pre_stats.sh)
+            const int64_t slots = std::max<int64_t>(1, 2 * (int64_t)ctx->n_cu - other_blocks * ((n_depth + kPreDepths - 1) / kPreDepths));
+            const int64_t fit = ((int64_t)p->cont_tiles * n_depth + slots - 1) / slots;
+            dgs = (int)std::max<int64_t>(dgs, std::min<int64_t>(kContDepths, fit));
         }
-        p->stage_table = ca.table_sigma && ca.n_table > 0 && ca.n_table <= 1024;  // 1-D cross-section table searched from LDS
-        if (p->stage_table) p->shmem = ((ca.bf_n_species > 0 ? (size_t)job->cont->bf_n_levels : 0) + 2 * (size_t)ca.n_table) * sizeof(double);
-        p->cont_tiles = (int)((job->nu_count + (int64_t)threads * kContPoints - 1) / ((int64_t)threads * kContPoints));
-        const size_t n_lev = ca.bf_n_species > 0 ? (size_t)job->cont->bf_n_levels : 0;
-        const size_t tile_shmem = ((size_t)kContDepths * (n_lev + 6) + (p->stage_table ? 2 * (size_t)ca.n_table : 0)) * sizeof(double);
-        p->cont_rows = (unsigned)n_depth;
-        p->tiled = false;
-        if (tile_shmem <= 48 * 1024) {
-            // depths per block: as many as leave ~2 x 1024 threads of such blocks per CU (one depth per block on small grids)
-            int dgs = (int)std::max<int64_t>(1, std::min<int64_t>(kContDepths, ((int64_t)p->cont_tiles * threads / kPreBlock * n_depth) / (2 * (int64_t)ctx->n_cu)));
-            if (threads == kPreBlock) {
-                // ... next to the launch's pre-pass blocks: ALL blocks of the launch in one round of the chip's 2 x n_cu slots of 1024
-                // threads (S-c2: 133 pre-pass blocks + 448 one-depth tiles were 581 on 512 slots — the 69 of the second round ended
-                // the launch at 15.6 us where two depths per tile end it at 12.0; device time stamps, scripts/r5/pre_stats.sh)
-                const int64_t slots = std::max<int64_t>(1, 2 * (int64_t)ctx->n_cu - ((int64_t)n_line_blocks + n_pixel_blocks) * ((n_depth + kPreDepths - 1) / kPreDepths));
-                const int64_t fit = ((int64_t)p->cont_tiles * n_depth + slots - 1) / slots;
-                dgs = (int)std::max<int64_t>(dgs, std::min<int64_t>(kContDepths, fit));
-            }
-            // riding with the classification stream (256-thread blocks) the chip is full anyway: as many depths per block as
-            // there are — the per-frequency work (table search, nu^-3, Rayleigh powers) is then shared by eight points
-            if (threads == kBlock) dgs = kContDepths;
-            p->stage_table |= 2 | (dgs << 4);
-            p->shmem = tile_shmem;
-            p->cont_rows = (unsigned)((n_depth + dgs - 1) / dgs);
-            p->tiled = true;
-        }
-        return SDX_OK;
-    };
-    // The grid plan (sdx_grid_plan): honoured on the un-culled pre-pass of a dense list next to the tiled continuum — the launch then has
-    // no pixel blocks, its line blocks read centres and spacing from the plan and its tiles the per-frequency values
-    // (k_prepass_continuum<false, LINES, true>).  Long grids: the grid-spacing launch stays only where it computes the far ranges.
-    ContPlan planned_cp;
-    bool planned = plan && ctx->grid_plan != 0 && fill_work && !cull && !gen && job && !lo_ref && (pre_lines == 16 || pre_lines == 32);
-    if (planned) {
-        const int pix = n_pixel_blocks;
-        n_pixel_blocks = 0;  // (the tiles are sized for the launch without them)
-        if ((rc = plan_continuum(kPreBlock, &planned_cp))) return rc;
-        planned = planned_cp.tiled;
-        if (!planned) n_pixel_blocks = pix;
-        w.n_pix = n_pixel_blocks;
+        // riding with the classification stream (256-thread blocks) the chip is full anyway: as many depths per block as
+        // there are — the per-frequency work (table search, nu^-3, Rayleigh powers) is then shared by eight points
+        if (threads == kBlock) dgs = kContDepths;
+        p->stage_table |= 2 | (dgs << 4);
+        p->shmem = tile_shmem;
+        p->cont_rows = (unsigned)((n_depth + dgs - 1) / dgs);
+        p->tiled = true;
     }
-    if (planned) {
-        w.cnt_ge = plan->i;
-        w.centre = plan->i + (n_nu + 2);
-        // no table in LDS: the bound-free edges instead
-        const size_t n_lev = planned_cp.ca.bf_n_species > 0 ? (size_t)job->cont->bf_n_levels : 0;
-        planned_cp.shmem = ((size_t)kContDepths * (n_lev + 6) + n_lev) * sizeof(double);
+    return SDX_OK;
+}
+
+// ... and what it gets back (where the caller wants it)
+struct PrepassResult {
+    LineWork w;
+    bool far_ranges;  // a launch has taken the requested far ranges along
+};
+// what line_prepass has decided when it comes to its launches: private to it and its pieces below
+struct PrepassLaunch {
+    LineWork w;
+    bool far_ranges;
+    int pre_lines, n_line_blocks, n_pixel_blocks, n_partial;
+    bool scan_in_block;       // every pre-pass block re-scans a small grid instead of a separate launch
+    const ContPlan* planned;  // the grid plan is honoured, with these continuum tiles; else null
+    bool continuum_done;      // the continuum plane rode with the classification launch
+};
+
+// culled runs: classification stream, the line lists, then ONE pre-pass launch with range + gather blocks.  In the fused
+// step the continuum plane rides with the classification launch — an HBM stream that leaves the vector units idle —
+// instead of the pre-pass launch, which a shard's line blocks already fill (S-c3 / 8: 540 line + gather blocks and 590
+// continuum blocks on 512 block slots)
+static int prepass_culled(sdx_ctx* ctx, const Grid& g, const Lines& l, const PrepassRequest& req, const CntLayout& cnt, PrepassLaunch& s)
+{
+    const int n_depth = g.n_depth;
+    const int64_t n_nu = g.n_nu, n_lines = l.n_lines;
+    const ClassifyPhase* const ph = req.ph;
+    const sdx_continuum* const cont = req.cont;
+    LineWork& w = s.w;
+    int* const sel = (int*)ctx->cnt_ws + cnt.sel;
+    w.sel = sel;
+    // classification blocks: contiguous runs of lines, a few blocks per CU (256 threads: 4 waves x 4 lines x 3 arrays in flight)
+    const int64_t cls_begin = ph && ph->phase == 1 ? ph->begin : 0, cls_end = ph && ph->phase == 1 ? ph->begin + ph->count : n_lines;
+    // (a SHARE of the list — two-collective mode — is a few microseconds of streaming: sixteen lines per block, one trip of each
+    // wave's loop, so that the launch is as long as one round trip and not as a chain of nine; the whole list is a stream that
+    // wants its bytes in flight, not short chains)
+    const bool share = ph && ph->phase == 1;
+    const int64_t cls_per_block = share ? 16 : 64;
+    const unsigned n_cls = (unsigned)std::max<int64_t>(1, std::min<int64_t>((cls_end - cls_begin + cls_per_block - 1) / cls_per_block, (int64_t)8 * ctx->n_cu));
+    // the per-line maxima: doubles behind the integer lists of cnt_ws (8-byte aligned), or the caller's array (two-collective mode)
+    double* const m_max = ph ? ph->m_max : (double*)((int*)ctx->cnt_ws + cnt.m_max);
+    double* const dnu_ws = (double*)ctx->small_ws;
+    ContPlan cp;
+    if (cont) {
+        if (int rc = plan_continuum(ctx, cont, g, kBlock, 0, &cp)) return rc;
+        s.continuum_done = cp.tiled;
     }
-    if (!cull && !scan_in_block && !(planned && !ctx->far_req.count) && (rc = launch_dnu(ctx, n_nu, nus, &n_partial))) return rc;
-    // culled runs: classification stream, the line lists, then ONE pre-pass launch with range + gather blocks.  In the fused
-    // step the continuum plane rides with the classification launch — an HBM stream that leaves the vector units idle —
-    // instead of the pre-pass launch, which a shard's line blocks already fill (S-c3 / 8: 540 line + gather blocks and 590
-    // continuum blocks on 512 block slots)
-    bool continuum_done = false;
-    if (cull) {
-        w.sel = sel;
-        // classification blocks: contiguous runs of lines, a few blocks per CU (256 threads: 4 waves x 4 lines x 3 arrays in flight)
-        const int64_t cls_begin = ph && ph->phase == 1 ? ph->begin : 0, cls_end = ph && ph->phase == 1 ? ph->begin + ph->count : n_lines;
-        // (a SHARE of the list — two-collective mode — is a few microseconds of streaming: sixteen lines per block, one trip of each
-        // wave's loop, so that the launch is as long as one round trip and not as a chain of nine; the whole list is a stream that
-        // wants its bytes in flight, not short chains)
-        const bool share = ph && ph->phase == 1;
-        const int64_t cls_per_block = share ? 16 : 64;
-        const unsigned n_cls = (unsigned)std::max<int64_t>(1, std::min<int64_t>((cls_end - cls_begin + cls_per_block - 1) / cls_per_block, (int64_t)8 * ctx->n_cu));
-        // the per-line maxima: doubles behind the integer lists of cnt_ws (8-byte aligned), or the caller's array (two-collective mode)
-        double* const m_max = ph ? ph->m_max : (double*)(((uintptr_t)(w.hcount + 16 + 3 * ((size_t)n_lines / 1024 + 8)) + 7) & ~(uintptr_t)7);
-        double* const dnu_ws = (double*)ctx->small_ws;
-        ContPlan cp;
-        if (job) {
-            if ((rc = plan_continuum(kBlock, &cp))) return rc;
-            continuum_done = cp.tiled;
-        }
-        if (ph && ph->phase == 2) {
-            // the classification launch ran in phase 1 (sdx_synthesize_classify_dev) and left the grid spacing, `sel` and the
-            // continuum plane in this context's scratch — for THIS problem, and no buffer has moved since
-            const auto& c = ctx->classified;
-            REQUIRE(c.valid && c.n_depth == n_depth && c.n_nu == n_nu && c.nu_begin == nu_begin && c.nu_count == nu_count && c.n_lines == n_lines,
-                    "synthesize: options->line_m_max needs sdx_synthesize_classify_dev on this context first, for the same grid, shard and line list");
-            REQUIRE(c.generation == ctx->ws_generation, "synthesize: the context's scratch was reallocated between sdx_synthesize_classify_dev and the synthesis");
-            REQUIRE(!job || continuum_done, "synthesize: two-collective mode needs the tiled continuum");
-            // consumed: a second phase 2 needs a new phase 1 (the resident inputs may have been updated in place since; a recorded
-            // graph replays both phases without this host check)
-            ctx->classified.valid = false;
+    if (ph && ph->phase == 2) {
+        // the classification launch ran in phase 1 (sdx_synthesize_classify_dev) and left the grid spacing, `sel` and the
+        // continuum plane in this context's scratch — for THIS problem, and no buffer has moved since
+        const auto& c = ctx->classified;
+        REQUIRE(c.valid && c.n_depth == n_depth && c.n_nu == n_nu && c.nu_begin == g.nu_begin && c.nu_count == g.nu_count && c.n_lines == n_lines,
+                "synthesize: options->line_m_max needs sdx_synthesize_classify_dev on this context first, for the same grid, shard and line list");
+        REQUIRE(c.generation == ctx->ws_generation, "synthesize: the context's scratch was reallocated between sdx_synthesize_classify_dev and the synthesis");
+        REQUIRE(!cont || s.continuum_done, "synthesize: two-collective mode needs the tiled continuum");
+        // consumed: a second phase 2 needs a new phase 1 (the resident inputs may have been updated in place since; a recorded
+        // graph replays both phases without this host check)
+        ctx->classified.valid = false;
+    } else {
+        REQUIRE(!ph || !cont || s.continuum_done, "synthesize: two-collective mode needs the tiled continuum (at most 4096 bound-free levels)");
+        LaunchScope ls(ctx, "k_classify");
+        if (s.continuum_done) {
+            // half the classification blocks (16 of 32 wave slots per CU: the stream keeps its bytes in flight), the
+            // continuum blocks take the other slots
+            const unsigned n_cls_half = share ? n_cls : std::max(1u, n_cls / 2);
+            hipLaunchKernelGGL(k_classify_continuum, dim3((unsigned)s.n_partial + n_cls_half + (unsigned)cp.cont_tiles * cp.cont_rows), dim3(kBlock), cp.shmem, ctx->stream,
+                               s.n_partial, (int)n_cls_half, n_depth, n_nu, n_lines, dnu_ws, l.doppler, l.gammas, l.gamma_cols, l.alphas, m_max, g.nus,
+                               cp.cont_tiles, g.nu_begin, g.nu_count, cp.ca, req.cont_plane, g.nu_count, cp.stage_table, l.line_nus, g.nu_begin, g.nu_count,
+                               sel, cls_begin, cls_end, req.far);
         } else {
-            REQUIRE(!ph || !job || continuum_done, "synthesize: two-collective mode needs the tiled continuum (at most 4096 bound-free levels)");
-            LaunchScope ls(ctx, "k_classify");
-            if (continuum_done) {
-                // half the classification blocks (16 of 32 wave slots per CU: the stream keeps its bytes in flight), the
-                // continuum blocks take the other slots
-                const unsigned n_cls_half = share ? n_cls : std::max(1u, n_cls / 2);
-                hipLaunchKernelGGL(k_classify_continuum, dim3((unsigned)n_partial + n_cls_half + (unsigned)cp.cont_tiles * cp.cont_rows), dim3(kBlock), cp.shmem, ctx->stream,
-                                   n_partial, (int)n_cls_half, n_depth, n_nu, n_lines, dnu_ws, doppler, gammas, gamma_cols, alphas, m_max, nus,
-                                   cp.cont_tiles, job->nu_begin, job->nu_count, cp.ca, job->plane, job->nu_count, cp.stage_table, line_nus, nu_begin, nu_count,
-                                   sel, cls_begin, cls_end, ctx->far_req);
-            } else {
-                hipLaunchKernelGGL(k_classify, dim3((unsigned)n_partial + n_cls), dim3(kBlock), 0, ctx->stream, n_partial, n_depth, n_nu, n_lines, dnu_ws,
-                                   doppler, gammas, gamma_cols, alphas, m_max, nus, line_nus, nu_begin, nu_count, sel, cls_begin, cls_end, ctx->far_req);
-            }
-            if (ctx->far_req.count && n_partial > 0) ctx->far_req_done = true;
+            hipLaunchKernelGGL(k_classify, dim3((unsigned)s.n_partial + n_cls), dim3(kBlock), 0, ctx->stream, s.n_partial, n_depth, n_nu, n_lines, dnu_ws,
+                               l.doppler, l.gammas, l.gamma_cols, l.alphas, m_max, g.nus, l.line_nus, g.nu_begin, g.nu_count, sel, cls_begin, cls_end, req.far);
         }
-        if (ph && ph->phase == 1) {
-            auto& c = ctx->classified;
-            c.valid = true, c.n_depth = n_depth, c.n_nu = n_nu, c.nu_begin = nu_begin, c.nu_count = nu_count, c.n_lines = n_lines;
-            c.far_ranges = ctx->far_req_done;
-            c.far = far_field_on(ctx, n_nu) && c.far_ranges;
-            c.generation = ctx->ws_generation;
-            return check_launch("k_classify");
-        }
-        // the pre-pass launch that follows draws its items from a counter (k_line_prepass_ticket); the list launch zeroes it
-        // (worth it where the candidates are many: at 1e6 lines 57 000 of 62 000 candidate blocks are empty and the launch takes 245
-        // instead of 292 us on an eighth of the grid; at 1.5e5 lines 9 500 candidates cost less than the counter's round trips)
-        const bool ticket = !(job && !continuum_done) && !gen && !lo_ref && n_line_blocks >= ctx->prepass_ticket_min_blocks;
-        if (ticket) w.ticket = (int*)((char*)ctx->small_ws + 2064);
-        {
-            LaunchScope ls(ctx, "k_hlist");
-            ClassSource cs{};
-            cs.m_max = m_max, cs.dnu_partial = dnu_ws, cs.n_partial = n_partial, cs.n_nu = n_nu;
-            launch_line_lists(ctx, n_lines, w, pre_lines, &cs);
-        }
-        w.gather = n_line_blocks;  // worst case: every line listed; blocks beyond the lists' end return at once
-        w.front = 1;
+        if (req.far.count && s.n_partial > 0) s.far_ranges = true;
     }
-    const dim3 grid((unsigned)(n_line_blocks + n_pixel_blocks + w.gather), (unsigned)((n_depth + kPreDepths - 1) / kPreDepths));
+    if (ph && ph->phase == 1) {
+        auto& c = ctx->classified;
+        c.valid = true, c.n_depth = n_depth, c.n_nu = n_nu, c.nu_begin = g.nu_begin, c.nu_count = g.nu_count, c.n_lines = n_lines;
+        c.far_ranges = s.far_ranges;
+        c.far = far_field_on(ctx, n_nu) && c.far_ranges;
+        c.generation = ctx->ws_generation;
+        return check_launch("k_classify");
+    }
+    // the pre-pass launch that follows draws its items from a counter (k_line_prepass_ticket); the list launch zeroes it
+    // (worth it where the candidates are many: at 1e6 lines 57 000 of 62 000 candidate blocks are empty and the launch takes 245
+    // instead of 292 us on an eighth of the grid; at 1.5e5 lines 9 500 candidates cost less than the counter's round trips)
+    const bool ticket = !(cont && !s.continuum_done) && !l.gen && !req.lo_ref && s.n_line_blocks >= ctx->prepass_ticket_min_blocks;
+    if (ticket) w.ticket = (int*)((char*)ctx->small_ws + kTicketOffset);
+    {
+        LaunchScope ls(ctx, "k_hlist");
+        ClassSource cs{};
+        cs.m_max = m_max, cs.dnu_partial = dnu_ws, cs.n_partial = s.n_partial, cs.n_nu = n_nu;
+        launch_line_lists(ctx, cnt, w, s.pre_lines, &cs);
+    }
+    w.gather = s.n_line_blocks;  // worst case: every line listed; blocks beyond the lists' end return at once
+    w.front = 1;
+    return SDX_OK;
+}
+
+// the pre-pass launch itself: line, pixel and gather blocks, with the continuum tiles behind them unless the classification launch took them
+static int prepass_launch(sdx_ctx* ctx, const Grid& g, const Lines& l, const PrepassRequest& req, PrepassLaunch& s)
+{
+    const int n_depth = g.n_depth, pre_lines = s.pre_lines, n_line_blocks = s.n_line_blocks, n_partial = s.n_partial;
+    const int64_t n_nu = g.n_nu, n_lines = l.n_lines;
+    const sdx_continuum* const cont = req.cont;
+    const bool planned = s.planned != nullptr, scan_in_block = s.scan_in_block;
+    const LineParams* const gen = l.gen;
+    const LineParams lp = gen ? *gen : LineParams{};
+    LineWork& w = s.w;
+    const dim3 grid((unsigned)(n_line_blocks + s.n_pixel_blocks + w.gather), (unsigned)((n_depth + kPreDepths - 1) / kPreDepths));
     const bool ticket_launch = w.ticket != nullptr;  // (the counter-driven launch of a culled shard)
     if (w.n_csplit) w.ticket = (int*)((char*)ctx->small_ws + kListTicketOffset);
-    if (job && !continuum_done) {
+    if (cont && !s.continuum_done) {
         ContPlan cp;
-        if (planned) cp = planned_cp;
-        else if ((rc = plan_continuum(kPreBlock, &cp))) return rc;
+        if (planned) cp = *s.planned;
+        else if (int rc = plan_continuum(ctx, cont, g, kPreBlock, (int64_t)n_line_blocks + s.n_pixel_blocks, &cp)) return rc;
         const ContinuumArgs& ca = cp.ca;
         const int cont_tiles = cp.cont_tiles, stage_table = cp.stage_table;
         const size_t shmem = cp.shmem;
         const unsigned total_blocks = grid.x * grid.y + (unsigned)cont_tiles * cp.cont_rows;
         {
         LaunchScope ls(ctx, "k_prepass_continuum", planned ? (w.n_csplit ? "planned + wide-line list" : "planned") : (w.n_csplit ? "+ wide-line list" : nullptr));
-#define SDX_PRE_ARGS (int)grid.x, (int)grid.y, cont_tiles, n_depth, n_nu, nus,                                                                     \
-                     planned ? (const double*)plan->d : (scan_in_block ? (const double*)nullptr : (const double*)ctx->small_ws),                \
-                     n_partial, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, w, n_line_blocks, job->nu_begin, job->nu_count, ca,          \
-                     job->plane, job->nu_count, lp, stage_table
+#define SDX_PRE_ARGS (int)grid.x, (int)grid.y, cont_tiles, n_depth, n_nu, g.nus,                                                                   \
+                     planned ? (const double*)req.plan->d : (scan_in_block ? (const double*)nullptr : (const double*)ctx->small_ws),            \
+                     n_partial, n_lines, l.line_nus, l.doppler, l.gammas, l.gamma_cols, l.alphas, w, n_line_blocks, g.nu_begin, g.nu_count, ca, \
+                     req.cont_plane, g.nu_count, lp, stage_table
         if (planned && pre_lines == 16) hipLaunchKernelGGL((k_prepass_continuum<false, 16, true>), dim3(total_blocks), dim3(kPreBlock), shmem, ctx->stream, SDX_PRE_ARGS);
         else if (planned) hipLaunchKernelGGL((k_prepass_continuum<false, 32, true>), dim3(total_blocks), dim3(kPreBlock), shmem, ctx->stream, SDX_PRE_ARGS);
         else if (gen && pre_lines == 16) hipLaunchKernelGGL((k_prepass_continuum<true, 16>), dim3(total_blocks), dim3(kPreBlock), shmem, ctx->stream, SDX_PRE_ARGS);
@@ -1217,13 +1180,13 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
 #undef SDX_PRE_ARGS
         }
     } else {
-        LaunchScope ls(ctx, job ? "k_prepass_continuum" : "k_line_prepass", w.n_csplit ? "+ wide-line list" : nullptr);
-#define SDX_PRE_ARGS n_depth, n_nu, nus, scan_in_block ? (const double*)nullptr : (const double*)ctx->small_ws, n_partial, n_lines, line_nus, doppler, \
-                     gammas, gamma_cols, alphas, w, (int*)lo_ref, (int*)hi_ref, n_line_blocks, lp
+        LaunchScope ls(ctx, cont ? "k_prepass_continuum" : "k_line_prepass", w.n_csplit ? "+ wide-line list" : nullptr);
+#define SDX_PRE_ARGS n_depth, n_nu, g.nus, scan_in_block ? (const double*)nullptr : (const double*)ctx->small_ws, n_partial, n_lines, l.line_nus, l.doppler, \
+                     l.gammas, l.gamma_cols, l.alphas, w, (int*)req.lo_ref, (int*)req.hi_ref, n_line_blocks, lp
         if (ticket_launch) {
             const dim3 pgrid(std::min<unsigned>(grid.x, 2u * (unsigned)ctx->n_cu), grid.y);
             const double* dnu_arg = scan_in_block ? (const double*)nullptr : (const double*)ctx->small_ws;
-#define SDX_TICKET_ARGS n_depth, n_nu, nus, dnu_arg, n_partial, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, w, n_line_blocks, lp
+#define SDX_TICKET_ARGS n_depth, n_nu, g.nus, dnu_arg, n_partial, n_lines, l.line_nus, l.doppler, l.gammas, l.gamma_cols, l.alphas, w, n_line_blocks, lp
             if (pre_lines == 16) hipLaunchKernelGGL((k_line_prepass_ticket<16>), pgrid, dim3(kPreBlock), 0, ctx->stream, SDX_TICKET_ARGS);
             else if (pre_lines == 48) hipLaunchKernelGGL((k_line_prepass_ticket<48>), pgrid, dim3(kPreBlock), 0, ctx->stream, SDX_TICKET_ARGS);
             else if (pre_lines == 54) hipLaunchKernelGGL((k_line_prepass_ticket<54>), pgrid, dim3(kPreBlock), 0, ctx->stream, SDX_TICKET_ARGS);
@@ -1237,8 +1200,121 @@ static int line_prepass(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* n
         else hipLaunchKernelGGL((k_line_prepass<false, 32>), grid, dim3(kPreBlock), 0, ctx->stream, SDX_PRE_ARGS);
 #undef SDX_PRE_ARGS
     }
-    if (w_out) *w_out = w;
     return check_launch("k_line_prepass");
+}
+
+// decides lines per block, culling, a short list's wide-line list, raw narrow records and the planned continuum; then its launches
+static int line_prepass(sdx_ctx* ctx, const Grid& g, const Lines& l, const PrepassRequest& req, PrepassResult* out)
+{
+    PrepassLaunch s{};
+    const int n_depth = g.n_depth;
+    const int64_t n_nu = g.n_nu, n_lines = l.n_lines;
+    const bool fill_work = !req.lo_ref;
+    // every pre-pass rewrites the scratch a two-collective phase 1 leaves for its phase 2 (grid spacing, line ranges, lists): only the
+    // phase 2 that consumes it may find it valid (phase 1 sets the flag again when its launch is enqueued)
+    const bool consumes_classified = req.ph && req.ph->phase == 2;
+    if (!consumes_classified) ctx->classified.valid = false;
+    int rc = ensure_small(ctx, kSmallHeader);
+    if (rc) return rc;
+    LineWork& w = s.w;
+    s.scan_in_block = n_nu <= 16384;
+    // 16 lines per block while all such blocks are resident at once (two 1024-thread blocks per CU), else 32
+    s.pre_lines = ((n_lines + 15) / 16) * ((n_depth + kPreDepths - 1) / kPreDepths) <= 2 * (int64_t)ctx->n_cu ? 16 : 32;
+    // A culled shard (`cull`, see below) prepares its own line range + the listed lines: at an eighth of 1.5e5
+    // lines ~22 000 lines, 690 blocks of 32 on the chip's 512 slots of 1024 threads — a whole second round of the block's chain of
+    // round trips for a third of a round's work.  48 lines per block (three items per thread, registers only) are 470 blocks:
+    // ONE round, a chain one item longer.
+    const bool cull = fill_work && n_lines >= ctx->indexed_min_lines && !req.count_evals && !l.gen && !s.scan_in_block && g.nu_count < n_nu;
+    // (lists long enough for the counter-driven launch keep 32: its looping kernel has no registers to spare for a third item)
+    // (54 when the model has at most 56 depth points — every MARCS model — and three items per thread still cover the block)
+    if (cull && !req.lo_ref && (n_lines + 31) / 32 < ctx->prepass_ticket_min_blocks)
+        s.pre_lines = n_depth <= 56 ? 54 : 48;
+    s.n_line_blocks = (int)((n_lines + s.pre_lines - 1) / s.pre_lines);
+    const CntLayout cnt(n_nu, n_lines);
+    if (fill_work) {
+        rc = ensure(ctx, &ctx->line_ws, &ctx->line_ws_bytes, line_ws_need(n_depth, n_lines));
+        if (rc) return rc;
+        rc = ensure(ctx, &ctx->cnt_ws, &ctx->cnt_ws_bytes, cnt.bytes);
+        if (rc) return rc;
+        w = carve(ctx, n_depth, n_lines, cnt);
+        if (n_depth > kPreDepths) HIP_TRY(hipMemsetAsync(w.nhw_max, 0, (size_t)2 * n_lines * sizeof(int), ctx->stream));  // nhw_max and whw_max
+        if (req.count_evals) HIP_TRY(hipMemsetAsync(w.evals, 0, sizeof(unsigned long long), ctx->stream));
+        else w.evals = nullptr;
+        s.n_pixel_blocks = (int)((n_nu + 2 + kPreBlock - 1) / kPreBlock);
+    }
+    // SHORT lists (never culled, no list launches): the last line block of the pre-pass launch to finish lists the lines with a wide
+    // window per line subset of the wide role (LineWork::n_csplit; in the space long lists keep hlist in, the counts and offsets where
+    // the list launches keep their per-block counts) and the wide role walks that list instead of every line.  Same hits in the
+    // same order: scheduling only (context option "wide_list").  Not in the mixed-precision mode, whose fp32 sums are flushed into
+    // the fp64 sums at chunk boundaries: other chunks would move those roundings.
+    // Automatic rule: from kListAutoChunks chunks of 64 lines per subset on.  Measured (profiles/EXPERIMENTS.md, "Short lists walk a
+    // list of their wide lines"): at S-c2 (16 chunks per subset, 2 listed) the line kernel runs 1.2 us faster and the list is built in
+    // the shadow of the launch's continuum tiles; at S-c1 (4 per subset, 1 listed) the line kernel gains nothing and the last block's
+    // 3 us show at the end of a pre-pass launch whose continuum tiles are done before its line blocks.
+    const int wide_splits = req.wide_splits;
+    const int64_t chunks_per_subset = wide_splits > 0 ? ((n_lines + 63) / 64 + wide_splits - 1) / wide_splits : 0;
+    if (fill_work && wide_splits > 0 && (ctx->wide_list == 1 || (ctx->wide_list < 0 && chunks_per_subset >= kListAutoChunks)) &&
+        !ctx->mixed_precision && n_lines > 0 && n_lines < ctx->indexed_min_lines && (n_lines + 63) / 64 <= kListMaxChunks) {
+        w.n_csplit = wide_splits;  // (its counter of finished line blocks: `ticket`, set where the launch is enqueued)
+    }
+    // VERY dense long fp64 lists (>= 4 lines per grid point: the rule of the narrow role's subsets): no narrow records — the narrow role
+    // reads the caller's three tables itself (LineWork::narrow_raw).  Pure scheduling (the same three operations form 1 / dw, y and the
+    // amplitude either way).  Measured in round 6 (profiles/r06_raw.txt): 1e6 lines on 120 398 points — pre-pass 904 -> 721 us (a stream:
+    // 2.13 GB of traffic counted, 1.31 GB of it these records), line kernel 5.93 -> 6.07 ms (ten more instructions per evaluated line), step
+    // 7.27 -> 7.24 ms and 1.35 GB less scratch; 1.5e5 lines: pre-pass 165 -> 149 us, line kernel 1.218 -> 1.241 ms, the step 7 us SLOWER —
+    // hence the density in the rule.
+    const int narrow_records = (int)ctx->narrow_records;  // (context option: -1 by this rule, 0 never, 1 always)
+    const bool very_dense = 2 * n_lines >= 8 * n_nu;
+    if (fill_work && !l.gen && !ctx->mixed_precision && n_lines >= ctx->indexed_min_lines && (narrow_records == 0 || (very_dense && narrow_records != 1))) {
+        w.narrow_raw = l.gamma_cols > 1 ? n_depth : 1;
+        w.n_inv = const_cast<double*>(l.doppler);
+        w.n_y = const_cast<double*>(l.gammas);
+        w.n_amp = const_cast<double*>(l.alphas);
+    }
+    // long lists find their wide lines through hlist / wlist: the scan words of a line without a wide window anywhere are never
+    // read (needs the line's widest window inside one block: one depth block per line)
+    w.skip_unlisted_scan = (fill_work && n_lines >= ctx->indexed_min_lines && n_depth <= kPreDepths) ? 1 : 0;
+    w.n_pix = s.n_pixel_blocks;
+    w.shard_begin = g.nu_begin;
+    w.shard_end = g.nu_begin + g.nu_count;
+    // A frequency shard of a long list does not need every line prepared: a streaming classification pass finds the lines
+    // that can reach any column (-> hlist), the full pre-pass then runs on the lines centred near the shard plus those.
+    // Everything is decided on the device (no host round trip, graph-capturable); which lines a shard prepares does not
+    // change what it computes for them.  (`cull`, above)
+    REQUIRE(!req.ph || cull, "two-collective mode is for frequency shards of long dense line lists (>= indexed_min_lines lines, a grid of more than "
+                             "16384 points, nu_count < n_nu, no evaluation count)");
+    // the grid-spacing reduction: a launch of its own, or — culled runs — the first blocks of the classification launch
+    // (grid-spacing blocks of a classification launch: four pairs of loads per thread — one trip of their loop — up to 256 blocks)
+    if (cull) s.n_partial = (int)std::min<int64_t>(kDnuPartials, std::max<int64_t>(1, (n_nu + kBlock * 4 - 1) / (kBlock * 4)));
+    // The grid plan (sdx_grid_plan): honoured on the un-culled pre-pass of a dense list next to the tiled continuum — the launch then has
+    // no pixel blocks, its line blocks read centres and spacing from the plan and its tiles the per-frequency values
+    // (k_prepass_continuum<false, LINES, true>).  Long grids: the grid-spacing launch stays only where it computes the far ranges.
+    ContPlan planned_cp;
+    bool planned = req.plan && ctx->grid_plan != 0 && fill_work && !cull && !l.gen && req.cont && !req.lo_ref && (s.pre_lines == 16 || s.pre_lines == 32);
+    if (planned) {
+        const int pix = s.n_pixel_blocks;
+        s.n_pixel_blocks = 0;  // (the tiles are sized for the launch without them)
+        if ((rc = plan_continuum(ctx, req.cont, g, kPreBlock, s.n_line_blocks, &planned_cp))) return rc;
+        planned = planned_cp.tiled;
+        if (!planned) s.n_pixel_blocks = pix;
+        w.n_pix = s.n_pixel_blocks;
+    }
+    if (planned) {
+        w.cnt_ge = req.plan->i;
+        w.centre = req.plan->i + (n_nu + 2);
+        // no table in LDS: the bound-free edges instead
+        const size_t n_lev = planned_cp.ca.bf_n_species > 0 ? (size_t)req.cont->bf_n_levels : 0;
+        planned_cp.shmem = ((size_t)kContDepths * (n_lev + 6) + n_lev) * sizeof(double);
+        s.planned = &planned_cp;
+    }
+    if (!cull && !s.scan_in_block && !(planned && !req.far.count)) {
+        if ((rc = launch_dnu(ctx, n_nu, g.nus, &s.n_partial, req.far))) return rc;
+        if (req.far.count) s.far_ranges = true;
+    }
+    if (cull && (rc = prepass_culled(ctx, g, l, req, cnt, s))) return rc;
+    if (!(req.ph && req.ph->phase == 1) && (rc = prepass_launch(ctx, g, l, req, s))) return rc;  // (phase 1 ends behind its classification launch)
+    if (out) *out = PrepassResult{s.w, s.far_ranges};
+    return SDX_OK;
 }
 
 static int check_line_args(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines,
@@ -1271,61 +1347,52 @@ static int choose_splits(int n_depth, int64_t n_nu_global, int64_t n_lines, int 
     return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, chunks), 8));  // the subsets are the waves of one workgroup
 }
 
-// FAR FIELD (line_far_body, the far role of the line kernels): a third plane.  Like every choice that moves a rounding it is made from the GLOBAL grid — grids of at
-// least kFarMinPoints frequencies (below that a launch of the line kernel is bound by latency, not by its evaluations) — or set
-// explicitly (context option "far_field").
-constexpr int64_t kFarMinPoints = 32768;
-static_assert(kFarMinPoints == 32768, "sdx_far_field_rule reports this constant");
-static bool far_field_on(const sdx_ctx* ctx, int64_t n_nu_global)
+// The (ihi, ilo) pair of every GLOBAL tile that holds columns of the launch: the request a step hands to its pre-pass, whose grid-spacing
+// launch (launch_dnu, the classification launch of a culled shard) computes them on the side.
+static int far_request(sdx_ctx* ctx, const Grid& g, FarReq* req)
 {
-    const int far_mode = (int)ctx->far_field;  // (context option: -1 by the rule, 0 never, 1 whenever possible)
-    return far_mode != 0 && (far_mode == 1 || n_nu_global >= kFarMinPoints);
-}
-// The (ihi, ilo) pair of every GLOBAL tile that holds columns of the launch: asked of the step's grid-spacing launch (launch_dnu, the
-// classification launch of a culled shard), which computes them on the side.
-static int request_far_ranges(sdx_ctx* ctx, int64_t n_nu, int64_t nu_begin, int64_t nu_count)
-{
-    int rc = ensure(ctx, &ctx->far_ws, &ctx->far_ws_bytes, (size_t)((n_nu + kFarTile - 1) / kFarTile) * 2 * sizeof(int));
+    int rc = ensure(ctx, &ctx->far_ws, &ctx->far_ws_bytes, (size_t)((g.n_nu + kFarTile - 1) / kFarTile) * 2 * sizeof(int));
     if (rc) return rc;
-    const int64_t t_first = nu_begin / kFarTile, t_last = (nu_begin + nu_count - 1) / kFarTile;
-    ctx->far_req = FarReq{(int*)ctx->far_ws, t_first, t_last - t_first + 1};
-    ctx->far_req_done = false;
+    const int64_t t_first = g.nu_begin / kFarTile, t_last = (g.nu_begin + g.nu_count - 1) / kFarTile;
+    *req = FarReq{(int*)ctx->far_ws, t_first, t_last - t_first + 1};
     return SDX_OK;
 }
 
-// pre-pass + the two gather kernels; leaves *n_planes_out partial planes in *partial_out ([planes][n_depth][*pld_out]):
-// the wide subsets in subset order, then the narrow-window plane.  With `job` the continuum plane of the fused step is
-// computed by the same launch as the pre-pass.
-static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
-                         int64_t n_lines, const double* line_nus, const double* doppler, const double* gammas, int gamma_cols,
-                         const double* alphas, const double** partial_out, int64_t* pld_out, int* n_planes_out, LineWork* w_out,
-                         bool count_evals, const ContinuumJob* job = nullptr, const LineParams* gen = nullptr, const ClassifyPhase* ph = nullptr,
-                         const sdx_grid_plan* plan = nullptr)
+// pre-pass + the two gather kernels; leaves n_planes partial planes in part ([planes][n_depth][pld]): the wide subsets in subset order,
+// then the narrow-window plane.  With req.cont the continuum plane of the fused step is computed by the same launch as the pre-pass.
+// (req: count_evals, cont, ph and plan as the caller wants them; the far ranges and the line subsets are asked for here)
+struct LinePlanes {
+    const double* part;
+    int64_t pld;
+    int n_planes;
+    LineWork w;
+};
+static int line_partials(sdx_ctx* ctx, const Grid& grid, const Lines& lines, PrepassRequest req, LinePlanes* out)
 {
+    const int n_depth = grid.n_depth;
+    const int64_t n_nu = grid.n_nu, nu_begin = grid.nu_begin, nu_count = grid.nu_count, n_lines = lines.n_lines;
+    const double *const nus = grid.nus, *const line_nus = lines.line_nus;
     // grid points per lane of a wide-role tile (tile = 64 R points), in every mode (fp32 far wings with 8 — twice the points per fetched
     // record — were measured slower: fewer tiles qualify as far wing)
     constexpr int R = 4;
     const bool far = far_field_on(ctx, n_nu) && nu_count > 0;
     int rc;
     // (phase 1 computed the ranges — with the far field on then; if the option was switched on in between, k_far_ranges below does it)
-    const bool classified_far = ph && ph->phase == 2 && ctx->classified.valid && ctx->classified.far && ctx->classified.far_ranges;
-    if (far && !classified_far && (rc = request_far_ranges(ctx, n_nu, nu_begin, nu_count))) return rc;
-    LineWork w;
+    const bool classified_far = req.ph && req.ph->phase == 2 && ctx->classified.valid && ctx->classified.far && ctx->classified.far_ranges;
+    if (far && !classified_far && (rc = far_request(ctx, grid, &req.far))) return rc;
     // (the number of line subsets depends on the global grid and the list alone; the pre-pass of a short list sorts its wide lines by it)
-    const int n_split = choose_splits(n_depth, n_nu, n_lines, R, n_lines >= ctx->indexed_min_lines ? 4 : 2);
-    rc = line_prepass(ctx, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, true, nullptr, nullptr, &w,
-                      count_evals, job, gen, nu_begin, nu_count, ph, n_split, plan);
-    const FarReq far_req = ctx->far_req;
-    const bool far_req_done = ctx->far_req_done || classified_far;
-    ctx->far_req = FarReq{nullptr, 0, 0};
-    if (rc) return rc;
+    const int n_split = req.wide_splits = choose_splits(n_depth, n_nu, n_lines, R, n_lines >= ctx->indexed_min_lines ? 4 : 2);
+    PrepassResult pre;
+    if ((rc = line_prepass(ctx, grid, lines, req, &pre))) return rc;
+    LineWork& w = pre.w;
+    const bool far_ranges_done = pre.far_ranges || classified_far;  // else k_far_ranges below computes them
     // long line lists: the lines with a window wider than kMediumHalfWidth are listed once (they are scanned by every tile);
     // all others are found by centre range.  Short lists are scanned completely, or — where the pre-pass has listed their wide lines
     // (LineWork::n_csplit, option "wide_list") — through that list: no further launch either way.
     const int indexed = n_lines >= ctx->indexed_min_lines ? 1 : 0;
     if (indexed && !w.hlist) {  // (a culled pre-pass has built the lists already)
         LaunchScope ls(ctx, "k_hlist");
-        launch_line_lists(ctx, n_lines, w, 32);
+        launch_line_lists(ctx, CntLayout(n_nu, n_lines), w, 32, nullptr);
     }
     if (indexed && !w.sel) {  // the huge lines' scan words in list order (a culled pre-pass has written them itself)
         LaunchScope ls(ctx, "k_hlist");
@@ -1339,9 +1406,9 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     // shallowest layer, and a launch is bound by its total work, not by its heaviest wave.  Removed.)
     w.far_range = nullptr;
     if (far) {
-        if (!far_req_done) {  // (no grid-spacing launch in this step: small grids scan the spacing inside the pre-pass blocks)
+        if (!far_ranges_done) {  // (no grid-spacing launch in this step: small grids scan the spacing inside the pre-pass blocks)
             LaunchScope ls(ctx, "k_far_ranges");
-            hipLaunchKernelGGL(k_far_ranges, dim3((unsigned)((2 * far_req.count + kBlock / 16 - 1) / (kBlock / 16))), dim3(kBlock), 0, ctx->stream, n_nu, nus, far_req);
+            hipLaunchKernelGGL(k_far_ranges, dim3((unsigned)((2 * req.far.count + kBlock / 16 - 1) / (kBlock / 16))), dim3(kBlock), 0, ctx->stream, n_nu, nus, req.far);
         }
         w.far_range = (const int*)ctx->far_ws;
     }
@@ -1423,43 +1490,36 @@ static int line_partials(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
 #undef SDX_LINE_FAR_ARGS
 #undef SDX_LINE_TAIL
     }
-    *partial_out = part;
-    *pld_out = pld;
-    *n_planes_out = far ? 3 : 2;
-    if (w_out) *w_out = w;
+    *out = LinePlanes{part, pld, far ? 3 : 2, w};
     return check_launch("line kernels");
 }
 
-static int line_opacity_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
-                            int64_t n_lines, const double* line_nus, const double* doppler, const double* gammas,
-                            int gamma_cols, const double* alphas, double* out, int64_t out_ld, int accumulate,
-                            int64_t* n_evaluations_dev, const LineParams* gen)
+static int line_opacity_impl(sdx_ctx* ctx, const Grid& g, const Lines& lines, double* out, int64_t out_ld, int accumulate, int64_t* n_evaluations_dev)
 {
     int rc;
-    REQUIRE(nu_begin >= 0 && nu_count >= 0 && nu_begin + nu_count <= n_nu, "line opacity: shard outside the grid");
+    const int n_depth = g.n_depth;
+    const int64_t nu_count = g.nu_count;
+    REQUIRE(g.nu_begin >= 0 && nu_count >= 0 && g.nu_begin + nu_count <= g.n_nu, "line opacity: shard outside the grid");
     REQUIRE(nu_count == 0 || (out && out_ld >= nu_count), "line opacity: bad output buffer");
     if (nu_count == 0) return SDX_OK;
-    if (n_lines == 0) {
+    if (lines.n_lines == 0) {
         if (!accumulate) HIP_TRY(hipMemset2DAsync(out, out_ld * sizeof(double), 0, nu_count * sizeof(double), n_depth, ctx->stream));
         if (n_evaluations_dev) HIP_TRY(hipMemsetAsync(n_evaluations_dev, 0, sizeof(int64_t), ctx->stream));
         return SDX_OK;
     }
-    const double* part;
-    int64_t pld;
-    int n_split;
-    LineWork w;
-    rc = line_partials(ctx, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, &part, &pld,
-                       &n_split, &w, n_evaluations_dev != nullptr, nullptr, gen);
-    if (rc) return rc;
+    PrepassRequest req{};
+    req.count_evals = n_evaluations_dev != nullptr;
+    LinePlanes p;
+    if ((rc = line_partials(ctx, g, lines, req, &p))) return rc;
     {
         LaunchScope ls(ctx, "k_reduce_partials");
-        hipLaunchKernelGGL(k_reduce_partials, grid2(nu_count, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, nu_count, n_split,
-                           part, pld, out, out_ld, accumulate);
+        hipLaunchKernelGGL(k_reduce_partials, grid2(nu_count, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, nu_count, p.n_planes,
+                           p.part, p.pld, out, out_ld, accumulate);
     }
     rc = check_launch("k_reduce_partials");
     if (rc) return rc;
     if (n_evaluations_dev)
-        HIP_TRY(hipMemcpyAsync(n_evaluations_dev, w.evals, sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(n_evaluations_dev, p.w.evals, sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream));
     return SDX_OK;
 }
 
@@ -1470,16 +1530,18 @@ int sdx_line_opacity_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
 {
     int rc = check_line_args(ctx, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas);
     if (rc) return rc;
-    return line_opacity_impl(ctx, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, out, out_ld,
-                             accumulate, n_evaluations_dev, nullptr);
+    return line_opacity_impl(ctx, Grid{n_depth, n_nu, nus, nu_begin, nu_count}, Lines{n_lines, line_nus, doppler, gammas, gamma_cols, alphas, nullptr}, out,
+                             out_ld, accumulate, n_evaluations_dev);
 }
 
-// ---- line parameters generated on the device
-static int to_line_params(const sdx_linelist* ll, int n_depth, LineParams* lp)
+// ---- line parameters generated on the device: an sdx_linelist as the line kernels' description (*lp) and as the lines
+// of a call — no dense tables, generated from *lp, which must outlive *lines; gammas in n_depth columns or one
+static int to_line_params(const sdx_linelist* ll, int n_depth, LineParams* lp, Lines* lines)
 {
     REQUIRE(ll, "line list: null description");
     REQUIRE(ll->n_lines >= 0 && ll->n_lines < (int64_t)2147483647 && n_depth > 0, "line list: bad sizes (n_lines must fit int32)");
     REQUIRE(ll->gamma_mode >= 0 && ll->gamma_mode <= 3, "line list: gamma_mode must be 0..3");
+    *lines = Lines{ll->n_lines, ll->nu, nullptr, nullptr, ll->gamma_mode >= 2 ? 1 : n_depth, nullptr, lp};
     if (ll->n_lines == 0) return SDX_OK;
     REQUIRE(ll->nu && ll->e_low_ev && ll->strength && ll->pop_row && ll->pop && ll->mass && ll->temperature,
             "line list: null alpha_line / doppler inputs");
@@ -1519,13 +1581,14 @@ int sdx_line_params_dev(sdx_ctx* ctx, int n_depth, const sdx_linelist* ll, doubl
 {
     REQUIRE(ctx, "null context");
     LineParams lp{};
-    int rc = to_line_params(ll, n_depth, &lp);
+    Lines l;
+    int rc = to_line_params(ll, n_depth, &lp, &l);
     if (rc) return rc;
-    if (ll->n_lines == 0) return SDX_OK;
+    if (l.n_lines == 0) return SDX_OK;
     {
         LaunchScope ls(ctx, "k_line_params");
-        hipLaunchKernelGGL(k_line_params, dim3(blocks1(ll->n_lines * n_depth)), dim3(kBlock), 0, ctx->stream, ll->n_lines, n_depth, ll->nu,
-                           lp, alphas, gammas, ll->gamma_mode >= 2 ? 1 : n_depth, doppler);
+        hipLaunchKernelGGL(k_line_params, dim3(blocks1(l.n_lines * n_depth)), dim3(kBlock), 0, ctx->stream, l.n_lines, n_depth, l.line_nus,
+                           lp, alphas, gammas, l.gamma_cols, doppler);
     }
     return check_launch("k_line_params");
 }
@@ -1552,10 +1615,10 @@ int sdx_line_opacity_linelist_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const
     REQUIRE(n_depth > 0 && n_nu >= 0 && n_nu < (int64_t)2147483647, "line opacity: bad sizes");
     REQUIRE(n_nu == 0 || nus, "line opacity: null frequency grid");
     LineParams lp{};
-    int rc = to_line_params(ll, n_depth, &lp);
+    Lines lines;
+    int rc = to_line_params(ll, n_depth, &lp, &lines);
     if (rc) return rc;
-    return line_opacity_impl(ctx, n_depth, n_nu, nus, nu_begin, nu_count, ll->n_lines, ll->nu, nullptr, nullptr,
-                             ll->gamma_mode >= 2 ? 1 : n_depth, nullptr, out, out_ld, accumulate, n_evaluations_dev, &lp);
+    return line_opacity_impl(ctx, Grid{n_depth, n_nu, nus, nu_begin, nu_count}, lines, out, out_ld, accumulate, n_evaluations_dev);
 }
 
 int sdx_line_windows_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus,
@@ -1566,8 +1629,9 @@ int sdx_line_windows_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     if (rc) return rc;
     REQUIRE(n_lines == 0 || (lower && upper), "line windows: null output");
     if (n_lines == 0) return SDX_OK;
-    return line_prepass(ctx, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, false, lower, upper,
-                        nullptr);
+    PrepassRequest req{};  // no continuum, no far ranges
+    req.lo_ref = lower, req.hi_ref = upper, req.count_evals = true;
+    return line_prepass(ctx, Grid{n_depth, n_nu, nus, 0, n_nu}, Lines{n_lines, line_nus, doppler, gammas, gamma_cols, alphas, nullptr}, req, nullptr);
 }
 
 // Host-pointer (*_f64) entry points — what a numpy caller (the reference's calc_alpha_line_at_nu, base.py:432-439) binds.
@@ -1698,11 +1762,14 @@ static int host_grid_check(int64_t n_nu, const double* nus)
 
 // The kernels take the line list in ascending frequency (calc_alpha_line_at_nu sorts it, base.py:392-397): cnt_ge is a
 // binary search over line_nus and the narrow role walks a contiguous index range per frequency.
-static int host_lines_check(int64_t n_lines, const double* line_nus)
+// ... and no Doppler width [n_lines][n_depth] may be zero
+static int host_lines_check(int64_t n_lines, const double* line_nus, const double* doppler, int n_depth)
 {
     for (int64_t l = 0; l + 1 < n_lines; ++l)
         if (!(line_nus[l + 1] >= line_nus[l]))
             return fail(SDX_ERR_ARG, "line_nus must be ascending (sort the line list by frequency, opacities_solvers/base.py:392-397)");
+    for (int64_t k = 0; k < n_lines * n_depth; ++k)
+        if (doppler[k] == 0.0) return fail(SDX_ERR_ARG, "doppler_width == 0 (ZeroDivisionError in the reference, voigt.py:148)");
     return SDX_OK;
 }
 
@@ -1714,9 +1781,7 @@ int sdx_line_opacity_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     if (rc) return rc;
     REQUIRE(n_nu == 0 || out, "line opacity: null output");
     if ((rc = host_grid_check(n_nu, nus))) return rc;
-    if ((rc = host_lines_check(n_lines, line_nus))) return rc;
-    for (int64_t k = 0; k < n_lines * n_depth; ++k)
-        if (doppler[k] == 0.0) return fail(SDX_ERR_ARG, "doppler_width == 0 (ZeroDivisionError in the reference, voigt.py:148)");
+    if ((rc = host_lines_check(n_lines, line_nus, doppler, n_depth))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t f8 = sizeof(double), ld = (size_t)n_lines * n_depth * f8, plane = (size_t)n_depth * n_nu * f8;
     const size_t in_bytes[] = {(size_t)n_nu * f8, (size_t)n_lines * f8, ld, (size_t)n_lines * gamma_cols * f8, ld};
@@ -1985,11 +2050,9 @@ int sdx_accumulate_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, double* total, i
     return check_launch("k_accumulate");
 }
 
-static int launch_total(sdx_ctx* ctx, int n_depth, const double* nus, int64_t nu_begin, int64_t nu_count,
-                        const sdx_continuum* cont, const double* line, int64_t line_ld, int n_split, double* line_out,
-                        int64_t line_out_ld, double* total, int64_t total_ld, hipStream_t stream = nullptr)
+// total = continuum (+ line, where there is one) for the grid's columns
+static int launch_total(sdx_ctx* ctx, const Grid& g, const sdx_continuum* cont, const double* line, int64_t line_ld, double* total, int64_t total_ld)
 {
-    if (!stream) stream = ctx->stream;
     ContinuumArgs a = to_args(cont, nullptr);
     a.bf_level_density = cont->bf_level_density;
     size_t shmem = 8;
@@ -1999,8 +2062,8 @@ static int launch_total(sdx_ctx* ctx, int n_depth, const double* nus, int64_t nu
     }
     {
         LaunchScope ls(ctx, "k_total_alphas");
-        hipLaunchKernelGGL(k_total_alphas, grid2(nu_count, n_depth), dim3(kBlock), shmem, stream, n_depth, nu_begin, nu_count,
-                           nus, a, line, line_ld, n_split, line_out, line_out_ld, total, total_ld);
+        hipLaunchKernelGGL(k_total_alphas, grid2(g.nu_count, g.n_depth), dim3(kBlock), shmem, ctx->stream, g.n_depth, g.nu_begin, g.nu_count,
+                           g.nus, a, line, line_ld, 1, (double*)nullptr, (int64_t)0, total, total_ld);
     }
     return check_launch("k_total_alphas");
 }
@@ -2013,7 +2076,7 @@ int sdx_total_alphas_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     REQUIRE(nu_count == 0 || (total && total_ld >= nu_count && (!alpha_line || line_ld >= nu_count)), "total_alphas: bad buffers");
     if (int rc = check_file_planes(cont, n_nu)) return rc;
     if (nu_count == 0) return SDX_OK;
-    return launch_total(ctx, n_depth, nus, nu_begin, nu_count, cont, alpha_line, line_ld, 1, nullptr, 0, total, total_ld);
+    return launch_total(ctx, Grid{n_depth, n_nu, nus, nu_begin, nu_count}, cont, alpha_line, line_ld, total, total_ld);
 }
 
 // ================================================================================================ formal solution
@@ -2039,10 +2102,19 @@ int sdx_calc_weights_dev(sdx_ctx* ctx, int64_t n, const double* tau, double* w0,
     return check_launch("k_weights");
 }
 
-static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
-                         const double* ray_dist, const double* wts, const double* alphas, int64_t ald, double* F, int64_t fld,
-                         double* I_nus, int accumulate, int inward, const FusedTotal* fused = nullptr, int64_t nu_global = -1,
-                         double* Fc = nullptr, int64_t fcld = 0);
+// what a formal solution of the grid's columns reads and writes, beyond the grid and the rays
+struct RtPlanes {
+    const double* alphas;  // total opacity [n_depth][ald], or null with a fused total
+    int64_t ald;
+    double* F;
+    int64_t fld;
+    double* I_nus;
+    int accumulate, inward;
+    const FusedTotal* fused;
+    double* Fc;  // the continuum flux beside a fused total
+    int64_t fcld;
+};
+static int raytrace_impl(sdx_ctx* ctx, const Grid& g, const Rays& rays, const RtPlanes& io);
 
 // the tail of spherical geometry: F_nu *= (r[-1] / reference_r)^2 (radiation_field_solvers/base.py:340-344); the continuum flux,
 // where there is one, in the same profiled launch scope
@@ -2060,7 +2132,7 @@ int sdx_raytrace_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const
                      const double* ray_dist, const double* wts, const double* alphas, int64_t ald, double* F, int64_t fld,
                      double* I_nus, int accumulate)
 {
-    return raytrace_impl(ctx, n_depth, n_nu, n_theta, nus, temps, ray_dist, wts, alphas, ald, F, fld, I_nus, accumulate, 0);
+    return raytrace_impl(ctx, Grid{n_depth, n_nu, nus, 0, n_nu}, Rays{n_theta, temps, ray_dist, wts}, RtPlanes{alphas, ald, F, fld, I_nus, accumulate, 0, nullptr, nullptr, 0});
 }
 
 int sdx_raytrace_source_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
@@ -2072,8 +2144,8 @@ int sdx_raytrace_source_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta
     FusedTotal ft{};
     ft.source = source;
     ft.sld = source_ld;
-    int rc = raytrace_impl(ctx, n_depth, n_nu, n_theta, nus, temps, ray_dist, wts, alphas, ald, F, fld, I_nus, accumulate, inward ? 1 : 0,
-                           source ? &ft : nullptr);
+    int rc = raytrace_impl(ctx, Grid{n_depth, n_nu, nus, 0, n_nu}, Rays{n_theta, temps, ray_dist, wts},
+                           RtPlanes{alphas, ald, F, fld, I_nus, accumulate, inward ? 1 : 0, source ? &ft : nullptr, nullptr, 0});
     if (rc || !inward || !F || n_nu == 0) return rc;
     return scale_flux(ctx, n_depth, n_nu, F, fld, photospheric_correction);
 }
@@ -2082,18 +2154,20 @@ int sdx_raytrace_spherical_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_th
                                const double* ray_dist, const double* wts, const double* alphas, int64_t ald, double* F,
                                int64_t fld, double* I_nus, int accumulate, double photospheric_correction)
 {
-    int rc = raytrace_impl(ctx, n_depth, n_nu, n_theta, nus, temps, ray_dist, wts, alphas, ald, F, fld, I_nus, accumulate, 1);
+    int rc = raytrace_impl(ctx, Grid{n_depth, n_nu, nus, 0, n_nu}, Rays{n_theta, temps, ray_dist, wts}, RtPlanes{alphas, ald, F, fld, I_nus, accumulate, 1, nullptr, nullptr, 0});
     if (rc || !F || n_nu == 0) return rc;
     return scale_flux(ctx, n_depth, n_nu, F, fld, photospheric_correction);
 }
 
-static int raytrace_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
-                         const double* ray_dist, const double* wts, const double* alphas, int64_t ald, double* F, int64_t fld,
-                         double* I_nus, int accumulate, int inward, const FusedTotal* fused, int64_t nu_global, double* Fc, int64_t fcld)
+// (the columns [nu_begin, nu_begin + nu_count) of the grid; which kernel runs is decided from the whole grid, g.n_nu)
+static int raytrace_impl(sdx_ctx* ctx, const Grid& g, const Rays& rays, const RtPlanes& io)
 {
-    if (nu_global < n_nu) nu_global = n_nu;  // stand-alone calls: the grid handed over is the whole grid
+    const int n_depth = g.n_depth, n_theta = rays.n_theta, accumulate = io.accumulate, inward = io.inward;
+    const int64_t n_nu = g.nu_count, nu_global = g.n_nu, ald = io.ald, fld = io.fld, fcld = io.fcld;
+    const double *const nus = g.nus + g.nu_begin, *const temps = rays.temps, *const ray_dist = rays.ray_dist, *const wts = rays.wts, *const alphas = io.alphas;
+    double *const F = io.F, *const I_nus = io.I_nus, *const Fc = io.Fc;
     FusedTotal ft{};
-    if (fused) ft = *fused;
+    if (io.fused) ft = *io.fused;
     REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "raytrace: need n_depth >= 2, n_theta > 0");
     if (n_nu == 0) return SDX_OK;
     REQUIRE(nus && temps && ray_dist && wts && ((alphas && ald >= n_nu) || ft.cont), "raytrace: null pointer");
@@ -2585,15 +2659,25 @@ int sdx_observe_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double
 }
 
 // ================================================================================================ fused synthesis
-static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
-                           int64_t n_lines, const double* line_nus, const double* doppler, const double* gammas, int gamma_cols,
-                           const double* alphas, const sdx_continuum* cont, int n_theta, const double* temps,
-                           const double* ray_dist, const double* wts, double* alpha_line_out, double* total_alphas, double* F_nu,
-                           int64_t ld, int64_t* n_evaluations_dev, const LineParams* gen, double* I_nus = nullptr, const double* source = nullptr,
-                           int64_t source_ld = 0, const sdx_synthesis_options* opt = nullptr)
+// the planes a synthesis writes ([n_depth][ld], the shard's columns) and the optional ones it reads.  synthesize_impl: device pointers.
+// synthesize_host_shard reads the three output planes and n_evaluations alone, as HOST pointers: whole-grid planes [n_depth][n_nu]
+// (ld = n_nu) of which it fills the shard's columns
+struct SynthPlanes {
+    double *alpha_line_out, *total_alphas, *F_nu;
+    int64_t ld;
+    int64_t* n_evaluations;
+    double* I_nus;
+    const double* source;
+    int64_t source_ld;
+};
+static int synthesize_impl(sdx_ctx* ctx, const Grid& g, const Lines& lines, const sdx_continuum* cont, const Rays& rays, const SynthPlanes& io,
+                           const sdx_synthesis_options* opt)
 {
     int rc;
-    REQUIRE(cont && temps && ray_dist && wts && n_theta > 0 && n_depth >= 2, "synthesize: bad arguments");
+    const int n_depth = g.n_depth, n_theta = rays.n_theta;
+    const int64_t n_nu = g.n_nu, nu_begin = g.nu_begin, nu_count = g.nu_count, n_lines = lines.n_lines, ld = io.ld;
+    double *const alpha_line_out = io.alpha_line_out, *const total_alphas = io.total_alphas, *const F_nu = io.F_nu;
+    REQUIRE(cont && rays.temps && rays.ray_dist && rays.wts && n_theta > 0 && n_depth >= 2, "synthesize: bad arguments");
     REQUIRE(nu_begin >= 0 && nu_count >= 0 && nu_begin + nu_count <= n_nu, "synthesize: shard outside the grid");
     REQUIRE(nu_count == 0 || (F_nu && ld >= nu_count), "synthesize: bad output buffers");
     if ((rc = check_file_planes(cont, n_nu))) return rc;
@@ -2601,8 +2685,8 @@ static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
     const int n_extra = opt ? opt->n_line_planes : 0;
     REQUIRE(n_extra >= 0 && n_extra <= 2, "synthesize: n_line_planes must be 0..2");
     // (a plan is for dense lists: the generating pre-pass ignores it, and so do culled shards and the two-collective mode)
-    const sdx_grid_plan* const plan = opt && !gen ? opt->grid_plan : nullptr;
-    if (plan && (rc = check_grid_plan(ctx, plan, n_nu, nus, n_lines, line_nus, cont))) return rc;
+    const sdx_grid_plan* const plan = opt && !lines.gen ? opt->grid_plan : nullptr;
+    if (plan && (rc = check_grid_plan(ctx, plan, g, lines, cont))) return rc;
     double* const Fc = opt ? opt->F_nu_continuum : nullptr;
     REQUIRE(!Fc || opt->continuum_ld >= nu_count, "synthesize: continuum_ld must cover the columns");
     for (int k = 0; k < n_extra; ++k) REQUIRE(opt->line_plane[k] && opt->line_plane_ld >= nu_count, "synthesize: bad line plane");
@@ -2627,25 +2711,21 @@ static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
         if (rc_trace || !inward) return rc_trace;
         return scale_flux(ctx, n_depth, nu_count, F_nu, ld, opt->photospheric_correction, Fc, Fc ? opt->continuum_ld : 0);
     };
-    const ContinuumJob job{cont, nu_begin, nu_count, cont_plane};
-    const double* part = nullptr;
-    int64_t pld = 0;
-    int n_planes = 0;
+    LinePlanes p{};  // (no lines: no planes)
     // two-collective mode: the classification launch ran already (sdx_synthesize_classify_dev), the per-line maxima were gathered
     const ClassifyPhase second{2, 0, 0, opt ? const_cast<double*>(opt->line_m_max) : nullptr};
-    REQUIRE(!second.m_max || (n_lines > 0 && !gen), "synthesize: options->line_m_max goes with a dense line list");
+    REQUIRE(!second.m_max || (n_lines > 0 && !lines.gen), "synthesize: options->line_m_max goes with a dense line list");
     if (!second.m_max) ctx->classified.valid = false;  // (this step rewrites the continuum plane a phase 1 left behind)
     if (n_lines > 0) {
-        LineWork w;
-        rc = line_partials(ctx, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, &part, &pld,
-                           &n_planes, &w, n_evaluations_dev != nullptr, &job, gen, second.m_max ? &second : nullptr, plan);
-        if (rc) return rc;
-        if (n_evaluations_dev)
-            HIP_TRY(hipMemcpyAsync(n_evaluations_dev, w.evals, sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream));
+        PrepassRequest req{};
+        req.count_evals = io.n_evaluations != nullptr, req.cont = cont, req.cont_plane = cont_plane, req.ph = second.m_max ? &second : nullptr, req.plan = plan;
+        if ((rc = line_partials(ctx, g, lines, req, &p))) return rc;
+        if (io.n_evaluations)
+            HIP_TRY(hipMemcpyAsync(io.n_evaluations, p.w.evals, sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream));
     } else {
-        rc = launch_total(ctx, n_depth, nus, nu_begin, nu_count, cont, nullptr, 0, 1, nullptr, 0, cont_plane, nu_count);
+        rc = launch_total(ctx, g, cont, nullptr, 0, cont_plane, nu_count);
         if (rc) return rc;
-        if (n_evaluations_dev) HIP_TRY(hipMemsetAsync(n_evaluations_dev, 0, sizeof(int64_t), ctx->stream));  // (an empty list evaluates nothing)
+        if (io.n_evaluations) HIP_TRY(hipMemsetAsync(io.n_evaluations, 0, sizeof(int64_t), ctx->stream));  // (an empty list evaluates nothing)
         if (alpha_line_out)
             HIP_TRY(hipMemset2DAsync(alpha_line_out, ld * sizeof(double), 0, nu_count * sizeof(double), n_depth, ctx->stream));
     }
@@ -2658,12 +2738,12 @@ static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
             if (total_alphas)
                 HIP_TRY(hipMemcpy2DAsync(total_alphas, ld * sizeof(double), cont_plane, nu_count * sizeof(double), nu_count * sizeof(double),
                                          n_depth, hipMemcpyDeviceToDevice, ctx->stream));
-            if (part) {
+            if (p.part) {
                 if (alpha_line_out)
                     hipLaunchKernelGGL(k_reduce_partials, grid2(nu_count, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, nu_count,
-                                       n_planes, part, pld, alpha_line_out, ld, 0);
-                hipLaunchKernelGGL(k_reduce_partials, grid2(nu_count, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, nu_count, n_planes,
-                                   part, pld, total, tld, 1);
+                                       p.n_planes, p.part, p.pld, alpha_line_out, ld, 0);
+                hipLaunchKernelGGL(k_reduce_partials, grid2(nu_count, n_depth), dim3(kBlock), 0, ctx->stream, n_depth, nu_count, p.n_planes,
+                                   p.part, p.pld, total, tld, 1);
             }
         }
         rc = check_launch("k_reduce_partials");
@@ -2671,27 +2751,25 @@ static int synthesize_impl(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
         for (int k = 0; k < n_extra; ++k)
             if ((rc = sdx_accumulate_dev(ctx, n_depth, nu_count, total, tld, opt->line_plane[k], opt->line_plane_ld))) return rc;
         FusedTotal only_source{};  // (no fused total: the formal solution reads `total`; the caller's source plane still applies)
-        only_source.source = source;
-        only_source.sld = source_ld;
-        return finish(raytrace_impl(ctx, n_depth, nu_count, n_theta, nus + nu_begin, temps, ray_dist, wts, total, tld, F_nu, ld, I_nus, 0, inward,
-                                    source ? &only_source : nullptr, n_nu));
+        only_source.source = io.source;
+        only_source.sld = io.source_ld;
+        return finish(raytrace_impl(ctx, g, rays, RtPlanes{total, tld, F_nu, ld, io.I_nus, 0, inward, io.source ? &only_source : nullptr, nullptr, 0}));
     }
     FusedTotal ft{};
-    ft.source = source;
-    ft.sld = source_ld;
+    ft.source = io.source;
+    ft.sld = io.source_ld;
     ft.cont = cont_plane;
     ft.cld = nu_count;
-    ft.planes = part;
-    ft.n_planes = n_planes;
-    ft.pld = pld;
+    ft.planes = p.part;
+    ft.n_planes = p.n_planes;
+    ft.pld = p.pld;
     ft.total_out = total_alphas;
-    ft.line_out = part ? alpha_line_out : nullptr;
+    ft.line_out = p.part ? alpha_line_out : nullptr;
     ft.out_ld = ld;
     ft.n_extra = n_extra;
     for (int k = 0; k < n_extra; ++k) ft.extra[k] = opt->line_plane[k];
     ft.eld = n_extra ? opt->line_plane_ld : 0;
-    return finish(raytrace_impl(ctx, n_depth, nu_count, n_theta, nus + nu_begin, temps, ray_dist, wts, nullptr, 0, F_nu, ld, I_nus, 0, inward, &ft, n_nu,
-                                Fc, Fc ? opt->continuum_ld : 0));
+    return finish(raytrace_impl(ctx, g, rays, RtPlanes{nullptr, 0, F_nu, ld, io.I_nus, 0, inward, &ft, Fc, Fc ? opt->continuum_ld : 0}));
 }
 
 int sdx_synthesize_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
@@ -2700,10 +2778,8 @@ int sdx_synthesize_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nu
                        const double* ray_dist, const double* wts, double* alpha_line_out, double* total_alphas, double* F_nu,
                        int64_t ld, int64_t* n_evaluations_dev)
 {
-    int rc = check_line_args(ctx, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas);
-    if (rc) return rc;
-    return synthesize_impl(ctx, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, cont, n_theta,
-                           temps, ray_dist, wts, alpha_line_out, total_alphas, F_nu, ld, n_evaluations_dev, nullptr);
+    return sdx_synthesize_ex_dev(ctx, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, cont, n_theta, temps, ray_dist,
+                                 wts, alpha_line_out, total_alphas, F_nu, ld, nullptr, 0, nullptr, n_evaluations_dev);  // (no source plane, no intensities)
 }
 
 int sdx_synthesize_ex_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
@@ -2715,8 +2791,8 @@ int sdx_synthesize_ex_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double*
     int rc = check_line_args(ctx, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas);
     if (rc) return rc;
     REQUIRE(!source || source_ld >= nu_count, "synthesize_ex: source_ld must cover the columns");
-    return synthesize_impl(ctx, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, cont, n_theta,
-                           temps, ray_dist, wts, alpha_line_out, total_alphas, F_nu, ld, n_evaluations_dev, nullptr, I_nus, source, source_ld);
+    return synthesize_impl(ctx, Grid{n_depth, n_nu, nus, nu_begin, nu_count}, Lines{n_lines, line_nus, doppler, gammas, gamma_cols, alphas, nullptr}, cont,
+                           Rays{n_theta, temps, ray_dist, wts}, SynthPlanes{alpha_line_out, total_alphas, F_nu, ld, n_evaluations_dev, I_nus, source, source_ld}, nullptr);
 }
 
 int sdx_synthesize_linelist_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
@@ -2728,11 +2804,11 @@ int sdx_synthesize_linelist_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const d
     REQUIRE(n_depth > 0 && n_nu >= 0 && n_nu < (int64_t)2147483647, "synthesize: bad sizes");
     REQUIRE(n_nu == 0 || nus, "synthesize: null frequency grid");
     LineParams lp{};
-    int rc = to_line_params(ll, n_depth, &lp);
+    Lines lines;
+    int rc = to_line_params(ll, n_depth, &lp, &lines);
     if (rc) return rc;
-    return synthesize_impl(ctx, n_depth, n_nu, nus, nu_begin, nu_count, ll->n_lines, ll->nu, nullptr, nullptr,
-                           ll->gamma_mode >= 2 ? 1 : n_depth, nullptr, cont, n_theta, temps, ray_dist, wts, alpha_line_out, total_alphas,
-                           F_nu, ld, n_evaluations_dev, &lp);
+    return synthesize_impl(ctx, Grid{n_depth, n_nu, nus, nu_begin, nu_count}, lines, cont, Rays{n_theta, temps, ray_dist, wts},
+                           SynthPlanes{alpha_line_out, total_alphas, F_nu, ld, n_evaluations_dev, nullptr, nullptr, 0}, nullptr);
 }
 
 int sdx_synthesize_opt_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
@@ -2743,20 +2819,18 @@ int sdx_synthesize_opt_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
 {
     REQUIRE(ctx && opt, "synthesize_opt: null context or options");
     REQUIRE(!opt->source || opt->source_ld >= nu_count, "synthesize_opt: source_ld must cover the columns");
+    LineParams lp{};
+    Lines lines{n_lines, line_nus, doppler, gammas, gamma_cols, alphas, nullptr};
+    int rc;
     if (opt->linelist) {  // line parameters generated in the pre-pass (f1): the dense arrays are not read
         REQUIRE(n_depth > 0 && n_nu >= 0 && n_nu < (int64_t)2147483647 && (n_nu == 0 || nus), "synthesize_opt: bad sizes");
-        LineParams lp{};
-        int rc = to_line_params(opt->linelist, n_depth, &lp);
-        if (rc) return rc;
-        return synthesize_impl(ctx, n_depth, n_nu, nus, nu_begin, nu_count, opt->linelist->n_lines, opt->linelist->nu, nullptr, nullptr,
-                               opt->linelist->gamma_mode >= 2 ? 1 : n_depth, nullptr, cont, n_theta, temps, ray_dist, wts, alpha_line_out,
-                               total_alphas, F_nu, ld, n_evaluations_dev, &lp, opt->I_nus, opt->source, opt->source_ld, opt);
+        rc = to_line_params(opt->linelist, n_depth, &lp, &lines);
+    } else {
+        rc = check_line_args(ctx, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas);
     }
-    int rc = check_line_args(ctx, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas);
     if (rc) return rc;
-    return synthesize_impl(ctx, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, cont, n_theta,
-                           temps, ray_dist, wts, alpha_line_out, total_alphas, F_nu, ld, n_evaluations_dev, nullptr, opt->I_nus, opt->source,
-                           opt->source_ld, opt);
+    return synthesize_impl(ctx, Grid{n_depth, n_nu, nus, nu_begin, nu_count}, lines, cont, Rays{n_theta, temps, ray_dist, wts},
+                           SynthPlanes{alpha_line_out, total_alphas, F_nu, ld, n_evaluations_dev, opt->I_nus, opt->source, opt->source_ld}, opt);
 }
 
 // Phase 1 of the two-collective mode (include/stardis_hip.h): the classification launch of a culled shard's step on a SHARE of the
@@ -2775,101 +2849,104 @@ int sdx_synthesize_classify_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const d
     if ((rc = ensure(ctx, &ctx->cont_ws, &ctx->cont_ws_bytes, (size_t)n_depth * nu_count * sizeof(double)))) return rc;
     // (the partial planes of the line kernels: reserved here so that the synthesis that follows moves nothing)
     if ((rc = ensure(ctx, &ctx->part_ws, &ctx->part_ws_bytes, (size_t)3 * n_depth * nu_count * sizeof(double)))) return rc;
-    const ContinuumJob job{cont, nu_begin, nu_count, (double*)ctx->cont_ws};
     const ClassifyPhase first{1, line_begin, line_count, m_max};
     ctx->classified.valid = false;
-    ctx->far_req_done = false;  // (request_far_ranges resets it only when the far field is on)
-    if (far_field_on(ctx, n_nu) && (rc = request_far_ranges(ctx, n_nu, nu_begin, nu_count))) return rc;
-    rc = line_prepass(ctx, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, true, nullptr, nullptr, nullptr, false, &job,
-                      nullptr, nu_begin, nu_count, &first);
-    ctx->far_req = FarReq{nullptr, 0, 0};
-    return rc;
+    const Grid g{n_depth, n_nu, nus, nu_begin, nu_count};
+    PrepassRequest req{};
+    req.cont = cont, req.cont_plane = (double*)ctx->cont_ws, req.ph = &first;
+    if (far_field_on(ctx, n_nu) && (rc = far_request(ctx, g, &req.far))) return rc;
+    return line_prepass(ctx, g, Lines{n_lines, line_nus, doppler, gammas, gamma_cols, alphas, nullptr}, req, nullptr);
 }
 
 // The fused synthesis for a caller that holds everything in host memory (C, or numpy through ctypes): uploads, runs
 // sdx_synthesize_dev, downloads.  `cont` carries HOST pointers here; array lengths follow from the sizes in the struct.
-static int synthesize_host_check(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus,
-                                 const double* doppler, const double* gammas, int gamma_cols, const double* alphas, const sdx_continuum* cont,
-                                 int n_theta, const double* temps, const double* ray_dist, const double* wts)
+static int synthesize_host_check(sdx_ctx* ctx, const Grid& g, const Lines& l, const sdx_continuum* cont, const Rays& rays)
 {
-    int rc = check_line_args(ctx, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas);
+    int rc = check_line_args(ctx, g.n_depth, g.n_nu, g.nus, l.n_lines, l.line_nus, l.doppler, l.gammas, l.gamma_cols, l.alphas);
     if (rc) return rc;
-    REQUIRE(cont && temps && ray_dist && wts && n_theta > 0 && n_depth >= 2, "synthesize: bad arguments");
-    if ((rc = host_grid_check(n_nu, nus))) return rc;
-    if ((rc = host_lines_check(n_lines, line_nus))) return rc;
-    for (int64_t k = 0; k < n_lines * n_depth; ++k)
-        if (doppler[k] == 0.0) return fail(SDX_ERR_ARG, "doppler_width == 0 (ZeroDivisionError in the reference, voigt.py:148)");
+    REQUIRE(cont && rays.temps && rays.ray_dist && rays.wts && rays.n_theta > 0 && g.n_depth >= 2, "synthesize: bad arguments");
+    if ((rc = host_grid_check(g.n_nu, g.nus))) return rc;
+    if ((rc = host_lines_check(l.n_lines, l.line_nus, l.doppler, g.n_depth))) return rc;
     REQUIRE(cont->bf_n_species == 0 || !cont->bf_cutoff || cont->bf_n_levels > 0, "synthesize: bf_n_levels must be set");
     REQUIRE(cont->n_file_planes == 0, "synthesize: file planes are device planes (sdx_synthesize_dev); the host-buffer entry points take tabulated sources as the 1-D table only");
     return SDX_OK;
 }
 
+// One row of a host-pointer entry point's upload table: every non-null host array goes up; lengths follow from the sizes in the struct
+struct HostIn {
+    const void* src;
+    size_t bytes;
+    const void** dst;
+};
+// the continuum's rows (HOST pointers in *cont, device pointers into *c), in the order both callers upload them; `temperature` is not
+// among them: the synthesis points it at the rays' temperatures, sdx_continuum_f64 uploads it behind these
+static void continuum_uploads(const sdx_continuum* cont, sdx_continuum* c, int n_depth, int64_t n_nu, int n_levels, std::vector<HostIn>* ins)
+{
+    const size_t f8 = sizeof(double), depth = (size_t)n_depth * f8;
+    ins->insert(ins->end(), {
+        {cont->lambdas, (size_t)n_nu * f8, (const void**)&c->lambdas},
+        {cont->table_wavelength, (size_t)c->n_table * f8, (const void**)&c->table_wavelength},
+        {cont->table_sigma, (size_t)c->n_table * f8, (const void**)&c->table_sigma},
+        {cont->table_density, depth, (const void**)&c->table_density},
+        {cont->bf_species_offsets, (size_t)(c->bf_n_species + 1) * sizeof(int32_t), (const void**)&c->bf_species_offsets},
+        {cont->bf_species_ion_number, (size_t)c->bf_n_species * sizeof(int32_t), (const void**)&c->bf_species_ion_number},
+        {cont->bf_cutoff, (size_t)n_levels * f8, (const void**)&c->bf_cutoff},
+        {cont->bf_level_density, (size_t)n_levels * depth, (const void**)&c->bf_level_density},
+        {cont->ff_species_ion_number, (size_t)c->ff_n_species * sizeof(int32_t), (const void**)&c->ff_species_ion_number},
+        {cont->ff_number_density, (size_t)c->ff_n_species * depth, (const void**)&c->ff_number_density},
+        {cont->ray_n_h, depth, (const void**)&c->ray_n_h},
+        {cont->ray_n_he, depth, (const void**)&c->ray_n_he},
+        {cont->ray_n_h2, depth, (const void**)&c->ray_n_h2},
+        {cont->electron_density, depth, (const void**)&c->electron_density},
+    });
+}
+
 // Uploads everything to ctx's device, enqueues the synthesis of columns [nu_begin, nu_begin + nu_count) and the downloads of the
 // requested planes into the caller's [n_depth][n_nu] host arrays (the shard's columns only).  `io` stays alive until the caller
 // has called io.finish(); *d_F_out is the shard's device flux plane [n_depth][nu_count] (valid until the next call on ctx).
-static int synthesize_host_shard(sdx_ctx* ctx, HostIo& io, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
-                                 int64_t n_lines, const double* line_nus, const double* doppler, const double* gammas, int gamma_cols,
-                                 const double* alphas, const sdx_continuum* cont, int n_theta, const double* temps, const double* ray_dist,
-                                 const double* wts, double* alpha_line_out, double* total_alphas, double* F_nu, int64_t* n_evaluations,
-                                 double** d_F_out, size_t extra_dev_bytes = 0)
+static int synthesize_host_shard(sdx_ctx* ctx, HostIo& io, const Grid& g, const Lines& l, const sdx_continuum* cont, const Rays& rays, const SynthPlanes& out,
+                                 double** d_F_out)
 {
     int rc;
     HIP_TRY(hipSetDevice(ctx->device));
+    const int n_depth = g.n_depth, n_theta = rays.n_theta;
+    const int64_t n_nu = g.n_nu, nu_begin = g.nu_begin, nu_count = g.nu_count, n_lines = l.n_lines;
+    double *const alpha_line_out = out.alpha_line_out, *const total_alphas = out.total_alphas, *const F_nu = out.F_nu;
     const size_t f8 = sizeof(double), plane = (size_t)n_depth * nu_count * f8, ld = (size_t)n_lines * n_depth * f8;
     sdx_continuum c = *cont;
-    const int n_levels = c.bf_n_species > 0 ? c.bf_n_levels : 0;
-    // every non-null host array goes up; lengths follow from the sizes in the struct
-    struct In {
-        const void* src;
-        size_t bytes;
-        const void** dst;
-    };
     const double *d_nus, *d_ln, *d_dw, *d_g, *d_a, *d_t, *d_rd, *d_w;
-    const In ins[] = {
-        {nus, (size_t)n_nu * f8, (const void**)&d_nus},
-        {line_nus, (size_t)n_lines * f8, (const void**)&d_ln},
-        {doppler, ld, (const void**)&d_dw},
-        {gammas, (size_t)n_lines * gamma_cols * f8, (const void**)&d_g},
-        {alphas, ld, (const void**)&d_a},
-        {temps, (size_t)n_depth * f8, (const void**)&d_t},
-        {ray_dist, (size_t)(n_depth - 1) * n_theta * f8, (const void**)&d_rd},
-        {wts, (size_t)n_theta * f8, (const void**)&d_w},
-        {cont->lambdas, (size_t)n_nu * f8, (const void**)&c.lambdas},
-        {cont->table_wavelength, (size_t)c.n_table * f8, (const void**)&c.table_wavelength},
-        {cont->table_sigma, (size_t)c.n_table * f8, (const void**)&c.table_sigma},
-        {cont->table_density, (size_t)n_depth * f8, (const void**)&c.table_density},
-        {cont->bf_species_offsets, (size_t)(c.bf_n_species + 1) * sizeof(int32_t), (const void**)&c.bf_species_offsets},
-        {cont->bf_species_ion_number, (size_t)c.bf_n_species * sizeof(int32_t), (const void**)&c.bf_species_ion_number},
-        {cont->bf_cutoff, (size_t)n_levels * f8, (const void**)&c.bf_cutoff},
-        {cont->bf_level_density, (size_t)n_levels * n_depth * f8, (const void**)&c.bf_level_density},
-        {cont->ff_species_ion_number, (size_t)c.ff_n_species * sizeof(int32_t), (const void**)&c.ff_species_ion_number},
-        {cont->ff_number_density, (size_t)c.ff_n_species * n_depth * f8, (const void**)&c.ff_number_density},
-        {cont->ray_n_h, (size_t)n_depth * f8, (const void**)&c.ray_n_h},
-        {cont->ray_n_he, (size_t)n_depth * f8, (const void**)&c.ray_n_he},
-        {cont->ray_n_h2, (size_t)n_depth * f8, (const void**)&c.ray_n_h2},
-        {cont->electron_density, (size_t)n_depth * f8, (const void**)&c.electron_density},
+    std::vector<HostIn> ins = {
+        {g.nus, (size_t)n_nu * f8, (const void**)&d_nus},
+        {l.line_nus, (size_t)n_lines * f8, (const void**)&d_ln},
+        {l.doppler, ld, (const void**)&d_dw},
+        {l.gammas, (size_t)n_lines * l.gamma_cols * f8, (const void**)&d_g},
+        {l.alphas, ld, (const void**)&d_a},
+        {rays.temps, (size_t)n_depth * f8, (const void**)&d_t},
+        {rays.ray_dist, (size_t)(n_depth - 1) * n_theta * f8, (const void**)&d_rd},
+        {rays.wts, (size_t)n_theta * f8, (const void**)&d_w},
     };
+    continuum_uploads(cont, &c, n_depth, n_nu, c.bf_n_species > 0 ? c.bf_n_levels : 0, &ins);
     const int n_out = 1 + (alpha_line_out ? 1 : 0) + (total_alphas ? 1 : 0);
-    size_t dev_need = (size_t)n_out * HostIo::pad(plane) + 512 + HostIo::pad(extra_dev_bytes);
-    size_t pin_need = (size_t)(F_nu ? n_out : n_out - 1) * HostIo::pad(plane) + 512 + HostIo::pad(extra_dev_bytes);
-    for (const In& in : ins)
+    size_t dev_need = (size_t)n_out * HostIo::pad(plane) + 512;
+    size_t pin_need = (size_t)(F_nu ? n_out : n_out - 1) * HostIo::pad(plane) + 512;
+    for (const HostIn& in : ins)
         if (in.src) dev_need += HostIo::pad(in.bytes ? in.bytes : 8), pin_need += HostIo::pad(in.bytes);
     if ((rc = io.begin(dev_need, pin_need))) return rc;
-    for (const In& in : ins)
+    for (const HostIn& in : ins)
         if (in.src && (rc = io.upload(in.src, in.bytes, in.dst))) return rc;
     c.temperature = d_t;
     double* d_line = alpha_line_out ? (double*)io.alloc(plane) : nullptr;
     double* d_total = total_alphas ? (double*)io.alloc(plane) : nullptr;
     double* d_F = (double*)io.alloc(plane);
     int64_t* d_ev = (int64_t*)io.alloc(sizeof(int64_t));
-    rc = sdx_synthesize_dev(ctx, n_depth, n_nu, d_nus, nu_begin, nu_count, n_lines, d_ln, d_dw, d_g, gamma_cols, d_a, &c, n_theta, d_t, d_rd, d_w,
-                            d_line, d_total, d_F, nu_count, n_evaluations ? d_ev : nullptr);
+    rc = sdx_synthesize_dev(ctx, n_depth, n_nu, d_nus, nu_begin, nu_count, n_lines, d_ln, d_dw, d_g, l.gamma_cols, d_a, &c, n_theta, d_t, d_rd, d_w,
+                            d_line, d_total, d_F, nu_count, out.n_evaluations ? d_ev : nullptr);
     if (rc) return rc;
     const size_t pitch = (size_t)n_nu * f8, row = (size_t)nu_count * f8;
     if (alpha_line_out && (rc = io.download2d(alpha_line_out + nu_begin, pitch, d_line, row, n_depth))) return rc;
     if (total_alphas && (rc = io.download2d(total_alphas + nu_begin, pitch, d_total, row, n_depth))) return rc;
     if (F_nu && (rc = io.download2d(F_nu + nu_begin, pitch, d_F, row, n_depth))) return rc;
-    if (n_evaluations) HIP_TRY(hipMemcpyAsync(n_evaluations, d_ev, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (out.n_evaluations) HIP_TRY(hipMemcpyAsync(out.n_evaluations, d_ev, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     if (d_F_out) *d_F_out = d_F;
     return SDX_OK;
 }
@@ -2879,14 +2956,16 @@ int sdx_synthesize_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nu
                        int n_theta, const double* temps, const double* ray_dist, const double* wts, double* alpha_line_out,
                        double* total_alphas, double* F_nu, int64_t* n_evaluations)
 {
-    int rc = synthesize_host_check(ctx, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, cont, n_theta, temps, ray_dist, wts);
+    const Grid g{n_depth, n_nu, nus, 0, n_nu};
+    const Lines lines{n_lines, line_nus, doppler, gammas, gamma_cols, alphas, nullptr};
+    const Rays rays{n_theta, temps, ray_dist, wts};
+    int rc = synthesize_host_check(ctx, g, lines, cont, rays);
     if (rc) return rc;
     REQUIRE(n_nu == 0 || F_nu, "synthesize: null output");
     if (n_nu == 0) return SDX_OK;
     HostIo io{ctx};
     int64_t ev = 0;
-    rc = synthesize_host_shard(ctx, io, n_depth, n_nu, nus, 0, n_nu, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, cont, n_theta, temps,
-                               ray_dist, wts, alpha_line_out, total_alphas, F_nu, n_evaluations ? &ev : nullptr, nullptr);
+    rc = synthesize_host_shard(ctx, io, g, lines, cont, rays, SynthPlanes{alpha_line_out, total_alphas, F_nu, n_nu, n_evaluations ? &ev : nullptr, nullptr, nullptr, 0}, nullptr);
     if (rc) return rc;
     if ((rc = io.finish())) return rc;
     if (n_evaluations) *n_evaluations = ev;
@@ -2917,45 +2996,25 @@ int sdx_continuum_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, double* nus, cons
     const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
     sdx_continuum c = *cont;
     const int n_levels = has_bf ? c.bf_n_levels : 0;
-    struct In {
-        const void* src;
-        size_t bytes;
-        const void** dst;
-    };
     const double* d_nus;
-    const In ins[] = {
-        {nus, (size_t)n_nu * f8, (const void**)&d_nus},
-        {cont->lambdas, (size_t)n_nu * f8, (const void**)&c.lambdas},
-        {cont->table_wavelength, (size_t)c.n_table * f8, (const void**)&c.table_wavelength},
-        {cont->table_sigma, (size_t)c.n_table * f8, (const void**)&c.table_sigma},
-        {cont->table_density, (size_t)n_depth * f8, (const void**)&c.table_density},
-        {cont->bf_species_offsets, (size_t)(c.bf_n_species + 1) * sizeof(int32_t), (const void**)&c.bf_species_offsets},
-        {cont->bf_species_ion_number, (size_t)c.bf_n_species * sizeof(int32_t), (const void**)&c.bf_species_ion_number},
-        {cont->bf_cutoff, (size_t)n_levels * f8, (const void**)&c.bf_cutoff},
-        {cont->bf_level_density, (size_t)n_levels * n_depth * f8, (const void**)&c.bf_level_density},
-        {cont->ff_species_ion_number, (size_t)c.ff_n_species * sizeof(int32_t), (const void**)&c.ff_species_ion_number},
-        {cont->ff_number_density, (size_t)c.ff_n_species * n_depth * f8, (const void**)&c.ff_number_density},
-        {cont->ray_n_h, (size_t)n_depth * f8, (const void**)&c.ray_n_h},
-        {cont->ray_n_he, (size_t)n_depth * f8, (const void**)&c.ray_n_he},
-        {cont->ray_n_h2, (size_t)n_depth * f8, (const void**)&c.ray_n_h2},
-        {cont->electron_density, (size_t)n_depth * f8, (const void**)&c.electron_density},
-        {cont->temperature, (size_t)n_depth * f8, (const void**)&c.temperature},
-    };
+    std::vector<HostIn> ins = {{nus, (size_t)n_nu * f8, (const void**)&d_nus}};
+    continuum_uploads(cont, &c, n_depth, n_nu, n_levels, &ins);
+    ins.push_back({cont->temperature, (size_t)n_depth * f8, (const void**)&c.temperature});
     double* const outs[] = {total_alphas, alpha_file, alpha_bf, alpha_ff, alpha_rayleigh, alpha_electron};
     int n_out = 0;
     for (double* o : outs) n_out += o ? 1 : 0;
     size_t dev_need = (size_t)n_out * HostIo::pad(plane) + 512, pin_need = (size_t)n_out * HostIo::pad(plane) + HostIo::pad((size_t)n_nu * f8) + 512;
-    for (const In& in : ins)
+    for (const HostIn& in : ins)
         if (in.src) dev_need += HostIo::pad(in.bytes ? in.bytes : 8), pin_need += HostIo::pad(in.bytes);
     HostIo io{ctx};
     if ((rc = io.begin(dev_need, pin_need))) return rc;
-    for (const In& in : ins)
+    for (const HostIn& in : ins)
         if (in.src && (rc = io.upload(in.src, in.bytes, in.dst))) return rc;
     double* d_out[6];
     for (int k = 0; k < 6; ++k) d_out[k] = outs[k] ? (double*)io.alloc(plane) : nullptr;
     // the total first: it reads the caller's frequencies as they came (the Rayleigh source clips its own copy of a frequency
     // above 2.3e15 Hz, :99, whether or not the array has been clipped yet)
-    if (total_alphas && (rc = launch_total(ctx, n_depth, d_nus, 0, n_nu, &c, nullptr, 0, 1, nullptr, 0, d_out[0], n_nu))) return rc;
+    if (total_alphas && (rc = launch_total(ctx, Grid{n_depth, n_nu, d_nus, 0, n_nu}, &c, nullptr, 0, d_out[0], n_nu))) return rc;
     if (alpha_file && (rc = sdx_alpha_file_1d_dev(ctx, n_depth, n_nu, c.lambdas, c.n_table, c.table_wavelength, c.table_sigma, c.table_density, d_out[1], n_nu)))
         return rc;
     if (alpha_bf) {
@@ -3250,7 +3309,9 @@ int sdx_synthesize_sharded_f64(sdx_group* g, int n_depth, int64_t n_nu, const do
 {
     REQUIRE(g, "null group");
     const int P = g->n;
-    int rc = synthesize_host_check(g->ctx[0], n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, cont, n_theta, temps, ray_dist, wts);
+    const Lines lines{n_lines, line_nus, doppler, gammas, gamma_cols, alphas, nullptr};
+    const Rays rays{n_theta, temps, ray_dist, wts};
+    int rc = synthesize_host_check(g->ctx[0], Grid{n_depth, n_nu, nus, 0, n_nu}, lines, cont, rays);
     if (rc) return rc;
     REQUIRE(n_nu == 0 || F_nu || emergent_flux, "synthesize_sharded: no output requested");
     if (n_nu == 0) return SDX_OK;
@@ -3286,8 +3347,8 @@ int sdx_synthesize_sharded_f64(sdx_group* g, int n_depth, int64_t n_nu, const do
         int rr = SDX_OK;
         if (hipSetDevice(ctx->device) != hipSuccess) rr = fail(SDX_ERR_HIP, "hipSetDevice failed");
         if (!rr && cnt > 0)
-            rr = synthesize_host_shard(ctx, *io[r], n_depth, n_nu, nus, b, cnt, n_lines, line_nus, doppler, gammas, gamma_cols, alphas, cont, n_theta,
-                                       temps, ray_dist, wts, alpha_line_out, total_alphas, F_nu, (r == ev_rank && n_evaluations) ? &ev : nullptr, &d_F);
+            rr = synthesize_host_shard(ctx, *io[r], Grid{n_depth, n_nu, nus, b, cnt}, lines, cont, rays,
+                                       SynthPlanes{alpha_line_out, total_alphas, F_nu, n_nu, (r == ev_rank && n_evaluations) ? &ev : nullptr, nullptr, nullptr, 0}, &d_F);
         if (!rr && hipMemsetAsync(g->send[r], 0, (size_t)per * sizeof(double), ctx->stream) != hipSuccess) rr = fail(SDX_ERR_HIP, "hipMemsetAsync(send) failed");
         if (!rr && cnt > 0 &&
             hipMemcpyAsync(g->send[r], d_F + (size_t)(n_depth - 1) * cnt, (size_t)cnt * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)

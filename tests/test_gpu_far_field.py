@@ -226,3 +226,47 @@ def test_the_stand_alone_line_opacity_entry_point_takes_the_option_too(far_ctx):
     assert np.array_equal(a0 == 0, a1 == 0) and rel_err(a1, a0) < FAR_VS_DIRECT
     ref, evals = oracle.calc_alan_entries(*args, return_evals=True)
     assert n1 == evals and rel_err(a1, ref) < 1e-12
+
+
+def test_a_step_that_fails_after_asking_for_far_ranges_leaves_nothing_behind(far_ctx):
+    """The far ranges a step wants travel with its pre-pass request, not in the context: a synthesis refused inside the pre-pass — behind
+    the request, where the continuum tiles are sized: bound-free species with a level count outside 1..4096 — leaves the context as it
+    found it.  A synthesis, a stand-alone line opacity and the line windows on that context equal a fresh context's, byte for byte.
+    Eight depths, eight 256-point tiles, 300 lines, four angles: no launch of such a step has the grid spacing to compute (the pre-pass
+    blocks scan it), so the ranges come from k_far_ranges — once per synthesis, once per stand-alone line opacity."""
+    from stardis_amd import ops
+    from test_gpu_engine import deep_atmosphere
+
+    atm = deep_atmosphere(8)
+    nus = synth.tracing_grid(4000.0, 4000.0 * np.exp(2048 / 1.0e5), n_override=2048)  # (the spacing of R = 1e5)
+    lines = synth.synth_lines(nus, atm, 300, seed=13, mix=(0.5, 0.3, 0.2))
+    cont = synth.synth_continuum_state(atm)
+    th, w = synth.thetas_and_weights(4)
+    args = (8, nus, lines["line_nus"], lines["doppler_widths"], lines["gammas"], lines["alphas"])
+
+    def everything(ctx):
+        planes, ran = run(ctx, 1, nus, atm, lines, cont, th, w)
+        assert ran and ctx.profile("k_far_ranges")[0] == 1
+        ctx.call("sdx_profile_enable", 1)
+        alan = ops.calc_alan_entries(*args, ctx=ctx)
+        assert ctx.profile("k_far_ranges")[0] == 2
+        ctx.call("sdx_profile_enable", 0)
+        return (*planes, alan, *ops.line_windows(*args, ctx=ctx))
+
+    fresh = _lib.Context(0)
+    try:
+        want = everything(fresh)
+    finally:
+        fresh.close()
+    far_ctx.set_option("far_field", 1)
+    syn = SpectralSynthesizer(nus, atm["temperatures"], atm["dist"], th, w, lines, cont, ctx=far_ctx, track_evaluations=False)
+    syn.cont.bf_n_levels = 5000
+    try:
+        with pytest.raises(ValueError, match=r"synthesize: bf_n_levels must be set \(1\.\.4096\)"):  # (the pre-pass's own refusal)
+            syn.step()
+    finally:
+        syn.close()
+    got = everything(far_ctx)
+    assert len(got) == len(want) == 6
+    for a, b in zip(got, want):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()

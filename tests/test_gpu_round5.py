@@ -159,7 +159,7 @@ def test_far_field_option_may_change_between_the_phases(ctx):
         want[mode] = one.F_nu()
         one.close()
     try:
-        for first, second in ((1, 0), (0, 1), (1, 0)):  # (the third pair: far_req_done left set by an earlier far-field phase 1)
+        for first, second in ((1, 0), (0, 1), (1, 0)):  # (the third pair: a far-field phase 1 after an earlier one — nothing of a far-range request may outlive its step)
             syn = SpectralSynthesizer(*args, ctx=ctx, shard=(b, c), track_evaluations=False, classify_share=(0, n_l), m_max=ctx.zeros((n_l,)))
             ctx.set_option("far_field", first)
             syn.enqueue_classify()
