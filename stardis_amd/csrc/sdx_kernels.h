@@ -1695,6 +1695,10 @@ __global__ __launch_bounds__(kBlock) void k_classify(int n_dnu, int n_depth, int
 // width, so the Faddeeva region rarely diverges inside a wave.  The candidate lines of a frequency are the
 // contiguous index range whose centre lies within kNarrowHalfWidth of it, read from cnt_ge; each lane walks that
 // range in ascending line order, tests its own window and accumulates in a register.  Deterministic, no atomics.
+// (This is what line_narrow_walk<1, false, false> below would be, as text of its own — a wave past the shard's end returns instead of
+// keeping act[], and SDX_WALK_STATS counts here.  Folding it into the walk was tried in three spellings: the four fp64 kernels without
+// subsets kept their registers, spills and occupancy and their bits, with a reordered schedule, and k_line_all ran 1217.9 us at S-c3
+// against the parent's 1213.2 - 1215.2 in seven alternated rounds: it stays, profiles/EXPERIMENTS.md.)
 __device__ __forceinline__ void line_narrow_wave(const int64_t i, const int depth_chunk, int n_depth, int64_t n_nu, const double* __restrict__ nus,
                                                         int64_t nu_begin, int64_t nu_count, int64_t n_lines,
                                                         const double* __restrict__ line_nus, LineWork w,
@@ -1782,85 +1786,18 @@ __device__ __forceinline__ void line_narrow_wave(const int64_t i, const int dept
     if (valid) plane[(size_t)d * pld + (i - nu_begin)] = acc;
 }
 
-// The same walk for F CONSECUTIVE frequencies per wave (F = 2, 4; groups aligned to the global grid index): the records of a
-// visited line — five coalesced loads, 1.9 KB per wave — serve up to F evaluations instead of one, the candidate test and the
-// region-I constants are shared, and a lane has F independent evaluations in flight.  At 1e6 lines the one-frequency walk
-// fetched 16 GB per launch through its record loads (each of the ~20 frequencies of a weak line's window loaded them again,
-// and 900 waves per XCD, each with its own 170 lines, do not fit the L2); a group fetches a line's records once.  Every
-// frequency still adds its lines in ascending line order: the bits are those of the one-frequency walk, whatever F — which
-// may therefore depend on the size of the launch (small grids keep F = 1: they need the waves).
-template <int F>
-__device__ __forceinline__ void line_narrow_group(const int64_t i0, const int depth_chunk, int n_depth, int64_t n_nu, const double* __restrict__ nus,
-                                                  int64_t nu_begin, int64_t nu_count, int64_t n_lines, const double* __restrict__ line_nus,
-                                                  LineWork w, double* __restrict__ plane, int64_t pld)
-{
-    const int lane = threadIdx.x & 63;
-    const int d = depth_chunk * 64 + lane;
-    const bool valid = d < n_depth;
-    const int dc = valid ? d : n_depth - 1;
-    const unsigned dcu = (unsigned)dc;
-    const bool one_gamma = w.narrow_raw == 1;  // (raw inputs with gammas (N_l, 1): the line's one value for every depth)
-    const int ia = (int)i0;
-    // lines with centre c in [i0 - H + 1, i0 + F - 1 + H]
-    const int64_t pa = max(i0 - kNarrowReach + 1, (int64_t)0);
-    const int64_t pb = min(i0 + F - 1 + kNarrowReach, n_nu);
-    const int la = __builtin_amdgcn_readfirstlane(w.cnt_ge[pb + 1]);
-    const int lb = __builtin_amdgcn_readfirstlane(w.cnt_ge[pa]);
-    double nu_k[F], acc[F];
-    bool act[F];  // the frequency belongs to this launch's columns (wave-uniform)
-#pragma unroll
-    for (int k = 0; k < F; ++k) {
-        act[k] = i0 + k >= nu_begin && i0 + k < nu_begin + nu_count;
-        nu_k[k] = nus[min(i0 + k, n_nu - 1)];
-        acc[k] = 0.0;
-    }
-    for (int base = la; base < lb; base += 64) {
-        const int lc = base + lane;
-        bool rel = false;
-        int c = 0;
-        if (lc < lb) {
-            const int hwm = w.nhw_max[lc];
-            c = w.centre[lc];
-            rel = hwm > 0 && ia + (F - 1) >= c - hwm && ia < c + hwm;
-        }
-        unsigned long long m = __ballot(rel);
-        int h = 0, cl = 0;
-        double y = 0.0, amp = 0.0, inv = 0.0, lnu = 0.0;
-        if (m) {
-            const int bit = __builtin_ctzll(m);
-            const int l = base + bit;
-            const size_t ob = (size_t)l * n_depth;
-            cl = __builtin_amdgcn_readlane(c, bit);
-            h = (w.nhw + ob)[dcu], y = (w.n_y + (one_gamma ? (size_t)l : ob))[one_gamma ? 0u : dcu], amp = (w.n_amp + ob)[dcu], inv = (w.n_inv + ob)[dcu], lnu = line_nus[l];
-        }
-        while (m) {
-            m &= m - 1;
-            int h_n = 0, cl_n = 0;
-            double y_n = 0.0, amp_n = 0.0, inv_n = 0.0, lnu_n = 0.0;
-            if (m) {
-                const int bit = __builtin_ctzll(m);
-                const int l = base + bit;
-                const size_t ob = (size_t)l * n_depth;
-                cl_n = __builtin_amdgcn_readlane(c, bit);
-                h_n = (w.nhw + ob)[dcu], y_n = (w.n_y + (one_gamma ? (size_t)l : ob))[one_gamma ? 0u : dcu], amp_n = (w.n_amp + ob)[dcu], inv_n = (w.n_inv + ob)[dcu], lnu_n = line_nus[l];
-            }
-            const int lo = cl - h, hi = cl + h;  // (h = 0: empty; the clamp to the grid is implied by ia + k being a grid index)
-            if (valid && ia + (F - 1) >= lo && ia < hi) {
-                if (w.narrow_raw) narrow_params(inv, y, amp, inv, y, amp);  // (inv, y, amp hold dw, gamma, alpha)
-                const RegionI k1 = region1_setup(y, amp);
-#pragma unroll
-                for (int k = 0; k < F; ++k)
-                    if (act[k] && ia + k >= lo && ia + k < hi) acc[k] = voigt_add(acc[k], nu_k[k] - lnu, inv, y, amp, k1);
-            }
-            h = h_n, cl = cl_n, y = y_n, amp = amp_n, inv = inv_n, lnu = lnu_n;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < F; ++k)
-        if (valid && act[k]) plane[(size_t)d * pld + (i0 + k - nu_begin)] = acc[k];
-}
-
-// The narrow role of DENSE long lists (at least one line per two grid points, four line subsets): the four waves of a workgroup
+// The same walk for F CONSECUTIVE frequencies per wave (F = 2, 4; groups aligned to the global grid index), in all its forms:
+// line_narrow_walk<F, SUB, F32> — the frequencies per wave, whether the wave walks one of four line subsets, and the arithmetic
+// (fp64 records, or the mixed-precision mode's fp32 ones).  The forms differ in the four places marked (1) - (4) below and nowhere else.
+//
+// F frequencies per wave: the records of a visited line — five coalesced loads, 1.9 KB per wave — serve up to F evaluations
+// instead of one, the candidate test and the region-I constants are shared, and a lane has F independent evaluations in flight.
+// At 1e6 lines the one-frequency walk fetched 16 GB per launch through its record loads (each of the ~20 frequencies of a weak
+// line's window loaded them again, and 900 waves per XCD, each with its own 170 lines, do not fit the L2); a group fetches a line's
+// records once.  Every frequency still adds its lines in ascending line order: the bits are those of the one-frequency walk,
+// whatever F — which may therefore depend on the size of the launch (small grids keep F = 1: they need the waves).
+//
+// SUB, the narrow role of DENSE long lists (at least one line per two grid points, four line subsets): the four waves of a workgroup
 // share ONE group of F consecutive frequencies and split its candidate lines — wave s takes the lines l with (l / 16) % 4 == s,
 // sixteen-line runs of the LIST going round the waves, so every wave gets a quarter of every stretch of the list — and the four
 // partial sums meet in LDS, where wave 0 adds them in subset order.  A wave still fetches a visited line's records once for up to
@@ -1869,83 +1806,140 @@ __device__ __forceinline__ void line_narrow_group(const int64_t i0, const int de
 // to fall back to one frequency per wave there: 3 000 four-times-longer waves are a launch's tail).  Which lines share a partial
 // sum is a property of the list (the run index of a line), so shards reproduce the unsharded bits; the sums differ from the
 // sequential walk's in the last bits (four partial sums instead of one).
-template <int F>
-__device__ __forceinline__ void line_narrow_subsets(const int64_t i0, const int depth_chunk, const int subset, int n_depth, int64_t n_nu,
-                                                    const double* __restrict__ nus, int64_t nu_begin, int64_t nu_count,
-                                                    const double* __restrict__ line_nus, LineWork w, double* __restrict__ acc_out)
+//
+// F32, the narrow role of the mixed-precision mode: every term evaluated by voigt_add32 (packed fp32, all four regions) from fp32
+// records; the frequency difference comes from the hi + lo float pairs of both frequencies (exact to 2^-48 of the frequency, i.e.
+// ~1e-7 of a narrow window's reach), the terms of one trip — 64 candidates — gather in an fp32 sum that goes into the fp64 sum once
+// per trip.
+
+// (1) lane -> candidate: line j of a trip that starts at base.  64 contiguous lines per trip; SUB: the 64 lines of this subset out of a
+// stretch of 256 aligned to the LIST (lanes ascend with the line index)
+#define SDX_NARROW_LINE(base, j) (SUB ? base + ((j >> 4) << 6) + (subset << 4) + (j & 15) : base + j)
+// The records of the lowest line of m into h##S, cl##S, ...: this depth's half-width, the line's centre (scalar), and (3).  fp64 addresses:
+// a per-line base (uniform: scalar arithmetic) + the lane's depth as an unsigned 32-bit offset.  Both are local macros because only
+// they give the instructions of the walks this one replaced: a lambda or an inline function, however spelled (results through
+// references or in a struct, always_inline or not), reordered all twelve line kernels, the mapping alone the six SUBSETS ones.
+#define SDX_NARROW_FETCH(S)                                                                                                                     \
+    do {                                                                                                                                        \
+        const int bit = __builtin_ctzll(m);                                                                                                     \
+        const int l = SDX_NARROW_LINE(base, bit);                                                                                               \
+        cl##S = __builtin_amdgcn_readlane(c, bit);                                                                                              \
+        if constexpr (F32) {                                                                                                                    \
+            const size_t o = (size_t)l * n_depth + dc;                                                                                          \
+            h##S = w.nhw[o], y##S = w.n_y32[o], amp##S = w.n_amp32[o], inv##S = w.n_inv32[o], lnu##S = w.lnu32[l];                              \
+        } else {                                                                                                                                \
+            const size_t ob = (size_t)l * n_depth;                                                                                              \
+            h##S = (w.nhw + ob)[dcu], y##S = (w.n_y + (one_gamma ? (size_t)l : ob))[one_gamma ? 0u : dcu], amp##S = (w.n_amp + ob)[dcu],        \
+            inv##S = (w.n_inv + ob)[dcu], lnu##S = line_nus[l];                                                                                 \
+        }                                                                                                                                       \
+    } while (0)
+template <int F, bool SUB, bool F32>
+__device__ __forceinline__ void line_narrow_walk(const int64_t i0, const int depth_chunk, const int subset, int n_depth, int64_t n_nu,
+                                                 const double* __restrict__ nus, int64_t nu_begin, int64_t nu_count,
+                                                 const double* __restrict__ line_nus, LineWork w, double* __restrict__ out, int64_t pld)
 {
+    constexpr int kStretch = SUB ? 256 : 64;
+    // (2) where the first trip starts.  At the list's own stretches (base = kStretch k) wherever the stretch a line falls into decides
+    // which partial sum its term joins — SUB: the run index of a line; F32: the fp32 sum of a trip, folded into the fp64 sum once per
+    // trip — because which terms share a sum must not depend on where the candidate range of a frequency, or of a group of F
+    // frequencies, happens to start: F follows the launch's width, and a shard's differs from the whole grid's.  The sequential
+    // fp64 sum has no such groups and starts at its first candidate.
+    constexpr bool kListAligned = SUB || F32;
+    // (3) the records and the term: fp64 ones for region1_setup and voigt_add (raw inputs through narrow_params), or fp32 ones for
+    // voigt_add32
+    using Rec = std::conditional_t<F32, float, double>;
+    using RecNu = std::conditional_t<F32, float2v, double>;
     const int lane = threadIdx.x & 63;
     const int d = depth_chunk * 64 + lane;
     const bool valid = d < n_depth;
     const int dc = valid ? d : n_depth - 1;
-    const unsigned dcu = (unsigned)dc;
-    const bool one_gamma = w.narrow_raw == 1;  // (raw inputs with gammas (N_l, 1): the line's one value for every depth)
+    [[maybe_unused]] const unsigned dcu = (unsigned)dc;
+    [[maybe_unused]] const bool one_gamma = w.narrow_raw == 1;  // (raw inputs with gammas (N_l, 1): the line's one value for every depth)
     const int ia = (int)i0;
     // lines with centre c in [i0 - H + 1, i0 + F - 1 + H]
     const int64_t pa = max(i0 - kNarrowReach + 1, (int64_t)0);
     const int64_t pb = min(i0 + F - 1 + kNarrowReach, n_nu);
     const int la = __builtin_amdgcn_readfirstlane(w.cnt_ge[pb + 1]);
     const int lb = __builtin_amdgcn_readfirstlane(w.cnt_ge[pa]);
-    double nu_k[F], acc[F];
+    [[maybe_unused]] double nu_k[F];
+    [[maybe_unused]] float nih[F], nil[F];
+    double acc[F];
     bool act[F];  // the frequency belongs to this launch's columns (wave-uniform)
 #pragma unroll
     for (int k = 0; k < F; ++k) {
         act[k] = i0 + k >= nu_begin && i0 + k < nu_begin + nu_count;
-        nu_k[k] = nus[min(i0 + k, n_nu - 1)];
+        const double nu = nus[min(i0 + k, n_nu - 1)];
+        if constexpr (F32) {
+            nih[k] = (float)nu;
+            nil[k] = (float)(nu - (double)nih[k]);
+        } else {
+            nu_k[k] = nu;
+        }
         acc[k] = 0.0;
     }
-    // lane -> candidate: 64 lines of this subset per trip, out of a stretch of 256 aligned to the LIST (lanes ascend with the line index)
-    const int lane_off = ((lane >> 4) << 6) + (subset << 4) + (lane & 15);
-    for (int base = la & ~255; base < lb; base += 256) {
+    const int lane_off = SDX_NARROW_LINE(0, lane);
+    for (int base = kListAligned ? la & ~(kStretch - 1) : la; base < lb; base += kStretch) {
         const int lc = base + lane_off;
         bool rel = false;
         int c = 0;
-        if (lc >= la && lc < lb) {
+        if ((!kListAligned || lc >= la) && lc < lb) {
             const int hwm = w.nhw_max[lc];
             c = w.centre[lc];
             rel = hwm > 0 && ia + (F - 1) >= c - hwm && ia < c + hwm;
         }
         unsigned long long m = __ballot(rel);
-        // the parameters of the NEXT relevant line are requested before the current one is evaluated
-        int h = 0, cl = 0;
-        double y = 0.0, amp = 0.0, inv = 0.0, lnu = 0.0;
-        if (m) {
-            const int bit = __builtin_ctzll(m);
-            const int l = base + ((bit >> 4) << 6) + (subset << 4) + (bit & 15);
-            const size_t ob = (size_t)l * n_depth;
-            cl = __builtin_amdgcn_readlane(c, bit);
-            h = (w.nhw + ob)[dcu], y = (w.n_y + (one_gamma ? (size_t)l : ob))[one_gamma ? 0u : dcu], amp = (w.n_amp + ob)[dcu], inv = (w.n_inv + ob)[dcu], lnu = line_nus[l];
+        [[maybe_unused]] float acc32[F];
+        if constexpr (F32) {
+#pragma unroll
+            for (int k = 0; k < F; ++k) acc32[k] = 0.f;
         }
+        // the records of the NEXT relevant line are requested before the current one is evaluated (line_narrow_wave says why, and what
+        // else was measured)
+        int h = 0, cl = 0;
+        Rec y = 0, amp = 0, inv = 0;
+        RecNu lnu{};
+        if (m) SDX_NARROW_FETCH();
         while (m) {
             m &= m - 1;
             int h_n = 0, cl_n = 0;
-            double y_n = 0.0, amp_n = 0.0, inv_n = 0.0, lnu_n = 0.0;
-            if (m) {
-                const int bit = __builtin_ctzll(m);
-                const int l = base + ((bit >> 4) << 6) + (subset << 4) + (bit & 15);
-                const size_t ob = (size_t)l * n_depth;
-                cl_n = __builtin_amdgcn_readlane(c, bit);
-                h_n = (w.nhw + ob)[dcu], y_n = (w.n_y + (one_gamma ? (size_t)l : ob))[one_gamma ? 0u : dcu], amp_n = (w.n_amp + ob)[dcu], inv_n = (w.n_inv + ob)[dcu], lnu_n = line_nus[l];
-            }
+            Rec y_n = 0, amp_n = 0, inv_n = 0;
+            RecNu lnu_n{};
+            if (m) SDX_NARROW_FETCH(_n);
             const int lo = cl - h, hi = cl + h;  // (h = 0: empty; the clamp to the grid is implied by ia + k being a grid index)
             if (valid && ia + (F - 1) >= lo && ia < hi) {
-                if (w.narrow_raw) narrow_params(inv, y, amp, inv, y, amp);  // (inv, y, amp hold dw, gamma, alpha)
-                const RegionI k1 = region1_setup(y, amp);
+                if constexpr (F32) {  // (3)
 #pragma unroll
-                for (int k = 0; k < F; ++k)
-                    if (act[k] && ia + k >= lo && ia + k < hi) acc[k] = voigt_add(acc[k], nu_k[k] - lnu, inv, y, amp, k1);
+                    for (int k = 0; k < F; ++k)
+                        if (act[k] && ia + k >= lo && ia + k < hi) acc32[k] = voigt_add32(acc32[k], ((nih[k] - lnu.x) + (nil[k] - lnu.y)) * inv, y, amp);
+                } else {
+                    if (w.narrow_raw) narrow_params(inv, y, amp, inv, y, amp);  // (inv, y, amp hold dw, gamma, alpha)
+                    const RegionI k1 = region1_setup(y, amp);
+#pragma unroll
+                    for (int k = 0; k < F; ++k)
+                        if (act[k] && ia + k >= lo && ia + k < hi) acc[k] = voigt_add(acc[k], nu_k[k] - lnu, inv, y, amp, k1);
+                }
             }
             h = h_n, cl = cl_n, y = y_n, amp = amp_n, inv = inv_n, lnu = lnu_n;
         }
-    }
+        if constexpr (F32) {
 #pragma unroll
-    for (int k = 0; k < F; ++k) acc_out[k] = acc[k];  // (the four subsets of a group meet in the kernel's common reduction)
+            for (int k = 0; k < F; ++k) acc[k] += (double)acc32[k];
+        }
+    }
+    // (4) where the sums go: the narrow plane, or SUB: the kernel's common reduction, where the four subsets of a group meet
+#pragma unroll
+    for (int k = 0; k < F; ++k) {
+        if constexpr (SUB) out[k] = acc[k];
+        else if (valid && act[k]) out[(size_t)d * pld + (i0 + k - nu_begin)] = acc[k];
+    }
 }
+#undef SDX_NARROW_FETCH
+#undef SDX_NARROW_LINE
 
-// The narrow role of the mixed-precision mode: the same walk, every term evaluated by voigt_add32 (packed fp32, all four
-// regions) from fp32 records; the frequency difference comes from the hi + lo float pairs of both frequencies (exact to
-// 2^-48 of the frequency, i.e. ~1e-7 of a narrow window's reach), the terms of one 64-candidate chunk gather in an fp32
-// sum that goes into the fp64 sum once per chunk.
+// The one-frequency walk of the mixed-precision mode: what line_narrow_walk<1, false, true> would be, as text of its own (a wave past
+// the shard's end returns instead of keeping act[]).  Folding it into the walk was tried in two spellings: k_line_all_mixed<4, false,
+// false> and <4, false, true> came out 26 and 15 instructions shorter but with 56 and 80 spilled SGPRs against 55 and 78, and the line
+// path takes no spill more than its parent's (profiles/EXPERIMENTS.md): it stays.
 __device__ __forceinline__ void line_narrow_wave32(const int64_t i, const int depth_chunk, int n_depth, int64_t n_nu, const double* __restrict__ nus,
                                                           int64_t nu_begin, int64_t nu_count, LineWork w, double* __restrict__ plane, int64_t pld)
 {
@@ -1962,9 +1956,7 @@ __device__ __forceinline__ void line_narrow_wave32(const int64_t i, const int de
     const double nu_i = nus[i];
     const float nih = (float)nu_i, nil = (float)(nu_i - (double)nih);
     double acc = 0.0;
-    // (chunks of 64 candidates aligned to the LIST — base = 64 k — not to this frequency's first candidate: the fp32 sum of a chunk
-    // is folded into the fp64 sum once per chunk, and which terms share a chunk must not depend on where the candidate range of a
-    // frequency, or of a group of F frequencies, happens to start — F follows the launch's width, a shard's differs from the whole grid's)
+    // (trips aligned to the list, like every walk with fp32 sums: (2) in line_narrow_walk)
     for (int base = la & ~63; base < lb; base += 64) {
         const int lc = base + lane;
         bool rel = false;
@@ -2004,163 +1996,6 @@ __device__ __forceinline__ void line_narrow_wave32(const int64_t i, const int de
         acc += (double)acc32;
     }
     if (valid) plane[(size_t)d * pld + (i - nu_begin)] = acc;
-}
-
-// ... and for F consecutive frequencies per wave, like line_narrow_group: a visited line's fp32 records serve up to F evaluations.
-template <int F>
-__device__ __forceinline__ void line_narrow_group32(const int64_t i0, const int depth_chunk, int n_depth, int64_t n_nu, const double* __restrict__ nus,
-                                                    int64_t nu_begin, int64_t nu_count, LineWork w, double* __restrict__ plane, int64_t pld)
-{
-    const int lane = threadIdx.x & 63;
-    const int d = depth_chunk * 64 + lane;
-    const bool valid = d < n_depth;
-    const int dc = valid ? d : n_depth - 1;
-    const int ia = (int)i0;
-    const int64_t pa = max(i0 - kNarrowReach + 1, (int64_t)0);
-    const int64_t pb = min(i0 + F - 1 + kNarrowReach, n_nu);
-    const int la = __builtin_amdgcn_readfirstlane(w.cnt_ge[pb + 1]);
-    const int lb = __builtin_amdgcn_readfirstlane(w.cnt_ge[pa]);
-    float nih[F], nil[F];
-    double acc[F];
-    bool act[F];
-#pragma unroll
-    for (int k = 0; k < F; ++k) {
-        act[k] = i0 + k >= nu_begin && i0 + k < nu_begin + nu_count;
-        const double nu = nus[min(i0 + k, n_nu - 1)];
-        nih[k] = (float)nu;
-        nil[k] = (float)(nu - (double)nih[k]);
-        acc[k] = 0.0;
-    }
-    // (chunks of 64 candidates aligned to the LIST — base = 64 k — not to this frequency's first candidate: the fp32 sum of a chunk
-    // is folded into the fp64 sum once per chunk, and which terms share a chunk must not depend on where the candidate range of a
-    // frequency, or of a group of F frequencies, happens to start — F follows the launch's width, a shard's differs from the whole grid's)
-    for (int base = la & ~63; base < lb; base += 64) {
-        const int lc = base + lane;
-        bool rel = false;
-        int c = 0;
-        if (lc >= la && lc < lb) {
-            const int hwm = w.nhw_max[lc];
-            c = w.centre[lc];
-            rel = hwm > 0 && ia + (F - 1) >= c - hwm && ia < c + hwm;
-        }
-        unsigned long long m = __ballot(rel);
-        float acc32[F];
-#pragma unroll
-        for (int k = 0; k < F; ++k) acc32[k] = 0.f;
-        int h = 0, cl = 0;
-        float y = 0.f, amp = 0.f, inv = 0.f;
-        float2v lnu = {0.f, 0.f};
-        if (m) {
-            const int bit = __builtin_ctzll(m);
-            const int l = base + bit;
-            const size_t o = (size_t)l * n_depth + dc;
-            cl = __builtin_amdgcn_readlane(c, bit);
-            h = w.nhw[o], y = w.n_y32[o], amp = w.n_amp32[o], inv = w.n_inv32[o], lnu = w.lnu32[l];
-        }
-        while (m) {
-            m &= m - 1;
-            int h_n = 0, cl_n = 0;
-            float y_n = 0.f, amp_n = 0.f, inv_n = 0.f;
-            float2v lnu_n = {0.f, 0.f};
-            if (m) {
-                const int bit = __builtin_ctzll(m);
-                const int l = base + bit;
-                const size_t o = (size_t)l * n_depth + dc;
-                cl_n = __builtin_amdgcn_readlane(c, bit);
-                h_n = w.nhw[o], y_n = w.n_y32[o], amp_n = w.n_amp32[o], inv_n = w.n_inv32[o], lnu_n = w.lnu32[l];
-            }
-            const int lo = cl - h, hi = cl + h;
-            if (valid && ia + (F - 1) >= lo && ia < hi) {
-#pragma unroll
-                for (int k = 0; k < F; ++k)
-                    if (act[k] && ia + k >= lo && ia + k < hi) acc32[k] = voigt_add32(acc32[k], ((nih[k] - lnu.x) + (nil[k] - lnu.y)) * inv, y, amp);
-            }
-            h = h_n, cl = cl_n, y = y_n, amp = amp_n, inv = inv_n, lnu = lnu_n;
-        }
-#pragma unroll
-        for (int k = 0; k < F; ++k) acc[k] += (double)acc32[k];
-    }
-#pragma unroll
-    for (int k = 0; k < F; ++k)
-        if (valid && act[k]) plane[(size_t)d * pld + (i0 + k - nu_begin)] = acc[k];
-}
-
-// ... and the subset walk of dense long lists (line_narrow_subsets) in the mixed-precision mode: the fp32 terms of one trip — the 64
-// candidates a wave takes out of a 256-line stretch of the list — gather in an fp32 sum that goes into the fp64 sum once per trip.
-template <int F>
-__device__ __forceinline__ void line_narrow_subsets32(const int64_t i0, const int depth_chunk, const int subset, int n_depth, int64_t n_nu,
-                                                      const double* __restrict__ nus, int64_t nu_begin, int64_t nu_count, LineWork w,
-                                                      double* __restrict__ acc_out)
-{
-    const int lane = threadIdx.x & 63;
-    const int d = depth_chunk * 64 + lane;
-    const bool valid = d < n_depth;
-    const int dc = valid ? d : n_depth - 1;
-    const int ia = (int)i0;
-    const int64_t pa = max(i0 - kNarrowReach + 1, (int64_t)0);
-    const int64_t pb = min(i0 + F - 1 + kNarrowReach, n_nu);
-    const int la = __builtin_amdgcn_readfirstlane(w.cnt_ge[pb + 1]);
-    const int lb = __builtin_amdgcn_readfirstlane(w.cnt_ge[pa]);
-    float nih[F], nil[F];
-    double acc[F];
-    bool act[F];
-#pragma unroll
-    for (int k = 0; k < F; ++k) {
-        act[k] = i0 + k >= nu_begin && i0 + k < nu_begin + nu_count;
-        const double nu = nus[min(i0 + k, n_nu - 1)];
-        nih[k] = (float)nu;
-        nil[k] = (float)(nu - (double)nih[k]);
-        acc[k] = 0.0;
-    }
-    const int lane_off = ((lane >> 4) << 6) + (subset << 4) + (lane & 15);
-    for (int base = la & ~255; base < lb; base += 256) {
-        const int lc = base + lane_off;
-        bool rel = false;
-        int c = 0;
-        if (lc >= la && lc < lb) {
-            const int hwm = w.nhw_max[lc];
-            c = w.centre[lc];
-            rel = hwm > 0 && ia + (F - 1) >= c - hwm && ia < c + hwm;
-        }
-        unsigned long long m = __ballot(rel);
-        float acc32[F];
-#pragma unroll
-        for (int k = 0; k < F; ++k) acc32[k] = 0.f;
-        int h = 0, cl = 0;
-        float y = 0.f, amp = 0.f, inv = 0.f;
-        float2v lnu = {0.f, 0.f};
-        if (m) {
-            const int bit = __builtin_ctzll(m);
-            const int l = base + ((bit >> 4) << 6) + (subset << 4) + (bit & 15);
-            const size_t o = (size_t)l * n_depth + dc;
-            cl = __builtin_amdgcn_readlane(c, bit);
-            h = w.nhw[o], y = w.n_y32[o], amp = w.n_amp32[o], inv = w.n_inv32[o], lnu = w.lnu32[l];
-        }
-        while (m) {
-            m &= m - 1;
-            int h_n = 0, cl_n = 0;
-            float y_n = 0.f, amp_n = 0.f, inv_n = 0.f;
-            float2v lnu_n = {0.f, 0.f};
-            if (m) {
-                const int bit = __builtin_ctzll(m);
-                const int l = base + ((bit >> 4) << 6) + (subset << 4) + (bit & 15);
-                const size_t o = (size_t)l * n_depth + dc;
-                cl_n = __builtin_amdgcn_readlane(c, bit);
-                h_n = w.nhw[o], y_n = w.n_y32[o], amp_n = w.n_amp32[o], inv_n = w.n_inv32[o], lnu_n = w.lnu32[l];
-            }
-            const int lo = cl - h, hi = cl + h;
-            if (valid && ia + (F - 1) >= lo && ia < hi) {
-#pragma unroll
-                for (int k = 0; k < F; ++k)
-                    if (act[k] && ia + k >= lo && ia + k < hi) acc32[k] = voigt_add32(acc32[k], ((nih[k] - lnu.x) + (nil[k] - lnu.y)) * inv, y, amp);
-            }
-            h = h_n, cl = cl_n, y = y_n, amp = amp_n, inv = inv_n, lnu = lnu_n;
-        }
-#pragma unroll
-        for (int k = 0; k < F; ++k) acc[k] += (double)acc32[k];
-    }
-#pragma unroll
-    for (int k = 0; k < F; ++k) acc_out[k] = acc[k];  // (the four subsets of a group meet in the kernel's common reduction)
 }
 
 // FAR FIELD of the line opacity (far_eligible above): the third plane of the line kernels.  One workgroup owns (depth d, a unit of
@@ -2615,19 +2450,15 @@ __device__ __forceinline__ void line_all_body(LineLaunchArg<FAR> g, int n_split,
         double* __restrict__ nplane = planes + (size_t)n_depth * pld;
         if constexpr (SUBSETS) {
             static_assert(!SUBSETS || R == 4, "the common reduction: R points per wide lane = F frequencies per narrow group");
-            if constexpr (MIXED) line_narrow_subsets32<4>(i0, chunk, wave, n_depth, n_nu, nus, nu_begin, nu_count, w, part);
-            else line_narrow_subsets<4>(i0, chunk, wave, n_depth, n_nu, nus, nu_begin, nu_count, line_nus, w, part);
+            line_narrow_walk<4, true, MIXED>(i0, chunk, wave, n_depth, n_nu, nus, nu_begin, nu_count, line_nus, w, part, 0);
             out_wide = false;
             out_row = chunk * 64 + (int)(threadIdx.x & 63);
             out_valid = out_row < n_depth;
             out_col = (int)i0;
-        } else if constexpr (MIXED) {
-            if (F == 4) line_narrow_group32<4>(i0, chunk, n_depth, n_nu, nus, nu_begin, nu_count, w, nplane, pld);
-            else if (F == 2) line_narrow_group32<2>(i0, chunk, n_depth, n_nu, nus, nu_begin, nu_count, w, nplane, pld);
-            else line_narrow_wave32(i0, chunk, n_depth, n_nu, nus, nu_begin, nu_count, w, nplane, pld);
         } else {
-            if (F == 4) line_narrow_group<4>(i0, chunk, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, nplane, pld);
-            else if (F == 2) line_narrow_group<2>(i0, chunk, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, nplane, pld);
+            if (F == 4) line_narrow_walk<4, false, MIXED>(i0, chunk, 0, n_depth, n_nu, nus, nu_begin, nu_count, line_nus, w, nplane, pld);
+            else if (F == 2) line_narrow_walk<2, false, MIXED>(i0, chunk, 0, n_depth, n_nu, nus, nu_begin, nu_count, line_nus, w, nplane, pld);
+            else if constexpr (MIXED) line_narrow_wave32(i0, chunk, n_depth, n_nu, nus, nu_begin, nu_count, w, nplane, pld);
             else line_narrow_wave(i0, chunk, n_depth, n_nu, nus, nu_begin, nu_count, n_lines, line_nus, w, nplane, pld);
         }
     }
