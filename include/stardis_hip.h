@@ -540,6 +540,47 @@ int sdx_observe_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double
 int sdx_observe_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
                     const double* edges, const double* sigma, double doppler, double* out);
 
+/* ---- the adjoint of the instrument model: from pixel weights to grid weights -----------------------
+ * The vector-Jacobian product of sdx_observe_dev: a vector c over the pixels pulled back to a vector over the grid points, so that the
+ * derivative of any functional of the OBSERVED pixels (a chi-square against data, an equivalent width measured on the detector) becomes
+ * weights over the model's own columns — what sdx_line_adjoint_dev and the response functions take.  In the notation above, every
+ * quantity formed with the same operations and roundings as k_observe:
+ *     x_i = lambdas[i] D,  h_i its trapezoid weight,  lo_j = edges[j] - 8 sigma[j],  hi_j = edges[j+1] + 8 sigma[j],
+ *     covered_j = (lo_j >= x_0 && hi_j <= x_{n-1}),  w_ij = r_ij h_i  (bit for bit the weight of k_observe's loop),
+ *     den_j = sum_i w_ij g_i  (g = 1, or reference),   out_j = (sum_i w_ij flux[i]) / den_j   over the window lo_j <= x_i <= hi_j,
+ * and for the pixel vector pixel_weight = c[n_pix]
+ *     a_j          = covered_j ? c_j / den_j : 0      (c_j of an uncovered pixel is never used, whatever it holds, NaN included)
+ *     w_flux[i]    = sum over the j with covered_j and lo_j <= x_i <= hi_j of  w_ij a_j
+ *     w_reference[i] = the same sum of  w_ij (-out_j a_j)     (with a reference only: the cotangent of `reference`)
+ * so that  sum_j c_j out_j = sum_i w_flux[i] flux[i]  over the covered pixels and  sum_j c_j d out_j / d reference[i] = w_reference[i].
+ * A grid point in no covered pixel's window is exactly 0.0.  The windows are fixed: no derivative to D or sigma.
+ * nus[n] (optional) turns weights over F_lambda into weights over F_nu, the transpose of sdx_flux_nu_to_lambda_dev: both outputs
+ * become (w nus[i]) / lambdas[i], and feed sdx_response_weight_dev (nu_weight) directly.
+ * sigma is per pixel, so lo_j and hi_j need not ascend with j and the pixels that hold a point need not be consecutive: the
+ * candidates of a point are bracketed by a prefix maximum of hi and a suffix minimum of lo (exact: max and min round nothing) and each is
+ * tested with the predicate above — the set is exactly the transpose of the forward windows on an ascending grid.
+ * fp64, every operation one rounded operation; no floating-point atomics; the order of every sum follows from the arrays alone
+ * (ascending j dealt round-robin to the lanes of the point, then a butterfly): two calls, and the replay of a captured graph, give the
+ * same bits.  The lanes per point (8 or 64) follow from an estimate of the pixels per point, 1 + 16 sigma / (the mean pixel width) with
+ * sigma that of pixel floor((x_i - edges[0]) / mean width) clamped to the array, against 32, over groups of 8 consecutive points.
+ * sdx_observe_adjoint_dev: device pointers, asynchronous on the context's stream, capturable; D is read from device memory when the
+ * kernels run (doppler_dev; NULL: 1), so a captured call follows a new velocity.  Its scratch (a, -out a and the two scans: 4 n_pix
+ * doubles and a little) is the context's and grows outside a capture only (one eager call of the same size first).  flux is read only with a
+ * reference (NULL otherwise); nus and w_reference are optional.  n_pix = 0 writes zeros to the outputs and returns.  SDX_ERR_ARG
+ * before anything is enqueued, the context usable afterwards: n < 2, a null required pointer (lambdas, w_flux; edges, sigma,
+ * pixel_weight unless n_pix = 0), w_reference without reference, reference without flux.  The arrays' contents cannot be checked
+ * here: whatever they hold (NaN, unordered values, sigma <= 0), every access stays inside the arrays and every loop has a bound that
+ * follows from n and n_pix — the result is then meaningless, never an out-of-range access.
+ * Stage name for sdx_profile_get: "k_observe_adjoint" (four launches: per-pixel factors, the scans in two, the gather per point). */
+int sdx_observe_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
+                            const double* edges, const double* sigma, const double* doppler_dev, const double* pixel_weight,
+                            const double* nus, double* w_flux, double* w_reference);
+/* host-buffer twin: host pointers, the Doppler factor by value.  lambdas, edges, sigma and doppler are checked as by sdx_observe_f64
+ * before any upload (SDX_ERR_ARG with a message that names the argument); pixel_weight may hold anything. */
+int sdx_observe_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
+                            const double* edges, const double* sigma, double doppler, const double* pixel_weight, const double* nus,
+                            double* w_flux, double* w_reference);
+
 /* Everything in one call for resident data: pre-pass + line opacity + total (above) + raytrace (F_nu
  * overwritten).  F_nu is [n_depth][ld].  alpha_line_out and total_alphas ([n_depth][ld]) are OPTIONAL outputs (NULL: the
  * plane is never written to HBM — the reference only reads them back through opacities_dict / Opacities.total_alphas;

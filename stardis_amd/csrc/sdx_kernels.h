@@ -4663,9 +4663,10 @@ __device__ __forceinline__ void obs_narrow(ObsBracket& b, int W, int c, int64_t 
 }
 // The window of a pixel, by its W lanes (W = 64: the wave; W = 8: each of the wave's eight segments its own pixel): i0 = the first index
 // with x >= lo, i1 = the first with x > hi, searched side by side (one round = one load per lane and bound).  Every lane of the wave
-// calls this; a pixel that is not searched (`on` false) reads nothing.
-__device__ __forceinline__ void obs_windows(const double* __restrict__ lam, int64_t n, double D, double lo, double hi, bool on, int W, int lane,
-                                            int64_t& i0, int64_t& i1)
+// calls this; a pixel that is not searched (`on` false) reads nothing.  The two bounds may be searched in two arrays of n values (the
+// forward kernel passes the grid twice; the adjoint's gather passes its two scans, with D = 1, which rounds nothing).
+__device__ __forceinline__ void obs_windows(const double* lam_a, const double* lam_b, int64_t n, double D, double lo, double hi, bool on, int W,
+                                            int lane, int64_t& i0, int64_t& i1)
 {
     const int t = W == 64 ? lane : lane & 7, shift = W == 64 ? 0 : lane & ~7;
     const unsigned long long seg = W == 64 ? ~0ull : 0xffull;
@@ -4673,7 +4674,7 @@ __device__ __forceinline__ void obs_windows(const double* __restrict__ lam, int6
     while (__any(a.hi > a.lo || b.hi > b.lo)) {
         int64_t ca, cb;
         const int64_t pa = obs_probe(a, W, t, ca), pb = obs_probe(b, W, t, cb);
-        const double xa = pa >= 0 ? mul_rn(lam[pa], D) : 0.0, xb = pb >= 0 ? mul_rn(lam[pb], D) : 0.0;
+        const double xa = pa >= 0 ? mul_rn(lam_a[pa], D) : 0.0, xb = pb >= 0 ? mul_rn(lam_b[pb], D) : 0.0;
         const unsigned long long ma = __ballot(pa >= 0 && xa < lo), mb = __ballot(pb >= 0 && xb <= hi);
         obs_narrow(a, W, __popcll((ma >> shift) & seg), ca);
         obs_narrow(b, W, __popcll((mb >> shift) & seg), cb);
@@ -4694,15 +4695,22 @@ __device__ __forceinline__ double obs_response(double e0, double e1, double x, d
     return mul_rn(0.5, sub_rn(erf(b), erf(a)));
 }
 
-__global__ __launch_bounds__(kBlock) void k_observe(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
-                                                    const double* __restrict__ ref, int64_t n_pix, const double* __restrict__ edges,
-                                                    const double* __restrict__ sigma, const double* __restrict__ doppler,
-                                                    double* __restrict__ out)
+// What a wave of k_observe's mapping sums for its pixel(s): num = sum_i w_ij flux[i] (flux = nullptr: not formed) and den = sum_i w_ij g_i
+// over the window, closed by the butterfly, in every lane of the pixel.  false: the wave has no pixel and leaves.
+struct ObsPixel {
+    int64_t pj;  // the lane's pixel (may lie behind n_pix in the last group: nothing is searched, nothing may be written)
+    int t;       // the lane's index among the pixel's W lanes
+    bool covered;
+    double num, den;
+};
+__device__ __forceinline__ bool obs_pixel_sums(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                               const double* __restrict__ ref, int64_t n_pix, const double* __restrict__ edges,
+                                               const double* __restrict__ sigma, const double* __restrict__ doppler, ObsPixel& p)
 {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     const int64_t first = wave - wave % kObsGroup;  // the group's first pixel
-    if (first >= n_pix) return;
+    if (first >= n_pix) return false;
     const double D = doppler ? *doppler : 1.0;
     const double x_first = mul_rn(lam[0], D), x_last = mul_rn(lam[n - 1], D);
 
@@ -4713,9 +4721,9 @@ __global__ __launch_bounds__(kBlock) void k_observe(int64_t n, const double* __r
     const double expected = (e1 - e0 + 16.0 * s) * (double)(n - 1) / (x_last - x_first);  // points in the window at the mean spacing
     int W = 8;
     if (__all(!(expected > (double)kObsShort))) {
-        if (wave != first) return;
+        if (wave != first) return false;
     } else {
-        if (wave >= n_pix) return;
+        if (wave >= n_pix) return false;
         pj = wave, W = 64;
         e0 = edges[pj], e1 = edges[pj + 1], s = sigma[pj];
     }
@@ -4724,18 +4732,191 @@ __global__ __launch_bounds__(kBlock) void k_observe(int64_t n, const double* __r
     const double reach = mul_rn(8.0, s), lo = sub_rn(e0, reach), hi = add_rn(e1, reach), s2 = mul_rn(s, 1.4142135623730951);
     const bool covered = pj < n_pix && lo >= x_first && hi <= x_last;
     int64_t i0, i1;
-    obs_windows(lam, n, D, lo, hi, covered, W, lane, i0, i1);
+    obs_windows(lam, lam, n, D, lo, hi, covered, W, lane, i0, i1);
 
     double num = 0.0, den = 0.0;
     for (int64_t i = i0 + t; i < i1; i += W) {
         const double x = mul_rn(lam[i], D);
         const double below = mul_rn(lam[i > 0 ? i - 1 : 0], D), above = mul_rn(lam[i < n - 1 ? i + 1 : n - 1], D);
         const double w = mul_rn(obs_response(e0, e1, x, s2), mul_rn(sub_rn(above, below), 0.5));
-        num = add_rn(num, mul_rn(w, flux[i]));
+        if (flux) num = add_rn(num, mul_rn(w, flux[i]));
         den = add_rn(den, ref ? mul_rn(w, ref[i]) : w);
     }
     for (int off = W >> 1; off > 0; off >>= 1) num = add_rn(num, __shfl_xor(num, off)), den = add_rn(den, __shfl_xor(den, off));
-    if (t == 0 && pj < n_pix) out[pj] = covered ? num / den : __longlong_as_double(0x7ff8000000000000LL);
+    p = ObsPixel{pj, t, covered, num, den};
+    return true;
+}
+
+__global__ __launch_bounds__(kBlock) void k_observe(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                                    const double* __restrict__ ref, int64_t n_pix, const double* __restrict__ edges,
+                                                    const double* __restrict__ sigma, const double* __restrict__ doppler,
+                                                    double* __restrict__ out)
+{
+    ObsPixel p;
+    if (!obs_pixel_sums(n, lam, flux, ref, n_pix, edges, sigma, doppler, p)) return;
+    if (p.t == 0 && p.pj < n_pix) out[p.pj] = p.covered ? p.num / p.den : __longlong_as_double(0x7ff8000000000000LL);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The adjoint of the instrument model (include/stardis_hip.h, sdx_observe_adjoint_dev): a vector c over the pixels pulled back to the
+// grid points,
+//     a_j = covered_j ? c_j / den_j : 0,   b_j = -out_j a_j,
+//     w_flux[i] = sum over the covered j with lo_j <= x_i <= hi_j of  w_ij a_j,     w_ref[i] = the same sum of  w_ij b_j,
+// w_ij = r_ij h_i the weight of k_observe's loop, bit for bit.  Four launches:
+//   k_observe_adjoint_pixels  k_observe's own mapping and sums (obs_pixel_sums) -> a, and b with a reference;
+//   k_observe_adjoint_tiles,  PH_j = max_{j' <= j} hi_j' and SL_j = min_{j' >= j} lo_j', in tiles of kObsScanTile pixels: the tiles'
+//   k_observe_adjoint_scan    own max and min first, then every tile scans itself behind those of the tiles before it (one block
+//                             walking 1e5 pixels took three times the forward kernel's time: EXPERIMENTS).  sigma is per pixel, so
+//                             lo and hi need not ascend with j and the pixels that hold a point need not be consecutive; PH and SL do
+//                             ascend, max and min round nothing, and PH_j >= hi_j, SL_j <= lo_j: every pixel that holds x lies in
+//                             [jA, jB), jA = the first j with PH_j >= x, jB = one past the last with SL_j <= x;
+//   k_observe_adjoint         the gather: W lanes per grid point, the points in groups of kObsGroup.  A group none of whose points is
+//                             expected to lie in more than kObsShort pixels — 1 + 16 sigma / (the MEAN pixel width), sigma that of the
+//                             pixel the point would fall in were all pixels of the mean width: an estimate, taken before anything is
+//                             searched — is done by its FIRST wave, eight lanes per point (the forward kernel's reasoning: an
+//                             instrument sampled at two pixels per FWHM has a point in ~15 pixels, and a wave per point would keep 15
+//                             lanes of 64 busy); otherwise every wave does its own point with 64 lanes.  The estimate only chooses
+//                             the mapping; either serves any point.  The point's lanes search jA and jB together (obs_windows on PH
+//                             and SL), the candidates are dealt to them round-robin from jA, each is tested with the forward's own
+//                             predicate (covered_j && lo_j <= x_i <= hi_j, the same roundings), each lane adds its terms in
+//                             ascending j and a butterfly over the W lanes (offsets W/2 ... 1) adds the partials.
+// No floating-point atomics; the order of every sum follows from the arrays alone.  A point in no covered window is exactly 0.
+//
+// Whatever the arrays hold (NaN, unordered values, sigma <= 0): the per-pixel pass has k_observe's bounds; a scan thread reads its own
+// pixel, if that lies inside [0, n_pix), and the partials of the n_tiles = ceil(n_pix / kObsScanTile) tiles; the searches read PH and
+// SL only inside their brackets within [0, n_pix) and shrink them at least W + 1 times per round, so 0 <= jA <= jB <= n_pix; a lane
+// makes at most (jB - jA) / W + 1 trips and reads edges[j], edges[j + 1], sigma[j], a[j], b[j] for jA <= j < jB alone; the estimate's
+// pixel index is clamped to [0, n_pix) (a NaN compares false and gives 0).
+constexpr int kObsScanTile = kBlock;  // positions per block of the two scan launches: one per thread
+
+__global__ __launch_bounds__(kBlock) void k_observe_adjoint_pixels(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                                                   const double* __restrict__ ref, int64_t n_pix,
+                                                                   const double* __restrict__ edges, const double* __restrict__ sigma,
+                                                                   const double* __restrict__ doppler, const double* __restrict__ c,
+                                                                   double* __restrict__ a, double* __restrict__ b)
+{
+    ObsPixel p;
+    if (!obs_pixel_sums(n, lam, ref ? flux : nullptr, ref, n_pix, edges, sigma, doppler, p)) return;
+    if (p.t != 0 || p.pj >= n_pix) return;
+    const double aj = p.covered ? c[p.pj] / p.den : 0.0;  // (c of an uncovered pixel is never used)
+    a[p.pj] = aj;
+    if (ref) b[p.pj] = p.covered ? mul_rn(-(p.num / p.den), aj) : 0.0;
+}
+
+// One scan position: position p of direction `up` is pixel p and carries hi_p; of the other, pixel n_pix - 1 - p and lo of that pixel.
+// A position behind the last pixel carries the identity of the direction's max or min.
+struct ObsScan {
+    bool up;
+    __device__ __forceinline__ double none() const { return __longlong_as_double(up ? 0xfff0000000000000LL : 0x7ff0000000000000LL); }
+    __device__ __forceinline__ double pick(double r, double v) const { return up ? (v > r ? v : r) : (v < r ? v : r); }
+    __device__ __forceinline__ double value(int64_t p, int64_t n_pix, const double* __restrict__ edges, const double* __restrict__ sigma) const
+    {
+        if (p >= n_pix) return none();
+        const int64_t j = up ? p : n_pix - 1 - p;
+        const double reach = mul_rn(8.0, sigma[j]);
+        return up ? add_rn(edges[j + 1], reach) : sub_rn(edges[j], reach);
+    }
+    // the block's max or min, in every thread (lds: one double per wave; max and min round nothing, so the order is free)
+    __device__ __forceinline__ double block(double v, double* lds) const
+    {
+        for (int off = 32; off > 0; off >>= 1) v = pick(v, __shfl_xor(v, off));
+        if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+        __syncthreads();
+        double r = lds[0];
+        for (int w = 1; w < kBlock / 64; ++w) r = pick(r, lds[w]);
+        __syncthreads();
+        return r;
+    }
+};
+
+// tiles[dir n_tiles + k]: the max of hi (dir 0) or the min of lo (dir 1) over the kObsScanTile positions of tile k
+__global__ __launch_bounds__(kBlock) void k_observe_adjoint_tiles(int64_t n_pix, const double* __restrict__ edges, const double* __restrict__ sigma,
+                                                                  int64_t n_tiles, double* __restrict__ tiles)
+{
+    __shared__ double lds[kBlock / 64];
+    const ObsScan sc{blockIdx.y == 0};
+    const double r = sc.block(sc.value((int64_t)blockIdx.x * kObsScanTile + threadIdx.x, n_pix, edges, sigma), lds);
+    if (threadIdx.x == 0) tiles[blockIdx.y * n_tiles + blockIdx.x] = r;
+}
+
+// PH (blockIdx.y = 0) and SL (1): a block takes the partials of the tiles before its own, then scans its own tile (within the wave by
+// shuffles, the waves before it through LDS)
+__global__ __launch_bounds__(kBlock) void k_observe_adjoint_scan(int64_t n_pix, const double* __restrict__ edges, const double* __restrict__ sigma,
+                                                                 int64_t n_tiles, const double* __restrict__ tiles, double* __restrict__ PH,
+                                                                 double* __restrict__ SL)
+{
+    __shared__ double lds[kBlock / 64], totals[kBlock / 64];
+    const ObsScan sc{blockIdx.y == 0};
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    double carry = sc.none();
+    for (int64_t k = t; k < (int64_t)blockIdx.x; k += kBlock) carry = sc.pick(carry, tiles[blockIdx.y * n_tiles + k]);
+    carry = sc.block(carry, lds);
+    const int64_t p = (int64_t)blockIdx.x * kObsScanTile + t;
+    double v = sc.value(p, n_pix, edges, sigma);
+    for (int off = 1; off < 64; off <<= 1) {
+        const double before = __shfl_up(v, off);
+        if (lane >= off) v = sc.pick(v, before);
+    }
+    if (lane == 63) totals[wave] = v;
+    __syncthreads();
+    for (int w = 0; w < wave; ++w) carry = sc.pick(carry, totals[w]);
+    if (p < n_pix) (sc.up ? PH : SL)[sc.up ? p : n_pix - 1 - p] = sc.pick(carry, v);
+}
+
+__global__ __launch_bounds__(kBlock) void k_observe_adjoint(int64_t n, const double* __restrict__ lam, int64_t n_pix,
+                                                            const double* __restrict__ edges, const double* __restrict__ sigma,
+                                                            const double* __restrict__ doppler, const double* __restrict__ a,
+                                                            const double* __restrict__ b, const double* __restrict__ PH,
+                                                            const double* __restrict__ SL, const double* __restrict__ nus,
+                                                            double* __restrict__ w_flux, double* __restrict__ w_ref)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    const int64_t first = wave - wave % kObsGroup;  // the group's first point
+    if (first >= n) return;
+    const double D = doppler ? *doppler : 1.0;
+    const double x_first = mul_rn(lam[0], D), x_last = mul_rn(lam[n - 1], D);
+
+    // the group's mapping, from point first + lane / 8 in every lane
+    int64_t pi = first + (lane >> 3);
+    const double e_first = edges[0], width = (edges[n_pix] - e_first) / (double)n_pix;  // the mean pixel width
+    double expected = 0.0;
+    if (pi < n) {
+        const double q = (mul_rn(lam[pi], D) - e_first) / width;
+        const int64_t jq = q > 0.0 ? (q < (double)n_pix ? (int64_t)q : n_pix - 1) : 0;
+        expected = (width + 16.0 * sigma[jq]) / width;  // pixels that hold the point
+    }
+    int W = 8;
+    if (__all(!(expected > (double)kObsShort))) {
+        if (wave != first) return;
+    } else {
+        if (wave >= n) return;
+        pi = wave, W = 64;
+    }
+    const int t = W == 64 ? lane : lane & 7;
+    const bool on = pi < n;
+    const int64_t i = on ? pi : n - 1;
+
+    const double x = mul_rn(lam[i], D);
+    const double below = mul_rn(lam[i > 0 ? i - 1 : 0], D), above = mul_rn(lam[i < n - 1 ? i + 1 : n - 1], D);
+    const double h = mul_rn(sub_rn(above, below), 0.5);
+    int64_t jA, jB;
+    obs_windows(PH, SL, n_pix, 1.0, x, x, on, W, lane, jA, jB);
+
+    double wf = 0.0, wr = 0.0;
+    for (int64_t j = jA + t; j < jB; j += W) {
+        const double e0 = edges[j], e1 = edges[j + 1], s = sigma[j];
+        const double reach = mul_rn(8.0, s), lo = sub_rn(e0, reach), hi = add_rn(e1, reach);
+        if (!(lo >= x_first && hi <= x_last && lo <= x && x <= hi)) continue;
+        const double w = mul_rn(obs_response(e0, e1, x, mul_rn(s, 1.4142135623730951)), h);
+        wf = add_rn(wf, mul_rn(w, a[j]));
+        if (b) wr = add_rn(wr, mul_rn(w, b[j]));
+    }
+    for (int off = W >> 1; off > 0; off >>= 1) wf = add_rn(wf, __shfl_xor(wf, off)), wr = add_rn(wr, __shfl_xor(wr, off));
+    if (t != 0 || !on) return;
+    // (the transpose of k_flux_nu_to_lambda, F_lambda = F_nu nu / lambda: the weights of F_lambda become weights of F_nu)
+    w_flux[i] = nus ? mul_rn(wf, nus[i]) / lam[i] : wf;
+    if (w_ref) w_ref[i] = nus ? mul_rn(wr, nus[i]) / lam[i] : wr;
 }
 
 // ------------------------------------------------------------------------------------------------

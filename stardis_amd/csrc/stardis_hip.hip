@@ -86,6 +86,8 @@ struct sdx_ctx {
     size_t part_ws_bytes = 0;
     void* adj_ws = nullptr;  // the per-line sensitivities' centres, lists and partial sums (sdx_line_adjoint_dev)
     size_t adj_ws_bytes = 0;
+    void* obs_ws = nullptr;  // the instrument adjoint's per-pixel factors a, b and scans PH, SL (sdx_observe_adjoint_dev)
+    size_t obs_ws_bytes = 0;
     void* far_ws = nullptr;  // far_range of the line kernels' far field: two ints per global tile
     size_t far_ws_bytes = 0;
     // cnt_ge[N_nu + 2] (lines per centre index, for the narrow-window kernel) and the per-line integer lists: CntLayout
@@ -454,6 +456,7 @@ void sdx_destroy(sdx_ctx* ctx)
     if (ctx->part_ws) hipFree(ctx->part_ws);
     if (ctx->far_ws) hipFree(ctx->far_ws);
     if (ctx->adj_ws) hipFree(ctx->adj_ws);
+    if (ctx->obs_ws) hipFree(ctx->obs_ws);
     if (ctx->cnt_ws) hipFree(ctx->cnt_ws);
     if (ctx->io_dev) hipFree(ctx->io_dev);
     if (ctx->io_pin) hipHostFree(ctx->io_pin);
@@ -2655,6 +2658,89 @@ int sdx_observe_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double
     double* d_o = (double*)io.alloc((size_t)n_pix * f8);
     if ((rc = sdx_observe_dev(ctx, n, d_l, d_f, d_r, n_pix, d_e, d_s, d_D, d_o))) return rc;
     if ((rc = io.download(out, d_o, (size_t)n_pix * f8))) return rc;
+    return io.finish();
+}
+
+// ---- the adjoint of the instrument model: pixel weights pulled back to the grid (k_observe_adjoint) ---------------------------
+// Everything is checked before anything is enqueued.  Four launches under the stage name k_observe_adjoint: the per-pixel factors, the
+// two scans (the tiles' partials, then the tiles), the gather per grid point.
+int sdx_observe_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
+                            const double* edges, const double* sigma, const double* doppler_dev, const double* pixel_weight, const double* nus,
+                            double* w_flux, double* w_reference)
+{
+    REQUIRE(ctx && n_pix >= 0, "observe_adjoint: null context or n_pix < 0");
+    REQUIRE(n >= 2, "observe_adjoint: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && w_flux, "observe_adjoint: null pointer (lambdas and w_flux are required)");
+    REQUIRE(n_pix == 0 || (edges && sigma && pixel_weight), "observe_adjoint: null pointer (edges, sigma and pixel_weight are required)");
+    REQUIRE(reference || !w_reference, "observe_adjoint: w_reference needs a reference");
+    REQUIRE(!reference || flux, "observe_adjoint: a reference needs the flux (out_j enters the cotangent of the reference)");
+    REQUIRE((n_pix + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31) && (n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31),
+            "observe_adjoint: too many pixels or points for one launch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n_pix == 0) {
+        HIP_TRY(hipMemsetAsync(w_flux, 0, (size_t)n * sizeof(double), ctx->stream));
+        if (w_reference) HIP_TRY(hipMemsetAsync(w_reference, 0, (size_t)n * sizeof(double), ctx->stream));
+        return SDX_OK;
+    }
+    const size_t row = ((size_t)n_pix * sizeof(double) + 255) & ~(size_t)255;
+    const int64_t n_tiles = (n_pix + kObsScanTile - 1) / kObsScanTile;
+    const size_t tile_row = (2 * (size_t)n_tiles * sizeof(double) + 255) & ~(size_t)255;
+    int rc = ensure(ctx, &ctx->obs_ws, &ctx->obs_ws_bytes, 4 * row + tile_row);
+    if (rc) return rc;
+    double* const a = (double*)ctx->obs_ws;
+    double* const b = (double*)((char*)ctx->obs_ws + row);
+    double* const PH = (double*)((char*)ctx->obs_ws + 2 * row);
+    double* const SL = (double*)((char*)ctx->obs_ws + 3 * row);
+    double* const tiles = (double*)((char*)ctx->obs_ws + 4 * row);
+    {
+        // one wave per pixel, then one per grid point (a short group is done by its first wave alone)
+        const int64_t pix_waves = (n_pix + kObsGroup - 1) / kObsGroup * kObsGroup, pt_waves = (n + kObsGroup - 1) / kObsGroup * kObsGroup;
+        const int per = kBlock / 64;
+        LaunchScope ls(ctx, "k_observe_adjoint");
+        hipLaunchKernelGGL(k_observe_adjoint_pixels, dim3((unsigned)((pix_waves + per - 1) / per)), dim3(kBlock), 0, ctx->stream, n, lambdas, flux,
+                           reference, n_pix, edges, sigma, doppler_dev, pixel_weight, a, b);
+        hipLaunchKernelGGL(k_observe_adjoint_tiles, dim3((unsigned)n_tiles, 2), dim3(kBlock), 0, ctx->stream, n_pix, edges, sigma, n_tiles, tiles);
+        hipLaunchKernelGGL(k_observe_adjoint_scan, dim3((unsigned)n_tiles, 2), dim3(kBlock), 0, ctx->stream, n_pix, edges, sigma, n_tiles,
+                           (const double*)tiles, PH, SL);
+        hipLaunchKernelGGL(k_observe_adjoint, dim3((unsigned)((pt_waves + per - 1) / per)), dim3(kBlock), 0, ctx->stream, n, lambdas, n_pix, edges,
+                           sigma, doppler_dev, (const double*)a, reference ? (const double*)b : nullptr, (const double*)PH, (const double*)SL, nus,
+                           w_flux, w_reference);
+    }
+    return check_launch("k_observe_adjoint");
+}
+
+int sdx_observe_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
+                            const double* edges, const double* sigma, double doppler, const double* pixel_weight, const double* nus,
+                            double* w_flux, double* w_reference)
+{
+    int rc;
+    // the device entry's refusals, then what only the host can check, all before any copy
+    REQUIRE(ctx && n_pix >= 0, "observe_adjoint: null context or n_pix < 0");
+    REQUIRE(n >= 2, "observe_adjoint: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && w_flux && edges, "observe_adjoint: null pointer (lambdas, edges and w_flux are required)");
+    REQUIRE(n_pix == 0 || (sigma && pixel_weight), "observe_adjoint: null pointer (sigma and pixel_weight are required)");
+    REQUIRE(reference || !w_reference, "observe_adjoint: w_reference needs a reference");
+    REQUIRE(!reference || flux, "observe_adjoint: a reference needs the flux (out_j enters the cotangent of the reference)");
+    if ((rc = observe_host_check(n, lambdas, n_pix, edges, sigma, doppler))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
+    const void* src[] = {lambdas, reference ? flux : nullptr, reference, edges, sigma, &doppler, pixel_weight, nus};
+    const size_t in_bytes[] = {grid, reference ? grid : 0, reference ? grid : 0, (size_t)(n_pix + 1) * f8, (size_t)n_pix * f8, f8, (size_t)n_pix * f8,
+                               nus ? grid : 0};
+    size_t dev_need = 256 + 2 * HostIo::pad(grid), pin_need = 2 * HostIo::pad(grid) + 256;
+    for (size_t b : in_bytes) dev_need += HostIo::pad(b ? b : 8), pin_need += HostIo::pad(b);
+    HostIo io{ctx};
+    if ((rc = io.begin(dev_need, pin_need))) return rc;
+    const void* d_in[8] = {};
+    for (int k = 0; k < 8; ++k)
+        if (in_bytes[k] && (rc = io.upload(src[k], in_bytes[k], &d_in[k]))) return rc;
+    double* d_wf = (double*)io.alloc(grid);
+    double* d_wr = w_reference ? (double*)io.alloc(grid) : nullptr;
+    rc = sdx_observe_adjoint_dev(ctx, n, (const double*)d_in[0], (const double*)d_in[1], (const double*)d_in[2], n_pix, (const double*)d_in[3],
+                                 (const double*)d_in[4], (const double*)d_in[5], (const double*)d_in[6], (const double*)d_in[7], d_wf, d_wr);
+    if (rc) return rc;
+    if ((rc = io.download(w_flux, d_wf, grid))) return rc;
+    if (w_reference && (rc = io.download(w_reference, d_wr, grid))) return rc;
     return io.finish();
 }
 

@@ -552,7 +552,10 @@ class SpectralSynthesizer:
         per_depth=True keeps the depth points apart: the response to the line's strength at depth point d alone.
         weights: None (1 for every column) or one value per column of this synthesizer (host array, DeviceArray or CUDA tensor).  The
         equivalent width W = sum_i (1 - F_i / F_c) dlambda_i of a feature on a flat continuum F_c has weights[i] = -dlambda_i / F_c on
-        its columns and 0 elsewhere:  dW / d ln gf_l = line_sensitivities(weights)[l].
+        its columns and 0 elsewhere:  dW / d ln gf_l = line_sensitivities(weights)[l].  For a functional of the OBSERVED pixels (a
+        chi-square against data, a width measured on the detector, the true continuum as reference) no weights need forming by hand:
+        observed_line_sensitivities(c) and chi2_line_gradient(data, ivar) pull pixel weights back through the instrument
+        (pixel_weights_to_grid) and call this.
         Fixed windows: the reference's window half-width is int(max(10, (gamma + doppler) alpha / d_nu * 20)), the flux is a step
         function of a line's strength wherever that integer moves, and this is the derivative between the steps.
         The line tables: a sorted dense list is read where the step reads it; a line list of scalars and an unsorted dense list are
@@ -582,6 +585,77 @@ class SpectralSynthesizer:
         c.call("sdx_line_adjoint_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, cnt, self.n_lines, ln_ptr, d_dw.ptr, d_g.ptr,
                self.gamma_cols, d_a.ptr, d_W.ptr, cnt, None if per_depth else out.ptr, out.ptr if per_depth else None)
         return out
+
+    def _require_instrument(self):
+        if self.instrument is None:
+            raise RuntimeError("no instrument: construct the synthesizer with instrument=Instrument(...)")
+
+    def _pixel_vector(self, name, c):
+        """a vector over the instrument's pixels (host array, DeviceArray or CUDA tensor) -> a device buffer; ValueError naming it"""
+        n_pix = self.instrument.n_pix
+        if isinstance(c, _lib.DeviceArray) or hasattr(c, "data_ptr"):
+            _require_f64_buffer(name, c, 0)
+            size = int(np.prod(tuple(c.shape), dtype=np.int64))
+            if size != n_pix:
+                raise ValueError(f"{name} must hold one value per pixel of the instrument ({n_pix}), got {size}")
+            return c
+        host = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
+        if host.size != n_pix:
+            raise ValueError(f"{name} must hold one value per pixel of the instrument ({n_pix}), got {host.size}")
+        return self.ctx.upload(host)
+
+    def pixel_weights_to_grid(self, c, normalized=False, with_continuum=False):
+        """-> DeviceArray (n_nu,): the weights w over the columns of F_nu[-1] with  sum_j c_j observed_j = sum_i w_i F_nu_i[-1]  over the
+        pixels the grid covers (c of a NaN pixel is never read) — the instrument transposed (sdx_observe_adjoint_dev, the factor nu /
+        lambda of F_lambda applied), at the instrument's present radial velocity.  c: one value per pixel (host array, DeviceArray or
+        CUDA tensor).  normalized=True: the weights of observed_normalized instead, its derivative to F_nu[-1] at the last step's
+        F_lambda and continuum (needs keep_continuum_flux=True).  with_continuum=True -> (w, w_continuum), the second over the
+        columns of F_nu_continuum[-1] (zeros unless normalized: the plain observed spectrum does not depend on the continuum).  On demand, after a step: what feeds line_sensitivities(weights=...)."""
+        self._require_instrument()
+        if normalized:
+            self._require_continuum()
+        d_c = self._pixel_vector("c", c)
+        inst, n = self.instrument, self.n_nu
+        if not normalized:  # (the plain observed spectrum does not depend on the continuum: its weights there are zeros)
+            w = inst.adjoint(self.d_lambdas, n, d_c, nus=self.d_nus)
+            return (w, self.ctx.zeros((n,))) if with_continuum else w
+        return inst.adjoint(self.d_lambdas, n, d_c, flux=self.d_Flam, reference=self.d_Fclam, nus=self.d_nus, out_reference=bool(with_continuum))
+
+    def observed_line_sensitivities(self, c, normalized=False, per_depth=False):
+        """-> DeviceArray (n_lines,), or (n_lines, N_d) with per_depth=True: d(sum_j c_j observed_j) / d ln gf_l for every line of the
+        list, at fixed windows, from the last step — line_sensitivities(weights=pixel_weights_to_grid(c, normalized), per_depth): the
+        chain response functions -> line adjoint -> instrument, from the detector's pixels to every line.  normalized=True: of
+        observed_normalized; the zero-line continuum does not depend on the lines, so its cotangent does not enter.  Needs
+        instrument= and keep_response=True (normalized: keep_continuum_flux=True)."""
+        self._require_instrument()
+        self._require_response()
+        return self.line_sensitivities(weights=self.pixel_weights_to_grid(c, normalized), per_depth=per_depth)
+
+    def chi2_line_gradient(self, data, inverse_variance, normalized=False, per_depth=False):
+        """-> (chi2, DeviceArray): chi2 = sum_j ivar_j (data_j - observed_j)^2 of the last step's observed (normalized=True:
+        observed_normalized) spectrum against data, and its gradient to ln gf of every line, (n_lines,) or (n_lines, N_d):
+        observed_line_sensitivities with c_j = -2 ivar_j (data_j - observed_j).  A pixel whose observed value is NaN (the grid does not
+        cover its window) or whose ivar is 0 is left out of both; leaving every pixel out is a ValueError.  data, inverse_variance:
+        host arrays, one value per pixel.  A diagnostic call, not part of the step: it waits for the stream and forms the n_pix
+        residuals on the host."""
+        self._require_instrument()
+        self._require_response()
+        if normalized:
+            self._require_continuum()
+        n_pix = self.instrument.n_pix
+        d = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
+        ivar = np.ascontiguousarray(inverse_variance, dtype=np.float64).reshape(-1)
+        for name, v in (("data", d), ("inverse_variance", ivar)):
+            if v.size != n_pix:
+                raise ValueError(f"{name} must hold one value per pixel of the instrument ({n_pix}), got {v.size}")
+        obs = (self.d_observed_normalized if normalized else self.d_observed).numpy()
+        use = ~np.isnan(obs) & (ivar != 0)
+        if not np.any(use):
+            raise ValueError("no pixel left: every pixel is NaN (not covered by the grid) or has inverse_variance 0")
+        r = np.where(use, d, 0.0) - np.where(use, obs, 0.0)
+        w = np.where(use, ivar, 0.0)
+        chi2 = float(np.sum(w * r * r))
+        return chi2, self.observed_line_sensitivities(-2.0 * w * r, normalized, per_depth)
 
     @property
     def observed(self):

@@ -470,3 +470,19 @@ def observe(lambdas, flux, pixel_edges, sigma, v_rad=0.0, reference=None, ctx=No
     if v_rad:
         inst.set_radial_velocity(v_rad)
     return inst.observe_host(lambdas, flux, reference)
+
+
+def observe_adjoint(lambdas, pixel_weights, pixel_edges, sigma, v_rad=0.0, flux=None, reference=None, nus=None, ctx=None):
+    """The transpose of observe (sdx_observe_adjoint_f64): pixel_weights c (n_pix,) -> weights w (n,) over the grid points with
+    sum_j c_j observe(flux)_j = sum_i w_i flux_i over the pixels the shifted grid covers (c of a NaN pixel is never read) — the
+    derivative of any functional of the observed pixels pulled back to the model's grid.  With a reference (which needs the flux) ->
+    (weights to the flux, weights to the reference) of the normalised spectrum.  nus: the weights then apply to F_nu instead of
+    F_lambda.  Arguments of the wrong length raise ValueError naming them, before any device work."""
+    from .instrument import Instrument, adjoint_host_arguments, pixel_sigma
+
+    edges, _ = pixel_sigma(pixel_edges, sigma=sigma)
+    adjoint_host_arguments(edges.size - 1, lambdas, pixel_weights, flux, reference, nus)
+    inst = Instrument(pixel_edges, sigma=sigma, ctx=ctx)
+    if v_rad:
+        inst.set_radial_velocity(v_rad)
+    return inst.adjoint_host(lambdas, pixel_weights, flux, reference, nus)
