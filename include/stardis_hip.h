@@ -200,6 +200,8 @@ int sdx_line_opacity_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
                          int64_t nu_count, int64_t n_lines, const double* line_nus, const double* doppler_widths,
                          const double* gammas, int gamma_cols, const double* alphas, double* out, int64_t out_ld,
                          int accumulate, int64_t* n_evaluations_dev);
+/* host-buffer twin: the whole grid, out [n_depth][n_nu] overwritten.  n_nu = 0 returns after the argument checks, copies nothing and
+ * stores 0 in *n_evaluations (optional). */
 int sdx_line_opacity_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines,
                          const double* line_nus, const double* doppler_widths, const double* gammas, int gamma_cols,
                          const double* alphas, double* out, int64_t* n_evaluations);

@@ -21,6 +21,7 @@
 
 #include "../../include/stardis_hip.h"
 #include "sdx_kernels.h"
+#include "sdx_host_plan.h"
 
 using namespace sdx;
 
@@ -1638,8 +1639,11 @@ int sdx_line_windows_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
 }
 
 // Host-pointer (*_f64) entry points — what a numpy caller (the reference's calc_alpha_line_at_nu, base.py:432-439) binds.
-// Their device buffers are sub-allocated from ONE arena owned by the context and their transfers go through ONE pinned host
-// buffer, both grown on demand and kept across calls: a call costs no hipMalloc / hipFree and every copy is a DMA from / to
+// Each one is: check, declare the rows of the call in a HostPlan (sdx_host_plan.h: in / out / inout / scratch, in the order they sit
+// on the device), stage, the device entry, collect, finish.  The plan's one layout pass gives every row its place and the call its two
+// sizes, so what is reserved and what is copied are read from the same rows; absent rows (null host pointers) get a null device
+// pointer and take nothing.  The device buffers are sub-allocated from ONE arena owned by the context and the transfers go through ONE
+// pinned host buffer, both grown on demand and kept across calls: a call costs no hipMalloc / hipFree and every copy is a DMA from / to
 // page-locked memory.  Inputs: memcpy user -> pinned, async DMA pinned -> device (the DMA of array k overlaps the memcpy of
 // array k + 1).  Outputs: async DMA device -> pinned, one synchronize, memcpy pinned -> user.  Transfers beyond
 // kPinnedStagingMax go straight from / to the caller's pages (the runtime pins them on the fly).
@@ -1647,14 +1651,12 @@ constexpr size_t kPinnedStagingMax = (size_t)512 << 20;
 
 struct HostIo {
     sdx_ctx* ctx;
-    size_t dev_off = 0, pin_off = 0;
-    bool pinned = true;
     struct Pending {
         void* dst;
         const void* src_pin;
         size_t bytes;      // bytes per row
-        size_t rows = 1;   // rows of `bytes`, packed in the pinned buffer, dst_pitch apart in the destination
-        size_t dst_pitch = 0;
+        size_t rows;       // rows of `bytes`, packed in the pinned buffer, dst_pitch apart in the destination
+        size_t dst_pitch;
     };
     std::vector<Pending> pending;
     bool finished = false;
@@ -1669,79 +1671,61 @@ struct HostIo {
         if (!finished) hipStreamSynchronize(ctx->stream);
     }
 
-    static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
-
-    // sizes: total device bytes and total staged host bytes of the call (padded per array by the caller through need())
-    int begin(size_t dev_need, size_t pin_need)
+    // lays the plan out, grows the arena and the pinned buffer to it, enqueues the uploads and sets every row's device pointer
+    // (after growing: the arena may have moved)
+    int stage(HostPlan& plan)
     {
         static const bool no_pin = knob("SDX_NO_PINNED_STAGING") != nullptr;
-        pinned = !no_pin && pin_need <= kPinnedStagingMax;
-        if (ctx->io_dev_bytes < dev_need) {
+        plan.layout(no_pin ? 0 : kPinnedStagingMax);
+        if (ctx->io_dev_bytes < plan.dev_need) {
             HIP_TRY(hipStreamSynchronize(ctx->stream));
             if (ctx->io_dev) HIP_TRY(hipFree(ctx->io_dev));
             ctx->io_dev = nullptr;
             ctx->io_dev_bytes = 0;
-            const size_t want = dev_need + dev_need / 4;  // head-room: repeated calls with slowly growing sizes do not reallocate each time
+            const size_t want = plan.dev_need + plan.dev_need / 4;  // head-room: repeated calls with slowly growing sizes do not reallocate each time
             HIP_TRY(hipMalloc(&ctx->io_dev, want));
             ctx->io_dev_bytes = want;
         }
-        if (pinned && ctx->io_pin_bytes < pin_need) {
+        if (ctx->io_pin_bytes < plan.pin_need) {
             HIP_TRY(hipStreamSynchronize(ctx->stream));
             if (ctx->io_pin) HIP_TRY(hipHostFree(ctx->io_pin));
             ctx->io_pin = nullptr;
             ctx->io_pin_bytes = 0;
-            const size_t want = pin_need + pin_need / 4;
+            const size_t want = plan.pin_need + plan.pin_need / 4;
             HIP_TRY(hipHostMalloc(&ctx->io_pin, want, hipHostMallocDefault));
             ctx->io_pin_bytes = want;
         }
-        return SDX_OK;
-    }
-    void* alloc(size_t bytes)
-    {
-        void* p = (char*)ctx->io_dev + dev_off;
-        dev_off += pad(bytes ? bytes : 8);
-        return p;
-    }
-    int upload(const void* src, size_t bytes, const void** dev_out)
-    {
-        void* d = alloc(bytes);
-        *dev_out = d;
-        if (!bytes) return SDX_OK;
-        const void* from = src;
-        if (pinned) {
-            void* h = (char*)ctx->io_pin + pin_off;
-            pin_off += pad(bytes);
-            std::memcpy(h, src, bytes);
-            from = h;
-        }
-        HIP_TRY(hipMemcpyAsync(d, from, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return SDX_OK;
-    }
-    int download(void* dst, const void* dev_src, size_t bytes)
-    {
-        if (!bytes) return SDX_OK;
-        if (pinned) {
-            void* h = (char*)ctx->io_pin + pin_off;
-            pin_off += pad(bytes);
-            HIP_TRY(hipMemcpyAsync(h, dev_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-            pending.push_back({dst, h, bytes, 1, 0});
-        } else {
-            HIP_TRY(hipMemcpyAsync(dst, dev_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        // the growth above makes this hold; no copy is issued on the strength of that alone
+        if (plan.dev_need > ctx->io_dev_bytes || plan.pin_need > ctx->io_pin_bytes)
+            return fail(SDX_ERR_OOM, "host staging: the call's plan does not fit the context's buffers");
+        plan.bind(ctx->io_dev);
+        for (const HostPlan::Row& r : plan.rows) {
+            if (!r.uploads()) continue;
+            const void* from = r.src;
+            if (plan.staged) {
+                void* h = (char*)ctx->io_pin + r.up_off;
+                std::memcpy(h, r.src, r.bytes);
+                from = h;
+            }
+            HIP_TRY(hipMemcpyAsync((char*)ctx->io_dev + r.dev_off, from, r.bytes, hipMemcpyHostToDevice, ctx->stream));
         }
         return SDX_OK;
     }
-    // rows x row_bytes, contiguous on the device, into a host array whose rows are dst_pitch bytes apart
-    int download2d(void* dst, size_t dst_pitch, const void* dev_src, size_t row_bytes, size_t rows)
+    // enqueues the downloads of the plan that was staged
+    int collect(const HostPlan& plan)
     {
-        if (dst_pitch == row_bytes || rows <= 1) return download(dst, dev_src, row_bytes * rows);
-        if (!row_bytes) return SDX_OK;
-        if (pinned) {
-            void* h = (char*)ctx->io_pin + pin_off;
-            pin_off += pad(row_bytes * rows);
-            HIP_TRY(hipMemcpyAsync(h, dev_src, row_bytes * rows, hipMemcpyDeviceToHost, ctx->stream));
-            pending.push_back({dst, h, row_bytes, rows, dst_pitch});
-        } else {
-            HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch, dev_src, row_bytes, row_bytes, rows, hipMemcpyDeviceToHost, ctx->stream));
+        for (const HostPlan::Row& r : plan.rows) {
+            if (!r.downloads()) continue;
+            const void* d = (const char*)ctx->io_dev + r.dev_off;
+            if (plan.staged) {
+                void* h = (char*)ctx->io_pin + r.down_off;
+                HIP_TRY(hipMemcpyAsync(h, d, r.bytes, hipMemcpyDeviceToHost, ctx->stream));
+                pending.push_back({r.dst, h, r.bytes / r.rows, r.rows, r.dst_pitch});
+            } else if (r.rows == 1) {
+                HIP_TRY(hipMemcpyAsync(r.dst, d, r.bytes, hipMemcpyDeviceToHost, ctx->stream));
+            } else {
+                HIP_TRY(hipMemcpy2DAsync(r.dst, r.dst_pitch, d, r.bytes / r.rows, r.bytes / r.rows, r.rows, hipMemcpyDeviceToHost, ctx->stream));
+            }
         }
         return SDX_OK;
     }
@@ -1785,26 +1769,27 @@ int sdx_line_opacity_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     REQUIRE(n_nu == 0 || out, "line opacity: null output");
     if ((rc = host_grid_check(n_nu, nus))) return rc;
     if ((rc = host_lines_check(n_lines, line_nus, doppler, n_depth))) return rc;
+    if (n_nu == 0) {  // nothing to stage, as for the formal solution and the synthesis on an empty grid
+        if (n_evaluations) *n_evaluations = 0;
+        return SDX_OK;
+    }
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), ld = (size_t)n_lines * n_depth * f8, plane = (size_t)n_depth * n_nu * f8;
-    const size_t in_bytes[] = {(size_t)n_nu * f8, (size_t)n_lines * f8, ld, (size_t)n_lines * gamma_cols * f8, ld};
-    size_t dev_need = HostIo::pad(plane) + 256, pin_need = HostIo::pad(plane) + 256;
-    for (size_t b : in_bytes) dev_need += HostIo::pad(b ? b : 8), pin_need += HostIo::pad(b);
-    HostIo io{ctx};
-    if ((rc = io.begin(dev_need, pin_need))) return rc;
+    const size_t f8 = sizeof(double), ld = (size_t)n_lines * n_depth * f8;
     const double *d_nus, *d_ln, *d_dw, *d_g, *d_a;
-    if ((rc = io.upload(nus, in_bytes[0], (const void**)&d_nus)) || (rc = io.upload(line_nus, in_bytes[1], (const void**)&d_ln)) ||
-        (rc = io.upload(doppler, in_bytes[2], (const void**)&d_dw)) || (rc = io.upload(gammas, in_bytes[3], (const void**)&d_g)) ||
-        (rc = io.upload(alphas, in_bytes[4], (const void**)&d_a)))
-        return rc;
-    double* d_out = (double*)io.alloc(plane);
-    int64_t* d_ev = (int64_t*)io.alloc(sizeof(int64_t));
-    rc = sdx_line_opacity_dev(ctx, n_depth, n_nu, d_nus, 0, n_nu, n_lines, d_ln, d_dw, d_g, gamma_cols, d_a, d_out, n_nu, 0, d_ev);
-    if (rc) return rc;
-    int64_t ev = 0;
-    if ((rc = io.download(out, d_out, plane))) return rc;
-    HIP_TRY(hipMemcpyAsync(&ev, d_ev, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = io.finish())) return rc;
+    double* d_out;
+    int64_t ev = 0, *d_ev;
+    HostPlan plan;
+    plan.in(nus, (size_t)n_nu * f8, &d_nus);
+    plan.in(line_nus, (size_t)n_lines * f8, &d_ln);
+    plan.in(doppler, ld, &d_dw);
+    plan.in(gammas, (size_t)n_lines * gamma_cols * f8, &d_g);
+    plan.in(alphas, ld, &d_a);
+    plan.out(out, (size_t)n_depth * n_nu * f8, &d_out);
+    plan.out(&ev, sizeof ev, &d_ev);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_line_opacity_dev(ctx, n_depth, n_nu, d_nus, 0, n_nu, n_lines, d_ln, d_dw, d_g, gamma_cols, d_a, d_out, n_nu, 0, d_ev))) return rc;
+    if ((rc = io.collect(plan)) || (rc = io.finish())) return rc;
     if (n_evaluations) *n_evaluations = ev;
     return SDX_OK;
 }
@@ -2315,22 +2300,20 @@ int sdx_raytrace_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const
     HIP_TRY(hipSetDevice(ctx->device));
     int rc;
     const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
-    const size_t in_bytes[] = {(size_t)n_nu * f8, (size_t)n_depth * f8, (size_t)(n_depth - 1) * n_theta * f8, (size_t)n_theta * f8, plane, plane};
-    size_t dev_need = 256, pin_need = HostIo::pad(plane) + 256;
-    for (size_t b : in_bytes) dev_need += HostIo::pad(b), pin_need += HostIo::pad(b);
-    if (I_nus) dev_need += HostIo::pad(plane * n_theta), pin_need += HostIo::pad(plane * n_theta);
+    const double *d_nus, *d_t, *d_rd, *d_w, *d_a;
+    double *d_f, *d_i;
+    HostPlan plan;
+    plan.in(nus, (size_t)n_nu * f8, &d_nus);
+    plan.in(temps, (size_t)n_depth * f8, &d_t);
+    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
+    plan.in(wts, (size_t)n_theta * f8, &d_w);
+    plan.in(alphas, plane, &d_a);
+    plan.inout(F, plane, &d_f);  // F_nu is accumulated into (base.py:336)
+    plan.out(I_nus, plane * n_theta, &d_i);
     HostIo io{ctx};
-    if ((rc = io.begin(dev_need, pin_need))) return rc;
-    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_f;
-    if ((rc = io.upload(nus, in_bytes[0], (const void**)&d_nus)) || (rc = io.upload(temps, in_bytes[1], (const void**)&d_t)) ||
-        (rc = io.upload(ray_dist, in_bytes[2], (const void**)&d_rd)) || (rc = io.upload(wts, in_bytes[3], (const void**)&d_w)) ||
-        (rc = io.upload(alphas, in_bytes[4], (const void**)&d_a)) || (rc = io.upload(F, in_bytes[5], (const void**)&d_f)))  // F_nu is accumulated into (base.py:336)
-        return rc;
-    double* d_i = I_nus ? (double*)io.alloc(plane * n_theta) : nullptr;
-    rc = sdx_raytrace_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, (double*)d_f, n_nu, d_i, 1);
-    if (rc) return rc;
-    if ((rc = io.download(F, d_f, plane))) return rc;
-    if (I_nus && (rc = io.download(I_nus, d_i, plane * n_theta))) return rc;
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_raytrace_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_f, n_nu, d_i, 1))) return rc;
+    if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }
 
@@ -2380,20 +2363,20 @@ int sdx_contribution_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
     if ((rc = sdx_contribution_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0))) return rc;  // refusals before any copy
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
-    const size_t in_bytes[] = {(size_t)n_nu * f8, (size_t)n_depth * f8, (size_t)(n_depth - 1) * n_theta * f8, (size_t)n_theta * f8, plane, source ? plane : 0};
-    size_t dev_need = 256 + HostIo::pad(plane), pin_need = HostIo::pad(plane) + 256;
-    for (size_t b : in_bytes) dev_need += HostIo::pad(b), pin_need += HostIo::pad(b);
+    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_s;
+    double* d_c;
+    HostPlan plan;
+    plan.in(nus, (size_t)n_nu * f8, &d_nus);
+    plan.in(temps, (size_t)n_depth * f8, &d_t);
+    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
+    plan.in(wts, (size_t)n_theta * f8, &d_w);
+    plan.in(alphas, plane, &d_a);
+    plan.in(source, plane, &d_s);
+    plan.out(C, plane, &d_c);
     HostIo io{ctx};
-    if ((rc = io.begin(dev_need, pin_need))) return rc;
-    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_s = nullptr;
-    if ((rc = io.upload(nus, in_bytes[0], (const void**)&d_nus)) || (rc = io.upload(temps, in_bytes[1], (const void**)&d_t)) ||
-        (rc = io.upload(ray_dist, in_bytes[2], (const void**)&d_rd)) || (rc = io.upload(wts, in_bytes[3], (const void**)&d_w)) ||
-        (rc = io.upload(alphas, in_bytes[4], (const void**)&d_a)) || (source && (rc = io.upload(source, in_bytes[5], (const void**)&d_s))))
-        return rc;
-    double* d_c = (double*)io.alloc(plane);
-    rc = sdx_contribution_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_s, n_nu, d_c, n_nu);
-    if (rc) return rc;
-    if ((rc = io.download(C, d_c, plane))) return rc;
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_contribution_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_s, n_nu, d_c, n_nu))) return rc;
+    if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }
 
@@ -2446,22 +2429,21 @@ int sdx_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const
         return rc;  // refusals before any copy
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
-    const size_t in_bytes[] = {(size_t)n_nu * f8, (size_t)n_depth * f8, (size_t)(n_depth - 1) * n_theta * f8, (size_t)n_theta * f8, plane, source ? plane : 0};
-    size_t dev_need = 256 + 2 * HostIo::pad(plane), pin_need = 2 * HostIo::pad(plane) + 256;
-    for (size_t b : in_bytes) dev_need += HostIo::pad(b), pin_need += HostIo::pad(b);
+    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_s;
+    double *d_ra, *d_rs;
+    HostPlan plan;
+    plan.in(nus, (size_t)n_nu * f8, &d_nus);
+    plan.in(temps, (size_t)n_depth * f8, &d_t);
+    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
+    plan.in(wts, (size_t)n_theta * f8, &d_w);
+    plan.in(alphas, plane, &d_a);
+    plan.in(source, plane, &d_s);
+    plan.out(R_alpha, plane, &d_ra);
+    plan.out(R_source, plane, &d_rs);
     HostIo io{ctx};
-    if ((rc = io.begin(dev_need, pin_need))) return rc;
-    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_s = nullptr;
-    if ((rc = io.upload(nus, in_bytes[0], (const void**)&d_nus)) || (rc = io.upload(temps, in_bytes[1], (const void**)&d_t)) ||
-        (rc = io.upload(ray_dist, in_bytes[2], (const void**)&d_rd)) || (rc = io.upload(wts, in_bytes[3], (const void**)&d_w)) ||
-        (rc = io.upload(alphas, in_bytes[4], (const void**)&d_a)) || (source && (rc = io.upload(source, in_bytes[5], (const void**)&d_s))))
-        return rc;
-    double* d_ra = R_alpha ? (double*)io.alloc(plane) : nullptr;
-    double* d_rs = R_source ? (double*)io.alloc(plane) : nullptr;
-    rc = sdx_response_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_s, n_nu, d_ra, n_nu, d_rs, n_nu);
-    if (rc) return rc;
-    if (R_alpha && (rc = io.download(R_alpha, d_ra, plane))) return rc;
-    if (R_source && (rc = io.download(R_source, d_rs, plane))) return rc;
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_response_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_s, n_nu, d_ra, n_nu, d_rs, n_nu))) return rc;
+    if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }
 
@@ -2547,24 +2529,21 @@ int sdx_line_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     REQUIRE(nus && line_nus && doppler && gammas && alphas && weight, "line_adjoint: null pointer");
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t f8 = sizeof(double), items = (size_t)n_lines * n_depth * f8;
-    const size_t in_bytes[] = {(size_t)n_nu * f8, (size_t)n_lines * f8, items, (size_t)n_lines * gamma_cols * f8, items, (size_t)n_depth * n_nu * f8};
-    const size_t out_bytes[] = {out_line ? (size_t)n_lines * f8 : 0, out_line_depth ? items : 0};
-    size_t dev_need = 256, pin_need = 256;
-    for (size_t b : in_bytes) dev_need += HostIo::pad(b), pin_need += HostIo::pad(b);
-    for (size_t b : out_bytes) dev_need += HostIo::pad(b ? b : 8), pin_need += HostIo::pad(b);
+    const double *d_nus, *d_ln, *d_dw, *d_g, *d_a, *d_wt;
+    double *d_line, *d_ld;
+    HostPlan plan;
+    plan.in(nus, (size_t)n_nu * f8, &d_nus);
+    plan.in(line_nus, (size_t)n_lines * f8, &d_ln);
+    plan.in(doppler, items, &d_dw);
+    plan.in(gammas, (size_t)n_lines * gamma_cols * f8, &d_g);
+    plan.in(alphas, items, &d_a);
+    plan.in(weight, (size_t)n_depth * n_nu * f8, &d_wt);
+    plan.out(out_line, (size_t)n_lines * f8, &d_line);
+    plan.out(out_line_depth, items, &d_ld);
     HostIo io{ctx};
-    if ((rc = io.begin(dev_need, pin_need))) return rc;
-    const void* d_in[6];
-    const void* src[] = {nus, line_nus, doppler, gammas, alphas, weight};
-    for (int k = 0; k < 6; ++k)
-        if ((rc = io.upload(src[k], in_bytes[k], &d_in[k]))) return rc;
-    double* d_line = out_line ? (double*)io.alloc(out_bytes[0]) : nullptr;
-    double* d_ld = out_line_depth ? (double*)io.alloc(out_bytes[1]) : nullptr;
-    rc = sdx_line_adjoint_dev(ctx, n_depth, n_nu, (const double*)d_in[0], 0, n_nu, n_lines, (const double*)d_in[1], (const double*)d_in[2], (const double*)d_in[3],
-                              gamma_cols, (const double*)d_in[4], (const double*)d_in[5], n_nu, d_line, d_ld);
-    if (rc) return rc;
-    if (out_line && (rc = io.download(out_line, d_line, out_bytes[0]))) return rc;
-    if (out_line_depth && (rc = io.download(out_line_depth, d_ld, out_bytes[1]))) return rc;
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_line_adjoint_dev(ctx, n_depth, n_nu, d_nus, 0, n_nu, n_lines, d_ln, d_dw, d_g, gamma_cols, d_a, d_wt, n_nu, d_line, d_ld))) return rc;
+    if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }
 
@@ -2644,20 +2623,21 @@ int sdx_observe_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double
     int rc;
     if ((rc = observe_host_check(n, lambdas, n_pix, edges, sigma, doppler))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double);
-    const size_t in_bytes[] = {(size_t)n * f8, (size_t)n * f8, reference ? (size_t)n * f8 : 0, (size_t)(n_pix + 1) * f8, (size_t)n_pix * f8, f8};
-    size_t dev_need = 256 + HostIo::pad((size_t)n_pix * f8), pin_need = HostIo::pad((size_t)n_pix * f8) + 256;
-    for (size_t b : in_bytes) dev_need += HostIo::pad(b ? b : 8), pin_need += HostIo::pad(b);
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
+    const double *d_l, *d_f, *d_r, *d_e, *d_s, *d_D;
+    double* d_o;
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(flux, grid, &d_f);
+    plan.in(reference, grid, &d_r);
+    plan.in(edges, (size_t)(n_pix + 1) * f8, &d_e);
+    plan.in(sigma, (size_t)n_pix * f8, &d_s);
+    plan.in(&doppler, f8, &d_D);
+    plan.out(out, (size_t)n_pix * f8, &d_o);
     HostIo io{ctx};
-    if ((rc = io.begin(dev_need, pin_need))) return rc;
-    const double *d_l, *d_f, *d_r = nullptr, *d_e, *d_s, *d_D;
-    if ((rc = io.upload(lambdas, in_bytes[0], (const void**)&d_l)) || (rc = io.upload(flux, in_bytes[1], (const void**)&d_f)) ||
-        (reference && (rc = io.upload(reference, in_bytes[2], (const void**)&d_r))) || (rc = io.upload(edges, in_bytes[3], (const void**)&d_e)) ||
-        (rc = io.upload(sigma, in_bytes[4], (const void**)&d_s)) || (rc = io.upload(&doppler, in_bytes[5], (const void**)&d_D)))
-        return rc;
-    double* d_o = (double*)io.alloc((size_t)n_pix * f8);
+    if ((rc = io.stage(plan))) return rc;
     if ((rc = sdx_observe_dev(ctx, n, d_l, d_f, d_r, n_pix, d_e, d_s, d_D, d_o))) return rc;
-    if ((rc = io.download(out, d_o, (size_t)n_pix * f8))) return rc;
+    if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }
 
@@ -2724,23 +2704,23 @@ int sdx_observe_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, cons
     if ((rc = observe_host_check(n, lambdas, n_pix, edges, sigma, doppler))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t f8 = sizeof(double), grid = (size_t)n * f8;
-    const void* src[] = {lambdas, reference ? flux : nullptr, reference, edges, sigma, &doppler, pixel_weight, nus};
-    const size_t in_bytes[] = {grid, reference ? grid : 0, reference ? grid : 0, (size_t)(n_pix + 1) * f8, (size_t)n_pix * f8, f8, (size_t)n_pix * f8,
-                               nus ? grid : 0};
-    size_t dev_need = 256 + 2 * HostIo::pad(grid), pin_need = 2 * HostIo::pad(grid) + 256;
-    for (size_t b : in_bytes) dev_need += HostIo::pad(b ? b : 8), pin_need += HostIo::pad(b);
+    const double *d_l, *d_f, *d_r, *d_e, *d_s, *d_D, *d_pw, *d_nus;
+    double *d_wf, *d_wr;
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(reference ? flux : nullptr, grid, &d_f);  // (the flux enters only through the reference's cotangent)
+    plan.in(reference, grid, &d_r);
+    plan.in(edges, (size_t)(n_pix + 1) * f8, &d_e);
+    plan.in(n_pix ? sigma : nullptr, (size_t)n_pix * f8, &d_s);
+    plan.in(&doppler, f8, &d_D);
+    plan.in(n_pix ? pixel_weight : nullptr, (size_t)n_pix * f8, &d_pw);
+    plan.in(nus, grid, &d_nus);
+    plan.out(w_flux, grid, &d_wf);
+    plan.out(w_reference, grid, &d_wr);
     HostIo io{ctx};
-    if ((rc = io.begin(dev_need, pin_need))) return rc;
-    const void* d_in[8] = {};
-    for (int k = 0; k < 8; ++k)
-        if (in_bytes[k] && (rc = io.upload(src[k], in_bytes[k], &d_in[k]))) return rc;
-    double* d_wf = (double*)io.alloc(grid);
-    double* d_wr = w_reference ? (double*)io.alloc(grid) : nullptr;
-    rc = sdx_observe_adjoint_dev(ctx, n, (const double*)d_in[0], (const double*)d_in[1], (const double*)d_in[2], n_pix, (const double*)d_in[3],
-                                 (const double*)d_in[4], (const double*)d_in[5], (const double*)d_in[6], (const double*)d_in[7], d_wf, d_wr);
-    if (rc) return rc;
-    if ((rc = io.download(w_flux, d_wf, grid))) return rc;
-    if (w_reference && (rc = io.download(w_reference, d_wr, grid))) return rc;
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_observe_adjoint_dev(ctx, n, d_l, d_f, d_r, n_pix, d_e, d_s, d_D, d_pw, d_nus, d_wf, d_wr))) return rc;
+    if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }
 
@@ -2958,33 +2938,25 @@ static int synthesize_host_check(sdx_ctx* ctx, const Grid& g, const Lines& l, co
     return SDX_OK;
 }
 
-// One row of a host-pointer entry point's upload table: every non-null host array goes up; lengths follow from the sizes in the struct
-struct HostIn {
-    const void* src;
-    size_t bytes;
-    const void** dst;
-};
-// the continuum's rows (HOST pointers in *cont, device pointers into *c), in the order both callers upload them; `temperature` is not
-// among them: the synthesis points it at the rays' temperatures, sdx_continuum_f64 uploads it behind these
-static void continuum_uploads(const sdx_continuum* cont, sdx_continuum* c, int n_depth, int64_t n_nu, int n_levels, std::vector<HostIn>* ins)
+// the continuum's rows (HOST pointers in *cont, device pointers into *c; a null one is absent), in the order both callers upload them;
+// `temperature` is not among them: the synthesis points it at the rays' temperatures, sdx_continuum_f64 uploads it behind these
+static void continuum_uploads(const sdx_continuum* cont, sdx_continuum* c, int n_depth, int64_t n_nu, int n_levels, HostPlan* plan)
 {
-    const size_t f8 = sizeof(double), depth = (size_t)n_depth * f8;
-    ins->insert(ins->end(), {
-        {cont->lambdas, (size_t)n_nu * f8, (const void**)&c->lambdas},
-        {cont->table_wavelength, (size_t)c->n_table * f8, (const void**)&c->table_wavelength},
-        {cont->table_sigma, (size_t)c->n_table * f8, (const void**)&c->table_sigma},
-        {cont->table_density, depth, (const void**)&c->table_density},
-        {cont->bf_species_offsets, (size_t)(c->bf_n_species + 1) * sizeof(int32_t), (const void**)&c->bf_species_offsets},
-        {cont->bf_species_ion_number, (size_t)c->bf_n_species * sizeof(int32_t), (const void**)&c->bf_species_ion_number},
-        {cont->bf_cutoff, (size_t)n_levels * f8, (const void**)&c->bf_cutoff},
-        {cont->bf_level_density, (size_t)n_levels * depth, (const void**)&c->bf_level_density},
-        {cont->ff_species_ion_number, (size_t)c->ff_n_species * sizeof(int32_t), (const void**)&c->ff_species_ion_number},
-        {cont->ff_number_density, (size_t)c->ff_n_species * depth, (const void**)&c->ff_number_density},
-        {cont->ray_n_h, depth, (const void**)&c->ray_n_h},
-        {cont->ray_n_he, depth, (const void**)&c->ray_n_he},
-        {cont->ray_n_h2, depth, (const void**)&c->ray_n_h2},
-        {cont->electron_density, depth, (const void**)&c->electron_density},
-    });
+    const size_t f8 = sizeof(double), i4 = sizeof(int32_t), depth = (size_t)n_depth * f8;
+    plan->in(cont->lambdas, (size_t)n_nu * f8, &c->lambdas);
+    plan->in(cont->table_wavelength, (size_t)c->n_table * f8, &c->table_wavelength);
+    plan->in(cont->table_sigma, (size_t)c->n_table * f8, &c->table_sigma);
+    plan->in(cont->table_density, depth, &c->table_density);
+    plan->in(cont->bf_species_offsets, (size_t)(c->bf_n_species + 1) * i4, &c->bf_species_offsets);
+    plan->in(cont->bf_species_ion_number, (size_t)c->bf_n_species * i4, &c->bf_species_ion_number);
+    plan->in(cont->bf_cutoff, (size_t)n_levels * f8, &c->bf_cutoff);
+    plan->in(cont->bf_level_density, (size_t)n_levels * depth, &c->bf_level_density);
+    plan->in(cont->ff_species_ion_number, (size_t)c->ff_n_species * i4, &c->ff_species_ion_number);
+    plan->in(cont->ff_number_density, (size_t)c->ff_n_species * depth, &c->ff_number_density);
+    plan->in(cont->ray_n_h, depth, &c->ray_n_h);
+    plan->in(cont->ray_n_he, depth, &c->ray_n_he);
+    plan->in(cont->ray_n_h2, depth, &c->ray_n_h2);
+    plan->in(cont->electron_density, depth, &c->electron_density);
 }
 
 // Uploads everything to ctx's device, enqueues the synthesis of columns [nu_begin, nu_begin + nu_count) and the downloads of the
@@ -3001,38 +2973,32 @@ static int synthesize_host_shard(sdx_ctx* ctx, HostIo& io, const Grid& g, const 
     const size_t f8 = sizeof(double), plane = (size_t)n_depth * nu_count * f8, ld = (size_t)n_lines * n_depth * f8;
     sdx_continuum c = *cont;
     const double *d_nus, *d_ln, *d_dw, *d_g, *d_a, *d_t, *d_rd, *d_w;
-    std::vector<HostIn> ins = {
-        {g.nus, (size_t)n_nu * f8, (const void**)&d_nus},
-        {l.line_nus, (size_t)n_lines * f8, (const void**)&d_ln},
-        {l.doppler, ld, (const void**)&d_dw},
-        {l.gammas, (size_t)n_lines * l.gamma_cols * f8, (const void**)&d_g},
-        {l.alphas, ld, (const void**)&d_a},
-        {rays.temps, (size_t)n_depth * f8, (const void**)&d_t},
-        {rays.ray_dist, (size_t)(n_depth - 1) * n_theta * f8, (const void**)&d_rd},
-        {rays.wts, (size_t)n_theta * f8, (const void**)&d_w},
-    };
-    continuum_uploads(cont, &c, n_depth, n_nu, c.bf_n_species > 0 ? c.bf_n_levels : 0, &ins);
-    const int n_out = 1 + (alpha_line_out ? 1 : 0) + (total_alphas ? 1 : 0);
-    size_t dev_need = (size_t)n_out * HostIo::pad(plane) + 512;
-    size_t pin_need = (size_t)(F_nu ? n_out : n_out - 1) * HostIo::pad(plane) + 512;
-    for (const HostIn& in : ins)
-        if (in.src) dev_need += HostIo::pad(in.bytes ? in.bytes : 8), pin_need += HostIo::pad(in.bytes);
-    if ((rc = io.begin(dev_need, pin_need))) return rc;
-    for (const HostIn& in : ins)
-        if (in.src && (rc = io.upload(in.src, in.bytes, in.dst))) return rc;
-    c.temperature = d_t;
-    double* d_line = alpha_line_out ? (double*)io.alloc(plane) : nullptr;
-    double* d_total = total_alphas ? (double*)io.alloc(plane) : nullptr;
-    double* d_F = (double*)io.alloc(plane);
-    int64_t* d_ev = (int64_t*)io.alloc(sizeof(int64_t));
-    rc = sdx_synthesize_dev(ctx, n_depth, n_nu, d_nus, nu_begin, nu_count, n_lines, d_ln, d_dw, d_g, l.gamma_cols, d_a, &c, n_theta, d_t, d_rd, d_w,
-                            d_line, d_total, d_F, nu_count, out.n_evaluations ? d_ev : nullptr);
-    if (rc) return rc;
+    double *d_line, *d_total, *d_F;
+    int64_t* d_ev;
     const size_t pitch = (size_t)n_nu * f8, row = (size_t)nu_count * f8;
-    if (alpha_line_out && (rc = io.download2d(alpha_line_out + nu_begin, pitch, d_line, row, n_depth))) return rc;
-    if (total_alphas && (rc = io.download2d(total_alphas + nu_begin, pitch, d_total, row, n_depth))) return rc;
-    if (F_nu && (rc = io.download2d(F_nu + nu_begin, pitch, d_F, row, n_depth))) return rc;
-    if (out.n_evaluations) HIP_TRY(hipMemcpyAsync(out.n_evaluations, d_ev, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HostPlan plan;
+    plan.in(g.nus, (size_t)n_nu * f8, &d_nus);
+    plan.in(l.line_nus, (size_t)n_lines * f8, &d_ln);
+    plan.in(l.doppler, ld, &d_dw);
+    plan.in(l.gammas, (size_t)n_lines * l.gamma_cols * f8, &d_g);
+    plan.in(l.alphas, ld, &d_a);
+    plan.in(rays.temps, (size_t)n_depth * f8, &d_t);
+    plan.in(rays.ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
+    plan.in(rays.wts, (size_t)n_theta * f8, &d_w);
+    continuum_uploads(cont, &c, n_depth, n_nu, c.bf_n_species > 0 ? c.bf_n_levels : 0, &plan);
+    plan.out2d(alpha_line_out ? alpha_line_out + nu_begin : nullptr, pitch, row, n_depth, &d_line);
+    plan.out2d(total_alphas ? total_alphas + nu_begin : nullptr, pitch, row, n_depth, &d_total);
+    if (F_nu)
+        plan.out2d(F_nu + nu_begin, pitch, row, n_depth, &d_F);
+    else
+        plan.scratch(plane, &d_F);  // (the sharded entry gathers its last row on the device)
+    plan.out(out.n_evaluations, sizeof(int64_t), &d_ev);
+    if ((rc = io.stage(plan))) return rc;
+    c.temperature = d_t;
+    rc = sdx_synthesize_dev(ctx, n_depth, n_nu, d_nus, nu_begin, nu_count, n_lines, d_ln, d_dw, d_g, l.gamma_cols, d_a, &c, n_theta, d_t, d_rd, d_w,
+                            d_line, d_total, d_F, nu_count, d_ev);
+    if (rc) return rc;
+    if ((rc = io.collect(plan))) return rc;
     if (d_F_out) *d_F_out = d_F;
     return SDX_OK;
 }
@@ -3082,22 +3048,17 @@ int sdx_continuum_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, double* nus, cons
     const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
     sdx_continuum c = *cont;
     const int n_levels = has_bf ? c.bf_n_levels : 0;
-    const double* d_nus;
-    std::vector<HostIn> ins = {{nus, (size_t)n_nu * f8, (const void**)&d_nus}};
-    continuum_uploads(cont, &c, n_depth, n_nu, n_levels, &ins);
-    ins.push_back({cont->temperature, (size_t)n_depth * f8, (const void**)&c.temperature});
+    const bool clip = alpha_rayleigh != nullptr;  // calc_alpha_rayleigh zeroes the caller's frequencies above 2.3e15 Hz in place (:99)
+    double* d_nus;
     double* const outs[] = {total_alphas, alpha_file, alpha_bf, alpha_ff, alpha_rayleigh, alpha_electron};
-    int n_out = 0;
-    for (double* o : outs) n_out += o ? 1 : 0;
-    size_t dev_need = (size_t)n_out * HostIo::pad(plane) + 512, pin_need = (size_t)n_out * HostIo::pad(plane) + HostIo::pad((size_t)n_nu * f8) + 512;
-    for (const HostIn& in : ins)
-        if (in.src) dev_need += HostIo::pad(in.bytes ? in.bytes : 8), pin_need += HostIo::pad(in.bytes);
-    HostIo io{ctx};
-    if ((rc = io.begin(dev_need, pin_need))) return rc;
-    for (const HostIn& in : ins)
-        if (in.src && (rc = io.upload(in.src, in.bytes, in.dst))) return rc;
     double* d_out[6];
-    for (int k = 0; k < 6; ++k) d_out[k] = outs[k] ? (double*)io.alloc(plane) : nullptr;
+    HostPlan plan;
+    plan.inout(nus, (size_t)n_nu * f8, &d_nus, clip);
+    continuum_uploads(cont, &c, n_depth, n_nu, n_levels, &plan);
+    plan.in(cont->temperature, (size_t)n_depth * f8, &c.temperature);
+    for (int k = 0; k < 6; ++k) plan.out(outs[k], plane, &d_out[k]);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
     // the total first: it reads the caller's frequencies as they came (the Rayleigh source clips its own copy of a frequency
     // above 2.3e15 Hz, :99, whether or not the array has been clipped yet)
     if (total_alphas && (rc = launch_total(ctx, Grid{n_depth, n_nu, d_nus, 0, n_nu}, &c, nullptr, 0, d_out[0], n_nu))) return rc;
@@ -3120,8 +3081,7 @@ int sdx_continuum_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, double* nus, cons
     if (alpha_ff && (rc = sdx_alpha_ff_dev(ctx, n_depth, n_nu, d_nus, c.temperature ? c.temperature : d_nus, has_ff ? c.ff_n_species : 0, c.ff_species_ion_number,
                                            c.ff_number_density, d_out[3], n_nu)))
         return rc;
-    const bool clip = alpha_rayleigh != nullptr;  // calc_alpha_rayleigh zeroes the caller's frequencies above 2.3e15 Hz in place (:99)
-    if (alpha_rayleigh && (rc = sdx_alpha_rayleigh_dev(ctx, n_depth, n_nu, (double*)d_nus, c.ray_n_h, c.ray_n_he, c.ray_n_h2, d_out[4], n_nu))) return rc;
+    if (alpha_rayleigh && (rc = sdx_alpha_rayleigh_dev(ctx, n_depth, n_nu, d_nus, c.ray_n_h, c.ray_n_he, c.ray_n_h2, d_out[4], n_nu))) return rc;
     if (alpha_electron) {
         if (c.electron_density) {
             if ((rc = sdx_alpha_electron_dev(ctx, n_depth, n_nu, c.electron_density, d_out[5], n_nu))) return rc;
@@ -3129,9 +3089,7 @@ int sdx_continuum_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, double* nus, cons
             HIP_TRY(hipMemsetAsync(d_out[5], 0, plane, ctx->stream));  // (the reference returns the scalar 0 when disabled, :164-165)
         }
     }
-    for (int k = 0; k < 6; ++k)
-        if (outs[k] && (rc = io.download(outs[k], d_out[k], plane))) return rc;
-    if (clip && (rc = io.download(nus, d_nus, (size_t)n_nu * f8))) return rc;
+    if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }
 
