@@ -125,6 +125,8 @@ int sdx_synchronize(sdx_ctx* ctx);
  *       of consecutive 1024-column tiles whose sums one wave adds — per item: min(tiles of the shard, partials / tiled items).  Scheduling
  *       and scratch only, but not bit-neutral: another number of supertiles adds an item's tiles in another grouping (the results stay
  *       deterministic and within the rounding of the sum).  32 MB at the default; tests lower it to run several tiles per supertile.
+ *       sdx_line_param_adjoint_dev keeps four sums per item: there the option bounds groups of four doubles per (tiled item, supertile),
+ *       min(tiles of the shard, (partials / 4) / tiled items) supertiles per item, and at least one group per item is always there.
  *   "wide_list" (default -1): how the wide role of the line kernel finds its candidates in a SHORT list (fewer than "indexed_min_lines"
  *       lines; long lists have the list launches).  0: every tile tests every line of its line subset, 64 per round trip.  1: the last
  *       line block of the pre-pass launch to finish lists the lines that have a wide window (half-width > 64 grid points) at any depth,
@@ -224,6 +226,15 @@ int sdx_voigt_term_dev(sdx_ctx* ctx, int64_t n, const double* delta_nu, const do
  * fp32, hardware exp / cos); same arguments, rounded to fp32 inside.  Test hook for the stated 1e-4 tolerance of that mode. */
 int sdx_voigt_term_f32_dev(sdx_ctx* ctx, int64_t n, const double* delta_nu, const double* inv_doppler_width, const double* y,
                            const double* amp, double* out);
+/* The term and its two partial derivatives, element-wise — the routine sdx_line_param_adjoint_dev evaluates per (line, depth,
+ * frequency): with x = delta_nu * inv_doppler_width and K = Re w(x + i y)
+ *     out_k = amp K,   out_kx = amp dK/dx,   out_ky = amp dK/dy.
+ * What is differentiated is the reference's formula in the Humlicek region it picks (voigt.py:39-84; y and amp as voigt.py:148-149
+ * form them), chosen by sdx_voigt_term_dev's own predicates on the same rounded x and y, the region boundaries held fixed: dK/dx =
+ * Re w'(z), dK/dy = -Im w'(z) of that region's rational (region IV: of exp(-z^2) minus its rational), not of the true Faddeeva
+ * function.  A test hook, like sdx_voigt_term_dev: it lets the routine be judged point by point. */
+int sdx_voigt_grad_dev(sdx_ctx* ctx, int64_t n, const double* delta_nu, const double* inv_doppler_width, const double* y,
+                       const double* amp, double* out_k, double* out_kx, double* out_ky);
 
 /* ---- broadening (opacities_solvers/broadening.py) -------------------------------------------
  * calc_gamma :550-656 with calculate_broadening's argument preparation :706-721 (ion_number is the
@@ -434,6 +445,36 @@ int sdx_line_adjoint_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
 int sdx_line_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus,
                          const double* doppler_widths, const double* gammas, int gamma_cols, const double* alphas,
                          const double* weight, double* out_line, double* out_line_depth);
+/* ---- line-profile sensitivities: damping, Doppler width and line centre ----------------------------
+ * The same gather for the three numbers that set the SHAPE of a line.  The term of line l at depth d and grid point i is T = amp K(x, y)
+ * with x = (nu_i - nu_l) / doppler_ld, y = (gamma_ld / (sqrt(pi) pi)) / doppler_ld, amp = alpha_ld / (sqrt(pi) doppler_ld), K = Re w(x + i y)
+ * (voigt.py:39-84 for w, :148-149 for x, y and amp).  With the sums over the item's window clipped to the shard
+ *     S0 = sum W T,   Sx = sum W amp K_x,   Sxx = sum W amp x K_x,   Sy = sum W amp K_y          (K_x, K_y: sdx_voigt_grad_dev)
+ * the outputs are, per (line, depth) in the _depth arrays and summed over depth per line,
+ *     out_damping :  d/d ln gamma_ld   =  y Sy
+ *     out_doppler :  d/d ln doppler_ld = -(S0 + Sxx + y Sy)           (x, y and amp all carry 1 / doppler)
+ *     out_centre  :  d/d nu_l          = -Sx / doppler_ld             (per Hz)
+ * of  sum_d sum_i W[d][i] alpha_line[d][i]  AT FIXED WINDOWS AND FIXED REGIONS: the windows as for sdx_line_adjoint_dev (for the centre:
+ * the window's centre index held fixed too), the Humlicek region of every term held fixed — the derivative between the steps of the
+ * reference's forward model, which is what difference quotients of it give wherever no integer moves.  out_damping[l] is the response
+ * to scaling gamma of line l at every depth by one factor, out_doppler[l] likewise; the per-depth arrays keep the depths apart.
+ * Arguments, windows, classes, determinism, sharding and refusals as for sdx_line_adjoint_dev (a null context, mixed_precision = 1, all
+ * six outputs NULL, gamma_cols neither 1 nor n_depth, a shard outside the grid, the int32 limits: SDX_ERR_ARG before anything is
+ * enqueued, also for n_nu = 0); any of the six outputs may be NULL; n_lines = 0 or nu_count = 0 launches nothing.  Only enqueues on the
+ * context's stream; scratch as sdx_line_adjoint_dev's, four sums per item: "adjoint_partials" bounds groups of FOUR doubles per (tiled
+ * item, supertile) here, i.e. at most min(tiles of the shard, (partials / 4) / tiled items) supertiles per item.  Stage name of the
+ * profile hooks: k_line_param_adjoint. */
+int sdx_line_param_adjoint_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
+                               int64_t n_lines, const double* line_nus, const double* doppler_widths, const double* gammas,
+                               int gamma_cols, const double* alphas, const double* weight, int64_t weight_ld,
+                               double* out_damping, double* out_doppler, double* out_centre,
+                               double* out_damping_depth, double* out_doppler_depth, double* out_centre_depth);
+/* host-buffer twin of sdx_line_param_adjoint_dev (x, y, amp: voigt.py:148-149; w: voigt.py:39-84): the whole grid, contiguous arrays,
+ * weight [n_depth][n_nu]; any of the six outputs may be NULL, not all. */
+int sdx_line_param_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus,
+                               const double* doppler_widths, const double* gammas, int gamma_cols, const double* alphas,
+                               const double* weight, double* out_damping, double* out_doppler, double* out_centre,
+                               double* out_damping_depth, double* out_doppler_depth, double* out_centre_depth);
 /* The weight plane of the flux sensitivities from the response functions (sdx_response_dev):
  *     weight[k][j] = nu_weight[j] (R_alpha[k][j] / total[k][j])          (nu_weight = NULL: 1)
  * every operation one correctly rounded fp64 operation; a zero in total gives what IEEE gives (as sdx_response_project_dev). */

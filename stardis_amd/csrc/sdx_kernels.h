@@ -5185,4 +5185,219 @@ __global__ __launch_bounds__(kBlock) void k_line_adjoint_gather(AdjLines a, AdjW
     if (lane == 0 && out_line) out_line[l] = line;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Line-profile sensitivities (include/stardis_hip.h, sdx_line_param_adjoint_dev): beside S0 = sum W T of the adjoint above, per item
+//     Sx = sum W amp K_x,   Sxx = sum W amp x K_x,   Sy = sum W amp K_y        (voigt_grad_x: K_x, K_y of the region's own formula)
+// over the same window clipped to the same shard, from which the gather forms
+//     d/d ln gamma_ld = y Sy,    d/d ln dw_ld = -(S0 + Sxx + y Sy),    d/d nu_l = -Sx / dw_ld.
+// The plan is the adjoint's (k_line_adjoint_setup, k_line_adjoint_plan: the same windows, the same three classes, the same lists), and so
+// is the discipline of the sums: a lane adds its points in ascending order, one FMA per term and sum; a butterfly per sum closes the
+// item or the tile; lane 0 adds the tiles of a supertile in ascending order; the gather adds the supertiles in ascending order and the
+// depths by the butterfly.  No floating-point atomics.  Storage: w.sld is [4][items] (sum k of an item at sld[k * items + item]; the
+// plan's zero for an empty item lands in plane 0 and is not read), w.partial [tiled items][M][4], w.cap counts the groups of four.
+constexpr int kAdjSums = 4;
+struct ParamOut {
+    double *damping, *doppler, *centre;                    // [N_l] or null
+    double *damping_depth, *doppler_depth, *centre_depth;  // [N_l][N_d] or null
+};
+// the four sums of one point into acc[0..3]
+__device__ __forceinline__ void param_add(double (&acc)[kAdjSums], double wt, double x, double t, double tx, double ty)
+{
+    acc[0] = fma(wt, t, acc[0]);
+    acc[1] = fma(wt, tx, acc[1]);
+    acc[2] = fma(wt, x * tx, acc[2]);
+    acc[3] = fma(wt, ty, acc[3]);
+}
+
+template <int G>
+__global__ __launch_bounds__(kBlock) void k_line_param_adjoint(AdjLines a, AdjWork w, const double* __restrict__ weight, int64_t wld)
+{
+    constexpr int kPerWave = 64 / G;
+    const int lane = threadIdx.x & 63, sub = lane & (G - 1);
+    const int64_t n_waves = (int64_t)gridDim.x * (kBlock / 64);
+    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    const double d_nu = w.pd[0], r_dnu = w.pd[1];
+    const int64_t n_units = w.counters[G == 64 ? 1 : 0];
+    const int64_t n_items = a.n_lines * a.n_depth;
+    const int* __restrict__ list = G == 64 ? w.list_long : w.list_short;
+    for (int64_t u0 = wave * kPerWave; u0 < n_units; u0 += n_waves * kPerWave) {  // (wave-uniform: every lane reaches the butterfly)
+        const int64_t u = u0 + lane / G;
+        const bool on = u < n_units;
+        const int64_t item = on ? list[u] : 0;
+        const int64_t l = item / a.n_depth;
+        const int d = (int)(item - l * a.n_depth);
+        const double lnu = a.line_nus[l], dw = a.doppler[item], g = a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)], al = a.alphas[item];
+        int64_t b, e;
+        adjoint_window(a, w, d_nu, r_dnu, l, dw, g, al, b, e);
+        if (!on) e = b;
+        double inv, y, amp;
+        narrow_params(dw, g, al, inv, y, amp);
+        const RegionIGrad k1 = region1_grad_setup(y, amp);
+        const double* __restrict__ wrow = weight + (size_t)d * wld;
+        double acc[kAdjSums] = {0.0, 0.0, 0.0, 0.0};
+        for (int64_t i = b + sub; i < e; i += G) {
+            const double x = (a.nus[i] - lnu) * inv;
+            double t, tx, ty;
+            voigt_grad_x(x, y, amp, k1, t, tx, ty);
+            param_add(acc, wrow[i - a.nu_begin], x, t, tx, ty);
+        }
+#pragma unroll
+        for (int k = 0; k < kAdjSums; ++k) {
+#pragma unroll
+            for (int off = G >> 1; off > 0; off >>= 1) acc[k] = add_rn(acc[k], __shfl_xor(acc[k], off));
+        }
+        if (sub == 0 && on) {
+#pragma unroll
+            for (int k = 0; k < kAdjSums; ++k) w.sld[(size_t)k * n_items + item] = acc[k];
+        }
+    }
+}
+
+// wave = (depth d, supertile s, line subset j of J), as k_line_adjoint_tiled
+__global__ __launch_bounds__(kBlock) void k_line_param_adjoint_tiled(AdjLines a, AdjWork w, const double* __restrict__ weight, int64_t wld, int J)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wid = (int64_t)blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int per_depth = w.n_tiles * J;
+    const int d = (int)(wid / per_depth);
+    if (d >= a.n_depth || w.counters[2] == 0) return;
+    const int r = (int)(wid - (int64_t)d * per_depth), s = r / J, j = r - s * J;
+    int M, tps;
+    adj_tiling(w, M, tps);
+    const int n_d = w.counters[4 + d];
+    if (s >= M || j >= n_d) return;
+    const double d_nu = w.pd[0], r_dnu = w.pd[1];
+    const int64_t shard_end = a.nu_begin + a.nu_count;
+    const double* __restrict__ wrow = weight + (size_t)d * wld;
+    const int* __restrict__ list = w.list_tiled + (size_t)d * a.n_lines;
+    const int t_end = min((s + 1) * tps, w.n_tiles);
+    for (int t = s * tps; t < t_end; ++t) {
+        const int64_t base = a.nu_begin + (int64_t)t * kAdjTile;
+        const int64_t tile_end = min(base + kAdjTile, shard_end);
+        const double nu_first = a.nus[base], nu_last = a.nus[tile_end - 1];  // (the grid descends)
+        double nu[kAdjTileP], wt[kAdjTileP];
+#pragma unroll
+        for (int p = 0; p < kAdjTileP; ++p) {
+            const int64_t i = base + p * 64 + lane;
+            const bool ok = i < shard_end;
+            nu[p] = ok ? a.nus[i] : 0.0;
+            wt[p] = ok ? wrow[i - a.nu_begin] : 0.0;
+        }
+        for (int e = j; e < n_d; e += J) {
+            const int64_t l = list[e];
+            const size_t item = (size_t)l * a.n_depth + d;
+            const double lnu = a.line_nus[l], dw = a.doppler[item], g = a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)], al = a.alphas[item];
+            int64_t b, we;
+            adjoint_window(a, w, d_nu, r_dnu, l, dw, g, al, b, we);
+            if (we <= base || b >= tile_end) continue;  // (uniform)
+            double inv, y, amp;
+            narrow_params(dw, g, al, inv, y, amp);
+            const RegionIGrad k1 = region1_grad_setup(y, amp);
+            double acc[kAdjSums] = {0.0, 0.0, 0.0, 0.0};
+            // the whole-tile wing path of k_line_adjoint_tiled, under its condition: every point passes voigt_grad_x's own test
+            const bool wings = (lnu > nu_first || lnu < nu_last) && add_rn(fabs((nu_first - lnu) * inv), y) > 15.0 && add_rn(fabs((nu_last - lnu) * inv), y) > 15.0;
+            if (wings && b <= base && we >= base + kAdjTile) {
+#pragma unroll
+                for (int p = 0; p < kAdjTileP; ++p) {
+                    const double x = (nu[p] - lnu) * inv;
+                    double tt, tx, ty;
+                    region1_grad(x, k1, tt, tx, ty);
+                    param_add(acc, wt[p], x, tt, tx, ty);
+                }
+            } else {
+                const unsigned len = (unsigned)(we - b);
+                const int rel0 = (int)(base + lane - b);  // (negative: in front of the window, far above len as an unsigned number)
+#pragma unroll
+                for (int p = 0; p < kAdjTileP; ++p)
+                    if ((unsigned)(rel0 + p * 64) < len) {
+                        const double x = (nu[p] - lnu) * inv;
+                        double tt, tx, ty;
+                        voigt_grad_x(x, y, amp, k1, tt, tx, ty);
+                        param_add(acc, wt[p], x, tt, tx, ty);
+                    }
+            }
+#pragma unroll
+            for (int k = 0; k < kAdjSums; ++k) {
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) acc[k] = add_rn(acc[k], __shfl_xor(acc[k], off));
+            }
+            if (lane == 0) {
+                double* const slot = w.partial + ((size_t)w.tslot[item] * M + s) * kAdjSums;
+                const bool first = t == max(s * tps, (int)((b - a.nu_begin) / kAdjTile));  // the supertile's first tile inside the window
+#pragma unroll
+                for (int k = 0; k < kAdjSums; ++k) slot[k] = first ? acc[k] : add_rn(slot[k], acc[k]);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_line_param_adjoint_gather(AdjLines a, AdjWork w, ParamOut o)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t l = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (l >= a.n_lines) return;
+    int M, tps;
+    adj_tiling(w, M, tps);
+    const size_t n_items = (size_t)a.n_lines * a.n_depth;
+    double line[3] = {0.0, 0.0, 0.0};
+    for (int d0 = 0; d0 < a.n_depth; d0 += 64) {
+        const int d = d0 + lane;
+        double v[3] = {0.0, 0.0, 0.0};
+        if (d < a.n_depth) {
+            const size_t item = (size_t)l * a.n_depth + d;
+            const double dw = a.doppler[item], g = a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)], al = a.alphas[item];
+            int64_t b, e;
+            const int64_t hw = adjoint_window(a, w, w.pd[0], w.pd[1], l, dw, g, al, b, e);
+            const int cls = adjoint_class(hw, b, e);
+            double sum[kAdjSums] = {0.0, 0.0, 0.0, 0.0};
+            if (cls == 3) {
+                const int slot = w.tslot[item];
+                const int sa = (int)((b - a.nu_begin) / kAdjTile) / tps, sb = (int)((e - 1 - a.nu_begin) / kAdjTile) / tps;
+                for (int s = sa; s <= sb; ++s) {
+#pragma unroll
+                    for (int k = 0; k < kAdjSums; ++k) sum[k] = add_rn(sum[k], w.partial[((size_t)slot * M + s) * kAdjSums + k]);
+                }
+            } else if (cls != 0) {
+#pragma unroll
+                for (int k = 0; k < kAdjSums; ++k) sum[k] = w.sld[(size_t)k * n_items + item];
+            }
+            if (cls != 0) {  // (an item without a term in the shard: exactly 0)
+                double inv, y, amp;
+                narrow_params(dw, g, al, inv, y, amp);
+                v[0] = mul_rn(y, sum[3]);
+                v[1] = -add_rn(add_rn(sum[0], sum[2]), v[0]);
+                v[2] = -mul_rn(sum[1], inv);
+            }
+            if (o.damping_depth) o.damping_depth[item] = v[0];
+            if (o.doppler_depth) o.doppler_depth[item] = v[1];
+            if (o.centre_depth) o.centre_depth[item] = v[2];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v[k] = add_rn(v[k], __shfl_xor(v[k], off));
+            line[k] = add_rn(line[k], v[k]);
+        }
+    }
+    if (lane == 0) {
+        if (o.damping) o.damping[l] = line[0];
+        if (o.doppler) o.doppler[l] = line[1];
+        if (o.centre) o.centre[l] = line[2];
+    }
+}
+
+// voigt_grad_x element-wise, the sibling of k_voigt_term: amp K, amp K_x, amp K_y at x = delta_nu * inv_dw with the routine's own region
+// tests (tests/test_gpu_voigt_grad.py judges it point by point)
+__global__ __launch_bounds__(kBlock) void k_voigt_grad(int64_t n, const double* __restrict__ dnu, const double* __restrict__ inv_dw,
+                                                       const double* __restrict__ y, const double* __restrict__ amp, double* __restrict__ out_k,
+                                                       double* __restrict__ out_kx, double* __restrict__ out_ky)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const RegionIGrad k1 = region1_grad_setup(y[i], amp[i]);
+    double t, tx, ty;
+    voigt_grad_x(dnu[i] * inv_dw[i], y[i], amp[i], k1, t, tx, ty);
+    out_k[i] = t, out_kx[i] = tx, out_ky[i] = ty;
+}
+
 }  // namespace sdx

@@ -419,6 +419,164 @@ __device__ __forceinline__ double voigt_term(double delta_nu, double inv_dw, dou
     return voigt_add(0.0, delta_nu, inv_dw, y, amp, k);
 }
 
+// ---- the term's partial derivatives ---------------------------------------------------------------------------------
+// voigt_grad: T = amp K, amp K_x and amp K_y with K = Re w(x + i y), K_x = dK/dx, K_y = dK/dy — what the line-profile sensitivities
+// (sdx_line_param_adjoint_dev) sum per (line, depth) item.  What is differentiated is the reference's formula in the region that
+// voigt_term's own predicates pick on the same rounded x and y (voigt.py:39-84), the region boundaries held fixed: the derivative
+// between the steps, as the windows are held fixed.  Each region's w is analytic in z, so K_x = Re w'(z) and K_y = -Im w'(z):
+//   I    w = (i / sqrt(pi)) z / (z^2 - 1/2):  the real rational of region1_add differentiated directly, with v = x^2 + y^2 - 1/2,
+//        D = v^2 + 2 y^2:  K = (y / sqrt(pi)) (v + 1) / D,  K_x = (2 x y / sqrt(pi)) (2 y^2 - v (v + 2)) / D^2,
+//        K_y = [(v + 1 + 2 y^2) D - 4 y^2 (v + 1)^2] / (sqrt(pi) D^2) — no test, one reciprocal, every bracket far from cancelling
+//        relative to |w'| (v >= 100);
+//   II   w = i N / Q in z:               w' = i (N' - (N / Q) Q') / Q;
+//   III  w = P / Q in t = y - i x:       w' = -i (P' - (P / Q) Q') / Q;
+//   IV   w = exp(u) - t F(u), F = P / Q, u = t^2 = -z^2:  w' = -2 z exp(u) + i (F + 2 u dF/du), which needs Im exp(u): the sine.
+// NOT w' = -2 z w + 2 i / sqrt(pi) on the W4 values: the approximation is good to 1e-4 and that identity amplifies its error by |z|.
+// The quotient rule is taken in the form (N' - w Q') / Q: one reciprocal per point, |Q|^2, serves the value and the derivative.  The
+// polynomials and their derivatives come from one complex Horner pass (p' <- p + m p', p <- c + m p, FMA): the derivative divides the
+// recurrences' error by a second small denominator, and the complex form keeps region IV at the reference's own operation order's
+// error (tests/test_gpu_voigt_grad.py judges the routine point by point against the formulas in extended precision).
+struct RegionIGrad {
+    double yk;   // amp * y / sqrt(pi), region1_setup's
+    double c;    // amp / sqrt(pi)
+    double cv;   // y^2 - 1/2
+    double cd;   // 2 y^2
+};
+__device__ __forceinline__ RegionIGrad region1_grad_setup(double y, double amp)
+{
+    const double y2 = y * y;
+    return {amp * (y * kInvSqrtPi), amp * kInvSqrtPi, y2 - 0.5, y2 + y2};
+}
+// region I, test-free (the tiled role of the adjoint calls it for whole tiles under the condition that guards region1_add there)
+__device__ __forceinline__ void region1_grad(double x, const RegionIGrad& k, double& t, double& tx, double& ty)
+{
+    const double v = fma(x, x, k.cv);
+    const double den = fma(v, v, k.cd);
+    const double e = v + 1.0;
+    const double r = recip(den), r2 = r * r;
+    t = fma(k.yk, v, k.yk) * r;
+    const double nx = fma(-v, v + 2.0, k.cd);                          // 2 y^2 - v^2 - 2 v
+    tx = ((x * (k.yk + k.yk)) * nx) * r2;
+    const double ny = fma(e + k.cd, den, -((k.cd + k.cd) * (e * e)));  // (v + 1 + 2 y^2) D - 4 y^2 (v + 1)^2
+    ty = (k.c * ny) * r2;
+}
+// sin(a) and cos(a) for |a| < ~1e3: cos_small's reduction and polynomials, both values
+__device__ __forceinline__ void sincos_small(double a, double& s, double& c)
+{
+    const double n = rint(a * 0x1.45f306dc9c883p-1);
+    double r = fma(n, -0x1.921fb54400000p+0, a);
+    r = fma(n, -0x1.0b4611a626331p-34, r);
+    const double z = r * r;
+    double ps = fma(z, 0x1.5d93a5acfd57cp-33, -0x1.ae5e68a2b9cebp-26);
+    ps = fma(z, ps, 0x1.71de357b1fe7dp-19);
+    ps = fma(z, ps, -0x1.a01a019c161d5p-13);
+    ps = fma(z, ps, 0x1.111111110f8a6p-7);
+    const double sn = fma(z * r, fma(z, ps, -0x1.5555555555549p-3), r);
+    double pc = fma(z, -0x1.8fae9be8838d4p-37, 0x1.1ee9ebdb4b1c4p-29);
+    pc = fma(z, pc, -0x1.27e4f809c52adp-22);
+    pc = fma(z, pc, 0x1.a01a019cb1590p-16);
+    pc = fma(z, pc, -0x1.6c16c16c15177p-10);
+    pc = fma(z, pc, 0x1.555555555554cp-5);
+    const double hz = 0.5 * z, w = 1.0 - hz;
+    const double cs = w + (((1.0 - w) - hz) + z * (z * pc));
+    const int q = (int)n & 3;
+    const double sv = (q & 1) ? cs : sn, cv = (q & 1) ? sn : cs;
+    s = (q >= 2) ? -sv : sv;
+    c = (q == 1 || q == 2) ? -cv : cv;
+}
+// one Horner step of a polynomial and of its derivative: dp <- p + m dp, then p <- c + m p
+__device__ __forceinline__ void horner_grad(double c, c64 m, c64& p, c64& dp)
+{
+    dp = {fma(m.re, dp.re, fma(-m.im, dp.im, p.re)), fma(m.re, dp.im, fma(m.im, dp.re, p.im))};
+    p = horner_add(c, m, p);
+}
+// regions II-IV -> K, K_x, K_y (not scaled; by value: a reference would send the results of the call through scratch memory)
+struct KGrad {
+    double k, kx, ky;
+};
+__device__ __attribute__((noinline)) KGrad faddeeva_grad_core(double x, double y, double ax)
+{
+    const c64 z = {x, y};
+    const double s = add_rn(ax, y);
+    if (s > 5.5) {  // region II: N = z (z^2 / sqrt(pi) - c), Q = 3/4 + z^2 (z^2 - 3)
+        const c64 z2 = cmul(z, z);
+        const c64 n = cmul(z, c64{fma(z2.re, kInvSqrtPi, -1.4104739589), z2.im * kInvSqrtPi});
+        const c64 dn = {fma(3.0 * z2.re, kInvSqrtPi, -1.4104739589), (3.0 * z2.im) * kInvSqrtPi};
+        c64 q = cmul(z2, c64{z2.re - 3.0, z2.im});
+        q.re += 0.75;
+        const c64 dq = cmul(c64{x + x, y + y}, c64{fma(2.0, z2.re, -3.0), z2.im + z2.im});
+        const double ri = recip(fma(q.re, q.re, q.im * q.im));
+        const c64 iq = {q.re * ri, -(q.im * ri)};
+        const c64 f = cmul(n, iq);                                           // N / Q;  w = i f
+        const c64 wq = cmul(f, dq);
+        const c64 g = cmul(c64{dn.re - wq.re, dn.im - wq.im}, iq);            // w' = i g
+        return {-f.im, -g.im, -g.re};
+    }
+    const c64 t = {y, -x};
+    if (y >= sub_rn(mul_rn(0.195, ax), 0.176)) {  // region III
+        c64 p = {0.5642236, 0.0}, dp = {0.0, 0.0};
+        horner_grad(3.778987, t, p, dp);
+        horner_grad(11.96482, t, p, dp);
+        horner_grad(20.20933, t, p, dp);
+        horner_grad(16.4955, t, p, dp);
+        c64 q = {1.0, 0.0}, dq = {0.0, 0.0};
+        horner_grad(6.699398, t, q, dq);
+        horner_grad(21.69274, t, q, dq);
+        horner_grad(39.27121, t, q, dq);
+        horner_grad(38.82363, t, q, dq);
+        horner_grad(16.4955, t, q, dq);
+        const double ri = recip(fma(q.re, q.re, q.im * q.im));
+        const c64 iq = {q.re * ri, -(q.im * ri)};
+        const c64 f = cmul(p, iq);                                            // w
+        const c64 wq = cmul(f, dq);
+        const c64 g = cmul(c64{dp.re - wq.re, dp.im - wq.im}, iq);            // dw/dt;  w' = -i g
+        return {f.re, g.im, g.re};
+    }
+    // region IV: polynomials in m = -u (all-positive coefficients), F = P / Q, dF/du = -dF/dm
+    const c64 u = cmul(t, t);
+    const double ex = exp_neg(-u.re);
+    double sn, cs;
+    sincos_small(u.im, sn, cs);
+    const c64 m = {-u.re, -u.im};
+    c64 p = {0.56419, 0.0}, dp = {0.0, 0.0};
+    horner_grad(1.320522, m, p, dp);
+    horner_grad(35.7668, m, p, dp);
+    horner_grad(219.031, m, p, dp);
+    horner_grad(1540.787, m, p, dp);
+    horner_grad(3321.99, m, p, dp);
+    horner_grad(36183.31, m, p, dp);
+    c64 q = {1.0, 0.0}, dq = {0.0, 0.0};
+    horner_grad(1.84144, m, q, dq);
+    horner_grad(61.5704, m, q, dq);
+    horner_grad(364.219, m, q, dq);
+    horner_grad(2186.18, m, q, dq);
+    horner_grad(9022.23, m, q, dq);
+    horner_grad(24322.8, m, q, dq);
+    horner_grad(32066.6, m, q, dq);
+    const double ri = recip(fma(q.re, q.re, q.im * q.im));
+    const c64 iq = {q.re * ri, -(q.im * ri)};
+    const c64 f = cmul(p, iq);
+    const c64 wq = cmul(f, dq);
+    const c64 fm = cmul(c64{dp.re - wq.re, dp.im - wq.im}, iq);              // dF/dm
+    const c64 um = cmul(u, fm);
+    const c64 h = {fma(-2.0, um.re, f.re), fma(-2.0, um.im, f.im)};          // F + 2 u dF/du
+    const c64 e = {ex * cs, ex * sn};                                         // exp(u)
+    const c64 ze = cmul(z, e), tf = cmul(t, f);
+    // w' = -2 z exp(u) + i h:  Re w' and -Im w'
+    return {e.re - tf.re, fma(-2.0, ze.re, -h.im), fma(2.0, ze.im, -h.re)};
+}
+// -> T = amp K, amp K_x, amp K_y at x = delta_nu * inv_dw (the amplitude is inside k for region I)
+__device__ __forceinline__ void voigt_grad_x(double x, double y, double amp, const RegionIGrad& k, double& t, double& tx, double& ty)
+{
+    const double ax = fabs(x);
+    if (add_rn(ax, y) > 15.0) {
+        region1_grad(x, k, t, tx, ty);
+        return;
+    }
+    const KGrad c = faddeeva_grad_core(x, y, ax);
+    t = amp * c.k, tx = amp * c.kx, ty = amp * c.ky;
+}
+
 // ---- fp32 evaluation, mixed-precision mode only ---------------------------------------------------------------------
 // The same four Humlicek regions evaluated in fp32 with the complex arithmetic PACKED: a complex number is one float2v
 // (re, im), a complex Horner step p <- c + t p is two v_pk_fma_f32 (t.re * p + (c, 0), then (-t.im, t.im) * p.yx + that)

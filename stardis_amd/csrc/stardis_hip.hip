@@ -1840,6 +1840,18 @@ int sdx_voigt_term_f32_dev(sdx_ctx* ctx, int64_t n, const double* delta_nu, cons
     return check_launch("k_voigt_term32");
 }
 
+int sdx_voigt_grad_dev(sdx_ctx* ctx, int64_t n, const double* delta_nu, const double* inv_doppler_width, const double* y, const double* amp,
+                       double* out_k, double* out_kx, double* out_ky)
+{
+    REQUIRE(ctx && n >= 0 && (n == 0 || (delta_nu && inv_doppler_width && y && amp && out_k && out_kx && out_ky)), "voigt_grad: bad arguments");
+    if (n == 0) return SDX_OK;
+    {
+        LaunchScope ls(ctx, "k_voigt_grad");
+        hipLaunchKernelGGL(k_voigt_grad, dim3(blocks1(n)), dim3(kBlock), 0, ctx->stream, n, delta_nu, inv_doppler_width, y, amp, out_k, out_kx, out_ky);
+    }
+    return check_launch("k_voigt_grad");
+}
+
 // ================================================================================================ broadening
 int sdx_calc_gamma_dev(sdx_ctx* ctx, int64_t n_lines, int n_depth, const int32_t* z, const int32_t* ion, const double* e_ion,
                        const double* e_up, const double* e_lo, const double* a_ul, const double* ne, const double* temps,
@@ -2543,6 +2555,96 @@ int sdx_line_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     HostIo io{ctx};
     if ((rc = io.stage(plan))) return rc;
     if ((rc = sdx_line_adjoint_dev(ctx, n_depth, n_nu, d_nus, 0, n_nu, n_lines, d_ln, d_dw, d_g, gamma_cols, d_a, d_wt, n_nu, d_line, d_ld))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+// ---- line-profile sensitivities (k_line_param_adjoint) ----------------------------------------------------------------------
+// sdx_line_adjoint_dev's checks, plan and launch geometry; four sums per item (AdjWork::sld [4][items], partial [tiled items][M][4],
+// cap in groups of four).  Six launches under the stage name k_line_param_adjoint.
+int sdx_line_param_adjoint_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count, int64_t n_lines,
+                               const double* line_nus, const double* doppler, const double* gammas, int gamma_cols, const double* alphas,
+                               const double* weight, int64_t weight_ld, double* out_damping, double* out_doppler, double* out_centre,
+                               double* out_damping_depth, double* out_doppler_depth, double* out_centre_depth)
+{
+    REQUIRE(ctx, "line_param_adjoint: null context");
+    REQUIRE(!ctx->mixed_precision, "line_param_adjoint: no line-profile sensitivities with mixed_precision = 1 (the adjoint is that of the fp64 direct sum)");
+    REQUIRE(n_depth > 0 && n_depth <= 65535 && n_nu >= 0 && n_lines >= 0 && n_nu < (int64_t)2147483647, "line_param_adjoint: need 1 <= n_depth <= 65535, sizes >= 0 and n_nu within int32");
+    REQUIRE(n_lines * (int64_t)n_depth < (int64_t)2147483647 - 64, "line_param_adjoint: n_lines * n_depth must fit int32");
+    REQUIRE(out_damping || out_doppler || out_centre || out_damping_depth || out_doppler_depth || out_centre_depth, "line_param_adjoint: no output requested");
+    REQUIRE(gamma_cols == n_depth || gamma_cols == 1, "line_param_adjoint: gammas must have n_depth or 1 columns");
+    REQUIRE(nu_begin >= 0 && nu_count >= 0 && nu_begin + nu_count <= n_nu, "line_param_adjoint: frequency shard outside the grid");
+    if (n_nu == 0 || n_lines == 0 || nu_count == 0) return SDX_OK;
+    REQUIRE(nus && line_nus && doppler && gammas && alphas && weight && weight_ld >= nu_count, "line_param_adjoint: null pointer or weight_ld below nu_count");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int64_t n_items = n_lines * n_depth;
+    AdjWork w{};
+    w.n_tiles = (int)((nu_count + kAdjTile - 1) / kAdjTile);
+    REQUIRE((int64_t)n_depth * w.n_tiles < ((int64_t)1 << 26), "line_param_adjoint: n_depth * nu_count too large for one launch");
+    w.cap = std::min<int64_t>(std::max<int64_t>(ctx->adjoint_partials / kAdjSums, n_items), n_items * w.n_tiles);
+    const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_int = pad(4 * (size_t)n_items), b_sums = pad(8 * (size_t)n_items * kAdjSums), b_lines = pad(4 * (size_t)n_lines), b_cnt = pad(4 * (size_t)(4 + n_depth));
+    const size_t need = 256 + b_cnt + b_lines + 4 * b_int + b_sums + pad(8 * (size_t)w.cap * kAdjSums);
+    int rc = ensure(ctx, &ctx->adj_ws, &ctx->adj_ws_bytes, need);
+    if (rc) return rc;
+    char* p = (char*)ctx->adj_ws;
+    w.pd = (double*)p, p += 256;
+    w.counters = (int*)p, p += b_cnt;
+    w.centre = (int*)p, p += b_lines;
+    w.list_short = (int*)p, p += b_int;
+    w.list_long = (int*)p, p += b_int;
+    w.list_tiled = (int*)p, p += b_int;
+    w.tslot = (int*)p, p += b_int;
+    w.sld = (double*)p, p += b_sums;
+    w.partial = (double*)p;
+    const AdjLines a{n_depth, gamma_cols, n_nu, nu_begin, nu_count, n_lines, nus, line_nus, doppler, gammas, alphas};
+    const ParamOut o{out_damping, out_doppler, out_centre, out_damping_depth, out_doppler_depth, out_centre_depth};
+    const int64_t cap = (int64_t)ctx->n_cu * 32;
+    const unsigned nb_short = (unsigned)std::min<int64_t>(cap, (n_items + 63) / 64);
+    const unsigned nb_long = (unsigned)std::min<int64_t>(cap, (n_items + 3) / 4);
+    const int64_t dt = (int64_t)n_depth * w.n_tiles;
+    const int J = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)32, n_lines, ((int64_t)ctx->n_cu * 32 + dt - 1) / dt}));
+    {
+        LaunchScope ls(ctx, "k_line_param_adjoint");
+        hipLaunchKernelGGL(k_line_adjoint_setup, dim3(1 + (unsigned)((n_lines + kPreBlock - 1) / kPreBlock)), dim3(kPreBlock), 0, ctx->stream, a, w);
+        hipLaunchKernelGGL(k_line_adjoint_plan, dim3(blocks1(n_items)), dim3(kBlock), 0, ctx->stream, a, w);
+        hipLaunchKernelGGL(k_line_param_adjoint<4>, dim3(nb_short), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld);
+        hipLaunchKernelGGL(k_line_param_adjoint<64>, dim3(nb_long), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld);
+        hipLaunchKernelGGL(k_line_param_adjoint_tiled, dim3((unsigned)((dt * J + 3) / 4)), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld, J);
+        hipLaunchKernelGGL(k_line_param_adjoint_gather, dim3((unsigned)((n_lines + 3) / 4)), dim3(kBlock), 0, ctx->stream, a, w, o);
+    }
+    return check_launch("k_line_param_adjoint");
+}
+
+int sdx_line_param_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus, const double* doppler,
+                               const double* gammas, int gamma_cols, const double* alphas, const double* weight, double* out_damping,
+                               double* out_doppler, double* out_centre, double* out_damping_depth, double* out_doppler_depth, double* out_centre_depth)
+{
+    int rc;
+    if ((rc = sdx_line_param_adjoint_dev(ctx, n_depth, 0, nullptr, 0, 0, n_lines, nullptr, nullptr, nullptr, gamma_cols, nullptr, nullptr, 0, out_damping,
+                                         out_doppler, out_centre, out_damping_depth, out_doppler_depth, out_centre_depth)))
+        return rc;  // refusals before any copy
+    REQUIRE(n_nu >= 0, "line_param_adjoint: negative n_nu");
+    if (n_nu == 0 || n_lines == 0) return SDX_OK;
+    REQUIRE(nus && line_nus && doppler && gammas && alphas && weight, "line_param_adjoint: null pointer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), items = (size_t)n_lines * n_depth * f8;
+    const double *d_nus, *d_ln, *d_dw, *d_g, *d_a, *d_wt;
+    double* d_out[6];
+    double* const host_out[6] = {out_damping, out_doppler, out_centre, out_damping_depth, out_doppler_depth, out_centre_depth};
+    HostPlan plan;
+    plan.in(nus, (size_t)n_nu * f8, &d_nus);
+    plan.in(line_nus, (size_t)n_lines * f8, &d_ln);
+    plan.in(doppler, items, &d_dw);
+    plan.in(gammas, (size_t)n_lines * gamma_cols * f8, &d_g);
+    plan.in(alphas, items, &d_a);
+    plan.in(weight, (size_t)n_depth * n_nu * f8, &d_wt);
+    for (int k = 0; k < 6; ++k) plan.out(host_out[k], k < 3 ? (size_t)n_lines * f8 : items, &d_out[k]);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_line_param_adjoint_dev(ctx, n_depth, n_nu, d_nus, 0, n_nu, n_lines, d_ln, d_dw, d_g, gamma_cols, d_a, d_wt, n_nu, d_out[0], d_out[1], d_out[2],
+                                         d_out[3], d_out[4], d_out[5])))
+        return rc;
     if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }

@@ -15,6 +15,8 @@ from . import constants as K
 from . import linelist as LL
 from ._lib import Continuum, default_context, ptr_of
 
+LINE_WRT = ("strength", "damping", "doppler", "centre")  # wrt= of the line sensitivities; the last three: sdx_line_param_adjoint_dev's outputs
+
 
 def shard_bounds(n_nu, world_size, rank):
     """Contiguous block of the GLOBAL frequency index owned by `rank`."""
@@ -543,7 +545,40 @@ class SpectralSynthesizer:
         (after the uploaded tables or the list's device arrays were overwritten in place)."""
         self._line_tables = None
 
-    def line_sensitivities(self, weights=None, per_depth=False):
+    @staticmethod
+    def _wrt_names(wrt):
+        """wrt= of the sensitivities -> (names, single): one name or a tuple of names out of LINE_WRT"""
+        single = isinstance(wrt, str)
+        names = (wrt,) if single else tuple(wrt)
+        if not names or any(k not in LINE_WRT for k in names) or len(set(names)) != len(names):
+            raise ValueError(f"wrt must be one of {LINE_WRT} or a tuple of different ones, got {wrt!r}")
+        return names, single
+
+    def _line_nus_in_caller_order(self):
+        """the lines' rest frequencies as a host array, row k = line k of the tables of _tables_in_caller_order"""
+        if self.linelist is not None:
+            return self.linelist._keep["nu"].numpy()
+        if self._line_order is None:
+            return self.d_ln.numpy()
+        self._tables_in_caller_order()
+        return self._line_tables[4].numpy()
+
+    def microturbulence_sensitivity(self, xi, weights=None):
+        """-> float: d(sum_i weights[i] F_nu_i[-1]) / d xi of the microturbulent velocity xi (cm/s) that the lines' Doppler widths were
+        built with, at fixed windows and regions, from the last step.  doppler_width = nu / c sqrt(2 k T / m + xi^2)
+        (sdx_broadening.h), so d ln doppler_ld / d xi = xi (nu_l / c)^2 / doppler_ld^2 whatever the mass, and the value is
+        sum_{l, d} line_sensitivities(weights, per_depth=True, wrt="doppler")[l, d] xi (nu_l / c)^2 / doppler_ld^2, summed on the host
+        (a diagnostic call: it waits for the stream).  The damping constants are taken not to depend on xi.  xi = 0 gives exactly 0."""
+        self._require_response()
+        xi = float(xi)
+        if xi == 0.0:
+            return 0.0
+        per = self.line_sensitivities(weights, per_depth=True, wrt="doppler").numpy()
+        dw = self._tables_in_caller_order()[1].numpy()
+        nu_over_c = self._line_nus_in_caller_order() / K.C_CGS
+        return float(np.sum(per * (xi * (nu_over_c * nu_over_c)[:, None] / (dw * dw))))
+
+    def line_sensitivities(self, weights=None, per_depth=False, wrt="strength"):
         """-> DeviceArray (n_lines,), or (n_lines, N_d) with per_depth=True: for every line l of the list, in the order the caller passed
         the lines, the derivative of  sum_i weights[i] F_nu_i[-1]  over this synthesizer's columns with respect to ln(strength of line
         l) — ln gf, or the abundance of a species that has this line alone — at FIXED WINDOWS, from the last step: the weight plane
@@ -561,7 +596,12 @@ class SpectralSynthesizer:
         The line tables: a sorted dense list is read where the step reads it; a line list of scalars and an unsorted dense list are
         read from a snapshot taken at the first call (forget_line_tables() after changing the uploaded values in place).
         A frequency shard returns the partial sum over its own columns: shards add.  Needs keep_response=True; on demand, like
-        flux_derivative — a synthesizer that never asks runs the launches it always ran."""
+        flux_derivative — a synthesizer that never asks runs the launches it always ran.
+        wrt: "strength" (the above), or the derivative of the same sum with respect to a number that sets the line's SHAPE, at fixed
+        windows and fixed Humlicek regions (sdx_line_param_adjoint_dev): "damping" — ln gamma_l (an enhancement factor on the damping
+        constant, the same at every depth), "doppler" — ln doppler_width_l, "centre" — the rest frequency nu_l, per Hz.  A tuple of
+        them returns a dict of arrays, the shape parameters from ONE pass over the terms."""
+        names, single = self._wrt_names(wrt)
         self._require_response()
         c = self.ctx
         d_w = None
@@ -581,10 +621,21 @@ class SpectralSynthesizer:
         d_W = c.empty((self.n_depth, cnt))
         c.call("sdx_response_weight_dev", self.n_depth, cnt, self.d_Ra.ptr, cnt, self.d_total.ptr, cnt, ptr_of(d_w), d_W.ptr, cnt)
         ln_ptr, d_dw, d_g, d_a = self._tables_in_caller_order()
-        out = c.empty((self.n_lines, self.n_depth) if per_depth else (self.n_lines,))
-        c.call("sdx_line_adjoint_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, cnt, self.n_lines, ln_ptr, d_dw.ptr, d_g.ptr,
-               self.gamma_cols, d_a.ptr, d_W.ptr, cnt, None if per_depth else out.ptr, out.ptr if per_depth else None)
-        return out
+        shape = (self.n_lines, self.n_depth) if per_depth else (self.n_lines,)
+        res = {}
+        if "strength" in names:
+            out = res["strength"] = c.empty(shape)
+            c.call("sdx_line_adjoint_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, cnt, self.n_lines, ln_ptr, d_dw.ptr, d_g.ptr,
+                   self.gamma_cols, d_a.ptr, d_W.ptr, cnt, None if per_depth else out.ptr, out.ptr if per_depth else None)
+        params = [k for k in LINE_WRT[1:] if k in names]
+        if params:
+            for k in params:
+                res[k] = c.empty(shape)
+            ptrs = [ptr_of(res.get(k)) for k in LINE_WRT[1:]]
+            none = [None] * 3
+            c.call("sdx_line_param_adjoint_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, cnt, self.n_lines, ln_ptr, d_dw.ptr,
+                   d_g.ptr, self.gamma_cols, d_a.ptr, d_W.ptr, cnt, *(none + ptrs if per_depth else ptrs + none))
+        return res[names[0]] if single else {k: res[k] for k in names}
 
     def _require_instrument(self):
         if self.instrument is None:
@@ -621,23 +672,25 @@ class SpectralSynthesizer:
             return (w, self.ctx.zeros((n,))) if with_continuum else w
         return inst.adjoint(self.d_lambdas, n, d_c, flux=self.d_Flam, reference=self.d_Fclam, nus=self.d_nus, out_reference=bool(with_continuum))
 
-    def observed_line_sensitivities(self, c, normalized=False, per_depth=False):
+    def observed_line_sensitivities(self, c, normalized=False, per_depth=False, wrt="strength"):
         """-> DeviceArray (n_lines,), or (n_lines, N_d) with per_depth=True: d(sum_j c_j observed_j) / d ln gf_l for every line of the
         list, at fixed windows, from the last step — line_sensitivities(weights=pixel_weights_to_grid(c, normalized), per_depth): the
         chain response functions -> line adjoint -> instrument, from the detector's pixels to every line.  normalized=True: of
         observed_normalized; the zero-line continuum does not depend on the lines, so its cotangent does not enter.  Needs
-        instrument= and keep_response=True (normalized: keep_continuum_flux=True)."""
+        instrument= and keep_response=True (normalized: keep_continuum_flux=True).  wrt: as for line_sensitivities."""
+        self._wrt_names(wrt)
         self._require_instrument()
         self._require_response()
-        return self.line_sensitivities(weights=self.pixel_weights_to_grid(c, normalized), per_depth=per_depth)
+        return self.line_sensitivities(weights=self.pixel_weights_to_grid(c, normalized), per_depth=per_depth, wrt=wrt)
 
-    def chi2_line_gradient(self, data, inverse_variance, normalized=False, per_depth=False):
+    def chi2_line_gradient(self, data, inverse_variance, normalized=False, per_depth=False, wrt="strength"):
         """-> (chi2, DeviceArray): chi2 = sum_j ivar_j (data_j - observed_j)^2 of the last step's observed (normalized=True:
         observed_normalized) spectrum against data, and its gradient to ln gf of every line, (n_lines,) or (n_lines, N_d):
         observed_line_sensitivities with c_j = -2 ivar_j (data_j - observed_j).  A pixel whose observed value is NaN (the grid does not
         cover its window) or whose ivar is 0 is left out of both; leaving every pixel out is a ValueError.  data, inverse_variance:
         host arrays, one value per pixel.  A diagnostic call, not part of the step: it waits for the stream and forms the n_pix
-        residuals on the host."""
+        residuals on the host.  wrt: as for line_sensitivities (a tuple: the gradient is a dict)."""
+        self._wrt_names(wrt)
         self._require_instrument()
         self._require_response()
         if normalized:
@@ -655,7 +708,7 @@ class SpectralSynthesizer:
         r = np.where(use, d, 0.0) - np.where(use, obs, 0.0)
         w = np.where(use, ivar, 0.0)
         chi2 = float(np.sum(w * r * r))
-        return chi2, self.observed_line_sensitivities(-2.0 * w * r, normalized, per_depth)
+        return chi2, self.observed_line_sensitivities(-2.0 * w * r, normalized, per_depth, wrt)
 
     @property
     def observed(self):

@@ -73,6 +73,28 @@ def voigt_term(delta_nu, doppler_width, gamma, alpha=1.0, ctx=None, fp32=False):
     return r if r.ndim else r[()]
 
 
+def voigt_grad(delta_nu, doppler_width, gamma, alpha=1.0, ctx=None):
+    """-> (K amp, K_x amp, K_y amp): voigt_term's value and its partial derivatives to x = delta_nu / doppler_width and to
+    y = (gamma / (sqrt(pi) pi)) / doppler_width, K = Re w(x + i y), amp = alpha / (sqrt(pi) doppler_width) (voigt.py:148-149) — the
+    derivative of the reference's formula in the Humlicek region it picks (voigt.py:39-84), through the routine the line-profile
+    sensitivities evaluate (sdx_voigt_grad_dev; sdx_math.h voigt_grad_x)."""
+    ctx = ctx or default_context()
+    both = np.broadcast_arrays(_host(delta_nu), _host(doppler_width), _host(gamma), _host(alpha))
+    shape = both[0].shape
+    dnu, dw, g, a = (np.ascontiguousarray(v).reshape(-1) for v in both)
+    if np.any(dw == 0):
+        raise ZeroDivisionError("float division by zero")
+    sqrt_pi = np.float64(1.7724538509055159)
+    inv = 1.0 / dw
+    y = (g / (sqrt_pi * np.float64(np.pi))) / dw
+    amp = a / (sqrt_pi * dw)
+    d = [ctx.upload(v) for v in (dnu, inv, y, amp)]
+    out = [ctx.empty(dnu.shape) for _ in range(3)]
+    ctx.call("sdx_voigt_grad_dev", dnu.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, out[0].ptr, out[1].ptr, out[2].ptr)
+    r = tuple(o.numpy().reshape(shape) for o in out)
+    return r if shape else tuple(v[()] for v in r)
+
+
 # ------------------------------------------------------------------------------------------------ line opacity
 def _line_inputs(no_of_depth_points, line_nus, doppler_widths, gammas, alphas_array, sort=True):
     """The four line arrays as contiguous float64 in the kernels' shapes.  sort=True: stably sorted by frequency when they
@@ -150,6 +172,38 @@ def line_adjoint(no_of_depth_points, tracing_nus_values, line_nus, doppler_width
     ctx.call("sdx_line_adjoint_dev", nd, nus.size, d[0].ptr, begin, count, ln.size, d[1].ptr, d[2].ptr, d[3].ptr, g.shape[1], d[4].ptr,
              ptr_of(d_w), count, None if per_depth else out.ptr, out.ptr if per_depth else None)
     return out if device else out.numpy()
+
+
+LINE_PARAMS = ("damping", "doppler", "centre")
+
+
+def line_param_adjoint(no_of_depth_points, tracing_nus_values, line_nus, doppler_widths, gammas, alphas_array, weight, per_depth=False,
+                       ctx=None, device=False, shard=None, wrt=LINE_PARAMS):
+    """The line-profile twin of line_adjoint (sdx_line_param_adjoint_dev) -> dict with the keys "damping", "doppler", "centre" (those
+    named in wrt): the derivative of  sum_d sum_i weight[d, i] alpha_line_at_nu[d, i]  with respect to ln gamma, ln doppler_width and
+    the rest frequency (per Hz) of every line, at fixed windows and fixed Humlicek regions -> (n_lines,) each, or with per_depth=True
+    with respect to the value at each depth point (n_lines, N_d).  Arguments as for line_adjoint."""
+    wrt = tuple(wrt)
+    if not wrt or any(k not in LINE_PARAMS for k in wrt):
+        raise ValueError(f"wrt must name some of {LINE_PARAMS}, got {wrt}")
+    nus = _host(tracing_nus_values).reshape(-1)
+    ln, dw, g, al = _line_inputs(no_of_depth_points, line_nus, doppler_widths, gammas, alphas_array, sort=False)
+    nd = int(no_of_depth_points)
+    begin, count = (0, nus.size) if shard is None else (int(v) for v in shard)
+    if begin < 0 or count < 0 or begin + count > nus.size:
+        raise ValueError(f"shard {(begin, count)} lies outside the grid of {nus.size} frequencies")
+    shape = tuple(int(v) for v in (weight.shape if hasattr(weight, "shape") else np.shape(weight)))
+    if shape != (nd, count):
+        raise ValueError(f"weight must have shape {(nd, count)}, got {shape}")
+    ctx = ctx or default_context()
+    d_w = _dev(ctx, weight)
+    d = [ctx.upload(x) for x in (nus, ln, dw, g, al)]
+    out = {k: ctx.empty((ln.size, nd) if per_depth else (ln.size,)) for k in wrt}
+    ptrs = [ptr_of(out.get(k)) for k in LINE_PARAMS]
+    none = [None] * 3
+    ctx.call("sdx_line_param_adjoint_dev", nd, nus.size, d[0].ptr, begin, count, ln.size, d[1].ptr, d[2].ptr, d[3].ptr, g.shape[1], d[4].ptr,
+             ptr_of(d_w), count, *(none + ptrs if per_depth else ptrs + none))
+    return out if device else {k: v.numpy() for k, v in out.items()}
 
 
 # ------------------------------------------------------------------------------------------------ broadening
