@@ -624,6 +624,52 @@ int sdx_observe_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, cons
                             const double* edges, const double* sigma, double doppler, const double* pixel_weight, const double* nus,
                             double* w_flux, double* w_reference);
 
+/* ---- rotational broadening (v sin i) in velocity space, and its adjoint ----------------------------
+ * Gray's rotation profile on ANY ascending grid, applied on the rest-frame grid in front of sdx_observe_dev (the operator is
+ * multiplicative in lambda, so it commutes with the Doppler shift and does not read the Doppler factor).  The reference's
+ * rotation_broadening (mirrored by stardis_amd.postprocess.rotation_broadening) samples the kernel at integer pixel offsets for one
+ * velocity per pixel, which is a rotation profile on a log-uniform grid only, and has no transpose.
+ *   lambdas[n]  strictly ascending rest-frame wavelengths (Angstrom), flux[n], reference[n] optional (NULL: none);
+ *   V = v sin i >= 0 in km/s, eps in [0, 1] the linear limb-darkening coefficient; beta = V / c, c = 299792.458 km/s.
+ * For point i, every operation one correctly rounded fp64 operation, in this order (the device function rot_weight):
+ *     reach_i = lambdas[i] beta,   lo_i = lambdas[i] - reach_i,   hi_i = lambdas[i] + reach_i,
+ *     y_ij = (lambdas[j] - lambdas[i]) / reach_i,   q_ij = 1 - y_ij y_ij,
+ *     INCLUDED(i, j) = (lo_i <= lambdas[j] && lambdas[j] <= hi_i && q_ij > 0) || j == i      (j = i: q = 1),
+ *     K_ij = (2 (1 - eps)) sqrt(q_ij) + ((pi / 2) eps) q_ij      (Gray's profile, unnormalised),
+ *     h_j = (lambdas[j+1] - lambdas[j-1]) / 2, the ends clamped as in sdx_observe_dev,      w_ij = K_ij h_j,
+ *     den_i = sum_j w_ij,   out[i] = (sum_j w_ij flux[j]) / den_i,   out_reference[i] = (sum_j w_ij reference[j]) / den_i
+ * over the included j — the discrete form of  integral flux(lambda_i (1 - v / c)) G_rot(v) dv.  den_i > 0 always (i includes itself),
+ * so a constant stays constant to rounding and nothing is NaN.  A window that reaches past an end of the grid is TRUNCATED AND
+ * RENORMALISED: it sums what exists, and the points within reach of either end are edge-affected (Instrument.edge_affected reports
+ * the pixels they feed).  !(V > 0) — zero, negative, NaN — is a copy: out[i] = flux[i] bit for bit.
+ * The sums: a point's 8 or 64 lanes take its window round-robin from the first point with lambdas >= lo_i, each adds in ascending j,
+ * and a butterfly (offsets W/2 ... 1) closes them; 8 lanes where no point of the group of 8 expects more than 32 points,
+ * 2 beta lambdas[i] (n - 1) / (lambdas[n-1] - lambdas[0]).  No floating-point atomics: two calls, and the replay of a captured graph,
+ * give the same bits.
+ * sdx_rotate_dev: device pointers, asynchronous on the context's stream, no allocation, capturable.  rot_dev: two doubles in device
+ * memory, {V, eps}, read when the kernel runs — a captured graph follows new values.  SDX_ERR_ARG before anything is enqueued: n < 2,
+ * a null required pointer, reference without out_reference or the reverse, an output that is one of the inputs.  The arrays'
+ * contents cannot be checked here: whatever they hold (NaN, unordered values, any V and eps), every access stays inside the arrays and
+ * every loop is bounded by its bracket within [0, n) — the result is then meaningless, never an out-of-range access.
+ * Stage name for sdx_profile_get: "k_rotate". */
+int sdx_rotate_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, const double* rot_dev,
+                   double* out, double* out_reference);
+/* The transpose: for weights u (and u_reference) over the BROADENED points,
+ *     a_i = u[i] / den_i,     w[j] = sum over the i with INCLUDED(i, j) of  w_ij a_i       (w_reference: the same with u_reference),
+ * w_ij bit for bit the forward's, so that  sum_i u[i] out[i] = sum_j w[j] flux[j].  With nus, both outputs become (w nus[j]) /
+ * lambdas[j], as sdx_observe_adjoint_dev ends.  The candidates i of a point j have lambdas[i] in [lambdas[j] / (1 + beta), lambdas[j] /
+ * (1 - beta)]; that range is searched a few 1e-15 wide and every candidate is tested with INCLUDED.  Ascending i round-robin over the
+ * point's lanes, then the butterfly; no floating-point atomics.  Its scratch (a: two rows of n) is the context's and grows outside a
+ * capture only.  !(V > 0): w = u.  Refusals and bounds as above.  Stage name: "k_rotate_adjoint" (two launches: a, the gather). */
+int sdx_rotate_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* rot_dev, const double* u, const double* u_reference,
+                           const double* nus, double* w, double* w_reference);
+/* host-buffer twins: host pointers, V and eps by value.  Checked before any copy: lambdas finite and strictly ascending, v_rot finite
+ * with 0 <= v_rot < 3000, 0 <= limb_darkening <= 1; anything else is SDX_ERR_ARG with a message that names the argument. */
+int sdx_rotate_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, double v_rot,
+                   double limb_darkening, double* out, double* out_reference);
+int sdx_rotate_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, double v_rot, double limb_darkening, const double* u,
+                           const double* u_reference, const double* nus, double* w, double* w_reference);
+
 /* Everything in one call for resident data: pre-pass + line opacity + total (above) + raytrace (F_nu
  * overwritten).  F_nu is [n_depth][ld].  alpha_line_out and total_alphas ([n_depth][ld]) are OPTIONAL outputs (NULL: the
  * plane is never written to HBM — the reference only reads them back through opacities_dict / Opacities.total_alphas;

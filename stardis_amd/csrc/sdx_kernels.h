@@ -4920,6 +4920,179 @@ __global__ __launch_bounds__(kBlock) void k_observe_adjoint(int64_t n, const dou
 }
 
 // ------------------------------------------------------------------------------------------------
+// Rotational broadening (include/stardis_hip.h, sdx_rotate_dev): Gray's profile for v sin i = V and linear limb darkening eps, in
+// velocity space on any ascending grid, applied on the rest-frame grid in front of k_observe.  With beta = V / c, for point i
+//     reach_i = lam_i beta,  lo_i = lam_i - reach_i,  hi_i = lam_i + reach_i,  y_ij = (lam_j - lam_i) / reach_i,  q_ij = 1 - y_ij^2,
+//     j is included iff (lo_i <= lam_j <= hi_i and q_ij > 0) or j = i (q = 1),
+//     K_ij = 2 (1 - eps) sqrt(q_ij) + (pi / 2) eps q_ij,   h_j = the trapezoid weight of lam_j (k_observe's, D = 1),   w_ij = K_ij h_j,
+//     out_i = (sum_j w_ij flux_j) / (sum_j w_ij)   over the included j: a window that reaches past an end of the grid sums what exists.
+// !(V > 0) copies.  rot_weight is the ONE place where reach, y, q, K and w are rounded and a pair is included or not: the forward
+// kernel, the adjoint's denominators and the adjoint's gather call it, so all three hold the same weights bit for bit.
+//
+// k_observe's mapping: points in groups of kObsGroup, eight lanes per point where no point of the group expects more than kObsShort
+// points in its window at the grid's MEAN spacing (2 beta lam_i (n - 1) / (lam_{n-1} - lam_0)), a wave per point otherwise; either
+// serves any point.  The lanes search the window together (obs_windows, D = 1), take it round-robin, add in ascending j, and a
+// butterfly closes the sums.
+//
+// The adjoint, for weights u over the broadened points: a_i = u_i / den_i (k_rotate_adjoint_den, rot_point_sums as the forward runs it),
+// then w_j = sum over the i that include j of w_ij a_i (k_rotate_adjoint).  The i that can include j have lam_i within
+// [lam_j / (1 + beta), lam_j / (1 - beta)]; that range is searched a few 1e-15 wide (beta >= 1: no upper bound) and every candidate is
+// tested by rot_weight.  No floating-point atomics; the order of every sum follows from the arrays alone.
+//
+// Whatever the arrays hold (NaN, unordered values, any V and eps): a search reads only inside its bracket within [0, n) and shrinks it
+// at least W + 1 times per round, a window is [i0, i1) with 0 <= i0 <= i1 <= n, a lane makes at most (i1 - i0) / W + 1 trips and reads
+// lam, flux, ref or a at j - 1, j, j + 1 clamped to [0, n) alone.
+constexpr double kCKms = 299792.458;
+constexpr double kHalfPi = 1.5707963267948966;
+
+struct RotProfile {
+    double beta, c_sqrt, c_q;  // V / c, 2 (1 - eps), (pi / 2) eps
+    bool on;                   // V > 0
+};
+__device__ __forceinline__ RotProfile rot_profile(const double* __restrict__ rot)
+{
+    const double V = rot[0], eps = rot[1];
+    return RotProfile{V / kCKms, mul_rn(2.0, sub_rn(1.0, eps)), mul_rn(kHalfPi, eps), V > 0.0};
+}
+// point i's weight for point j (self: j == i), h = the trapezoid weight of j; false: i does not include j
+__device__ __forceinline__ bool rot_weight(const RotProfile& r, double lam_i, double lam_j, bool self, double h, double& w)
+{
+    double q = 1.0;
+    if (!self) {
+        const double reach = mul_rn(lam_i, r.beta), lo = sub_rn(lam_i, reach), hi = add_rn(lam_i, reach);
+        const double y = sub_rn(lam_j, lam_i) / reach;
+        q = sub_rn(1.0, mul_rn(y, y));
+        if (!(lo <= lam_j && lam_j <= hi && q > 0.0)) return false;
+    }
+    w = mul_rn(add_rn(mul_rn(r.c_sqrt, __dsqrt_rn(q)), mul_rn(r.c_q, q)), h);
+    return true;
+}
+__device__ __forceinline__ double rot_trapezoid(const double* __restrict__ lam, int64_t n, int64_t j)
+{
+    return mul_rn(sub_rn(lam[j < n - 1 ? j + 1 : n - 1], lam[j > 0 ? j - 1 : 0]), 0.5);
+}
+
+// The mapping of the three kernels: the lane's point, its index among the point's W lanes.  false: the wave has no point and leaves.
+struct RotLane {
+    int64_t pi;  // the lane's point (may lie behind n in the last group: nothing is searched, nothing may be written)
+    int W, t, lane;
+    bool on;  // pi < n
+};
+__device__ __forceinline__ bool rot_mapping(int64_t n, const double* __restrict__ lam, const RotProfile& r, RotLane& m)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    const int64_t first = wave - wave % kObsGroup;  // the group's first point
+    if (first >= n) return false;
+    int64_t pi = first + (lane >> 3);
+    double expected = 0.0;
+    if (r.on && pi < n) expected = 2.0 * r.beta * lam[pi] * (double)(n - 1) / (lam[n - 1] - lam[0]);  // points in the window at the mean spacing
+    int W = 8;
+    if (__all(!(expected > (double)kObsShort))) {
+        if (wave != first) return false;
+    } else {
+        if (wave >= n) return false;
+        pi = wave, W = 64;
+    }
+    m = RotLane{pi, W, W == 64 ? lane : lane & 7, lane, pi < n};
+    return true;
+}
+
+// What the point's lanes sum: num = sum_j w_ij flux[j], numr = sum_j w_ij ref[j] (nullptr: not formed), den = sum_j w_ij, closed by the
+// butterfly, in every lane of the point.  Not called where !(V > 0).
+__device__ __forceinline__ void rot_point_sums(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                               const double* __restrict__ ref, const RotProfile& r, const RotLane& m, double& num, double& numr,
+                                               double& den)
+{
+    const int64_t i = m.on ? m.pi : n - 1;
+    const double li = lam[i];
+    const double reach = mul_rn(li, r.beta);
+    int64_t i0, i1;
+    obs_windows(lam, lam, n, 1.0, sub_rn(li, reach), add_rn(li, reach), m.on, m.W, m.lane, i0, i1);
+    num = 0.0, numr = 0.0, den = 0.0;
+    for (int64_t j = i0 + m.t; j < i1; j += m.W) {
+        double w;
+        if (!rot_weight(r, li, lam[j], j == i, rot_trapezoid(lam, n, j), w)) continue;
+        if (flux) num = add_rn(num, mul_rn(w, flux[j]));
+        if (ref) numr = add_rn(numr, mul_rn(w, ref[j]));
+        den = add_rn(den, w);
+    }
+    for (int off = m.W >> 1; off > 0; off >>= 1)
+        num = add_rn(num, __shfl_xor(num, off)), numr = add_rn(numr, __shfl_xor(numr, off)), den = add_rn(den, __shfl_xor(den, off));
+}
+
+__global__ __launch_bounds__(kBlock) void k_rotate(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                                   const double* __restrict__ ref, const double* __restrict__ rot, double* __restrict__ out,
+                                                   double* __restrict__ out_ref)
+{
+    const RotProfile r = rot_profile(rot);
+    RotLane m;
+    if (!rot_mapping(n, lam, r, m)) return;
+    if (!r.on) {  // (the group's first wave, eight lanes per point: a copy)
+        if (m.t == 0 && m.on) {
+            out[m.pi] = flux[m.pi];
+            if (ref) out_ref[m.pi] = ref[m.pi];
+        }
+        return;
+    }
+    double num, numr, den;
+    rot_point_sums(n, lam, flux, ref, r, m, num, numr, den);
+    if (m.t != 0 || !m.on) return;
+    out[m.pi] = num / den;
+    if (ref) out_ref[m.pi] = numr / den;
+}
+
+// a[i] = u[i] / den_i, a_ref[i] = u_ref[i] / den_i (u_ref = nullptr: none); !(V > 0): den = 1
+__global__ __launch_bounds__(kBlock) void k_rotate_adjoint_den(int64_t n, const double* __restrict__ lam, const double* __restrict__ rot,
+                                                               const double* __restrict__ u, const double* __restrict__ u_ref,
+                                                               double* __restrict__ a, double* __restrict__ a_ref)
+{
+    const RotProfile r = rot_profile(rot);
+    RotLane m;
+    if (!rot_mapping(n, lam, r, m)) return;
+    double num, numr, den = 1.0;
+    if (r.on) rot_point_sums(n, lam, nullptr, nullptr, r, m, num, numr, den);
+    if (m.t != 0 || !m.on) return;
+    a[m.pi] = r.on ? u[m.pi] / den : u[m.pi];
+    if (u_ref) a_ref[m.pi] = r.on ? u_ref[m.pi] / den : u_ref[m.pi];
+}
+
+__global__ __launch_bounds__(kBlock) void k_rotate_adjoint(int64_t n, const double* __restrict__ lam, const double* __restrict__ rot,
+                                                           const double* __restrict__ a, const double* __restrict__ a_ref,
+                                                           const double* __restrict__ nus, double* __restrict__ w_out,
+                                                           double* __restrict__ w_ref)
+{
+    const RotProfile r = rot_profile(rot);
+    RotLane m;
+    if (!rot_mapping(n, lam, r, m)) return;
+    const int64_t j = m.on ? m.pi : n - 1;
+    const double lj = lam[j];
+    double wf = 0.0, wr = 0.0;
+    if (r.on) {
+        // the candidates: lam_i in [lam_j / (1 + beta), lam_j / (1 - beta)], a few 1e-15 wide; rot_weight decides
+        const double lo = mul_rn(lj / add_rn(1.0, r.beta), 1.0 - 0x1p-48);
+        const double hi = r.beta < 1.0 ? mul_rn(lj / sub_rn(1.0, r.beta), 1.0 + 0x1p-48) : __longlong_as_double(0x7ff0000000000000LL);
+        int64_t iA, iB;
+        obs_windows(lam, lam, n, 1.0, lo, hi, m.on, m.W, m.lane, iA, iB);
+        const double h = rot_trapezoid(lam, n, j);
+        for (int64_t i = iA + m.t; i < iB; i += m.W) {
+            double w;
+            if (!rot_weight(r, lam[i], lj, i == j, h, w)) continue;
+            wf = add_rn(wf, mul_rn(w, a[i]));
+            if (a_ref) wr = add_rn(wr, mul_rn(w, a_ref[i]));
+        }
+        for (int off = m.W >> 1; off > 0; off >>= 1) wf = add_rn(wf, __shfl_xor(wf, off)), wr = add_rn(wr, __shfl_xor(wr, off));
+    } else {
+        wf = a[j];
+        if (a_ref) wr = a_ref[j];
+    }
+    if (m.t != 0 || !m.on) return;
+    // (the transpose of k_flux_nu_to_lambda, as k_observe_adjoint ends)
+    w_out[j] = nus ? mul_rn(wf, nus[j]) / lj : wf;
+    if (w_ref) w_ref[j] = nus ? mul_rn(wr, nus[j]) / lj : wr;
+}
+
+// ------------------------------------------------------------------------------------------------
 // The weight plane of the per-line sensitivities from the response functions: W[k][j] = w[j] R_alpha[k][j] / total[k][j] (w = nullptr: 1),
 // every operation one correctly rounded fp64 operation; a zero in total gives what IEEE gives.
 __global__ __launch_bounds__(kBlock) void k_response_weight(int n_depth, int64_t n_nu, const double* __restrict__ R, int64_t rld,

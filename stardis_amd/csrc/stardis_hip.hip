@@ -89,6 +89,8 @@ struct sdx_ctx {
     size_t adj_ws_bytes = 0;
     void* obs_ws = nullptr;  // the instrument adjoint's per-pixel factors a, b and scans PH, SL (sdx_observe_adjoint_dev)
     size_t obs_ws_bytes = 0;
+    void* rot_ws = nullptr;  // the rotation adjoint's factors a = u / den, two rows of n (sdx_rotate_adjoint_dev)
+    size_t rot_ws_bytes = 0;
     void* far_ws = nullptr;  // far_range of the line kernels' far field: two ints per global tile
     size_t far_ws_bytes = 0;
     // cnt_ge[N_nu + 2] (lines per centre index, for the narrow-window kernel) and the per-line integer lists: CntLayout
@@ -458,6 +460,7 @@ void sdx_destroy(sdx_ctx* ctx)
     if (ctx->far_ws) hipFree(ctx->far_ws);
     if (ctx->adj_ws) hipFree(ctx->adj_ws);
     if (ctx->obs_ws) hipFree(ctx->obs_ws);
+    if (ctx->rot_ws) hipFree(ctx->rot_ws);
     if (ctx->cnt_ws) hipFree(ctx->cnt_ws);
     if (ctx->io_dev) hipFree(ctx->io_dev);
     if (ctx->io_pin) hipHostFree(ctx->io_pin);
@@ -2822,6 +2825,122 @@ int sdx_observe_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, cons
     HostIo io{ctx};
     if ((rc = io.stage(plan))) return rc;
     if ((rc = sdx_observe_adjoint_dev(ctx, n, d_l, d_f, d_r, n_pix, d_e, d_s, d_D, d_pw, d_nus, d_wf, d_wr))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+// ---- rotational broadening (k_rotate) and its adjoint (k_rotate_adjoint_den, k_rotate_adjoint) ---------------------------------------
+// one wave per grid point (the last group's waves included: a short group is done by its first wave alone)
+static unsigned rotate_blocks(int64_t n)
+{
+    const int64_t waves = (n + kObsGroup - 1) / kObsGroup * kObsGroup;
+    return (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
+}
+
+int sdx_rotate_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, const double* rot_dev,
+                   double* out, double* out_reference)
+{
+    REQUIRE(ctx, "rotate: null context");
+    REQUIRE(n >= 2, "rotate: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && flux && rot_dev && out, "rotate: null pointer (lambdas, flux, rot_dev and out are required)");
+    REQUIRE(!reference == !out_reference, "rotate: reference and out_reference go together");
+    REQUIRE(out != flux && out != reference && out_reference != flux && (!reference || out_reference != reference) && out != out_reference,
+            "rotate: not in place (out and out_reference must be buffers of their own)");
+    REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "rotate: too many points for one launch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    {
+        LaunchScope ls(ctx, "k_rotate");
+        hipLaunchKernelGGL(k_rotate, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, flux, reference, rot_dev, out, out_reference);
+    }
+    return check_launch("k_rotate");
+}
+
+int sdx_rotate_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* rot_dev, const double* u, const double* u_reference,
+                           const double* nus, double* w, double* w_reference)
+{
+    REQUIRE(ctx, "rotate_adjoint: null context");
+    REQUIRE(n >= 2, "rotate_adjoint: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && rot_dev && u && w, "rotate_adjoint: null pointer (lambdas, rot_dev, u and w are required)");
+    REQUIRE(!u_reference == !w_reference, "rotate_adjoint: u_reference and w_reference go together");
+    REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "rotate_adjoint: too many points for one launch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t row = ((size_t)n * sizeof(double) + 255) & ~(size_t)255;
+    int rc = ensure(ctx, &ctx->rot_ws, &ctx->rot_ws_bytes, 2 * row);
+    if (rc) return rc;
+    double* const a = (double*)ctx->rot_ws;
+    double* const a_ref = (double*)((char*)ctx->rot_ws + row);
+    {
+        LaunchScope ls(ctx, "k_rotate_adjoint");
+        hipLaunchKernelGGL(k_rotate_adjoint_den, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, rot_dev, u, u_reference, a, a_ref);
+        hipLaunchKernelGGL(k_rotate_adjoint, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, rot_dev, (const double*)a,
+                           u_reference ? (const double*)a_ref : nullptr, nus, w, w_reference);
+    }
+    return check_launch("k_rotate_adjoint");
+}
+
+// what the kernels cannot check: the host-buffer twins do, before any upload
+static int rotate_host_check(int64_t n, const double* lambdas, double v_rot, double limb_darkening)
+{
+    REQUIRE(std::isfinite(v_rot) && v_rot >= 0.0 && v_rot < 3000.0, "rotate: v_rot must be finite with 0 <= v_rot < 3000 km/s");
+    REQUIRE(limb_darkening >= 0.0 && limb_darkening <= 1.0, "rotate: limb_darkening must lie in [0, 1]");
+    for (int64_t i = 0; i < n; ++i)
+        REQUIRE(std::isfinite(lambdas[i]) && (i == 0 || lambdas[i - 1] < lambdas[i]), "rotate: lambdas must be finite and strictly ascending");
+    return SDX_OK;
+}
+
+int sdx_rotate_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, double v_rot,
+                   double limb_darkening, double* out, double* out_reference)
+{
+    REQUIRE(ctx, "rotate: null context");
+    REQUIRE(n >= 2, "rotate: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && flux && out, "rotate: null pointer (lambdas, flux and out are required)");
+    REQUIRE(!reference == !out_reference, "rotate: reference and out_reference go together");
+    int rc;
+    if ((rc = rotate_host_check(n, lambdas, v_rot, limb_darkening))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
+    const double pair[2] = {v_rot, limb_darkening};
+    const double *d_l, *d_f, *d_r, *d_rot;
+    double *d_o, *d_or;
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(flux, grid, &d_f);
+    plan.in(reference, grid, &d_r);
+    plan.in(pair, 2 * f8, &d_rot);
+    plan.out(out, grid, &d_o);
+    plan.out(out_reference, grid, &d_or);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_rotate_dev(ctx, n, d_l, d_f, d_r, d_rot, d_o, d_or))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+int sdx_rotate_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, double v_rot, double limb_darkening, const double* u,
+                           const double* u_reference, const double* nus, double* w, double* w_reference)
+{
+    REQUIRE(ctx, "rotate_adjoint: null context");
+    REQUIRE(n >= 2, "rotate_adjoint: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && u && w, "rotate_adjoint: null pointer (lambdas, u and w are required)");
+    REQUIRE(!u_reference == !w_reference, "rotate_adjoint: u_reference and w_reference go together");
+    int rc;
+    if ((rc = rotate_host_check(n, lambdas, v_rot, limb_darkening))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
+    const double pair[2] = {v_rot, limb_darkening};
+    const double *d_l, *d_rot, *d_u, *d_ur, *d_nus;
+    double *d_w, *d_wr;
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(pair, 2 * f8, &d_rot);
+    plan.in(u, grid, &d_u);
+    plan.in(u_reference, grid, &d_ur);
+    plan.in(nus, grid, &d_nus);
+    plan.out(w, grid, &d_w);
+    plan.out(w_reference, grid, &d_wr);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_rotate_adjoint_dev(ctx, n, d_l, d_rot, d_u, d_ur, d_nus, d_w, d_wr))) return rc;
     if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }

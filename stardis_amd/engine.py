@@ -152,7 +152,9 @@ class SpectralSynthesizer:
         self.d_Rs = c.empty((self.n_depth, self.count)) if self.keep_response else None
         self.instrument = instrument
         if instrument is not None:
-            self.d_lambdas = c.upload(K.nu_to_angstrom(nus))
+            self.lambdas = K.nu_to_angstrom(nus)
+            self.d_lambdas = c.upload(self.lambdas)
+            instrument.reserve(self.n_nu)  # (a rotating instrument's scratch: a capture of the step allocates nothing)
             self.d_Flam = c.empty((self.n_nu,))
             self.d_observed = c.empty((instrument.n_pix,))
             if self.keep_continuum_flux:
@@ -278,10 +280,20 @@ class SpectralSynthesizer:
         c, n, inst = self.ctx, self.n_nu, self.instrument
         last = 8 * (self.n_depth - 1) * self.count  # row N_d - 1
         c.call("sdx_flux_nu_to_lambda_dev", n, self.flux_ptr + last, self.d_nus.ptr, self.d_lambdas.ptr, self.d_Flam.ptr)
-        inst.observe(self.d_lambdas, self.d_Flam, n, out=self.d_observed)
-        if self.keep_continuum_flux:
-            c.call("sdx_flux_nu_to_lambda_dev", n, self.d_Fc.ptr + last, self.d_nus.ptr, self.d_lambdas.ptr, self.d_Fclam.ptr)
-            inst.observe(self.d_lambdas, self.d_Flam, n, reference=self.d_Fclam, out=self.d_observed_normalized)
+        if not inst.rotates:
+            inst.observe(self.d_lambdas, self.d_Flam, n, out=self.d_observed)
+            if self.keep_continuum_flux:
+                c.call("sdx_flux_nu_to_lambda_dev", n, self.d_Fc.ptr + last, self.d_nus.ptr, self.d_lambdas.ptr, self.d_Fclam.ptr)
+                inst.observe(self.d_lambdas, self.d_Flam, n, reference=self.d_Fclam, out=self.d_observed_normalized)
+            return
+        # a rotating instrument: F_lambda (and the continuum's) broadened ONCE per step, whatever is observed of them
+        if not self.keep_continuum_flux:
+            inst.observe(self.d_lambdas, inst.rotate(self.d_lambdas, self.d_Flam, n), n, out=self.d_observed, broadened=True)
+            return
+        c.call("sdx_flux_nu_to_lambda_dev", n, self.d_Fc.ptr + last, self.d_nus.ptr, self.d_lambdas.ptr, self.d_Fclam.ptr)
+        flux, cont = inst.rotate(self.d_lambdas, self.d_Flam, n, reference=self.d_Fclam)
+        inst.observe(self.d_lambdas, flux, n, out=self.d_observed, broadened=True)
+        inst.observe(self.d_lambdas, flux, n, reference=cont, out=self.d_observed_normalized, broadened=True)
 
     def _enqueue_contribution(self):
         cnt = self.count
@@ -688,8 +700,10 @@ class SpectralSynthesizer:
         observed_normalized) spectrum against data, and its gradient to ln gf of every line, (n_lines,) or (n_lines, N_d):
         observed_line_sensitivities with c_j = -2 ivar_j (data_j - observed_j).  A pixel whose observed value is NaN (the grid does not
         cover its window) or whose ivar is 0 is left out of both; leaving every pixel out is a ValueError.  data, inverse_variance:
-        host arrays, one value per pixel.  A diagnostic call, not part of the step: it waits for the stream and forms the n_pix
-        residuals on the host.  wrt: as for line_sensitivities (a tuple: the gradient is a dict)."""
+        host arrays, one value per pixel.  With a rotating instrument (Instrument(v_rot=...)) the pixels it reports as edge_affected —
+        those that may see a point whose rotation window is truncated at an end of the grid — are left out in the same way.  A
+        diagnostic call, not part of the step: it waits for the stream and forms the n_pix residuals on the host.  wrt: as for
+        line_sensitivities (a tuple: the gradient is a dict)."""
         self._wrt_names(wrt)
         self._require_instrument()
         self._require_response()
@@ -703,8 +717,10 @@ class SpectralSynthesizer:
                 raise ValueError(f"{name} must hold one value per pixel of the instrument ({n_pix}), got {v.size}")
         obs = (self.d_observed_normalized if normalized else self.d_observed).numpy()
         use = ~np.isnan(obs) & (ivar != 0)
+        if self.instrument.rotates:
+            use &= ~self.instrument.edge_affected(self.lambdas)
         if not np.any(use):
-            raise ValueError("no pixel left: every pixel is NaN (not covered by the grid) or has inverse_variance 0")
+            raise ValueError("no pixel left: every pixel is NaN (not covered by the grid), edge-affected or has inverse_variance 0")
         r = np.where(use, d, 0.0) - np.where(use, obs, 0.0)
         w = np.where(use, ivar, 0.0)
         chi2 = float(np.sum(w * r * r))

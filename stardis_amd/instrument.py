@@ -2,7 +2,11 @@
 integration over the detector's pixels — one launch of k_observe behind the synthesis (include/stardis_hip.h, sdx_observe_dev, states
 the operator).  The reference has no counterpart; its rotation-broadening walk-through applies scipy.ndimage.gaussian_filter1d at one
 sigma in grid points (postprocess.gaussian_filter1d mirrors that), which is a constant resolving power on a log-uniform grid only.
-Instrument.adjoint is the operator transposed (sdx_observe_adjoint_dev): weights over the pixels pulled back to weights over the grid."""
+Instrument.adjoint is the operator transposed (sdx_observe_adjoint_dev): weights over the pixels pulled back to weights over the grid.
+With v_rot the star's rotation (v sin i, Gray's profile with linear limb darkening; sdx_rotate_dev states the operator) is applied on
+the rest-frame grid in front of k_observe, in velocity space on any ascending grid, and its transpose behind the instrument's: one more
+launch forward, two more transposed.  postprocess.rotation_broadening, which mirrors the reference, is another thing: a kernel at
+integer pixel offsets, a rotation profile on a log-uniform grid only."""
 import math
 
 import numpy as np
@@ -48,6 +52,20 @@ def pixel_sigma(pixel_edges, resolving_power=None, sigma=None):
     return edges, v
 
 
+def rotation_pair(v_rot, limb_darkening=0.6):
+    """-> (V, eps) as floats, validated as sdx_rotate_f64 validates them: v sin i finite with 0 <= V < 3000 km/s, the linear
+    limb-darkening coefficient in [0, 1].  Needs no device."""
+    try:
+        V, eps = float(getattr(v_rot, "value", v_rot)), float(limb_darkening)
+    except (TypeError, ValueError):
+        raise ValueError("v_rot and limb_darkening must be numbers") from None
+    if not (math.isfinite(V) and 0.0 <= V < 3000.0):
+        raise ValueError("v_rot must be finite with 0 <= v_rot < 3000 km/s")
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError("limb_darkening must lie in [0, 1]")
+    return V, eps
+
+
 def _host_vector(name, a, n, what):
     v = np.ascontiguousarray(getattr(a, "value", a), dtype=np.float64).reshape(-1)
     if v.size != n:
@@ -74,10 +92,16 @@ def adjoint_host_arguments(n_pix, lambdas, pixel_weights, flux=None, reference=N
 class Instrument:
     """A spectrograph: pixel edges (Angstrom, ascending), the line-spread function as a resolving power or a Gaussian sigma (Angstrom),
     and the star's radial velocity.  Edges, sigma, the Doppler factor and the output stay on the device; observe() is one launch, and a
-    graph that recorded it follows set_radial_velocity() without being recorded again (the kernel reads the factor from device memory)."""
+    graph that recorded it follows set_radial_velocity() without being recorded again (the kernel reads the factor from device memory).
+    v_rot (km/s; None: no rotation, and nothing below exists or runs) and limb_darkening: the star's v sin i and linear limb-darkening
+    coefficient.  The pair lives on the device like the Doppler factor (set_rotation); observe() then broadens flux and reference
+    into scratch of the instrument's (k_rotate, sized at first use or by reserve(n)) and observes that.  A rotation window that reaches
+    past an end of the grid is truncated and renormalised: edge_affected() names the pixels that see such points."""
 
-    def __init__(self, pixel_edges, resolving_power=None, sigma=None, ctx=None):
+    def __init__(self, pixel_edges, resolving_power=None, sigma=None, ctx=None, v_rot=None, limb_darkening=0.6):
         self.edges, self.sigma = pixel_sigma(pixel_edges, resolving_power, sigma)  # (ValueError before any device work)
+        self.rotates = v_rot is not None
+        pair = rotation_pair(v_rot, limb_darkening) if self.rotates else None
         self.n_pix = self.edges.size - 1
         self.ctx = ctx or default_context()
         self.d_edges = self.ctx.upload(self.edges)
@@ -85,6 +109,62 @@ class Instrument:
         self.d_doppler = self.ctx.empty((1,))
         self.d_out = self.ctx.empty((self.n_pix,))
         self.set_radial_velocity(0.0)
+        self.v_rot, self.limb_darkening = None, float(limb_darkening)
+        self._scratch_n, self._scratch = 0, None
+        if self.rotates:
+            self.d_rot = self.ctx.empty((2,))
+            self.set_rotation(*pair)
+
+    def set_rotation(self, v_rot, limb_darkening=None):
+        """Write (v sin i, limb darkening) into the device pair, in order on the context's stream; limb_darkening=None keeps the
+        present coefficient.  Only for an instrument constructed with v_rot (0 allowed)."""
+        if not self.rotates:
+            raise RuntimeError("no rotation: construct the Instrument with v_rot= (0 allowed)")
+        V, eps = rotation_pair(v_rot, self.limb_darkening if limb_darkening is None else limb_darkening)
+        self.d_rot.set(np.array([V, eps]))
+        self.v_rot, self.limb_darkening = V, eps
+
+    def reserve(self, n):
+        """Size the rotation's scratch for grids of up to n points now (broadened flux and reference, and the adjoint's two
+        intermediate weight vectors), so that a later observe() or adjoint() — inside a graph capture, say — allocates nothing.
+        Without rotation there is no scratch and this does nothing."""
+        n = int(n)
+        if self.rotates and n > self._scratch_n:
+            self._scratch = tuple(self.ctx.empty((n,)) for _ in range(4))
+            self._scratch_n = n
+
+    def rotate(self, d_lambdas, d_flux, n, reference=None, out=None, out_reference=None):
+        """The rotation stage alone (sdx_rotate_dev): n points of (rest-frame wavelength, flux[, reference]) on the device -> the
+        broadened flux, or (flux, reference) with a reference; into the instrument's scratch unless `out` (and out_reference) are given."""
+        if not self.rotates:
+            raise RuntimeError("no rotation: construct the Instrument with v_rot= (0 allowed)")
+        addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
+        self.reserve(n)
+        out = self._scratch[0] if out is None else out
+        if reference is None:
+            out_reference = None
+        elif out_reference is None:
+            out_reference = self._scratch[1]
+        self.ctx.call("sdx_rotate_dev", int(n), addr(d_lambdas), addr(d_flux), addr(reference), self.d_rot.ptr, addr(out), addr(out_reference))
+        return out if reference is None else (out, out_reference)
+
+    def rotate_host(self, lambdas, flux, reference=None):
+        """numpy in, numpy out (sdx_rotate_f64, which checks the arrays): -> the broadened flux, or (flux, reference)."""
+        if not self.rotates:
+            raise RuntimeError("no rotation: construct the Instrument with v_rot= (0 allowed)")
+        return rotate_host(self.ctx, lambdas, flux, self.v_rot, self.limb_darkening, reference)
+
+    def edge_affected(self, lambdas):
+        """-> boolean host array (n_pix,): the pixels whose window [edges[j] - 8 sigma[j], edges[j+1] + 8 sigma[j]], taken back to the
+        rest frame, comes within the rotation's reach of an end of the grid `lambdas` — lo (1 - beta) < lambdas[0] or hi (1 + beta) >
+        lambdas[-1] — so that a rotation window of a point they may see is truncated there.  Without rotation (beta = 0) these are
+        the pixels the grid does not cover.  Plain numpy."""
+        lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
+        _ascending("lambdas", lam)
+        beta = (self.v_rot or 0.0) / K.C_KMS
+        lo = (self.edges[:-1] - 8.0 * self.sigma) / self.doppler
+        hi = (self.edges[1:] + 8.0 * self.sigma) / self.doppler
+        return (lo * (1.0 - beta) < lam[0]) | (hi * (1.0 + beta) > lam[-1])
 
     def set_radial_velocity(self, v_kms):
         """Write the Doppler factor of v_kms into the device scalar, in order on the context's stream."""
@@ -92,11 +172,16 @@ class Instrument:
         self.d_doppler.set(np.array([D]))
         self.v_kms, self.doppler = float(v_kms), D
 
-    def observe(self, d_lambdas, d_flux, n, reference=None, out=None):
+    def observe(self, d_lambdas, d_flux, n, reference=None, out=None, broadened=False):
         """n points of (wavelength, flux[, reference]) already on the device (DeviceArrays, CUDA tensors or raw addresses) -> the
-        DeviceArray (n_pix,) of the instrument (or `out`), enqueued on the context's stream: nothing is allocated, nothing waits."""
+        DeviceArray (n_pix,) of the instrument (or `out`), enqueued on the context's stream: nothing is allocated, nothing waits.
+        With rotation, flux and reference are broadened first (rotate(), into the scratch: sized here at first use, or by
+        reserve(n)); broadened=True says they are already — what rotate() returned — so that several outputs share one k_rotate."""
         addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
         out = self.d_out if out is None else out
+        if self.rotates and not broadened:
+            res = self.rotate(d_lambdas, d_flux, n, reference)
+            d_flux, reference = res if reference is not None else (res, None)
         self.ctx.call("sdx_observe_dev", int(n), addr(d_lambdas), addr(d_flux), addr(reference), self.n_pix, self.d_edges.ptr,
                       self.d_sigma.ptr, self.d_doppler.ptr, out.ptr)
         return out
@@ -113,9 +198,12 @@ class Instrument:
             g = np.ascontiguousarray(getattr(reference, "value", reference), dtype=np.float64).reshape(-1)
             if g.size != lam.size:
                 raise ValueError("reference must hold one value per grid point")
+        if self.rotates:  # (the host-buffer twin, then the pixels as without rotation)
+            f, g = self.rotate_host(lam, f, g) if reference is not None else (self.rotate_host(lam, f), None)
+        if reference is not None:
             d_ref = self.ctx.upload(g)
         d_lam, d_f = self.ctx.upload(lam), self.ctx.upload(f)
-        return self.observe(d_lam, d_f, lam.size, d_ref).numpy()
+        return self.observe(d_lam, d_f, lam.size, d_ref, broadened=True).numpy()
 
     def adjoint(self, d_lambdas, n, pixel_weights, flux=None, reference=None, nus=None, out=None, out_reference=None):
         """The transpose of observe() (sdx_observe_adjoint_dev): pixel_weights c (n_pix,) on the device -> the DeviceArray (n,) of
@@ -124,7 +212,10 @@ class Instrument:
         normalised spectrum to the flux, and out_reference — given, or asked for with out_reference=True — receives the weights to
         the reference; then -> (w, w_reference).  nus: the grid's frequencies; the weights then apply to F_nu instead of F_lambda
         (the transpose of sdx_flux_nu_to_lambda_dev).  Device buffers in (DeviceArrays, CUDA tensors or raw addresses), enqueued on
-        the context's stream: nothing waits, and nothing is allocated when `out` (and out_reference) are given."""
+        the context's stream: nothing waits, and nothing is allocated when `out` (and out_reference) are given.
+        With rotation the chain is transposed stage by stage: flux and reference are broadened here (the normalised pixel value
+        enters), sdx_observe_adjoint_dev gives the weights over the BROADENED points, and sdx_rotate_adjoint_dev takes those back to
+        the grid and applies nus — three stages where there was one, the scratch the instrument's (reserve(n))."""
         addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
         if reference is None and out_reference is not None and out_reference is not False:
             raise ValueError("out_reference needs a reference")
@@ -135,6 +226,16 @@ class Instrument:
             out_reference = self.ctx.empty((int(n),))
         elif out_reference is False:
             out_reference = None
+        if self.rotates:
+            self.reserve(n)
+            if reference is not None:
+                flux, reference = self.rotate(d_lambdas, flux, n, reference)
+            u, u_ref = self._scratch[2], self._scratch[3] if out_reference is not None else None
+            self.ctx.call("sdx_observe_adjoint_dev", int(n), addr(d_lambdas), addr(flux) if reference is not None else None, addr(reference),
+                          self.n_pix, self.d_edges.ptr, self.d_sigma.ptr, self.d_doppler.ptr, addr(pixel_weights), None, u.ptr, addr(u_ref))
+            self.ctx.call("sdx_rotate_adjoint_dev", int(n), addr(d_lambdas), self.d_rot.ptr, u.ptr, addr(u_ref), addr(nus), addr(out),
+                          addr(out_reference))
+            return out if out_reference is None else (out, out_reference)
         self.ctx.call("sdx_observe_adjoint_dev", int(n), addr(d_lambdas), addr(flux) if reference is not None else None, addr(reference),
                       self.n_pix, self.d_edges.ptr, self.d_sigma.ptr, self.d_doppler.ptr, addr(pixel_weights), addr(nus), addr(out),
                       addr(out_reference))
@@ -148,6 +249,32 @@ class Instrument:
         host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
         w = np.empty(lam.size)
         w_ref = np.empty(lam.size) if g is not None else None
+        if self.rotates:  # (the three stages of adjoint(), each through its host-buffer twin)
+            if g is not None:
+                f, g = self.rotate_host(lam, f, g)
+            u, u_ref = np.empty(lam.size), np.empty(lam.size) if g is not None else None
+            self.ctx.call("sdx_observe_adjoint_f64", lam.size, host(lam), host(f), host(g), self.n_pix, host(self.edges), host(self.sigma),
+                          float(self.doppler), host(c), None, host(u), host(u_ref))
+            self.ctx.call("sdx_rotate_adjoint_f64", lam.size, host(lam), self.v_rot, self.limb_darkening, host(u), host(u_ref), host(nu), host(w),
+                          host(w_ref))
+            return w if w_ref is None else (w, w_ref)
         self.ctx.call("sdx_observe_adjoint_f64", lam.size, host(lam), host(f), host(g), self.n_pix, host(self.edges), host(self.sigma),
                       float(self.doppler), host(c), host(nu), host(w), host(w_ref))
         return w if w_ref is None else (w, w_ref)
+
+
+def rotate_host(ctx, lambdas, flux, v_rot, limb_darkening=0.6, reference=None):
+    """Rotational broadening of host arrays (sdx_rotate_f64) -> the broadened flux, or (flux, reference) with a reference.  The
+    arguments are checked before any device work (ValueError naming the argument)."""
+    V, eps = rotation_pair(v_rot, limb_darkening)
+    lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
+    _ascending("lambdas", lam)
+    if lam.size < 2:
+        raise ValueError("lambdas must hold at least two points")
+    f = _host_vector("flux", flux, lam.size, "grid point")
+    g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
+    out = np.empty(lam.size)
+    out_ref = None if g is None else np.empty(lam.size)
+    host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    (ctx or default_context()).call("sdx_rotate_f64", lam.size, host(lam), host(f), host(g), V, eps, host(out), host(out_ref))
+    return out if g is None else (out, out_ref)
