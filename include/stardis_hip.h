@@ -670,6 +670,59 @@ int sdx_rotate_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double*
 int sdx_rotate_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, double v_rot, double limb_darkening, const double* u,
                            const double* u_reference, const double* nus, double* w, double* w_reference);
 
+/* ---- radial-tangential macroturbulence in velocity space, its adjoint and its derivative to zeta ----
+ * Gray's radial-tangential profile with equal areas and zeta_R = zeta_T = zeta, integrated over the disk without limb darkening, has
+ * the closed form  M(u) ~ K(u) = exp(-u^2) - sqrt(pi) u erfc(u),  u = |dv| / zeta:  K(0) = 1, K > 0, K ~ exp(-u^2) / (2 u^2) for large u,
+ * integral of K du = sqrt(pi) / 4 per side, and dK/du = -sqrt(pi) erfc(u), so that  dK / d ln zeta = s(u) = sqrt(pi) u erfc(u), the term K
+ * is made of.  K(6) = 3.1e-18 and the mass beyond u = 6 is 5.6e-19 of the total: the window is |u| <= 6.
+ * ORDER IN THE CHAIN: rotation (sdx_rotate_dev), then macroturbulence, then sdx_observe_dev; the adjoint runs the stages in reverse.
+ * Both broadenings are convolutions in velocity and commute on a log-uniform grid; on other grids, and at the ends, this order is the
+ * definition.  Applied on the rest-frame grid, like the rotation.
+ *   lambdas[n]  strictly ascending rest-frame wavelengths (Angstrom), flux[n], reference[n] optional (NULL: none);
+ *   zeta >= 0 in km/s; beta = zeta / c, c = 299792.458 km/s.
+ * For point i, every operation one rounded fp64 operation (exp and erfc: the device library's), in this order (the device function
+ * mac_weight):
+ *     reach_i = lambdas[i] (6 beta),   lo_i = lambdas[i] - reach_i,   hi_i = lambdas[i] + reach_i,
+ *     INCLUDED(i, j) = (lo_i <= lambdas[j] && lambdas[j] <= hi_i) || j == i,
+ *     u_ij = |lambdas[j] - lambdas[i]| / (lambdas[i] beta),
+ *     j == i: K = 1, s = 0;   else e = exp(-(u u)),   s = (sqrt(pi) u) erfc(u),   K = max(e - s, 0),
+ *     h_j = (lambdas[j+1] - lambdas[j-1]) / 2, the ends clamped as in sdx_observe_dev,      w_ij = K h_j,   v_ij = s h_j,
+ *     den_i = sum_j w_ij,   out[i] = (sum_j w_ij flux[j]) / den_i,   out_reference[i] = (sum_j w_ij reference[j]) / den_i,
+ *     dout[i] = (sum_j v_ij flux[j] - out[i] sum_j v_ij) / den_i,   dout_reference[i] likewise with reference and out_reference
+ * over the included j.  dout = d out / d ln zeta AT FIXED WINDOWS (a point entering a window brings 3e-18 of the peak); d out / d zeta
+ * = dout / zeta.  den_i > 0 always (i includes itself).  A window that reaches past an end of the grid is TRUNCATED AND RENORMALISED, as
+ * the rotation's is: it sums what exists (Instrument.edge_affected reports the pixels concerned).  !(zeta > 0) — zero, negative, NaN —
+ * is a copy: out[i] = flux[i] bit for bit, dout[i] = 0.
+ * The sums: as sdx_rotate_dev's — a point's 8 or 64 lanes take its window round-robin from the first point with lambdas >= lo_i, each
+ * adds in ascending j, and a butterfly (offsets W/2 ... 1) closes them; 8 lanes where no point of the group of 8 expects more than 32
+ * points, 2 (6 beta) lambdas[i] (n - 1) / (lambdas[n-1] - lambdas[0]).  No floating-point atomics: two calls, the replay of a captured
+ * graph and the host-buffer twin give the same bits.
+ * sdx_macroturbulence_dev: device pointers, asynchronous on the context's stream, no allocation, capturable.  mac_dev: one double in
+ * device memory, zeta, read when the kernel runs — a captured graph follows a new value.  dout and dout_reference are optional (NULL:
+ * not formed).  SDX_ERR_ARG before anything is enqueued: n < 2, a null required pointer (out is required: no dout without out),
+ * reference without out_reference or the reverse, dout_reference without reference, an output that is one of the inputs or another
+ * output.  The arrays' contents cannot be checked here: whatever they hold (NaN, unordered values, any zeta), every access stays inside
+ * the arrays and every loop is bounded by its bracket within [0, n) — the result is then meaningless, never an out-of-range access.
+ * Stage name for sdx_profile_get: "k_macroturbulence". */
+int sdx_macroturbulence_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, const double* mac_dev,
+                            double* out, double* out_reference, double* dout, double* dout_reference);
+/* The transpose: for weights u (and u_reference) over the BROADENED points,
+ *     a_i = u[i] / den_i,     w[j] = sum over the i with INCLUDED(i, j) of  w_ij a_i       (w_reference: the same with u_reference),
+ * w_ij bit for bit the forward's, so that  sum_i u[i] out[i] = sum_j w[j] flux[j].  With nus, both outputs become (w nus[j]) /
+ * lambdas[j], as sdx_observe_adjoint_dev ends.  The candidates i of a point j have lambdas[i] in [lambdas[j] / (1 + 6 beta), lambdas[j] /
+ * (1 - 6 beta)]; that range is searched a few 1e-15 wide and every candidate is tested with INCLUDED.  Ascending i round-robin over
+ * the point's lanes, then the butterfly; no floating-point atomics.  Its scratch (a: two rows of n) is the context's and grows outside
+ * a capture only.  !(zeta > 0): w = u.  Refusals (w and w_reference must be buffers of their own) and bounds as above.  Stage name:
+ * "k_macroturbulence_adjoint" (two launches: a, the gather). */
+int sdx_macroturbulence_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* mac_dev, const double* u,
+                                    const double* u_reference, const double* nus, double* w, double* w_reference);
+/* host-buffer twins: host pointers, zeta by value.  Checked before any copy: lambdas finite and strictly ascending, zeta finite with
+ * 0 <= zeta < 500; anything else is SDX_ERR_ARG with a message that names the argument. */
+int sdx_macroturbulence_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, double zeta,
+                            double* out, double* out_reference, double* dout, double* dout_reference);
+int sdx_macroturbulence_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, double zeta, const double* u, const double* u_reference,
+                                    const double* nus, double* w, double* w_reference);
+
 /* Everything in one call for resident data: pre-pass + line opacity + total (above) + raytrace (F_nu
  * overwritten).  F_nu is [n_depth][ld].  alpha_line_out and total_alphas ([n_depth][ld]) are OPTIONAL outputs (NULL: the
  * plane is never written to HBM — the reference only reads them back through opacities_dict / Opacities.total_alphas;

@@ -22,7 +22,7 @@ def run_stardis(config_fname, tracing_lambdas_or_nus, add_config_dict=None, *, c
     instrument (a stardis_amd.instrument.Instrument): the output gains spectrum_observed (n_pix,), spectrum_lambda through the instrument
     (radial velocity, line-spread function, pixels; Instrument.observe_host); with continuum=True also spectrum_observed_normalized, the
     same with spectrum_lambda_continuum as reference.  Works unchanged with a rotating instrument (Instrument(v_rot=...)): the star's
-    rotation is applied in front of the pixels."""
+    rotation is applied in front of the pixels; Instrument(v_mac=...) adds the radial-tangential macroturbulence behind it."""
     try:
         from astropy import units as u
         from stardis.base import STARDISOutput, set_num_threads

@@ -4978,7 +4978,8 @@ struct RotLane {
     int W, t, lane;
     bool on;  // pi < n
 };
-__device__ __forceinline__ bool rot_mapping(int64_t n, const double* __restrict__ lam, const RotProfile& r, RotLane& m)
+// width: the window's whole width over lam_i (rotation: 2 beta; macroturbulence: 2 (6 beta)); on: the stage broadens at all
+__device__ __forceinline__ bool rot_mapping(int64_t n, const double* __restrict__ lam, double width, bool on, RotLane& m)
 {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
@@ -4986,7 +4987,7 @@ __device__ __forceinline__ bool rot_mapping(int64_t n, const double* __restrict_
     if (first >= n) return false;
     int64_t pi = first + (lane >> 3);
     double expected = 0.0;
-    if (r.on && pi < n) expected = 2.0 * r.beta * lam[pi] * (double)(n - 1) / (lam[n - 1] - lam[0]);  // points in the window at the mean spacing
+    if (on && pi < n) expected = width * lam[pi] * (double)(n - 1) / (lam[n - 1] - lam[0]);  // points in the window at the mean spacing
     int W = 8;
     if (__all(!(expected > (double)kObsShort))) {
         if (wave != first) return false;
@@ -4996,6 +4997,14 @@ __device__ __forceinline__ bool rot_mapping(int64_t n, const double* __restrict_
     }
     m = RotLane{pi, W, W == 64 ? lane : lane & 7, lane, pi < n};
     return true;
+}
+
+// The range of lam_i whose window of relative reach b can hold lam_j: [lam_j / (1 + b), lam_j / (1 - b)], a few 1e-15 wide (b >= 1: no
+// upper bound).  What the adjoints' gathers search; the stage's weight function then tests every candidate.
+__device__ __forceinline__ void rot_candidates(double lj, double b, double& lo, double& hi)
+{
+    lo = mul_rn(lj / add_rn(1.0, b), 1.0 - 0x1p-48);
+    hi = b < 1.0 ? mul_rn(lj / sub_rn(1.0, b), 1.0 + 0x1p-48) : __longlong_as_double(0x7ff0000000000000LL);
 }
 
 // What the point's lanes sum: num = sum_j w_ij flux[j], numr = sum_j w_ij ref[j] (nullptr: not formed), den = sum_j w_ij, closed by the
@@ -5027,7 +5036,7 @@ __global__ __launch_bounds__(kBlock) void k_rotate(int64_t n, const double* __re
 {
     const RotProfile r = rot_profile(rot);
     RotLane m;
-    if (!rot_mapping(n, lam, r, m)) return;
+    if (!rot_mapping(n, lam, 2.0 * r.beta, r.on, m)) return;
     if (!r.on) {  // (the group's first wave, eight lanes per point: a copy)
         if (m.t == 0 && m.on) {
             out[m.pi] = flux[m.pi];
@@ -5049,7 +5058,7 @@ __global__ __launch_bounds__(kBlock) void k_rotate_adjoint_den(int64_t n, const 
 {
     const RotProfile r = rot_profile(rot);
     RotLane m;
-    if (!rot_mapping(n, lam, r, m)) return;
+    if (!rot_mapping(n, lam, 2.0 * r.beta, r.on, m)) return;
     double num, numr, den = 1.0;
     if (r.on) rot_point_sums(n, lam, nullptr, nullptr, r, m, num, numr, den);
     if (m.t != 0 || !m.on) return;
@@ -5064,20 +5073,177 @@ __global__ __launch_bounds__(kBlock) void k_rotate_adjoint(int64_t n, const doub
 {
     const RotProfile r = rot_profile(rot);
     RotLane m;
-    if (!rot_mapping(n, lam, r, m)) return;
+    if (!rot_mapping(n, lam, 2.0 * r.beta, r.on, m)) return;
     const int64_t j = m.on ? m.pi : n - 1;
     const double lj = lam[j];
     double wf = 0.0, wr = 0.0;
     if (r.on) {
         // the candidates: lam_i in [lam_j / (1 + beta), lam_j / (1 - beta)], a few 1e-15 wide; rot_weight decides
-        const double lo = mul_rn(lj / add_rn(1.0, r.beta), 1.0 - 0x1p-48);
-        const double hi = r.beta < 1.0 ? mul_rn(lj / sub_rn(1.0, r.beta), 1.0 + 0x1p-48) : __longlong_as_double(0x7ff0000000000000LL);
+        double lo, hi;
+        rot_candidates(lj, r.beta, lo, hi);
         int64_t iA, iB;
         obs_windows(lam, lam, n, 1.0, lo, hi, m.on, m.W, m.lane, iA, iB);
         const double h = rot_trapezoid(lam, n, j);
         for (int64_t i = iA + m.t; i < iB; i += m.W) {
             double w;
             if (!rot_weight(r, lam[i], lj, i == j, h, w)) continue;
+            wf = add_rn(wf, mul_rn(w, a[i]));
+            if (a_ref) wr = add_rn(wr, mul_rn(w, a_ref[i]));
+        }
+        for (int off = m.W >> 1; off > 0; off >>= 1) wf = add_rn(wf, __shfl_xor(wf, off)), wr = add_rn(wr, __shfl_xor(wr, off));
+    } else {
+        wf = a[j];
+        if (a_ref) wr = a_ref[j];
+    }
+    if (m.t != 0 || !m.on) return;
+    // (the transpose of k_flux_nu_to_lambda, as k_observe_adjoint ends)
+    w_out[j] = nus ? mul_rn(wf, nus[j]) / lj : wf;
+    if (w_ref) w_ref[j] = nus ? mul_rn(wr, nus[j]) / lj : wr;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Radial-tangential macroturbulence (include/stardis_hip.h, sdx_macroturbulence_dev): Gray's profile with equal areas and zeta_R = zeta_T =
+// zeta, integrated over the disk without limb darkening, K(u) = exp(-u^2) - sqrt(pi) u erfc(u), u = |dv| / zeta, in velocity space on any
+// ascending grid, between k_rotate and k_observe.  With beta = zeta / c, for point i
+//     reach_i = lam_i (6 beta),  lo_i = lam_i - reach_i,  hi_i = lam_i + reach_i,   j is included iff lo_i <= lam_j <= hi_i or j = i,
+//     u_ij = |lam_j - lam_i| / (lam_i beta),   e = exp(-(u u)),   s = (sqrt(pi) u) erfc(u),   K = max(e - s, 0)     (j = i: K = 1, s = 0),
+//     w_ij = K h_j,   v_ij = s h_j   (h_j: rot_trapezoid),   out_i = (sum_j w_ij flux_j) / den_i,   den_i = sum_j w_ij,
+//     dout_i = (sum_j v_ij flux_j - out_i sum_j v_ij) / den_i = d out_i / d ln zeta at fixed windows  (dK / d ln zeta = s: no new term).
+// K(6) = 3e-18 of the peak: the window ends where the profile has left fp64.  !(zeta > 0) copies, dout = 0.  mac_weight is the ONE place
+// where reach, u, K, s, w and v are rounded and a pair is included or not: the forward kernel, the adjoint's denominators and the
+// adjoint's gather call it.  Mapping (rot_mapping with the window's width 2 (6 beta)), window search (obs_windows), trapezoid weights,
+// order of the sums and the adjoint's two launches are k_rotate's; so are the bounds on every access and loop stated there.
+constexpr double kMacReach = 6.0;
+
+struct MacProfile {
+    double beta, reach;  // zeta / c, 6 beta
+    bool on;             // zeta > 0
+};
+__device__ __forceinline__ MacProfile mac_profile(const double* __restrict__ mac)
+{
+    const double zeta = mac[0], beta = zeta / kCKms;
+    return MacProfile{beta, mul_rn(kMacReach, beta), zeta > 0.0};
+}
+// point i's weights for point j (self: j == i), h = the trapezoid weight of j: w = K h, v = s h; false: i does not include j
+__device__ __forceinline__ bool mac_weight(const MacProfile& r, double lam_i, double lam_j, bool self, double h, double& w, double& v)
+{
+    double K = 1.0, s = 0.0;
+    if (!self) {
+        const double reach = mul_rn(lam_i, r.reach), lo = sub_rn(lam_i, reach), hi = add_rn(lam_i, reach);
+        if (!(lo <= lam_j && lam_j <= hi)) return false;
+        const double u = fabs(sub_rn(lam_j, lam_i)) / mul_rn(lam_i, r.beta);
+        s = mul_rn(mul_rn(kSqrtPi, u), erfc(u));
+        K = fmax(sub_rn(exp(-mul_rn(u, u)), s), 0.0);
+    }
+    w = mul_rn(K, h), v = mul_rn(s, h);
+    return true;
+}
+
+// What the point's lanes sum, closed by the butterfly, in every lane of the point: num = sum_j w_ij flux[j], numr = sum_j w_ij ref[j],
+// den = sum_j w_ij and, with deriv, the same three sums of v_ij (nullptr / false: not formed).  Not called where !(zeta > 0).
+struct MacSums {
+    double num, numr, den, vnum, vnumr, vden;
+};
+__device__ __forceinline__ void mac_point_sums(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                               const double* __restrict__ ref, bool deriv, const MacProfile& r, const RotLane& m, MacSums& s)
+{
+    const int64_t i = m.on ? m.pi : n - 1;
+    const double li = lam[i];
+    const double reach = mul_rn(li, r.reach);
+    int64_t i0, i1;
+    obs_windows(lam, lam, n, 1.0, sub_rn(li, reach), add_rn(li, reach), m.on, m.W, m.lane, i0, i1);
+    s = MacSums{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int64_t j = i0 + m.t; j < i1; j += m.W) {
+        double w, v;
+        if (!mac_weight(r, li, lam[j], j == i, rot_trapezoid(lam, n, j), w, v)) continue;
+        const double f = flux ? flux[j] : 0.0, g = ref ? ref[j] : 0.0;
+        if (flux) s.num = add_rn(s.num, mul_rn(w, f));
+        if (ref) s.numr = add_rn(s.numr, mul_rn(w, g));
+        s.den = add_rn(s.den, w);
+        if (deriv) {
+            if (flux) s.vnum = add_rn(s.vnum, mul_rn(v, f));
+            if (ref) s.vnumr = add_rn(s.vnumr, mul_rn(v, g));
+            s.vden = add_rn(s.vden, v);
+        }
+    }
+    for (int off = m.W >> 1; off > 0; off >>= 1) {
+        s.num = add_rn(s.num, __shfl_xor(s.num, off)), s.numr = add_rn(s.numr, __shfl_xor(s.numr, off));
+        s.den = add_rn(s.den, __shfl_xor(s.den, off));
+        if (deriv) {
+            s.vnum = add_rn(s.vnum, __shfl_xor(s.vnum, off)), s.vnumr = add_rn(s.vnumr, __shfl_xor(s.vnumr, off));
+            s.vden = add_rn(s.vden, __shfl_xor(s.vden, off));
+        }
+    }
+}
+
+// dout, dout_ref: optional (nullptr: the v sums are not formed); dout_ref only with ref
+__global__ __launch_bounds__(kBlock) void k_macroturbulence(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                                            const double* __restrict__ ref, const double* __restrict__ mac,
+                                                            double* __restrict__ out, double* __restrict__ out_ref, double* __restrict__ dout,
+                                                            double* __restrict__ dout_ref)
+{
+    const MacProfile r = mac_profile(mac);
+    RotLane m;
+    if (!rot_mapping(n, lam, 2.0 * r.reach, r.on, m)) return;
+    if (!r.on) {  // (the group's first wave, eight lanes per point: a copy)
+        if (m.t == 0 && m.on) {
+            out[m.pi] = flux[m.pi];
+            if (ref) out_ref[m.pi] = ref[m.pi];
+            if (dout) dout[m.pi] = 0.0;
+            if (dout_ref) dout_ref[m.pi] = 0.0;
+        }
+        return;
+    }
+    MacSums s;
+    mac_point_sums(n, lam, flux, ref, dout != nullptr || dout_ref != nullptr, r, m, s);
+    if (m.t != 0 || !m.on) return;
+    const double o = s.num / s.den;
+    out[m.pi] = o;
+    if (dout) dout[m.pi] = sub_rn(s.vnum, mul_rn(o, s.vden)) / s.den;
+    if (ref) {
+        const double g = s.numr / s.den;
+        out_ref[m.pi] = g;
+        if (dout_ref) dout_ref[m.pi] = sub_rn(s.vnumr, mul_rn(g, s.vden)) / s.den;
+    }
+}
+
+// a[i] = u[i] / den_i, a_ref[i] = u_ref[i] / den_i (u_ref = nullptr: none); !(zeta > 0): den = 1
+__global__ __launch_bounds__(kBlock) void k_macroturbulence_adjoint_den(int64_t n, const double* __restrict__ lam, const double* __restrict__ mac,
+                                                                        const double* __restrict__ u, const double* __restrict__ u_ref,
+                                                                        double* __restrict__ a, double* __restrict__ a_ref)
+{
+    const MacProfile r = mac_profile(mac);
+    RotLane m;
+    if (!rot_mapping(n, lam, 2.0 * r.reach, r.on, m)) return;
+    MacSums s;
+    s.den = 1.0;
+    if (r.on) mac_point_sums(n, lam, nullptr, nullptr, false, r, m, s);
+    if (m.t != 0 || !m.on) return;
+    a[m.pi] = r.on ? u[m.pi] / s.den : u[m.pi];
+    if (u_ref) a_ref[m.pi] = r.on ? u_ref[m.pi] / s.den : u_ref[m.pi];
+}
+
+__global__ __launch_bounds__(kBlock) void k_macroturbulence_adjoint(int64_t n, const double* __restrict__ lam, const double* __restrict__ mac,
+                                                                    const double* __restrict__ a, const double* __restrict__ a_ref,
+                                                                    const double* __restrict__ nus, double* __restrict__ w_out,
+                                                                    double* __restrict__ w_ref)
+{
+    const MacProfile r = mac_profile(mac);
+    RotLane m;
+    if (!rot_mapping(n, lam, 2.0 * r.reach, r.on, m)) return;
+    const int64_t j = m.on ? m.pi : n - 1;
+    const double lj = lam[j];
+    double wf = 0.0, wr = 0.0;
+    if (r.on) {
+        // the candidates: lam_i in [lam_j / (1 + 6 beta), lam_j / (1 - 6 beta)], a few 1e-15 wide; mac_weight decides
+        double lo, hi;
+        rot_candidates(lj, r.reach, lo, hi);
+        int64_t iA, iB;
+        obs_windows(lam, lam, n, 1.0, lo, hi, m.on, m.W, m.lane, iA, iB);
+        const double h = rot_trapezoid(lam, n, j);
+        for (int64_t i = iA + m.t; i < iB; i += m.W) {
+            double w, v;
+            if (!mac_weight(r, lam[i], lj, i == j, h, w, v)) continue;
             wf = add_rn(wf, mul_rn(w, a[i]));
             if (a_ref) wr = add_rn(wr, mul_rn(w, a_ref[i]));
         }

@@ -91,6 +91,8 @@ struct sdx_ctx {
     size_t obs_ws_bytes = 0;
     void* rot_ws = nullptr;  // the rotation adjoint's factors a = u / den, two rows of n (sdx_rotate_adjoint_dev)
     size_t rot_ws_bytes = 0;
+    void* mac_ws = nullptr;  // the macroturbulence adjoint's factors a = u / den, two rows of n (sdx_macroturbulence_adjoint_dev)
+    size_t mac_ws_bytes = 0;
     void* far_ws = nullptr;  // far_range of the line kernels' far field: two ints per global tile
     size_t far_ws_bytes = 0;
     // cnt_ge[N_nu + 2] (lines per centre index, for the narrow-window kernel) and the per-line integer lists: CntLayout
@@ -461,6 +463,7 @@ void sdx_destroy(sdx_ctx* ctx)
     if (ctx->adj_ws) hipFree(ctx->adj_ws);
     if (ctx->obs_ws) hipFree(ctx->obs_ws);
     if (ctx->rot_ws) hipFree(ctx->rot_ws);
+    if (ctx->mac_ws) hipFree(ctx->mac_ws);
     if (ctx->cnt_ws) hipFree(ctx->cnt_ws);
     if (ctx->io_dev) hipFree(ctx->io_dev);
     if (ctx->io_pin) hipHostFree(ctx->io_pin);
@@ -2941,6 +2944,129 @@ int sdx_rotate_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, doubl
     HostIo io{ctx};
     if ((rc = io.stage(plan))) return rc;
     if ((rc = sdx_rotate_adjoint_dev(ctx, n, d_l, d_rot, d_u, d_ur, d_nus, d_w, d_wr))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+// ---- radial-tangential macroturbulence (k_macroturbulence) and its adjoint (k_macroturbulence_adjoint_den, k_macroturbulence_adjoint) ----
+// (k_rotate's launch geometry: rotate_blocks)
+int sdx_macroturbulence_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, const double* mac_dev,
+                            double* out, double* out_reference, double* dout, double* dout_reference)
+{
+    REQUIRE(ctx, "macroturbulence: null context");
+    REQUIRE(n >= 2, "macroturbulence: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && flux && mac_dev && out, "macroturbulence: null pointer (lambdas, flux, mac_dev and out are required)");
+    REQUIRE(!reference == !out_reference, "macroturbulence: reference and out_reference go together");
+    REQUIRE(!dout_reference || reference, "macroturbulence: dout_reference needs a reference");
+    const double* const ins[4] = {lambdas, flux, reference, mac_dev};
+    double* const outs[4] = {out, out_reference, dout, dout_reference};
+    for (int a = 0; a < 4; ++a) {
+        if (!outs[a]) continue;
+        for (int b = 0; b < 4; ++b)
+            REQUIRE(outs[a] != ins[b] && (b <= a || outs[a] != outs[b]),
+                    "macroturbulence: not in place (out, out_reference, dout and dout_reference must be buffers of their own)");
+    }
+    REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "macroturbulence: too many points for one launch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    {
+        LaunchScope ls(ctx, "k_macroturbulence");
+        hipLaunchKernelGGL(k_macroturbulence, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, flux, reference, mac_dev, out,
+                           out_reference, dout, dout_reference);
+    }
+    return check_launch("k_macroturbulence");
+}
+
+int sdx_macroturbulence_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* mac_dev, const double* u,
+                                    const double* u_reference, const double* nus, double* w, double* w_reference)
+{
+    REQUIRE(ctx, "macroturbulence_adjoint: null context");
+    REQUIRE(n >= 2, "macroturbulence_adjoint: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && mac_dev && u && w, "macroturbulence_adjoint: null pointer (lambdas, mac_dev, u and w are required)");
+    REQUIRE(!u_reference == !w_reference, "macroturbulence_adjoint: u_reference and w_reference go together");
+    const double* const ins[5] = {lambdas, mac_dev, u, u_reference, nus};
+    for (int b = 0; b < 5; ++b)
+        REQUIRE(w != ins[b] && (!w_reference || w_reference != ins[b]) && w != w_reference,
+                "macroturbulence_adjoint: not in place (w and w_reference must be buffers of their own)");
+    REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "macroturbulence_adjoint: too many points for one launch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t row = ((size_t)n * sizeof(double) + 255) & ~(size_t)255;
+    int rc = ensure(ctx, &ctx->mac_ws, &ctx->mac_ws_bytes, 2 * row);
+    if (rc) return rc;
+    double* const a = (double*)ctx->mac_ws;
+    double* const a_ref = (double*)((char*)ctx->mac_ws + row);
+    {
+        LaunchScope ls(ctx, "k_macroturbulence_adjoint");
+        hipLaunchKernelGGL(k_macroturbulence_adjoint_den, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, mac_dev, u, u_reference,
+                           a, a_ref);
+        hipLaunchKernelGGL(k_macroturbulence_adjoint, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, mac_dev, (const double*)a,
+                           u_reference ? (const double*)a_ref : nullptr, nus, w, w_reference);
+    }
+    return check_launch("k_macroturbulence_adjoint");
+}
+
+// what the kernels cannot check: the host-buffer twins do, before any upload
+static int macroturbulence_host_check(int64_t n, const double* lambdas, double zeta)
+{
+    REQUIRE(std::isfinite(zeta) && zeta >= 0.0 && zeta < 500.0, "macroturbulence: zeta must be finite with 0 <= zeta < 500 km/s");
+    for (int64_t i = 0; i < n; ++i)
+        REQUIRE(std::isfinite(lambdas[i]) && (i == 0 || lambdas[i - 1] < lambdas[i]), "macroturbulence: lambdas must be finite and strictly ascending");
+    return SDX_OK;
+}
+
+int sdx_macroturbulence_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, double zeta,
+                            double* out, double* out_reference, double* dout, double* dout_reference)
+{
+    REQUIRE(ctx, "macroturbulence: null context");
+    REQUIRE(n >= 2, "macroturbulence: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && flux && out, "macroturbulence: null pointer (lambdas, flux and out are required)");
+    REQUIRE(!reference == !out_reference, "macroturbulence: reference and out_reference go together");
+    REQUIRE(!dout_reference || reference, "macroturbulence: dout_reference needs a reference");
+    int rc;
+    if ((rc = macroturbulence_host_check(n, lambdas, zeta))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
+    const double *d_l, *d_f, *d_r, *d_mac;
+    double *d_o, *d_or, *d_d, *d_dr;
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(flux, grid, &d_f);
+    plan.in(reference, grid, &d_r);
+    plan.in(&zeta, f8, &d_mac);
+    plan.out(out, grid, &d_o);
+    plan.out(out_reference, grid, &d_or);
+    plan.out(dout, grid, &d_d);
+    plan.out(dout_reference, grid, &d_dr);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_macroturbulence_dev(ctx, n, d_l, d_f, d_r, d_mac, d_o, d_or, d_d, d_dr))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+int sdx_macroturbulence_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, double zeta, const double* u, const double* u_reference,
+                                    const double* nus, double* w, double* w_reference)
+{
+    REQUIRE(ctx, "macroturbulence_adjoint: null context");
+    REQUIRE(n >= 2, "macroturbulence_adjoint: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && u && w, "macroturbulence_adjoint: null pointer (lambdas, u and w are required)");
+    REQUIRE(!u_reference == !w_reference, "macroturbulence_adjoint: u_reference and w_reference go together");
+    int rc;
+    if ((rc = macroturbulence_host_check(n, lambdas, zeta))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
+    const double *d_l, *d_mac, *d_u, *d_ur, *d_nus;
+    double *d_w, *d_wr;
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(&zeta, f8, &d_mac);
+    plan.in(u, grid, &d_u);
+    plan.in(u_reference, grid, &d_ur);
+    plan.in(nus, grid, &d_nus);
+    plan.out(w, grid, &d_w);
+    plan.out(w_reference, grid, &d_wr);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_macroturbulence_adjoint_dev(ctx, n, d_l, d_mac, d_u, d_ur, d_nus, d_w, d_wr))) return rc;
     if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }

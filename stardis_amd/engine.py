@@ -7,6 +7,7 @@ calc_alphas + raytrace in stardis_amd.radiation_field (and hence the reference's
 radiation_field/base.py:104-115): total = ((((file + bf) + ff) + rayleigh) + electron) + line.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -68,6 +69,8 @@ class SpectralSynthesizer:
         (sdx_flux_nu_to_lambda_dev) and passes it through the instrument (sdx_observe_dev: radial velocity, line-spread function,
         pixels) -> `observed` (n_pix,); with keep_continuum_flux also `observed_normalized`, the same with the continuum's F_lambda as
         reference.  Both launches are part of whatever capture() records, and a recorded step follows instrument.set_radial_velocity().
+        An instrument with v_rot or v_mac broadens F_lambda (and the continuum's) once per step in front of the pixels — rotation,
+        then macroturbulence — and a recorded step follows set_rotation() and set_macroturbulence() too.
         Needs the whole grid (a shard raises ValueError: gather first).  Off, the step is unchanged.
         grid_plan: build an sdx_grid_plan (include/stardis_hip.h) from the uploaded grid, line frequencies and cross-section table
         and pass it with every step: what the pre-pass launch forms from them alone is then formed once, here.  The same bits; dense
@@ -154,7 +157,7 @@ class SpectralSynthesizer:
         if instrument is not None:
             self.lambdas = K.nu_to_angstrom(nus)
             self.d_lambdas = c.upload(self.lambdas)
-            instrument.reserve(self.n_nu)  # (a rotating instrument's scratch: a capture of the step allocates nothing)
+            instrument.reserve(self.n_nu)  # (a broadening instrument's scratch: a capture of the step allocates nothing)
             self.d_Flam = c.empty((self.n_nu,))
             self.d_observed = c.empty((instrument.n_pix,))
             if self.keep_continuum_flux:
@@ -280,18 +283,18 @@ class SpectralSynthesizer:
         c, n, inst = self.ctx, self.n_nu, self.instrument
         last = 8 * (self.n_depth - 1) * self.count  # row N_d - 1
         c.call("sdx_flux_nu_to_lambda_dev", n, self.flux_ptr + last, self.d_nus.ptr, self.d_lambdas.ptr, self.d_Flam.ptr)
-        if not inst.rotates:
+        if not inst.broadens:
             inst.observe(self.d_lambdas, self.d_Flam, n, out=self.d_observed)
             if self.keep_continuum_flux:
                 c.call("sdx_flux_nu_to_lambda_dev", n, self.d_Fc.ptr + last, self.d_nus.ptr, self.d_lambdas.ptr, self.d_Fclam.ptr)
                 inst.observe(self.d_lambdas, self.d_Flam, n, reference=self.d_Fclam, out=self.d_observed_normalized)
             return
-        # a rotating instrument: F_lambda (and the continuum's) broadened ONCE per step, whatever is observed of them
+        # rotation, macroturbulence: F_lambda (and the continuum's) broadened ONCE per step, whatever is observed of them
         if not self.keep_continuum_flux:
-            inst.observe(self.d_lambdas, inst.rotate(self.d_lambdas, self.d_Flam, n), n, out=self.d_observed, broadened=True)
+            inst.observe(self.d_lambdas, inst.broaden(self.d_lambdas, self.d_Flam, n), n, out=self.d_observed, broadened=True)
             return
         c.call("sdx_flux_nu_to_lambda_dev", n, self.d_Fc.ptr + last, self.d_nus.ptr, self.d_lambdas.ptr, self.d_Fclam.ptr)
-        flux, cont = inst.rotate(self.d_lambdas, self.d_Flam, n, reference=self.d_Fclam)
+        flux, cont = inst.broaden(self.d_lambdas, self.d_Flam, n, reference=self.d_Fclam)
         inst.observe(self.d_lambdas, flux, n, out=self.d_observed, broadened=True)
         inst.observe(self.d_lambdas, flux, n, reference=cont, out=self.d_observed_normalized, broadened=True)
 
@@ -653,6 +656,13 @@ class SpectralSynthesizer:
         if self.instrument is None:
             raise RuntimeError("no instrument: construct the synthesizer with instrument=Instrument(...)")
 
+    def _require_macroturbulence(self):
+        self._require_instrument()
+        if not self.instrument.macroturbulent:
+            raise RuntimeError("no macroturbulence: construct the Instrument with v_mac=")
+        if not self.instrument.v_mac > 0.0:
+            raise ValueError("the derivative to zeta needs zeta > 0 (at zeta = 0 the stage is a copy)")
+
     def _pixel_vector(self, name, c):
         """a vector over the instrument's pixels (host array, DeviceArray or CUDA tensor) -> a device buffer; ValueError naming it"""
         n_pix = self.instrument.n_pix
@@ -700,13 +710,20 @@ class SpectralSynthesizer:
         observed_normalized) spectrum against data, and its gradient to ln gf of every line, (n_lines,) or (n_lines, N_d):
         observed_line_sensitivities with c_j = -2 ivar_j (data_j - observed_j).  A pixel whose observed value is NaN (the grid does not
         cover its window) or whose ivar is 0 is left out of both; leaving every pixel out is a ValueError.  data, inverse_variance:
-        host arrays, one value per pixel.  With a rotating instrument (Instrument(v_rot=...)) the pixels it reports as edge_affected —
-        those that may see a point whose rotation window is truncated at an end of the grid — are left out in the same way.  A
+        host arrays, one value per pixel.  With rotation or macroturbulence (Instrument(v_rot=..., v_mac=...)) the pixels it reports
+        as edge_affected — those that may see a point whose broadening window is truncated at an end of the grid — are left out in
+        the same way.  A
         diagnostic call, not part of the step: it waits for the stream and forms the n_pix residuals on the host.  wrt: as for
         line_sensitivities (a tuple: the gradient is a dict)."""
         self._wrt_names(wrt)
         self._require_instrument()
         self._require_response()
+        chi2, c = self._chi2_pixel_weights(data, inverse_variance, normalized)
+        return chi2, self.observed_line_sensitivities(c, normalized, per_depth, wrt)
+
+    def _chi2_pixel_weights(self, data, inverse_variance, normalized):
+        """-> (chi2, c): chi-square over the pixels chi2_line_gradient uses and c_j = d chi2 / d observed_j = -2 ivar_j (data_j -
+        observed_j), 0 at the pixels left out"""
         if normalized:
             self._require_continuum()
         n_pix = self.instrument.n_pix
@@ -717,14 +734,51 @@ class SpectralSynthesizer:
                 raise ValueError(f"{name} must hold one value per pixel of the instrument ({n_pix}), got {v.size}")
         obs = (self.d_observed_normalized if normalized else self.d_observed).numpy()
         use = ~np.isnan(obs) & (ivar != 0)
-        if self.instrument.rotates:
+        if self.instrument.broadens:
             use &= ~self.instrument.edge_affected(self.lambdas)
         if not np.any(use):
             raise ValueError("no pixel left: every pixel is NaN (not covered by the grid), edge-affected or has inverse_variance 0")
         r = np.where(use, d, 0.0) - np.where(use, obs, 0.0)
         w = np.where(use, ivar, 0.0)
-        chi2 = float(np.sum(w * r * r))
-        return chi2, self.observed_line_sensitivities(-2.0 * w * r, normalized, per_depth, wrt)
+        return float(np.sum(w * r * r)), -2.0 * w * r
+
+    def observed_macroturbulence_derivative(self, c, normalized=False):
+        """-> float: d(sum_j c_j observed_j) / d zeta per km/s (normalized=True: of observed_normalized) at the last step's spectrum
+        and the instrument's present zeta, at fixed windows — the first instrument-PARAMETER derivative.  On demand, a diagnostic
+        call like chi2_line_gradient: the stages in front of the macroturbulence run again, then one k_macroturbulence with its
+        derivative outputs (d / d ln zeta of the broadened flux and continuum, from the terms the profile is made of) and one
+        k_observe_adjoint for the weights w over the BROADENED points; the result is sum_i (w_flux_i dout_i + w_reference_i
+        dout_reference_i) / zeta, summed ON THE HOST after one download (math.fsum of the fp64 products: exactly rounded, so the
+        same bits everywhere).  c: one value per pixel; c of a NaN pixel is never read.  Needs Instrument(v_mac=...) with zeta > 0."""
+        self._require_macroturbulence()
+        inst, n = self.instrument, self.n_nu
+        if normalized:
+            self._require_continuum()
+        d_c = self._pixel_vector("c", c)
+        ref = self.d_Fclam if normalized else None
+        flux = self.d_Flam
+        if inst.rotates:
+            res = inst.rotate(self.d_lambdas, flux, n, reference=ref)
+            flux, ref = res if normalized else (res, None)
+        d_dout, d_w = self.ctx.empty((n,)), self.ctx.empty((n,))
+        d_dref, d_wref = (self.ctx.empty((n,)), self.ctx.empty((n,))) if normalized else (None, None)
+        res = inst.macroturbulence(self.d_lambdas, flux, n, reference=ref, dout=d_dout, dout_reference=d_dref)
+        flux, ref = res if normalized else (res, None)
+        self.ctx.call("sdx_observe_adjoint_dev", n, self.d_lambdas.ptr, flux.ptr if normalized else None, _lib.ptr_of(ref), inst.n_pix,
+                      inst.d_edges.ptr, inst.d_sigma.ptr, inst.d_doppler.ptr, _lib.ptr_of(d_c), None, d_w.ptr, _lib.ptr_of(d_wref))
+        terms = d_w.numpy() * d_dout.numpy()
+        if normalized:
+            terms = np.concatenate([terms, d_wref.numpy() * d_dref.numpy()])
+        return math.fsum(terms) / inst.v_mac
+
+    def chi2_macroturbulence_gradient(self, data, inverse_variance, normalized=False):
+        """-> (chi2, d chi2 / d zeta): chi-square of the last step's observed (normalized=True: observed_normalized) spectrum against
+        data over the pixels chi2_line_gradient uses (NaN, inverse_variance 0 and edge_affected pixels left out), and its derivative
+        to the macroturbulence zeta per km/s: observed_macroturbulence_derivative with c_j = -2 ivar_j (data_j - observed_j).  No
+        v_mac, or zeta = 0, raises."""
+        self._require_macroturbulence()
+        chi2, c = self._chi2_pixel_weights(data, inverse_variance, normalized)
+        return chi2, self.observed_macroturbulence_derivative(c, normalized)
 
     @property
     def observed(self):

@@ -6,7 +6,10 @@ Instrument.adjoint is the operator transposed (sdx_observe_adjoint_dev): weights
 With v_rot the star's rotation (v sin i, Gray's profile with linear limb darkening; sdx_rotate_dev states the operator) is applied on
 the rest-frame grid in front of k_observe, in velocity space on any ascending grid, and its transpose behind the instrument's: one more
 launch forward, two more transposed.  postprocess.rotation_broadening, which mirrors the reference, is another thing: a kernel at
-integer pixel offsets, a rotation profile on a log-uniform grid only."""
+integer pixel offsets, a rotation profile on a log-uniform grid only.
+With v_mac the radial-tangential macroturbulence zeta (sdx_macroturbulence_dev states the operator) follows the rotation and precedes
+k_observe — the order is rotate -> macroturbulence -> observe, and the adjoint runs it in reverse; both broadenings are convolutions in
+velocity, so on a log-uniform grid the order does not matter, and elsewhere this one is the definition."""
 import math
 
 import numpy as np
@@ -66,6 +69,20 @@ def rotation_pair(v_rot, limb_darkening=0.6):
     return V, eps
 
 
+def macroturbulence_zeta(v_mac):
+    """-> zeta as a float, validated as sdx_macroturbulence_f64 validates it: finite with 0 <= zeta < 500 km/s.  Needs no device."""
+    try:
+        zeta = float(getattr(v_mac, "value", v_mac))
+    except (TypeError, ValueError):
+        raise ValueError("v_mac must be a number") from None
+    if not (math.isfinite(zeta) and 0.0 <= zeta < 500.0):
+        raise ValueError("v_mac must be finite with 0 <= v_mac < 500 km/s")
+    return zeta
+
+
+MACROTURBULENCE_REACH = 6.0  # the profile's window in units of zeta (K(6) = 3e-18 of the peak)
+
+
 def _host_vector(name, a, n, what):
     v = np.ascontiguousarray(getattr(a, "value", a), dtype=np.float64).reshape(-1)
     if v.size != n:
@@ -96,12 +113,18 @@ class Instrument:
     v_rot (km/s; None: no rotation, and nothing below exists or runs) and limb_darkening: the star's v sin i and linear limb-darkening
     coefficient.  The pair lives on the device like the Doppler factor (set_rotation); observe() then broadens flux and reference
     into scratch of the instrument's (k_rotate, sized at first use or by reserve(n)) and observes that.  A rotation window that reaches
-    past an end of the grid is truncated and renormalised: edge_affected() names the pixels that see such points."""
+    past an end of the grid is truncated and renormalised: edge_affected() names the pixels that see such points.
+    v_mac (km/s; None: no macroturbulence, and nothing of it exists or runs): the radial-tangential macroturbulence zeta, one more
+    device scalar (set_macroturbulence) and one more stage (k_macroturbulence) between the rotation and the pixels, with the same
+    scratch rules and the same treatment of the grid's ends."""
 
-    def __init__(self, pixel_edges, resolving_power=None, sigma=None, ctx=None, v_rot=None, limb_darkening=0.6):
+    def __init__(self, pixel_edges, resolving_power=None, sigma=None, ctx=None, v_rot=None, limb_darkening=0.6, v_mac=None):
         self.edges, self.sigma = pixel_sigma(pixel_edges, resolving_power, sigma)  # (ValueError before any device work)
         self.rotates = v_rot is not None
         pair = rotation_pair(v_rot, limb_darkening) if self.rotates else None
+        self.macroturbulent = v_mac is not None
+        zeta = macroturbulence_zeta(v_mac) if self.macroturbulent else None
+        self.broadens = self.rotates or self.macroturbulent  # a stage in front of k_observe
         self.n_pix = self.edges.size - 1
         self.ctx = ctx or default_context()
         self.d_edges = self.ctx.upload(self.edges)
@@ -114,6 +137,10 @@ class Instrument:
         if self.rotates:
             self.d_rot = self.ctx.empty((2,))
             self.set_rotation(*pair)
+        self.v_mac = None
+        if self.macroturbulent:
+            self.d_mac = self.ctx.empty((1,))
+            self.set_macroturbulence(zeta)
 
     def set_rotation(self, v_rot, limb_darkening=None):
         """Write (v sin i, limb darkening) into the device pair, in order on the context's stream; limb_darkening=None keeps the
@@ -124,13 +151,22 @@ class Instrument:
         self.d_rot.set(np.array([V, eps]))
         self.v_rot, self.limb_darkening = V, eps
 
+    def set_macroturbulence(self, zeta):
+        """Write zeta (km/s) into the device scalar, in order on the context's stream.  Only for an instrument constructed with v_mac
+        (0 allowed)."""
+        if not self.macroturbulent:
+            raise RuntimeError("no macroturbulence: construct the Instrument with v_mac= (0 allowed)")
+        zeta = macroturbulence_zeta(zeta)
+        self.d_mac.set(np.array([zeta]))
+        self.v_mac = zeta
+
     def reserve(self, n):
-        """Size the rotation's scratch for grids of up to n points now (broadened flux and reference, and the adjoint's two
-        intermediate weight vectors), so that a later observe() or adjoint() — inside a graph capture, say — allocates nothing.
-        Without rotation there is no scratch and this does nothing."""
+        """Size the broadening stages' scratch for grids of up to n points now (per stage: broadened flux and reference, and the
+        adjoint's two intermediate weight vectors), so that a later observe() or adjoint() — inside a graph capture, say — allocates
+        nothing.  Without rotation and macroturbulence there is no scratch and this does nothing."""
         n = int(n)
-        if self.rotates and n > self._scratch_n:
-            self._scratch = tuple(self.ctx.empty((n,)) for _ in range(4))
+        if self.broadens and n > self._scratch_n:
+            self._scratch = tuple(self.ctx.empty((n,)) for _ in range(4 * (self.rotates + self.macroturbulent)))
             self._scratch_n = n
 
     def rotate(self, d_lambdas, d_flux, n, reference=None, out=None, out_reference=None):
@@ -154,14 +190,58 @@ class Instrument:
             raise RuntimeError("no rotation: construct the Instrument with v_rot= (0 allowed)")
         return rotate_host(self.ctx, lambdas, flux, self.v_rot, self.limb_darkening, reference)
 
+    def macroturbulence(self, d_lambdas, d_flux, n, reference=None, out=None, out_reference=None, dout=None, dout_reference=None):
+        """The macroturbulence stage alone (sdx_macroturbulence_dev): n points of (rest-frame wavelength, flux[, reference]) on the
+        device -> the broadened flux, or (flux, reference) with a reference; into the instrument's scratch unless `out` (and
+        out_reference) are given.  dout (and dout_reference, with a reference): buffers that receive d out / d ln zeta from the
+        same launch."""
+        if not self.macroturbulent:
+            raise RuntimeError("no macroturbulence: construct the Instrument with v_mac= (0 allowed)")
+        addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
+        self.reserve(n)
+        first = 4 if self.rotates else 0  # (behind the rotation's four)
+        out = self._scratch[first] if out is None else out
+        if reference is None:
+            out_reference = None
+        elif out_reference is None:
+            out_reference = self._scratch[first + 1]
+        self.ctx.call("sdx_macroturbulence_dev", int(n), addr(d_lambdas), addr(d_flux), addr(reference), self.d_mac.ptr, addr(out),
+                      addr(out_reference), addr(dout), addr(dout_reference))
+        return out if reference is None else (out, out_reference)
+
+    def macroturbulence_host(self, lambdas, flux, reference=None, derivative=False):
+        """numpy in, numpy out (sdx_macroturbulence_f64, which checks the arrays): -> the broadened flux, or (flux, reference);
+        derivative=True appends d / d ln zeta of each."""
+        if not self.macroturbulent:
+            raise RuntimeError("no macroturbulence: construct the Instrument with v_mac= (0 allowed)")
+        return macroturbulence_host(self.ctx, lambdas, flux, self.v_mac, reference, derivative)
+
+    def broaden(self, d_lambdas, d_flux, n, reference=None):
+        """The stages in front of k_observe in their order — rotation, then macroturbulence, whichever the instrument has — into the
+        instrument's scratch -> the broadened flux, or (flux, reference) with a reference: what observe(..., broadened=True) takes."""
+        res = d_flux if reference is None else (d_flux, reference)
+        for on, stage in ((self.rotates, self.rotate), (self.macroturbulent, self.macroturbulence)):
+            if on:
+                res = stage(d_lambdas, res, n) if reference is None else stage(d_lambdas, res[0], n, res[1])
+        return res
+
+    def _broaden_host(self, lam, f, g):
+        """broaden() through the host-buffer twins -> (flux, reference or None)"""
+        for on, stage in ((self.rotates, self.rotate_host), (self.macroturbulent, self.macroturbulence_host)):
+            if on:
+                f, g = (stage(lam, f), None) if g is None else stage(lam, f, g)
+        return f, g
+
     def edge_affected(self, lambdas):
         """-> boolean host array (n_pix,): the pixels whose window [edges[j] - 8 sigma[j], edges[j+1] + 8 sigma[j]], taken back to the
-        rest frame, comes within the rotation's reach of an end of the grid `lambdas` — lo (1 - beta) < lambdas[0] or hi (1 + beta) >
-        lambdas[-1] — so that a rotation window of a point they may see is truncated there.  Without rotation (beta = 0) these are
-        the pixels the grid does not cover.  Plain numpy."""
+        rest frame, comes within the broadening's reach of an end of the grid `lambdas` — lo (1 - beta) < lambdas[0] or hi (1 + beta) >
+        lambdas[-1], beta = (v_rot + 6 v_mac) / c the combined reach of rotation and macroturbulence — so that a window of a point
+        they may see is truncated there.  Without either (beta = 0) these are the pixels the grid does not cover.  Plain numpy."""
         lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
         _ascending("lambdas", lam)
         beta = (self.v_rot or 0.0) / K.C_KMS
+        if getattr(self, "v_mac", None):
+            beta = ((self.v_rot or 0.0) + MACROTURBULENCE_REACH * self.v_mac) / K.C_KMS
         lo = (self.edges[:-1] - 8.0 * self.sigma) / self.doppler
         hi = (self.edges[1:] + 8.0 * self.sigma) / self.doppler
         return (lo * (1.0 - beta) < lam[0]) | (hi * (1.0 + beta) > lam[-1])
@@ -175,12 +255,13 @@ class Instrument:
     def observe(self, d_lambdas, d_flux, n, reference=None, out=None, broadened=False):
         """n points of (wavelength, flux[, reference]) already on the device (DeviceArrays, CUDA tensors or raw addresses) -> the
         DeviceArray (n_pix,) of the instrument (or `out`), enqueued on the context's stream: nothing is allocated, nothing waits.
-        With rotation, flux and reference are broadened first (rotate(), into the scratch: sized here at first use, or by
-        reserve(n)); broadened=True says they are already — what rotate() returned — so that several outputs share one k_rotate."""
+        With rotation or macroturbulence, flux and reference are broadened first (broaden(), into the scratch: sized here at first
+        use, or by reserve(n)); broadened=True says they are already — what broaden() returned — so that several outputs share one
+        k_rotate and one k_macroturbulence."""
         addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
         out = self.d_out if out is None else out
-        if self.rotates and not broadened:
-            res = self.rotate(d_lambdas, d_flux, n, reference)
+        if self.broadens and not broadened:
+            res = self.broaden(d_lambdas, d_flux, n, reference)
             d_flux, reference = res if reference is not None else (res, None)
         self.ctx.call("sdx_observe_dev", int(n), addr(d_lambdas), addr(d_flux), addr(reference), self.n_pix, self.d_edges.ptr,
                       self.d_sigma.ptr, self.d_doppler.ptr, out.ptr)
@@ -198,8 +279,8 @@ class Instrument:
             g = np.ascontiguousarray(getattr(reference, "value", reference), dtype=np.float64).reshape(-1)
             if g.size != lam.size:
                 raise ValueError("reference must hold one value per grid point")
-        if self.rotates:  # (the host-buffer twin, then the pixels as without rotation)
-            f, g = self.rotate_host(lam, f, g) if reference is not None else (self.rotate_host(lam, f), None)
+        if self.broadens:  # (the host-buffer twins, then the pixels as without them)
+            f, g = self._broaden_host(lam, f, g if reference is not None else None)
         if reference is not None:
             d_ref = self.ctx.upload(g)
         d_lam, d_f = self.ctx.upload(lam), self.ctx.upload(f)
@@ -215,7 +296,8 @@ class Instrument:
         the context's stream: nothing waits, and nothing is allocated when `out` (and out_reference) are given.
         With rotation the chain is transposed stage by stage: flux and reference are broadened here (the normalised pixel value
         enters), sdx_observe_adjoint_dev gives the weights over the BROADENED points, and sdx_rotate_adjoint_dev takes those back to
-        the grid and applies nus — three stages where there was one, the scratch the instrument's (reserve(n))."""
+        the grid and applies nus — three stages where there was one, the scratch the instrument's (reserve(n)).  With
+        macroturbulence sdx_macroturbulence_adjoint_dev stands between the two (the forward order reversed); the last stage applies nus."""
         addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
         if reference is None and out_reference is not None and out_reference is not False:
             raise ValueError("out_reference needs a reference")
@@ -226,15 +308,22 @@ class Instrument:
             out_reference = self.ctx.empty((int(n),))
         elif out_reference is False:
             out_reference = None
-        if self.rotates:
+        if self.broadens:
             self.reserve(n)
             if reference is not None:
-                flux, reference = self.rotate(d_lambdas, flux, n, reference)
+                flux, reference = self.broaden(d_lambdas, flux, n, reference)
             u, u_ref = self._scratch[2], self._scratch[3] if out_reference is not None else None
             self.ctx.call("sdx_observe_adjoint_dev", int(n), addr(d_lambdas), addr(flux) if reference is not None else None, addr(reference),
                           self.n_pix, self.d_edges.ptr, self.d_sigma.ptr, self.d_doppler.ptr, addr(pixel_weights), None, u.ptr, addr(u_ref))
-            self.ctx.call("sdx_rotate_adjoint_dev", int(n), addr(d_lambdas), self.d_rot.ptr, u.ptr, addr(u_ref), addr(nus), addr(out),
-                          addr(out_reference))
+            if self.macroturbulent:
+                last = not self.rotates  # (the last stage writes the caller's buffers and applies nus)
+                t, t_ref = (out, out_reference) if last else (self._scratch[6], self._scratch[7] if out_reference is not None else None)
+                self.ctx.call("sdx_macroturbulence_adjoint_dev", int(n), addr(d_lambdas), self.d_mac.ptr, u.ptr, addr(u_ref),
+                              addr(nus) if last else None, addr(t), addr(t_ref))
+                u, u_ref = t, t_ref
+            if self.rotates:
+                self.ctx.call("sdx_rotate_adjoint_dev", int(n), addr(d_lambdas), self.d_rot.ptr, u.ptr, addr(u_ref), addr(nus), addr(out),
+                              addr(out_reference))
             return out if out_reference is None else (out, out_reference)
         self.ctx.call("sdx_observe_adjoint_dev", int(n), addr(d_lambdas), addr(flux) if reference is not None else None, addr(reference),
                       self.n_pix, self.d_edges.ptr, self.d_sigma.ptr, self.d_doppler.ptr, addr(pixel_weights), addr(nus), addr(out),
@@ -249,14 +338,21 @@ class Instrument:
         host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
         w = np.empty(lam.size)
         w_ref = np.empty(lam.size) if g is not None else None
-        if self.rotates:  # (the three stages of adjoint(), each through its host-buffer twin)
+        if self.broadens:  # (the stages of adjoint(), each through its host-buffer twin)
             if g is not None:
-                f, g = self.rotate_host(lam, f, g)
+                f, g = self._broaden_host(lam, f, g)
             u, u_ref = np.empty(lam.size), np.empty(lam.size) if g is not None else None
             self.ctx.call("sdx_observe_adjoint_f64", lam.size, host(lam), host(f), host(g), self.n_pix, host(self.edges), host(self.sigma),
                           float(self.doppler), host(c), None, host(u), host(u_ref))
-            self.ctx.call("sdx_rotate_adjoint_f64", lam.size, host(lam), self.v_rot, self.limb_darkening, host(u), host(u_ref), host(nu), host(w),
-                          host(w_ref))
+            if self.macroturbulent:
+                last = not self.rotates
+                t, t_ref = (w, w_ref) if last else (np.empty(lam.size), np.empty(lam.size) if g is not None else None)
+                self.ctx.call("sdx_macroturbulence_adjoint_f64", lam.size, host(lam), self.v_mac, host(u), host(u_ref), host(nu) if last else None,
+                              host(t), host(t_ref))
+                u, u_ref = t, t_ref
+            if self.rotates:
+                self.ctx.call("sdx_rotate_adjoint_f64", lam.size, host(lam), self.v_rot, self.limb_darkening, host(u), host(u_ref), host(nu),
+                              host(w), host(w_ref))
             return w if w_ref is None else (w, w_ref)
         self.ctx.call("sdx_observe_adjoint_f64", lam.size, host(lam), host(f), host(g), self.n_pix, host(self.edges), host(self.sigma),
                       float(self.doppler), host(c), host(nu), host(w), host(w_ref))
@@ -278,3 +374,22 @@ def rotate_host(ctx, lambdas, flux, v_rot, limb_darkening=0.6, reference=None):
     host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     (ctx or default_context()).call("sdx_rotate_f64", lam.size, host(lam), host(f), host(g), V, eps, host(out), host(out_ref))
     return out if g is None else (out, out_ref)
+
+
+def macroturbulence_host(ctx, lambdas, flux, zeta, reference=None, derivative=False):
+    """Radial-tangential macroturbulence of host arrays (sdx_macroturbulence_f64) -> the broadened flux, or (flux, reference) with a
+    reference; derivative=True appends d / d ln zeta of each (flux, dflux) or (flux, reference, dflux, dreference).  The arguments are
+    checked before any device work (ValueError naming the argument)."""
+    zeta = macroturbulence_zeta(zeta)
+    lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
+    _ascending("lambdas", lam)
+    if lam.size < 2:
+        raise ValueError("lambdas must hold at least two points")
+    f = _host_vector("flux", flux, lam.size, "grid point")
+    g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
+    outs = [np.empty(lam.size), None if g is None else np.empty(lam.size), np.empty(lam.size) if derivative else None,
+            np.empty(lam.size) if derivative and g is not None else None]
+    host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    (ctx or default_context()).call("sdx_macroturbulence_f64", lam.size, host(lam), host(f), host(g), zeta, *(host(a) for a in outs))
+    res = tuple(a for a in outs if a is not None)
+    return res[0] if len(res) == 1 else res

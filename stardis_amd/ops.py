@@ -512,12 +512,13 @@ def formation_mean(contribution, x, ctx=None, device=False):
 
 
 # ------------------------------------------------------------------------------------------------ instrument model
-def _rotation_keywords(v_rot, limb_darkening):
-    """the Instrument's rotation keywords: none for v_rot = 0 (the default), so that the call is the one it was"""
-    from .instrument import rotation_pair
+def _rotation_keywords(v_rot, limb_darkening, v_mac=0.0):
+    """the Instrument's broadening keywords: none for v_rot = 0 and v_mac = 0 (the defaults), so that the call is the one it was"""
+    from .instrument import macroturbulence_zeta, rotation_pair
 
     V, eps = rotation_pair(v_rot, limb_darkening)
-    return dict(v_rot=V, limb_darkening=eps) if V else {}
+    zeta = macroturbulence_zeta(v_mac)
+    return dict(dict(v_rot=V, limb_darkening=eps) if V else {}, **(dict(v_mac=zeta) if zeta else {}))
 
 
 def rotate(lambdas, flux, v_rot, limb_darkening=0.6, reference=None, ctx=None):
@@ -531,34 +532,46 @@ def rotate(lambdas, flux, v_rot, limb_darkening=0.6, reference=None, ctx=None):
     return rotate_host(ctx, lambdas, flux, v_rot, limb_darkening, reference)
 
 
-def observe(lambdas, flux, pixel_edges, sigma, v_rad=0.0, reference=None, ctx=None, v_rot=0.0, limb_darkening=0.6):
+def macroturbulence(lambdas, flux, zeta, reference=None, derivative=False, ctx=None):
+    """Radial-tangential macroturbulence in velocity space on any ascending grid (sdx_macroturbulence_f64): Gray's profile with equal
+    areas and zeta_R = zeta_T = zeta (km/s), disk-integrated without limb darkening, K(u) = exp(-u^2) - sqrt(pi) u erfc(u) with u =
+    |dv| / zeta, out_i = sum_j K_ij h_j flux_j / sum_j K_ij h_j over the points within 6 zeta of lambda_i -> (n,); with a reference ->
+    (flux, reference), both broadened.  derivative=True appends d / d ln zeta of each, from the same launch.  Windows that reach past
+    an end of the grid sum what exists.  zeta = 0 is a copy."""
+    from .instrument import macroturbulence_host
+
+    return macroturbulence_host(ctx, lambdas, flux, zeta, reference, derivative)
+
+
+def observe(lambdas, flux, pixel_edges, sigma, v_rad=0.0, reference=None, ctx=None, v_rot=0.0, limb_darkening=0.6, v_mac=0.0):
     """What a spectrograph records of a spectrum (sdx_observe_dev): the wavelengths shifted by the radial velocity v_rad (km/s), a
     Gaussian line-spread function of width sigma (Angstrom; a scalar or one value per pixel) and integration over the pixels between
     pixel_edges -> (n_pix,).  With a reference the continuum-normalised observed spectrum, observe(flux) / observe(reference).  A
     pixel whose window (its edges -+ 8 sigma) the shifted grid does not cover is NaN.  v_rot > 0 (km/s): the star's rotation first
-    (ops.rotate with limb_darkening, on the rest-frame grid).  stardis_amd.instrument.Instrument keeps the pixels on the device for
-    repeated calls."""
+    (ops.rotate with limb_darkening, on the rest-frame grid); v_mac > 0 (km/s): then the macroturbulence (ops.macroturbulence).
+    stardis_amd.instrument.Instrument keeps the pixels on the device for repeated calls."""
     from .instrument import Instrument
 
-    inst = Instrument(pixel_edges, sigma=sigma, ctx=ctx, **_rotation_keywords(v_rot, limb_darkening))
+    inst = Instrument(pixel_edges, sigma=sigma, ctx=ctx, **_rotation_keywords(v_rot, limb_darkening, v_mac))
     if v_rad:
         inst.set_radial_velocity(v_rad)
     return inst.observe_host(lambdas, flux, reference)
 
 
 def observe_adjoint(lambdas, pixel_weights, pixel_edges, sigma, v_rad=0.0, flux=None, reference=None, nus=None, ctx=None, v_rot=0.0,
-                    limb_darkening=0.6):
+                    limb_darkening=0.6, v_mac=0.0):
     """The transpose of observe (sdx_observe_adjoint_f64): pixel_weights c (n_pix,) -> weights w (n,) over the grid points with
     sum_j c_j observe(flux)_j = sum_i w_i flux_i over the pixels the shifted grid covers (c of a NaN pixel is never read) — the
     derivative of any functional of the observed pixels pulled back to the model's grid.  With a reference (which needs the flux) ->
     (weights to the flux, weights to the reference) of the normalised spectrum.  nus: the weights then apply to F_nu instead of
-    F_lambda.  v_rot > 0: the transpose of observe with the same v_rot and limb_darkening, rotation included.  Arguments of the
+    F_lambda.  v_rot > 0, v_mac > 0: the transpose of observe with the same v_rot, limb_darkening and v_mac, the broadenings
+    included.  Arguments of the
     wrong length raise ValueError naming them, before any device work."""
     from .instrument import Instrument, adjoint_host_arguments, pixel_sigma
 
     edges, _ = pixel_sigma(pixel_edges, sigma=sigma)
     adjoint_host_arguments(edges.size - 1, lambdas, pixel_weights, flux, reference, nus)
-    inst = Instrument(pixel_edges, sigma=sigma, ctx=ctx, **_rotation_keywords(v_rot, limb_darkening))
+    inst = Instrument(pixel_edges, sigma=sigma, ctx=ctx, **_rotation_keywords(v_rot, limb_darkening, v_mac))
     if v_rad:
         inst.set_radial_velocity(v_rad)
     return inst.adjoint_host(lambdas, pixel_weights, flux, reference, nus)

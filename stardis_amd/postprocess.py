@@ -139,7 +139,8 @@ class DeviceSpectrum:
         """spectrum_lambda through a stardis_amd.instrument.Instrument (radial velocity, line-spread function, pixels) without leaving
         the device -> DeviceArray (n_pix,).  normalized=True: the continuum's F_lambda goes along as the reference (the synthesizer needs
         keep_continuum_flux=True) and the result is the continuum-normalised observed spectrum, from the same launch.  Works unchanged
-        with a rotating instrument (Instrument(v_rot=...)): flux and reference are broadened by the star's rotation first."""
+        with a rotating instrument (Instrument(v_rot=...)): flux and reference are broadened by the star's rotation first, and likewise by
+        the macroturbulence of Instrument(v_mac=...), behind the rotation."""
         if instrument.ctx is not self.ctx:
             raise ValueError("the instrument and the synthesizer must share a context (one stream orders the launches)")
         syn, reference = self.syn, None
