@@ -723,6 +723,69 @@ int sdx_macroturbulence_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, cons
 int sdx_macroturbulence_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, double zeta, const double* u, const double* u_reference,
                                     const double* nus, double* w, double* w_reference);
 
+/* ---- the tangent of the instrument model: d observed / d (v_rad, LSF width, input spectrum), forward mode ----
+ * The Jacobian-vector products of sdx_observe_dev, one pass over sdx_observe_dev's own windows (k_observe_tangent): where the adjoint
+ * above takes one functional of the pixels back to every grid point, this takes one direction — a parameter, or a tangent of the
+ * spectrum on the grid — forward to every pixel: the columns d out_j / d p that a Gauss-Newton or Levenberg-Marquardt fit of the few
+ * global parameters needs.  In the notation of sdx_observe_dev (x_i = lambdas[i] D, h_i, lo_j, hi_j, covered_j, r_ij, w_ij = r_ij h_i,
+ * den_j = sum_i w_ij g_i, out_j = sum_i w_ij flux[i] / den_j, every one of them formed by the same code as k_observe's), with
+ * a' = (edges[j] - x_i) / sigma[j], b' = (edges[j+1] - x_i) / sigma[j] and phi the unit normal density:
+ *     dr/dx = (phi(a') - phi(b')) / sigma[j],        dr/d ln sigma = a' phi(a') - b' phi(b')        (the device function obs_response_grad),
+ *     d w_ij / d ln D = (x_i dr/dx + r_ij) h_i   (h_i scales with D),        d w_ij / d ln sigma[j] = (dr/d ln sigma) h_i,
+ *     dout_p[j] = (sum_i d_p w_ij flux[i] - out_j sum_i d_p w_ij g_i) / den_j        for p = ln D and p = ln sigma,
+ *     dout_velocity[j] = dout_lnD[j] (D^2 + 1)^2 / (4 D^2 c)      per km/s of v_rad (d ln D / dv for D = sqrt((1 + beta) / (1 - beta))),
+ *     dout_lsf[j]      = dout_ln sigma[j]: the derivative to ln kappa of a common factor kappa on every sigma[j]; for a resolving power
+ *                        R (sigma = centre / (R 2 sqrt(2 ln 2))) this is -d / d ln R,
+ *     dout_flux[j]     = (sum_i w_ij dflux[i] - out_j sum_i w_ij dreference[i]) / den_j     (the tangent of the quotient for the direction
+ *                        (dflux, dreference) of (flux, reference); without dreference the second term is absent).
+ * THE WINDOWS AND covered ARE FIXED, as for the derivative to zeta: a point that enters a window when D or sigma moves carries 1e-15 of
+ * the sum.  The difference phi(a') - phi(b') is formed as e^(-near^2 / 2) expm1(-(|a'^2 - b'^2|) / 2) from the nearer edge, a'^2 - b'^2 =
+ * (a' - b')(a' + b') taken from the differences of the edges and of the point, so that it keeps its relative accuracy for a pixel much
+ * narrower than sigma and where both edges lie in one tail; dr/d ln sigma = near (phi(a') - phi(b')) + (a' - b') phi(far), the product
+ * rule over the same two differences.  An uncovered pixel is NaN in every output.  `out`, when asked for, is sdx_observe_dev's bit for
+ * bit.  fp64, every operation one rounded operation (exp, expm1, erf, erfc: the device library's); no floating-point atomics, the order
+ * of every sum follows from the arrays alone: two calls, the replay of a captured graph and the host-buffer twin give the same bits.
+ * The derivative to v sin i is NOT offered: Gray's profile ends in a square root, dK/d ln V = y^2 (2 (1 - eps) / sqrt(q) + pi eps), and on
+ * the trapezoid sum the forward model has a square-root kink in V wherever a point enters a window; a central difference of two whole
+ * steps remains the answer there.  The derivative to eps is bounded and is sdx_rotate_tangent_dev below.
+ * sdx_observe_tangent_dev: device pointers, asynchronous on the context's stream, no allocation, capturable; D is read from device
+ * memory when the kernel runs (doppler_dev; NULL: 1) and the velocity factor is formed from it there, so a captured call follows a new
+ * velocity.  reference, dflux, dreference and every output are optional (NULL: not read, not formed, not written; the parameter sums
+ * are formed only with dout_velocity or dout_lsf).  SDX_ERR_ARG before anything is enqueued: n < 2 (n_pix = 0 returns at once), a null
+ * required pointer (lambdas, flux, edges, sigma), dreference without reference, dflux without dout_flux or the reverse, an output that
+ * is one of the inputs or another output.  The arrays' contents cannot be checked here: whatever they hold (NaN, unordered values,
+ * sigma <= 0), the searches and loops are sdx_observe_dev's own — every access stays inside the arrays and a pixel's loop runs at most n
+ * trips, reading lambdas at i - 1, i, i + 1 clamped and flux, reference, dflux, dreference at i — and a pixel writes only its own
+ * element of each output: the result is then meaningless, never an out-of-range access.
+ * Stage name for sdx_profile_get: "k_observe_tangent". */
+int sdx_observe_tangent_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
+                            const double* edges, const double* sigma, const double* doppler_dev, const double* dflux,
+                            const double* dreference, double* out, double* dout_velocity, double* dout_lsf, double* dout_flux);
+/* host-buffer twin: host pointers, the Doppler factor by value; lambdas, edges, sigma and doppler are checked as by sdx_observe_f64
+ * before any upload. */
+int sdx_observe_tangent_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
+                            const double* edges, const double* sigma, double doppler, const double* dflux, const double* dreference,
+                            double* out, double* dout_velocity, double* dout_lsf, double* dout_flux);
+/* r, dr/dx and dr/d ln sigma of the pixel response point by point, as the tangent's loop evaluates them (obs_response and
+ * obs_response_grad with sigma sqrt 2 rounded as there): n values of (e0, e1, x, sigma) -> three arrays of n.  For tests.
+ * Stage name: "k_observe_response_grad". */
+int sdx_observe_response_grad_dev(sdx_ctx* ctx, int64_t n, const double* e0, const double* e1, const double* x, const double* sigma,
+                                  double* out_r, double* out_rx, double* out_rs);
+int sdx_observe_response_grad_f64(sdx_ctx* ctx, int64_t n, const double* e0, const double* e1, const double* x, const double* sigma,
+                                  double* out_r, double* out_rx, double* out_rs);
+/* sdx_rotate_dev with its derivative to the limb-darkening coefficient from the same pass (k_rotate_tangent: k_rotate's body with a
+ * compile-time flag; rot_weight stays the one place where a pair is included and K is rounded).  K is linear in eps, so with the
+ * sqrt(q_ij) and q_ij of the forward weight
+ *     dw_ij = (-2 sqrt(q_ij) + (pi / 2) q_ij) h_j,      dout_eps[i] = (sum_j dw_ij flux[j] - out[i] sum_j dw_ij) / den_i,
+ * dout_eps_reference likewise with reference and out_reference: d out / d eps, exact (the windows do not depend on eps).  out and
+ * out_reference are sdx_rotate_dev's bit for bit.  !(V > 0) copies and writes zeros to the derivative outputs.  out and dout_eps are
+ * required, dout_eps_reference is optional and needs a reference; otherwise sdx_rotate_dev's refusals (every output a buffer of its
+ * own) and bounds.  Stage name: "k_rotate_tangent".  The host-buffer twin checks its arguments as sdx_rotate_f64 does. */
+int sdx_rotate_tangent_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, const double* rot_dev,
+                           double* out, double* out_reference, double* dout_eps, double* dout_eps_reference);
+int sdx_rotate_tangent_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, double v_rot,
+                           double limb_darkening, double* out, double* out_reference, double* dout_eps, double* dout_eps_reference);
+
 /* Everything in one call for resident data: pre-pass + line opacity + total (above) + raytrace (F_nu
  * overwritten).  F_nu is [n_depth][ld].  alpha_line_out and total_alphas ([n_depth][ld]) are OPTIONAL outputs (NULL: the
  * plane is never written to HBM — the reference only reads them back through opacities_dict / Opacities.total_alphas;

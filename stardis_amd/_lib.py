@@ -200,6 +200,12 @@ PROTOTYPES = {
     "sdx_macroturbulence_f64": (_int, [_vp, _i64, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
     "sdx_macroturbulence_adjoint_dev": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sdx_macroturbulence_adjoint_f64": (_int, [_vp, _i64, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_observe_tangent_dev": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_observe_tangent_f64": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_observe_response_grad_dev": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_observe_response_grad_f64": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_rotate_tangent_dev": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_rotate_tangent_f64": (_int, [_vp, _i64, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
     "sdx_synthesize_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, C.POINTER(Continuum), _int,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sdx_synthesize_ex_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, C.POINTER(Continuum), _int,

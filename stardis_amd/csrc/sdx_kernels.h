@@ -4639,6 +4639,7 @@ __global__ __launch_bounds__(kBlock) void k_convolve1d_reflect(int64_t n, const 
 // (i1 - i0) / W + 1 trips.
 constexpr int kObsGroup = 8;
 constexpr int kObsShort = 32;
+constexpr double kCKms = 299792.458;
 
 // One round of a (W + 1)-ary search for the first index in [lo, hi) at which a predicate that holds on a prefix fails: lane t of the
 // pixel's W probes p = lo + (t + 1) chunk - 1, chunk = ceil((hi - lo) / (W + 1)).
@@ -4695,17 +4696,37 @@ __device__ __forceinline__ double obs_response(double e0, double e1, double x, d
     return mul_rn(0.5, sub_rn(erf(b), erf(a)));
 }
 
-// What a wave of k_observe's mapping sums for its pixel(s): num = sum_i w_ij flux[i] (flux = nullptr: not formed) and den = sum_i w_ij g_i
-// over the window, closed by the butterfly, in every lane of the pixel.  false: the wave has no pixel and leaves.
-struct ObsPixel {
+// The two partials of obs_response that the instrument's tangent needs, with a' = (e0 - x) / sigma, b' = (e1 - x) / sigma and phi the unit
+// normal density:  rx = dr/dx = (phi(a') - phi(b')) / sigma,   rs = dr/d ln sigma = a' phi(a') - b' phi(b').  In the kernel's a = a' / sqrt 2,
+// b = b' / sqrt 2:  phi(a') - phi(b') = G / sqrt(2 pi),  G = e^(-a^2) - e^(-b^2).  G cancels for a pixel much narrower than sigma and where
+// both edges lie in one tail, so it is formed from the exponential of the NEARER edge (the smaller |.|) and expm1 of -(|a^2 - b^2|),
+// a^2 - b^2 = (a - b)(a + b) with a - b from e0 - e1 and a + b from (e0 - x) + (e1 - x): each a difference of neighbours, then one
+// division.  rs sqrt(pi) = a e^(-a^2) - b e^(-b^2) = near G + (a - b) e^(-far^2): the product rule over the same two differences.
+__device__ __forceinline__ void obs_response_grad(double e0, double e1, double x, double s2, double& rx, double& rs)
+{
+    const double da = sub_rn(e0, x), db = sub_rn(e1, x);
+    const double m = sub_rn(e0, e1) / s2, p = add_rn(da, db) / s2;  // a - b, a + b
+    const bool first = p >= 0.0;                                    // |a| <= |b|
+    const double near = (first ? da : db) / s2, far = (first ? db : da) / s2;
+    const double d = mul_rn(m, p);  // a^2 - b^2: <= 0 where `first`
+    const double en = exp(-mul_rn(near, near)), ef = exp(-mul_rn(far, far));
+    const double g = mul_rn(en, expm1(first ? d : -d));  // e^(-far^2) - e^(-near^2)
+    const double G = first ? -g : g;
+    rx = mul_rn(G, kInvSqrtPi) / s2;
+    rs = mul_rn(add_rn(mul_rn(near, G), mul_rn(m, ef)), kInvSqrtPi);
+}
+
+// The pixel(s) of a wave in k_observe's mapping and the window each searched: what obs_pixel_sums and k_observe_tangent share.
+// false: the wave has no pixel and leaves.
+struct ObsWindow {
     int64_t pj;  // the lane's pixel (may lie behind n_pix in the last group: nothing is searched, nothing may be written)
-    int t;       // the lane's index among the pixel's W lanes
+    int W, t;    // the pixel's lanes and the lane's index among them
     bool covered;
-    double num, den;
+    double D, e0, e1, s2;
+    int64_t i0, i1;
 };
-__device__ __forceinline__ bool obs_pixel_sums(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
-                                               const double* __restrict__ ref, int64_t n_pix, const double* __restrict__ edges,
-                                               const double* __restrict__ sigma, const double* __restrict__ doppler, ObsPixel& p)
+__device__ __forceinline__ bool obs_pixel_window(int64_t n, const double* __restrict__ lam, int64_t n_pix, const double* __restrict__ edges,
+                                                 const double* __restrict__ sigma, const double* __restrict__ doppler, ObsWindow& q)
 {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
@@ -4733,17 +4754,42 @@ __device__ __forceinline__ bool obs_pixel_sums(int64_t n, const double* __restri
     const bool covered = pj < n_pix && lo >= x_first && hi <= x_last;
     int64_t i0, i1;
     obs_windows(lam, lam, n, D, lo, hi, covered, W, lane, i0, i1);
+    q = ObsWindow{pj, W, t, covered, D, e0, e1, s2, i0, i1};
+    return true;
+}
+// point i of the window: x = its shifted wavelength, h = its trapezoid weight, -> r, the pixel's response to it (w_ij = r h)
+__device__ __forceinline__ double obs_point(int64_t n, const double* __restrict__ lam, int64_t i, const ObsWindow& q, double& x, double& h)
+{
+    x = mul_rn(lam[i], q.D);
+    const double below = mul_rn(lam[i > 0 ? i - 1 : 0], q.D), above = mul_rn(lam[i < n - 1 ? i + 1 : n - 1], q.D);
+    h = mul_rn(sub_rn(above, below), 0.5);
+    return obs_response(q.e0, q.e1, x, q.s2);
+}
 
+// What a wave of k_observe's mapping sums for its pixel(s): num = sum_i w_ij flux[i] (flux = nullptr: not formed) and den = sum_i w_ij g_i
+// over the window, closed by the butterfly, in every lane of the pixel.  false: the wave has no pixel and leaves.
+struct ObsPixel {
+    int64_t pj;  // the lane's pixel (may lie behind n_pix in the last group: nothing is searched, nothing may be written)
+    int t;       // the lane's index among the pixel's W lanes
+    bool covered;
+    double num, den;
+};
+__device__ __forceinline__ bool obs_pixel_sums(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                               const double* __restrict__ ref, int64_t n_pix, const double* __restrict__ edges,
+                                               const double* __restrict__ sigma, const double* __restrict__ doppler, ObsPixel& p)
+{
+    ObsWindow q;
+    if (!obs_pixel_window(n, lam, n_pix, edges, sigma, doppler, q)) return false;
     double num = 0.0, den = 0.0;
-    for (int64_t i = i0 + t; i < i1; i += W) {
-        const double x = mul_rn(lam[i], D);
-        const double below = mul_rn(lam[i > 0 ? i - 1 : 0], D), above = mul_rn(lam[i < n - 1 ? i + 1 : n - 1], D);
-        const double w = mul_rn(obs_response(e0, e1, x, s2), mul_rn(sub_rn(above, below), 0.5));
+    for (int64_t i = q.i0 + q.t; i < q.i1; i += q.W) {
+        double x, h;
+        const double r = obs_point(n, lam, i, q, x, h);
+        const double w = mul_rn(r, h);
         if (flux) num = add_rn(num, mul_rn(w, flux[i]));
         den = add_rn(den, ref ? mul_rn(w, ref[i]) : w);
     }
-    for (int off = W >> 1; off > 0; off >>= 1) num = add_rn(num, __shfl_xor(num, off)), den = add_rn(den, __shfl_xor(den, off));
-    p = ObsPixel{pj, t, covered, num, den};
+    for (int off = q.W >> 1; off > 0; off >>= 1) num = add_rn(num, __shfl_xor(num, off)), den = add_rn(den, __shfl_xor(den, off));
+    p = ObsPixel{q.pj, q.t, q.covered, num, den};
     return true;
 }
 
@@ -4755,6 +4801,87 @@ __global__ __launch_bounds__(kBlock) void k_observe(int64_t n, const double* __r
     ObsPixel p;
     if (!obs_pixel_sums(n, lam, flux, ref, n_pix, edges, sigma, doppler, p)) return;
     if (p.t == 0 && p.pj < n_pix) out[p.pj] = p.covered ? p.num / p.den : __longlong_as_double(0x7ff8000000000000LL);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The tangent of the instrument model (include/stardis_hip.h, sdx_observe_tangent_dev): k_observe's pass over k_observe's windows
+// (obs_pixel_window, obs_point: the same mapping, search, covered, weights and order of the sums, so `out` is k_observe's bit for bit),
+// which also forms, per pixel, with w_ij = r_ij h_i,
+//     d w / d ln D     = (x_i dr/dx + r) h_i       (h_i scales with D),        d w / d ln sigma_j = (dr/d ln sigma) h_i      (obs_response_grad),
+//     dout_p = (sum_i d_p w_ij flux_i - out_j sum_i d_p w_ij g_i) / den_j      for p = ln D and p = ln sigma,
+//     dout_velocity = dout_lnD (D^2 + 1)^2 / (4 D^2 c)  per km/s  (d ln D / dv of D = sqrt((1 + beta) / (1 - beta)), from the D in device memory),
+//     dout_flux = (sum_i w_ij dflux_i - out_j sum_i w_ij dref_i) / den_j        (the tangent of the quotient; dref = nullptr: no second term).
+// The windows and `covered` are FIXED: a point entering a window brings 1e-15 of the sum.  An uncovered pixel is NaN in every output.  The
+// parameter sums are formed only where dout_velocity or dout_lsf is asked for, the tangent sums only with dflux.  No floating-point
+// atomics; a butterfly closes every sum.
+//
+// Whatever the arrays hold (NaN, unordered values, sigma <= 0): the search and the loop are k_observe's own — indices inside a bracket
+// within [0, n), a window [i0, i1) with 0 <= i0 <= i1 <= n, at most (i1 - i0) / W + 1 trips per lane — and the loop reads lam at i - 1, i,
+// i + 1 clamped to [0, n) and flux, ref, dflux, dref at i alone; a lane writes only at its own pixel pj < n_pix.
+__global__ __launch_bounds__(kBlock) void k_observe_tangent(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                                            const double* __restrict__ ref, int64_t n_pix, const double* __restrict__ edges,
+                                                            const double* __restrict__ sigma, const double* __restrict__ doppler,
+                                                            const double* __restrict__ dflux, const double* __restrict__ dref,
+                                                            double* __restrict__ out, double* __restrict__ dout_v, double* __restrict__ dout_s,
+                                                            double* __restrict__ dout_f)
+{
+    ObsWindow q;
+    if (!obs_pixel_window(n, lam, n_pix, edges, sigma, doppler, q)) return;
+    const bool params = dout_v != nullptr || dout_s != nullptr;
+    double num = 0.0, den = 0.0, nD = 0.0, dD = 0.0, nS = 0.0, dS = 0.0, tF = 0.0, tG = 0.0;
+    for (int64_t i = q.i0 + q.t; i < q.i1; i += q.W) {
+        double x, h;
+        const double r = obs_point(n, lam, i, q, x, h);
+        const double w = mul_rn(r, h), f = flux[i], g = ref ? ref[i] : 1.0;
+        num = add_rn(num, mul_rn(w, f));
+        den = add_rn(den, ref ? mul_rn(w, g) : w);
+        if (params) {
+            double rx, rs;
+            obs_response_grad(q.e0, q.e1, x, q.s2, rx, rs);
+            const double wD = mul_rn(add_rn(mul_rn(x, rx), r), h), wS = mul_rn(rs, h);
+            nD = add_rn(nD, mul_rn(wD, f)), dD = add_rn(dD, ref ? mul_rn(wD, g) : wD);
+            nS = add_rn(nS, mul_rn(wS, f)), dS = add_rn(dS, ref ? mul_rn(wS, g) : wS);
+        }
+        if (dflux) tF = add_rn(tF, mul_rn(w, dflux[i]));
+        if (dref) tG = add_rn(tG, mul_rn(w, dref[i]));
+    }
+    for (int off = q.W >> 1; off > 0; off >>= 1) {
+        num = add_rn(num, __shfl_xor(num, off)), den = add_rn(den, __shfl_xor(den, off));
+        if (params) {
+            nD = add_rn(nD, __shfl_xor(nD, off)), dD = add_rn(dD, __shfl_xor(dD, off));
+            nS = add_rn(nS, __shfl_xor(nS, off)), dS = add_rn(dS, __shfl_xor(dS, off));
+        }
+        if (dflux) tF = add_rn(tF, __shfl_xor(tF, off));
+        if (dref) tG = add_rn(tG, __shfl_xor(tG, off));
+    }
+    if (q.t != 0 || q.pj >= n_pix) return;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const double o = num / den;
+    if (out) out[q.pj] = q.covered ? o : nan;
+    if (dout_v) {
+        const double D2 = mul_rn(q.D, q.D), up = add_rn(D2, 1.0);
+        const double per_kms = mul_rn(up, up) / mul_rn(mul_rn(4.0, D2), kCKms);  // d ln D / dv
+        dout_v[q.pj] = q.covered ? mul_rn(sub_rn(nD, mul_rn(o, dD)) / den, per_kms) : nan;
+    }
+    if (dout_s) dout_s[q.pj] = q.covered ? sub_rn(nS, mul_rn(o, dS)) / den : nan;
+    if (dout_f) dout_f[q.pj] = q.covered ? (dref ? sub_rn(tF, mul_rn(o, tG)) : tF) / den : nan;
+}
+
+// obs_response and obs_response_grad element-wise, as k_observe_tangent's loop calls them (s2 = sigma sqrt 2 rounded as there):
+// r, dr/dx and dr/d ln sigma per point (tests/test_gpu_observe_tangent.py judges them point by point)
+__global__ __launch_bounds__(kBlock) void k_observe_response_grad(int64_t n, const double* __restrict__ e0, const double* __restrict__ e1,
+                                                                  const double* __restrict__ x, const double* __restrict__ sigma,
+                                                                  double* __restrict__ out_r, double* __restrict__ out_rx,
+                                                                  double* __restrict__ out_rs)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const double s2 = mul_rn(sigma[i], 1.4142135623730951);
+    double rx, rs;
+    obs_response_grad(e0[i], e1[i], x[i], s2, rx, rs);
+    out_r[i] = obs_response(e0[i], e1[i], x[i], s2);
+    out_rx[i] = rx;
+    out_rs[i] = rs;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4928,6 +5055,10 @@ __global__ __launch_bounds__(kBlock) void k_observe_adjoint(int64_t n, const dou
 //     out_i = (sum_j w_ij flux_j) / (sum_j w_ij)   over the included j: a window that reaches past an end of the grid sums what exists.
 // !(V > 0) copies.  rot_weight is the ONE place where reach, y, q, K and w are rounded and a pair is included or not: the forward
 // kernel, the adjoint's denominators and the adjoint's gather call it, so all three hold the same weights bit for bit.
+// k_rotate_tangent is the forward kernel's body with a compile-time flag (rotate_body<true>): rot_weight also hands out dw_ij = d w_ij /
+// d eps = (-2 sqrt(q_ij) + (pi / 2) q_ij) h_j, and dout_i = (sum_j dw_ij flux_j - out_i sum_j dw_ij) / den_i from the same pass.  There is
+// no d / dV: dK / d ln V = y^2 (2 (1 - eps) / sqrt(q) + pi eps), and the trapezoid sum has a square-root kink in V wherever a point enters
+// a window.
 //
 // k_observe's mapping: points in groups of kObsGroup, eight lanes per point where no point of the group expects more than kObsShort
 // points in its window at the grid's MEAN spacing (2 beta lam_i (n - 1) / (lam_{n-1} - lam_0)), a wave per point otherwise; either
@@ -4942,7 +5073,6 @@ __global__ __launch_bounds__(kBlock) void k_observe_adjoint(int64_t n, const dou
 // Whatever the arrays hold (NaN, unordered values, any V and eps): a search reads only inside its bracket within [0, n) and shrinks it
 // at least W + 1 times per round, a window is [i0, i1) with 0 <= i0 <= i1 <= n, a lane makes at most (i1 - i0) / W + 1 trips and reads
 // lam, flux, ref or a at j - 1, j, j + 1 clamped to [0, n) alone.
-constexpr double kCKms = 299792.458;
 constexpr double kHalfPi = 1.5707963267948966;
 
 struct RotProfile {
@@ -4954,8 +5084,9 @@ __device__ __forceinline__ RotProfile rot_profile(const double* __restrict__ rot
     const double V = rot[0], eps = rot[1];
     return RotProfile{V / kCKms, mul_rn(2.0, sub_rn(1.0, eps)), mul_rn(kHalfPi, eps), V > 0.0};
 }
-// point i's weight for point j (self: j == i), h = the trapezoid weight of j; false: i does not include j
-__device__ __forceinline__ bool rot_weight(const RotProfile& r, double lam_i, double lam_j, bool self, double h, double& w)
+// point i's weight for point j (self: j == i), h = the trapezoid weight of j; false: i does not include j.  dw (nullptr: not formed): d w /
+// d eps = (-2 sqrt(q) + (pi / 2) q) h from the same sqrt(q) and q (K is linear in eps; bounded, unlike dK / dV with its 1 / sqrt(q))
+__device__ __forceinline__ bool rot_weight(const RotProfile& r, double lam_i, double lam_j, bool self, double h, double& w, double* dw = nullptr)
 {
     double q = 1.0;
     if (!self) {
@@ -4964,7 +5095,9 @@ __device__ __forceinline__ bool rot_weight(const RotProfile& r, double lam_i, do
         q = sub_rn(1.0, mul_rn(y, y));
         if (!(lo <= lam_j && lam_j <= hi && q > 0.0)) return false;
     }
-    w = mul_rn(add_rn(mul_rn(r.c_sqrt, __dsqrt_rn(q)), mul_rn(r.c_q, q)), h);
+    const double root = __dsqrt_rn(q);
+    w = mul_rn(add_rn(mul_rn(r.c_sqrt, root), mul_rn(r.c_q, q)), h);
+    if (dw) *dw = mul_rn(add_rn(mul_rn(-2.0, root), mul_rn(kHalfPi, q)), h);
     return true;
 }
 __device__ __forceinline__ double rot_trapezoid(const double* __restrict__ lam, int64_t n, int64_t j)
@@ -5008,10 +5141,11 @@ __device__ __forceinline__ void rot_candidates(double lj, double b, double& lo, 
 }
 
 // What the point's lanes sum: num = sum_j w_ij flux[j], numr = sum_j w_ij ref[j] (nullptr: not formed), den = sum_j w_ij, closed by the
-// butterfly, in every lane of the point.  Not called where !(V > 0).
+// butterfly, in every lane of the point; with dsums (three doubles; nullptr: not formed) the same three sums of dw_ij = d w_ij / d eps.
+// Not called where !(V > 0).
 __device__ __forceinline__ void rot_point_sums(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
                                                const double* __restrict__ ref, const RotProfile& r, const RotLane& m, double& num, double& numr,
-                                               double& den)
+                                               double& den, double* dsums = nullptr)
 {
     const int64_t i = m.on ? m.pi : n - 1;
     const double li = lam[i];
@@ -5019,20 +5153,35 @@ __device__ __forceinline__ void rot_point_sums(int64_t n, const double* __restri
     int64_t i0, i1;
     obs_windows(lam, lam, n, 1.0, sub_rn(li, reach), add_rn(li, reach), m.on, m.W, m.lane, i0, i1);
     num = 0.0, numr = 0.0, den = 0.0;
+    double dnum = 0.0, dnumr = 0.0, dden = 0.0;
     for (int64_t j = i0 + m.t; j < i1; j += m.W) {
-        double w;
-        if (!rot_weight(r, li, lam[j], j == i, rot_trapezoid(lam, n, j), w)) continue;
+        double w, dw;
+        if (!rot_weight(r, li, lam[j], j == i, rot_trapezoid(lam, n, j), w, dsums ? &dw : nullptr)) continue;
         if (flux) num = add_rn(num, mul_rn(w, flux[j]));
         if (ref) numr = add_rn(numr, mul_rn(w, ref[j]));
         den = add_rn(den, w);
+        if (dsums) {
+            if (flux) dnum = add_rn(dnum, mul_rn(dw, flux[j]));
+            if (ref) dnumr = add_rn(dnumr, mul_rn(dw, ref[j]));
+            dden = add_rn(dden, dw);
+        }
     }
     for (int off = m.W >> 1; off > 0; off >>= 1)
         num = add_rn(num, __shfl_xor(num, off)), numr = add_rn(numr, __shfl_xor(numr, off)), den = add_rn(den, __shfl_xor(den, off));
+    if (dsums) {
+        for (int off = m.W >> 1; off > 0; off >>= 1)
+            dnum = add_rn(dnum, __shfl_xor(dnum, off)), dnumr = add_rn(dnumr, __shfl_xor(dnumr, off)), dden = add_rn(dden, __shfl_xor(dden, off));
+        dsums[0] = dnum, dsums[1] = dnumr, dsums[2] = dden;
+    }
 }
 
-__global__ __launch_bounds__(kBlock) void k_rotate(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
-                                                   const double* __restrict__ ref, const double* __restrict__ rot, double* __restrict__ out,
-                                                   double* __restrict__ out_ref)
+// k_rotate (kDeriv false: dout, dout_ref unused) and k_rotate_tangent (kDeriv true): with the derivative,
+//     dout_i = (sum_j dw_ij flux_j - out_i sum_j dw_ij) / den_i = d out_i / d eps   (the windows do not depend on eps: exact),
+// dout_ref likewise with ref and out_ref (nullptr: not written); !(V > 0): a copy, and zeros
+template <bool kDeriv>
+__device__ __forceinline__ void rotate_body(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                            const double* __restrict__ ref, const double* __restrict__ rot, double* __restrict__ out,
+                                            double* __restrict__ out_ref, double* __restrict__ dout, double* __restrict__ dout_ref)
 {
     const RotProfile r = rot_profile(rot);
     RotLane m;
@@ -5041,14 +5190,38 @@ __global__ __launch_bounds__(kBlock) void k_rotate(int64_t n, const double* __re
         if (m.t == 0 && m.on) {
             out[m.pi] = flux[m.pi];
             if (ref) out_ref[m.pi] = ref[m.pi];
+            if (kDeriv) {
+                dout[m.pi] = 0.0;
+                if (dout_ref) dout_ref[m.pi] = 0.0;
+            }
         }
         return;
     }
-    double num, numr, den;
-    rot_point_sums(n, lam, flux, ref, r, m, num, numr, den);
+    double num, numr, den, d[3];
+    rot_point_sums(n, lam, flux, ref, r, m, num, numr, den, kDeriv ? d : nullptr);
     if (m.t != 0 || !m.on) return;
-    out[m.pi] = num / den;
-    if (ref) out_ref[m.pi] = numr / den;
+    const double dnum = d[0], dnumr = d[1], dden = d[2];
+    const double o = num / den;
+    out[m.pi] = o;
+    if (kDeriv) dout[m.pi] = sub_rn(dnum, mul_rn(o, dden)) / den;
+    if (ref) {
+        const double g = numr / den;
+        out_ref[m.pi] = g;
+        if (kDeriv && dout_ref) dout_ref[m.pi] = sub_rn(dnumr, mul_rn(g, dden)) / den;
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_rotate(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                                   const double* __restrict__ ref, const double* __restrict__ rot, double* __restrict__ out,
+                                                   double* __restrict__ out_ref)
+{
+    rotate_body<false>(n, lam, flux, ref, rot, out, out_ref, nullptr, nullptr);
+}
+__global__ __launch_bounds__(kBlock) void k_rotate_tangent(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                                           const double* __restrict__ ref, const double* __restrict__ rot,
+                                                           double* __restrict__ out, double* __restrict__ out_ref, double* __restrict__ dout,
+                                                           double* __restrict__ dout_ref)
+{
+    rotate_body<true>(n, lam, flux, ref, rot, out, out_ref, dout, dout_ref);
 }
 
 // a[i] = u[i] / den_i, a_ref[i] = u_ref[i] / den_i (u_ref = nullptr: none); !(V > 0): den = 1

@@ -2749,6 +2749,118 @@ int sdx_observe_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double
     return io.finish();
 }
 
+// ---- the tangent of the instrument model (k_observe_tangent): k_observe's launch geometry, one pass over the same windows ------
+static int observe_tangent_check(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
+                                 const double* edges, const double* sigma, const double* dflux, const double* dreference, const double* out,
+                                 const double* dout_velocity, const double* dout_lsf, const double* dout_flux)
+{
+    REQUIRE(ctx && n_pix >= 0, "observe_tangent: null context or n_pix < 0");
+    if (n_pix == 0) return SDX_OK;
+    REQUIRE(n >= 2, "observe_tangent: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && flux && edges && sigma, "observe_tangent: null pointer (lambdas, flux, edges and sigma are required)");
+    REQUIRE(reference || !dreference, "observe_tangent: dreference needs a reference");
+    REQUIRE(!dflux == !dout_flux, "observe_tangent: dflux and dout_flux go together");
+    const double* const ins[7] = {lambdas, flux, reference, edges, sigma, dflux, dreference};
+    const double* const outs[4] = {out, dout_velocity, dout_lsf, dout_flux};
+    for (int a = 0; a < 4; ++a) {
+        if (!outs[a]) continue;
+        for (int b = 0; b < 7; ++b) REQUIRE(outs[a] != ins[b], "observe_tangent: not in place (an output must not be one of the inputs)");
+        for (int b = a + 1; b < 4; ++b) REQUIRE(outs[a] != outs[b], "observe_tangent: the outputs must be buffers of their own");
+    }
+    return SDX_OK;
+}
+
+int sdx_observe_tangent_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
+                            const double* edges, const double* sigma, const double* doppler_dev, const double* dflux,
+                            const double* dreference, double* out, double* dout_velocity, double* dout_lsf, double* dout_flux)
+{
+    int rc;
+    if ((rc = observe_tangent_check(ctx, n, lambdas, flux, reference, n_pix, edges, sigma, dflux, dreference, out, dout_velocity, dout_lsf, dout_flux)))
+        return rc;
+    if (n_pix == 0 || !(out || dout_velocity || dout_lsf || dout_flux)) return SDX_OK;
+    REQUIRE((n_pix + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "observe_tangent: too many pixels for one launch");
+    {
+        // one wave per pixel (the last group's waves included: a short group is done by its first wave alone)
+        const int64_t waves = (n_pix + kObsGroup - 1) / kObsGroup * kObsGroup;
+        LaunchScope ls(ctx, "k_observe_tangent");
+        hipLaunchKernelGGL(k_observe_tangent, dim3((unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, ctx->stream, n, lambdas,
+                           flux, reference, n_pix, edges, sigma, doppler_dev, dflux, dflux ? dreference : nullptr, out, dout_velocity, dout_lsf,
+                           dout_flux);
+    }
+    return check_launch("k_observe_tangent");
+}
+
+int sdx_observe_tangent_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
+                            const double* edges, const double* sigma, double doppler, const double* dflux, const double* dreference,
+                            double* out, double* dout_velocity, double* dout_lsf, double* dout_flux)
+{
+    int rc;
+    if ((rc = observe_tangent_check(ctx, n, lambdas, flux, reference, n_pix, edges, sigma, dflux, dreference, out, dout_velocity, dout_lsf, dout_flux)))
+        return rc;
+    if (n_pix == 0) return SDX_OK;
+    if ((rc = observe_host_check(n, lambdas, n_pix, edges, sigma, doppler))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8, pix = (size_t)n_pix * f8;
+    const double *d_l, *d_f, *d_r, *d_e, *d_s, *d_D, *d_df, *d_dr;
+    double *d_o, *d_v, *d_k, *d_t;
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(flux, grid, &d_f);
+    plan.in(reference, grid, &d_r);
+    plan.in(edges, (size_t)(n_pix + 1) * f8, &d_e);
+    plan.in(sigma, pix, &d_s);
+    plan.in(&doppler, f8, &d_D);
+    plan.in(dflux, grid, &d_df);
+    plan.in(dreference, grid, &d_dr);
+    plan.out(out, pix, &d_o);
+    plan.out(dout_velocity, pix, &d_v);
+    plan.out(dout_lsf, pix, &d_k);
+    plan.out(dout_flux, pix, &d_t);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_observe_tangent_dev(ctx, n, d_l, d_f, d_r, n_pix, d_e, d_s, d_D, d_df, d_dr, d_o, d_v, d_k, d_t))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+// the pixel response and its two partials, point by point (k_observe_response_grad): what the tangent's loop evaluates
+int sdx_observe_response_grad_dev(sdx_ctx* ctx, int64_t n, const double* e0, const double* e1, const double* x, const double* sigma,
+                                  double* out_r, double* out_rx, double* out_rs)
+{
+    REQUIRE(ctx && n >= 0 && (n == 0 || (e0 && e1 && x && sigma && out_r && out_rx && out_rs)), "observe_response_grad: bad arguments");
+    if (n == 0) return SDX_OK;
+    {
+        LaunchScope ls(ctx, "k_observe_response_grad");
+        hipLaunchKernelGGL(k_observe_response_grad, dim3(blocks1(n)), dim3(kBlock), 0, ctx->stream, n, e0, e1, x, sigma, out_r, out_rx, out_rs);
+    }
+    return check_launch("k_observe_response_grad");
+}
+
+int sdx_observe_response_grad_f64(sdx_ctx* ctx, int64_t n, const double* e0, const double* e1, const double* x, const double* sigma,
+                                  double* out_r, double* out_rx, double* out_rs)
+{
+    REQUIRE(ctx && n >= 0 && (n == 0 || (e0 && e1 && x && sigma && out_r && out_rx && out_rs)), "observe_response_grad: bad arguments");
+    if (n == 0) return SDX_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n * sizeof(double);
+    const double *d_e0, *d_e1, *d_x, *d_s;
+    double *d_r, *d_rx, *d_rs;
+    HostPlan plan;
+    plan.in(e0, bytes, &d_e0);
+    plan.in(e1, bytes, &d_e1);
+    plan.in(x, bytes, &d_x);
+    plan.in(sigma, bytes, &d_s);
+    plan.out(out_r, bytes, &d_r);
+    plan.out(out_rx, bytes, &d_rx);
+    plan.out(out_rs, bytes, &d_rs);
+    HostIo io{ctx};
+    int rc;
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_observe_response_grad_dev(ctx, n, d_e0, d_e1, d_x, d_s, d_r, d_rx, d_rs))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
 // ---- the adjoint of the instrument model: pixel weights pulled back to the grid (k_observe_adjoint) ---------------------------
 // Everything is checked before anything is enqueued.  Four launches under the stage name k_observe_adjoint: the per-pixel factors, the
 // two scans (the tiles' partials, then the tiles), the gather per grid point.
@@ -2915,6 +3027,68 @@ int sdx_rotate_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double*
     HostIo io{ctx};
     if ((rc = io.stage(plan))) return rc;
     if ((rc = sdx_rotate_dev(ctx, n, d_l, d_f, d_r, d_rot, d_o, d_or))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+// ---- rotation with its derivative to the limb-darkening coefficient (k_rotate_tangent: k_rotate's body with the derivative flag) ----
+static int rotate_tangent_check(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, const double* out,
+                                const double* out_reference, const double* dout_eps, const double* dout_eps_reference)
+{
+    REQUIRE(ctx, "rotate_tangent: null context");
+    REQUIRE(n >= 2, "rotate_tangent: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && flux && out && dout_eps, "rotate_tangent: null pointer (lambdas, flux, out and dout_eps are required)");
+    REQUIRE(!reference == !out_reference, "rotate_tangent: reference and out_reference go together");
+    REQUIRE(!dout_eps_reference || reference, "rotate_tangent: dout_eps_reference needs a reference");
+    const double* const ins[3] = {lambdas, flux, reference};
+    const double* const outs[4] = {out, out_reference, dout_eps, dout_eps_reference};
+    for (int a = 0; a < 4; ++a) {
+        if (!outs[a]) continue;
+        for (int b = 0; b < 3; ++b) REQUIRE(outs[a] != ins[b], "rotate_tangent: not in place (an output must not be one of the inputs)");
+        for (int b = a + 1; b < 4; ++b) REQUIRE(outs[a] != outs[b], "rotate_tangent: the outputs must be buffers of their own");
+    }
+    return SDX_OK;
+}
+
+int sdx_rotate_tangent_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, const double* rot_dev,
+                           double* out, double* out_reference, double* dout_eps, double* dout_eps_reference)
+{
+    int rc;
+    if ((rc = rotate_tangent_check(ctx, n, lambdas, flux, reference, out, out_reference, dout_eps, dout_eps_reference))) return rc;
+    REQUIRE(rot_dev, "rotate_tangent: null pointer (rot_dev is required)");
+    REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "rotate_tangent: too many points for one launch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    {
+        LaunchScope ls(ctx, "k_rotate_tangent");
+        hipLaunchKernelGGL(k_rotate_tangent, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, flux, reference, rot_dev, out,
+                           out_reference, dout_eps, dout_eps_reference);
+    }
+    return check_launch("k_rotate_tangent");
+}
+
+int sdx_rotate_tangent_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, double v_rot,
+                           double limb_darkening, double* out, double* out_reference, double* dout_eps, double* dout_eps_reference)
+{
+    int rc;
+    if ((rc = rotate_tangent_check(ctx, n, lambdas, flux, reference, out, out_reference, dout_eps, dout_eps_reference))) return rc;
+    if ((rc = rotate_host_check(n, lambdas, v_rot, limb_darkening))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
+    const double pair[2] = {v_rot, limb_darkening};
+    const double *d_l, *d_f, *d_r, *d_rot;
+    double *d_o, *d_or, *d_d, *d_dr;
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(flux, grid, &d_f);
+    plan.in(reference, grid, &d_r);
+    plan.in(pair, 2 * f8, &d_rot);
+    plan.out(out, grid, &d_o);
+    plan.out(out_reference, grid, &d_or);
+    plan.out(dout_eps, grid, &d_d);
+    plan.out(dout_eps_reference, grid, &d_dr);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_rotate_tangent_dev(ctx, n, d_l, d_f, d_r, d_rot, d_o, d_or, d_d, d_dr))) return rc;
     if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }

@@ -780,6 +780,76 @@ class SpectralSynthesizer:
         chi2, c = self._chi2_pixel_weights(data, inverse_variance, normalized)
         return chi2, self.observed_macroturbulence_derivative(c, normalized)
 
+    # -- forward mode: one direction, every pixel ---------------------------------------------------------------------------------
+    def _column_tangent(self, name, v):
+        """a tangent over the columns of F_nu[-1] (host array, DeviceArray or CUDA tensor) -> F_lambda's tangent on the device:
+        the factor nu / lambda of sdx_flux_nu_to_lambda_dev applied"""
+        n = self.n_nu
+        if isinstance(v, _lib.DeviceArray) or hasattr(v, "data_ptr"):
+            _require_f64_buffer(name, v, n)
+            d_v = v
+        else:
+            host = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+            if host.size != n:
+                raise ValueError(f"{name} must hold one value per column of the spectrum ({n}), got {host.size}")
+            d_v = self.ctx.upload(host)
+        out = self.ctx.empty((n,))
+        self.ctx.call("sdx_flux_nu_to_lambda_dev", n, ptr_of(d_v), self.d_nus.ptr, self.d_lambdas.ptr, out.ptr)
+        return out
+
+    def observed_tangent(self, dF_nu, dF_nu_continuum=None, normalized=False):
+        """-> DeviceArray (n_pix,): a tangent dF_nu over the columns of F_nu[-1] — flux_derivative(...)'s dF/d ln(abundance), say —
+        pushed to the detector's pixels at the last step's spectrum: the factor nu / lambda, then Instrument.tangent (rotation,
+        macroturbulence, sdx_observe_tangent_dev).  normalized=True: the tangent of observed_normalized (needs
+        keep_continuum_flux=True), with dF_nu_continuum the tangent of F_nu_continuum[-1] (None: the continuum does not move).
+        NaN where the observed spectrum is NaN.  On demand, after a step."""
+        self._require_instrument()
+        if dF_nu_continuum is not None and not normalized:
+            raise ValueError("dF_nu_continuum enters the normalised spectrum only: pass normalized=True")
+        if normalized:
+            self._require_continuum()
+        d_f = self._column_tangent("dF_nu", dF_nu)
+        d_g = None if dF_nu_continuum is None else self._column_tangent("dF_nu_continuum", dF_nu_continuum)
+        return self.instrument.tangent(self.d_lambdas, self.n_nu, self.d_Flam, d_f, reference=self.d_Fclam if normalized else None,
+                                       dreference=d_g)
+
+    def observed_jacobian(self, wrt, normalized=False):
+        """-> {name: DeviceArray (n_pix,)}: the columns d observed_j / d p (normalized=True: of observed_normalized) of the
+        instrument's parameters at the last step's spectrum — Instrument.parameter_tangents: "v_rad" per km/s, "lsf" per ln of a
+        common factor on sigma (-d / d ln R), "v_mac" per km/s, "limb_darkening" per unit; a single name gives a one-entry dict.  v sin i
+        has no column (see Instrument.parameter_tangents).  On demand, after a step."""
+        self._require_instrument()
+        if normalized:
+            self._require_continuum()
+        return self.instrument.parameter_tangents(self.d_lambdas, self.n_nu, self.d_Flam, reference=self.d_Fclam if normalized else None,
+                                                  wrt=wrt)
+
+    def chi2_instrument_gradient(self, data, inverse_variance, wrt, normalized=False, curvature=False):
+        """-> (chi2, {p: d chi2 / d p}), with curvature=True -> (chi2, gradient, H): chi-square of the last step's observed
+        (normalized=True: observed_normalized) spectrum against data over the pixels chi2_line_gradient uses (NaN, inverse_variance 0
+        and edge_affected pixels left out), its derivative to the instrument parameters named by wrt (observed_jacobian's names and
+        units) and the Gauss-Newton matrix H = 2 J^T W J, H[a][b] = 2 sum_j ivar_j J_ja J_jb in the order of wrt.  The tangent route:
+        the columns J are downloaded and the sums are taken ON THE HOST (math.fsum of the fp64 products: exactly rounded, the same
+        bits everywhere), as observed_macroturbulence_derivative takes its own."""
+        self._require_instrument()
+        names = self.instrument._wrt(wrt)
+        chi2, c = self._chi2_pixel_weights(data, inverse_variance, normalized)
+        ivar =np.ascontiguousarray(inverse_variance, dtype=np.float64).reshape(-1)
+        obs = (self.d_observed_normalized if normalized else self.d_observed).numpy()
+        used = ~np.isnan(obs) & (ivar != 0)
+        if self.instrument.broadens:
+            used &= ~self.instrument.edge_affected(self.lambdas)
+        J = {k: np.where(used, v.numpy(), 0.0) for k, v in self.observed_jacobian(names, normalized).items()}
+        grad = {k: math.fsum(c * J[k]) for k in names}
+        if not curvature:
+            return chi2, grad
+        w = np.where(used, ivar, 0.0)
+        H = np.empty((len(names), len(names)))
+        for ia, a in enumerate(names):  # (the upper triangle, mirrored: symmetric bit for bit)
+            for ib in range(ia, len(names)):
+                H[ia, ib] = H[ib, ia] = 2.0 * math.fsum(w * J[a] * J[names[ib]])
+        return chi2, grad, H
+
     @property
     def observed(self):
         """-> DeviceArray (n_pix,): the last step's spectrum as the instrument records it (`.numpy()` for a host array)."""

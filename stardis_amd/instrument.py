@@ -9,7 +9,11 @@ launch forward, two more transposed.  postprocess.rotation_broadening, which mir
 integer pixel offsets, a rotation profile on a log-uniform grid only.
 With v_mac the radial-tangential macroturbulence zeta (sdx_macroturbulence_dev states the operator) follows the rotation and precedes
 k_observe — the order is rotate -> macroturbulence -> observe, and the adjoint runs it in reverse; both broadenings are convolutions in
-velocity, so on a log-uniform grid the order does not matter, and elsewhere this one is the definition."""
+velocity, so on a log-uniform grid the order does not matter, and elsewhere this one is the definition.
+Forward mode — one direction, every pixel — is Instrument.tangent (the Jacobian-vector product of observe(): sdx_observe_tangent_dev
+behind the broadening stages, which carry a tangent as a (flux, reference) pair of their own) and Instrument.parameter_tangents (the
+columns to the radial velocity, the line-spread function's width, zeta and the limb darkening); both on demand, with scratch of their
+own that an instrument which never asks does not have."""
 import math
 
 import numpy as np
@@ -329,6 +333,192 @@ class Instrument:
                       self.n_pix, self.d_edges.ptr, self.d_sigma.ptr, self.d_doppler.ptr, addr(pixel_weights), addr(nus), addr(out),
                       addr(out_reference))
         return out if out_reference is None else (out, out_reference)
+
+    # -- forward mode: tangents of observe() ----------------------------------------------------------------------------------------
+    PARAMETERS = ("v_rad", "lsf", "v_mac", "limb_darkening")
+
+    def reserve_tangent(self, n):
+        """Size the scratch of tangent() and parameter_tangents() for grids of up to n points now: per broadening stage the tangent
+        pair that goes through it, and one pair for a stage's own parameter derivative.  Made at the first tangent call otherwise;
+        an instrument that never asks has none, and reserve() keeps its sizes.  Without rotation and macroturbulence there is none."""
+        n = int(n)
+        self.reserve(n)
+        if self.broadens and n > getattr(self, "_tangent_n", 0):
+            self._tangent_scratch = tuple(self.ctx.empty((n,)) for _ in range(2 * (self.rotates + self.macroturbulent) + 2))
+            self._tangent_n = n
+
+    def _push(self, d_lambdas, n, dflux, dreference, first_stage=0):
+        """a tangent pair through the broadening stages from first_stage on (0: rotation, 1: macroturbulence), as a (flux, reference)
+        pair of the stages themselves — they are linear in the flux and their denominators do not depend on it — into the tangent
+        scratch -> (dflux, dreference or None) at the pixel stage's input"""
+        k = 0
+        for index, (on, stage) in enumerate(((self.rotates, self.rotate), (self.macroturbulent, self.macroturbulence))):
+            if not on:
+                continue
+            if index >= first_stage:
+                t, t_ref = self._tangent_scratch[2 * k], self._tangent_scratch[2 * k + 1]
+                if dreference is None:
+                    dflux = stage(d_lambdas, dflux, n, out=t)
+                else:
+                    dflux, dreference = stage(d_lambdas, dflux, n, dreference, out=t, out_reference=t_ref)
+            k += 1
+        return dflux, dreference
+
+    def _observe_tangent(self, d_lambdas, n, flux, reference, dflux=None, dreference=None, out=None, dout_velocity=None, dout_lsf=None,
+                         dout_flux=None):
+        addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
+        self.ctx.call("sdx_observe_tangent_dev", int(n), addr(d_lambdas), addr(flux), addr(reference), self.n_pix, self.d_edges.ptr,
+                      self.d_sigma.ptr, self.d_doppler.ptr, addr(dflux), addr(dreference), addr(out), addr(dout_velocity), addr(dout_lsf),
+                      addr(dout_flux))
+
+    def tangent(self, d_lambdas, n, flux, dflux, reference=None, dreference=None, out=None):
+        """The Jacobian-vector product of observe(): the direction (dflux, dreference) of (flux, reference) on the grid -> the
+        DeviceArray (n_pix,) (or `out`) of d observe(flux)_j, or of the normalised spectrum's tangent (sum w dflux - out_j sum w
+        dreference) / den_j with a reference (dreference=None: the reference does not move).  NaN where observe() is NaN.  Rotation
+        and macroturbulence are linear in the flux with denominators that do not depend on it, so the pair goes through each stage
+        as a (flux, reference) pair of rotate() / macroturbulence() — one more launch per stage — and the pixel stage is
+        sdx_observe_tangent_dev's dout_flux.  Device buffers in, enqueued on the context's stream; the scratch is made at the first
+        call or by reserve_tangent(n), so a captured call allocates nothing when `out` is given, and follows set_radial_velocity()."""
+        if dreference is not None and reference is None:
+            raise ValueError("dreference needs a reference")
+        if dflux is None:
+            raise ValueError("tangent() needs dflux, the direction of the flux")
+        out = self.ctx.empty((self.n_pix,)) if out is None else out
+        if self.broadens:
+            self.reserve_tangent(n)
+            res = self.broaden(d_lambdas, flux, n, reference)
+            flux, reference = res if reference is not None else (res, None)
+            dflux, dreference = self._push(d_lambdas, n, dflux, dreference)
+        self._observe_tangent(d_lambdas, n, flux, reference, dflux, dreference, dout_flux=out)
+        return out
+
+    def _wrt(self, wrt):
+        if wrt is None:  # every parameter this instrument has
+            return ("v_rad", "lsf") + (("v_mac",) if self.macroturbulent and self.v_mac > 0.0 else ()) + (
+                ("limb_darkening",) if self.rotates and self.v_rot > 0.0 else ())
+        names = (wrt,) if isinstance(wrt, str) else tuple(wrt)
+        for name in names:
+            if name not in self.PARAMETERS:
+                raise ValueError(f"unknown parameter {name!r}: wrt takes {', '.join(self.PARAMETERS)}")
+        if "v_mac" in names:
+            if not self.macroturbulent:
+                raise RuntimeError("no macroturbulence: construct the Instrument with v_mac=")
+            if not self.v_mac > 0.0:
+                raise ValueError("the derivative to zeta needs zeta > 0 (at zeta = 0 the stage is a copy)")
+        if "limb_darkening" in names:
+            if not self.rotates:
+                raise RuntimeError("no rotation: construct the Instrument with v_rot=")
+            if not self.v_rot > 0.0:
+                raise ValueError("the derivative to the limb darkening needs v_rot > 0 (at v_rot = 0 the stage is a copy)")
+        return names
+
+    def parameter_tangents(self, d_lambdas, n, flux, reference=None, wrt=None):
+        """-> {name: DeviceArray (n_pix,)}: the columns d observe(flux[, reference])_j / d p of the instrument's own parameters at
+        fixed windows, NaN where observe() is NaN.
+          "v_rad"           per km/s of the radial velocity   (sdx_observe_tangent_dev's dout_velocity)
+          "lsf"             per ln kappa of a common factor kappa on every sigma; for a resolving power, -d / d ln R   (dout_lsf)
+          "v_mac"           per km/s of zeta: k_macroturbulence's d / d ln zeta over zeta, through the pixel stage as a tangent
+          "limb_darkening"  per unit of eps: k_rotate_tangent's d / d eps through the macroturbulence and the pixel stage
+        v sin i has no such column: on the trapezoid sum the forward model has a square-root kink in V wherever a point enters a
+        window; a central difference of two observe() calls remains the answer.  wrt=None: every column this instrument has.
+        Unknown names are a ValueError; "v_mac" needs
+        Instrument(v_mac > 0), "limb_darkening" Instrument(v_rot > 0).  On demand: it allocates its outputs (and the tangent scratch
+        at the first call) and runs the stages in front of the pixels again."""
+        names = self._wrt(wrt)
+        res = {name: self.ctx.empty((self.n_pix,)) for name in names}
+        normal = reference is not None
+        if self.broadens:
+            self.reserve_tangent(n)
+        ts = getattr(self, "_tangent_scratch", ())
+        d_par, d_par_ref = (ts[-2], ts[-1] if normal else None) if ts else (None, None)
+        addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
+        f, g = flux, reference
+        eps_f = eps_g = None  # d / d eps at the pixel stage's input
+        if self.rotates:
+            if "limb_darkening" in names:
+                rf, rg = self._scratch[0], self._scratch[1] if normal else None
+                self.ctx.call("sdx_rotate_tangent_dev", int(n), addr(d_lambdas), addr(f), addr(g), self.d_rot.ptr, rf.ptr, addr(rg), d_par.ptr,
+                              addr(d_par_ref))
+                f, g = rf, rg
+                # (through the macroturbulence now: its own derivative takes the pair's place in the scratch below)
+                eps_f, eps_g = self._push(d_lambdas, n, d_par, d_par_ref, first_stage=1)
+            else:
+                r = self.rotate(d_lambdas, f, n, g)
+                f, g = r if normal else (r, None)
+        if self.macroturbulent:
+            want = "v_mac" in names
+            b = self.macroturbulence(d_lambdas, f, n, g, dout=d_par if want else None, dout_reference=d_par_ref if want else None)
+            f, g = b if normal else (b, None)
+            if want:
+                per_ln, zeta = self.ctx.empty((self.n_pix,)), self.ctx.upload(np.full(self.n_pix, self.v_mac))
+                self._observe_tangent(d_lambdas, n, f, g, d_par, d_par_ref, dout_flux=per_ln)
+                self.ctx.call("sdx_divide_dev", self.n_pix, per_ln.ptr, zeta.ptr, res["v_mac"].ptr)
+        if eps_f is not None:
+            self._observe_tangent(d_lambdas, n, f, g, eps_f, eps_g, dout_flux=res["limb_darkening"])
+        if "v_rad" in names or "lsf" in names:
+            self._observe_tangent(d_lambdas, n, f, g, dout_velocity=res.get("v_rad"), dout_lsf=res.get("lsf"))
+        return res
+
+    def tangent_host(self, lambdas, flux, dflux, reference=None, dreference=None):
+        """numpy in, numpy out: tangent() through the host-buffer twins (sdx_rotate_f64, sdx_macroturbulence_f64,
+        sdx_observe_tangent_f64, which check the arrays) -> (n_pix,)."""
+        if dreference is not None and reference is None:
+            raise ValueError("dreference needs a reference")
+        lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
+        _ascending("lambdas", lam)
+        if lam.size < 2:
+            raise ValueError("lambdas must hold at least two points")
+        f, df = _host_vector("flux", flux, lam.size, "grid point"), _host_vector("dflux", dflux, lam.size, "grid point")
+        g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
+        dg = None if dreference is None else _host_vector("dreference", dreference, lam.size, "grid point")
+        if self.broadens:
+            f, g = self._broaden_host(lam, f, g)
+            df, dg = self._broaden_host(lam, df, dg)
+        return self._observe_tangent_host(lam, f, g, df, dg, flux_tangent=True)[0]
+
+    def _observe_tangent_host(self, lam, f, g, df=None, dg=None, velocity=False, lsf=False, flux_tangent=False):
+        host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        outs = [np.empty(self.n_pix) if on else None for on in (flux_tangent, velocity, lsf)]
+        self.ctx.call("sdx_observe_tangent_f64", lam.size, host(lam), host(f), host(g), self.n_pix, host(self.edges), host(self.sigma),
+                      float(self.doppler), host(df), host(dg), None, host(outs[1]), host(outs[2]), host(outs[0]))
+        return outs
+
+    def parameter_tangents_host(self, lambdas, flux, reference=None, wrt=None):
+        """numpy in, numpy out: parameter_tangents() through the host-buffer twins -> {name: (n_pix,)}."""
+        names = self._wrt(wrt)
+        lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
+        _ascending("lambdas", lam)
+        if lam.size < 2:
+            raise ValueError("lambdas must hold at least two points")
+        f = _host_vector("flux", flux, lam.size, "grid point")
+        g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
+        host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        res = {}
+        if self.rotates:
+            if "limb_darkening" in names:
+                o = [np.empty(lam.size) if (g is not None or k % 2 == 0) else None for k in range(4)]
+                self.ctx.call("sdx_rotate_tangent_f64", lam.size, host(lam), host(f), host(g), self.v_rot, self.limb_darkening,
+                              *(host(a) for a in o))
+                bf, bg, tf, tg = o
+                if self.macroturbulent:
+                    bf, bg = (self.macroturbulence_host(lam, bf), None) if bg is None else self.macroturbulence_host(lam, bf, bg)
+                    tf, tg = (self.macroturbulence_host(lam, tf), None) if tg is None else self.macroturbulence_host(lam, tf, tg)
+                res["limb_darkening"] = self._observe_tangent_host(lam, bf, bg, tf, tg, flux_tangent=True)[0]
+            f, g = (self.rotate_host(lam, f), None) if g is None else self.rotate_host(lam, f, g)
+        if self.macroturbulent:
+            if "v_mac" in names:
+                m = self.macroturbulence_host(lam, f, g, derivative=True)
+                f, g, tf, tg = (m[0], None, m[1], None) if g is None else m
+                res["v_mac"] = self._observe_tangent_host(lam, f, g, tf, tg, flux_tangent=True)[0] / self.v_mac
+            else:
+                f, g = (self.macroturbulence_host(lam, f), None) if g is None else self.macroturbulence_host(lam, f, g)
+        if "v_rad" in names or "lsf" in names:
+            _, v, k = self._observe_tangent_host(lam, f, g, velocity="v_rad" in names, lsf="lsf" in names)
+            if v is not None:
+                res["v_rad"] = v
+            if k is not None:
+                res["lsf"] = k
+        return {name: res[name] for name in names}
 
     def adjoint_host(self, lambdas, pixel_weights, flux=None, reference=None, nus=None):
         """numpy in, numpy out: (n,) wavelengths and (n_pix,) pixel weights -> (n,) weights over the grid points; with a reference

@@ -575,3 +575,65 @@ def observe_adjoint(lambdas, pixel_weights, pixel_edges, sigma, v_rad=0.0, flux=
     if v_rad:
         inst.set_radial_velocity(v_rad)
     return inst.adjoint_host(lambdas, pixel_weights, flux, reference, nus)
+
+
+def observe_response_grad(e0, e1, x, sigma, ctx=None):
+    """-> (r, dr/dx, dr/d ln sigma): the Gaussian of width sigma around x integrated from e0 to e1, and its two partial derivatives, point
+    by point through the routines the instrument's tangent evaluates (sdx_observe_response_grad_dev; sdx_kernels.h obs_response,
+    obs_response_grad).  The arguments broadcast."""
+    ctx = ctx or default_context()
+    both = np.broadcast_arrays(_host(e0), _host(e1), _host(x), _host(sigma))
+    shape = both[0].shape
+    d = [ctx.upload(np.ascontiguousarray(v).reshape(-1)) for v in both]
+    out = [ctx.empty((both[0].size,)) for _ in range(3)]
+    ctx.call("sdx_observe_response_grad_dev", both[0].size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, out[0].ptr, out[1].ptr, out[2].ptr)
+    r = tuple(o.numpy().reshape(shape) for o in out)
+    return r if shape else tuple(v[()] for v in r)
+
+
+def rotate_tangent(lambdas, flux, v_rot, limb_darkening=0.6, reference=None, ctx=None):
+    """ops.rotate with its derivative to the limb-darkening coefficient from the same pass (sdx_rotate_tangent_f64) -> (out, dout_eps), or
+    (out, out_reference, dout_eps, dout_eps_reference) with a reference.  v_rot = 0 copies and the derivatives are zeros."""
+    from .instrument import _ascending, _host_vector, rotation_pair
+
+    V, eps = rotation_pair(v_rot, limb_darkening)
+    lam = np.ascontiguousarray(_lib.plain(lambdas), dtype=F8).reshape(-1)
+    _ascending("lambdas", lam)
+    if lam.size < 2:
+        raise ValueError("lambdas must hold at least two points")
+    f = _host_vector("flux", flux, lam.size, "grid point")
+    g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
+    outs = [np.empty(lam.size) if (g is not None or k % 2 == 0) else None for k in range(4)]
+    host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    (ctx or default_context()).call("sdx_rotate_tangent_f64", lam.size, host(lam), host(f), host(g), V, eps, *(host(a) for a in outs))
+    return tuple(a for a in outs if a is not None)
+
+
+def observe_tangent(lambdas, flux, pixel_edges, sigma, v_rad=0.0, reference=None, dflux=None, dreference=None, ctx=None):
+    """The pixel stage's tangents (sdx_observe_tangent_f64) -> a dict of (n_pix,) arrays: "out" (ops.observe's own bits), "v_rad"
+    (d out / d v_rad per km/s), "lsf" (d out / d ln kappa of a common factor on sigma) and, with dflux (and dreference, which needs a
+    reference), "flux": the tangent of out for that direction of (flux, reference).  NaN where out is NaN.  No rotation or
+    macroturbulence here: stardis_amd.instrument.Instrument.tangent and parameter_tangents run the whole chain."""
+    from .instrument import _ascending, _host_vector, doppler_factor, pixel_sigma
+
+    edges, sig = pixel_sigma(pixel_edges, sigma=sigma)
+    lam = np.ascontiguousarray(_lib.plain(lambdas), dtype=F8).reshape(-1)
+    _ascending("lambdas", lam)
+    if lam.size < 2:
+        raise ValueError("lambdas must hold at least two points")
+    if dreference is not None and reference is None:
+        raise ValueError("dreference needs a reference")
+    if dreference is not None and dflux is None:
+        raise ValueError("dreference needs dflux")
+    f = _host_vector("flux", flux, lam.size, "grid point")
+    g, df, dg = (None if a is None else _host_vector(name, a, lam.size, "grid point")
+                 for name, a in (("reference", reference), ("dflux", dflux), ("dreference", dreference)))
+    n_pix = edges.size - 1
+    res = {"out": np.empty(n_pix), "v_rad": np.empty(n_pix), "lsf": np.empty(n_pix)}
+    if df is not None:
+        res["flux"] = np.empty(n_pix)
+    host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    (ctx or default_context()).call("sdx_observe_tangent_f64", lam.size, host(lam), host(f), host(g), n_pix, host(edges), host(sig),
+                                    doppler_factor(v_rad), host(df), host(dg), host(res["out"]), host(res["v_rad"]), host(res["lsf"]),
+                                    host(res.get("flux")))
+    return res
