@@ -745,9 +745,9 @@ int sdx_macroturbulence_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambd
  * rule over the same two differences.  An uncovered pixel is NaN in every output.  `out`, when asked for, is sdx_observe_dev's bit for
  * bit.  fp64, every operation one rounded operation (exp, expm1, erf, erfc: the device library's); no floating-point atomics, the order
  * of every sum follows from the arrays alone: two calls, the replay of a captured graph and the host-buffer twin give the same bits.
- * The derivative to v sin i is NOT offered: Gray's profile ends in a square root, dK/d ln V = y^2 (2 (1 - eps) / sqrt(q) + pi eps), and on
- * the trapezoid sum the forward model has a square-root kink in V wherever a point enters a window; a central difference of two whole
- * steps remains the answer there.  The derivative to eps is bounded and is sdx_rotate_tangent_dev below.
+ * The derivative to v sin i is sdx_rotate_integrated_dev's dout_lnv below, for the cell-integrated rotation profile; the sampled sum of
+ * sdx_rotate_dev has none (Gray's profile ends in a square root, and the trapezoid sum has a square-root kink in V wherever a point enters
+ * a window).  Its derivative to eps is bounded and is sdx_rotate_tangent_dev below.
  * sdx_observe_tangent_dev: device pointers, asynchronous on the context's stream, no allocation, capturable; D is read from device
  * memory when the kernel runs (doppler_dev; NULL: 1) and the velocity factor is formed from it there, so a captured call follows a new
  * velocity.  reference, dflux, dreference and every output are optional (NULL: not read, not formed, not written; the parameter sums
@@ -785,6 +785,59 @@ int sdx_rotate_tangent_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const
                            double* out, double* out_reference, double* dout_eps, double* dout_eps_reference);
 int sdx_rotate_tangent_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, double v_rot,
                            double limb_darkening, double* out, double* out_reference, double* dout_eps, double* dout_eps_reference);
+
+/* ---- the cell-integrated rotation profile: a second rotation mode, with d / d (v sin i) ----
+ * sdx_rotate_dev samples Gray's profile at the grid points.  Here the flux is taken as piecewise linear between the nodes (as
+ * sdx_observe_dev's trapezoid assumes) and the profile K(y) = (2 (1 - eps)) sqrt(q) + ((pi / 2) eps) q, q = 1 - y^2, is integrated against
+ * it exactly, cell by cell: the operator tends to the identity continuously as V -> 0, a node on the profile's edge contributes a cell of
+ * zero length, a linear flux is reproduced at interior points of any grid, and out is differentiable in V.  sdx_rotate_dev is unchanged.
+ * For point i, every operation one correctly rounded fp64 operation (atan2: the device library's), in this order (the device functions
+ * rot_cell, rot_moments, rot_half), beta = V / c, reach_i = lambdas[i] beta, and every cell g = [j, j + 1]:
+ *     y_j = (lambdas[j] - lambdas[i]) / reach_i  (y_i = 0),   c_j = min(max(y_j, -1), 1),   COUNTS(i, g) = c_{j+1} > c_j,
+ *     Delta_g = (lambdas[j+1] - lambdas[j]) / reach_i,      d_g = Delta_g where neither end is clamped, else c_{j+1} - c_j,
+ *     S0, Q0, S1, Q1 = the integrals of sqrt(q), q, y sqrt(q), y q over [c_j, c_{j+1}]: for 0 <= p < s <= 1 (the other half mirrored), with
+ *       u = 1 - y, q = u (1 + y), R = sqrt(q_p) sqrt(q_s), D = d (s + p):
+ *       sin = D / (s sqrt(q_p) + p sqrt(q_s)),   cos = p s + R,   dl = atan2(sin, cos),
+ *       S0 = ((dl - sin dl) + sin (u_p + u_s p + R)) / 2,  dl - sin dl = dl^3 (1/3! - dl^2 (1/5! - ... 1/25!)),
+ *       Q0 = d ((u_p + u_s) - (u_p^2 + u_p u_s + u_s^2) / 3),   S1 = D (q_p + R + q_s) / (3 (sqrt(q_p) + sqrt(q_s))),   Q1 = D (q_p + q_s) / 4
+ *       (sums of non-negative terms: each keeps its relative accuracy for a cell of any width, also one that touches +-1),
+ *     M0_g = c_sqrt S0 + c_q Q0,   M1_g = c_sqrt S1 + c_q Q1,   r_g = (M1_g - y_j M0_g) / Delta_g,   t_g = M1_g / Delta_g,
+ *     den_i = sum_g M0_g,   out[i] = sum_g ((M0_g - r_g) flux[j] + r_g flux[j+1]) / den_i      (W_ij = r_{j-1} + (M0_j - r_j)),
+ *     e_0 = y_0 K(y_0) if -1 < y_0 else 0,   e_1 = y_{n-1} K(y_{n-1}) if y_{n-1} < 1 else 0      (a truncated window's end terms; there
+ *       1 - |y| = (reach_i - |lambdas[end] - lambdas[i]|) / reach_i, the difference first, and q = (1 - |y|)(1 + |y|)),
+ *     dout_lnv[i] = (sum_g t_g (flux[j+1] - flux[j]) + e_0 flux[0] - e_1 flux[n-1] - out[i] (e_0 - e_1)) / den_i = d out[i] / d ln V,
+ *     dout_eps[i] = (sum_g ((dM0_g - dr_g) flux[j] + dr_g flux[j+1]) - out[i] sum_g dM0_g) / den_i, dM0, dr: M0, r with c_sqrt = -2, c_q = pi / 2
+ * over the cells that count; the *_reference outputs likewise with reference.  dout_lnv is EXACT, not "at fixed windows": written over
+ * lambda the domain does not move with V, K(+-1) = 0 removes the boundary terms, and one integration by parts leaves the integral of
+ * K y phi_j' with phi_j' piecewise constant; d / dV = dout_lnv / V.  The cells of point i are those of sdx_rotate_dev's window [i0, i1) and
+ * the partial cell on each side; a window narrower than one spacing still has three weights.  A window that reaches past an end of the
+ * grid is TRUNCATED AND RENORMALISED as sdx_rotate_dev's is.  !(V > 0) is a copy bit for bit, and zeros in the derivative outputs.
+ * Mapping, window search, round-robin over the point's 8 or 64 lanes, ascending order and butterfly are sdx_rotate_dev's; no
+ * floating-point atomics: two calls, the replay of a captured graph and the host-buffer twin give the same bits.
+ * sdx_rotate_integrated_dev: device pointers, asynchronous, no allocation, capturable; rot_dev is sdx_rotate_dev's {V, eps} pair, read
+ * when the kernel runs.  The four derivative outputs are optional (all NULL: not formed, the kernel without them runs).  SDX_ERR_ARG
+ * before anything is enqueued: n < 2, a null required pointer, reference without out_reference or the reverse, a *_reference derivative
+ * without a reference, an output that is one of the inputs or another output.  Contents unchecked as for sdx_rotate_dev: every access
+ * stays inside the arrays (a cell index g has 0 <= g < n - 1) and every loop is bounded by its bracket.  Stage name: "k_rotate_integrated". */
+int sdx_rotate_integrated_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference,
+                              const double* rot_dev, double* out, double* out_reference, double* dout_lnv, double* dout_lnv_reference,
+                              double* dout_eps, double* dout_eps_reference);
+/* The transpose: a_i = u[i] / den_i, w[j] = sum_i W_ij a_i over the i with lambdas[i] in [lambdas[j-1] / (1 + beta), lambdas[j+1] / (1 -
+ * beta)], searched a few 1e-15 wide; rot_cell decides, so the weights are the forward's bit for bit and  sum_i u[i] out[i] = sum_j w[j]
+ * flux[j].  nus, scratch (the rotation adjoint's), refusals and bounds as sdx_rotate_adjoint_dev.  Stage name:
+ * "k_rotate_integrated_adjoint" (two launches: a, the gather). */
+int sdx_rotate_integrated_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* rot_dev, const double* u,
+                                      const double* u_reference, const double* nus, double* w, double* w_reference);
+/* host-buffer twins: lambdas, v_rot and limb_darkening checked as by sdx_rotate_f64 before any copy */
+int sdx_rotate_integrated_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, double v_rot,
+                              double limb_darkening, double* out, double* out_reference, double* dout_lnv, double* dout_lnv_reference,
+                              double* dout_eps, double* dout_eps_reference);
+int sdx_rotate_integrated_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, double v_rot, double limb_darkening, const double* u,
+                                      const double* u_reference, const double* nus, double* w, double* w_reference);
+/* M0 = int K and M1 = int y K over [ya[i], yb[i]] clamped to [-1, 1] for the limb darkening eps[i], point by point, as rot_cell forms them
+ * (d = yb - ya rounded once; an empty cell gives zeros; a cell that spans 0 is split there).  For tests.  Stage name: "k_rotate_moments". */
+int sdx_rotate_moments_dev(sdx_ctx* ctx, int64_t n, const double* ya, const double* yb, const double* eps, double* out_m0, double* out_m1);
+int sdx_rotate_moments_f64(sdx_ctx* ctx, int64_t n, const double* ya, const double* yb, const double* eps, double* out_m0, double* out_m1);
 
 /* Everything in one call for resident data: pre-pass + line opacity + total (above) + raytrace (F_nu
  * overwritten).  F_nu is [n_depth][ld].  alpha_line_out and total_alphas ([n_depth][ld]) are OPTIONAL outputs (NULL: the

@@ -206,6 +206,12 @@ PROTOTYPES = {
     "sdx_observe_response_grad_f64": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sdx_rotate_tangent_dev": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sdx_rotate_tangent_f64": (_int, [_vp, _i64, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
+    "sdx_rotate_integrated_dev": (_int, [_vp, _i64] + [_vp] * 10),
+    "sdx_rotate_integrated_f64": (_int, [_vp, _i64, _vp, _vp, _vp, C.c_double, C.c_double] + [_vp] * 6),
+    "sdx_rotate_integrated_adjoint_dev": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_rotate_integrated_adjoint_f64": (_int, [_vp, _i64, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_rotate_moments_dev": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_rotate_moments_f64": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sdx_synthesize_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, C.POINTER(Continuum), _int,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sdx_synthesize_ex_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, C.POINTER(Continuum), _int,

@@ -5056,9 +5056,9 @@ __global__ __launch_bounds__(kBlock) void k_observe_adjoint(int64_t n, const dou
 // !(V > 0) copies.  rot_weight is the ONE place where reach, y, q, K and w are rounded and a pair is included or not: the forward
 // kernel, the adjoint's denominators and the adjoint's gather call it, so all three hold the same weights bit for bit.
 // k_rotate_tangent is the forward kernel's body with a compile-time flag (rotate_body<true>): rot_weight also hands out dw_ij = d w_ij /
-// d eps = (-2 sqrt(q_ij) + (pi / 2) q_ij) h_j, and dout_i = (sum_j dw_ij flux_j - out_i sum_j dw_ij) / den_i from the same pass.  There is
-// no d / dV: dK / d ln V = y^2 (2 (1 - eps) / sqrt(q) + pi eps), and the trapezoid sum has a square-root kink in V wherever a point enters
-// a window.
+// d eps = (-2 sqrt(q_ij) + (pi / 2) q_ij) h_j, and dout_i = (sum_j dw_ij flux_j - out_i sum_j dw_ij) / den_i from the same pass.  This
+// sampled sum has no d / dV (dK / d ln V = y^2 (2 (1 - eps) / sqrt(q) + pi eps), and the sum has a square-root kink in V wherever a point
+// enters a window); the cell-integrated profile below (k_rotate_integrated, sdx_rotate_integrated_dev) has a bounded one.
 //
 // k_observe's mapping: points in groups of kObsGroup, eight lanes per point where no point of the group expects more than kObsShort
 // points in its window at the grid's MEAN spacing (2 beta lam_i (n - 1) / (lam_{n-1} - lam_0)), a wave per point otherwise; either
@@ -5272,6 +5272,321 @@ __global__ __launch_bounds__(kBlock) void k_rotate_adjoint(int64_t n, const doub
     // (the transpose of k_flux_nu_to_lambda, as k_observe_adjoint ends)
     w_out[j] = nus ? mul_rn(wf, nus[j]) / lj : wf;
     if (w_ref) w_ref[j] = nus ? mul_rn(wr, nus[j]) / lj : wr;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The cell-integrated rotation profile (include/stardis_hip.h, sdx_rotate_integrated_dev): the flux is piecewise linear between the grid's
+// nodes, as k_observe's trapezoid assumes, and Gray's profile K(y) = c_sqrt sqrt(q) + c_q q, q = 1 - y^2, is integrated against it exactly,
+// cell by cell.  A second mode beside k_rotate, which stays what it is.  For point i, reach_i = lam_i beta, and cell g = [j, j + 1]:
+//     y_j = (lam_j - lam_i) / reach_i  (y_i = 0),   c = clamp(y, -1, 1),   the cell counts iff c_{j+1} > c_j,
+//     Delta = (lam_{j+1} - lam_j) / reach_i: the difference of the neighbours, then one division,
+//     d = Delta where neither end is clamped, else c_{j+1} - c_j,
+//     M0 = int_{c_j}^{c_{j+1}} K,   M1 = int y K,   r = (M1 - y_j M0) / Delta (node j + 1's share),   M0 - r (node j's),   t = M1 / Delta,
+//     out_i = sum_g ((M0 - r) f_j + r f_{j+1}) / den_i,   den_i = sum_g M0   — ascending g, the two products of a cell added in this order,
+//     d out_i / d ln V = (sum_g t (f_{j+1} - f_j) + e_0 f_0 - e_1 f_{n-1} - out_i (e_0 - e_1)) / den_i,
+//         e_0 = y_0 K(y_0) if y_0 > -1, e_1 = y_{n-1} K(y_{n-1}) if y_{n-1} < 1, else 0: the end terms of a truncated window,
+//     d out_i / d eps: the quotient rule over the same sums with K replaced by -2 sqrt(q) + (pi / 2) q.
+// The derivative to V is exact, not "at fixed windows": over lambda the domain does not move, K(+-1) = 0 removes the Leibniz terms, and one
+// integration by parts leaves int K y phi_j' with phi_j' piecewise constant.
+//
+// The moments of a cell are NOT differences of antiderivatives: a window of V = 100 km/s holds hundreds of cells, and a difference of
+// asin loses what the cell is narrower than 1.  rot_half forms them for 0 <= p < s <= 1 (the other half by symmetry; a cell of a point's
+// own row never spans 0, since y_i = 0 is a node) from d = s - p, u = 1 - y, q = u (1 + y), the angles theta = acos y:
+//     sin dl = d (s + p) / (s sqrt(q_p) + p sqrt(q_s)),   cos dl = p s + sqrt(q_p q_s),   dl = theta_p - theta_s = atan2(sin dl, cos dl),
+//     int sqrt(q)   = ((dl - sin dl) + sin dl (u_p + u_s p + sqrt(q_p q_s))) / 2      (the bracket: 1 - cos(theta_p + theta_s)),
+//     int q         = d ((u_p + u_s) - (u_p^2 + u_p u_s + u_s^2) / 3),
+//     int y sqrt(q) = d (s + p) (q_p + sqrt(q_p q_s) + q_s) / (3 (sqrt(q_p) + sqrt(q_s))),      int y q = d (s + p) (q_p + q_s) / 4,
+// dl - sin dl from its series in dl^2 (twelve terms serve dl <= pi / 2).  Every sum is one of non-negative terms, so each moment keeps its
+// relative accuracy for a cell of any width anywhere in [-1, 1].  r's numerator cancels by |y| / d for a narrow cell far from the centre:
+// an error of an ulp of den_i per cell, which moves out_i by that times f_{j+1} - f_j.
+//
+// rot_cell is the ONE place where y, the clamp, the moments, r and t are rounded and a cell counts or not: the forward kernel, the
+// adjoint's denominators and the adjoint's gather call it, so all three hold the same weights bit for bit.  Mapping, window search,
+// round-robin, ascending order and butterfly are k_rotate's; the cells of point i are those of its window [i0, i1) and the partial cell
+// on each side, g in [max(i0 - 1, 0), min(i1, n - 1)).  The adjoint: a_i = u_i / den_i (k_rotate_integrated_adjoint_den), then per node j
+// w_j = sum_i (r of cell j - 1 + (M0 - r) of cell j) a_i over the candidates lam_i in [lam_{j-1} / (1 + beta), lam_{j+1} / (1 - beta)],
+// searched a few 1e-15 wide; rot_cell decides.  No floating-point atomics.
+//
+// Whatever the arrays hold (NaN, unordered values, any V and eps): the searches are obs_windows' (inside [0, n), bounded by their
+// brackets), a cell index g satisfies 0 <= g < n - 1 so that g + 1 <= n - 1, a lane makes at most (n - 1) / W + 1 trips, the gather reads
+// lam at j - 1, j, j + 1 clamped to [0, n) and cells j - 1 >= 0 and j < n - 1 alone, and a point writes only its own element.
+struct RotMoments {
+    double s0, q0, s1, q1;  // int sqrt(q), int q, int y sqrt(q), int y q over the cell
+};
+__device__ __forceinline__ void rot_half(double p, double s, double d, RotMoments& m)
+{
+    const double up = sub_rn(1.0, p), us = sub_rn(1.0, s);
+    const double qp = mul_rn(up, add_rn(1.0, p)), qs = mul_rn(us, add_rn(1.0, s));
+    const double rp = __dsqrt_rn(qp), rs = __dsqrt_rn(qs), rr = mul_rn(rp, rs);
+    const double dsum = mul_rn(d, add_rn(s, p));  // s^2 - p^2 = q_p - q_s
+    const double sn = dsum / add_rn(mul_rn(s, rp), mul_rn(p, rs)), cs = add_rn(mul_rn(p, s), rr);
+    const double dl = atan2(sn, cs), x = mul_rn(dl, dl);
+    // (dl - sin dl) / dl^3 = 1 / 3! - x / 5! + x^2 / 7! - ...
+    double h = 1.0 / 15511210043330985984000000.0;  // 25!
+    h = sub_rn(1.0 / 25852016738884976640000.0, mul_rn(x, h));
+    h = sub_rn(1.0 / 51090942171709440000.0, mul_rn(x, h));
+    h = sub_rn(1.0 / 121645100408832000.0, mul_rn(x, h));
+    h = sub_rn(1.0 / 355687428096000.0, mul_rn(x, h));
+    h = sub_rn(1.0 / 1307674368000.0, mul_rn(x, h));
+    h = sub_rn(1.0 / 6227020800.0, mul_rn(x, h));
+    h = sub_rn(1.0 / 39916800.0, mul_rn(x, h));
+    h = sub_rn(1.0 / 362880.0, mul_rn(x, h));
+    h = sub_rn(1.0 / 5040.0, mul_rn(x, h));
+    h = sub_rn(1.0 / 120.0, mul_rn(x, h));
+    h = sub_rn(1.0 / 6.0, mul_rn(x, h));
+    const double dms = mul_rn(mul_rn(dl, x), h);
+    const double lift = add_rn(add_rn(up, mul_rn(us, p)), rr);
+    m.s0 = mul_rn(0.5, add_rn(dms, mul_rn(sn, lift)));
+    m.q0 = mul_rn(d, sub_rn(add_rn(up, us), add_rn(add_rn(mul_rn(up, up), mul_rn(up, us)), mul_rn(us, us)) / 3.0));
+    m.s1 = mul_rn(dsum, add_rn(add_rn(qp, rr), qs)) / mul_rn(3.0, add_rn(rp, rs));
+    m.q1 = mul_rn(mul_rn(dsum, add_rn(qp, qs)), 0.25);
+}
+// -1 <= a < b <= 1, d = b - a: what k_rotate_moments evaluates, and rot_cell for a cell in one half (its two first branches).  A cell that
+// spans 0 is the sum of its halves for the even moments, and for the odd ones the cell between |a| and |b| with the sign of the longer half.
+__device__ __forceinline__ void rot_moments(double a, double b, double d, RotMoments& m)
+{
+    if (a >= 0.0) {
+        rot_half(a, b, d, m);
+    } else if (b <= 0.0) {
+        rot_half(-b, -a, d, m);
+        m.s1 = -m.s1, m.q1 = -m.q1;
+    } else {
+        RotMoments lo, hi;
+        rot_half(0.0, -a, -a, lo);
+        rot_half(0.0, b, b, hi);
+        m.s0 = add_rn(lo.s0, hi.s0), m.q0 = add_rn(lo.q0, hi.q0), m.s1 = 0.0, m.q1 = 0.0;
+        const double na = -a;
+        if (na != b) {
+            RotMoments odd;
+            rot_half(fmin(na, b), fmax(na, b), fabs(add_rn(a, b)), odd);
+            m.s1 = b > na ? odd.s1 : -odd.s1, m.q1 = b > na ? odd.q1 : -odd.q1;
+        }
+    }
+}
+
+struct RotCell {
+    double m0, r, t;  // int K over the cell, node j + 1's share of it, M1 / Delta
+    double dm0, dr;   // d / d eps of m0 and r (kDeriv)
+};
+// point i's cell [a, b] = [j, j + 1] (self: 0 if a is the point itself, 1 if b is, else -1); false: the cell does not count
+template <bool kDeriv>
+__device__ __forceinline__ bool rot_cell(const RotProfile& r, double lam_i, double lam_a, double lam_b, int self, RotCell& c)
+{
+    const double reach = mul_rn(lam_i, r.beta);
+    const double ya = self == 0 ? 0.0 : sub_rn(lam_a, lam_i) / reach, yb = self == 1 ? 0.0 : sub_rn(lam_b, lam_i) / reach;
+    const double ca = fmin(fmax(ya, -1.0), 1.0), cb = fmin(fmax(yb, -1.0), 1.0);
+    if (!(cb > ca)) return false;
+    const double delta = sub_rn(lam_b, lam_a) / reach;
+    RotMoments m;
+    // (y_i = 0 is a node: on an ascending grid a cell of the point's own row lies in one half, and only there is the result meant)
+    const double d = ca == ya && cb == yb ? delta : sub_rn(cb, ca);
+    if (ca >= 0.0) {
+        rot_half(ca, cb, d, m);
+    } else {
+        rot_half(fmax(-cb, 0.0), -ca, d, m);
+        m.s1 = -m.s1, m.q1 = -m.q1;
+    }
+    const double m1 = add_rn(mul_rn(r.c_sqrt, m.s1), mul_rn(r.c_q, m.q1));
+    c.m0 = add_rn(mul_rn(r.c_sqrt, m.s0), mul_rn(r.c_q, m.q0));
+    c.r = sub_rn(m1, mul_rn(ya, c.m0)) / delta;
+    c.t = m1 / delta;
+    if (kDeriv) {
+        const double dm1 = add_rn(mul_rn(-2.0, m.s1), mul_rn(kHalfPi, m.q1));
+        c.dm0 = add_rn(mul_rn(-2.0, m.s0), mul_rn(kHalfPi, m.q0));
+        c.dr = sub_rn(dm1, mul_rn(ya, c.dm0)) / delta;
+    }
+    return true;
+}
+// y K(y) at an end of the grid seen from point i, 0 where the window does not reach it (|y| >= 1) or the end is the point itself.  The term
+// ends in sqrt(1 - |y|): 1 - |y| = (reach - |lam_end - lam_i|) / reach, the difference first (exact where the end node lies near the
+// profile's edge), so that an end node ON the edge does not leave sqrt(a few ulp) = 1e-8 here.
+__device__ __forceinline__ double rot_end_term(const RotProfile& r, double lam_i, double lam_end, bool self)
+{
+    if (self) return 0.0;
+    const double reach = mul_rn(lam_i, r.beta), dl = sub_rn(lam_end, lam_i), ay = fabs(dl);
+    const double u = sub_rn(reach, ay) / reach;
+    if (!(u > 0.0)) return 0.0;
+    const double q = mul_rn(u, add_rn(1.0, ay / reach));
+    return mul_rn(dl / reach, add_rn(mul_rn(r.c_sqrt, __dsqrt_rn(q)), mul_rn(r.c_q, q)));
+}
+
+// What the point's lanes sum over its cells, closed by the butterfly, in every lane of the point: num, numr (flux, ref; nullptr: not
+// formed), den and, with kDeriv, t* = sum t (f_{j+1} - f_j) and e* = the three sums of the d / d eps weights.  Not called where !(V > 0).
+struct RotIntSums {
+    double num, numr, den, tnum, tnumr, enum_, enumr, eden;
+};
+template <bool kDeriv>
+__device__ __forceinline__ void rot_int_point_sums(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                                   const double* __restrict__ ref, const RotProfile& r, const RotLane& m, RotIntSums& s)
+{
+    const int64_t i = m.on ? m.pi : n - 1;
+    const double li = lam[i];
+    const double reach = mul_rn(li, r.beta);
+    int64_t i0, i1;
+    obs_windows(lam, lam, n, 1.0, sub_rn(li, reach), add_rn(li, reach), m.on, m.W, m.lane, i0, i1);
+    const int64_t g0 = i0 > 0 ? i0 - 1 : 0, g1 = i1 < n - 1 ? i1 : n - 1;  // the window's cells and the partial cell on each side
+    s = RotIntSums{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int64_t g = g0 + m.t; g < g1; g += m.W) {
+        RotCell c;
+        if (!rot_cell<kDeriv>(r, li, lam[g], lam[g + 1], g == i ? 0 : (g + 1 == i ? 1 : -1), c)) continue;
+        const double wa = sub_rn(c.m0, c.r);
+        s.den = add_rn(s.den, c.m0);
+        if (flux) {
+            const double fa = flux[g], fb = flux[g + 1];
+            s.num = add_rn(add_rn(s.num, mul_rn(wa, fa)), mul_rn(c.r, fb));
+            if (kDeriv) {
+                s.tnum = add_rn(s.tnum, mul_rn(c.t, sub_rn(fb, fa)));
+                s.enum_ = add_rn(add_rn(s.enum_, mul_rn(sub_rn(c.dm0, c.dr), fa)), mul_rn(c.dr, fb));
+            }
+        }
+        if (ref) {
+            const double ga = ref[g], gb = ref[g + 1];
+            s.numr = add_rn(add_rn(s.numr, mul_rn(wa, ga)), mul_rn(c.r, gb));
+            if (kDeriv) {
+                s.tnumr = add_rn(s.tnumr, mul_rn(c.t, sub_rn(gb, ga)));
+                s.enumr = add_rn(add_rn(s.enumr, mul_rn(sub_rn(c.dm0, c.dr), ga)), mul_rn(c.dr, gb));
+            }
+        }
+        if (kDeriv) s.eden = add_rn(s.eden, c.dm0);
+    }
+    for (int off = m.W >> 1; off > 0; off >>= 1) {
+        s.num = add_rn(s.num, __shfl_xor(s.num, off)), s.numr = add_rn(s.numr, __shfl_xor(s.numr, off));
+        s.den = add_rn(s.den, __shfl_xor(s.den, off));
+        if (kDeriv) {
+            s.tnum = add_rn(s.tnum, __shfl_xor(s.tnum, off)), s.tnumr = add_rn(s.tnumr, __shfl_xor(s.tnumr, off));
+            s.enum_ = add_rn(s.enum_, __shfl_xor(s.enum_, off)), s.enumr = add_rn(s.enumr, __shfl_xor(s.enumr, off));
+            s.eden = add_rn(s.eden, __shfl_xor(s.eden, off));
+        }
+    }
+}
+
+// out, out_ref as above; with kDeriv dlnv, dlnv_ref, deps, deps_ref (each nullptr: not written).  !(V > 0): a copy, and zeros.
+template <bool kDeriv>
+__global__ __launch_bounds__(kBlock) void k_rotate_integrated(int64_t n, const double* __restrict__ lam, const double* __restrict__ flux,
+                                                              const double* __restrict__ ref, const double* __restrict__ rot,
+                                                              double* __restrict__ out, double* __restrict__ out_ref,
+                                                              double* __restrict__ dlnv, double* __restrict__ dlnv_ref,
+                                                              double* __restrict__ deps, double* __restrict__ deps_ref)
+{
+    const RotProfile r = rot_profile(rot);
+    RotLane m;
+    if (!rot_mapping(n, lam, 2.0 * r.beta, r.on, m)) return;
+    if (!r.on) {  // (the group's first wave, eight lanes per point: a copy)
+        if (m.t == 0 && m.on) {
+            out[m.pi] = flux[m.pi];
+            if (ref) out_ref[m.pi] = ref[m.pi];
+            if (kDeriv) {
+                if (dlnv) dlnv[m.pi] = 0.0;
+                if (dlnv_ref) dlnv_ref[m.pi] = 0.0;
+                if (deps) deps[m.pi] = 0.0;
+                if (deps_ref) deps_ref[m.pi] = 0.0;
+            }
+        }
+        return;
+    }
+    RotIntSums s;
+    rot_int_point_sums<kDeriv>(n, lam, flux, ref, r, m, s);
+    if (m.t != 0 || !m.on) return;
+    const double o = s.num / s.den;
+    out[m.pi] = o;
+    double e0 = 0.0, e1 = 0.0;
+    if (kDeriv) {
+        const double li = lam[m.pi];
+        e0 = rot_end_term(r, li, lam[0], m.pi == 0), e1 = rot_end_term(r, li, lam[n - 1], m.pi == n - 1);
+        if (dlnv) {
+            const double tf = add_rn(s.tnum, sub_rn(mul_rn(e0, flux[0]), mul_rn(e1, flux[n - 1])));
+            dlnv[m.pi] = sub_rn(tf, mul_rn(o, sub_rn(e0, e1))) / s.den;
+        }
+        if (deps) deps[m.pi] = sub_rn(s.enum_, mul_rn(o, s.eden)) / s.den;
+    }
+    if (ref) {
+        const double g = s.numr / s.den;
+        out_ref[m.pi] = g;
+        if (kDeriv && dlnv_ref) {
+            const double tg = add_rn(s.tnumr, sub_rn(mul_rn(e0, ref[0]), mul_rn(e1, ref[n - 1])));
+            dlnv_ref[m.pi] = sub_rn(tg, mul_rn(g, sub_rn(e0, e1))) / s.den;
+        }
+        if (kDeriv && deps_ref) deps_ref[m.pi] = sub_rn(s.enumr, mul_rn(g, s.eden)) / s.den;
+    }
+}
+
+// a[i] = u[i] / den_i, a_ref[i] = u_ref[i] / den_i (u_ref = nullptr: none); !(V > 0): den = 1
+__global__ __launch_bounds__(kBlock) void k_rotate_integrated_adjoint_den(int64_t n, const double* __restrict__ lam,
+                                                                          const double* __restrict__ rot, const double* __restrict__ u,
+                                                                          const double* __restrict__ u_ref, double* __restrict__ a,
+                                                                          double* __restrict__ a_ref)
+{
+    const RotProfile r = rot_profile(rot);
+    RotLane m;
+    if (!rot_mapping(n, lam, 2.0 * r.beta, r.on, m)) return;
+    RotIntSums s;
+    s.den = 1.0;
+    if (r.on) rot_int_point_sums<false>(n, lam, nullptr, nullptr, r, m, s);
+    if (m.t != 0 || !m.on) return;
+    a[m.pi] = r.on ? u[m.pi] / s.den : u[m.pi];
+    if (u_ref) a_ref[m.pi] = r.on ? u_ref[m.pi] / s.den : u_ref[m.pi];
+}
+
+__global__ __launch_bounds__(kBlock) void k_rotate_integrated_adjoint(int64_t n, const double* __restrict__ lam,
+                                                                      const double* __restrict__ rot, const double* __restrict__ a,
+                                                                      const double* __restrict__ a_ref, const double* __restrict__ nus,
+                                                                      double* __restrict__ w_out, double* __restrict__ w_ref)
+{
+    const RotProfile r = rot_profile(rot);
+    RotLane m;
+    if (!rot_mapping(n, lam, 2.0 * r.beta, r.on, m)) return;
+    const int64_t j = m.on ? m.pi : n - 1;
+    const double lj = lam[j];
+    double wf = 0.0, wr = 0.0;
+    if (r.on) {
+        // the candidates: lam_i in [lam_{j-1} / (1 + beta), lam_{j+1} / (1 - beta)], a few 1e-15 wide; rot_cell decides
+        const double below = lam[j > 0 ? j - 1 : 0], above = lam[j < n - 1 ? j + 1 : n - 1];
+        double lo, hi, unused;
+        rot_candidates(below, r.beta, lo, unused);
+        rot_candidates(above, r.beta, unused, hi);
+        int64_t iA, iB;
+        obs_windows(lam, lam, n, 1.0, lo, hi, m.on, m.W, m.lane, iA, iB);
+        for (int64_t i = iA + m.t; i < iB; i += m.W) {
+            const double li = lam[i];
+            RotCell c;
+            double w = 0.0;
+            bool any = false;
+            if (j > 0 && rot_cell<false>(r, li, below, lj, j - 1 == i ? 0 : (j == i ? 1 : -1), c)) w = c.r, any = true;
+            if (j < n - 1 && rot_cell<false>(r, li, lj, above, j == i ? 0 : (j + 1 == i ? 1 : -1), c)) w = add_rn(w, sub_rn(c.m0, c.r)), any = true;
+            if (!any) continue;
+            wf = add_rn(wf, mul_rn(w, a[i]));
+            if (a_ref) wr = add_rn(wr, mul_rn(w, a_ref[i]));
+        }
+        for (int off = m.W >> 1; off > 0; off >>= 1) wf = add_rn(wf, __shfl_xor(wf, off)), wr = add_rn(wr, __shfl_xor(wr, off));
+    } else {
+        wf = a[j];
+        if (a_ref) wr = a_ref[j];
+    }
+    if (m.t != 0 || !m.on) return;
+    // (the transpose of k_flux_nu_to_lambda, as k_observe_adjoint ends)
+    w_out[j] = nus ? mul_rn(wf, nus[j]) / lj : wf;
+    if (w_ref) w_ref[j] = nus ? mul_rn(wr, nus[j]) / lj : wr;
+}
+
+// rot_moments point by point, as rot_cell calls it (d = yb - ya rounded once; the ends clamped to [-1, 1]): M0 = int K, M1 = int y K for
+// the limb darkening eps[i]; an empty cell gives zeros (tests/test_gpu_rotation_integrated.py judges them point by point)
+__global__ __launch_bounds__(kBlock) void k_rotate_moments(int64_t n, const double* __restrict__ ya, const double* __restrict__ yb,
+                                                           const double* __restrict__ eps, double* __restrict__ out_m0,
+                                                           double* __restrict__ out_m1)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const double a = fmin(fmax(ya[i], -1.0), 1.0), b = fmin(fmax(yb[i], -1.0), 1.0);
+    double m0 = 0.0, m1 = 0.0;
+    if (b > a) {
+        const double c_sqrt = mul_rn(2.0, sub_rn(1.0, eps[i])), c_q = mul_rn(kHalfPi, eps[i]);
+        RotMoments m;
+        rot_moments(a, b, sub_rn(b, a), m);
+        m0 = add_rn(mul_rn(c_sqrt, m.s0), mul_rn(c_q, m.q0));
+        m1 = add_rn(mul_rn(c_sqrt, m.s1), mul_rn(c_q, m.q1));
+    }
+    out_m0[i] = m0;
+    out_m1[i] = m1;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -3122,6 +3122,173 @@ int sdx_rotate_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, doubl
     return io.finish();
 }
 
+// ---- the cell-integrated rotation profile (k_rotate_integrated), its adjoint and the moments' test entry ------------------------------
+// (k_rotate's launch geometry and the rotation adjoint's scratch: rotate_blocks, rot_ws)
+static int rotate_integrated_check(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, const double* out,
+                                   const double* out_reference, const double* dout_lnv, const double* dout_lnv_reference,
+                                   const double* dout_eps, const double* dout_eps_reference)
+{
+    REQUIRE(ctx, "rotate_integrated: null context");
+    REQUIRE(n >= 2, "rotate_integrated: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && flux && out, "rotate_integrated: null pointer (lambdas, flux and out are required)");
+    REQUIRE(!reference == !out_reference, "rotate_integrated: reference and out_reference go together");
+    REQUIRE((!dout_lnv_reference && !dout_eps_reference) || reference,
+            "rotate_integrated: dout_lnv_reference and dout_eps_reference need a reference");
+    const double* const ins[3] = {lambdas, flux, reference};
+    const double* const outs[6] = {out, out_reference, dout_lnv, dout_lnv_reference, dout_eps, dout_eps_reference};
+    for (int a = 0; a < 6; ++a) {
+        if (!outs[a]) continue;
+        for (int b = 0; b < 3; ++b) REQUIRE(outs[a] != ins[b], "rotate_integrated: not in place (an output must not be one of the inputs)");
+        for (int b = a + 1; b < 6; ++b) REQUIRE(outs[a] != outs[b], "rotate_integrated: the outputs must be buffers of their own");
+    }
+    return SDX_OK;
+}
+
+int sdx_rotate_integrated_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference,
+                              const double* rot_dev, double* out, double* out_reference, double* dout_lnv, double* dout_lnv_reference,
+                              double* dout_eps, double* dout_eps_reference)
+{
+    int rc;
+    if ((rc = rotate_integrated_check(ctx, n, lambdas, flux, reference, out, out_reference, dout_lnv, dout_lnv_reference, dout_eps,
+                                      dout_eps_reference)))
+        return rc;
+    REQUIRE(rot_dev, "rotate_integrated: null pointer (rot_dev is required)");
+    REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "rotate_integrated: too many points for one launch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    {
+        LaunchScope ls(ctx, "k_rotate_integrated");
+        if (dout_lnv || dout_lnv_reference || dout_eps || dout_eps_reference)
+            hipLaunchKernelGGL(k_rotate_integrated<true>, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, flux, reference, rot_dev,
+                               out, out_reference, dout_lnv, dout_lnv_reference, dout_eps, dout_eps_reference);
+        else
+            hipLaunchKernelGGL(k_rotate_integrated<false>, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, flux, reference, rot_dev,
+                               out, out_reference, (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr);
+    }
+    return check_launch("k_rotate_integrated");
+}
+
+int sdx_rotate_integrated_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* rot_dev, const double* u,
+                                      const double* u_reference, const double* nus, double* w, double* w_reference)
+{
+    REQUIRE(ctx, "rotate_integrated_adjoint: null context");
+    REQUIRE(n >= 2, "rotate_integrated_adjoint: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && rot_dev && u && w, "rotate_integrated_adjoint: null pointer (lambdas, rot_dev, u and w are required)");
+    REQUIRE(!u_reference == !w_reference, "rotate_integrated_adjoint: u_reference and w_reference go together");
+    REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "rotate_integrated_adjoint: too many points for one launch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t row = ((size_t)n * sizeof(double) + 255) & ~(size_t)255;
+    int rc = ensure(ctx, &ctx->rot_ws, &ctx->rot_ws_bytes, 2 * row);
+    if (rc) return rc;
+    double* const a = (double*)ctx->rot_ws;
+    double* const a_ref = (double*)((char*)ctx->rot_ws + row);
+    {
+        LaunchScope ls(ctx, "k_rotate_integrated_adjoint");
+        hipLaunchKernelGGL(k_rotate_integrated_adjoint_den, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, rot_dev, u,
+                           u_reference, a, a_ref);
+        hipLaunchKernelGGL(k_rotate_integrated_adjoint, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, rot_dev, (const double*)a,
+                           u_reference ? (const double*)a_ref : nullptr, nus, w, w_reference);
+    }
+    return check_launch("k_rotate_integrated_adjoint");
+}
+
+int sdx_rotate_integrated_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, double v_rot,
+                              double limb_darkening, double* out, double* out_reference, double* dout_lnv, double* dout_lnv_reference,
+                              double* dout_eps, double* dout_eps_reference)
+{
+    int rc;
+    if ((rc = rotate_integrated_check(ctx, n, lambdas, flux, reference, out, out_reference, dout_lnv, dout_lnv_reference, dout_eps,
+                                      dout_eps_reference)))
+        return rc;
+    if ((rc = rotate_host_check(n, lambdas, v_rot, limb_darkening))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
+    const double pair[2] = {v_rot, limb_darkening};
+    const double *d_l, *d_f, *d_r, *d_rot;
+    double *d_o, *d_or, *d_v, *d_vr, *d_e, *d_er;
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(flux, grid, &d_f);
+    plan.in(reference, grid, &d_r);
+    plan.in(pair, 2 * f8, &d_rot);
+    plan.out(out, grid, &d_o);
+    plan.out(out_reference, grid, &d_or);
+    plan.out(dout_lnv, grid, &d_v);
+    plan.out(dout_lnv_reference, grid, &d_vr);
+    plan.out(dout_eps, grid, &d_e);
+    plan.out(dout_eps_reference, grid, &d_er);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_rotate_integrated_dev(ctx, n, d_l, d_f, d_r, d_rot, d_o, d_or, d_v, d_vr, d_e, d_er))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+int sdx_rotate_integrated_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, double v_rot, double limb_darkening, const double* u,
+                                      const double* u_reference, const double* nus, double* w, double* w_reference)
+{
+    REQUIRE(ctx, "rotate_integrated_adjoint: null context");
+    REQUIRE(n >= 2, "rotate_integrated_adjoint: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && u && w, "rotate_integrated_adjoint: null pointer (lambdas, u and w are required)");
+    REQUIRE(!u_reference == !w_reference, "rotate_integrated_adjoint: u_reference and w_reference go together");
+    int rc;
+    if ((rc = rotate_host_check(n, lambdas, v_rot, limb_darkening))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
+    const double pair[2] = {v_rot, limb_darkening};
+    const double *d_l, *d_rot, *d_u, *d_ur, *d_nus;
+    double *d_w, *d_wr;
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(pair, 2 * f8, &d_rot);
+    plan.in(u, grid, &d_u);
+    plan.in(u_reference, grid, &d_ur);
+    plan.in(nus, grid, &d_nus);
+    plan.out(w, grid, &d_w);
+    plan.out(w_reference, grid, &d_wr);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_rotate_integrated_adjoint_dev(ctx, n, d_l, d_rot, d_u, d_ur, d_nus, d_w, d_wr))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+// the moments of one cell, point by point (k_rotate_moments): what rot_cell evaluates
+int sdx_rotate_moments_dev(sdx_ctx* ctx, int64_t n, const double* ya, const double* yb, const double* eps, double* out_m0, double* out_m1)
+{
+    REQUIRE(ctx, "rotate_moments: null context");
+    REQUIRE(n >= 0 && (n == 0 || (ya && yb && eps && out_m0 && out_m1)), "rotate_moments: bad arguments");
+    if (n == 0) return SDX_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    {
+        LaunchScope ls(ctx, "k_rotate_moments");
+        hipLaunchKernelGGL(k_rotate_moments, dim3(blocks1(n)), dim3(kBlock), 0, ctx->stream, n, ya, yb, eps, out_m0, out_m1);
+    }
+    return check_launch("k_rotate_moments");
+}
+
+int sdx_rotate_moments_f64(sdx_ctx* ctx, int64_t n, const double* ya, const double* yb, const double* eps, double* out_m0, double* out_m1)
+{
+    REQUIRE(ctx, "rotate_moments: null context");
+    REQUIRE(n >= 0 && (n == 0 || (ya && yb && eps && out_m0 && out_m1)), "rotate_moments: bad arguments");
+    if (n == 0) return SDX_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n * sizeof(double);
+    const double *d_a, *d_b, *d_e;
+    double *d_m0, *d_m1;
+    HostPlan plan;
+    plan.in(ya, bytes, &d_a);
+    plan.in(yb, bytes, &d_b);
+    plan.in(eps, bytes, &d_e);
+    plan.out(out_m0, bytes, &d_m0);
+    plan.out(out_m1, bytes, &d_m1);
+    HostIo io{ctx};
+    int rc;
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_rotate_moments_dev(ctx, n, d_a, d_b, d_e, d_m0, d_m1))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
 // ---- radial-tangential macroturbulence (k_macroturbulence) and its adjoint (k_macroturbulence_adjoint_den, k_macroturbulence_adjoint) ----
 // (k_rotate's launch geometry: rotate_blocks)
 int sdx_macroturbulence_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, const double* mac_dev,

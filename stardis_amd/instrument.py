@@ -120,10 +120,20 @@ class Instrument:
     past an end of the grid is truncated and renormalised: edge_affected() names the pixels that see such points.
     v_mac (km/s; None: no macroturbulence, and nothing of it exists or runs): the radial-tangential macroturbulence zeta, one more
     device scalar (set_macroturbulence) and one more stage (k_macroturbulence) between the rotation and the pixels, with the same
-    scratch rules and the same treatment of the grid's ends."""
+    scratch rules and the same treatment of the grid's ends.
+    rotation: "sampled" (the default: k_rotate, Gray's profile at the grid points under trapezoid weights) or "integrated"
+    (k_rotate_integrated: the profile integrated exactly against the piecewise-linear flux, cell by cell; sdx_rotate_integrated_dev
+    states the operator).  The mode routes every call that rotates — forward, adjoint and tangents — and only the integrated one has
+    the column "v_rot" of parameter_tangents: it is differentiable in v sin i and tends to the identity as v sin i -> 0."""
 
-    def __init__(self, pixel_edges, resolving_power=None, sigma=None, ctx=None, v_rot=None, limb_darkening=0.6, v_mac=None):
+    ROTATION_MODES = ("sampled", "integrated")
+
+    def __init__(self, pixel_edges, resolving_power=None, sigma=None, ctx=None, v_rot=None, limb_darkening=0.6, v_mac=None,
+                 rotation="sampled"):
         self.edges, self.sigma = pixel_sigma(pixel_edges, resolving_power, sigma)  # (ValueError before any device work)
+        if rotation not in self.ROTATION_MODES:
+            raise ValueError(f"rotation must be one of {', '.join(self.ROTATION_MODES)}, got {rotation!r}")
+        self.rotation = rotation
         self.rotates = v_rot is not None
         pair = rotation_pair(v_rot, limb_darkening) if self.rotates else None
         self.macroturbulent = v_mac is not None
@@ -185,13 +195,24 @@ class Instrument:
             out_reference = None
         elif out_reference is None:
             out_reference = self._scratch[1]
-        self.ctx.call("sdx_rotate_dev", int(n), addr(d_lambdas), addr(d_flux), addr(reference), self.d_rot.ptr, addr(out), addr(out_reference))
+        if self._integrated():
+            self.ctx.call("sdx_rotate_integrated_dev", int(n), addr(d_lambdas), addr(d_flux), addr(reference), self.d_rot.ptr, addr(out),
+                          addr(out_reference), None, None, None, None)
+        else:
+            self.ctx.call("sdx_rotate_dev", int(n), addr(d_lambdas), addr(d_flux), addr(reference), self.d_rot.ptr, addr(out),
+                          addr(out_reference))
         return out if reference is None else (out, out_reference)
+
+    def _integrated(self):
+        """the rotation stage is the cell-integrated one (instruments built without the keyword are sampled)"""
+        return getattr(self, "rotation", "sampled") == "integrated"
 
     def rotate_host(self, lambdas, flux, reference=None):
         """numpy in, numpy out (sdx_rotate_f64, which checks the arrays): -> the broadened flux, or (flux, reference)."""
         if not self.rotates:
             raise RuntimeError("no rotation: construct the Instrument with v_rot= (0 allowed)")
+        if self._integrated():
+            return rotate_integrated_host(self.ctx, lambdas, flux, self.v_rot, self.limb_darkening, reference)
         return rotate_host(self.ctx, lambdas, flux, self.v_rot, self.limb_darkening, reference)
 
     def macroturbulence(self, d_lambdas, d_flux, n, reference=None, out=None, out_reference=None, dout=None, dout_reference=None):
@@ -326,7 +347,7 @@ class Instrument:
                               addr(nus) if last else None, addr(t), addr(t_ref))
                 u, u_ref = t, t_ref
             if self.rotates:
-                self.ctx.call("sdx_rotate_adjoint_dev", int(n), addr(d_lambdas), self.d_rot.ptr, u.ptr, addr(u_ref), addr(nus), addr(out),
+                self.ctx.call("sdx_rotate_integrated_adjoint_dev" if self._integrated() else "sdx_rotate_adjoint_dev", int(n), addr(d_lambdas), self.d_rot.ptr, u.ptr, addr(u_ref), addr(nus), addr(out),
                               addr(out_reference))
             return out if out_reference is None else (out, out_reference)
         self.ctx.call("sdx_observe_adjoint_dev", int(n), addr(d_lambdas), addr(flux) if reference is not None else None, addr(reference),
@@ -336,6 +357,7 @@ class Instrument:
 
     # -- forward mode: tangents of observe() ----------------------------------------------------------------------------------------
     PARAMETERS = ("v_rad", "lsf", "v_mac", "limb_darkening")
+    INTEGRATED_PARAMETERS = ("v_rot",)  # only with rotation="integrated"
 
     def reserve_tangent(self, n):
         """Size the scratch of tangent() and parameter_tangents() for grids of up to n points now: per broadening stage the tangent
@@ -395,11 +417,23 @@ class Instrument:
     def _wrt(self, wrt):
         if wrt is None:  # every parameter this instrument has
             return ("v_rad", "lsf") + (("v_mac",) if self.macroturbulent and self.v_mac > 0.0 else ()) + (
-                ("limb_darkening",) if self.rotates and self.v_rot > 0.0 else ())
+                ("limb_darkening",) if self.rotates and self.v_rot > 0.0 else ()) + (
+                self.INTEGRATED_PARAMETERS if self._integrated() and self.rotates and self.v_rot > 0.0 else ())
         names = (wrt,) if isinstance(wrt, str) else tuple(wrt)
         for name in names:
-            if name not in self.PARAMETERS:
-                raise ValueError(f"unknown parameter {name!r}: wrt takes {', '.join(self.PARAMETERS)}")
+            if name in self.INTEGRATED_PARAMETERS:
+                if not self._integrated():
+                    raise ValueError(f'{name!r} needs the cell-integrated rotation profile: construct the Instrument with '
+                                     'rotation="integrated" (the sampled sum has a square-root kink in v sin i wherever a point enters a window); '
+                                     f"in the sampled mode wrt takes {', '.join(self.PARAMETERS)}")
+            elif name not in self.PARAMETERS:
+                raise ValueError(f"unknown parameter {name!r}: wrt takes {', '.join(self.PARAMETERS)}"
+                                 f' (and {", ".join(self.INTEGRATED_PARAMETERS)} with rotation="integrated")')
+        if "v_rot" in names:
+            if not self.rotates:
+                raise RuntimeError("no rotation: construct the Instrument with v_rot=")
+            if not self.v_rot > 0.0:
+                raise ValueError("the derivative to v sin i needs v_rot > 0 (at v_rot = 0 the stage is a copy)")
         if "v_mac" in names:
             if not self.macroturbulent:
                 raise RuntimeError("no macroturbulence: construct the Instrument with v_mac=")
@@ -419,8 +453,10 @@ class Instrument:
           "lsf"             per ln kappa of a common factor kappa on every sigma; for a resolving power, -d / d ln R   (dout_lsf)
           "v_mac"           per km/s of zeta: k_macroturbulence's d / d ln zeta over zeta, through the pixel stage as a tangent
           "limb_darkening"  per unit of eps: k_rotate_tangent's d / d eps through the macroturbulence and the pixel stage
-        v sin i has no such column: on the trapezoid sum the forward model has a square-root kink in V wherever a point enters a
-        window; a central difference of two observe() calls remains the answer.  wrt=None: every column this instrument has.
+          "v_rot"           per km/s of v sin i, with rotation="integrated" only: k_rotate_integrated's exact d / d ln V over V, through
+                            the macroturbulence and the pixel stage; "limb_darkening" then comes from the same launch
+        In the sampled mode v sin i has no such column: on the trapezoid sum the forward model has a square-root kink in V wherever a
+        point enters a window.  wrt=None: every column this instrument has.
         Unknown names are a ValueError; "v_mac" needs
         Instrument(v_mac > 0), "limb_darkening" Instrument(v_rot > 0).  On demand: it allocates its outputs (and the tangent scratch
         at the first call) and runs the stages in front of the pixels again."""
@@ -434,8 +470,25 @@ class Instrument:
         addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
         f, g = flux, reference
         eps_f = eps_g = None  # d / d eps at the pixel stage's input
+        lnv_f = lnv_g = None  # d / d ln v_rot at the pixel stage's input
         if self.rotates:
-            if "limb_darkening" in names:
+            if self._integrated() and ("limb_darkening" in names or "v_rot" in names):
+                # one launch of k_rotate_integrated gives the broadened pair and both derivatives
+                rf, rg = self._scratch[0], self._scratch[1] if normal else None
+                want_eps, want_v = "limb_darkening" in names, "v_rot" in names
+                d_lnv, d_lnv_ref = (self.ctx.empty((int(n),)), self.ctx.empty((int(n),)) if normal else None) if want_v else (None, None)
+                self.ctx.call("sdx_rotate_integrated_dev", int(n), addr(d_lambdas), addr(f), addr(g), self.d_rot.ptr, rf.ptr, addr(rg),
+                              addr(d_lnv), addr(d_lnv_ref), d_par.ptr if want_eps else None, addr(d_par_ref) if want_eps else None)
+                f, g = rf, rg
+                if want_eps:
+                    eps_f, eps_g = self._push(d_lambdas, n, d_par, d_par_ref, first_stage=1)
+                if want_v:
+                    lnv_f, lnv_g = d_lnv, d_lnv_ref
+                    if self.macroturbulent:  # (buffers of its own: the tangent scratch holds the limb darkening's pair)
+                        t, t_ref = self.ctx.empty((int(n),)), self.ctx.empty((int(n),)) if normal else None
+                        m = self.macroturbulence(d_lambdas, d_lnv, n, d_lnv_ref, out=t, out_reference=t_ref)
+                        lnv_f, lnv_g = m if normal else (m, None)
+            elif "limb_darkening" in names:
                 rf, rg = self._scratch[0], self._scratch[1] if normal else None
                 self.ctx.call("sdx_rotate_tangent_dev", int(n), addr(d_lambdas), addr(f), addr(g), self.d_rot.ptr, rf.ptr, addr(rg), d_par.ptr,
                               addr(d_par_ref))
@@ -455,6 +508,10 @@ class Instrument:
                 self.ctx.call("sdx_divide_dev", self.n_pix, per_ln.ptr, zeta.ptr, res["v_mac"].ptr)
         if eps_f is not None:
             self._observe_tangent(d_lambdas, n, f, g, eps_f, eps_g, dout_flux=res["limb_darkening"])
+        if lnv_f is not None:
+            per_ln, V = self.ctx.empty((self.n_pix,)), self.ctx.upload(np.full(self.n_pix, self.v_rot))
+            self._observe_tangent(d_lambdas, n, f, g, lnv_f, lnv_g, dout_flux=per_ln)
+            self.ctx.call("sdx_divide_dev", self.n_pix, per_ln.ptr, V.ptr, res["v_rot"].ptr)
         if "v_rad" in names or "lsf" in names:
             self._observe_tangent(d_lambdas, n, f, g, dout_velocity=res.get("v_rad"), dout_lsf=res.get("lsf"))
         return res
@@ -494,7 +551,17 @@ class Instrument:
         g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
         host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
         res = {}
-        if self.rotates:
+        if self.rotates and self._integrated() and ("limb_darkening" in names or "v_rot" in names):
+            bf, bg, vf, vg, ef, eg = _unpack_integrated(rotate_integrated_host(self.ctx, lam, f, self.v_rot, self.limb_darkening, g, True), g)
+            through = lambda a, b: (a, b) if not self.macroturbulent else (  # noqa: E731
+                (self.macroturbulence_host(lam, a), None) if b is None else self.macroturbulence_host(lam, a, b))
+            mf, mg = through(bf, bg)
+            if "limb_darkening" in names:
+                res["limb_darkening"] = self._observe_tangent_host(lam, mf, mg, *through(ef, eg), flux_tangent=True)[0]
+            if "v_rot" in names:
+                res["v_rot"] = self._observe_tangent_host(lam, mf, mg, *through(vf, vg), flux_tangent=True)[0] / self.v_rot
+            f, g = bf, bg
+        elif self.rotates:
             if "limb_darkening" in names:
                 o = [np.empty(lam.size) if (g is not None or k % 2 == 0) else None for k in range(4)]
                 self.ctx.call("sdx_rotate_tangent_f64", lam.size, host(lam), host(f), host(g), self.v_rot, self.limb_darkening,
@@ -541,7 +608,7 @@ class Instrument:
                               host(t), host(t_ref))
                 u, u_ref = t, t_ref
             if self.rotates:
-                self.ctx.call("sdx_rotate_adjoint_f64", lam.size, host(lam), self.v_rot, self.limb_darkening, host(u), host(u_ref), host(nu),
+                self.ctx.call("sdx_rotate_integrated_adjoint_f64" if self._integrated() else "sdx_rotate_adjoint_f64", lam.size, host(lam), self.v_rot, self.limb_darkening, host(u), host(u_ref), host(nu),
                               host(w), host(w_ref))
             return w if w_ref is None else (w, w_ref)
         self.ctx.call("sdx_observe_adjoint_f64", lam.size, host(lam), host(f), host(g), self.n_pix, host(self.edges), host(self.sigma),
@@ -564,6 +631,30 @@ def rotate_host(ctx, lambdas, flux, v_rot, limb_darkening=0.6, reference=None):
     host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     (ctx or default_context()).call("sdx_rotate_f64", lam.size, host(lam), host(f), host(g), V, eps, host(out), host(out_ref))
     return out if g is None else (out, out_ref)
+
+
+def rotate_integrated_host(ctx, lambdas, flux, v_rot, limb_darkening=0.6, reference=None, derivatives=False):
+    """The cell-integrated rotation of host arrays (sdx_rotate_integrated_f64) -> the broadened flux, or (flux, reference) with a
+    reference; derivatives=True appends d / d ln v_rot and d / d limb_darkening of each: (out, dout_lnv, dout_eps), or (out,
+    out_reference, dout_lnv, dout_lnv_reference, dout_eps, dout_eps_reference).  The arguments are checked before any device work."""
+    V, eps = rotation_pair(v_rot, limb_darkening)
+    lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
+    _ascending("lambdas", lam)
+    if lam.size < 2:
+        raise ValueError("lambdas must hold at least two points")
+    f = _host_vector("flux", flux, lam.size, "grid point")
+    g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
+    outs = [np.empty(lam.size) if (k < 2 or derivatives) and (k % 2 == 0 or g is not None) else None for k in range(6)]
+    host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    (ctx or default_context()).call("sdx_rotate_integrated_f64", lam.size, host(lam), host(f), host(g), V, eps, *(host(a) for a in outs))
+    res = tuple(a for a in outs if a is not None)
+    return res[0] if len(res) == 1 else res
+
+
+def _unpack_integrated(res, reference):
+    """rotate_integrated_host(..., derivatives=True)'s tuple -> (out, out_reference, dout_lnv, dout_lnv_reference, dout_eps,
+    dout_eps_reference), None where there is no reference"""
+    return res if reference is not None else (res[0], None, res[1], None, res[2], None)
 
 
 def macroturbulence_host(ctx, lambdas, flux, zeta, reference=None, derivative=False):

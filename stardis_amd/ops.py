@@ -637,3 +637,48 @@ def observe_tangent(lambdas, flux, pixel_edges, sigma, v_rad=0.0, reference=None
                                     doppler_factor(v_rad), host(df), host(dg), host(res["out"]), host(res["v_rad"]), host(res["lsf"]),
                                     host(res.get("flux")))
     return res
+
+
+def rotate_integrated(lambdas, flux, v_rot, limb_darkening=0.6, reference=None, derivatives=False, ctx=None):
+    """Rotational broadening with the profile integrated over the grid's cells (sdx_rotate_integrated_f64): the flux is piecewise
+    linear between the nodes and Gray's profile is integrated against it exactly, so the result is differentiable in v_rot and tends
+    to the identity as v_rot -> 0 -> (n,), or (flux, reference) with a reference.  derivatives=True appends d / d ln v_rot and
+    d / d limb_darkening of each, from the same launch: (out, dout_lnv, dout_eps), or (out, out_reference, dout_lnv,
+    dout_lnv_reference, dout_eps, dout_eps_reference).  v_rot = 0 copies and the derivatives are zeros."""
+    from .instrument import rotate_integrated_host
+
+    return rotate_integrated_host(ctx, lambdas, flux, v_rot, limb_darkening, reference, derivatives)
+
+
+def rotate_integrated_adjoint(lambdas, u, v_rot, limb_darkening=0.6, u_reference=None, nus=None, ctx=None):
+    """The transpose of rotate_integrated (sdx_rotate_integrated_adjoint_f64): weights u over the broadened points -> weights w over
+    the grid points with sum_i u_i rotate_integrated(flux)_i = sum_j w_j flux_j, or (w, w_reference) with u_reference.  nus: the
+    weights then apply to F_nu instead of F_lambda."""
+    from .instrument import _ascending, _host_vector, rotation_pair
+
+    V, eps = rotation_pair(v_rot, limb_darkening)
+    lam = np.ascontiguousarray(_lib.plain(lambdas), dtype=F8).reshape(-1)
+    _ascending("lambdas", lam)
+    if lam.size < 2:
+        raise ValueError("lambdas must hold at least two points")
+    uu = _host_vector("u", u, lam.size, "grid point")
+    ur, nu = (None if a is None else _host_vector(name, a, lam.size, "grid point") for name, a in (("u_reference", u_reference), ("nus", nus)))
+    w, w_ref = np.empty(lam.size), None if ur is None else np.empty(lam.size)
+    host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    (ctx or default_context()).call("sdx_rotate_integrated_adjoint_f64", lam.size, host(lam), V, eps, host(uu), host(ur), host(nu), host(w),
+                                    host(w_ref))
+    return w if w_ref is None else (w, w_ref)
+
+
+def rotate_moments(ya, yb, limb_darkening=0.6, ctx=None):
+    """-> (M0, M1): the integrals of K(y) and y K(y), K Gray's rotation profile 2 (1 - eps) sqrt(1 - y^2) + (pi / 2) eps (1 - y^2), over
+    [ya, yb] clamped to [-1, 1], point by point through the routine the integrated rotation evaluates (sdx_rotate_moments_f64;
+    sdx_kernels.h rot_moments).  The arguments broadcast."""
+    both = np.broadcast_arrays(_host(ya), _host(yb), _host(limb_darkening))
+    shape = both[0].shape
+    a, b, e = (np.ascontiguousarray(v, dtype=F8).reshape(-1) for v in both)
+    m0, m1 = np.empty(a.size), np.empty(a.size)
+    (ctx or default_context()).call("sdx_rotate_moments_f64", a.size, a.ctypes.data, b.ctypes.data, e.ctypes.data, m0.ctypes.data,
+                                    m1.ctypes.data)
+    r = (m0.reshape(shape), m1.reshape(shape))
+    return r if shape else tuple(v[()] for v in r)
