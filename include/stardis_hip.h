@@ -149,6 +149,16 @@ int sdx_set_int_option(sdx_ctx* ctx, const char* name, int64_t value);
  * half-widths).  Replaces nothing in the reference (its sum is always the direct one, opacities_solvers/base.py:577-592). */
 int sdx_far_field_active(const sdx_ctx* ctx, int64_t n_nu_global);
 int sdx_far_field_rule(int64_t* min_points, int* tile_points, int* near_points);
+/* Which way the continuum plane of the last fused step on this context was computed, as the site that enqueued its launch decided
+ * it (tests assert the route they mean to exercise; nothing here changes a launch).  Fills out[0 .. min(n_out, 10)):
+ * [0] kernel: 0 no fused continuum launch yet, 1 the pre-pass launch (k_prepass_continuum), 2 the classification launch of a culled
+ * shard or of the two-collective mode (k_classify_continuum); [1] 1: depth-group tiles, 0: one block per (tile, depth) that evaluates
+ * every point from scratch (more bound-free levels than the tiles' per-depth factors fit in 48 KiB of LDS); [2] depths per block (1..8;
+ * 1 when untiled); [3] 1: the 1-D cross-section table is searched from LDS (at most 1024 nodes), 0: from global memory, or there is
+ * none, or the launch is planned; [4] 1: the launch honoured an sdx_grid_plan; [5] threads per block; [6] frequency tiles;
+ * [7] block rows (depth groups); [8] dynamic LDS of the launch in bytes; [9] the device's compute units, which the choice of [2]
+ * depends on.  A step of the two-collective mode reports the launch of its phase 1. */
+int sdx_continuum_route(const sdx_ctx* ctx, int64_t* out, int n_out);
 
 /* device memory for callers that do not bring their own (numpy-only users) */
 /* (freed blocks are kept by the context — up to 4 GiB — and handed out again: all uses are ordered on the context's stream, so the

@@ -123,6 +123,7 @@ PROTOTYPES = {
     "sdx_set_int_option": (_int, [_vp, C.c_char_p, _i64]),
     "sdx_far_field_active": (_int, [_vp, _i64]),
     "sdx_far_field_rule": (_int, [C.POINTER(_i64), C.POINTER(_int), C.POINTER(_int)]),
+    "sdx_continuum_route": (_int, [_vp, C.POINTER(_i64), _int]),
     "sdx_malloc": (_vp, [_vp, C.c_size_t]),
     "sdx_free": (_int, [_vp, _vp]),
     "sdx_memcpy_h2d": (_int, [_vp, _vp, _vp, C.c_size_t]),
@@ -343,6 +344,15 @@ class Context:
         buf = C.create_string_buffer(96)
         check(self.lib.sdx_profile_variant(self.handle, kernel.encode(), buf, 96))
         return buf.value.decode()
+
+    def continuum_route(self):
+        """how the last fused step on this context computed its continuum plane (sdx_continuum_route) -> dict"""
+        v = (C.c_int64 * 10)()
+        check(self.lib.sdx_continuum_route(self.handle, v, 10))
+        names = ("kernel", "tiled", "depths_per_block", "table_in_lds", "planned", "threads", "tiles", "rows", "shmem", "n_cu")
+        out = dict(zip(names, (int(x) for x in v)))
+        out["kernel"] = ("", "k_prepass_continuum", "k_classify_continuum")[out["kernel"]]
+        return out
 
     @property
     def pinned(self):

@@ -138,6 +138,12 @@ struct sdx_ctx {
         int64_t n_nu = 0, nu_begin = 0, nu_count = 0, n_lines = 0;
         uint64_t generation = 0;
     } classified;
+    // the continuum launch of the last fused step, as its launch site enqueued it (sdx_continuum_route): kernel 0 none yet,
+    // 1 k_prepass_continuum, 2 k_classify_continuum
+    struct {
+        int kernel = 0, tiled = 0, depths_per_block = 0, table_in_lds = 0, planned = 0, threads = 0, tiles = 0, rows = 0;
+        int64_t shmem = 0;
+    } cont_route;
     bool profile = false;
     std::vector<ProfileRecord> records;
     std::vector<hipEvent_t> event_pool;
@@ -548,6 +554,15 @@ int sdx_far_field_active(const sdx_ctx* ctx, int64_t n_nu_global)
 {
     REQUIRE(ctx, "null context");
     return far_field_on(ctx, n_nu_global) ? 1 : 0;
+}
+
+int sdx_continuum_route(const sdx_ctx* ctx, int64_t* out, int n_out)
+{
+    REQUIRE(ctx && out && n_out >= 0, "sdx_continuum_route: null pointer");
+    const auto& r = ctx->cont_route;
+    const int64_t v[10] = {r.kernel, r.tiled, r.depths_per_block, r.table_in_lds, r.planned, r.threads, r.tiles, r.rows, r.shmem, ctx->n_cu};
+    for (int k = 0; k < n_out && k < 10; ++k) out[k] = v[k];
+    return SDX_OK;
 }
 
 int sdx_far_field_rule(int64_t* min_points, int* tile_points, int* near_points)
@@ -1056,6 +1071,22 @@ static int plan_continuum(const sdx_ctx* ctx, const sdx_continuum* cont, const G
     return SDX_OK;
 }
 
+// sdx_continuum_route: what a launch hands its continuum blocks, read the way the kernels read it (`stage_table` bit 0: table in
+// LDS, bit 1: depth-group tiles, bits 4..7: depths per block; a planned launch always runs tiles and stages no table)
+static void note_cont_route(sdx_ctx* ctx, int kernel, const ContPlan& cp, bool planned, int threads)
+{
+    auto& r = ctx->cont_route;
+    r.kernel = kernel;
+    r.tiled = planned || (cp.stage_table & 2) != 0;
+    r.depths_per_block = r.tiled ? (cp.stage_table >> 4) & 15 : 1;
+    r.table_in_lds = !planned && (cp.stage_table & 1) != 0;
+    r.planned = planned;
+    r.threads = threads;
+    r.tiles = cp.cont_tiles;
+    r.rows = (int)cp.cont_rows;
+    r.shmem = (int64_t)cp.shmem;
+}
+
 // ... and what it gets back (where the caller wants it)
 struct PrepassResult {
     LineWork w;
@@ -1118,6 +1149,7 @@ static int prepass_culled(sdx_ctx* ctx, const Grid& g, const Lines& l, const Pre
             // half the classification blocks (16 of 32 wave slots per CU: the stream keeps its bytes in flight), the
             // continuum blocks take the other slots
             const unsigned n_cls_half = share ? n_cls : std::max(1u, n_cls / 2);
+            note_cont_route(ctx, 2, cp, false, kBlock);
             hipLaunchKernelGGL(k_classify_continuum, dim3((unsigned)s.n_partial + n_cls_half + (unsigned)cp.cont_tiles * cp.cont_rows), dim3(kBlock), cp.shmem, ctx->stream,
                                s.n_partial, (int)n_cls_half, n_depth, n_nu, n_lines, dnu_ws, l.doppler, l.gammas, l.gamma_cols, l.alphas, m_max, g.nus,
                                cp.cont_tiles, g.nu_begin, g.nu_count, cp.ca, req.cont_plane, g.nu_count, cp.stage_table, l.line_nus, g.nu_begin, g.nu_count,
@@ -1173,6 +1205,7 @@ static int prepass_launch(sdx_ctx* ctx, const Grid& g, const Lines& l, const Pre
         const int cont_tiles = cp.cont_tiles, stage_table = cp.stage_table;
         const size_t shmem = cp.shmem;
         const unsigned total_blocks = grid.x * grid.y + (unsigned)cont_tiles * cp.cont_rows;
+        note_cont_route(ctx, 1, cp, planned, kPreBlock);
         {
         LaunchScope ls(ctx, "k_prepass_continuum", planned ? (w.n_csplit ? "planned + wide-line list" : "planned") : (w.n_csplit ? "+ wide-line list" : nullptr));
 #define SDX_PRE_ARGS (int)grid.x, (int)grid.y, cont_tiles, n_depth, n_nu, g.nus,                                                                   \

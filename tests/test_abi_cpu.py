@@ -157,3 +157,4 @@ def test_planner_constants_are_the_librarys():
     assert tile.value == 256 and near.value == int(3.5 * tile.value)
     assert parallel.far_field_active(mn.value) and not parallel.far_field_active(mn.value - 1)
     assert lib.sdx_far_field_active(None, 100000) < 0  # null context
+    assert lib.sdx_continuum_route(None, (ctypes.c_int64 * 10)(), 10) < 0  # null context
