@@ -485,6 +485,40 @@ int sdx_line_param_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const do
                                const double* doppler_widths, const double* gammas, int gamma_cols, const double* alphas,
                                const double* weight, double* out_damping, double* out_doppler, double* out_centre,
                                double* out_damping_depth, double* out_doppler_depth, double* out_centre_depth);
+/* ---- the tangent of the line-opacity sum: forward mode through the lines ----------------------------
+ * The Jacobian-vector product the two gathers above are the transposes of.  With T, x, y and amp as above and per line, or per (line,
+ * depth), the directions  a = d ln alpha,  g = d ln gamma,  b = d ln doppler,  n = d nu_l (Hz):
+ *     out[d][i] = sum over the items (l, d) with i in [lo_ld, hi_ld) of
+ *                     a T  +  g (amp y K_y)  -  b (T + amp x K_x + amp y K_y)  -  n (amp K_x / doppler_ld)
+ * AT FIXED WINDOWS AND FIXED REGIONS, the window's centre index held too — so that, for every weight plane W,
+ *     sum_d sum_i W[d][i] out[d][i] = sum_l sum_d (a S0 + g out_damping + b out_doppler + n out_centre)[l][d]
+ * with S0 = sdx_line_adjoint_dev's out_line_depth and the three outputs of sdx_line_param_adjoint_dev.  It is the column of the line
+ * opacity for ONE global parameter that acts on many lines: an abundance (a = 1 on the lines of the species), the microturbulence
+ * (b = xi (nu_l / c)^2 / doppler_ld^2), a damping enhancement (g), a velocity shift (n); sdx_response_project_dev takes it to the flux.
+ * Windows bit for bit those of sdx_line_windows_dev on the GLOBAL grid; T is what the fp64 line kernels evaluate, K_x and K_y are
+ * sdx_voigt_grad_dev's; always the direct sum, always fp64, no far field.
+ * PRECONDITION, as for sdx_line_opacity_dev: line_nus ascending (the kernel finds a tile's lines as a range of the list); a list in
+ * another order gives wrong sums, not an error.  line arrays as for sdx_line_windows_dev; each direction NULL (zero) or
+ * [n_lines][dir_cols] with dir_cols 1 or n_depth, one dir_cols for all four; out [n_depth][out_ld], column 0 at global index nu_begin:
+ * EVERY element of the columns [0, nu_count) is written, exactly 0.0 where no window covers it.  An item all of whose directions are
+ * exactly zero is skipped before any evaluation: a 0 / 1 mask over a species costs what the species costs.
+ * Deterministic: no floating-point atomics; a column's sum stays in one lane and runs over the items that cover it in an order the tables
+ * alone fix — first those whose half-width exceeds 256 grid points, then the others, each in ascending line order.  The bits are
+ * therefore the same from run to run, under graph replay, through the host twin and WHATEVER THE SHARD: a shard's columns are bit for
+ * bit the whole-grid call's.
+ * Refused with SDX_ERR_ARG before anything is enqueued, also for n_nu = 0: a null context, mixed_precision = 1, all four directions
+ * NULL, dir_cols or gamma_cols neither 1 nor n_depth, a shard outside the grid, the int32 limits (n_nu, n_lines * n_depth).  n_lines = 0
+ * still writes the zeros; nu_count = 0 launches nothing.  Only enqueues on the context's stream; its scratch is the context's (shared
+ * with the two gathers) and grows outside a capture only.  Stage name of the profile hooks: k_line_tangent. */
+int sdx_line_tangent_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
+                         int64_t n_lines, const double* line_nus, const double* doppler_widths, const double* gammas,
+                         int gamma_cols, const double* alphas, const double* d_strength, const double* d_damping,
+                         const double* d_doppler, const double* d_centre, int dir_cols, double* out, int64_t out_ld);
+/* host-buffer twin of sdx_line_tangent_dev: the whole grid, contiguous arrays, out [n_depth][n_nu]; the same bits. */
+int sdx_line_tangent_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus,
+                         const double* doppler_widths, const double* gammas, int gamma_cols, const double* alphas,
+                         const double* d_strength, const double* d_damping, const double* d_doppler, const double* d_centre,
+                         int dir_cols, double* out);
 /* The weight plane of the flux sensitivities from the response functions (sdx_response_dev):
  *     weight[k][j] = nu_weight[j] (R_alpha[k][j] / total[k][j])          (nu_weight = NULL: 1)
  * every operation one correctly rounded fp64 operation; a zero in total gives what IEEE gives (as sdx_response_project_dev). */

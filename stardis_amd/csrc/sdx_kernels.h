@@ -6213,6 +6213,253 @@ __global__ __launch_bounds__(kBlock) void k_line_param_adjoint_gather(AdjLines a
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The tangent of the line-opacity sum (include/stardis_hip.h, sdx_line_tangent_dev): the plane
+//     out[d][i] = sum over the items (l, d) whose window covers i of  a T + g y Ty - b (T + x Tx + y Ty) - n Tx / dw
+// with T = amp K, Tx = amp K_x, Ty = amp K_y from voigt_grad_x and the directions a = d ln alpha, g = d ln gamma, b = d ln dw, n = d nu_l
+// of the item — the transpose of k_line_adjoint and k_line_param_adjoint, at their windows (adjoint_window's rule on the GLOBAL grid)
+// and regions.  Always the direct sum, always fp64.
+//
+// A column's sum must not depend on the run or on the shard, so nothing here appends with atomics and no sum crosses lanes:
+//   k_line_tangent_plan  (depth, 256 lines) per block: the window of every item clipped to the shard into win_lo / win_hi [N_d][N_l] —
+//                        empty (0, 0) where the window misses the shard or EVERY direction of the item is exactly zero (a species mask
+//                        costs what the species costs); a WIDE item (half-width of the rule above kTanWide) is marked by -1 - lo.  The
+//                        block counts its wide items;
+//   k_line_tangent_scan  a wave per depth: exclusive prefix of the blocks' counts;
+//   k_line_tangent_list  the plan's geometry: ballot and prefix place the wide lines of a depth in ASCENDING line order in its list;
+//   k_line_tangent       a wave per (depth, tile of kTanTile columns of the shard), a lane owns kTanP columns (stride 64: coalesced).  It
+//                        walks the depth's wide list, then the contiguous range of lines whose centre index lies within kTanWide of the
+//                        tile (centre[] descends as the lines ascend: a 64-ary search, all lanes probing) — 64 candidates at a time: each
+//                        lane tests one window against the tile and, where it hits, forms its item's constants (one round of loads, one
+//                        reciprocal for the 64); a ballot names the hits, and the wave evaluates them in ascending order, the constants
+//                        of each from its lane by v_readlane.  A whole tile in a line's far wing takes region1_grad without a test.
+// So every column adds its wide items in ascending line order and then its other items in ascending line order, whatever the tile it
+// falls in: the bits do not depend on the shard.  A column no item covers is written as 0.0.  (Tiles of 512 and 1024 columns were
+// measured and lost at both sizes: profiles/EXPERIMENTS.md, "The tangent of the line-opacity sum".)
+constexpr int kTanP = 4;
+constexpr int kTanTile = 64 * kTanP;
+constexpr int kTanWide = 256;
+struct TanDirs {
+    const double *strength, *damping, *doppler, *centre;  // [N_l][cols] or null
+    int cols;                                             // 1 or N_d
+};
+struct TanWork {
+    int* centre;    // [N_l] (k_line_adjoint_setup)
+    double* pd;     // [0] = d_nu, [1] = 1 / d_nu (k_line_adjoint_setup)
+    int* win_lo;    // [N_d][N_l]
+    int* win_hi;    // [N_d][N_l]
+    int* list;      // [N_d][N_l] the wide lines of each depth, ascending
+    int* chunk;     // [N_d][n_chunks] wide items per block of the plan, then their exclusive prefix
+    int* n_wide;    // [N_d]
+    int n_chunks;
+};
+
+// the wave's count of `flag` into s_cnt -> this thread's rank among the block's flagged threads, and (total) their number
+__device__ __forceinline__ int tan_block_rank(bool flag, int* s_cnt, int& total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(flag);
+    if (lane == 0) s_cnt[wv] = __popcll(m);
+    __syncthreads();
+    int before = 0;
+    total = 0;
+    for (int k = 0; k < kBlock / 64; ++k) {
+        if (k < wv) before += s_cnt[k];
+        total += s_cnt[k];
+    }
+    return before + __popcll(m & ((1ull << lane) - 1));
+}
+
+__global__ __launch_bounds__(kBlock) void k_line_tangent_plan(AdjLines a, TanDirs dir, TanWork w)
+{
+    __shared__ int s_cnt[kBlock / 64];
+    const int d = blockIdx.y;
+    const int64_t l = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    bool wide = false;
+    if (l < a.n_lines) {
+        const size_t item = (size_t)l * a.n_depth + d, k = (size_t)l * dir.cols + (dir.cols == 1 ? 0 : d);
+        const bool live = (dir.strength && dir.strength[k] != 0.0) || (dir.damping && dir.damping[k] != 0.0) ||
+                          (dir.doppler && dir.doppler[k] != 0.0) || (dir.centre && dir.centre[k] != 0.0);
+        int lo = 0, hi = 0;
+        if (live) {
+            int rlo, rhi;
+            const int64_t hw = window_rule(w.centre[l], a.n_nu, w.pd[0], w.pd[1], a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)],
+                                           a.doppler[item], a.alphas[item], rlo, rhi);
+            const int64_t b = max((int64_t)rlo, a.nu_begin), e = min((int64_t)rhi, a.nu_begin + a.nu_count);
+            if (e > b) {
+                wide = hw > kTanWide;
+                lo = wide ? -1 - (int)b : (int)b;
+                hi = (int)e;
+            }
+        }
+        w.win_lo[(size_t)d * a.n_lines + l] = lo;
+        w.win_hi[(size_t)d * a.n_lines + l] = hi;
+    }
+    int total;
+    tan_block_rank(wide, s_cnt, total);
+    if (threadIdx.x == 0) w.chunk[(size_t)d * w.n_chunks + blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(64) void k_line_tangent_scan(TanWork w)
+{
+    const int d = blockIdx.x, lane = threadIdx.x;
+    int* const c = w.chunk + (size_t)d * w.n_chunks;
+    int base = 0;
+    for (int k0 = 0; k0 < w.n_chunks; k0 += 64) {  // (uniform)
+        const int k = k0 + lane;
+        const int v = k < w.n_chunks ? c[k] : 0;
+        int inc = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int t = __shfl_up(inc, off);
+            if (lane >= off) inc += t;
+        }
+        if (k < w.n_chunks) c[k] = base + inc - v;
+        base += __shfl(inc, 63);
+    }
+    if (lane == 0) w.n_wide[d] = base;
+}
+
+__global__ __launch_bounds__(kBlock) void k_line_tangent_list(AdjLines a, TanWork w)
+{
+    __shared__ int s_cnt[kBlock / 64];
+    const int d = blockIdx.y;
+    const int64_t l = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool wide = l < a.n_lines && w.win_lo[(size_t)d * a.n_lines + l] < 0;
+    int total;
+    const int rank = tan_block_rank(wide, s_cnt, total);
+    if (wide) w.list[(size_t)d * a.n_lines + w.chunk[(size_t)d * w.n_chunks + blockIdx.x] + rank] = (int)l;
+}
+
+// first l in [0, n) with centre[l] <= v, n if there is none; centre[] does not ascend.  All 64 lanes probe: log64(n) dependent loads.
+__device__ __forceinline__ int64_t tan_first_le(const int* __restrict__ centre, int64_t n, int64_t v, int lane)
+{
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {  // (uniform)
+        const int64_t step = (hi - lo + 63) >> 6;
+        const int64_t idx = lo + lane * step;
+        const int k = __popcll(__ballot(idx < hi && centre[idx] > v));  // the probes in front of the answer: lanes 0 ... k - 1
+        if (k == 0) break;
+        hi = min(hi, lo + k * step);
+        lo += (k - 1) * step + 1;
+    }
+    return lo;
+}
+
+// a lane's value at the wave-uniform lane k
+__device__ __forceinline__ double tan_bcast(double v, int k)
+{
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), k), __builtin_amdgcn_readlane(__double2loint(v), k));
+}
+
+// kGrad = false: strength is the only direction — the term alone, by voigt_term as the line kernels evaluate it, one FMA per point
+template <bool kGrad>
+__global__ __launch_bounds__(kBlock) void k_line_tangent(AdjLines a, TanDirs dir, TanWork w, double* __restrict__ out, int64_t out_ld, int n_tiles)
+{
+    constexpr int P = kTanP, kTile = kTanTile;
+    const int lane = threadIdx.x & 63;
+    const int64_t wid = (int64_t)blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int d = (int)(wid / n_tiles);
+    if (d >= a.n_depth) return;
+    const int t = (int)(wid - (int64_t)d * n_tiles);
+    const int64_t base = a.nu_begin + (int64_t)t * kTile;
+    const int64_t tile_end = min(base + kTile, a.nu_begin + a.nu_count);
+    const bool whole = tile_end == base + kTile;
+    const double nu_first = a.nus[base], nu_last = a.nus[tile_end - 1];  // (the grid descends)
+    double nu[P], acc[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const int64_t i = base + p * 64 + lane;
+        nu[p] = i < tile_end ? a.nus[i] : 0.0;
+        acc[p] = 0.0;
+    }
+    if (a.n_lines > 0) {
+        const int* __restrict__ lo_row = w.win_lo + (size_t)d * a.n_lines;
+        const int* __restrict__ hi_row = w.win_hi + (size_t)d * a.n_lines;
+        const int* __restrict__ list = w.list + (size_t)d * a.n_lines;
+        // the other items reach at most kTanWide points from their centre index
+        const int64_t l0 = tan_first_le(w.centre, a.n_lines, tile_end + kTanWide, lane);
+        const int64_t l1 = tan_first_le(w.centre, a.n_lines, base - kTanWide - 1, lane);
+        for (int seg = 0; seg < 2; ++seg) {
+            const int64_t first = seg ? l0 : 0, last = seg ? l1 : w.n_wide[d];
+            for (int64_t e0 = first; e0 < last; e0 += 64) {  // (uniform)
+                const int64_t e = e0 + lane;
+                int64_t l = 0;
+                int lo = -1, hi = 0;
+                if (e < last) {
+                    l = seg ? e : list[e];
+                    lo = lo_row[l], hi = hi_row[l];
+                    if (!seg) lo = -1 - lo;  // (the list holds wide items only; in the range they stay negative and are passed over)
+                }
+                const bool hit = lo >= 0 && hi > base && lo < tile_end;
+                // the constants of the 64 candidates side by side, each hit in its own lane: one round of loads and one reciprocal
+                // for all of them, where a walk that formed them hit by hit would wait for every item's loads in turn
+                double lnu = 0.0, inv = 0.0, y = 0.0, amp = 0.0, ct = 0.0, cy = 0.0, cxx = 0.0, cx = 0.0;
+                RegionIGrad k1 = {0.0, 0.0, 0.0, 0.0};
+                bool wing = false;
+                if (hit) {
+                    const size_t item = (size_t)l * a.n_depth + d, kd = (size_t)l * dir.cols + (dir.cols == 1 ? 0 : d);
+                    lnu = a.line_nus[l];
+                    narrow_params(a.doppler[item], a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)], a.alphas[item], inv, y, amp);
+                    k1 = region1_grad_setup(y, amp);
+                    const double da = dir.strength ? dir.strength[kd] : 0.0, dg = dir.damping ? dir.damping[kd] : 0.0;
+                    const double db = dir.doppler ? dir.doppler[kd] : 0.0, dn = dir.centre ? dir.centre[kd] : 0.0;
+                    // a T + g y Ty - b (T + x Tx + y Ty) - n Tx / dw  =  ct T + cy Ty + cxx (x Tx) + cx Tx
+                    ct = da - db, cy = (dg - db) * y, cxx = -db, cx = -(dn * inv);
+                    // A whole tile inside the window and in the line's far wing — k_line_adjoint_tiled's condition — needs no test per
+                    // point: every point then passes voigt_grad_x's own test, and region1_grad is what it evaluates (the same bits).
+                    wing = whole && lo <= base && hi >= base + kTile && (lnu > nu_first || lnu < nu_last) &&
+                           add_rn(fabs((nu_first - lnu) * inv), y) > 15.0 && add_rn(fabs((nu_last - lnu) * inv), y) > 15.0;
+                }
+                unsigned long long hits = __ballot(hit);
+                const unsigned long long wings = __ballot(wing);
+                while (hits) {  // (uniform) ascending
+                    const int k = __builtin_ctzll(hits);
+                    hits &= hits - 1;
+                    const double s_lnu = tan_bcast(lnu, k), s_inv = tan_bcast(inv, k), s_ct = tan_bcast(ct, k), s_cy = tan_bcast(cy, k);
+                    const double s_cxx = tan_bcast(cxx, k), s_cx = tan_bcast(cx, k);
+                    const RegionIGrad s_k1 = {tan_bcast(k1.yk, k), tan_bcast(k1.c, k), tan_bcast(k1.cv, k), tan_bcast(k1.cd, k)};
+                    if ((wings >> k) & 1) {
+#pragma unroll
+                        for (int p = 0; p < P; ++p) {
+                            const double x = (nu[p] - s_lnu) * s_inv;
+                            if constexpr (kGrad) {
+                                double tt, tx, ty;
+                                region1_grad(x, s_k1, tt, tx, ty);
+                                acc[p] = add_rn(acc[p], fma(s_ct, tt, fma(s_cy, ty, fma(s_cxx, x * tx, s_cx * tx))));
+                            } else {
+                                acc[p] = fma(s_ct, region1_add(0.0, x, RegionI{s_k1.yk, s_k1.cv, s_k1.cd}), acc[p]);
+                            }
+                        }
+                    } else {
+                        const double s_y = tan_bcast(y, k), s_amp = tan_bcast(amp, k);
+                        const int b = __builtin_amdgcn_readlane(lo, k), we = __builtin_amdgcn_readlane(hi, k);
+                        const unsigned len = (unsigned)(we - b);
+                        const int rel0 = (int)(base + lane - b);  // (negative: in front of the window, far above len as an unsigned number)
+#pragma unroll
+                        for (int p = 0; p < P; ++p)
+                            if ((unsigned)(rel0 + p * 64) < len) {
+                                if constexpr (kGrad) {
+                                    const double x = (nu[p] - s_lnu) * s_inv;
+                                    double tt, tx, ty;
+                                    voigt_grad_x(x, s_y, s_amp, s_k1, tt, tx, ty);
+                                    acc[p] = add_rn(acc[p], fma(s_ct, tt, fma(s_cy, ty, fma(s_cxx, x * tx, s_cx * tx))));
+                                } else {
+                                    acc[p] = fma(s_ct, voigt_term(nu[p] - s_lnu, s_inv, s_y, s_amp, RegionI{s_k1.yk, s_k1.cv, s_k1.cd}), acc[p]);
+                                }
+                            }
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const int64_t i = base + p * 64 + lane;
+        if (i < tile_end) out[(size_t)d * out_ld + (i - a.nu_begin)] = acc[p];
+    }
+}
+
 // voigt_grad_x element-wise, the sibling of k_voigt_term: amp K, amp K_x, amp K_y at x = delta_nu * inv_dw with the routine's own region
 // tests (tests/test_gpu_voigt_grad.py judges it point by point)
 __global__ __launch_bounds__(kBlock) void k_voigt_grad(int64_t n, const double* __restrict__ dnu, const double* __restrict__ inv_dw,

@@ -2688,6 +2688,96 @@ int sdx_line_param_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const do
     return io.finish();
 }
 
+// ---- the tangent of the line-opacity sum (k_line_tangent) ---------------------------------------------------------------------
+// The adjoints' checks.  Five launches under the stage name k_line_tangent: the grid spacing and the centres (k_line_adjoint_setup), the
+// windows, the prefix of the wide items per depth, their lists, the plane.  The scratch is the adjoints' (adj_ws).
+int sdx_line_tangent_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count, int64_t n_lines,
+                         const double* line_nus, const double* doppler, const double* gammas, int gamma_cols, const double* alphas,
+                         const double* d_strength, const double* d_damping, const double* d_doppler, const double* d_centre, int dir_cols,
+                         double* out, int64_t out_ld)
+{
+    REQUIRE(ctx, "line_tangent: null context");
+    REQUIRE(!ctx->mixed_precision, "line_tangent: no line tangent with mixed_precision = 1 (the tangent is that of the fp64 direct sum)");
+    REQUIRE(n_depth > 0 && n_depth <= 65535 && n_nu >= 0 && n_lines >= 0 && n_nu < (int64_t)2147483647, "line_tangent: need 1 <= n_depth <= 65535, sizes >= 0 and n_nu within int32");
+    REQUIRE(n_lines * (int64_t)n_depth < (int64_t)2147483647 - 64, "line_tangent: n_lines * n_depth must fit int32");
+    REQUIRE(d_strength || d_damping || d_doppler || d_centre, "line_tangent: no direction given");
+    REQUIRE(dir_cols == n_depth || dir_cols == 1, "line_tangent: the directions must have n_depth or 1 columns");
+    REQUIRE(gamma_cols == n_depth || gamma_cols == 1, "line_tangent: gammas must have n_depth or 1 columns");
+    REQUIRE(nu_begin >= 0 && nu_count >= 0 && nu_begin + nu_count <= n_nu, "line_tangent: frequency shard outside the grid");
+    if (n_nu == 0 || nu_count == 0) return SDX_OK;
+    REQUIRE(nus && out && out_ld >= nu_count, "line_tangent: null pointer or out_ld below nu_count");
+    REQUIRE(n_lines == 0 || (line_nus && doppler && gammas && alphas), "line_tangent: null pointer");
+    const int n_tiles = (int)((nu_count + kTanTile - 1) / kTanTile);
+    REQUIRE((int64_t)n_depth * n_tiles < ((int64_t)1 << 30), "line_tangent: n_depth * nu_count too large for one launch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    TanWork w{};
+    w.n_chunks = (int)((n_lines + kBlock - 1) / kBlock);
+    const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_int = pad(4 * (size_t)n_lines * n_depth), b_lines = pad(4 * (size_t)n_lines), b_cnt = pad(4 * (size_t)(4 + n_depth));
+    const size_t b_chunk = pad(4 * (size_t)w.n_chunks * n_depth), b_depth = pad(4 * (size_t)n_depth);
+    int rc = ensure(ctx, &ctx->adj_ws, &ctx->adj_ws_bytes, 256 + b_cnt + b_lines + 3 * b_int + b_chunk + b_depth);
+    if (rc) return rc;
+    AdjWork setup{};  // what k_line_adjoint_setup writes: d_nu, the centres (and the adjoint's counters, not read here)
+    char* p = (char*)ctx->adj_ws;
+    setup.pd = w.pd = (double*)p, p += 256;
+    setup.counters = (int*)p, p += b_cnt;
+    setup.centre = w.centre = (int*)p, p += b_lines;
+    w.win_lo = (int*)p, p += b_int;
+    w.win_hi = (int*)p, p += b_int;
+    w.list = (int*)p, p += b_int;
+    w.chunk = (int*)p, p += b_chunk;
+    w.n_wide = (int*)p;
+    const AdjLines a{n_depth, gamma_cols, n_nu, nu_begin, nu_count, n_lines, nus, line_nus, doppler, gammas, alphas};
+    const TanDirs dir{d_strength, d_damping, d_doppler, d_centre, dir_cols};
+    {
+        LaunchScope ls(ctx, "k_line_tangent");
+        if (n_lines > 0) {
+            const dim3 plan_grid((unsigned)w.n_chunks, (unsigned)n_depth);
+            hipLaunchKernelGGL(k_line_adjoint_setup, dim3(1 + (unsigned)((n_lines + kPreBlock - 1) / kPreBlock)), dim3(kPreBlock), 0, ctx->stream, a, setup);
+            hipLaunchKernelGGL(k_line_tangent_plan, plan_grid, dim3(kBlock), 0, ctx->stream, a, dir, w);
+            hipLaunchKernelGGL(k_line_tangent_scan, dim3((unsigned)n_depth), dim3(64), 0, ctx->stream, w);
+            hipLaunchKernelGGL(k_line_tangent_list, plan_grid, dim3(kBlock), 0, ctx->stream, a, w);
+        }
+        const dim3 grid((unsigned)(((int64_t)n_depth * n_tiles + 3) / 4));
+        if (d_damping || d_doppler || d_centre) hipLaunchKernelGGL(k_line_tangent<true>, grid, dim3(kBlock), 0, ctx->stream, a, dir, w, out, out_ld, n_tiles);
+        else hipLaunchKernelGGL(k_line_tangent<false>, grid, dim3(kBlock), 0, ctx->stream, a, dir, w, out, out_ld, n_tiles);
+    }
+    return check_launch("k_line_tangent");
+}
+
+int sdx_line_tangent_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus, const double* doppler,
+                         const double* gammas, int gamma_cols, const double* alphas, const double* d_strength, const double* d_damping,
+                         const double* d_doppler, const double* d_centre, int dir_cols, double* out)
+{
+    int rc;
+    if ((rc = sdx_line_tangent_dev(ctx, n_depth, 0, nullptr, 0, 0, n_lines, nullptr, nullptr, nullptr, gamma_cols, nullptr, d_strength, d_damping, d_doppler,
+                                   d_centre, dir_cols, nullptr, 0)))
+        return rc;  // refusals before any copy
+    REQUIRE(n_nu >= 0, "line_tangent: negative n_nu");
+    if (n_nu == 0) return SDX_OK;
+    REQUIRE(nus && out && (n_lines == 0 || (line_nus && doppler && gammas && alphas)), "line_tangent: null pointer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), items = (size_t)n_lines * n_depth * f8, dirs = (size_t)n_lines * dir_cols * f8;
+    const double *d_nus, *d_ln, *d_dw, *d_g, *d_a, *d_dir[4];
+    const double* const host_dir[4] = {d_strength, d_damping, d_doppler, d_centre};
+    double* d_out;
+    HostPlan plan;
+    plan.in(nus, (size_t)n_nu * f8, &d_nus);
+    plan.in(line_nus, (size_t)n_lines * f8, &d_ln);
+    plan.in(doppler, items, &d_dw);
+    plan.in(gammas, (size_t)n_lines * gamma_cols * f8, &d_g);
+    plan.in(alphas, items, &d_a);
+    for (int k = 0; k < 4; ++k) plan.in(host_dir[k], dirs, &d_dir[k]);
+    plan.out(out, (size_t)n_depth * n_nu * f8, &d_out);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_line_tangent_dev(ctx, n_depth, n_nu, d_nus, 0, n_nu, n_lines, d_ln, d_dw, d_g, gamma_cols, d_a, d_dir[0], d_dir[1], d_dir[2], d_dir[3], dir_cols,
+                                   d_out, n_nu)))
+        return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
 // ================================================================================================ post-processing
 int sdx_convolve1d_reflect_dev(sdx_ctx* ctx, int64_t n, const double* in, int m, const double* weights, int symmetric, double* out)
 {

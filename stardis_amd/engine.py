@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib
 from . import constants as K
 from . import linelist as LL
+from . import ops
 from ._lib import Continuum, default_context, ptr_of
 
 LINE_WRT = ("strength", "damping", "doppler", "centre")  # wrt= of the line sensitivities; the last three: sdx_line_param_adjoint_dev's outputs
@@ -652,6 +653,70 @@ class SpectralSynthesizer:
                    d_g.ptr, self.gamma_cols, d_a.ptr, d_W.ptr, cnt, *(none + ptrs if per_depth else ptrs + none))
         return res[names[0]] if single else {k: res[k] for k in names}
 
+    # -- forward mode through the lines: one direction over the lines, every column ----------------------------------------------------
+    def line_tangent(self, strength=None, damping=None, doppler=None, centre=None):
+        """-> DeviceArray (N_d, count): the plane by which the line opacity of this synthesizer's columns moves, at fixed windows and
+        fixed Humlicek regions, when every line moves along the given directions (sdx_line_tangent_dev, the transpose of what
+        line_sensitivities gathers): strength = d ln(strength), damping = d ln gamma, doppler = d ln doppler_width, centre = d nu_l in
+        Hz; each None (zero), a scalar, (n_lines,) or (n_lines, N_d), in the order the caller passed the lines.  A 0 / 1 mask over the
+        lines of a species as strength gives that species' line opacity — d alpha_line / d ln(abundance) — and costs what the species
+        costs.  The line tables: a dense list is read where the step reads it (sorted; the directions are permuted with it), a line
+        list of scalars from the snapshot line_sensitivities keeps (forget_line_tables()).  On demand: a synthesizer that never asks
+        allocates and launches nothing new.  A frequency shard returns its own columns, bit for bit those of the whole grid."""
+        dirs, cols = ops.line_directions(self.n_lines, self.n_depth, strength, damping, doppler, centre)
+        c = self.ctx
+        if self.linelist is not None:
+            ln_ptr, d_dw, d_g, d_a = self._tables_in_caller_order()  # (a line list of scalars is sorted: check_sorted)
+        else:
+            ln_ptr, d_dw, d_g, d_a = self.d_ln.ptr, self.d_dw, self.d_g, self.d_a
+            if self._line_order is not None:
+                dirs = [None if v is None else np.ascontiguousarray(v[self._line_order]) for v in dirs]
+        d_dirs = [None if v is None else c.upload(v) for v in dirs]
+        out = c.empty((self.n_depth, self.count))
+        c.call("sdx_line_tangent_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, self.n_lines, ln_ptr, d_dw.ptr,
+               d_g.ptr, self.gamma_cols, d_a.ptr, *(ptr_of(v) for v in d_dirs), cols, out.ptr, self.count)
+        return out
+
+    def flux_tangent(self, strength=None, damping=None, doppler=None, centre=None):
+        """-> DeviceArray (count,): the derivative of F_nu[-1] along the given line directions, from the last step:
+        flux_derivative(line_tangent(...)).  Needs keep_response=True."""
+        self._require_response()
+        return self.flux_derivative(self.line_tangent(strength, damping, doppler, centre))
+
+    def _microturbulence_direction(self, xi):
+        """d ln doppler_ld / d xi = xi (nu_l / c)^2 / doppler_ld^2 (microturbulence_sensitivity's factor), rows in the caller's order"""
+        dw = self._tables_in_caller_order()[1].numpy()
+        nu_over_c = self._line_nus_in_caller_order() / K.C_CGS
+        return float(xi) * (nu_over_c * nu_over_c)[:, None] / (dw * dw)
+
+    def microturbulence_tangent(self, xi):
+        """-> DeviceArray (count,): d F_nu[-1] / d xi per column, of the microturbulent velocity xi (cm/s) the lines' Doppler widths
+        were built with — the forward twin of microturbulence_sensitivity: flux_tangent(doppler=xi (nu_l / c)^2 / doppler_ld^2).  The
+        damping constants are taken not to depend on xi.  xi = 0 gives zeros.  Needs keep_response=True."""
+        self._require_response()
+        if float(xi) == 0.0:
+            return self.ctx.zeros((self.count,))
+        return self.flux_tangent(doppler=self._microturbulence_direction(xi))
+
+    def observed_line_jacobian(self, directions, normalized=False):
+        """-> {name: DeviceArray (n_pix,)}: for every entry name -> dict of line directions (flux_tangent's keywords; or
+        {"microturbulence": xi}) the column d observed_j / d p of the global parameter p that moves the lines along them, at the last
+        step's spectrum: observed_tangent(flux_tangent(...)).  normalized=True: of observed_normalized; the continuum does not move.
+        Needs instrument= and keep_response=True."""
+        self._require_instrument()
+        self._require_response()
+        if normalized:
+            self._require_continuum()
+        out = {}
+        for name, dirs in dict(directions).items():
+            dirs = dict(dirs)
+            if set(dirs) == {"microturbulence"}:
+                d_f = self.microturbulence_tangent(dirs["microturbulence"])
+            else:
+                d_f = self.flux_tangent(**dirs)
+            out[name] = self.observed_tangent(d_f, None, normalized)
+        return out
+
     def _require_instrument(self):
         if self.instrument is None:
             raise RuntimeError("no instrument: construct the synthesizer with instrument=Instrument(...)")
@@ -840,6 +905,42 @@ class SpectralSynthesizer:
         if self.instrument.broadens:
             used &= ~self.instrument.edge_affected(self.lambdas)
         J = {k: np.where(used, v.numpy(), 0.0) for k, v in self.observed_jacobian(names, normalized).items()}
+        grad = {k: math.fsum(c * J[k]) for k in names}
+        if not curvature:
+            return chi2, grad
+        w = np.where(used, ivar, 0.0)
+        H = np.empty((len(names), len(names)))
+        for ia, a in enumerate(names):  # (the upper triangle, mirrored: symmetric bit for bit)
+            for ib in range(ia, len(names)):
+                H[ia, ib] = H[ib, ia] = 2.0 * math.fsum(w * J[a] * J[names[ib]])
+        return chi2, grad, H
+
+    def chi2_joint_gradient(self, data, inverse_variance, instrument_wrt=(), line_directions=None, normalized=False, curvature=False):
+        """-> (chi2, {p: d chi2 / d p}), with curvature=True -> (chi2, gradient, H): chi2_instrument_gradient over the instrument
+        parameters named by instrument_wrt AND the global line parameters of line_directions (observed_line_jacobian's argument)
+        together — the gradient and the Gauss-Newton matrix H = 2 J^T W J of one fit of both, rows and columns in the order
+        instrument_wrt, then line_directions.  The same pixels and the same host sums (math.fsum) as chi2_instrument_gradient; with
+        no line direction it IS chi2_instrument_gradient."""
+        line_directions = dict(line_directions or {})
+        if not line_directions:
+            return self.chi2_instrument_gradient(data, inverse_variance, instrument_wrt, normalized, curvature)
+        self._require_instrument()
+        self._require_response()
+        none_asked = instrument_wrt is not None and not isinstance(instrument_wrt, str) and len(tuple(instrument_wrt)) == 0
+        inst_names = () if none_asked else self.instrument._wrt(instrument_wrt)
+        clash = [k for k in line_directions if k in inst_names]
+        if clash:
+            raise ValueError(f"line_directions reuses the instrument's parameter names {clash}")
+        chi2, c = self._chi2_pixel_weights(data, inverse_variance, normalized)
+        ivar = np.ascontiguousarray(inverse_variance, dtype=np.float64).reshape(-1)
+        obs = (self.d_observed_normalized if normalized else self.d_observed).numpy()
+        used = ~np.isnan(obs) & (ivar != 0)
+        if self.instrument.broadens:
+            used &= ~self.instrument.edge_affected(self.lambdas)
+        columns = dict(self.observed_jacobian(inst_names, normalized)) if inst_names else {}
+        columns.update(self.observed_line_jacobian(line_directions, normalized))
+        names = tuple(inst_names) + tuple(line_directions)
+        J = {k: np.where(used, columns[k].numpy(), 0.0) for k in names}
         grad = {k: math.fsum(c * J[k]) for k in names}
         if not curvature:
             return chi2, grad

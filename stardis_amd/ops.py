@@ -206,6 +206,80 @@ def line_param_adjoint(no_of_depth_points, tracing_nus_values, line_nus, doppler
     return out if device else {k: v.numpy() for k, v in out.items()}
 
 
+LINE_DIRECTIONS = ("strength", "damping", "doppler", "centre")
+
+
+def line_directions(n_lines, no_of_depth_points, strength=None, damping=None, doppler=None, centre=None):
+    """The directions of line_tangent as host arrays -> (list of four (n_lines, cols) arrays or None, cols): each direction None, a
+    scalar, (n_lines,) or (n_lines, N_d); cols is N_d when any of them is per depth, else 1."""
+    n_lines, nd = int(n_lines), int(no_of_depth_points)
+    given = []
+    for name, v in zip(LINE_DIRECTIONS, (strength, damping, doppler, centre)):
+        if v is None:
+            given.append(None)
+            continue
+        v = _host(v)
+        if v.ndim == 0:
+            v = np.full((n_lines, 1), float(v))
+        elif v.shape == (n_lines,):
+            v = v.reshape(n_lines, 1)
+        elif v.shape != (n_lines, nd):
+            raise ValueError(f"direction {name!r} must be a scalar or have shape {(n_lines,)} or {(n_lines, nd)}, got {v.shape}")
+        given.append(v)
+    if all(v is None for v in given):
+        raise ValueError(f"line_tangent needs a direction: one of {LINE_DIRECTIONS}")
+    cols = nd if any(v is not None and v.shape[1] == nd for v in given) else 1  # ((n_lines, 1) with N_d = 1 is both)
+    return [None if v is None else np.ascontiguousarray(np.broadcast_to(v, (n_lines, cols))) for v in given], cols
+
+
+def line_tangent(no_of_depth_points, nus, line_nus, doppler_widths, gammas, alphas, strength=None, damping=None, doppler=None, centre=None,
+                 ctx=None, device=False, shard=None):
+    """The tangent of calc_alan_entries (sdx_line_tangent_dev), the transpose of line_adjoint and line_param_adjoint: the plane
+    (N_d, N_nu) by which alpha_line_at_nu moves, at fixed windows and fixed Humlicek regions, when every line moves along
+    strength = d ln alpha, damping = d ln gamma, doppler = d ln doppler_width and centre = d line_nu (Hz) — each None (zero), a scalar,
+    (n_lines,) or (n_lines, N_d) in the order of the caller's list, which may be any (sorted here as for calc_alan_entries, the
+    directions with it).  A direction may also be a DeviceArray or CUDA tensor of shape (n_lines,), (n_lines, 1) or (n_lines, N_d): it is
+    read where it lies, so the list must then be ascending and every direction of the call have that many columns.
+    shard = (begin, count): only these columns, bit for bit those of the whole grid.  device=True: a DeviceArray."""
+    nus = _host(nus).reshape(-1)
+    ln, dw, g, al = _line_inputs(no_of_depth_points, line_nus, doppler_widths, gammas, alphas, sort=False)
+    nd = int(no_of_depth_points)
+    given = dict(zip(LINE_DIRECTIONS, (strength, damping, doppler, centre)))
+    resident = {k: v for k, v in given.items() if isinstance(v, DeviceArray) or hasattr(v, "data_ptr")}
+    unsorted = ln.size > 1 and bool(np.any(ln[1:] < ln[:-1]))
+    if resident:
+        shapes = [tuple(int(s) for s in v.shape) for v in resident.values()]
+        widths = {1 if s == (ln.size,) else (s[1] if len(s) == 2 and s[0] == ln.size and s[1] in (1, nd) else None) for s in shapes}
+        if None in widths or len(widths) != 1:
+            raise ValueError(f"directions on the device must share one width: {(ln.size,)}, {(ln.size, 1)} or {(ln.size, nd)}, got {shapes}")
+        if unsorted:
+            raise ValueError("directions on the device are read where they lie: the line list must be ascending in frequency")
+        cols = widths.pop()
+        on_host = {k: v for k, v in given.items() if k not in resident and v is not None}
+        dirs = [None] * 4
+        if on_host:
+            dirs, host_cols = line_directions(ln.size, nd, **on_host)
+            if host_cols != cols and not (host_cols == 1 and cols == nd):
+                raise ValueError(f"direction on the host with {host_cols} columns beside directions on the device with {cols}")
+            dirs = [None if v is None else np.ascontiguousarray(np.broadcast_to(v, (ln.size, cols))) for v in dirs]
+    else:
+        dirs, cols = line_directions(ln.size, nd, strength, damping, doppler, centre)
+    begin, count = (0, nus.size) if shard is None else (int(v) for v in shard)
+    if begin < 0 or count < 0 or begin + count > nus.size:
+        raise ValueError(f"shard {(begin, count)} lies outside the grid of {nus.size} frequencies")
+    if unsorted:
+        order = np.argsort(ln, kind="stable")
+        ln, dw, g, al = (np.ascontiguousarray(a[order]) for a in (ln, dw, g, al))
+        dirs = [None if v is None else np.ascontiguousarray(v[order]) for v in dirs]
+    ctx = ctx or default_context()
+    d = [ctx.upload(x) for x in (nus, ln, dw, g, al)]
+    d_dirs = [resident[k] if k in resident else (None if v is None else ctx.upload(v)) for k, v in zip(LINE_DIRECTIONS, dirs)]
+    out = ctx.empty((nd, count))
+    ctx.call("sdx_line_tangent_dev", nd, nus.size, d[0].ptr, begin, count, ln.size, d[1].ptr, d[2].ptr, d[3].ptr, g.shape[1], d[4].ptr,
+             *(ptr_of(v) for v in d_dirs), cols, out.ptr, count)
+    return out if device else out.numpy()
+
+
 # ------------------------------------------------------------------------------------------------ broadening
 def _flags(linear_stark, quadratic_stark, van_der_waals, radiation):
     return (1 if linear_stark else 0) | (2 if quadratic_stark else 0) | (4 if van_der_waals else 0) | (8 if radiation else 0)
