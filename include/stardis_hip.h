@@ -704,7 +704,11 @@ int sdx_rotate_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double*
  * lambdas[j], as sdx_observe_adjoint_dev ends.  The candidates i of a point j have lambdas[i] in [lambdas[j] / (1 + beta), lambdas[j] /
  * (1 - beta)]; that range is searched a few 1e-15 wide and every candidate is tested with INCLUDED.  Ascending i round-robin over the
  * point's lanes, then the butterfly; no floating-point atomics.  Its scratch (a: two rows of n) is the context's and grows outside a
- * capture only.  !(V > 0): w = u.  Refusals and bounds as above.  Stage name: "k_rotate_adjoint" (two launches: a, the gather). */
+ * capture only.  !(V > 0): w = u.  Refusals and bounds as above.  Stage name: "k_rotate_adjoint" (two launches: a, the gather).
+ * The broadening stages (this one, sdx_rotate_integrated_dev, sdx_macroturbulence_dev) share this adjoint and their host-buffer twins.
+ * A stage provides its profile from its device scalar(s) with "the stage is on", its window's width over lambdas[i], den_i from its own
+ * sums, per node j the candidate range and what j's weights share, and the weight of point i for node j; one kernel pair, one launch
+ * routine with one scratch of the context's (an adjoint consumes it between its own two launches) and one twin each way serve all. */
 int sdx_rotate_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* rot_dev, const double* u, const double* u_reference,
                            const double* nus, double* w, double* w_reference);
 /* host-buffer twins: host pointers, V and eps by value.  Checked before any copy: lambdas finite and strictly ascending, v_rot finite
@@ -868,7 +872,7 @@ int sdx_rotate_integrated_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, co
                               double* dout_eps, double* dout_eps_reference);
 /* The transpose: a_i = u[i] / den_i, w[j] = sum_i W_ij a_i over the i with lambdas[i] in [lambdas[j-1] / (1 + beta), lambdas[j+1] / (1 -
  * beta)], searched a few 1e-15 wide; rot_cell decides, so the weights are the forward's bit for bit and  sum_i u[i] out[i] = sum_j w[j]
- * flux[j].  nus, scratch (the rotation adjoint's), refusals and bounds as sdx_rotate_adjoint_dev.  Stage name:
+ * flux[j].  nus, scratch, refusals and bounds as sdx_rotate_adjoint_dev.  Stage name:
  * "k_rotate_integrated_adjoint" (two launches: a, the gather). */
 int sdx_rotate_integrated_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* rot_dev, const double* u,
                                       const double* u_reference, const double* nus, double* w, double* w_reference);

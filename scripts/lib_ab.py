@@ -8,7 +8,17 @@ alternated round by round (clocks drift between sessions and within one):
       `python bench.py` at its defaults, RUNS times per build, interleaved, the first of each discarded; then one
       `--steps 20 --warmup 5` pair
 
+  python scripts/lib_ab.py stages OLD.so NEW.so [ROUNDS] [OUT.json]
+      the broadening stages (rotation, cell-integrated rotation, macroturbulence; forward with every output, adjoint with nus and
+      reference).  Bits: SHA-256 of every output on seeded small grids (n = 2, 3, 8, 9, 17 around the group of eight; a non-uniform
+      grid whose expected window crosses the threshold between the eight-lane mapping and a wave per point; V = 0 and zeta = 0, the copy;
+      with and without a reference; every window at an end of a grid is truncated) and one S-c2-sized call, device entries and
+      host-buffer twins — every hash must agree.  Time: per stage name (sdx_profile_get) the six kernels at S-c2 with V = 2, 10, 100
+      km/s and at S-c3 with V = 10, and the wall time of one forward and one adjoint host-buffer twin, ROUNDS children per build,
+      alternated.  The bar: the new median within the old leg's own max - min of the old median.
+
 Prints mean, max - min, min and max per leg.  The other build: a copy of csrc/ at the other revision, `make -C` there."""
+import hashlib
 import json
 import os
 import subprocess
@@ -56,6 +66,139 @@ def child(tag, options):
     print(json.dumps(out))
 
 
+STAGES = ("k_rotate", "k_rotate_adjoint", "k_rotate_integrated", "k_rotate_integrated_adjoint", "k_macroturbulence", "k_macroturbulence_adjoint")
+STAGE_TIMES = {"S-c2": (2.0, 10.0, 100.0), "S-c3": (10.0,)}
+
+
+def stage_calls(ctx, lam, f, g, u, ur, nus, V, eps, zeta):
+    """every stage entry on device buffers -> {entry: ([outputs], stage name, call)}; g = None: no reference"""
+    import numpy as np
+
+    n = lam.size
+    d = {k: (None if a is None else ctx.upload(a)) for k, a in dict(lam=lam, f=f, g=g, u=u, ur=ur, nus=nus).items()}
+    rot, mac = ctx.upload(np.array([V, eps])), ctx.upload(np.array([zeta]))
+    ptr = lambda a: None if a is None else a.ptr  # noqa: E731
+    outs = lambda k: [ctx.empty((n,)) if g is not None or i % 2 == 0 else None for i in range(k)]  # noqa: E731
+    res = {}
+    for entry, stage, scalars, k in (("sdx_rotate_dev", "k_rotate", rot, 2), ("sdx_rotate_tangent_dev", "k_rotate_tangent", rot, 4),
+                                     ("sdx_rotate_integrated_dev", "k_rotate_integrated", rot, 6), ("sdx_macroturbulence_dev", "k_macroturbulence", mac, 4)):
+        o = outs(k)
+        res[entry] = (o, stage, lambda entry=entry, scalars=scalars, o=o: ctx.call(
+            entry, n, d["lam"].ptr, d["f"].ptr, ptr(d["g"]), scalars.ptr, *map(ptr, o)))
+    for name, scalars in (("rotate", rot), ("rotate_integrated", rot), ("macroturbulence", mac)):
+        o = outs(2)
+        res[f"sdx_{name}_adjoint_dev"] = (o, f"k_{name}_adjoint", lambda name=name, scalars=scalars, o=o: ctx.call(
+            f"sdx_{name}_adjoint_dev", n, d["lam"].ptr, scalars.ptr, d["u"].ptr, ptr(d["ur"] if g is not None else None), d["nus"].ptr, *map(ptr, o)))
+    return res
+
+
+def stage_twins(ctx, lam, f, g, u, ur, nus, V, eps, zeta):
+    """the host-buffer twins -> {entry: ([outputs], call)}"""
+    import numpy as np
+
+    n = lam.size
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    outs = lambda k: [np.empty(n) if g is not None or i % 2 == 0 else None for i in range(k)]  # noqa: E731
+    res = {}
+    for entry, scalars, k in (("sdx_rotate_f64", (V, eps), 2), ("sdx_rotate_tangent_f64", (V, eps), 4), ("sdx_rotate_integrated_f64", (V, eps), 6),
+                              ("sdx_macroturbulence_f64", (zeta,), 4)):
+        o = outs(k)
+        res[entry] = (o, lambda entry=entry, scalars=scalars, o=o: ctx.call(entry, n, ptr(lam), ptr(f), ptr(g), *scalars, *map(ptr, o)))
+    for name, scalars in (("rotate", (V, eps)), ("rotate_integrated", (V, eps)), ("macroturbulence", (zeta,))):
+        o = outs(2)
+        res[f"sdx_{name}_adjoint_f64"] = (o, lambda name=name, scalars=scalars, o=o: ctx.call(
+            f"sdx_{name}_adjoint_f64", n, ptr(lam), *scalars, ptr(u), ptr(ur if g is not None else None), ptr(nus), *map(ptr, o)))
+    return res
+
+
+def stage_inputs(lam, seed):
+    import numpy as np
+    from stardis_amd import constants as K
+
+    rng = np.random.default_rng(seed)
+    draw = lambda: rng.uniform(0.2, 1.0, lam.size)  # noqa: E731
+    return dict(lam=lam, f=draw(), g=1.0 + 0.1 * draw(), u=draw() - 0.6, ur=draw() - 0.6, nus=K.C_CGS * 1.0e8 / lam)
+
+
+def workload_lambdas(tag):
+    import numpy as np
+    from stardis_amd import constants as K
+    from stardis_amd import synth
+
+    w = synth.WORKLOADS[tag]
+    return np.ascontiguousarray(K.nu_to_angstrom(synth.tracing_grid(w["lam0"], w["lam1"], R=w["R"])))
+
+
+def stages_child():
+    import numpy as np
+    from stardis_amd import _lib
+    from stardis_amd import constants as K
+
+    ctx = _lib.Context(0)
+    rng = np.random.default_rng(20250926)
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()  # noqa: E731
+    # ---- bits
+    grids = {f"n={n}": 6000.0 + np.cumsum(rng.uniform(0.02, 0.08, n)) for n in (2, 3, 8, 9, 17)}
+    lam = 5000.0 + np.cumsum(rng.uniform(0.2, 1.8, 400) * (1250.0 / 400))
+    # the expected window (2 beta lam (n - 1) / span points) is kObsShort = 32 at the grid's median: groups on both sides of the threshold
+    V_cross = 32.0 * (lam[-1] - lam[0]) / (2.0 * np.median(lam) * (lam.size - 1)) * K.C_KMS
+    grids["non-uniform 400"] = lam
+    grids["S-c2"] = workload_lambdas("S-c2")
+    hashes = {}
+    for name, lam in grids.items():
+        settings = {"V=25": (25.0, 25.0 / 6)} if name != "non-uniform 400" else {"threshold": (V_cross, V_cross / 6), "V=40": (40.0, 40.0 / 6)}
+        if name in ("n=9", "non-uniform 400"):
+            settings["copy"] = (0.0, 0.0)
+        for label, (V, zeta) in settings.items():
+            for normal in (False, True):
+                a = stage_inputs(lam, 7)
+                if not normal:
+                    a["g"] = None
+                case = {}
+                for entry, (outs, _, call) in stage_calls(ctx, V=V, eps=0.6, zeta=zeta, **a).items():
+                    call()
+                    ctx.synchronize()
+                    case[entry] = [None if o is None else sha(o.numpy()) for o in outs]
+                if name != "S-c2" or normal:
+                    for entry, (outs, call) in stage_twins(ctx, V=V, eps=0.6, zeta=zeta, **a).items():
+                        call()
+                        case[entry] = [None if o is None else sha(o) for o in outs]
+                hashes[f"{name}, {label}, {'with' if normal else 'no'} reference"] = case
+    # ---- time: the median over 31 single profiled calls per stage, then the twins' wall time (each call ends in a synchronize)
+    times = {}
+    for tag, velocities in STAGE_TIMES.items():
+        a = stage_inputs(workload_lambdas(tag), 11)
+        for V in velocities:
+            calls = stage_calls(ctx, V=V, eps=0.6, zeta=V / 6.0, **a)
+            ctx.call("sdx_profile_enable", 1)
+            for entry, (_, stage, call) in calls.items():
+                if stage not in STAGES:
+                    continue
+                for _ in range(3):
+                    call()
+                us = []
+                for _ in range(31):
+                    ctx.call("sdx_profile_reset")
+                    call()
+                    ctx.synchronize()
+                    us.append(ctx.profile(stage)[1] * 1e3)
+                times[f"{tag} V={V:g} {stage}"] = float(np.median(us))
+            ctx.call("sdx_profile_enable", 0)
+            if tag == "S-c2" and V == 10.0:
+                twins = stage_twins(ctx, V=V, eps=0.6, zeta=V / 6.0, **a)
+                for entry in ("sdx_rotate_f64", "sdx_rotate_adjoint_f64"):
+                    call = twins[entry][1]
+                    for _ in range(5):
+                        call()
+                    ts = []
+                    for _ in range(30):
+                        t0 = time.perf_counter()
+                        call()
+                        ts.append((time.perf_counter() - t0) * 1e6)
+                    times[f"{tag} V={V:g} {entry} wall"] = float(np.median(ts))
+    print(json.dumps({"hashes": hashes, "us": times}))
+
+
 def spawn(lib, argv, timeout):
     p = subprocess.run([sys.executable] + argv, env=dict(os.environ, STARDIS_AMD_LIB=os.path.abspath(lib)), capture_output=True, text=True,
                        timeout=timeout, cwd=ROOT)
@@ -76,6 +219,9 @@ def main():
     mode = sys.argv[1]
     if mode == "child":
         child(sys.argv[2], sys.argv[3:])
+        return
+    if mode == "stages-child":
+        stages_child()
         return
     old, new = sys.argv[2], sys.argv[3]
     if mode == "kernels":
@@ -105,6 +251,32 @@ def main():
             res[name + " 20 after 5"].append({"ms_per_step": j["ms_per_step"]})
         for name, rows in res.items():
             summary(name, rows, "us", 1e3, drop_first=True)
+    elif mode == "stages":
+        rounds = int(sys.argv[4]) if len(sys.argv) > 4 else 7
+        res = {"old": [], "new": []}
+        for r in range(rounds):
+            for name, lib in (("old", old), ("new", new)):
+                res[name].append(spawn(lib, [os.path.abspath(__file__), "stages-child"], 300))
+                print(r, name, {k: round(v, 2) for k, v in res[name][-1]["us"].items()}, flush=True)
+        hashes = [r["hashes"] for rows in res.values() for r in rows]
+        differing = sorted({f"{case}: {entry}" for h in hashes[1:] for case in h for entry in h[case] if h[case][entry] != hashes[0][case][entry]})
+        n_hashes = sum(o is not None for case in hashes[0].values() for outs in case.values() for o in outs)
+        print(f"{n_hashes} hashes per child, {len(hashes)} children: {'ALL EQUAL' if not differing else 'DIFFERENT: ' + '; '.join(differing)}")
+        summary("old", [r["us"] for r in res["old"]], "us")
+        summary("new", [r["us"] for r in res["new"]], "us")
+        table, missed = {}, []
+        for k in res["old"][0]["us"]:
+            o, n = sorted(r["us"][k] for r in res["old"]), sorted(r["us"][k] for r in res["new"])
+            row = dict(old_median=o[len(o) // 2], old_spread=o[-1] - o[0], new_median=n[len(n) // 2], new_spread=n[-1] - n[0], old=o, new=n)
+            row["within"] = abs(row["new_median"] - row["old_median"]) <= row["old_spread"]
+            table[k] = row
+            if not row["within"]:
+                missed.append(f"{k} ({'slower' if row['new_median'] > row['old_median'] else 'faster'})")
+        print("time bar (new median within old max - min of the old median):", "MET" if not missed else "MISSED by " + "; ".join(missed))
+        if len(sys.argv) > 5:
+            with open(sys.argv[5], "w") as fh:
+                json.dump(dict(rounds=rounds, hashes_per_child=n_hashes, hashes_equal=not differing, differing=differing, hashes=hashes[0],
+                               us=table, time_bar_missed=missed), fh, indent=1)
     else:
         print(__doc__)
 

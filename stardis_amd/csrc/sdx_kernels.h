@@ -5224,42 +5224,75 @@ __global__ __launch_bounds__(kBlock) void k_rotate_tangent(int64_t n, const doub
     rotate_body<true>(n, lam, flux, ref, rot, out, out_ref, dout, dout_ref);
 }
 
-// a[i] = u[i] / den_i, a_ref[i] = u_ref[i] / den_i (u_ref = nullptr: none); !(V > 0): den = 1
-__global__ __launch_bounds__(kBlock) void k_rotate_adjoint_den(int64_t n, const double* __restrict__ lam, const double* __restrict__ rot,
-                                                               const double* __restrict__ u, const double* __restrict__ u_ref,
-                                                               double* __restrict__ a, double* __restrict__ a_ref)
+// What a broadening stage provides to get its adjoint (stage_adjoint_den, stage_adjoint): a struct of static functions,
+//     load(p): its profile from the device scalar(s), with .on (false: the stage copies);   width(r): the window's whole width over lam_i,
+//     den(n, lam, r, m): den_i, through the stage's own *_point_sums, as the forward kernel runs it,
+//     node(n, lam, j): what node j's weights share (formed once per node, not per candidate),
+//     candidates(r, nd, lj, lo, hi): the range of lam_i that can include node j, a few 1e-15 wide,
+//     weight(r, nd, n, i, j, lam_i, lj, w): point i's weight for node j; false: i does not include j.
+struct RotSampledStage {
+    struct Node {
+        double h;  // the trapezoid weight of lam_j
+    };
+    static __device__ __forceinline__ RotProfile load(const double* __restrict__ rot) { return rot_profile(rot); }
+    static __device__ __forceinline__ double width(const RotProfile& r) { return 2.0 * r.beta; }
+    static __device__ __forceinline__ double den(int64_t n, const double* __restrict__ lam, const RotProfile& r, const RotLane& m)
+    {
+        double num, numr, den;
+        rot_point_sums(n, lam, nullptr, nullptr, r, m, num, numr, den);
+        return den;
+    }
+    static __device__ __forceinline__ Node node(int64_t n, const double* __restrict__ lam, int64_t j) { return Node{rot_trapezoid(lam, n, j)}; }
+    // lam_i in [lam_j / (1 + beta), lam_j / (1 - beta)]; rot_weight decides
+    static __device__ __forceinline__ void candidates(const RotProfile& r, const Node&, double lj, double& lo, double& hi)
+    {
+        rot_candidates(lj, r.beta, lo, hi);
+    }
+    static __device__ __forceinline__ bool weight(const RotProfile& r, const Node& nd, int64_t, int64_t i, int64_t j, double lam_i, double lj, double& w)
+    {
+        return rot_weight(r, lam_i, lj, i == j, nd.h, w);
+    }
+};
+
+// The first launch of a stage's adjoint: a[i] = u[i] / den_i, a_ref[i] = u_ref[i] / den_i (u_ref = nullptr: none); a stage that is not
+// on: den = 1
+template <class Stage>
+__device__ __forceinline__ void stage_adjoint_den(int64_t n, const double* __restrict__ lam, const double* __restrict__ scalars,
+                                                  const double* __restrict__ u, const double* __restrict__ u_ref, double* __restrict__ a,
+                                                  double* __restrict__ a_ref)
 {
-    const RotProfile r = rot_profile(rot);
+    const auto r = Stage::load(scalars);
     RotLane m;
-    if (!rot_mapping(n, lam, 2.0 * r.beta, r.on, m)) return;
-    double num, numr, den = 1.0;
-    if (r.on) rot_point_sums(n, lam, nullptr, nullptr, r, m, num, numr, den);
+    if (!rot_mapping(n, lam, Stage::width(r), r.on, m)) return;
+    double den = 1.0;
+    if (r.on) den = Stage::den(n, lam, r, m);
     if (m.t != 0 || !m.on) return;
     a[m.pi] = r.on ? u[m.pi] / den : u[m.pi];
     if (u_ref) a_ref[m.pi] = r.on ? u_ref[m.pi] / den : u_ref[m.pi];
 }
 
-__global__ __launch_bounds__(kBlock) void k_rotate_adjoint(int64_t n, const double* __restrict__ lam, const double* __restrict__ rot,
-                                                           const double* __restrict__ a, const double* __restrict__ a_ref,
-                                                           const double* __restrict__ nus, double* __restrict__ w_out,
-                                                           double* __restrict__ w_ref)
+// The second: w_j = sum over the candidates i that include node j of w_ij a_i, round-robin over the node's lanes in ascending i, closed
+// by the butterfly; a stage that is not on copies a.  The accesses and trips are bounded as stated above k_rotate.
+template <class Stage>
+__device__ __forceinline__ void stage_adjoint(int64_t n, const double* __restrict__ lam, const double* __restrict__ scalars,
+                                              const double* __restrict__ a, const double* __restrict__ a_ref, const double* __restrict__ nus,
+                                              double* __restrict__ w_out, double* __restrict__ w_ref)
 {
-    const RotProfile r = rot_profile(rot);
+    const auto r = Stage::load(scalars);
     RotLane m;
-    if (!rot_mapping(n, lam, 2.0 * r.beta, r.on, m)) return;
+    if (!rot_mapping(n, lam, Stage::width(r), r.on, m)) return;
     const int64_t j = m.on ? m.pi : n - 1;
     const double lj = lam[j];
     double wf = 0.0, wr = 0.0;
     if (r.on) {
-        // the candidates: lam_i in [lam_j / (1 + beta), lam_j / (1 - beta)], a few 1e-15 wide; rot_weight decides
+        const typename Stage::Node nd = Stage::node(n, lam, j);
         double lo, hi;
-        rot_candidates(lj, r.beta, lo, hi);
+        Stage::candidates(r, nd, lj, lo, hi);
         int64_t iA, iB;
         obs_windows(lam, lam, n, 1.0, lo, hi, m.on, m.W, m.lane, iA, iB);
-        const double h = rot_trapezoid(lam, n, j);
         for (int64_t i = iA + m.t; i < iB; i += m.W) {
             double w;
-            if (!rot_weight(r, lam[i], lj, i == j, h, w)) continue;
+            if (!Stage::weight(r, nd, n, i, j, lam[i], lj, w)) continue;
             wf = add_rn(wf, mul_rn(w, a[i]));
             if (a_ref) wr = add_rn(wr, mul_rn(w, a_ref[i]));
         }
@@ -5272,6 +5305,20 @@ __global__ __launch_bounds__(kBlock) void k_rotate_adjoint(int64_t n, const doub
     // (the transpose of k_flux_nu_to_lambda, as k_observe_adjoint ends)
     w_out[j] = nus ? mul_rn(wf, nus[j]) / lj : wf;
     if (w_ref) w_ref[j] = nus ? mul_rn(wr, nus[j]) / lj : wr;
+}
+
+__global__ __launch_bounds__(kBlock) void k_rotate_adjoint_den(int64_t n, const double* __restrict__ lam, const double* __restrict__ rot,
+                                                               const double* __restrict__ u, const double* __restrict__ u_ref,
+                                                               double* __restrict__ a, double* __restrict__ a_ref)
+{
+    stage_adjoint_den<RotSampledStage>(n, lam, rot, u, u_ref, a, a_ref);
+}
+__global__ __launch_bounds__(kBlock) void k_rotate_adjoint(int64_t n, const double* __restrict__ lam, const double* __restrict__ rot,
+                                                           const double* __restrict__ a, const double* __restrict__ a_ref,
+                                                           const double* __restrict__ nus, double* __restrict__ w_out,
+                                                           double* __restrict__ w_ref)
+{
+    stage_adjoint<RotSampledStage>(n, lam, rot, a, a_ref, nus, w_out, w_ref);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -5510,62 +5557,53 @@ __global__ __launch_bounds__(kBlock) void k_rotate_integrated(int64_t n, const d
     }
 }
 
-// a[i] = u[i] / den_i, a_ref[i] = u_ref[i] / den_i (u_ref = nullptr: none); !(V > 0): den = 1
+// the stage of stage_adjoint_den and stage_adjoint: node j's weight is r of cell j - 1 plus M0 - r of cell j
+struct RotIntegratedStage {
+    struct Node {
+        double below, above;  // lam_{j-1}, lam_{j+1}, clamped to the grid
+    };
+    static __device__ __forceinline__ RotProfile load(const double* __restrict__ rot) { return rot_profile(rot); }
+    static __device__ __forceinline__ double width(const RotProfile& r) { return 2.0 * r.beta; }
+    static __device__ __forceinline__ double den(int64_t n, const double* __restrict__ lam, const RotProfile& r, const RotLane& m)
+    {
+        RotIntSums s;
+        rot_int_point_sums<false>(n, lam, nullptr, nullptr, r, m, s);
+        return s.den;
+    }
+    static __device__ __forceinline__ Node node(int64_t n, const double* __restrict__ lam, int64_t j)
+    {
+        return Node{lam[j > 0 ? j - 1 : 0], lam[j < n - 1 ? j + 1 : n - 1]};
+    }
+    // lam_i in [lam_{j-1} / (1 + beta), lam_{j+1} / (1 - beta)]; rot_cell decides
+    static __device__ __forceinline__ void candidates(const RotProfile& r, const Node& nd, double, double& lo, double& hi)
+    {
+        double unused;
+        rot_candidates(nd.below, r.beta, lo, unused);
+        rot_candidates(nd.above, r.beta, unused, hi);
+    }
+    static __device__ __forceinline__ bool weight(const RotProfile& r, const Node& nd, int64_t n, int64_t i, int64_t j, double lam_i, double lj, double& w)
+    {
+        RotCell c;
+        bool any = false;
+        w = 0.0;
+        if (j > 0 && rot_cell<false>(r, lam_i, nd.below, lj, j - 1 == i ? 0 : (j == i ? 1 : -1), c)) w = c.r, any = true;
+        if (j < n - 1 && rot_cell<false>(r, lam_i, lj, nd.above, j == i ? 0 : (j + 1 == i ? 1 : -1), c)) w = add_rn(w, sub_rn(c.m0, c.r)), any = true;
+        return any;
+    }
+};
 __global__ __launch_bounds__(kBlock) void k_rotate_integrated_adjoint_den(int64_t n, const double* __restrict__ lam,
                                                                           const double* __restrict__ rot, const double* __restrict__ u,
                                                                           const double* __restrict__ u_ref, double* __restrict__ a,
                                                                           double* __restrict__ a_ref)
 {
-    const RotProfile r = rot_profile(rot);
-    RotLane m;
-    if (!rot_mapping(n, lam, 2.0 * r.beta, r.on, m)) return;
-    RotIntSums s;
-    s.den = 1.0;
-    if (r.on) rot_int_point_sums<false>(n, lam, nullptr, nullptr, r, m, s);
-    if (m.t != 0 || !m.on) return;
-    a[m.pi] = r.on ? u[m.pi] / s.den : u[m.pi];
-    if (u_ref) a_ref[m.pi] = r.on ? u_ref[m.pi] / s.den : u_ref[m.pi];
+    stage_adjoint_den<RotIntegratedStage>(n, lam, rot, u, u_ref, a, a_ref);
 }
-
 __global__ __launch_bounds__(kBlock) void k_rotate_integrated_adjoint(int64_t n, const double* __restrict__ lam,
                                                                       const double* __restrict__ rot, const double* __restrict__ a,
                                                                       const double* __restrict__ a_ref, const double* __restrict__ nus,
                                                                       double* __restrict__ w_out, double* __restrict__ w_ref)
 {
-    const RotProfile r = rot_profile(rot);
-    RotLane m;
-    if (!rot_mapping(n, lam, 2.0 * r.beta, r.on, m)) return;
-    const int64_t j = m.on ? m.pi : n - 1;
-    const double lj = lam[j];
-    double wf = 0.0, wr = 0.0;
-    if (r.on) {
-        // the candidates: lam_i in [lam_{j-1} / (1 + beta), lam_{j+1} / (1 - beta)], a few 1e-15 wide; rot_cell decides
-        const double below = lam[j > 0 ? j - 1 : 0], above = lam[j < n - 1 ? j + 1 : n - 1];
-        double lo, hi, unused;
-        rot_candidates(below, r.beta, lo, unused);
-        rot_candidates(above, r.beta, unused, hi);
-        int64_t iA, iB;
-        obs_windows(lam, lam, n, 1.0, lo, hi, m.on, m.W, m.lane, iA, iB);
-        for (int64_t i = iA + m.t; i < iB; i += m.W) {
-            const double li = lam[i];
-            RotCell c;
-            double w = 0.0;
-            bool any = false;
-            if (j > 0 && rot_cell<false>(r, li, below, lj, j - 1 == i ? 0 : (j == i ? 1 : -1), c)) w = c.r, any = true;
-            if (j < n - 1 && rot_cell<false>(r, li, lj, above, j == i ? 0 : (j + 1 == i ? 1 : -1), c)) w = add_rn(w, sub_rn(c.m0, c.r)), any = true;
-            if (!any) continue;
-            wf = add_rn(wf, mul_rn(w, a[i]));
-            if (a_ref) wr = add_rn(wr, mul_rn(w, a_ref[i]));
-        }
-        for (int off = m.W >> 1; off > 0; off >>= 1) wf = add_rn(wf, __shfl_xor(wf, off)), wr = add_rn(wr, __shfl_xor(wr, off));
-    } else {
-        wf = a[j];
-        if (a_ref) wr = a_ref[j];
-    }
-    if (m.t != 0 || !m.on) return;
-    // (the transpose of k_flux_nu_to_lambda, as k_observe_adjoint ends)
-    w_out[j] = nus ? mul_rn(wf, nus[j]) / lj : wf;
-    if (w_ref) w_ref[j] = nus ? mul_rn(wr, nus[j]) / lj : wr;
+    stage_adjoint<RotIntegratedStage>(n, lam, rot, a, a_ref, nus, w_out, w_ref);
 }
 
 // rot_moments point by point, as rot_cell calls it (d = yb - ya rounded once; the ends clamped to [-1, 1]): M0 = int K, M1 = int y K for
@@ -5695,55 +5733,43 @@ __global__ __launch_bounds__(kBlock) void k_macroturbulence(int64_t n, const dou
     }
 }
 
-// a[i] = u[i] / den_i, a_ref[i] = u_ref[i] / den_i (u_ref = nullptr: none); !(zeta > 0): den = 1
+// the stage of stage_adjoint_den and stage_adjoint
+struct MacStage {
+    struct Node {
+        double h;  // the trapezoid weight of lam_j
+    };
+    static __device__ __forceinline__ MacProfile load(const double* __restrict__ mac) { return mac_profile(mac); }
+    static __device__ __forceinline__ double width(const MacProfile& r) { return 2.0 * r.reach; }
+    static __device__ __forceinline__ double den(int64_t n, const double* __restrict__ lam, const MacProfile& r, const RotLane& m)
+    {
+        MacSums s;
+        mac_point_sums(n, lam, nullptr, nullptr, false, r, m, s);
+        return s.den;
+    }
+    static __device__ __forceinline__ Node node(int64_t n, const double* __restrict__ lam, int64_t j) { return Node{rot_trapezoid(lam, n, j)}; }
+    // lam_i in [lam_j / (1 + 6 beta), lam_j / (1 - 6 beta)]; mac_weight decides
+    static __device__ __forceinline__ void candidates(const MacProfile& r, const Node&, double lj, double& lo, double& hi)
+    {
+        rot_candidates(lj, r.reach, lo, hi);
+    }
+    static __device__ __forceinline__ bool weight(const MacProfile& r, const Node& nd, int64_t, int64_t i, int64_t j, double lam_i, double lj, double& w)
+    {
+        double v;
+        return mac_weight(r, lam_i, lj, i == j, nd.h, w, v);
+    }
+};
 __global__ __launch_bounds__(kBlock) void k_macroturbulence_adjoint_den(int64_t n, const double* __restrict__ lam, const double* __restrict__ mac,
                                                                         const double* __restrict__ u, const double* __restrict__ u_ref,
                                                                         double* __restrict__ a, double* __restrict__ a_ref)
 {
-    const MacProfile r = mac_profile(mac);
-    RotLane m;
-    if (!rot_mapping(n, lam, 2.0 * r.reach, r.on, m)) return;
-    MacSums s;
-    s.den = 1.0;
-    if (r.on) mac_point_sums(n, lam, nullptr, nullptr, false, r, m, s);
-    if (m.t != 0 || !m.on) return;
-    a[m.pi] = r.on ? u[m.pi] / s.den : u[m.pi];
-    if (u_ref) a_ref[m.pi] = r.on ? u_ref[m.pi] / s.den : u_ref[m.pi];
+    stage_adjoint_den<MacStage>(n, lam, mac, u, u_ref, a, a_ref);
 }
-
 __global__ __launch_bounds__(kBlock) void k_macroturbulence_adjoint(int64_t n, const double* __restrict__ lam, const double* __restrict__ mac,
                                                                     const double* __restrict__ a, const double* __restrict__ a_ref,
                                                                     const double* __restrict__ nus, double* __restrict__ w_out,
                                                                     double* __restrict__ w_ref)
 {
-    const MacProfile r = mac_profile(mac);
-    RotLane m;
-    if (!rot_mapping(n, lam, 2.0 * r.reach, r.on, m)) return;
-    const int64_t j = m.on ? m.pi : n - 1;
-    const double lj = lam[j];
-    double wf = 0.0, wr = 0.0;
-    if (r.on) {
-        // the candidates: lam_i in [lam_j / (1 + 6 beta), lam_j / (1 - 6 beta)], a few 1e-15 wide; mac_weight decides
-        double lo, hi;
-        rot_candidates(lj, r.reach, lo, hi);
-        int64_t iA, iB;
-        obs_windows(lam, lam, n, 1.0, lo, hi, m.on, m.W, m.lane, iA, iB);
-        const double h = rot_trapezoid(lam, n, j);
-        for (int64_t i = iA + m.t; i < iB; i += m.W) {
-            double w, v;
-            if (!mac_weight(r, lam[i], lj, i == j, h, w, v)) continue;
-            wf = add_rn(wf, mul_rn(w, a[i]));
-            if (a_ref) wr = add_rn(wr, mul_rn(w, a_ref[i]));
-        }
-        for (int off = m.W >> 1; off > 0; off >>= 1) wf = add_rn(wf, __shfl_xor(wf, off)), wr = add_rn(wr, __shfl_xor(wr, off));
-    } else {
-        wf = a[j];
-        if (a_ref) wr = a_ref[j];
-    }
-    if (m.t != 0 || !m.on) return;
-    // (the transpose of k_flux_nu_to_lambda, as k_observe_adjoint ends)
-    w_out[j] = nus ? mul_rn(wf, nus[j]) / lj : wf;
-    if (w_ref) w_ref[j] = nus ? mul_rn(wr, nus[j]) / lj : wr;
+    stage_adjoint<MacStage>(n, lam, mac, a, a_ref, nus, w_out, w_ref);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -89,10 +89,8 @@ struct sdx_ctx {
     size_t adj_ws_bytes = 0;
     void* obs_ws = nullptr;  // the instrument adjoint's per-pixel factors a, b and scans PH, SL (sdx_observe_adjoint_dev)
     size_t obs_ws_bytes = 0;
-    void* rot_ws = nullptr;  // the rotation adjoint's factors a = u / den, two rows of n (sdx_rotate_adjoint_dev)
-    size_t rot_ws_bytes = 0;
-    void* mac_ws = nullptr;  // the macroturbulence adjoint's factors a = u / den, two rows of n (sdx_macroturbulence_adjoint_dev)
-    size_t mac_ws_bytes = 0;
+    void* stage_ws = nullptr;  // a broadening stage's adjoint factors a = u / den, two rows of n (stage_adjoint)
+    size_t stage_ws_bytes = 0;
     void* far_ws = nullptr;  // far_range of the line kernels' far field: two ints per global tile
     size_t far_ws_bytes = 0;
     // cnt_ge[N_nu + 2] (lines per centre index, for the narrow-window kernel) and the per-line integer lists: CntLayout
@@ -468,8 +466,7 @@ void sdx_destroy(sdx_ctx* ctx)
     if (ctx->far_ws) hipFree(ctx->far_ws);
     if (ctx->adj_ws) hipFree(ctx->adj_ws);
     if (ctx->obs_ws) hipFree(ctx->obs_ws);
-    if (ctx->rot_ws) hipFree(ctx->rot_ws);
-    if (ctx->mac_ws) hipFree(ctx->mac_ws);
+    if (ctx->stage_ws) hipFree(ctx->stage_ws);
     if (ctx->cnt_ws) hipFree(ctx->cnt_ws);
     if (ctx->io_dev) hipFree(ctx->io_dev);
     if (ctx->io_pin) hipHostFree(ctx->io_pin);
@@ -2813,6 +2810,31 @@ int sdx_divide_dev(sdx_ctx* ctx, int64_t n, const double* a, const double* b, do
     return check_launch("k_divide");
 }
 
+// ---- checks the instrument entries share ---------------------------------------------------------------------------------------------
+// An output is none of the inputs and none of the other outputs (null pointers are no buffers).  With `own`, the entry's one message
+// for both; without, the two messages of the tangent entries.
+static int distinct_buffers(const char* name, const double* const* ins, int n_ins, const double* const* outs, int n_outs,
+                            const char* own = nullptr)
+{
+    for (int a = 0; a < n_outs; ++a) {
+        if (!outs[a]) continue;
+        for (int b = 0; b < n_ins; ++b)
+            if (outs[a] == ins[b]) return fail(SDX_ERR_ARG, std::string(name) + (own ? own : ": not in place (an output must not be one of the inputs)"));
+        for (int b = a + 1; b < n_outs; ++b)
+            if (outs[a] == outs[b]) return fail(SDX_ERR_ARG, std::string(name) + (own ? own : ": the outputs must be buffers of their own"));
+    }
+    return SDX_OK;
+}
+
+// what no kernel can check: the host-buffer twins do, before any upload
+static int ascending_check(const char* name, const char* what, int64_t n, const double* x)
+{
+    for (int64_t i = 0; i < n; ++i)
+        if (!(std::isfinite(x[i]) && (i == 0 || x[i - 1] < x[i])))
+            return fail(SDX_ERR_ARG, std::string(name) + ": " + what + " must be finite and strictly ascending");
+    return SDX_OK;
+}
+
 // ---- the instrument model (k_observe): Doppler shift, line-spread function and pixel integration in one launch ------------------
 int sdx_observe_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
                     const double* edges, const double* sigma, const double* doppler_dev, double* out)
@@ -2836,10 +2858,9 @@ int sdx_observe_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double
 static int observe_host_check(int64_t n, const double* lambdas, int64_t n_pix, const double* edges, const double* sigma, double doppler)
 {
     REQUIRE(std::isfinite(doppler) && doppler > 0.0, "observe: doppler must be finite and > 0");
-    for (int64_t i = 0; i < n; ++i)
-        REQUIRE(std::isfinite(lambdas[i]) && (i == 0 || lambdas[i - 1] < lambdas[i]), "observe: lambdas must be finite and strictly ascending");
-    for (int64_t j = 0; j <= n_pix; ++j)
-        REQUIRE(std::isfinite(edges[j]) && (j == 0 || edges[j - 1] < edges[j]), "observe: edges must be finite and strictly ascending");
+    int rc;
+    if ((rc = ascending_check("observe", "lambdas", n, lambdas))) return rc;
+    if ((rc = ascending_check("observe", "edges", n_pix + 1, edges))) return rc;
     for (int64_t j = 0; j < n_pix; ++j) REQUIRE(std::isfinite(sigma[j]) && sigma[j] > 0.0, "observe: sigma must be finite and > 0");
     return SDX_OK;
 }
@@ -2885,12 +2906,7 @@ static int observe_tangent_check(sdx_ctx* ctx, int64_t n, const double* lambdas,
     REQUIRE(!dflux == !dout_flux, "observe_tangent: dflux and dout_flux go together");
     const double* const ins[7] = {lambdas, flux, reference, edges, sigma, dflux, dreference};
     const double* const outs[4] = {out, dout_velocity, dout_lsf, dout_flux};
-    for (int a = 0; a < 4; ++a) {
-        if (!outs[a]) continue;
-        for (int b = 0; b < 7; ++b) REQUIRE(outs[a] != ins[b], "observe_tangent: not in place (an output must not be one of the inputs)");
-        for (int b = a + 1; b < 4; ++b) REQUIRE(outs[a] != outs[b], "observe_tangent: the outputs must be buffers of their own");
-    }
-    return SDX_OK;
+    return distinct_buffers("observe_tangent", ins, 7, outs, 4);
 }
 
 int sdx_observe_tangent_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, int64_t n_pix,
@@ -3067,7 +3083,8 @@ int sdx_observe_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, cons
     return io.finish();
 }
 
-// ---- rotational broadening (k_rotate) and its adjoint (k_rotate_adjoint_den, k_rotate_adjoint) ---------------------------------------
+// ---- the broadening stages: rotation (k_rotate, k_rotate_tangent), the cell-integrated profile (k_rotate_integrated) and
+// radial-tangential macroturbulence (k_macroturbulence), each with its adjoint (k_*_adjoint_den, k_*_adjoint) ---------------------------
 // one wave per grid point (the last group's waves included: a short group is done by its first wave alone)
 static unsigned rotate_blocks(int64_t n)
 {
@@ -3075,6 +3092,85 @@ static unsigned rotate_blocks(int64_t n)
     return (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
 }
 
+// The adjoint of a stage, under its stage name ("k_" and the entry's name): a = u / den into the context's scratch, then the gather.
+// An adjoint consumes its rows between its own two launches on the context's one stream, so the stages share the scratch.
+typedef void (*StageDenKernel)(int64_t, const double*, const double*, const double*, const double*, double*, double*);
+typedef void (*StageGatherKernel)(int64_t, const double*, const double*, const double*, const double*, const double*, double*, double*);
+static int stage_adjoint(sdx_ctx* ctx, const char* stage, const char* scalars_name, StageDenKernel den, StageGatherKernel gather, int64_t n,
+                         const double* lambdas, const double* scalars, const double* u, const double* u_reference, const double* nus, double* w,
+                         double* w_reference)
+{
+    const auto msg = [&](const char* text) { return std::string(stage + 2) + text; };
+    REQUIRE(ctx, msg(": null context"));
+    REQUIRE(n >= 2, msg(": the grid needs at least two points (n >= 2)"));
+    REQUIRE(lambdas && scalars && u && w, msg(": null pointer (lambdas, ") + scalars_name + ", u and w are required)");
+    REQUIRE(!u_reference == !w_reference, msg(": u_reference and w_reference go together"));
+    REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), msg(": too many points for one launch"));
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t row = ((size_t)n * sizeof(double) + 255) & ~(size_t)255;
+    int rc = ensure(ctx, &ctx->stage_ws, &ctx->stage_ws_bytes, 2 * row);
+    if (rc) return rc;
+    double* const a = (double*)ctx->stage_ws;
+    double* const a_ref = (double*)((char*)ctx->stage_ws + row);
+    {
+        LaunchScope ls(ctx, stage);
+        hipLaunchKernelGGL(den, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, scalars, u, u_reference, a, a_ref);
+        hipLaunchKernelGGL(gather, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, scalars, (const double*)a,
+                           u_reference ? (const double*)a_ref : nullptr, nus, w, w_reference);
+    }
+    return check_launch(stage);
+}
+
+// The host-buffer twin of a stage's forward entry: the grid, flux, reference and the stage's scalars (a device row) go up, up to six
+// grid-sized outputs, each optional, come back.  dev: the device entry, on device addresses, its outputs in the order of outs.
+typedef int (*StageForwardDev)(sdx_ctx*, int64_t, const double*, const double*, const double*, const double*, double* const*);
+static int stage_forward_host(sdx_ctx* ctx, StageForwardDev dev, int64_t n, const double* lambdas, const double* flux, const double* reference,
+                              const double* scalars, int n_scalars, double* const* outs, int n_outs)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
+    const double *d_l, *d_f, *d_r, *d_s;
+    double* d_o[6];
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(flux, grid, &d_f);
+    plan.in(reference, grid, &d_r);
+    plan.in(scalars, (size_t)n_scalars * f8, &d_s);
+    for (int k = 0; k < n_outs; ++k) plan.out(outs[k], grid, &d_o[k]);
+    HostIo io{ctx};
+    int rc;
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = dev(ctx, n, d_l, d_f, d_r, d_s, d_o))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+// The twin of a stage's adjoint entry (the three have one signature)
+typedef int (*StageAdjointDev)(sdx_ctx*, int64_t, const double*, const double*, const double*, const double*, const double*, double*, double*);
+static int stage_adjoint_host(sdx_ctx* ctx, StageAdjointDev dev, int64_t n, const double* lambdas, const double* scalars, int n_scalars,
+                              const double* u, const double* u_reference, const double* nus, double* w, double* w_reference)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
+    const double *d_l, *d_s, *d_u, *d_ur, *d_nus;
+    double *d_w, *d_wr;
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(scalars, (size_t)n_scalars * f8, &d_s);
+    plan.in(u, grid, &d_u);
+    plan.in(u_reference, grid, &d_ur);
+    plan.in(nus, grid, &d_nus);
+    plan.out(w, grid, &d_w);
+    plan.out(w_reference, grid, &d_wr);
+    HostIo io{ctx};
+    int rc;
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = dev(ctx, n, d_l, d_s, d_u, d_ur, d_nus, d_w, d_wr))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+// ---- rotational broadening (k_rotate) and its adjoint
 int sdx_rotate_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, const double* rot_dev,
                    double* out, double* out_reference)
 {
@@ -3082,8 +3178,10 @@ int sdx_rotate_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double*
     REQUIRE(n >= 2, "rotate: the grid needs at least two points (n >= 2)");
     REQUIRE(lambdas && flux && rot_dev && out, "rotate: null pointer (lambdas, flux, rot_dev and out are required)");
     REQUIRE(!reference == !out_reference, "rotate: reference and out_reference go together");
-    REQUIRE(out != flux && out != reference && out_reference != flux && (!reference || out_reference != reference) && out != out_reference,
-            "rotate: not in place (out and out_reference must be buffers of their own)");
+    const double* const ins[2] = {flux, reference};
+    const double* const outs[2] = {out, out_reference};
+    int rc;
+    if ((rc = distinct_buffers("rotate", ins, 2, outs, 2, ": not in place (out and out_reference must be buffers of their own)"))) return rc;
     REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "rotate: too many points for one launch");
     HIP_TRY(hipSetDevice(ctx->device));
     {
@@ -3096,24 +3194,8 @@ int sdx_rotate_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double*
 int sdx_rotate_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* rot_dev, const double* u, const double* u_reference,
                            const double* nus, double* w, double* w_reference)
 {
-    REQUIRE(ctx, "rotate_adjoint: null context");
-    REQUIRE(n >= 2, "rotate_adjoint: the grid needs at least two points (n >= 2)");
-    REQUIRE(lambdas && rot_dev && u && w, "rotate_adjoint: null pointer (lambdas, rot_dev, u and w are required)");
-    REQUIRE(!u_reference == !w_reference, "rotate_adjoint: u_reference and w_reference go together");
-    REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "rotate_adjoint: too many points for one launch");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t row = ((size_t)n * sizeof(double) + 255) & ~(size_t)255;
-    int rc = ensure(ctx, &ctx->rot_ws, &ctx->rot_ws_bytes, 2 * row);
-    if (rc) return rc;
-    double* const a = (double*)ctx->rot_ws;
-    double* const a_ref = (double*)((char*)ctx->rot_ws + row);
-    {
-        LaunchScope ls(ctx, "k_rotate_adjoint");
-        hipLaunchKernelGGL(k_rotate_adjoint_den, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, rot_dev, u, u_reference, a, a_ref);
-        hipLaunchKernelGGL(k_rotate_adjoint, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, rot_dev, (const double*)a,
-                           u_reference ? (const double*)a_ref : nullptr, nus, w, w_reference);
-    }
-    return check_launch("k_rotate_adjoint");
+    return stage_adjoint(ctx, "k_rotate_adjoint", "rot_dev", k_rotate_adjoint_den, k_rotate_adjoint, n, lambdas, rot_dev, u, u_reference, nus, w,
+                         w_reference);
 }
 
 // what the kernels cannot check: the host-buffer twins do, before any upload
@@ -3121,9 +3203,7 @@ static int rotate_host_check(int64_t n, const double* lambdas, double v_rot, dou
 {
     REQUIRE(std::isfinite(v_rot) && v_rot >= 0.0 && v_rot < 3000.0, "rotate: v_rot must be finite with 0 <= v_rot < 3000 km/s");
     REQUIRE(limb_darkening >= 0.0 && limb_darkening <= 1.0, "rotate: limb_darkening must lie in [0, 1]");
-    for (int64_t i = 0; i < n; ++i)
-        REQUIRE(std::isfinite(lambdas[i]) && (i == 0 || lambdas[i - 1] < lambdas[i]), "rotate: lambdas must be finite and strictly ascending");
-    return SDX_OK;
+    return ascending_check("rotate", "lambdas", n, lambdas);
 }
 
 int sdx_rotate_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, double v_rot,
@@ -3135,23 +3215,27 @@ int sdx_rotate_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double*
     REQUIRE(!reference == !out_reference, "rotate: reference and out_reference go together");
     int rc;
     if ((rc = rotate_host_check(n, lambdas, v_rot, limb_darkening))) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
     const double pair[2] = {v_rot, limb_darkening};
-    const double *d_l, *d_f, *d_r, *d_rot;
-    double *d_o, *d_or;
-    HostPlan plan;
-    plan.in(lambdas, grid, &d_l);
-    plan.in(flux, grid, &d_f);
-    plan.in(reference, grid, &d_r);
-    plan.in(pair, 2 * f8, &d_rot);
-    plan.out(out, grid, &d_o);
-    plan.out(out_reference, grid, &d_or);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_rotate_dev(ctx, n, d_l, d_f, d_r, d_rot, d_o, d_or))) return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    double* const outs[2] = {out, out_reference};
+    return stage_forward_host(
+        ctx,
+        [](sdx_ctx* c, int64_t m, const double* l, const double* f, const double* r, const double* rot, double* const* o) {
+            return sdx_rotate_dev(c, m, l, f, r, rot, o[0], o[1]);
+        },
+        n, lambdas, flux, reference, pair, 2, outs, 2);
+}
+
+int sdx_rotate_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, double v_rot, double limb_darkening, const double* u,
+                           const double* u_reference, const double* nus, double* w, double* w_reference)
+{
+    REQUIRE(ctx, "rotate_adjoint: null context");
+    REQUIRE(n >= 2, "rotate_adjoint: the grid needs at least two points (n >= 2)");
+    REQUIRE(lambdas && u && w, "rotate_adjoint: null pointer (lambdas, u and w are required)");
+    REQUIRE(!u_reference == !w_reference, "rotate_adjoint: u_reference and w_reference go together");
+    int rc;
+    if ((rc = rotate_host_check(n, lambdas, v_rot, limb_darkening))) return rc;
+    const double pair[2] = {v_rot, limb_darkening};
+    return stage_adjoint_host(ctx, sdx_rotate_adjoint_dev, n, lambdas, pair, 2, u, u_reference, nus, w, w_reference);
 }
 
 // ---- rotation with its derivative to the limb-darkening coefficient (k_rotate_tangent: k_rotate's body with the derivative flag) ----
@@ -3165,12 +3249,7 @@ static int rotate_tangent_check(sdx_ctx* ctx, int64_t n, const double* lambdas, 
     REQUIRE(!dout_eps_reference || reference, "rotate_tangent: dout_eps_reference needs a reference");
     const double* const ins[3] = {lambdas, flux, reference};
     const double* const outs[4] = {out, out_reference, dout_eps, dout_eps_reference};
-    for (int a = 0; a < 4; ++a) {
-        if (!outs[a]) continue;
-        for (int b = 0; b < 3; ++b) REQUIRE(outs[a] != ins[b], "rotate_tangent: not in place (an output must not be one of the inputs)");
-        for (int b = a + 1; b < 4; ++b) REQUIRE(outs[a] != outs[b], "rotate_tangent: the outputs must be buffers of their own");
-    }
-    return SDX_OK;
+    return distinct_buffers("rotate_tangent", ins, 3, outs, 4);
 }
 
 int sdx_rotate_tangent_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, const double* rot_dev,
@@ -3195,58 +3274,17 @@ int sdx_rotate_tangent_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const
     int rc;
     if ((rc = rotate_tangent_check(ctx, n, lambdas, flux, reference, out, out_reference, dout_eps, dout_eps_reference))) return rc;
     if ((rc = rotate_host_check(n, lambdas, v_rot, limb_darkening))) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
     const double pair[2] = {v_rot, limb_darkening};
-    const double *d_l, *d_f, *d_r, *d_rot;
-    double *d_o, *d_or, *d_d, *d_dr;
-    HostPlan plan;
-    plan.in(lambdas, grid, &d_l);
-    plan.in(flux, grid, &d_f);
-    plan.in(reference, grid, &d_r);
-    plan.in(pair, 2 * f8, &d_rot);
-    plan.out(out, grid, &d_o);
-    plan.out(out_reference, grid, &d_or);
-    plan.out(dout_eps, grid, &d_d);
-    plan.out(dout_eps_reference, grid, &d_dr);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_rotate_tangent_dev(ctx, n, d_l, d_f, d_r, d_rot, d_o, d_or, d_d, d_dr))) return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
-}
-
-int sdx_rotate_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, double v_rot, double limb_darkening, const double* u,
-                           const double* u_reference, const double* nus, double* w, double* w_reference)
-{
-    REQUIRE(ctx, "rotate_adjoint: null context");
-    REQUIRE(n >= 2, "rotate_adjoint: the grid needs at least two points (n >= 2)");
-    REQUIRE(lambdas && u && w, "rotate_adjoint: null pointer (lambdas, u and w are required)");
-    REQUIRE(!u_reference == !w_reference, "rotate_adjoint: u_reference and w_reference go together");
-    int rc;
-    if ((rc = rotate_host_check(n, lambdas, v_rot, limb_darkening))) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
-    const double pair[2] = {v_rot, limb_darkening};
-    const double *d_l, *d_rot, *d_u, *d_ur, *d_nus;
-    double *d_w, *d_wr;
-    HostPlan plan;
-    plan.in(lambdas, grid, &d_l);
-    plan.in(pair, 2 * f8, &d_rot);
-    plan.in(u, grid, &d_u);
-    plan.in(u_reference, grid, &d_ur);
-    plan.in(nus, grid, &d_nus);
-    plan.out(w, grid, &d_w);
-    plan.out(w_reference, grid, &d_wr);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_rotate_adjoint_dev(ctx, n, d_l, d_rot, d_u, d_ur, d_nus, d_w, d_wr))) return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    double* const outs[4] = {out, out_reference, dout_eps, dout_eps_reference};
+    return stage_forward_host(
+        ctx,
+        [](sdx_ctx* c, int64_t m, const double* l, const double* f, const double* r, const double* rot, double* const* o) {
+            return sdx_rotate_tangent_dev(c, m, l, f, r, rot, o[0], o[1], o[2], o[3]);
+        },
+        n, lambdas, flux, reference, pair, 2, outs, 4);
 }
 
 // ---- the cell-integrated rotation profile (k_rotate_integrated), its adjoint and the moments' test entry ------------------------------
-// (k_rotate's launch geometry and the rotation adjoint's scratch: rotate_blocks, rot_ws)
 static int rotate_integrated_check(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, const double* out,
                                    const double* out_reference, const double* dout_lnv, const double* dout_lnv_reference,
                                    const double* dout_eps, const double* dout_eps_reference)
@@ -3259,12 +3297,7 @@ static int rotate_integrated_check(sdx_ctx* ctx, int64_t n, const double* lambda
             "rotate_integrated: dout_lnv_reference and dout_eps_reference need a reference");
     const double* const ins[3] = {lambdas, flux, reference};
     const double* const outs[6] = {out, out_reference, dout_lnv, dout_lnv_reference, dout_eps, dout_eps_reference};
-    for (int a = 0; a < 6; ++a) {
-        if (!outs[a]) continue;
-        for (int b = 0; b < 3; ++b) REQUIRE(outs[a] != ins[b], "rotate_integrated: not in place (an output must not be one of the inputs)");
-        for (int b = a + 1; b < 6; ++b) REQUIRE(outs[a] != outs[b], "rotate_integrated: the outputs must be buffers of their own");
-    }
-    return SDX_OK;
+    return distinct_buffers("rotate_integrated", ins, 3, outs, 6);
 }
 
 int sdx_rotate_integrated_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference,
@@ -3293,25 +3326,8 @@ int sdx_rotate_integrated_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, co
 int sdx_rotate_integrated_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* rot_dev, const double* u,
                                       const double* u_reference, const double* nus, double* w, double* w_reference)
 {
-    REQUIRE(ctx, "rotate_integrated_adjoint: null context");
-    REQUIRE(n >= 2, "rotate_integrated_adjoint: the grid needs at least two points (n >= 2)");
-    REQUIRE(lambdas && rot_dev && u && w, "rotate_integrated_adjoint: null pointer (lambdas, rot_dev, u and w are required)");
-    REQUIRE(!u_reference == !w_reference, "rotate_integrated_adjoint: u_reference and w_reference go together");
-    REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "rotate_integrated_adjoint: too many points for one launch");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t row = ((size_t)n * sizeof(double) + 255) & ~(size_t)255;
-    int rc = ensure(ctx, &ctx->rot_ws, &ctx->rot_ws_bytes, 2 * row);
-    if (rc) return rc;
-    double* const a = (double*)ctx->rot_ws;
-    double* const a_ref = (double*)((char*)ctx->rot_ws + row);
-    {
-        LaunchScope ls(ctx, "k_rotate_integrated_adjoint");
-        hipLaunchKernelGGL(k_rotate_integrated_adjoint_den, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, rot_dev, u,
-                           u_reference, a, a_ref);
-        hipLaunchKernelGGL(k_rotate_integrated_adjoint, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, rot_dev, (const double*)a,
-                           u_reference ? (const double*)a_ref : nullptr, nus, w, w_reference);
-    }
-    return check_launch("k_rotate_integrated_adjoint");
+    return stage_adjoint(ctx, "k_rotate_integrated_adjoint", "rot_dev", k_rotate_integrated_adjoint_den, k_rotate_integrated_adjoint, n, lambdas,
+                         rot_dev, u, u_reference, nus, w, w_reference);
 }
 
 int sdx_rotate_integrated_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, double v_rot,
@@ -3323,27 +3339,14 @@ int sdx_rotate_integrated_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, co
                                       dout_eps_reference)))
         return rc;
     if ((rc = rotate_host_check(n, lambdas, v_rot, limb_darkening))) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
     const double pair[2] = {v_rot, limb_darkening};
-    const double *d_l, *d_f, *d_r, *d_rot;
-    double *d_o, *d_or, *d_v, *d_vr, *d_e, *d_er;
-    HostPlan plan;
-    plan.in(lambdas, grid, &d_l);
-    plan.in(flux, grid, &d_f);
-    plan.in(reference, grid, &d_r);
-    plan.in(pair, 2 * f8, &d_rot);
-    plan.out(out, grid, &d_o);
-    plan.out(out_reference, grid, &d_or);
-    plan.out(dout_lnv, grid, &d_v);
-    plan.out(dout_lnv_reference, grid, &d_vr);
-    plan.out(dout_eps, grid, &d_e);
-    plan.out(dout_eps_reference, grid, &d_er);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_rotate_integrated_dev(ctx, n, d_l, d_f, d_r, d_rot, d_o, d_or, d_v, d_vr, d_e, d_er))) return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    double* const outs[6] = {out, out_reference, dout_lnv, dout_lnv_reference, dout_eps, dout_eps_reference};
+    return stage_forward_host(
+        ctx,
+        [](sdx_ctx* c, int64_t m, const double* l, const double* f, const double* r, const double* rot, double* const* o) {
+            return sdx_rotate_integrated_dev(c, m, l, f, r, rot, o[0], o[1], o[2], o[3], o[4], o[5]);
+        },
+        n, lambdas, flux, reference, pair, 2, outs, 6);
 }
 
 int sdx_rotate_integrated_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, double v_rot, double limb_darkening, const double* u,
@@ -3355,24 +3358,8 @@ int sdx_rotate_integrated_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lam
     REQUIRE(!u_reference == !w_reference, "rotate_integrated_adjoint: u_reference and w_reference go together");
     int rc;
     if ((rc = rotate_host_check(n, lambdas, v_rot, limb_darkening))) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
     const double pair[2] = {v_rot, limb_darkening};
-    const double *d_l, *d_rot, *d_u, *d_ur, *d_nus;
-    double *d_w, *d_wr;
-    HostPlan plan;
-    plan.in(lambdas, grid, &d_l);
-    plan.in(pair, 2 * f8, &d_rot);
-    plan.in(u, grid, &d_u);
-    plan.in(u_reference, grid, &d_ur);
-    plan.in(nus, grid, &d_nus);
-    plan.out(w, grid, &d_w);
-    plan.out(w_reference, grid, &d_wr);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_rotate_integrated_adjoint_dev(ctx, n, d_l, d_rot, d_u, d_ur, d_nus, d_w, d_wr))) return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    return stage_adjoint_host(ctx, sdx_rotate_integrated_adjoint_dev, n, lambdas, pair, 2, u, u_reference, nus, w, w_reference);
 }
 
 // the moments of one cell, point by point (k_rotate_moments): what rot_cell evaluates
@@ -3412,8 +3399,7 @@ int sdx_rotate_moments_f64(sdx_ctx* ctx, int64_t n, const double* ya, const doub
     return io.finish();
 }
 
-// ---- radial-tangential macroturbulence (k_macroturbulence) and its adjoint (k_macroturbulence_adjoint_den, k_macroturbulence_adjoint) ----
-// (k_rotate's launch geometry: rotate_blocks)
+// ---- radial-tangential macroturbulence (k_macroturbulence) and its adjoint -------------------------------------------------------------
 int sdx_macroturbulence_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, const double* mac_dev,
                             double* out, double* out_reference, double* dout, double* dout_reference)
 {
@@ -3423,13 +3409,11 @@ int sdx_macroturbulence_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, cons
     REQUIRE(!reference == !out_reference, "macroturbulence: reference and out_reference go together");
     REQUIRE(!dout_reference || reference, "macroturbulence: dout_reference needs a reference");
     const double* const ins[4] = {lambdas, flux, reference, mac_dev};
-    double* const outs[4] = {out, out_reference, dout, dout_reference};
-    for (int a = 0; a < 4; ++a) {
-        if (!outs[a]) continue;
-        for (int b = 0; b < 4; ++b)
-            REQUIRE(outs[a] != ins[b] && (b <= a || outs[a] != outs[b]),
-                    "macroturbulence: not in place (out, out_reference, dout and dout_reference must be buffers of their own)");
-    }
+    const double* const outs[4] = {out, out_reference, dout, dout_reference};
+    int rc;
+    if ((rc = distinct_buffers("macroturbulence", ins, 4, outs, 4,
+                               ": not in place (out, out_reference, dout and dout_reference must be buffers of their own)")))
+        return rc;
     REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "macroturbulence: too many points for one launch");
     HIP_TRY(hipSetDevice(ctx->device));
     {
@@ -3440,41 +3424,24 @@ int sdx_macroturbulence_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, cons
     return check_launch("k_macroturbulence");
 }
 
+// (this adjoint alone refuses outputs that alias its inputs; the rotation adjoints never did)
 int sdx_macroturbulence_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* mac_dev, const double* u,
                                     const double* u_reference, const double* nus, double* w, double* w_reference)
 {
-    REQUIRE(ctx, "macroturbulence_adjoint: null context");
-    REQUIRE(n >= 2, "macroturbulence_adjoint: the grid needs at least two points (n >= 2)");
-    REQUIRE(lambdas && mac_dev && u && w, "macroturbulence_adjoint: null pointer (lambdas, mac_dev, u and w are required)");
-    REQUIRE(!u_reference == !w_reference, "macroturbulence_adjoint: u_reference and w_reference go together");
     const double* const ins[5] = {lambdas, mac_dev, u, u_reference, nus};
-    for (int b = 0; b < 5; ++b)
-        REQUIRE(w != ins[b] && (!w_reference || w_reference != ins[b]) && w != w_reference,
-                "macroturbulence_adjoint: not in place (w and w_reference must be buffers of their own)");
-    REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "macroturbulence_adjoint: too many points for one launch");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t row = ((size_t)n * sizeof(double) + 255) & ~(size_t)255;
-    int rc = ensure(ctx, &ctx->mac_ws, &ctx->mac_ws_bytes, 2 * row);
-    if (rc) return rc;
-    double* const a = (double*)ctx->mac_ws;
-    double* const a_ref = (double*)((char*)ctx->mac_ws + row);
-    {
-        LaunchScope ls(ctx, "k_macroturbulence_adjoint");
-        hipLaunchKernelGGL(k_macroturbulence_adjoint_den, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, mac_dev, u, u_reference,
-                           a, a_ref);
-        hipLaunchKernelGGL(k_macroturbulence_adjoint, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, mac_dev, (const double*)a,
-                           u_reference ? (const double*)a_ref : nullptr, nus, w, w_reference);
-    }
-    return check_launch("k_macroturbulence_adjoint");
+    const double* const outs[2] = {w, w_reference};
+    int rc;
+    if ((rc = distinct_buffers("macroturbulence_adjoint", ins, 5, outs, 2, ": not in place (w and w_reference must be buffers of their own)")))
+        return rc;
+    return stage_adjoint(ctx, "k_macroturbulence_adjoint", "mac_dev", k_macroturbulence_adjoint_den, k_macroturbulence_adjoint, n, lambdas, mac_dev,
+                         u, u_reference, nus, w, w_reference);
 }
 
 // what the kernels cannot check: the host-buffer twins do, before any upload
 static int macroturbulence_host_check(int64_t n, const double* lambdas, double zeta)
 {
     REQUIRE(std::isfinite(zeta) && zeta >= 0.0 && zeta < 500.0, "macroturbulence: zeta must be finite with 0 <= zeta < 500 km/s");
-    for (int64_t i = 0; i < n; ++i)
-        REQUIRE(std::isfinite(lambdas[i]) && (i == 0 || lambdas[i - 1] < lambdas[i]), "macroturbulence: lambdas must be finite and strictly ascending");
-    return SDX_OK;
+    return ascending_check("macroturbulence", "lambdas", n, lambdas);
 }
 
 int sdx_macroturbulence_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, const double* flux, const double* reference, double zeta,
@@ -3487,24 +3454,13 @@ int sdx_macroturbulence_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, cons
     REQUIRE(!dout_reference || reference, "macroturbulence: dout_reference needs a reference");
     int rc;
     if ((rc = macroturbulence_host_check(n, lambdas, zeta))) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
-    const double *d_l, *d_f, *d_r, *d_mac;
-    double *d_o, *d_or, *d_d, *d_dr;
-    HostPlan plan;
-    plan.in(lambdas, grid, &d_l);
-    plan.in(flux, grid, &d_f);
-    plan.in(reference, grid, &d_r);
-    plan.in(&zeta, f8, &d_mac);
-    plan.out(out, grid, &d_o);
-    plan.out(out_reference, grid, &d_or);
-    plan.out(dout, grid, &d_d);
-    plan.out(dout_reference, grid, &d_dr);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_macroturbulence_dev(ctx, n, d_l, d_f, d_r, d_mac, d_o, d_or, d_d, d_dr))) return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    double* const outs[4] = {out, out_reference, dout, dout_reference};
+    return stage_forward_host(
+        ctx,
+        [](sdx_ctx* c, int64_t m, const double* l, const double* f, const double* r, const double* mac, double* const* o) {
+            return sdx_macroturbulence_dev(c, m, l, f, r, mac, o[0], o[1], o[2], o[3]);
+        },
+        n, lambdas, flux, reference, &zeta, 1, outs, 4);
 }
 
 int sdx_macroturbulence_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, double zeta, const double* u, const double* u_reference,
@@ -3516,23 +3472,7 @@ int sdx_macroturbulence_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambd
     REQUIRE(!u_reference == !w_reference, "macroturbulence_adjoint: u_reference and w_reference go together");
     int rc;
     if ((rc = macroturbulence_host_check(n, lambdas, zeta))) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), grid = (size_t)n * f8;
-    const double *d_l, *d_mac, *d_u, *d_ur, *d_nus;
-    double *d_w, *d_wr;
-    HostPlan plan;
-    plan.in(lambdas, grid, &d_l);
-    plan.in(&zeta, f8, &d_mac);
-    plan.in(u, grid, &d_u);
-    plan.in(u_reference, grid, &d_ur);
-    plan.in(nus, grid, &d_nus);
-    plan.out(w, grid, &d_w);
-    plan.out(w_reference, grid, &d_wr);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_macroturbulence_adjoint_dev(ctx, n, d_l, d_mac, d_u, d_ur, d_nus, d_w, d_wr))) return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    return stage_adjoint_host(ctx, sdx_macroturbulence_adjoint_dev, n, lambdas, &zeta, 1, u, u_reference, nus, w, w_reference);
 }
 
 // ================================================================================================ fused synthesis

@@ -37,6 +37,30 @@ def _ascending(name, a):
         raise ValueError(f"{name} must be a finite, strictly ascending 1-d array")
 
 
+def _addr(a):
+    """a device buffer's address: a DeviceArray or CUDA tensor through ptr_of, a raw address or None as it is"""
+    return a if isinstance(a, int) or a is None else ptr_of(a)
+
+
+def _host_ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _grid(lambdas):
+    """-> the grid as a contiguous fp64 vector, validated (ValueError): finite, strictly ascending, at least two points"""
+    lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
+    _ascending("lambdas", lam)
+    if lam.size < 2:
+        raise ValueError("lambdas must hold at least two points")
+    return lam
+
+
+def _public(outs):
+    """what a stage returns to the caller: the arrays that exist, the flux alone where it is the only one"""
+    res = tuple(a for a in outs if a is not None)
+    return res[0] if len(res) == 1 else res
+
+
 def pixel_sigma(pixel_edges, resolving_power=None, sigma=None):
     """-> (edges, sigma): the validated pixel edges and the line-spread function's Gaussian width per pixel (Angstrom).  Exactly one of
     resolving_power (sigma_j = centre_j / (R 2 sqrt(2 ln 2))) and sigma is given, each a scalar or one value per pixel.  Needs no device."""
@@ -97,10 +121,7 @@ def _host_vector(name, a, n, what):
 def adjoint_host_arguments(n_pix, lambdas, pixel_weights, flux=None, reference=None, nus=None):
     """The host arrays of Instrument.adjoint_host, validated (ValueError naming the argument; needs no device) ->
     (lambdas, pixel_weights, flux, reference, nus), the optional ones None where not given."""
-    lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
-    _ascending("lambdas", lam)
-    if lam.size < 2:
-        raise ValueError("lambdas must hold at least two points")
+    lam = _grid(lambdas)
     c = _host_vector("pixel_weights", pixel_weights, n_pix, "pixel")
     if reference is not None and flux is None:
         raise ValueError("a reference needs the flux: the normalised pixel value enters the weights")
@@ -127,6 +148,7 @@ class Instrument:
     the column "v_rot" of parameter_tangents: it is differentiable in v sin i and tends to the identity as v sin i -> 0."""
 
     ROTATION_MODES = ("sampled", "integrated")
+    rotation, v_mac = ROTATION_MODES[0], None  # (the class's defaults; __init__ sets the instance's)
 
     def __init__(self, pixel_edges, resolving_power=None, sigma=None, ctx=None, v_rot=None, limb_darkening=0.6, v_mac=None,
                  rotation="sampled"):
@@ -147,7 +169,7 @@ class Instrument:
         self.d_out = self.ctx.empty((self.n_pix,))
         self.set_radial_velocity(0.0)
         self.v_rot, self.limb_darkening = None, float(limb_darkening)
-        self._scratch_n, self._scratch = 0, None
+        self._scratch_n, self._scratch, self._tangent_n = 0, None, 0
         if self.rotates:
             self.d_rot = self.ctx.empty((2,))
             self.set_rotation(*pair)
@@ -183,37 +205,59 @@ class Instrument:
             self._scratch = tuple(self.ctx.empty((n,)) for _ in range(4 * (self.rotates + self.macroturbulent)))
             self._scratch_n = n
 
+    def _pair(self, k, adjoint=False):
+        """the scratch pair of the instrument's k-th stage (rotation first): its broadened (flux, reference), or, with adjoint, the
+        k-th intermediate (weights, weights to the reference) of adjoint()"""
+        first = 4 * k + 2 * adjoint
+        return self._scratch[first], self._scratch[first + 1]
+
+    def _stage_out(self, k, n, reference, out, out_reference):
+        """where the k-th stage writes: the caller's buffers, else its scratch pair (sized here at first use); out_reference only with
+        a reference"""
+        self.reserve(n)
+        s, s_ref = self._pair(k)
+        return s if out is None else out, None if reference is None else (s_ref if out_reference is None else out_reference)
+
+    def _integrated(self):
+        """the rotation stage is the cell-integrated one"""
+        return self.rotation == "integrated"
+
+    def _stages(self):
+        """the stages the instrument has, in their order: (0: rotation / 1: macroturbulence, the stage on device buffers, on host arrays)"""
+        return ((0, self._rotate, self._rotate_host),) * self.rotates + ((1, self._macroturbulence, self._macroturbulence_host),) * self.macroturbulent
+
+    def _rotate(self, d_lambdas, n, flux, reference, out=None, out_reference=None):
+        """rotate() -> (out, out_reference or None)"""
+        out, out_reference = self._stage_out(0, n, reference, out, out_reference)
+        derivatives = (None,) * 4 if self._integrated() else ()
+        self.ctx.call("sdx_rotate_integrated_dev" if self._integrated() else "sdx_rotate_dev", int(n), _addr(d_lambdas), _addr(flux),
+                      _addr(reference), self.d_rot.ptr, _addr(out), _addr(out_reference), *derivatives)
+        return out, out_reference
+
     def rotate(self, d_lambdas, d_flux, n, reference=None, out=None, out_reference=None):
         """The rotation stage alone (sdx_rotate_dev): n points of (rest-frame wavelength, flux[, reference]) on the device -> the
         broadened flux, or (flux, reference) with a reference; into the instrument's scratch unless `out` (and out_reference) are given."""
         if not self.rotates:
             raise RuntimeError("no rotation: construct the Instrument with v_rot= (0 allowed)")
-        addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
-        self.reserve(n)
-        out = self._scratch[0] if out is None else out
-        if reference is None:
-            out_reference = None
-        elif out_reference is None:
-            out_reference = self._scratch[1]
-        if self._integrated():
-            self.ctx.call("sdx_rotate_integrated_dev", int(n), addr(d_lambdas), addr(d_flux), addr(reference), self.d_rot.ptr, addr(out),
-                          addr(out_reference), None, None, None, None)
-        else:
-            self.ctx.call("sdx_rotate_dev", int(n), addr(d_lambdas), addr(d_flux), addr(reference), self.d_rot.ptr, addr(out),
-                          addr(out_reference))
-        return out if reference is None else (out, out_reference)
+        return _public(self._rotate(d_lambdas, n, d_flux, reference, out, out_reference))
 
-    def _integrated(self):
-        """the rotation stage is the cell-integrated one (instruments built without the keyword are sampled)"""
-        return getattr(self, "rotation", "sampled") == "integrated"
+    def _rotate_host(self, lam, f, g):
+        """rotate_host() -> [out, out_reference or None]"""
+        entry, n_outs = ("sdx_rotate_integrated_f64", 6) if self._integrated() else ("sdx_rotate_f64", 2)
+        return _stage_host(self.ctx, entry, lam, f, g, (self.v_rot, self.limb_darkening), n_outs, 2)
 
     def rotate_host(self, lambdas, flux, reference=None):
         """numpy in, numpy out (sdx_rotate_f64, which checks the arrays): -> the broadened flux, or (flux, reference)."""
         if not self.rotates:
             raise RuntimeError("no rotation: construct the Instrument with v_rot= (0 allowed)")
-        if self._integrated():
-            return rotate_integrated_host(self.ctx, lambdas, flux, self.v_rot, self.limb_darkening, reference)
-        return rotate_host(self.ctx, lambdas, flux, self.v_rot, self.limb_darkening, reference)
+        return _public(self._rotate_host(lambdas, flux, reference))
+
+    def _macroturbulence(self, d_lambdas, n, flux, reference, out=None, out_reference=None, dout=None, dout_reference=None):
+        """macroturbulence() -> (out, out_reference or None)"""
+        out, out_reference = self._stage_out(int(self.rotates), n, reference, out, out_reference)  # (behind the rotation's scratch)
+        self.ctx.call("sdx_macroturbulence_dev", int(n), _addr(d_lambdas), _addr(flux), _addr(reference), self.d_mac.ptr, _addr(out),
+                      _addr(out_reference), _addr(dout), _addr(dout_reference))
+        return out, out_reference
 
     def macroturbulence(self, d_lambdas, d_flux, n, reference=None, out=None, out_reference=None, dout=None, dout_reference=None):
         """The macroturbulence stage alone (sdx_macroturbulence_dev): n points of (rest-frame wavelength, flux[, reference]) on the
@@ -222,39 +266,34 @@ class Instrument:
         same launch."""
         if not self.macroturbulent:
             raise RuntimeError("no macroturbulence: construct the Instrument with v_mac= (0 allowed)")
-        addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
-        self.reserve(n)
-        first = 4 if self.rotates else 0  # (behind the rotation's four)
-        out = self._scratch[first] if out is None else out
-        if reference is None:
-            out_reference = None
-        elif out_reference is None:
-            out_reference = self._scratch[first + 1]
-        self.ctx.call("sdx_macroturbulence_dev", int(n), addr(d_lambdas), addr(d_flux), addr(reference), self.d_mac.ptr, addr(out),
-                      addr(out_reference), addr(dout), addr(dout_reference))
-        return out if reference is None else (out, out_reference)
+        return _public(self._macroturbulence(d_lambdas, n, d_flux, reference, out, out_reference, dout, dout_reference))
+
+    def _macroturbulence_host(self, lam, f, g, derivative=False):
+        """macroturbulence_host() -> [out, out_reference or None], with derivative [.., dout, dout_reference or None]"""
+        return _stage_host(self.ctx, "sdx_macroturbulence_f64", lam, f, g, (self.v_mac,), 4, 4 if derivative else 2)
 
     def macroturbulence_host(self, lambdas, flux, reference=None, derivative=False):
         """numpy in, numpy out (sdx_macroturbulence_f64, which checks the arrays): -> the broadened flux, or (flux, reference);
         derivative=True appends d / d ln zeta of each."""
         if not self.macroturbulent:
             raise RuntimeError("no macroturbulence: construct the Instrument with v_mac= (0 allowed)")
-        return macroturbulence_host(self.ctx, lambdas, flux, self.v_mac, reference, derivative)
+        return _public(self._macroturbulence_host(lambdas, flux, reference, derivative))
+
+    def _broaden(self, d_lambdas, n, flux, reference):
+        """broaden() -> (flux, reference or None)"""
+        for _, stage, _ in self._stages():
+            flux, reference = stage(d_lambdas, n, flux, reference)
+        return flux, reference
 
     def broaden(self, d_lambdas, d_flux, n, reference=None):
         """The stages in front of k_observe in their order — rotation, then macroturbulence, whichever the instrument has — into the
         instrument's scratch -> the broadened flux, or (flux, reference) with a reference: what observe(..., broadened=True) takes."""
-        res = d_flux if reference is None else (d_flux, reference)
-        for on, stage in ((self.rotates, self.rotate), (self.macroturbulent, self.macroturbulence)):
-            if on:
-                res = stage(d_lambdas, res, n) if reference is None else stage(d_lambdas, res[0], n, res[1])
-        return res
+        return _public(self._broaden(d_lambdas, n, d_flux, reference))
 
     def _broaden_host(self, lam, f, g):
         """broaden() through the host-buffer twins -> (flux, reference or None)"""
-        for on, stage in ((self.rotates, self.rotate_host), (self.macroturbulent, self.macroturbulence_host)):
-            if on:
-                f, g = (stage(lam, f), None) if g is None else stage(lam, f, g)
+        for _, _, stage in self._stages():
+            f, g = stage(lam, f, g)
         return f, g
 
     def edge_affected(self, lambdas):
@@ -262,10 +301,9 @@ class Instrument:
         rest frame, comes within the broadening's reach of an end of the grid `lambdas` — lo (1 - beta) < lambdas[0] or hi (1 + beta) >
         lambdas[-1], beta = (v_rot + 6 v_mac) / c the combined reach of rotation and macroturbulence — so that a window of a point
         they may see is truncated there.  Without either (beta = 0) these are the pixels the grid does not cover.  Plain numpy."""
-        lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
-        _ascending("lambdas", lam)
+        lam = _grid(lambdas)
         beta = (self.v_rot or 0.0) / K.C_KMS
-        if getattr(self, "v_mac", None):
+        if self.v_mac:
             beta = ((self.v_rot or 0.0) + MACROTURBULENCE_REACH * self.v_mac) / K.C_KMS
         lo = (self.edges[:-1] - 8.0 * self.sigma) / self.doppler
         hi = (self.edges[1:] + 8.0 * self.sigma) / self.doppler
@@ -283,21 +321,18 @@ class Instrument:
         With rotation or macroturbulence, flux and reference are broadened first (broaden(), into the scratch: sized here at first
         use, or by reserve(n)); broadened=True says they are already — what broaden() returned — so that several outputs share one
         k_rotate and one k_macroturbulence."""
-        addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
         out = self.d_out if out is None else out
         if self.broadens and not broadened:
-            res = self.broaden(d_lambdas, d_flux, n, reference)
-            d_flux, reference = res if reference is not None else (res, None)
-        self.ctx.call("sdx_observe_dev", int(n), addr(d_lambdas), addr(d_flux), addr(reference), self.n_pix, self.d_edges.ptr,
+            d_flux, reference = self._broaden(d_lambdas, n, d_flux, reference)
+        self.ctx.call("sdx_observe_dev", int(n), _addr(d_lambdas), _addr(d_flux), _addr(reference), self.n_pix, self.d_edges.ptr,
                       self.d_sigma.ptr, self.d_doppler.ptr, out.ptr)
         return out
 
     def observe_host(self, lambdas, flux, reference=None):
         """numpy in, numpy out: (n,) wavelengths (ascending, Angstrom) and flux -> (n_pix,)."""
-        lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
+        lam = _grid(lambdas)
         f = np.ascontiguousarray(getattr(flux, "value", flux), dtype=np.float64).reshape(-1)
-        _ascending("lambdas", lam)
-        if lam.size < 2 or f.size != lam.size:
+        if f.size != lam.size:
             raise ValueError("lambdas and flux must hold the same number of points, at least two")
         d_ref = None
         if reference is not None:
@@ -323,7 +358,6 @@ class Instrument:
         enters), sdx_observe_adjoint_dev gives the weights over the BROADENED points, and sdx_rotate_adjoint_dev takes those back to
         the grid and applies nus — three stages where there was one, the scratch the instrument's (reserve(n)).  With
         macroturbulence sdx_macroturbulence_adjoint_dev stands between the two (the forward order reversed); the last stage applies nus."""
-        addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
         if reference is None and out_reference is not None and out_reference is not False:
             raise ValueError("out_reference needs a reference")
         if reference is not None and flux is None:
@@ -336,23 +370,26 @@ class Instrument:
         if self.broadens:
             self.reserve(n)
             if reference is not None:
-                flux, reference = self.broaden(d_lambdas, flux, n, reference)
-            u, u_ref = self._scratch[2], self._scratch[3] if out_reference is not None else None
-            self.ctx.call("sdx_observe_adjoint_dev", int(n), addr(d_lambdas), addr(flux) if reference is not None else None, addr(reference),
-                          self.n_pix, self.d_edges.ptr, self.d_sigma.ptr, self.d_doppler.ptr, addr(pixel_weights), None, u.ptr, addr(u_ref))
+                flux, reference = self._broaden(d_lambdas, n, flux, reference)
+            normal = out_reference is not None
+            u, u_ref = self._pair(0, adjoint=True)
+            u_ref = u_ref if normal else None
+            self.ctx.call("sdx_observe_adjoint_dev", int(n), _addr(d_lambdas), _addr(flux) if reference is not None else None, _addr(reference),
+                          self.n_pix, self.d_edges.ptr, self.d_sigma.ptr, self.d_doppler.ptr, _addr(pixel_weights), None, u.ptr, _addr(u_ref))
             if self.macroturbulent:
                 last = not self.rotates  # (the last stage writes the caller's buffers and applies nus)
-                t, t_ref = (out, out_reference) if last else (self._scratch[6], self._scratch[7] if out_reference is not None else None)
-                self.ctx.call("sdx_macroturbulence_adjoint_dev", int(n), addr(d_lambdas), self.d_mac.ptr, u.ptr, addr(u_ref),
-                              addr(nus) if last else None, addr(t), addr(t_ref))
+                t, t_ref = (out, out_reference) if last else self._pair(1, adjoint=True)
+                t_ref = t_ref if normal else None
+                self.ctx.call("sdx_macroturbulence_adjoint_dev", int(n), _addr(d_lambdas), self.d_mac.ptr, u.ptr, _addr(u_ref),
+                              _addr(nus) if last else None, _addr(t), _addr(t_ref))
                 u, u_ref = t, t_ref
             if self.rotates:
-                self.ctx.call("sdx_rotate_integrated_adjoint_dev" if self._integrated() else "sdx_rotate_adjoint_dev", int(n), addr(d_lambdas), self.d_rot.ptr, u.ptr, addr(u_ref), addr(nus), addr(out),
-                              addr(out_reference))
+                self.ctx.call("sdx_rotate_integrated_adjoint_dev" if self._integrated() else "sdx_rotate_adjoint_dev", int(n), _addr(d_lambdas),
+                              self.d_rot.ptr, u.ptr, _addr(u_ref), _addr(nus), _addr(out), _addr(out_reference))
             return out if out_reference is None else (out, out_reference)
-        self.ctx.call("sdx_observe_adjoint_dev", int(n), addr(d_lambdas), addr(flux) if reference is not None else None, addr(reference),
-                      self.n_pix, self.d_edges.ptr, self.d_sigma.ptr, self.d_doppler.ptr, addr(pixel_weights), addr(nus), addr(out),
-                      addr(out_reference))
+        self.ctx.call("sdx_observe_adjoint_dev", int(n), _addr(d_lambdas), _addr(flux) if reference is not None else None, _addr(reference),
+                      self.n_pix, self.d_edges.ptr, self.d_sigma.ptr, self.d_doppler.ptr, _addr(pixel_weights), _addr(nus), _addr(out),
+                      _addr(out_reference))
         return out if out_reference is None else (out, out_reference)
 
     # -- forward mode: tangents of observe() ----------------------------------------------------------------------------------------
@@ -365,33 +402,28 @@ class Instrument:
         an instrument that never asks has none, and reserve() keeps its sizes.  Without rotation and macroturbulence there is none."""
         n = int(n)
         self.reserve(n)
-        if self.broadens and n > getattr(self, "_tangent_n", 0):
+        if self.broadens and n > self._tangent_n:
             self._tangent_scratch = tuple(self.ctx.empty((n,)) for _ in range(2 * (self.rotates + self.macroturbulent) + 2))
             self._tangent_n = n
+
+    def _tangent_pair(self, k):
+        """the tangent scratch: the pair that leaves the instrument's k-th stage; k = -1: the pair of a stage's own parameter derivative"""
+        return self._tangent_scratch[2 * k], self._tangent_scratch[2 * k + 1]
 
     def _push(self, d_lambdas, n, dflux, dreference, first_stage=0):
         """a tangent pair through the broadening stages from first_stage on (0: rotation, 1: macroturbulence), as a (flux, reference)
         pair of the stages themselves — they are linear in the flux and their denominators do not depend on it — into the tangent
         scratch -> (dflux, dreference or None) at the pixel stage's input"""
-        k = 0
-        for index, (on, stage) in enumerate(((self.rotates, self.rotate), (self.macroturbulent, self.macroturbulence))):
-            if not on:
-                continue
+        for k, (index, stage, _) in enumerate(self._stages()):
             if index >= first_stage:
-                t, t_ref = self._tangent_scratch[2 * k], self._tangent_scratch[2 * k + 1]
-                if dreference is None:
-                    dflux = stage(d_lambdas, dflux, n, out=t)
-                else:
-                    dflux, dreference = stage(d_lambdas, dflux, n, dreference, out=t, out_reference=t_ref)
-            k += 1
+                dflux, dreference = stage(d_lambdas, n, dflux, dreference, *self._tangent_pair(k))
         return dflux, dreference
 
     def _observe_tangent(self, d_lambdas, n, flux, reference, dflux=None, dreference=None, out=None, dout_velocity=None, dout_lsf=None,
                          dout_flux=None):
-        addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
-        self.ctx.call("sdx_observe_tangent_dev", int(n), addr(d_lambdas), addr(flux), addr(reference), self.n_pix, self.d_edges.ptr,
-                      self.d_sigma.ptr, self.d_doppler.ptr, addr(dflux), addr(dreference), addr(out), addr(dout_velocity), addr(dout_lsf),
-                      addr(dout_flux))
+        self.ctx.call("sdx_observe_tangent_dev", int(n), _addr(d_lambdas), _addr(flux), _addr(reference), self.n_pix, self.d_edges.ptr,
+                      self.d_sigma.ptr, self.d_doppler.ptr, _addr(dflux), _addr(dreference), _addr(out), _addr(dout_velocity), _addr(dout_lsf),
+                      _addr(dout_flux))
 
     def tangent(self, d_lambdas, n, flux, dflux, reference=None, dreference=None, out=None):
         """The Jacobian-vector product of observe(): the direction (dflux, dreference) of (flux, reference) on the grid -> the
@@ -408,8 +440,7 @@ class Instrument:
         out = self.ctx.empty((self.n_pix,)) if out is None else out
         if self.broadens:
             self.reserve_tangent(n)
-            res = self.broaden(d_lambdas, flux, n, reference)
-            flux, reference = res if reference is not None else (res, None)
+            flux, reference = self._broaden(d_lambdas, n, flux, reference)
             dflux, dreference = self._push(d_lambdas, n, dflux, dreference)
         self._observe_tangent(d_lambdas, n, flux, reference, dflux, dreference, dout_flux=out)
         return out
@@ -463,45 +494,40 @@ class Instrument:
         names = self._wrt(wrt)
         res = {name: self.ctx.empty((self.n_pix,)) for name in names}
         normal = reference is not None
+        d_par = d_par_ref = None  # a stage's own parameter derivative
         if self.broadens:
             self.reserve_tangent(n)
-        ts = getattr(self, "_tangent_scratch", ())
-        d_par, d_par_ref = (ts[-2], ts[-1] if normal else None) if ts else (None, None)
-        addr = lambda a: a if isinstance(a, int) or a is None else ptr_of(a)  # noqa: E731
+            d_par, d_par_ref = self._tangent_pair(-1)
+            d_par_ref = d_par_ref if normal else None
         f, g = flux, reference
         eps_f = eps_g = None  # d / d eps at the pixel stage's input
         lnv_f = lnv_g = None  # d / d ln v_rot at the pixel stage's input
-        if self.rotates:
-            if self._integrated() and ("limb_darkening" in names or "v_rot" in names):
-                # one launch of k_rotate_integrated gives the broadened pair and both derivatives
-                rf, rg = self._scratch[0], self._scratch[1] if normal else None
-                want_eps, want_v = "limb_darkening" in names, "v_rot" in names
+        want_eps, want_v = "limb_darkening" in names, "v_rot" in names  # (_wrt: "v_rot" with the integrated profile only)
+        if self.rotates and (want_eps or want_v):
+            # one launch gives the broadened pair and the derivatives: k_rotate_integrated both, k_rotate_tangent d / d eps
+            rf, rg = self._pair(0)
+            rg = rg if normal else None
+            if self._integrated():
                 d_lnv, d_lnv_ref = (self.ctx.empty((int(n),)), self.ctx.empty((int(n),)) if normal else None) if want_v else (None, None)
-                self.ctx.call("sdx_rotate_integrated_dev", int(n), addr(d_lambdas), addr(f), addr(g), self.d_rot.ptr, rf.ptr, addr(rg),
-                              addr(d_lnv), addr(d_lnv_ref), d_par.ptr if want_eps else None, addr(d_par_ref) if want_eps else None)
-                f, g = rf, rg
-                if want_eps:
-                    eps_f, eps_g = self._push(d_lambdas, n, d_par, d_par_ref, first_stage=1)
-                if want_v:
-                    lnv_f, lnv_g = d_lnv, d_lnv_ref
-                    if self.macroturbulent:  # (buffers of its own: the tangent scratch holds the limb darkening's pair)
-                        t, t_ref = self.ctx.empty((int(n),)), self.ctx.empty((int(n),)) if normal else None
-                        m = self.macroturbulence(d_lambdas, d_lnv, n, d_lnv_ref, out=t, out_reference=t_ref)
-                        lnv_f, lnv_g = m if normal else (m, None)
-            elif "limb_darkening" in names:
-                rf, rg = self._scratch[0], self._scratch[1] if normal else None
-                self.ctx.call("sdx_rotate_tangent_dev", int(n), addr(d_lambdas), addr(f), addr(g), self.d_rot.ptr, rf.ptr, addr(rg), d_par.ptr,
-                              addr(d_par_ref))
-                f, g = rf, rg
+                self.ctx.call("sdx_rotate_integrated_dev", int(n), _addr(d_lambdas), _addr(f), _addr(g), self.d_rot.ptr, rf.ptr, _addr(rg),
+                              _addr(d_lnv), _addr(d_lnv_ref), d_par.ptr if want_eps else None, _addr(d_par_ref) if want_eps else None)
+            else:
+                self.ctx.call("sdx_rotate_tangent_dev", int(n), _addr(d_lambdas), _addr(f), _addr(g), self.d_rot.ptr, rf.ptr, _addr(rg),
+                              d_par.ptr, _addr(d_par_ref))
+            f, g = rf, rg
+            if want_eps:
                 # (through the macroturbulence now: its own derivative takes the pair's place in the scratch below)
                 eps_f, eps_g = self._push(d_lambdas, n, d_par, d_par_ref, first_stage=1)
-            else:
-                r = self.rotate(d_lambdas, f, n, g)
-                f, g = r if normal else (r, None)
+            if want_v:
+                lnv_f, lnv_g = d_lnv, d_lnv_ref
+                if self.macroturbulent:  # (buffers of its own: the tangent scratch holds the limb darkening's pair)
+                    t, t_ref = self.ctx.empty((int(n),)), self.ctx.empty((int(n),)) if normal else None
+                    lnv_f, lnv_g = self._macroturbulence(d_lambdas, n, d_lnv, d_lnv_ref, out=t, out_reference=t_ref)
+        elif self.rotates:
+            f, g = self._rotate(d_lambdas, n, f, g)
         if self.macroturbulent:
             want = "v_mac" in names
-            b = self.macroturbulence(d_lambdas, f, n, g, dout=d_par if want else None, dout_reference=d_par_ref if want else None)
-            f, g = b if normal else (b, None)
+            f, g = self._macroturbulence(d_lambdas, n, f, g, dout=d_par if want else None, dout_reference=d_par_ref if want else None)
             if want:
                 per_ln, zeta = self.ctx.empty((self.n_pix,)), self.ctx.upload(np.full(self.n_pix, self.v_mac))
                 self._observe_tangent(d_lambdas, n, f, g, d_par, d_par_ref, dout_flux=per_ln)
@@ -521,10 +547,7 @@ class Instrument:
         sdx_observe_tangent_f64, which check the arrays) -> (n_pix,)."""
         if dreference is not None and reference is None:
             raise ValueError("dreference needs a reference")
-        lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
-        _ascending("lambdas", lam)
-        if lam.size < 2:
-            raise ValueError("lambdas must hold at least two points")
+        lam = _grid(lambdas)
         f, df = _host_vector("flux", flux, lam.size, "grid point"), _host_vector("dflux", dflux, lam.size, "grid point")
         g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
         dg = None if dreference is None else _host_vector("dreference", dreference, lam.size, "grid point")
@@ -534,51 +557,42 @@ class Instrument:
         return self._observe_tangent_host(lam, f, g, df, dg, flux_tangent=True)[0]
 
     def _observe_tangent_host(self, lam, f, g, df=None, dg=None, velocity=False, lsf=False, flux_tangent=False):
-        host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
         outs = [np.empty(self.n_pix) if on else None for on in (flux_tangent, velocity, lsf)]
-        self.ctx.call("sdx_observe_tangent_f64", lam.size, host(lam), host(f), host(g), self.n_pix, host(self.edges), host(self.sigma),
-                      float(self.doppler), host(df), host(dg), None, host(outs[1]), host(outs[2]), host(outs[0]))
+        self.ctx.call("sdx_observe_tangent_f64", lam.size, _host_ptr(lam), _host_ptr(f), _host_ptr(g), self.n_pix, _host_ptr(self.edges),
+                      _host_ptr(self.sigma), float(self.doppler), _host_ptr(df), _host_ptr(dg), None, _host_ptr(outs[1]), _host_ptr(outs[2]),
+                      _host_ptr(outs[0]))
         return outs
 
     def parameter_tangents_host(self, lambdas, flux, reference=None, wrt=None):
         """numpy in, numpy out: parameter_tangents() through the host-buffer twins -> {name: (n_pix,)}."""
         names = self._wrt(wrt)
-        lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
-        _ascending("lambdas", lam)
-        if lam.size < 2:
-            raise ValueError("lambdas must hold at least two points")
+        lam = _grid(lambdas)
         f = _host_vector("flux", flux, lam.size, "grid point")
         g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
-        host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
         res = {}
-        if self.rotates and self._integrated() and ("limb_darkening" in names or "v_rot" in names):
-            bf, bg, vf, vg, ef, eg = _unpack_integrated(rotate_integrated_host(self.ctx, lam, f, self.v_rot, self.limb_darkening, g, True), g)
-            through = lambda a, b: (a, b) if not self.macroturbulent else (  # noqa: E731
-                (self.macroturbulence_host(lam, a), None) if b is None else self.macroturbulence_host(lam, a, b))
+        want_eps, want_v = "limb_darkening" in names, "v_rot" in names  # (_wrt: "v_rot" with the integrated profile only)
+        if self.rotates and (want_eps or want_v):
+            # one launch gives the broadened pair and the derivatives: k_rotate_integrated both, k_rotate_tangent d / d eps
+            pair = (self.v_rot, self.limb_darkening)
+            if self._integrated():
+                bf, bg, vf, vg, ef, eg = _stage_host(self.ctx, "sdx_rotate_integrated_f64", lam, f, g, pair, 6, 6)
+            else:
+                bf, bg, ef, eg = _stage_host(self.ctx, "sdx_rotate_tangent_f64", lam, f, g, pair, 4, 4)
+            through = (lambda a, b: self._macroturbulence_host(lam, a, b)) if self.macroturbulent else (lambda a, b: (a, b))
             mf, mg = through(bf, bg)
-            if "limb_darkening" in names:
+            if want_eps:
                 res["limb_darkening"] = self._observe_tangent_host(lam, mf, mg, *through(ef, eg), flux_tangent=True)[0]
-            if "v_rot" in names:
+            if want_v:
                 res["v_rot"] = self._observe_tangent_host(lam, mf, mg, *through(vf, vg), flux_tangent=True)[0] / self.v_rot
-            f, g = bf, bg
+            f, g = (bf, bg) if self._integrated() else self._rotate_host(lam, f, g)
         elif self.rotates:
-            if "limb_darkening" in names:
-                o = [np.empty(lam.size) if (g is not None or k % 2 == 0) else None for k in range(4)]
-                self.ctx.call("sdx_rotate_tangent_f64", lam.size, host(lam), host(f), host(g), self.v_rot, self.limb_darkening,
-                              *(host(a) for a in o))
-                bf, bg, tf, tg = o
-                if self.macroturbulent:
-                    bf, bg = (self.macroturbulence_host(lam, bf), None) if bg is None else self.macroturbulence_host(lam, bf, bg)
-                    tf, tg = (self.macroturbulence_host(lam, tf), None) if tg is None else self.macroturbulence_host(lam, tf, tg)
-                res["limb_darkening"] = self._observe_tangent_host(lam, bf, bg, tf, tg, flux_tangent=True)[0]
-            f, g = (self.rotate_host(lam, f), None) if g is None else self.rotate_host(lam, f, g)
+            f, g = self._rotate_host(lam, f, g)
         if self.macroturbulent:
             if "v_mac" in names:
-                m = self.macroturbulence_host(lam, f, g, derivative=True)
-                f, g, tf, tg = (m[0], None, m[1], None) if g is None else m
+                f, g, tf, tg = self._macroturbulence_host(lam, f, g, derivative=True)
                 res["v_mac"] = self._observe_tangent_host(lam, f, g, tf, tg, flux_tangent=True)[0] / self.v_mac
             else:
-                f, g = (self.macroturbulence_host(lam, f), None) if g is None else self.macroturbulence_host(lam, f, g)
+                f, g = self._macroturbulence_host(lam, f, g)
         if "v_rad" in names or "lsf" in names:
             _, v, k = self._observe_tangent_host(lam, f, g, velocity="v_rad" in names, lsf="lsf" in names)
             if v is not None:
@@ -592,69 +606,53 @@ class Instrument:
         (and the flux) -> (weights to the flux, weights to the reference).  The host-buffer twin sdx_observe_adjoint_f64, which
         checks the arrays as observe_host's does."""
         lam, c, f, g, nu = adjoint_host_arguments(self.n_pix, lambdas, pixel_weights, flux, reference, nus)
-        host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
         w = np.empty(lam.size)
         w_ref = np.empty(lam.size) if g is not None else None
         if self.broadens:  # (the stages of adjoint(), each through its host-buffer twin)
             if g is not None:
                 f, g = self._broaden_host(lam, f, g)
             u, u_ref = np.empty(lam.size), np.empty(lam.size) if g is not None else None
-            self.ctx.call("sdx_observe_adjoint_f64", lam.size, host(lam), host(f), host(g), self.n_pix, host(self.edges), host(self.sigma),
-                          float(self.doppler), host(c), None, host(u), host(u_ref))
+            self.ctx.call("sdx_observe_adjoint_f64", lam.size, _host_ptr(lam), _host_ptr(f), _host_ptr(g), self.n_pix, _host_ptr(self.edges), _host_ptr(self.sigma),
+                          float(self.doppler), _host_ptr(c), None, _host_ptr(u), _host_ptr(u_ref))
             if self.macroturbulent:
                 last = not self.rotates
                 t, t_ref = (w, w_ref) if last else (np.empty(lam.size), np.empty(lam.size) if g is not None else None)
-                self.ctx.call("sdx_macroturbulence_adjoint_f64", lam.size, host(lam), self.v_mac, host(u), host(u_ref), host(nu) if last else None,
-                              host(t), host(t_ref))
+                self.ctx.call("sdx_macroturbulence_adjoint_f64", lam.size, _host_ptr(lam), self.v_mac, _host_ptr(u), _host_ptr(u_ref), _host_ptr(nu) if last else None,
+                              _host_ptr(t), _host_ptr(t_ref))
                 u, u_ref = t, t_ref
             if self.rotates:
-                self.ctx.call("sdx_rotate_integrated_adjoint_f64" if self._integrated() else "sdx_rotate_adjoint_f64", lam.size, host(lam), self.v_rot, self.limb_darkening, host(u), host(u_ref), host(nu),
-                              host(w), host(w_ref))
+                self.ctx.call("sdx_rotate_integrated_adjoint_f64" if self._integrated() else "sdx_rotate_adjoint_f64", lam.size, _host_ptr(lam),
+                              self.v_rot, self.limb_darkening, _host_ptr(u), _host_ptr(u_ref), _host_ptr(nu), _host_ptr(w), _host_ptr(w_ref))
             return w if w_ref is None else (w, w_ref)
-        self.ctx.call("sdx_observe_adjoint_f64", lam.size, host(lam), host(f), host(g), self.n_pix, host(self.edges), host(self.sigma),
-                      float(self.doppler), host(c), host(nu), host(w), host(w_ref))
+        self.ctx.call("sdx_observe_adjoint_f64", lam.size, _host_ptr(lam), _host_ptr(f), _host_ptr(g), self.n_pix, _host_ptr(self.edges), _host_ptr(self.sigma),
+                      float(self.doppler), _host_ptr(c), _host_ptr(nu), _host_ptr(w), _host_ptr(w_ref))
         return w if w_ref is None else (w, w_ref)
+
+
+def _stage_host(ctx, entry, lambdas, flux, reference, scalars, n_outs, wanted):
+    """The host-buffer twin `entry` of a stage's forward entry, which takes n_outs grid-sized outputs in pairs (of the flux, of the
+    reference), on host arrays that are checked here before any device work (ValueError naming the argument) -> the list of the first
+    `wanted` outputs, None in place of a reference's where there is no reference"""
+    lam = _grid(lambdas)
+    f = _host_vector("flux", flux, lam.size, "grid point")
+    g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
+    outs = [np.empty(lam.size) if k < wanted and (k % 2 == 0 or g is not None) else None for k in range(n_outs)]
+    (ctx or default_context()).call(entry, lam.size, _host_ptr(lam), _host_ptr(f), _host_ptr(g), *scalars, *map(_host_ptr, outs))
+    return outs[:wanted]
 
 
 def rotate_host(ctx, lambdas, flux, v_rot, limb_darkening=0.6, reference=None):
     """Rotational broadening of host arrays (sdx_rotate_f64) -> the broadened flux, or (flux, reference) with a reference.  The
     arguments are checked before any device work (ValueError naming the argument)."""
-    V, eps = rotation_pair(v_rot, limb_darkening)
-    lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
-    _ascending("lambdas", lam)
-    if lam.size < 2:
-        raise ValueError("lambdas must hold at least two points")
-    f = _host_vector("flux", flux, lam.size, "grid point")
-    g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
-    out = np.empty(lam.size)
-    out_ref = None if g is None else np.empty(lam.size)
-    host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-    (ctx or default_context()).call("sdx_rotate_f64", lam.size, host(lam), host(f), host(g), V, eps, host(out), host(out_ref))
-    return out if g is None else (out, out_ref)
+    return _public(_stage_host(ctx, "sdx_rotate_f64", lambdas, flux, reference, rotation_pair(v_rot, limb_darkening), 2, 2))
 
 
 def rotate_integrated_host(ctx, lambdas, flux, v_rot, limb_darkening=0.6, reference=None, derivatives=False):
     """The cell-integrated rotation of host arrays (sdx_rotate_integrated_f64) -> the broadened flux, or (flux, reference) with a
     reference; derivatives=True appends d / d ln v_rot and d / d limb_darkening of each: (out, dout_lnv, dout_eps), or (out,
     out_reference, dout_lnv, dout_lnv_reference, dout_eps, dout_eps_reference).  The arguments are checked before any device work."""
-    V, eps = rotation_pair(v_rot, limb_darkening)
-    lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
-    _ascending("lambdas", lam)
-    if lam.size < 2:
-        raise ValueError("lambdas must hold at least two points")
-    f = _host_vector("flux", flux, lam.size, "grid point")
-    g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
-    outs = [np.empty(lam.size) if (k < 2 or derivatives) and (k % 2 == 0 or g is not None) else None for k in range(6)]
-    host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-    (ctx or default_context()).call("sdx_rotate_integrated_f64", lam.size, host(lam), host(f), host(g), V, eps, *(host(a) for a in outs))
-    res = tuple(a for a in outs if a is not None)
-    return res[0] if len(res) == 1 else res
-
-
-def _unpack_integrated(res, reference):
-    """rotate_integrated_host(..., derivatives=True)'s tuple -> (out, out_reference, dout_lnv, dout_lnv_reference, dout_eps,
-    dout_eps_reference), None where there is no reference"""
-    return res if reference is not None else (res[0], None, res[1], None, res[2], None)
+    pair = rotation_pair(v_rot, limb_darkening)
+    return _public(_stage_host(ctx, "sdx_rotate_integrated_f64", lambdas, flux, reference, pair, 6, 6 if derivatives else 2))
 
 
 def macroturbulence_host(ctx, lambdas, flux, zeta, reference=None, derivative=False):
@@ -662,15 +660,4 @@ def macroturbulence_host(ctx, lambdas, flux, zeta, reference=None, derivative=Fa
     reference; derivative=True appends d / d ln zeta of each (flux, dflux) or (flux, reference, dflux, dreference).  The arguments are
     checked before any device work (ValueError naming the argument)."""
     zeta = macroturbulence_zeta(zeta)
-    lam = np.ascontiguousarray(getattr(lambdas, "value", lambdas), dtype=np.float64).reshape(-1)
-    _ascending("lambdas", lam)
-    if lam.size < 2:
-        raise ValueError("lambdas must hold at least two points")
-    f = _host_vector("flux", flux, lam.size, "grid point")
-    g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
-    outs = [np.empty(lam.size), None if g is None else np.empty(lam.size), np.empty(lam.size) if derivative else None,
-            np.empty(lam.size) if derivative and g is not None else None]
-    host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-    (ctx or default_context()).call("sdx_macroturbulence_f64", lam.size, host(lam), host(f), host(g), zeta, *(host(a) for a in outs))
-    res = tuple(a for a in outs if a is not None)
-    return res[0] if len(res) == 1 else res
+    return _public(_stage_host(ctx, "sdx_macroturbulence_f64", lambdas, flux, reference, (zeta,), 4, 4 if derivative else 2))

@@ -668,19 +668,10 @@ def observe_response_grad(e0, e1, x, sigma, ctx=None):
 def rotate_tangent(lambdas, flux, v_rot, limb_darkening=0.6, reference=None, ctx=None):
     """ops.rotate with its derivative to the limb-darkening coefficient from the same pass (sdx_rotate_tangent_f64) -> (out, dout_eps), or
     (out, out_reference, dout_eps, dout_eps_reference) with a reference.  v_rot = 0 copies and the derivatives are zeros."""
-    from .instrument import _ascending, _host_vector, rotation_pair
+    from .instrument import _public, _stage_host, rotation_pair
 
-    V, eps = rotation_pair(v_rot, limb_darkening)
-    lam = np.ascontiguousarray(_lib.plain(lambdas), dtype=F8).reshape(-1)
-    _ascending("lambdas", lam)
-    if lam.size < 2:
-        raise ValueError("lambdas must hold at least two points")
-    f = _host_vector("flux", flux, lam.size, "grid point")
-    g = None if reference is None else _host_vector("reference", reference, lam.size, "grid point")
-    outs = [np.empty(lam.size) if (g is not None or k % 2 == 0) else None for k in range(4)]
-    host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-    (ctx or default_context()).call("sdx_rotate_tangent_f64", lam.size, host(lam), host(f), host(g), V, eps, *(host(a) for a in outs))
-    return tuple(a for a in outs if a is not None)
+    pair = rotation_pair(v_rot, limb_darkening)
+    return _public(_stage_host(ctx, "sdx_rotate_tangent_f64", _lib.plain(lambdas), flux, reference, pair, 4, 4))
 
 
 def observe_tangent(lambdas, flux, pixel_edges, sigma, v_rad=0.0, reference=None, dflux=None, dreference=None, ctx=None):
@@ -688,13 +679,10 @@ def observe_tangent(lambdas, flux, pixel_edges, sigma, v_rad=0.0, reference=None
     (d out / d v_rad per km/s), "lsf" (d out / d ln kappa of a common factor on sigma) and, with dflux (and dreference, which needs a
     reference), "flux": the tangent of out for that direction of (flux, reference).  NaN where out is NaN.  No rotation or
     macroturbulence here: stardis_amd.instrument.Instrument.tangent and parameter_tangents run the whole chain."""
-    from .instrument import _ascending, _host_vector, doppler_factor, pixel_sigma
+    from .instrument import _grid, _host_ptr as host, _host_vector, doppler_factor, pixel_sigma
 
     edges, sig = pixel_sigma(pixel_edges, sigma=sigma)
-    lam = np.ascontiguousarray(_lib.plain(lambdas), dtype=F8).reshape(-1)
-    _ascending("lambdas", lam)
-    if lam.size < 2:
-        raise ValueError("lambdas must hold at least two points")
+    lam = _grid(_lib.plain(lambdas))
     if dreference is not None and reference is None:
         raise ValueError("dreference needs a reference")
     if dreference is not None and dflux is None:
@@ -706,7 +694,6 @@ def observe_tangent(lambdas, flux, pixel_edges, sigma, v_rad=0.0, reference=None
     res = {"out": np.empty(n_pix), "v_rad": np.empty(n_pix), "lsf": np.empty(n_pix)}
     if df is not None:
         res["flux"] = np.empty(n_pix)
-    host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     (ctx or default_context()).call("sdx_observe_tangent_f64", lam.size, host(lam), host(f), host(g), n_pix, host(edges), host(sig),
                                     doppler_factor(v_rad), host(df), host(dg), host(res["out"]), host(res["v_rad"]), host(res["lsf"]),
                                     host(res.get("flux")))
@@ -728,17 +715,13 @@ def rotate_integrated_adjoint(lambdas, u, v_rot, limb_darkening=0.6, u_reference
     """The transpose of rotate_integrated (sdx_rotate_integrated_adjoint_f64): weights u over the broadened points -> weights w over
     the grid points with sum_i u_i rotate_integrated(flux)_i = sum_j w_j flux_j, or (w, w_reference) with u_reference.  nus: the
     weights then apply to F_nu instead of F_lambda."""
-    from .instrument import _ascending, _host_vector, rotation_pair
+    from .instrument import _grid, _host_ptr as host, _host_vector, rotation_pair
 
     V, eps = rotation_pair(v_rot, limb_darkening)
-    lam = np.ascontiguousarray(_lib.plain(lambdas), dtype=F8).reshape(-1)
-    _ascending("lambdas", lam)
-    if lam.size < 2:
-        raise ValueError("lambdas must hold at least two points")
+    lam = _grid(_lib.plain(lambdas))
     uu = _host_vector("u", u, lam.size, "grid point")
     ur, nu = (None if a is None else _host_vector(name, a, lam.size, "grid point") for name, a in (("u_reference", u_reference), ("nus", nus)))
     w, w_ref = np.empty(lam.size), None if ur is None else np.empty(lam.size)
-    host = lambda a: None if a is None else a.ctypes.data  # noqa: E731
     (ctx or default_context()).call("sdx_rotate_integrated_adjoint_f64", lam.size, host(lam), V, eps, host(uu), host(ur), host(nu), host(w),
                                     host(w_ref))
     return w if w_ref is None else (w, w_ref)
