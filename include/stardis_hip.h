@@ -984,7 +984,10 @@ int sdx_synthesize_sharded_f64(sdx_group* group, int n_depth, int64_t n_nu, cons
  *   alpha = ((alpha_coefficient * ((exp(-e_low/(k T)) * pop[pop_row]) [* g_lo])) * strength) * (1 - exp(-h nu/(k T)))
  * gamma_mode: 0 = calc_gamma (broadening.py:550-656), 1 = calc_vald_gamma (:1009-1085), 2 = A_ul only, one column
  * (molecules, :799-801), 3 = zero.  broadening_flags: 1 linear Stark | 2 quadratic Stark | 4 van der Waals | 8 radiation.
- * ion_number is the charge seen by the outer electron (`ion_number + 1`, broadening.py:708-709). */
+ * ion_number is the charge seen by the outer electron (`ion_number + 1`, broadening.py:708-709).
+ * mass and temperature must be positive and finite at every line and depth: the arrays live on the device, so the library
+ * cannot look at them, and the generated Doppler width forms 2 k T / m from the reciprocal of the mass without the
+ * division's handling of a zero or infinite quotient.  The caller checks them (the Python LineList refuses mass <= 0). */
 typedef struct sdx_linelist {
     int64_t n_lines;
     const double* nu;          /* [n_lines] Hz, ascending */

@@ -274,8 +274,9 @@ __device__ inline double gen_alpha(const LineParams& p, const GenLine& L, const 
 
 __device__ inline double gen_doppler(const LineParams& p, const GenLine& L, const GenDepth& D)
 {
-    // (2 k T / m by div_by's three instructions without its fall-back: T and m are ordinary positive magnitudes — a zero mass or
-    // temperature never reaches the generating pre-pass, the host refuses it)
+    // (2 k T / m by div_by's three instructions without its fall-back: T and m are ordinary positive magnitudes.  Keeping a zero
+    // mass or temperature away is the CALLER's duty (include/stardis_hip.h, sdx_linelist): the arrays are on the device, so the
+    // library's host code cannot refuse them; of the callers only the Python LineList checks, and only mass <= 0)
     const double q = mul_rn(D.two_kt, L.inv_mass);
     const double two_kt_over_m = fma(fma(-q, L.mass, D.two_kt), L.inv_mass, q);
     return mul_rn(L.nu_over_c, sqrt(add_rn(two_kt_over_m, mul_rn(p.xi, p.xi))));  // broadening.py:32-66
