@@ -17,6 +17,16 @@ alternated round by round (clocks drift between sessions and within one):
       km/s and at S-c3 with V = 10, and the wall time of one forward and one adjoint host-buffer twin, ROUNDS children per build,
       alternated.  The bar: the new median within the old leg's own max - min of the old median.
 
+  python scripts/lib_ab.py adjoints OLD.so NEW.so [ROUNDS] [OUT.json]
+      the line adjoints (sdx_line_adjoint_dev, sdx_line_param_adjoint_dev) and the line tangent's host entry.  Bits: SHA-256 of every output
+      on the six seeded models of tests/line_adjoint_truth.py (every class of item, gamma_cols = 1, tiled windows and the wing shortcut,
+      partial last tiles), each entry in the forms that differ in storage (out_line, out_line_depth, both; all six outputs, one per
+      line, one per depth; a strength direction, four directions per depth), the three host-buffer twins, the tests' shards, both
+      adjoints of the tiled models at adjoint_partials = 1, 100, 160 and 1 << 22, and one S-c2 call per stage through
+      SpectralSynthesizer — every hash must agree, also among the children of one build (the item lists' order depends on the run,
+      the sums do not).  Time: per stage name the median of 31 single profiled calls at S-c2 and S-c3, per line and per depth
+      (k_line_tangent: an unchanged control), and the wall time of sdx_line_param_adjoint_f64 at S-c2.  The bar as for `stages`.
+
 Prints mean, max - min, min and max per leg.  The other build: a copy of csrc/ at the other revision, `make -C` there."""
 import hashlib
 import json
@@ -199,6 +209,145 @@ def stages_child():
     print(json.dumps({"hashes": hashes, "us": times}))
 
 
+ADJ_STAGES = ("k_line_adjoint", "k_line_param_adjoint", "k_line_tangent")
+ADJ_MODELS = ("tiny", "odd", "small", "ragged", "long", "inner")  # tests/line_adjoint_truth.py: every class, gamma_cols = 1, tiled windows
+ADJ_SHARDS = (("small", (0, 100)), ("small", (100, 120)), ("small", (220, 80)), ("long", (1500, 6000)), ("inner", (3000, 6000)), ("inner", (5000, 7001)))
+ADJ_PARTIALS = (1, 100, 160, 1 << 22)  # `long`, `inner`: one supertile, two, three, every tile a supertile of its own
+ADJ_PARAMS = ("damping", "doppler", "centre")
+
+
+def adjoint_calls(ctx, m, shard=None):
+    """the forms of the three device entries on a model of tests/line_adjoint_truth.py -> {form: [host outputs]}"""
+    import numpy as np
+    from stardis_amd import ops
+
+    b, n = (0, m.n_nu) if shard is None else shard
+    nl, nd, L = m.n_lines, m.n_depth, m.lines
+    ptr = lambda a: None if a is None else a.ptr  # noqa: E731
+    d = [ctx.upload(np.ascontiguousarray(a)) for a in (m.nus, L["line_nus"], L["doppler_widths"], L["gammas"], L["alphas"], m.W[:, b:b + n])]
+    head = (nd, m.n_nu, d[0].ptr, b, n, nl, d[1].ptr, d[2].ptr, d[3].ptr, L["gammas"].shape[1], d[4].ptr, d[5].ptr, n)
+    res = {}
+    for form, want in (("out_line", (1, 0)), ("out_line_depth", (0, 1)), ("both", (1, 1))):  # (sld: scratch, the caller's buffer, the caller's)
+        o = [ctx.zeros(s) if w else None for s, w in zip(((nl,), (nl, nd)), want)]
+        ctx.call("sdx_line_adjoint_dev", *head, *map(ptr, o))
+        res[f"sdx_line_adjoint_dev {form}"] = o
+    for form, want in (("all six", (1,) * 6), ("damping per line", (1, 0, 0, 0, 0, 0)), ("centre per depth", (0, 0, 0, 0, 0, 1))):
+        o = [ctx.zeros((nl,) if k < 3 else (nl, nd)) if w else None for k, w in enumerate(want)]
+        ctx.call("sdx_line_param_adjoint_dev", *head, *map(ptr, o))
+        res[f"sdx_line_param_adjoint_dev {form}"] = o
+    rng = np.random.default_rng(3)
+    for form, dirs in (("strength", dict(strength=rng.standard_normal(nl))),
+                       ("four per depth", {k: rng.standard_normal((nl, nd)) * (1.0 if k != "centre" else 1e9) for k in ops.LINE_DIRECTIONS})):
+        res[f"sdx_line_tangent_dev {form}"] = [ops.line_tangent(nd, m.nus, L["line_nus"], L["doppler_widths"], L["gammas"], L["alphas"], ctx=ctx, device=True,
+                                                                shard=shard, **dirs)]
+    ctx.synchronize()
+    return {k: [None if o is None else np.array(o.numpy()) for o in outs] for k, outs in res.items()}
+
+
+def adjoint_twins(ctx, nd, nus, L, W):
+    """the three host-buffer twins -> {entry: ([outputs], call)}"""
+    import numpy as np
+
+    nl = L["line_nus"].size
+    tables = [np.ascontiguousarray(L[k]) for k in ("line_nus", "doppler_widths", "gammas", "alphas")]
+    head = (nd, nus.size, nus.ctypes.data, nl, tables[0].ctypes.data, tables[1].ctypes.data, tables[2].ctypes.data, tables[2].shape[1], tables[3].ctypes.data)
+    order = np.argsort(tables[0], kind="stable")  # (the tangent wants an ascending list)
+    asc = [np.ascontiguousarray(t[order]) for t in tables]
+    dirs = [np.ascontiguousarray(np.random.default_rng(5).standard_normal((nl, nd)) * s) for s in (1.0, 1.0, 1.0, 1e9)]
+    res = {}
+    o1 = [np.zeros(nl), np.zeros((nl, nd))]
+    res["sdx_line_adjoint_f64"] = (o1, lambda: ctx.call("sdx_line_adjoint_f64", *head, W.ctypes.data, *(o.ctypes.data for o in o1)))
+    o2 = [np.zeros(nl) for _ in range(3)] + [np.zeros((nl, nd)) for _ in range(3)]
+    res["sdx_line_param_adjoint_f64"] = (o2, lambda: ctx.call("sdx_line_param_adjoint_f64", *head, W.ctypes.data, *(o.ctypes.data for o in o2)))
+    o3 = [np.zeros((nd, nus.size))]
+    res["sdx_line_tangent_f64"] = (o3, lambda: ctx.call("sdx_line_tangent_f64", nd, nus.size, nus.ctypes.data, nl, *(t.ctypes.data for t in asc[:3]),
+                                                        asc[2].shape[1], asc[3].ctypes.data, *(v.ctypes.data for v in dirs), nd, o3[0].ctypes.data))
+    return res
+
+
+def adjoints_child():
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import line_adjoint_truth as A
+    from stardis_amd import _lib, synth
+    from stardis_amd.engine import SpectralSynthesizer
+
+    ctx = _lib.Context(0)
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()  # noqa: E731
+    digest = lambda forms: {k: [None if o is None else sha(o) for o in outs] for k, outs in forms.items()}  # noqa: E731
+    # ---- bits
+    hashes = {}
+    for name in ADJ_MODELS:
+        m = A.model(name)
+        case = digest(adjoint_calls(ctx, m))
+        for entry, (outs, call) in adjoint_twins(ctx, m.n_depth, m.nus, m.lines, m.W).items():
+            call()
+            case[entry] = [sha(o) for o in outs]
+        hashes[name] = case
+    for name, shard in ADJ_SHARDS:
+        hashes[f"{name}, shard {shard}"] = digest(adjoint_calls(ctx, A.model(name), shard))
+    try:
+        for name in ("long", "inner"):
+            for partials in ADJ_PARTIALS:
+                ctx.set_option("adjoint_partials", partials)
+                forms = adjoint_calls(ctx, A.model(name))
+                hashes[f"{name}, adjoint_partials = {partials}"] = digest({k: v for k, v in forms.items() if "tangent" not in k})
+    finally:
+        ctx.set_option("adjoint_partials", 1 << 22)
+    # ---- the engine at S-c2 (bits and time) and S-c3 (time), driven as scripts/line_param_sensitivity_cost.py drives it: the median
+    # of 31 single profiled calls per stage name
+    times = {}
+    for tag in ("S-c2", "S-c3"):
+        w = synth.make_workload(tag)
+        atm, L = w["atm"], w["lines"]
+        nd, nl = int(atm["temperatures"].size), int(L["line_nus"].size)
+        syn = SpectralSynthesizer(w["nus"], atm["temperatures"], atm["dist"], w["thetas"], w["weights"], L, w["cont"], ctx=ctx, track_evaluations=False,
+                                  keep_line=False, keep_response=True)
+        d_weights = ctx.upload(np.random.default_rng(1).standard_normal(w["nus"].size))
+        syn.step()
+        ctx.synchronize()
+        rng = np.random.default_rng(2)
+        for per_depth in (False, True):
+            dirs = [rng.standard_normal((nl, nd) if per_depth else (nl,)) * s for s in (1.0, 1.0, 1.0, 1e9)]
+            calls = {"k_line_adjoint": lambda: syn.line_sensitivities(d_weights, per_depth=per_depth),
+                     "k_line_param_adjoint": lambda: syn.line_sensitivities(d_weights, per_depth=per_depth, wrt=ADJ_PARAMS),
+                     "k_line_tangent": lambda: syn.line_tangent(*dirs)}
+            label = f"{tag} per {'depth' if per_depth else 'line'}"
+            if tag == "S-c2":
+                case = {}
+                for stage, call in calls.items():
+                    out = call()
+                    ctx.synchronize()
+                    case[stage] = [sha(o.numpy()) for o in (out.values() if isinstance(out, dict) else [out])]
+                hashes[f"engine, {label}"] = case
+            ctx.call("sdx_profile_enable", 1)
+            for stage, call in calls.items():
+                for _ in range(3):
+                    call()
+                us = []
+                for _ in range(31):
+                    ctx.call("sdx_profile_reset")
+                    call()
+                    ctx.synchronize()
+                    us.append(ctx.profile(stage)[1] * 1e3)
+                times[f"{label} {stage}"] = float(np.median(us))
+            ctx.call("sdx_profile_enable", 0)
+        if tag == "S-c2":  # the wall time of a host-buffer twin (each call ends in a synchronize)
+            W = np.random.default_rng(4).standard_normal((nd, w["nus"].size))
+            call = adjoint_twins(ctx, nd, np.ascontiguousarray(w["nus"]), L, W)["sdx_line_param_adjoint_f64"][1]
+            for _ in range(5):
+                call()
+            ts = []
+            for _ in range(30):
+                t0 = time.perf_counter()
+                call()
+                ts.append((time.perf_counter() - t0) * 1e6)
+            times[f"{tag} sdx_line_param_adjoint_f64 wall"] = float(np.median(ts))
+        syn.close()
+    print(json.dumps({"hashes": hashes, "us": times}))
+
+
 def spawn(lib, argv, timeout):
     p = subprocess.run([sys.executable] + argv, env=dict(os.environ, STARDIS_AMD_LIB=os.path.abspath(lib)), capture_output=True, text=True,
                        timeout=timeout, cwd=ROOT)
@@ -222,6 +371,9 @@ def main():
         return
     if mode == "stages-child":
         stages_child()
+        return
+    if mode == "adjoints-child":
+        adjoints_child()
         return
     old, new = sys.argv[2], sys.argv[3]
     if mode == "kernels":
@@ -251,17 +403,19 @@ def main():
             res[name + " 20 after 5"].append({"ms_per_step": j["ms_per_step"]})
         for name, rows in res.items():
             summary(name, rows, "us", 1e3, drop_first=True)
-    elif mode == "stages":
+    elif mode in ("stages", "adjoints"):
         rounds = int(sys.argv[4]) if len(sys.argv) > 4 else 7
         res = {"old": [], "new": []}
         for r in range(rounds):
             for name, lib in (("old", old), ("new", new)):
-                res[name].append(spawn(lib, [os.path.abspath(__file__), "stages-child"], 300))
+                res[name].append(spawn(lib, [os.path.abspath(__file__), mode + "-child"], 300))
                 print(r, name, {k: round(v, 2) for k, v in res[name][-1]["us"].items()}, flush=True)
         hashes = [r["hashes"] for rows in res.values() for r in rows]
         differing = sorted({f"{case}: {entry}" for h in hashes[1:] for case in h for entry in h[case] if h[case][entry] != hashes[0][case][entry]})
         n_hashes = sum(o is not None for case in hashes[0].values() for outs in case.values() for o in outs)
         print(f"{n_hashes} hashes per child, {len(hashes)} children: {'ALL EQUAL' if not differing else 'DIFFERENT: ' + '; '.join(differing)}")
+        within = {name: all(r["hashes"] == rows[0]["hashes"] for r in rows) for name, rows in res.items()}  # (the item lists' order depends on the run)
+        print("children of the same build agree among themselves:", within)
         summary("old", [r["us"] for r in res["old"]], "us")
         summary("new", [r["us"] for r in res["new"]], "us")
         table, missed = {}, []
@@ -275,7 +429,7 @@ def main():
         print("time bar (new median within old max - min of the old median):", "MET" if not missed else "MISSED by " + "; ".join(missed))
         if len(sys.argv) > 5:
             with open(sys.argv[5], "w") as fh:
-                json.dump(dict(rounds=rounds, hashes_per_child=n_hashes, hashes_equal=not differing, differing=differing, hashes=hashes[0],
+                json.dump(dict(rounds=rounds, hashes_per_child=n_hashes, hashes_equal=not differing, equal_within_build=within, differing=differing, hashes=hashes[0],
                                us=table, time_bar_missed=missed), fh, indent=1)
     else:
         print(__doc__)

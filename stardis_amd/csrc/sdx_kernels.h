@@ -5787,28 +5787,34 @@ __global__ __launch_bounds__(kBlock) void k_response_weight(int n_depth, int64_t
 }
 
 // ------------------------------------------------------------------------------------------------
-// The adjoint of the line-opacity sum (include/stardis_hip.h, sdx_line_adjoint_dev): per (line, depth) item
-//     s[l][d] = sum over i in [lo_ld, hi_ld) within the shard of  W[d][i] * voigt_term(nu_i - nu_l; 1 / dw_ld, y_ld, amp_ld),
+// The adjoints of the line-opacity sum (include/stardis_hip.h): per (line, depth) item, over i in [lo_ld, hi_ld) within the shard,
+//   sdx_line_adjoint_dev        s[l][d] = sum W[d][i] * voigt_term(nu_i - nu_l; 1 / dw_ld, y_ld, amp_ld)                (StrengthSums)
+//   sdx_line_param_adjoint_dev  S0 = sum W T,  Sx = sum W amp K_x,  Sxx = sum W amp x K_x,  Sy = sum W amp K_y           (ProfileSums)
 // the window from window_rule on the GLOBAL grid (d_nu by block_dnu_scan, the centre by closest_index: what sdx_line_windows_dev
-// reports), the term with narrow_params + region1_setup as the fp64 line kernels form it.  Always the direct sum, always fp64.
+// reports), the term with narrow_params + region1_setup as the fp64 line kernels form it, K_x and K_y of the region's own formula
+// (voigt_grad_x).  Always the direct sum, always fp64.  One set of kernel bodies serves both: a sums policy names the number of sums
+// of an item (kSums), its constants and what one point adds to the sums; everything else below is written once.
 //
 // Windows run from 20 points to the whole grid, so k_line_adjoint_plan (one thread per item) sorts the items by the length of the
 // clipped window first.  It appends with integer atomics, so the position of an item in a list depends on the run — which wave sums
 // an item does, the order of its sum does not:
-//   short  half-width <= kNarrowHalfWidth: k_line_adjoint<4>, sixteen items per wave, four lanes per item — the 20 points of a floor
+//   short  half-width <= kNarrowHalfWidth: adj_direct<P, 4>, sixteen items per wave, four lanes per item — the 20 points of a floor
 //          window keep all four lanes busy for five trips, where sixteen lanes per item idle 12 of 32 lane-trips and a wave per item
 //          44 of 64 lanes; the floor windows are line cores, every point the long Faddeeva regions;
-//   long   up to kAdjTiledMin points: k_line_adjoint<64>, one wave per item, lanes striding the window (coalesced loads of W and nus);
-//   tiled  longer: k_line_adjoint_tiled, the transpose of the line kernels' wide role.  A wave per item reads 16 bytes per term and is
+//   long   up to kAdjTiledMin points: adj_direct<P, 64>, one wave per item, lanes striding the window (coalesced loads of W and nus);
+//   tiled  longer: adj_tiled<P>, the transpose of the line kernels' wide role.  A wave per item reads 16 bytes per term and is
 //          bound by the L2 (the first measurement in profiles/EXPERIMENTS.md: 5 x the direct sum at S-c3); here a wave holds a TILE of kAdjTile columns of one depth
 //          in registers (nus, W: sixteen of each per lane), walks the depth's list of tiled lines and closes every (line, tile) with a
 //          butterfly — the loads are shared by all the lines of the depth.  A wave owns a run of consecutive tiles (a supertile) and
 //          every J-th line of the list; lane 0 adds the tiles of a supertile in ascending order into the item's slot of `partial`.
-//          The number of supertiles M follows from the number of tiled items (adj_tiling: `cap` partial sums in all), i.e. from the
-//          shapes, the windows and the shard.
-// A lane adds its points in ascending order with one FMA each, a butterfly over the lanes (offsets G/2 ... 1) closes the item or the
-// tile; k_line_adjoint_gather (one wave per line, lane <-> depth) adds an item's supertiles in ascending order and the line's depths
-// by the same butterfly.  No floating-point atomics.  An item whose window misses the shard is exactly 0.
+//          The number of supertiles M follows from the number of tiled items (adj_tiling: `cap` groups of kSums partial sums in all),
+//          i.e. from the shapes, the windows and the shard.
+// The discipline of the sums: x = (nu_i - nu_l) * inv is one product, formed before the point function; a lane adds its points in
+// ascending order, one FMA per term and sum; a butterfly per sum over the lanes (offsets G/2 ... 1) closes the item or the tile; the
+// gathers (one wave per line, lane <-> depth) add an item's supertiles in ascending order (adj_item_sums) and the line's depths by the
+// same butterfly.  No floating-point atomics.  An item whose window misses the shard is exactly 0.
+// Storage: sum k of an item at sld[k * items + item] (the plan's zero for an empty item lands in plane 0: the strength gather reads
+// it, the profile gather does not), sum k of supertile s of a tiled item at partial[(tslot * M + s) * kSums + k].
 constexpr int kAdjTileP = 16;
 constexpr int kAdjTile = 64 * kAdjTileP;
 constexpr int kAdjTiledMin = 4 * kAdjTile;
@@ -5820,9 +5826,9 @@ struct AdjWork {
     int* list_long;    // [items]
     int* list_tiled;   // [N_d][N_l] the lines of the tiled items of each depth
     int* tslot;        // [items] a tiled item's row of `partial` (not written for the others)
-    double* sld;       // [items] s[l][d]: the caller's out_line_depth, or scratch
-    double* partial;   // [tiled items][M]
-    int64_t cap;       // doubles in `partial`, at least the number of items
+    double* sld;       // [kSums][items]; the strength adjoint's is the caller's out_line_depth where that is given
+    double* partial;   // [tiled items][M][kSums]
+    int64_t cap;       // groups of kSums doubles in `partial`, at least the number of items
     int n_tiles;       // tiles of the shard
 };
 struct AdjLines {
@@ -5909,15 +5915,54 @@ __global__ __launch_bounds__(kBlock) void k_line_adjoint_plan(AdjLines a, AdjWor
     }
 }
 
-template <int G>
-__global__ __launch_bounds__(kBlock) void k_line_adjoint(AdjLines a, AdjWork w, const double* __restrict__ weight, int64_t wld)
+// The sums policies: the constants of an item, and what one point (weight wt, x, the item's y and amp) adds to the item's sums —
+// add() with the point function's own region tests, add_wing() without them, for a whole tile in the line's far wing.
+struct StrengthSums {
+    static constexpr int kSums = 1;
+    using Consts = RegionI;
+    static __device__ __forceinline__ Consts setup(double y, double amp) { return region1_setup(y, amp); }
+    static __device__ __forceinline__ void add(double (&acc)[1], double wt, double x, double y, double amp, const Consts& k)
+    {
+        acc[0] = fma(wt, voigt_add_x(0.0, x, y, amp, k), acc[0]);  // (voigt_term at x)
+    }
+    static __device__ __forceinline__ void add_wing(double (&acc)[1], double wt, double x, const Consts& k) { acc[0] = fma(wt, region1_add(0.0, x, k), acc[0]); }
+};
+struct ProfileSums {
+    static constexpr int kSums = 4;  // S0, Sx, Sxx, Sy
+    using Consts = RegionIGrad;
+    static __device__ __forceinline__ Consts setup(double y, double amp) { return region1_grad_setup(y, amp); }
+    static __device__ __forceinline__ void param_add(double (&acc)[4], double wt, double x, double t, double tx, double ty)
+    {
+        acc[0] = fma(wt, t, acc[0]);
+        acc[1] = fma(wt, tx, acc[1]);
+        acc[2] = fma(wt, x * tx, acc[2]);
+        acc[3] = fma(wt, ty, acc[3]);
+    }
+    static __device__ __forceinline__ void add(double (&acc)[4], double wt, double x, double y, double amp, const Consts& k)
+    {
+        double t, tx, ty;
+        voigt_grad_x(x, y, amp, k, t, tx, ty);
+        param_add(acc, wt, x, t, tx, ty);
+    }
+    static __device__ __forceinline__ void add_wing(double (&acc)[4], double wt, double x, const Consts& k)
+    {
+        double t, tx, ty;
+        region1_grad(x, k, t, tx, ty);
+        param_add(acc, wt, x, t, tx, ty);
+    }
+};
+
+// the short (G = 4) and the long (G = 64) items: G lanes per item, striding its window
+template <class P, int G>
+__device__ __forceinline__ void adj_direct(const AdjLines& a, const AdjWork& w, const double* __restrict__ weight, int64_t wld)
 {
-    constexpr int kPerWave = 64 / G;
+    constexpr int kPerWave = 64 / G, kSums = P::kSums;
     const int lane = threadIdx.x & 63, sub = lane & (G - 1);
     const int64_t n_waves = (int64_t)gridDim.x * (kBlock / 64);
     const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     const double d_nu = w.pd[0], r_dnu = w.pd[1];
     const int64_t n_units = w.counters[G == 64 ? 1 : 0];
+    const int64_t n_items = a.n_lines * a.n_depth;
     const int* __restrict__ list = G == 64 ? w.list_long : w.list_short;
     for (int64_t u0 = wave * kPerWave; u0 < n_units; u0 += n_waves * kPerWave) {  // (wave-uniform: every lane reaches the butterfly)
         const int64_t u = u0 + lane / G;
@@ -5931,17 +5976,128 @@ __global__ __launch_bounds__(kBlock) void k_line_adjoint(AdjLines a, AdjWork w, 
         if (!on) e = b;
         double inv, y, amp;
         narrow_params(dw, g, al, inv, y, amp);
-        const RegionI k1 = region1_setup(y, amp);
+        const typename P::Consts k1 = P::setup(y, amp);
         const double* __restrict__ wrow = weight + (size_t)d * wld;
-        double acc = 0.0;
-        for (int64_t i = b + sub; i < e; i += G) acc = fma(wrow[i - a.nu_begin], voigt_term(a.nus[i] - lnu, inv, y, amp, k1), acc);
+        double acc[kSums] = {};
+        for (int64_t i = b + sub; i < e; i += G) {
+            const double x = (a.nus[i] - lnu) * inv;
+            P::add(acc, wrow[i - a.nu_begin], x, y, amp, k1);
+        }
 #pragma unroll
-        for (int off = G >> 1; off > 0; off >>= 1) acc = add_rn(acc, __shfl_xor(acc, off));
-        if (sub == 0 && on) w.sld[item] = acc;
+        for (int k = 0; k < kSums; ++k) {
+#pragma unroll
+            for (int off = G >> 1; off > 0; off >>= 1) acc[k] = add_rn(acc[k], __shfl_xor(acc[k], off));
+        }
+        if (sub == 0 && on) {
+#pragma unroll
+            for (int k = 0; k < kSums; ++k) w.sld[(size_t)k * n_items + item] = acc[k];
+        }
     }
 }
 
 // wave = (depth d, supertile s, line subset j of J): the tiles of s in ascending order, in each the lines j, j + J, ... of depth d's list
+template <class P>
+__device__ __forceinline__ void adj_tiled(const AdjLines& a, const AdjWork& w, const double* __restrict__ weight, int64_t wld, int J)
+{
+    constexpr int kSums = P::kSums;
+    const int lane = threadIdx.x & 63;
+    const int64_t wid = (int64_t)blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int per_depth = w.n_tiles * J;
+    const int d = (int)(wid / per_depth);
+    if (d >= a.n_depth || w.counters[2] == 0) return;
+    const int r = (int)(wid - (int64_t)d * per_depth), s = r / J, j = r - s * J;
+    int M, tps;
+    adj_tiling(w, M, tps);
+    const int n_d = w.counters[4 + d];
+    if (s >= M || j >= n_d) return;
+    const double d_nu = w.pd[0], r_dnu = w.pd[1];
+    const int64_t shard_end = a.nu_begin + a.nu_count;
+    const double* __restrict__ wrow = weight + (size_t)d * wld;
+    const int* __restrict__ list = w.list_tiled + (size_t)d * a.n_lines;
+    const int t_end = min((s + 1) * tps, w.n_tiles);
+    for (int t = s * tps; t < t_end; ++t) {
+        const int64_t base = a.nu_begin + (int64_t)t * kAdjTile;
+        const int64_t tile_end = min(base + kAdjTile, shard_end);
+        const double nu_first = a.nus[base], nu_last = a.nus[tile_end - 1];  // (the grid descends)
+        double nu[kAdjTileP], wt[kAdjTileP];
+#pragma unroll
+        for (int p = 0; p < kAdjTileP; ++p) {
+            const int64_t i = base + p * 64 + lane;
+            const bool ok = i < shard_end;
+            nu[p] = ok ? a.nus[i] : 0.0;
+            wt[p] = ok ? wrow[i - a.nu_begin] : 0.0;
+        }
+        for (int e = j; e < n_d; e += J) {
+            const int64_t l = list[e];
+            const size_t item = (size_t)l * a.n_depth + d;
+            const double lnu = a.line_nus[l], dw = a.doppler[item], g = a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)], al = a.alphas[item];
+            int64_t b, we;
+            adjoint_window(a, w, d_nu, r_dnu, l, dw, g, al, b, we);
+            if (we <= base || b >= tile_end) continue;  // (uniform)
+            double inv, y, amp;
+            narrow_params(dw, g, al, inv, y, amp);
+            const typename P::Consts k1 = P::setup(y, amp);
+            double acc[kSums] = {};
+            // A whole tile inside the window and in the line's far wing — the line's frequency outside the tile's, both end points
+            // with |x| + y > 15 — needs no test per point: the rounded difference and product are monotone in the frequency, so every
+            // point of the tile then passes the point function's own test, and add_wing is what it evaluates.
+            const bool wings = (lnu > nu_first || lnu < nu_last) && add_rn(fabs((nu_first - lnu) * inv), y) > 15.0 && add_rn(fabs((nu_last - lnu) * inv), y) > 15.0;
+            if (wings && b <= base && we >= base + kAdjTile) {
+#pragma unroll
+                for (int p = 0; p < kAdjTileP; ++p) P::add_wing(acc, wt[p], (nu[p] - lnu) * inv, k1);
+            } else {
+                const unsigned len = (unsigned)(we - b);
+                const int rel0 = (int)(base + lane - b);  // (negative: in front of the window, far above len as an unsigned number)
+#pragma unroll
+                for (int p = 0; p < kAdjTileP; ++p)
+                    if ((unsigned)(rel0 + p * 64) < len) P::add(acc, wt[p], (nu[p] - lnu) * inv, y, amp, k1);
+            }
+#pragma unroll
+            for (int k = 0; k < kSums; ++k) {
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) acc[k] = add_rn(acc[k], __shfl_xor(acc[k], off));
+            }
+            if (lane == 0) {
+                double* const slot = w.partial + ((size_t)w.tslot[item] * M + s) * kSums;
+                const bool first = t == max(s * tps, (int)((b - a.nu_begin) / kAdjTile));  // the supertile's first tile inside the window
+#pragma unroll
+                for (int k = 0; k < kSums; ++k) slot[k] = first ? acc[k] : add_rn(slot[k], acc[k]);
+            }
+        }
+    }
+}
+
+// the gathers' common part, an item's sums -> sum: a tiled item's supertiles in ascending order, any other item's from sld (class 0
+// there: the plan's zero in plane 0)
+template <class P>
+__device__ __forceinline__ void adj_item_sums(const AdjLines& a, const AdjWork& w, int M, int tps, size_t item, int cls, int64_t b, int64_t e,
+                                              double (&sum)[P::kSums])
+{
+    constexpr int kSums = P::kSums;
+    if (cls == 3) {
+        const int slot = w.tslot[item];
+        const int sa = (int)((b - a.nu_begin) / kAdjTile) / tps, sb = (int)((e - 1 - a.nu_begin) / kAdjTile) / tps;
+#pragma unroll
+        for (int k = 0; k < kSums; ++k) sum[k] = 0.0;
+        for (int s = sa; s <= sb; ++s) {
+#pragma unroll
+            for (int k = 0; k < kSums; ++k) sum[k] = add_rn(sum[k], w.partial[((size_t)slot * M + s) * kSums + k]);
+        }
+    } else {
+        const size_t n_items = (size_t)a.n_lines * a.n_depth;
+#pragma unroll
+        for (int k = 0; k < kSums; ++k) sum[k] = w.sld[k * n_items + item];
+    }
+}
+
+template <int G>
+__global__ __launch_bounds__(kBlock) void k_line_adjoint(AdjLines a, AdjWork w, const double* __restrict__ weight, int64_t wld)
+{
+    adj_direct<StrengthSums, G>(a, w, weight, wld);
+}
+// The strength adjoint's tiled role stays the hand-written copy of adj_tiled<StrengthSums>: the bits are the same, but the shared body
+// compiled the whole-tile wing condition as one mask instead of two branches and measured 3.5 % slower at S-c3 (profiles/EXPERIMENTS.md,
+// "Line adjoints: one kernel set").  A change to adj_tiled is made here too; the hash A/B of scripts/lib_ab.py `adjoints` holds the two together.
 __global__ __launch_bounds__(kBlock) void k_line_adjoint_tiled(AdjLines a, AdjWork w, const double* __restrict__ weight, int64_t wld, int J)
 {
     const int lane = threadIdx.x & 63;
@@ -6006,7 +6162,17 @@ __global__ __launch_bounds__(kBlock) void k_line_adjoint_tiled(AdjLines a, AdjWo
         }
     }
 }
+template <int G>
+__global__ __launch_bounds__(kBlock) void k_line_param_adjoint(AdjLines a, AdjWork w, const double* __restrict__ weight, int64_t wld)
+{
+    adj_direct<ProfileSums, G>(a, w, weight, wld);
+}
+__global__ __launch_bounds__(kBlock) void k_line_param_adjoint_tiled(AdjLines a, AdjWork w, const double* __restrict__ weight, int64_t wld, int J)
+{
+    adj_tiled<ProfileSums>(a, w, weight, wld, J);
+}
 
+// s[l][d] of the line's items (a tiled item's is written back into sld), and their sum over the depths
 __global__ __launch_bounds__(kBlock) void k_line_adjoint_gather(AdjLines a, AdjWork w, double* __restrict__ out_line)
 {
     const int lane = threadIdx.x & 63;
@@ -6017,173 +6183,27 @@ __global__ __launch_bounds__(kBlock) void k_line_adjoint_gather(AdjLines a, AdjW
     double line = 0.0;
     for (int d0 = 0; d0 < a.n_depth; d0 += 64) {
         const int d = d0 + lane;
-        double v = 0.0;
+        double v[1] = {0.0};
         if (d < a.n_depth) {
             const size_t item = (size_t)l * a.n_depth + d;
             int64_t b, e;
             const int64_t hw = adjoint_window(a, w, w.pd[0], w.pd[1], l, a.doppler[item], a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)],
                                               a.alphas[item], b, e);
-            if (adjoint_class(hw, b, e) == 3) {
-                const int slot = w.tslot[item];
-                const int sa = (int)((b - a.nu_begin) / kAdjTile) / tps, sb = (int)((e - 1 - a.nu_begin) / kAdjTile) / tps;
-                for (int s = sa; s <= sb; ++s) v = add_rn(v, w.partial[(size_t)slot * M + s]);
-                w.sld[item] = v;
-            } else {
-                v = w.sld[item];
-            }
+            const int cls = adjoint_class(hw, b, e);
+            adj_item_sums<StrengthSums>(a, w, M, tps, item, cls, b, e, v);
+            if (cls == 3) w.sld[item] = v[0];
         }
-        for (int off = 32; off > 0; off >>= 1) v = add_rn(v, __shfl_xor(v, off));
-        line = add_rn(line, v);
+        for (int off = 32; off > 0; off >>= 1) v[0] = add_rn(v[0], __shfl_xor(v[0], off));
+        line = add_rn(line, v[0]);
     }
     if (lane == 0 && out_line) out_line[l] = line;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Line-profile sensitivities (include/stardis_hip.h, sdx_line_param_adjoint_dev): beside S0 = sum W T of the adjoint above, per item
-//     Sx = sum W amp K_x,   Sxx = sum W amp x K_x,   Sy = sum W amp K_y        (voigt_grad_x: K_x, K_y of the region's own formula)
-// over the same window clipped to the same shard, from which the gather forms
-//     d/d ln gamma_ld = y Sy,    d/d ln dw_ld = -(S0 + Sxx + y Sy),    d/d nu_l = -Sx / dw_ld.
-// The plan is the adjoint's (k_line_adjoint_setup, k_line_adjoint_plan: the same windows, the same three classes, the same lists), and so
-// is the discipline of the sums: a lane adds its points in ascending order, one FMA per term and sum; a butterfly per sum closes the
-// item or the tile; lane 0 adds the tiles of a supertile in ascending order; the gather adds the supertiles in ascending order and the
-// depths by the butterfly.  No floating-point atomics.  Storage: w.sld is [4][items] (sum k of an item at sld[k * items + item]; the
-// plan's zero for an empty item lands in plane 0 and is not read), w.partial [tiled items][M][4], w.cap counts the groups of four.
-constexpr int kAdjSums = 4;
+// d/d ln gamma_ld = y Sy,    d/d ln dw_ld = -(S0 + Sxx + y Sy),    d/d nu_l = -Sx / dw_ld    of the line's items, and their sums over the depths
 struct ParamOut {
     double *damping, *doppler, *centre;                    // [N_l] or null
     double *damping_depth, *doppler_depth, *centre_depth;  // [N_l][N_d] or null
 };
-// the four sums of one point into acc[0..3]
-__device__ __forceinline__ void param_add(double (&acc)[kAdjSums], double wt, double x, double t, double tx, double ty)
-{
-    acc[0] = fma(wt, t, acc[0]);
-    acc[1] = fma(wt, tx, acc[1]);
-    acc[2] = fma(wt, x * tx, acc[2]);
-    acc[3] = fma(wt, ty, acc[3]);
-}
-
-template <int G>
-__global__ __launch_bounds__(kBlock) void k_line_param_adjoint(AdjLines a, AdjWork w, const double* __restrict__ weight, int64_t wld)
-{
-    constexpr int kPerWave = 64 / G;
-    const int lane = threadIdx.x & 63, sub = lane & (G - 1);
-    const int64_t n_waves = (int64_t)gridDim.x * (kBlock / 64);
-    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    const double d_nu = w.pd[0], r_dnu = w.pd[1];
-    const int64_t n_units = w.counters[G == 64 ? 1 : 0];
-    const int64_t n_items = a.n_lines * a.n_depth;
-    const int* __restrict__ list = G == 64 ? w.list_long : w.list_short;
-    for (int64_t u0 = wave * kPerWave; u0 < n_units; u0 += n_waves * kPerWave) {  // (wave-uniform: every lane reaches the butterfly)
-        const int64_t u = u0 + lane / G;
-        const bool on = u < n_units;
-        const int64_t item = on ? list[u] : 0;
-        const int64_t l = item / a.n_depth;
-        const int d = (int)(item - l * a.n_depth);
-        const double lnu = a.line_nus[l], dw = a.doppler[item], g = a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)], al = a.alphas[item];
-        int64_t b, e;
-        adjoint_window(a, w, d_nu, r_dnu, l, dw, g, al, b, e);
-        if (!on) e = b;
-        double inv, y, amp;
-        narrow_params(dw, g, al, inv, y, amp);
-        const RegionIGrad k1 = region1_grad_setup(y, amp);
-        const double* __restrict__ wrow = weight + (size_t)d * wld;
-        double acc[kAdjSums] = {0.0, 0.0, 0.0, 0.0};
-        for (int64_t i = b + sub; i < e; i += G) {
-            const double x = (a.nus[i] - lnu) * inv;
-            double t, tx, ty;
-            voigt_grad_x(x, y, amp, k1, t, tx, ty);
-            param_add(acc, wrow[i - a.nu_begin], x, t, tx, ty);
-        }
-#pragma unroll
-        for (int k = 0; k < kAdjSums; ++k) {
-#pragma unroll
-            for (int off = G >> 1; off > 0; off >>= 1) acc[k] = add_rn(acc[k], __shfl_xor(acc[k], off));
-        }
-        if (sub == 0 && on) {
-#pragma unroll
-            for (int k = 0; k < kAdjSums; ++k) w.sld[(size_t)k * n_items + item] = acc[k];
-        }
-    }
-}
-
-// wave = (depth d, supertile s, line subset j of J), as k_line_adjoint_tiled
-__global__ __launch_bounds__(kBlock) void k_line_param_adjoint_tiled(AdjLines a, AdjWork w, const double* __restrict__ weight, int64_t wld, int J)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t wid = (int64_t)blockIdx.x * (kBlock / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int per_depth = w.n_tiles * J;
-    const int d = (int)(wid / per_depth);
-    if (d >= a.n_depth || w.counters[2] == 0) return;
-    const int r = (int)(wid - (int64_t)d * per_depth), s = r / J, j = r - s * J;
-    int M, tps;
-    adj_tiling(w, M, tps);
-    const int n_d = w.counters[4 + d];
-    if (s >= M || j >= n_d) return;
-    const double d_nu = w.pd[0], r_dnu = w.pd[1];
-    const int64_t shard_end = a.nu_begin + a.nu_count;
-    const double* __restrict__ wrow = weight + (size_t)d * wld;
-    const int* __restrict__ list = w.list_tiled + (size_t)d * a.n_lines;
-    const int t_end = min((s + 1) * tps, w.n_tiles);
-    for (int t = s * tps; t < t_end; ++t) {
-        const int64_t base = a.nu_begin + (int64_t)t * kAdjTile;
-        const int64_t tile_end = min(base + kAdjTile, shard_end);
-        const double nu_first = a.nus[base], nu_last = a.nus[tile_end - 1];  // (the grid descends)
-        double nu[kAdjTileP], wt[kAdjTileP];
-#pragma unroll
-        for (int p = 0; p < kAdjTileP; ++p) {
-            const int64_t i = base + p * 64 + lane;
-            const bool ok = i < shard_end;
-            nu[p] = ok ? a.nus[i] : 0.0;
-            wt[p] = ok ? wrow[i - a.nu_begin] : 0.0;
-        }
-        for (int e = j; e < n_d; e += J) {
-            const int64_t l = list[e];
-            const size_t item = (size_t)l * a.n_depth + d;
-            const double lnu = a.line_nus[l], dw = a.doppler[item], g = a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)], al = a.alphas[item];
-            int64_t b, we;
-            adjoint_window(a, w, d_nu, r_dnu, l, dw, g, al, b, we);
-            if (we <= base || b >= tile_end) continue;  // (uniform)
-            double inv, y, amp;
-            narrow_params(dw, g, al, inv, y, amp);
-            const RegionIGrad k1 = region1_grad_setup(y, amp);
-            double acc[kAdjSums] = {0.0, 0.0, 0.0, 0.0};
-            // the whole-tile wing path of k_line_adjoint_tiled, under its condition: every point passes voigt_grad_x's own test
-            const bool wings = (lnu > nu_first || lnu < nu_last) && add_rn(fabs((nu_first - lnu) * inv), y) > 15.0 && add_rn(fabs((nu_last - lnu) * inv), y) > 15.0;
-            if (wings && b <= base && we >= base + kAdjTile) {
-#pragma unroll
-                for (int p = 0; p < kAdjTileP; ++p) {
-                    const double x = (nu[p] - lnu) * inv;
-                    double tt, tx, ty;
-                    region1_grad(x, k1, tt, tx, ty);
-                    param_add(acc, wt[p], x, tt, tx, ty);
-                }
-            } else {
-                const unsigned len = (unsigned)(we - b);
-                const int rel0 = (int)(base + lane - b);  // (negative: in front of the window, far above len as an unsigned number)
-#pragma unroll
-                for (int p = 0; p < kAdjTileP; ++p)
-                    if ((unsigned)(rel0 + p * 64) < len) {
-                        const double x = (nu[p] - lnu) * inv;
-                        double tt, tx, ty;
-                        voigt_grad_x(x, y, amp, k1, tt, tx, ty);
-                        param_add(acc, wt[p], x, tt, tx, ty);
-                    }
-            }
-#pragma unroll
-            for (int k = 0; k < kAdjSums; ++k) {
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) acc[k] = add_rn(acc[k], __shfl_xor(acc[k], off));
-            }
-            if (lane == 0) {
-                double* const slot = w.partial + ((size_t)w.tslot[item] * M + s) * kAdjSums;
-                const bool first = t == max(s * tps, (int)((b - a.nu_begin) / kAdjTile));  // the supertile's first tile inside the window
-#pragma unroll
-                for (int k = 0; k < kAdjSums; ++k) slot[k] = first ? acc[k] : add_rn(slot[k], acc[k]);
-            }
-        }
-    }
-}
-
 __global__ __launch_bounds__(kBlock) void k_line_param_adjoint_gather(AdjLines a, AdjWork w, ParamOut o)
 {
     const int lane = threadIdx.x & 63;
@@ -6191,7 +6211,6 @@ __global__ __launch_bounds__(kBlock) void k_line_param_adjoint_gather(AdjLines a
     if (l >= a.n_lines) return;
     int M, tps;
     adj_tiling(w, M, tps);
-    const size_t n_items = (size_t)a.n_lines * a.n_depth;
     double line[3] = {0.0, 0.0, 0.0};
     for (int d0 = 0; d0 < a.n_depth; d0 += 64) {
         const int d = d0 + lane;
@@ -6202,19 +6221,9 @@ __global__ __launch_bounds__(kBlock) void k_line_param_adjoint_gather(AdjLines a
             int64_t b, e;
             const int64_t hw = adjoint_window(a, w, w.pd[0], w.pd[1], l, dw, g, al, b, e);
             const int cls = adjoint_class(hw, b, e);
-            double sum[kAdjSums] = {0.0, 0.0, 0.0, 0.0};
-            if (cls == 3) {
-                const int slot = w.tslot[item];
-                const int sa = (int)((b - a.nu_begin) / kAdjTile) / tps, sb = (int)((e - 1 - a.nu_begin) / kAdjTile) / tps;
-                for (int s = sa; s <= sb; ++s) {
-#pragma unroll
-                    for (int k = 0; k < kAdjSums; ++k) sum[k] = add_rn(sum[k], w.partial[((size_t)slot * M + s) * kAdjSums + k]);
-                }
-            } else if (cls != 0) {
-#pragma unroll
-                for (int k = 0; k < kAdjSums; ++k) sum[k] = w.sld[(size_t)k * n_items + item];
-            }
             if (cls != 0) {  // (an item without a term in the shard: exactly 0)
+                double sum[ProfileSums::kSums];
+                adj_item_sums<ProfileSums>(a, w, M, tps, item, cls, b, e, sum);
                 double inv, y, amp;
                 narrow_params(dw, g, al, inv, y, amp);
                 v[0] = mul_rn(y, sum[3]);

@@ -2510,60 +2510,111 @@ int sdx_response_weight_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const doubl
     return check_launch("k_response_weight");
 }
 
-// Everything is checked before anything is enqueued, also for an empty grid.  Six launches under the stage name k_line_adjoint: the grid
-// spacing and the centres, the item lists, the short (k_line_adjoint<4>), the long (<64>) and the tiled items, the sums per line.
-int sdx_line_adjoint_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count, int64_t n_lines,
-                         const double* line_nus, const double* doppler, const double* gammas, int gamma_cols, const double* alphas,
-                         const double* weight, int64_t weight_ld, double* out_line, double* out_line_depth)
+// ---- what the two line adjoints and the line tangent share -------------------------------------------------------------------------
+// The refusals of all three device entries, under the entry's name (`what` and `kind`: the words of its mixed_precision message).
+// Everything is checked before anything is enqueued, also for an empty grid.
+static int line_entry_check(const char* name, const char* what, const char* kind, const sdx_ctx* ctx, int n_depth, int64_t n_nu, int64_t n_lines,
+                            int gamma_cols, int64_t nu_begin, int64_t nu_count)
 {
-    REQUIRE(ctx, "line_adjoint: null context");
-    REQUIRE(!ctx->mixed_precision, "line_adjoint: no per-line sensitivities with mixed_precision = 1 (the adjoint is that of the fp64 direct sum)");
-    REQUIRE(n_depth > 0 && n_depth <= 65535 && n_nu >= 0 && n_lines >= 0 && n_nu < (int64_t)2147483647, "line_adjoint: need 1 <= n_depth <= 65535, sizes >= 0 and n_nu within int32");
-    REQUIRE(n_lines * (int64_t)n_depth < (int64_t)2147483647 - 64, "line_adjoint: n_lines * n_depth must fit int32");
-    REQUIRE(out_line || out_line_depth, "line_adjoint: no output requested");
-    REQUIRE(gamma_cols == n_depth || gamma_cols == 1, "line_adjoint: gammas must have n_depth or 1 columns");
-    REQUIRE(nu_begin >= 0 && nu_count >= 0 && nu_begin + nu_count <= n_nu, "line_adjoint: frequency shard outside the grid");
-    if (n_nu == 0 || n_lines == 0 || nu_count == 0) return SDX_OK;
-    REQUIRE(nus && line_nus && doppler && gammas && alphas && weight && weight_ld >= nu_count, "line_adjoint: null pointer or weight_ld below nu_count");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const int64_t n_items = n_lines * n_depth;
-    AdjWork w{};
-    w.n_tiles = (int)((nu_count + kAdjTile - 1) / kAdjTile);
-    REQUIRE((int64_t)n_depth * w.n_tiles < ((int64_t)1 << 26), "line_adjoint: n_depth * nu_count too large for one launch");
-    w.cap = std::min<int64_t>(std::max<int64_t>(ctx->adjoint_partials, n_items), n_items * w.n_tiles);
-    const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_int = pad(4 * (size_t)n_items), b_dbl = pad(8 * (size_t)n_items), b_lines = pad(4 * (size_t)n_lines), b_cnt = pad(4 * (size_t)(4 + n_depth));
-    const size_t need = 256 + b_cnt + b_lines + 4 * b_int + (out_line_depth ? 0 : b_dbl) + pad(8 * (size_t)w.cap);
-    int rc = ensure(ctx, &ctx->adj_ws, &ctx->adj_ws_bytes, need);
+    const std::string s = std::string(name) + ": ";
+    REQUIRE(ctx, s + "null context");
+    REQUIRE(!ctx->mixed_precision, s + "no " + what + " with mixed_precision = 1 (the " + kind + " is that of the fp64 direct sum)");
+    REQUIRE(n_depth > 0 && n_depth <= 65535 && n_nu >= 0 && n_lines >= 0 && n_nu < (int64_t)2147483647, s + "need 1 <= n_depth <= 65535, sizes >= 0 and n_nu within int32");
+    REQUIRE(n_lines * (int64_t)n_depth < (int64_t)2147483647 - 64, s + "n_lines * n_depth must fit int32");
+    REQUIRE(gamma_cols == n_depth || gamma_cols == 1, s + "gammas must have n_depth or 1 columns");
+    REQUIRE(nu_begin >= 0 && nu_count >= 0 && nu_begin + nu_count <= n_nu, s + "frequency shard outside the grid");
+    return SDX_OK;
+}
+
+// adj_ws: the head that k_line_adjoint_setup writes (pd, counters, centre) into `w`, then `tail` bytes of the entry's own -> *rest
+static int adj_scratch(sdx_ctx* ctx, int n_depth, int64_t n_lines, size_t tail, AdjWork& w, char** rest)
+{
+    const size_t b_cnt = HostPlan::pad(4 * (size_t)(4 + n_depth)), b_lines = HostPlan::pad(4 * (size_t)n_lines);
+    int rc = ensure(ctx, &ctx->adj_ws, &ctx->adj_ws_bytes, 256 + b_cnt + b_lines + tail);
     if (rc) return rc;
     char* p = (char*)ctx->adj_ws;
     w.pd = (double*)p, p += 256;
     w.counters = (int*)p, p += b_cnt;
     w.centre = (int*)p, p += b_lines;
+    *rest = p;
+    return SDX_OK;
+}
+
+static void launch_adjoint_setup(sdx_ctx* ctx, const AdjLines& a, const AdjWork& w)
+{
+    hipLaunchKernelGGL(k_line_adjoint_setup, dim3(1 + (unsigned)((a.n_lines + kPreBlock - 1) / kPreBlock)), dim3(kPreBlock), 0, ctx->stream, a, w);
+}
+
+// One adjoint of k_sums sums per item: the scratch behind the head (the four item tables, sld [k_sums][items] unless the caller's `sld`
+// is given, partial [cap][k_sums]) and six launches under the stage name `stage`: the grid spacing and the centres, the item lists, the
+// short, the long and the tiled items, the sums per line.
+using AdjWalk = void (*)(AdjLines, AdjWork, const double*, int64_t);
+using AdjTiledWalk = void (*)(AdjLines, AdjWork, const double*, int64_t, int);
+extern "C++" template <class GatherArg>
+static int line_adjoint_launch(sdx_ctx* ctx, const char* stage, int k_sums, const AdjLines& a, const double* weight, int64_t weight_ld, double* sld,
+                               AdjWalk k_short, AdjWalk k_long, AdjTiledWalk k_tiled, void (*k_gather)(AdjLines, AdjWork, GatherArg), GatherArg gather_arg)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int64_t n_items = a.n_lines * a.n_depth;
+    AdjWork w{};
+    w.n_tiles = (int)((a.nu_count + kAdjTile - 1) / kAdjTile);
+    w.cap = std::min<int64_t>(std::max<int64_t>(ctx->adjoint_partials / k_sums, n_items), n_items * w.n_tiles);
+    const size_t b_int = HostPlan::pad(4 * (size_t)n_items), b_sums = sld ? 0 : HostPlan::pad(8 * (size_t)n_items * k_sums);
+    char* p;
+    int rc = adj_scratch(ctx, a.n_depth, a.n_lines, 4 * b_int + b_sums + HostPlan::pad(8 * (size_t)w.cap * k_sums), w, &p);
+    if (rc) return rc;
     w.list_short = (int*)p, p += b_int;
     w.list_long = (int*)p, p += b_int;
     w.list_tiled = (int*)p, p += b_int;
     w.tslot = (int*)p, p += b_int;
-    if (out_line_depth) w.sld = out_line_depth;
-    else w.sld = (double*)p, p += b_dbl;
+    w.sld = sld ? sld : (double*)p, p += b_sums;
     w.partial = (double*)p;
-    const AdjLines a{n_depth, gamma_cols, n_nu, nu_begin, nu_count, n_lines, nus, line_nus, doppler, gammas, alphas};
     const int64_t cap = (int64_t)ctx->n_cu * 32;  // blocks of a list walk: the lists' lengths are known on the device only
     const unsigned nb_short = (unsigned)std::min<int64_t>(cap, (n_items + 63) / 64);
     const unsigned nb_long = (unsigned)std::min<int64_t>(cap, (n_items + 3) / 4);
     // the tiled role: a wave per (depth, supertile, line subset); the line subsets fill the chip where depths x tiles alone do not
-    const int64_t dt = (int64_t)n_depth * w.n_tiles;
-    const int J = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)32, n_lines, ((int64_t)ctx->n_cu * 32 + dt - 1) / dt}));
+    const int64_t dt = (int64_t)a.n_depth * w.n_tiles;
+    const int J = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)32, a.n_lines, ((int64_t)ctx->n_cu * 32 + dt - 1) / dt}));
     {
-        LaunchScope ls(ctx, "k_line_adjoint");
-        hipLaunchKernelGGL(k_line_adjoint_setup, dim3(1 + (unsigned)((n_lines + kPreBlock - 1) / kPreBlock)), dim3(kPreBlock), 0, ctx->stream, a, w);
+        LaunchScope ls(ctx, stage);
+        launch_adjoint_setup(ctx, a, w);
         hipLaunchKernelGGL(k_line_adjoint_plan, dim3(blocks1(n_items)), dim3(kBlock), 0, ctx->stream, a, w);
-        hipLaunchKernelGGL(k_line_adjoint<4>, dim3(nb_short), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld);
-        hipLaunchKernelGGL(k_line_adjoint<64>, dim3(nb_long), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld);
-        hipLaunchKernelGGL(k_line_adjoint_tiled, dim3((unsigned)((dt * J + 3) / 4)), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld, J);
-        hipLaunchKernelGGL(k_line_adjoint_gather, dim3((unsigned)((n_lines + 3) / 4)), dim3(kBlock), 0, ctx->stream, a, w, out_line);
+        hipLaunchKernelGGL(k_short, dim3(nb_short), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld);
+        hipLaunchKernelGGL(k_long, dim3(nb_long), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld);
+        hipLaunchKernelGGL(k_tiled, dim3((unsigned)((dt * J + 3) / 4)), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld, J);
+        hipLaunchKernelGGL(k_gather, dim3((unsigned)((a.n_lines + 3) / 4)), dim3(kBlock), 0, ctx->stream, a, w, gather_arg);
     }
-    return check_launch("k_line_adjoint");
+    return check_launch(stage);
+}
+
+// nus and the four line tables of a host-buffer twin into its plan, in the order of the arena
+struct LineTables {
+    const double *nus, *line_nus, *doppler, *gammas, *alphas;
+};
+static void plan_line_tables(HostPlan& plan, LineTables& d, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus,
+                             const double* doppler, const double* gammas, int gamma_cols, const double* alphas)
+{
+    const size_t f8 = sizeof(double), items = (size_t)n_lines * n_depth * f8;
+    plan.in(nus, (size_t)n_nu * f8, &d.nus);
+    plan.in(line_nus, (size_t)n_lines * f8, &d.line_nus);
+    plan.in(doppler, items, &d.doppler);
+    plan.in(gammas, (size_t)n_lines * gamma_cols * f8, &d.gammas);
+    plan.in(alphas, items, &d.alphas);
+}
+
+int sdx_line_adjoint_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count, int64_t n_lines,
+                         const double* line_nus, const double* doppler, const double* gammas, int gamma_cols, const double* alphas,
+                         const double* weight, int64_t weight_ld, double* out_line, double* out_line_depth)
+{
+    int rc = line_entry_check("line_adjoint", "per-line sensitivities", "adjoint", ctx, n_depth, n_nu, n_lines, gamma_cols, nu_begin, nu_count);
+    if (rc) return rc;
+    REQUIRE(out_line || out_line_depth, "line_adjoint: no output requested");
+    if (n_nu == 0 || n_lines == 0 || nu_count == 0) return SDX_OK;
+    REQUIRE(nus && line_nus && doppler && gammas && alphas && weight && weight_ld >= nu_count, "line_adjoint: null pointer or weight_ld below nu_count");
+    REQUIRE((int64_t)n_depth * ((nu_count + kAdjTile - 1) / kAdjTile) < ((int64_t)1 << 26), "line_adjoint: n_depth * nu_count too large for one launch");
+    const AdjLines a{n_depth, gamma_cols, n_nu, nu_begin, nu_count, n_lines, nus, line_nus, doppler, gammas, alphas};
+    return line_adjoint_launch(ctx, "k_line_adjoint", StrengthSums::kSums, a, weight, weight_ld, out_line_depth, k_line_adjoint<4>, k_line_adjoint<64>, k_line_adjoint_tiled,
+                               k_line_adjoint_gather, out_line);
 }
 
 int sdx_line_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus, const double* doppler,
@@ -2577,79 +2628,37 @@ int sdx_line_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     REQUIRE(nus && line_nus && doppler && gammas && alphas && weight, "line_adjoint: null pointer");
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t f8 = sizeof(double), items = (size_t)n_lines * n_depth * f8;
-    const double *d_nus, *d_ln, *d_dw, *d_g, *d_a, *d_wt;
+    const double* d_wt;
+    LineTables t;
     double *d_line, *d_ld;
     HostPlan plan;
-    plan.in(nus, (size_t)n_nu * f8, &d_nus);
-    plan.in(line_nus, (size_t)n_lines * f8, &d_ln);
-    plan.in(doppler, items, &d_dw);
-    plan.in(gammas, (size_t)n_lines * gamma_cols * f8, &d_g);
-    plan.in(alphas, items, &d_a);
+    plan_line_tables(plan, t, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas);
     plan.in(weight, (size_t)n_depth * n_nu * f8, &d_wt);
     plan.out(out_line, (size_t)n_lines * f8, &d_line);
     plan.out(out_line_depth, items, &d_ld);
     HostIo io{ctx};
     if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_line_adjoint_dev(ctx, n_depth, n_nu, d_nus, 0, n_nu, n_lines, d_ln, d_dw, d_g, gamma_cols, d_a, d_wt, n_nu, d_line, d_ld))) return rc;
+    if ((rc = sdx_line_adjoint_dev(ctx, n_depth, n_nu, t.nus, 0, n_nu, n_lines, t.line_nus, t.doppler, t.gammas, gamma_cols, t.alphas, d_wt, n_nu, d_line, d_ld))) return rc;
     if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }
 
 // ---- line-profile sensitivities (k_line_param_adjoint) ----------------------------------------------------------------------
-// sdx_line_adjoint_dev's checks, plan and launch geometry; four sums per item (AdjWork::sld [4][items], partial [tiled items][M][4],
-// cap in groups of four).  Six launches under the stage name k_line_param_adjoint.
 int sdx_line_param_adjoint_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count, int64_t n_lines,
                                const double* line_nus, const double* doppler, const double* gammas, int gamma_cols, const double* alphas,
                                const double* weight, int64_t weight_ld, double* out_damping, double* out_doppler, double* out_centre,
                                double* out_damping_depth, double* out_doppler_depth, double* out_centre_depth)
 {
-    REQUIRE(ctx, "line_param_adjoint: null context");
-    REQUIRE(!ctx->mixed_precision, "line_param_adjoint: no line-profile sensitivities with mixed_precision = 1 (the adjoint is that of the fp64 direct sum)");
-    REQUIRE(n_depth > 0 && n_depth <= 65535 && n_nu >= 0 && n_lines >= 0 && n_nu < (int64_t)2147483647, "line_param_adjoint: need 1 <= n_depth <= 65535, sizes >= 0 and n_nu within int32");
-    REQUIRE(n_lines * (int64_t)n_depth < (int64_t)2147483647 - 64, "line_param_adjoint: n_lines * n_depth must fit int32");
+    int rc = line_entry_check("line_param_adjoint", "line-profile sensitivities", "adjoint", ctx, n_depth, n_nu, n_lines, gamma_cols, nu_begin, nu_count);
+    if (rc) return rc;
     REQUIRE(out_damping || out_doppler || out_centre || out_damping_depth || out_doppler_depth || out_centre_depth, "line_param_adjoint: no output requested");
-    REQUIRE(gamma_cols == n_depth || gamma_cols == 1, "line_param_adjoint: gammas must have n_depth or 1 columns");
-    REQUIRE(nu_begin >= 0 && nu_count >= 0 && nu_begin + nu_count <= n_nu, "line_param_adjoint: frequency shard outside the grid");
     if (n_nu == 0 || n_lines == 0 || nu_count == 0) return SDX_OK;
     REQUIRE(nus && line_nus && doppler && gammas && alphas && weight && weight_ld >= nu_count, "line_param_adjoint: null pointer or weight_ld below nu_count");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const int64_t n_items = n_lines * n_depth;
-    AdjWork w{};
-    w.n_tiles = (int)((nu_count + kAdjTile - 1) / kAdjTile);
-    REQUIRE((int64_t)n_depth * w.n_tiles < ((int64_t)1 << 26), "line_param_adjoint: n_depth * nu_count too large for one launch");
-    w.cap = std::min<int64_t>(std::max<int64_t>(ctx->adjoint_partials / kAdjSums, n_items), n_items * w.n_tiles);
-    const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_int = pad(4 * (size_t)n_items), b_sums = pad(8 * (size_t)n_items * kAdjSums), b_lines = pad(4 * (size_t)n_lines), b_cnt = pad(4 * (size_t)(4 + n_depth));
-    const size_t need = 256 + b_cnt + b_lines + 4 * b_int + b_sums + pad(8 * (size_t)w.cap * kAdjSums);
-    int rc = ensure(ctx, &ctx->adj_ws, &ctx->adj_ws_bytes, need);
-    if (rc) return rc;
-    char* p = (char*)ctx->adj_ws;
-    w.pd = (double*)p, p += 256;
-    w.counters = (int*)p, p += b_cnt;
-    w.centre = (int*)p, p += b_lines;
-    w.list_short = (int*)p, p += b_int;
-    w.list_long = (int*)p, p += b_int;
-    w.list_tiled = (int*)p, p += b_int;
-    w.tslot = (int*)p, p += b_int;
-    w.sld = (double*)p, p += b_sums;
-    w.partial = (double*)p;
+    REQUIRE((int64_t)n_depth * ((nu_count + kAdjTile - 1) / kAdjTile) < ((int64_t)1 << 26), "line_param_adjoint: n_depth * nu_count too large for one launch");
     const AdjLines a{n_depth, gamma_cols, n_nu, nu_begin, nu_count, n_lines, nus, line_nus, doppler, gammas, alphas};
     const ParamOut o{out_damping, out_doppler, out_centre, out_damping_depth, out_doppler_depth, out_centre_depth};
-    const int64_t cap = (int64_t)ctx->n_cu * 32;
-    const unsigned nb_short = (unsigned)std::min<int64_t>(cap, (n_items + 63) / 64);
-    const unsigned nb_long = (unsigned)std::min<int64_t>(cap, (n_items + 3) / 4);
-    const int64_t dt = (int64_t)n_depth * w.n_tiles;
-    const int J = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)32, n_lines, ((int64_t)ctx->n_cu * 32 + dt - 1) / dt}));
-    {
-        LaunchScope ls(ctx, "k_line_param_adjoint");
-        hipLaunchKernelGGL(k_line_adjoint_setup, dim3(1 + (unsigned)((n_lines + kPreBlock - 1) / kPreBlock)), dim3(kPreBlock), 0, ctx->stream, a, w);
-        hipLaunchKernelGGL(k_line_adjoint_plan, dim3(blocks1(n_items)), dim3(kBlock), 0, ctx->stream, a, w);
-        hipLaunchKernelGGL(k_line_param_adjoint<4>, dim3(nb_short), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld);
-        hipLaunchKernelGGL(k_line_param_adjoint<64>, dim3(nb_long), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld);
-        hipLaunchKernelGGL(k_line_param_adjoint_tiled, dim3((unsigned)((dt * J + 3) / 4)), dim3(kBlock), 0, ctx->stream, a, w, weight, weight_ld, J);
-        hipLaunchKernelGGL(k_line_param_adjoint_gather, dim3((unsigned)((n_lines + 3) / 4)), dim3(kBlock), 0, ctx->stream, a, w, o);
-    }
-    return check_launch("k_line_param_adjoint");
+    return line_adjoint_launch(ctx, "k_line_param_adjoint", ProfileSums::kSums, a, weight, weight_ld, nullptr, k_line_param_adjoint<4>, k_line_param_adjoint<64>,
+                               k_line_param_adjoint_tiled, k_line_param_adjoint_gather, o);
 }
 
 int sdx_line_param_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t n_lines, const double* line_nus, const double* doppler,
@@ -2665,20 +2674,17 @@ int sdx_line_param_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const do
     REQUIRE(nus && line_nus && doppler && gammas && alphas && weight, "line_param_adjoint: null pointer");
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t f8 = sizeof(double), items = (size_t)n_lines * n_depth * f8;
-    const double *d_nus, *d_ln, *d_dw, *d_g, *d_a, *d_wt;
+    const double* d_wt;
+    LineTables t;
     double* d_out[6];
     double* const host_out[6] = {out_damping, out_doppler, out_centre, out_damping_depth, out_doppler_depth, out_centre_depth};
     HostPlan plan;
-    plan.in(nus, (size_t)n_nu * f8, &d_nus);
-    plan.in(line_nus, (size_t)n_lines * f8, &d_ln);
-    plan.in(doppler, items, &d_dw);
-    plan.in(gammas, (size_t)n_lines * gamma_cols * f8, &d_g);
-    plan.in(alphas, items, &d_a);
+    plan_line_tables(plan, t, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas);
     plan.in(weight, (size_t)n_depth * n_nu * f8, &d_wt);
     for (int k = 0; k < 6; ++k) plan.out(host_out[k], k < 3 ? (size_t)n_lines * f8 : items, &d_out[k]);
     HostIo io{ctx};
     if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_line_param_adjoint_dev(ctx, n_depth, n_nu, d_nus, 0, n_nu, n_lines, d_ln, d_dw, d_g, gamma_cols, d_a, d_wt, n_nu, d_out[0], d_out[1], d_out[2],
+    if ((rc = sdx_line_param_adjoint_dev(ctx, n_depth, n_nu, t.nus, 0, n_nu, n_lines, t.line_nus, t.doppler, t.gammas, gamma_cols, t.alphas, d_wt, n_nu, d_out[0], d_out[1], d_out[2],
                                          d_out[3], d_out[4], d_out[5])))
         return rc;
     if ((rc = io.collect(plan))) return rc;
@@ -2686,21 +2692,18 @@ int sdx_line_param_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const do
 }
 
 // ---- the tangent of the line-opacity sum (k_line_tangent) ---------------------------------------------------------------------
-// The adjoints' checks.  Five launches under the stage name k_line_tangent: the grid spacing and the centres (k_line_adjoint_setup), the
-// windows, the prefix of the wide items per depth, their lists, the plane.  The scratch is the adjoints' (adj_ws).
+// The adjoints' checks (line_entry_check) and its own.  Five launches under the stage name k_line_tangent: the grid spacing and the centres
+// (k_line_adjoint_setup), the windows, the prefix of the wide items per depth, their lists, the plane.  The scratch is the adjoints'
+// (adj_scratch: their head, then the tangent's tables).
 int sdx_line_tangent_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count, int64_t n_lines,
                          const double* line_nus, const double* doppler, const double* gammas, int gamma_cols, const double* alphas,
                          const double* d_strength, const double* d_damping, const double* d_doppler, const double* d_centre, int dir_cols,
                          double* out, int64_t out_ld)
 {
-    REQUIRE(ctx, "line_tangent: null context");
-    REQUIRE(!ctx->mixed_precision, "line_tangent: no line tangent with mixed_precision = 1 (the tangent is that of the fp64 direct sum)");
-    REQUIRE(n_depth > 0 && n_depth <= 65535 && n_nu >= 0 && n_lines >= 0 && n_nu < (int64_t)2147483647, "line_tangent: need 1 <= n_depth <= 65535, sizes >= 0 and n_nu within int32");
-    REQUIRE(n_lines * (int64_t)n_depth < (int64_t)2147483647 - 64, "line_tangent: n_lines * n_depth must fit int32");
+    int rc = line_entry_check("line_tangent", "line tangent", "tangent", ctx, n_depth, n_nu, n_lines, gamma_cols, nu_begin, nu_count);
+    if (rc) return rc;
     REQUIRE(d_strength || d_damping || d_doppler || d_centre, "line_tangent: no direction given");
     REQUIRE(dir_cols == n_depth || dir_cols == 1, "line_tangent: the directions must have n_depth or 1 columns");
-    REQUIRE(gamma_cols == n_depth || gamma_cols == 1, "line_tangent: gammas must have n_depth or 1 columns");
-    REQUIRE(nu_begin >= 0 && nu_count >= 0 && nu_begin + nu_count <= n_nu, "line_tangent: frequency shard outside the grid");
     if (n_nu == 0 || nu_count == 0) return SDX_OK;
     REQUIRE(nus && out && out_ld >= nu_count, "line_tangent: null pointer or out_ld below nu_count");
     REQUIRE(n_lines == 0 || (line_nus && doppler && gammas && alphas), "line_tangent: null pointer");
@@ -2709,16 +2712,11 @@ int sdx_line_tangent_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     HIP_TRY(hipSetDevice(ctx->device));
     TanWork w{};
     w.n_chunks = (int)((n_lines + kBlock - 1) / kBlock);
-    const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_int = pad(4 * (size_t)n_lines * n_depth), b_lines = pad(4 * (size_t)n_lines), b_cnt = pad(4 * (size_t)(4 + n_depth));
-    const size_t b_chunk = pad(4 * (size_t)w.n_chunks * n_depth), b_depth = pad(4 * (size_t)n_depth);
-    int rc = ensure(ctx, &ctx->adj_ws, &ctx->adj_ws_bytes, 256 + b_cnt + b_lines + 3 * b_int + b_chunk + b_depth);
-    if (rc) return rc;
+    const size_t b_int = HostPlan::pad(4 * (size_t)n_lines * n_depth), b_chunk = HostPlan::pad(4 * (size_t)w.n_chunks * n_depth);
     AdjWork setup{};  // what k_line_adjoint_setup writes: d_nu, the centres (and the adjoint's counters, not read here)
-    char* p = (char*)ctx->adj_ws;
-    setup.pd = w.pd = (double*)p, p += 256;
-    setup.counters = (int*)p, p += b_cnt;
-    setup.centre = w.centre = (int*)p, p += b_lines;
+    char* p;
+    if ((rc = adj_scratch(ctx, n_depth, n_lines, 3 * b_int + b_chunk + HostPlan::pad(4 * (size_t)n_depth), setup, &p))) return rc;
+    w.pd = setup.pd, w.centre = setup.centre;
     w.win_lo = (int*)p, p += b_int;
     w.win_hi = (int*)p, p += b_int;
     w.list = (int*)p, p += b_int;
@@ -2730,7 +2728,7 @@ int sdx_line_tangent_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
         LaunchScope ls(ctx, "k_line_tangent");
         if (n_lines > 0) {
             const dim3 plan_grid((unsigned)w.n_chunks, (unsigned)n_depth);
-            hipLaunchKernelGGL(k_line_adjoint_setup, dim3(1 + (unsigned)((n_lines + kPreBlock - 1) / kPreBlock)), dim3(kPreBlock), 0, ctx->stream, a, setup);
+            launch_adjoint_setup(ctx, a, setup);
             hipLaunchKernelGGL(k_line_tangent_plan, plan_grid, dim3(kBlock), 0, ctx->stream, a, dir, w);
             hipLaunchKernelGGL(k_line_tangent_scan, dim3((unsigned)n_depth), dim3(64), 0, ctx->stream, w);
             hipLaunchKernelGGL(k_line_tangent_list, plan_grid, dim3(kBlock), 0, ctx->stream, a, w);
@@ -2754,21 +2752,18 @@ int sdx_line_tangent_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
     if (n_nu == 0) return SDX_OK;
     REQUIRE(nus && out && (n_lines == 0 || (line_nus && doppler && gammas && alphas)), "line_tangent: null pointer");
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), items = (size_t)n_lines * n_depth * f8, dirs = (size_t)n_lines * dir_cols * f8;
-    const double *d_nus, *d_ln, *d_dw, *d_g, *d_a, *d_dir[4];
+    const size_t f8 = sizeof(double), dirs = (size_t)n_lines * dir_cols * f8;
+    const double* d_dir[4];
+    LineTables t;
     const double* const host_dir[4] = {d_strength, d_damping, d_doppler, d_centre};
     double* d_out;
     HostPlan plan;
-    plan.in(nus, (size_t)n_nu * f8, &d_nus);
-    plan.in(line_nus, (size_t)n_lines * f8, &d_ln);
-    plan.in(doppler, items, &d_dw);
-    plan.in(gammas, (size_t)n_lines * gamma_cols * f8, &d_g);
-    plan.in(alphas, items, &d_a);
+    plan_line_tables(plan, t, n_depth, n_nu, nus, n_lines, line_nus, doppler, gammas, gamma_cols, alphas);
     for (int k = 0; k < 4; ++k) plan.in(host_dir[k], dirs, &d_dir[k]);
     plan.out(out, (size_t)n_depth * n_nu * f8, &d_out);
     HostIo io{ctx};
     if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_line_tangent_dev(ctx, n_depth, n_nu, d_nus, 0, n_nu, n_lines, d_ln, d_dw, d_g, gamma_cols, d_a, d_dir[0], d_dir[1], d_dir[2], d_dir[3], dir_cols,
+    if ((rc = sdx_line_tangent_dev(ctx, n_depth, n_nu, t.nus, 0, n_nu, n_lines, t.line_nus, t.doppler, t.gammas, gamma_cols, t.alphas, d_dir[0], d_dir[1], d_dir[2], d_dir[3], dir_cols,
                                    d_out, n_nu)))
         return rc;
     if ((rc = io.collect(plan))) return rc;

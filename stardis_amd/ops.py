@@ -156,6 +156,15 @@ def line_adjoint(no_of_depth_points, tracing_nus_values, line_nus, doppler_width
     (n_lines, N_d).  Row k belongs to line k of the caller's list whatever its order.  weight: (N_d, N_nu) host array, DeviceArray or
     CUDA tensor; shard = (begin, count): only these columns of the global grid are summed and weight is (N_d, count) — shards add.
     device=True: a DeviceArray instead of a host array."""
+    ctx, head, held, shape = _adjoint_inputs(ctx, no_of_depth_points, tracing_nus_values, line_nus, doppler_widths, gammas, alphas_array, weight, per_depth, shard)
+    out = ctx.empty(shape)
+    ctx.call("sdx_line_adjoint_dev", *head, None if per_depth else out.ptr, out.ptr if per_depth else None)
+    return out if device else out.numpy()
+
+
+def _adjoint_inputs(ctx, no_of_depth_points, tracing_nus_values, line_nus, doppler_widths, gammas, alphas_array, weight, per_depth, shard):
+    """What line_adjoint and line_param_adjoint share: the grid, the tables, the shard and the weight checked and on the device ->
+    (the context, the arguments of either entry up to weight_ld, the device arrays they point into, the shape of an output)."""
     nus = _host(tracing_nus_values).reshape(-1)
     ln, dw, g, al = _line_inputs(no_of_depth_points, line_nus, doppler_widths, gammas, alphas_array, sort=False)
     nd = int(no_of_depth_points)
@@ -168,10 +177,8 @@ def line_adjoint(no_of_depth_points, tracing_nus_values, line_nus, doppler_width
     ctx = ctx or default_context()
     d_w = _dev(ctx, weight)
     d = [ctx.upload(x) for x in (nus, ln, dw, g, al)]
-    out = ctx.empty((ln.size, nd) if per_depth else (ln.size,))
-    ctx.call("sdx_line_adjoint_dev", nd, nus.size, d[0].ptr, begin, count, ln.size, d[1].ptr, d[2].ptr, d[3].ptr, g.shape[1], d[4].ptr,
-             ptr_of(d_w), count, None if per_depth else out.ptr, out.ptr if per_depth else None)
-    return out if device else out.numpy()
+    head = (nd, nus.size, d[0].ptr, begin, count, ln.size, d[1].ptr, d[2].ptr, d[3].ptr, g.shape[1], d[4].ptr, ptr_of(d_w), count)
+    return ctx, head, d + [d_w], ((ln.size, nd) if per_depth else (ln.size,))
 
 
 LINE_PARAMS = ("damping", "doppler", "centre")
@@ -186,23 +193,11 @@ def line_param_adjoint(no_of_depth_points, tracing_nus_values, line_nus, doppler
     wrt = tuple(wrt)
     if not wrt or any(k not in LINE_PARAMS for k in wrt):
         raise ValueError(f"wrt must name some of {LINE_PARAMS}, got {wrt}")
-    nus = _host(tracing_nus_values).reshape(-1)
-    ln, dw, g, al = _line_inputs(no_of_depth_points, line_nus, doppler_widths, gammas, alphas_array, sort=False)
-    nd = int(no_of_depth_points)
-    begin, count = (0, nus.size) if shard is None else (int(v) for v in shard)
-    if begin < 0 or count < 0 or begin + count > nus.size:
-        raise ValueError(f"shard {(begin, count)} lies outside the grid of {nus.size} frequencies")
-    shape = tuple(int(v) for v in (weight.shape if hasattr(weight, "shape") else np.shape(weight)))
-    if shape != (nd, count):
-        raise ValueError(f"weight must have shape {(nd, count)}, got {shape}")
-    ctx = ctx or default_context()
-    d_w = _dev(ctx, weight)
-    d = [ctx.upload(x) for x in (nus, ln, dw, g, al)]
-    out = {k: ctx.empty((ln.size, nd) if per_depth else (ln.size,)) for k in wrt}
+    ctx, head, held, shape = _adjoint_inputs(ctx, no_of_depth_points, tracing_nus_values, line_nus, doppler_widths, gammas, alphas_array, weight, per_depth, shard)
+    out = {k: ctx.empty(shape) for k in wrt}
     ptrs = [ptr_of(out.get(k)) for k in LINE_PARAMS]
     none = [None] * 3
-    ctx.call("sdx_line_param_adjoint_dev", nd, nus.size, d[0].ptr, begin, count, ln.size, d[1].ptr, d[2].ptr, d[3].ptr, g.shape[1], d[4].ptr,
-             ptr_of(d_w), count, *(none + ptrs if per_depth else ptrs + none))
+    ctx.call("sdx_line_param_adjoint_dev", *head, *(none + ptrs if per_depth else ptrs + none))
     return out if device else {k: v.numpy() for k, v in out.items()}
 
 
