@@ -27,6 +27,18 @@ alternated round by round (clocks drift between sessions and within one):
       the sums do not).  Time: per stage name the median of 31 single profiled calls at S-c2 and S-c3, per line and per depth
       (k_line_tangent: an unchanged control), and the wall time of sdx_line_param_adjoint_f64 at S-c2.  The bar as for `stages`.
 
+  python scripts/lib_ab.py engine OLD_TREE NEW_TREE [ROUNDS] [OUT.json]
+      two trees of the PYTHON package on the one built library (the refactors of stardis_amd/engine.py and radiation_field/fused.py): each
+      child puts its tree in front of sys.path.  Bits: SHA-256 of every output of SpectralSynthesizer on the small workload of
+      tests/test_gpu_engine.py — dense sorted (with and without the plan), dense unsorted and a LineList, each with the continuum flux
+      and as a shard of the middle third; eager, captured, capture(batch=3), a step after close(); the two-collective mode, eager and captured, on the long-list shard
+      of tests/test_gpu_round5.py (the library refuses it on anything smaller); then
+      everything asked on demand behind a step with every kept plane and a rotating, macroturbulent instrument (contribution,
+      responses, sensitivities for every wrt, tangents, the instrument's transposes and Jacobian, the chi-square calls with
+      curvature) — and of one drop-in run per branch fused.py's step call had.  Time at S-c2, constructed as bench.py constructs it,
+      with the plan and with grid_plan=False: 500 eager enqueue() to one synchronize (`step_us`), the host time of that loop alone, 500
+      captured step().  The bar as for `stages`.
+
 Prints mean, max - min, min and max per leg.  The other build: a copy of csrc/ at the other revision, `make -C` there."""
 import hashlib
 import json
@@ -348,6 +360,197 @@ def adjoints_child():
     print(json.dumps({"hashes": hashes, "us": times}))
 
 
+ENGINE_WRT = ("strength", "damping", "doppler", "centre")
+
+
+def engine_child(tree):
+    """one leg of `engine`: the Python tree `tree` in front of sys.path, the library STARDIS_AMD_LIB names"""
+    sys.path.insert(0, os.path.abspath(tree))
+    import struct
+    import types
+
+    import numpy as np
+    import stardis_amd
+    from stardis_amd import _lib, synth
+    from stardis_amd import constants as K
+    from stardis_amd.engine import SpectralSynthesizer
+    from stardis_amd.instrument import Instrument
+
+    assert os.path.abspath(stardis_amd.__file__).startswith(os.path.abspath(tree) + os.sep), stardis_amd.__file__
+    ctx = _lib.Context(0)
+
+    def sha(a):
+        if a is None or isinstance(a, str):
+            return a
+        if isinstance(a, dict):
+            return {k: sha(v) for k, v in a.items()}
+        if isinstance(a, (tuple, list)):
+            return [sha(v) for v in a]
+        if isinstance(a, float):
+            return hashlib.sha256(struct.pack("<d", a)).hexdigest()
+        if isinstance(a, int):
+            return a
+        return hashlib.sha256(np.ascontiguousarray(a.numpy() if hasattr(a, "ptr") else a).tobytes()).hexdigest()
+
+    # ---- bits: the workload of tests/test_gpu_engine.py::small_workload (300 lines, ~500 frequencies, 56 depths, 8 angles)
+    atm = synth.solar_atmosphere()
+    nus = synth.tracing_grid(6560.0, 6570.0, step=0.02)
+    dense = synth.synth_lines(nus, atm, 300, seed=11, mix=(0.8, 0.15, 0.05))
+    perm = np.random.default_rng(3).permutation(300)
+    lists = {"dense sorted": dense, "dense unsorted": {k: np.ascontiguousarray(v[perm]) for k, v in dense.items()},
+             "line list": synth.synth_linelist(nus, atm, 300, seed=11)}
+    cont = synth.synth_continuum_state(atm)
+    th, w = synth.thetas_and_weights(8)
+    make = lambda lines, **kw: SpectralSynthesizer(nus, atm["temperatures"], atm["dist"], th, w, lines, cont, ctx=ctx, **kw)  # noqa: E731
+
+    def planes(syn):
+        out = dict(F_nu=syn.F_nu(), alpha_line=syn.alpha_line(), total_alphas=syn.total_alphas(), evaluations=syn.evaluations())
+        if syn.keep_continuum_flux:
+            out["F_nu_continuum"] = syn.F_nu_continuum
+        return sha(out)
+
+    hashes = {}
+    third = nus.size // 3
+    for name, lines in lists.items():
+        variants = {"": {}, ", continuum": dict(keep_continuum_flux=True), ", shard": dict(shard=(third, third))}
+        if name == "dense sorted":
+            variants[", grid_plan=False"] = dict(grid_plan=False)
+            variants[", grid_plan=False, continuum"] = dict(grid_plan=False, keep_continuum_flux=True)
+        for label, kw in variants.items():
+            syn = make(lines, **kw)
+            case = {}
+            syn.enqueue()
+            case["eager"] = planes(syn)
+            syn.capture(batch=3)
+            for mode, step in (("captured", syn.step), ("batch of 3", syn.step_batch)):
+                syn.d_F.zero()
+                step()
+                case[mode] = planes(syn)
+            syn.close()
+            syn.d_F.zero()
+            syn.step()
+            case["after close()"] = planes(syn)
+            hashes[name + label] = case
+    # the two-collective mode, the whole list as the share.  The library takes it on frequency shards of long lists alone: the case of
+    # tests/test_gpu_round5.py (9000 lines, the second quarter of 20000 frequencies)
+    long_nus = synth.tracing_grid(5000.0, 5000.0 * (1.0 + 1.02 * 20000 / 1.0e5), R=1.0e5)[:20000]
+    long_lines = synth.synth_lines(long_nus, atm, 9000, seed=3, mix=(0.85, 0.12, 0.03))
+    for label, kw in (("", {}), (", continuum", dict(keep_continuum_flux=True))):
+        syn = SpectralSynthesizer(long_nus, atm["temperatures"], atm["dist"], th, w, long_lines, cont, ctx=ctx, shard=(5000, 5000), track_evaluations=False,
+                                  classify_share=(0, 9000), m_max=ctx.zeros((9000,)), **kw)
+        case = {}
+        syn.enqueue_classify()
+        syn.enqueue()
+        case["eager"] = planes(syn)
+        syn.capture()
+        syn.d_F.zero()
+        syn.step_classify()
+        syn.step()
+        case["captured"] = planes(syn)
+        syn.close()
+        hashes["two-collective" + label] = case
+
+    # ---- bits: everything that is asked on demand, behind a step with every kept plane and a broadening instrument
+    edges = np.r_[6560.75, 6561.2, np.linspace(6562.0, 6568.0, 25), 6571.0]  # (tests/test_gpu_macroturbulence.py: edge-affected and NaN pixels)
+    rng = np.random.default_rng(7)
+    col_w, pix_c, xi = rng.standard_normal(nus.size), rng.standard_normal(edges.size - 1), 1.5e5
+    direction, dF, dFc = rng.standard_normal(300), rng.standard_normal(nus.size), rng.standard_normal(nus.size)
+    noise, ivar = rng.standard_normal(edges.size - 1), rng.uniform(0.5, 2.0, edges.size - 1)
+    ivar[5] = 0.0
+    for name, lines in lists.items():
+        inst = Instrument(edges, sigma=0.05, ctx=ctx, v_rot=10.0, v_mac=3.0)
+        inst.set_radial_velocity(12.0)
+        syn = make(lines, keep_continuum_flux=True, keep_contribution=True, keep_response=True, instrument=inst)
+        case = {}
+        for mode, step in (("eager", syn.enqueue), ("unfused", syn.enqueue_unfused), ("captured", lambda: syn.capture().step())):
+            syn.d_F.zero()
+            step()
+            case[mode] = sha(dict(planes=planes(syn), contribution=syn.contribution, response_opacity=syn.response_opacity,
+                                  response_source=syn.response_source, observed=syn.observed, observed_normalized=syn.observed_normalized))
+        part = syn.alpha_line()
+        case["formation_mean"] = sha([syn.formation_mean(atm["temperatures"]), syn.formation_mean(ctx.upload(np.asarray(atm["temperatures"], dtype=np.float64)))])
+        case["flux_derivative"] = sha([syn.flux_derivative(part), syn.flux_derivative(ctx.upload(part))])
+        for per_depth in (False, True):
+            for wrt in ENGINE_WRT + (ENGINE_WRT,):
+                case[f"line_sensitivities {wrt} per_depth={per_depth}"] = sha([syn.line_sensitivities(col_w, per_depth, wrt), syn.line_sensitivities(None, per_depth, wrt)])
+        case["line_sensitivities device weights"] = sha(syn.line_sensitivities(ctx.upload(col_w)))
+        case["line_tangent"] = sha([syn.line_tangent(strength=direction), syn.line_tangent(damping=0.5, centre=direction * 1e8)])
+        case["flux_tangent"] = sha(syn.flux_tangent(doppler=direction))
+        case["microturbulence"] = sha([syn.microturbulence_sensitivity(xi, col_w), syn.microturbulence_sensitivity(xi), syn.microturbulence_tangent(xi)])
+        for normalized in (False, True):
+            tag = f" normalized={normalized}"
+            case["pixel_weights_to_grid" + tag] = sha([syn.pixel_weights_to_grid(pix_c, normalized), syn.pixel_weights_to_grid(ctx.upload(pix_c), normalized, True)])
+            case["observed_tangent" + tag] = sha([syn.observed_tangent(dF, dFc if normalized else None, normalized), syn.observed_tangent(ctx.upload(dF), None, normalized)])
+            case["observed_jacobian" + tag] = sha(syn.observed_jacobian(None, normalized))
+            case["observed_line_sensitivities" + tag] = sha(syn.observed_line_sensitivities(pix_c, normalized, wrt=ENGINE_WRT))
+            case["observed_macroturbulence_derivative" + tag] = sha(syn.observed_macroturbulence_derivative(pix_c, normalized))
+            obs = (syn.observed_normalized if normalized else syn.observed).numpy()
+            data = np.nan_to_num(obs) * (1.0 + 0.01 * noise)
+            directions = {"gf": dict(strength=(direction > 0).astype(np.float64)), "xi": {"microturbulence": xi}}
+            case["chi2_line_gradient" + tag] = sha(syn.chi2_line_gradient(data, ivar, normalized, wrt=ENGINE_WRT))
+            case["chi2_macroturbulence_gradient" + tag] = sha(syn.chi2_macroturbulence_gradient(data, ivar, normalized))
+            case["chi2_instrument_gradient" + tag] = sha(syn.chi2_instrument_gradient(data, ivar, None, normalized, curvature=True))
+            case["chi2_joint_gradient" + tag] = sha([syn.chi2_joint_gradient(data, ivar, ("v_rad", "v_mac"), directions, normalized, curvature=True),
+                                                     syn.chi2_joint_gradient(data, ivar, (), directions, normalized, curvature=True),
+                                                     syn.chi2_joint_gradient(data, ivar, None, None, normalized, curvature=True)])
+        syn.close()
+        hashes["on demand, " + name] = case
+
+    # ---- bits: the drop-in, one run per branch its step call had
+    import stardis_amd.radiation_field.base as rf
+    from stardis_amd.radiation_field import fused
+    from stardis_amd.radiation_field.source_functions.blackbody import blackbody_flux_at_nu
+
+    NS = types.SimpleNamespace
+    for variant in ("plain", "tracked", "source", "spherical", "line list", "molecules"):
+        plasma, model, config, _ = synth.fake_plasma(nus, atm, 300, seed=41, n_molecule_lines=200 if variant == "molecules" else 0)
+        config.no_of_thetas = 8
+        config.result_options = NS(return_radiation_field=variant in ("tracked", "spherical"))
+        if variant == "molecules":
+            config.opacity.line.include_molecules = True
+        if variant == "line list":
+            plasma.alpha_line_from_linelist = None
+        if variant == "spherical":
+            model.spherical = True
+            r = 7.0e10 + np.concatenate([[0.0], np.cumsum(np.asarray(model.geometry.dist_to_next_depth_point))])
+            model.geometry = NS(dist_to_next_depth_point=model.geometry.dist_to_next_depth_point, r=r, reference_r=r[-12])
+        source = (lambda nu, t: 1.0e-13 * t**4 * (nu / nu[0]) ** 2) if variant == "source" else blackbody_flux_at_nu
+        for continuum in (False, True):
+            field = fused.try_fused(rf.RadiationField, nus.copy(), model, plasma, config, source, continuum=continuum)
+            assert field is not None, variant
+            case = dict(F_nu=field.F_nu, total_alphas=field.opacities.total_alphas)
+            if continuum:
+                case["F_nu_continuum"] = field.F_nu_continuum
+            if config.result_options.return_radiation_field:
+                case["I_nus"] = field.I_nus
+            hashes[f"drop-in {variant}, continuum={continuum}"] = sha(case)
+
+    # ---- time at S-c2, constructed as bench.py constructs it: 500 eager enqueue() and their host time alone, 500 captured step()
+    wl = synth.make_workload("S-c2")
+    times = {}
+    for label, kw in (("", {}), (" grid_plan=False", dict(grid_plan=False))):
+        syn = SpectralSynthesizer(wl["nus"], wl["atm"]["temperatures"], wl["atm"]["dist"], wl["thetas"], wl["weights"], wl["lines"], wl["cont"], ctx=ctx,
+                                  track_evaluations=False, keep_line=False, **kw)
+        for step in (syn.enqueue, syn.capture().step):
+            t_end = time.perf_counter() + 0.5
+            while time.perf_counter() < t_end:
+                for _ in range(10):
+                    step()
+                ctx.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(500):
+                step()
+            t1 = time.perf_counter()
+            ctx.synchronize()
+            t2 = time.perf_counter()
+            if step == syn.enqueue:
+                times["step_us" + label], times["enqueue_host_us" + label] = (t2 - t0) / 500 * 1e6, (t1 - t0) / 500 * 1e6
+            else:
+                times["captured_step_us" + label] = (t2 - t0) / 500 * 1e6
+        syn.close()
+    print(json.dumps({"hashes": hashes, "us": times}))
+
+
 def spawn(lib, argv, timeout):
     p = subprocess.run([sys.executable] + argv, env=dict(os.environ, STARDIS_AMD_LIB=os.path.abspath(lib)), capture_output=True, text=True,
                        timeout=timeout, cwd=ROOT)
@@ -374,6 +577,9 @@ def main():
         return
     if mode == "adjoints-child":
         adjoints_child()
+        return
+    if mode == "engine-child":
+        engine_child(sys.argv[2])
         return
     old, new = sys.argv[2], sys.argv[3]
     if mode == "kernels":
@@ -403,16 +609,20 @@ def main():
             res[name + " 20 after 5"].append({"ms_per_step": j["ms_per_step"]})
         for name, rows in res.items():
             summary(name, rows, "us", 1e3, drop_first=True)
-    elif mode in ("stages", "adjoints"):
+    elif mode in ("stages", "adjoints", "engine"):
         rounds = int(sys.argv[4]) if len(sys.argv) > 4 else 7
         res = {"old": [], "new": []}
+        built = os.environ.get("STARDIS_AMD_LIB") or os.path.join(ROOT, "stardis_amd", "lib", "libstardis_hip.so")
         for r in range(rounds):
-            for name, lib in (("old", old), ("new", new)):
-                res[name].append(spawn(lib, [os.path.abspath(__file__), mode + "-child"], 300))
+            for name, leg in (("old", old), ("new", new)):
+                # (engine: the legs are two Python trees on the one built library)
+                lib, argv = (built, ["engine-child", os.path.abspath(leg)]) if mode == "engine" else (leg, [mode + "-child"])
+                res[name].append(spawn(lib, [os.path.abspath(__file__)] + argv, 300))
                 print(r, name, {k: round(v, 2) for k, v in res[name][-1]["us"].items()}, flush=True)
         hashes = [r["hashes"] for rows in res.values() for r in rows]
         differing = sorted({f"{case}: {entry}" for h in hashes[1:] for case in h for entry in h[case] if h[case][entry] != hashes[0][case][entry]})
-        n_hashes = sum(o is not None for case in hashes[0].values() for outs in case.values() for o in outs)
+        count = lambda v: sum(map(count, v.values() if isinstance(v, dict) else v)) if isinstance(v, (dict, list)) else int(isinstance(v, str))  # noqa: E731
+        n_hashes = count(hashes[0])
         print(f"{n_hashes} hashes per child, {len(hashes)} children: {'ALL EQUAL' if not differing else 'DIFFERENT: ' + '; '.join(differing)}")
         within = {name: all(r["hashes"] == rows[0]["hashes"] for r in rows) for name, rows in res.items()}  # (the item lists' order depends on the run)
         print("children of the same build agree among themselves:", within)

@@ -257,6 +257,28 @@ class SpectralSynthesizer:
     def flux_ptr(self):
         return ptr_of(self._flux_tensor) if self._flux_tensor is not None else self.d_F.ptr
 
+    def _device_vector(self, name, value, want, noun=None, at_least=False):
+        """A caller's vector (host array, DeviceArray or CUDA tensor) -> a device buffer of float64 values, checked on the host before
+        anything is uploaded; ValueError naming it.  want: a number — the values are flattened and there is one per `noun` — or a
+        shape, which the value has as it stands.  at_least: a device buffer may hold more values than want."""
+        shaped = isinstance(want, tuple)
+        n = int(np.prod(want, dtype=np.int64)) if shaped else int(want)
+        on_device = isinstance(value, _lib.DeviceArray) or hasattr(value, "data_ptr")
+        if on_device:
+            _require_f64_buffer(name, value, n if shaped or at_least else 0)
+            got = tuple(int(v) for v in value.shape)
+        else:
+            value = np.ascontiguousarray(value, dtype=np.float64)
+            got = value.shape if shaped else (value.size,)
+        if shaped:
+            if got != want:
+                raise ValueError(f"{name} must have shape {want}, got {got}")
+        elif not (on_device and at_least):
+            size = int(np.prod(got, dtype=np.int64))
+            if size != n:
+                raise ValueError(f"{name} must hold one value per {noun} ({n}), got {size}")
+        return value if on_device else self.ctx.upload(value if shaped else value.reshape(-1))
+
     # -- one step: everything from resident inputs to F_nu -----------------------------------------
     def enqueue_classify(self):
         """Two-collective mode, phase 1: this rank's share of the classification stream (+ grid spacing, line ranges and continuum
@@ -269,10 +291,14 @@ class SpectralSynthesizer:
                self.d_dw.ptr, self.d_g.ptr, self.gamma_cols, self.d_a.ptr, C.byref(self.cont), int(b), int(n), base)
 
     def enqueue(self):
-        """One fused step on the context's stream: sdx_synthesize_dev (pre-pass, line gather, total, raytrace); with
+        """One fused step on the context's stream: sdx_synthesize_opt_dev (pre-pass, line gather, total, raytrace); with
         keep_contribution, sdx_contribution_dev on the step's total_alphas behind it; with keep_response, sdx_response_dev behind that;
         with an instrument, F_lambda and sdx_observe_dev last."""
         self._enqueue_synthesis()
+        self._enqueue_tail()
+
+    def _enqueue_tail(self):
+        """what follows the synthesis of a step, fused or not: contribution, response, the instrument"""
         if self.keep_contribution:
             self._enqueue_contribution()
         if self.keep_response:
@@ -284,17 +310,17 @@ class SpectralSynthesizer:
         c, n, inst = self.ctx, self.n_nu, self.instrument
         last = 8 * (self.n_depth - 1) * self.count  # row N_d - 1
         c.call("sdx_flux_nu_to_lambda_dev", n, self.flux_ptr + last, self.d_nus.ptr, self.d_lambdas.ptr, self.d_Flam.ptr)
+        if self.keep_continuum_flux:
+            c.call("sdx_flux_nu_to_lambda_dev", n, self.d_Fc.ptr + last, self.d_nus.ptr, self.d_lambdas.ptr, self.d_Fclam.ptr)
         if not inst.broadens:
             inst.observe(self.d_lambdas, self.d_Flam, n, out=self.d_observed)
             if self.keep_continuum_flux:
-                c.call("sdx_flux_nu_to_lambda_dev", n, self.d_Fc.ptr + last, self.d_nus.ptr, self.d_lambdas.ptr, self.d_Fclam.ptr)
                 inst.observe(self.d_lambdas, self.d_Flam, n, reference=self.d_Fclam, out=self.d_observed_normalized)
             return
         # rotation, macroturbulence: F_lambda (and the continuum's) broadened ONCE per step, whatever is observed of them
         if not self.keep_continuum_flux:
             inst.observe(self.d_lambdas, inst.broaden(self.d_lambdas, self.d_Flam, n), n, out=self.d_observed, broadened=True)
             return
-        c.call("sdx_flux_nu_to_lambda_dev", n, self.d_Fc.ptr + last, self.d_nus.ptr, self.d_lambdas.ptr, self.d_Fclam.ptr)
         flux, cont = inst.broaden(self.d_lambdas, self.d_Flam, n, reference=self.d_Fclam)
         inst.observe(self.d_lambdas, flux, n, out=self.d_observed, broadened=True)
         inst.observe(self.d_lambdas, flux, n, reference=cont, out=self.d_observed_normalized, broadened=True)
@@ -310,60 +336,27 @@ class SpectralSynthesizer:
                       self.d_w.ptr, self.d_total.ptr, cnt, None, 0, self.d_Ra.ptr, cnt, self.d_Rs.ptr, cnt)
 
     def _enqueue_synthesis(self):
-        c = self.ctx
-        if self.keep_continuum_flux:
-            self._enqueue_opt()
-            return
-        if self.m_max is not None:  # phase 2 of the two-collective mode: everything behind the classification launch
-            opt = _lib.SynthesisOptions()
-            opt.line_m_max = ptr_of(self.m_max)
-            c.call("sdx_synthesize_opt_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, self.n_lines,
-                   self.d_ln.ptr, self.d_dw.ptr, self.d_g.ptr, self.gamma_cols, self.d_a.ptr, C.byref(self.cont), self.n_theta,
-                   self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, self.d_line.ptr if self.keep_line else None,
-                   self.d_total.ptr if self.keep_total else None, self.flux_ptr, self.count, C.byref(opt), None)
-            return
-        if self.linelist is not None:
-            c.call("sdx_synthesize_linelist_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count,
-                   self.linelist.byref(), C.byref(self.cont), self.n_theta, self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr,
-                   self.d_line.ptr if self.keep_line else None, self.d_total.ptr if self.keep_total else None, self.flux_ptr, self.count,
-                   ptr_of(self.d_evals) if self.count_evaluations else None)
-            return
-        if self.plan is not None:  # (a description that is zero but for the plan: sdx_synthesize_dev, bit for bit)
-            opt = _lib.SynthesisOptions()
-            opt.grid_plan = self.plan
-            c.call("sdx_synthesize_opt_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, self.n_lines,
-                   self.d_ln.ptr, self.d_dw.ptr, self.d_g.ptr, self.gamma_cols, self.d_a.ptr, C.byref(self.cont), self.n_theta,
-                   self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, self.d_line.ptr if self.keep_line else None,
-                   self.d_total.ptr if self.keep_total else None, self.flux_ptr, self.count, C.byref(opt),
-                   ptr_of(self.d_evals) if self.count_evaluations else None)
-            return
-        c.call("sdx_synthesize_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, self.n_lines,
-               self.d_ln.ptr, self.d_dw.ptr, self.d_g.ptr, self.gamma_cols, self.d_a.ptr, C.byref(self.cont), self.n_theta,
-               self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, self.d_line.ptr if self.keep_line else None,
-               self.d_total.ptr if self.keep_total else None, self.flux_ptr, self.count, ptr_of(self.d_evals) if self.count_evaluations else None)
-
-    def _enqueue_opt(self):
-        """The step through sdx_synthesize_opt_dev with the continuum flux (dense list, line list or phase 2 of the two-collective
-        mode)."""
-        c = self.ctx
+        """The step, whatever its configuration: one sdx_synthesis_options, one sdx_synthesize_opt_dev call.  A line list of scalars
+        goes in the options (the dense pointers are not read); the plan only with a dense list outside the two-collective mode, where
+        the library would ignore it; phase 2 of the two-collective mode counts no evaluations."""
         opt = _lib.SynthesisOptions()
-        opt.F_nu_continuum = self.d_Fc.ptr
-        opt.continuum_ld = self.count
-        if self.m_max is not None:
-            opt.line_m_max = ptr_of(self.m_max)
-        evals = ptr_of(self.d_evals) if self.count_evaluations and self.m_max is None else None
-        line, total = self.d_line.ptr if self.keep_line else None, self.d_total.ptr if self.keep_total else None
+        m_max = self.m_max
+        if self.keep_continuum_flux:
+            opt.F_nu_continuum, opt.continuum_ld = self.d_Fc.ptr, self.count
+        if m_max is not None:  # phase 2 of the two-collective mode: everything behind the classification launch
+            opt.line_m_max = ptr_of(m_max)
         if self.linelist is not None:
             opt.linelist = C.cast(self.linelist.byref(), C.POINTER(_lib.LineListStruct))
-            c.call("sdx_synthesize_opt_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, self.n_lines, None, None,
-                   None, self.gamma_cols, None, C.byref(self.cont), self.n_theta, self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, line, total,
-                   self.flux_ptr, self.count, C.byref(opt), evals)
-            return
-        if self.plan is not None and self.m_max is None:
-            opt.grid_plan = self.plan
-        c.call("sdx_synthesize_opt_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, self.n_lines, self.d_ln.ptr,
-               self.d_dw.ptr, self.d_g.ptr, self.gamma_cols, self.d_a.ptr, C.byref(self.cont), self.n_theta, self.d_t.ptr, self.d_ray.ptr,
-               self.d_w.ptr, line, total, self.flux_ptr, self.count, C.byref(opt), evals)
+            ln = dw = g = al = None
+        else:
+            ln, dw, g, al = self.d_ln.ptr, self.d_dw.ptr, self.d_g.ptr, self.d_a.ptr
+            if self.plan is not None and m_max is None:
+                opt.grid_plan = self.plan
+        evals = ptr_of(self.d_evals) if self.count_evaluations and m_max is None else None
+        self.ctx.call("sdx_synthesize_opt_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, self.n_lines, ln, dw, g,
+                      self.gamma_cols, al, C.byref(self.cont), self.n_theta, self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr,
+                      self.d_line.ptr if self.keep_line else None, self.d_total.ptr if self.keep_total else None, self.flux_ptr, self.count,
+                      C.byref(opt), evals)
 
     def enqueue_unfused(self):
         """The same step through the individual entry points (what calc_alphas + raytrace issue)."""
@@ -381,12 +374,7 @@ class SpectralSynthesizer:
         nus_shard = self.d_nus.ptr + 8 * self.begin
         c.call("sdx_raytrace_dev", nd, cnt, self.n_theta, nus_shard, self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr,
                self.d_total.ptr, cnt, self.flux_ptr, cnt, None, 0)
-        if self.keep_contribution:
-            self._enqueue_contribution()
-        if self.keep_response:
-            self._enqueue_response()
-        if self.instrument is not None:
-            self._enqueue_observe()
+        self._enqueue_tail()
 
     def capture(self, eager_phase2=True, batch=1):
         """Record one step into a hipGraph (after one eager step has sized the scratch).  batch > 1: ALSO a graph of `batch` consecutive
@@ -424,29 +412,27 @@ class SpectralSynthesizer:
             self.graph_batch, self.batch = record(many), int(batch)
         return self
 
+    def _replay(self, which, **capture_args):
+        """Launch the recorded graph `which`.  Another, larger synthesis on this context may have made the library reallocate its
+        scratch: the captured pointers are dead then.  Capture again with this graph's own arguments (the scratch is large enough
+        for both now) and replay."""
+        try:
+            self.ctx.call("sdx_graph_launch", getattr(self, which))
+        except _lib.StaleGraphError:
+            self._destroy_graphs()
+            self.capture(**capture_args)
+            self.ctx.call("sdx_graph_launch", getattr(self, which))
+
     def step_classify(self):
         if self.graph_classify is not None:
-            try:
-                self.ctx.call("sdx_graph_launch", self.graph_classify)
-                return
-            except _lib.StaleGraphError:
-                # (m_max holds the previous step's values or nothing yet: no eager phase 2 on it)
-                self._destroy_graphs()
-                self.capture(eager_phase2=False)
-                self.ctx.call("sdx_graph_launch", self.graph_classify)
-                return
-        self.enqueue_classify()
+            # (m_max holds the previous step's values or nothing yet: no eager phase 2 on it)
+            self._replay("graph_classify", eager_phase2=False)
+        else:
+            self.enqueue_classify()
 
     def step(self):
         if self.graph is not None:
-            try:
-                self.ctx.call("sdx_graph_launch", self.graph)
-            except _lib.StaleGraphError:
-                # another, larger synthesis on this context made the library reallocate its scratch: the captured pointers
-                # are dead.  Capture again (the scratch is large enough for both now) and replay.
-                self._destroy_graphs()
-                self.capture()
-                self.ctx.call("sdx_graph_launch", self.graph)
+            self._replay("graph")
         else:
             self.enqueue()
 
@@ -455,14 +441,9 @@ class SpectralSynthesizer:
         if self.graph_batch is None:
             self.step()
             return 1
-        try:
-            self.ctx.call("sdx_graph_launch", self.graph_batch)
-        except _lib.StaleGraphError:
-            n = self.batch
-            self._destroy_graphs()
-            self.capture(batch=n)
-            self.ctx.call("sdx_graph_launch", self.graph_batch)
-        return self.batch
+        n = self.batch  # (read here: destroying a stale graph resets it)
+        self._replay("graph_batch", batch=n)
+        return n
 
     def synchronize(self):
         self.ctx.synchronize()
@@ -519,17 +500,7 @@ class SpectralSynthesizer:
         and continuum."""
         c = self.ctx
         d_R = self.response_opacity
-        n = self.n_depth * self.count
-        if isinstance(alpha_part, _lib.DeviceArray) or hasattr(alpha_part, "data_ptr"):
-            _require_f64_buffer("alpha_part", alpha_part, n)
-            if tuple(int(v) for v in alpha_part.shape) != (self.n_depth, self.count):
-                raise ValueError(f"alpha_part must have shape {(self.n_depth, self.count)}, got {tuple(alpha_part.shape)}")
-            d_part = alpha_part
-        else:
-            host = np.ascontiguousarray(alpha_part, dtype=np.float64)
-            if host.shape != (self.n_depth, self.count):
-                raise ValueError(f"alpha_part must have shape {(self.n_depth, self.count)}, got {host.shape}")
-            d_part = c.upload(host)
+        d_part = self._device_vector("alpha_part", alpha_part, (self.n_depth, self.count))
         out = c.empty((self.count,))
         c.call("sdx_response_project_dev", self.n_depth, self.count, d_R.ptr, self.count, ptr_of(d_part), self.count, self.d_total.ptr,
                self.count, out.ptr)
@@ -590,9 +561,7 @@ class SpectralSynthesizer:
         if xi == 0.0:
             return 0.0
         per = self.line_sensitivities(weights, per_depth=True, wrt="doppler").numpy()
-        dw = self._tables_in_caller_order()[1].numpy()
-        nu_over_c = self._line_nus_in_caller_order() / K.C_CGS
-        return float(np.sum(per * (xi * (nu_over_c * nu_over_c)[:, None] / (dw * dw))))
+        return float(np.sum(per * self._microturbulence_direction(xi)))
 
     def line_sensitivities(self, weights=None, per_depth=False, wrt="strength"):
         """-> DeviceArray (n_lines,), or (n_lines, N_d) with per_depth=True: for every line l of the list, in the order the caller passed
@@ -620,19 +589,7 @@ class SpectralSynthesizer:
         names, single = self._wrt_names(wrt)
         self._require_response()
         c = self.ctx
-        d_w = None
-        if weights is not None:
-            if isinstance(weights, _lib.DeviceArray) or hasattr(weights, "data_ptr"):
-                _require_f64_buffer("weights", weights, 0)
-                size = int(np.prod(tuple(weights.shape), dtype=np.int64))
-                d_w = weights
-            else:
-                host = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-                size = host.size
-            if size != self.count:
-                raise ValueError(f"weights must hold one value per column of the synthesizer ({self.count}), got {size}")
-            if d_w is None:
-                d_w = c.upload(host)
+        d_w = None if weights is None else self._device_vector("weights", weights, self.count, "column of the synthesizer")
         cnt = self.count
         d_W = c.empty((self.n_depth, cnt))
         c.call("sdx_response_weight_dev", self.n_depth, cnt, self.d_Ra.ptr, cnt, self.d_total.ptr, cnt, ptr_of(d_w), d_W.ptr, cnt)
@@ -730,17 +687,7 @@ class SpectralSynthesizer:
 
     def _pixel_vector(self, name, c):
         """a vector over the instrument's pixels (host array, DeviceArray or CUDA tensor) -> a device buffer; ValueError naming it"""
-        n_pix = self.instrument.n_pix
-        if isinstance(c, _lib.DeviceArray) or hasattr(c, "data_ptr"):
-            _require_f64_buffer(name, c, 0)
-            size = int(np.prod(tuple(c.shape), dtype=np.int64))
-            if size != n_pix:
-                raise ValueError(f"{name} must hold one value per pixel of the instrument ({n_pix}), got {size}")
-            return c
-        host = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
-        if host.size != n_pix:
-            raise ValueError(f"{name} must hold one value per pixel of the instrument ({n_pix}), got {host.size}")
-        return self.ctx.upload(host)
+        return self._device_vector(name, c, self.instrument.n_pix, "pixel of the instrument")
 
     def pixel_weights_to_grid(self, c, normalized=False, with_continuum=False):
         """-> DeviceArray (n_nu,): the weights w over the columns of F_nu[-1] with  sum_j c_j observed_j = sum_i w_i F_nu_i[-1]  over the
@@ -783,12 +730,13 @@ class SpectralSynthesizer:
         self._wrt_names(wrt)
         self._require_instrument()
         self._require_response()
-        chi2, c = self._chi2_pixel_weights(data, inverse_variance, normalized)
+        chi2, c, _, _ = self._chi2_pixel_weights(data, inverse_variance, normalized)
         return chi2, self.observed_line_sensitivities(c, normalized, per_depth, wrt)
 
     def _chi2_pixel_weights(self, data, inverse_variance, normalized):
-        """-> (chi2, c): chi-square over the pixels chi2_line_gradient uses and c_j = d chi2 / d observed_j = -2 ivar_j (data_j -
-        observed_j), 0 at the pixels left out"""
+        """-> (chi2, c, use, w): chi-square over the pixels chi2_line_gradient uses, c_j = d chi2 / d observed_j = -2 ivar_j (data_j -
+        observed_j), 0 at the pixels left out, the mask of the pixels used and the inverse variance, 0 at the others.  The one
+        download of the observed spectrum of a chi-square call."""
         if normalized:
             self._require_continuum()
         n_pix = self.instrument.n_pix
@@ -805,7 +753,21 @@ class SpectralSynthesizer:
             raise ValueError("no pixel left: every pixel is NaN (not covered by the grid), edge-affected or has inverse_variance 0")
         r = np.where(use, d, 0.0) - np.where(use, obs, 0.0)
         w = np.where(use, ivar, 0.0)
-        return float(np.sum(w * r * r)), -2.0 * w * r
+        return float(np.sum(w * r * r)), -2.0 * w * r, use, w
+
+    @staticmethod
+    def _chi2_normal_equations(chi2, c, use, w, names, columns, curvature):
+        """-> (chi2, gradient) or (chi2, gradient, H) of the parameters `names` from their columns d observed / d p (device arrays, by
+        name): the sums over the pixels used, taken on the host (math.fsum of the fp64 products)"""
+        J = {k: np.where(use, columns[k].numpy(), 0.0) for k in names}
+        grad = {k: math.fsum(c * J[k]) for k in names}
+        if not curvature:
+            return chi2, grad
+        H = np.empty((len(names), len(names)))
+        for ia, a in enumerate(names):  # (the upper triangle, mirrored: symmetric bit for bit)
+            for ib in range(ia, len(names)):
+                H[ia, ib] = H[ib, ia] = 2.0 * math.fsum(w * J[a] * J[names[ib]])
+        return chi2, grad, H
 
     def observed_macroturbulence_derivative(self, c, normalized=False):
         """-> float: d(sum_j c_j observed_j) / d zeta per km/s (normalized=True: of observed_normalized) at the last step's spectrum
@@ -842,7 +804,7 @@ class SpectralSynthesizer:
         to the macroturbulence zeta per km/s: observed_macroturbulence_derivative with c_j = -2 ivar_j (data_j - observed_j).  No
         v_mac, or zeta = 0, raises."""
         self._require_macroturbulence()
-        chi2, c = self._chi2_pixel_weights(data, inverse_variance, normalized)
+        chi2, c, _, _ = self._chi2_pixel_weights(data, inverse_variance, normalized)
         return chi2, self.observed_macroturbulence_derivative(c, normalized)
 
     # -- forward mode: one direction, every pixel ---------------------------------------------------------------------------------
@@ -850,14 +812,7 @@ class SpectralSynthesizer:
         """a tangent over the columns of F_nu[-1] (host array, DeviceArray or CUDA tensor) -> F_lambda's tangent on the device:
         the factor nu / lambda of sdx_flux_nu_to_lambda_dev applied"""
         n = self.n_nu
-        if isinstance(v, _lib.DeviceArray) or hasattr(v, "data_ptr"):
-            _require_f64_buffer(name, v, n)
-            d_v = v
-        else:
-            host = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
-            if host.size != n:
-                raise ValueError(f"{name} must hold one value per column of the spectrum ({n}), got {host.size}")
-            d_v = self.ctx.upload(host)
+        d_v = self._device_vector(name, v, n, "column of the spectrum", at_least=True)  # (a longer device buffer passes, as it always did)
         out = self.ctx.empty((n,))
         self.ctx.call("sdx_flux_nu_to_lambda_dev", n, ptr_of(d_v), self.d_nus.ptr, self.d_lambdas.ptr, out.ptr)
         return out
@@ -898,22 +853,8 @@ class SpectralSynthesizer:
         bits everywhere), as observed_macroturbulence_derivative takes its own."""
         self._require_instrument()
         names = self.instrument._wrt(wrt)
-        chi2, c = self._chi2_pixel_weights(data, inverse_variance, normalized)
-        ivar =np.ascontiguousarray(inverse_variance, dtype=np.float64).reshape(-1)
-        obs = (self.d_observed_normalized if normalized else self.d_observed).numpy()
-        used = ~np.isnan(obs) & (ivar != 0)
-        if self.instrument.broadens:
-            used &= ~self.instrument.edge_affected(self.lambdas)
-        J = {k: np.where(used, v.numpy(), 0.0) for k, v in self.observed_jacobian(names, normalized).items()}
-        grad = {k: math.fsum(c * J[k]) for k in names}
-        if not curvature:
-            return chi2, grad
-        w = np.where(used, ivar, 0.0)
-        H = np.empty((len(names), len(names)))
-        for ia, a in enumerate(names):  # (the upper triangle, mirrored: symmetric bit for bit)
-            for ib in range(ia, len(names)):
-                H[ia, ib] = H[ib, ia] = 2.0 * math.fsum(w * J[a] * J[names[ib]])
-        return chi2, grad, H
+        chi2, c, use, w = self._chi2_pixel_weights(data, inverse_variance, normalized)
+        return self._chi2_normal_equations(chi2, c, use, w, names, self.observed_jacobian(names, normalized), curvature)
 
     def chi2_joint_gradient(self, data, inverse_variance, instrument_wrt=(), line_directions=None, normalized=False, curvature=False):
         """-> (chi2, {p: d chi2 / d p}), with curvature=True -> (chi2, gradient, H): chi2_instrument_gradient over the instrument
@@ -931,38 +872,21 @@ class SpectralSynthesizer:
         clash = [k for k in line_directions if k in inst_names]
         if clash:
             raise ValueError(f"line_directions reuses the instrument's parameter names {clash}")
-        chi2, c = self._chi2_pixel_weights(data, inverse_variance, normalized)
-        ivar = np.ascontiguousarray(inverse_variance, dtype=np.float64).reshape(-1)
-        obs = (self.d_observed_normalized if normalized else self.d_observed).numpy()
-        used = ~np.isnan(obs) & (ivar != 0)
-        if self.instrument.broadens:
-            used &= ~self.instrument.edge_affected(self.lambdas)
+        chi2, c, use, w = self._chi2_pixel_weights(data, inverse_variance, normalized)
         columns = dict(self.observed_jacobian(inst_names, normalized)) if inst_names else {}
         columns.update(self.observed_line_jacobian(line_directions, normalized))
-        names = tuple(inst_names) + tuple(line_directions)
-        J = {k: np.where(used, columns[k].numpy(), 0.0) for k in names}
-        grad = {k: math.fsum(c * J[k]) for k in names}
-        if not curvature:
-            return chi2, grad
-        w = np.where(used, ivar, 0.0)
-        H = np.empty((len(names), len(names)))
-        for ia, a in enumerate(names):  # (the upper triangle, mirrored: symmetric bit for bit)
-            for ib in range(ia, len(names)):
-                H[ia, ib] = H[ib, ia] = 2.0 * math.fsum(w * J[a] * J[names[ib]])
-        return chi2, grad, H
+        return self._chi2_normal_equations(chi2, c, use, w, tuple(inst_names) + tuple(line_directions), columns, curvature)
 
     @property
     def observed(self):
         """-> DeviceArray (n_pix,): the last step's spectrum as the instrument records it (`.numpy()` for a host array)."""
-        if self.instrument is None:
-            raise RuntimeError("no instrument: construct the synthesizer with instrument=Instrument(...)")
+        self._require_instrument()
         return self.d_observed
 
     @property
     def observed_normalized(self):
         """-> DeviceArray (n_pix,): the continuum-normalised observed spectrum of the last step."""
-        if self.instrument is None:
-            raise RuntimeError("no instrument: construct the synthesizer with instrument=Instrument(...)")
+        self._require_instrument()
         self._require_continuum()
         return self.d_observed_normalized
 
@@ -971,14 +895,7 @@ class SpectralSynthesizer:
         under the last step's contribution function (sdx_formation_mean_dev)."""
         c = self.ctx
         d_C = self.contribution
-        if isinstance(x, _lib.DeviceArray) or hasattr(x, "data_ptr"):
-            _require_f64_buffer("x", x, self.n_depth)
-            d_x = x
-        else:
-            host = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
-            if host.size != self.n_depth:
-                raise ValueError(f"x must hold one value per depth point ({self.n_depth}), got {host.size}")
-            d_x = c.upload(host)
+        d_x = self._device_vector("x", x, self.n_depth, "depth point", at_least=True)  # (a longer device buffer passes, as it always did)
         out = c.empty((self.count,))
         c.call("sdx_formation_mean_dev", self.n_depth, self.count, d_C.ptr, self.count, ptr_of(d_x), out.ptr)
         return out
@@ -1018,15 +935,11 @@ class SpectralSynthesizer:
             pass
 
     def _destroy_graphs(self):
-        if self.graph is not None:
-            self.ctx.call("sdx_graph_destroy", self.graph)
-            self.graph = None
-        if self.graph_classify is not None:
-            self.ctx.call("sdx_graph_destroy", self.graph_classify)
-            self.graph_classify = None
-        if self.graph_batch is not None:
-            self.ctx.call("sdx_graph_destroy", self.graph_batch)
-            self.graph_batch, self.batch = None, 1
+        for which in ("graph", "graph_classify", "graph_batch"):
+            if getattr(self, which) is not None:
+                self.ctx.call("sdx_graph_destroy", getattr(self, which))
+                setattr(self, which, None)
+        self.batch = 1
 
 
 class SynthesisPool:

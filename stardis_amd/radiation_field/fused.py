@@ -1,5 +1,5 @@
 """create_stellar_radiation_field in ONE device pass: what stardis/radiation_field/base.py:71-117 computes, through
-sdx_synthesize_dev instead of one kernel + one (N_d, N_nu) download per opacity source.
+sdx_synthesize_opt_dev instead of one kernel + one (N_d, N_nu) download per opacity source.
 
 The general mirror (calc_alphas, raytrace) forms every entry of `opacities_dict` as a host array because the reference does;
 a caller of run_stardis reads `F_nu` and, now and then, one of those entries.  Here the fused step (pre-pass + continuum +
@@ -295,23 +295,18 @@ def _run_step(v):
         field._I_dev = ctx.empty((nd, nus.size, int(config.no_of_thetas)))
     line_struct = None
     d_Fc = ctx.empty((nd, nus.size)) if continuum else None
-    if spherical or n_mol or (line_spec is not None and n_lines) or continuum:
-        opt = SynthesisOptions()
-        if continuum:
-            opt.F_nu_continuum, opt.continuum_ld = d_Fc.ptr, nus.size
-        opt.source, opt.source_ld = P("source"), nus.size
-        opt.I_nus = field._I_dev.ptr if tracked else None
-        opt.inward_rays, opt.photospheric_correction = (1 if spherical else 0), float(correction)
-        if n_mol:
-            opt.n_line_planes, opt.line_plane[0], opt.line_plane_ld = 1, d_mol.ptr, nus.size
-        if line_spec is not None and n_lines:
-            line_struct = _linelist_struct(line_spec, "ls", P)
-            opt.linelist = C.pointer(line_struct)
-        ctx.call("sdx_synthesize_opt_dev", *step, C.byref(opt), None)
-    elif tracked or source is not None:
-        ctx.call("sdx_synthesize_ex_dev", *step, P("source"), nus.size, field._I_dev.ptr if tracked else None, None)
-    else:
-        ctx.call("sdx_synthesize_dev", *step, None)
+    opt = SynthesisOptions()  # (every configuration through the one entry: an option that is not asked for stays zero)
+    if continuum:
+        opt.F_nu_continuum, opt.continuum_ld = d_Fc.ptr, nus.size
+    opt.source, opt.source_ld = P("source"), nus.size
+    opt.I_nus = field._I_dev.ptr if tracked else None
+    opt.inward_rays, opt.photospheric_correction = (1 if spherical else 0), float(correction)
+    if n_mol:
+        opt.n_line_planes, opt.line_plane[0], opt.line_plane_ld = 1, d_mol.ptr, nus.size
+    if line_spec is not None and n_lines:
+        line_struct = _linelist_struct(line_spec, "ls", P)
+        opt.linelist = C.pointer(line_struct)
+    ctx.call("sdx_synthesize_opt_dev", *step, C.byref(opt), None)
     d_C = None
     if contribution:  # the decomposition of the emergent flux by layer, from the total opacity and source function the step traced
         d_C = ctx.empty((nd, nus.size))
