@@ -525,6 +525,48 @@ int sdx_line_tangent_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* 
 int sdx_response_weight_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* R_alpha, int64_t R_ld,
                             const double* total, int64_t total_ld, const double* nu_weight, double* weight, int64_t weight_ld);
 
+/* ---- isolated-line equivalent widths and line depths: one line alone over a background ----------------
+ * HOW STRONG is this one line, on its own: what a one-line synthesis over the background gives, integrated by the trapezoid rule over
+ * the points the line reaches — per selected line and per trial strength, without a step per line.  The reference has no counterpart.
+ * For a selected line l and a strength factor s (row j, column k of the outputs):
+ *   alpha'[d] = mul_rn(alphas[l][d], s).
+ *   The window at depth d is the window rule (opacities_solvers/base.py:556-575) on the GLOBAL grid with alpha'[d]: bit for bit the window
+ *     sdx_line_windows_dev gives for a table holding alpha'.
+ *   A[d][i] = add_rn(B[d][i], term), B the caller's background opacity plane; inside the depth's window term is the line's term as the
+ *     fp64 line kernels and the adjoints evaluate it (1 / doppler, y and the amplitude from doppler, gamma and alpha'), outside it is +0.
+ *   F(i) and F_B(i) are the emergent fluxes (row n_depth - 1) of the plane-parallel formal solution of A and of B: the Planck source, the
+ *     step's coefficients with the tau = 0 -> (1, 0) rule, the angles summed in sdx_raytrace_dev's order.  Both are formed in the same
+ *     launch by the same operations from the same staged source values and ray lengths, so where the line adds exactly zero at every
+ *     depth F and F_B have the same bits.
+ *   r(i) = (F_B(i) - F(i)) / F_B(i): one subtraction and one IEEE division (not 1 - F / F_B).
+ *   U is the union over depth of the windows (an interval).
+ *   Node weights on the caller's abscissa x[n_nu] (global, strictly monotone; lambda in Angstrom gives W in Angstrom):
+ *     h(i) = 1/2 (|x[i+1] - x[i]| [i+1 in U] + |x[i] - x[i-1]| [i-1 in U]),  U the UNCLIPPED union, so frequency shards add.
+ *   W = sum over i in U within the shard of h(i) r(i);  depth = max over the same i of r(i);  both 0.0 where no such i exists.
+ *   Shards combine W by addition and depth by max; the max of the shards' depths is exact whenever some r >= 0 (a shard without
+ *   points reports 0.0, which the max then ignores; where every r is negative it would win).
+ * A zero-strength line gives W = depth = 0 exactly.  Row j depends on its own line and strength alone: not on what else is selected,
+ * nor on n_scale.  Deterministic: no floating-point atomics, every sum in an order that the tables, the selection and the shard fix.
+ * Always fp64, always the direct sum (no far field), the Planck source, plane-parallel geometry.
+ * nus [n_nu]; the shard is the columns [nu_begin, nu_begin + nu_count); line arrays as for sdx_line_adjoint_dev (any order; gamma_cols 1
+ * or n_depth); line_index [n_sel] (int64, device; repeats allowed), NULL: all lines, n_sel = n_lines; scale [n_sel][n_scale], NULL: 1.0,
+ * n_scale >= 1; background [n_depth][background_ld], column 0 at global index nu_begin; temperatures [n_depth]; ray_dist
+ * [n_depth - 1][n_theta]; theta_weights [n_theta]; out_W and out_depth [n_sel][n_scale], either may be NULL, not both.
+ * Refused with SDX_ERR_ARG before anything is enqueued (also for an empty selection, so a caller can ask at set-up time): a null context,
+ * mixed_precision = 1, n_depth < 2, n_theta outside 1..64, a model whose columns do not fit LDS at one frequency per wave, both outputs
+ * NULL, gamma_cols neither 1 nor n_depth, a shard outside the grid, n_sel * n_scale * nu_count beyond 2^34.  The indices of line_index
+ * live in device memory and are NOT checked here: the kernels clamp them into [0, n_lines) (no access out of bounds, the clamped line's
+ * values); ops.equivalent_widths and SpectralSynthesizer.equivalent_widths check them on the host before upload and raise.
+ * n_sel = 0 or nu_count = 0: SDX_OK, nothing is launched.  Only enqueues on the context's stream and reads nothing back, so it can be
+ * captured; its scratch is the context's (shared with the line adjoints) and grows outside a capture only (one eager call of the same
+ * size first).  Stage name of the profile hooks: k_line_ew (five launches). */
+int sdx_line_equivalent_widths_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count,
+                                   const double* x, int64_t n_lines, const double* line_nus, const double* doppler_widths,
+                                   const double* gammas, int gamma_cols, const double* alphas, int64_t n_sel,
+                                   const int64_t* line_index, int n_scale, const double* scale, const double* background,
+                                   int64_t background_ld, int n_theta, const double* temperatures, const double* ray_dist,
+                                   const double* theta_weights, double* out_W, double* out_depth);
+
 /* ---- fused synthesis for resident data (the benchmark path) ---------------------------------
  * total_alphas[d,i] = ((((file + bf) + ff) + rayleigh) + electron) + line   in calc_alphas order
  * (:655-738), then raytrace.  Any source pointer group may be NULL (skipped, contributes nothing).

@@ -187,6 +187,8 @@ PROTOTYPES = {
     "sdx_line_tangent_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp] + [_vp] * 4 + [_int, _vp, _i64]),
     "sdx_line_tangent_f64": (_int, [_vp, _int, _i64, _vp, _i64, _vp, _vp, _vp, _int, _vp] + [_vp] * 4 + [_int, _vp]),
     "sdx_response_weight_dev": (_int, [_vp, _int, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64]),
+    "sdx_line_equivalent_widths_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _int, _vp, _i64, _vp, _int, _vp, _vp, _i64, _int,
+                                              _vp, _vp, _vp, _vp, _vp]),
     "sdx_total_alphas_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, C.POINTER(Continuum), _vp, _i64, _vp, _i64]),
     "sdx_convolve1d_reflect_dev": (_int, [_vp, _i64, _vp, _int, _vp, _int, _vp]),
     "sdx_flux_nu_to_lambda_dev": (_int, [_vp, _i64, _vp, _vp, _vp, _vp]),

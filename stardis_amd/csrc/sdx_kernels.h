@@ -6509,4 +6509,254 @@ __global__ __launch_bounds__(kBlock) void k_voigt_grad(int64_t n, const double* 
     out_k[i] = t, out_kx[i] = tx, out_ky[i] = ty;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Isolated-line equivalent widths (sdx_line_equivalent_widths_dev; the definition stands in include/stardis_hip.h).  An ITEM is a
+// (selected line j, strength factor k) pair, item = j * n_scale + k; its line's opacities are alpha' = mul_rn(alpha, s) at every depth.
+//   k_line_adjoint_setup  the grid spacing and the centres of all lines (the adjoints' kernel, their scratch head)
+//   k_ew_plan    one thread per item: window_rule on the global grid with alpha' at every depth -> the union [ulo, uhi) (every window
+//                holds the centre's neighbourhood, so the union is an interval: the smallest lower and the largest upper bound), and
+//                the number of work units of the item: segments of kEwSegment points of the union clipped to the shard
+//   k_ew_scan    one block: the exclusive prefix sum of the unit counts -> uoff [items + 1].  Unit u of item t is segment u - uoff[t]:
+//                the lists follow from the tables, the selection and the shard alone (no atomics anywhere)
+//   k_ew_walk    a workgroup per unit (blocks stride the units; the item of a unit by bisection of uoff).  The block stages the item's
+//                per-depth constants once (EwColumns), then every wave takes gpw points of the segment at a time: lane <-> (point,
+//                angle) as k_raytrace_cont; the lanes of a point stage its column — voigt_term inside the depth's window, +0 outside,
+//                A = add_rn(B, term), sqrt(A), sqrt(B), the Planck source — and walk the two recurrences, total and background, on
+//                the same ray lengths and source values with the same rt_coef operations.  One theta-sum per chain at the end, in
+//                k_raytrace's order (two ascending halves); r = (F_B - F) / F_B, the node weight h, and the term h r and r into the
+//                segment's slots.  Wave 0 closes the unit: lane p adds slots p, p + 64, p + 128, p + 192 in this order, a
+//                butterfly (offsets 32 ... 1) adds the lanes; the maximum of r likewise -> partial[u]
+//   k_ew_gather  one thread per item: the units in ascending order, add_rn for W, fmax for the depth; no unit: both 0.0
+// An index of line_index outside [0, n_lines) is clamped here (no access out of bounds); the Python layer refuses it before upload.
+struct EwArgs {
+    int n_depth, gamma_cols, n_scale, n_theta;
+    int64_t n_nu, nu_begin, nu_count, n_lines, n_sel;
+    const double *nus, *x, *line_nus, *doppler, *gammas, *alphas;
+    const int64_t* line_index;  // [n_sel] or null: line j
+    const double* scale;        // [n_sel][n_scale] or null: 1.0
+    const double* background;   // [n_depth][bld], column 0 at nu_begin
+    int64_t bld;
+    const double *temps, *ray_dist, *wts;
+};
+struct EwWork {
+    const double* pd;   // [0] = d_nu, [1] = 1 / d_nu (k_line_adjoint_setup)
+    const int* centre;  // [N_l] (k_line_adjoint_setup)
+    int* ulo;           // [items] the union of the item's windows, unclipped
+    int* uhi;
+    int* uoff;          // [items + 1] the item's first unit
+    double2* partial;   // [units] (W, depth) of a unit
+};
+
+__device__ __forceinline__ int64_t ew_line(const EwArgs& a, int64_t j)
+{
+    const int64_t l = a.line_index ? a.line_index[j] : j;
+    return l < 0 ? 0 : (l >= a.n_lines ? a.n_lines - 1 : l);
+}
+
+__global__ __launch_bounds__(kBlock) void k_ew_plan(EwArgs a, EwWork w)
+{
+    const int64_t n_items = a.n_sel * a.n_scale;
+    const int64_t item = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (item >= n_items) return;
+    const int64_t j = item / a.n_scale;
+    const int64_t l = ew_line(a, j);
+    const double s = a.scale ? a.scale[item] : 1.0;
+    const double d_nu = w.pd[0], r_dnu = w.pd[1];
+    const int c = w.centre[l];
+    int ulo = 2147483647, uhi = 0;
+    for (int d = 0; d < a.n_depth; ++d) {
+        int lo, hi;
+        window_rule(c, a.n_nu, d_nu, r_dnu, a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)], a.doppler[l * a.n_depth + d],
+                    mul_rn(a.alphas[l * a.n_depth + d], s), lo, hi);
+        ulo = min(ulo, lo), uhi = max(uhi, hi);
+    }
+    w.ulo[item] = ulo, w.uhi[item] = uhi;
+    const int64_t b = max((int64_t)ulo, a.nu_begin), e = min((int64_t)uhi, a.nu_begin + a.nu_count);
+    w.uoff[item] = e > b ? (int)((e - b + kEwSegment - 1) / kEwSegment) : 0;
+}
+
+// counts in uoff[0 .. n) -> their exclusive prefix sums in place, the total in uoff[n]; one block of kPreBlock threads, a run of
+// consecutive items per thread
+__global__ __launch_bounds__(kPreBlock) void k_ew_scan(int64_t n, int* __restrict__ uoff)
+{
+    __shared__ int s_sum[kPreBlock];
+    const int tid = threadIdx.x;
+    const int64_t per = (n + kPreBlock - 1) / kPreBlock;
+    const int64_t b = min(n, tid * per), e = min(n, b + per);
+    int sum = 0;
+    for (int64_t i = b; i < e; ++i) sum += uoff[i];
+    s_sum[tid] = sum;
+    __syncthreads();
+    for (int off = 1; off < kPreBlock; off <<= 1) {
+        const int below = tid >= off ? s_sum[tid - off] : 0;
+        __syncthreads();
+        s_sum[tid] += below;
+        __syncthreads();
+    }
+    int run = s_sum[tid] - sum;
+    for (int64_t i = b; i < e; ++i) {
+        const int cnt = uoff[i];
+        uoff[i] = run;
+        run += cnt;
+    }
+    if (tid == kPreBlock - 1) uoff[n] = s_sum[tid];
+}
+
+__global__ __launch_bounds__(kRtBlock) void k_ew_walk(EwArgs a, EwWork w, int G, int gpw)
+{
+    extern __shared__ double smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = lane / G, g = lane - grp * G;
+    const bool active = grp < gpw;
+    const int n_depth = a.n_depth, n_gap = n_depth - 1, col = n_depth, n_theta = a.n_theta;
+    const EwColumns L(G, n_depth, gpw);  // (sdx_rt_layout.h: the host sizes the launch by the same struct)
+    int2* cW = (int2*)(smem + L.window());
+    double* cInv = smem + L.inv();
+    double* cY = smem + L.y();
+    double* cAmp = smem + L.amp();
+    double* cYk = smem + L.region1();
+    double* cCv = cYk + col;
+    double* cCd = cCv + col;
+    double* sT = smem + L.terms();
+    double* sR = smem + L.ratios();
+    double* wbase = smem + L.shared_doubles() + (size_t)wave * L.wave_doubles();
+    double2* sP = (double2*)(wbase + L.pairs());  // (source function, sqrt(alpha total)) [gpw][col]
+    double* sC = wbase + L.back();                // sqrt(alpha background)             [gpw][col]
+    double* sX = wbase + L.flux();                // emergent flux terms, total         [gpw][G]
+    double* sXc = wbase + L.flux_back();          // emergent flux terms, background    [gpw][G]
+    const int64_t n_items = a.n_sel * a.n_scale;
+    const int n_units = w.uoff[n_items];
+    const RtConst kc = rt_const_literals();  // (literals, as in k_raytrace)
+    const int th = min(g, n_theta - 1);
+    const double wt = g < n_theta ? a.wts[th] : 0.0;
+    const int gi = (active ? grp : 0) * col;
+    const int half = (n_theta + 1) >> 1;
+
+    for (int u = blockIdx.x; u < n_units; u += gridDim.x) {
+        int64_t item = 0;
+        {  // the last item whose first unit is not behind u (items without units share the offset of the next one with units)
+            int64_t hi = n_items;
+            while (hi - item > 1) {
+                const int64_t mid = (item + hi) >> 1;
+                if (w.uoff[mid] <= u) item = mid; else hi = mid;
+            }
+        }
+        const int seg = u - w.uoff[item];
+        const int64_t l = ew_line(a, item / a.n_scale);
+        const double s = a.scale ? a.scale[item] : 1.0;
+        const int64_t ulo = w.ulo[item], uhi = w.uhi[item];
+        const int64_t ue = min(uhi, a.nu_begin + a.nu_count);
+        const int64_t sb = max(ulo, a.nu_begin) + (int64_t)seg * kEwSegment;
+        const int len = (int)min((int64_t)kEwSegment, ue - sb);
+        const double lnu = a.line_nus[l];
+
+        __syncthreads();  // the unit before: its constants and slots are read no more
+        for (int d = tid; d < n_depth; d += kRtBlock) {
+            const double dw = a.doppler[l * n_depth + d], gm = a.gammas[l * a.gamma_cols + (a.gamma_cols == 1 ? 0 : d)];
+            const double al = mul_rn(a.alphas[l * n_depth + d], s);
+            int lo, hi;
+            window_rule(w.centre[l], a.n_nu, w.pd[0], w.pd[1], gm, dw, al, lo, hi);
+            double inv, y, amp;
+            narrow_params(dw, gm, al, inv, y, amp);
+            const RegionI k1 = region1_setup(y, amp);
+            cW[d] = int2{lo, hi};
+            cInv[d] = inv, cY[d] = y, cAmp[d] = amp, cYk[d] = k1.yk, cCv[d] = k1.cv, cCd[d] = k1.cd;
+        }
+        __syncthreads();
+
+        for (int p0 = wave * gpw; p0 < len; p0 += kRtWaves * gpw) {
+            const int64_t i = sb + min(p0 + grp, len - 1);  // (lanes behind the segment's end repeat its last point and are not read)
+            const double nu = a.nus[i];
+            if (active) {
+                const int ii = (int)i;
+                const double delta = nu - lnu;
+                for (int d = g; d < n_depth; d += G) {
+                    const double ab = a.background[(size_t)d * a.bld + (i - a.nu_begin)];
+                    const int2 win = cW[d];
+                    double term = 0.0;
+                    if (ii >= win.x && ii < win.y) term = voigt_term(delta, cInv[d], cY[d], cAmp[d], RegionI{cYk[d], cCv[d], cCd[d]});
+                    sP[grp * col + d] = double2{planck_staged(nu, a.temps[d]), sqrt(add_rn(ab, term))};
+                    sC[grp * col + d] = sqrt(ab);
+                }
+            }
+            wave_sync();
+
+            // the outward walk of k_raytrace_cont: two chains on the same ray lengths and source values
+            double inten = 0.0, intc = 0.0;
+            const double2 q0 = sP[gi], q1 = sP[gi + 1];
+            double a1 = q1.y, ac1 = sC[gi + 1];
+            const double* rdp = a.ray_dist + th;
+            double tau0 = mul_rn(q0.y * a1, *rdp), tauc0 = mul_rn(sC[gi] * ac1, *rdp);
+            rdp += n_gap > 1 ? n_theta : 0;
+            double rd_next = *rdp;
+            double s1 = q1.x, d10 = q0.x - s1;
+            for (int gap = 0; gap < n_gap - 1; ++gap) {
+                const double2 q2 = sP[gi + gap + 2];
+                const double s2 = q2.x, a2 = q2.y, ac2 = sC[gi + gap + 2];
+                const double mean1 = a1 * a2, meanc1 = ac1 * ac2, d21 = s2 - s1;
+                const double rd = rd_next;
+                const double t1 = mul_rn(mean1, rd), tc1 = mul_rn(meanc1, rd);
+                rdp += gap + 2 < n_gap ? n_theta : 0;
+                rd_next = *rdp;
+                double c, e, cc, ec;
+                rt_coef<false>(tau0, t1, d10, d21, s1, c, e, kc);
+                rt_coef<false>(tauc0, tc1, d10, d21, s1, cc, ec, kc);
+                inten = fma(c, inten, e), intc = fma(cc, intc, ec);
+                tau0 = t1, tauc0 = tc1;
+                d10 = -d21, s1 = s2, a1 = a2, ac1 = ac2;
+            }
+            {
+                double c, e, cc, ec;
+                rt_coef<true>(tau0, 0.0, d10, 0.0, s1, c, e, kc);
+                rt_coef<true>(tauc0, 0.0, d10, 0.0, s1, cc, ec, kc);
+                inten = fma(c, inten, e), intc = fma(cc, intc, ec);
+            }
+            if (active) sX[grp * G + g] = inten * wt, sXc[grp * G + g] = intc * wt;
+            wave_sync();
+            if (lane < gpw && p0 + lane < len) {
+                const double* c = sX + lane * G;
+                const double* cc = sXc + lane * G;
+                double f0 = 0.0, f1 = 0.0, b0 = 0.0, b1 = 0.0;
+                for (int t = 0; t < half; ++t) f0 = add_rn(f0, c[t]), b0 = add_rn(b0, cc[t]);
+                for (int t = half; t < n_theta; ++t) f1 = add_rn(f1, c[t]), b1 = add_rn(b1, cc[t]);
+                const double F = add_rn(f0, f1), Fb = add_rn(b0, b1);
+                const double r = (Fb - F) / Fb;
+                const int64_t ip = sb + p0 + lane;
+                const double xi = a.x[ip];
+                const double right = ip + 1 < uhi ? fabs(a.x[ip + 1] - xi) : 0.0, left = ip - 1 >= ulo ? fabs(xi - a.x[ip - 1]) : 0.0;
+                const double h = mul_rn(0.5, add_rn(right, left));
+                sT[p0 + lane] = mul_rn(h, r);
+                sR[p0 + lane] = r;
+            }
+            wave_sync();
+        }
+        __syncthreads();
+        if (wave == 0) {
+            double sum = 0.0, top = -__builtin_huge_val();
+#pragma unroll
+            for (int q = 0; q < kEwSegment / 64; ++q) {
+                const int p = lane + 64 * q;
+                if (p < len) sum = add_rn(sum, sT[p]), top = fmax(top, sR[p]);
+            }
+            for (int off = 32; off > 0; off >>= 1) sum = add_rn(sum, __shfl_xor(sum, off)), top = fmax(top, __shfl_xor(top, off));
+            if (lane == 0) w.partial[u] = double2{sum, top};
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_ew_gather(int64_t n_items, EwWork w, double* __restrict__ out_W, double* __restrict__ out_depth)
+{
+    const int64_t item = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (item >= n_items) return;
+    const int b = w.uoff[item], e = w.uoff[item + 1];
+    double sum = 0.0, top = 0.0;
+    for (int u = b; u < e; ++u) {
+        const double2 p = w.partial[u];
+        sum = add_rn(sum, p.x);
+        top = u == b ? p.y : fmax(top, p.y);
+    }
+    if (out_W) out_W[item] = sum;
+    if (out_depth) out_depth[item] = top;
+}
+
 }  // namespace sdx

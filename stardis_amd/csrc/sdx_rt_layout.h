@@ -36,6 +36,32 @@ struct RtContColumns {
     __host__ __device__ constexpr size_t bytes() const { return (size_t)kRtWaves * wave_doubles() * sizeof(double); }
 };
 
+// k_ew_walk (isolated-line equivalent widths): a workgroup walks one segment of kEwSegment window points of one (line, strength) item.
+// Shared by the block, one array [col] each (a lane staging depth d reads entry d of each: consecutive lanes, consecutive 8 bytes):
+// the depth's window [lo, hi) as two ints in one slot, 1 / doppler width, y, the amplitude, the three region-I constants; then the
+// segment's terms h r and ratios r [kEwSegment] each.  Then per wave RtContColumns' columns — the (source function, sqrt(alpha total))
+// pairs [gpw][col] as double2, sqrt(alpha background) [gpw][col] — and ONE set of flux terms per chain [gpw][G]: only the emergent flux
+// is summed.  Every region that holds double2 starts at an even double.
+constexpr int kEwSegment = 256;  // window points per work unit of k_ew_walk
+struct EwColumns {
+    int gpw, col, G;
+    __host__ __device__ constexpr EwColumns(int G_, int n_depth, int gpw_) : gpw(gpw_), col(n_depth), G(G_) {}
+    __host__ __device__ constexpr int window() const { return 0; }
+    __host__ __device__ constexpr int inv() const { return col; }
+    __host__ __device__ constexpr int y() const { return 2 * col; }
+    __host__ __device__ constexpr int amp() const { return 3 * col; }
+    __host__ __device__ constexpr int region1() const { return 4 * col; }  // yk, cv, cd: [3][col]
+    __host__ __device__ constexpr int terms() const { return (7 * col + 1) & ~1; }
+    __host__ __device__ constexpr int ratios() const { return terms() + kEwSegment; }
+    __host__ __device__ constexpr int shared_doubles() const { return ratios() + kEwSegment; }
+    __host__ __device__ constexpr int pairs() const { return 0; }  // (this and the next three: from the wave's base)
+    __host__ __device__ constexpr int back() const { return 2 * gpw * col; }
+    __host__ __device__ constexpr int flux() const { return back() + gpw * col; }
+    __host__ __device__ constexpr int flux_back() const { return flux() + gpw * G; }
+    __host__ __device__ constexpr int wave_doubles() const { return (flux_back() + gpw * G + 1) & ~1; }
+    __host__ __device__ constexpr size_t bytes() const { return ((size_t)shared_doubles() + (size_t)kRtWaves * wave_doubles()) * sizeof(double); }
+};
+
 // k_raytrace_f32 (floats).  Shared by the block: the ray table [n_gap][n_theta], 1 / (k T) [col] and the relative temperature
 // differences [col], rounded up to whole float4s; then per wave the float4 of every point [gpw][col] and the flux terms [batch][gpw][G].
 constexpr int kRt32Batch = 8;  // gaps per flux reduction of k_raytrace_f32 (6 measured: no gain from the eighth block a CU's LDS then holds)
@@ -151,6 +177,17 @@ constexpr bool response_ok(int G, int n_depth, int gpw)
            r.terms_alpha() + kRtBatch * r.slots() <= r.terms_source() && r.terms_source() + kRtBatch * r.slots() <= r.wave_doubles() &&
            even(r.pairs()) && even(r.wave_doubles());
 }
+constexpr bool ew_ok(int G, int n_depth, int gpw)
+{
+    const EwColumns c(G, n_depth, gpw);
+    return gpw * G <= 64 && c.region1() + 3 * n_depth <= c.terms() && c.terms() + kEwSegment <= c.ratios() && even(c.shared_doubles()) &&
+           c.pairs() + 2 * gpw * n_depth <= c.back() && c.back() + gpw * n_depth <= c.flux() && c.flux() + gpw * G <= c.flux_back() &&
+           c.flux_back() + gpw * G <= c.wave_doubles() && even(c.pairs()) && even(c.wave_doubles());
+}
+// the benchmark's shape fits at three points per wave; odd depth counts, both ends of the angle range; 20 angles keep three points per
+// wave up to 167 depth points
+static_assert(ew_ok(20, 56, 3) && ew_ok(1, 3, 64) && ew_ok(7, 57, 9) && ew_ok(64, 2, 1) && ew_ok(20, 167, 3) && ew_ok(20, 168, 2), "EwColumns");
+static_assert(EwColumns(20, 167, 3).bytes() <= kLdsBytes && EwColumns(20, 168, 3).bytes() > kLdsBytes && EwColumns(20, 168, 2).bytes() <= kLdsBytes, "EwColumns");
 // 3, 7 and 20 angles (odd row counts), deep models with gpw lowered, 64 angles at the shallowest model
 static_assert(columns_ok(3, 56, 21) && columns_ok(7, 301, 3) && columns_ok(20, 302, 2) && columns_ok(5, 984, 1), "RtColumns / RtContColumns");
 static_assert(columns_ok(20, 175, 2) && columns_ok(64, 2, 1), "RtColumns / RtContColumns");

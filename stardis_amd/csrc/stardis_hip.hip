@@ -2691,6 +2691,64 @@ int sdx_line_param_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, const do
     return io.finish();
 }
 
+// ---- isolated-line equivalent widths (k_line_ew) -----------------------------------------------------------------------------------
+// The adjoints' checks (line_entry_check) and its own, all before anything is enqueued.  Five launches under the stage name k_line_ew: the
+// grid spacing and the centres (k_line_adjoint_setup), the unions and unit counts, their prefix sums, the walk, the gather.  The scratch
+// is the adjoints' (adj_scratch: their head, then the unions, the unit offsets and one (W, depth) pair per unit).  The number of units
+// is known on the device only; the host bounds it from the shapes — no item has more segments than the shard — sizes `partial` by the
+// bound and lets the walk's blocks stride the units, so nothing is read back and the entry can be captured once its scratch exists.
+int sdx_line_equivalent_widths_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* nus, int64_t nu_begin, int64_t nu_count, const double* x,
+                                   int64_t n_lines, const double* line_nus, const double* doppler, const double* gammas, int gamma_cols,
+                                   const double* alphas, int64_t n_sel, const int64_t* line_index, int n_scale, const double* scale,
+                                   const double* background, int64_t background_ld, int n_theta, const double* temps, const double* ray_dist,
+                                   const double* wts, double* out_W, double* out_depth)
+{
+    // the model's own limits first (whatever the tables look like), then what the line adjoints check
+    REQUIRE(ctx, "line_equivalent_widths: null context");
+    REQUIRE(n_depth >= 2, "line_equivalent_widths: need n_depth >= 2 (the formal solution has no gap to walk)");
+    REQUIRE(n_theta > 0 && n_theta <= 64, "line_equivalent_widths: need 1 <= n_theta <= 64 (all angles are traced in one launch)");
+    const int G = n_theta;
+    const int gpw = rt_fit_gpw<EwColumns>(G, n_depth);
+    REQUIRE(gpw > 0, "line_equivalent_widths: no equivalent widths for models this deep (the columns do not fit LDS at one frequency per wave)");
+    int rc = line_entry_check("line_equivalent_widths", "equivalent widths", "line's term", ctx, n_depth, n_nu, n_lines, gamma_cols, nu_begin, nu_count);
+    if (rc) return rc;
+    REQUIRE(n_sel >= 0 && n_scale >= 1, "line_equivalent_widths: need n_sel >= 0 and n_scale >= 1");
+    REQUIRE(line_index || n_sel == n_lines, "line_equivalent_widths: without line_index every line is selected, n_sel = n_lines");
+    REQUIRE(out_W || out_depth, "line_equivalent_widths: no output requested");
+    if (n_sel == 0 || nu_count == 0) return SDX_OK;
+    REQUIRE(n_lines > 0, "line_equivalent_widths: lines selected from an empty list");
+    REQUIRE(nus && x && line_nus && doppler && gammas && alphas && background && background_ld >= nu_count && temps && ray_dist && wts,
+            "line_equivalent_widths: null pointer or background_ld below nu_count");
+    const int64_t n_items = n_sel * (int64_t)n_scale;
+    const int64_t seg_max = (nu_count + kEwSegment - 1) / kEwSegment;
+    REQUIRE(n_items < ((int64_t)1 << 26) / seg_max, "line_equivalent_widths: n_sel * n_scale * nu_count too large for one call (select fewer lines)");
+    const int64_t unit_max = n_items * seg_max;
+    HIP_TRY(hipSetDevice(ctx->device));
+    AdjWork head{};
+    char* p;
+    const size_t b_int = HostPlan::pad(4 * (size_t)(n_items + 1));
+    if ((rc = adj_scratch(ctx, n_depth, n_lines, 3 * b_int + HostPlan::pad(16 * (size_t)unit_max), head, &p))) return rc;
+    EwWork w{};
+    w.pd = head.pd, w.centre = head.centre;
+    w.ulo = (int*)p, p += b_int;
+    w.uhi = (int*)p, p += b_int;
+    w.uoff = (int*)p, p += b_int;
+    w.partial = (double2*)p;
+    const AdjLines lines{n_depth, gamma_cols, n_nu, nu_begin, nu_count, n_lines, nus, line_nus, doppler, gammas, alphas};
+    const EwArgs a{n_depth, gamma_cols, n_scale, n_theta, n_nu, nu_begin, nu_count, n_lines, n_sel, nus, x, line_nus, doppler, gammas, alphas,
+                   line_index, scale, background, background_ld, temps, ray_dist, wts};
+    const unsigned walk_blocks = (unsigned)std::min<int64_t>(unit_max, (int64_t)ctx->n_cu * 16);
+    {
+        LaunchScope ls(ctx, "k_line_ew");
+        launch_adjoint_setup(ctx, lines, head);
+        hipLaunchKernelGGL(k_ew_plan, dim3(blocks1(n_items)), dim3(kBlock), 0, ctx->stream, a, w);
+        hipLaunchKernelGGL(k_ew_scan, dim3(1), dim3(kPreBlock), 0, ctx->stream, n_items, w.uoff);
+        hipLaunchKernelGGL(k_ew_walk, dim3(walk_blocks), dim3(kRtBlock), EwColumns(G, n_depth, gpw).bytes(), ctx->stream, a, w, G, gpw);
+        hipLaunchKernelGGL(k_ew_gather, dim3(blocks1(n_items)), dim3(kBlock), 0, ctx->stream, n_items, w, out_W, out_depth);
+    }
+    return check_launch("k_line_ew");
+}
+
 // ---- the tangent of the line-opacity sum (k_line_tangent) ---------------------------------------------------------------------
 // The adjoints' checks (line_entry_check) and its own.  Five launches under the stage name k_line_tangent: the grid spacing and the centres
 // (k_line_adjoint_setup), the windows, the prefix of the wide items per depth, their lists, the plane.  The scratch is the adjoints'

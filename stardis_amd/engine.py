@@ -133,6 +133,8 @@ class SpectralSynthesizer:
 
         self._keep = []
         self.cont = self._build_continuum(continuum, nus, t)
+        self._has_continuum = continuum is not None
+        self._ew = None  # equivalent_widths: (abscissa, continuum plane) on the device, allocated at its first call
 
         # optional output planes: allocated only when asked for (0.5 GB each at 1.2e6 frequencies)
         self.keep_contribution = bool(keep_contribution)
@@ -609,6 +611,49 @@ class SpectralSynthesizer:
             c.call("sdx_line_param_adjoint_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, cnt, self.n_lines, ln_ptr, d_dw.ptr,
                    d_g.ptr, self.gamma_cols, d_a.ptr, d_W.ptr, cnt, *(none + ptrs if per_depth else ptrs + none))
         return res[names[0]] if single else {k: res[k] for k in names}
+
+    # -- one line alone over a background: equivalent widths and curves of growth ----------------------------------------------------------
+    def equivalent_widths(self, lines=None, ln_strength=None, background=None):
+        """-> (W, depth), DeviceArrays (n_sel, K): the isolated-line equivalent width in Angstrom and the line depth of every selected
+        line at every strength factor exp(ln_strength), over `background` — the line alone, not its blend (sdx_line_equivalent_widths_dev;
+        ops.equivalent_widths states the definition).  lines: None (all) or indices into the list in the order the caller passed it
+        (repeats allowed; ValueError for one outside it); ln_strength: None, a scalar, (K,) or (n_sel, K).  background: an opacity plane
+        (N_d, count) of this synthesizer's columns (host array, DeviceArray or CUDA tensor), or None: the continuum plane, formed at
+        every such call by sdx_total_alphas_dev with no line plane into a buffer allocated at the first — that needs continuum=.
+        The synthesizer's own shard and angles: W of frequency shards adds, depth combines by max.  The line tables as
+        line_sensitivities reads them (forget_line_tables()).  On demand: a synthesizer that never asks allocates nothing and launches
+        what it launched; the step's outputs are not touched."""
+        c = self.ctx
+        index, scale = ops.line_selection(self.n_lines, lines, ln_strength)
+        if background is None and not self._has_continuum:
+            raise ValueError("equivalent_widths: background=None means the continuum plane, which needs continuum= at construction")
+        if self._ew is None:
+            self._ew = [c.upload(K.nu_to_angstrom(self.nus_host)), None]
+        d_x = self._ew[0]
+        if background is None:
+            if self._ew[1] is None:
+                self._ew[1] = c.empty((self.n_depth, self.count))
+            d_b = self._ew[1]
+            c.call("sdx_total_alphas_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, C.byref(self.cont), None, 0, d_b.ptr,
+                   self.count)
+        else:
+            d_b = self._device_vector("background", background, (self.n_depth, self.count))
+        ln_ptr, d_dw, d_g, d_a = self._tables_in_caller_order()
+        n_sel, k = scale.shape
+        d_index = None if index is None else c.upload(index, np.int64)
+        d_scale = c.upload(scale)
+        out_w, out_d = c.empty((n_sel, k)), c.empty((n_sel, k))
+        c.call("sdx_line_equivalent_widths_dev", self.n_depth, self.n_nu, self.d_nus.ptr, self.begin, self.count, d_x.ptr, self.n_lines, ln_ptr,
+               d_dw.ptr, d_g.ptr, self.gamma_cols, d_a.ptr, n_sel, ptr_of(d_index), k, d_scale.ptr, ptr_of(d_b), self.count, self.n_theta,
+               self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, out_w.ptr, out_d.ptr)
+        return out_w, out_d
+
+    def fit_equivalent_widths(self, W_obs, lines=None, **solve_args):
+        """curve_of_growth.solve over equivalent_widths: for every selected line the offset delta log gf (dex) at which its isolated-line
+        equivalent width over the continuum plane equals W_obs (n_sel,) in Angstrom -> curve_of_growth.Solution."""
+        from . import curve_of_growth
+
+        return curve_of_growth.solve(lambda ln_s: self.equivalent_widths(lines=lines, ln_strength=ln_s)[0].numpy(), W_obs, **solve_args)
 
     # -- forward mode through the lines: one direction over the lines, every column ----------------------------------------------------
     def line_tangent(self, strength=None, damping=None, doppler=None, centre=None):

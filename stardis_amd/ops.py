@@ -181,6 +181,68 @@ def _adjoint_inputs(ctx, no_of_depth_points, tracing_nus_values, line_nus, doppl
     return ctx, head, d + [d_w], ((ln.size, nd) if per_depth else (ln.size,))
 
 
+def line_selection(n_lines, lines=None, ln_strength=None):
+    """The selection of equivalent_widths as host arrays -> (line_index int64 (n_sel,) or None for every line, scale (n_sel, K)):
+    lines None (all) or indices into the caller's list, repeats allowed, ValueError for one outside [0, n_lines); ln_strength None
+    (no change), a scalar, (K,) or (n_sel, K): the natural logarithm of the factor on the line's strength, exponentiated here."""
+    n_lines = int(n_lines)
+    index = None
+    if lines is not None:
+        index = np.ascontiguousarray(np.asarray(lines).reshape(-1), dtype=np.int64)
+        if index.size and (index.min() < 0 or index.max() >= n_lines):
+            raise ValueError(f"lines must index the list of {n_lines} lines, got an index outside [0, {n_lines})")
+    n_sel = n_lines if index is None else index.size
+    ln_s = np.zeros((1,)) if ln_strength is None else _host(ln_strength)
+    if ln_s.ndim == 0:
+        ln_s = ln_s.reshape(1)
+    if ln_s.ndim == 1:
+        ln_s = np.broadcast_to(ln_s[None, :], (n_sel, ln_s.size))
+    if ln_s.ndim != 2 or ln_s.shape[0] != n_sel or ln_s.shape[1] < 1:
+        raise ValueError(f"ln_strength must be a scalar, (K,) or ({n_sel}, K) with K >= 1, got shape {ln_s.shape}")
+    return index, np.ascontiguousarray(np.exp(ln_s))
+
+
+def equivalent_widths(no_of_depth_points, nus, line_nus, doppler_widths, gammas, alphas, background, temperatures, ray_distances,
+                      theta_weights, x=None, lines=None, ln_strength=None, shard=None, ctx=None, device=False):
+    """Isolated-line equivalent widths and line depths (sdx_line_equivalent_widths_dev; the definition stands in include/stardis_hip.h)
+    -> (W, depth), each (n_sel, K): for every selected line and strength factor exp(ln_strength), the trapezoid integral over the
+    points the line reaches of r = (F_B - F) / F_B and the largest r — F the emergent flux of the plane-parallel formal solution of
+    background + this line alone, F_B that of the background.  Row j belongs to lines[j] of the caller's list, whatever its order.
+    background (N_d, count): host array, DeviceArray or CUDA tensor; ray_distances (N_d - 1, N_theta) as raytrace forms them
+    (dist / cos(theta)); x: the abscissa of the integral on the whole grid, None: lambda in Angstrom (W in Angstrom).  lines: None
+    (all) or indices, checked here before anything is uploaded; ln_strength: None, a scalar, (K,) or (n_sel, K).  shard = (begin,
+    count): only these columns of the global grid — W of the shards adds, depth combines by max.  device=True: DeviceArrays."""
+    nus = _host(nus).reshape(-1)
+    ln, dw, g, al = _line_inputs(no_of_depth_points, line_nus, doppler_widths, gammas, alphas, sort=False)
+    nd = int(no_of_depth_points)
+    begin, count = (0, nus.size) if shard is None else (int(v) for v in shard)
+    if begin < 0 or count < 0 or begin + count > nus.size:
+        raise ValueError(f"shard {(begin, count)} lies outside the grid of {nus.size} frequencies")
+    shape = tuple(int(v) for v in (background.shape if hasattr(background, "shape") else np.shape(background)))
+    if shape != (nd, count):
+        raise ValueError(f"background must have shape {(nd, count)}, got {shape}")
+    index, scale = line_selection(ln.size, lines, ln_strength)
+    t = _host(temperatures).reshape(-1)
+    w = _host(theta_weights).reshape(-1)
+    ray = _host(ray_distances)
+    if t.size != nd or ray.shape != (nd - 1, w.size):
+        raise ValueError(f"temperatures must hold {nd} values and ray_distances have shape {(nd - 1, w.size)}, got {t.size} and {ray.shape}")
+    from . import constants as K
+
+    xs = K.nu_to_angstrom(nus) if x is None else _host(x).reshape(-1)
+    if xs.size != nus.size:
+        raise ValueError(f"x must hold one value per frequency ({nus.size}), got {xs.size}")
+    ctx = ctx or default_context()
+    d_b = _dev(ctx, background)
+    d = [ctx.upload(v) for v in (nus, xs, ln, dw, g, al, scale, t, ray, w)]
+    d_index = None if index is None else ctx.upload(index, np.int64)
+    n_sel, k = scale.shape
+    out_w, out_d = ctx.empty((n_sel, k)), ctx.empty((n_sel, k))
+    ctx.call("sdx_line_equivalent_widths_dev", nd, nus.size, d[0].ptr, begin, count, d[1].ptr, ln.size, d[2].ptr, d[3].ptr, d[4].ptr, g.shape[1],
+             d[5].ptr, n_sel, ptr_of(d_index), k, d[6].ptr, ptr_of(d_b), count, w.size, d[7].ptr, d[8].ptr, d[9].ptr, out_w.ptr, out_d.ptr)
+    return (out_w, out_d) if device else (out_w.numpy(), out_d.numpy())
+
+
 LINE_PARAMS = ("damping", "doppler", "centre")
 
 
