@@ -423,6 +423,72 @@ int sdx_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const
 int sdx_response_project_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* R_alpha, int64_t R_ld, const double* part,
                              int64_t part_ld, const double* total, int64_t total_ld, double* out);
 
+/* ---- continuum scattering: mean intensity and the scattering source function -----------------------
+ * Every formal solution above takes the LTE source function S = B and treats Thomson and Rayleigh opacity — part of total_alphas,
+ * ((((file + bf) + ff) + rayleigh) + electron) + line — as true absorption, as the reference does.  These two entry points produce
+ * what the source-plane arguments of sdx_raytrace_source_dev, sdx_contribution_dev and sdx_response_dev consume instead: the mean
+ * intensity J of the project's own formal solution at every depth point, over both hemispheres, and the solution of
+ *     S = (1 - albedo) B + albedo J[S],   albedo = alpha_scatter / alpha_total
+ * for coherent, isotropic scattering (every frequency its own linear problem).  The reference has no counterpart.
+ * Plane-parallel, fp64, n_theta <= 64.  Per frequency and angle k the optical depth of gap g is the kernels' own,
+ * tau_k[g] = (sqrt(alpha[g]) sqrt(alpha[g+1])) ray_dist[g][k].  For a source column S of N_d values (row 0 deepest):
+ *   upward sweep    exactly the outward recurrence of the flux kernels: U_k[g+1] = c U_k[g] + e with (c, e) of the inner gaps from
+ *                   (tau[g], tau[g+1], S[g] - S[g+1], S[g+2] - S[g+1], S[g+1]) and of the last gap from its own form (:253-266), the
+ *                   tau == 0 -> (1, 0) rule and the rare-lane fallback included — but started from U_k[0] = S[0], a THERMALISED lower
+ *                   boundary (the reference's I[0] = 0, which stays what the flux kernels use, would halve J at the bottom);
+ *   downward sweep  the same recurrence on the depth-reversed column, started from D_k[N_d-1] = 0: arrival at point g >= 1 takes the
+ *                   inner form with (tau[g], tau[g-1], S[g+1] - S[g], S[g-1] - S[g], S[g]), arrival at point 0 the last-gap form with
+ *                   (tau[0], 0, S[1] - S[0], 0, S[0]); no negative-index wrap as in the spherical inward sweep;
+ *   mean intensity  J[d] = (sum_k m_k U_k[d]) + (sum_k m_k D_k[d]), each sum over k as the flux is summed (two ascending halves, the
+ *                   lower added to the upper); the downward sum of row N_d-1 is a sum of zeros;
+ *   diagonal        L[d] = (sum_k m_k qU_k[d]) + (sum_k m_k qD_k[d]), q the coefficient of the arrival point's source value in the
+ *                   step's e (q of sdx_response_dev above; 0 for a gap with tau == 0), qU_k[0] = 1, qD_k[N_d-1] = 0.  It depends on
+ *                   the optical depths alone;
+ *   mean weights    m [n_theta] is an argument, with sum_k 2 m_k = 1 so that an isotropic field gives J = I (otherwise the iteration
+ *                   creates or destroys photons).  For Gauss-Legendre nodes in theta with the field's weights w:
+ *                   m_k = w_k sin(theta_k) / (2 sum_j w_j sin(theta_j)).
+ * sdx_mean_intensity_dev is one application: J and / or lambda_diag [n_depth][ld] (either may be NULL, not both) of the source plane
+ * (NULL: Planck, as the flux kernels stage it).
+ * sdx_scatter_source_dev iterates.  albedo[d] = alpha_scatter[d] / total_alphas[d] clamped to [0, 1] (NaN -> 0), 0 where
+ * total_alphas == 0; alpha_scatter [n_depth][scatter_ld], or with scatter_ld == 0 one value per depth point [n_depth] (Thomson).
+ * The thermal term is (1 - albedo) B, B the plane `thermal` or (NULL) Planck.  Jacobi iteration with a local operator:
+ *     S^0 = B,   S^(n+1) = S^n + ((1 - albedo) B + albedo J[S^n] - S^n) / (1 - albedo Lc),   Lc = clamp(L, 0, 1) (NaN -> 0)
+ * (the clamp changes the rate, never the fixed point; L is formed once).  Every point of a column is updated from the J of the
+ * finished sweeps: no point sees a neighbour's new value within an iteration.  A column stops
+ *   status 0   when max_d |S^(n+1)[d] - S^n[d]| <= tol max_d |S^(n+1)[d]|;
+ *   status 1   after max_iter iterations;
+ *   status 2   when the change is not finite; the update is then not applied — S is the last finite iterate — and `change` is +inf.
+ * `iterations` counts the updates evaluated (the refused one of status 2 included), `change` is the last max_d |S^(n+1) - S^n|.
+ * A column that has stopped is never written again while the others of its launch finish: its bits do not depend on the grid, the
+ * shard or the other columns.  max_iter bounds the kernel's loop.  J, when asked for, is the mean intensity OF THE RETURNED S (one more
+ * application).  No atomics anywhere: the same bits from run to run.
+ * The step is second order and NOT a positive operator.  On grids as fine as stellar model atmospheres (57 points over 7 decades of
+ * tau) L lies in (0, 1) and the iteration converges (albedo 0.5 / 0.9 / 0.99 / 0.999: 23 / 77 / 242 / 516 iterations at tol = 1e-12);
+ * on coarse grids L leaves [0, 1] (seen: -0.59 and 1.71 at 3 points over 7 decades), and for albedo >= 0.9 the discrete problem
+ * itself has no positive solution: the iteration diverges, which is what status 1 and 2 report.  DESIGN.md, "Scattering in the source function".
+ * Refused with SDX_ERR_ARG before anything is enqueued (also for n_nu = 0): mixed_precision = 1, n_theta > 64, tol < 0 or NaN,
+ * max_iter < 1, a model whose columns — (6 n_depth + 4 n_theta) doubles at one frequency per wave — do not fit 64 KB of LDS (1352
+ * depth points at 20 angles).  Out of scope: spherical geometry, line scattering, derivatives of the scattering solution. */
+int sdx_mean_intensity_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                           const double* temperature, const double* ray_dist, const double* mean_weights,
+                           const double* total_alphas, int64_t alpha_ld, const double* source, int64_t source_ld,
+                           double* J, int64_t J_ld, double* lambda_diag, int64_t L_ld);
+int sdx_scatter_source_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                           const double* temperature, const double* ray_dist, const double* mean_weights,
+                           const double* total_alphas, int64_t alpha_ld, const double* alpha_scatter, int64_t scatter_ld,
+                           const double* thermal, int64_t thermal_ld, double tol, int max_iter, double* S, int64_t S_ld,
+                           double* J, int64_t J_ld, int* iterations, int* status, double* change);
+/* host-buffer twins: contiguous arrays, planes [n_depth][n_nu]; source / thermal = NULL: Planck; outputs that may be NULL as above.
+ * scatter_per_frequency != 0: alpha_scatter [n_depth][n_nu], else [n_depth]. */
+int sdx_mean_intensity_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                           const double* temperature, const double* ray_dist, const double* mean_weights,
+                           const double* total_alphas, const double* source, double* J, double* lambda_diag);
+int sdx_scatter_source_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                           const double* temperature, const double* ray_dist, const double* mean_weights,
+                           const double* total_alphas, const double* alpha_scatter, int scatter_per_frequency,
+                           const double* thermal, double tol, int max_iter, double* S, double* J, int* iterations,
+                           int* status, double* change);
+
 /* ---- per-line flux sensitivities: the adjoint of the line-opacity sum -----------------------------
  * WHICH lines matter: the line opacity scatters, for every line l and depth point d,
  *     alpha_line[d][i] += alpha_ld voigt(nu_i - nu_l; doppler_ld, gamma_ld)     for i in the reference's window [lo_ld, hi_ld)

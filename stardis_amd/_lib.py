@@ -179,6 +179,11 @@ PROTOTYPES = {
     "sdx_response_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
     "sdx_response_f64": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sdx_response_project_dev": (_int, [_vp, _int, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "sdx_mean_intensity_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
+    "sdx_scatter_source_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, C.c_double, _int, _vp, _i64, _vp, _i64,
+                                      _vp, _vp, _vp]),
+    "sdx_mean_intensity_f64": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_scatter_source_f64": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, C.c_double, _int, _vp, _vp, _vp, _vp, _vp]),
     "sdx_line_adjoint_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp]),
     "sdx_line_adjoint_f64": (_int, [_vp, _int, _i64, _vp, _i64, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
     "sdx_voigt_grad_dev": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -4574,6 +4574,222 @@ __global__ __launch_bounds__(kRespBlock) void k_response(int n_depth, int64_t n_
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Mean intensity of the formal solution and the scattering source function S = (1 - albedo) B + albedo J[S] (include/stardis_hip.h,
+// sdx_mean_intensity_dev and sdx_scatter_source_dev, state the definition).  Coherent scattering leaves the frequencies independent:
+// a column's whole iteration — the iterate, its thermal term, albedo, accelerating diagonal and mean intensity — lives in its wave's
+// LDS (RtLambda) and no wave ever waits for another.
+// The layout is k_contribution's and k_response's: lane <-> (frequency, angle), (S, sqrt(alpha)) pairs staged per wave from a FINISHED
+// total_alphas plane, the terms of kRtBatch rows summed over theta through LDS in the flux's order.  One APPLICATION is two sweeps of
+// the kernels' own step (rt_coef, tau = (sqrt(alpha[g]) sqrt(alpha[g+1])) ray_dist[g]) over the same column, written once: sweep 0 runs
+// from row 0 upwards and starts at S[0], sweep 1 from row N_d - 1 downwards and starts at 0 — behind, arrival and ahead are the points
+// (j, j+1, j+2) of the one and (g+1, g, g-1) of the other, the step that arrives at the sweep's last row is rt_coef<true>.  Each sweep
+// leaves sum_theta m_theta (value at the row) in the wave's column, the second added to the first.  With kDiag the value is not the
+// intensity but the coefficient q of the arrival point's source value in the step's e (rt_coef_derivative), 1 at the first row of the
+// upward sweep: the diagonal of the operator, which depends on the optical depths alone.
+// kIterate: Jacobi with that diagonal as the local operator.  All lanes of a wave sweep together for as long as one of its columns
+// is live (a ballot), but a column that has stopped is never written again, so its bits do not depend on what shares its wave; the
+// update of a column reads only what the two sweeps left, after both have finished.  The trip count is bounded by max_iter.
+struct LambdaIteration {
+    const double* scatter;  // alpha_scatter [n_depth][scatter_ld]; scatter_ld == 0: [n_depth], one value per depth point
+    int64_t scatter_ld;
+    double tol;
+    int max_iter;
+    double* S;  // [n_depth][S_ld]
+    int64_t S_ld;
+    int* iterations;  // per column, each may be NULL
+    int* status;
+    double* change;
+};
+constexpr double kDoubleMax = 0x1.fffffffffffffp+1023;
+template <bool kIterate>
+__global__ __launch_bounds__(kRtBlock) void k_lambda(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
+                                                   const double* __restrict__ nus, const double* __restrict__ temps,
+                                                   const double* __restrict__ ray_dist, const double* __restrict__ mean_wts,
+                                                   const double* __restrict__ alphas, int64_t ald, const double* __restrict__ source,
+                                                   int64_t sld, double* __restrict__ J, int64_t jld, double* __restrict__ Ldiag, int64_t lld,
+                                                   int gpw, int waves, LambdaIteration it)
+{
+    constexpr int kBatch = kRtBatch;
+    extern __shared__ double smem[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int grp = lane / G, g = lane - grp * G;
+    const int64_t i0 = ((int64_t)blockIdx.x * waves + wave) * gpw;  // first frequency of this wave
+    const int64_t i = i0 + grp;
+    const bool active = grp < gpw;
+    const bool valid = active && i < n_nu;
+    const int64_t ic = i < n_nu ? i : n_nu - 1;
+    const int n_gap = n_depth - 1;
+    const int col = n_depth;
+    const RtLambda lay(G, n_depth, gpw);
+    double* wbase = smem + (size_t)wave * lay.wave_doubles();
+    double2* sP = (double2*)(wbase + lay.pairs());  // (source function — the iterate —, sqrt(alpha)) [gpw][col]
+    double* sT = wbase + lay.thermal();             // (1 - albedo) B [gpw][col]
+    double* sW = wbase + lay.albedo();              // albedo [gpw][col]
+    double* sD = wbase + lay.diag();                // L, then 1 / (1 - albedo clamp(L)) [gpw][col]
+    double* sJ = wbase + lay.mean();                // J; between the sweeps and the update, the change of the iterate [gpw][col]
+    double* sX = wbase + lay.terms();               // terms of a batch of rows [kBatch][gpw][G]; the maxima of the stopping rule [2][gpw][G]
+    const double nu = nus[ic];
+    const int cbase = (active ? grp : 0) * col;     // idle lanes shadow group 0 and never store
+
+    if (active) {
+        for (int d = g; d < n_depth; d += G) {
+            const double a = alphas[(size_t)d * ald + ic];
+            const double b = source ? source[(size_t)d * sld + ic] : planck_staged(nu, temps[d]);
+            sP[cbase + d] = double2{b, sqrt(a)};  // S^0 = B
+            if constexpr (kIterate) {
+                double w = a == 0.0 ? 0.0 : it.scatter[it.scatter_ld ? (size_t)d * it.scatter_ld + ic : (size_t)d] / a;
+                w = w > 0.0 ? (w < 1.0 ? w : 1.0) : 0.0;  // clamped to [0, 1]; NaN -> 0
+                sT[cbase + d] = mul_rn(sub_rn(1.0, w), b);
+                sW[cbase + d] = w;
+            }
+        }
+    }
+    wave_sync();
+    const RtConst kc = rt_const_literals();  // (literals, as in k_raytrace: the step loops are rolled)
+    const int th = min(g, n_theta - 1);
+    const double wt = g < n_theta ? mean_wts[th] : 0.0;
+    const double* rd = ray_dist + th;  // rd[gap * theta_stride]
+    const float inv_gpw = 1.0f / (float)gpw;
+    const int half = (n_theta + 1) >> 1;
+
+    // the nb rows first, first + step, ... of a batch: lanes <-> (row, frequency, half of the angles), each half summed in ascending theta
+    // and the lower half added to the upper one (k_raytrace's flux sum) -> dst[frequency][row], written or added to
+    auto reduce = [&](int nb, int first, int step, bool add, double* dst) {
+        for (int p = lane; p < 2 * nb * gpw; p += 64) {
+            const int h = p & 1, q = p >> 1;
+            const int b = (int)(((float)q + 0.5f) * inv_gpw), gq = q - b * gpw;  // q / gpw without an integer division (q < 2^20: exact)
+            const double* t = sX + (b * gpw + gq) * G + (h ? half : 0);
+            const int cnt = h ? n_theta - half : half;
+            double sum = 0.0;
+            for (int j = 0; j < cnt; ++j) sum = add_rn(sum, t[j]);
+            const double other = __shfl_xor(sum, 1);  // 2 nb gpw is even: the partner lane is in the loop too
+            if (h == 0) {
+                double* o = dst + gq * col + first + b * step;
+                const double tot = add_rn(sum, other);
+                *o = add ? add_rn(*o, tot) : tot;
+            }
+        }
+    };
+    // one application of the operator (or, kDiag, its diagonal) to the wave's columns -> dst [gpw][col]
+    auto apply = [&](auto diag_tag, double* dst) {
+        constexpr bool kDiag = decltype(diag_tag)::value;
+        for (int dir = 0; dir < 2; ++dir) {
+            const int sgn = dir ? -1 : 1, start = dir ? n_gap : 0;
+            double2 pa = sP[cbase + start], pb = sP[cbase + start + sgn];  // the points behind and at the arrival of step 0
+            double t0 = mul_rn(pa.y * pb.y, rd[(size_t)(dir ? n_gap - 1 : 0) * theta_stride]);
+            double val = dir ? 0.0 : (kDiag ? 1.0 : pa.x);  // U[0] = S[0]: a thermalised lower boundary; D[N_d-1] = 0
+            if (active) sX[grp * G + g] = val * wt;
+            wave_sync();
+            reduce(1, start, sgn, dir != 0, dst);
+            wave_sync();
+            for (int s0 = 0; s0 < n_gap; s0 += kBatch) {
+                const int nb = min(kBatch, n_gap - s0);
+                for (int b = 0; b < nb; ++b) {
+                    const int s = s0 + b;
+                    const bool last = s == n_gap - 1;
+                    const int pt = start + sgn * (s + 1);                      // the arrival point
+                    const double2 pc = sP[cbase + (last ? pt : pt + sgn)];     // the point ahead
+                    const double t1 = last ? 0.0 : mul_rn(pb.y * pc.y, rd[(size_t)(dir ? pt - 1 : pt) * theta_stride]);
+                    if constexpr (kDiag) {
+                        val = last ? rt_coef_derivative<true>(t0, 0.0, 0.0, 0.0, 0.0).q : rt_coef_derivative<false>(t0, t1, 0.0, 0.0, 0.0).q;
+                    } else {
+                        double c, e;
+                        if (last) rt_coef<true>(t0, 0.0, pa.x - pb.x, 0.0, pb.x, c, e, kc);
+                        else rt_coef<false>(t0, t1, pa.x - pb.x, pc.x - pb.x, pb.x, c, e, kc);
+                        val = fma(c, val, e);
+                    }
+                    if (active) sX[(b * gpw + grp) * G + g] = val * wt;
+                    pa = pb, pb = pc, t0 = t1;
+                }
+                wave_sync();
+                reduce(nb, start + sgn * (s0 + 1), sgn, dir != 0, dst);
+                wave_sync();
+            }
+        }
+    };
+    auto store_column = [&](const double* colv, double* out, int64_t ld) {
+        if (valid)
+            for (int d = g; d < n_depth; d += G) out[(size_t)d * ld + i] = colv[cbase + d];
+    };
+
+    if constexpr (!kIterate) {
+        if (J) {
+            apply(std::false_type{}, sJ);
+            store_column(sJ, J, jld);
+        }
+        if (Ldiag) {
+            apply(std::true_type{}, sD);
+            store_column(sD, Ldiag, lld);
+        }
+    } else {
+        apply(std::true_type{}, sD);
+        if (active) {
+            for (int d = g; d < n_depth; d += G) {
+                const double l = sD[cbase + d];
+                const double lh = l > 0.0 ? (l < 1.0 ? l : 1.0) : 0.0;  // clamp(L, 0, 1): changes the rate, never the fixed point
+                sD[cbase + d] = 1.0 / sub_rn(1.0, mul_rn(sW[cbase + d], lh));
+            }
+        }
+        wave_sync();
+        bool live = valid;
+        int iters = 0, status = 1;
+        double change = 0.0;
+        for (int n = 1;; ++n) {
+            const bool more = n <= it.max_iter && __builtin_amdgcn_ballot_w64(live) != 0;  // wave-uniform
+            if (!more && !J) break;
+            apply(std::false_type{}, sJ);  // J[S^n]; in the trip after the last update, the J of what is returned
+            if (!more) break;
+            double md = 0.0, ms = 0.0;
+            if (active) {
+                for (int d = g; d < n_depth; d += G) {
+                    const double s = sP[cbase + d].x;
+                    const double r = sub_rn(add_rn(sT[cbase + d], mul_rn(sW[cbase + d], sJ[cbase + d])), s);
+                    const double ds = mul_rn(r, sD[cbase + d]);
+                    sJ[cbase + d] = ds;
+                    double ad = fabs(ds);
+                    if (!(ad <= kDoubleMax)) ad = __builtin_huge_val();  // not finite: the column stops (status 2)
+                    const double as = fabs(add_rn(s, ds));
+                    md = ad > md ? ad : md;
+                    ms = as > ms ? as : ms;
+                }
+                sX[grp * G + g] = md;
+                sX[(gpw + grp) * G + g] = ms;
+            }
+            wave_sync();
+            double cd = 0.0, cs = 0.0;  // the column's max |dS| and max |S^(n+1)|: maxima, so the order of the lanes does not matter
+            {
+                const int xb = (active ? grp : 0) * G;
+                for (int t = 0; t < G; ++t) {
+                    const double vd = sX[xb + t], vs = sX[gpw * G + xb + t];
+                    cd = vd > cd ? vd : cd;
+                    cs = vs > cs ? vs : cs;
+                }
+            }
+            wave_sync();
+            if (live) {
+                iters = n, change = cd;
+                if (!(cd <= kDoubleMax)) {
+                    status = 2, live = false;  // S stays at the last finite iterate
+                } else {
+                    for (int d = g; d < n_depth; d += G) sP[cbase + d].x = add_rn(sP[cbase + d].x, sJ[cbase + d]);
+                    if (cd <= mul_rn(it.tol, cs)) status = 0, live = false;
+                }
+            }
+            wave_sync();
+        }
+        if (valid) {
+            for (int d = g; d < n_depth; d += G) it.S[(size_t)d * it.S_ld + i] = sP[cbase + d].x;
+            if (g == 0) {
+                if (it.iterations) it.iterations[i] = iters;
+                if (it.status) it.status[i] = status;
+                if (it.change) it.change[i] = change;
+            }
+        }
+        if (J) store_column(sJ, J, jld);
+    }
+}
+
 // The response to a scale factor on ONE part of the opacity: out[nu] = sum_k R_alpha[k][nu] (part[k][nu] / total[k][nu]), the
 // derivative of the emergent flux with respect to the logarithm of that factor (d ln alpha[k] = part[k] / total[k] d ln factor).  One lane per
 // frequency, ascending k, every operation one correctly rounded fp64 operation; a zero in total gives what IEEE gives.

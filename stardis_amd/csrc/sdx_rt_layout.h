@@ -121,6 +121,25 @@ struct RtResponse {
     __host__ __device__ constexpr size_t bytes() const { return (size_t)kRespWaves * wave_doubles() * sizeof(double); }
 };
 
+// k_lambda<kIterate> (mean intensity, and the scattering source iteration).  Per wave: RtColumns' pairs [gpw][col] as double2 — the
+// source column is the ITERATE, rewritten in place —; then four columns [gpw][col] each: the thermal term (1 - albedo) B, the albedo,
+// the diagonal (the iteration turns it into 1 / (1 - albedo clamp(L))) and the mean intensity J (between the sweeps and the update it
+// holds the change of the iterate); then the terms of a batch of rows [kRtBatch][gpw][G], which also serve the per-column maxima of
+// the stopping rule ([2][gpw][G]).  A column's whole iteration lives in these bytes: the block size follows from them (lambda_waves),
+// bytes() is ONE wave's share.
+struct RtLambda {
+    int gpw, col, G;
+    __host__ __device__ constexpr RtLambda(int G_, int n_depth, int gpw_) : gpw(gpw_), col(n_depth), G(G_) {}
+    __host__ __device__ constexpr int pairs() const { return 0; }
+    __host__ __device__ constexpr int thermal() const { return 2 * gpw * col; }
+    __host__ __device__ constexpr int albedo() const { return thermal() + gpw * col; }
+    __host__ __device__ constexpr int diag() const { return albedo() + gpw * col; }
+    __host__ __device__ constexpr int mean() const { return diag() + gpw * col; }
+    __host__ __device__ constexpr int terms() const { return mean() + gpw * col; }
+    __host__ __device__ constexpr int wave_doubles() const { return (terms() + kRtBatch * gpw * G + 1) & ~1; }
+    __host__ __device__ constexpr size_t bytes() const { return (size_t)wave_doubles() * sizeof(double); }
+};
+
 // ---- the host's choice of a launch shape ----------------------------------------------------------------------------------------
 // A model whose column alone is larger than LDS fits no layout; asked first, it also keeps every int above far from overflow.
 constexpr int kRtMaxDepth = (int)(kLdsBytes / sizeof(double));
@@ -144,6 +163,18 @@ inline unsigned rt_blocks(long long n_nu, int gpw)
 inline unsigned response_blocks(long long n_nu, int gpw)
 {
     return (unsigned)((n_nu + (long long)gpw * kRespWaves - 1) / ((long long)gpw * kRespWaves));
+}
+
+// k_lambda: waves per workgroup — as many of RtLambda's shares as 64 KB hold, at most kRtWaves — and the workgroups that cover n_nu
+// frequencies at gpw frequencies per wave (gpw from rt_fit_gpw<RtLambda>: one wave's share fits by then).
+inline int lambda_waves(int G, int n_depth, int gpw)
+{
+    const size_t fit = kLdsBytes / RtLambda(G, n_depth, gpw).bytes();
+    return fit >= (size_t)kRtWaves ? kRtWaves : (int)fit;
+}
+inline unsigned lambda_blocks(long long n_nu, int gpw, int waves)
+{
+    return (unsigned)((n_nu + (long long)gpw * waves - 1) / ((long long)gpw * waves));
 }
 
 // ---- what the kernels rely on, at a few representative shapes --------------------------------------------------------------------
@@ -184,6 +215,18 @@ constexpr bool ew_ok(int G, int n_depth, int gpw)
            c.pairs() + 2 * gpw * n_depth <= c.back() && c.back() + gpw * n_depth <= c.flux() && c.flux() + gpw * G <= c.flux_back() &&
            c.flux_back() + gpw * G <= c.wave_doubles() && even(c.pairs()) && even(c.wave_doubles());
 }
+constexpr bool lambda_ok(int G, int n_depth, int gpw)
+{
+    const RtLambda l(G, n_depth, gpw);
+    return gpw * G <= 64 && l.pairs() + 2 * gpw * n_depth <= l.thermal() && l.thermal() + gpw * n_depth <= l.albedo() &&
+           l.albedo() + gpw * n_depth <= l.diag() && l.diag() + gpw * n_depth <= l.mean() && l.mean() + gpw * n_depth <= l.terms() &&
+           l.terms() + kRtBatch * gpw * G <= l.wave_doubles() && 2 * gpw * G <= kRtBatch * gpw * G && even(l.pairs()) && even(l.wave_doubles());
+}
+// the benchmark's shape (four waves of it fit a workgroup); odd depth and angle counts, both ends of the angle range; the deepest
+// model at 20 angles and at one
+static_assert(lambda_ok(20, 56, 3) && 4 * RtLambda(20, 56, 3).bytes() <= kLdsBytes, "RtLambda: four waves of 56 depth points at 20 angles must fit");
+static_assert(lambda_ok(1, 2, 64) && lambda_ok(1, 3, 64) && lambda_ok(3, 3, 21) && lambda_ok(7, 9, 9) && lambda_ok(20, 57, 3) && lambda_ok(64, 40, 1), "RtLambda");
+static_assert(RtLambda(20, 1352, 1).bytes() <= kLdsBytes && RtLambda(20, 1353, 1).bytes() > kLdsBytes && RtLambda(1, 1364, 1).bytes() <= kLdsBytes, "RtLambda");
 // the benchmark's shape fits at three points per wave; odd depth counts, both ends of the angle range; 20 angles keep three points per
 // wave up to 167 depth points
 static_assert(ew_ok(20, 56, 3) && ew_ok(1, 3, 64) && ew_ok(7, 57, 9) && ew_ok(64, 2, 1) && ew_ok(20, 167, 3) && ew_ok(20, 168, 2), "EwColumns");

@@ -2495,6 +2495,129 @@ int sdx_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const
     return io.finish();
 }
 
+// ---- mean intensity and the scattering source function (k_lambda) ----------------------------------------------------------
+// As for the response functions, everything is checked before anything is enqueued, also for an empty grid.
+namespace {
+// the refusals both entries share, under the entry's name; -> the launch shape
+int lambda_shape(sdx_ctx* ctx, const char* what, int n_depth, int64_t n_nu, int n_theta, int* gpw, int* waves)
+{
+    auto refuse = [&](const char* why) { return fail(SDX_ERR_ARG, std::string(what) + ": " + why); };
+    if (!(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0)) return refuse("need n_depth >= 2, n_theta > 0");
+    if (ctx->mixed_precision) return refuse("not with mixed_precision = 1 (the mean intensity is that of the fp64 formal solution)");
+    if (n_theta > 64) return refuse("more than 64 angles are not supported (all angles are traced in one launch)");
+    *gpw = rt_fit_gpw<RtLambda>(n_theta, n_depth);
+    if (*gpw <= 0) return refuse("models this deep are not served (the columns of one frequency do not fit LDS)");
+    *waves = lambda_waves(n_theta, n_depth, *gpw);
+    return SDX_OK;
+}
+}  // namespace
+
+int sdx_mean_intensity_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                           const double* mean_weights, const double* alphas, int64_t ald, const double* source, int64_t source_ld, double* J,
+                           int64_t J_ld, double* lambda_diag, int64_t L_ld)
+{
+    int gpw = 0, waves = 0, rc;
+    if ((rc = lambda_shape(ctx, "mean_intensity", n_depth, n_nu, n_theta, &gpw, &waves))) return rc;
+    if (n_nu == 0) return SDX_OK;
+    REQUIRE(J || lambda_diag, "mean_intensity: no output requested");
+    REQUIRE(nus && ray_dist && mean_weights && alphas && ald >= n_nu, "mean_intensity: null pointer or alpha_ld below n_nu");
+    REQUIRE((!J || J_ld >= n_nu) && (!lambda_diag || L_ld >= n_nu), "mean_intensity: leading dimension of an output below n_nu");
+    REQUIRE(source ? source_ld >= n_nu : temps != nullptr, "mean_intensity: bad source plane (source_ld < n_nu), or neither a source plane nor temperatures");
+    {
+        LaunchScope ls(ctx, "k_lambda", "k_lambda<false>");
+        hipLaunchKernelGGL(k_lambda<false>, dim3(lambda_blocks(n_nu, gpw, waves)), dim3(64 * waves), waves * RtLambda(n_theta, n_depth, gpw).bytes(), ctx->stream,
+                           n_depth, n_nu, n_theta, n_theta, n_theta, nus, temps, ray_dist, mean_weights, alphas, ald, source, source_ld, J, J_ld, lambda_diag, L_ld,
+                           gpw, waves, LambdaIteration{});
+    }
+    return check_launch("k_lambda");
+}
+
+int sdx_scatter_source_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                           const double* mean_weights, const double* alphas, int64_t ald, const double* alpha_scatter, int64_t scatter_ld,
+                           const double* thermal, int64_t thermal_ld, double tol, int max_iter, double* S, int64_t S_ld, double* J, int64_t J_ld,
+                           int* iterations, int* status, double* change)
+{
+    int gpw = 0, waves = 0, rc;
+    if ((rc = lambda_shape(ctx, "scatter_source", n_depth, n_nu, n_theta, &gpw, &waves))) return rc;
+    REQUIRE(tol >= 0.0 && max_iter >= 1, "scatter_source: need tol >= 0 (not NaN) and max_iter >= 1");
+    if (n_nu == 0) return SDX_OK;
+    REQUIRE(nus && ray_dist && mean_weights && alphas && ald >= n_nu && alpha_scatter && S, "scatter_source: null pointer or alpha_ld below n_nu");
+    REQUIRE((scatter_ld == 0 || scatter_ld >= n_nu) && S_ld >= n_nu && (!J || J_ld >= n_nu), "scatter_source: a leading dimension below n_nu (scatter_ld: 0 or >= n_nu)");
+    REQUIRE(thermal ? thermal_ld >= n_nu : temps != nullptr, "scatter_source: bad thermal plane (thermal_ld < n_nu), or neither a thermal plane nor temperatures");
+    {
+        LaunchScope ls(ctx, "k_lambda", "k_lambda<true>");
+        hipLaunchKernelGGL(k_lambda<true>, dim3(lambda_blocks(n_nu, gpw, waves)), dim3(64 * waves), waves * RtLambda(n_theta, n_depth, gpw).bytes(), ctx->stream,
+                           n_depth, n_nu, n_theta, n_theta, n_theta, nus, temps, ray_dist, mean_weights, alphas, ald, thermal, thermal_ld, J, J_ld, (double*)nullptr,
+                           (int64_t)0, gpw, waves, LambdaIteration{alpha_scatter, scatter_ld, tol, max_iter, S, S_ld, iterations, status, change});
+    }
+    return check_launch("k_lambda");
+}
+
+int sdx_mean_intensity_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                           const double* mean_weights, const double* alphas, const double* source, double* J, double* lambda_diag)
+{
+    int rc;
+    if ((rc = sdx_mean_intensity_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0)) || n_nu == 0)
+        return rc;  // refusals before any copy
+    REQUIRE(n_nu > 0 && nus && temps && ray_dist && mean_weights && alphas, "mean_intensity: null pointer");
+    REQUIRE(J || lambda_diag, "mean_intensity: no output requested");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
+    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_s;
+    double *d_j, *d_l;
+    HostPlan plan;
+    plan.in(nus, (size_t)n_nu * f8, &d_nus);
+    plan.in(temps, (size_t)n_depth * f8, &d_t);
+    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
+    plan.in(mean_weights, (size_t)n_theta * f8, &d_w);
+    plan.in(alphas, plane, &d_a);
+    plan.in(source, plane, &d_s);
+    plan.out(J, plane, &d_j);
+    plan.out(lambda_diag, plane, &d_l);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_mean_intensity_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_s, n_nu, d_j, n_nu, d_l, n_nu))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+int sdx_scatter_source_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                           const double* mean_weights, const double* alphas, const double* alpha_scatter, int scatter_per_frequency,
+                           const double* thermal, double tol, int max_iter, double* S, double* J, int* iterations, int* status, double* change)
+{
+    int rc;
+    if ((rc = sdx_scatter_source_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, tol, max_iter, nullptr, 0,
+                                     nullptr, 0, nullptr, nullptr, nullptr)) ||
+        n_nu == 0)
+        return rc;  // refusals before any copy
+    REQUIRE(n_nu > 0 && nus && temps && ray_dist && mean_weights && alphas && alpha_scatter && S, "scatter_source: null pointer");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
+    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_sc, *d_b;
+    double *d_s, *d_j, *d_c;
+    int *d_it, *d_st;
+    HostPlan plan;
+    plan.in(nus, (size_t)n_nu * f8, &d_nus);
+    plan.in(temps, (size_t)n_depth * f8, &d_t);
+    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
+    plan.in(mean_weights, (size_t)n_theta * f8, &d_w);
+    plan.in(alphas, plane, &d_a);
+    plan.in(alpha_scatter, scatter_per_frequency ? plane : (size_t)n_depth * f8, &d_sc);
+    plan.in(thermal, plane, &d_b);
+    plan.out(S, plane, &d_s);
+    plan.out(J, plane, &d_j);
+    plan.out(iterations, (size_t)n_nu * sizeof(int), &d_it);
+    plan.out(status, (size_t)n_nu * sizeof(int), &d_st);
+    plan.out(change, (size_t)n_nu * f8, &d_c);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_scatter_source_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_sc, scatter_per_frequency ? n_nu : 0, d_b, n_nu, tol,
+                                     max_iter, d_s, n_nu, d_j, n_nu, d_it, d_st, d_c)))
+        return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
 // ---- per-line flux sensitivities (k_response_weight, k_line_adjoint) --------------------------------------------------------
 int sdx_response_weight_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* R_alpha, int64_t R_ld, const double* total, int64_t total_ld,
                             const double* nu_weight, double* weight, int64_t weight_ld)

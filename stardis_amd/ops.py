@@ -628,6 +628,102 @@ def response(tracing_nus, temperatures, ray_distances, theta_weights, total_alph
     return (d_Ra.numpy() if want_opacity else None), (d_Rs.numpy() if want_source else None)
 
 
+def mean_weights(thetas, theta_weights):
+    """Weights m (N_theta,) of the mean intensity J = sum_k m_k (I_k up + I_k down) for the field's Gauss-Legendre nodes in theta:
+    m_k = w_k sin(theta_k) / (2 sum_j w_j sin(theta_j)) with w = I_nus_weights, normalised so that sum_k 2 m_k = 1 to rounding (an
+    isotropic field gives J = I).  Host arithmetic on N_theta numbers; the sum is exact (math.fsum) and every quotient correctly rounded."""
+    import math
+
+    th, w = _host(thetas).reshape(-1), _host(theta_weights).reshape(-1)
+    if th.size == 0 or th.size != w.size:
+        raise ValueError(f"thetas and theta_weights must hold the same number of angles, got {th.size} and {w.size}")
+    x = w * np.sin(th)
+    return x / (2.0 * math.fsum(x))
+
+
+def _lambda_inputs(what, tracing_nus, temperatures, ray_distances, weights, total_alphas, planes):
+    """The host-side checks mean_intensity and scatter_source share, before any device is asked for -> (nus, t, rd, m, {name: plane})."""
+    nus = _host(tracing_nus).reshape(-1)
+    t = _host(temperatures).reshape(-1)
+    m = _host(weights).reshape(-1)
+    if m.size > 64:
+        raise ValueError(f"{what}: more than 64 angles are not supported, got {m.size}")
+    rd = _host(ray_distances)
+    if t.size < 2 or m.size == 0 or rd.size != (t.size - 1) * m.size:
+        raise ValueError(f"ray_distances must have shape {(t.size - 1, m.size)}, got {rd.shape}")
+    rd = rd.reshape(t.size - 1, m.size)
+    shape = tuple(int(v) for v in (total_alphas.shape if hasattr(total_alphas, "shape") else np.shape(total_alphas)))
+    if shape != (t.size, nus.size):
+        raise ValueError(f"total_alphas must have shape {(t.size, nus.size)}, got {shape}")
+    out = {}
+    for name, plane in planes.items():
+        if plane is not None and not (isinstance(plane, DeviceArray) or hasattr(plane, "data_ptr")):
+            plane = _host(plane)
+        if plane is not None and tuple(int(v) for v in plane.shape) != (t.size, nus.size):
+            raise ValueError(f"{name} must have shape {(t.size, nus.size)}, got {tuple(plane.shape)}")
+        out[name] = plane
+    return nus, t, rd, m, out
+
+
+def mean_intensity(tracing_nus, temperatures, ray_distances, mean_weights, total_alphas, ctx=None, source=None, device=False,
+                   want_J=True, want_L=True):
+    """Mean intensity of the plane-parallel formal solution (sdx_mean_intensity_dev) -> (J, L), each (N_d, N_nu): J over both
+    hemispheres for the source plane (default: Planck) with a thermalised lower boundary, and L, the diagonal of that operator.
+    mean_weights: ops.mean_weights(thetas, theta_weights); the other arguments as for response().  want_J / want_L = False: that
+    output is not formed (None in its place).  device=True: DeviceArrays instead of host arrays."""
+    nus, t, rd, m, planes = _lambda_inputs("mean_intensity", tracing_nus, temperatures, ray_distances, mean_weights, total_alphas, dict(source=source))
+    if not (want_J or want_L):
+        raise ValueError("mean_intensity: no output requested")
+    ctx = ctx or default_context()
+    d_alpha = _dev(ctx, total_alphas)
+    d_S = _dev(ctx, planes["source"])
+    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd), ctx.upload(m)]
+    d_J = ctx.empty((t.size, nus.size)) if want_J else None
+    d_L = ctx.empty((t.size, nus.size)) if want_L else None
+    ctx.call("sdx_mean_intensity_dev", t.size, nus.size, m.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, ptr_of(d_alpha), nus.size,
+             ptr_of(d_S), nus.size, ptr_of(d_J), nus.size, ptr_of(d_L), nus.size)
+    if device:
+        return d_J, d_L
+    return (d_J.numpy() if want_J else None), (d_L.numpy() if want_L else None)
+
+
+def scatter_source(tracing_nus, temperatures, ray_distances, mean_weights, total_alphas, alpha_scatter, ctx=None, thermal=None,
+                   tol=1e-12, max_iter=2000, device=False, want_J=True):
+    """Source function with coherent continuum scattering (sdx_scatter_source_dev): S = (1 - albedo) B + albedo J[S], albedo =
+    alpha_scatter / total_alphas, by Jacobi iteration with the local operator, every column on its own until it meets
+    max |dS| <= tol max |S| (status 0), has taken max_iter iterations (1) or its change is not finite (2).
+    alpha_scatter: (N_d,) — one value per depth point, e.g. Thomson — or (N_d, N_nu), host or device; thermal: optional plane B
+    (default: Planck).  -> namespace(S, J, iterations, status, change): S and J (N_d, N_nu) (J of the returned S; None with
+    want_J=False), per column the iteration count and status (int32) and the last change.  device=True: DeviceArrays."""
+    import types
+
+    nus, t, rd, m, planes = _lambda_inputs("scatter_source", tracing_nus, temperatures, ray_distances, mean_weights, total_alphas, dict(thermal=thermal))
+    on_device = isinstance(alpha_scatter, DeviceArray) or hasattr(alpha_scatter, "data_ptr")
+    sc = alpha_scatter if on_device else _host(alpha_scatter)
+    sc_shape = tuple(int(v) for v in sc.shape)
+    if sc_shape not in ((t.size,), (t.size, nus.size)):
+        raise ValueError(f"alpha_scatter must have shape {(t.size,)} or {(t.size, nus.size)}, got {sc_shape}")
+    if not float(tol) >= 0.0:
+        raise ValueError(f"scatter_source: tol must be >= 0, got {tol}")
+    if int(max_iter) < 1:
+        raise ValueError(f"scatter_source: max_iter must be >= 1, got {max_iter}")
+    ctx = ctx or default_context()
+    d_alpha = _dev(ctx, total_alphas)
+    d_sc = _dev(ctx, sc)
+    d_B = _dev(ctx, planes["thermal"])
+    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd), ctx.upload(m)]
+    out = types.SimpleNamespace(S=ctx.empty((t.size, nus.size)), J=ctx.empty((t.size, nus.size)) if want_J else None,
+                                iterations=ctx.empty((nus.size,), np.int32), status=ctx.empty((nus.size,), np.int32), change=ctx.empty((nus.size,)))
+    ctx.call("sdx_scatter_source_dev", t.size, nus.size, m.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, ptr_of(d_alpha), nus.size,
+             ptr_of(d_sc), nus.size if len(sc_shape) == 2 else 0, ptr_of(d_B), nus.size, float(tol), int(max_iter), out.S.ptr, nus.size,
+             ptr_of(out.J), nus.size, out.iterations.ptr, out.status.ptr, out.change.ptr)
+    if not device:
+        for name in ("S", "J", "iterations", "status", "change"):
+            value = getattr(out, name)
+            setattr(out, name, None if value is None else value.numpy())
+    return out
+
+
 def formation_mean(contribution, x, ctx=None, device=False):
     """Formation mean of a per-depth quantity x (N_d) under a contribution function (N_d, N_nu; host or device array):
     (sum_{k>=1} C[k] m_k) / (sum_{k>=1} C[k]), m_k = (x[k-1] + x[k]) / 2 (sdx_formation_mean_dev) -> (N_nu,)."""

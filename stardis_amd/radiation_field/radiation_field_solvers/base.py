@@ -154,6 +154,52 @@ def response_functions(stellar_model, stellar_radiation_field):
     )
 
 
+SPHERICAL_SCATTERING = ("the mean intensity and the scattering source function are defined for plane-parallel models: the downward sweep "
+                        "of a spherical model runs along chords that miss the inner shells, which the two-hemisphere quadrature here does not describe")
+
+
+def _lambda_arguments(stellar_model, field):
+    """what ops.mean_intensity and ops.scatter_source take from a model and its field: frequencies, temperatures, the ray table of
+    :302-305, the mean weights of the field's angles, the total opacity (on the device where the field keeps it there), the context"""
+    if bool(getattr(stellar_model, "spherical", False)):
+        raise NotImplementedError(SPHERICAL_SCATTERING)
+    thetas = np.asarray(field.thetas, dtype=np.float64)
+    dist = np.asarray(plain(stellar_model.geometry.dist_to_next_depth_point), dtype=np.float64)
+    ray_distances = dist.reshape(-1, 1) / np.cos(thetas)
+    ctx = default_context()
+    opac = field.opacities
+    alphas = opac.total_alphas_device(ctx) if hasattr(opac, "total_alphas_device") else opac.total_alphas
+    return (field.frequencies, plain(stellar_model.temperatures), ray_distances, ops.mean_weights(thetas, field.I_nus_weights), alphas), ctx
+
+
+def mean_intensity(stellar_model, stellar_radiation_field):
+    """Mean intensity J and the diagonal L of its operator, each (N_d, N_nu), of the field's formal solution over both hemispheres
+    (sdx_mean_intensity_dev): the same angles, source function, geometry and total opacity as raytrace() above, the lower boundary
+    thermalised.  The reference has no counterpart.  A spherical model raises NotImplementedError."""
+    field = stellar_radiation_field
+    args, ctx = _lambda_arguments(stellar_model, field)
+    return ops.mean_intensity(*args, ctx=ctx, source=_source_plane(getattr(field, "source_function", None), field.frequencies, stellar_model.temperatures))
+
+
+def scattering_source(stellar_model, stellar_radiation_field, tol=1e-12, max_iter=2000):
+    """Source function with coherent continuum scattering, S = (1 - albedo) B + albedo J[S] (sdx_scatter_source_dev) -> namespace(S, J,
+    iterations, status, change) as ops.scatter_source returns it.  The scattering opacity is the field's own Rayleigh + Thomson entries
+    (opacities_dict["alpha_rayleigh"] + ["alpha_electron"], which the total holds as absorption); B is the field's source function.
+    S feeds raytrace(), contribution_function() and response_functions() as a source plane: a field whose source_function returns it
+    is traced with scattering.  The reference has no counterpart.  A spherical model raises NotImplementedError."""
+    field = stellar_radiation_field
+    args, ctx = _lambda_arguments(stellar_model, field)
+    entries = field.opacities.opacities_dict
+    shape = (np.size(args[1]), np.size(plain(field.frequencies)))
+    scatter = np.zeros(shape)
+    for key in ("alpha_rayleigh", "alpha_electron"):  # (the order of the total: ... + rayleigh) + electron)
+        if key not in entries:
+            raise ValueError(f"the field's opacities carry no {key}: calc_alphas has not run")
+        scatter = scatter + np.broadcast_to(np.asarray(plain(entries[key]), dtype=np.float64), shape)
+    return ops.scatter_source(*args, scatter, ctx=ctx, tol=tol, max_iter=max_iter,
+                              thermal=_source_plane(getattr(field, "source_function", None), field.frequencies, stellar_model.temperatures))
+
+
 def formation_mean(stellar_radiation_field, x):
     """Formation mean (N_nu,) of a per-depth quantity x (N_d: geometric depth, temperature, a reference log tau) under the field's
     contribution function: (sum_{k>=1} C[k] m_k) / (sum_{k>=1} C[k]), m_k = (x[k-1] + x[k]) / 2 (sdx_formation_mean_dev).  The field must
