@@ -468,7 +468,8 @@ int sdx_response_project_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const doub
  * itself has no positive solution: the iteration diverges, which is what status 1 and 2 report.  DESIGN.md, "Scattering in the source function".
  * Refused with SDX_ERR_ARG before anything is enqueued (also for n_nu = 0): mixed_precision = 1, n_theta > 64, tol < 0 or NaN,
  * max_iter < 1, a model whose columns — (6 n_depth + 4 n_theta) doubles at one frequency per wave — do not fit 64 KB of LDS (1352
- * depth points at 20 angles).  Out of scope: spherical geometry, line scattering, derivatives of the scattering solution. */
+ * depth points at 20 angles).  Out of scope: spherical geometry, line scattering.  Derivatives of the scattering solution:
+ * sdx_scatter_response_dev below. */
 int sdx_mean_intensity_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
                            const double* temperature, const double* ray_dist, const double* mean_weights,
                            const double* total_alphas, int64_t alpha_ld, const double* source, int64_t source_ld,
@@ -488,6 +489,75 @@ int sdx_scatter_source_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta,
                            const double* total_alphas, const double* alpha_scatter, int scatter_per_frequency,
                            const double* thermal, double tol, int max_iter, double* S, double* J, int* iterations,
                            int* status, double* change);
+
+/* ---- continuum scattering: the adjoint solve and the flux responses --------------------------------
+ * The derivative of a functional of the scattering solution is the adjoint of a fixed point: one transposed solve per column with
+ * the operator of sdx_mean_intensity_dev, not a derivative through the iterations.  Notation as there: Lambda is the linear map
+ * S -> J of one column (upward sweep from U[0] = S[0], downward sweep from 0, mean weights m), W = diag(albedo).  Both sweeps are
+ * chains of the kernels' own step, val[s+1] = c[s] val[s] + e[s], e[s] = a[s] S[behind] + q[s] S[arrival] + r[s] S[ahead] — behind,
+ * arrival, ahead are the rows (s, s+1, s+2) of the upward sweep and (N_d-1-s, N_d-2-s, N_d-3-s) of the downward one; the last step of
+ * a sweep has r = 0 and the last-gap a and q.  (c, a, q, r, p0 = -dc/dt0, de/dt0, de/dt1) are those of sdx_response_dev above, with
+ * t0 the optical depth of the step's own gap and t1 that of the sweep's next gap.
+ * Transposed application.  Given a plane z, for each sweep and angle theta walk against the sweep with
+ *     vbar[last] = m_theta z[p_last],   vbar[s] = m_theta z[p_s] + c[s] vbar[s+1]        (p_s: the row the sweep reaches after s steps)
+ * and accumulate
+ *     (Lambda^T z)[behind_s] += a[s] vbar[s+1],  (Lambda^T z)[arrival_s] += q[s] vbar[s+1],  (Lambda^T z)[ahead_s] += r[s] vbar[s+1],
+ * and in the upward sweep (Lambda^T z)[0] += vbar[0].  A gap with tau == 0 is the (1, 0) step: c = 1, a = q = r = 0.  Per ray a row
+ * collects (a[j] vbar[j+1] + q[j-1] vbar[j]) + r[j-2] vbar[j-1]; the sum over theta runs in the flux's order (two ascending halves,
+ * the lower added to the upper), the downward sweep's sum is added to the upward one's.  The kernel takes (c, a, q, r) of this walk
+ * from the forward step itself (the step is linear in the three source values): sum z J[x] = sum (Lambda^T z) x holds between the
+ * two entry points to rounding, also where the step's own rounding near tau = 5e-4 is far above that.
+ * Opacity derivative of one application, at fixed S.  With val[s] of the forward sweep, the gap of step s collects
+ *     tbar[gap t0_s] += vbar[s+1] (de/dt0[s] - p0[s] val[s]),     tbar[gap t1_s] += vbar[s+1] de/dt1[s]
+ * and  G[k] = d(z^T J[S]) / d ln alpha[k] = sum_theta (t[k-1] tbar[k-1] + t[k] tbar[k]) / 2  (terms that do not exist are dropped: the
+ * shape of R_alpha), per sweep, the downward sweep's sum added to the upward one's.
+ * sdx_mean_intensity_adjoint_dev is one application: Lt = Lambda^T z and / or G [n_depth][ld] (either may be NULL, not both) for the
+ * planes z [n_depth][z_ld] and source (NULL: Planck; it enters G only).  Either output alone has the bits it has beside the other.
+ * Adjoint solve.  For a functional Phi(S, alpha) with cotangent c = dPhi/dS and direct part d = dPhi/d ln alpha at fixed S — for the
+ * emergent flux R_source and R_alpha of sdx_response_dev(source = S) — sdx_scatter_response_dev solves y = c + Lambda^T (W y):
+ *     y^0 = c,   y^(n+1) = y^n + (c + Lambda^T (W y^n) - y^n) / (1 - albedo Lc),   Lc = clamp(L, 0, 1) (NaN -> 0)
+ * with L, the clamp, the stopping rule max |dy| <= tol max |y^(n+1)|, status 0 / 1 / 2, the refused non-finite update, the frozen
+ * column, `iterations` and `change` exactly those of sdx_scatter_source_dev.  (1 - D M^T) is the transpose of (1 - M D), and M D is
+ * similar to D M: the spectral radius is the forward iteration's.  albedo is formed as there (clamped to [0, 1], NaN -> 0, 0 where
+ * total_alphas == 0); thermal = NULL: Planck; direct = NULL: 0.
+ * Outputs, with z = W y, G of that z, J = Lambda S of the S passed in, A[k] = d[k] + G[k] (the total derivative to ln alpha at fixed
+ * albedo) and H[k] = y[k] (J[k] - B[k]) = dPhi/d albedo[k]:
+ *     y                                                             (optional)
+ *     R_thermal[k]    = (1 - albedo[k]) y[k]                            = dPhi/dB[k]
+ *     R_absorption[k] = A[k] - albedo[k] H[k]                           = dPhi/d ln alpha[k] when the added opacity is true absorption
+ *                                                                        (alpha_scatter and B fixed): what takes R_alpha's place
+ *     R_scatter[k]    = albedo[k] A[k] + albedo[k] (1 - albedo[k]) H[k]  = dPhi/d ln alpha_scatter[k] at fixed absorption
+ * each [n_depth][ld], each may be NULL, not all.  The derivatives are exact for the discrete problem AT THE S THAT IS PASSED IN: at an
+ * unconverged S (status 1 of sdx_scatter_source_dev) they are the derivatives of the fixed-point equations, not of the truncated
+ * iteration.  No atomics and no grid-wide synchronisation: the same bits from run to run, a column's bits do not depend on the grid,
+ * the shard or the other columns.
+ * Refused with SDX_ERR_ARG before anything is enqueued (also for n_nu = 0): mixed_precision = 1, n_theta > 64, tol < 0 or NaN,
+ * max_iter < 1, a model whose columns and stashed sweep — ((n_theta + 10) n_depth + 3 n_theta) doubles at one frequency per wave — do
+ * not fit 64 KB of LDS (271 depth points at 20 angles).  Out of scope: spherical geometry, line scattering, second derivatives. */
+int sdx_mean_intensity_adjoint_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                                   const double* temperature, const double* ray_dist, const double* mean_weights,
+                                   const double* total_alphas, int64_t alpha_ld, const double* z, int64_t z_ld,
+                                   const double* source, int64_t source_ld, double* Lt, int64_t Lt_ld, double* G,
+                                   int64_t G_ld);
+int sdx_scatter_response_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                             const double* temperature, const double* ray_dist, const double* mean_weights,
+                             const double* total_alphas, int64_t alpha_ld, const double* alpha_scatter, int64_t scatter_ld,
+                             const double* thermal, int64_t thermal_ld, const double* S, int64_t S_ld,
+                             const double* cotangent, int64_t cotangent_ld, const double* direct, int64_t direct_ld,
+                             double tol, int max_iter, double* y, int64_t y_ld, double* R_thermal, int64_t R_thermal_ld,
+                             double* R_absorption, int64_t R_absorption_ld, double* R_scatter, int64_t R_scatter_ld,
+                             int* iterations, int* status, double* change);
+/* host-buffer twins: contiguous arrays, planes [n_depth][n_nu]; NULL as above. */
+int sdx_mean_intensity_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                                   const double* temperature, const double* ray_dist, const double* mean_weights,
+                                   const double* total_alphas, const double* z, const double* source, double* Lt,
+                                   double* G);
+int sdx_scatter_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                             const double* temperature, const double* ray_dist, const double* mean_weights,
+                             const double* total_alphas, const double* alpha_scatter, int scatter_per_frequency,
+                             const double* thermal, const double* S, const double* cotangent, const double* direct,
+                             double tol, int max_iter, double* y, double* R_thermal, double* R_absorption,
+                             double* R_scatter, int* iterations, int* status, double* change);
 
 /* ---- per-line flux sensitivities: the adjoint of the line-opacity sum -----------------------------
  * WHICH lines matter: the line opacity scatters, for every line l and depth point d,

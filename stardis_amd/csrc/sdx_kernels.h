@@ -4790,6 +4790,351 @@ __global__ __launch_bounds__(kRtBlock) void k_lambda(int n_depth, int64_t n_nu, 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The adjoint of the mean-intensity operator and of the scattering solve (include/stardis_hip.h, sdx_mean_intensity_adjoint_dev and
+// sdx_scatter_response_dev, state the definitions).  k_lambda's mapping — lane <-> (frequency, angle), a wave's columns in its own LDS
+// (RtLambdaAdjoint), no wave waits for another, no atomics — and k_response's two-walk scheme, once per sweep of the operator:
+//   transposed application   a lane walks AGAINST the sweep with the adjoint of the value, vbar[s] = m z[p_s] + c[s] vbar[s+1], and the
+//                            row at sweep position j collects (a[j] vbar[j+1] + q[j-1] vbar[j]) + r[j-2] vbar[j-1] — the walk visits
+//                            step j-2 and then emits row j, two rows behind the step, as k_response does; the row the upward sweep
+//                            starts from also takes vbar[0].  (c, a, q, r) are the forward step's OWN: e is linear in the three
+//                            source values, so rt_coef on unit differences returns them, and what is transposed is the operator
+//                            k_lambda applies, to rounding (rt_coef_derivative's forms of the same coefficients are more accurate
+//                            near tau = 5e-4 than the step is, and z . J[x] = (Lambda^T z) . x would hold to 1e-8 only).  They
+//                            depend on the optical depths alone, so the solve's loop needs no stash.
+//   differentiated           the forward sweep (k_lambda's, rt_coef) stashes the value entering every step per ray; the reverse walk forms
+//   application              tbar[j] = vbar[j+1] (de/dt0[j] - p0[j] val[j]) + vbar[j] de/dt1[j-1] and the row takes (t[j-1] tbar[j-1] +
+//                            t[j] tbar[j]) / 2.  One stash serves both sweeps in turn.
+// The rows of a batch are summed over theta through LDS in the flux's order; the downward sweep's sums are added to the upward one's.
+// kSolve: y = c + Lambda^T (W y) by Jacobi with the forward kernel's local operator 1 / (1 - albedo clamp(L)), L formed as k_lambda
+// forms it; the stopping rule, the three statuses, the refused non-finite update and the frozen column are k_lambda<true>'s, line by
+// line.  Then, where an opacity derivative is asked for, the differentiated application at z = W y (which also leaves J of S), and the
+// combination of the outputs per depth point.
+struct LambdaAdjointSolve {
+    const double* scatter;  // alpha_scatter [n_depth][scatter_ld]; scatter_ld == 0: [n_depth]
+    int64_t scatter_ld;
+    const double* thermal;  // B [n_depth][thermal_ld]; NULL: Planck
+    int64_t thermal_ld;
+    const double* cotangent;  // [n_depth][cotangent_ld]
+    int64_t cotangent_ld;
+    const double* direct;  // [n_depth][direct_ld]; NULL: 0
+    int64_t direct_ld;
+    double tol;
+    int max_iter;
+    double* y;  // outputs [n_depth][ld], each may be NULL
+    int64_t y_ld;
+    double* R_thermal;
+    int64_t R_thermal_ld;
+    double* R_absorption;
+    int64_t R_absorption_ld;
+    double* R_scatter;
+    int64_t R_scatter_ld;
+    int* iterations;  // per column, each may be NULL
+    int* status;
+    double* change;
+};
+template <bool kSolve>
+__global__ __launch_bounds__(kRtBlock) void k_lambda_adjoint(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
+                                                           const double* __restrict__ nus, const double* __restrict__ temps,
+                                                           const double* __restrict__ ray_dist, const double* __restrict__ mean_wts,
+                                                           const double* __restrict__ alphas, int64_t ald, const double* __restrict__ source,
+                                                           int64_t sld, const double* __restrict__ z, int64_t zld, double* __restrict__ Lt,
+                                                           int64_t ltld, double* __restrict__ Gout, int64_t gld, int gpw, int waves,
+                                                           LambdaAdjointSolve it)
+{
+    constexpr int kBatch = kRtBatch;
+    extern __shared__ double smem[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int grp = lane / G, g = lane - grp * G;
+    const int64_t i0 = ((int64_t)blockIdx.x * waves + wave) * gpw;  // first frequency of this wave
+    const int64_t i = i0 + grp;
+    const bool active = grp < gpw;
+    const bool valid = active && i < n_nu;
+    const int64_t ic = i < n_nu ? i : n_nu - 1;
+    const int n_gap = n_depth - 1;
+    const int col = n_depth;
+    const RtLambdaAdjoint lay(G, n_depth, gpw);
+    const int n_slot = lay.slots();
+    double* wbase = smem + (size_t)wave * lay.wave_doubles();
+    double2* sP = (double2*)(wbase + lay.pairs());  // (source function S, sqrt(alpha)) [gpw][col]
+    double* sZ = wbase + lay.z();                   // what Lambda^T is applied to [gpw][col]
+    double* sR = wbase + lay.result();              // Lambda^T z
+    double* sY = wbase + lay.iterate();             // y
+    double* sC = wbase + lay.cotangent();           // c
+    double* sW = wbase + lay.albedo();              // albedo
+    double* sD = wbase + lay.diag();                // L, then 1 / (1 - albedo clamp(L))
+    double* sJ = wbase + lay.mean();                // J of S
+    double* sG = wbase + lay.gradient();            // d(z^T J[S]) / d ln alpha
+    double* sI = wbase + lay.stash();               // the value entering step s, [n_gap][n_slot]
+    double* sX = wbase + lay.terms();               // terms of a batch of rows [kBatch][gpw][G]; the maxima of the stopping rule [2][gpw][G]
+    const double nu = nus[ic];
+    const int cbase = (active ? grp : 0) * col;     // idle lanes shadow group 0 and never store
+    const int slot = (active ? grp : 0) * G + g;
+
+    if (active) {
+        for (int d = g; d < n_depth; d += G) {
+            const double a = alphas[(size_t)d * ald + ic];
+            sP[cbase + d] = double2{source ? source[(size_t)d * sld + ic] : planck_staged(nu, temps[d]), sqrt(a)};
+            if constexpr (kSolve) {
+                double w = a == 0.0 ? 0.0 : it.scatter[it.scatter_ld ? (size_t)d * it.scatter_ld + ic : (size_t)d] / a;
+                w = w > 0.0 ? (w < 1.0 ? w : 1.0) : 0.0;  // clamped to [0, 1]; NaN -> 0
+                const double c = it.cotangent[(size_t)d * it.cotangent_ld + ic];
+                sW[cbase + d] = w;
+                sC[cbase + d] = c;
+                sY[cbase + d] = c;  // y^0 = c
+            } else {
+                sZ[cbase + d] = z[(size_t)d * zld + ic];
+            }
+        }
+    }
+    wave_sync();
+    const RtConst kc = rt_const_literals();
+    const int th = min(g, n_theta - 1);
+    const double wt = g < n_theta ? mean_wts[th] : 0.0;
+    const double* rd = ray_dist + th;  // rd[gap * theta_stride]
+    const float inv_gpw = 1.0f / (float)gpw;
+    const int half = (n_theta + 1) >> 1;
+
+    // k_lambda's: the nb rows first, first + step, ... of a batch, each half of the angles summed in ascending theta and the lower half
+    // added to the upper one -> dst[frequency][row], written or added to
+    auto reduce = [&](int nb, int first, int step, bool add, double* dst) {
+        for (int p = lane; p < 2 * nb * gpw; p += 64) {
+            const int h = p & 1, q = p >> 1;
+            const int b = (int)(((float)q + 0.5f) * inv_gpw), gq = q - b * gpw;  // q / gpw without an integer division (q < 2^20: exact)
+            const double* t = sX + (b * gpw + gq) * G + (h ? half : 0);
+            const int cnt = h ? n_theta - half : half;
+            double sum = 0.0;
+            for (int j = 0; j < cnt; ++j) sum = add_rn(sum, t[j]);
+            const double other = __shfl_xor(sum, 1);  // 2 nb gpw is even: the partner lane is in the loop too
+            if (h == 0) {
+                double* o = dst + gq * col + first + b * step;
+                const double tot = add_rn(sum, other);
+                *o = add ? add_rn(*o, tot) : tot;
+            }
+        }
+    };
+    // k_lambda's sweep dir over the wave's columns.  kDiag: the diagonal -> dst.  Otherwise the values of S: the value entering every
+    // step goes to the stash, and with dst the mean intensity is summed (dir 0 written, dir 1 added).
+    auto forward = [&](auto diag_tag, int dir, double* dst) {
+        constexpr bool kDiag = decltype(diag_tag)::value;
+        const int sgn = dir ? -1 : 1, start = dir ? n_gap : 0;
+        double2 pa = sP[cbase + start], pb = sP[cbase + start + sgn];  // the points behind and at the arrival of step 0
+        double t0 = mul_rn(pa.y * pb.y, rd[(size_t)(dir ? n_gap - 1 : 0) * theta_stride]);
+        double val = dir ? 0.0 : (kDiag ? 1.0 : pa.x);  // U[0] = S[0]: a thermalised lower boundary; D[N_d-1] = 0
+        if (dst) {
+            if (active) sX[grp * G + g] = val * wt;
+            wave_sync();
+            reduce(1, start, sgn, dir != 0, dst);
+            wave_sync();
+        }
+        for (int s0 = 0; s0 < n_gap; s0 += kBatch) {
+            const int nb = min(kBatch, n_gap - s0);
+            for (int b = 0; b < nb; ++b) {
+                const int s = s0 + b;
+                const bool last = s == n_gap - 1;
+                const int pt = start + sgn * (s + 1);                      // the arrival point
+                const double2 pc = sP[cbase + (last ? pt : pt + sgn)];     // the point ahead
+                const double t1 = last ? 0.0 : mul_rn(pb.y * pc.y, rd[(size_t)(dir ? pt - 1 : pt) * theta_stride]);
+                if constexpr (kDiag) {
+                    val = last ? rt_coef_derivative<true>(t0, 0.0, 0.0, 0.0, 0.0).q : rt_coef_derivative<false>(t0, t1, 0.0, 0.0, 0.0).q;
+                } else {
+                    if (active) sI[s * n_slot + slot] = val;
+                    double c, e;
+                    if (last) rt_coef<true>(t0, 0.0, pa.x - pb.x, 0.0, pb.x, c, e, kc);
+                    else rt_coef<false>(t0, t1, pa.x - pb.x, pc.x - pb.x, pb.x, c, e, kc);
+                    val = fma(c, val, e);
+                }
+                if (dst && active) sX[(b * gpw + grp) * G + g] = val * wt;
+                pa = pb, pb = pc, t0 = t1;
+            }
+            if (dst) {
+                wave_sync();
+                reduce(nb, start + sgn * (s0 + 1), sgn, dir != 0, dst);
+                wave_sync();
+            }
+        }
+    };
+    // the walk against sweep dir with the plane zc.  kGrad: the opacity derivative of z^T J[S] from the stash of forward(dir) -> dst;
+    // otherwise Lambda^T z -> dst.  dir 0 writes, dir 1 adds.
+    auto backward = [&](auto grad_tag, int dir, const double* zc, double* dst) {
+        constexpr bool kGrad = decltype(grad_tag)::value;
+        const int sgn = dir ? -1 : 1, start = dir ? n_gap : 0;
+        double vbar = mul_rn(wt, zc[cbase + start + sgn * n_gap]);  // of the value at the sweep's last row
+        double t_up = 0.0;                   // tau of step m+1
+        double x0_up = 0.0;                  // vbar[m+2] (de/dt0 - p0 val) of step m+1
+        double tg_up = 0.0;                  // t[m+2] tbar[m+2]
+        double ta_up = 0.0, ta_up2 = 0.0;    // vbar[m+2] a[m+1], vbar[m+3] a[m+2]
+        double tq_up = 0.0;                  // vbar[m+2] q[m+1]
+        double2 pB = sP[cbase + start + sgn * n_gap], pC = pB;  // the arrival point of step m and the point ahead
+        double x0 = 0.0, x1 = 0.0, ta = 0.0, tq = 0.0, tr = 0.0, tm = 0.0;
+        // one visit: step m from the points (m, m+1, m+2) of the sweep -> x0, x1 or ta, tq, tr, and tm; zeros below the first step
+        auto visit = [&](int m) {
+            if (m < 0) {
+                x0 = x1 = ta = tq = tr = tm = 0.0;
+                return;
+            }
+            const double2 pA = sP[cbase + start + sgn * m];
+            tm = mul_rn(pA.y * pB.y, rd[(size_t)(dir ? n_gap - 1 - m : m) * theta_stride]);
+            double c;
+            if constexpr (kGrad) {
+                const RtStepDerivative d = m == n_gap - 1 ? rt_coef_derivative<true>(tm, 0.0, pA.x - pB.x, 0.0, pB.x)
+                                                          : rt_coef_derivative<false>(tm, t_up, pA.x - pB.x, pC.x - pB.x, pB.x);
+                const double val = sI[m * n_slot + slot];
+                x0 = mul_rn(vbar, sub_rn(d.de_dt0, mul_rn(d.p0, val)));
+                x1 = mul_rn(vbar, d.de_dt1);
+                c = d.c;
+            } else {
+                // e is linear in (S[behind] - S[arrival], S[ahead] - S[arrival], S[arrival]): the step on unit differences gives a, r and q
+                double a, q, r = 0.0;
+                if (m == n_gap - 1) {
+                    rt_coef<true>(tm, 0.0, 1.0, 0.0, 0.0, c, a, kc);
+                    rt_coef<true>(tm, 0.0, -1.0, 0.0, 1.0, c, q, kc);
+                } else {
+                    rt_coef<false>(tm, t_up, 1.0, 0.0, 0.0, c, a, kc);
+                    rt_coef<false>(tm, t_up, 0.0, 1.0, 0.0, c, r, kc);
+                    rt_coef<false>(tm, t_up, -1.0, -1.0, 1.0, c, q, kc);
+                }
+                ta = mul_rn(vbar, a), tq = mul_rn(vbar, q), tr = mul_rn(vbar, r);
+            }
+            vbar = add_rn(mul_rn(wt, zc[cbase + start + sgn * m]), mul_rn(c, vbar));
+            pC = pB, pB = pA;
+        };
+        visit(n_gap - 1);  // the sweep's last step: no row is complete yet
+        t_up = tm, x0_up = x0, ta_up = ta, tq_up = tq;
+        for (int ktop = n_depth - 1; ktop >= 0; ktop -= kBatch) {
+            const int nb = min(kBatch, ktop + 1);
+            for (int b = 0; b < nb; ++b) {
+                const int k = ktop - b;  // the row's position in the sweep
+                visit(k - 2);
+                double term;
+                if constexpr (kGrad) {
+                    const double tg = mul_rn(t_up, add_rn(x0_up, x1));  // t[k-1] tbar[k-1]
+                    term = mul_rn(0.5, add_rn(tg, tg_up));
+                    tg_up = tg, x0_up = x0;
+                } else {
+                    term = add_rn(add_rn(ta_up2, tq_up), tr);
+                    if (k == 0 && dir == 0) term = add_rn(term, vbar);  // U[0] = S[0]
+                    ta_up2 = ta_up, ta_up = ta, tq_up = tq;
+                }
+                t_up = tm;
+                if (active) sX[(b * gpw + grp) * G + g] = g < n_theta ? term : 0.0;
+            }
+            wave_sync();
+            reduce(nb, start + sgn * ktop, -sgn, dir != 0, dst);
+            wave_sync();
+        }
+    };
+    auto store_column = [&](const double* colv, double* out, int64_t ld) {
+        if (valid)
+            for (int d = g; d < n_depth; d += G) out[(size_t)d * ld + i] = colv[cbase + d];
+    };
+
+    if constexpr (!kSolve) {
+        if (Lt) {
+            backward(std::false_type{}, 0, sZ, sR);
+            backward(std::false_type{}, 1, sZ, sR);
+            store_column(sR, Lt, ltld);
+        }
+        if (Gout) {
+            for (int dir = 0; dir < 2; ++dir) {
+                forward(std::false_type{}, dir, (double*)nullptr);
+                wave_sync();
+                backward(std::true_type{}, dir, sZ, sG);
+            }
+            store_column(sG, Gout, gld);
+        }
+    } else {
+        forward(std::true_type{}, 0, sD);
+        forward(std::true_type{}, 1, sD);
+        if (active) {
+            for (int d = g; d < n_depth; d += G) {
+                const double l = sD[cbase + d];
+                const double lh = l > 0.0 ? (l < 1.0 ? l : 1.0) : 0.0;  // clamp(L, 0, 1)
+                sD[cbase + d] = 1.0 / sub_rn(1.0, mul_rn(sW[cbase + d], lh));
+                sZ[cbase + d] = mul_rn(sW[cbase + d], sY[cbase + d]);
+            }
+        }
+        wave_sync();
+        bool live = valid;
+        int iters = 0, status = 1;
+        double change = 0.0;
+        for (int n = 1;; ++n) {
+            const bool more = n <= it.max_iter && __builtin_amdgcn_ballot_w64(live) != 0;  // wave-uniform
+            if (!more) break;
+            backward(std::false_type{}, 0, sZ, sR);  // Lambda^T (W y^n)
+            backward(std::false_type{}, 1, sZ, sR);
+            double md = 0.0, ms = 0.0;
+            if (active) {
+                for (int d = g; d < n_depth; d += G) {
+                    const double y = sY[cbase + d];
+                    const double r = sub_rn(add_rn(sC[cbase + d], sR[cbase + d]), y);
+                    const double dy = mul_rn(r, sD[cbase + d]);
+                    sR[cbase + d] = dy;
+                    double ad = fabs(dy);
+                    if (!(ad <= kDoubleMax)) ad = __builtin_huge_val();  // not finite: the column stops (status 2)
+                    const double as = fabs(add_rn(y, dy));
+                    md = ad > md ? ad : md;
+                    ms = as > ms ? as : ms;
+                }
+                sX[grp * G + g] = md;
+                sX[(gpw + grp) * G + g] = ms;
+            }
+            wave_sync();
+            double cd = 0.0, cs = 0.0;  // the column's max |dy| and max |y^(n+1)|
+            {
+                const int xb = (active ? grp : 0) * G;
+                for (int t = 0; t < G; ++t) {
+                    const double vd = sX[xb + t], vs = sX[gpw * G + xb + t];
+                    cd = vd > cd ? vd : cd;
+                    cs = vs > cs ? vs : cs;
+                }
+            }
+            wave_sync();
+            if (live) {
+                iters = n, change = cd;
+                if (!(cd <= kDoubleMax)) {
+                    status = 2, live = false;  // y stays at the last finite iterate
+                } else {
+                    for (int d = g; d < n_depth; d += G) {
+                        const double y = add_rn(sY[cbase + d], sR[cbase + d]);
+                        sY[cbase + d] = y;
+                        sZ[cbase + d] = mul_rn(sW[cbase + d], y);
+                    }
+                    if (cd <= mul_rn(it.tol, cs)) status = 0, live = false;
+                }
+            }
+            wave_sync();
+        }
+        const bool want_grad = it.R_absorption || it.R_scatter;
+        if (want_grad) {
+            for (int dir = 0; dir < 2; ++dir) {
+                forward(std::false_type{}, dir, sJ);
+                backward(std::true_type{}, dir, sZ, sG);
+            }
+        }
+        if (valid) {
+            for (int d = g; d < n_depth; d += G) {
+                const double y = sY[cbase + d], w = sW[cbase + d];
+                const size_t row = (size_t)d;
+                if (it.y) it.y[row * it.y_ld + i] = y;
+                if (it.R_thermal) it.R_thermal[row * it.R_thermal_ld + i] = mul_rn(sub_rn(1.0, w), y);
+                if (want_grad) {
+                    const double b = it.thermal ? it.thermal[row * it.thermal_ld + i] : planck_staged(nu, temps[d]);
+                    const double A = add_rn(it.direct ? it.direct[row * it.direct_ld + i] : 0.0, sG[cbase + d]);
+                    const double H = mul_rn(y, sub_rn(sJ[cbase + d], b));
+                    if (it.R_absorption) it.R_absorption[row * it.R_absorption_ld + i] = sub_rn(A, mul_rn(w, H));
+                    if (it.R_scatter) it.R_scatter[row * it.R_scatter_ld + i] = add_rn(mul_rn(w, A), mul_rn(mul_rn(w, sub_rn(1.0, w)), H));
+                }
+            }
+            if (g == 0) {
+                if (it.iterations) it.iterations[i] = iters;
+                if (it.status) it.status[i] = status;
+                if (it.change) it.change[i] = change;
+            }
+        }
+    }
+}
+
 // The response to a scale factor on ONE part of the opacity: out[nu] = sum_k R_alpha[k][nu] (part[k][nu] / total[k][nu]), the
 // derivative of the emergent flux with respect to the logarithm of that factor (d ln alpha[k] = part[k] / total[k] d ln factor).  One lane per
 // frequency, ascending k, every operation one correctly rounded fp64 operation; a zero in total gives what IEEE gives.

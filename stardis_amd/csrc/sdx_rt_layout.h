@@ -140,6 +140,36 @@ struct RtLambda {
     __host__ __device__ constexpr size_t bytes() const { return (size_t)wave_doubles() * sizeof(double); }
 };
 
+// k_lambda_adjoint<kSolve> (the transposed mean-intensity operator, its opacity derivative, and the adjoint scattering solve).  Per
+// wave: RtColumns' pairs [gpw][col] as double2 (the source column S the derivative is taken at, sqrt(alpha)); then eight columns
+// [gpw][col] each: z (what the transposed operator is applied to; in the solve albedo y), the result Lambda^T z, the iterate y, the
+// cotangent, the albedo, the diagonal (the solve turns it into 1 / (1 - albedo clamp(L))), the mean intensity J of S, and the opacity
+// derivative G; then k_response's stash of the forward sweep, the value entering every step per ray [col - 1][gpw * G], reused by the
+// second sweep; then the terms of a batch of rows [kRtBatch][gpw][G], which also serve the maxima of the stopping rule ([2][gpw][G]).
+// One wave's share at one frequency: ((n_theta + 10) n_depth + 3 n_theta) doubles.  bytes() is ONE wave's share; waves() and blocks()
+// are the launch: as many shares as 64 KB hold, at most kRtWaves.
+struct RtLambdaAdjoint {
+    int gpw, col, G;
+    __host__ __device__ constexpr RtLambdaAdjoint(int G_, int n_depth, int gpw_) : gpw(gpw_), col(n_depth), G(G_) {}
+    __host__ __device__ constexpr int pairs() const { return 0; }
+    __host__ __device__ constexpr int slots() const { return gpw * G; }  // rays of a wave
+    __host__ __device__ constexpr int column(int n) const { return (2 + n) * gpw * col; }
+    __host__ __device__ constexpr int z() const { return column(0); }
+    __host__ __device__ constexpr int result() const { return column(1); }
+    __host__ __device__ constexpr int iterate() const { return column(2); }
+    __host__ __device__ constexpr int cotangent() const { return column(3); }
+    __host__ __device__ constexpr int albedo() const { return column(4); }
+    __host__ __device__ constexpr int diag() const { return column(5); }
+    __host__ __device__ constexpr int mean() const { return column(6); }
+    __host__ __device__ constexpr int gradient() const { return column(7); }
+    __host__ __device__ constexpr int stash() const { return column(8); }
+    __host__ __device__ constexpr int terms() const { return stash() + (col - 1) * slots(); }
+    __host__ __device__ constexpr int wave_doubles() const { return (terms() + kRtBatch * slots() + 1) & ~1; }
+    __host__ __device__ constexpr size_t bytes() const { return (size_t)wave_doubles() * sizeof(double); }
+    int waves() const { return kLdsBytes / bytes() >= (size_t)kRtWaves ? kRtWaves : (int)(kLdsBytes / bytes()); }
+    unsigned blocks(long long n_nu) const { return (unsigned)((n_nu + (long long)gpw * waves() - 1) / ((long long)gpw * waves())); }
+};
+
 // ---- the host's choice of a launch shape ----------------------------------------------------------------------------------------
 // A model whose column alone is larger than LDS fits no layout; asked first, it also keeps every int above far from overflow.
 constexpr int kRtMaxDepth = (int)(kLdsBytes / sizeof(double));
@@ -222,6 +252,13 @@ constexpr bool lambda_ok(int G, int n_depth, int gpw)
            l.albedo() + gpw * n_depth <= l.diag() && l.diag() + gpw * n_depth <= l.mean() && l.mean() + gpw * n_depth <= l.terms() &&
            l.terms() + kRtBatch * gpw * G <= l.wave_doubles() && 2 * gpw * G <= kRtBatch * gpw * G && even(l.pairs()) && even(l.wave_doubles());
 }
+constexpr bool lambda_adjoint_ok(int G, int n_depth, int gpw)
+{
+    const RtLambdaAdjoint l(G, n_depth, gpw);
+    return gpw * G <= 64 && l.pairs() + 2 * gpw * n_depth <= l.z() && l.gradient() + gpw * n_depth <= l.stash() &&
+           l.stash() + (n_depth - 1) * l.slots() <= l.terms() && l.terms() + kRtBatch * l.slots() <= l.wave_doubles() && 2 * l.slots() <= kRtBatch * l.slots() &&
+           even(l.pairs()) && even(l.wave_doubles());
+}
 // the benchmark's shape (four waves of it fit a workgroup); odd depth and angle counts, both ends of the angle range; the deepest
 // model at 20 angles and at one
 static_assert(lambda_ok(20, 56, 3) && 4 * RtLambda(20, 56, 3).bytes() <= kLdsBytes, "RtLambda: four waves of 56 depth points at 20 angles must fit");
@@ -242,4 +279,9 @@ static_assert(RtSegments(8, 7, 1, 57).doubles() == RtSegments(8, 7, 1, 57).stagi
 // the benchmark's shape (56 depth points, 20 angles: three frequencies per wave) fits; odd ray counts, both ends of the angle range
 static_assert(response_ok(20, 56, 3) && RtResponse(20, 56, 3).bytes() <= kLdsBytes, "RtResponse: 56 depth points at 20 angles must fit");
 static_assert(response_ok(1, 2, 64) && response_ok(5, 3, 12) && response_ok(7, 9, 9) && response_ok(64, 40, 1) && response_ok(3, 117, 21), "RtResponse");
+// the benchmark's shape fits at three frequencies per wave (one wave per workgroup); odd counts, both ends of the angle range; the
+// deepest model at 20 angles
+static_assert(lambda_adjoint_ok(20, 56, 3) && RtLambdaAdjoint(20, 56, 3).bytes() <= kLdsBytes, "RtLambdaAdjoint: 56 depth points at 20 angles must fit");
+static_assert(lambda_adjoint_ok(1, 2, 64) && lambda_adjoint_ok(1, 3, 64) && lambda_adjoint_ok(3, 3, 21) && lambda_adjoint_ok(7, 9, 9) && lambda_adjoint_ok(64, 40, 1), "RtLambdaAdjoint");
+static_assert(RtLambdaAdjoint(20, 271, 1).bytes() <= kLdsBytes && RtLambdaAdjoint(20, 272, 1).bytes() > kLdsBytes, "RtLambdaAdjoint");
 }  // namespace rt_layout_checks

@@ -2618,6 +2618,149 @@ int sdx_scatter_source_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta,
     return io.finish();
 }
 
+// ---- the adjoint of the mean intensity and of the scattering solve (k_lambda_adjoint) ---------------------------------------
+// As above, everything is checked before anything is enqueued, also for an empty grid.
+namespace {
+// the refusals both entries share, under the entry's name; -> the frequencies per wave of the launch
+int lambda_adjoint_shape(sdx_ctx* ctx, const char* what, int n_depth, int64_t n_nu, int n_theta, int* gpw)
+{
+    auto refuse = [&](const char* why) { return fail(SDX_ERR_ARG, std::string(what) + ": " + why); };
+    if (!(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0)) return refuse("need n_depth >= 2, n_theta > 0");
+    if (ctx->mixed_precision) return refuse("not with mixed_precision = 1 (the mean intensity is that of the fp64 formal solution)");
+    if (n_theta > 64) return refuse("more than 64 angles are not supported (all angles are traced in one launch)");
+    *gpw = rt_fit_gpw<RtLambdaAdjoint>(n_theta, n_depth);
+    if (*gpw <= 0) return refuse("models this deep are not served (the columns and stashed values of one frequency do not fit LDS)");
+    return SDX_OK;
+}
+}  // namespace
+
+int sdx_mean_intensity_adjoint_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
+                                   const double* ray_dist, const double* mean_weights, const double* alphas, int64_t ald, const double* z, int64_t z_ld,
+                                   const double* source, int64_t source_ld, double* Lt, int64_t Lt_ld, double* G, int64_t G_ld)
+{
+    int gpw = 0, rc;
+    if ((rc = lambda_adjoint_shape(ctx, "mean_intensity_adjoint", n_depth, n_nu, n_theta, &gpw))) return rc;
+    if (n_nu == 0) return SDX_OK;
+    REQUIRE(Lt || G, "mean_intensity_adjoint: no output requested");
+    REQUIRE(nus && ray_dist && mean_weights && alphas && ald >= n_nu && z && z_ld >= n_nu, "mean_intensity_adjoint: null pointer or a leading dimension of an input below n_nu");
+    REQUIRE((!Lt || Lt_ld >= n_nu) && (!G || G_ld >= n_nu), "mean_intensity_adjoint: leading dimension of an output below n_nu");
+    REQUIRE(source ? source_ld >= n_nu : temps != nullptr, "mean_intensity_adjoint: bad source plane (source_ld < n_nu), or neither a source plane nor temperatures");
+    const RtLambdaAdjoint lay(n_theta, n_depth, gpw);
+    const int waves = lay.waves();
+    {
+        LaunchScope ls(ctx, "k_lambda_adjoint", "k_lambda_adjoint<false>");
+        hipLaunchKernelGGL(k_lambda_adjoint<false>, dim3(lay.blocks(n_nu)), dim3(64 * waves), waves * lay.bytes(), ctx->stream, n_depth, n_nu, n_theta, n_theta,
+                           n_theta, nus, temps, ray_dist, mean_weights, alphas, ald, source, source_ld, z, z_ld, Lt, Lt_ld, G, G_ld, gpw, waves, LambdaAdjointSolve{});
+    }
+    return check_launch("k_lambda_adjoint");
+}
+
+int sdx_scatter_response_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                             const double* mean_weights, const double* alphas, int64_t ald, const double* alpha_scatter, int64_t scatter_ld,
+                             const double* thermal, int64_t thermal_ld, const double* S, int64_t S_ld, const double* cotangent, int64_t cotangent_ld,
+                             const double* direct, int64_t direct_ld, double tol, int max_iter, double* y, int64_t y_ld, double* R_thermal,
+                             int64_t R_thermal_ld, double* R_absorption, int64_t R_absorption_ld, double* R_scatter, int64_t R_scatter_ld,
+                             int* iterations, int* status, double* change)
+{
+    int gpw = 0, rc;
+    if ((rc = lambda_adjoint_shape(ctx, "scatter_response", n_depth, n_nu, n_theta, &gpw))) return rc;
+    REQUIRE(tol >= 0.0 && max_iter >= 1, "scatter_response: need tol >= 0 (not NaN) and max_iter >= 1");
+    if (n_nu == 0) return SDX_OK;
+    REQUIRE(y || R_thermal || R_absorption || R_scatter, "scatter_response: no output requested");
+    REQUIRE(nus && ray_dist && mean_weights && alphas && ald >= n_nu && alpha_scatter && S && cotangent, "scatter_response: null pointer or alpha_ld below n_nu");
+    REQUIRE((scatter_ld == 0 || scatter_ld >= n_nu) && S_ld >= n_nu && cotangent_ld >= n_nu && (!direct || direct_ld >= n_nu),
+            "scatter_response: a leading dimension of an input below n_nu (scatter_ld: 0 or >= n_nu)");
+    REQUIRE((!y || y_ld >= n_nu) && (!R_thermal || R_thermal_ld >= n_nu) && (!R_absorption || R_absorption_ld >= n_nu) && (!R_scatter || R_scatter_ld >= n_nu),
+            "scatter_response: leading dimension of an output below n_nu");
+    REQUIRE(thermal ? thermal_ld >= n_nu : temps != nullptr, "scatter_response: bad thermal plane (thermal_ld < n_nu), or neither a thermal plane nor temperatures");
+    const RtLambdaAdjoint lay(n_theta, n_depth, gpw);
+    const int waves = lay.waves();
+    {
+        LaunchScope ls(ctx, "k_lambda_adjoint", "k_lambda_adjoint<true>");
+        hipLaunchKernelGGL(k_lambda_adjoint<true>, dim3(lay.blocks(n_nu)), dim3(64 * waves), waves * lay.bytes(), ctx->stream, n_depth, n_nu, n_theta, n_theta,
+                           n_theta, nus, temps, ray_dist, mean_weights, alphas, ald, S, S_ld, (const double*)nullptr, (int64_t)0, (double*)nullptr, (int64_t)0,
+                           (double*)nullptr, (int64_t)0, gpw, waves,
+                           LambdaAdjointSolve{alpha_scatter, scatter_ld, thermal, thermal_ld, cotangent, cotangent_ld, direct, direct_ld, tol, max_iter, y, y_ld,
+                                              R_thermal, R_thermal_ld, R_absorption, R_absorption_ld, R_scatter, R_scatter_ld, iterations, status, change});
+    }
+    return check_launch("k_lambda_adjoint");
+}
+
+int sdx_mean_intensity_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
+                                   const double* ray_dist, const double* mean_weights, const double* alphas, const double* z, const double* source,
+                                   double* Lt, double* G)
+{
+    int rc;
+    if ((rc = sdx_mean_intensity_adjoint_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0)) ||
+        n_nu == 0)
+        return rc;  // refusals before any copy
+    REQUIRE(n_nu > 0 && nus && temps && ray_dist && mean_weights && alphas && z, "mean_intensity_adjoint: null pointer");
+    REQUIRE(Lt || G, "mean_intensity_adjoint: no output requested");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
+    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_z, *d_s;
+    double *d_lt, *d_g;
+    HostPlan plan;
+    plan.in(nus, (size_t)n_nu * f8, &d_nus);
+    plan.in(temps, (size_t)n_depth * f8, &d_t);
+    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
+    plan.in(mean_weights, (size_t)n_theta * f8, &d_w);
+    plan.in(alphas, plane, &d_a);
+    plan.in(z, plane, &d_z);
+    plan.in(source, plane, &d_s);
+    plan.out(Lt, plane, &d_lt);
+    plan.out(G, plane, &d_g);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_mean_intensity_adjoint_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_z, n_nu, d_s, n_nu, d_lt, n_nu, d_g, n_nu))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+int sdx_scatter_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                             const double* mean_weights, const double* alphas, const double* alpha_scatter, int scatter_per_frequency,
+                             const double* thermal, const double* S, const double* cotangent, const double* direct, double tol, int max_iter, double* y,
+                             double* R_thermal, double* R_absorption, double* R_scatter, int* iterations, int* status, double* change)
+{
+    int rc;
+    if ((rc = sdx_scatter_response_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0,
+                                       nullptr, 0, tol, max_iter, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr)) ||
+        n_nu == 0)
+        return rc;  // refusals before any copy
+    REQUIRE(n_nu > 0 && nus && temps && ray_dist && mean_weights && alphas && alpha_scatter && S && cotangent, "scatter_response: null pointer");
+    REQUIRE(y || R_thermal || R_absorption || R_scatter, "scatter_response: no output requested");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
+    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_sc, *d_b, *d_s, *d_c, *d_d;
+    double *d_y, *d_rt, *d_ra, *d_rs, *d_ch;
+    int *d_it, *d_st;
+    HostPlan plan;
+    plan.in(nus, (size_t)n_nu * f8, &d_nus);
+    plan.in(temps, (size_t)n_depth * f8, &d_t);
+    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
+    plan.in(mean_weights, (size_t)n_theta * f8, &d_w);
+    plan.in(alphas, plane, &d_a);
+    plan.in(alpha_scatter, scatter_per_frequency ? plane : (size_t)n_depth * f8, &d_sc);
+    plan.in(thermal, plane, &d_b);
+    plan.in(S, plane, &d_s);
+    plan.in(cotangent, plane, &d_c);
+    plan.in(direct, plane, &d_d);
+    plan.out(y, plane, &d_y);
+    plan.out(R_thermal, plane, &d_rt);
+    plan.out(R_absorption, plane, &d_ra);
+    plan.out(R_scatter, plane, &d_rs);
+    plan.out(iterations, (size_t)n_nu * sizeof(int), &d_it);
+    plan.out(status, (size_t)n_nu * sizeof(int), &d_st);
+    plan.out(change, (size_t)n_nu * f8, &d_ch);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_scatter_response_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_sc, scatter_per_frequency ? n_nu : 0, d_b, n_nu, d_s, n_nu,
+                                       d_c, n_nu, d_d, n_nu, tol, max_iter, d_y, n_nu, d_rt, n_nu, d_ra, n_nu, d_rs, n_nu, d_it, d_st, d_ch)))
+        return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
 // ---- per-line flux sensitivities (k_response_weight, k_line_adjoint) --------------------------------------------------------
 int sdx_response_weight_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* R_alpha, int64_t R_ld, const double* total, int64_t total_ld,
                             const double* nu_weight, double* weight, int64_t weight_ld)

@@ -96,7 +96,12 @@ class SpectralSynthesizer:
         the total — and traces that source function (sdx_raytrace_source_dev) into a flux buffer of its own: `scattering_source`,
         `scattering_mean_intensity`, `scattering_flux`, `scattering_iterations`, `scattering_status`.  Needs continuum= (the electron
         densities); plane-parallel, fp64, at most 64 angles.  F_nu, the response functions and everything else stay the LTE ones.  Both
-        launches are part of whatever capture() records.  Off, the synthesizer has no such buffer and the step is unchanged."""
+        launches are part of whatever capture() records.  Off, the synthesizer has no such buffer and the step is unchanged.
+        With keep_response as well, the step also forms the derivatives of scattering_flux: sdx_response_dev at source = scattering_source
+        into buffers of its own, then the adjoint solve (sdx_scatter_response_dev) — `scattering_response_opacity` (for added true
+        absorption), `scattering_response_thermal`, `scattering_response_scatter`, `scattering_response_iterations`,
+        `scattering_response_status`; flux_derivative(..., scattering=True) and line_sensitivities(..., scattering=True) use the first
+        where they otherwise use response_opacity.  Without both options no buffer and no launch is added."""
         self.ctx = ctx or default_context()
         c = self.ctx
         nus = np.ascontiguousarray(nus, dtype=np.float64)
@@ -171,6 +176,10 @@ class SpectralSynthesizer:
             c.call("sdx_scatter_source_dev", self.n_depth, 0, self.n_theta, None, None, None, None, None, 0, None, 0, None, 0,
                    self.scattering["tol"], self.scattering["max_iter"], None, 0, None, 0, None, None, None)
             keep_total = True
+        self._scattering_response = self.scattering is not None and self.keep_response
+        if self._scattering_response:
+            c.call("sdx_scatter_response_dev", self.n_depth, 0, self.n_theta, None, None, None, None, None, 0, None, 0, None, 0, None, 0, None, 0, None, 0,
+                   self.scattering["tol"], self.scattering["max_iter"], None, 0, None, 0, None, 0, None, 0, None, None, None)
         self.d_line = c.empty((self.n_depth, self.count)) if keep_line else None
         self.d_total = c.empty((self.n_depth, self.count)) if keep_total else None
         self._flux_tensor = flux_out
@@ -191,6 +200,11 @@ class SpectralSynthesizer:
             self.d_Ssc, self.d_Jsc, self.d_Fsc = c.empty(plane), c.empty(plane), c.empty(plane)
             self.d_sc_iterations, self.d_sc_status = c.empty((self.count,), np.int32), c.empty((self.count,), np.int32)
             self.d_sc_change = c.empty((self.count,))
+            if self._scattering_response:
+                # the flux's direct part and cotangent at source = S, then the three response planes of the adjoint solve
+                self.d_sc_direct, self.d_sc_cotangent = c.empty(plane), c.empty(plane)
+                self.d_sc_Ra, self.d_sc_Rt, self.d_sc_Rs = c.empty(plane), c.empty(plane), c.empty(plane)
+                self.d_scr_iterations, self.d_scr_status = c.empty((self.count,), np.int32), c.empty((self.count,), np.int32)
         self.instrument = instrument
         if instrument is not None:
             self.lambdas = K.nu_to_angstrom(nus)
@@ -404,6 +418,14 @@ class SpectralSynthesizer:
                self.d_sc_iterations.ptr, self.d_sc_status.ptr, self.d_sc_change.ptr)
         c.call("sdx_raytrace_source_dev", self.n_depth, cnt, self.n_theta, nus, self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, self.d_total.ptr, cnt,
                self.d_Ssc.ptr, cnt, self.d_Fsc.ptr, cnt, None, 0, 0, 1.0)
+        if self._scattering_response:
+            # the derivative of that flux: the response functions at source = S are its direct part and cotangent, the adjoint solve the rest
+            c.call("sdx_response_dev", self.n_depth, cnt, self.n_theta, nus, self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, self.d_total.ptr, cnt,
+                   self.d_Ssc.ptr, cnt, self.d_sc_direct.ptr, cnt, self.d_sc_cotangent.ptr, cnt)
+            c.call("sdx_scatter_response_dev", self.n_depth, cnt, self.n_theta, nus, self.d_t.ptr, self.d_ray.ptr, self.d_mean_w.ptr, self.d_total.ptr, cnt,
+                   self.d_thomson.ptr, 0, None, 0, self.d_Ssc.ptr, cnt, self.d_sc_cotangent.ptr, cnt, self.d_sc_direct.ptr, cnt, self.scattering["tol"],
+                   self.scattering["max_iter"], None, 0, self.d_sc_Rt.ptr, cnt, self.d_sc_Ra.ptr, cnt, self.d_sc_Rs.ptr, cnt, self.d_scr_iterations.ptr,
+                   self.d_scr_status.ptr, None)
 
     def _enqueue_synthesis(self):
         """The step, whatever its configuration: one sdx_synthesis_options, one sdx_synthesize_opt_dev call.  A line list of scalars
@@ -597,13 +619,49 @@ class SpectralSynthesizer:
         self._require_scattering()
         return self.d_sc_status.numpy()
 
-    def flux_derivative(self, alpha_part):
+    def _require_scattering_response(self):
+        if self.scattering is None or not self.keep_response:
+            raise RuntimeError("no scattering responses were formed: construct the synthesizer with scattering=True and keep_response=True")
+
+    @property
+    def scattering_response_opacity(self):
+        """-> DeviceArray (N_d, count): d scattering_flux / d ln alpha[k] for added TRUE ABSORPTION at fixed Thomson opacity and Planck
+        function (R_absorption of sdx_scatter_response_dev): what response_opacity is to F_nu."""
+        self._require_scattering_response()
+        return self.d_sc_Ra
+
+    @property
+    def scattering_response_thermal(self):
+        """-> DeviceArray (N_d, count): d scattering_flux / dB[k]."""
+        self._require_scattering_response()
+        return self.d_sc_Rt
+
+    @property
+    def scattering_response_scatter(self):
+        """-> DeviceArray (N_d, count): d scattering_flux / d ln alpha_scatter[k] at fixed absorption."""
+        self._require_scattering_response()
+        return self.d_sc_Rs
+
+    @property
+    def scattering_response_iterations(self):
+        """-> (count,) int32 numpy array: the iterations the adjoint solve of every column of the last step took."""
+        self._require_scattering_response()
+        return self.d_scr_iterations.numpy()
+
+    @property
+    def scattering_response_status(self):
+        """-> (count,) int32 numpy array: as scattering_status, of the adjoint solve."""
+        self._require_scattering_response()
+        return self.d_scr_status.numpy()
+
+    def flux_derivative(self, alpha_part, scattering=False):
         """-> DeviceArray (count,): sum_k response_opacity[k] alpha_part[k] / total_alphas[k] (sdx_response_project_dev), the derivative
         of the emergent flux with respect to the logarithm of a scale factor on the part alpha_part (N_d, count; host array,
         DeviceArray or CUDA tensor) of the last step's opacity — the line opacity of one species: dF/d ln(abundance) at fixed ionisation
-        and continuum."""
+        and continuum.  scattering=True: of scattering_flux, with scattering_response_opacity in response_opacity's place (the part is
+        true absorption)."""
         c = self.ctx
-        d_R = self.response_opacity
+        d_R = self.scattering_response_opacity if scattering else self.response_opacity
         d_part = self._device_vector("alpha_part", alpha_part, (self.n_depth, self.count))
         out = c.empty((self.count,))
         c.call("sdx_response_project_dev", self.n_depth, self.count, d_R.ptr, self.count, ptr_of(d_part), self.count, self.d_total.ptr,
@@ -667,7 +725,7 @@ class SpectralSynthesizer:
         per = self.line_sensitivities(weights, per_depth=True, wrt="doppler").numpy()
         return float(np.sum(per * self._microturbulence_direction(xi)))
 
-    def line_sensitivities(self, weights=None, per_depth=False, wrt="strength"):
+    def line_sensitivities(self, weights=None, per_depth=False, wrt="strength", scattering=False):
         """-> DeviceArray (n_lines,), or (n_lines, N_d) with per_depth=True: for every line l of the list, in the order the caller passed
         the lines, the derivative of  sum_i weights[i] F_nu_i[-1]  over this synthesizer's columns with respect to ln(strength of line
         l) — ln gf, or the abundance of a species that has this line alone — at FIXED WINDOWS, from the last step: the weight plane
@@ -689,14 +747,19 @@ class SpectralSynthesizer:
         wrt: "strength" (the above), or the derivative of the same sum with respect to a number that sets the line's SHAPE, at fixed
         windows and fixed Humlicek regions (sdx_line_param_adjoint_dev): "damping" — ln gamma_l (an enhancement factor on the damping
         constant, the same at every depth), "doppler" — ln doppler_width_l, "centre" — the rest frequency nu_l, per Hz.  A tuple of
-        them returns a dict of arrays, the shape parameters from ONE pass over the terms."""
+        them returns a dict of arrays, the shape parameters from ONE pass over the terms.
+        scattering=True: the derivatives of the same sum over scattering_flux — the weight plane is formed from
+        scattering_response_opacity, everything behind it is the same (needs scattering=True at construction as well)."""
         names, single = self._wrt_names(wrt)
         self._require_response()
+        if scattering:
+            self._require_scattering_response()
         c = self.ctx
         d_w = None if weights is None else self._device_vector("weights", weights, self.count, "column of the synthesizer")
         cnt = self.count
         d_W = c.empty((self.n_depth, cnt))
-        c.call("sdx_response_weight_dev", self.n_depth, cnt, self.d_Ra.ptr, cnt, self.d_total.ptr, cnt, ptr_of(d_w), d_W.ptr, cnt)
+        d_R = self.d_sc_Ra if scattering else self.d_Ra
+        c.call("sdx_response_weight_dev", self.n_depth, cnt, d_R.ptr, cnt, self.d_total.ptr, cnt, ptr_of(d_w), d_W.ptr, cnt)
         ln_ptr, d_dw, d_g, d_a = self._tables_in_caller_order()
         shape = (self.n_lines, self.n_depth) if per_depth else (self.n_lines,)
         res = {}

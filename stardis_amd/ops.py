@@ -724,6 +724,74 @@ def scatter_source(tracing_nus, temperatures, ray_distances, mean_weights, total
     return out
 
 
+def mean_intensity_adjoint(tracing_nus, temperatures, ray_distances, mean_weights, total_alphas, z, ctx=None, source=None, device=False,
+                           want_Lt=True, want_G=True):
+    """The transpose of mean_intensity's operator (sdx_mean_intensity_adjoint_dev) -> (Lt, G), each (N_d, N_nu): Lt = Lambda^T z for
+    the plane z, and G[k] = d(z^T J[S]) / d ln alpha[k] at the fixed source plane S (default: Planck).  Arguments as mean_intensity;
+    want_Lt / want_G = False: that output is not formed (None in its place).  device=True: DeviceArrays instead of host arrays."""
+    nus, t, rd, m, planes = _lambda_inputs("mean_intensity_adjoint", tracing_nus, temperatures, ray_distances, mean_weights, total_alphas,
+                                           dict(z=z, source=source))
+    if planes["z"] is None:
+        raise ValueError("mean_intensity_adjoint: z is required")
+    if not (want_Lt or want_G):
+        raise ValueError("mean_intensity_adjoint: no output requested")
+    ctx = ctx or default_context()
+    d_alpha = _dev(ctx, total_alphas)
+    d_z = _dev(ctx, planes["z"])
+    d_S = _dev(ctx, planes["source"])
+    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd), ctx.upload(m)]
+    d_Lt = ctx.empty((t.size, nus.size)) if want_Lt else None
+    d_G = ctx.empty((t.size, nus.size)) if want_G else None
+    ctx.call("sdx_mean_intensity_adjoint_dev", t.size, nus.size, m.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, ptr_of(d_alpha), nus.size,
+             ptr_of(d_z), nus.size, ptr_of(d_S), nus.size, ptr_of(d_Lt), nus.size, ptr_of(d_G), nus.size)
+    if device:
+        return d_Lt, d_G
+    return (d_Lt.numpy() if want_Lt else None), (d_G.numpy() if want_G else None)
+
+
+def scatter_response(tracing_nus, temperatures, ray_distances, mean_weights, total_alphas, alpha_scatter, S, cotangent, ctx=None, direct=None,
+                     thermal=None, tol=1e-12, max_iter=2000, device=False, want_y=True):
+    """Derivatives of a functional Phi of the scattering solution (sdx_scatter_response_dev): the adjoint solve y = c + Lambda^T (W y)
+    by scatter_source's own iteration, transposed, and from it the responses.  S: the source plane of scatter_source; cotangent:
+    dPhi/dS; direct: dPhi/d ln alpha at fixed S (default 0) — for the emergent flux, R_source and R_alpha of response(source=S).
+    alpha_scatter, thermal, tol, max_iter as for scatter_source.  -> namespace(y, R_thermal, R_absorption, R_scatter, iterations,
+    status, change): (N_d, N_nu) planes — dPhi/dB, dPhi/d ln alpha for added true absorption (what takes R_alpha's place), dPhi/d ln
+    alpha_scatter — and per column the iteration count and status (int32) and the last change.  device=True: DeviceArrays."""
+    import types
+
+    nus, t, rd, m, planes = _lambda_inputs("scatter_response", tracing_nus, temperatures, ray_distances, mean_weights, total_alphas,
+                                           dict(S=S, cotangent=cotangent, direct=direct, thermal=thermal))
+    if planes["S"] is None or planes["cotangent"] is None:
+        raise ValueError("scatter_response: S and cotangent are required")
+    on_device = isinstance(alpha_scatter, DeviceArray) or hasattr(alpha_scatter, "data_ptr")
+    sc = alpha_scatter if on_device else _host(alpha_scatter)
+    sc_shape = tuple(int(v) for v in sc.shape)
+    if sc_shape not in ((t.size,), (t.size, nus.size)):
+        raise ValueError(f"alpha_scatter must have shape {(t.size,)} or {(t.size, nus.size)}, got {sc_shape}")
+    if not float(tol) >= 0.0:
+        raise ValueError(f"scatter_response: tol must be >= 0, got {tol}")
+    if int(max_iter) < 1:
+        raise ValueError(f"scatter_response: max_iter must be >= 1, got {max_iter}")
+    ctx = ctx or default_context()
+    d_alpha = _dev(ctx, total_alphas)
+    d_sc = _dev(ctx, sc)
+    d_in = {name: _dev(ctx, planes[name]) for name in ("thermal", "S", "cotangent", "direct")}
+    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd), ctx.upload(m)]
+    plane = lambda: ctx.empty((t.size, nus.size))  # noqa: E731
+    out = types.SimpleNamespace(y=plane() if want_y else None, R_thermal=plane(), R_absorption=plane(), R_scatter=plane(),
+                                iterations=ctx.empty((nus.size,), np.int32), status=ctx.empty((nus.size,), np.int32), change=ctx.empty((nus.size,)))
+    ctx.call("sdx_scatter_response_dev", t.size, nus.size, m.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, ptr_of(d_alpha), nus.size,
+             ptr_of(d_sc), nus.size if len(sc_shape) == 2 else 0, ptr_of(d_in["thermal"]), nus.size, ptr_of(d_in["S"]), nus.size,
+             ptr_of(d_in["cotangent"]), nus.size, ptr_of(d_in["direct"]), nus.size, float(tol), int(max_iter), ptr_of(out.y), nus.size,
+             out.R_thermal.ptr, nus.size, out.R_absorption.ptr, nus.size, out.R_scatter.ptr, nus.size, out.iterations.ptr, out.status.ptr,
+             out.change.ptr)
+    if not device:
+        for name in ("y", "R_thermal", "R_absorption", "R_scatter", "iterations", "status", "change"):
+            value = getattr(out, name)
+            setattr(out, name, None if value is None else value.numpy())
+    return out
+
+
 def formation_mean(contribution, x, ctx=None, device=False):
     """Formation mean of a per-depth quantity x (N_d) under a contribution function (N_d, N_nu; host or device array):
     (sum_{k>=1} C[k] m_k) / (sum_{k>=1} C[k]), m_k = (x[k-1] + x[k]) / 2 (sdx_formation_mean_dev) -> (N_nu,)."""

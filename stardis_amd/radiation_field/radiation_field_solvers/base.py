@@ -181,6 +181,17 @@ def mean_intensity(stellar_model, stellar_radiation_field):
     return ops.mean_intensity(*args, ctx=ctx, source=_source_plane(getattr(field, "source_function", None), field.frequencies, stellar_model.temperatures))
 
 
+def _scatter_plane(field, shape):
+    """the field's own Rayleigh + Thomson entries as one plane, summed in the order of the total"""
+    entries = field.opacities.opacities_dict
+    scatter = np.zeros(shape)
+    for key in ("alpha_rayleigh", "alpha_electron"):  # (the order of the total: ... + rayleigh) + electron)
+        if key not in entries:
+            raise ValueError(f"the field's opacities carry no {key}: calc_alphas has not run")
+        scatter = scatter + np.broadcast_to(np.asarray(plain(entries[key]), dtype=np.float64), shape)
+    return scatter
+
+
 def scattering_source(stellar_model, stellar_radiation_field, tol=1e-12, max_iter=2000):
     """Source function with coherent continuum scattering, S = (1 - albedo) B + albedo J[S] (sdx_scatter_source_dev) -> namespace(S, J,
     iterations, status, change) as ops.scatter_source returns it.  The scattering opacity is the field's own Rayleigh + Thomson entries
@@ -189,15 +200,26 @@ def scattering_source(stellar_model, stellar_radiation_field, tol=1e-12, max_ite
     is traced with scattering.  The reference has no counterpart.  A spherical model raises NotImplementedError."""
     field = stellar_radiation_field
     args, ctx = _lambda_arguments(stellar_model, field)
-    entries = field.opacities.opacities_dict
-    shape = (np.size(args[1]), np.size(plain(field.frequencies)))
-    scatter = np.zeros(shape)
-    for key in ("alpha_rayleigh", "alpha_electron"):  # (the order of the total: ... + rayleigh) + electron)
-        if key not in entries:
-            raise ValueError(f"the field's opacities carry no {key}: calc_alphas has not run")
-        scatter = scatter + np.broadcast_to(np.asarray(plain(entries[key]), dtype=np.float64), shape)
+    scatter = _scatter_plane(field, (np.size(args[1]), np.size(plain(field.frequencies))))
     return ops.scatter_source(*args, scatter, ctx=ctx, tol=tol, max_iter=max_iter,
                               thermal=_source_plane(getattr(field, "source_function", None), field.frequencies, stellar_model.temperatures))
+
+
+def scattering_response(stellar_model, stellar_radiation_field, tol=1e-12, max_iter=2000):
+    """Response functions of the emergent flux WITH continuum scattering (sdx_scatter_response_dev): solves for the scattering source
+    function S as scattering_source() does, takes the flux's cotangent and direct part from the response functions at source = S, and
+    solves the adjoint problem -> namespace(y, R_thermal, R_absorption, R_scatter, iterations, status, change) as ops.scatter_response
+    returns it, with S and the forward solve's own `source_iterations` and `source_status` beside them.  R_absorption takes the place
+    of response_functions()'s R_alpha once scattering is on.  A spherical model raises NotImplementedError."""
+    field = stellar_radiation_field
+    args, ctx = _lambda_arguments(stellar_model, field)
+    scatter = _scatter_plane(field, (np.size(args[1]), np.size(plain(field.frequencies))))
+    thermal = _source_plane(getattr(field, "source_function", None), field.frequencies, stellar_model.temperatures)
+    forward = ops.scatter_source(*args, scatter, ctx=ctx, tol=tol, max_iter=max_iter, thermal=thermal, want_J=False)
+    R_alpha, R_source = ops.response(args[0], args[1], args[2], field.I_nus_weights, args[4], ctx=ctx, source=forward.S)
+    out = ops.scatter_response(*args, scatter, forward.S, R_source, ctx=ctx, direct=R_alpha, thermal=thermal, tol=tol, max_iter=max_iter)
+    out.S, out.source_iterations, out.source_status = forward.S, forward.iterations, forward.status
+    return out
 
 
 def formation_mean(stellar_radiation_field, x):
