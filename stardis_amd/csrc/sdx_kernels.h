@@ -3949,7 +3949,11 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
 //             under their latency, and a point's (source, sqrt(alpha)) pair is ONE 16-byte LDS write.  The ray table goes to the waves
 //             in descending order, so that the waves without columns take its extra trip;
 //   replay    no test for the optional intensity output;
-//   flux      (gap, frequency) of a lane from the host's reciprocal of gpw.
+//   flux      (gap, frequency) of a lane from the host's reciprocal of gpw; at 20 angles (geo.fx_pairs) a lane reads its half of the
+//             angles as five 16-byte words, all in flight before the first add; the two lanes of a pair exchange their sums inside
+//             the quad; F's row stride is 32 bits.  The same adds in the same order.  (Unpredicated replay stores, the segment maps
+//             read ahead of the fold and the ray table loaded ahead of the staging were built and measured: nothing, or 0.3 us of 30
+//             each — profiles/EXPERIMENTS.md.)
 struct SegStepGeom {
     int gpw, g_recip;         // frequencies per workgroup 64 / n_theta; lane_recip(n_theta)
     int per;                  // 64 / n_theta: gaps of the ray table per wave and trip
@@ -3958,13 +3962,31 @@ struct SegStepGeom {
     int sp_off;               // doubles from the ray table to the (source, sqrt(alpha)) pairs: RtSegments::pairs_from_table()
     unsigned gpw_magic;       // small_div_magic(gpw)
     unsigned n_wg, per_xcd;   // as k_raytrace_seg
+    int fx_pairs;             // kStepFluxPairs where a half of the flux sum is that many aligned 16-byte reads and a wave's items fit
+                              // its lanes (seg_step_flux_pairs); 0: the general form
+    unsigned fld;             // the row stride of F (the host launches this kernel only where it fits 32 bits)
 };
+// The flux sum's 128-bit form: n_theta = 20 (two halves of ten angles: five 16-byte reads each).  Every run of a half then starts at
+// an even double — n_theta, the half and with them a gap's and a wave's share of the terms are even, and the flux terms start where
+// the ray table does (RtSegments::flux(): even) — and the 2 LMAX gpw (gap, frequency, half) items of a wave are at most its 64 lanes.
+constexpr int kStepFluxPairs = 5;
+inline int seg_step_flux_pairs(const RtSegments& s)
+{
+    const int half = (s.n_theta + 1) >> 1;
+    return s.n_theta % 4 == 0 && half == 2 * kStepFluxPairs && s.flux() % 2 == 0 && 2 * s.LMAX * s.gpw() <= 64 ? kStepFluxPairs : 0;
+}
+// lanes 2k and 2k + 1 exchange v (what __shfl_xor(v, 1) moves, as two DPP moves inside the quad instead of a trip through LDS)
+__device__ __forceinline__ double swap_lane_pairs(double v)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0xB1, 0xF, 0xF, true);  // quad_perm: [1, 0, 3, 2]
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0xB1, 0xF, 0xF, true);
+    return __hiloint2double(hi, lo);
+}
 template <int NS, int LMAX, int N_PLANES, bool KEEP_TOTAL>
 __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8 ? 6 : 4, 8))) void k_raytrace_seg_step(
     int n_depth, int64_t n_nu, int n_theta, int theta_stride, const double* __restrict__ nus, const double* __restrict__ temps,
     const double* __restrict__ ray_dist, const double* __restrict__ wts, const double* __restrict__ cont, int64_t cld,
-    const double* __restrict__ planes, int64_t pld, double* __restrict__ total_out, int64_t out_ld, double* __restrict__ F, int64_t fld,
-    SegStepGeom geo)
+    const double* __restrict__ planes, int64_t pld, double* __restrict__ total_out, int64_t out_ld, double* __restrict__ F, SegStepGeom geo)
 {
     extern __shared__ double smem[];
     const int lane = threadIdx.x & 63;
@@ -4090,17 +4112,40 @@ __global__ __launch_bounds__(64 * NS) __attribute__((amdgpu_waves_per_eu(NS >= 8
     }
     fx = sFx + seg * LMAX * gpw * G;
     wave_sync();
+    // the flux: lane p sums one half of the angles of (gap b, frequency gq), ascending; the halves meet in one add
+    if (geo.fx_pairs == kStepFluxPairs) {
+        // the 128-bit form: a half is kStepFluxPairs 16-byte reads, all in flight before the first add — the same adds —, and a wave's
+        // items fit its lanes.  4 kStepFluxPairs angles, hence kW frequencies per workgroup, are constants here: lane p's run starts
+        // (q n_theta + h n_theta / 2 =) p halves into the wave's terms
+        constexpr int kW = 64 / (4 * kStepFluxPairs);
+        if (lane < 2 * count * kW) {
+            const int h = lane & 1, q = lane >> 1;  // q = b * kW + gq
+            const int b = q / kW, gq = q - b * kW;
+            const double2* cc = (const double2*)(fx + lane * (2 * kStepFluxPairs));
+            double2 v[kStepFluxPairs];
+#pragma unroll
+            for (int t = 0; t < kStepFluxPairs; ++t) v[t] = cc[t];
+            double sum = 0.0;
+#pragma unroll
+            for (int t = 0; t < kStepFluxPairs; ++t) sum = add_rn(add_rn(sum, v[t].x), v[t].y);
+            const double other = swap_lane_pairs(sum);
+            const int64_t iq = i0 + gq;
+            if (h == 0 && iq < n_nu) F[(size_t)(unsigned)(g_lo + b + 1) * geo.fld + iq] = add_rn(sum, other);
+        }
+        return;
+    }
     const int half = (n_theta + 1) >> 1;
     for (int p = lane; p < 2 * count * gpw; p += 64) {
         const int h = p & 1, q = p >> 1;  // q = b * gpw + gq
         const int b = small_div(q, geo.gpw_magic), gq = q - b * gpw;
-        const double* cc = fx + q * G + (h ? half : 0);
-        const int cnt = h ? n_theta - half : half;
+        const double* cc = fx + q * G + h * half;
+        const int cnt = half - (h & n_theta & 1);  // (the second half of an odd count is one angle shorter)
         double sum = 0.0;
+#pragma unroll 1
         for (int t = 0; t < cnt; ++t) sum = add_rn(sum, cc[t]);
-        const double other = __shfl_xor(sum, 1);
+        const double other = swap_lane_pairs(sum);
         const int64_t iq = i0 + gq;
-        if (h == 0 && iq < n_nu) F[(size_t)(g_lo + b + 1) * fld + iq] = add_rn(sum, other);
+        if (h == 0 && iq < n_nu) F[(size_t)(unsigned)(g_lo + b + 1) * geo.fld + iq] = add_rn(sum, other);
     }
 }
 

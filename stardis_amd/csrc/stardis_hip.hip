@@ -2240,15 +2240,17 @@ static int raytrace_impl(sdx_ctx* ctx, const Grid& g, const Rays& rays, const Rt
             // of its own (k_raytrace_seg_step: the same bits); "segmented_raytrace" = 1 keeps the general kernel
             const int step_planes = ft.planes ? ft.n_planes : 0;
             const bool step_shape = segmented_mode(ctx) != 1 && ft.cont && !ft.source && ft.n_extra == 0 && !ft.line_out && !inus && F &&
-                                    (step_planes == 0 || step_planes == 2 || step_planes == 3);
+                                    (step_planes == 0 || step_planes == 2 || step_planes == 3) && fld <= (int64_t)UINT32_MAX;
             SegStepGeom geo{};
             geo.gpw = seg_gpw, geo.g_recip = lane_recip(nth), geo.per = 64 / nth, geo.L = seg.segment();
             geo.rstride = seg.rstride(), geo.sp_off = seg.pairs_from_table(), geo.gpw_magic = small_div_magic(seg_gpw);
             geo.n_wg = seg_wg, geo.per_xcd = seg_per_xcd;
+            geo.fx_pairs = seg_step_flux_pairs(seg);
             auto launch_step = [&](int planes_n, const double* planes, double* total_out, double* flux, int64_t flux_ld) {
+                geo.fld = (unsigned)flux_ld;  // (the caller has asked that it fits)
 #define SDX_STEP_LAUNCH(NP, KEEP)                                                                                                              \
     hipLaunchKernelGGL((k_raytrace_seg_step<8, 7, NP, KEEP>), dim3(seg_blocks), dim3(512), seg.bytes(), ctx->stream, n_depth, n_nu, nth, \
-                       n_theta, nus, temps, rd, w, ft.cont, ft.cld, planes, ft.pld, total_out, ft.out_ld, flux, flux_ld, geo)
+                       n_theta, nus, temps, rd, w, ft.cont, ft.cld, planes, ft.pld, total_out, ft.out_ld, flux, geo)
                 if (planes_n == 0) {
                     if (total_out) SDX_STEP_LAUNCH(0, true);
                     else SDX_STEP_LAUNCH(0, false);
@@ -2282,7 +2284,7 @@ static int raytrace_impl(sdx_ctx* ctx, const Grid& g, const Rays& rays, const Rt
                 // (DESIGN.md).  Removed.
                 FusedTotal fc{};
                 fc.cont = ft.cont, fc.cld = ft.cld, fc.source = ft.source, fc.sld = ft.sld;
-                if (segmented_mode(ctx) != 1 && !ft.source) {  // (this launch has the step kernel's shape whatever the first one had)
+                if (segmented_mode(ctx) != 1 && !ft.source && fcld <= (int64_t)UINT32_MAX) {  // (this launch has the step kernel's shape whatever the first one had)
                     LaunchScope ls(ctx, "k_raytrace", "k_raytrace_seg_step<8,7> (continuum)");
                     launch_step(0, nullptr, nullptr, Fc, fcld);
                 } else {
