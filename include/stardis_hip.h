@@ -379,6 +379,27 @@ int sdx_contribution_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
                          const double* temperature, const double* ray_dist, const double* theta_weights,
                          const double* total_alphas, const double* source, double* C);
 
+/* ---- emergent intensity of every ray: the surface row alone ------------------------------------
+ * I(theta, nu) at the surface, without the [n_depth][n_nu][n_theta] volume that I_nus costs: the walk of the plain formal-solution kernel
+ * (k_raytrace: columns of (S, sqrt(alpha)) staged per wave from a FINISHED total_alphas plane, the inward sweep of :141-198 first where
+ * inward != 0, the step of :200-266 per gap through the same device functions on the same operands in the same order) that keeps what a
+ * ray holds after the last gap.  I_out[theta][nu] is therefore row n_depth-1 of I_nus as sdx_raytrace_source_dev returns it from that
+ * kernel on the same inputs, bit for bit.  These are INTENSITIES: no theta weights and no photospheric correction are applied (the flux
+ * is sum_theta w_theta I_out[theta], in two ascending halves, times the correction of a spherical model).
+ * I_out is theta-major, [n_theta][I_ld] with I_ld >= n_nu: one angle's spectrum is contiguous, which is what sdx_disk_integrate_dev
+ * reads.  nus / total_alphas / source hold the n_nu columns being traced, as for sdx_contribution_dev; ray_dist [n_depth-1][n_theta];
+ * source = NULL: Planck, else a plane [n_depth][source_ld].
+ * Refused with SDX_ERR_ARG before anything is enqueued (also for n_nu = 0, so a caller can ask at set-up time): a context with
+ * mixed_precision = 1, n_theta > 64, a model whose columns do not fit 64 KB of LDS at one frequency per wave, I_out that is one of the
+ * inputs.  Device pointers, asynchronous, no allocation, capturable.  Stage name: "k_emergent_intensity". */
+int sdx_emergent_intensity_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                               const double* temperature, const double* ray_dist, const double* total_alphas, int64_t alpha_ld,
+                               const double* source, int64_t source_ld, int inward, double* I_out, int64_t I_ld);
+/* host-buffer twin: contiguous arrays, total_alphas / source [n_depth][n_nu], I_out [n_theta][n_nu]; source = NULL: Planck. */
+int sdx_emergent_intensity_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                               const double* temperature, const double* ray_dist, const double* total_alphas,
+                               const double* source, int inward, double* I_out);
+
 /* ---- response functions: flux derivatives to opacity and source per depth ------------------------
  * HOW the emergent flux changes: the exact derivative of the formal solution above, the companion of the contribution function.
  * It is the derivative of the reference's formulas as written, branch by branch (radiation_field_solvers/base.py:22-45, :200-266).
@@ -1064,6 +1085,51 @@ int sdx_rotate_integrated_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lam
  * (d = yb - ya rounded once; an empty cell gives zeros; a cell that spans 0 is split there).  For tests.  Stage name: "k_rotate_moments". */
 int sdx_rotate_moments_dev(sdx_ctx* ctx, int64_t n, const double* ya, const double* yb, const double* eps, double* out_m0, double* out_m1);
 int sdx_rotate_moments_f64(sdx_ctx* ctx, int64_t n, const double* ya, const double* yb, const double* eps, double* out_m0, double* out_m1);
+
+/* ---- disk integration with rigid rotation: per-ring spectra instead of a limb-darkening law ----
+ * sdx_rotate_dev and sdx_rotate_integrated_dev apply Gray's profile, i.e. I(mu, lambda) = f(lambda) (1 - eps + eps mu) with one chosen
+ * eps.  Here the disk is a set of rings of constant mu, ring r at the projected radius ring_scale[r] = sin theta_r in [0, 1] (b / R for a
+ * spherical model) with its OWN spectrum I[r][.] (sdx_emergent_intensity_dev's rows, in any one unit) and the flux weight
+ * ring_weights[r].  Along a ring the line-of-sight velocity of a rigid rotator is V ring_scale[r] cos phi with phi uniform, so the ring's
+ * average is the convolution of its spectrum with the arcsine density 1 / (pi sqrt(1 - y^2)) of half-width V ring_scale[r] / c.  The
+ * spectrum is piecewise linear between the nodes and the density is integrated against it exactly, cell by cell, as
+ * sdx_rotate_integrated_dev does with Gray's profile.  lambdas[n] ascending; I [n_rings][I_ld], I_ld >= n.
+ * For point i and ring r, every operation one correctly rounded fp64 operation (atan2: the device library's), in this order (the device
+ * functions disk_cell, arc_moments, arc_half), beta_r = (V / c) ring_scale[r], reach = lambdas[i] beta_r:
+ *     !(reach > 0):  A_r[i] = I[r][i], a copy;   otherwise over every cell g = [j, j + 1] of sdx_rotate_dev's window for that reach and
+ *     the partial cell on each side:
+ *     y_j = (lambdas[j] - lambdas[i]) / reach  (y_i = 0),   c_j = min(max(y_j, -1), 1),   COUNTS(g) = c_{j+1} > c_j,
+ *     Delta_g = (lambdas[j+1] - lambdas[j]) / reach,      d_g = Delta_g where neither end is clamped, else c_{j+1} - c_j,
+ *     M0_g, M1_g = the integrals of 1 / (pi sqrt(1 - y^2)) and y / (pi sqrt(1 - y^2)) over [c_j, c_{j+1}]: for 0 <= p < s <= 1 (the
+ *       other half mirrored, a cell that spans 0 split there), with q = (1 - y)(1 + y), D = d (s + p):
+ *       sin = D / (s sqrt(q_p) + p sqrt(q_s)),   cos = p s + sqrt(q_p) sqrt(q_s),   M0 = atan2(sin, cos) / pi,
+ *       M1 = D / (pi (sqrt(q_p) + sqrt(q_s)))      (no difference of asin or of square roots: a cell of any width keeps its accuracy),
+ *     r_g = (M1_g - y_j M0_g) / Delta_g,
+ *     A_r[i] = sum_g ((M0_g - r_g) I[r][j] + r_g I[r][j+1]) / sum_g M0_g       (ascending g; the two products of a cell in this order),
+ *     out[i] = sum_r ring_weights[r] A_r[i]      in the flux's order: two ascending halves over r, the lower added to the upper.
+ * out_reference likewise from I_reference (both or neither).  A window truncated at an end of the grid is renormalised by its own sum
+ * of M0, as sdx_rotate_dev's is.  Consequences: V = 0 gives the flux sum sum_r w_r I[r][i] in the flux's order bit for bit (fed
+ * sdx_emergent_intensity_dev's rows and the field's weights: F_nu[n_depth-1] of the plain kernel, plane-parallel); the result is
+ * continuous as V -> 0 (a window under one spacing still has three weights); a spectrum linear in lambda is reproduced at interior
+ * points of any grid; a node on a ring's edge closes a cell of zero length.  With I[r] = f (1 - eps + eps mu_r) and rings that
+ * resolve s = sin theta in [0, 1] with weight 2 s ds the result tends to sdx_rotate_integrated_dev's.
+ * Mapping, window search, round-robin over the point's 8 or 64 lanes, ascending order and butterfly are sdx_rotate_dev's (the mapping
+ * chosen by the widest possible ring, ring_scale = 1); a point's lanes take the rings one after the other.  No floating-point atomics:
+ * two calls, the replay of a captured graph and the host-buffer twin give the same bits.
+ * sdx_disk_integrate_dev: device pointers, asynchronous, no allocation, capturable; rot_dev is sdx_rotate_dev's {V, eps} pair in device
+ * memory, of which only V is read, when the kernel runs (a captured call follows a rewritten pair).  SDX_ERR_ARG before anything is
+ * enqueued: n < 2, n_rings outside 1 .. 64, a null required pointer, I_reference without out_reference or the reverse, I_ld < n, an
+ * output that is one of the inputs or the other output.  Contents unchecked as for sdx_rotate_dev: every access stays inside the arrays
+ * (a cell index g has 0 <= g < n - 1, a ring index 0 <= r < n_rings) and every loop is bounded by its bracket.
+ * Stage name: "k_disk_integrate". */
+int sdx_disk_integrate_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale,
+                           const double* ring_weights, const double* I, int64_t I_ld, const double* I_reference, const double* rot_dev,
+                           double* out, double* out_reference);
+/* host-buffer twin: I and I_reference [n_rings][n] contiguous; additionally refuses, before any copy, lambdas that are not finite and
+ * strictly ascending, v_rot that is not finite with 0 <= v_rot < 3000 km/s, and ring_scale outside [0, 1]. */
+int sdx_disk_integrate_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale,
+                           const double* ring_weights, const double* I, const double* I_reference, double v_rot, double* out,
+                           double* out_reference);
 
 /* Everything in one call for resident data: pre-pass + line opacity + total (above) + raytrace (F_nu
  * overwritten).  F_nu is [n_depth][ld].  alpha_line_out and total_alphas ([n_depth][ld]) are OPTIONAL outputs (NULL: the

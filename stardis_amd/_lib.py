@@ -176,6 +176,8 @@ PROTOTYPES = {
     "sdx_contribution_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64]),
     "sdx_formation_mean_dev": (_int, [_vp, _int, _i64, _vp, _i64, _vp, _vp]),
     "sdx_contribution_f64": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_emergent_intensity_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _int, _vp, _i64]),
+    "sdx_emergent_intensity_f64": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "sdx_response_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
     "sdx_response_f64": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sdx_response_project_dev": (_int, [_vp, _int, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -226,6 +228,8 @@ PROTOTYPES = {
     "sdx_rotate_integrated_adjoint_f64": (_int, [_vp, _i64, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "sdx_rotate_moments_dev": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sdx_rotate_moments_f64": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_disk_integrate_dev": (_int, [_vp, _i64, _vp, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "sdx_disk_integrate_f64": (_int, [_vp, _i64, _vp, _int, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
     "sdx_synthesize_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, C.POINTER(Continuum), _int,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sdx_synthesize_ex_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, C.POINTER(Continuum), _int,

@@ -3610,6 +3610,90 @@ __global__ __launch_bounds__(kRtBlock) void k_raytrace(int n_depth, int64_t n_nu
     }
 }
 
+// The emergent intensity of every ray (include/stardis_hip.h, sdx_emergent_intensity_dev): k_raytrace's walk — the same lane <->
+// (frequency, angle) mapping, the same RtColumns staging of (S, sqrt(alpha)) from a FINISHED total_alphas plane, the inward sweep where
+// asked for, rt_coef<false> per inner gap and rt_coef<true> for the last, each on the operands k_raytrace forms, in its order — that keeps
+// the last row alone: no flux, no weights, no I_nus volume.  What a lane holds after the last gap is row N_d - 1 of k_raytrace's I_nus bit
+// for bit.  The output is theta-major, I_out[theta][ild] (a ring's spectrum contiguous for k_disk_integrate): the wave parks its
+// gpw x G values in the flux region of its LDS share and writes them out angle by angle, consecutive lanes consecutive frequencies.
+__global__ __launch_bounds__(kRtBlock) void k_emergent_intensity(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
+                                                               const double* __restrict__ nus, const double* __restrict__ temps,
+                                                               const double* __restrict__ ray_dist, const double* __restrict__ alphas,
+                                                               int64_t ald, const double* __restrict__ source, int64_t sld, int inward,
+                                                               double* __restrict__ I_out, int64_t ild, int gpw)
+{
+    extern __shared__ double smem[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int grp = lane / G, g = lane - grp * G;
+    const int64_t i0 = ((int64_t)blockIdx.x * (kRtBlock / 64) + wave) * gpw;  // first frequency of this wave
+    const int64_t i = i0 + grp;
+    const bool active = grp < gpw;
+    const int64_t ic = i < n_nu ? i : n_nu - 1;
+    const int n_gap = n_depth - 1;
+    const int col = n_depth;
+    const RtColumns lay(G, n_depth, gpw);
+    double* wbase = smem + (size_t)wave * lay.wave_doubles();
+    double2* sP = (double2*)(wbase + lay.pairs());  // (source function, sqrt(alpha)) [gpw][col]
+    double* sX = wbase + lay.flux();                // the emergent intensities [gpw][G] (the first of the kRtBatch flux slots)
+    const double nu = nus[ic];
+    if (active) {
+        for (int d = g; d < n_depth; d += G)
+            sP[grp * col + d] = double2{source ? source[(size_t)d * sld + ic] : planck_staged(nu, temps[d]), sqrt(alphas[(size_t)d * ald + ic])};
+    }
+    wave_sync();
+    const RtConst kc = rt_const_literals();  // (literals, as in k_raytrace: the gap loop is rolled)
+
+    const int gi = (active ? grp : 0) * col;  // idle lanes shadow group 0 and never store
+    const int th = min(g, n_theta - 1);
+    double inten = 0.0;  // np.zeros (:134)
+    if (inward) {        // the surface-to-centre sweep of k_raytrace (:141-198)
+        for (int gap = n_gap - 1; gap >= 0; --gap) {
+            const int gm = gap > 0 ? gap - 1 : n_gap - 1;
+            const int dm = gap > 0 ? gap - 1 : n_depth - 1;
+            const double2 q0 = sP[gi + gap + 1], q1 = sP[gi + gap], q2 = sP[gi + dm];
+            const double s0 = q0.x, s1 = q1.x, s2 = q2.x;
+            const double mg = q1.y * q0.y, mm = sP[gi + gm].y * sP[gi + gm + 1].y;
+            const double tg = mul_rn(mg, ray_dist[(size_t)gap * theta_stride + th]), tm = mul_rn(mm, ray_dist[(size_t)gm * theta_stride + th]);
+            double c, e;
+            rt_coef<false>(tg, tm, s0 - s1, s2 - s1, s1, c, e, kc);
+            inten = tm == 0.0 ? inten : fma(c, inten, e);
+        }
+    }
+    const double2 p0 = sP[gi], p1 = sP[gi + 1];
+    double a1 = p1.y;
+    const double* rdp = ray_dist + th;
+    double tau0 = mul_rn(p0.y * a1, *rdp);
+    rdp += n_gap > 1 ? theta_stride : 0;
+    double rd_next = *rdp;  // gap 1
+    double s1 = p1.x, d10 = p0.x - s1;
+    for (int gap = 0; gap < n_gap; ++gap) {
+        double c, e;
+        if (gap < n_gap - 1) {  // :208-249
+            const double2 p2 = sP[gi + gap + 2];
+            const double s2 = p2.x, a2 = p2.y;
+            const double mean1 = a1 * a2, d21 = s2 - s1;
+            const double t1 = mul_rn(mean1, rd_next);
+            rdp += gap + 2 < n_gap ? theta_stride : 0;
+            rd_next = *rdp;  // gap + 2, for the next trip
+            rt_coef<false>(tau0, t1, d10, d21, s1, c, e, kc);
+            inten = fma(c, inten, e);
+            tau0 = t1;
+            d10 = -d21, s1 = s2, a1 = a2;
+        } else {  // the final gap (:253-266)
+            rt_coef<true>(tau0, 0.0, d10, 0.0, s1, c, e, kc);
+            inten = fma(c, inten, e);
+        }
+    }
+    if (active) sX[grp * G + g] = inten;
+    wave_sync();
+    // theta-major: entry p <-> (angle p / gpw, frequency p % gpw) of the wave; gpw n_theta <= 64 entries, so t < n_theta and f < gpw
+    const float inv_gpw = 1.0f / (float)gpw;
+    for (int p = lane; p < n_theta * gpw; p += 64) {
+        const int t = (int)(((float)p + 0.5f) * inv_gpw), f = p - t * gpw;  // p / gpw without an integer division (p < 2^20: exact)
+        if (i0 + f < n_nu) I_out[(size_t)t * ild + i0 + f] = sX[f * G + t];
+    }
+}
+
 // The formal solution of the fp32-mixed TOLERANCE path (mixed_precision = 1; plane-parallel, one angle per lane, flux only): the
 // layout of k_raytrace — lane <-> (frequency, angle), columns staged per wave — with the recurrence in fp32 (rt_coef32:
 // hardware exp2 / rcp, ~27 instructions per step at twice the fp64 issue rate against ~54).  sqrt(alpha), the source function, its
@@ -6231,6 +6315,118 @@ __global__ __launch_bounds__(kBlock) void k_rotate_moments(int64_t n, const doub
     }
     out_m0[i] = m0;
     out_m1[i] = m1;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Disk integration with rigid rotation (include/stardis_hip.h, sdx_disk_integrate_dev): the star's disk as rings of constant mu, ring r
+// at the projected radius scale_r = sin theta_r with its OWN spectrum I_r (the formal solution's emergent intensity of that angle,
+// k_emergent_intensity) instead of one spectrum times a limb-darkening law.  Along a ring the line-of-sight velocity is V scale_r cos phi,
+// phi uniform: the ring's average is the convolution of I_r with the arcsine density 1 / (pi sqrt(1 - y^2)) of half-width V scale_r / c.
+// As in k_rotate_integrated the spectrum is piecewise linear between the nodes and the density is integrated against it exactly, cell by
+// cell: for point i and ring r, beta_r = (V / c) scale_r, reach = lam_i beta_r; !(reach > 0): A_r[i] = I_r[i]; otherwise over the cells
+// g = [j, j + 1] of k_rotate's window for that reach and the partial cell on each side, with y, the clamp c, COUNTS, Delta and d as in
+// rot_cell,
+//     M0 = int_{c_j}^{c_{j+1}} dy / (pi sqrt(1 - y^2)),   M1 = int y dy / (pi sqrt(1 - y^2)),   r = (M1 - y_j M0) / Delta,
+//     A_r[i] = sum_g ((M0 - r) I_r[j] + r I_r[j+1]) / sum_g M0     — ascending g, the two products of a cell added in this order,
+//     out[i] = sum_r w_r A_r[i]                                    — two ascending halves over r, the lower added to the upper: the flux's order.
+// The moments are rot_half's forms (arc_half): for 0 <= p < s <= 1, D = d (s + p), sin = D / (s sqrt(q_p) + p sqrt(q_s)), cos = p s +
+// sqrt(q_p) sqrt(q_s), M0 = atan2(sin, cos) / pi, M1 = D / (pi (sqrt(q_p) + sqrt(q_s)))  (sqrt(q_p) - sqrt(q_s) without the cancellation);
+// the other half mirrored, a cell that spans 0 split there (arc_moments, as rot_moments).  The density is integrable but unbounded at
+// +-1: sampled at the nodes it would need the cell integrals anyway.  A truncated window is renormalised by its own sum of M0.
+//
+// disk_cell is the ONE place where a ring's cell is rounded and counts or not.  Mapping (rot_mapping, by the widest ring a disk can have,
+// scale = 1), window search, round-robin, ascending order and butterfly are k_rotate's; a point's lanes take the rings one after the
+// other, every lane holds every A_r after the butterfly and keeps the two half sums itself: no LDS, no floating-point atomics.
+// Whatever the arrays hold: whether a ring is searched at all depends on V and scale_r alone (the same in every lane of the wave, as the
+// window search needs); a ring that is searched runs obs_windows in every lane, a point whose own reach is not positive with nothing to
+// search; a cell index g satisfies 0 <= g < n - 1, a lane makes at most (n - 1) / W + 1 trips per ring, and a point writes only its own
+// element.
+__device__ __forceinline__ void arc_half(double p, double s, double d, double& m0, double& m1)
+{
+    const double qp = mul_rn(sub_rn(1.0, p), add_rn(1.0, p)), qs = mul_rn(sub_rn(1.0, s), add_rn(1.0, s));
+    const double rp = __dsqrt_rn(qp), rs = __dsqrt_rn(qs);
+    const double dsum = mul_rn(d, add_rn(s, p));  // s^2 - p^2 = q_p - q_s
+    const double sn = dsum / add_rn(mul_rn(s, rp), mul_rn(p, rs)), cs = add_rn(mul_rn(p, s), mul_rn(rp, rs));
+    m0 = atan2(sn, cs) / kPi;
+    m1 = dsum / mul_rn(kPi, add_rn(rp, rs));
+}
+// -1 <= a < b <= 1, d = b - a (rot_moments' cases)
+__device__ __forceinline__ void arc_moments(double a, double b, double d, double& m0, double& m1)
+{
+    if (a >= 0.0) {
+        arc_half(a, b, d, m0, m1);
+    } else if (b <= 0.0) {
+        arc_half(-b, -a, d, m0, m1);
+        m1 = -m1;
+    } else {
+        double l0, l1, h0, h1;
+        arc_half(0.0, -a, -a, l0, l1);
+        arc_half(0.0, b, b, h0, h1);
+        m0 = add_rn(l0, h0), m1 = 0.0;
+        const double na = -a;
+        if (na != b) {
+            double o0, o1;
+            arc_half(fmin(na, b), fmax(na, b), fabs(add_rn(a, b)), o0, o1);
+            m1 = b > na ? o1 : -o1;
+        }
+    }
+}
+// point i's cell [a, b] = [j, j + 1] of a ring of reach `reach` (self as for rot_cell); false: the cell does not count
+__device__ __forceinline__ bool disk_cell(double reach, double lam_i, double lam_a, double lam_b, int self, double& m0, double& r)
+{
+    const double ya = self == 0 ? 0.0 : sub_rn(lam_a, lam_i) / reach, yb = self == 1 ? 0.0 : sub_rn(lam_b, lam_i) / reach;
+    const double ca = fmin(fmax(ya, -1.0), 1.0), cb = fmin(fmax(yb, -1.0), 1.0);
+    if (!(cb > ca)) return false;
+    const double delta = sub_rn(lam_b, lam_a) / reach;
+    const double d = ca == ya && cb == yb ? delta : sub_rn(cb, ca);
+    double m1;
+    arc_moments(ca, cb, d, m0, m1);
+    r = sub_rn(m1, mul_rn(ya, m0)) / delta;
+    return true;
+}
+__global__ __launch_bounds__(kBlock) void k_disk_integrate(int64_t n, const double* __restrict__ lam, int n_rings,
+                                                           const double* __restrict__ scale, const double* __restrict__ wts,
+                                                           const double* __restrict__ I, int64_t ild, const double* __restrict__ I_ref,
+                                                           const double* __restrict__ rot, double* __restrict__ out,
+                                                           double* __restrict__ out_ref)
+{
+    const double V = rot[0], beta = V / kCKms;  // (the pair's limb darkening is not read: every ring has its own spectrum)
+    RotLane m;
+    if (!rot_mapping(n, lam, 2.0 * beta, V > 0.0, m)) return;
+    const int64_t i = m.on ? m.pi : n - 1;
+    const double li = lam[i];
+    const int half = (n_rings + 1) >> 1;
+    double lower = 0.0, upper = 0.0, lower_ref = 0.0, upper_ref = 0.0;
+    for (int r = 0; r < n_rings; ++r) {
+        const double* __restrict__ Ir = I + (size_t)r * ild;
+        const double* __restrict__ Gr = I_ref ? I_ref + (size_t)r * ild : nullptr;
+        const double beta_r = mul_rn(beta, scale[r]), reach = mul_rn(li, beta_r);
+        double a = Ir[i], a_ref = Gr ? Gr[i] : 0.0;  // !(reach > 0): a copy
+        if (beta_r > 0.0) {                          // (the same in every lane of the wave)
+            const bool on = m.on && reach > 0.0;
+            int64_t i0, i1;
+            obs_windows(lam, lam, n, 1.0, sub_rn(li, reach), add_rn(li, reach), on, m.W, m.lane, i0, i1);
+            const int64_t g0 = i0 > 0 ? i0 - 1 : 0, g1 = i1 < n - 1 ? i1 : n - 1;  // the window's cells and the partial cell on each side
+            double num = 0.0, numr = 0.0, den = 0.0;
+            for (int64_t g = g0 + m.t; on && g < g1; g += m.W) {
+                double m0, sh;
+                if (!disk_cell(reach, li, lam[g], lam[g + 1], g == i ? 0 : (g + 1 == i ? 1 : -1), m0, sh)) continue;
+                const double wa = sub_rn(m0, sh);
+                den = add_rn(den, m0);
+                num = add_rn(add_rn(num, mul_rn(wa, Ir[g])), mul_rn(sh, Ir[g + 1]));
+                if (Gr) numr = add_rn(add_rn(numr, mul_rn(wa, Gr[g])), mul_rn(sh, Gr[g + 1]));
+            }
+            for (int off = m.W >> 1; off > 0; off >>= 1)
+                num = add_rn(num, __shfl_xor(num, off)), numr = add_rn(numr, __shfl_xor(numr, off)), den = add_rn(den, __shfl_xor(den, off));
+            if (reach > 0.0) a = num / den, a_ref = numr / den;
+        }
+        const double w = wts[r], term = mul_rn(a, w), term_ref = mul_rn(a_ref, w);
+        if (r < half) lower = add_rn(lower, term), lower_ref = add_rn(lower_ref, term_ref);
+        else upper = add_rn(upper, term), upper_ref = add_rn(upper_ref, term_ref);
+    }
+    if (m.t != 0 || !m.on) return;
+    out[m.pi] = add_rn(lower, upper);
+    if (I_ref) out_ref[m.pi] = add_rn(lower_ref, upper_ref);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -14,6 +14,8 @@ constexpr size_t kLdsBytes = 64 * 1024;   // what a workgroup may ask for
 constexpr int kRtBatch = 4;  // gaps per flux reduction of k_raytrace, k_raytrace_cont and k_contribution
 // k_raytrace, k_contribution.  Per wave: the (source function, sqrt(alpha)) pairs [gpw][col] as double2, then the flux terms
 // [kRtBatch][gpw][G] of a batch of gaps.  G lanes per frequency, one angle per lane, gpw frequencies per wave.
+// k_emergent_intensity takes the same layout (k_raytrace's budget decides what it serves) and parks its [gpw][G] emergent intensities
+// in the first of the flux slots for the theta-major write.
 struct RtColumns {
     int gpw, col, G;
     __host__ __device__ constexpr RtColumns(int G_, int n_depth, int gpw_) : gpw(gpw_), col(n_depth), G(G_) {}

@@ -2430,6 +2430,58 @@ int sdx_contribution_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, c
     return io.finish();
 }
 
+// ---- emergent intensity of every ray, the surface row alone (k_emergent_intensity) -----------------------------------------
+// As for the contribution function, everything is checked before anything is enqueued, also for an empty grid.
+int sdx_emergent_intensity_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
+                               const double* ray_dist, const double* alphas, int64_t ald, const double* source, int64_t source_ld, int inward,
+                               double* I_out, int64_t I_ld)
+{
+    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "emergent_intensity: need n_depth >= 2, n_theta > 0");
+    REQUIRE(!ctx->mixed_precision, "emergent_intensity: no emergent intensities with mixed_precision = 1 (they are the fp64 formal solution's last row)");
+    REQUIRE(n_theta <= 64, "emergent_intensity: more than 64 angles are not supported (all angles are traced in one launch)");
+    const int G = n_theta;
+    const int gpw = rt_fit_gpw<RtColumns>(G, n_depth);  // (k_raytrace's budget)
+    REQUIRE(gpw > 0, "emergent_intensity: no emergent intensities for models this deep (the columns do not fit LDS)");
+    for (const double* in : {nus, temps, ray_dist, alphas, source})
+        REQUIRE(!I_out || I_out != in, "emergent_intensity: not in place (I_out must not be one of the inputs)");
+    if (n_nu == 0) return SDX_OK;
+    REQUIRE(nus && ray_dist && alphas && ald >= n_nu && I_out && I_ld >= n_nu, "emergent_intensity: null pointer or leading dimension below n_nu");
+    REQUIRE(source ? source_ld >= n_nu : temps != nullptr, "emergent_intensity: bad source plane (source_ld < n_nu), or neither a source plane nor temperatures");
+    HIP_TRY(hipSetDevice(ctx->device));
+    {
+        LaunchScope ls(ctx, "k_emergent_intensity");
+        hipLaunchKernelGGL(k_emergent_intensity, dim3(rt_blocks(n_nu, gpw)), dim3(kRtBlock), RtColumns(G, n_depth, gpw).bytes(), ctx->stream, n_depth, n_nu, n_theta,
+                           n_theta, G, nus, temps, ray_dist, alphas, ald, source, source_ld, inward ? 1 : 0, I_out, I_ld, gpw);
+    }
+    return check_launch("k_emergent_intensity");
+}
+
+int sdx_emergent_intensity_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
+                               const double* ray_dist, const double* alphas, const double* source, int inward, double* I_out)
+{
+    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "emergent_intensity: need n_depth >= 2, n_theta > 0");
+    REQUIRE(n_nu == 0 || (nus && temps && ray_dist && alphas && I_out), "emergent_intensity: null pointer");
+    int rc;
+    if ((rc = sdx_emergent_intensity_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, inward, nullptr, 0))) return rc;  // refusals before any copy
+    if (n_nu == 0) return SDX_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
+    const double *d_nus, *d_t, *d_rd, *d_a, *d_s;
+    double* d_i;
+    HostPlan plan;
+    plan.in(nus, (size_t)n_nu * f8, &d_nus);
+    plan.in(temps, (size_t)n_depth * f8, &d_t);
+    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
+    plan.in(alphas, plane, &d_a);
+    plan.in(source, plane, &d_s);
+    plan.out(I_out, (size_t)n_theta * n_nu * f8, &d_i);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_emergent_intensity_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_a, n_nu, d_s, n_nu, inward, d_i, n_nu))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
 // ---- response functions (k_response, k_response_project) -------------------------------------------------------------------
 // As for the contribution function, everything is checked before anything is enqueued, also for an empty grid.
 int sdx_response_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
@@ -3716,6 +3768,65 @@ int sdx_rotate_moments_f64(sdx_ctx* ctx, int64_t n, const double* ya, const doub
     int rc;
     if ((rc = io.stage(plan))) return rc;
     if ((rc = sdx_rotate_moments_dev(ctx, n, d_a, d_b, d_e, d_m0, d_m1))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+// ---- disk integration with rigid rotation (k_disk_integrate): per-ring spectra, the arcsine density of each ring integrated cell by cell --
+static int disk_integrate_check(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale, const double* ring_weights,
+                                const double* I, const double* I_reference, const double* rot, const double* out, const double* out_reference)
+{
+    REQUIRE(ctx, "disk_integrate: null context");
+    REQUIRE(n >= 2, "disk_integrate: the grid needs at least two points (n >= 2)");
+    REQUIRE(n_rings >= 1 && n_rings <= 64, "disk_integrate: n_rings must lie in 1 .. 64");
+    REQUIRE(lambdas && ring_scale && ring_weights && I && out, "disk_integrate: null pointer (lambdas, ring_scale, ring_weights, I and out are required)");
+    REQUIRE(!I_reference == !out_reference, "disk_integrate: I_reference and out_reference go together");
+    const double* const ins[6] = {lambdas, ring_scale, ring_weights, I, I_reference, rot};
+    const double* const outs[2] = {out, out_reference};
+    return distinct_buffers("disk_integrate", ins, 6, outs, 2);
+}
+
+int sdx_disk_integrate_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale, const double* ring_weights,
+                           const double* I, int64_t I_ld, const double* I_reference, const double* rot_dev, double* out, double* out_reference)
+{
+    int rc;
+    if ((rc = disk_integrate_check(ctx, n, lambdas, n_rings, ring_scale, ring_weights, I, I_reference, rot_dev, out, out_reference))) return rc;
+    REQUIRE(rot_dev, "disk_integrate: null pointer (rot_dev is required)");
+    REQUIRE(I_ld >= n, "disk_integrate: I_ld below n");
+    REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "disk_integrate: too many points for one launch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    {
+        LaunchScope ls(ctx, "k_disk_integrate");
+        hipLaunchKernelGGL(k_disk_integrate, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, n_rings, ring_scale, ring_weights, I, I_ld,
+                           I_reference, rot_dev, out, out_reference);
+    }
+    return check_launch("k_disk_integrate");
+}
+
+int sdx_disk_integrate_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale, const double* ring_weights,
+                           const double* I, const double* I_reference, double v_rot, double* out, double* out_reference)
+{
+    int rc;
+    if ((rc = disk_integrate_check(ctx, n, lambdas, n_rings, ring_scale, ring_weights, I, I_reference, nullptr, out, out_reference))) return rc;
+    if ((rc = rotate_host_check(n, lambdas, v_rot, 0.0))) return rc;
+    for (int r = 0; r < n_rings; ++r) REQUIRE(ring_scale[r] >= 0.0 && ring_scale[r] <= 1.0, "disk_integrate: ring_scale must lie in [0, 1]");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8, rings = (size_t)n_rings * f8;
+    const double pair[2] = {v_rot, 0.0};
+    const double *d_l, *d_s, *d_w, *d_i, *d_r, *d_p;
+    double *d_o, *d_or;
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(ring_scale, rings, &d_s);
+    plan.in(ring_weights, rings, &d_w);
+    plan.in(I, grid * n_rings, &d_i);
+    plan.in(I_reference, grid * n_rings, &d_r);
+    plan.in(pair, 2 * f8, &d_p);
+    plan.out(out, grid, &d_o);
+    plan.out(out_reference, grid, &d_or);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_disk_integrate_dev(ctx, n, d_l, n_rings, d_s, d_w, d_i, n, d_r, d_p, d_o, d_or))) return rc;
     if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }

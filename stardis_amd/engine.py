@@ -54,9 +54,12 @@ class _DeviceRow(_lib.DeviceArray):
 
 
 class SpectralSynthesizer:
+    keep_intensities = False  # (the class's default; __init__ sets the instance's)
+
     def __init__(self, nus, temperatures, dist, thetas, theta_weights, lines, continuum=None, ctx=None, shard=None,
                  flux_out=None, track_evaluations=True, keep_line=True, keep_total=True, classify_share=None, m_max=None, m_share_out=None,
-                 keep_continuum_flux=False, keep_contribution=False, instrument=None, grid_plan=True, keep_response=False, scattering=None):
+                 keep_continuum_flux=False, keep_contribution=False, instrument=None, grid_plan=True, keep_response=False, scattering=None,
+                 keep_intensities=False):
         """nus: global grid (descending).  lines: dict(line_nus, doppler_widths, gammas, alphas) in the
         reference layout (N_l, N_d), or a stardis_amd.linelist.LineList (per-line scalars; the pre-pass generates the
         three values per (line, depth) itself).  continuum: dict as produced by synth.synth_continuum_state or None.
@@ -167,6 +170,10 @@ class SpectralSynthesizer:
             # the library's own refusals (mixed precision, angles, depth), asked with an empty grid: nothing is enqueued
             c.call("sdx_contribution_dev", self.n_depth, 0, self.n_theta, None, None, None, None, None, 0, None, 0, None, 0)
             keep_total = True
+        self.keep_intensities = bool(keep_intensities)
+        if self.keep_intensities:
+            c.call("sdx_emergent_intensity_dev", self.n_depth, 0, self.n_theta, None, None, None, None, 0, None, 0, 0, None, 0)
+            keep_total = True
         self.keep_response = bool(keep_response)
         if self.keep_response:
             c.call("sdx_response_dev", self.n_depth, 0, self.n_theta, None, None, None, None, None, 0, None, 0, None, 0, None, 0)
@@ -188,6 +195,9 @@ class SpectralSynthesizer:
         self.keep_continuum_flux = bool(keep_continuum_flux)
         self.d_Fc = c.empty((self.n_depth, self.count)) if self.keep_continuum_flux else None
         self.d_C = c.empty((self.n_depth, self.count)) if self.keep_contribution else None
+        self.d_I = c.empty((self.n_theta, self.count)) if self.keep_intensities else None
+        self.ring_scale = np.sin(thetas).reshape(-1)  # the projected radius of each angle's ring on the disk
+        self._disk = None  # disk_integrated's buffers, made at its first call
         self.d_Ra = c.empty((self.n_depth, self.count)) if self.keep_response else None
         self.d_Rs = c.empty((self.n_depth, self.count)) if self.keep_response else None
         if self.scattering is not None:
@@ -316,6 +326,8 @@ class SpectralSynthesizer:
             raise ValueError("keep_contribution reads the step's total_alphas: keep_total stays on")
         if not on and self.keep_response:
             raise ValueError("keep_response reads the step's total_alphas: keep_total stays on")
+        if not on and self.keep_intensities:
+            raise ValueError("keep_intensities reads the step's total_alphas: keep_total stays on")
         if not on and self.scattering is not None:
             raise ValueError("scattering reads the step's total_alphas: keep_total stays on")
         if on and self.d_total is None:
@@ -371,9 +383,11 @@ class SpectralSynthesizer:
         self._enqueue_tail()
 
     def _enqueue_tail(self):
-        """what follows the synthesis of a step, fused or not: contribution, response, scattering, the instrument"""
+        """what follows the synthesis of a step, fused or not: contribution, emergent intensities, response, scattering, the instrument"""
         if self.keep_contribution:
             self._enqueue_contribution()
+        if self.keep_intensities:
+            self._enqueue_intensities()
         if self.keep_response:
             self._enqueue_response()
         if self.scattering is not None:
@@ -404,6 +418,11 @@ class SpectralSynthesizer:
         cnt = self.count
         self.ctx.call("sdx_contribution_dev", self.n_depth, cnt, self.n_theta, self.d_nus.ptr + 8 * self.begin, self.d_t.ptr, self.d_ray.ptr,
                       self.d_w.ptr, self.d_total.ptr, cnt, None, 0, self.d_C.ptr, cnt)
+
+    def _enqueue_intensities(self):
+        cnt = self.count
+        self.ctx.call("sdx_emergent_intensity_dev", self.n_depth, cnt, self.n_theta, self.d_nus.ptr + 8 * self.begin, self.d_t.ptr, self.d_ray.ptr,
+                      self.d_total.ptr, cnt, None, 0, 0, self.d_I.ptr, cnt)
 
     def _enqueue_response(self):
         cnt = self.count
@@ -568,6 +587,53 @@ class SpectralSynthesizer:
         if not self.keep_contribution:
             raise RuntimeError("the contribution function was not kept: construct the synthesizer with keep_contribution=True")
         return self.d_C
+
+    @property
+    def emergent_intensities(self):
+        """-> DeviceArray (N_theta, count): the emergent intensity of every ray of the last step, angle by angle (`.numpy()` for a host
+        array): no theta weights applied."""
+        if not self.keep_intensities:
+            raise RuntimeError("the emergent intensities were not kept: construct the synthesizer with keep_intensities=True")
+        return self.d_I
+
+    def disk_integrated(self, v_rot):
+        """-> DeviceArray (n_nu,): F_lambda of the last step integrated over the disk of a rigid rotator with v sin i = v_rot (km/s):
+        every angle's emergent intensity converted to per Angstrom (sdx_flux_nu_to_lambda_dev's operation, ring by ring), the ring at
+        the projected radius sin(theta) convolved with its own arcsine density and the rings summed with the flux weights in the flux's
+        order (sdx_disk_integrate_dev) — the model's own centre-to-limb variation, line by line, in place of a limb-darkening
+        coefficient.  v_rot = 0 is F_lambda itself.  Needs the whole spectrum (a shard raises ValueError: gather first).  The buffers
+        are made at the first call and reused: the result is overwritten by the next call."""
+        from .instrument import rotation_pair
+
+        d_I = self.emergent_intensities
+        if self.begin != 0 or self.count != self.n_nu:
+            raise ValueError("the disk integration needs the whole spectrum: gather the shards first")
+        V, _ = rotation_pair(v_rot)
+        c, n = self.ctx, self.n_nu
+        if self._disk is None:
+            d_lam = self.d_lambdas if self.instrument is not None else c.upload(K.nu_to_angstrom(self.nus_host))
+            self._disk = dict(lambdas=d_lam, scale=c.upload(self.ring_scale), I_lambda=c.empty((self.n_theta, n)), rot=c.empty((2,)), out=c.empty((n,)))
+        d = self._disk
+        d["rot"].set(np.array([V, 0.0]))
+        for r in range(self.n_theta):
+            c.call("sdx_flux_nu_to_lambda_dev", n, d_I.ptr + 8 * r * n, self.d_nus.ptr, d["lambdas"].ptr, d["I_lambda"].ptr + 8 * r * n)
+        c.call("sdx_disk_integrate_dev", n, d["lambdas"].ptr, self.n_theta, d["scale"].ptr, self.d_w.ptr, d["I_lambda"].ptr, n, None, d["rot"].ptr,
+               d["out"].ptr, None)
+        return d["out"]
+
+    def observed_disk_integrated(self, v_rot):
+        """-> DeviceArray (n_pix,): disk_integrated(v_rot) through the instrument — its macroturbulence (if any), then the radial
+        velocity, line-spread function and pixels (observe(..., broadened=True)).  An instrument that carries a v_rot of its own
+        raises ValueError: the star would be rotated twice."""
+        inst = self.instrument
+        if inst is None:
+            raise RuntimeError("no instrument: construct the synthesizer with instrument=")
+        if inst.rotates:
+            raise ValueError("the instrument already carries a v_rot: the disk integration is the rotation (rotation twice)")
+        flux = self.disk_integrated(v_rot)
+        if inst.macroturbulent:
+            flux = inst.macroturbulence(self.d_lambdas, flux, self.n_nu)
+        return inst.observe(self.d_lambdas, flux, self.n_nu, out=self.ctx.empty((inst.n_pix,)), broadened=True)
 
     def _require_response(self):
         if not self.keep_response:

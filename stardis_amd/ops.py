@@ -592,6 +592,38 @@ def contribution_arrays(tracing_nus, temperatures, ray_distances, theta_weights,
     return d_C if device else d_C.numpy()
 
 
+def emergent_intensity(tracing_nus, temperatures, ray_distances, total_alphas, ctx=None, source=None, inward_rays=False, device=False):
+    """Emergent intensity of every ray (sdx_emergent_intensity_dev) -> (N_theta, N_nu): row N_d - 1 of the I_nus that raytrace_arrays
+    (track=True) returns from the plain kernel, bit for bit, without the (N_d, N_nu, N_theta) volume.  Intensities: no theta weights,
+    no photospheric correction.  ray_distances is the (N_d-1, N_theta) table of radiation_field_solvers/base.py:302-305, or of
+    calculate_spherical_ray with inward_rays=True; total_alphas a host or device array; source an optional (N_d, N_nu)
+    source-function plane.  The shapes are checked before any device work.  device=True: the DeviceArray instead of a host array."""
+    nus = _host(tracing_nus).reshape(-1)
+    t = _host(temperatures).reshape(-1)
+    rd = _host(ray_distances)
+    if t.size < 2 or rd.ndim != 2 or rd.shape[0] != t.size - 1 or rd.shape[1] < 1:
+        raise ValueError(f"ray_distances must have shape ({t.size - 1}, N_theta), got {rd.shape}")
+    n_theta = rd.shape[1]
+    if n_theta > 64:
+        raise ValueError(f"at most 64 angles are traced in one launch, got {n_theta}")
+    shape = tuple(int(v) for v in (total_alphas.shape if hasattr(total_alphas, "shape") else np.shape(total_alphas)))
+    if shape != (t.size, nus.size):
+        raise ValueError(f"total_alphas must have shape {(t.size, nus.size)}, got {shape}")
+    src = None
+    if source is not None:
+        src = _host(source)
+        if src.shape != (t.size, nus.size):
+            raise ValueError(f"source function must return shape {(t.size, nus.size)}, got {src.shape}")
+    ctx = ctx or default_context()
+    d_alpha = _dev(ctx, total_alphas)
+    d_S = ctx.upload(src) if src is not None else None
+    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd)]
+    d_I = ctx.empty((n_theta, nus.size))
+    ctx.call("sdx_emergent_intensity_dev", t.size, nus.size, n_theta, d[0].ptr, d[1].ptr, d[2].ptr, ptr_of(d_alpha), nus.size, ptr_of(d_S),
+             nus.size, 1 if inward_rays else 0, d_I.ptr, nus.size)
+    return d_I if device else d_I.numpy()
+
+
 def response(tracing_nus, temperatures, ray_distances, theta_weights, total_alphas, ctx=None, source=None, device=False,
              want_opacity=True, want_source=True):
     """Response functions of the plane-parallel formal solution (sdx_response_dev) -> (R_alpha, R_source), each (N_d, N_nu): the
@@ -946,6 +978,39 @@ def rotate_integrated_adjoint(lambdas, u, v_rot, limb_darkening=0.6, u_reference
     (ctx or default_context()).call("sdx_rotate_integrated_adjoint_f64", lam.size, host(lam), V, eps, host(uu), host(ur), host(nu), host(w),
                                     host(w_ref))
     return w if w_ref is None else (w, w_ref)
+
+
+def disk_integrate(lambdas, intensities, ring_scale, ring_weights, v_rot, reference=None, ctx=None):
+    """Disk integration with rigid rotation (sdx_disk_integrate_f64): per-ring spectra intensities (n_rings, n) on the ascending grid
+    lambdas, ring r at the projected radius ring_scale[r] = sin theta_r in [0, 1] with the flux weight ring_weights[r]; every ring is
+    convolved with the arcsine density of half-width v_rot ring_scale[r] / c, integrated exactly against the piecewise-linear spectrum,
+    and the rings are summed in the flux's order -> (n,), or (out, out_reference) with a reference (n_rings, n).  v_rot = 0 is the
+    flux sum itself.  No limb-darkening coefficient: the centre-to-limb variation is in the spectra (ops.emergent_intensity).  The
+    arguments are checked before any device work (ValueError naming the argument)."""
+    from .instrument import _grid, _host_ptr as host, _host_vector, rotation_pair
+
+    lam = _grid(_lib.plain(lambdas))
+    V, _ = rotation_pair(v_rot)
+    scale = np.ascontiguousarray(_lib.plain(ring_scale), dtype=F8).reshape(-1)
+    n_rings = scale.size
+    if not 1 <= n_rings <= 64:
+        raise ValueError(f"ring_scale must hold 1 to 64 rings, got {n_rings}")
+    if not np.all((scale >= 0.0) & (scale <= 1.0)):
+        raise ValueError("ring_scale must lie in [0, 1]")
+    w = _host_vector("ring_weights", _lib.plain(ring_weights), n_rings, "ring")
+
+    def rings(name, a):
+        a = np.ascontiguousarray(_lib.plain(a), dtype=F8)
+        if a.shape != (n_rings, lam.size):
+            raise ValueError(f"{name} must have shape {(n_rings, lam.size)}, got {a.shape}")
+        return a
+
+    I = rings("intensities", intensities)
+    G = None if reference is None else rings("reference", reference)
+    out, out_ref = np.empty(lam.size), None if G is None else np.empty(lam.size)
+    (ctx or default_context()).call("sdx_disk_integrate_f64", lam.size, host(lam), n_rings, host(scale), host(w), host(I), host(G), V, host(out),
+                                    host(out_ref))
+    return out if out_ref is None else (out, out_ref)
 
 
 def rotate_moments(ya, yb, limb_darkening=0.6, ctx=None):

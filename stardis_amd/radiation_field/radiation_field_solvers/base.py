@@ -106,6 +106,49 @@ def continuum_flux(stellar_model, stellar_radiation_field, continuum_alphas):
     return F
 
 
+def _ray_table(stellar_model, field):
+    """-> (ray_distances (N_d-1, N_theta), photospheric correction) of the field's angles, as raytrace() builds them"""
+    thetas = np.asarray(field.thetas, dtype=np.float64)
+    if stellar_model.spherical:  # :296-300, :340-344
+        radii = np.asarray(plain(stellar_model.geometry.r), dtype=np.float64)
+        return calculate_spherical_ray(thetas, radii), (radii[-1] / float(plain(stellar_model.geometry.reference_r))) ** 2
+    dist = np.asarray(plain(stellar_model.geometry.dist_to_next_depth_point), dtype=np.float64)
+    return dist.reshape(-1, 1) / np.cos(thetas), 1.0  # :302-305
+
+
+def emergent_intensities(stellar_model, stellar_radiation_field):
+    """Emergent intensity (N_theta, N_nu) of every angle of the field's formal solution (sdx_emergent_intensity_dev): the last row of
+    the I_nus that track_individual_intensities would fill, without the (N_d, N_nu, N_theta) volume.  The same angles, source
+    function, geometry (plane-parallel or spherical) and total opacity as raytrace() above; no weights and no photospheric correction
+    are applied.  The reference has no counterpart."""
+    field = stellar_radiation_field
+    ray_distances, _ = _ray_table(stellar_model, field)
+    ctx = default_context()
+    opac = field.opacities
+    alphas = opac.total_alphas_device(ctx) if hasattr(opac, "total_alphas_device") else opac.total_alphas
+    return ops.emergent_intensity(
+        field.frequencies, plain(stellar_model.temperatures), ray_distances, alphas, ctx=ctx, inward_rays=bool(stellar_model.spherical),
+        source=_source_plane(getattr(field, "source_function", None), field.frequencies, stellar_model.temperatures),
+    )
+
+
+def disk_integrated_flux(stellar_model, stellar_radiation_field, v_rot):
+    """F_lambda (N_nu,) on the field's grid, integrated over the disk of a rigid rotator with v sin i = v_rot (km/s): every angle's
+    emergent intensity (emergent_intensities above) converted to per Angstrom (I nu / lambda, sdx_flux_nu_to_lambda_dev's operation),
+    the ring at the projected radius sin(theta) convolved with its own arcsine density and the rings summed with the field's
+    I_nus_weights (sdx_disk_integrate_dev); for a spherical model times the photospheric correction.  The field's frequencies descend,
+    so its wavelengths ascend as the operator needs.  v_rot = 0 gives the F_lambda of raytrace()'s F_nu[-1]."""
+    from stardis_amd import constants as K
+
+    field = stellar_radiation_field
+    nus = np.asarray(plain(field.frequencies), dtype=np.float64).reshape(-1)
+    lambdas = K.nu_to_angstrom(nus)
+    I_lambda = emergent_intensities(stellar_model, field) * nus / lambdas
+    _, correction = _ray_table(stellar_model, field)
+    thetas = np.asarray(field.thetas, dtype=np.float64)
+    out = ops.disk_integrate(lambdas, I_lambda, np.sin(thetas), field.I_nus_weights, v_rot, ctx=default_context())
+    return out * correction if stellar_model.spherical else out
+
 
 SPHERICAL_CONTRIBUTION = ("the flux contribution function is defined for plane-parallel models: the inward sweep of the spherical formal "
                           "solution makes the intensity at the innermost point non-zero, and the emergent flux is then not a sum over layers alone")
