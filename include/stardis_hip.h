@@ -437,6 +437,24 @@ int sdx_response_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const
 int sdx_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
                      const double* temperature, const double* ray_dist, const double* theta_weights,
                      const double* total_alphas, const double* source, double* R_alpha, double* R_source);
+/* The response for a cotangent per (angle, frequency): what carries a weight on sdx_emergent_intensity_dev's rows — the transpose of
+ * sdx_disk_integrate_dev, say — back to the opacity and the source function.  The arguments are sdx_response_dev's with the plane
+ * cotangent[n_theta][cot_ld] (cot_ld >= n_nu) in place of theta_weights:
+ *     R_alpha[k][nu]  = sum_theta cot[theta][nu] (t[k-1] G[k-1] + t[k] G[k]) / 2  = d(sum_theta cot[theta][nu] I_theta(nu)) / d ln alpha[k][nu]
+ *     R_source[k][nu] = sum_theta cot[theta][nu] (T[k+1] a[k] + T[k] q[k-1] + T[k-1] r[k-2])
+ * The kernel is k_response with a compile-time flag: the same device functions, two walks, LDS layout and theta sum (the flux's order),
+ * a ray's terms times cot[theta][nu] where the flux weight w_theta stands otherwise.  cot[theta][nu] = w_theta for every nu therefore
+ * reproduces sdx_response_dev bit for bit, and n_theta calls of sdx_response_dev with one-hot weights hold the same products.
+ * Plane-parallel geometry only; sdx_response_dev's refusals, and cot_ld < n_nu or an output that is the cotangent.  Device pointers,
+ * asynchronous, no allocation, capturable.  Stage name: "k_response_angles". */
+int sdx_response_angles_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                            const double* temperature, const double* ray_dist, const double* cotangent, int64_t cot_ld,
+                            const double* total_alphas, int64_t alpha_ld, const double* source, int64_t source_ld,
+                            double* R_alpha, int64_t R_alpha_ld, double* R_source, int64_t R_source_ld);
+/* host-buffer twin: contiguous arrays, cotangent [n_theta][n_nu], the planes [n_depth][n_nu]. */
+int sdx_response_angles_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                            const double* temperature, const double* ray_dist, const double* cotangent,
+                            const double* total_alphas, const double* source, double* R_alpha, double* R_source);
 /* The response to a scale factor on one part of the opacity (the line opacity of one species, say: dF/d ln epsilon at fixed
  * ionisation and continuum):
  *     out[nu] = sum_k R_alpha[k][nu] (part[k][nu] / total[k][nu])
@@ -1130,6 +1148,48 @@ int sdx_disk_integrate_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, int n
 int sdx_disk_integrate_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale,
                            const double* ring_weights, const double* I, const double* I_reference, double v_rot, double* out,
                            double* out_reference);
+/* The same with d out / d ln V from the same pass (the kernel's second instantiation; out and out_reference are sdx_disk_integrate_dev's
+ * bit for bit).  The derivative is exact for the discrete operator — the spectrum is piecewise linear and the domain over lambda does
+ * not move, so it needs no integration by parts.  With disk_cell's quantities, for ring r, point i, reach > 0:
+ *     dnum = sum_g (M1_g / Delta_g) (I[r][j+1] - I[r][j])             (M1_g over the clamped cell; ascending g)
+ *            - y_hi K(y_hi) I[r][n-1]   if the window is truncated above,  y_hi = (lambdas[n-1] - lambdas[i]) / reach < 1,
+ *            + y_lo K(y_lo) I[r][0]     if it is truncated below,          y_lo = (lambdas[0] - lambdas[i]) / reach > -1,
+ *     dden =   - y_hi K(y_hi) + y_lo K(y_lo)   (each under the same condition),     K(y) = 1 / (pi sqrt((1 - y)(1 + y))),
+ *     dA_r[i] = (dnum - A_r[i] dden) / den,     dout_lnv[i] = sum_r ring_weights[r] dA_r[i]   in the flux's two-halves order;
+ * 1 - |y_end| is formed as (reach - |lambdas[end] - lambdas[i]|) / reach, the difference first.  !(reach > 0) contributes 0, !(V > 0)
+ * gives zeros.  Per km/s: dout_lnv / V.  K is singular at the ring's edge: a truncated window whose end node lies within 1e-5 of the
+ * edge (1 - |y_end| < 1e-5) is OUTSIDE the derivative's contract — the term is finite but grows as the inverse square root of that
+ * distance, and the operator itself has a square-root kink in V there.
+ * dout_lnv is required, dout_lnv_reference optional and needs I_reference; otherwise sdx_disk_integrate_dev's refusals, the four outputs
+ * distinct buffers.  Stage name: "k_disk_integrate". */
+int sdx_disk_integrate_deriv_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale,
+                                 const double* ring_weights, const double* I, int64_t I_ld, const double* I_reference,
+                                 const double* rot_dev, double* out, double* out_reference, double* dout_lnv,
+                                 double* dout_lnv_reference);
+int sdx_disk_integrate_deriv_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale,
+                                 const double* ring_weights, const double* I, const double* I_reference, double v_rot, double* out,
+                                 double* out_reference, double* dout_lnv, double* dout_lnv_reference);
+/* The transpose of sdx_disk_integrate_dev.  The cotangent of a disk-integrated spectrum is not a vector over the grid but a plane over
+ * (ring, node), because each ring's spectrum is convolved with its own kernel: for weights u[n] over the broadened points,
+ *     W[r][j] = ring_weights[r] sum_i (u_i / den_r(i)) (weight of node j in point i's row for ring r),
+ * the node weight being (M0_g - r_g) of cell [j, j + 1] plus r_g' of cell [j - 1, j], with disk_cell deciding: the forward's weights bit
+ * for bit, den_r(i) in the forward's order, so that sum_i u_i out_i = sum_r sum_j W[r][j] I[r][j] up to the rounding of the sums.  A
+ * ring with !(reach > 0) passes ring_weights[r] u_j through (V = 0: W[r][j] = ring_weights[r] u_j exactly).  It is the broadening
+ * stages' pair of launches (sdx_rotate_integrated_adjoint_dev), one ring per row of the launch: a_r[i] = u_i / den_r(i) into the context's
+ * stage scratch (2 n_rings rows, sdx_rotate_adjoint_dev's convention: grown at the first call of a size, so warm a call before capturing
+ * it), then per node the gather over the candidates lambdas[i] in [lambdas[j-1] / (1 + beta_r), lambdas[j+1] / (1 - beta_r)], round-robin
+ * in ascending i and closed by the butterfly.  nus (optional): W[r][j] is further multiplied by nus[j] / lambdas[j], the transpose of
+ * sdx_flux_nu_to_lambda_dev per ring — the rows then apply to I_nu instead of I_lambda, as sdx_rotate_integrated_adjoint_dev treats nus.
+ * W [n_rings][W_ld]; W_reference likewise from u_reference (both or neither).  No floating-point atomics.  SDX_ERR_ARG before anything is
+ * enqueued: as for sdx_disk_integrate_dev, and W_ld < n, a reference output without its input or the reverse, an output that is one of
+ * the inputs or the other output.  Stage name: "k_disk_integrate_adjoint". */
+int sdx_disk_integrate_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale,
+                                   const double* ring_weights, const double* rot_dev, const double* u, const double* u_reference,
+                                   const double* nus, double* W, int64_t W_ld, double* W_reference);
+/* host-buffer twin: W and W_reference [n_rings][n] contiguous; the host checks of sdx_disk_integrate_f64. */
+int sdx_disk_integrate_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale,
+                                   const double* ring_weights, double v_rot, const double* u, const double* u_reference,
+                                   const double* nus, double* W, double* W_reference);
 
 /* Everything in one call for resident data: pre-pass + line opacity + total (above) + raytrace (F_nu
  * overwritten).  F_nu is [n_depth][ld].  alpha_line_out and total_alphas ([n_depth][ld]) are OPTIONAL outputs (NULL: the

@@ -180,6 +180,8 @@ PROTOTYPES = {
     "sdx_emergent_intensity_f64": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "sdx_response_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
     "sdx_response_f64": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_response_angles_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
+    "sdx_response_angles_f64": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sdx_response_project_dev": (_int, [_vp, _int, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "sdx_mean_intensity_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64]),
     "sdx_scatter_source_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, C.c_double, _int, _vp, _i64, _vp, _i64,
@@ -230,6 +232,10 @@ PROTOTYPES = {
     "sdx_rotate_moments_f64": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sdx_disk_integrate_dev": (_int, [_vp, _i64, _vp, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "sdx_disk_integrate_f64": (_int, [_vp, _i64, _vp, _int, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
+    "sdx_disk_integrate_deriv_dev": (_int, [_vp, _i64, _vp, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_disk_integrate_deriv_f64": (_int, [_vp, _i64, _vp, _int, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
+    "sdx_disk_integrate_adjoint_dev": (_int, [_vp, _i64, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sdx_disk_integrate_adjoint_f64": (_int, [_vp, _i64, _vp, _int, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "sdx_synthesize_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, C.POINTER(Continuum), _int,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sdx_synthesize_ex_dev": (_int, [_vp, _int, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _int, _vp, C.POINTER(Continuum), _int,

@@ -4573,12 +4573,18 @@ __global__ __launch_bounds__(kBlock) void k_formation_mean(int n_depth, int64_t 
 // The layout is k_contribution's — lane <-> (frequency, angle), (S, sqrt(alpha)) pairs staged per wave from a FINISHED total_alphas
 // plane, the terms of kRtBatch rows summed over theta through LDS in the flux's order — in a workgroup of one wave (RtResponse).
 // Either output may be NULL: its terms are neither formed nor stored.
-__global__ __launch_bounds__(kRespBlock) void k_response(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
-                                                       const double* __restrict__ nus, const double* __restrict__ temps,
-                                                       const double* __restrict__ ray_dist, const double* __restrict__ wts,
-                                                       const double* __restrict__ alphas, int64_t ald, const double* __restrict__ source,
-                                                       int64_t sld, double* __restrict__ Ra, int64_t rald, double* __restrict__ Rs,
-                                                       int64_t rsld, int gpw)
+// The body with a compile-time flag, k_response (kAngles false: the code as it always was, wld unused) and k_response_angles below.
+// kAngles (sdx_response_angles_dev): wts is a plane cot[theta][wld] and a ray's terms are weighted with ITS OWN
+// frequency's cot[theta][nu] where the flux's w_theta stands otherwise — the response of sum_theta cot[theta][nu] I_theta(nu), the cotangent
+// of the emergent intensities.  Nothing else differs: the same walks, the same LDS layout, the same theta sum; cot[theta][nu] = w_theta
+// gives k_response's bits.
+template <bool kAngles>
+__device__ __forceinline__ void response_body(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
+                                              const double* __restrict__ nus, const double* __restrict__ temps,
+                                              const double* __restrict__ ray_dist, const double* __restrict__ wts, int64_t wld,
+                                              const double* __restrict__ alphas, int64_t ald, const double* __restrict__ source,
+                                              int64_t sld, double* __restrict__ Ra, int64_t rald, double* __restrict__ Rs,
+                                              int64_t rsld, int gpw)
 {
     constexpr int kBatch = kRtBatch;
     extern __shared__ double smem[];
@@ -4609,7 +4615,7 @@ __global__ __launch_bounds__(kRespBlock) void k_response(int n_depth, int64_t n_
     const int gi = (active ? grp : 0) * col;            // idle lanes shadow group 0 and never store
     const int slot = (active ? grp : 0) * G + g;        // (their slot is group 0's: a valid read)
     const int th = min(g, n_theta - 1);
-    const double wt = g < n_theta ? wts[th] : 0.0;
+    const double wt = g < n_theta ? (kAngles ? wts[(size_t)th * wld + ic] : wts[th]) : 0.0;
     const double* rd = ray_dist + th;                   // rd[gap * theta_stride]
 
     // ---- walk 1, from the bottom up: I[j], the intensity entering gap j (I[0] = 0, :134) ----
@@ -4701,6 +4707,25 @@ __global__ __launch_bounds__(kRespBlock) void k_response(int n_depth, int64_t n_
         }
         wave_sync();
     }
+}
+
+__global__ __launch_bounds__(kRespBlock) void k_response(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
+                                                       const double* __restrict__ nus, const double* __restrict__ temps,
+                                                       const double* __restrict__ ray_dist, const double* __restrict__ wts,
+                                                       const double* __restrict__ alphas, int64_t ald, const double* __restrict__ source,
+                                                       int64_t sld, double* __restrict__ Ra, int64_t rald, double* __restrict__ Rs,
+                                                       int64_t rsld, int gpw)
+{
+    response_body<false>(n_depth, n_nu, n_theta, theta_stride, G, nus, temps, ray_dist, wts, 0, alphas, ald, source, sld, Ra, rald, Rs, rsld, gpw);
+}
+__global__ __launch_bounds__(kRespBlock) void k_response_angles(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
+                                                              const double* __restrict__ nus, const double* __restrict__ temps,
+                                                              const double* __restrict__ ray_dist, const double* __restrict__ cot, int64_t cld,
+                                                              const double* __restrict__ alphas, int64_t ald,
+                                                              const double* __restrict__ source, int64_t sld, double* __restrict__ Ra,
+                                                              int64_t rald, double* __restrict__ Rs, int64_t rsld, int gpw)
+{
+    response_body<true>(n_depth, n_nu, n_theta, theta_stride, G, nus, temps, ray_dist, cot, cld, alphas, ald, source, sld, Ra, rald, Rs, rsld, gpw);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -5946,12 +5971,11 @@ struct RotSampledStage {
 
 // The first launch of a stage's adjoint: a[i] = u[i] / den_i, a_ref[i] = u_ref[i] / den_i (u_ref = nullptr: none); a stage that is not
 // on: den = 1
-template <class Stage>
-__device__ __forceinline__ void stage_adjoint_den(int64_t n, const double* __restrict__ lam, const double* __restrict__ scalars,
-                                                  const double* __restrict__ u, const double* __restrict__ u_ref, double* __restrict__ a,
-                                                  double* __restrict__ a_ref)
+template <class Stage, class Profile>
+__device__ __forceinline__ void stage_adjoint_den_of(int64_t n, const double* __restrict__ lam, const Profile& r,
+                                                     const double* __restrict__ u, const double* __restrict__ u_ref, double* __restrict__ a,
+                                                     double* __restrict__ a_ref)
 {
-    const auto r = Stage::load(scalars);
     RotLane m;
     if (!rot_mapping(n, lam, Stage::width(r), r.on, m)) return;
     double den = 1.0;
@@ -5960,15 +5984,29 @@ __device__ __forceinline__ void stage_adjoint_den(int64_t n, const double* __res
     a[m.pi] = r.on ? u[m.pi] / den : u[m.pi];
     if (u_ref) a_ref[m.pi] = r.on ? u_ref[m.pi] / den : u_ref[m.pi];
 }
+template <class Stage>
+__device__ __forceinline__ void stage_adjoint_den(int64_t n, const double* __restrict__ lam, const double* __restrict__ scalars,
+                                                  const double* __restrict__ u, const double* __restrict__ u_ref, double* __restrict__ a,
+                                                  double* __restrict__ a_ref)
+{
+    stage_adjoint_den_of<Stage>(n, lam, Stage::load(scalars), u, u_ref, a, a_ref);
+}
 
 // The second: w_j = sum over the candidates i that include node j of w_ij a_i, round-robin over the node's lanes in ascending i, closed
 // by the butterfly; a stage that is not on copies a.  The accesses and trips are bounded as stated above k_rotate.
-template <class Stage>
-__device__ __forceinline__ void stage_adjoint(int64_t n, const double* __restrict__ lam, const double* __restrict__ scalars,
-                                              const double* __restrict__ a, const double* __restrict__ a_ref, const double* __restrict__ nus,
-                                              double* __restrict__ w_out, double* __restrict__ w_ref)
+// (stage_out: what a stage does to a node's sum before the nu / lambda factor — nothing, but for a disk's ring, which applies its flux
+// weight: the overload for DiskRing, declared with it further down, is the one an instantiation with that profile finds.  The *_of forms
+// take the stage's profile already loaded — a disk has one per ring —, the forms without load it from the stage's device scalars.)
+template <class Profile>
+__device__ __forceinline__ double stage_out(const Profile&, double w)
 {
-    const auto r = Stage::load(scalars);
+    return w;
+}
+template <class Stage, class Profile>
+__device__ __forceinline__ void stage_adjoint_of(int64_t n, const double* __restrict__ lam, const Profile& r,
+                                                 const double* __restrict__ a, const double* __restrict__ a_ref, const double* __restrict__ nus,
+                                                 double* __restrict__ w_out, double* __restrict__ w_ref)
+{
     RotLane m;
     if (!rot_mapping(n, lam, Stage::width(r), r.on, m)) return;
     const int64_t j = m.on ? m.pi : n - 1;
@@ -5992,9 +6030,17 @@ __device__ __forceinline__ void stage_adjoint(int64_t n, const double* __restric
         if (a_ref) wr = a_ref[j];
     }
     if (m.t != 0 || !m.on) return;
+    wf = stage_out(r, wf), wr = stage_out(r, wr);
     // (the transpose of k_flux_nu_to_lambda, as k_observe_adjoint ends)
     w_out[j] = nus ? mul_rn(wf, nus[j]) / lj : wf;
     if (w_ref) w_ref[j] = nus ? mul_rn(wr, nus[j]) / lj : wr;
+}
+template <class Stage>
+__device__ __forceinline__ void stage_adjoint(int64_t n, const double* __restrict__ lam, const double* __restrict__ scalars,
+                                              const double* __restrict__ a, const double* __restrict__ a_ref, const double* __restrict__ nus,
+                                              double* __restrict__ w_out, double* __restrict__ w_ref)
+{
+    stage_adjoint_of<Stage>(n, lam, Stage::load(scalars), a, a_ref, nus, w_out, w_ref);
 }
 
 __global__ __launch_bounds__(kBlock) void k_rotate_adjoint_den(int64_t n, const double* __restrict__ lam, const double* __restrict__ rot,
@@ -6371,8 +6417,10 @@ __device__ __forceinline__ void arc_moments(double a, double b, double d, double
         }
     }
 }
-// point i's cell [a, b] = [j, j + 1] of a ring of reach `reach` (self as for rot_cell); false: the cell does not count
-__device__ __forceinline__ bool disk_cell(double reach, double lam_i, double lam_a, double lam_b, int self, double& m0, double& r)
+// point i's cell [a, b] = [j, j + 1] of a ring of reach `reach` (self as for rot_cell); false: the cell does not count.
+// t (nullptr: not formed): M1 / Delta with M1 over the clamped cell, the cell's coefficient in d / d ln V
+__device__ __forceinline__ bool disk_cell(double reach, double lam_i, double lam_a, double lam_b, int self, double& m0, double& r,
+                                          double* t = nullptr)
 {
     const double ya = self == 0 ? 0.0 : sub_rn(lam_a, lam_i) / reach, yb = self == 1 ? 0.0 : sub_rn(lam_b, lam_i) / reach;
     const double ca = fmin(fmax(ya, -1.0), 1.0), cb = fmin(fmax(yb, -1.0), 1.0);
@@ -6382,13 +6430,76 @@ __device__ __forceinline__ bool disk_cell(double reach, double lam_i, double lam
     double m1;
     arc_moments(ca, cb, d, m0, m1);
     r = sub_rn(m1, mul_rn(ya, m0)) / delta;
+    if (t) *t = m1 / delta;
     return true;
 }
+// y K(y) = y / (pi sqrt((1 - y)(1 + y))) at an end of the grid seen from point i: the end term of a truncated window in d / d ln V; 0 where
+// the window does not reach the end (|y| >= 1) or the end is the point itself.  1 - |y| = (reach - |lam_end - lam_i|) / reach, the
+// difference first, as rot_end_term forms it.  K is singular at |y| = 1: an end within 1e-5 of a ring's edge is outside the
+// derivative's contract (include/stardis_hip.h).
+__device__ __forceinline__ double disk_end_term(double reach, double lam_i, double lam_end, bool self)
+{
+    if (self) return 0.0;
+    const double dl = sub_rn(lam_end, lam_i), ay = fabs(dl);
+    const double u = sub_rn(reach, ay) / reach;
+    if (!(u > 0.0)) return 0.0;
+    const double q = mul_rn(u, add_rn(1.0, ay / reach));
+    return (dl / reach) / mul_rn(kPi, __dsqrt_rn(q));
+}
+
+// What the point's lanes sum over the cells of one ring, closed by the butterfly, in every lane of the point: num, numr (Ir, Gr; nullptr:
+// not formed), den and, with kDeriv, tnum = sum_g (M1_g / Delta_g) (I[j+1] - I[j]) and tnumr.  The forward kernel and the adjoint's
+// denominators call it (the mapping m is the forward's in both), so den has the same bits in both.  Every lane of the wave calls it;
+// `on` false: nothing is searched or read.
+struct DiskSums {
+    double num, numr, den, tnum, tnumr;
+};
+template <bool kDeriv>
+__device__ __forceinline__ void disk_ring_sums(int64_t n, const double* __restrict__ lam, const double* __restrict__ Ir,
+                                               const double* __restrict__ Gr, int64_t i, double li, double reach, bool on, const RotLane& m,
+                                               DiskSums& s)
+{
+    int64_t i0, i1;
+    obs_windows(lam, lam, n, 1.0, sub_rn(li, reach), add_rn(li, reach), on, m.W, m.lane, i0, i1);
+    const int64_t g0 = i0 > 0 ? i0 - 1 : 0, g1 = i1 < n - 1 ? i1 : n - 1;  // the window's cells and the partial cell on each side
+    s = DiskSums{0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int64_t g = g0 + m.t; on && g < g1; g += m.W) {
+        double m0, sh, t = 0.0;
+        if (!disk_cell(reach, li, lam[g], lam[g + 1], g == i ? 0 : (g + 1 == i ? 1 : -1), m0, sh, kDeriv ? &t : nullptr)) continue;
+        const double wa = sub_rn(m0, sh);
+        s.den = add_rn(s.den, m0);
+        if (Ir) {
+            const double fa = Ir[g], fb = Ir[g + 1];
+            s.num = add_rn(add_rn(s.num, mul_rn(wa, fa)), mul_rn(sh, fb));
+            if (kDeriv) s.tnum = add_rn(s.tnum, mul_rn(t, sub_rn(fb, fa)));
+        }
+        if (Gr) {
+            const double ga = Gr[g], gb = Gr[g + 1];
+            s.numr = add_rn(add_rn(s.numr, mul_rn(wa, ga)), mul_rn(sh, gb));
+            if (kDeriv) s.tnumr = add_rn(s.tnumr, mul_rn(t, sub_rn(gb, ga)));
+        }
+    }
+    for (int off = m.W >> 1; off > 0; off >>= 1) {
+        s.num = add_rn(s.num, __shfl_xor(s.num, off)), s.numr = add_rn(s.numr, __shfl_xor(s.numr, off));
+        s.den = add_rn(s.den, __shfl_xor(s.den, off));
+        if (kDeriv) s.tnum = add_rn(s.tnum, __shfl_xor(s.tnum, off)), s.tnumr = add_rn(s.tnumr, __shfl_xor(s.tnumr, off));
+    }
+}
+
+// kDeriv false: the forward sum alone (dlnv, dlnv_ref unused).  kDeriv true: also d out / d ln V, exact for the discrete operator (the
+// spectrum is piecewise linear and the domain over lambda does not move, so no integration by parts is needed): per ring, reach > 0,
+//     dnum = sum_g (M1_g / Delta_g) (I[j+1] - I[j]) - e_hi I[n-1] + e_lo I[0],   dden = -e_hi + e_lo,
+//     e_hi = y_hi K(y_hi) where the window is truncated above (y_hi = (lam[n-1] - lam_i) / reach < 1), e_lo = y_lo K(y_lo) where it is
+//     truncated below (y_lo = (lam[0] - lam_i) / reach > -1), else 0 (disk_end_term),
+//     dA_r[i] = (dnum - A_r[i] dden) / den,   dout[i] = sum_r w_r dA_r[i] in the flux's order;
+// !(reach > 0) contributes 0, !(V > 0) gives zeros.  out and out_ref are the same operations on the same operands in both.
+template <bool kDeriv>
 __global__ __launch_bounds__(kBlock) void k_disk_integrate(int64_t n, const double* __restrict__ lam, int n_rings,
                                                            const double* __restrict__ scale, const double* __restrict__ wts,
                                                            const double* __restrict__ I, int64_t ild, const double* __restrict__ I_ref,
                                                            const double* __restrict__ rot, double* __restrict__ out,
-                                                           double* __restrict__ out_ref)
+                                                           double* __restrict__ out_ref, double* __restrict__ dlnv,
+                                                           double* __restrict__ dlnv_ref)
 {
     const double V = rot[0], beta = V / kCKms;  // (the pair's limb darkening is not read: every ring has its own spectrum)
     RotLane m;
@@ -6397,36 +6508,118 @@ __global__ __launch_bounds__(kBlock) void k_disk_integrate(int64_t n, const doub
     const double li = lam[i];
     const int half = (n_rings + 1) >> 1;
     double lower = 0.0, upper = 0.0, lower_ref = 0.0, upper_ref = 0.0;
+    double dlower = 0.0, dupper = 0.0, dlower_ref = 0.0, dupper_ref = 0.0;
     for (int r = 0; r < n_rings; ++r) {
         const double* __restrict__ Ir = I + (size_t)r * ild;
         const double* __restrict__ Gr = I_ref ? I_ref + (size_t)r * ild : nullptr;
         const double beta_r = mul_rn(beta, scale[r]), reach = mul_rn(li, beta_r);
         double a = Ir[i], a_ref = Gr ? Gr[i] : 0.0;  // !(reach > 0): a copy
+        double da = 0.0, da_ref = 0.0;
         if (beta_r > 0.0) {                          // (the same in every lane of the wave)
-            const bool on = m.on && reach > 0.0;
-            int64_t i0, i1;
-            obs_windows(lam, lam, n, 1.0, sub_rn(li, reach), add_rn(li, reach), on, m.W, m.lane, i0, i1);
-            const int64_t g0 = i0 > 0 ? i0 - 1 : 0, g1 = i1 < n - 1 ? i1 : n - 1;  // the window's cells and the partial cell on each side
-            double num = 0.0, numr = 0.0, den = 0.0;
-            for (int64_t g = g0 + m.t; on && g < g1; g += m.W) {
-                double m0, sh;
-                if (!disk_cell(reach, li, lam[g], lam[g + 1], g == i ? 0 : (g + 1 == i ? 1 : -1), m0, sh)) continue;
-                const double wa = sub_rn(m0, sh);
-                den = add_rn(den, m0);
-                num = add_rn(add_rn(num, mul_rn(wa, Ir[g])), mul_rn(sh, Ir[g + 1]));
-                if (Gr) numr = add_rn(add_rn(numr, mul_rn(wa, Gr[g])), mul_rn(sh, Gr[g + 1]));
+            DiskSums s;
+            disk_ring_sums<kDeriv>(n, lam, Ir, Gr, i, li, reach, m.on && reach > 0.0, m, s);
+            if (reach > 0.0) {
+                a = s.num / s.den, a_ref = s.numr / s.den;
+                if (kDeriv) {
+                    const double e_lo = disk_end_term(reach, li, lam[0], i == 0), e_hi = disk_end_term(reach, li, lam[n - 1], i == n - 1);
+                    const double dden = sub_rn(e_lo, e_hi);
+                    da = sub_rn(add_rn(s.tnum, sub_rn(mul_rn(e_lo, Ir[0]), mul_rn(e_hi, Ir[n - 1]))), mul_rn(a, dden)) / s.den;
+                    if (Gr) da_ref = sub_rn(add_rn(s.tnumr, sub_rn(mul_rn(e_lo, Gr[0]), mul_rn(e_hi, Gr[n - 1]))), mul_rn(a_ref, dden)) / s.den;
+                }
             }
-            for (int off = m.W >> 1; off > 0; off >>= 1)
-                num = add_rn(num, __shfl_xor(num, off)), numr = add_rn(numr, __shfl_xor(numr, off)), den = add_rn(den, __shfl_xor(den, off));
-            if (reach > 0.0) a = num / den, a_ref = numr / den;
         }
         const double w = wts[r], term = mul_rn(a, w), term_ref = mul_rn(a_ref, w);
         if (r < half) lower = add_rn(lower, term), lower_ref = add_rn(lower_ref, term_ref);
         else upper = add_rn(upper, term), upper_ref = add_rn(upper_ref, term_ref);
+        if (kDeriv) {
+            const double dterm = mul_rn(da, w), dterm_ref = mul_rn(da_ref, w);
+            if (r < half) dlower = add_rn(dlower, dterm), dlower_ref = add_rn(dlower_ref, dterm_ref);
+            else dupper = add_rn(dupper, dterm), dupper_ref = add_rn(dupper_ref, dterm_ref);
+        }
     }
     if (m.t != 0 || !m.on) return;
     out[m.pi] = add_rn(lower, upper);
     if (I_ref) out_ref[m.pi] = add_rn(lower_ref, upper_ref);
+    if (kDeriv) {
+        dlnv[m.pi] = add_rn(dlower, dupper);
+        if (I_ref && dlnv_ref) dlnv_ref[m.pi] = add_rn(dlower_ref, dupper_ref);
+    }
+}
+
+// The transpose of k_disk_integrate (include/stardis_hip.h, sdx_disk_integrate_adjoint_dev).  The cotangent of a disk-integrated spectrum
+// is a plane over (ring, node), each ring's spectrum being convolved with its own kernel:
+//     W[r][j] = w_r sum_i (u_i / den_r(i)) ((M0 - r) of cell [j, j + 1] + r of cell [j - 1, j] in point i's row for ring r),
+// disk_cell deciding, so the weights are the forward's bit for bit.  It is the broadening stages' pair per ring (blockIdx.y): a_r[i] = u_i /
+// den_r(i) through disk_ring_sums in the forward's mapping (k_disk_integrate_adjoint_den), then the gather over the candidates
+// lam_i in [lam_{j-1} / (1 + beta_r), lam_{j+1} / (1 - beta_r)] (k_disk_integrate_adjoint; stage_adjoint_of), times w_r, times nu_j / lam_j
+// where nus is given.  A ring with !(beta_r > 0) passes w_r u_j through, as does a point whose own reach is not positive.
+struct DiskRing {
+    double beta, beta_r, weight;  // V / c (the mapping's: the widest ring a disk can have), beta ring_scale[r], w_r
+    bool on;                      // beta_r > 0
+};
+__device__ __forceinline__ DiskRing disk_ring(const double* __restrict__ rot, const double* __restrict__ scale, const double* __restrict__ wts, int r)
+{
+    const double beta = rot[0] / kCKms, beta_r = mul_rn(beta, scale[r]);
+    return DiskRing{beta, beta_r, wts[r], beta_r > 0.0};
+}
+__device__ __forceinline__ double stage_out(const DiskRing& r, double w)
+{
+    return mul_rn(r.weight, w);
+}
+struct DiskStage {
+    struct Node {
+        double below, above;  // lam_{j-1}, lam_{j+1}, clamped to the grid
+    };
+    static __device__ __forceinline__ double width(const DiskRing& r) { return 2.0 * r.beta; }
+    static __device__ __forceinline__ double den(int64_t n, const double* __restrict__ lam, const DiskRing& r, const RotLane& m)
+    {
+        const int64_t i = m.on ? m.pi : n - 1;
+        const double li = lam[i], reach = mul_rn(li, r.beta_r);
+        DiskSums s;
+        disk_ring_sums<false>(n, lam, nullptr, nullptr, i, li, reach, m.on && reach > 0.0, m, s);
+        return reach > 0.0 ? s.den : 1.0;
+    }
+    static __device__ __forceinline__ Node node(int64_t n, const double* __restrict__ lam, int64_t j)
+    {
+        return Node{lam[j > 0 ? j - 1 : 0], lam[j < n - 1 ? j + 1 : n - 1]};
+    }
+    static __device__ __forceinline__ void candidates(const DiskRing& r, const Node& nd, double, double& lo, double& hi)
+    {
+        double unused;
+        rot_candidates(nd.below, r.beta_r, lo, unused);
+        rot_candidates(nd.above, r.beta_r, unused, hi);
+    }
+    static __device__ __forceinline__ bool weight(const DiskRing& r, const Node& nd, int64_t n, int64_t i, int64_t j, double lam_i, double lj, double& w)
+    {
+        const double reach = mul_rn(lam_i, r.beta_r);
+        w = 1.0;
+        if (!(reach > 0.0)) return i == j;  // (the forward's copy)
+        double m0, sh;
+        bool any = false;
+        w = 0.0;
+        if (j > 0 && disk_cell(reach, lam_i, nd.below, lj, j - 1 == i ? 0 : (j == i ? 1 : -1), m0, sh)) w = sh, any = true;
+        if (j < n - 1 && disk_cell(reach, lam_i, lj, nd.above, j == i ? 0 : (j + 1 == i ? 1 : -1), m0, sh)) w = add_rn(w, sub_rn(m0, sh)), any = true;
+        return any;
+    }
+};
+// a, a_ref: [n_rings][row] doubles; blockIdx.y: the ring
+__global__ __launch_bounds__(kBlock) void k_disk_integrate_adjoint_den(int64_t n, const double* __restrict__ lam, const double* __restrict__ scale,
+                                                                       const double* __restrict__ wts, const double* __restrict__ rot,
+                                                                       const double* __restrict__ u, const double* __restrict__ u_ref,
+                                                                       double* __restrict__ a, double* __restrict__ a_ref, int64_t row)
+{
+    const int r = blockIdx.y;
+    stage_adjoint_den_of<DiskStage>(n, lam, disk_ring(rot, scale, wts, r), u, u_ref, a + (size_t)r * row, u_ref ? a_ref + (size_t)r * row : nullptr);
+}
+__global__ __launch_bounds__(kBlock) void k_disk_integrate_adjoint(int64_t n, const double* __restrict__ lam, const double* __restrict__ scale,
+                                                                   const double* __restrict__ wts, const double* __restrict__ rot,
+                                                                   const double* __restrict__ a, const double* __restrict__ a_ref, int64_t row,
+                                                                   const double* __restrict__ nus, double* __restrict__ W, double* __restrict__ W_ref,
+                                                                   int64_t wld)
+{
+    const int r = blockIdx.y;
+    stage_adjoint_of<DiskStage>(n, lam, disk_ring(rot, scale, wts, r), a + (size_t)r * row, a_ref ? a_ref + (size_t)r * row : nullptr, nus,
+                                W + (size_t)r * wld, W_ref ? W_ref + (size_t)r * wld : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -2484,27 +2484,54 @@ int sdx_emergent_intensity_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_th
 
 // ---- response functions (k_response, k_response_project) -------------------------------------------------------------------
 // As for the contribution function, everything is checked before anything is enqueued, also for an empty grid.
+// wts: the flux weights [n_theta], or with `angles` the cotangent plane [n_theta][wld] (k_response_angles)
+static int response_launch(sdx_ctx* ctx, bool angles, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
+                           const double* ray_dist, const double* wts, int64_t wld, const double* alphas, int64_t ald, const double* source,
+                           int64_t source_ld, double* R_alpha, int64_t R_alpha_ld, double* R_source, int64_t R_source_ld)
+{
+    const char* const stage = angles ? "k_response_angles" : "k_response";
+    const auto msg = [&](const char* text) { return std::string(stage + 2) + text; };
+    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, msg(": need n_depth >= 2, n_theta > 0"));
+    REQUIRE(!ctx->mixed_precision, msg(": no response functions with mixed_precision = 1 (they differentiate the fp64 formal solution)"));
+    REQUIRE(n_theta <= 64, msg(": more than 64 angles are not supported (all angles are traced in one launch)"));
+    const int G = n_theta;
+    const int gpw = rt_fit_gpw<RtResponse>(G, n_depth);
+    REQUIRE(gpw > 0, msg(": no response functions for models this deep (the columns and the stashed intensities do not fit LDS)"));
+    if (n_nu == 0) return SDX_OK;
+    REQUIRE(R_alpha || R_source, msg(": no output requested"));
+    REQUIRE(nus && ray_dist && wts && alphas && ald >= n_nu, msg(": null pointer or alpha_ld below n_nu"));
+    REQUIRE(!angles || wld >= n_nu, msg(": cot_ld below n_nu"));
+    REQUIRE((!R_alpha || R_alpha_ld >= n_nu) && (!R_source || R_source_ld >= n_nu), msg(": leading dimension of an output below n_nu"));
+    REQUIRE(source ? source_ld >= n_nu : temps != nullptr, msg(": bad source plane (source_ld < n_nu), or neither a source plane nor temperatures"));
+    for (const double* o : {(const double*)R_alpha, (const double*)R_source})
+        REQUIRE(!angles || !o || o != wts, msg(": not in place (an output must not be the cotangent)"));
+    {
+        LaunchScope ls(ctx, stage);
+        if (angles)
+            hipLaunchKernelGGL(k_response_angles, dim3(response_blocks(n_nu, gpw)), dim3(kRespBlock), RtResponse(G, n_depth, gpw).bytes(), ctx->stream, n_depth,
+                               n_nu, n_theta, n_theta, G, nus, temps, ray_dist, wts, wld, alphas, ald, source, source_ld, R_alpha, R_alpha_ld, R_source, R_source_ld,
+                               gpw);
+        else
+            hipLaunchKernelGGL(k_response, dim3(response_blocks(n_nu, gpw)), dim3(kRespBlock), RtResponse(G, n_depth, gpw).bytes(), ctx->stream, n_depth, n_nu,
+                               n_theta, n_theta, G, nus, temps, ray_dist, wts, alphas, ald, source, source_ld, R_alpha, R_alpha_ld, R_source, R_source_ld, gpw);
+    }
+    return check_launch(stage);
+}
+
 int sdx_response_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
                      const double* wts, const double* alphas, int64_t ald, const double* source, int64_t source_ld, double* R_alpha,
                      int64_t R_alpha_ld, double* R_source, int64_t R_source_ld)
 {
-    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "response: need n_depth >= 2, n_theta > 0");
-    REQUIRE(!ctx->mixed_precision, "response: no response functions with mixed_precision = 1 (they differentiate the fp64 formal solution)");
-    REQUIRE(n_theta <= 64, "response: more than 64 angles are not supported (all angles are traced in one launch)");
-    const int G = n_theta;
-    const int gpw = rt_fit_gpw<RtResponse>(G, n_depth);
-    REQUIRE(gpw > 0, "response: no response functions for models this deep (the columns and the stashed intensities do not fit LDS)");
-    if (n_nu == 0) return SDX_OK;
-    REQUIRE(R_alpha || R_source, "response: no output requested");
-    REQUIRE(nus && ray_dist && wts && alphas && ald >= n_nu, "response: null pointer or alpha_ld below n_nu");
-    REQUIRE((!R_alpha || R_alpha_ld >= n_nu) && (!R_source || R_source_ld >= n_nu), "response: leading dimension of an output below n_nu");
-    REQUIRE(source ? source_ld >= n_nu : temps != nullptr, "response: bad source plane (source_ld < n_nu), or neither a source plane nor temperatures");
-    {
-        LaunchScope ls(ctx, "k_response");
-        hipLaunchKernelGGL(k_response, dim3(response_blocks(n_nu, gpw)), dim3(kRespBlock), RtResponse(G, n_depth, gpw).bytes(), ctx->stream, n_depth, n_nu, n_theta,
-                           n_theta, G, nus, temps, ray_dist, wts, alphas, ald, source, source_ld, R_alpha, R_alpha_ld, R_source, R_source_ld, gpw);
-    }
-    return check_launch("k_response");
+    return response_launch(ctx, false, n_depth, n_nu, n_theta, nus, temps, ray_dist, wts, 0, alphas, ald, source, source_ld, R_alpha, R_alpha_ld, R_source,
+                           R_source_ld);
+}
+
+int sdx_response_angles_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                            const double* cotangent, int64_t cot_ld, const double* alphas, int64_t ald, const double* source, int64_t source_ld,
+                            double* R_alpha, int64_t R_alpha_ld, double* R_source, int64_t R_source_ld)
+{
+    return response_launch(ctx, true, n_depth, n_nu, n_theta, nus, temps, ray_dist, cotangent, cot_ld, alphas, ald, source, source_ld, R_alpha, R_alpha_ld,
+                           R_source, R_source_ld);
 }
 
 int sdx_response_project_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* R_alpha, int64_t R_ld, const double* part, int64_t part_ld,
@@ -2520,14 +2547,15 @@ int sdx_response_project_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const doub
     return check_launch("k_response_project");
 }
 
-int sdx_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
-                     const double* wts, const double* alphas, const double* source, double* R_alpha, double* R_source)
+// wts: [n_theta], or with `angles` the cotangent [n_theta][n_nu]
+static int response_host(sdx_ctx* ctx, bool angles, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
+                         const double* ray_dist, const double* wts, const double* alphas, const double* source, double* R_alpha, double* R_source)
 {
     REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "response: need n_depth >= 2, n_theta > 0");
     REQUIRE(n_nu == 0 || (nus && temps && ray_dist && wts && alphas), "response: null pointer");
     REQUIRE(n_nu == 0 || R_alpha || R_source, "response: no output requested");
     int rc;
-    if ((rc = sdx_response_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0)) || n_nu == 0)
+    if ((rc = response_launch(ctx, angles, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0)) || n_nu == 0)
         return rc;  // refusals before any copy
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
@@ -2537,16 +2565,28 @@ int sdx_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const
     plan.in(nus, (size_t)n_nu * f8, &d_nus);
     plan.in(temps, (size_t)n_depth * f8, &d_t);
     plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
-    plan.in(wts, (size_t)n_theta * f8, &d_w);
+    plan.in(wts, (angles ? (size_t)n_theta * n_nu : (size_t)n_theta) * f8, &d_w);
     plan.in(alphas, plane, &d_a);
     plan.in(source, plane, &d_s);
     plan.out(R_alpha, plane, &d_ra);
     plan.out(R_source, plane, &d_rs);
     HostIo io{ctx};
     if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_response_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_s, n_nu, d_ra, n_nu, d_rs, n_nu))) return rc;
+    if ((rc = response_launch(ctx, angles, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, n_nu, d_a, n_nu, d_s, n_nu, d_ra, n_nu, d_rs, n_nu))) return rc;
     if ((rc = io.collect(plan))) return rc;
     return io.finish();
+}
+
+int sdx_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                     const double* wts, const double* alphas, const double* source, double* R_alpha, double* R_source)
+{
+    return response_host(ctx, false, n_depth, n_nu, n_theta, nus, temps, ray_dist, wts, alphas, source, R_alpha, R_source);
+}
+
+int sdx_response_angles_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                            const double* cotangent, const double* alphas, const double* source, double* R_alpha, double* R_source)
+{
+    return response_host(ctx, true, n_depth, n_nu, n_theta, nus, temps, ray_dist, cotangent, alphas, source, R_alpha, R_source);
 }
 
 // ---- mean intensity and the scattering source function (k_lambda) ----------------------------------------------------------
@@ -3786,35 +3826,74 @@ static int disk_integrate_check(sdx_ctx* ctx, int64_t n, const double* lambdas, 
     return distinct_buffers("disk_integrate", ins, 6, outs, 2);
 }
 
-int sdx_disk_integrate_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale, const double* ring_weights,
-                           const double* I, int64_t I_ld, const double* I_reference, const double* rot_dev, double* out, double* out_reference)
+// deriv: k_disk_integrate<true>, which also writes d out / d ln V (dout_lnv required, dout_lnv_reference optional with a reference)
+static int disk_integrate_launch(sdx_ctx* ctx, bool deriv, int64_t n, const double* lambdas, int n_rings, const double* ring_scale,
+                                 const double* ring_weights, const double* I, int64_t I_ld, const double* I_reference, const double* rot_dev,
+                                 double* out, double* out_reference, double* dout_lnv, double* dout_lnv_reference)
 {
     int rc;
     if ((rc = disk_integrate_check(ctx, n, lambdas, n_rings, ring_scale, ring_weights, I, I_reference, rot_dev, out, out_reference))) return rc;
     REQUIRE(rot_dev, "disk_integrate: null pointer (rot_dev is required)");
     REQUIRE(I_ld >= n, "disk_integrate: I_ld below n");
+    if (deriv) {
+        REQUIRE(dout_lnv, "disk_integrate: null pointer (dout_lnv is required)");
+        REQUIRE(!dout_lnv_reference || I_reference, "disk_integrate: dout_lnv_reference needs I_reference");
+        const double* const ins[6] = {lambdas, ring_scale, ring_weights, I, I_reference, rot_dev};
+        const double* const outs[4] = {out, out_reference, dout_lnv, dout_lnv_reference};
+        if ((rc = distinct_buffers("disk_integrate", ins, 6, outs, 4))) return rc;
+    }
     REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "disk_integrate: too many points for one launch");
     HIP_TRY(hipSetDevice(ctx->device));
     {
         LaunchScope ls(ctx, "k_disk_integrate");
-        hipLaunchKernelGGL(k_disk_integrate, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, n_rings, ring_scale, ring_weights, I, I_ld,
-                           I_reference, rot_dev, out, out_reference);
+        if (deriv)
+            hipLaunchKernelGGL(k_disk_integrate<true>, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, n_rings, ring_scale, ring_weights, I,
+                               I_ld, I_reference, rot_dev, out, out_reference, dout_lnv, dout_lnv_reference);
+        else
+            hipLaunchKernelGGL(k_disk_integrate<false>, dim3(rotate_blocks(n)), dim3(kBlock), 0, ctx->stream, n, lambdas, n_rings, ring_scale, ring_weights, I,
+                               I_ld, I_reference, rot_dev, out, out_reference, (double*)nullptr, (double*)nullptr);
     }
     return check_launch("k_disk_integrate");
 }
 
-int sdx_disk_integrate_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale, const double* ring_weights,
-                           const double* I, const double* I_reference, double v_rot, double* out, double* out_reference)
+int sdx_disk_integrate_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale, const double* ring_weights,
+                           const double* I, int64_t I_ld, const double* I_reference, const double* rot_dev, double* out, double* out_reference)
+{
+    return disk_integrate_launch(ctx, false, n, lambdas, n_rings, ring_scale, ring_weights, I, I_ld, I_reference, rot_dev, out, out_reference, nullptr,
+                                 nullptr);
+}
+
+int sdx_disk_integrate_deriv_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale, const double* ring_weights,
+                                 const double* I, int64_t I_ld, const double* I_reference, const double* rot_dev, double* out, double* out_reference,
+                                 double* dout_lnv, double* dout_lnv_reference)
+{
+    return disk_integrate_launch(ctx, true, n, lambdas, n_rings, ring_scale, ring_weights, I, I_ld, I_reference, rot_dev, out, out_reference, dout_lnv,
+                                 dout_lnv_reference);
+}
+
+// what the kernels cannot check: the disk twins do, before any upload
+static int disk_host_check(int64_t n, const double* lambdas, int n_rings, const double* ring_scale, double v_rot)
+{
+    int rc;
+    if ((rc = rotate_host_check(n, lambdas, v_rot, 0.0))) return rc;
+    for (int r = 0; r < n_rings; ++r) REQUIRE(ring_scale[r] >= 0.0 && ring_scale[r] <= 1.0, "disk_integrate: ring_scale must lie in [0, 1]");
+    return SDX_OK;
+}
+
+static int disk_integrate_host(sdx_ctx* ctx, bool deriv, int64_t n, const double* lambdas, int n_rings, const double* ring_scale,
+                               const double* ring_weights, const double* I, const double* I_reference, double v_rot, double* out,
+                               double* out_reference, double* dout_lnv, double* dout_lnv_reference)
 {
     int rc;
     if ((rc = disk_integrate_check(ctx, n, lambdas, n_rings, ring_scale, ring_weights, I, I_reference, nullptr, out, out_reference))) return rc;
-    if ((rc = rotate_host_check(n, lambdas, v_rot, 0.0))) return rc;
-    for (int r = 0; r < n_rings; ++r) REQUIRE(ring_scale[r] >= 0.0 && ring_scale[r] <= 1.0, "disk_integrate: ring_scale must lie in [0, 1]");
+    REQUIRE(!deriv || dout_lnv, "disk_integrate: null pointer (dout_lnv is required)");
+    REQUIRE(!dout_lnv_reference || I_reference, "disk_integrate: dout_lnv_reference needs I_reference");
+    if ((rc = disk_host_check(n, lambdas, n_rings, ring_scale, v_rot))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t f8 = sizeof(double), grid = (size_t)n * f8, rings = (size_t)n_rings * f8;
     const double pair[2] = {v_rot, 0.0};
     const double *d_l, *d_s, *d_w, *d_i, *d_r, *d_p;
-    double *d_o, *d_or;
+    double *d_o, *d_or, *d_d = nullptr, *d_dr = nullptr;
     HostPlan plan;
     plan.in(lambdas, grid, &d_l);
     plan.in(ring_scale, rings, &d_s);
@@ -3824,9 +3903,98 @@ int sdx_disk_integrate_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, int n
     plan.in(pair, 2 * f8, &d_p);
     plan.out(out, grid, &d_o);
     plan.out(out_reference, grid, &d_or);
+    if (deriv) {
+        plan.out(dout_lnv, grid, &d_d);
+        plan.out(dout_lnv_reference, grid, &d_dr);
+    }
     HostIo io{ctx};
     if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_disk_integrate_dev(ctx, n, d_l, n_rings, d_s, d_w, d_i, n, d_r, d_p, d_o, d_or))) return rc;
+    if ((rc = disk_integrate_launch(ctx, deriv, n, d_l, n_rings, d_s, d_w, d_i, n, d_r, d_p, d_o, d_or, d_d, d_dr))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+
+int sdx_disk_integrate_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale, const double* ring_weights,
+                           const double* I, const double* I_reference, double v_rot, double* out, double* out_reference)
+{
+    return disk_integrate_host(ctx, false, n, lambdas, n_rings, ring_scale, ring_weights, I, I_reference, v_rot, out, out_reference, nullptr, nullptr);
+}
+
+int sdx_disk_integrate_deriv_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale, const double* ring_weights,
+                                 const double* I, const double* I_reference, double v_rot, double* out, double* out_reference, double* dout_lnv,
+                                 double* dout_lnv_reference)
+{
+    return disk_integrate_host(ctx, true, n, lambdas, n_rings, ring_scale, ring_weights, I, I_reference, v_rot, out, out_reference, dout_lnv,
+                               dout_lnv_reference);
+}
+
+// ---- the transpose of the disk integration (k_disk_integrate_adjoint_den, k_disk_integrate_adjoint): the broadening stages' pair per ring
+static int disk_adjoint_check(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale, const double* ring_weights,
+                              const double* rot, const double* u, const double* u_reference, const double* nus, const double* W,
+                              const double* W_reference)
+{
+    REQUIRE(ctx, "disk_integrate_adjoint: null context");
+    REQUIRE(n >= 2, "disk_integrate_adjoint: the grid needs at least two points (n >= 2)");
+    REQUIRE(n_rings >= 1 && n_rings <= 64, "disk_integrate_adjoint: n_rings must lie in 1 .. 64");
+    REQUIRE(lambdas && ring_scale && ring_weights && u && W, "disk_integrate_adjoint: null pointer (lambdas, ring_scale, ring_weights, u and W are required)");
+    REQUIRE(!u_reference == !W_reference, "disk_integrate_adjoint: u_reference and W_reference go together");
+    const double* const ins[7] = {lambdas, ring_scale, ring_weights, u, u_reference, nus, rot};
+    const double* const outs[2] = {W, W_reference};
+    return distinct_buffers("disk_integrate_adjoint", ins, 7, outs, 2);
+}
+
+int sdx_disk_integrate_adjoint_dev(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale,
+                                   const double* ring_weights, const double* rot_dev, const double* u, const double* u_reference,
+                                   const double* nus, double* W, int64_t W_ld, double* W_reference)
+{
+    int rc;
+    if ((rc = disk_adjoint_check(ctx, n, lambdas, n_rings, ring_scale, ring_weights, rot_dev, u, u_reference, nus, W, W_reference))) return rc;
+    REQUIRE(rot_dev, "disk_integrate_adjoint: null pointer (rot_dev is required)");
+    REQUIRE(W_ld >= n, "disk_integrate_adjoint: W_ld below n");
+    REQUIRE((n + kObsGroup - 1) / (kBlock / 64) < ((int64_t)1 << 31), "disk_integrate_adjoint: too many points for one launch");
+    HIP_TRY(hipSetDevice(ctx->device));
+    // a_r = u / den_r: two blocks of n_rings rows in the stages' scratch (stage_adjoint), consumed between this call's two launches
+    const size_t row = ((size_t)n * sizeof(double) + 255) & ~(size_t)255, block = row * (size_t)n_rings;
+    if ((rc = ensure(ctx, &ctx->stage_ws, &ctx->stage_ws_bytes, 2 * block))) return rc;
+    double* const a = (double*)ctx->stage_ws;
+    double* const a_ref = (double*)((char*)ctx->stage_ws + block);
+    const int64_t row_doubles = (int64_t)(row / sizeof(double));
+    {
+        LaunchScope ls(ctx, "k_disk_integrate_adjoint");
+        const dim3 grid(rotate_blocks(n), (unsigned)n_rings);
+        hipLaunchKernelGGL(k_disk_integrate_adjoint_den, grid, dim3(kBlock), 0, ctx->stream, n, lambdas, ring_scale, ring_weights, rot_dev, u, u_reference, a,
+                           a_ref, row_doubles);
+        hipLaunchKernelGGL(k_disk_integrate_adjoint, grid, dim3(kBlock), 0, ctx->stream, n, lambdas, ring_scale, ring_weights, rot_dev, (const double*)a,
+                           u_reference ? (const double*)a_ref : nullptr, row_doubles, nus, W, W_reference, W_ld);
+    }
+    return check_launch("k_disk_integrate_adjoint");
+}
+
+int sdx_disk_integrate_adjoint_f64(sdx_ctx* ctx, int64_t n, const double* lambdas, int n_rings, const double* ring_scale,
+                                   const double* ring_weights, double v_rot, const double* u, const double* u_reference, const double* nus,
+                                   double* W, double* W_reference)
+{
+    int rc;
+    if ((rc = disk_adjoint_check(ctx, n, lambdas, n_rings, ring_scale, ring_weights, nullptr, u, u_reference, nus, W, W_reference))) return rc;
+    if ((rc = disk_host_check(n, lambdas, n_rings, ring_scale, v_rot))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t f8 = sizeof(double), grid = (size_t)n * f8, rings = (size_t)n_rings * f8;
+    const double pair[2] = {v_rot, 0.0};
+    const double *d_l, *d_s, *d_w, *d_p, *d_u, *d_ur, *d_nus;
+    double *d_W, *d_Wr;
+    HostPlan plan;
+    plan.in(lambdas, grid, &d_l);
+    plan.in(ring_scale, rings, &d_s);
+    plan.in(ring_weights, rings, &d_w);
+    plan.in(pair, 2 * f8, &d_p);
+    plan.in(u, grid, &d_u);
+    plan.in(u_reference, grid, &d_ur);
+    plan.in(nus, grid, &d_nus);
+    plan.out(W, grid * n_rings, &d_W);
+    plan.out(W_reference, grid * n_rings, &d_Wr);
+    HostIo io{ctx};
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = sdx_disk_integrate_adjoint_dev(ctx, n, d_l, n_rings, d_s, d_w, d_p, d_u, d_ur, d_nus, d_W, n, d_Wr))) return rc;
     if ((rc = io.collect(plan))) return rc;
     return io.finish();
 }

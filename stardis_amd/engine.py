@@ -603,9 +603,18 @@ class SpectralSynthesizer:
         order (sdx_disk_integrate_dev) — the model's own centre-to-limb variation, line by line, in place of a limb-darkening
         coefficient.  v_rot = 0 is F_lambda itself.  Needs the whole spectrum (a shard raises ValueError: gather first).  The buffers
         are made at the first call and reused: the result is overwritten by the next call."""
+        d = self._disk_rings(v_rot)  # (raises before anything else is looked at)
+        c, n = self.ctx, self.n_nu
+        c.call("sdx_disk_integrate_dev", n, d["lambdas"].ptr, self.n_theta, d["scale"].ptr, self.d_w.ptr, d["I_lambda"].ptr, n, None, d["rot"].ptr,
+               d["out"].ptr, None)
+        return d["out"]
+
+    def _disk_buffers(self, v_rot):
+        """the disk's buffers (made at the first call) with {V, 0} written into the device pair -> (dict, V); raises without
+        keep_intensities or on a shard"""
         from .instrument import rotation_pair
 
-        d_I = self.emergent_intensities
+        self.emergent_intensities
         if self.begin != 0 or self.count != self.n_nu:
             raise ValueError("the disk integration needs the whole spectrum: gather the shards first")
         V, _ = rotation_pair(v_rot)
@@ -613,13 +622,132 @@ class SpectralSynthesizer:
         if self._disk is None:
             d_lam = self.d_lambdas if self.instrument is not None else c.upload(K.nu_to_angstrom(self.nus_host))
             self._disk = dict(lambdas=d_lam, scale=c.upload(self.ring_scale), I_lambda=c.empty((self.n_theta, n)), rot=c.empty((2,)), out=c.empty((n,)))
-        d = self._disk
-        d["rot"].set(np.array([V, 0.0]))
+        self._disk["rot"].set(np.array([V, 0.0]))
+        return self._disk, V
+
+    def _disk_rings(self, v_rot):
+        """_disk_buffers, and the last step's emergent intensities converted to per Angstrom ring by ring into I_lambda -> dict"""
+        d, _ = self._disk_buffers(v_rot)
+        c, n, d_I = self.ctx, self.n_nu, self.d_I
         for r in range(self.n_theta):
             c.call("sdx_flux_nu_to_lambda_dev", n, d_I.ptr + 8 * r * n, self.d_nus.ptr, d["lambdas"].ptr, d["I_lambda"].ptr + 8 * r * n)
-        c.call("sdx_disk_integrate_dev", n, d["lambdas"].ptr, self.n_theta, d["scale"].ptr, self.d_w.ptr, d["I_lambda"].ptr, n, None, d["rot"].ptr,
-               d["out"].ptr, None)
-        return d["out"]
+        return d
+
+    @staticmethod
+    def _positive_rotation(v_rot):
+        from .instrument import rotation_pair
+
+        V, _ = rotation_pair(v_rot)
+        if not V > 0.0:
+            raise ValueError("the derivative to v sin i needs v_rot > 0 (at v_rot = 0 the disk integration is the flux sum)")
+        return V
+
+    def _disk_dlnv(self, V, out):
+        """disk_integrated(V) into the disk's `out` (the same bits) and its derivative to ln V into `out` given, one launch
+        (sdx_disk_integrate_deriv_dev)"""
+        d = self._disk_rings(V)
+        c, n = self.ctx, self.n_nu
+        c.call("sdx_disk_integrate_deriv_dev", n, d["lambdas"].ptr, self.n_theta, d["scale"].ptr, self.d_w.ptr, d["I_lambda"].ptr, n, None,
+               d["rot"].ptr, d["out"].ptr, None, out.ptr, None)
+        return out
+
+    def disk_integrated_derivative(self, v_rot):
+        """-> (F_lambda, dF_lambda / dV), DeviceArrays (n_nu,): disk_integrated(v_rot) — the same bits — and its derivative to v sin i
+        per km/s from the same launch (sdx_disk_integrate_deriv_dev: exact for the discrete operator; d / d ln V divided by V on the
+        host: a diagnostic call, it waits for the stream).  v_rot > 0 is required (ValueError at 0, where the operator is a copy).
+        Not meant where an end of the grid lies within 1e-5 of a ring's edge (include/stardis_hip.h).  The buffers are
+        disk_integrated's and one more, reused: overwritten by the next call."""
+        self.emergent_intensities
+        V = self._positive_rotation(v_rot)
+        d, _ = self._disk_buffers(V)
+        if "dout" not in d:
+            d["dout"] = self.ctx.empty((self.n_nu,))
+        self._disk_dlnv(V, d["dout"])
+        d["dout"].set(d["dout"].numpy() / V)
+        return d["out"], d["dout"]
+
+    def disk_weights_to_rays(self, u, v_rot):
+        """-> DeviceArray (N_theta, n_nu): the cotangent on emergent_intensities of weights u (n_nu; host array, DeviceArray or CUDA
+        tensor) over disk_integrated(v_rot) — sum_i u_i disk_integrated(v_rot)_i = sum_theta sum_j W[theta, j] emergent_intensities[theta,
+        j] — the transpose of the disk integration ring by ring with the factor nu / lambda of F_lambda applied
+        (sdx_disk_integrate_adjoint_dev with nus).  v_rot = 0: W[theta, j] = w_theta u_j nu_j / lambda_j.  Needs keep_intensities=True
+        and the whole spectrum.  On demand: a synthesizer that never asks allocates and launches nothing new."""
+        d, _ = self._disk_buffers(v_rot)
+        c, n = self.ctx, self.n_nu
+        d_u = self._device_vector("u", u, n, "column of the spectrum")
+        W = c.empty((self.n_theta, n))
+        c.call("sdx_disk_integrate_adjoint_dev", n, d["lambdas"].ptr, self.n_theta, d["scale"].ptr, self.d_w.ptr, d["rot"].ptr, ptr_of(d_u), None,
+               self.d_nus.ptr, W.ptr, n, None)
+        return W
+
+    def ray_response(self, cotangent, want_opacity=True, want_source=True):
+        """-> (R_alpha, R_source), DeviceArrays (N_d, count) (None for one not wanted): the derivatives of sum_theta cotangent[theta, i]
+        emergent_intensities[theta, i] with respect to ln alpha[k, i] and to the source function S[k, i], from the last step's
+        total_alphas and its source (the Planck function) — sdx_response_angles_dev: one launch that costs what the step's own
+        k_response costs, in place of N_theta launches with one-hot weights.  cotangent (N_theta, count): host array, DeviceArray or
+        CUDA tensor — disk_weights_to_rays(u, v_rot), say.  The step's total_alphas are kept with keep_intensities=True."""
+        self.emergent_intensities
+        if not (want_opacity or want_source):
+            raise ValueError("ray_response: no output requested")
+        c, cnt = self.ctx, self.count
+        d_cot = self._device_vector("cotangent", cotangent, (self.n_theta, cnt))
+        d_Ra = c.empty((self.n_depth, cnt)) if want_opacity else None
+        d_Rs = c.empty((self.n_depth, cnt)) if want_source else None
+        c.call("sdx_response_angles_dev", self.n_depth, cnt, self.n_theta, self.d_nus.ptr + 8 * self.begin, self.d_t.ptr, self.d_ray.ptr,
+               ptr_of(d_cot), cnt, self.d_total.ptr, cnt, None, 0, ptr_of(d_Ra), cnt, ptr_of(d_Rs), cnt)
+        return d_Ra, d_Rs
+
+    def disk_line_sensitivities(self, u, v_rot, per_depth=False, wrt="strength"):
+        """-> DeviceArray (n_lines,), or (n_lines, N_d) with per_depth=True: d(sum_i u_i disk_integrated(v_rot)_i) / d ln gf_l for every
+        line of the list, at fixed windows, from the last step: disk_weights_to_rays(u, v_rot) -> ray_response -> the weight plane and
+        the line adjoints of line_sensitivities, which this is with the disk integration in the flux sum's place (v_rot = 0:
+        line_sensitivities(weights=u nu / lambda) up to the rounding of the theta sum).  wrt: as for line_sensitivities.  Needs
+        keep_intensities=True and keep_response=True; plane-parallel, no scattering, the whole spectrum."""
+        names, single = self._wrt_names(wrt)
+        self._require_response()
+        d_R, _ = self.ray_response(self.disk_weights_to_rays(u, v_rot), want_source=False)
+        return self._sensitivities_of_response(d_R, None, names, single, per_depth)
+
+    def _require_disk_instrument(self):
+        self._require_instrument()
+        if self.instrument.rotates:
+            raise ValueError("the instrument already carries a v_rot: the disk integration is the rotation (rotation twice)")
+
+    def observed_disk_line_sensitivities(self, c, v_rot, per_depth=False, wrt="strength"):
+        """-> as disk_line_sensitivities: d(sum_j c_j observed_disk_integrated(v_rot)_j) / d ln gf_l — the pixel weights c taken back
+        through the instrument's pixel and macroturbulence stages (Instrument.adjoint without nus: weights over the disk-integrated
+        F_lambda), then disk_line_sensitivities.  An instrument with a v_rot of its own raises, as observed_disk_integrated does."""
+        self._wrt_names(wrt)
+        self._require_disk_instrument()
+        self._require_response()
+        self.emergent_intensities
+        u = self.instrument.adjoint(self.d_lambdas, self.n_nu, self._pixel_vector("c", c))
+        return self.disk_line_sensitivities(u, v_rot, per_depth, wrt)
+
+    def chi2_disk_gradient(self, data, inverse_variance, v_rot, wrt="strength", per_depth=False):
+        """-> (chi2, d chi2 / dV, line gradient): chi2 = sum_j ivar_j (data_j - observed_disk_integrated(v_rot)_j)^2 of the last step,
+        its derivative to v sin i per km/s, and its gradient to ln gf of every line ((n_lines,), or (n_lines, N_d); wrt as for
+        line_sensitivities) — one fit step of the rotation and the line list together with the model's own centre-to-limb variation.
+        d chi2 / dV = sum_j c_j t_j, c_j = -2 ivar_j (data_j - observed_j), t = Instrument.tangent of d disk_integrated / dV (the sum on
+        the host, math.fsum); the line gradient is observed_disk_line_sensitivities(c, v_rot).  Left out of all three: NaN pixels,
+        pixels with inverse_variance 0 and the pixels edge-affected at the reach (v_rot + 6 v_mac) / c (Instrument.edge_affected(...,
+        v_rot=v_rot)), as chi2_line_gradient leaves them out.  v_rot > 0; an instrument with a v_rot of its own raises.  A diagnostic
+        call: it waits for the stream."""
+        self._wrt_names(wrt)
+        self._require_disk_instrument()
+        self._require_response()
+        self.emergent_intensities
+        V = self._positive_rotation(v_rot)
+        inst, n = self.instrument, self.n_nu
+        # one launch gives disk_integrated(V), bit for bit, and its derivative; then the instrument as observed_disk_integrated applies it
+        d_dlnv = self._disk_dlnv(V, self.ctx.empty((n,)))
+        flux = self._disk["out"]
+        broadened = inst.macroturbulence(self.d_lambdas, flux, n) if inst.macroturbulent else flux
+        observed = inst.observe(self.d_lambdas, broadened, n, out=self.ctx.empty((inst.n_pix,)), broadened=True).numpy()
+        chi2, c, use, _ = self._chi2_pixel_weights(data, inverse_variance, False, observed=observed, v_rot=V)
+        t = inst.tangent(self.d_lambdas, n, flux, d_dlnv).numpy()
+        dchi2_dv = math.fsum(c * np.where(use, t, 0.0)) / V
+        return chi2, dchi2_dv, self.observed_disk_line_sensitivities(c, V, per_depth, wrt)
 
     def observed_disk_integrated(self, v_rot):
         """-> DeviceArray (n_pix,): disk_integrated(v_rot) through the instrument — its macroturbulence (if any), then the radial
@@ -820,11 +948,16 @@ class SpectralSynthesizer:
         self._require_response()
         if scattering:
             self._require_scattering_response()
-        c = self.ctx
         d_w = None if weights is None else self._device_vector("weights", weights, self.count, "column of the synthesizer")
+        return self._sensitivities_of_response(self.d_sc_Ra if scattering else self.d_Ra, d_w, names, single, per_depth)
+
+    def _sensitivities_of_response(self, d_R, d_w, names, single, per_depth):
+        """line_sensitivities behind its response plane: the weight plane d_w[i] d_R[k, i] / total_alphas[k, i] (d_w None: 1), then the
+        line adjoints for `names`.  d_R: response_opacity, scattering_response_opacity, or the plane of a per-ray cotangent
+        (disk_line_sensitivities)."""
+        c = self.ctx
         cnt = self.count
         d_W = c.empty((self.n_depth, cnt))
-        d_R = self.d_sc_Ra if scattering else self.d_Ra
         c.call("sdx_response_weight_dev", self.n_depth, cnt, d_R.ptr, cnt, self.d_total.ptr, cnt, ptr_of(d_w), d_W.ptr, cnt)
         ln_ptr, d_dw, d_g, d_a = self._tables_in_caller_order()
         shape = (self.n_lines, self.n_depth) if per_depth else (self.n_lines,)
@@ -1009,10 +1142,11 @@ class SpectralSynthesizer:
         chi2, c, _, _ = self._chi2_pixel_weights(data, inverse_variance, normalized)
         return chi2, self.observed_line_sensitivities(c, normalized, per_depth, wrt)
 
-    def _chi2_pixel_weights(self, data, inverse_variance, normalized):
+    def _chi2_pixel_weights(self, data, inverse_variance, normalized, observed=None, v_rot=None):
         """-> (chi2, c, use, w): chi-square over the pixels chi2_line_gradient uses, c_j = d chi2 / d observed_j = -2 ivar_j (data_j -
         observed_j), 0 at the pixels left out, the mask of the pixels used and the inverse variance, 0 at the others.  The one
-        download of the observed spectrum of a chi-square call."""
+        download of the observed spectrum of a chi-square call.  observed, v_rot: a host spectrum in the step's place and the
+        rotation whose reach decides the edge-affected pixels (chi2_disk_gradient: the disk integration is no stage of the instrument)."""
         if normalized:
             self._require_continuum()
         n_pix = self.instrument.n_pix
@@ -1021,9 +1155,11 @@ class SpectralSynthesizer:
         for name, v in (("data", d), ("inverse_variance", ivar)):
             if v.size != n_pix:
                 raise ValueError(f"{name} must hold one value per pixel of the instrument ({n_pix}), got {v.size}")
-        obs = (self.d_observed_normalized if normalized else self.d_observed).numpy()
+        obs = (self.d_observed_normalized if normalized else self.d_observed).numpy() if observed is None else observed
         use = ~np.isnan(obs) & (ivar != 0)
-        if self.instrument.broadens:
+        if v_rot is not None:
+            use &= ~self.instrument.edge_affected(self.lambdas, v_rot=v_rot)
+        elif self.instrument.broadens:
             use &= ~self.instrument.edge_affected(self.lambdas)
         if not np.any(use):
             raise ValueError("no pixel left: every pixel is NaN (not covered by the grid), edge-affected or has inverse_variance 0")

@@ -296,15 +296,18 @@ class Instrument:
             f, g = stage(lam, f, g)
         return f, g
 
-    def edge_affected(self, lambdas):
+    def edge_affected(self, lambdas, v_rot=None):
         """-> boolean host array (n_pix,): the pixels whose window [edges[j] - 8 sigma[j], edges[j+1] + 8 sigma[j]], taken back to the
         rest frame, comes within the broadening's reach of an end of the grid `lambdas` — lo (1 - beta) < lambdas[0] or hi (1 + beta) >
         lambdas[-1], beta = (v_rot + 6 v_mac) / c the combined reach of rotation and macroturbulence — so that a window of a point
-        they may see is truncated there.  Without either (beta = 0) these are the pixels the grid does not cover.  Plain numpy."""
+        they may see is truncated there.  Without either (beta = 0) these are the pixels the grid does not cover.  v_rot: a rotation
+        (km/s) in the place of the instrument's own — the disk integration's, which is no stage of the instrument; None: the
+        instrument's.  Plain numpy."""
         lam = _grid(lambdas)
-        beta = (self.v_rot or 0.0) / K.C_KMS
+        rot = (self.v_rot or 0.0) if v_rot is None else float(v_rot)
+        beta = rot / K.C_KMS
         if self.v_mac:
-            beta = ((self.v_rot or 0.0) + MACROTURBULENCE_REACH * self.v_mac) / K.C_KMS
+            beta = (rot + MACROTURBULENCE_REACH * self.v_mac) / K.C_KMS
         lo = (self.edges[:-1] - 8.0 * self.sigma) / self.doppler
         hi = (self.edges[1:] + 8.0 * self.sigma) / self.doppler
         return (lo * (1.0 - beta) < lam[0]) | (hi * (1.0 + beta) > lam[-1])

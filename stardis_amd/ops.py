@@ -660,6 +660,46 @@ def response(tracing_nus, temperatures, ray_distances, theta_weights, total_alph
     return (d_Ra.numpy() if want_opacity else None), (d_Rs.numpy() if want_source else None)
 
 
+def response_angles(tracing_nus, temperatures, ray_distances, cotangent, total_alphas, ctx=None, source=None, device=False,
+                    want_opacity=True, want_source=True):
+    """The response for a cotangent per (angle, frequency) (sdx_response_angles_dev) -> (R_alpha, R_source), each (N_d, N_nu): the
+    derivatives of sum_theta cotangent[theta, nu] I_theta(nu), I the emergent intensities (ops.emergent_intensity), with respect to
+    ln alpha[k] and to S[k].  cotangent (N_theta, N_nu), host or device; the other arguments as response.  A cotangent that holds the
+    flux weights in every column gives response's bits."""
+    nus = _host(tracing_nus).reshape(-1)
+    t = _host(temperatures).reshape(-1)
+    rd = _host(ray_distances)
+    cshape = tuple(int(v) for v in (cotangent.shape if hasattr(cotangent, "shape") else np.shape(cotangent)))
+    if len(cshape) != 2 or cshape[1] != nus.size or cshape[0] < 1:
+        raise ValueError(f"cotangent must have shape (n_theta, {nus.size}), got {cshape}")
+    n_theta = cshape[0]
+    if t.size < 2 or rd.size != (t.size - 1) * n_theta:
+        raise ValueError(f"ray_distances must have shape {(t.size - 1, n_theta)}, got {rd.shape}")
+    rd = rd.reshape(t.size - 1, n_theta)
+    shape = tuple(int(v) for v in (total_alphas.shape if hasattr(total_alphas, "shape") else np.shape(total_alphas)))
+    if shape != (t.size, nus.size):
+        raise ValueError(f"total_alphas must have shape {(t.size, nus.size)}, got {shape}")
+    src = None
+    if source is not None:
+        src = _host(source)
+        if src.shape != (t.size, nus.size):
+            raise ValueError(f"source function must return shape {(t.size, nus.size)}, got {src.shape}")
+    if not (want_opacity or want_source):
+        raise ValueError("response_angles: no output requested")
+    ctx = ctx or default_context()
+    d_alpha = _dev(ctx, total_alphas)
+    d_cot = _dev(ctx, cotangent)
+    d_S = ctx.upload(src) if src is not None else None
+    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd)]
+    d_Ra = ctx.empty((t.size, nus.size)) if want_opacity else None
+    d_Rs = ctx.empty((t.size, nus.size)) if want_source else None
+    ctx.call("sdx_response_angles_dev", t.size, nus.size, n_theta, d[0].ptr, d[1].ptr, d[2].ptr, ptr_of(d_cot), nus.size, ptr_of(d_alpha),
+             nus.size, ptr_of(d_S), nus.size, ptr_of(d_Ra), nus.size, ptr_of(d_Rs), nus.size)
+    if device:
+        return d_Ra, d_Rs
+    return (d_Ra.numpy() if want_opacity else None), (d_Rs.numpy() if want_source else None)
+
+
 def mean_weights(thetas, theta_weights):
     """Weights m (N_theta,) of the mean intensity J = sum_k m_k (I_k up + I_k down) for the field's Gauss-Legendre nodes in theta:
     m_k = w_k sin(theta_k) / (2 sum_j w_j sin(theta_j)) with w = I_nus_weights, normalised so that sum_k 2 m_k = 1 to rounding (an
@@ -980,14 +1020,9 @@ def rotate_integrated_adjoint(lambdas, u, v_rot, limb_darkening=0.6, u_reference
     return w if w_ref is None else (w, w_ref)
 
 
-def disk_integrate(lambdas, intensities, ring_scale, ring_weights, v_rot, reference=None, ctx=None):
-    """Disk integration with rigid rotation (sdx_disk_integrate_f64): per-ring spectra intensities (n_rings, n) on the ascending grid
-    lambdas, ring r at the projected radius ring_scale[r] = sin theta_r in [0, 1] with the flux weight ring_weights[r]; every ring is
-    convolved with the arcsine density of half-width v_rot ring_scale[r] / c, integrated exactly against the piecewise-linear spectrum,
-    and the rings are summed in the flux's order -> (n,), or (out, out_reference) with a reference (n_rings, n).  v_rot = 0 is the
-    flux sum itself.  No limb-darkening coefficient: the centre-to-limb variation is in the spectra (ops.emergent_intensity).  The
-    arguments are checked before any device work (ValueError naming the argument)."""
-    from .instrument import _grid, _host_ptr as host, _host_vector, rotation_pair
+def _disk_arguments(lambdas, ring_scale, ring_weights, v_rot):
+    """The checked arguments the disk entries share -> (lam, V, scale, w)"""
+    from .instrument import _grid, _host_vector, rotation_pair
 
     lam = _grid(_lib.plain(lambdas))
     V, _ = rotation_pair(v_rot)
@@ -998,6 +1033,22 @@ def disk_integrate(lambdas, intensities, ring_scale, ring_weights, v_rot, refere
     if not np.all((scale >= 0.0) & (scale <= 1.0)):
         raise ValueError("ring_scale must lie in [0, 1]")
     w = _host_vector("ring_weights", _lib.plain(ring_weights), n_rings, "ring")
+    return lam, V, scale, w
+
+
+def disk_integrate(lambdas, intensities, ring_scale, ring_weights, v_rot, reference=None, ctx=None, derivative=False):
+    """Disk integration with rigid rotation (sdx_disk_integrate_f64): per-ring spectra intensities (n_rings, n) on the ascending grid
+    lambdas, ring r at the projected radius ring_scale[r] = sin theta_r in [0, 1] with the flux weight ring_weights[r]; every ring is
+    convolved with the arcsine density of half-width v_rot ring_scale[r] / c, integrated exactly against the piecewise-linear spectrum,
+    and the rings are summed in the flux's order -> (n,), or (out, out_reference) with a reference (n_rings, n).  v_rot = 0 is the
+    flux sum itself.  No limb-darkening coefficient: the centre-to-limb variation is in the spectra (ops.emergent_intensity).
+    derivative=True (sdx_disk_integrate_deriv_f64) appends d / d ln v_rot of each from the same launch: (out, dout_lnv), or (out,
+    out_reference, dout_lnv, dout_lnv_reference); exact for the discrete operator, zeros at v_rot = 0, and not meant where an end of
+    the grid lies within 1e-5 of a ring's edge.  The arguments are checked before any device work (ValueError naming the argument)."""
+    from .instrument import _host_ptr as host
+
+    lam, V, scale, w = _disk_arguments(lambdas, ring_scale, ring_weights, v_rot)
+    n_rings = scale.size
 
     def rings(name, a):
         a = np.ascontiguousarray(_lib.plain(a), dtype=F8)
@@ -1008,9 +1059,29 @@ def disk_integrate(lambdas, intensities, ring_scale, ring_weights, v_rot, refere
     I = rings("intensities", intensities)
     G = None if reference is None else rings("reference", reference)
     out, out_ref = np.empty(lam.size), None if G is None else np.empty(lam.size)
-    (ctx or default_context()).call("sdx_disk_integrate_f64", lam.size, host(lam), n_rings, host(scale), host(w), host(I), host(G), V, host(out),
-                                    host(out_ref))
-    return out if out_ref is None else (out, out_ref)
+    if not derivative:
+        (ctx or default_context()).call("sdx_disk_integrate_f64", lam.size, host(lam), n_rings, host(scale), host(w), host(I), host(G), V, host(out),
+                                        host(out_ref))
+        return out if out_ref is None else (out, out_ref)
+    d, d_ref = np.empty(lam.size), None if G is None else np.empty(lam.size)
+    (ctx or default_context()).call("sdx_disk_integrate_deriv_f64", lam.size, host(lam), n_rings, host(scale), host(w), host(I), host(G), V,
+                                    host(out), host(out_ref), host(d), host(d_ref))
+    return (out, d) if out_ref is None else (out, out_ref, d, d_ref)
+
+
+def disk_integrate_adjoint(lambdas, u, ring_scale, ring_weights, v_rot, u_reference=None, nus=None, ctx=None):
+    """The transpose of disk_integrate (sdx_disk_integrate_adjoint_f64): weights u (n,) over the disk-integrated points -> the plane W
+    (n_rings, n) over (ring, grid point) with sum_i u_i disk_integrate(I)_i = sum_r sum_j W[r, j] I[r, j], or (W, W_reference) with
+    u_reference.  v_rot = 0: W[r, j] = ring_weights[r] u[j].  nus: the plane then applies to I_nu instead of I_lambda."""
+    from .instrument import _host_ptr as host, _host_vector
+
+    lam, V, scale, w = _disk_arguments(lambdas, ring_scale, ring_weights, v_rot)
+    uu = _host_vector("u", u, lam.size, "grid point")
+    ur, nu = (None if a is None else _host_vector(name, a, lam.size, "grid point") for name, a in (("u_reference", u_reference), ("nus", nus)))
+    W, W_ref = np.empty((scale.size, lam.size)), None if ur is None else np.empty((scale.size, lam.size))
+    (ctx or default_context()).call("sdx_disk_integrate_adjoint_f64", lam.size, host(lam), scale.size, host(scale), host(w), V, host(uu), host(ur),
+                                    host(nu), host(W), host(W_ref))
+    return W if W_ref is None else (W, W_ref)
 
 
 def rotate_moments(ya, yb, limb_darkening=0.6, ctx=None):

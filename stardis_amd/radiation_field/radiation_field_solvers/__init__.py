@@ -1,2 +1,2 @@
 from stardis_amd.radiation_field.radiation_field_solvers.base import continuum_flux, contribution_function, formation_mean, raytrace, response_functions  # noqa: F401
-from stardis_amd.radiation_field.radiation_field_solvers.base import mean_intensity, scattering_response, scattering_source  # noqa: F401
+from stardis_amd.radiation_field.radiation_field_solvers.base import mean_intensity, ray_response, scattering_response, scattering_source  # noqa: F401

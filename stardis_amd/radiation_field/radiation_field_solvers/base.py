@@ -197,6 +197,27 @@ def response_functions(stellar_model, stellar_radiation_field):
     )
 
 
+def ray_response(stellar_model, stellar_radiation_field, cotangent):
+    """(R_alpha, R_source), each (N_d, N_nu), for a cotangent (N_theta, N_nu) on emergent_intensities() above: the derivatives of
+    sum_theta cotangent[theta, nu] I_theta(nu) with respect to ln(total opacity) and to the source function at every depth point
+    (sdx_response_angles_dev) — what carries the transpose of the disk integration (ops.disk_integrate_adjoint) back into the
+    atmosphere.  With the field's I_nus_weights in every column it is response_functions() bit for bit.  A spherical model raises
+    NotImplementedError."""
+    field = stellar_radiation_field
+    if bool(getattr(stellar_model, "spherical", False)):
+        raise NotImplementedError(SPHERICAL_RESPONSE)
+    thetas = np.asarray(field.thetas, dtype=np.float64)
+    dist = np.asarray(plain(stellar_model.geometry.dist_to_next_depth_point), dtype=np.float64)
+    ray_distances = dist.reshape(-1, 1) / np.cos(thetas)  # :302-305
+    ctx = default_context()
+    opac = field.opacities
+    alphas = opac.total_alphas_device(ctx) if hasattr(opac, "total_alphas_device") else opac.total_alphas
+    return ops.response_angles(
+        field.frequencies, plain(stellar_model.temperatures), ray_distances, cotangent, alphas, ctx=ctx,
+        source=_source_plane(getattr(field, "source_function", None), field.frequencies, stellar_model.temperatures),
+    )
+
+
 SPHERICAL_SCATTERING = ("the mean intensity and the scattering source function are defined for plane-parallel models: the downward sweep "
                         "of a spherical model runs along chords that miss the inner shells, which the two-hemisphere quadrature here does not describe")
 
