@@ -12,6 +12,7 @@ import pytest
 
 import observe_reference as oref
 import observe_tangent_reference as tref
+import observe_truth as OT
 import rotation_reference as rref
 from observe_tangent_reference import FLUX_TOL, LD, SUM_TOL
 from rotation_reference import ROT_TOL
@@ -105,12 +106,37 @@ def response_gradient_distances(ctx):
     return tuple(worst)
 
 
+def response_within_its_bound(ctx):
+    """obs_response itself, per point of response_grad_points(), against 50 digits:
+        |r - exact| <= (U (E(p) + E(q)) / 2 + 4 |r|) 2^-53 + c_args,   c_args = 2^-53 (|a| e^(-a^2) + |b| e^(-b^2)) 2 / sqrt(pi),
+    U the recorded error of the device's erf and erfc (tests/observe_truth.py), E(.) the two values the branch subtracts, c_args the
+    rounding of a and b carried through the response.  -> the worst |r - exact| / bound"""
+    U = OT.device_U()
+    a, b = tref.response_grad_points()
+    r = ops.observe_response_grad(a, b, 0.0, 1.0, ctx=ctx)[0]
+    worst = 0.0
+    with mpmath.workdps(50):
+        eps = mpmath.mpf(2) ** -53
+        for k in range(a.size):
+            exact = tref.mp_response(a[k], b[k])[0]
+            ma, mb = mpmath.mpf(float(a[k])) / mpmath.sqrt(2), mpmath.mpf(float(b[k])) / mpmath.sqrt(2)
+            E = (mpmath.erfc(ma) + mpmath.erfc(mb)) / 2 if ma > 0 else ((mpmath.erfc(-mb) + mpmath.erfc(-ma)) / 2 if mb < 0 else (abs(mpmath.erf(mb)) + abs(mpmath.erf(ma))) / 2)
+            c_args = eps * (abs(ma) * mpmath.exp(-ma * ma) + abs(mb) * mpmath.exp(-mb * mb)) * 2 / mpmath.sqrt(mpmath.pi)
+            bound = (U * E + 4 * abs(mpmath.mpf(float(r[k])))) * eps + c_args
+            err = abs(mpmath.mpf(float(r[k])) - exact)
+            assert err <= bound, (float(a[k]), float(b[k]), float(r[k]), float(err), float(bound))
+            worst = max(worst, float(err / bound))
+    return worst
+
+
 def test_response_gradient_against_mpmath(ctx):
     """the gradient is allowed four times the distance of obs_response itself on the same points: the same exp and erf family, one more
     product.  obs_response's distance is that of a difference of two erfc for the pixel 1e-4 sigma wide in a tail; the gradient, formed
-    through expm1, keeps its relative accuracy there, and what it measures is printed beside what it is allowed."""
+    through expm1, keeps its relative accuracy there, and what it measures is printed beside what it is allowed.  obs_response in turn
+    has its own bound per point (response_within_its_bound), so a worse response does not make the gradient's allowance wider."""
     d_r, d_rx, d_rs = response_gradient_distances(ctx)
     print(f"distance from 50 digits: obs_response {d_r:.3e}, dr/dx {d_rx:.3e}, dr/d ln sigma {d_rs:.3e}; allowed 4 x {d_r:.3e} = {4 * d_r:.3e}")
+    print(f"obs_response against its own bound: worst |r - exact| / bound {response_within_its_bound(ctx):.3e}")
     assert 0 < d_rx <= 4 * d_r and 0 < d_rs <= 4 * d_r
     # the host-buffer twin and scalars
     a, b = tref.response_grad_points()
