@@ -27,6 +27,13 @@ alternated round by round (clocks drift between sessions and within one):
       the sums do not).  Time: per stage name the median of 31 single profiled calls at S-c2 and S-c3, per line and per depth
       (k_line_tangent: an unchanged control), and the wall time of sdx_line_param_adjoint_f64 at S-c2.  The bar as for `stages`.
 
+  python scripts/lib_ab.py columns OLD.so NEW.so [ROUNDS] [OUT.json]
+      the products of the formal solution over the grid's columns (contribution, emergent intensity, response, response_angles, mean
+      intensity, scatter source, mean-intensity adjoint, scatter response: device entry and host-buffer twin each, and
+      sdx_raytrace_f64).  Bits: SHA-256 of every output of the calls of tests/test_gpu_column_entries.py — 2, 3, 9 depths x 1, 3, 20, 64
+      angles x 1, 7 frequencies, every form — and of one call each at S-c2's size; every hash must agree.  Time, host code only: 500
+      enqueues of each device entry at 7 frequencies, and one call of each twin at S-c2's size.  The bar as for `stages`.
+
   python scripts/lib_ab.py engine OLD_TREE NEW_TREE [ROUNDS] [OUT.json]
       two trees of the PYTHON package on the one built library (the refactors of stardis_amd/engine.py and radiation_field/fused.py): each
       child puts its tree in front of sys.path.  Bits: SHA-256 of every output of SpectralSynthesizer on the small workload of
@@ -360,6 +367,54 @@ def adjoints_child():
     print(json.dumps({"hashes": hashes, "us": times}))
 
 
+def columns_child():
+    """one leg of `columns`: the calls of tests/test_gpu_column_entries.py, hashed and timed"""
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_gpu_column_entries as T
+    from stardis_amd import _lib, synth
+
+    ctx = _lib.Context(0)
+    w = synth.WORKLOADS["S-c2"]
+    big = T.Problem(ctx, int(synth.solar_atmosphere()["temperatures"].size), synth.N_THETAS, int(synth.tracing_grid(w["lam0"], w["lam1"], R=w["R"]).size))
+    shapes = [(f"{nd} depths, {nt} angles, {nn} frequencies", T.Problem(ctx, nd, nt, nn)) for nd in T.DEPTHS for nt in T.ANGLES for nn in T.FREQUENCIES]
+    hashes = {}
+    for label, p in shapes + [("S-c2 size", big)]:
+        case = {}
+        for entry in T.DEVICE:
+            for twin in (False, True):  # one hash per entry: every output of every form, in order
+                h = hashlib.sha256()
+                for form in (T.forms(entry) if p is not big else [{}]):
+                    for name, a in p.run(entry, twin, form).items():
+                        h.update(name.encode() + (b"-" if a is None else np.ascontiguousarray(a).tobytes()))
+                case[f"sdx_{entry}_{'f64' if twin else 'dev'}"] = h.hexdigest()
+        hashes[label] = case
+    times = {}
+    small = T.Problem(ctx, 9, synth.N_THETAS, 7)
+    for entry in T.PRODUCTS:  # the host cost of a device entry: 500 enqueues at 7 frequencies, then one synchronize
+        outs = small.outputs(entry, False, {})
+        args = small.arguments(entry, False, {}, outs)
+        for _ in range(50):
+            ctx.call(f"sdx_{entry}_dev", *args)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(500):
+            ctx.call(f"sdx_{entry}_dev", *args)
+        times[f"sdx_{entry}_dev enqueue"] = (time.perf_counter() - t0) / 500 * 1e6
+        ctx.synchronize()
+    for entry in T.DEVICE:  # one twin call at S-c2 size (each ends in a synchronize): the median of seven
+        outs = big.outputs(entry, True, {})
+        args = big.arguments(entry, True, {}, outs)
+        ts = []
+        for k in range(9):
+            t0 = time.perf_counter()
+            ctx.call(f"sdx_{entry}_f64", *args)
+            ts.append((time.perf_counter() - t0) * 1e6)
+        times[f"S-c2 sdx_{entry}_f64 wall"] = float(np.median(ts[2:]))
+    print(json.dumps({"hashes": hashes, "us": times}))
+
+
 ENGINE_WRT = ("strength", "damping", "doppler", "centre")
 
 
@@ -578,6 +633,9 @@ def main():
     if mode == "adjoints-child":
         adjoints_child()
         return
+    if mode == "columns-child":
+        columns_child()
+        return
     if mode == "engine-child":
         engine_child(sys.argv[2])
         return
@@ -609,7 +667,7 @@ def main():
             res[name + " 20 after 5"].append({"ms_per_step": j["ms_per_step"]})
         for name, rows in res.items():
             summary(name, rows, "us", 1e3, drop_first=True)
-    elif mode in ("stages", "adjoints", "engine"):
+    elif mode in ("stages", "adjoints", "columns", "engine"):
         rounds = int(sys.argv[4]) if len(sys.argv) > 4 else 7
         res = {"old": [], "new": []}
         built = os.environ.get("STARDIS_AMD_LIB") or os.path.join(ROOT, "stardis_amd", "lib", "libstardis_hip.so")

@@ -2341,48 +2341,134 @@ static int raytrace_impl(sdx_ctx* ctx, const Grid& g, const Rays& rays, const Rt
     return SDX_OK;
 }
 
+// ---- the products of the formal solution over the grid's columns ------------------------------------------------------------------
+// The contribution function, the emergent intensities, the response functions, the mean intensity, the scattering source and the two
+// scattering adjoints solve one problem (Columns).  Every device entry passes the gate, then checks its own scalars (tol, max_iter),
+// then its pointers and outputs: everything before anything is enqueued, and the gate and the scalars also for an empty grid, so that
+// a caller can ask at set-up time whether this context and shape are served (the engine does).  Every host-buffer twin makes the same
+// refusals in the same order on its host pointers, before any copy, and runs the one skeleton (columns_host) around its device entry.
+extern "C++" {
+namespace {
+struct Plane {  // [n_depth][ld]
+    const double* p;
+    int64_t ld;
+};
+struct Columns {  // the grid, the rays, the total opacity and the source (or thermal) plane — null: the Planck function of rays.temps
+    Grid g;
+    Rays rays;
+    Plane alphas, source;
+};
+Columns columns(int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist, const double* wts,
+                Plane alphas, Plane source)
+{
+    return Columns{Grid{n_depth, n_nu, nus, 0, n_nu}, Rays{n_theta, temps, ray_dist, wts}, alphas, source};
+}
+
+// What the gate says under each entry's name: to a context with mixed_precision = 1, and to a model whose columns do not fit LDS
+struct ColumnEntry {
+    const char *name, *mixed, *deep;
+};
+constexpr const char* kResponseMixed = "no response functions with mixed_precision = 1 (they differentiate the fp64 formal solution)";
+constexpr const char* kResponseDeep = "no response functions for models this deep (the columns and the stashed intensities do not fit LDS)";
+constexpr const char* kLambdaMixed = "not with mixed_precision = 1 (the mean intensity is that of the fp64 formal solution)";
+constexpr const char* kLambdaDeep = "models this deep are not served (the columns of one frequency do not fit LDS)";
+constexpr const char* kAdjointDeep = "models this deep are not served (the columns and stashed values of one frequency do not fit LDS)";
+constexpr ColumnEntry kContribution{"contribution", "no contribution function with mixed_precision = 1 (it decomposes the fp64 formal solution)",
+                                    "no contribution function for models this deep (the columns do not fit LDS)"},
+    kEmergentIntensity{"emergent_intensity", "no emergent intensities with mixed_precision = 1 (they are the fp64 formal solution's last row)",
+                       "no emergent intensities for models this deep (the columns do not fit LDS)"},
+    kResponse{"response", kResponseMixed, kResponseDeep}, kResponseAngles{"response_angles", kResponseMixed, kResponseDeep},
+    kMeanIntensity{"mean_intensity", kLambdaMixed, kLambdaDeep}, kScatterSource{"scatter_source", kLambdaMixed, kLambdaDeep},
+    kMeanIntensityAdjoint{"mean_intensity_adjoint", kLambdaMixed, kAdjointDeep}, kScatterResponse{"scatter_response", kLambdaMixed, kAdjointDeep};
+
+int refuse(const ColumnEntry& e, const std::string& why) { return fail(SDX_ERR_ARG, std::string(e.name) + ": " + why); }
+
+// The gate: the refusals all products share -> the frequencies per wave of the launch (Layout: the kernel's LDS layout), or the error code
+static_assert(SDX_ERR_ARG < 0, "column_gate returns a count or an error code");
+template <class Layout>
+int column_gate(const sdx_ctx* ctx, const ColumnEntry& e, int n_depth, int64_t n_nu, int n_theta)
+{
+    if (!(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0)) return refuse(e, "need n_depth >= 2, n_theta > 0");
+    if (ctx->mixed_precision) return refuse(e, e.mixed);
+    if (n_theta > 64) return refuse(e, "more than 64 angles are not supported (all angles are traced in one launch)");
+    const int gpw = rt_fit_gpw<Layout>(n_theta, n_depth);
+    return gpw > 0 ? gpw : refuse(e, e.deep);
+}
+// the scalars of the two iterations
+int iteration_check(const ColumnEntry& e, double tol, int max_iter)
+{
+    return tol >= 0.0 && max_iter >= 1 ? SDX_OK : refuse(e, "need tol >= 0 (not NaN) and max_iter >= 1");
+}
+// a source plane (`kind`: "source", or "thermal") that is wide enough, or temperatures
+int source_or_temps(const ColumnEntry& e, const std::string& kind, const Columns& c)
+{
+    if (c.source.p ? c.source.ld >= c.g.n_nu : c.rays.temps != nullptr) return SDX_OK;
+    return refuse(e, "bad " + kind + " plane (" + kind + "_ld < n_nu), or neither a " + kind + " plane nor temperatures");
+}
+// an optional plane: absent, or its leading dimension at least n_nu
+bool fits(const double* p, int64_t ld, int64_t n_nu) { return !p || ld >= n_nu; }
+// the inputs every product needs: the grid, the ray table, the opacity plane and — where the entry reads them — weights and temperatures
+bool columns_given(const Columns& c, bool wts = true, bool temps = false)
+{
+    return c.g.nus && c.rays.ray_dist && (c.rays.wts || !wts) && (c.rays.temps || !temps) && c.alphas.p && c.alphas.ld >= c.g.n_nu;
+}
+
+// The host-buffer twin of an entry, after its refusals.  The five rows every twin uploads — n_wts doubles of weights: [n_theta], a
+// cotangent plane, or none (h.rays.wts null) — then rows(plan, plane, d): the entry's own rows, `plane` the bytes of [n_depth][n_nu], the
+// source plane's slot d.source.p; then stage -> launch(d) -> collect -> finish, d the problem on device addresses, every ld = n_nu.
+template <class Rows, class Launch>
+int columns_host(sdx_ctx* ctx, const Columns& h, size_t n_wts, Rows rows, Launch launch)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int n_depth = h.g.n_depth, n_theta = h.rays.n_theta;
+    const int64_t n_nu = h.g.n_nu;
+    const double *const nus = h.g.nus, *const temps = h.rays.temps, *const ray_dist = h.rays.ray_dist, *const wts = h.rays.wts;
+    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
+    Columns d{h.g, h.rays, {nullptr, n_nu}, {nullptr, n_nu}};
+    HostPlan plan;
+    plan.in(nus, (size_t)n_nu * f8, &d.g.nus);
+    plan.in(temps, (size_t)n_depth * f8, &d.rays.temps);
+    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d.rays.ray_dist);
+    plan.in(wts, n_wts * f8, &d.rays.wts);
+    plan.in(h.alphas.p, plane, &d.alphas.p);
+    rows(plan, plane, d);
+    HostIo io{ctx};
+    int rc;
+    if ((rc = io.stage(plan))) return rc;
+    if ((rc = launch(d))) return rc;
+    if ((rc = io.collect(plan))) return rc;
+    return io.finish();
+}
+}  // namespace
+}  // extern "C++"
+
 int sdx_raytrace_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
                      const double* ray_dist, const double* wts, const double* alphas, double* F, double* I_nus)
 {
     REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "raytrace: need n_depth >= 2, n_theta > 0");
     REQUIRE(n_nu == 0 || (nus && temps && ray_dist && wts && alphas && F), "raytrace: null pointer");
     if (n_nu == 0) return SDX_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    int rc;
-    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
-    const double *d_nus, *d_t, *d_rd, *d_w, *d_a;
     double *d_f, *d_i;
-    HostPlan plan;
-    plan.in(nus, (size_t)n_nu * f8, &d_nus);
-    plan.in(temps, (size_t)n_depth * f8, &d_t);
-    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
-    plan.in(wts, (size_t)n_theta * f8, &d_w);
-    plan.in(alphas, plane, &d_a);
-    plan.inout(F, plane, &d_f);  // F_nu is accumulated into (base.py:336)
-    plan.out(I_nus, plane * n_theta, &d_i);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_raytrace_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_f, n_nu, d_i, 1))) return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    const auto rows = [&](HostPlan& plan, size_t plane, Columns&) {
+        plan.inout(F, plane, &d_f);  // F_nu is accumulated into (base.py:336)
+        plan.out(I_nus, plane * n_theta, &d_i);
+    };
+    return columns_host(ctx, columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, wts, {alphas, n_nu}, {}), n_theta, rows, [&](const Columns& d) {
+        return sdx_raytrace_dev(ctx, n_depth, n_nu, n_theta, d.g.nus, d.rays.temps, d.rays.ray_dist, d.rays.wts, d.alphas.p, n_nu, d_f, n_nu, d_i, 1);
+    });
 }
 
 // ---- flux contribution function and formation depth (k_contribution, k_formation_mean) ------------------------------------
-// Everything is checked before anything is enqueued — also for an empty grid, so that a caller can ask at set-up time whether this
-// context and shape are served (the engine does).
 int sdx_contribution_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
                          const double* ray_dist, const double* wts, const double* alphas, int64_t ald, const double* source,
                          int64_t source_ld, double* C, int64_t cld)
 {
-    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "contribution: need n_depth >= 2, n_theta > 0");
-    REQUIRE(!ctx->mixed_precision, "contribution: no contribution function with mixed_precision = 1 (it decomposes the fp64 formal solution)");
-    REQUIRE(n_theta <= 64, "contribution: more than 64 angles are not supported (all angles are traced in one launch)");
-    const int G = n_theta;
-    const int gpw = rt_fit_gpw<RtColumns>(G, n_depth);  // (k_raytrace's budget)
-    REQUIRE(gpw > 0, "contribution: no contribution function for models this deep (the columns do not fit LDS)");
+    const int G = n_theta, gpw = column_gate<RtColumns>(ctx, kContribution, n_depth, n_nu, n_theta);  // (k_raytrace's budget)
+    if (gpw < 0) return gpw;
     if (n_nu == 0) return SDX_OK;
-    REQUIRE(nus && ray_dist && wts && alphas && ald >= n_nu && C && cld >= n_nu, "contribution: null pointer or leading dimension below n_nu");
-    REQUIRE(source ? source_ld >= n_nu : temps != nullptr, "contribution: bad source plane (source_ld < n_nu), or neither a source plane nor temperatures");
+    const Columns c = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, wts, {alphas, ald}, {source, source_ld});
+    REQUIRE(columns_given(c) && C && cld >= n_nu, "contribution: null pointer or leading dimension below n_nu");
+    if (int rc = source_or_temps(kContribution, "source", c)) return rc;
     {
         LaunchScope ls(ctx, "k_contribution", "k_contribution<1>");
         hipLaunchKernelGGL(k_contribution, dim3(rt_blocks(n_nu, gpw)), dim3(kRtBlock), RtColumns(G, n_depth, gpw).bytes(), ctx->stream, n_depth, n_nu, n_theta, n_theta, G,
@@ -2406,47 +2492,33 @@ int sdx_formation_mean_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double
 int sdx_contribution_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
                          const double* ray_dist, const double* wts, const double* alphas, const double* source, double* C)
 {
-    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "contribution: need n_depth >= 2, n_theta > 0");
-    REQUIRE(n_nu == 0 || (nus && temps && ray_dist && wts && alphas && C), "contribution: null pointer");
-    int rc;
-    if (n_nu == 0) return sdx_contribution_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0);
-    if ((rc = sdx_contribution_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0))) return rc;  // refusals before any copy
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
-    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_s;
+    if (const int no = column_gate<RtColumns>(ctx, kContribution, n_depth, n_nu, n_theta); no < 0) return no;
+    if (n_nu == 0) return SDX_OK;
+    const Columns h = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, wts, {alphas, n_nu}, {source, n_nu});
+    REQUIRE(columns_given(h, true, true) && C, "contribution: null pointer");
     double* d_c;
-    HostPlan plan;
-    plan.in(nus, (size_t)n_nu * f8, &d_nus);
-    plan.in(temps, (size_t)n_depth * f8, &d_t);
-    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
-    plan.in(wts, (size_t)n_theta * f8, &d_w);
-    plan.in(alphas, plane, &d_a);
-    plan.in(source, plane, &d_s);
-    plan.out(C, plane, &d_c);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_contribution_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_s, n_nu, d_c, n_nu))) return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    const auto rows = [&](HostPlan& plan, size_t plane, Columns& d) {
+        plan.in(source, plane, &d.source.p);
+        plan.out(C, plane, &d_c);
+    };
+    return columns_host(ctx, h, n_theta, rows, [&](const Columns& d) {
+        return sdx_contribution_dev(ctx, n_depth, n_nu, n_theta, d.g.nus, d.rays.temps, d.rays.ray_dist, d.rays.wts, d.alphas.p, n_nu, d.source.p, n_nu, d_c, n_nu);
+    });
 }
 
 // ---- emergent intensity of every ray, the surface row alone (k_emergent_intensity) -----------------------------------------
-// As for the contribution function, everything is checked before anything is enqueued, also for an empty grid.
 int sdx_emergent_intensity_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
                                const double* ray_dist, const double* alphas, int64_t ald, const double* source, int64_t source_ld, int inward,
                                double* I_out, int64_t I_ld)
 {
-    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "emergent_intensity: need n_depth >= 2, n_theta > 0");
-    REQUIRE(!ctx->mixed_precision, "emergent_intensity: no emergent intensities with mixed_precision = 1 (they are the fp64 formal solution's last row)");
-    REQUIRE(n_theta <= 64, "emergent_intensity: more than 64 angles are not supported (all angles are traced in one launch)");
-    const int G = n_theta;
-    const int gpw = rt_fit_gpw<RtColumns>(G, n_depth);  // (k_raytrace's budget)
-    REQUIRE(gpw > 0, "emergent_intensity: no emergent intensities for models this deep (the columns do not fit LDS)");
+    const int G = n_theta, gpw = column_gate<RtColumns>(ctx, kEmergentIntensity, n_depth, n_nu, n_theta);  // (k_raytrace's budget)
+    if (gpw < 0) return gpw;
     for (const double* in : {nus, temps, ray_dist, alphas, source})
         REQUIRE(!I_out || I_out != in, "emergent_intensity: not in place (I_out must not be one of the inputs)");
     if (n_nu == 0) return SDX_OK;
-    REQUIRE(nus && ray_dist && alphas && ald >= n_nu && I_out && I_ld >= n_nu, "emergent_intensity: null pointer or leading dimension below n_nu");
-    REQUIRE(source ? source_ld >= n_nu : temps != nullptr, "emergent_intensity: bad source plane (source_ld < n_nu), or neither a source plane nor temperatures");
+    const Columns c = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, nullptr, {alphas, ald}, {source, source_ld});
+    REQUIRE(columns_given(c, false) && I_out && I_ld >= n_nu, "emergent_intensity: null pointer or leading dimension below n_nu");
+    if (int rc = source_or_temps(kEmergentIntensity, "source", c)) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     {
         LaunchScope ls(ctx, "k_emergent_intensity");
@@ -2459,50 +2531,40 @@ int sdx_emergent_intensity_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_th
 int sdx_emergent_intensity_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
                                const double* ray_dist, const double* alphas, const double* source, int inward, double* I_out)
 {
-    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "emergent_intensity: need n_depth >= 2, n_theta > 0");
-    REQUIRE(n_nu == 0 || (nus && temps && ray_dist && alphas && I_out), "emergent_intensity: null pointer");
-    int rc;
-    if ((rc = sdx_emergent_intensity_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, inward, nullptr, 0))) return rc;  // refusals before any copy
+    if (const int no = column_gate<RtColumns>(ctx, kEmergentIntensity, n_depth, n_nu, n_theta); no < 0) return no;
     if (n_nu == 0) return SDX_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
-    const double *d_nus, *d_t, *d_rd, *d_a, *d_s;
+    const Columns h = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, nullptr, {alphas, n_nu}, {source, n_nu});
+    REQUIRE(columns_given(h, false, true) && I_out, "emergent_intensity: null pointer");
     double* d_i;
-    HostPlan plan;
-    plan.in(nus, (size_t)n_nu * f8, &d_nus);
-    plan.in(temps, (size_t)n_depth * f8, &d_t);
-    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
-    plan.in(alphas, plane, &d_a);
-    plan.in(source, plane, &d_s);
-    plan.out(I_out, (size_t)n_theta * n_nu * f8, &d_i);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_emergent_intensity_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_a, n_nu, d_s, n_nu, inward, d_i, n_nu))) return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    const auto rows = [&](HostPlan& plan, size_t plane, Columns& d) {
+        plan.in(source, plane, &d.source.p);
+        plan.out(I_out, (size_t)n_theta * n_nu * sizeof(double), &d_i);
+    };
+    return columns_host(ctx, h, 0, rows, [&](const Columns& d) {
+        return sdx_emergent_intensity_dev(ctx, n_depth, n_nu, n_theta, d.g.nus, d.rays.temps, d.rays.ray_dist, d.alphas.p, n_nu, d.source.p, n_nu, inward, d_i, n_nu);
+    });
 }
 
 // ---- response functions (k_response, k_response_project) -------------------------------------------------------------------
-// As for the contribution function, everything is checked before anything is enqueued, also for an empty grid.
-// wts: the flux weights [n_theta], or with `angles` the cotangent plane [n_theta][wld] (k_response_angles)
-static int response_launch(sdx_ctx* ctx, bool angles, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
-                           const double* ray_dist, const double* wts, int64_t wld, const double* alphas, int64_t ald, const double* source,
-                           int64_t source_ld, double* R_alpha, int64_t R_alpha_ld, double* R_source, int64_t R_source_ld)
+// c.rays.wts: the flux weights [n_theta], or with `angles` the cotangent plane [n_theta][wld] (k_response_angles)
+static int response_launch(sdx_ctx* ctx, bool angles, const Columns& c, int64_t wld, double* R_alpha, int64_t R_alpha_ld, double* R_source,
+                           int64_t R_source_ld)
 {
+    const ColumnEntry& e = angles ? kResponseAngles : kResponse;
     const char* const stage = angles ? "k_response_angles" : "k_response";
-    const auto msg = [&](const char* text) { return std::string(stage + 2) + text; };
-    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, msg(": need n_depth >= 2, n_theta > 0"));
-    REQUIRE(!ctx->mixed_precision, msg(": no response functions with mixed_precision = 1 (they differentiate the fp64 formal solution)"));
-    REQUIRE(n_theta <= 64, msg(": more than 64 angles are not supported (all angles are traced in one launch)"));
-    const int G = n_theta;
-    const int gpw = rt_fit_gpw<RtResponse>(G, n_depth);
-    REQUIRE(gpw > 0, msg(": no response functions for models this deep (the columns and the stashed intensities do not fit LDS)"));
+    const auto msg = [&](const char* text) { return std::string(e.name) + text; };
+    const int n_depth = c.g.n_depth, n_theta = c.rays.n_theta;
+    const int64_t n_nu = c.g.n_nu, ald = c.alphas.ld, source_ld = c.source.ld;
+    const double *const nus = c.g.nus, *const temps = c.rays.temps, *const ray_dist = c.rays.ray_dist, *const wts = c.rays.wts, *const alphas = c.alphas.p,
+                 *const source = c.source.p;
+    const int G = n_theta, gpw = column_gate<RtResponse>(ctx, e, n_depth, n_nu, n_theta);
+    if (gpw < 0) return gpw;
     if (n_nu == 0) return SDX_OK;
     REQUIRE(R_alpha || R_source, msg(": no output requested"));
-    REQUIRE(nus && ray_dist && wts && alphas && ald >= n_nu, msg(": null pointer or alpha_ld below n_nu"));
+    REQUIRE(columns_given(c), msg(": null pointer or alpha_ld below n_nu"));
     REQUIRE(!angles || wld >= n_nu, msg(": cot_ld below n_nu"));
-    REQUIRE((!R_alpha || R_alpha_ld >= n_nu) && (!R_source || R_source_ld >= n_nu), msg(": leading dimension of an output below n_nu"));
-    REQUIRE(source ? source_ld >= n_nu : temps != nullptr, msg(": bad source plane (source_ld < n_nu), or neither a source plane nor temperatures"));
+    REQUIRE(fits(R_alpha, R_alpha_ld, n_nu) && fits(R_source, R_source_ld, n_nu), msg(": leading dimension of an output below n_nu"));
+    if (int rc = source_or_temps(e, "source", c)) return rc;
     for (const double* o : {(const double*)R_alpha, (const double*)R_source})
         REQUIRE(!angles || !o || o != wts, msg(": not in place (an output must not be the cotangent)"));
     {
@@ -2522,16 +2584,16 @@ int sdx_response_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const
                      const double* wts, const double* alphas, int64_t ald, const double* source, int64_t source_ld, double* R_alpha,
                      int64_t R_alpha_ld, double* R_source, int64_t R_source_ld)
 {
-    return response_launch(ctx, false, n_depth, n_nu, n_theta, nus, temps, ray_dist, wts, 0, alphas, ald, source, source_ld, R_alpha, R_alpha_ld, R_source,
-                           R_source_ld);
+    return response_launch(ctx, false, columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, wts, {alphas, ald}, {source, source_ld}), 0, R_alpha, R_alpha_ld,
+                           R_source, R_source_ld);
 }
 
 int sdx_response_angles_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
                             const double* cotangent, int64_t cot_ld, const double* alphas, int64_t ald, const double* source, int64_t source_ld,
                             double* R_alpha, int64_t R_alpha_ld, double* R_source, int64_t R_source_ld)
 {
-    return response_launch(ctx, true, n_depth, n_nu, n_theta, nus, temps, ray_dist, cotangent, cot_ld, alphas, ald, source, source_ld, R_alpha, R_alpha_ld,
-                           R_source, R_source_ld);
+    return response_launch(ctx, true, columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, cotangent, {alphas, ald}, {source, source_ld}), cot_ld, R_alpha,
+                           R_alpha_ld, R_source, R_source_ld);
 }
 
 int sdx_response_project_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const double* R_alpha, int64_t R_ld, const double* part, int64_t part_ld,
@@ -2551,30 +2613,20 @@ int sdx_response_project_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, const doub
 static int response_host(sdx_ctx* ctx, bool angles, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
                          const double* ray_dist, const double* wts, const double* alphas, const double* source, double* R_alpha, double* R_source)
 {
-    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "response: need n_depth >= 2, n_theta > 0");
-    REQUIRE(n_nu == 0 || (nus && temps && ray_dist && wts && alphas), "response: null pointer");
-    REQUIRE(n_nu == 0 || R_alpha || R_source, "response: no output requested");
-    int rc;
-    if ((rc = response_launch(ctx, angles, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0)) || n_nu == 0)
-        return rc;  // refusals before any copy
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
-    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_s;
+    REQUIRE(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0, "response: need n_depth >= 2, n_theta > 0");  // (both twins say this, and what follows the gate, as "response")
+    if (const int no = column_gate<RtResponse>(ctx, angles ? kResponseAngles : kResponse, n_depth, n_nu, n_theta); no < 0) return no;
+    if (n_nu == 0) return SDX_OK;
+    const Columns h = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, wts, {alphas, n_nu}, {source, n_nu});
+    REQUIRE(columns_given(h, true, true), "response: null pointer");
+    REQUIRE(R_alpha || R_source, "response: no output requested");
     double *d_ra, *d_rs;
-    HostPlan plan;
-    plan.in(nus, (size_t)n_nu * f8, &d_nus);
-    plan.in(temps, (size_t)n_depth * f8, &d_t);
-    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
-    plan.in(wts, (angles ? (size_t)n_theta * n_nu : (size_t)n_theta) * f8, &d_w);
-    plan.in(alphas, plane, &d_a);
-    plan.in(source, plane, &d_s);
-    plan.out(R_alpha, plane, &d_ra);
-    plan.out(R_source, plane, &d_rs);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = response_launch(ctx, angles, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, n_nu, d_a, n_nu, d_s, n_nu, d_ra, n_nu, d_rs, n_nu))) return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    const auto rows = [&](HostPlan& plan, size_t plane, Columns& d) {
+        plan.in(source, plane, &d.source.p);
+        plan.out(R_alpha, plane, &d_ra);
+        plan.out(R_source, plane, &d_rs);
+    };
+    return columns_host(ctx, h, angles ? (size_t)n_theta * n_nu : (size_t)n_theta, rows,
+                        [&](const Columns& d) { return response_launch(ctx, angles, d, n_nu, d_ra, n_nu, d_rs, n_nu); });
 }
 
 int sdx_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
@@ -2590,33 +2642,19 @@ int sdx_response_angles_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta
 }
 
 // ---- mean intensity and the scattering source function (k_lambda) ----------------------------------------------------------
-// As for the response functions, everything is checked before anything is enqueued, also for an empty grid.
-namespace {
-// the refusals both entries share, under the entry's name; -> the launch shape
-int lambda_shape(sdx_ctx* ctx, const char* what, int n_depth, int64_t n_nu, int n_theta, int* gpw, int* waves)
-{
-    auto refuse = [&](const char* why) { return fail(SDX_ERR_ARG, std::string(what) + ": " + why); };
-    if (!(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0)) return refuse("need n_depth >= 2, n_theta > 0");
-    if (ctx->mixed_precision) return refuse("not with mixed_precision = 1 (the mean intensity is that of the fp64 formal solution)");
-    if (n_theta > 64) return refuse("more than 64 angles are not supported (all angles are traced in one launch)");
-    *gpw = rt_fit_gpw<RtLambda>(n_theta, n_depth);
-    if (*gpw <= 0) return refuse("models this deep are not served (the columns of one frequency do not fit LDS)");
-    *waves = lambda_waves(n_theta, n_depth, *gpw);
-    return SDX_OK;
-}
-}  // namespace
-
 int sdx_mean_intensity_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
                            const double* mean_weights, const double* alphas, int64_t ald, const double* source, int64_t source_ld, double* J,
                            int64_t J_ld, double* lambda_diag, int64_t L_ld)
 {
-    int gpw = 0, waves = 0, rc;
-    if ((rc = lambda_shape(ctx, "mean_intensity", n_depth, n_nu, n_theta, &gpw, &waves))) return rc;
+    const int gpw = column_gate<RtLambda>(ctx, kMeanIntensity, n_depth, n_nu, n_theta);
+    if (gpw < 0) return gpw;
     if (n_nu == 0) return SDX_OK;
+    const Columns c = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, {alphas, ald}, {source, source_ld});
     REQUIRE(J || lambda_diag, "mean_intensity: no output requested");
-    REQUIRE(nus && ray_dist && mean_weights && alphas && ald >= n_nu, "mean_intensity: null pointer or alpha_ld below n_nu");
-    REQUIRE((!J || J_ld >= n_nu) && (!lambda_diag || L_ld >= n_nu), "mean_intensity: leading dimension of an output below n_nu");
-    REQUIRE(source ? source_ld >= n_nu : temps != nullptr, "mean_intensity: bad source plane (source_ld < n_nu), or neither a source plane nor temperatures");
+    REQUIRE(columns_given(c), "mean_intensity: null pointer or alpha_ld below n_nu");
+    REQUIRE(fits(J, J_ld, n_nu) && fits(lambda_diag, L_ld, n_nu), "mean_intensity: leading dimension of an output below n_nu");
+    if (int rc = source_or_temps(kMeanIntensity, "source", c)) return rc;
+    const int waves = lambda_waves(n_theta, n_depth, gpw);
     {
         LaunchScope ls(ctx, "k_lambda", "k_lambda<false>");
         hipLaunchKernelGGL(k_lambda<false>, dim3(lambda_blocks(n_nu, gpw, waves)), dim3(64 * waves), waves * RtLambda(n_theta, n_depth, gpw).bytes(), ctx->stream,
@@ -2631,13 +2669,15 @@ int sdx_scatter_source_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta,
                            const double* thermal, int64_t thermal_ld, double tol, int max_iter, double* S, int64_t S_ld, double* J, int64_t J_ld,
                            int* iterations, int* status, double* change)
 {
-    int gpw = 0, waves = 0, rc;
-    if ((rc = lambda_shape(ctx, "scatter_source", n_depth, n_nu, n_theta, &gpw, &waves))) return rc;
-    REQUIRE(tol >= 0.0 && max_iter >= 1, "scatter_source: need tol >= 0 (not NaN) and max_iter >= 1");
+    const int gpw = column_gate<RtLambda>(ctx, kScatterSource, n_depth, n_nu, n_theta);
+    if (gpw < 0) return gpw;
+    if (int rc = iteration_check(kScatterSource, tol, max_iter)) return rc;
     if (n_nu == 0) return SDX_OK;
-    REQUIRE(nus && ray_dist && mean_weights && alphas && ald >= n_nu && alpha_scatter && S, "scatter_source: null pointer or alpha_ld below n_nu");
-    REQUIRE((scatter_ld == 0 || scatter_ld >= n_nu) && S_ld >= n_nu && (!J || J_ld >= n_nu), "scatter_source: a leading dimension below n_nu (scatter_ld: 0 or >= n_nu)");
-    REQUIRE(thermal ? thermal_ld >= n_nu : temps != nullptr, "scatter_source: bad thermal plane (thermal_ld < n_nu), or neither a thermal plane nor temperatures");
+    const Columns c = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, {alphas, ald}, {thermal, thermal_ld});
+    REQUIRE(columns_given(c) && alpha_scatter && S, "scatter_source: null pointer or alpha_ld below n_nu");
+    REQUIRE((scatter_ld == 0 || scatter_ld >= n_nu) && S_ld >= n_nu && fits(J, J_ld, n_nu), "scatter_source: a leading dimension below n_nu (scatter_ld: 0 or >= n_nu)");
+    if (int rc = source_or_temps(kScatterSource, "thermal", c)) return rc;
+    const int waves = lambda_waves(n_theta, n_depth, gpw);
     {
         LaunchScope ls(ctx, "k_lambda", "k_lambda<true>");
         hipLaunchKernelGGL(k_lambda<true>, dim3(lambda_blocks(n_nu, gpw, waves)), dim3(64 * waves), waves * RtLambda(n_theta, n_depth, gpw).bytes(), ctx->stream,
@@ -2650,95 +2690,62 @@ int sdx_scatter_source_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta,
 int sdx_mean_intensity_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
                            const double* mean_weights, const double* alphas, const double* source, double* J, double* lambda_diag)
 {
-    int rc;
-    if ((rc = sdx_mean_intensity_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0)) || n_nu == 0)
-        return rc;  // refusals before any copy
-    REQUIRE(n_nu > 0 && nus && temps && ray_dist && mean_weights && alphas, "mean_intensity: null pointer");
+    if (const int no = column_gate<RtLambda>(ctx, kMeanIntensity, n_depth, n_nu, n_theta); no < 0) return no;
+    if (n_nu == 0) return SDX_OK;
+    const Columns h = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, {alphas, n_nu}, {source, n_nu});
+    REQUIRE(columns_given(h, true, true), "mean_intensity: null pointer");
     REQUIRE(J || lambda_diag, "mean_intensity: no output requested");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
-    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_s;
     double *d_j, *d_l;
-    HostPlan plan;
-    plan.in(nus, (size_t)n_nu * f8, &d_nus);
-    plan.in(temps, (size_t)n_depth * f8, &d_t);
-    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
-    plan.in(mean_weights, (size_t)n_theta * f8, &d_w);
-    plan.in(alphas, plane, &d_a);
-    plan.in(source, plane, &d_s);
-    plan.out(J, plane, &d_j);
-    plan.out(lambda_diag, plane, &d_l);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_mean_intensity_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_s, n_nu, d_j, n_nu, d_l, n_nu))) return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    const auto rows = [&](HostPlan& plan, size_t plane, Columns& d) {
+        plan.in(source, plane, &d.source.p);
+        plan.out(J, plane, &d_j);
+        plan.out(lambda_diag, plane, &d_l);
+    };
+    return columns_host(ctx, h, n_theta, rows, [&](const Columns& d) {
+        return sdx_mean_intensity_dev(ctx, n_depth, n_nu, n_theta, d.g.nus, d.rays.temps, d.rays.ray_dist, d.rays.wts, d.alphas.p, n_nu, d.source.p, n_nu, d_j, n_nu, d_l, n_nu);
+    });
 }
 
 int sdx_scatter_source_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
                            const double* mean_weights, const double* alphas, const double* alpha_scatter, int scatter_per_frequency,
                            const double* thermal, double tol, int max_iter, double* S, double* J, int* iterations, int* status, double* change)
 {
-    int rc;
-    if ((rc = sdx_scatter_source_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, tol, max_iter, nullptr, 0,
-                                     nullptr, 0, nullptr, nullptr, nullptr)) ||
-        n_nu == 0)
-        return rc;  // refusals before any copy
-    REQUIRE(n_nu > 0 && nus && temps && ray_dist && mean_weights && alphas && alpha_scatter && S, "scatter_source: null pointer");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
-    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_sc, *d_b;
+    if (const int no = column_gate<RtLambda>(ctx, kScatterSource, n_depth, n_nu, n_theta); no < 0) return no;
+    if (int rc = iteration_check(kScatterSource, tol, max_iter)) return rc;
+    if (n_nu == 0) return SDX_OK;
+    const Columns h = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, {alphas, n_nu}, {thermal, n_nu});
+    REQUIRE(columns_given(h, true, true) && alpha_scatter && S, "scatter_source: null pointer");
+    const double* d_sc;
     double *d_s, *d_j, *d_c;
     int *d_it, *d_st;
-    HostPlan plan;
-    plan.in(nus, (size_t)n_nu * f8, &d_nus);
-    plan.in(temps, (size_t)n_depth * f8, &d_t);
-    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
-    plan.in(mean_weights, (size_t)n_theta * f8, &d_w);
-    plan.in(alphas, plane, &d_a);
-    plan.in(alpha_scatter, scatter_per_frequency ? plane : (size_t)n_depth * f8, &d_sc);
-    plan.in(thermal, plane, &d_b);
-    plan.out(S, plane, &d_s);
-    plan.out(J, plane, &d_j);
-    plan.out(iterations, (size_t)n_nu * sizeof(int), &d_it);
-    plan.out(status, (size_t)n_nu * sizeof(int), &d_st);
-    plan.out(change, (size_t)n_nu * f8, &d_c);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_scatter_source_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_sc, scatter_per_frequency ? n_nu : 0, d_b, n_nu, tol,
-                                     max_iter, d_s, n_nu, d_j, n_nu, d_it, d_st, d_c)))
-        return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    const auto rows = [&](HostPlan& plan, size_t plane, Columns& d) {
+        plan.in(alpha_scatter, scatter_per_frequency ? plane : (size_t)n_depth * sizeof(double), &d_sc);
+        plan.in(thermal, plane, &d.source.p);
+        plan.out(S, plane, &d_s);
+        plan.out(J, plane, &d_j);
+        plan.out(iterations, (size_t)n_nu * sizeof(int), &d_it);
+        plan.out(status, (size_t)n_nu * sizeof(int), &d_st);
+        plan.out(change, (size_t)n_nu * sizeof(double), &d_c);
+    };
+    return columns_host(ctx, h, n_theta, rows, [&](const Columns& d) {
+        return sdx_scatter_source_dev(ctx, n_depth, n_nu, n_theta, d.g.nus, d.rays.temps, d.rays.ray_dist, d.rays.wts, d.alphas.p, n_nu, d_sc,
+                                      scatter_per_frequency ? n_nu : 0, d.source.p, n_nu, tol, max_iter, d_s, n_nu, d_j, n_nu, d_it, d_st, d_c);
+    });
 }
 
 // ---- the adjoint of the mean intensity and of the scattering solve (k_lambda_adjoint) ---------------------------------------
-// As above, everything is checked before anything is enqueued, also for an empty grid.
-namespace {
-// the refusals both entries share, under the entry's name; -> the frequencies per wave of the launch
-int lambda_adjoint_shape(sdx_ctx* ctx, const char* what, int n_depth, int64_t n_nu, int n_theta, int* gpw)
-{
-    auto refuse = [&](const char* why) { return fail(SDX_ERR_ARG, std::string(what) + ": " + why); };
-    if (!(ctx && n_depth >= 2 && n_nu >= 0 && n_theta > 0)) return refuse("need n_depth >= 2, n_theta > 0");
-    if (ctx->mixed_precision) return refuse("not with mixed_precision = 1 (the mean intensity is that of the fp64 formal solution)");
-    if (n_theta > 64) return refuse("more than 64 angles are not supported (all angles are traced in one launch)");
-    *gpw = rt_fit_gpw<RtLambdaAdjoint>(n_theta, n_depth);
-    if (*gpw <= 0) return refuse("models this deep are not served (the columns and stashed values of one frequency do not fit LDS)");
-    return SDX_OK;
-}
-}  // namespace
-
 int sdx_mean_intensity_adjoint_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
                                    const double* ray_dist, const double* mean_weights, const double* alphas, int64_t ald, const double* z, int64_t z_ld,
                                    const double* source, int64_t source_ld, double* Lt, int64_t Lt_ld, double* G, int64_t G_ld)
 {
-    int gpw = 0, rc;
-    if ((rc = lambda_adjoint_shape(ctx, "mean_intensity_adjoint", n_depth, n_nu, n_theta, &gpw))) return rc;
+    const int gpw = column_gate<RtLambdaAdjoint>(ctx, kMeanIntensityAdjoint, n_depth, n_nu, n_theta);
+    if (gpw < 0) return gpw;
     if (n_nu == 0) return SDX_OK;
+    const Columns c = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, {alphas, ald}, {source, source_ld});
     REQUIRE(Lt || G, "mean_intensity_adjoint: no output requested");
-    REQUIRE(nus && ray_dist && mean_weights && alphas && ald >= n_nu && z && z_ld >= n_nu, "mean_intensity_adjoint: null pointer or a leading dimension of an input below n_nu");
-    REQUIRE((!Lt || Lt_ld >= n_nu) && (!G || G_ld >= n_nu), "mean_intensity_adjoint: leading dimension of an output below n_nu");
-    REQUIRE(source ? source_ld >= n_nu : temps != nullptr, "mean_intensity_adjoint: bad source plane (source_ld < n_nu), or neither a source plane nor temperatures");
+    REQUIRE(columns_given(c) && z && z_ld >= n_nu, "mean_intensity_adjoint: null pointer or a leading dimension of an input below n_nu");
+    REQUIRE(fits(Lt, Lt_ld, n_nu) && fits(G, G_ld, n_nu), "mean_intensity_adjoint: leading dimension of an output below n_nu");
+    if (int rc = source_or_temps(kMeanIntensityAdjoint, "source", c)) return rc;
     const RtLambdaAdjoint lay(n_theta, n_depth, gpw);
     const int waves = lay.waves();
     {
@@ -2756,17 +2763,18 @@ int sdx_scatter_response_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_thet
                              int64_t R_thermal_ld, double* R_absorption, int64_t R_absorption_ld, double* R_scatter, int64_t R_scatter_ld,
                              int* iterations, int* status, double* change)
 {
-    int gpw = 0, rc;
-    if ((rc = lambda_adjoint_shape(ctx, "scatter_response", n_depth, n_nu, n_theta, &gpw))) return rc;
-    REQUIRE(tol >= 0.0 && max_iter >= 1, "scatter_response: need tol >= 0 (not NaN) and max_iter >= 1");
+    const int gpw = column_gate<RtLambdaAdjoint>(ctx, kScatterResponse, n_depth, n_nu, n_theta);
+    if (gpw < 0) return gpw;
+    if (int rc = iteration_check(kScatterResponse, tol, max_iter)) return rc;
     if (n_nu == 0) return SDX_OK;
+    const Columns c = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, {alphas, ald}, {thermal, thermal_ld});
     REQUIRE(y || R_thermal || R_absorption || R_scatter, "scatter_response: no output requested");
-    REQUIRE(nus && ray_dist && mean_weights && alphas && ald >= n_nu && alpha_scatter && S && cotangent, "scatter_response: null pointer or alpha_ld below n_nu");
-    REQUIRE((scatter_ld == 0 || scatter_ld >= n_nu) && S_ld >= n_nu && cotangent_ld >= n_nu && (!direct || direct_ld >= n_nu),
+    REQUIRE(columns_given(c) && alpha_scatter && S && cotangent, "scatter_response: null pointer or alpha_ld below n_nu");
+    REQUIRE((scatter_ld == 0 || scatter_ld >= n_nu) && S_ld >= n_nu && cotangent_ld >= n_nu && fits(direct, direct_ld, n_nu),
             "scatter_response: a leading dimension of an input below n_nu (scatter_ld: 0 or >= n_nu)");
-    REQUIRE((!y || y_ld >= n_nu) && (!R_thermal || R_thermal_ld >= n_nu) && (!R_absorption || R_absorption_ld >= n_nu) && (!R_scatter || R_scatter_ld >= n_nu),
+    REQUIRE(fits(y, y_ld, n_nu) && fits(R_thermal, R_thermal_ld, n_nu) && fits(R_absorption, R_absorption_ld, n_nu) && fits(R_scatter, R_scatter_ld, n_nu),
             "scatter_response: leading dimension of an output below n_nu");
-    REQUIRE(thermal ? thermal_ld >= n_nu : temps != nullptr, "scatter_response: bad thermal plane (thermal_ld < n_nu), or neither a thermal plane nor temperatures");
+    if (int rc = source_or_temps(kScatterResponse, "thermal", c)) return rc;
     const RtLambdaAdjoint lay(n_theta, n_depth, gpw);
     const int waves = lay.waves();
     {
@@ -2784,31 +2792,23 @@ int sdx_mean_intensity_adjoint_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int 
                                    const double* ray_dist, const double* mean_weights, const double* alphas, const double* z, const double* source,
                                    double* Lt, double* G)
 {
-    int rc;
-    if ((rc = sdx_mean_intensity_adjoint_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0)) ||
-        n_nu == 0)
-        return rc;  // refusals before any copy
-    REQUIRE(n_nu > 0 && nus && temps && ray_dist && mean_weights && alphas && z, "mean_intensity_adjoint: null pointer");
+    if (const int no = column_gate<RtLambdaAdjoint>(ctx, kMeanIntensityAdjoint, n_depth, n_nu, n_theta); no < 0) return no;
+    if (n_nu == 0) return SDX_OK;
+    const Columns h = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, {alphas, n_nu}, {source, n_nu});
+    REQUIRE(columns_given(h, true, true) && z, "mean_intensity_adjoint: null pointer");
     REQUIRE(Lt || G, "mean_intensity_adjoint: no output requested");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
-    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_z, *d_s;
+    const double* d_z;
     double *d_lt, *d_g;
-    HostPlan plan;
-    plan.in(nus, (size_t)n_nu * f8, &d_nus);
-    plan.in(temps, (size_t)n_depth * f8, &d_t);
-    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
-    plan.in(mean_weights, (size_t)n_theta * f8, &d_w);
-    plan.in(alphas, plane, &d_a);
-    plan.in(z, plane, &d_z);
-    plan.in(source, plane, &d_s);
-    plan.out(Lt, plane, &d_lt);
-    plan.out(G, plane, &d_g);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_mean_intensity_adjoint_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_z, n_nu, d_s, n_nu, d_lt, n_nu, d_g, n_nu))) return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    const auto rows = [&](HostPlan& plan, size_t plane, Columns& d) {
+        plan.in(z, plane, &d_z);
+        plan.in(source, plane, &d.source.p);
+        plan.out(Lt, plane, &d_lt);
+        plan.out(G, plane, &d_g);
+    };
+    return columns_host(ctx, h, n_theta, rows, [&](const Columns& d) {
+        return sdx_mean_intensity_adjoint_dev(ctx, n_depth, n_nu, n_theta, d.g.nus, d.rays.temps, d.rays.ray_dist, d.rays.wts, d.alphas.p, n_nu, d_z, n_nu,
+                                              d.source.p, n_nu, d_lt, n_nu, d_g, n_nu);
+    });
 }
 
 int sdx_scatter_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
@@ -2816,43 +2816,34 @@ int sdx_scatter_response_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_thet
                              const double* thermal, const double* S, const double* cotangent, const double* direct, double tol, int max_iter, double* y,
                              double* R_thermal, double* R_absorption, double* R_scatter, int* iterations, int* status, double* change)
 {
-    int rc;
-    if ((rc = sdx_scatter_response_dev(ctx, n_depth, 0, n_theta, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0,
-                                       nullptr, 0, tol, max_iter, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr)) ||
-        n_nu == 0)
-        return rc;  // refusals before any copy
-    REQUIRE(n_nu > 0 && nus && temps && ray_dist && mean_weights && alphas && alpha_scatter && S && cotangent, "scatter_response: null pointer");
+    if (const int no = column_gate<RtLambdaAdjoint>(ctx, kScatterResponse, n_depth, n_nu, n_theta); no < 0) return no;
+    if (int rc = iteration_check(kScatterResponse, tol, max_iter)) return rc;
+    if (n_nu == 0) return SDX_OK;
+    const Columns h = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, {alphas, n_nu}, {thermal, n_nu});
+    REQUIRE(columns_given(h, true, true) && alpha_scatter && S && cotangent, "scatter_response: null pointer");
     REQUIRE(y || R_thermal || R_absorption || R_scatter, "scatter_response: no output requested");
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t f8 = sizeof(double), plane = (size_t)n_depth * n_nu * f8;
-    const double *d_nus, *d_t, *d_rd, *d_w, *d_a, *d_sc, *d_b, *d_s, *d_c, *d_d;
+    const double *d_sc, *d_s, *d_c, *d_d;
     double *d_y, *d_rt, *d_ra, *d_rs, *d_ch;
     int *d_it, *d_st;
-    HostPlan plan;
-    plan.in(nus, (size_t)n_nu * f8, &d_nus);
-    plan.in(temps, (size_t)n_depth * f8, &d_t);
-    plan.in(ray_dist, (size_t)(n_depth - 1) * n_theta * f8, &d_rd);
-    plan.in(mean_weights, (size_t)n_theta * f8, &d_w);
-    plan.in(alphas, plane, &d_a);
-    plan.in(alpha_scatter, scatter_per_frequency ? plane : (size_t)n_depth * f8, &d_sc);
-    plan.in(thermal, plane, &d_b);
-    plan.in(S, plane, &d_s);
-    plan.in(cotangent, plane, &d_c);
-    plan.in(direct, plane, &d_d);
-    plan.out(y, plane, &d_y);
-    plan.out(R_thermal, plane, &d_rt);
-    plan.out(R_absorption, plane, &d_ra);
-    plan.out(R_scatter, plane, &d_rs);
-    plan.out(iterations, (size_t)n_nu * sizeof(int), &d_it);
-    plan.out(status, (size_t)n_nu * sizeof(int), &d_st);
-    plan.out(change, (size_t)n_nu * f8, &d_ch);
-    HostIo io{ctx};
-    if ((rc = io.stage(plan))) return rc;
-    if ((rc = sdx_scatter_response_dev(ctx, n_depth, n_nu, n_theta, d_nus, d_t, d_rd, d_w, d_a, n_nu, d_sc, scatter_per_frequency ? n_nu : 0, d_b, n_nu, d_s, n_nu,
-                                       d_c, n_nu, d_d, n_nu, tol, max_iter, d_y, n_nu, d_rt, n_nu, d_ra, n_nu, d_rs, n_nu, d_it, d_st, d_ch)))
-        return rc;
-    if ((rc = io.collect(plan))) return rc;
-    return io.finish();
+    const auto rows = [&](HostPlan& plan, size_t plane, Columns& d) {
+        plan.in(alpha_scatter, scatter_per_frequency ? plane : (size_t)n_depth * sizeof(double), &d_sc);
+        plan.in(thermal, plane, &d.source.p);
+        plan.in(S, plane, &d_s);
+        plan.in(cotangent, plane, &d_c);
+        plan.in(direct, plane, &d_d);
+        plan.out(y, plane, &d_y);
+        plan.out(R_thermal, plane, &d_rt);
+        plan.out(R_absorption, plane, &d_ra);
+        plan.out(R_scatter, plane, &d_rs);
+        plan.out(iterations, (size_t)n_nu * sizeof(int), &d_it);
+        plan.out(status, (size_t)n_nu * sizeof(int), &d_st);
+        plan.out(change, (size_t)n_nu * sizeof(double), &d_ch);
+    };
+    return columns_host(ctx, h, n_theta, rows, [&](const Columns& d) {
+        return sdx_scatter_response_dev(ctx, n_depth, n_nu, n_theta, d.g.nus, d.rays.temps, d.rays.ray_dist, d.rays.wts, d.alphas.p, n_nu, d_sc,
+                                        scatter_per_frequency ? n_nu : 0, d.source.p, n_nu, d_s, n_nu, d_c, n_nu, d_d, n_nu, tol, max_iter, d_y, n_nu, d_rt, n_nu, d_ra,
+                                        n_nu, d_rs, n_nu, d_it, d_st, d_ch);
+    });
 }
 
 // ---- per-line flux sensitivities (k_response_weight, k_line_adjoint) --------------------------------------------------------

@@ -414,37 +414,33 @@ class SpectralSynthesizer:
         inst.observe(self.d_lambdas, flux, n, out=self.d_observed, broadened=True)
         inst.observe(self.d_lambdas, flux, n, reference=cont, out=self.d_observed_normalized, broadened=True)
 
+    def _columns(self, weights=None):
+        """what every formal solution of the step's columns is called with first: the shape, the shard's frequencies, the temperatures, the
+        ray table, the angle weights (the intensities take none) and the step's total_alphas"""
+        w = () if weights is None else (weights.ptr,)
+        return (self.n_depth, self.count, self.n_theta, self.d_nus.ptr + 8 * self.begin, self.d_t.ptr, self.d_ray.ptr, *w, self.d_total.ptr, self.count)
+
     def _enqueue_contribution(self):
-        cnt = self.count
-        self.ctx.call("sdx_contribution_dev", self.n_depth, cnt, self.n_theta, self.d_nus.ptr + 8 * self.begin, self.d_t.ptr, self.d_ray.ptr,
-                      self.d_w.ptr, self.d_total.ptr, cnt, None, 0, self.d_C.ptr, cnt)
+        self.ctx.call("sdx_contribution_dev", *self._columns(self.d_w), None, 0, self.d_C.ptr, self.count)
 
     def _enqueue_intensities(self):
-        cnt = self.count
-        self.ctx.call("sdx_emergent_intensity_dev", self.n_depth, cnt, self.n_theta, self.d_nus.ptr + 8 * self.begin, self.d_t.ptr, self.d_ray.ptr,
-                      self.d_total.ptr, cnt, None, 0, 0, self.d_I.ptr, cnt)
+        self.ctx.call("sdx_emergent_intensity_dev", *self._columns(), None, 0, 0, self.d_I.ptr, self.count)
 
     def _enqueue_response(self):
-        cnt = self.count
-        self.ctx.call("sdx_response_dev", self.n_depth, cnt, self.n_theta, self.d_nus.ptr + 8 * self.begin, self.d_t.ptr, self.d_ray.ptr,
-                      self.d_w.ptr, self.d_total.ptr, cnt, None, 0, self.d_Ra.ptr, cnt, self.d_Rs.ptr, cnt)
+        self.ctx.call("sdx_response_dev", *self._columns(self.d_w), None, 0, self.d_Ra.ptr, self.count, self.d_Rs.ptr, self.count)
 
     def _enqueue_scattering(self):
         """the scattering source function of the step's columns from its total_alphas, then the flux of that source function"""
-        c, cnt, nus = self.ctx, self.count, self.d_nus.ptr + 8 * self.begin
-        c.call("sdx_scatter_source_dev", self.n_depth, cnt, self.n_theta, nus, self.d_t.ptr, self.d_ray.ptr, self.d_mean_w.ptr, self.d_total.ptr, cnt,
-               self.d_thomson.ptr, 0, None, 0, self.scattering["tol"], self.scattering["max_iter"], self.d_Ssc.ptr, cnt, self.d_Jsc.ptr, cnt,
-               self.d_sc_iterations.ptr, self.d_sc_status.ptr, self.d_sc_change.ptr)
-        c.call("sdx_raytrace_source_dev", self.n_depth, cnt, self.n_theta, nus, self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, self.d_total.ptr, cnt,
-               self.d_Ssc.ptr, cnt, self.d_Fsc.ptr, cnt, None, 0, 0, 1.0)
+        c, cnt, flux, mean = self.ctx, self.count, self._columns(self.d_w), self._columns(self.d_mean_w)
+        c.call("sdx_scatter_source_dev", *mean, self.d_thomson.ptr, 0, None, 0, self.scattering["tol"], self.scattering["max_iter"], self.d_Ssc.ptr, cnt,
+               self.d_Jsc.ptr, cnt, self.d_sc_iterations.ptr, self.d_sc_status.ptr, self.d_sc_change.ptr)
+        c.call("sdx_raytrace_source_dev", *flux, self.d_Ssc.ptr, cnt, self.d_Fsc.ptr, cnt, None, 0, 0, 1.0)
         if self._scattering_response:
             # the derivative of that flux: the response functions at source = S are its direct part and cotangent, the adjoint solve the rest
-            c.call("sdx_response_dev", self.n_depth, cnt, self.n_theta, nus, self.d_t.ptr, self.d_ray.ptr, self.d_w.ptr, self.d_total.ptr, cnt,
-                   self.d_Ssc.ptr, cnt, self.d_sc_direct.ptr, cnt, self.d_sc_cotangent.ptr, cnt)
-            c.call("sdx_scatter_response_dev", self.n_depth, cnt, self.n_theta, nus, self.d_t.ptr, self.d_ray.ptr, self.d_mean_w.ptr, self.d_total.ptr, cnt,
-                   self.d_thomson.ptr, 0, None, 0, self.d_Ssc.ptr, cnt, self.d_sc_cotangent.ptr, cnt, self.d_sc_direct.ptr, cnt, self.scattering["tol"],
-                   self.scattering["max_iter"], None, 0, self.d_sc_Rt.ptr, cnt, self.d_sc_Ra.ptr, cnt, self.d_sc_Rs.ptr, cnt, self.d_scr_iterations.ptr,
-                   self.d_scr_status.ptr, None)
+            c.call("sdx_response_dev", *flux, self.d_Ssc.ptr, cnt, self.d_sc_direct.ptr, cnt, self.d_sc_cotangent.ptr, cnt)
+            c.call("sdx_scatter_response_dev", *mean, self.d_thomson.ptr, 0, None, 0, self.d_Ssc.ptr, cnt, self.d_sc_cotangent.ptr, cnt,
+                   self.d_sc_direct.ptr, cnt, self.scattering["tol"], self.scattering["max_iter"], None, 0, self.d_sc_Rt.ptr, cnt, self.d_sc_Ra.ptr, cnt,
+                   self.d_sc_Rs.ptr, cnt, self.d_scr_iterations.ptr, self.d_scr_status.ptr, None)
 
     def _enqueue_synthesis(self):
         """The step, whatever its configuration: one sdx_synthesis_options, one sdx_synthesize_opt_dev call.  A line list of scalars

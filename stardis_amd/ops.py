@@ -19,13 +19,30 @@ def _host(a, dtype=F8):
     return a if a.ndim == 0 else np.ascontiguousarray(a)  # ascontiguousarray would turn a scalar into shape (1,)
 
 
+def _on_device(a):
+    return isinstance(a, DeviceArray) or hasattr(a, "data_ptr")
+
+
 def _dev(ctx, a, dtype=F8):
     """DeviceArray for a host array (uploads) or pass a DeviceArray / CUDA tensor through."""
-    if a is None:
-        return None
-    if isinstance(a, DeviceArray) or hasattr(a, "data_ptr"):
+    if a is None or _on_device(a):
         return a
     return ctx.upload(_host(a, dtype), dtype)
+
+
+def _shape(a):
+    """the shape of a host or device array as a tuple of ints"""
+    return tuple(int(v) for v in (a.shape if hasattr(a, "shape") else np.shape(a)))
+
+
+def _source_plane(source, shape):
+    """a caller's source-function plane on the host, its shape checked (None stays None)"""
+    if source is None:
+        return None
+    src = _host(source)
+    if src.shape != shape:
+        raise ValueError(f"source function must return shape {shape}, got {src.shape}")
+    return src
 
 
 # ------------------------------------------------------------------------------------------------ voigt.py
@@ -556,10 +573,7 @@ def raytrace_arrays(tracing_nus, temperatures, ray_distances, theta_weights, tot
     args = (t.size, nus.size, n_theta, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, ptr_of(d_alpha), nus.size, ptr_of(d_F), nus.size,
             ptr_of(d_I), 0 if F_nu is None else 1)
     if source is not None:
-        src = _host(source)
-        if src.shape != (t.size, nus.size):
-            raise ValueError(f"source function must return shape {(t.size, nus.size)}, got {src.shape}")
-        d_S = ctx.upload(src)
+        d_S = ctx.upload(_source_plane(source, (t.size, nus.size)))
         ctx.call("sdx_raytrace_source_dev", *args[:9], d_S.ptr, nus.size, *args[9:], 1 if inward_rays else 0, float(photospheric_correction))
     elif inward_rays:
         ctx.call("sdx_raytrace_spherical_dev", *args, float(photospheric_correction))
@@ -568,27 +582,95 @@ def raytrace_arrays(tracing_nus, temperatures, ray_distances, theta_weights, tot
     return (d_F.numpy() if want_flux else None), (d_I.numpy() if track else None)
 
 
+def _column_inputs(tracing_nus, temperatures, ray_distances, total_alphas, weights=None, cotangent=None, source=None, what=None, planes=None,
+                   checked=True):
+    """The host-side intake of the products of the formal solution, before any device is asked for -> namespace(nus, t, rd, w, n_theta,
+    shape, source, planes).  The number of angles is that of `weights`, else of the rows of `cotangent` (response_angles' (N_theta, N_nu)),
+    else of ray_distances' columns.  source: a host source-function plane; planes: {name: plane or None}, host or device (with `what`,
+    the name the scattering entries refuse more than 64 or no angles under).  checked=False (contribution_arrays: arguments as
+    raytrace_arrays): no shape is checked but the source plane's."""
+    import types
+
+    nus = _host(tracing_nus).reshape(-1)
+    t = _host(temperatures).reshape(-1)
+    rd = _host(ray_distances)
+    shape = (t.size, nus.size)
+    w = None
+    if weights is not None:
+        w = _host(weights).reshape(-1)
+        n_theta = w.size
+        if what and n_theta > 64:
+            raise ValueError(f"{what}: more than 64 angles are not supported, got {n_theta}")
+    elif cotangent is not None:
+        cshape = _shape(cotangent)
+        if len(cshape) != 2 or cshape[1] != nus.size or cshape[0] < 1:
+            raise ValueError(f"cotangent must have shape (n_theta, {nus.size}), got {cshape}")
+        n_theta = cshape[0]
+    else:
+        if t.size < 2 or rd.ndim != 2 or rd.shape[0] != t.size - 1 or rd.shape[1] < 1:
+            raise ValueError(f"ray_distances must have shape ({t.size - 1}, N_theta), got {rd.shape}")
+        n_theta = rd.shape[1]
+        if n_theta > 64:
+            raise ValueError(f"at most 64 angles are traced in one launch, got {n_theta}")
+    if checked:
+        if t.size < 2 or (what and n_theta == 0) or rd.size != (t.size - 1) * n_theta:
+            raise ValueError(f"ray_distances must have shape {(t.size - 1, n_theta)}, got {rd.shape}")
+        if _shape(total_alphas) != shape:
+            raise ValueError(f"total_alphas must have shape {shape}, got {_shape(total_alphas)}")
+    rd = rd.reshape(t.size - 1, n_theta if checked else -1)
+    out = {}
+    for name, plane in (planes or {}).items():
+        if plane is not None and not _on_device(plane):
+            plane = _host(plane)
+        if plane is not None and _shape(plane) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(plane.shape)}")
+        out[name] = plane
+    return types.SimpleNamespace(nus=nus, t=t, rd=rd, w=w, n_theta=n_theta, shape=shape, source=_source_plane(source, shape), planes=out)
+
+
+def _column_uploads(ctx, p, total_alphas, *planes):
+    """total_alphas, `planes`, then the grid, the temperatures, the ray table and the weights on the device (what is there already is passed
+    through) -> (the arguments every entry begins with, as far as the weights; total_alphas; the planes).  p keeps the uploads alive."""
+    d_alpha = _dev(ctx, total_alphas)
+    d_planes = [_dev(ctx, plane) for plane in planes]
+    p.uploads = [ctx.upload(a) for a in (p.nus, p.t, p.rd, p.w) if a is not None]
+    return (p.t.size, p.nus.size, p.n_theta, *(a.ptr for a in p.uploads)), d_alpha, d_planes
+
+
+def _scatter_inputs(what, alpha_scatter, shape, tol, max_iter):
+    """alpha_scatter, (N_d,) or (N_d, N_nu), host or device, and the iteration's scalars -> (alpha_scatter, its leading dimension)"""
+    sc = alpha_scatter if _on_device(alpha_scatter) else _host(alpha_scatter)
+    if _shape(sc) not in (shape[:1], shape):
+        raise ValueError(f"alpha_scatter must have shape {shape[:1]} or {shape}, got {_shape(sc)}")
+    if not float(tol) >= 0.0:
+        raise ValueError(f"{what}: tol must be >= 0, got {tol}")
+    if int(max_iter) < 1:
+        raise ValueError(f"{what}: max_iter must be >= 1, got {max_iter}")
+    return sc, shape[1] if len(_shape(sc)) == 2 else 0
+
+
+def _results(out, device):
+    """a tuple or a namespace of device outputs as it is, or with every one of them on the host (None stays None)"""
+    if device:
+        return out
+    if isinstance(out, tuple):
+        return tuple(None if x is None else x.numpy() for x in out)
+    for name, x in vars(out).items():
+        setattr(out, name, None if x is None else x.numpy())
+    return out
+
+
 def contribution_arrays(tracing_nus, temperatures, ray_distances, theta_weights, total_alphas, ctx=None, source=None, device=False):
     """Flux contribution function C (N_d, N_nu) of the plane-parallel formal solution (sdx_contribution_dev): what the layer below
     row k adds to the emergent flux, sum_k C[k] = F_nu[-1] up to rounding.  Arguments as raytrace_arrays (ray_distances is the
     (N_d-1, N_theta) table of radiation_field_solvers/base.py:302-305; total_alphas a host or device array; source an optional
     (N_d, N_nu) source-function plane).  device=True: the DeviceArray instead of a host array."""
     ctx = ctx or default_context()
-    nus = _host(tracing_nus).reshape(-1)
-    t = _host(temperatures).reshape(-1)
-    rd = _host(ray_distances).reshape(t.size - 1, -1)
-    w = _host(theta_weights).reshape(-1)
-    d_alpha = _dev(ctx, total_alphas)
-    d_S = None
-    if source is not None:
-        src = _host(source)
-        if src.shape != (t.size, nus.size):
-            raise ValueError(f"source function must return shape {(t.size, nus.size)}, got {src.shape}")
-        d_S = ctx.upload(src)
-    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd), ctx.upload(w)]
-    d_C = ctx.empty((t.size, nus.size))
-    ctx.call("sdx_contribution_dev", t.size, nus.size, w.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, ptr_of(d_alpha), nus.size,
-             ptr_of(d_S), nus.size, d_C.ptr, nus.size)
+    p = _column_inputs(tracing_nus, temperatures, ray_distances, total_alphas, weights=theta_weights, source=source, checked=False)
+    head, d_alpha, (d_S,) = _column_uploads(ctx, p, total_alphas, p.source)
+    n_nu = p.nus.size
+    d_C = ctx.empty(p.shape)
+    ctx.call("sdx_contribution_dev", *head, ptr_of(d_alpha), n_nu, ptr_of(d_S), n_nu, d_C.ptr, n_nu)
     return d_C if device else d_C.numpy()
 
 
@@ -598,29 +680,12 @@ def emergent_intensity(tracing_nus, temperatures, ray_distances, total_alphas, c
     no photospheric correction.  ray_distances is the (N_d-1, N_theta) table of radiation_field_solvers/base.py:302-305, or of
     calculate_spherical_ray with inward_rays=True; total_alphas a host or device array; source an optional (N_d, N_nu)
     source-function plane.  The shapes are checked before any device work.  device=True: the DeviceArray instead of a host array."""
-    nus = _host(tracing_nus).reshape(-1)
-    t = _host(temperatures).reshape(-1)
-    rd = _host(ray_distances)
-    if t.size < 2 or rd.ndim != 2 or rd.shape[0] != t.size - 1 or rd.shape[1] < 1:
-        raise ValueError(f"ray_distances must have shape ({t.size - 1}, N_theta), got {rd.shape}")
-    n_theta = rd.shape[1]
-    if n_theta > 64:
-        raise ValueError(f"at most 64 angles are traced in one launch, got {n_theta}")
-    shape = tuple(int(v) for v in (total_alphas.shape if hasattr(total_alphas, "shape") else np.shape(total_alphas)))
-    if shape != (t.size, nus.size):
-        raise ValueError(f"total_alphas must have shape {(t.size, nus.size)}, got {shape}")
-    src = None
-    if source is not None:
-        src = _host(source)
-        if src.shape != (t.size, nus.size):
-            raise ValueError(f"source function must return shape {(t.size, nus.size)}, got {src.shape}")
+    p = _column_inputs(tracing_nus, temperatures, ray_distances, total_alphas, source=source)
     ctx = ctx or default_context()
-    d_alpha = _dev(ctx, total_alphas)
-    d_S = ctx.upload(src) if src is not None else None
-    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd)]
-    d_I = ctx.empty((n_theta, nus.size))
-    ctx.call("sdx_emergent_intensity_dev", t.size, nus.size, n_theta, d[0].ptr, d[1].ptr, d[2].ptr, ptr_of(d_alpha), nus.size, ptr_of(d_S),
-             nus.size, 1 if inward_rays else 0, d_I.ptr, nus.size)
+    head, d_alpha, (d_S,) = _column_uploads(ctx, p, total_alphas, p.source)
+    n_nu = p.nus.size
+    d_I = ctx.empty((p.n_theta, n_nu))
+    ctx.call("sdx_emergent_intensity_dev", *head, ptr_of(d_alpha), n_nu, ptr_of(d_S), n_nu, 1 if inward_rays else 0, d_I.ptr, n_nu)
     return d_I if device else d_I.numpy()
 
 
@@ -630,34 +695,16 @@ def response(tracing_nus, temperatures, ray_distances, theta_weights, total_alph
     derivative of the emergent flux F_nu[-1] with respect to ln alpha[k] and to the source function S[k] at every depth point
     (sum_k R_source[k] S[k] = F_nu[-1] up to rounding).  Arguments as contribution_arrays; want_opacity / want_source = False: that
     output is not formed (None in its place).  device=True: DeviceArrays instead of host arrays."""
-    nus = _host(tracing_nus).reshape(-1)
-    t = _host(temperatures).reshape(-1)
-    w = _host(theta_weights).reshape(-1)
-    rd = _host(ray_distances)
-    if t.size < 2 or rd.size != (t.size - 1) * w.size:
-        raise ValueError(f"ray_distances must have shape {(t.size - 1, w.size)}, got {rd.shape}")
-    rd = rd.reshape(t.size - 1, w.size)
-    shape = tuple(int(v) for v in (total_alphas.shape if hasattr(total_alphas, "shape") else np.shape(total_alphas)))
-    if shape != (t.size, nus.size):
-        raise ValueError(f"total_alphas must have shape {(t.size, nus.size)}, got {shape}")
-    src = None
-    if source is not None:
-        src = _host(source)
-        if src.shape != (t.size, nus.size):
-            raise ValueError(f"source function must return shape {(t.size, nus.size)}, got {src.shape}")
+    p = _column_inputs(tracing_nus, temperatures, ray_distances, total_alphas, weights=theta_weights, source=source)
     if not (want_opacity or want_source):
         raise ValueError("response: no output requested")
     ctx = ctx or default_context()
-    d_alpha = _dev(ctx, total_alphas)
-    d_S = ctx.upload(src) if src is not None else None
-    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd), ctx.upload(w)]
-    d_Ra = ctx.empty((t.size, nus.size)) if want_opacity else None
-    d_Rs = ctx.empty((t.size, nus.size)) if want_source else None
-    ctx.call("sdx_response_dev", t.size, nus.size, w.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, ptr_of(d_alpha), nus.size,
-             ptr_of(d_S), nus.size, ptr_of(d_Ra), nus.size, ptr_of(d_Rs), nus.size)
-    if device:
-        return d_Ra, d_Rs
-    return (d_Ra.numpy() if want_opacity else None), (d_Rs.numpy() if want_source else None)
+    head, d_alpha, (d_S,) = _column_uploads(ctx, p, total_alphas, p.source)
+    n_nu = p.nus.size
+    d_Ra = ctx.empty(p.shape) if want_opacity else None
+    d_Rs = ctx.empty(p.shape) if want_source else None
+    ctx.call("sdx_response_dev", *head, ptr_of(d_alpha), n_nu, ptr_of(d_S), n_nu, ptr_of(d_Ra), n_nu, ptr_of(d_Rs), n_nu)
+    return _results((d_Ra, d_Rs), device)
 
 
 def response_angles(tracing_nus, temperatures, ray_distances, cotangent, total_alphas, ctx=None, source=None, device=False,
@@ -666,38 +713,16 @@ def response_angles(tracing_nus, temperatures, ray_distances, cotangent, total_a
     derivatives of sum_theta cotangent[theta, nu] I_theta(nu), I the emergent intensities (ops.emergent_intensity), with respect to
     ln alpha[k] and to S[k].  cotangent (N_theta, N_nu), host or device; the other arguments as response.  A cotangent that holds the
     flux weights in every column gives response's bits."""
-    nus = _host(tracing_nus).reshape(-1)
-    t = _host(temperatures).reshape(-1)
-    rd = _host(ray_distances)
-    cshape = tuple(int(v) for v in (cotangent.shape if hasattr(cotangent, "shape") else np.shape(cotangent)))
-    if len(cshape) != 2 or cshape[1] != nus.size or cshape[0] < 1:
-        raise ValueError(f"cotangent must have shape (n_theta, {nus.size}), got {cshape}")
-    n_theta = cshape[0]
-    if t.size < 2 or rd.size != (t.size - 1) * n_theta:
-        raise ValueError(f"ray_distances must have shape {(t.size - 1, n_theta)}, got {rd.shape}")
-    rd = rd.reshape(t.size - 1, n_theta)
-    shape = tuple(int(v) for v in (total_alphas.shape if hasattr(total_alphas, "shape") else np.shape(total_alphas)))
-    if shape != (t.size, nus.size):
-        raise ValueError(f"total_alphas must have shape {(t.size, nus.size)}, got {shape}")
-    src = None
-    if source is not None:
-        src = _host(source)
-        if src.shape != (t.size, nus.size):
-            raise ValueError(f"source function must return shape {(t.size, nus.size)}, got {src.shape}")
+    p = _column_inputs(tracing_nus, temperatures, ray_distances, total_alphas, cotangent=cotangent, source=source)
     if not (want_opacity or want_source):
         raise ValueError("response_angles: no output requested")
     ctx = ctx or default_context()
-    d_alpha = _dev(ctx, total_alphas)
-    d_cot = _dev(ctx, cotangent)
-    d_S = ctx.upload(src) if src is not None else None
-    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd)]
-    d_Ra = ctx.empty((t.size, nus.size)) if want_opacity else None
-    d_Rs = ctx.empty((t.size, nus.size)) if want_source else None
-    ctx.call("sdx_response_angles_dev", t.size, nus.size, n_theta, d[0].ptr, d[1].ptr, d[2].ptr, ptr_of(d_cot), nus.size, ptr_of(d_alpha),
-             nus.size, ptr_of(d_S), nus.size, ptr_of(d_Ra), nus.size, ptr_of(d_Rs), nus.size)
-    if device:
-        return d_Ra, d_Rs
-    return (d_Ra.numpy() if want_opacity else None), (d_Rs.numpy() if want_source else None)
+    head, d_alpha, (d_cot, d_S) = _column_uploads(ctx, p, total_alphas, cotangent, p.source)
+    n_nu = p.nus.size
+    d_Ra = ctx.empty(p.shape) if want_opacity else None
+    d_Rs = ctx.empty(p.shape) if want_source else None
+    ctx.call("sdx_response_angles_dev", *head, ptr_of(d_cot), n_nu, ptr_of(d_alpha), n_nu, ptr_of(d_S), n_nu, ptr_of(d_Ra), n_nu, ptr_of(d_Rs), n_nu)
+    return _results((d_Ra, d_Rs), device)
 
 
 def mean_weights(thetas, theta_weights):
@@ -713,50 +738,22 @@ def mean_weights(thetas, theta_weights):
     return x / (2.0 * math.fsum(x))
 
 
-def _lambda_inputs(what, tracing_nus, temperatures, ray_distances, weights, total_alphas, planes):
-    """The host-side checks mean_intensity and scatter_source share, before any device is asked for -> (nus, t, rd, m, {name: plane})."""
-    nus = _host(tracing_nus).reshape(-1)
-    t = _host(temperatures).reshape(-1)
-    m = _host(weights).reshape(-1)
-    if m.size > 64:
-        raise ValueError(f"{what}: more than 64 angles are not supported, got {m.size}")
-    rd = _host(ray_distances)
-    if t.size < 2 or m.size == 0 or rd.size != (t.size - 1) * m.size:
-        raise ValueError(f"ray_distances must have shape {(t.size - 1, m.size)}, got {rd.shape}")
-    rd = rd.reshape(t.size - 1, m.size)
-    shape = tuple(int(v) for v in (total_alphas.shape if hasattr(total_alphas, "shape") else np.shape(total_alphas)))
-    if shape != (t.size, nus.size):
-        raise ValueError(f"total_alphas must have shape {(t.size, nus.size)}, got {shape}")
-    out = {}
-    for name, plane in planes.items():
-        if plane is not None and not (isinstance(plane, DeviceArray) or hasattr(plane, "data_ptr")):
-            plane = _host(plane)
-        if plane is not None and tuple(int(v) for v in plane.shape) != (t.size, nus.size):
-            raise ValueError(f"{name} must have shape {(t.size, nus.size)}, got {tuple(plane.shape)}")
-        out[name] = plane
-    return nus, t, rd, m, out
-
-
 def mean_intensity(tracing_nus, temperatures, ray_distances, mean_weights, total_alphas, ctx=None, source=None, device=False,
                    want_J=True, want_L=True):
     """Mean intensity of the plane-parallel formal solution (sdx_mean_intensity_dev) -> (J, L), each (N_d, N_nu): J over both
     hemispheres for the source plane (default: Planck) with a thermalised lower boundary, and L, the diagonal of that operator.
     mean_weights: ops.mean_weights(thetas, theta_weights); the other arguments as for response().  want_J / want_L = False: that
     output is not formed (None in its place).  device=True: DeviceArrays instead of host arrays."""
-    nus, t, rd, m, planes = _lambda_inputs("mean_intensity", tracing_nus, temperatures, ray_distances, mean_weights, total_alphas, dict(source=source))
+    p = _column_inputs(tracing_nus, temperatures, ray_distances, total_alphas, weights=mean_weights, what="mean_intensity", planes=dict(source=source))
     if not (want_J or want_L):
         raise ValueError("mean_intensity: no output requested")
     ctx = ctx or default_context()
-    d_alpha = _dev(ctx, total_alphas)
-    d_S = _dev(ctx, planes["source"])
-    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd), ctx.upload(m)]
-    d_J = ctx.empty((t.size, nus.size)) if want_J else None
-    d_L = ctx.empty((t.size, nus.size)) if want_L else None
-    ctx.call("sdx_mean_intensity_dev", t.size, nus.size, m.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, ptr_of(d_alpha), nus.size,
-             ptr_of(d_S), nus.size, ptr_of(d_J), nus.size, ptr_of(d_L), nus.size)
-    if device:
-        return d_J, d_L
-    return (d_J.numpy() if want_J else None), (d_L.numpy() if want_L else None)
+    head, d_alpha, (d_S,) = _column_uploads(ctx, p, total_alphas, p.planes["source"])
+    n_nu = p.nus.size
+    d_J = ctx.empty(p.shape) if want_J else None
+    d_L = ctx.empty(p.shape) if want_L else None
+    ctx.call("sdx_mean_intensity_dev", *head, ptr_of(d_alpha), n_nu, ptr_of(d_S), n_nu, ptr_of(d_J), n_nu, ptr_of(d_L), n_nu)
+    return _results((d_J, d_L), device)
 
 
 def scatter_source(tracing_nus, temperatures, ray_distances, mean_weights, total_alphas, alpha_scatter, ctx=None, thermal=None,
@@ -769,31 +766,16 @@ def scatter_source(tracing_nus, temperatures, ray_distances, mean_weights, total
     want_J=False), per column the iteration count and status (int32) and the last change.  device=True: DeviceArrays."""
     import types
 
-    nus, t, rd, m, planes = _lambda_inputs("scatter_source", tracing_nus, temperatures, ray_distances, mean_weights, total_alphas, dict(thermal=thermal))
-    on_device = isinstance(alpha_scatter, DeviceArray) or hasattr(alpha_scatter, "data_ptr")
-    sc = alpha_scatter if on_device else _host(alpha_scatter)
-    sc_shape = tuple(int(v) for v in sc.shape)
-    if sc_shape not in ((t.size,), (t.size, nus.size)):
-        raise ValueError(f"alpha_scatter must have shape {(t.size,)} or {(t.size, nus.size)}, got {sc_shape}")
-    if not float(tol) >= 0.0:
-        raise ValueError(f"scatter_source: tol must be >= 0, got {tol}")
-    if int(max_iter) < 1:
-        raise ValueError(f"scatter_source: max_iter must be >= 1, got {max_iter}")
+    p = _column_inputs(tracing_nus, temperatures, ray_distances, total_alphas, weights=mean_weights, what="scatter_source", planes=dict(thermal=thermal))
+    sc, sc_ld = _scatter_inputs("scatter_source", alpha_scatter, p.shape, tol, max_iter)
     ctx = ctx or default_context()
-    d_alpha = _dev(ctx, total_alphas)
-    d_sc = _dev(ctx, sc)
-    d_B = _dev(ctx, planes["thermal"])
-    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd), ctx.upload(m)]
-    out = types.SimpleNamespace(S=ctx.empty((t.size, nus.size)), J=ctx.empty((t.size, nus.size)) if want_J else None,
-                                iterations=ctx.empty((nus.size,), np.int32), status=ctx.empty((nus.size,), np.int32), change=ctx.empty((nus.size,)))
-    ctx.call("sdx_scatter_source_dev", t.size, nus.size, m.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, ptr_of(d_alpha), nus.size,
-             ptr_of(d_sc), nus.size if len(sc_shape) == 2 else 0, ptr_of(d_B), nus.size, float(tol), int(max_iter), out.S.ptr, nus.size,
-             ptr_of(out.J), nus.size, out.iterations.ptr, out.status.ptr, out.change.ptr)
-    if not device:
-        for name in ("S", "J", "iterations", "status", "change"):
-            value = getattr(out, name)
-            setattr(out, name, None if value is None else value.numpy())
-    return out
+    head, d_alpha, (d_sc, d_B) = _column_uploads(ctx, p, total_alphas, sc, p.planes["thermal"])
+    n_nu = p.nus.size
+    out = types.SimpleNamespace(S=ctx.empty(p.shape), J=ctx.empty(p.shape) if want_J else None, iterations=ctx.empty((n_nu,), np.int32),
+                                status=ctx.empty((n_nu,), np.int32), change=ctx.empty((n_nu,)))
+    ctx.call("sdx_scatter_source_dev", *head, ptr_of(d_alpha), n_nu, ptr_of(d_sc), sc_ld, ptr_of(d_B), n_nu, float(tol), int(max_iter), out.S.ptr, n_nu,
+             ptr_of(out.J), n_nu, out.iterations.ptr, out.status.ptr, out.change.ptr)
+    return _results(out, device)
 
 
 def mean_intensity_adjoint(tracing_nus, temperatures, ray_distances, mean_weights, total_alphas, z, ctx=None, source=None, device=False,
@@ -801,24 +783,19 @@ def mean_intensity_adjoint(tracing_nus, temperatures, ray_distances, mean_weight
     """The transpose of mean_intensity's operator (sdx_mean_intensity_adjoint_dev) -> (Lt, G), each (N_d, N_nu): Lt = Lambda^T z for
     the plane z, and G[k] = d(z^T J[S]) / d ln alpha[k] at the fixed source plane S (default: Planck).  Arguments as mean_intensity;
     want_Lt / want_G = False: that output is not formed (None in its place).  device=True: DeviceArrays instead of host arrays."""
-    nus, t, rd, m, planes = _lambda_inputs("mean_intensity_adjoint", tracing_nus, temperatures, ray_distances, mean_weights, total_alphas,
-                                           dict(z=z, source=source))
-    if planes["z"] is None:
+    p = _column_inputs(tracing_nus, temperatures, ray_distances, total_alphas, weights=mean_weights, what="mean_intensity_adjoint",
+                       planes=dict(z=z, source=source))
+    if p.planes["z"] is None:
         raise ValueError("mean_intensity_adjoint: z is required")
     if not (want_Lt or want_G):
         raise ValueError("mean_intensity_adjoint: no output requested")
     ctx = ctx or default_context()
-    d_alpha = _dev(ctx, total_alphas)
-    d_z = _dev(ctx, planes["z"])
-    d_S = _dev(ctx, planes["source"])
-    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd), ctx.upload(m)]
-    d_Lt = ctx.empty((t.size, nus.size)) if want_Lt else None
-    d_G = ctx.empty((t.size, nus.size)) if want_G else None
-    ctx.call("sdx_mean_intensity_adjoint_dev", t.size, nus.size, m.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, ptr_of(d_alpha), nus.size,
-             ptr_of(d_z), nus.size, ptr_of(d_S), nus.size, ptr_of(d_Lt), nus.size, ptr_of(d_G), nus.size)
-    if device:
-        return d_Lt, d_G
-    return (d_Lt.numpy() if want_Lt else None), (d_G.numpy() if want_G else None)
+    head, d_alpha, (d_z, d_S) = _column_uploads(ctx, p, total_alphas, p.planes["z"], p.planes["source"])
+    n_nu = p.nus.size
+    d_Lt = ctx.empty(p.shape) if want_Lt else None
+    d_G = ctx.empty(p.shape) if want_G else None
+    ctx.call("sdx_mean_intensity_adjoint_dev", *head, ptr_of(d_alpha), n_nu, ptr_of(d_z), n_nu, ptr_of(d_S), n_nu, ptr_of(d_Lt), n_nu, ptr_of(d_G), n_nu)
+    return _results((d_Lt, d_G), device)
 
 
 def scatter_response(tracing_nus, temperatures, ray_distances, mean_weights, total_alphas, alpha_scatter, S, cotangent, ctx=None, direct=None,
@@ -831,37 +808,21 @@ def scatter_response(tracing_nus, temperatures, ray_distances, mean_weights, tot
     alpha_scatter — and per column the iteration count and status (int32) and the last change.  device=True: DeviceArrays."""
     import types
 
-    nus, t, rd, m, planes = _lambda_inputs("scatter_response", tracing_nus, temperatures, ray_distances, mean_weights, total_alphas,
-                                           dict(S=S, cotangent=cotangent, direct=direct, thermal=thermal))
-    if planes["S"] is None or planes["cotangent"] is None:
+    p = _column_inputs(tracing_nus, temperatures, ray_distances, total_alphas, weights=mean_weights, what="scatter_response",
+                       planes=dict(S=S, cotangent=cotangent, direct=direct, thermal=thermal))
+    if p.planes["S"] is None or p.planes["cotangent"] is None:
         raise ValueError("scatter_response: S and cotangent are required")
-    on_device = isinstance(alpha_scatter, DeviceArray) or hasattr(alpha_scatter, "data_ptr")
-    sc = alpha_scatter if on_device else _host(alpha_scatter)
-    sc_shape = tuple(int(v) for v in sc.shape)
-    if sc_shape not in ((t.size,), (t.size, nus.size)):
-        raise ValueError(f"alpha_scatter must have shape {(t.size,)} or {(t.size, nus.size)}, got {sc_shape}")
-    if not float(tol) >= 0.0:
-        raise ValueError(f"scatter_response: tol must be >= 0, got {tol}")
-    if int(max_iter) < 1:
-        raise ValueError(f"scatter_response: max_iter must be >= 1, got {max_iter}")
+    sc, sc_ld = _scatter_inputs("scatter_response", alpha_scatter, p.shape, tol, max_iter)
     ctx = ctx or default_context()
-    d_alpha = _dev(ctx, total_alphas)
-    d_sc = _dev(ctx, sc)
-    d_in = {name: _dev(ctx, planes[name]) for name in ("thermal", "S", "cotangent", "direct")}
-    d = [ctx.upload(nus), ctx.upload(t), ctx.upload(rd), ctx.upload(m)]
-    plane = lambda: ctx.empty((t.size, nus.size))  # noqa: E731
-    out = types.SimpleNamespace(y=plane() if want_y else None, R_thermal=plane(), R_absorption=plane(), R_scatter=plane(),
-                                iterations=ctx.empty((nus.size,), np.int32), status=ctx.empty((nus.size,), np.int32), change=ctx.empty((nus.size,)))
-    ctx.call("sdx_scatter_response_dev", t.size, nus.size, m.size, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, ptr_of(d_alpha), nus.size,
-             ptr_of(d_sc), nus.size if len(sc_shape) == 2 else 0, ptr_of(d_in["thermal"]), nus.size, ptr_of(d_in["S"]), nus.size,
-             ptr_of(d_in["cotangent"]), nus.size, ptr_of(d_in["direct"]), nus.size, float(tol), int(max_iter), ptr_of(out.y), nus.size,
-             out.R_thermal.ptr, nus.size, out.R_absorption.ptr, nus.size, out.R_scatter.ptr, nus.size, out.iterations.ptr, out.status.ptr,
-             out.change.ptr)
-    if not device:
-        for name in ("y", "R_thermal", "R_absorption", "R_scatter", "iterations", "status", "change"):
-            value = getattr(out, name)
-            setattr(out, name, None if value is None else value.numpy())
-    return out
+    head, d_alpha, d_in = _column_uploads(ctx, p, total_alphas, sc, *(p.planes[name] for name in ("thermal", "S", "cotangent", "direct")))
+    n_nu = p.nus.size
+    out = types.SimpleNamespace(y=ctx.empty(p.shape) if want_y else None, R_thermal=ctx.empty(p.shape), R_absorption=ctx.empty(p.shape),
+                                R_scatter=ctx.empty(p.shape), iterations=ctx.empty((n_nu,), np.int32), status=ctx.empty((n_nu,), np.int32),
+                                change=ctx.empty((n_nu,)))
+    ctx.call("sdx_scatter_response_dev", *head, ptr_of(d_alpha), n_nu, ptr_of(d_in[0]), sc_ld, *(v for d in d_in[1:] for v in (ptr_of(d), n_nu)),
+             float(tol), int(max_iter), ptr_of(out.y), n_nu, out.R_thermal.ptr, n_nu, out.R_absorption.ptr, n_nu, out.R_scatter.ptr, n_nu,
+             out.iterations.ptr, out.status.ptr, out.change.ptr)
+    return _results(out, device)
 
 
 def formation_mean(contribution, x, ctx=None, device=False):
