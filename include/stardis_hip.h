@@ -529,6 +529,56 @@ int sdx_scatter_source_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta,
                            const double* thermal, double tol, int max_iter, double* S, double* J, int* iterations,
                            int* status, double* change);
 
+/* ---- continuum scattering: Ng acceleration of the source iteration ----------------------------------
+ * sdx_scatter_source_ng_dev is sdx_scatter_source_dev's iteration with the unweighted second-order Ng extrapolation (Olson, Auer &
+ * Buchler 1986) and a safeguard, per column.  Arguments, outputs and refusals are the sibling's; `accelerations` [n_nu] (may be
+ * NULL) receives the extrapolations applied.  The bits differ from the plain solve's: it is a different sequence to the same fixed
+ * point, stopped by the same rule.
+ *   update          exactly the plain one: same residual, same local operator 1 / (1 - albedo Lc), same order of operations.  The
+ *                   stopping rule is evaluated on updates only, never on an extrapolation's jump, and is otherwise unchanged: statuses
+ *                   0 / 1 / 2, the refused non-finite update, the frozen column, `iterations` (updates evaluated) and `change` keep
+ *                   their meaning, and status 0 always follows a plain update.
+ *   history         the last four iterates SINCE THE LAST EXTRAPOLATION, x0 the newest .. x3; S^0 and an extrapolated iterate count.
+ *   extrapolation   after update n, where the column is live and still accelerated, ng_start <= n < max_iter (what is returned has
+ *                   always been through an update), at least ng_period updates have passed since the last extrapolation and the
+ *                   history holds four iterates:
+ *                       q1 = (x0 - 2 x1) + x2,   q2 = ((x0 - x1) - x2) + x3,   q3 = x0 - x1
+ *                       A1 = sum_d q1 q1, B1 = sum_d q1 q2, C1 = sum_d q1 q3, B2 = sum_d q2 q2, C2 = sum_d q2 q3
+ *                       det = A1 B2 - B1 B1,   a = (C1 B2 - C2 B1) / det,   b = (C2 A1 - C1 B1) / det
+ *                       S <- (((1 - a) - b) x0 + a x1) + b x2
+ *                   every operation one rounded fp64 operation.  The sums are unweighted: lane g of the column's n_theta lanes adds
+ *                   its depths g, g + n_theta, ... in ascending order from 0, then the n_theta partials are added in ascending lane
+ *                   order from 0 — the order is fixed by (n_depth, n_theta) alone.
+ *   skipped         if any component of the extrapolated column is not finite (det == 0 included) the extrapolation is skipped: the
+ *                   iterate stays x0, nothing is counted, the history continues.
+ *   safeguard       an extrapolation remembers `reference`, the change of the update before it, and keeps a copy of the iterate it
+ *                   replaced.  ng_period updates later — at the update before the next extrapolation would be due — the change is
+ *                   compared with the reference.  Smaller: a gain; the next extrapolation takes a new reference and a new copy.
+ *                   Not smaller: a strike; the next extrapolation goes ahead but keeps reference and copy.  Two strikes in a row:
+ *                   the column takes the copy back (the iterate before the first of the two extrapolations), continues plain for
+ *                   good, and `accelerations` stops counting.  It costs no operator application and reads the column's own
+ *                   numbers alone, so a column's bits depend on nothing that shares its wave, launch or shard.
+ * Defaults of the Python layers: ng_start = 4, ng_period = 4.  One strike alone is too quick for this iteration (after a good
+ * extrapolation the max-norm change often rises by a few percent for one period while the error has halved), none at all is the
+ * bare method.  DESIGN.md, "Scattering in the source function", has the rule's evidence and the variants that failed.
+ * The adjoint solve (sdx_scatter_response_dev) has NO accelerated sibling: no safeguard tried keeps it within the plain iteration's
+ * cost on every column ("The scattering adjoint").
+ * Refused with SDX_ERR_ARG before anything is enqueued (also for n_nu = 0): what sdx_scatter_source_dev refuses, ng_start < 4,
+ * ng_period < 1, and a model whose columns — (10 n_depth + 5 n_theta) doubles at one frequency per wave: the iteration's and four
+ * columns of history — do not fit 64 KB of LDS (809 depth points at 20 angles; sdx_scatter_source_dev, the plain iteration, serves
+ * 1352). */
+int sdx_scatter_source_ng_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                              const double* temperature, const double* ray_dist, const double* mean_weights,
+                              const double* total_alphas, int64_t alpha_ld, const double* alpha_scatter, int64_t scatter_ld,
+                              const double* thermal, int64_t thermal_ld, double tol, int max_iter, double* S, int64_t S_ld,
+                              double* J, int64_t J_ld, int* iterations, int* status, double* change, int ng_start,
+                              int ng_period, int* accelerations);
+int sdx_scatter_source_ng_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus,
+                              const double* temperature, const double* ray_dist, const double* mean_weights,
+                              const double* total_alphas, const double* alpha_scatter, int scatter_per_frequency,
+                              const double* thermal, double tol, int max_iter, double* S, double* J, int* iterations,
+                              int* status, double* change, int ng_start, int ng_period, int* accelerations);
+
 /* ---- continuum scattering: the adjoint solve and the flux responses --------------------------------
  * The derivative of a functional of the scattering solution is the adjoint of a fixed point: one transposed solve per column with
  * the operator of sdx_mean_intensity_dev, not a derivative through the iterations.  Notation as there: Lambda is the linear map

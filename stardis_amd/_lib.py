@@ -188,6 +188,10 @@ PROTOTYPES = {
                                       _vp, _vp, _vp]),
     "sdx_mean_intensity_f64": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sdx_scatter_source_f64": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, C.c_double, _int, _vp, _vp, _vp, _vp, _vp]),
+    "sdx_scatter_source_ng_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, C.c_double, _int, _vp, _i64, _vp, _i64,
+                                         _vp, _vp, _vp, _int, _int, _vp]),
+    "sdx_scatter_source_ng_f64": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, C.c_double, _int, _vp, _vp, _vp, _vp, _vp,
+                                         _int, _int, _vp]),
     "sdx_mean_intensity_adjoint_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp] + [_vp, _i64] * 5),
     "sdx_scatter_response_dev": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp] + [_vp, _i64] * 6 + [C.c_double, _int] + [_vp, _i64] * 4 + [_vp, _vp, _vp]),
     "sdx_mean_intensity_adjoint_f64": (_int, [_vp, _int, _i64, _int] + [_vp] * 9),

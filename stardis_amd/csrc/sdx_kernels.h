@@ -4755,15 +4755,28 @@ struct LambdaIteration {
     int* status;
     double* change;
 };
+// kNg: Ng acceleration of that iteration (include/stardis_hip.h, sdx_scatter_source_ng_dev, states the rule).  The updates are the plain
+// ones; an update also writes the iterate it replaces into a ring of three columns (RtLambdaNg), and after it a column that is due
+// replaces its iterate by the unweighted second-order extrapolation of its last four.  The five sums are per column: each lane sums
+// its depths g, g + G, ... in ascending order, the G partials pass through the terms region and are added in ascending lane order, every
+// operation rounded once — the order depends on (n_depth, G) alone.  Whether to extrapolate, whether the result is finite and what
+// the safeguard decides are per-column decisions under the wave-uniform trip: ballots, no LDS flags, and a stopped column is never
+// written.  The safeguard's state (reference change, strikes) lives in registers, the same in every lane of a column.
+struct LambdaIterationNg : LambdaIteration {
+    int ng_start, ng_period;
+    int* accelerations;  // per column, may be NULL
+};
+constexpr int kNgStrikes = 2;  // extrapolations in a row without a gain before a column continues plain
 constexpr double kDoubleMax = 0x1.fffffffffffffp+1023;
-template <bool kIterate>
-__global__ __launch_bounds__(kRtBlock) void k_lambda(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
-                                                   const double* __restrict__ nus, const double* __restrict__ temps,
-                                                   const double* __restrict__ ray_dist, const double* __restrict__ mean_wts,
-                                                   const double* __restrict__ alphas, int64_t ald, const double* __restrict__ source,
-                                                   int64_t sld, double* __restrict__ J, int64_t jld, double* __restrict__ Ldiag, int64_t lld,
-                                                   int gpw, int waves, LambdaIteration it)
+template <bool kIterate, bool kNg>
+__device__ __forceinline__ void lambda_body(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G, const double* __restrict__ nus,
+                                            const double* __restrict__ temps, const double* __restrict__ ray_dist,
+                                            const double* __restrict__ mean_wts, const double* __restrict__ alphas, int64_t ald,
+                                            const double* __restrict__ source, int64_t sld, double* __restrict__ J, int64_t jld,
+                                            double* __restrict__ Ldiag, int64_t lld, int gpw, int waves,
+                                            const std::conditional_t<kNg, LambdaIterationNg, LambdaIteration>& it)
 {
+    static_assert(kIterate || !kNg, "only the iteration is accelerated");
     constexpr int kBatch = kRtBatch;
     extern __shared__ double smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -4775,7 +4788,7 @@ __global__ __launch_bounds__(kRtBlock) void k_lambda(int n_depth, int64_t n_nu, 
     const int64_t ic = i < n_nu ? i : n_nu - 1;
     const int n_gap = n_depth - 1;
     const int col = n_depth;
-    const RtLambda lay(G, n_depth, gpw);
+    const std::conditional_t<kNg, RtLambdaNg, RtLambda> lay(G, n_depth, gpw);
     double* wbase = smem + (size_t)wave * lay.wave_doubles();
     double2* sP = (double2*)(wbase + lay.pairs());  // (source function — the iterate —, sqrt(alpha)) [gpw][col]
     double* sT = wbase + lay.thermal();             // (1 - albedo) B [gpw][col]
@@ -4889,6 +4902,12 @@ __global__ __launch_bounds__(kRtBlock) void k_lambda(int n_depth, int64_t n_nu, 
         bool live = valid;
         int iters = 0, status = 1;
         double change = 0.0;
+        // kNg, per column: iterates of history (the current one included), updates since the last extrapolation, whether the column
+        // is still accelerated and awaits the safeguard's judgement, its strikes, the reference change, the extrapolations applied
+        [[maybe_unused]] int held = 1, since = 0, strikes = 0, accs = 0;
+        [[maybe_unused]] bool ng_on = true, probation = false;
+        [[maybe_unused]] double reference = 0.0;
+        if constexpr (kNg) since = it.ng_period;
         for (int n = 1;; ++n) {
             const bool more = n <= it.max_iter && __builtin_amdgcn_ballot_w64(live) != 0;  // wave-uniform
             if (!more && !J) break;
@@ -4926,8 +4945,87 @@ __global__ __launch_bounds__(kRtBlock) void k_lambda(int n_depth, int64_t n_nu, 
                 if (!(cd <= kDoubleMax)) {
                     status = 2, live = false;  // S stays at the last finite iterate
                 } else {
-                    for (int d = g; d < n_depth; d += G) sP[cbase + d].x = add_rn(sP[cbase + d].x, sJ[cbase + d]);
+                    if constexpr (kNg) {
+                        double* ring = wbase + lay.history(n % 3);  // the iterate this update replaces: x1 of the next extrapolation
+                        for (int d = g; d < n_depth; d += G) {
+                            const double s = sP[cbase + d].x;
+                            ring[cbase + d] = s;
+                            sP[cbase + d].x = add_rn(s, sJ[cbase + d]);
+                        }
+                        ++held, ++since;
+                    } else {
+                        for (int d = g; d < n_depth; d += G) sP[cbase + d].x = add_rn(sP[cbase + d].x, sJ[cbase + d]);
+                    }
                     if (cd <= mul_rn(it.tol, cs)) status = 0, live = false;
+                }
+            }
+            if constexpr (kNg) {
+                double* sF = wbase + lay.history(3);  // the iterate the last judged-from extrapolation replaced
+                // the safeguard: a whole period after an extrapolation, the change against the one before it
+                if (live && ng_on && probation && since >= it.ng_period) {
+                    if (cd < reference) {
+                        strikes = 0;
+                    } else if (++strikes >= kNgStrikes) {
+                        for (int d = g; d < n_depth; d += G) sP[cbase + d].x = sF[cbase + d];
+                        ng_on = false;
+                    }
+                }
+                if (since >= it.ng_period) probation = false;
+                const bool want = live && ng_on && n >= it.ng_start && n < it.max_iter && since >= it.ng_period && held >= 4;
+                if (__builtin_amdgcn_ballot_w64(want) != 0) {  // wave-uniform
+                    const double* h1 = wbase + lay.history(n % 3);
+                    const double* h2 = wbase + lay.history((n + 2) % 3);
+                    const double* h3 = wbase + lay.history((n + 1) % 3);
+                    if (want) {
+                        double a1 = 0.0, b1 = 0.0, c1 = 0.0, b2 = 0.0, c2 = 0.0;
+                        for (int d = g; d < n_depth; d += G) {
+                            const double x0 = sP[cbase + d].x, x1 = h1[cbase + d], x2 = h2[cbase + d], x3 = h3[cbase + d];
+                            const double q1 = add_rn(sub_rn(x0, mul_rn(2.0, x1)), x2);
+                            const double q2 = add_rn(sub_rn(sub_rn(x0, x1), x2), x3);
+                            const double q3 = sub_rn(x0, x1);
+                            a1 = add_rn(a1, mul_rn(q1, q1));
+                            b1 = add_rn(b1, mul_rn(q1, q2));
+                            c1 = add_rn(c1, mul_rn(q1, q3));
+                            b2 = add_rn(b2, mul_rn(q2, q2));
+                            c2 = add_rn(c2, mul_rn(q2, q3));
+                        }
+                        const int xs = grp * G + g, stride = gpw * G;
+                        sX[xs] = a1, sX[stride + xs] = b1, sX[2 * stride + xs] = c1, sX[3 * stride + xs] = b2, sX[4 * stride + xs] = c2;
+                    }
+                    wave_sync();
+                    bool bad = false;
+                    if (want) {
+                        const int xb = grp * G, stride = gpw * G;
+                        double A1 = 0.0, B1 = 0.0, C1 = 0.0, B2 = 0.0, C2 = 0.0;
+                        for (int t = 0; t < G; ++t) {
+                            A1 = add_rn(A1, sX[xb + t]);
+                            B1 = add_rn(B1, sX[stride + xb + t]);
+                            C1 = add_rn(C1, sX[2 * stride + xb + t]);
+                            B2 = add_rn(B2, sX[3 * stride + xb + t]);
+                            C2 = add_rn(C2, sX[4 * stride + xb + t]);
+                        }
+                        const double det = sub_rn(mul_rn(A1, B2), mul_rn(B1, B1));
+                        const double a = sub_rn(mul_rn(C1, B2), mul_rn(C2, B1)) / det;
+                        const double b = sub_rn(mul_rn(C2, A1), mul_rn(C1, B1)) / det;
+                        const double k0 = sub_rn(sub_rn(1.0, a), b);
+                        for (int d = g; d < n_depth; d += G) {
+                            const double e = add_rn(add_rn(mul_rn(k0, sP[cbase + d].x), mul_rn(a, h1[cbase + d])), mul_rn(b, h2[cbase + d]));
+                            sJ[cbase + d] = e;  // (the change of the iterate has been consumed)
+                            bad = bad || !(fabs(e) <= kDoubleMax);
+                        }
+                    }
+                    // a column's lanes are grp G .. grp G + G - 1: one non-finite component anywhere skips the column's extrapolation
+                    const uint64_t bad_lanes = __builtin_amdgcn_ballot_w64(bad);
+                    const uint64_t mine = (G == 64 ? ~0ull : ((1ull << G) - 1)) << (active ? grp * G : 0);
+                    if (want && !(bad_lanes & mine)) {
+                        const bool fresh = strikes == 0;
+                        for (int d = g; d < n_depth; d += G) {
+                            if (fresh) sF[cbase + d] = sP[cbase + d].x;
+                            sP[cbase + d].x = sJ[cbase + d];
+                        }
+                        if (fresh) reference = cd;
+                        held = 1, since = 0, probation = true, ++accs;
+                    }
                 }
             }
             wave_sync();
@@ -4938,10 +5036,32 @@ __global__ __launch_bounds__(kRtBlock) void k_lambda(int n_depth, int64_t n_nu, 
                 if (it.iterations) it.iterations[i] = iters;
                 if (it.status) it.status[i] = status;
                 if (it.change) it.change[i] = change;
+                if constexpr (kNg)
+                    if (it.accelerations) it.accelerations[i] = accs;
             }
         }
         if (J) store_column(sJ, J, jld);
     }
+}
+
+template <bool kIterate>
+__global__ __launch_bounds__(kRtBlock) void k_lambda(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
+                                                   const double* __restrict__ nus, const double* __restrict__ temps,
+                                                   const double* __restrict__ ray_dist, const double* __restrict__ mean_wts,
+                                                   const double* __restrict__ alphas, int64_t ald, const double* __restrict__ source,
+                                                   int64_t sld, double* __restrict__ J, int64_t jld, double* __restrict__ Ldiag, int64_t lld,
+                                                   int gpw, int waves, LambdaIteration it)
+{
+    lambda_body<kIterate, false>(n_depth, n_nu, n_theta, theta_stride, G, nus, temps, ray_dist, mean_wts, alphas, ald, source, sld, J, jld, Ldiag, lld, gpw, waves, it);
+}
+// k_lambda<true> with Ng acceleration (a kernel name of its own: the plain family keeps its two instantiations and their figures)
+__global__ __launch_bounds__(kRtBlock) void k_lambda_ng(int n_depth, int64_t n_nu, int n_theta, int theta_stride, int G,
+                                                      const double* __restrict__ nus, const double* __restrict__ temps,
+                                                      const double* __restrict__ ray_dist, const double* __restrict__ mean_wts,
+                                                      const double* __restrict__ alphas, int64_t ald, const double* __restrict__ source,
+                                                      int64_t sld, double* __restrict__ J, int64_t jld, int gpw, int waves, LambdaIterationNg it)
+{
+    lambda_body<true, true>(n_depth, n_nu, n_theta, theta_stride, G, nus, temps, ray_dist, mean_wts, alphas, ald, source, sld, J, jld, nullptr, 0, gpw, waves, it);
 }
 
 // ------------------------------------------------------------------------------------------------

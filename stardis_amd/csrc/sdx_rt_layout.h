@@ -142,6 +142,28 @@ struct RtLambda {
     __host__ __device__ constexpr size_t bytes() const { return (size_t)wave_doubles() * sizeof(double); }
 };
 
+// k_lambda_ng (k_lambda<true> with Ng acceleration).  RtLambda's regions in RtLambda's order; then the
+// history [4][gpw][col]: slots 0..2 are a ring over the three iterates before the current one (an update writes the iterate it
+// replaces into the slot the trip count selects: one extra column write), slot 3 is the copy of the iterate an extrapolation replaced,
+// which the safeguard may take back; then the terms [kRtBatch + 1][gpw][G]: RtLambda's batch of rows and maxima, and the G partials of each
+// of the extrapolation's five sums per column ([5][gpw][G]: the per-column scalars pass through LDS in lane order).  bytes() is ONE
+// wave's share, as RtLambda's.
+constexpr int kNgHistory = 4;  // ring of three and the safeguard's copy
+constexpr int kNgSums = 5;     // A1, B1, C1, B2, C2
+struct RtLambdaNg {
+    int gpw, col, G;
+    __host__ __device__ constexpr RtLambdaNg(int G_, int n_depth, int gpw_) : gpw(gpw_), col(n_depth), G(G_) {}
+    __host__ __device__ constexpr int pairs() const { return 0; }
+    __host__ __device__ constexpr int thermal() const { return 2 * gpw * col; }
+    __host__ __device__ constexpr int albedo() const { return thermal() + gpw * col; }
+    __host__ __device__ constexpr int diag() const { return albedo() + gpw * col; }
+    __host__ __device__ constexpr int mean() const { return diag() + gpw * col; }
+    __host__ __device__ constexpr int history(int slot) const { return mean() + (1 + slot) * gpw * col; }
+    __host__ __device__ constexpr int terms() const { return history(kNgHistory); }
+    __host__ __device__ constexpr int wave_doubles() const { return (terms() + (kRtBatch + 1) * gpw * G + 1) & ~1; }
+    __host__ __device__ constexpr size_t bytes() const { return (size_t)wave_doubles() * sizeof(double); }
+};
+
 // k_lambda_adjoint<kSolve> (the transposed mean-intensity operator, its opacity derivative, and the adjoint scattering solve).  Per
 // wave: RtColumns' pairs [gpw][col] as double2 (the source column S the derivative is taken at, sqrt(alpha)); then eight columns
 // [gpw][col] each: z (what the transposed operator is applied to; in the solve albedo y), the result Lambda^T z, the iterate y, the
@@ -199,11 +221,13 @@ inline unsigned response_blocks(long long n_nu, int gpw)
 
 // k_lambda: waves per workgroup — as many of RtLambda's shares as 64 KB hold, at most kRtWaves — and the workgroups that cover n_nu
 // frequencies at gpw frequencies per wave (gpw from rt_fit_gpw<RtLambda>: one wave's share fits by then).
-inline int lambda_waves(int G, int n_depth, int gpw)
+template <class Layout>
+inline int lambda_waves_of(int G, int n_depth, int gpw)
 {
-    const size_t fit = kLdsBytes / RtLambda(G, n_depth, gpw).bytes();
+    const size_t fit = kLdsBytes / Layout(G, n_depth, gpw).bytes();
     return fit >= (size_t)kRtWaves ? kRtWaves : (int)fit;
 }
+inline int lambda_waves(int G, int n_depth, int gpw) { return lambda_waves_of<RtLambda>(G, n_depth, gpw); }
 inline unsigned lambda_blocks(long long n_nu, int gpw, int waves)
 {
     return (unsigned)((n_nu + (long long)gpw * waves - 1) / ((long long)gpw * waves));
@@ -266,6 +290,18 @@ constexpr bool lambda_adjoint_ok(int G, int n_depth, int gpw)
 static_assert(lambda_ok(20, 56, 3) && 4 * RtLambda(20, 56, 3).bytes() <= kLdsBytes, "RtLambda: four waves of 56 depth points at 20 angles must fit");
 static_assert(lambda_ok(1, 2, 64) && lambda_ok(1, 3, 64) && lambda_ok(3, 3, 21) && lambda_ok(7, 9, 9) && lambda_ok(20, 57, 3) && lambda_ok(64, 40, 1), "RtLambda");
 static_assert(RtLambda(20, 1352, 1).bytes() <= kLdsBytes && RtLambda(20, 1353, 1).bytes() > kLdsBytes && RtLambda(1, 1364, 1).bytes() <= kLdsBytes, "RtLambda");
+constexpr bool lambda_ng_ok(int G, int n_depth, int gpw)
+{
+    const RtLambdaNg l(G, n_depth, gpw);
+    const RtLambda p(G, n_depth, gpw);
+    return gpw * G <= 64 && l.thermal() == p.thermal() && l.albedo() == p.albedo() && l.diag() == p.diag() && l.mean() == p.mean() &&
+           l.mean() + gpw * n_depth <= l.history(0) && l.history(kNgHistory - 1) + gpw * n_depth <= l.terms() &&
+           l.terms() + kNgSums * gpw * G <= l.wave_doubles() && l.terms() + kRtBatch * gpw * G <= l.wave_doubles() && even(l.pairs()) && even(l.wave_doubles());
+}
+// the accelerated iteration: the benchmark's shape still fits four waves; the siblings' odd shapes; the deepest model at 20 angles
+static_assert(lambda_ng_ok(20, 56, 3) && 4 * RtLambdaNg(20, 56, 3).bytes() <= kLdsBytes, "RtLambdaNg: four waves of 56 depth points at 20 angles must fit");
+static_assert(lambda_ng_ok(1, 2, 64) && lambda_ng_ok(1, 3, 64) && lambda_ng_ok(3, 3, 21) && lambda_ng_ok(7, 9, 9) && lambda_ng_ok(20, 57, 3) && lambda_ng_ok(64, 40, 1), "RtLambdaNg");
+static_assert(RtLambdaNg(20, 809, 1).bytes() <= kLdsBytes && RtLambdaNg(20, 810, 1).bytes() > kLdsBytes, "RtLambdaNg");
 // the benchmark's shape fits at three points per wave; odd depth counts, both ends of the angle range; 20 angles keep three points per
 // wave up to 167 depth points
 static_assert(ew_ok(20, 56, 3) && ew_ok(1, 3, 64) && ew_ok(7, 57, 9) && ew_ok(64, 2, 1) && ew_ok(20, 167, 3) && ew_ok(20, 168, 2), "EwColumns");

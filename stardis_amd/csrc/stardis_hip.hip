@@ -2379,7 +2379,10 @@ constexpr ColumnEntry kContribution{"contribution", "no contribution function wi
                        "no emergent intensities for models this deep (the columns do not fit LDS)"},
     kResponse{"response", kResponseMixed, kResponseDeep}, kResponseAngles{"response_angles", kResponseMixed, kResponseDeep},
     kMeanIntensity{"mean_intensity", kLambdaMixed, kLambdaDeep}, kScatterSource{"scatter_source", kLambdaMixed, kLambdaDeep},
-    kMeanIntensityAdjoint{"mean_intensity_adjoint", kLambdaMixed, kAdjointDeep}, kScatterResponse{"scatter_response", kLambdaMixed, kAdjointDeep};
+    kMeanIntensityAdjoint{"mean_intensity_adjoint", kLambdaMixed, kAdjointDeep}, kScatterResponse{"scatter_response", kLambdaMixed, kAdjointDeep},
+    kScatterSourceNg{"scatter_source_ng", kLambdaMixed,
+                     "models this deep are not served with acceleration (the history columns of one frequency do not fit LDS beside the "
+                     "iteration's; sdx_scatter_source_dev, the plain iteration, serves deeper models)"};
 
 int refuse(const ColumnEntry& e, const std::string& why) { return fail(SDX_ERR_ARG, std::string(e.name) + ": " + why); }
 
@@ -2398,6 +2401,11 @@ int column_gate(const sdx_ctx* ctx, const ColumnEntry& e, int n_depth, int64_t n
 int iteration_check(const ColumnEntry& e, double tol, int max_iter)
 {
     return tol >= 0.0 && max_iter >= 1 ? SDX_OK : refuse(e, "need tol >= 0 (not NaN) and max_iter >= 1");
+}
+// the scalars of the accelerated iterations
+int acceleration_check(const ColumnEntry& e, int ng_start, int ng_period)
+{
+    return ng_start >= 4 && ng_period >= 1 ? SDX_OK : refuse(e, "need ng_start >= 4 (an extrapolation reads four iterates) and ng_period >= 1");
 }
 // a source plane (`kind`: "source", or "thermal") that is wide enough, or temperatures
 int source_or_temps(const ColumnEntry& e, const std::string& kind, const Columns& c)
@@ -2664,27 +2672,64 @@ int sdx_mean_intensity_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta,
     return check_launch("k_lambda");
 }
 
+// The scattering source iteration, plain (ng null) or with Ng acceleration: one set of refusals, one launch
+extern "C++" {
+namespace {
+struct NgOptions {
+    int start, period;
+    int* accelerations;
+};
+int scatter_source_device(sdx_ctx* ctx, const NgOptions* ng, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
+                          const double* ray_dist, const double* mean_weights, const double* alphas, int64_t ald, const double* alpha_scatter,
+                          int64_t scatter_ld, const double* thermal, int64_t thermal_ld, double tol, int max_iter, double* S, int64_t S_ld, double* J,
+                          int64_t J_ld, int* iterations, int* status, double* change)
+{
+    const ColumnEntry& e = ng ? kScatterSourceNg : kScatterSource;
+    const int gpw = ng ? column_gate<RtLambdaNg>(ctx, e, n_depth, n_nu, n_theta) : column_gate<RtLambda>(ctx, e, n_depth, n_nu, n_theta);
+    if (gpw < 0) return gpw;
+    if (int rc = iteration_check(e, tol, max_iter)) return rc;
+    if (n_nu == 0) return SDX_OK;
+    const Columns c = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, {alphas, ald}, {thermal, thermal_ld});
+    REQUIRE(columns_given(c) && alpha_scatter && S, "scatter_source: null pointer or alpha_ld below n_nu");
+    REQUIRE((scatter_ld == 0 || scatter_ld >= n_nu) && S_ld >= n_nu && fits(J, J_ld, n_nu), "scatter_source: a leading dimension below n_nu (scatter_ld: 0 or >= n_nu)");
+    if (int rc = source_or_temps(e, "thermal", c)) return rc;
+    const LambdaIteration it{alpha_scatter, scatter_ld, tol, max_iter, S, S_ld, iterations, status, change};
+    if (ng) {
+        const int waves = lambda_waves_of<RtLambdaNg>(n_theta, n_depth, gpw);
+        LaunchScope ls(ctx, "k_lambda", "k_lambda_ng");
+        hipLaunchKernelGGL(k_lambda_ng, dim3(lambda_blocks(n_nu, gpw, waves)), dim3(64 * waves), waves * RtLambdaNg(n_theta, n_depth, gpw).bytes(), ctx->stream,
+                           n_depth, n_nu, n_theta, n_theta, n_theta, nus, temps, ray_dist, mean_weights, alphas, ald, thermal, thermal_ld, J, J_ld, gpw, waves,
+                           LambdaIterationNg{it, ng->start, ng->period, ng->accelerations});
+    } else {
+        const int waves = lambda_waves(n_theta, n_depth, gpw);
+        LaunchScope ls(ctx, "k_lambda", "k_lambda<true>");
+        hipLaunchKernelGGL(k_lambda<true>, dim3(lambda_blocks(n_nu, gpw, waves)), dim3(64 * waves), waves * RtLambda(n_theta, n_depth, gpw).bytes(), ctx->stream,
+                           n_depth, n_nu, n_theta, n_theta, n_theta, nus, temps, ray_dist, mean_weights, alphas, ald, thermal, thermal_ld, J, J_ld, (double*)nullptr,
+                           (int64_t)0, gpw, waves, it);
+    }
+    return check_launch("k_lambda");
+}
+}  // namespace
+}  // extern "C++"
+
 int sdx_scatter_source_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
                            const double* mean_weights, const double* alphas, int64_t ald, const double* alpha_scatter, int64_t scatter_ld,
                            const double* thermal, int64_t thermal_ld, double tol, int max_iter, double* S, int64_t S_ld, double* J, int64_t J_ld,
                            int* iterations, int* status, double* change)
 {
-    const int gpw = column_gate<RtLambda>(ctx, kScatterSource, n_depth, n_nu, n_theta);
-    if (gpw < 0) return gpw;
-    if (int rc = iteration_check(kScatterSource, tol, max_iter)) return rc;
-    if (n_nu == 0) return SDX_OK;
-    const Columns c = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, {alphas, ald}, {thermal, thermal_ld});
-    REQUIRE(columns_given(c) && alpha_scatter && S, "scatter_source: null pointer or alpha_ld below n_nu");
-    REQUIRE((scatter_ld == 0 || scatter_ld >= n_nu) && S_ld >= n_nu && fits(J, J_ld, n_nu), "scatter_source: a leading dimension below n_nu (scatter_ld: 0 or >= n_nu)");
-    if (int rc = source_or_temps(kScatterSource, "thermal", c)) return rc;
-    const int waves = lambda_waves(n_theta, n_depth, gpw);
-    {
-        LaunchScope ls(ctx, "k_lambda", "k_lambda<true>");
-        hipLaunchKernelGGL(k_lambda<true>, dim3(lambda_blocks(n_nu, gpw, waves)), dim3(64 * waves), waves * RtLambda(n_theta, n_depth, gpw).bytes(), ctx->stream,
-                           n_depth, n_nu, n_theta, n_theta, n_theta, nus, temps, ray_dist, mean_weights, alphas, ald, thermal, thermal_ld, J, J_ld, (double*)nullptr,
-                           (int64_t)0, gpw, waves, LambdaIteration{alpha_scatter, scatter_ld, tol, max_iter, S, S_ld, iterations, status, change});
-    }
-    return check_launch("k_lambda");
+    return scatter_source_device(ctx, nullptr, n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, alphas, ald, alpha_scatter, scatter_ld, thermal,
+                                 thermal_ld, tol, max_iter, S, S_ld, J, J_ld, iterations, status, change);
+}
+
+int sdx_scatter_source_ng_dev(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                              const double* mean_weights, const double* alphas, int64_t ald, const double* alpha_scatter, int64_t scatter_ld,
+                              const double* thermal, int64_t thermal_ld, double tol, int max_iter, double* S, int64_t S_ld, double* J, int64_t J_ld,
+                              int* iterations, int* status, double* change, int ng_start, int ng_period, int* accelerations)
+{
+    if (int rc = acceleration_check(kScatterSourceNg, ng_start, ng_period)) return rc;  // (its own scalars first: they need no context)
+    const NgOptions ng{ng_start, ng_period, accelerations};
+    return scatter_source_device(ctx, &ng, n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, alphas, ald, alpha_scatter, scatter_ld, thermal,
+                                 thermal_ld, tol, max_iter, S, S_ld, J, J_ld, iterations, status, change);
 }
 
 int sdx_mean_intensity_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
@@ -2706,18 +2751,21 @@ int sdx_mean_intensity_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta,
     });
 }
 
-int sdx_scatter_source_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
-                           const double* mean_weights, const double* alphas, const double* alpha_scatter, int scatter_per_frequency,
-                           const double* thermal, double tol, int max_iter, double* S, double* J, int* iterations, int* status, double* change)
+extern "C++" {
+namespace {
+int scatter_source_host(sdx_ctx* ctx, const NgOptions* ng, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps,
+                        const double* ray_dist, const double* mean_weights, const double* alphas, const double* alpha_scatter, int scatter_per_frequency,
+                        const double* thermal, double tol, int max_iter, double* S, double* J, int* iterations, int* status, double* change)
 {
-    if (const int no = column_gate<RtLambda>(ctx, kScatterSource, n_depth, n_nu, n_theta); no < 0) return no;
-    if (int rc = iteration_check(kScatterSource, tol, max_iter)) return rc;
+    const ColumnEntry& e = ng ? kScatterSourceNg : kScatterSource;
+    if (const int no = ng ? column_gate<RtLambdaNg>(ctx, e, n_depth, n_nu, n_theta) : column_gate<RtLambda>(ctx, e, n_depth, n_nu, n_theta); no < 0) return no;
+    if (int rc = iteration_check(e, tol, max_iter)) return rc;
     if (n_nu == 0) return SDX_OK;
     const Columns h = columns(n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, {alphas, n_nu}, {thermal, n_nu});
     REQUIRE(columns_given(h, true, true) && alpha_scatter && S, "scatter_source: null pointer");
     const double* d_sc;
     double *d_s, *d_j, *d_c;
-    int *d_it, *d_st;
+    int *d_it, *d_st, *d_acc = nullptr;
     const auto rows = [&](HostPlan& plan, size_t plane, Columns& d) {
         plan.in(alpha_scatter, scatter_per_frequency ? plane : (size_t)n_depth * sizeof(double), &d_sc);
         plan.in(thermal, plane, &d.source.p);
@@ -2726,11 +2774,34 @@ int sdx_scatter_source_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta,
         plan.out(iterations, (size_t)n_nu * sizeof(int), &d_it);
         plan.out(status, (size_t)n_nu * sizeof(int), &d_st);
         plan.out(change, (size_t)n_nu * sizeof(double), &d_c);
+        if (ng) plan.out(ng->accelerations, (size_t)n_nu * sizeof(int), &d_acc);
     };
     return columns_host(ctx, h, n_theta, rows, [&](const Columns& d) {
-        return sdx_scatter_source_dev(ctx, n_depth, n_nu, n_theta, d.g.nus, d.rays.temps, d.rays.ray_dist, d.rays.wts, d.alphas.p, n_nu, d_sc,
-                                      scatter_per_frequency ? n_nu : 0, d.source.p, n_nu, tol, max_iter, d_s, n_nu, d_j, n_nu, d_it, d_st, d_c);
+        const NgOptions on_device{ng ? ng->start : 0, ng ? ng->period : 0, d_acc};
+        return scatter_source_device(ctx, ng ? &on_device : nullptr, n_depth, n_nu, n_theta, d.g.nus, d.rays.temps, d.rays.ray_dist, d.rays.wts, d.alphas.p, n_nu,
+                                     d_sc, scatter_per_frequency ? n_nu : 0, d.source.p, n_nu, tol, max_iter, d_s, n_nu, d_j, n_nu, d_it, d_st, d_c);
     });
+}
+}  // namespace
+}  // extern "C++"
+
+int sdx_scatter_source_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                           const double* mean_weights, const double* alphas, const double* alpha_scatter, int scatter_per_frequency,
+                           const double* thermal, double tol, int max_iter, double* S, double* J, int* iterations, int* status, double* change)
+{
+    return scatter_source_host(ctx, nullptr, n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, alphas, alpha_scatter, scatter_per_frequency, thermal,
+                               tol, max_iter, S, J, iterations, status, change);
+}
+
+int sdx_scatter_source_ng_f64(sdx_ctx* ctx, int n_depth, int64_t n_nu, int n_theta, const double* nus, const double* temps, const double* ray_dist,
+                              const double* mean_weights, const double* alphas, const double* alpha_scatter, int scatter_per_frequency,
+                              const double* thermal, double tol, int max_iter, double* S, double* J, int* iterations, int* status, double* change,
+                              int ng_start, int ng_period, int* accelerations)
+{
+    if (int rc = acceleration_check(kScatterSourceNg, ng_start, ng_period)) return rc;  // (its own scalars first: they need no context)
+    const NgOptions ng{ng_start, ng_period, accelerations};
+    return scatter_source_host(ctx, &ng, n_depth, n_nu, n_theta, nus, temps, ray_dist, mean_weights, alphas, alpha_scatter, scatter_per_frequency, thermal,
+                               tol, max_iter, S, J, iterations, status, change);
 }
 
 // ---- the adjoint of the mean intensity and of the scattering solve (k_lambda_adjoint) ---------------------------------------

@@ -93,7 +93,9 @@ class SpectralSynthesizer:
         and pass it with every step: what the pre-pass launch forms from them alone is then formed once, here.  The same bits; dense
         line lists only (a line list of scalars and the two-collective mode step without one).  refresh_grid_plan() after changing the
         uploaded values in place; False: no plan.
-        scattering: True, or dict(tol=1e-12, max_iter=2000).  After the synthesis every step also solves S = (1 - albedo) B + albedo J[S]
+        scattering: True, or dict(tol=1e-12, max_iter=2000, acceleration=None); acceleration="ng" or dict(start=4, period=4) solves
+        with Ng acceleration (sdx_scatter_source_ng_dev, same buffers, `scattering_accelerations` beside them; the adjoint solve of
+        keep_response stays the plain one — it has no accelerated kernel).  After the synthesis every step also solves S = (1 - albedo) B + albedo J[S]
         on its own columns (sdx_scatter_source_dev on the step's total_alphas; implies keep_total) with Thomson scattering — albedo =
         alpha_electron / total_alphas, the per-depth vector of sdx_alpha_electron_dev formed once here: the bits of the electron term in
         the total — and traces that source function (sdx_raytrace_source_dev) into a flux buffer of its own: `scattering_source`,
@@ -180,8 +182,10 @@ class SpectralSynthesizer:
             keep_total = True
         self.scattering = self._scattering_options(scattering, continuum)
         if self.scattering is not None:
-            c.call("sdx_scatter_source_dev", self.n_depth, 0, self.n_theta, None, None, None, None, None, 0, None, 0, None, 0,
-                   self.scattering["tol"], self.scattering["max_iter"], None, 0, None, 0, None, None, None)
+            ng = self.scattering.get("acceleration")
+            c.call("sdx_scatter_source_dev" if ng is None else "sdx_scatter_source_ng_dev", self.n_depth, 0, self.n_theta, None, None, None, None, None, 0,
+                   None, 0, None, 0, self.scattering["tol"], self.scattering["max_iter"], None, 0, None, 0, None, None, None,
+                   *(() if ng is None else (ng["start"], ng["period"], None)))
             keep_total = True
         self._scattering_response = self.scattering is not None and self.keep_response
         if self._scattering_response:
@@ -210,6 +214,8 @@ class SpectralSynthesizer:
             self.d_Ssc, self.d_Jsc, self.d_Fsc = c.empty(plane), c.empty(plane), c.empty(plane)
             self.d_sc_iterations, self.d_sc_status = c.empty((self.count,), np.int32), c.empty((self.count,), np.int32)
             self.d_sc_change = c.empty((self.count,))
+            if self.scattering.get("acceleration") is not None:
+                self.d_sc_accelerations = c.empty((self.count,), np.int32)
             if self._scattering_response:
                 # the flux's direct part and cotangent at source = S, then the three response planes of the adjoint solve
                 self.d_sc_direct, self.d_sc_cotangent = c.empty(plane), c.empty(plane)
@@ -256,16 +262,21 @@ class SpectralSynthesizer:
 
     @staticmethod
     def _scattering_options(scattering, continuum):
-        """None (off), or dict(tol, max_iter) checked on the host"""
+        """None (off), or dict(tol, max_iter, acceleration) checked on the host; acceleration: None or dict(start, period)"""
         if scattering is None or scattering is False:
             return None
-        opts = dict(tol=1e-12, max_iter=2000)
+        opts = dict(tol=1e-12, max_iter=2000, acceleration=None)
         if scattering is not True:
             unknown = set(scattering) - set(opts)
             if unknown:
-                raise ValueError(f"scattering: unknown option(s) {sorted(unknown)} (tol, max_iter)")
+                raise ValueError(f"scattering: unknown option(s) {sorted(unknown)} (tol, max_iter, acceleration)")
             opts.update(scattering)
+        from . import ops
+
+        ng = ops.acceleration_options("scattering", opts["acceleration"])
         opts = dict(tol=float(opts["tol"]), max_iter=int(opts["max_iter"]))
+        if ng is not None:
+            opts["acceleration"] = ng  # (without the key the options are what they were: dict(tol, max_iter))
         if not opts["tol"] >= 0.0 or opts["max_iter"] < 1:
             raise ValueError("scattering: need tol >= 0 and max_iter >= 1")
         if continuum is None:
@@ -432,8 +443,13 @@ class SpectralSynthesizer:
     def _enqueue_scattering(self):
         """the scattering source function of the step's columns from its total_alphas, then the flux of that source function"""
         c, cnt, flux, mean = self.ctx, self.count, self._columns(self.d_w), self._columns(self.d_mean_w)
-        c.call("sdx_scatter_source_dev", *mean, self.d_thomson.ptr, 0, None, 0, self.scattering["tol"], self.scattering["max_iter"], self.d_Ssc.ptr, cnt,
-               self.d_Jsc.ptr, cnt, self.d_sc_iterations.ptr, self.d_sc_status.ptr, self.d_sc_change.ptr)
+        ng = self.scattering.get("acceleration")
+        solve = (*mean, self.d_thomson.ptr, 0, None, 0, self.scattering["tol"], self.scattering["max_iter"], self.d_Ssc.ptr, cnt,
+                 self.d_Jsc.ptr, cnt, self.d_sc_iterations.ptr, self.d_sc_status.ptr, self.d_sc_change.ptr)
+        if ng is None:
+            c.call("sdx_scatter_source_dev", *solve)
+        else:
+            c.call("sdx_scatter_source_ng_dev", *solve, ng["start"], ng["period"], self.d_sc_accelerations.ptr)
         c.call("sdx_raytrace_source_dev", *flux, self.d_Ssc.ptr, cnt, self.d_Fsc.ptr, cnt, None, 0, 0, 1.0)
         if self._scattering_response:
             # the derivative of that flux: the response functions at source = S are its direct part and cotangent, the adjoint solve the rest
@@ -808,6 +824,14 @@ class SpectralSynthesizer:
         """-> (count,) int32 numpy array: 0 converged, 1 max_iter reached, 2 the change was not finite (include/stardis_hip.h)."""
         self._require_scattering()
         return self.d_sc_status.numpy()
+
+    @property
+    def scattering_accelerations(self):
+        """-> (count,) int32 numpy array: the Ng extrapolations every column of the last step took (scattering=dict(acceleration="ng"))."""
+        self._require_scattering()
+        if self.scattering.get("acceleration") is None:
+            raise RuntimeError('the scattering solve is not accelerated: construct the synthesizer with scattering=dict(acceleration="ng")')
+        return self.d_sc_accelerations.numpy()
 
     def _require_scattering_response(self):
         if self.scattering is None or not self.keep_response:

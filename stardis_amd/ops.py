@@ -649,6 +649,32 @@ def _scatter_inputs(what, alpha_scatter, shape, tol, max_iter):
     return sc, shape[1] if len(_shape(sc)) == 2 else 0
 
 
+NG_DEFAULTS = dict(start=4, period=4)
+
+
+def acceleration_options(what, acceleration):
+    """acceleration: None (the plain iteration), "ng", or a dict with start and / or period -> None or dict(start, period); raises
+    ValueError on anything else.  Host code alone: no device is asked for."""
+    if acceleration is None:
+        return None
+    if isinstance(acceleration, str):
+        if acceleration != "ng":
+            raise ValueError(f'{what}: acceleration must be None, "ng" or a dict(start=, period=), got {acceleration!r}')
+        return dict(NG_DEFAULTS)
+    if not isinstance(acceleration, dict):
+        raise ValueError(f'{what}: acceleration must be None, "ng" or a dict(start=, period=), got {acceleration!r}')
+    unknown = sorted(set(acceleration) - set(NG_DEFAULTS))
+    if unknown:
+        raise ValueError(f"{what}: unknown acceleration option {unknown}; known: {sorted(NG_DEFAULTS)}")
+    o = dict(NG_DEFAULTS)
+    o.update({k: int(v) for k, v in acceleration.items()})
+    if o["start"] < 4:
+        raise ValueError(f"{what}: acceleration start must be >= 4 (an extrapolation reads four iterates), got {o['start']}")
+    if o["period"] < 1:
+        raise ValueError(f"{what}: acceleration period must be >= 1, got {o['period']}")
+    return o
+
+
 def _results(out, device):
     """a tuple or a namespace of device outputs as it is, or with every one of them on the host (None stays None)"""
     if device:
@@ -757,24 +783,33 @@ def mean_intensity(tracing_nus, temperatures, ray_distances, mean_weights, total
 
 
 def scatter_source(tracing_nus, temperatures, ray_distances, mean_weights, total_alphas, alpha_scatter, ctx=None, thermal=None,
-                   tol=1e-12, max_iter=2000, device=False, want_J=True):
+                   tol=1e-12, max_iter=2000, device=False, want_J=True, acceleration=None):
     """Source function with coherent continuum scattering (sdx_scatter_source_dev): S = (1 - albedo) B + albedo J[S], albedo =
     alpha_scatter / total_alphas, by Jacobi iteration with the local operator, every column on its own until it meets
     max |dS| <= tol max |S| (status 0), has taken max_iter iterations (1) or its change is not finite (2).
     alpha_scatter: (N_d,) — one value per depth point, e.g. Thomson — or (N_d, N_nu), host or device; thermal: optional plane B
     (default: Planck).  -> namespace(S, J, iterations, status, change): S and J (N_d, N_nu) (J of the returned S; None with
-    want_J=False), per column the iteration count and status (int32) and the last change.  device=True: DeviceArrays."""
+    want_J=False), per column the iteration count and status (int32) and the last change.  device=True: DeviceArrays.
+    acceleration: None — the plain iteration, the call above —, "ng" or dict(start=4, period=4): Ng acceleration with its safeguard
+    (sdx_scatter_source_ng_dev); the namespace then also holds `accelerations`, the extrapolations applied per column (int32).  The
+    same fixed point by the same stopping rule in fewer updates where the albedo is high; not the same bits."""
     import types
 
     p = _column_inputs(tracing_nus, temperatures, ray_distances, total_alphas, weights=mean_weights, what="scatter_source", planes=dict(thermal=thermal))
     sc, sc_ld = _scatter_inputs("scatter_source", alpha_scatter, p.shape, tol, max_iter)
+    ng = acceleration_options("scatter_source", acceleration)
     ctx = ctx or default_context()
     head, d_alpha, (d_sc, d_B) = _column_uploads(ctx, p, total_alphas, sc, p.planes["thermal"])
     n_nu = p.nus.size
     out = types.SimpleNamespace(S=ctx.empty(p.shape), J=ctx.empty(p.shape) if want_J else None, iterations=ctx.empty((n_nu,), np.int32),
                                 status=ctx.empty((n_nu,), np.int32), change=ctx.empty((n_nu,)))
-    ctx.call("sdx_scatter_source_dev", *head, ptr_of(d_alpha), n_nu, ptr_of(d_sc), sc_ld, ptr_of(d_B), n_nu, float(tol), int(max_iter), out.S.ptr, n_nu,
-             ptr_of(out.J), n_nu, out.iterations.ptr, out.status.ptr, out.change.ptr)
+    args = (*head, ptr_of(d_alpha), n_nu, ptr_of(d_sc), sc_ld, ptr_of(d_B), n_nu, float(tol), int(max_iter), out.S.ptr, n_nu,
+            ptr_of(out.J), n_nu, out.iterations.ptr, out.status.ptr, out.change.ptr)
+    if ng is None:
+        ctx.call("sdx_scatter_source_dev", *args)
+    else:
+        out.accelerations = ctx.empty((n_nu,), np.int32)
+        ctx.call("sdx_scatter_source_ng_dev", *args, ng["start"], ng["period"], out.accelerations.ptr)
     return _results(out, device)
 
 

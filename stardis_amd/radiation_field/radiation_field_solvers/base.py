@@ -256,33 +256,41 @@ def _scatter_plane(field, shape):
     return scatter
 
 
-def scattering_source(stellar_model, stellar_radiation_field, tol=1e-12, max_iter=2000):
+def scattering_source(stellar_model, stellar_radiation_field, tol=1e-12, max_iter=2000, acceleration=None):
     """Source function with coherent continuum scattering, S = (1 - albedo) B + albedo J[S] (sdx_scatter_source_dev) -> namespace(S, J,
     iterations, status, change) as ops.scatter_source returns it.  The scattering opacity is the field's own Rayleigh + Thomson entries
     (opacities_dict["alpha_rayleigh"] + ["alpha_electron"], which the total holds as absorption); B is the field's source function.
     S feeds raytrace(), contribution_function() and response_functions() as a source plane: a field whose source_function returns it
-    is traced with scattering.  The reference has no counterpart.  A spherical model raises NotImplementedError."""
+    is traced with scattering.  acceleration: None, "ng" or dict(start=, period=) as ops.scatter_source takes it (Ng acceleration,
+    sdx_scatter_source_ng_dev; the namespace then holds `accelerations`).  The reference has no counterpart.  A spherical model raises
+    NotImplementedError."""
+    ops.acceleration_options("scattering_source", acceleration)
     field = stellar_radiation_field
     args, ctx = _lambda_arguments(stellar_model, field)
     scatter = _scatter_plane(field, (np.size(args[1]), np.size(plain(field.frequencies))))
-    return ops.scatter_source(*args, scatter, ctx=ctx, tol=tol, max_iter=max_iter,
+    return ops.scatter_source(*args, scatter, ctx=ctx, tol=tol, max_iter=max_iter, acceleration=acceleration,
                               thermal=_source_plane(getattr(field, "source_function", None), field.frequencies, stellar_model.temperatures))
 
 
-def scattering_response(stellar_model, stellar_radiation_field, tol=1e-12, max_iter=2000):
+def scattering_response(stellar_model, stellar_radiation_field, tol=1e-12, max_iter=2000, acceleration=None):
     """Response functions of the emergent flux WITH continuum scattering (sdx_scatter_response_dev): solves for the scattering source
     function S as scattering_source() does, takes the flux's cotangent and direct part from the response functions at source = S, and
     solves the adjoint problem -> namespace(y, R_thermal, R_absorption, R_scatter, iterations, status, change) as ops.scatter_response
     returns it, with S and the forward solve's own `source_iterations` and `source_status` beside them.  R_absorption takes the place
-    of response_functions()'s R_alpha once scattering is on.  A spherical model raises NotImplementedError."""
+    of response_functions()'s R_alpha once scattering is on.  acceleration (as scattering_source takes it) accelerates the FORWARD solve
+    alone — the adjoint solve has no accelerated kernel ("The scattering adjoint") —; `source_accelerations` then stands beside
+    `source_iterations`.  A spherical model raises NotImplementedError."""
+    ops.acceleration_options("scattering_response", acceleration)
     field = stellar_radiation_field
     args, ctx = _lambda_arguments(stellar_model, field)
     scatter = _scatter_plane(field, (np.size(args[1]), np.size(plain(field.frequencies))))
     thermal = _source_plane(getattr(field, "source_function", None), field.frequencies, stellar_model.temperatures)
-    forward = ops.scatter_source(*args, scatter, ctx=ctx, tol=tol, max_iter=max_iter, thermal=thermal, want_J=False)
+    forward = ops.scatter_source(*args, scatter, ctx=ctx, tol=tol, max_iter=max_iter, thermal=thermal, want_J=False, acceleration=acceleration)
     R_alpha, R_source = ops.response(args[0], args[1], args[2], field.I_nus_weights, args[4], ctx=ctx, source=forward.S)
     out = ops.scatter_response(*args, scatter, forward.S, R_source, ctx=ctx, direct=R_alpha, thermal=thermal, tol=tol, max_iter=max_iter)
     out.S, out.source_iterations, out.source_status = forward.S, forward.iterations, forward.status
+    if acceleration is not None:
+        out.source_accelerations = forward.accelerations
     return out
 
 
